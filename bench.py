@@ -36,10 +36,6 @@ import time
 
 import numpy as np
 
-# the hull pass of the `hpr` leg keeps keyframes in flight on several streams; the HIP runtime reads this when it initialises
-# (before `import torch` touches the device): 8 hardware queues instead of 4 (pcp_create sets the same default for C++ hosts)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
@@ -55,6 +51,8 @@ MLS_PMC_SUMMARY = "r05_mls_pmc.json"  # MLS alone (profiles/collect_mls.sh)
 CHAIN_PMC_SUMMARY = "r05_chain_pmc.json"  # the enableMLS chain SOR -> MLS -> SOR (profiles/collect_chain.sh)
 SIMDS, CLOCK_GHZ = 1024, 2.4  # 256 CUs x 4 SIMDs; MI355X_MICROARCH.md max clock
 C3_POINTS, C3_FRAMES = 50_000_000, 1024  # BASELINE.json configs[3]
+# --dump-outputs: 24 B per point written (index f64, rgb 3 x f32, has f32), so 2 M points stay under 64 MB in all
+DUMP_MAX_POINTS, DUMP_SEED = 2_000_000, 20240611
 
 
 _LIB_SHA = [None]
@@ -93,6 +91,25 @@ def read_summary(name):
     stale = not (have == lib_sha256() or same_sources)
     SUMMARY_STATE[name] = {"stale": stale, "collected_on": have, "same_library_bytes": have == lib_sha256(), "same_sources": bool(same_sources)}
     return {} if stale else d
+
+
+def dump_outputs(out_dir, packed, rank, world):
+    """The colours of the last timed step as a caller of the timed path receives them (PointCloudColorizer.run: rgb (n, 3)
+    and has (n,), unpacked from the packed words the step downloads), for a fixed seeded sample of this rank's points:
+    index = the sampled points' positions in the rank's cloud.  The inputs are seeded, so two builds run with the same
+    arguments can be compared file for file.  N > 1: every rank writes its own files (suffix _rank<r>) of a sample of
+    DUMP_MAX_POINTS / N points."""
+    n = len(packed)
+    cap = DUMP_MAX_POINTS // world
+    idx = np.arange(n) if n <= cap else np.sort(np.random.default_rng(DUMP_SEED).choice(n, cap, replace=False))
+    words = packed[idx]
+    arrays = {"index": idx.astype(np.float64),
+              "rgb": np.stack([(words >> s) & 255 for s in (0, 8, 16)], axis=1).astype(np.float32),
+              "has": (words >> 24).astype(np.float32)}
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if world == 1 else f"_rank{rank}"
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
 
 
 def cli_e2e_leg(synth, n_points=1_000_000, n_frames=32, W=1920, H=1080):
@@ -173,8 +190,11 @@ def cli_e2e_leg(synth, n_points=1_000_000, n_frames=32, W=1920, H=1080):
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=0, help="0: 100 at N = 1, 20 at N > 1")
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 100 at N = 1, 20 at N > 1)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the colours of the last timed step (a fixed sample of at most "
+                         f"{DUMP_MAX_POINTS} points: index, rgb, has) as DIR/<name>.npy, float64 / float32")
     ap.add_argument("--settle-ms", type=float, default=400.0,
                     help="untimed whole steps before the warm-up until this much time has passed (clock / power state of a fresh box)")
     ap.add_argument("--points", type=int, default=0, help="points per GPU (0: 10 M at N = 1, 50 M / N at N > 1)")
@@ -207,7 +227,10 @@ def parse():
                          "colours are compared with a one-GPU run of the whole map on rank 0 (first multi-GPU lease)")
     ap.add_argument("--match-mode", default="roundtrip", choices=["roundtrip", "identity"],
                     help="pcp_cull_params.match_mode (default: the reference's fp32 round-trip arithmetic)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def upload_keyframes(eng, dist, torch, synth, cam, F, rank, world, device):
@@ -285,7 +308,7 @@ def main():
     sharded = world > 1
     F = args.frames or (C3_FRAMES if sharded else 256)
     N = args.points or (C3_POINTS // world if sharded else 10_000_000)
-    steps = args.steps or (20 if sharded else 100)
+    steps = args.steps if args.steps is not None else (20 if sharded else 100)
     cam = synth.camera_dict(args.camera)
     W, H = cam["image_width"], cam["image_height"]
     if sharded:
@@ -401,6 +424,8 @@ def main():
     # of the cpu_baseline leg compares exactly these with the oracle's
     step_colours = pinned[(step_no[0] - 1) & 1].numpy().view(np.uint32).copy()
     coloured = int(((step_colours >> 24) & 1).sum())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, step_colours, rank, world)
     verify = None
     if args.verify and sharded:
         # the shards' colours, all-gathered, against the whole map coloured by ONE context on rank 0
@@ -769,7 +794,7 @@ def main():
                        "Mpoints_frames_per_s": round(N * F / t_hull / 1e6, 1), "cull_frame": per_kf,
                        "hull_pass_runs_s": [round(v, 4) for v in runs_hull],
                        "keyframes_in_flight": int(os.environ.get("PCP_HPR_LANES", "4")),
-                       "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
+                       "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),  # the machine's setting; None: the runtime's default
                        "value_hpr": round(N * F / t_hcol / 1e6, 1), "value_hpr_unit": "Mpoints*frames/s",
                        "colourise_s": round(t_hcol, 3), "coloured_points": int(hres["has"].sum()),
                        "what": "spherical flip + convex-hull vertex test of every keyframe's candidates on the GPU "

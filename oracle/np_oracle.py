@@ -6,7 +6,7 @@ restatements check each other; it also generates the committed golden vectors
 (tests/golden/make_golden.py).  numpy fp32 / fp64 array ops are individually
 rounded (no FMA contraction), which is the arithmetic model of Appendix A.
 
-PCP/ = /root/reference/PointCloudProcessor/.
+PCP/ = the reference project's PointCloudProcessor/.
 """
 from __future__ import annotations
 

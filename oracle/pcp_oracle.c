@@ -3,7 +3,7 @@
  * top-5 mean).  See pcp_oracle.h: TEST INFRASTRUCTURE ONLY, PARITY UNPINNED.
  *
  * Every function cites the reference lines it restates.  PCP/ =
- * /root/reference/PointCloudProcessor/.  Build: oracle/Makefile
+ * the reference project's PointCloudProcessor/.  Build: oracle/Makefile
  * (-O2 -ffp-contract=off -fno-fast-math).
  */
 #include "pcp_oracle.h"

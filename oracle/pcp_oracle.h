@@ -14,7 +14,7 @@
  * and (iii) analytic known-answer tests.  Statements about upstream PCL /
  * Eigen internals are marked [upstream].
  *
- * Shorthand: PCP/ = /root/reference/PointCloudProcessor/.
+ * Shorthand: PCP/ = the reference project's PointCloudProcessor/.
  * All fp32 / fp64 operations are individually rounded: build with
  * -ffp-contract=off (see oracle/Makefile).
  */

@@ -7,7 +7,7 @@
  * The reference flips every candidate about a sphere of radius 90000 (:291-292,
  * view_culling.hpp:14), appends the origin (:297) and asks qhull ("qhull ", defaults) for the
  * convex hull; visible = the hull's vertices other than the origin (:316-329).  qhull is a
- * third-party library that is not under /root/reference (cloned at HEAD by the reference's
+ * third-party library that is not part of the reference (cloned at HEAD by the reference's
  * Dockerfile:21-27, unpinned) and not in this image as a C library, so the hull is restated
  * here from its definition: a candidate is visible iff its flipped point is an EXTREME POINT
  * of conv(flipped points + origin).  qhull computes the same set up to its round-off

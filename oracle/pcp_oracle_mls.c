@@ -7,7 +7,7 @@
  *
  * The reference only configures and calls PCL (PCP/src/cloudSmooth.cpp:109-164,
  * parameters PCP/src/PointCloudProcessor.cpp:67-86); the arithmetic lives in
- * PCL 1.10.0 (libpcl from osrf/ros:noetic, /root/reference/Dockerfile:2), which
+ * PCL 1.10.0 (libpcl from osrf/ros:noetic, the reference's Dockerfile:2), which
  * is not vendored.  Everything below restates PCL's published algorithm
  * (surface/include/pcl/surface/impl/mls.hpp, common/impl/centroid.hpp,
  * common/impl/eigen.hpp, filters/impl/statistical_outlier_removal.hpp,

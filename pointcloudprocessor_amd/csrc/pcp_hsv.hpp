@@ -1,7 +1,7 @@
 // pcp_hsv.hpp -- the 8-bit BGR -> HSV -> BGR round trip generateColorMap applies to every keyframe
-// (PointCloudProcessor.cpp:722-741), as OpenCV 4.2.0 (the version osrf/ros:noetic ships, /root/reference/
+// (PointCloudProcessor.cpp:722-741), as OpenCV 4.2.0 (the version osrf/ros:noetic ships, the reference's
 // Dockerfile:2) computes it for CV_8UC3: imgproc/src/color_hsv.simd.hpp RGB2HSV_b / HSV2RGB_b [upstream: OpenCV is
-// not under /root/reference; restated from its published source].
+// not part of the reference; restated from its published source].
 //
 // Forward (exact, integer): v = max, diff = max - min, s = (diff * sdiv[v] + 2^11) >> 12,
 //   h = (sector term) * hdiv180[diff], rounded the same way, + 180 when negative;

@@ -2,7 +2,6 @@
 """The whole-run hull pass of C3 repeated for ~6 s: does its time drift with the clock the device holds under a sustained load?"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 from pointcloudprocessor_amd import capi, synth
 cam = synth.camera_dict("cfg")
 x, y, z, _ = synth.make_cloud(10_000_000)

@@ -4,16 +4,17 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
 
-def test_bench_line_carries_the_contract():
+def test_bench_line_carries_the_contract(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--points", "300000", "--frames", "16", "--steps", "3", "--warmup", "1",
            "--roofline-points", "4000000", "--roofline-launches", "8", "--mls-points", "300000", "--cpu-points", "100000",
-           "--cpu-frames", "4"]
+           "--cpu-frames", "4", "--dump-outputs", str(tmp_path / "dump")]
     proc = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
     assert proc.returncode == 0, proc.stderr[-2000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.strip()]
@@ -68,3 +69,7 @@ def test_bench_line_carries_the_contract():
     if prof["summaries"].get("r05_pmc.json", {}).get("stale", True):
         assert line["roofline"]["traffic"] is None and line["roofline"]["traffic_stale"] is True
     assert ("kernels_ms" in line) != ("kernels_ms_timing_pass" in line)
+    # --dump-outputs: the last timed step's colours of every point (300 k is below the sample size)
+    dump = {k: np.load(tmp_path / "dump" / f"{k}.npy") for k in ("index", "rgb", "has")}
+    assert np.array_equal(dump["index"], np.arange(300000)) and dump["rgb"].shape == (300000, 3)
+    assert int((dump["has"] > 0).sum()) == line["coloured_points_rank0"] > 0
