@@ -40,7 +40,9 @@ extern "C" {
                                 multi-GPU host exchanges them with RCCL instead of through the host)
                              6: entry points added: pcp_cloud_smooth_stream_begin / _next / _end / _stats (the whole enableMLS chain
                                 with its trailing outlier removal over a chunked voxel dilation); pcp_hpr_stats reports
-                                candidates = -1 after a call served from the whole-run bits */
+                                candidates = -1 after a call served from the whole-run bits;
+                                entry points added, no layout changed: pcp_colour_smooth_local / _packed (PCP_K_COLOUR_SMOOTH = 12,
+                                PCP_K_COUNT 13) */
 
 #define PCP_OK 0
 #define PCP_ERR_INVALID (-1) /* bad argument */
@@ -130,7 +132,8 @@ enum {
   PCP_K_TILE_MASK = 9,  /* tile x keyframe visibility masks (conservative culling) */
   PCP_K_NID = 10,       /* NID joint histograms (value + SE(3) tangent gradient) */
   PCP_K_HPR = 11,       /* hidden_points_removal: flip, binning, per-candidate hull membership */
-  PCP_K_COUNT = 12
+  PCP_K_COLOUR_SMOOTH = 12, /* smoothColorsWithLocalRegion: records, work items, radius-weighted colour means */
+  PCP_K_COUNT = 13
 };
 
 /* ---- lifecycle ---------------------------------------------------------- */
@@ -288,6 +291,25 @@ int pcp_download_wait_previous(pcp_context *ctx);
 /* device address of the packed per-point result (r | g<<8 | b<<16 | has<<24),
  * valid after pcp_colour_finalise / pcp_colorize, for device-side gathers */
 int pcp_colour_result_device(pcp_context *ctx, void **device_ptr, int64_t *n_words);
+
+/* PointCloudProcessor::smoothColorsWithLocalRegion(rgbCloud, radius), PointCloudProcessor.cpp:634-703, whose call
+ * smoothColorsWithLocalRegion(rgbCloud, 0.1) is commented out at :597 between smoothColors (:596) and
+ * removePointsWithNoColor (:598): an opt-in post-pass over the finished colours.  Every finite point
+ * takes floor(sum w_j c_j / sum w_j) per channel over the finite points j with fl32 squared distance <= radius^2 (itself
+ * included), w_j = fl32(1 / (1 + d2)); the sums are exact (integer weights w_j * 2^24), so the result is bit-reproducible.
+ * Every output reads the unsmoothed colours; has = (r | g | b) != 0 afterwards; non-finite points keep their word.
+ * radius must be finite with 0 < radius <= 1 (else PCP_ERR_INVALID).  *out_has_count (nullable) = points with has set.
+ * The pass builds the smoothing stages' grid: an open pcp_mls_stream_* / pcp_cloud_smooth_stream_* / pcp_sor_partial
+ * state of the context ends (as with any call that builds it).
+ * In place on the context's colour result (valid after pcp_colour_finalise / pcp_colorize / pcp_colorize_from_depth, else
+ * PCP_ERR_STATE); later pcp_download_result_packed[_async] / pcp_colour_result_device return the smoothed words.  The
+ * top-5 lists of pcp_colour_finalise are not touched.  The result moves to the other half of the double buffer: an
+ * asynchronous download still in flight keeps reading the unsmoothed words. */
+int pcp_colour_smooth_local(pcp_context *ctx, float radius, int64_t *out_has_count);
+/* The same over caller-supplied packed words r | g<<8 | b<<16 | has<<24 (n = pcp_cloud_size; the has bit of the input is
+ * not read), host memory or device memory of the context's GPU; in == out allowed.  Synchronous. */
+int pcp_colour_smooth_local_packed(pcp_context *ctx, float radius, const uint32_t *in_rgba, uint32_t *out_rgba,
+                                   int64_t *out_has_count);
 
 /* ---- MLS (CloudSmooth::process, PCP/src/cloudSmooth.cpp:77-185) ---------- */
 /* pcl::MovingLeastSquares on the uploaded cloud (radius search + order-2 fit +

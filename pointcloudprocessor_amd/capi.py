@@ -25,7 +25,8 @@ PCP_ERR_RANGE = -5
 NID_EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                           C.POINTER(C.c_int32))
 K_PROJECT, K_DEPTH, K_COLOUR, K_VISIBILITY, K_MLS_GRID, K_MLS_FIT, K_MISC, K_SOR, K_MLS_VOXEL, K_TILE_MASK, K_NID, K_HPR = range(12)
-K_COUNT = 12
+K_COLOUR_SMOOTH = 12
+K_COUNT = 13
 
 
 class PcpError(RuntimeError):
@@ -422,6 +423,24 @@ class Context:
         n = C.c_int64()
         self._check(self.lib.pcp_colour_result_device(self.h, C.byref(p), C.byref(n)))
         return p.value, n.value
+
+    def colour_smooth_local(self, radius: float) -> int:
+        """smoothColorsWithLocalRegion (PointCloudProcessor.cpp:634-703) in place on the colour result; returns the number
+        of points with a colour afterwards.  The downloads then return the smoothed words."""
+        cnt = C.c_int64()
+        self._check(self.lib.pcp_colour_smooth_local(self.h, C.c_float(radius), C.byref(cnt)))
+        return cnt.value
+
+    def colour_smooth_local_packed(self, radius: float, rgba) -> tuple[np.ndarray, int]:
+        """The same over caller-supplied packed words (n uint32 r | g<<8 | b<<16 | has<<24, input order):
+        (smoothed words, points with a colour)."""
+        words = np.ascontiguousarray(rgba, np.uint32)
+        if words.shape != (self.n,):
+            raise ValueError(f"colour_smooth_local_packed: {self.n} words expected, got shape {words.shape}")
+        out = np.empty(self.n, np.uint32)
+        cnt = C.c_int64()
+        self._check(self.lib.pcp_colour_smooth_local_packed(self.h, C.c_float(radius), _ptr(words), _ptr(out), C.byref(cnt)))
+        return out, cnt.value
 
     # -- MLS --------------------------------------------------------------
     def mls_process(self, params: MLSParams) -> int:

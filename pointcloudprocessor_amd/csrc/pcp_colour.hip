@@ -2036,6 +2036,27 @@ static int result_in_input_order(pcp_context *ctx) {
   return PCP_OK;
 }
 
+int pcp_colour_smooth_local(pcp_context *ctx, float radius, int64_t *out_has_count) {
+  if (!ctx) return PCP_ERR_INVALID;
+  if (!smooth_radius_ok(radius))
+    return set_error(ctx, PCP_ERR_INVALID, "pcp_colour_smooth_local: radius %g outside (0, 1]", static_cast<double>(radius));
+  if (!ctx->colour_result_live)
+    return set_error(ctx, PCP_ERR_STATE, "pcp_colour_smooth_local: no result (call pcp_colorize / pcp_colour_finalise)");
+  if (out_has_count) *out_has_count = 0;
+  if (ctx->n == 0) return PCP_OK;
+  PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // the unsmoothed words in input order are read from the current buffer, the smoothed ones go to the other half of the
+  // double buffer (begin_result waits for a download that may still read it), which then becomes the result
+  int rc = result_in_input_order(ctx);
+  if (rc != PCP_OK) return rc;
+  const uint32_t *src = ctx->rgba2[ctx->rgba_cur].p;
+  uint32_t *dst = nullptr;
+  if ((rc = begin_result(ctx, &dst)) != PCP_OK) return rc;
+  if ((rc = colour_smooth_words(ctx, radius, src, dst, out_has_count)) != PCP_OK) return rc;
+  ctx->last_pass_sorted = false;
+  return end_result(ctx, nullptr, nullptr);
+}
+
 int pcp_download_result_packed(pcp_context *ctx, uint32_t *out_rgba) {
   if (!ctx) return PCP_ERR_INVALID;
   if (!ctx->colour_result_live)

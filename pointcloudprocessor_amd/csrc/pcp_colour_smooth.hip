@@ -1,0 +1,330 @@
+// pcp_colour_smooth.hip -- PointCloudProcessor::smoothColorsWithLocalRegion (PCP/src/PointCloudProcessor.cpp:634-703; its
+// call, smoothColorsWithLocalRegion(rgbCloud, 0.1), is commented out at :597) on gfx950, as an opt-in post-pass over the
+// packed colour words of the whole map.  The rules are DESIGN.md LS1-LS7:
+//   - the finite points are both the queries and the candidates (LS1); non-finite points keep their word;
+//   - j is a neighbour of i iff fl32 d2 = ((dx*dx + dy*dy) + dz*dz) <= t, t = the largest float with (double)t <= (double)r^2
+//     -- the same decision as (double)d2 <= (double)r * (double)r (LS2);
+//   - w = fl32(1 / fl32(1 + d2)) (LS3), an IEEE quotient (-fhip-fp32-correctly-rounded-divide-sqrt);
+//   - out_c = floor(sum m_j c_j / sum m_j) with m_j = w_j * 2^24, an integer (w_j in [0.5, 1] for r <= 1): both sums are
+//     exact 64-bit integer sums, so the result does not depend on the order of the neighbours (LS4);
+//   - every output reads the unsmoothed words (LS5); has = (r | g | b) != 0 afterwards (LS6).
+//
+// Search: the finite points are binned into the uniform grid of the MLS / SOR stages (pcp_mls.hip build_grid; cell >= r,
+// reach 1) and copied into cell order as 16-B records (x, y, z, word).  One wavefront-sized workgroup takes up to 64
+// queries of ONE cell (one query per lane); their candidates are the 9 rows of 3 neighbouring cells, each a contiguous run
+// of records, staged through LDS in tiles of kLsTile records and read back as wave-wide broadcasts.  A cell of any size is
+// walked tile by tile (an all-duplicate cloud is one cell).  Results are stored in the caller's order.
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+
+#include "pcp_internal.hpp"
+
+namespace pcp {
+
+constexpr int kLsBlock = 256;   // the 1-D helper kernels
+constexpr int kLsQ = 64;        // queries per work item: one wavefront, one cell
+constexpr int kLsTile = 512;    // candidate records per LDS tile (8 KiB: ~20 one-wave workgroups per CU hide the LDS latency)
+constexpr int kLsMaxRows = 25;  // (2 reach + 1)^2 rows of neighbouring cells, reach <= 2
+
+static inline uint32_t ls_blocks(int64_t n) { return static_cast<uint32_t>(std::max<int64_t>(1, div_up(n, kLsBlock))); }
+
+// 1 = point j of the sorted copy has three finite coordinates
+__global__ __launch_bounds__(kLsBlock) void k_ls_finite(const float *__restrict__ x, const float *__restrict__ y,
+                                                        const float *__restrict__ z, int64_t n, uint8_t *__restrict__ flag) {
+  const int64_t j = static_cast<int64_t>(blockIdx.x) * kLsBlock + threadIdx.x;
+  if (j >= n) return;
+  flag[j] = (fabsf(x[j]) <= FLT_MAX && fabsf(y[j]) <= FLT_MAX && fabsf(z[j]) <= FLT_MAX) ? 1 : 0;
+}
+
+// the finite points as a view: point k of the view = sorted point pos[k], caller's index perm[pos[k]]
+__global__ __launch_bounds__(kLsBlock) void k_ls_gather(const float *__restrict__ x, const float *__restrict__ y,
+                                                        const float *__restrict__ z, const int32_t *__restrict__ perm,
+                                                        const int32_t *__restrict__ pos, int64_t m, float *__restrict__ vx,
+                                                        float *__restrict__ vy, float *__restrict__ vz,
+                                                        int32_t *__restrict__ vremap) {
+  const int64_t k = static_cast<int64_t>(blockIdx.x) * kLsBlock + threadIdx.x;
+  if (k >= m) return;
+  const int32_t j = pos[k];
+  vx[k] = x[j];
+  vy[k] = y[j];
+  vz[k] = z[j];
+  vremap[k] = perm[j];
+}
+
+// records in cell order: (x, y, z, unsmoothed word) and the caller's index the result goes to
+__global__ __launch_bounds__(kLsBlock) void k_ls_records(const float *__restrict__ gx, const float *__restrict__ gy,
+                                                         const float *__restrict__ gz, const int32_t *__restrict__ order,
+                                                         const int32_t *__restrict__ remap, int64_t m,
+                                                         const uint32_t *__restrict__ words, uint4 *__restrict__ rec,
+                                                         int32_t *__restrict__ dst) {
+  const int64_t k = static_cast<int64_t>(blockIdx.x) * kLsBlock + threadIdx.x;
+  if (k >= m) return;
+  const int32_t i = remap[order[k]];
+  rec[k] = make_uint4(__float_as_uint(gx[k]), __float_as_uint(gy[k]), __float_as_uint(gz[k]), words[i]);
+  dst[k] = i;
+}
+
+// place k opens a work item when it is the first place of its cell or kLsQ places after the previous opening
+__global__ __launch_bounds__(kLsBlock) void k_ls_items(const uint4 *__restrict__ rec, int64_t m, GridDesc g,
+                                                       const int32_t *__restrict__ start, uint8_t *__restrict__ flag) {
+  const int64_t k = static_cast<int64_t>(blockIdx.x) * kLsBlock + threadIdx.x;
+  if (k >= m) return;
+  const uint4 r = rec[k];
+  int32_t ix, iy, iz;
+  grid_coords(g, __uint_as_float(r.x), __uint_as_float(r.y), __uint_as_float(r.z), ix, iy, iz);
+  const int64_t first = cell_start(g, start, iz, iy, ix);
+  flag[k] = ((k - first) % kLsQ) == 0 ? 1 : 0;
+}
+
+// one work item: the queries k0 .. k0 + nq - 1 of one cell against the records of the neighbouring cells
+__global__ __launch_bounds__(kLsQ) void k_ls_smooth(const uint4 *__restrict__ rec, const int32_t *__restrict__ dst,
+                                                    const int32_t *__restrict__ items, GridDesc g,
+                                                    const int32_t *__restrict__ start, float t, uint32_t *__restrict__ out) {
+  __shared__ uint4 tile[kLsTile];
+  __shared__ int32_t row_b[kLsMaxRows], row_e[kLsMaxRows];
+  const int32_t k0 = items[blockIdx.x];
+  const int lane = threadIdx.x;
+  int32_t ix, iy, iz;
+  {
+    const uint4 r0 = rec[k0];
+    grid_coords(g, __uint_as_float(r0.x), __uint_as_float(r0.y), __uint_as_float(r0.z), ix, iy, iz);
+  }
+  const int32_t nq = min(kLsQ, cell_start(g, start, iz, iy, ix + 1) - k0);
+  const bool active = lane < nq;
+  const uint4 q = rec[k0 + (active ? lane : 0)];
+  const float qx = __uint_as_float(q.x), qy = __uint_as_float(q.y), qz = __uint_as_float(q.z);
+  const int32_t R = g.reach, side = 2 * R + 1, rows = side * side;
+  if (lane < rows) {
+    const int32_t zz = iz + lane / side - R, yy = iy + lane % side - R;
+    int32_t b = 0, e = 0;
+    if (zz >= 0 && zz < g.nz && yy >= 0 && yy < g.ny) {
+      b = cell_start(g, start, zz, yy, max(ix - R, 0));
+      e = cell_start(g, start, zz, yy, min(ix + R, g.nx - 1) + 1);
+    }
+    row_b[lane] = b;
+    row_e[lane] = e;
+  }
+  __syncthreads();
+  // m_j <= 2^24 and c_j <= 255: every product fits 32 bits, the sums stay below 2^63 for fewer than 2^31 points
+  uint64_t sm = 0, sr = 0, sg = 0, sb = 0;
+  for (int32_t row = 0; row < rows; ++row) {
+    const int32_t b = row_b[row], e = row_e[row];
+    for (int32_t t0 = b; t0 < e; t0 += kLsTile) {
+      const int32_t cnt = min(kLsTile, e - t0);
+      __syncthreads();  // the previous tile has been read by every lane
+      for (int32_t u = lane; u < cnt; u += kLsQ) tile[u] = rec[t0 + u];
+      __syncthreads();
+      if (active) {
+#pragma unroll 4
+        for (int32_t u = 0; u < cnt; ++u) {
+          const uint4 c = tile[u];
+          const float dx = __uint_as_float(c.x) - qx, dy = __uint_as_float(c.y) - qy, dz = __uint_as_float(c.z) - qz;
+          const float d2 = (dx * dx + dy * dy) + dz * dz;  // every operation rounded on its own (-ffp-contract=off)
+          if (d2 <= t) {
+            const float w = 1.0f / (1.0f + d2);
+            const uint32_t mw = static_cast<uint32_t>(w * 16777216.0f);  // exact: w is a multiple of 2^-24 in [0.5, 1]
+            sm += mw;
+            sr += mw * (c.w & 0xffu);
+            sg += mw * ((c.w >> 8) & 0xffu);
+            sb += mw * ((c.w >> 16) & 0xffu);
+          }
+        }
+      }
+    }
+  }
+  if (!active) return;
+  // sm >= 2^24: the query is its own neighbour (d2 = 0, w = 1)
+  const uint32_t r = static_cast<uint32_t>(sr / sm), gg = static_cast<uint32_t>(sg / sm), bb = static_cast<uint32_t>(sb / sm);
+  const uint32_t has = (r | gg | bb) != 0u ? 1u : 0u;
+  out[dst[k0 + lane]] = r | (gg << 8) | (bb << 16) | (has << 24);
+}
+
+// words with the has bit set: a grid-stride loop, one atomic per workgroup (one per wavefront on a single address
+// queued up in its L2 channel: 1.9 ms for 10 M words)
+constexpr uint32_t kLsCountBlocks = 1024;
+__global__ __launch_bounds__(kLsBlock) void k_ls_count_has(const uint32_t *__restrict__ words, int64_t n,
+                                                           unsigned long long *__restrict__ count) {
+  __shared__ uint32_t part[kLsBlock / 64];
+  uint32_t c = 0;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kLsBlock + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * kLsBlock)
+    c += (words[i] >> 24) & 1u;
+  for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o, 64);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long t = 0;
+    for (int w = 0; w < kLsBlock / 64; ++w) t += part[w];
+    if (t) atomicAdd(count, t);
+  }
+}
+
+// per-call scratch: released when the call returns (a 10 M-point map holds ~300 MB of it)
+struct LsScratch {
+  DevBuf<uint8_t> flag;
+  DevBuf<int32_t> pos, vremap, dst, items;
+  DevBuf<float> vxyz;
+  DevBuf<uint4> rec;
+  ~LsScratch() {
+    flag.release();
+    pos.release();
+    vremap.release();
+    dst.release();
+    items.release();
+    vxyz.release();
+    rec.release();
+  }
+};
+
+// the m > 0 finite points of view cv: grid, records in cell order, work items, the smoothing pass into d_out
+static int smooth_finite(pcp_context *ctx, const CloudView &cv, float radius, float t, const uint32_t *d_in, uint32_t *d_out,
+                         LsScratch &s) {
+  const int64_t m = cv.n;
+  // build_grid replaces the grid that an open MLS stream or a pcp_sor_partial rests on (as every call that builds one does)
+  ctx->vgd_next = -1;
+  ctx->css_next = -1;
+  ctx->sor_partial_slab = ctx->sor_partial_slabs = -1;
+  // cell edge: the radius (reach 1), but never finer than ~8 cells per point (pcp_close_pairs: a tiny radius on a large
+  // map would otherwise take the finest grid there is; the search is as exact with the coarser cell)
+  const double vol = std::max<double>(cv.mx[0] - cv.mn[0], 1e-3) * std::max<double>(cv.mx[1] - cv.mn[1], 1e-3) *
+                     std::max<double>(cv.mx[2] - cv.mn[2], 1e-3);
+  const float by_density = static_cast<float>(std::cbrt(vol / (8.0 * static_cast<double>(m))));
+  const float cell = std::max(radius * 1.001f, by_density);
+  GridDesc g;
+  int rc = build_grid(ctx, cv, cell, radius, &g);
+  if (rc != PCP_OK) return rc;
+  if (g.reach < 1 || (2 * g.reach + 1) * (2 * g.reach + 1) > kLsMaxRows)
+    return set_error(ctx, PCP_ERR_INVALID, "local colour smoothing: grid reach %d outside 1..2", g.reach);
+  const size_t gplane = (static_cast<size_t>(m) + 3) & ~size_t(3);
+  PCP_HIP_TRY(ctx, s.rec.ensure(static_cast<size_t>(m) + 4));
+  PCP_HIP_TRY(ctx, s.dst.ensure(static_cast<size_t>(m) + 4));
+  PCP_HIP_TRY(ctx, s.flag.ensure(static_cast<size_t>(m) + 16));
+  PCP_HIP_TRY(ctx, s.items.ensure(static_cast<size_t>(m) + 4));
+  {
+    LaunchTimer lt(ctx, PCP_K_COLOUR_SMOOTH);
+    hipLaunchKernelGGL(k_ls_records, dim3(ls_blocks(m)), dim3(kLsBlock), 0, ctx->stream, ctx->g_xyz.p, ctx->g_xyz.p + gplane,
+                       ctx->g_xyz.p + 2 * gplane, ctx->g_order.p, cv.remap, m, d_in, s.rec.p, s.dst.p);
+    hipLaunchKernelGGL(k_ls_items, dim3(ls_blocks(m)), dim3(kLsBlock), 0, ctx->stream, s.rec.p, m, g, ctx->g_start.p, s.flag.p);
+    PCP_HIP_TRY(ctx, hipGetLastError());
+  }
+  int64_t n_items = 0;
+  if ((rc = compact_flags(ctx, s.flag.p, m, s.items.p, m, &n_items)) != PCP_OK) return rc;
+  {
+    LaunchTimer lt(ctx, PCP_K_COLOUR_SMOOTH);
+    if (n_items > 0)
+      hipLaunchKernelGGL(k_ls_smooth, dim3(static_cast<uint32_t>(n_items)), dim3(kLsQ), 0, ctx->stream, s.rec.p, s.dst.p,
+                         s.items.p, g, ctx->g_start.p, t, d_out);
+    PCP_HIP_TRY(ctx, hipGetLastError());
+  }
+  return PCP_OK;
+}
+
+bool smooth_radius_ok(float radius) { return std::isfinite(radius) && radius > 0.0f && radius <= 1.0f; }
+
+int colour_smooth_words(pcp_context *ctx, float radius, const uint32_t *d_in, uint32_t *d_out, int64_t *out_has_count) {
+  const int64_t n = ctx->n;
+  if (out_has_count) *out_has_count = 0;
+  if (n == 0) return PCP_OK;
+  if (d_in != d_out)  // the non-finite points keep their word; the finite ones are all overwritten below
+    PCP_HIP_TRY(ctx, hipMemcpyAsync(d_out, d_in, static_cast<size_t>(n) * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  // LS2: (double)d2 <= (double)r * (double)r  <=>  d2 <= t for every float d2
+  const double r2 = static_cast<double>(radius) * static_cast<double>(radius);
+  float t = static_cast<float>(r2);
+  if (static_cast<double>(t) > r2) t = std::nextafter(t, 0.0f);
+  LsScratch s;
+  const size_t sn = static_cast<size_t>(n);
+  const size_t plane = (sn + 3) & ~size_t(3);
+  CloudView cv{};
+  cv.x = ctx->sxyz.p;
+  cv.y = ctx->sxyz.p + plane;
+  cv.z = ctx->sxyz.p + 2 * plane;
+  cv.remap = ctx->perm.p;
+  cv.n = n;
+  for (int a = 0; a < 3; ++a) {  // the box of the finite coordinates (a superset of the finite points' box)
+    cv.mn[a] = ctx->host_min[static_cast<size_t>(a)];
+    cv.mx[a] = ctx->host_max[static_cast<size_t>(a)];
+  }
+  if (ctx->nonfinite_points > 0) {
+    // LS1: the grid (which needs finite coordinates) is built over the finite points only
+    PCP_HIP_TRY(ctx, s.flag.ensure(sn + 16));
+    PCP_HIP_TRY(ctx, s.pos.ensure(sn + 4));
+    hipLaunchKernelGGL(k_ls_finite, dim3(ls_blocks(n)), dim3(kLsBlock), 0, ctx->stream, cv.x, cv.y, cv.z, n, s.flag.p);
+    PCP_HIP_TRY(ctx, hipGetLastError());
+    int64_t m = 0;
+    int rc = compact_flags(ctx, s.flag.p, n, s.pos.p, n, &m);
+    if (rc != PCP_OK) return rc;
+    const size_t pm = (static_cast<size_t>(m) + 3) & ~size_t(3);
+    PCP_HIP_TRY(ctx, s.vxyz.ensure(3 * pm + 4));
+    PCP_HIP_TRY(ctx, s.vremap.ensure(static_cast<size_t>(m) + 4));
+    hipLaunchKernelGGL(k_ls_gather, dim3(ls_blocks(m)), dim3(kLsBlock), 0, ctx->stream, cv.x, cv.y, cv.z, ctx->perm.p, s.pos.p,
+                       m, s.vxyz.p, s.vxyz.p + pm, s.vxyz.p + 2 * pm, s.vremap.p);
+    PCP_HIP_TRY(ctx, hipGetLastError());
+    cv.x = s.vxyz.p;
+    cv.y = s.vxyz.p + pm;
+    cv.z = s.vxyz.p + 2 * pm;
+    cv.remap = s.vremap.p;
+    cv.n = m;
+  }
+  const int64_t m = cv.n;
+  PCP_HIP_TRY(ctx, ctx->s_counter.ensure(4));
+  if (m > 0) {
+    int rc = smooth_finite(ctx, cv, radius, t, d_in, d_out, s);
+    if (rc != PCP_OK) return rc;
+  }
+  PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->s_counter.p, 0, 8, ctx->stream));
+  {
+    LaunchTimer lt(ctx, PCP_K_COLOUR_SMOOTH);
+    hipLaunchKernelGGL(k_ls_count_has, dim3(std::min(ls_blocks(n), kLsCountBlocks)), dim3(kLsBlock), 0, ctx->stream, d_out, n,
+                       ctx->s_counter.p);
+    PCP_HIP_TRY(ctx, hipGetLastError());
+  }
+  unsigned long long c = 0;
+  PCP_HIP_TRY(ctx, hipMemcpyAsync(&c, ctx->s_counter.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+  PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (also: the scratch is released on return)
+  if (out_has_count) *out_has_count = static_cast<int64_t>(c);
+  // a tiny radius on a large map may take the sparse grid: do not keep its bitmap
+  if (ctx->g_occ.count > (size_t(1) << 25)) {
+    ctx->g_occ.release();
+    ctx->g_occ_rank.release();
+  }
+  return PCP_OK;
+}
+
+// (pcp_create loads every code object of the library up front: see preload_code_objects in pcp_context.hip)
+hipError_t preload_colour_smooth() {
+  hipFuncAttributes a;
+  return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_ls_smooth));
+}
+
+}  // namespace pcp
+
+using namespace pcp;
+
+extern "C" {
+
+int pcp_colour_smooth_local_packed(pcp_context *ctx, float radius, const uint32_t *in_rgba, uint32_t *out_rgba,
+                                   int64_t *out_has_count) {
+  if (!ctx) return PCP_ERR_INVALID;
+  if (!smooth_radius_ok(radius))
+    return set_error(ctx, PCP_ERR_INVALID, "pcp_colour_smooth_local_packed: radius %g outside (0, 1]", static_cast<double>(radius));
+  if (!ctx->xyz.p && ctx->n > 0) return set_error(ctx, PCP_ERR_STATE, "pcp_colour_smooth_local_packed: no cloud uploaded");
+  if (out_has_count) *out_has_count = 0;
+  const int64_t n = ctx->n;
+  if (n == 0) return PCP_OK;
+  if (!in_rgba || !out_rgba) return set_error(ctx, PCP_ERR_INVALID, "pcp_colour_smooth_local_packed: NULL words");
+  PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  DevBuf<uint32_t> words;  // the caller's words (host or device memory; in == out allowed)
+  PCP_HIP_TRY(ctx, words.ensure(static_cast<size_t>(n) + 4));
+  struct Release {
+    DevBuf<uint32_t> &b;
+    ~Release() { b.release(); }
+  } release{words};
+  PCP_HIP_TRY(ctx, hipMemcpyAsync(words.p, in_rgba, static_cast<size_t>(n) * 4, hipMemcpyDefault, ctx->stream));
+  int rc = colour_smooth_words(ctx, radius, words.p, words.p, out_has_count);
+  if (rc != PCP_OK) return rc;
+  PCP_HIP_TRY(ctx, hipMemcpyAsync(out_rgba, words.p, static_cast<size_t>(n) * 4, hipMemcpyDefault, ctx->stream));
+  PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return PCP_OK;
+}
+
+}  // extern "C"

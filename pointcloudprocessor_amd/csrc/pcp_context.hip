@@ -577,7 +577,7 @@ int pcp_create(int32_t device, pcp_context **out) {
     // others cost.
     hipFuncAttributes a;
     const hipError_t pl[] = {hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_up_bbox)), preload_colour(), preload_mls(),
-                             preload_nid(), preload_hpr()};
+                             preload_nid(), preload_hpr(), preload_colour_smooth()};
     for (hipError_t x : pl)
       if (x != hipSuccess && e == hipSuccess) e = x;
   }
@@ -1013,7 +1013,7 @@ int pcp_timing_get(pcp_context *ctx, int32_t kernel_id, double *total_ms, int64_
 const char *pcp_kernel_name(int32_t kernel_id) {
   static const char *names[PCP_K_COUNT] = {"project_frame", "depth_pass", "colour_pass", "visibility", "mls_grid",
                                            "mls_fit",       "misc",       "sor",         "mls_voxel",   "tile_mask",
-                                           "nid_hist",      "hpr"};
+                                           "nid_hist",      "hpr",        "colour_smooth"};
   return (kernel_id >= 0 && kernel_id < PCP_K_COUNT) ? names[kernel_id] : "?";
 }
 

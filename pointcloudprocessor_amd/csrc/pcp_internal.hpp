@@ -325,12 +325,66 @@ struct pcp_context {
 
 namespace pcp {
 
+// ---- the uniform grid of the radius searches (built by pcp_mls.hip build_grid; read by the MLS / SOR kernels and by
+// the local colour smoothing, pcp_colour_smooth.hip) -------------------------------------------------------------------
+struct GridDesc {
+  float minx, miny, minz, inv_cell;
+  int32_t nx, ny, nz;
+  int32_t reach;  // cells to visit on each side: ceil(r / cell)
+  // Sparse form (nullptr: dense form, the table of cell starts has one entry per cell).  Grids of more than 2^29 cells keep
+  // table entries for the OCCUPIED cells only; a bitmap with one bit per cell and the running popcount per 64-bit word
+  // give the number of occupied cells before a cell -- its place in the table (1.5 bits per cell instead of 32).
+  const unsigned long long *occ;
+  const int32_t *occ_rank;
+};
+
+// number of occupied cells before cell c (sparse form)
+__device__ __forceinline__ int32_t cell_rank(const GridDesc &g, int64_t c) {
+  const unsigned long long bits = g.occ[c >> 6];
+  return g.occ_rank[c >> 6] + static_cast<int32_t>(__popcll(bits & ((1ull << (c & 63)) - 1ull)));
+}
+
+// Entry (zz, yy, xx) of the table of cell starts = number of points in the cells before that cell (xx may be nx: the
+// first cell of the next row).  The cells of a row are consecutive in either form, so start(x0) .. start(x1 + 1) is the
+// run of candidates of the cells x0 .. x1 of a row.
+__device__ __forceinline__ int32_t cell_start(const GridDesc &g, const int32_t *__restrict__ start, int32_t zz, int32_t yy,
+                                              int32_t xx) {
+  if (!g.occ) return start[(zz * g.ny + yy) * g.nx + xx];
+  return start[cell_rank(g, (static_cast<int64_t>(zz) * g.ny + yy) * g.nx + xx)];
+}
+
+__device__ __forceinline__ void grid_coords(const GridDesc &g, float x, float y, float z, int32_t &ix, int32_t &iy,
+                                            int32_t &iz) {
+  ix = min(max(static_cast<int32_t>(floorf((x - g.minx) * g.inv_cell)), 0), g.nx - 1);
+  iy = min(max(static_cast<int32_t>(floorf((y - g.miny) * g.inv_cell)), 0), g.ny - 1);
+  iz = min(max(static_cast<int32_t>(floorf((z - g.minz) * g.inv_cell)), 0), g.nz - 1);
+}
+
+// a cloud on the device the smoothing stages operate on (the uploaded map, or an
+// intermediate of pcp_cloud_smooth); mn/mx = its bounding box
+struct CloudView {
+  const float *x, *y, *z;
+  int64_t n;
+  float mn[3], mx[3];
+  // nullptr, or view index -> caller's point index: the uploaded map is walked through its
+  // Morton-ordered copy (cell binning then permutes nearby memory only) and results are
+  // reported under the caller's indices
+  const int32_t *remap;
+};
+
+// uniform grid over a cloud view, cell edge >= `cell`, reach = ceil(radius / cell): the table of cell starts in
+// ctx->g_start, the view's points in cell order in ctx->g_order (view indices; ascending inside a cell) and ctx->g_xyz
+// (SoA planes of (n + 3) & ~3 floats).  Coordinates must be finite.
+// geometry_only: just the grid description and a large enough cell table (the density probe of sor_run fills it).
+int build_grid(pcp_context *ctx, const CloudView &cv, float cell, float radius, GridDesc *out, bool geometry_only = false);
+
 int set_error(const pcp_context *ctx, int code, const char *fmt, ...);
 // one per translation unit with kernels: forces the runtime to load that unit's code object (pcp_context.hip preload_code_objects)
 hipError_t preload_colour();
 hipError_t preload_mls();
 hipError_t preload_nid();
 hipError_t preload_hpr();
+hipError_t preload_colour_smooth();
 void set_global_error(const char *fmt, ...);
 
 #define PCP_HIP_TRY(ctx, expr)                                                                       \
@@ -368,6 +422,11 @@ int cull_frame_indices(pcp_context *ctx, int32_t frame, int32_t *d_index, int64_
 int hpr_run(pcp_context *ctx, int32_t frame, uint8_t *d_flags, uint32_t *hull_plane, uint32_t bit);
 // the hulls of keyframes [f0, f1) into the (cleared) whole-run bits, `lanes` keyframes in flight on streams of their own
 int hpr_run_range(pcp_context *ctx, int32_t f0, int32_t f1, int32_t lanes, const uint32_t *tile_mask = nullptr);
+
+// smoothColorsWithLocalRegion (pcp_colour_smooth.hip): the packed words d_in (device, input order, n = ctx->n) smoothed into
+// d_out (device; d_in == d_out allowed); *out_has_count = words of d_out with the has bit.  Synchronises the stream.
+bool smooth_radius_ok(float radius);  // LS7: finite, 0 < radius <= 1
+int colour_smooth_words(pcp_context *ctx, float radius, const uint32_t *d_in, uint32_t *d_out, int64_t *out_has_count);
 
 inline int64_t div_up(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

@@ -35,39 +35,6 @@ constexpr int kMB = 256;
 constexpr double kMaxGridCells = 536870912.0;      // 2^29: dense table of cell starts
 constexpr double kMaxSparseCells = 34359738368.0;  // 2^35: bitmap (4 GiB) + running popcounts (2 GiB)
 
-struct GridDesc {
-  float minx, miny, minz, inv_cell;
-  int32_t nx, ny, nz;
-  int32_t reach;  // cells to visit on each side: ceil(r / cell)
-  // Sparse form (nullptr: dense form, the table of cell starts has one entry per cell).  Grids of more than 2^29 cells keep
-  // table entries for the OCCUPIED cells only; a bitmap with one bit per cell and the running popcount per 64-bit word
-  // give the number of occupied cells before a cell -- its place in the table (1.5 bits per cell instead of 32).
-  const unsigned long long *occ;
-  const int32_t *occ_rank;
-};
-
-// number of occupied cells before cell c (sparse form)
-__device__ __forceinline__ int32_t cell_rank(const GridDesc &g, int64_t c) {
-  const unsigned long long bits = g.occ[c >> 6];
-  return g.occ_rank[c >> 6] + static_cast<int32_t>(__popcll(bits & ((1ull << (c & 63)) - 1ull)));
-}
-
-// Entry (zz, yy, xx) of the table of cell starts = number of points in the cells before that cell (xx may be nx: the
-// first cell of the next row).  The cells of a row are consecutive in either form, so start(x0) .. start(x1 + 1) is the
-// run of candidates of the cells x0 .. x1 of a row.
-__device__ __forceinline__ int32_t cell_start(const GridDesc &g, const int32_t *__restrict__ start, int32_t zz, int32_t yy,
-                                              int32_t xx) {
-  if (!g.occ) return start[(zz * g.ny + yy) * g.nx + xx];
-  return start[cell_rank(g, (static_cast<int64_t>(zz) * g.ny + yy) * g.nx + xx)];
-}
-
-__device__ __forceinline__ void grid_coords(const GridDesc &g, float x, float y, float z, int32_t &ix, int32_t &iy,
-                                            int32_t &iz) {
-  ix = min(max(static_cast<int32_t>(floorf((x - g.minx) * g.inv_cell)), 0), g.nx - 1);
-  iy = min(max(static_cast<int32_t>(floorf((y - g.miny) * g.inv_cell)), 0), g.ny - 1);
-  iz = min(max(static_cast<int32_t>(floorf((z - g.minz) * g.inv_cell)), 0), g.nz - 1);
-}
-
 // cell id and arrival rank of every input point; histogram in `count`.  The views are spatially ordered (Morton copy of
 // the upload, survivors of it), so a wavefront's 64 points fall into a handful of cells: the lanes of one cell share one
 // atomic (ranks by lane, i.e. by index) instead of queueing 64 returning atomics on a few addresses (545 -> 60 us per
@@ -1963,18 +1930,6 @@ __global__ __launch_bounds__(kMB) void k_sor_classify(const float *__restrict__ 
   keep[i] = !(static_cast<double>(distances[i]) > *threshold) ? 1 : 0;
 }
 
-// a cloud on the device the smoothing stages operate on (the uploaded map, or an
-// intermediate of pcp_cloud_smooth); mn/mx = its bounding box
-struct CloudView {
-  const float *x, *y, *z;
-  int64_t n;
-  float mn[3], mx[3];
-  // nullptr, or view index -> caller's point index: the uploaded map is walked through its
-  // Morton-ordered copy (cell binning then permutes nearby memory only) and results are
-  // reported under the caller's indices
-  const int32_t *remap;
-};
-
 __device__ __forceinline__ uint32_t ordered_bits(float f) {
   const uint32_t b = __float_as_uint(f);
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
@@ -2126,10 +2081,8 @@ static int exclusive_scan(pcp_context *ctx, int32_t *counts, int64_t m) {
   return PCP_OK;
 }
 
-// uniform grid over a cloud view, cell edge >= `cell`; fills ctx->g_*
-// geometry_only: just the grid description and a large enough cell table (the density probe of sor_run fills it).
-static int build_grid(pcp_context *ctx, const CloudView &cv, float cell, float radius, GridDesc *out,
-                      bool geometry_only = false) {
+// uniform grid over a cloud view, cell edge >= `cell`; fills ctx->g_* (declared in pcp_internal.hpp)
+int build_grid(pcp_context *ctx, const CloudView &cv, float cell, float radius, GridDesc *out, bool geometry_only) {
   const int64_t n = cv.n;
   GridDesc g{};
   const float *mn = cv.mn, *mx = cv.mx;

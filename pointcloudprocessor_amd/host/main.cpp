@@ -31,6 +31,10 @@
 //     output file is identical to the one-GPU run.  The NID refinement sums its joint histograms over the shards
 //     (same optimum, last-digit differences in the printed cost); --enableMLS deals the MLS queries / the dilated voxel
 //     chunks out over the GPUs (MultiCloudSmooth), the two outlier-removal brackets run on GPU 0.
+//   * --smoothColorsRadius r (new, default 0 = off, as in the reference): smoothColorsWithLocalRegion(rgbCloud, r)
+//     (PointCloudProcessor.cpp:634-703) between smoothColors and removePointsWithNoColor -- the call the reference has
+//     commented out at :597 with r = 0.1.  0 < r <= 1; only cloudInWorldWithRGB.pcd changes.  With --gpus N the gathered
+//     colours are smoothed on GPU 0 over the whole map: the files equal the one-GPU run's.
 #include <cfloat>
 #include <chrono>
 #include <cmath>
@@ -103,6 +107,7 @@ struct Options {
   float mls_voxel_size = -1.0f;  // < 0: the reference's constants (PointCloudProcessor.cpp:67-86)
   int mls_dilation_iterations = -1;
   int mls_upsampling = -1;
+  float smooth_colors_radius = 0.0f;  // 0: smoothColorsWithLocalRegion off (PointCloudProcessor.cpp:597)
 };
 
 static bool parse_bool(const std::string &v) {  // boost::program_options bool semantics
@@ -147,6 +152,17 @@ static Options parse(int argc, char **argv) {
       if (v == "none") o.mls_upsampling = 0;
       else if (v == "vgd") o.mls_upsampling = 3;
       else throw std::runtime_error("the argument ('" + v + "') for option '--mlsUpsampling' is invalid (none, vgd)");
+    }
+    else if (a == "--smoothColorsRadius") {
+      const std::string v = next();
+      const char *s = v.c_str();
+      char *end = nullptr;
+      const double r = std::strtod(s, &end);
+      const float rf = static_cast<float>(r);
+      // 0 (off) or a radius the library accepts (finite, 0 < r <= 1)
+      if (v.empty() || end != s + v.size() || !std::isfinite(r) || !(rf == 0.0f || (rf > 0.0f && rf <= 1.0f)))
+        throw std::runtime_error("the argument ('" + v + "') for option '--smoothColorsRadius' is invalid (0 = off, or 0 < r <= 1)");
+      o.smooth_colors_radius = rf;
     }
     else if (a == "--cull") {
       const std::string v = next();
@@ -582,6 +598,10 @@ class Processor {
     {
       Phase ph("colourise_gpu_s");
       gpu->colorize(rgb, has);  // smoothColors + removePointsWithNoColor flag
+    }
+    if (opt.smooth_colors_radius > 0.0f) {  // smoothColorsWithLocalRegion(rgbCloud, r), :597
+      Phase ph("colour_smooth_gpu_s");
+      gpu->smoothColorsWithLocalRegion(opt.smooth_colors_radius, rgb, has);
     }
     Phase ph_w("final_pcd_write_ascii_s");
     XYZICloud out;

@@ -234,6 +234,38 @@ class MultiDevice {
     }
   }
 
+  // smoothColorsWithLocalRegion(rgbCloud, radius) (PointCloudProcessor.cpp:634-703) over the colours colorize() returned.
+  // One GPU: in place on its result.  N > 1: the index shards hold slices of the map only, so the gathered words are
+  // smoothed on a context of GPU 0 that holds the whole map (the hull context when there is one) -- the one-GPU result.
+  void smoothColorsWithLocalRegion(float radius, std::vector<uint8_t> &rgb, std::vector<uint8_t> &has) {
+    if (size() == 1) {
+      Colorizer(device(0)).smoothColorsWithLocalRegion(radius, rgb, has);
+      return;
+    }
+    Device *whole = hull_.empty() ? nullptr : hull_[0].get();
+    if (!whole) {
+      if (!whole_) {
+        whole_.reset(new Device(ordinal(0)));
+        whole_->uploadCloud(hx_, hy_, hz_, n_);
+      }
+      whole = whole_.get();
+    }
+    const size_t n = static_cast<size_t>(n_);
+    std::vector<uint32_t> words(n);
+    for (size_t i = 0; i < n; ++i)
+      words[i] = static_cast<uint32_t>(rgb[3 * i]) | (static_cast<uint32_t>(rgb[3 * i + 1]) << 8) |
+                 (static_cast<uint32_t>(rgb[3 * i + 2]) << 16) | (static_cast<uint32_t>(has[i] ? 1 : 0) << 24);
+    int64_t coloured = 0;
+    whole->check(pcp_colour_smooth_local_packed(whole->get(), radius, words.data(), words.data(), &coloured));
+    for (size_t i = 0; i < n; ++i) {
+      const uint32_t v = words[i];
+      rgb[3 * i] = static_cast<uint8_t>(v & 0xffu);
+      rgb[3 * i + 1] = static_cast<uint8_t>((v >> 8) & 0xffu);
+      rgb[3 * i + 2] = static_cast<uint8_t>((v >> 16) & 0xffu);
+      has[i] = static_cast<uint8_t>((v >> 24) & 1u);
+    }
+  }
+
   // ViewCulling::cull of one keyframe: kept indices into the whole cloud, input order
   std::vector<int32_t> cull(int keyframe) {
     if (size() > 1 && !depth_ready_) depthPassAll();
@@ -471,6 +503,7 @@ class MultiDevice {
   bool hpr_ = false;
   const float *hx_ = nullptr, *hy_ = nullptr, *hz_ = nullptr;
   std::vector<std::unique_ptr<Device>> hull_;  // PCP_CULL_HPR, N > 1: the whole map on every GPU
+  std::unique_ptr<Device> whole_;  // N > 1, local colour smoothing without hull contexts: the whole map on GPU 0
   std::vector<std::unique_ptr<Device>> dev_;
   std::vector<hipStream_t> stream_;
   std::vector<ncclComm_t> comm_;

@@ -106,6 +106,26 @@ class Colorizer {
     has.resize(n);
     dev_.check(pcp_colorize(dev_.get(), rgb.data(), has.data()));
   }
+  // PointCloudProcessor::smoothColorsWithLocalRegion(rgbCloud, radius), PointCloudProcessor.cpp:634-703 (its call
+  // smoothColorsWithLocalRegion(rgbCloud, 0.1) is commented out at :597): in place on the result of colorize(); rgb / has
+  // (3 + 1 per input point) receive the smoothed colours and the removePointsWithNoColor flag.  Returns the coloured points.
+  int64_t smoothColorsWithLocalRegion(float radius, std::vector<uint8_t> &rgb, std::vector<uint8_t> &has) const {
+    const size_t n = static_cast<size_t>(dev_.cloudSize());
+    int64_t coloured = 0;
+    dev_.check(pcp_colour_smooth_local(dev_.get(), radius, &coloured));
+    std::vector<uint32_t> words(n);
+    dev_.check(pcp_download_result_packed(dev_.get(), words.data()));
+    rgb.resize(3 * n);
+    has.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+      const uint32_t v = words[i];
+      rgb[3 * i] = static_cast<uint8_t>(v & 0xffu);
+      rgb[3 * i + 1] = static_cast<uint8_t>((v >> 8) & 0xffu);
+      rgb[3 * i + 2] = static_cast<uint8_t>((v >> 16) & 0xffu);
+      has[i] = static_cast<uint8_t>((v >> 24) & 1u);
+    }
+    return coloured;
+  }
   // One cull per keyframe as a rule.  The outputs are sized by the largest keyframe seen so far (a keyframe sees a few
   // per cent of the map; sizing them for the whole cloud meant 33 B x n of zero-filled vectors per call, 1.65 GB at
   // 50 M points -- ADVICE r2); a keyframe that needs more reports its count and is fetched again with room for it.

@@ -93,6 +93,16 @@ class HipEngine:
     def colour_from_depth(self, download=True):
         return self.ctx.colorize_from_depth(download=download)
 
+    def smooth_colours_local(self, radius: float, download: bool = True):
+        """smoothColorsWithLocalRegion(rgbCloud, radius) (PointCloudProcessor.cpp:634-703, call commented out at :597) in
+        place on the colour result of this context: dict(rgb (n,3) uint8, has (n,) uint8), None entries without download."""
+        self.ctx.colour_smooth_local(radius)
+        if not download:
+            return dict(rgb=None, has=None)
+        w = self.ctx.download_result_packed()
+        rgb = np.stack([w & 0xFF, (w >> 8) & 0xFF, (w >> 16) & 0xFF], axis=1).astype(np.uint8)
+        return dict(rgb=rgb, has=((w >> 24) & 1).astype(np.uint8))
+
     def close(self):
         self.ctx.close()
 
@@ -119,14 +129,22 @@ class PointCloudColorizer:
         self.group = group
         self.chunks = chunks
 
-    def run(self, download: bool = True):
+    def run(self, download: bool = True, local_smooth_radius: float = 0.0):
         """Local points' colours: dict(rgb (n,3) uint8, has (n,) uint8).
 
         Multi-rank: the keyframes are split into `chunks` groups (0 = chosen from the size of the maps); the
-        all-reduce(MIN) of one group's depth maps (RCCL stream) overlaps the depth pass of the next group."""
+        all-reduce(MIN) of one group's depth maps (RCCL stream) overlaps the depth pass of the next group.
+        local_smooth_radius > 0: smoothColorsWithLocalRegion over the finished colours (one rank only; the reference
+        leaves it off, PointCloudProcessor.cpp:597)."""
+        if local_smooth_radius and self.world > 1:
+            raise ValueError("local_smooth_radius: the local colour smoothing runs on one rank holding the whole map "
+                             "(smooth the gathered words with Context.colour_smooth_local_packed)")
         if self.world == 1:
             self.engine.depth_pass()
-            return self.engine.colour_from_depth(download=download)
+            out = self.engine.colour_from_depth(download=download)
+            if local_smooth_radius:
+                out = self.engine.smooth_colours_local(local_smooth_radius, download=download)
+            return out
         import torch.distributed as dist
 
         F = self.engine.n_frames
