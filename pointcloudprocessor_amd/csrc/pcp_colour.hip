@@ -584,8 +584,7 @@ struct TopState {
 };
 
 // kMatch: 0 = match mode read from the camera block, else the mode itself (PCP_MATCH_IDENTITY 1 ... see match_constant)
-// kOneShot: flags == 4 or 12 (no top-5 state loaded or stored; packed result written in input order, or -- bit 8 -- in the
-// sorted order the pass walks, un-permuted by whatever reads it): the usual whole-run call
+// kOneShot: flags == 4 (no top-5 state loaded or stored; packed result written in input order): the usual whole-run call
 template <bool kCommon, int kMatch, bool kOneShot>
 __global__ __launch_bounds__(kBlock) void k_colour_pass(const float *__restrict__ x, const float *__restrict__ y,
                                                         const float *__restrict__ z, int64_t n, DevCamera cam_in,
@@ -595,17 +594,14 @@ __global__ __launch_bounds__(kBlock) void k_colour_pass(const float *__restrict_
                                                         const uint32_t *__restrict__ images, int64_t image_px,
                                                         TopState st, const int32_t *__restrict__ perm,
                                                         uint32_t *__restrict__ rgba, int32_t flags_in,
-                                                        const int32_t *__restrict__ tile_order_in,
                                                         const uint32_t *__restrict__ hull_bits_in) {
   DevCamera cam = common_camera<kCommon>(cam_in);
   if constexpr (kMatch == 1) cam.match_mode = PCP_MATCH_IDENTITY;
   if constexpr (kMatch == 2) cam.match_mode = PCP_MATCH_ROUNDTRIP;
-  // the common configuration walks the cloud order and has no hull bits (both are null then: the host checks)
-  const int32_t *__restrict__ tile_order = kCommon ? nullptr : tile_order_in;
+  // the common configuration has no hull bits (null then: the host checks)
   const uint32_t *__restrict__ hull_bits = kCommon ? nullptr : hull_bits_in;
-  const int32_t flags = kOneShot ? (4 | (flags_in & 8)) : flags_in;
-  const int64_t j = tile_order ? static_cast<int64_t>(tile_order[blockIdx.x]) * 64 + threadIdx.x
-                               : static_cast<int64_t>(xcd_chunked_block()) * kBlock + threadIdx.x;
+  const int32_t flags = kOneShot ? 4 : flags_in;
+  const int64_t j = static_cast<int64_t>(xcd_chunked_block()) * kBlock + threadIdx.x;
   const bool live = j < n;
   // a wavefront wholly past the cloud (tail of a 256-thread workgroup) has no tile: its mask words do not exist
   if (!__ballot(live)) return;
@@ -669,32 +665,14 @@ __global__ __launch_bounds__(kBlock) void k_colour_pass(const float *__restrict_
     st.frame[3 * n + j] = t.f3; st.frame[4 * n + j] = t.f4;
     st.count[j] = t.count;
   }
-  // The packed result.  Straight into input order (flags & 8 clear: PCP_RESULT_UNPERMUTE=0, the form of rounds 2-4) it is a
-  // scattered 4-B store per point, each a 32-B partial write in HBM: WRITE_SIZE 316 MB for 40 MB of results
-  // (profiles/r04_pmc.json) -- it retires under this VALU-bound kernel for free, but it is 8x the bytes.  flags & 8: coalesced
-  // stores in the sorted order the pass walks (40 MB); the un-permutation is then fused into whatever READS the result
-  // (round 5, PCP_RESULT_UNPERMUTE=2; slower, see unpermute_mode): the download (k_unpermute on the COPY stream, beside the next step's passes, then the copy engine),
-  // the byte-splitting kernel of pcp_colorize's outputs, or -- for a caller that asks for the device array -- a kernel of its own.  PCP_RESULT_UNPERMUTE=1: sorted stores + that kernel right after
-  // the pass (45 MB, +35 us per step: the first form of this alternative).  Results identical in all three.
-  if (flags & 4) rgba[(flags & 8) ? j : static_cast<int64_t>(perm[j])] = t.finalise();
-}
-
-// out[i] = sorted[inv_perm[i]]: coalesced index loads and result stores; the gathers hit a 4n-byte buffer that the
-// producing kernel has just written (L2 / Infinity Cache)
-__global__ __launch_bounds__(kBlock) void k_unpermute(const uint32_t *__restrict__ sorted, const int32_t *__restrict__ inv_perm,
-                                                      int64_t n, uint32_t *__restrict__ out) {
-  const int64_t q = (static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x) * 4;
-  if (q + 3 < n) {
-    const int4 k = *reinterpret_cast<const int4 *>(inv_perm + q);
-    *reinterpret_cast<uint4 *>(out + q) = make_uint4(sorted[k.x], sorted[k.y], sorted[k.z], sorted[k.w]);
-  } else {
-    for (int64_t i = q; i < n; ++i) out[i] = sorted[inv_perm[i]];
-  }
+  // The packed result, scattered straight into input order: sorted stores un-permuted by a kernel after the pass or by
+  // every reader were measured slower ("The result store of the colour pass").
+  if (flags & 4) rgba[static_cast<int64_t>(perm[j])] = t.finalise();
 }
 
 // finalise from stored state (multi-batch runs)
 __global__ __launch_bounds__(kBlock) void k_finalise(int64_t n, TopState st, const int32_t *__restrict__ perm,
-                                                     uint32_t *__restrict__ rgba, int32_t sorted_out) {
+                                                     uint32_t *__restrict__ rgba) {
   const int64_t j = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (j >= n) return;
   Top5 t;
@@ -705,7 +683,7 @@ __global__ __launch_bounds__(kBlock) void k_finalise(int64_t n, TopState st, con
   t.f0 = st.frame[0 * n + j]; t.f1 = st.frame[1 * n + j]; t.f2 = st.frame[2 * n + j];
   t.f3 = st.frame[3 * n + j]; t.f4 = st.frame[4 * n + j];
   t.count = st.count[j];
-  rgba[sorted_out ? j : static_cast<int64_t>(perm[j])] = t.finalise();  // see k_colour_pass
+  rgba[static_cast<int64_t>(perm[j])] = t.finalise();  // see k_colour_pass
 }
 
 // ---------------------------------------------------------------------------
@@ -768,13 +746,11 @@ __global__ __launch_bounds__(kBlock) void k_selftest_div32(DevCamera cam, unsign
 // small utility kernels
 // ---------------------------------------------------------------------------
 // packed result r | g<<8 | b<<16 | has<<24  ->  rgb[3n] (r, g, b) and has[n]
-// inv_perm (nullable): `packed` is in sorted order -- point i's word is packed[inv_perm[i]] (the un-permutation fused in)
 __global__ __launch_bounds__(kBlock) void k_unpack_result(const uint32_t *__restrict__ packed, int64_t n,
-                                                         uint8_t *__restrict__ rgb, uint8_t *__restrict__ has,
-                                                         const int32_t *__restrict__ inv_perm) {
+                                                         uint8_t *__restrict__ rgb, uint8_t *__restrict__ has) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (i >= n) return;
-  const uint32_t v = packed[inv_perm ? inv_perm[i] : i];
+  const uint32_t v = packed[i];
   rgb[3 * i + 0] = static_cast<uint8_t>(v & 0xffu);
   rgb[3 * i + 1] = static_cast<uint8_t>((v >> 8) & 0xffu);
   rgb[3 * i + 2] = static_cast<uint8_t>((v >> 16) & 0xffu);
@@ -1108,19 +1084,6 @@ static int ensure_depth(pcp_context *ctx) {
   return PCP_OK;
 }
 
-// PCP_RESULT_UNPERMUTE: 0 (default) = the colour pass scatters its result into input order; 1 = sorted stores + an un-permuting
-// kernel right after the pass; 2 = sorted stores, un-permuted by whatever reads the result.  Read per call: tests flip it
-// inside one process.  Measured at C3 in round 5 (100 steps, driver protocol): 0: 1.345 ms per step; 1: 1.56 ms (the gather
-// of 10 M random words is a 0.17 ms kernel); 2: 1.45 ms (the same kernel on the copy stream, beside the next step's passes,
-// then the copy engine; with the kernel writing the pinned buffer over PCIe itself: 2.06 ms).  The un-permutation is 10 M
-// random 4-byte accesses wherever it is put; as scattered stores of the VALU-bound pass it costs 0.045 ms and 8x the bytes.
-static int unpermute_mode() {
-  const char *e = std::getenv("PCP_RESULT_UNPERMUTE");
-  if (!e || !e[0]) return 0;
-  return e[0] == '0' ? 0 : (e[0] == '1' ? 1 : 2);
-}
-static bool unpermute_results() { return unpermute_mode() == 1; }
-
 static int ensure_state(pcp_context *ctx) {
   const size_t sn = static_cast<size_t>(ctx->n);
   PCP_HIP_TRY(ctx, ctx->top_score.ensure(kTopM * sn + 4));
@@ -1129,7 +1092,6 @@ static int ensure_state(pcp_context *ctx) {
   PCP_HIP_TRY(ctx, ctx->view_count.ensure(sn + 4));
   PCP_HIP_TRY(ctx, ctx->rgba2[0].ensure(sn + 4));
   PCP_HIP_TRY(ctx, ctx->rgba2[1].ensure(sn + 4));
-  PCP_HIP_TRY(ctx, ctx->rgba_sorted.ensure(sn + 4));
   return PCP_OK;
 }
 
@@ -1383,13 +1345,9 @@ static int upload_image_impl(pcp_context *ctx, const char *who, int32_t frame, c
     PCP_HIP_TRY(ctx, hipMemcpyAsync(ctx->upload_stage[lane].p, bgr, block_bytes, hipMemcpyHostToDevice, us));
     src = ctx->upload_stage[lane].p;
   } else {
-    static const bool direct = [] {
-      const char *e = std::getenv("PCP_UPLOAD_DIRECT");
-      return !(e && e[0] == '0');
-    }();
     hipPointerAttribute_t attr{};
     if (hipPointerGetAttributes(&attr, bgr) == hipSuccess &&
-        (attr.type == hipMemoryTypeDevice || (direct && attr.type == hipMemoryTypeHost)) && attr.devicePointer) {
+        (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeHost) && attr.devicePointer) {
       src = static_cast<const uint8_t *>(attr.devicePointer);
       if (attr.type == hipMemoryTypeDevice) {
         // bytes produced on the device (a collective on the context's stream): this lane starts after that work
@@ -1885,28 +1843,17 @@ static int colour_pass_impl(pcp_context *ctx, int32_t frame_begin, int32_t frame
     // the colour pass keeps the cloud order (256-thread workgroups, XCD-chunked): it does not end in a tail of heavy
     // tiles (longest-first order: no gain at 1920x1080), and its texel gathers want neighbouring tiles on the same L2
     // (longest-first order at 4096x3000: 1.96 -> 2.18 ms)
-    const bool ordered = false;
-    const bool common = is_common_camera(ctx->dcam) && !ordered && ctx->cull.cull_mode != PCP_CULL_HPR;
-    // (mode 1 writes the scratch buffer a download of mode 2 may still be filling on the copy stream: tests flip the modes)
-    if (one_shot && unpermute_mode() == 1) PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->copy_stream));
-    const int32_t launch_flags = flags | ((one_shot && unpermute_mode() != 0) ? 8 : 0);
-    ctx->last_pass_sorted = one_shot && unpermute_mode() == 2;  // the result stays in sorted order: end_result marks the buffer
+    const bool common = is_common_camera(ctx->dcam) && ctx->cull.cull_mode != PCP_CULL_HPR;
     auto kernel = k_colour_pass<false, 0, false>;
     if (common && ctx->dcam.match_mode == PCP_MATCH_IDENTITY)
-      kernel = (launch_flags & ~8) == 4 ? k_colour_pass<true, 1, true> : k_colour_pass<true, 1, false>;
+      kernel = flags == 4 ? k_colour_pass<true, 1, true> : k_colour_pass<true, 1, false>;
     if (common && ctx->dcam.match_mode == PCP_MATCH_ROUNDTRIP)
-      kernel = (launch_flags & ~8) == 4 ? k_colour_pass<true, 2, true> : k_colour_pass<true, 2, false>;
-    hipLaunchKernelGGL(kernel, dim3(ordered ? static_cast<uint32_t>(ctx->n_tiles) : blocks_for(ctx->n)),
-                       dim3(ordered ? 64 : kBlock), 0, ctx->stream, ctx->sxyz.p, ctx->sxyz.p + plane,
+      kernel = flags == 4 ? k_colour_pass<true, 2, true> : k_colour_pass<true, 2, false>;
+    hipLaunchKernelGGL(kernel, dim3(blocks_for(ctx->n)), dim3(kBlock), 0, ctx->stream, ctx->sxyz.p, ctx->sxyz.p + plane,
                        ctx->sxyz.p + 2 * plane, ctx->n, ctx->dcam, ctx->frames.p, frame_begin, frame_end, ctx->depth.p,
                        cells_of(ctx), ctx->tile_mask.p, ctx->mask_words, ctx->images.p,
-                       static_cast<int64_t>(ctx->dcam.img_w) * ctx->dcam.img_h, st, ctx->perm.p,
-                       (one_shot && unpermute_results()) ? ctx->rgba_sorted.p : result,
-                       launch_flags, ordered ? ctx->tile_order.p : static_cast<const int32_t *>(nullptr),
+                       static_cast<int64_t>(ctx->dcam.img_w) * ctx->dcam.img_h, st, ctx->perm.p, result, flags,
                        ctx->cull.cull_mode == PCP_CULL_HPR ? ctx->hull_bits.p : static_cast<const uint32_t *>(nullptr));
-    if (one_shot && unpermute_results())
-      hipLaunchKernelGGL(k_unpermute, dim3(blocks_for(div_up(ctx->n, 4))), dim3(kBlock), 0, ctx->stream, ctx->rgba_sorted.p,
-                         ctx->inv_perm.p, ctx->n, result);
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
   if (!one_shot) ctx->colour_state_live = true;
@@ -1924,15 +1871,12 @@ static int end_result(pcp_context *ctx, uint8_t *out_rgb, uint8_t *out_has) {
   PCP_HIP_TRY(ctx, hipEventRecord(ctx->result_ready[cur], ctx->stream));
   ctx->rgba_cur = cur;
   ctx->colour_result_live = true;
-  ctx->result_sorted[cur] = ctx->last_pass_sorted;  // the producer left the words in sorted order: readers un-permute
-  ctx->last_pass_sorted = false;
   if ((out_rgb || out_has) && n > 0) {
     // split the packed words on the device: 3 + 1 bytes per point cross PCIe, and no host loop over the points
     const size_t sn = static_cast<size_t>(n);
     PCP_HIP_TRY(ctx, ctx->s_keep.ensure(4 * sn + 16));
     uint8_t *d_rgb = ctx->s_keep.p, *d_has = ctx->s_keep.p + 3 * sn;
-    hipLaunchKernelGGL(k_unpack_result, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, dst, n, d_rgb, d_has,
-                       ctx->result_sorted[cur] ? ctx->inv_perm.p : static_cast<const int32_t *>(nullptr));
+    hipLaunchKernelGGL(k_unpack_result, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, dst, n, d_rgb, d_has);
     PCP_HIP_TRY(ctx, hipGetLastError());
     if (out_rgb) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_rgb, d_rgb, 3 * sn, hipMemcpyDeviceToHost, ctx->stream));
     if (out_has) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_has, d_has, sn, hipMemcpyDeviceToHost, ctx->stream));
@@ -1960,13 +1904,7 @@ int pcp_colour_finalise(pcp_context *ctx, uint8_t *out_rgb, uint8_t *out_has, in
   } else if (n > 0) {
     TopState st{ctx->top_score.p, ctx->top_rgb.p, ctx->top_frame.p, ctx->view_count.p};
     LaunchTimer t(ctx, PCP_K_COLOUR);
-    const bool un = unpermute_results();
-    ctx->last_pass_sorted = unpermute_mode() == 2;
-    hipLaunchKernelGGL(k_finalise, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, n, st, ctx->perm.p,
-                       un ? ctx->rgba_sorted.p : result, (un || ctx->last_pass_sorted) ? 1 : 0);
-    if (un)
-      hipLaunchKernelGGL(k_unpermute, dim3(blocks_for(div_up(n, 4))), dim3(kBlock), 0, ctx->stream, ctx->rgba_sorted.p,
-                         ctx->inv_perm.p, n, result);
+    hipLaunchKernelGGL(k_finalise, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, n, st, ctx->perm.p, result);
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
   if ((rc = end_result(ctx, out_rgb, out_has)) != PCP_OK) return rc;
@@ -2016,26 +1954,6 @@ int pcp_colorize_from_depth(pcp_context *ctx, uint8_t *out_rgb, uint8_t *out_has
   return end_result(ctx, out_rgb, out_has);
 }
 
-// The current result as a device array in INPUT order (callers that read rgba2[cur] themselves): where the producer left it in
-// sorted order, one un-permuting kernel into the scratch buffer, which then becomes the result buffer.
-static int result_in_input_order(pcp_context *ctx) {
-  const int32_t cur = ctx->rgba_cur;
-  if (!ctx->result_sorted[cur]) return PCP_OK;
-  if (ctx->copy_pending[cur]) {  // a download of this buffer may still be reading it on the copy stream
-    PCP_HIP_TRY(ctx, hipEventSynchronize(ctx->copy_done[cur]));
-    ctx->copy_pending[cur] = false;
-  }
-  PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->copy_stream));  // (... or still writing the scratch)
-  PCP_HIP_TRY(ctx, ctx->rgba_sorted.ensure(static_cast<size_t>(ctx->n) + 4));
-  hipLaunchKernelGGL(k_unpermute, dim3(blocks_for(div_up(ctx->n, 4))), dim3(kBlock), 0, ctx->stream, ctx->rgba2[cur].p,
-                     ctx->inv_perm.p, ctx->n, ctx->rgba_sorted.p);
-  PCP_HIP_TRY(ctx, hipGetLastError());
-  std::swap(ctx->rgba2[cur], ctx->rgba_sorted);
-  ctx->result_sorted[cur] = false;
-  PCP_HIP_TRY(ctx, hipEventRecord(ctx->result_ready[cur], ctx->stream));
-  return PCP_OK;
-}
-
 int pcp_colour_smooth_local(pcp_context *ctx, float radius, int64_t *out_has_count) {
   if (!ctx) return PCP_ERR_INVALID;
   if (!smooth_radius_ok(radius))
@@ -2045,15 +1963,13 @@ int pcp_colour_smooth_local(pcp_context *ctx, float radius, int64_t *out_has_cou
   if (out_has_count) *out_has_count = 0;
   if (ctx->n == 0) return PCP_OK;
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  // the unsmoothed words in input order are read from the current buffer, the smoothed ones go to the other half of the
-  // double buffer (begin_result waits for a download that may still read it), which then becomes the result
-  int rc = result_in_input_order(ctx);
-  if (rc != PCP_OK) return rc;
+  // the unsmoothed words are read from the current buffer, the smoothed ones go to the other half of the double buffer
+  // (begin_result waits for a download that may still read it), which then becomes the result
   const uint32_t *src = ctx->rgba2[ctx->rgba_cur].p;
   uint32_t *dst = nullptr;
-  if ((rc = begin_result(ctx, &dst)) != PCP_OK) return rc;
+  int rc = begin_result(ctx, &dst);
+  if (rc != PCP_OK) return rc;
   if ((rc = colour_smooth_words(ctx, radius, src, dst, out_has_count)) != PCP_OK) return rc;
-  ctx->last_pass_sorted = false;
   return end_result(ctx, nullptr, nullptr);
 }
 
@@ -2062,12 +1978,9 @@ int pcp_download_result_packed(pcp_context *ctx, uint32_t *out_rgba) {
   if (!ctx->colour_result_live)
     return set_error(ctx, PCP_ERR_STATE, "pcp_download_result_packed: no result (call pcp_colorize / pcp_colour_finalise)");
   if (!out_rgba && ctx->n > 0) return set_error(ctx, PCP_ERR_INVALID, "pcp_download_result_packed: NULL output");
-  if (ctx->n > 0) {
-    int rc = result_in_input_order(ctx);
-    if (rc != PCP_OK) return rc;
+  if (ctx->n > 0)
     PCP_HIP_TRY(ctx, hipMemcpyAsync(out_rgba, ctx->rgba2[ctx->rgba_cur].p, static_cast<size_t>(ctx->n) * 4,
                                     hipMemcpyDeviceToHost, ctx->stream));
-  }
   PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return PCP_OK;
 }
@@ -2079,21 +1992,9 @@ int pcp_download_result_packed_async(pcp_context *ctx, uint32_t *out_rgba) {
   if (!out_rgba && ctx->n > 0) return set_error(ctx, PCP_ERR_INVALID, "pcp_download_result_packed_async: NULL output");
   const int32_t cur = ctx->rgba_cur;
   PCP_HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->result_ready[cur], 0));
-  if (ctx->n > 0 && ctx->result_sorted[cur]) {
-    // the result sits in the sorted order the colour pass walks: the un-permutation rides on the copy stream -- a kernel gathers
-    // sorted[inv_perm[i]] into a device scratch in input order (~35 us at 10 M points, beside the next step's passes), the copy
-    // engine takes it from there.  (Measured and left out: the kernel writing the caller's pinned buffer itself over PCIe, in
-    // place of the blit -- 19.5 GB/s against the copy engine's 55: a step of 2.06 ms instead of 1.30.)
-    PCP_HIP_TRY(ctx, ctx->rgba_sorted.ensure(static_cast<size_t>(ctx->n) + 4));
-    uint32_t *target = ctx->rgba_sorted.p;
-    hipLaunchKernelGGL(k_unpermute, dim3(blocks_for(div_up(ctx->n, 4))), dim3(kBlock), 0, ctx->copy_stream, ctx->rgba2[cur].p,
-                       ctx->inv_perm.p, ctx->n, target);
-    PCP_HIP_TRY(ctx, hipGetLastError());
-    PCP_HIP_TRY(ctx, hipMemcpyAsync(out_rgba, target, static_cast<size_t>(ctx->n) * 4, hipMemcpyDeviceToHost, ctx->copy_stream));
-  } else if (ctx->n > 0) {
+  if (ctx->n > 0)
     PCP_HIP_TRY(ctx, hipMemcpyAsync(out_rgba, ctx->rgba2[cur].p, static_cast<size_t>(ctx->n) * 4, hipMemcpyDeviceToHost,
                                     ctx->copy_stream));
-  }
   PCP_HIP_TRY(ctx, hipEventRecord(ctx->copy_done[cur], ctx->copy_stream));
   ctx->copy_pending[cur] = true;
   return PCP_OK;
@@ -2137,10 +2038,6 @@ int pcp_colour_result_device(pcp_context *ctx, void **device_ptr, int64_t *n_wor
   if (!ctx) return PCP_ERR_INVALID;
   if (!ctx->colour_result_live)
     return set_error(ctx, PCP_ERR_STATE, "pcp_colour_result_device: no result (call pcp_colorize / pcp_colour_finalise)");
-  if (ctx->n > 0) {
-    const int rc = result_in_input_order(ctx);
-    if (rc != PCP_OK) return rc;
-  }
   if (device_ptr) *device_ptr = ctx->rgba2[ctx->rgba_cur].p;
   if (n_words) *n_words = ctx->n;
   return PCP_OK;

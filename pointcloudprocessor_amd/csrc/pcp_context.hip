@@ -241,20 +241,20 @@ __device__ __forceinline__ uint32_t hilbert30(uint32_t x, uint32_t y, uint32_t z
 }
 
 // Spatial order for the batched run: 64 consecutive points (one wavefront) then fall in few z-buffer cells
-// and mostly share their keyframe visibility.  Hilbert order by default (PCP_CLOUD_ORDER=morton: Z order, as rounds 1-3
-// shipped it): on the C3 scene the bounding spheres of the 64-point tiles shrink from 8.4 to 6.0 cm on average, and the
-// few tiles that straddle a jump of the Z curve (radius up to metres) disappear.
+// and mostly share their keyframe visibility.  Hilbert order rather than the Z order rounds 1-3 shipped: on the C3 scene
+// the bounding spheres of the 64-point tiles shrink from 8.4 to 6.0 cm on average, and the few tiles that straddle a jump
+// of the Z curve (radius up to metres) disappear.
 __global__ __launch_bounds__(kUpBlock) void k_up_keys(const float *__restrict__ x, const float *__restrict__ y,
                                                      const float *__restrict__ z, int64_t n, float mnx, float mny,
                                                      float mnz, float scx, float scy, float scz,
-                                                     uint32_t *__restrict__ key, int32_t *__restrict__ val, int32_t hilbert) {
+                                                     uint32_t *__restrict__ key, int32_t *__restrict__ val) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kUpBlock + threadIdx.x;
   if (i >= n) return;
   // non-finite coordinates convert to 0 / saturate: any key is fine, the order only affects speed
   const uint32_t ix = static_cast<uint32_t>(fminf(fmaxf((x[i] - mnx) * scx, 0.0f), 1023.0f));
   const uint32_t iy = static_cast<uint32_t>(fminf(fmaxf((y[i] - mny) * scy, 0.0f), 1023.0f));
   const uint32_t iz = static_cast<uint32_t>(fminf(fmaxf((z[i] - mnz) * scz, 0.0f), 1023.0f));
-  key[i] = hilbert ? hilbert30(ix, iy, iz) : (spread10(ix) | (spread10(iy) << 1) | (spread10(iz) << 2));
+  key[i] = hilbert30(ix, iy, iz);
   val[i] = static_cast<int32_t>(i);
 }
 
@@ -497,10 +497,8 @@ static int store_cloud(pcp_context *ctx, const float *x, const float *y, const f
   PCP_HIP_TRY(ctx, hist.ensure(static_cast<size_t>(hm) + 8));
   const int64_t scan_tiles = std::max<int64_t>(1, (hm + 1 + kScanTile - 1) / kScanTile);
   PCP_HIP_TRY(ctx, ctx->s_tiles.ensure(static_cast<size_t>(scan_tiles) + 4));
-  const char *order_env = std::getenv("PCP_CLOUD_ORDER");
-  const int32_t hilbert = !(order_env && order_env[0] == 'm');
   hipLaunchKernelGGL(k_up_keys, dim3(up_blocks(n)), dim3(kUpBlock), 0, st, dx, dy, dz, n, mn[0], mn[1], mn[2], sc[0], sc[1],
-                     sc[2], key_a.p, ctx->perm.p, hilbert);
+                     sc[2], key_a.p, ctx->perm.p);
   uint32_t *kin = key_a.p, *kout = key_b.p;
   int32_t *vin = ctx->perm.p, *vout = val_b.p;
   for (int pass = 0; pass < 4; ++pass) {  // 30 key bits: 4 passes of 8 (an even count: the result lands in perm)
@@ -645,7 +643,6 @@ void pcp_destroy(pcp_context *ctx) {
   ctx->sxyz.release();
   ctx->perm.release();
   ctx->inv_perm.release();
-  ctx->rgba_sorted.release();
   ctx->frames.release();
   ctx->images.release();
   ctx->hsv_tables.release();

@@ -175,7 +175,6 @@ struct pcp_context {
   pcp::DevBuf<float> sxyz;   // sorted x[n] y[n] z[n]
   pcp::DevBuf<int32_t> perm; // n
   pcp::DevBuf<int32_t> inv_perm;  // n: inv_perm[perm[j]] = j (un-permutes per-point results with coalesced stores)
-  pcp::DevBuf<uint32_t> rgba_sorted;  // packed result in Morton order, before the un-permute
   std::vector<float> host_min = {0, 0, 0}, host_max = {0, 0, 0};
 
   // frames
@@ -237,8 +236,6 @@ struct pcp_context {
   bool copy_pending[2] = {false, false};
   bool colour_state_live = false;
   bool colour_result_live = false;
-  bool result_sorted[2] = {false, false};  // rgba2[k] holds its words in the sorted (Morton) order of the passes: readers un-permute
-  bool last_pass_sorted = false;           // ... as the pass that has just run left them (end_result moves it to the buffer)
 
   // scratch for the single-frame calls
   pcp::DevBuf<int32_t> s_cell, s_pixel;

@@ -1325,7 +1325,7 @@ __global__ __launch_bounds__(kSelWave) __attribute__((amdgpu_waves_per_eu(PCP_SE
   grid_coords(g, qx, qy, qz, cx, cy, cz);
   const float cell = 1.0f / g.inv_cell;
   // every point closer than g.reach cells lies in the (2 reach + 1)^3 cells; 0.999: fp32 slop of the cell assignment.
-  // (reach = 1 unless PCP_SOR_REACH says otherwise: see sor_run)
+  // (sor_run builds grids of reach 1)
   const int32_t sr = g.reach;
   const float limit = static_cast<float>(sr) * cell * 0.999f, limit2 = limit * limit;
   const int32_t x0 = max(cx - sr, 0), x1 = min(cx + sr, g.nx - 1);
@@ -2797,10 +2797,8 @@ static int sor_run(pcp_context *ctx, const CloudView &cv, int32_t mean_k, double
     if (const char *e = std::getenv("PCP_SOR_BALL")) ball = atof(e);
     double final_cell = std::sqrt(ball * (mean_k + 1) / (3.14159265358979 * area_density));
     if (!(final_cell > 1e-7) || !(final_cell < 1e30)) final_cell = static_cast<double>(cell);
-    // (cells of 1 / PCP_SOR_REACH of the ball's radius: as below)
-    int sel_reach = 1;
-    if (const char *e = std::getenv("PCP_SOR_REACH")) sel_reach = std::max(1, std::min(4, atoi(e)));
-    rc = build_grid(ctx, cv, static_cast<float>(final_cell / sel_reach), static_cast<float>(final_cell * 0.9999), &g);
+    // (cells of the ball's radius: as below)
+    rc = build_grid(ctx, cv, static_cast<float>(final_cell), static_cast<float>(final_cell * 0.9999), &g);
     if (rc != PCP_OK) return rc;
   } else {
     // density probe on every 8th point, every 32nd of a large cloud (cell edge from the sub-sample's own volume guess):
@@ -2840,13 +2838,11 @@ static int sor_run(pcp_context *ctx, const CloudView &cv, int32_t mean_k, double
       const double want = std::sqrt(ball * (mean_k + 1) / (3.14159265358979 * per_area));
       if (want > 0.0 && want < 1e30) final_cell = want;
     }
-    // final_cell is the radius of the selection's ball; the cells are 1 / PCP_SOR_REACH of it.  Measured at C3: reach 1
-    // (27 cells, 9 runs per lane) sor 7.33 ms / grids 0.99 ms; reach 2 (125 half-size cells, 25 runs, 31 % fewer candidates
-    // on a surface) 7.64 / 1.65 ms; reach 3 9.88 / 3.01 ms -- the runs' fixed costs and ragged ends outweigh the candidates saved
-    int sel_reach = 1;
-    if (const char *e = std::getenv("PCP_SOR_REACH")) sel_reach = std::max(1, std::min(4, atoi(e)));
-    // (0.9999: reach = ceil(radius / cell) must not round up to sel_reach + 1)
-    rc = build_grid(ctx, cv, static_cast<float>(final_cell / sel_reach), static_cast<float>(final_cell * 0.9999), &g);
+    // final_cell is the radius of the selection's ball and the cells' edge (reach 1).  Measured at C3: reach 1 (27 cells,
+    // 9 runs per lane) sor 7.33 ms / grids 0.99 ms; reach 2 (125 half-size cells, 25 runs, 31 % fewer candidates on a
+    // surface) 7.64 / 1.65 ms; reach 3 9.88 / 3.01 ms -- the runs' fixed costs and ragged ends outweigh the candidates saved
+    // (0.9999: reach = ceil(radius / cell) must not round up to 2)
+    rc = build_grid(ctx, cv, static_cast<float>(final_cell), static_cast<float>(final_cell * 0.9999), &g);
     if (rc != PCP_OK) return rc;
   }
   PCP_HIP_TRY(ctx, ctx->s_dist.ensure(sn + 8));

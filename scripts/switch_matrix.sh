@@ -19,8 +19,6 @@ run hull PCP_HPR_ONESTEP=0 PCP_TILT_BUDGET=0 PCP_HPR_LANES=1 -- tests/test_hpr_g
 run hull PCP_HPR_QUICK=0 PCP_HPR_RADIAL=0 -- tests/test_hpr_gpu.py
 run hull PCP_HPR_TILT=0 -- tests/test_hpr_gpu.py
 run hull PCP_HPR_LANES=8 PCP_TILT_BUDGET=8 -- tests/test_hpr_gpu.py tests/test_full_size_gpu.py
-run colour PCP_RESULT_UNPERMUTE=2 -- tests/test_colour_gpu.py tests/test_golden_gpu.py tests/test_baseline_configs_gpu.py
-run colour PCP_RESULT_UNPERMUTE=1 -- tests/test_colour_gpu.py tests/test_golden_gpu.py
 run smooth PCP_SOR_CLUSTERED=1 -- tests/test_sor_gpu.py tests/test_mls_gpu.py tests/test_smooth_stream_gpu.py
 run smooth PCP_SOR_CLUSTERED=0 -- tests/test_smooth_stream_gpu.py tests/test_mls_gpu.py
 run smooth PCP_GRID_SPARSE=1 -- tests/test_smooth_stream_gpu.py tests/test_sor_gpu.py

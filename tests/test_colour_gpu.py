@@ -440,9 +440,9 @@ def test_hpr_candidates_and_roundtrip_modes_match_oracle(gpu_ctx_factory, oracle
         assert ref["count"].sum() > zb["count"].sum()
 
 
-def test_result_unpermute_switch_gives_identical_results(gpu_ctx_factory, small_scene, monkeypatch):
-    """PCP_RESULT_UNPERMUTE=1: the colour pass stores its packed result in Morton order with coalesced stores and a
-    second kernel un-permutes it (8x fewer bytes written, 35 us slower per step at 10 M points): same bits."""
+def test_one_shot_result_equals_multi_batch_result(gpu_ctx_factory, small_scene):
+    """The one-shot colour pass (packed result scattered straight into input order) and the multi-batch path (top-5 state
+    over two keyframe batches, then k_finalise): same bits."""
     from pointcloudprocessor_amd import capi
 
     ctx = gpu_ctx_factory()
@@ -453,36 +453,29 @@ def test_result_unpermute_switch_gives_identical_results(gpu_ctx_factory, small_
     ctx.colour_pass(0, 3)
     ctx.colour_pass(3, 6)
     base2 = ctx.colour_finalise()
-    monkeypatch.setenv("PCP_RESULT_UNPERMUTE", "1")
-    alt = ctx.colorize()
-    ctx.colour_reset()
-    ctx.depth_pass()
-    ctx.colour_pass(0, 3)
-    ctx.colour_pass(3, 6)
-    alt2 = ctx.colour_finalise()
-    for a, b in ((base, alt), (base2, alt2), (base, base2)):
-        assert np.array_equal(a["rgb"], b["rgb"]) and np.array_equal(a["has"], b["has"])
+    assert np.array_equal(base["rgb"], base2["rgb"]) and np.array_equal(base["has"], base2["has"])
     assert base["has"].sum() > 500
 
 
-def test_sorted_result_is_unpermuted_by_every_reader(gpu_ctx_factory, small_scene, monkeypatch):
-    """PCP_RESULT_UNPERMUTE=2 (round 5; measured slower than the scattered store, kept as a switch): the colour pass stores its packed result in the sorted order it walks and
-    whatever reads the result un-permutes it -- the byte outputs of pcp_colorize, the packed downloads (synchronous; on the copy
-    stream into pinned and into pageable memory: an un-permuting kernel into a scratch buffer, then the copy engine), the
-    device array.  All equal to the scattered form of rounds 2-4 (PCP_RESULT_UNPERMUTE=0)."""
+def test_every_reader_returns_input_order(gpu_ctx_factory, oracle, small_scene):
+    """Every reader of the packed result sees it in input order: the byte outputs of pcp_colorize, the packed downloads
+    (synchronous; on the copy stream into pinned memory, over both result buffers, and into pageable memory), the device
+    array and the multi-batch path (k_finalise).  The byte outputs are anchored to the oracle."""
     import torch
 
     from pointcloudprocessor_amd import capi
 
     ctx = gpu_ctx_factory()
-    _setup(ctx, capi, small_scene)
-    monkeypatch.setenv("PCP_RESULT_UNPERMUTE", "0")
+    cd = _setup(ctx, capi, small_scene)
+    s = small_scene
     base = ctx.colorize()
+    ref = oracle.colorize(cam_struct(oracle, cd), oracle.default_cull_params(), s["x"], s["y"], s["z"], s["poses"], s["images"])
+    _colour_close(base["rgb"], ref)
+    assert np.array_equal(base["has"] > 0, ref["has"] > 0)
     want = ctx.download_result_packed()
     assert np.array_equal(want & 0xFF, base["rgb"][:, 0]) and np.array_equal(want >> 24, base["has"])
-    monkeypatch.setenv("PCP_RESULT_UNPERMUTE", "2")
     n = len(want)
-    got = ctx.colorize()  # the byte-splitting kernel gathers through inv_perm
+    got = ctx.colorize()
     assert np.array_equal(got["rgb"], base["rgb"]) and np.array_equal(got["has"], base["has"])
     pinned = torch.zeros(n, dtype=torch.int32).pin_memory()
     for rep in range(3):  # both result buffers in turn
@@ -502,9 +495,9 @@ def test_sorted_result_is_unpermuted_by_every_reader(gpu_ctx_factory, small_scen
     ctx.synchronize()
     assert np.array_equal(pageable, want)
     ctx.colorize(download=False)
-    assert np.array_equal(ctx.download_result_packed(), want)  # synchronous: un-permuted on the device first
+    assert np.array_equal(ctx.download_result_packed(), want)
     ctx.colorize(download=False)
-    ptr, words = ctx.colour_result_device()  # the device array in input order
+    ptr, words = ctx.colour_result_device()
     assert words == n
     dev = torch.zeros(n, dtype=torch.int32, device="cuda")
     ctx.synchronize()
