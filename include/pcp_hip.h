@@ -91,7 +91,18 @@ typedef struct pcp_camera {
                               |p_w - p_i|^2 < f32(1e-5^2) in fp32 (what radiusSearch(1e-5) tests for point i itself,
                               :571), scores from p_c' = c2w.inverse() p_w in fp32 (:578-579).  Samples that the
                               reference's kd-tree would ALSO credit to other map points closer than 10 um to p_w are
-                              not replicated (needs map points < ~20 um apart). */
+                              not credited to them here (needs map points < ~20 um apart): PCP_MATCH_RADIUS does. */
+#define PCP_MATCH_RADIUS 2 /* the reference's whole match-back (:480-482,555,571-592): every map point j with
+                              |p_w - p_j|^2 < f32(1e-5^2) (fp32 L2_Simple, strict <) receives the sample, j = i included
+                              when it passes; per point, samples arrive in (keyframe, input index) order.  Built on
+                              ROUNDTRIP: points with no other map point within R_c = (1e-5 + E)(1 + 1e-3), E a proven
+                              bound of the fp32 round-trip displacement (DESIGN.md "Radius match-back"), are served by the
+                              colour pass as in ROUNDTRIP; the others (set A) by a fix-up kernel over a neighbour table
+                              that the first colour pass in this mode builds.  Costs sum_{j in A} |row(j)| x keyframes.
+                              Not available on an index shard (PCP_DEPTH_BATCHED): the colour pass returns
+                              PCP_ERR_STATE.  A sample displaced further than E (never, by the proof) makes the colour
+                              pass fail rather than return a result.  Libraries before this mode reject it in
+                              pcp_set_camera with PCP_ERR_INVALID: that is how a caller detects support. */
 
 /* vlcal::ViewCullingParams, PCP/include/vlcal/calib/view_culling.hpp:10-19, plus
  * the constants 14 (view_culling.cpp:63) and 0.05 (:157). */
@@ -100,7 +111,7 @@ typedef struct pcp_cull_params {
   int32_t downsample_factor;
   double depth_slack;
   int32_t cull_mode;  /* PCP_CULL_ZBUFFER (default) / PCP_CULL_HPR_CANDIDATES / PCP_CULL_HPR */
-  int32_t match_mode; /* PCP_MATCH_ROUNDTRIP (default) / PCP_MATCH_IDENTITY */
+  int32_t match_mode; /* PCP_MATCH_ROUNDTRIP (default) / PCP_MATCH_IDENTITY / PCP_MATCH_RADIUS */
   double hpr_flip_radius; /* ViewCullingParams::hidden_points_removal_max_z = 90000 (view_culling.hpp:14) */
 } pcp_cull_params;
 
@@ -443,11 +454,12 @@ int pcp_nid_optimize_with(pcp_context *ctx, pcp_nid_eval_fn eval, void *user, co
 /* ---- precondition of the match-back (PointCloudProcessor.cpp:480-482,571) ------------------------------- */
 /* Number of map points that have ANOTHER map point closer than `radius` (fp32 squared distance, strict <, as
  * kdtree.radiusSearch compares).  The reference credits a visible sample to every map point within 1e-5 m of the
- * sample's fp32 world position; libpcp_hip credits the sample's own point only (PCP_MATCH_ROUNDTRIP / _IDENTITY).  The
- * two agree when no two map points can both lie within 1e-5 m of one sample: call this with radius = 2.5e-5 (the
- * match radius plus twice the largest fp32 round-trip error of maps within +-50 m) and expect 0; a non-zero count
- * (duplicated or near-duplicated points, e.g. un-deduplicated scan accumulations) names how many points may receive
- * a neighbour's samples in the reference and not here. */
+ * sample's fp32 world position; PCP_MATCH_ROUNDTRIP / _IDENTITY credit the sample's own point only, PCP_MATCH_RADIUS
+ * credits every such point.  ROUNDTRIP agrees with the reference when no two map points can both lie within 1e-5 m of
+ * one sample: call this with radius = 2.5e-5 (the match radius plus twice the largest fp32 round-trip error measured
+ * on maps within +-50 m) and expect 0; a non-zero count (duplicated or near-duplicated points, e.g. un-deduplicated
+ * scan accumulations) names how many points may receive a neighbour's samples in the reference and under
+ * PCP_MATCH_RADIUS, but not under ROUNDTRIP. */
 int pcp_close_pairs(pcp_context *ctx, double radius, int64_t *points_with_close_neighbour);
 
 /* ---- measurement -------------------------------------------------------- */

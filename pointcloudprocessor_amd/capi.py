@@ -51,13 +51,16 @@ class CullParams(C.Structure):
         ("downsample_factor", C.c_int32),
         ("depth_slack", C.c_double),
         ("cull_mode", C.c_int32),   # CULL_ZBUFFER / CULL_HPR_CANDIDATES / CULL_HPR
-        ("match_mode", C.c_int32),  # MATCH_IDENTITY / MATCH_ROUNDTRIP
+        ("match_mode", C.c_int32),  # MATCH_IDENTITY / MATCH_ROUNDTRIP / MATCH_RADIUS
         ("hpr_flip_radius", C.c_double),  # hidden_points_removal_max_z, view_culling.hpp:14
     ]
 
 
 CULL_ZBUFFER, CULL_HPR_CANDIDATES, CULL_HPR = 0, 1, 2
 MATCH_IDENTITY, MATCH_ROUNDTRIP = 0, 1
+# the reference's whole match-back: every map point within 1e-5 m of a sample's world position receives it
+# (PointCloudProcessor.cpp:480-482,571-592); whole-map contexts only (pcp_hip.h PCP_MATCH_RADIUS)
+MATCH_RADIUS = 2
 
 
 class MLSParams(C.Structure):

@@ -583,7 +583,16 @@ struct TopState {
   int32_t *count;
 };
 
-// kMatch: 0 = match mode read from the camera block, else the mode itself (PCP_MATCH_IDENTITY 1 ... see match_constant)
+// PCP_MATCH_RADIUS (kMatch 3): the neighbour table's flags and the displacement check (pcp_match.hip); unused otherwise
+struct MatchArgs {
+  const uint8_t *in_a;        // n flags, Morton order: the point is in A (k_match_fixup credits it)
+  unsigned long long *moved;  // samples whose round trip moved them further than E
+  float e2;                   // E^2, rounded up
+};
+
+// kMatch: 0 = match mode read from the camera block, else the mode itself (PCP_MATCH_IDENTITY 1 ... see match_constant);
+// 3 = PCP_MATCH_RADIUS: ROUNDTRIP for the points outside A, nothing inserted for the points of A (k_match_fixup), and every
+// kept sample's round-trip displacement counted against E
 // kOneShot: flags == 4 (no top-5 state loaded or stored; packed result written in input order): the usual whole-run call
 template <bool kCommon, int kMatch, bool kOneShot>
 __global__ __launch_bounds__(kBlock) void k_colour_pass(const float *__restrict__ x, const float *__restrict__ y,
@@ -594,10 +603,10 @@ __global__ __launch_bounds__(kBlock) void k_colour_pass(const float *__restrict_
                                                         const uint32_t *__restrict__ images, int64_t image_px,
                                                         TopState st, const int32_t *__restrict__ perm,
                                                         uint32_t *__restrict__ rgba, int32_t flags_in,
-                                                        const uint32_t *__restrict__ hull_bits_in) {
+                                                        const uint32_t *__restrict__ hull_bits_in, MatchArgs mb) {
   DevCamera cam = common_camera<kCommon>(cam_in);
   if constexpr (kMatch == 1) cam.match_mode = PCP_MATCH_IDENTITY;
-  if constexpr (kMatch == 2) cam.match_mode = PCP_MATCH_ROUNDTRIP;
+  if constexpr (kMatch == 2 || kMatch == 3) cam.match_mode = PCP_MATCH_ROUNDTRIP;
   // the common configuration has no hull bits (null then: the host checks)
   const uint32_t *__restrict__ hull_bits = kCommon ? nullptr : hull_bits_in;
   const int32_t flags = kOneShot ? 4 : flags_in;
@@ -620,6 +629,9 @@ __global__ __launch_bounds__(kBlock) void k_colour_pass(const float *__restrict_
     t.f3 = st.frame[3 * n + j]; t.f4 = st.frame[4 * n + j];
     t.count = st.count[j];
   }
+  [[maybe_unused]] bool in_a = false;
+  [[maybe_unused]] uint32_t moved = 0u;
+  if constexpr (kMatch == 3) in_a = live && mb.in_a[j] != 0;
   for (int32_t w = f0 >> 5; w <= (f1 - 1) >> 5; ++w) {
     uint32_t todo = range_bits(w, f0, f1);
     if (tile_mask) todo &= tile_mask[tile * words + w];
@@ -641,7 +653,11 @@ __global__ __launch_bounds__(kBlock) void k_colour_pass(const float *__restrict_
         bool keep = true;
         if (cam.enable_zbuf) keep = keep_by_depth(p.xc, p.yc, p.zc, static_cast<double>(__uint_as_float(dbits)) + cam.slack);
         float sx = p.xc, sy = p.yc, sz = p.zc;
-        if (cam.match_mode == PCP_MATCH_ROUNDTRIP && keep) keep = roundtrip_sample(cam, fr, px, py, pz, sx, sy, sz);
+        if constexpr (kMatch == 3) {
+          if (keep) keep = roundtrip_sample_moved(cam, fr, px, py, pz, sx, sy, sz, mb.e2, moved) && !in_a;
+        } else {
+          if (cam.match_mode == PCP_MATCH_ROUNDTRIP && keep) keep = roundtrip_sample(cam, fr, px, py, pz, sx, sy, sz);
+        }
         // only samples that pass the keep rule fetch their texel: nearly every fetch is a 64-B sector of its own
         // (neighbouring candidates image a median 4 px apart at 1920x1080, 11 px at 4096x3000), and the depth test
         // drops 51 % / 37 % of the candidates (profiles/r02_candidates.json).  Issuing both gathers up front (one
@@ -654,6 +670,9 @@ __global__ __launch_bounds__(kBlock) void k_colour_pass(const float *__restrict_
         }
       }
     }
+  }
+  if constexpr (kMatch == 3) {
+    if (moved) atomicAdd(mb.moved, static_cast<unsigned long long>(moved));
   }
   if (!live) return;
   if (flags & 2) {
@@ -684,6 +703,73 @@ __global__ __launch_bounds__(kBlock) void k_finalise(int64_t n, TopState st, con
   t.f3 = st.frame[3 * n + j]; t.f4 = st.frame[4 * n + j];
   t.count = st.count[j];
   rgba[static_cast<int64_t>(perm[j])] = t.finalise();  // see k_colour_pass
+}
+
+// PCP_MATCH_RADIUS fix-up: one lane per point j of A (pcp_match.hip).  The lane starts from the state the colour pass started
+// from (loaded, or empty in one-shot mode) and, for f in [f0, f1) and i in row(j) in input order -- the order in which the
+// reference's loop at PointCloudProcessor.cpp:559-594 reaches the samples --, recomputes i's sample exactly as k_colour_pass
+// does (candidate rule, hull bit, keep rule, pixel, fp32 round trip) and inserts it when |p_w - p_j|^2 < f32(1e-5^2).  A
+// (tile, keyframe) pair that the tile mask clears holds no candidate: i is skipped there.  Cost: sum over A of |row(j)| per
+// keyframe -- quadratic in the multiplicity of a duplicated point, as the reference's radius searches are.
+__global__ __launch_bounds__(kBlock) void k_match_fixup(const float *__restrict__ x, const float *__restrict__ y,
+                                                        const float *__restrict__ z, int64_t n, DevCamera cam,
+                                                        const DevFrame *__restrict__ frames, int32_t f0, int32_t f1,
+                                                        const uint32_t *__restrict__ depth, int64_t cells,
+                                                        const uint32_t *__restrict__ tile_mask, int32_t words,
+                                                        const uint32_t *__restrict__ images, int64_t image_px, TopState st,
+                                                        const int32_t *__restrict__ perm, uint32_t *__restrict__ rgba,
+                                                        int32_t flags, const uint32_t *__restrict__ hull_bits,
+                                                        const int32_t *__restrict__ list, int64_t na,
+                                                        const int64_t *__restrict__ off, const int32_t *__restrict__ cols) {
+  const int64_t a = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (a >= na) return;
+  const int64_t j = list[a];
+  Top5 t;
+  t.init();
+  if (flags & 1) {
+    t.s0 = st.score[0 * n + j]; t.s1 = st.score[1 * n + j]; t.s2 = st.score[2 * n + j];
+    t.s3 = st.score[3 * n + j]; t.s4 = st.score[4 * n + j];
+    t.c0 = st.rgb[0 * n + j]; t.c1 = st.rgb[1 * n + j]; t.c2 = st.rgb[2 * n + j];
+    t.c3 = st.rgb[3 * n + j]; t.c4 = st.rgb[4 * n + j];
+    t.f0 = st.frame[0 * n + j]; t.f1 = st.frame[1 * n + j]; t.f2 = st.frame[2 * n + j];
+    t.f3 = st.frame[3 * n + j]; t.f4 = st.frame[4 * n + j];
+    t.count = st.count[j];
+  }
+  const float qx = x[j], qy = y[j], qz = z[j];
+  const int64_t r0 = off[a], r1 = off[a + 1];
+  for (int32_t f = f0; f < f1; ++f) {
+    const DevFrame &fr = frames[f];
+    const int32_t w = f >> 5;
+    const uint32_t bit = 1u << (f & 31);
+    for (int64_t r = r0; r < r1; ++r) {
+      const int64_t i = cols[r];
+      if (tile_mask && !(tile_mask[(i >> 6) * words + w] & bit)) continue;
+      if (hull_bits && !(hull_bits[static_cast<int64_t>(w) * n + i] & bit)) continue;
+      const float px = x[i], py = y[i], pz = z[i];
+      const Projected p = project_point<false>(cam, fr.w2c, px, py, pz);
+      const bool cand = p.pixel >= 0 && (cam.enable_zbuf ? p.cell >= 0 : p.cell != -1);
+      if (!cand) continue;
+      if (cam.enable_zbuf) {
+        const uint32_t dbits = depth[static_cast<uint64_t>(static_cast<uint32_t>(f)) * static_cast<uint32_t>(cells) + static_cast<uint32_t>(p.cell)];
+        if (!keep_by_depth(p.xc, p.yc, p.zc, static_cast<double>(__uint_as_float(dbits)) + cam.slack)) continue;
+      }
+      // the sample's world position, matched against p_j (roundtrip_sample with the matched point in place of i)
+      float sx = p.xc, sy = p.yc, sz = p.zc;
+      if (!roundtrip_sample(cam, fr, qx, qy, qz, sx, sy, sz)) continue;
+      const uint32_t texel = images[static_cast<uint64_t>(static_cast<uint32_t>(f)) * static_cast<uint32_t>(image_px) + static_cast<uint32_t>(p.pixel)];
+      t.insert(final_score(sx, sy, sz, fr.px, fr.py, fr.pz), texel & 0xffffffu, f);
+    }
+  }
+  if (flags & 2) {
+    st.score[0 * n + j] = t.s0; st.score[1 * n + j] = t.s1; st.score[2 * n + j] = t.s2;
+    st.score[3 * n + j] = t.s3; st.score[4 * n + j] = t.s4;
+    st.rgb[0 * n + j] = t.c0; st.rgb[1 * n + j] = t.c1; st.rgb[2 * n + j] = t.c2;
+    st.rgb[3 * n + j] = t.c3; st.rgb[4 * n + j] = t.c4;
+    st.frame[0 * n + j] = t.f0; st.frame[1 * n + j] = t.f1; st.frame[2 * n + j] = t.f2;
+    st.frame[3 * n + j] = t.f3; st.frame[4 * n + j] = t.f4;
+    st.count[j] = t.count;
+  }
+  if (flags & 4) rgba[static_cast<int64_t>(perm[j])] = t.finalise();
 }
 
 // ---------------------------------------------------------------------------
@@ -1823,9 +1909,14 @@ static int colour_pass_impl(pcp_context *ctx, int32_t frame_begin, int32_t frame
         (static_cast<size_t>(f) >= ctx->hull_valid.size() || !ctx->hull_valid[static_cast<size_t>(f)]))
       return set_error(ctx, PCP_ERR_STATE, "pcp_colour_pass: PCP_CULL_HPR on an index shard, pcp_hull_flags_import has not covered keyframe %d", f);
   }
+  const bool radius = ctx->dcam.match_mode == PCP_MATCH_RADIUS;
+  if (radius && ctx->depth_from_batch)
+    return set_error(ctx, PCP_ERR_STATE, "pcp_colour_pass: PCP_MATCH_RADIUS needs the whole map on one context: an index shard "
+                     "(PCP_DEPTH_BATCHED) cannot see the neighbours that other shards hold");
   if ((rc = ensure_state(ctx)) != PCP_OK) return rc;
   if ((rc = wait_images(ctx, frame_begin, frame_end)) != PCP_OK) return rc;
   if (ctx->n == 0) return PCP_OK;
+  if (radius && (rc = match_table_prepare(ctx)) != PCP_OK) return rc;
   if (frame_begin == frame_end) {
     if (one_shot && result) PCP_HIP_TRY(ctx, hipMemsetAsync(result, 0, static_cast<size_t>(ctx->n) * 4, ctx->stream));
     return PCP_OK;
@@ -1838,6 +1929,12 @@ static int colour_pass_impl(pcp_context *ctx, int32_t frame_begin, int32_t frame
     flags |= 4;
   else
     flags |= 2;
+  MatchArgs mb{nullptr, nullptr, 0.0f};
+  if (radius) {
+    mb = MatchArgs{ctx->match_in_a.p, ctx->match_moved.p, ctx->match_e2};
+    PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->match_moved.p, 0, 8, ctx->stream));
+  }
+  const uint32_t *hull = ctx->cull.cull_mode == PCP_CULL_HPR ? ctx->hull_bits.p : static_cast<const uint32_t *>(nullptr);
   {
     LaunchTimer t(ctx, PCP_K_COLOUR);
     // the colour pass keeps the cloud order (256-thread workgroups, XCD-chunked): it does not end in a tail of heavy
@@ -1849,14 +1946,32 @@ static int colour_pass_impl(pcp_context *ctx, int32_t frame_begin, int32_t frame
       kernel = flags == 4 ? k_colour_pass<true, 1, true> : k_colour_pass<true, 1, false>;
     if (common && ctx->dcam.match_mode == PCP_MATCH_ROUNDTRIP)
       kernel = flags == 4 ? k_colour_pass<true, 2, true> : k_colour_pass<true, 2, false>;
+    if (radius) kernel = !common ? k_colour_pass<false, 3, false> : flags == 4 ? k_colour_pass<true, 3, true> : k_colour_pass<true, 3, false>;
     hipLaunchKernelGGL(kernel, dim3(blocks_for(ctx->n)), dim3(kBlock), 0, ctx->stream, ctx->sxyz.p, ctx->sxyz.p + plane,
                        ctx->sxyz.p + 2 * plane, ctx->n, ctx->dcam, ctx->frames.p, frame_begin, frame_end, ctx->depth.p,
                        cells_of(ctx), ctx->tile_mask.p, ctx->mask_words, ctx->images.p,
-                       static_cast<int64_t>(ctx->dcam.img_w) * ctx->dcam.img_h, st, ctx->perm.p, result, flags,
-                       ctx->cull.cull_mode == PCP_CULL_HPR ? ctx->hull_bits.p : static_cast<const uint32_t *>(nullptr));
+                       static_cast<int64_t>(ctx->dcam.img_w) * ctx->dcam.img_h, st, ctx->perm.p, result, flags, hull, mb);
     PCP_HIP_TRY(ctx, hipGetLastError());
+    if (radius && ctx->match_a > 0) {
+      hipLaunchKernelGGL(k_match_fixup, dim3(blocks_for(ctx->match_a)), dim3(kBlock), 0, ctx->stream, ctx->sxyz.p,
+                         ctx->sxyz.p + plane, ctx->sxyz.p + 2 * plane, ctx->n, ctx->dcam, ctx->frames.p, frame_begin, frame_end,
+                         ctx->depth.p, cells_of(ctx), ctx->tile_mask.p, ctx->mask_words, ctx->images.p,
+                         static_cast<int64_t>(ctx->dcam.img_w) * ctx->dcam.img_h, st, ctx->perm.p, result, flags, hull,
+                         ctx->match_list.p, ctx->match_a, ctx->match_off.p, ctx->match_cols.p);
+      PCP_HIP_TRY(ctx, hipGetLastError());
+    }
   }
   if (!one_shot) ctx->colour_state_live = true;
+  if (radius) {
+    // the proof of E says this count is 0; a sample moved further would have escaped the table: no silent result
+    unsigned long long moved = 0;
+    unsigned long long *dst = ctx->readback ? static_cast<unsigned long long *>(ctx->readback) : &moved;  // pinned: no staging
+    PCP_HIP_TRY(ctx, hipMemcpyAsync(dst, ctx->match_moved.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+    PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (*dst != 0)
+      return set_error(ctx, PCP_ERR_RANGE, "pcp_colour_pass: PCP_MATCH_RADIUS: %llu samples moved further than the bound E = %g m "
+                       "in their fp32 round trip; the neighbour table may miss their matches", *dst, ctx->match_e);
+  }
   return PCP_OK;
 }
 

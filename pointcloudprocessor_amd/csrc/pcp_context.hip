@@ -436,6 +436,7 @@ static int store_cloud(pcp_context *ctx, const float *x, const float *y, const f
   ctx->nid_chunks = 0;
   ctx->colour_state_live = false;
   ctx->colour_result_live = false;
+  match_table_release(ctx);  // PCP_MATCH_RADIUS: the table belongs to the cloud that is being replaced
   ctx->mls_count = 0;
   ctx->vgd_next = ctx->css_next = -1;  // the streams of the smoothing stage belong to the cloud that is being replaced
   ctx->css_ball = 0.0;
@@ -570,12 +571,12 @@ int pcp_create(int32_t device, pcp_context **out) {
   e = hipSetDevice(device);
   if (e == hipSuccess) {
     // The HIP runtime loads a translation unit's code object at the first launch of one of its kernels (deferred loading), on
-    // the calling thread: tens of milliseconds of host work per unit, wherever that first launch happens to fall.  All five
+    // the calling thread: tens of milliseconds of host work per unit, wherever that first launch happens to fall.  All the
     // units are loaded here, where a caller expects set-up time; the first call of every entry point then costs what the
     // others cost.
     hipFuncAttributes a;
     const hipError_t pl[] = {hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_up_bbox)), preload_colour(), preload_mls(),
-                             preload_nid(), preload_hpr(), preload_colour_smooth()};
+                             preload_nid(), preload_hpr(), preload_colour_smooth(), preload_match()};
     for (hipError_t x : pl)
       if (x != hipSuccess && e == hipSuccess) e = x;
   }
@@ -661,6 +662,8 @@ void pcp_destroy(pcp_context *ctx) {
   ctx->view_count.release();
   ctx->rgba2[0].release();
   ctx->rgba2[1].release();
+  match_table_release(ctx);
+  ctx->match_moved.release();
   for (int k = 0; k < 2; ++k) {
     if (ctx->result_ready[k]) (void)hipEventDestroy(ctx->result_ready[k]);
     if (ctx->copy_done[k]) (void)hipEventDestroy(ctx->copy_done[k]);
@@ -796,7 +799,7 @@ int pcp_set_camera(pcp_context *ctx, const pcp_camera *cam, const pcp_cull_param
     return set_error(ctx, PCP_ERR_INVALID, "pcp_set_camera: unknown cull_mode %d", cp.cull_mode);
   if (cp.cull_mode == PCP_CULL_HPR && !(cp.hpr_flip_radius > 0.0 && cp.hpr_flip_radius < 1e300))
     return set_error(ctx, PCP_ERR_INVALID, "pcp_set_camera: hpr_flip_radius must be positive and finite");
-  if (cp.match_mode != PCP_MATCH_IDENTITY && cp.match_mode != PCP_MATCH_ROUNDTRIP)
+  if (cp.match_mode != PCP_MATCH_IDENTITY && cp.match_mode != PCP_MATCH_ROUNDTRIP && cp.match_mode != PCP_MATCH_RADIUS)
     return set_error(ctx, PCP_ERR_INVALID, "pcp_set_camera: unknown match_mode %d", cp.match_mode);
   if (cam->cull_width > (1 << 24) || cam->cull_height > (1 << 24))
     return set_error(ctx, PCP_ERR_INVALID, "pcp_set_camera: cull size above 2^24 is not supported");
@@ -974,6 +977,7 @@ int pcp_set_frames(pcp_context *ctx, const pcp_pose *poses, int32_t n_frames, co
   ctx->mask_set.assign(static_cast<size_t>(n_frames), 0);
   ctx->depth_valid.assign(static_cast<size_t>(n_frames), 0);
   ctx->hull_valid.clear();
+  ctx->match_live = false;  // PCP_MATCH_RADIUS: E (and with it R_c) depends on the keyframes
   ctx->colour_state_live = false;
   ctx->colour_result_live = false;
   return PCP_OK;

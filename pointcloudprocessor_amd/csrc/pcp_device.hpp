@@ -242,6 +242,25 @@ __device__ __forceinline__ bool roundtrip_sample(const DevCamera &c, const DevFr
   return true;
 }
 
+// PCP_MATCH_RADIUS: roundtrip_sample, plus one to `moved` when p_w lies further than sqrt(e2) from the sample's own point
+// (the neighbour table's bound E failed: the colour pass reports it as an error)
+__device__ __forceinline__ bool roundtrip_sample_moved(const DevCamera &c, const DevFrame &fr, float wx0, float wy0, float wz0,
+                                                       float &xc, float &yc, float &zc, float e2, uint32_t &moved) {
+  float wx, wy, wz;
+  xform(fr.c2w, xc, yc, zc, wx, wy, wz);
+  const float dx = wx - wx0, dy = wy - wy0, dz = wz - wz0;
+  float d2 = dx * dx;
+  d2 += dy * dy;
+  d2 += dz * dz;
+  moved += (d2 <= e2) ? 0u : 1u;
+  if (!(d2 < c.match_r2)) return false;
+  const float *m = fr.c2w_inv;
+  xc = (m[0] * wx + m[1] * wy) + (m[2] * wz + m[3]);
+  yc = (m[4] * wx + m[5] * wy) + (m[6] * wz + m[7]);
+  zc = (m[8] * wx + m[9] * wy) + (m[10] * wz + m[11]);
+  return true;
+}
+
 // A6 scores: computeOrientationScore hpp:205-220 (B4 reproduced),
 // computeDistanceScore hpp:222-236, final cpp:588; (xc, yc, zc) is p_c (PCP_MATCH_IDENTITY) or p_c' (PCP_MATCH_ROUNDTRIP).
 //

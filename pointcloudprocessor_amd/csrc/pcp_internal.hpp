@@ -34,7 +34,7 @@ struct DevCamera {
   int32_t enable_zbuf;
   int32_t cull_mode;   // PCP_CULL_ZBUFFER / PCP_CULL_HPR_CANDIDATES (enable_zbuf is 0 with the latter; PCP_CULL_HPR runs
                        // the candidate filter here and the hull in pcp_hpr.hip)
-  int32_t match_mode;  // PCP_MATCH_IDENTITY / PCP_MATCH_ROUNDTRIP
+  int32_t match_mode;  // PCP_MATCH_IDENTITY / PCP_MATCH_ROUNDTRIP / PCP_MATCH_RADIUS
   double cull_wd, cull_hd;  // cull size as fp64: bounds of hidden_points_removal's (int)u, (int)v rule
   float match_r2;      // f32(1e-5 * 1e-5): radiusSearch(epsilon) squared radius, PointCloudProcessor.cpp:482,571
   int32_t pretest;  // 1: run the conservative fp32 rejection test before the fp64 projection
@@ -237,6 +237,19 @@ struct pcp_context {
   bool colour_state_live = false;
   bool colour_result_live = false;
 
+  // PCP_MATCH_RADIUS (pcp_match.hip): the neighbour table within R_c, built by the first colour pass in that mode and
+  // dropped by pcp_upload_cloud / pcp_set_frames (E depends on both).  Set A = points whose row holds another point.
+  bool match_live = false;
+  double match_e = 0.0, match_rc = 0.0;  // E (proven round-trip displacement bound) and R_c, metres
+  float match_e2 = 0.0f;                 // E^2 rounded up: the colour pass counts samples displaced further
+  int64_t match_a = 0;                   // |A|
+  int64_t match_entries = 0;             // sum over A of the row lengths
+  pcp::DevBuf<uint8_t> match_in_a;       // n flags, Morton order
+  pcp::DevBuf<int32_t> match_list;       // the points of A (Morton indices, ascending)
+  pcp::DevBuf<int64_t> match_off;        // |A| + 1 row offsets
+  pcp::DevBuf<int32_t> match_cols;       // rows: Morton indices, each row sorted by input index, the point itself included
+  pcp::DevBuf<unsigned long long> match_moved;  // samples displaced further than E by the last colour pass
+
   // scratch for the single-frame calls
   pcp::DevBuf<int32_t> s_cell, s_pixel;
   pcp::DevBuf<float> s_range, s_cam;
@@ -424,6 +437,11 @@ int hpr_run_range(pcp_context *ctx, int32_t f0, int32_t f1, int32_t lanes, const
 // d_out (device; d_in == d_out allowed); *out_has_count = words of d_out with the has bit.  Synchronises the stream.
 bool smooth_radius_ok(float radius);  // LS7: finite, 0 < radius <= 1
 int colour_smooth_words(pcp_context *ctx, float radius, const uint32_t *d_in, uint32_t *d_out, int64_t *out_has_count);
+
+// PCP_MATCH_RADIUS (pcp_match.hip): builds the neighbour table if it is not live (E, R_c, flags, list, rows)
+int match_table_prepare(pcp_context *ctx);
+void match_table_release(pcp_context *ctx);
+hipError_t preload_match();
 
 inline int64_t div_up(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

@@ -35,6 +35,11 @@
 //     (PointCloudProcessor.cpp:634-703) between smoothColors and removePointsWithNoColor -- the call the reference has
 //     commented out at :597 with r = 0.1.  0 < r <= 1; only cloudInWorldWithRGB.pcd changes.  With --gpus N the gathered
 //     colours are smoothed on GPU 0 over the whole map: the files equal the one-GPU run's.
+//   * --matchBack roundtrip|radius (new, default roundtrip): how a coloured sample is credited back to map points
+//     (PointCloudProcessor.cpp:480-482,571-592).  roundtrip = PCP_MATCH_ROUNDTRIP, the sample's own point when its fp32
+//     world round trip finds it; radius = PCP_MATCH_RADIUS, every map point within 10 um of the sample, as the reference's
+//     kdtree.radiusSearch does (maps with duplicated points differ).  radius needs the whole map on one GPU: --gpus N > 1
+//     with it is rejected.
 #include <cfloat>
 #include <chrono>
 #include <cmath>
@@ -104,6 +109,7 @@ struct Options {
   bool skip_filtered_dumps = false;
   int gpus = 1;
   int cull_mode = PCP_CULL_ZBUFFER;
+  int match_mode = PCP_MATCH_ROUNDTRIP;
   float mls_voxel_size = -1.0f;  // < 0: the reference's constants (PointCloudProcessor.cpp:67-86)
   int mls_dilation_iterations = -1;
   int mls_upsampling = -1;
@@ -171,8 +177,16 @@ static Options parse(int argc, char **argv) {
       else if (v == "hpr_candidates") o.cull_mode = PCP_CULL_HPR_CANDIDATES;
       else throw std::runtime_error("the argument ('" + v + "') for option '--cull' is invalid (zbuffer, hpr, hpr_candidates)");
     }
+    else if (a == "--matchBack") {
+      const std::string v = next();
+      if (v == "roundtrip") o.match_mode = PCP_MATCH_ROUNDTRIP;
+      else if (v == "radius") o.match_mode = PCP_MATCH_RADIUS;
+      else throw std::runtime_error("the argument ('" + v + "') for option '--matchBack' is invalid (roundtrip, radius)");
+    }
     else throw std::runtime_error("unrecognised option '" + a + "'");
   }
+  if (o.match_mode == PCP_MATCH_RADIUS && o.gpus > 1)
+    throw std::runtime_error("the option '--matchBack radius' needs the whole map on one GPU (--gpus 1)");
   return o;
 }
 
@@ -388,13 +402,14 @@ class Processor {
     pcp_cull_params cull;
     pcp_default_cull_params(&cull);
     cull.cull_mode = opt.cull_mode;
+    cull.match_mode = opt.match_mode;
     gpu->setCamera(cam, &cull);
     std::vector<pcp_pose> poses;
     for (const auto &k : keyframes) poses.push_back(k.pose);
     gpu->setKeyframes(poses);
-    if (gpu->size() == 1) {
-      // the reference credits a sample to EVERY map point within 10 um of it (radiusSearch, :571); the library to the
-      // sample's own point.  Say so when the map holds points that close together (duplicates of merged scans).
+    if (gpu->size() == 1 && opt.match_mode != PCP_MATCH_RADIUS) {
+      // the reference credits a sample to EVERY map point within 10 um of it (radiusSearch, :571); --matchBack roundtrip to
+      // the sample's own point.  Say so when the map holds points that close together (duplicates of merged scans).
       int64_t close = 0;
       if (pcp_close_pairs(gpu->device(0).get(), 2.5e-5, &close) != PCP_OK)  // a map with NaN / infinite points: no grid
         std::cerr << "Warning: " << pcp_last_error(gpu->device(0).get()) << "; the close-pair check is skipped." << std::endl;

@@ -99,7 +99,9 @@ class Colorizer {
  public:
   explicit Colorizer(Device &dev) : dev_(dev) {}
   // rgbCloud.cloudWithSmoothedColor after smoothColors: rgb (3 per input point) and the
-  // removePointsWithNoColor keep flag
+  // removePointsWithNoColor keep flag.  How samples are credited back to map points is the camera's cull parameters'
+  // match_mode (Device::setCamera): PCP_MATCH_RADIUS reproduces the reference's radiusSearch match-back in full
+  // (PointCloudProcessor.cpp:480-482,571-592), every map point within 10 um of a sample receiving it.
   void colorize(std::vector<uint8_t> &rgb, std::vector<uint8_t> &has) const {
     const size_t n = static_cast<size_t>(dev_.cloudSize());
     rgb.resize(3 * n);

@@ -44,6 +44,7 @@ class HipEngine:
     def configure(self, camera: dict | capi.Camera, cull: capi.CullParams | None = None):
         cam = camera if isinstance(camera, capi.Camera) else capi.camera_from_dict(camera)
         self.ctx.set_camera(cam, cull)
+        self.match_mode = capi.MATCH_ROUNDTRIP if cull is None else int(cull.match_mode)
 
     def upload_cloud(self, x, y, z):
         self.ctx.upload_cloud(x, y, z)
@@ -135,7 +136,11 @@ class PointCloudColorizer:
         Multi-rank: the keyframes are split into `chunks` groups (0 = chosen from the size of the maps); the
         all-reduce(MIN) of one group's depth maps (RCCL stream) overlaps the depth pass of the next group.
         local_smooth_radius > 0: smoothColorsWithLocalRegion over the finished colours (one rank only; the reference
-        leaves it off, PointCloudProcessor.cpp:597)."""
+        leaves it off, PointCloudProcessor.cpp:597).
+        capi.MATCH_RADIUS needs the whole map on one rank: with world > 1 it raises ValueError."""
+        if self.world > 1 and getattr(self.engine, "match_mode", None) == capi.MATCH_RADIUS:
+            raise ValueError("match_mode MATCH_RADIUS: a map point takes samples from its neighbours, which other ranks "
+                             "hold; run it on one rank holding the whole map")
         if local_smooth_radius and self.world > 1:
             raise ValueError("local_smooth_radius: the local colour smoothing runs on one rank holding the whole map "
                              "(smooth the gathered words with Context.colour_smooth_local_packed)")
