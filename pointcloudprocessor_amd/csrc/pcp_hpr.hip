@@ -40,7 +40,6 @@
 // pcp_hpr_stats) and classified hidden, as qhull classifies points on a facet ("coplanar points" are not vertices).
 // Exact duplicates: the lowest input index of a group of identical flipped points stands for the group.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <type_traits>
@@ -61,11 +60,8 @@ constexpr int kStatStride = 32, kStatCopies = 64;  // counters: block 0 + kStatC
 // The tallies of the passes every candidate goes through cost what they count: an atomic or three per candidate from every
 // wavefront of k_hpr_quick / k_hpr_radial / k_hpr_tilt were 11.5 of the 182 ms of kernels in a run of C3 and 9 % of the pass
 // (device-scope atomics execute beyond the L2; profiles/r05_hpr_tally_ab.log).  Now: visible / hidden are counted ONCE, from
-// the final states (k_hpr_writeback / k_hpr_set_bits, a ballot per wavefront); the work of the 16-lane passes (trial normals,
-// batches of point tests) goes into word kStatPacked of the copies as ONE atomic per wavefront: normals in bits 0..23,
-// batches above (a copy holds a 64th of one keyframe's tallies: < 2^24 normals).
-constexpr int kStatPacked = 5;
-constexpr int kStatPackedShift = 24;
+// the final states (k_hpr_writeback / k_hpr_set_bits, a ballot per wavefront), and the 16-lane passes do not count their work
+// (trial normals, batches of point tests) at all: even as ONE packed atomic per wavefront the counting was 6-15 % of the pass.
 constexpr double kHprBox = 1073741824.0;  // half-width of the initial box of trial normals (2^30 rad of tilt)
 constexpr double kPointSlack = 1.0e-15;  // |fl(n . (q - p)) - exact| <= 4.44e-16 sum |n_i (q_i - p_i)| (see test_range)
 
@@ -1056,7 +1052,7 @@ constexpr int kStatRadial = 22;  // block 0 of the tallies: length of that list
 // (tilt_add on an empty active set) and runs the ordinary traversal with THAT plane: a plane that has every other point
 // strictly on its inner side is a witness whatever produced it (same point test, same cell bound).  Whatever it cannot
 // certify stays undecided for k_hpr_tilt.  `stat_len`: the word of block 0 that holds the length of `todo`.
-template <bool kOneStep, bool kTally /* PCP_HPR_DEBUG: trial normals and batches counted (the counting is 6-15 % of the pass) */>
+template <bool kOneStep>
 __global__ __launch_bounds__(kHprBlock) void k_hpr_radial(HprArrays A, HprGrid G, uint8_t *__restrict__ state,
                                                           const int32_t *__restrict__ todo, unsigned long long *__restrict__ stats,
                                                           int32_t stat_len) {
@@ -1084,7 +1080,6 @@ __global__ __launch_bounds__(kHprBlock) void k_hpr_radial(HprArrays A, HprGrid G
   bool open = have && state[S.self] == kStUndecided;  // the row may still certify its candidate (k_hpr_quick may have settled it)
   const bool mine_to_write = open;
   bool hidden_dup = false;
-  unsigned long long batches = 0;
   const double two_rho = 2.0 * *G.rho_max;
   double abs_clear = abs_clear_of(S.nn_hi, two_rho);  // t below this: the point is strictly inside whatever its T (point_side)
   const int32_t cell = A.scell[S.self];
@@ -1117,7 +1112,6 @@ __global__ __launch_bounds__(kHprBlock) void k_hpr_radial(HprArrays A, HprGrid G
             }
           }
         }
-        if (kTally && in && open && base < k1 && rl == 0) batches += 1;
       }
     }
     const float worst = row_max16(best);
@@ -1159,7 +1153,6 @@ __global__ __launch_bounds__(kHprBlock) void k_hpr_radial(HprArrays A, HprGrid G
             bad = !point_cleared_rel(S.n, dx, dy, dz, t, T);
         }
       }
-      if (kTally && go && open && base < k1 && rl == 0) batches += 1;
       if (__ballot(bad || dup_lower)) {  // (rare: one ballot in front of the two row masks)
         if (row_mask(dup_lower)) {
           hidden_dup = true;
@@ -1220,17 +1213,7 @@ __global__ __launch_bounds__(kHprBlock) void k_hpr_radial(HprArrays A, HprGrid G
       }
     }
   }
-  unsigned long long work = 0;  // this row's trial normal (if it decided) and batches, packed
-  if (mine_to_write && rl == 0) {
-    const int32_t out = hidden_dup ? kStHidden : (open ? kStVisible : kStUndecided);
-    state[j] = static_cast<uint8_t>(out);
-    work = (out != kStUndecided ? 1ull : 0ull) + (batches << kStatPackedShift);
-  }
-  if (kTally) {  // the wavefront's four rows as one atomic
-    work += __shfl_xor(work, 16, 64);
-    work += __shfl_xor(work, 32, 64);
-    if (lane == 0 && work) atomicAdd(&stats[kStatStride * (1 + (blockIdx.x % kStatCopies)) + kStatPacked], work);
-  }
+  if (mine_to_write && rl == 0) state[j] = static_cast<uint8_t>(hidden_dup ? kStHidden : (open ? kStVisible : kStUndecided));
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1252,10 +1235,6 @@ __global__ __launch_bounds__(kHprBlock) void k_hpr_radial(HprArrays A, HprGrid G
 constexpr int kStatTilt = 23;  // block 0 of the tallies: length of k_hpr_tilt's list
 constexpr int kStatOneStep = 30;   // block 0: length of the list of k_hpr_radial<true>
 constexpr int kStatTiltCont = 29;  // block 0: length of the list of searches the 16-lane rows handed on to a wavefront each
-// PCP_HPR_DEBUG only: searches by the binary logarithm of their round trips [0..15], the round trips of each class [16..31], and
-// per wavefront the rows' round trips summed [32] against (rows x the longest row's) [33] (what lockstep rows cost),
-// wavefronts [34], rows of cell tests [35]
-__device__ unsigned long long g_tilt_hist[40];
 // The state of a search lives in LDS, one record per row (every lane of the row writes the same values, so each thread
 // reads what it wrote itself): carried in registers through the eight loop levels below it cost a copy per level -- the
 // first build of this kernel took 263 VGPRs (one wavefront per SIMD) for ~100 registers of state.
@@ -1307,7 +1286,7 @@ struct TiltCont {
 constexpr int kTiltBlock = PCP_TILT_BLOCK;
 // kRow = 16: four searches per wavefront, from the list `todo`, each with a budget of round trips; kRow = 64: one search per
 // wavefront, from the records `cont` the first launch wrote (budget: none).
-template <bool kDebug, int kRow>
+template <int kRow>
 __global__ __launch_bounds__(kTiltBlock) __attribute__((amdgpu_waves_per_eu(PCP_TILT_WPE, PCP_TILT_WPE))) void k_hpr_tilt(
     HprArrays A, HprGrid G, uint8_t *__restrict__ state, const int32_t *__restrict__ todo, unsigned long long *__restrict__ stats,
     int32_t wide_window, int32_t *__restrict__ left_over, TiltCont *__restrict__ cont, int32_t budget) {
@@ -1338,7 +1317,6 @@ __global__ __launch_bounds__(kTiltBlock) __attribute__((amdgpu_waves_per_eu(PCP_
     }
     return v;
   };
-  const int32_t n_coarse = G.cgw * G.cgh;
   const double two_rho = 2.0 * *G.rho_max;
   for (int32_t u0 = static_cast<int32_t>(blockIdx.x) * kRowsPerBlock + static_cast<int32_t>(threadIdx.x >> 6) * kRowsPerWave; u0 < count;
        u0 += rows_total) {  // (u0: the first row of this wavefront; uniform over the wavefront)
@@ -1381,9 +1359,8 @@ __global__ __launch_bounds__(kTiltBlock) __attribute__((amdgpu_waves_per_eu(PCP_
     bool changed = false;   // the trial plane moved during this pass
     int outcome = 0;        // 0 none, 1 visible, 2 hidden duplicate, 3 empty (a, b, c below), 4 gave up, 5 handed on (budget)
     int32_t ca = -1, cb = -1, cc = -1;
-    int steps = 0, passes = 0, why4 = 0, wide = 0, last_wn = 0;
+    int steps = 0;
     int32_t trips = 0;      // round trips of this row so far: batches of point tests + rows of cell tests (row-uniform)
-    unsigned long long batches = 0, csteps = 0;  // (tallies, lane 0 of the row; csteps: PCP_HPR_DEBUG only)
     auto stop = [&](int why) {
       outcome = why;
       run = false;
@@ -1423,7 +1400,6 @@ __global__ __launch_bounds__(kTiltBlock) __attribute__((amdgpu_waves_per_eu(PCP_
         cc = qid;
         stop(3);
       } else {
-        why4 = 2;
         stop(4);
       }
     };
@@ -1441,7 +1417,6 @@ __global__ __launch_bounds__(kTiltBlock) __attribute__((amdgpu_waves_per_eu(PCP_
           dy = A.sy[k] - p.y;
           dz = A.sz[k] - p.z;
         }
-        if (kDebug && on && rl == 0) batches += 1;
         for (int guard = 0;; ++guard) {
           TILT_FENCE();
           const Vec3d nn = {R.n[0], R.n[1], R.n[2]};
@@ -1478,7 +1453,6 @@ __global__ __launch_bounds__(kTiltBlock) __attribute__((amdgpu_waves_per_eu(PCP_
             TILT_FENCE();
             const int32_t last_id = R.last_id;
             if (qid == last_id || ++steps > kTiltMaxSteps || guard > 24) {
-              why4 = qid == last_id ? 0 : 1;
               stop(4);
             } else {
               R.last_id = qid;
@@ -1495,11 +1469,7 @@ __global__ __launch_bounds__(kTiltBlock) __attribute__((amdgpu_waves_per_eu(PCP_
     const int32_t cell = A.scell[self];
     const int32_t ci = cell % G.gw, cj = cell / G.gw;
     for (int pass = 0; __ballot(run); ++pass) {
-      if (run && pass >= kTiltMaxPasses) {
-        why4 = 3;
-        stop(4);
-      }
-      if (run) ++passes;
+      if (run && pass >= kTiltMaxPasses) stop(4);
       // the 3 x 3 cells around the candidate's own -- that is where the binding half-planes are -- until the plane rests there
       bool again = run;
       for (int nit = 0; __ballot(again); ++nit) {
@@ -1511,10 +1481,7 @@ __global__ __launch_bounds__(kTiltBlock) __attribute__((amdgpu_waves_per_eu(PCP_
           const int32_t c0n = (in ? rj : cj) * G.gw + max(ci - 1, 0), c1n = (in ? rj : cj) * G.gw + min(ci + 1, G.gw - 1);
           test_points(in && again, A.cstart[c0n], A.cstart[c1n + 1]);
         }
-        if (run && again && changed && nit >= 12) {
-          why4 = 3;
-          stop(4);
-        }
+        if (run && again && changed && nit >= 12) stop(4);
         again = again && run && changed;
       }
       // (rows still running: the near cells accept the plane, changed == false)
@@ -1552,17 +1519,12 @@ __global__ __launch_bounds__(kTiltBlock) __attribute__((amdgpu_waves_per_eu(PCP_
       const double r_upper = (big ? G.r_coarse : G.r_mid) + kCell4Slack;
       const bool has_window = run && W.i0 <= W.i1 && W.j0 <= W.j1;
       const int32_t ww = has_window ? W.i1 - W.i0 + 1 : 1, wn = has_window ? ww * (W.j1 - W.j0 + 1) : 0;
-      if (kDebug) {
-        if (wn > 256) ++wide;
-        if (run) last_wn = wn;
-      }
       for (int32_t cbk = 0; __ballot(run && cbk < wn); cbk += kRow) {
         if (run && cbk < wn && trips >= budget) stop(5);
         if (run && cbk < wn) ++trips;
         const int32_t t = cbk + rl;
         const int32_t tq = small_div(t, ww);
         const int32_t Ci = W.i0 + (t - tq * ww), Cj = W.j0 + tq;
-        if (kDebug && run && cbk < wn && rl == 0) ++csteps;
         const int32_t C = (run && t < wn) ? Cj * ugw + Ci : -1;
         bool copen = false;
         if (C >= 0) {
@@ -1579,7 +1541,6 @@ __global__ __launch_bounds__(kTiltBlock) __attribute__((amdgpu_waves_per_eu(PCP_
             if (go_c && run && q4 < fsteps && trips >= budget) stop(5);
             const bool go_q = go_c && run && q4 < fsteps;
             if (go_q) ++trips;
-            if (kDebug && go_q && rl == 0) ++csteps;
             const int fidx = q4 * kRow + rl;
             const int32_t fi = ((go_q ? Cci : 0) << eshift) + (fidx & ((1 << eshift) - 1)), fj = ((go_q ? Ccj : 0) << eshift) + (fidx >> eshift);
             bool fopen = false;
@@ -1616,11 +1577,7 @@ __global__ __launch_bounds__(kTiltBlock) __attribute__((amdgpu_waves_per_eu(PCP_
           tetra_contains_filtered(p, load_point(A, ca), load_point(A, cb), load_point(A, cc)))
         out = kStHidden;
     }
-    unsigned long long work = 0;
     if (have && rl == 0) {
-      unsigned long long *mine = stats + kStatStride * (1 + (blockIdx.x % kStatCopies));
-      (void)mine;
-      work = static_cast<unsigned long long>(steps + 1) + (((batches * kRow + 63ull) / 64ull) << kStatPackedShift);
       if (out != kStUndecided) {
         state[j] = static_cast<uint8_t>(out);
       } else if (kRow == 16 && outcome == 5) {
@@ -1636,46 +1593,6 @@ __global__ __launch_bounds__(kTiltBlock) __attribute__((amdgpu_waves_per_eu(PCP_
         // what this pass gives up on (a handful per keyframe) goes straight onto the list of the polygon search
         left_over[atomicAdd(&stats[kStatSearch], 1ull)] = j;
       }
-      if (kDebug) {  // PCP_HPR_DEBUG: what became of the searches (words 9.. of the copies; nothing else uses them)
-        if (outcome == 4)
-          printf("hpr: tilt%d gave up on %d: why %d passes %d steps %d batches %llu |s| %.3g na %d window %d coarse cells of %d, p = (%.17g, %.17g, %.17g)\n",
-                 kRow, j, why4, passes, steps, batches, sqrt(R.sx * R.sx + R.sy * R.sy), R.na, last_wn, n_coarse, p.x, p.y, p.z);
-        atomicAdd(&mine[9], 1ull);
-        atomicAdd(&mine[10 + min(outcome, 4)], 1ull);  // 10 none 11 visible 12 duplicate 13 empty 14 gave up / handed on
-        if (outcome == 3 && out == kStHidden) atomicAdd(&mine[15], 1ull);
-        if (outcome == 4) atomicAdd(&mine[16 + min(why4, 3)], 1ull);  // 16 same point again 17 step cap 18 no conclusion 19 pass cap
-        atomicAdd(&mine[20], static_cast<unsigned long long>(passes));
-        atomicAdd(&mine[21], static_cast<unsigned long long>(steps));
-        atomicAdd(&mine[22], batches);
-        atomicMax(&mine[28], batches);
-        if (outcome == 5) atomicAdd(&mine[29], 1ull);
-        atomicAdd(&mine[30], static_cast<unsigned long long>(wide));
-        const int hb = trips ? min(31 - __clz(trips), 15) : 0;
-        atomicAdd(&g_tilt_hist[hb], 1ull);
-        atomicAdd(&g_tilt_hist[16 + hb], static_cast<unsigned long long>(trips));
-        atomicAdd(&g_tilt_hist[35], csteps);
-      }
-    }
-    if (kDebug) {
-      if (kRow == 16) {
-        work += __shfl_xor(work, 16, 64);
-        work += __shfl_xor(work, 32, 64);
-      }
-      if (lane == 0 && work) atomicAdd(&stats[kStatStride * (1 + (blockIdx.x % kStatCopies)) + kStatPacked], work);
-    }
-    if (kDebug) {
-      unsigned long long tsum = 0, tmax = 0;
-#pragma unroll
-      for (int r4 = 0; r4 < kRowsPerWave; ++r4) {
-        const unsigned long long tr = static_cast<unsigned long long>(__shfl(trips, r4 * kRow, 64));
-        tsum += tr;
-        tmax = max(tmax, tr);
-      }
-      if (lane == 0) {
-        atomicAdd(&g_tilt_hist[32], tsum);
-        atomicAdd(&g_tilt_hist[33], kRowsPerWave * tmax);
-        atomicAdd(&g_tilt_hist[34], 1ull);
-      }
     }
   }
 }
@@ -1685,8 +1602,7 @@ __global__ __launch_bounds__(kTiltBlock) __attribute__((amdgpu_waves_per_eu(PCP_
 #undef TILT_FENCE
 
 // stats: [0] hidden [1] visible (both from the final states) [2] - [3] trial normals [4] batches of 64 point tests (polygon and exact
-// searches; the 16-lane passes': packed in [5] = kStatPacked of the copies)
-// [6] unresolved [7] exact predicate evaluations [8] length of the list for k_hpr_exact
+// searches only) [5] - [6] unresolved [7] exact predicate evaluations [8] length of the list for k_hpr_exact
 // The candidates the passes in front left undecided, as a list (any order): the searches then run on wavefronts that all have
 // work.  Launched over every candidate, nine wavefronts in ten found theirs decided and left after one load -- and the
 // dispatcher could not refill the slots as fast as they emptied: 1.15 resident wavefronts per SIMD of the 3 the registers
@@ -1762,7 +1678,7 @@ constexpr int32_t kHprDecideGrid = 65536;
 constexpr int32_t kHprTiltGrid = 4096;  // workgroups of k_hpr_tilt (16 rows each) striding over its list
 constexpr int32_t kHprOneStepGrid = 1 << 20;  // (k_hpr_radial does not stride: its grid covers the list's upper bound, extra workgroups leave at once)
 constexpr int32_t kHprTilt64Grid = 768;  // workgroups of its continuation (4 rows of 64 each): every resident slot at 3 wavefronts per SIMD
-constexpr int32_t kTiltBudget = 128;     // round trips of a search on a row of 16 lanes before it is handed on (PCP_TILT_BUDGET; 32: pass +12 %, 48-128 and never: within 1 %)
+constexpr int32_t kTiltBudget = 128;     // round trips of a search on a row of 16 lanes before it is handed on (measured: 32: pass +12 %, 48-128 and never: within 1 %)
 #ifndef PCP_DECIDE_WPE
 #define PCP_DECIDE_WPE 2  // 214 VGPRs, nothing spilled; at 3 wavefronts per SIMD (168 VGPRs) 63 registers went to scratch: hull pass 0.312 -> 0.285 s once the searches ran from a list
 #endif
@@ -2129,7 +2045,6 @@ int hpr_finish(pcp_context *ctx, HprLane &L, bool timed) {
   // The one host wait of a keyframe: polling the sequence number k_hpr_publish writes last (an error on the stream ends it)
   const volatile HprCounts *hc = static_cast<const volatile HprCounts *>(L.readback);
   {
-    const auto t_wait = std::chrono::steady_clock::now();
     for (uint64_t spins = 0; hc->seq != L.seq; ++spins) {
       __builtin_ia32_pause();
       if ((spins & 0xfffffu) == 0xfffffu) {  // now and then: is the stream still alive?
@@ -2142,7 +2057,6 @@ int hpr_finish(pcp_context *ctx, HprLane &L, bool timed) {
       }
     }
     __sync_synchronize();
-    ctx->hpr_host_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_wait).count();
   }
   const int64_t m64 = static_cast<int64_t>(hc->count);
   unsigned long long hb[4] = {~hc->inv_amin, hc->amax, ~hc->inv_bmin, hc->bmax};  // the minima were kept as maxima of the inverted keys
@@ -2214,8 +2128,7 @@ int hpr_finish(pcp_context *ctx, HprLane &L, bool timed) {
   float4 *cell4 = reinterpret_cast<float4 *>(crho + off4), *Cell4 = cell4 + nf, *Mid4 = Cell4 + nc;
   hipLaunchKernelGGL(k_hpr_zero, dim3(static_cast<uint32_t>(std::min<int64_t>(div_up(static_cast<int64_t>(2 * nf + int_words), kHprBlock), 1024))),
                      dim3(kHprBlock), 0, stream, reinterpret_cast<unsigned long long *>(crho), static_cast<int64_t>(2 * nf + int_words));
-  // PCP_HPR_QUICK=0 / PCP_HPR_RADIAL=0: without the two passes in front of the search (results identical; the place of a
-  // representative needs 26 bits)
+  // PCP_HPR_QUICK=0: without the quick certificate (results identical; the place of a representative needs 26 bits)
   const char *qe = std::getenv("PCP_HPR_QUICK");
   const bool quick = !(qe && qe[0] == '0') && m < (1 << 26);
   unsigned long long *crep = quick ? crep_all : nullptr;
@@ -2232,103 +2145,50 @@ int hpr_finish(pcp_context *ctx, HprLane &L, bool timed) {
                        reinterpret_cast<unsigned long long *>(crho), crep);
     hipLaunchKernelGGL(k_hpr_cells, dim3(hpr_blocks(std::max(n_fine, n_coarse))), dim3(kHprBlock), 0, stream, G,
                        reinterpret_cast<const unsigned long long *>(crho), cdir, Crho, Cdir, stats + 28, cell4, Cell4, Mid4);
-    // PCP_HPR_RADIAL=0: every candidate through k_hpr_decide (results identical)
-    const char *re = std::getenv("PCP_HPR_RADIAL");
     if (quick && !force_exact)
       hipLaunchKernelGGL(k_hpr_quick, dim3(hpr_blocks(m)), dim3(kHprBlock), 0, stream, A, G, L.state.p, stats);
     else
       PCP_HIP_TRY(ctx, hipMemsetAsync(L.state.p, kStUndecided, sm, stream));
-    if (!(force_exact || (re && re[0] == '0'))) {
+    if (!force_exact) {
       const int32_t *radial_todo = nullptr;
       if (quick) {  // rows for the candidates the quick certificate left, and only for them
         hipLaunchKernelGGL(k_hpr_list, dim3(static_cast<uint32_t>(div_up(m, kHprBlock * kHprListPer))), dim3(kHprBlock), 0, stream,
                            L.state.p, m, undecided, stats + kStatRadial);  // (`undecided` is free until the searches)
         radial_todo = undecided;
       }
-      const bool tally = std::getenv("PCP_HPR_DEBUG") != nullptr;  // (the 16-lane passes count their work only then)
-      hipLaunchKernelGGL((tally ? k_hpr_radial<false, true> : k_hpr_radial<false, false>), dim3(static_cast<uint32_t>(div_up(m, kHprBlock / 16))),
-                         dim3(kHprBlock), 0, stream, A, G, L.state.p, radial_todo, stats, static_cast<int32_t>(kStatRadial));
-      // PCP_HPR_ONESTEP=0: without the once-tilted plane for what the radial plane failed (results identical)
-      const char *oe = std::getenv("PCP_HPR_ONESTEP");
-      if (!(oe && oe[0] == '0')) {
-        hipLaunchKernelGGL(k_hpr_list, dim3(static_cast<uint32_t>(div_up(m, kHprBlock * kHprListPer))), dim3(kHprBlock), 0, stream,
-                           L.state.p, m, todo, stats + kStatOneStep);
-        hipLaunchKernelGGL((tally ? k_hpr_radial<true, true> : k_hpr_radial<true, false>),
-                           dim3(static_cast<uint32_t>(std::min<int64_t>(div_up(m, kHprBlock / 16), kHprOneStepGrid))),
-                           dim3(kHprBlock), 0, stream, A, G, L.state.p, todo, stats, static_cast<int32_t>(kStatOneStep));
-      }
-    }
-    std::vector<uint8_t> dbg_before;
-    if (std::getenv("PCP_HPR_DEBUG")) {  // what the two passes in front left to the searches
-      dbg_before.resize(sm);
-      (void)hipMemcpyAsync(dbg_before.data(), L.state.p, sm, hipMemcpyDeviceToHost, stream);
-      (void)hipStreamSynchronize(stream);
-    }
-    // PCP_HPR_TILT=0: without the least-norm searches in front of the polygon search (results identical)
-    const char *te = std::getenv("PCP_HPR_TILT");
-    if (!force_exact && !(te && te[0] == '0')) {
-      const bool dbg = std::getenv("PCP_HPR_DEBUG") != nullptr;
-      // PCP_TILT_BUDGET: round trips a search gets on a row of 16 lanes before it is handed on to a wavefront of its own
-      // (0: never handed on -- the form of round 4)
-      const char *be = std::getenv("PCP_TILT_BUDGET");
-      int32_t budget = be ? std::atoi(be) : kTiltBudget;
-      if (budget <= 0) budget = INT32_MAX;
+      hipLaunchKernelGGL(k_hpr_radial<false>, dim3(static_cast<uint32_t>(div_up(m, kHprBlock / 16))), dim3(kHprBlock), 0, stream, A, G,
+                         L.state.p, radial_todo, stats, static_cast<int32_t>(kStatRadial));
+      // the once-tilted plane for what the radial plane failed
+      hipLaunchKernelGGL(k_hpr_list, dim3(static_cast<uint32_t>(div_up(m, kHprBlock * kHprListPer))), dim3(kHprBlock), 0, stream,
+                         L.state.p, m, todo, stats + kStatOneStep);
+      hipLaunchKernelGGL(k_hpr_radial<true>, dim3(static_cast<uint32_t>(std::min<int64_t>(div_up(m, kHprBlock / 16), kHprOneStepGrid))),
+                         dim3(kHprBlock), 0, stream, A, G, L.state.p, todo, stats, static_cast<int32_t>(kStatOneStep));
+      // the least-norm searches on rows of 16 lanes; a search still running after kTiltBudget round trips is handed on to a
+      // wavefront of its own
       PCP_HIP_TRY(ctx, L.cont.ensure((sizeof(TiltCont) / sizeof(double)) * sm + 16));
       TiltCont *cont = reinterpret_cast<TiltCont *>(L.cont.p);
-      auto debug_hist = [&](const char *what, int rows_per_wave) {
-        if (!dbg) return;
-        (void)hipStreamSynchronize(stream);
-        unsigned long long hist[40] = {0}, zero[40] = {0};
-        (void)hipMemcpyFromSymbol(hist, HIP_SYMBOL(g_tilt_hist), sizeof(hist));
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_tilt_hist), zero, sizeof(zero));
-        fprintf(stderr, "hpr: tilt (%s): searches by log2(round trips):", what);
-        for (int b = 0; b < 16; ++b) fprintf(stderr, " %llu", hist[b]);
-        fprintf(stderr, "\nhpr: tilt (%s): round trips of each class:", what);
-        for (int b = 0; b < 16; ++b) fprintf(stderr, " %llu", hist[16 + b]);
-        fprintf(stderr, "\nhpr: tilt (%s): %llu wavefronts, rows' round trips (point batches + cell rows) %llu of %llu row slots (%d x the longest row); cell rows %llu\n",
-                what, hist[34], hist[32], hist[33], rows_per_wave, hist[35]);
-      };
       hipLaunchKernelGGL(k_hpr_list, dim3(static_cast<uint32_t>(div_up(m, kHprBlock * kHprListPer))), dim3(kHprBlock), 0, stream,
                          L.state.p, m, todo, stats + kStatTilt);
       // (`cell`, the candidates' cells in arrival order, is free after k_hpr_scatter: the list of what the searches give up on)
-      hipLaunchKernelGGL((dbg ? k_hpr_tilt<true, 16> : k_hpr_tilt<false, 16>),
+      hipLaunchKernelGGL(k_hpr_tilt<16>,
                          dim3(static_cast<uint32_t>(std::min<int64_t>(div_up(m, kTiltBlock / 16), kHprTiltGrid * (kHprBlock / kTiltBlock)))),
-                         dim3(kTiltBlock), 0, stream, A, G, L.state.p, todo, stats, kTiltWideWindow, cell, cont, budget);
-      debug_hist("rows of 16", 4);
-      if (budget != INT32_MAX) {
-        hipLaunchKernelGGL((dbg ? k_hpr_tilt<true, 64> : k_hpr_tilt<false, 64>),
-                           dim3(static_cast<uint32_t>(std::min<int64_t>(div_up(m, kTiltBlock / 64), kHprTilt64Grid * (kHprBlock / kTiltBlock)))),
-                           dim3(kTiltBlock), 0, stream, A, G, L.state.p, static_cast<const int32_t *>(nullptr), stats, kTiltWideWindow, cell,
-                           cont, INT32_MAX);
-        debug_hist("rows of 64", 1);
-      }
+                         dim3(kTiltBlock), 0, stream, A, G, L.state.p, todo, stats, kTiltWideWindow, cell, cont, kTiltBudget);
+      hipLaunchKernelGGL(k_hpr_tilt<64>,
+                         dim3(static_cast<uint32_t>(std::min<int64_t>(div_up(m, kTiltBlock / 64), kHprTilt64Grid * (kHprBlock / kTiltBlock)))),
+                         dim3(kTiltBlock), 0, stream, A, G, L.state.p, static_cast<const int32_t *>(nullptr), stats, kTiltWideWindow, cell,
+                         cont, INT32_MAX);
     }
-    // the list of the 64-lane search: what k_hpr_tilt gave up on (it appended them itself: no third listing launch), or, without
-    // that pass, every candidate still undecided
-    const bool tilted = !force_exact && !(te && te[0] == '0');
+    // the list of the 64-lane search: what k_hpr_tilt gave up on (it appended them itself: no third listing launch), or, with
+    // force-exact, every candidate
     const int32_t *decide_todo = cell;
-    if (!tilted) {
+    if (force_exact) {
       hipLaunchKernelGGL(k_hpr_list, dim3(static_cast<uint32_t>(div_up(m, kHprBlock * kHprListPer))), dim3(kHprBlock), 0, stream,
                          L.state.p, m, todo, stats + kStatSearch);
       decide_todo = todo;
     }
     // (after k_hpr_tilt a few dozen candidates are left: a grid of 64 K one-wavefront workgroups that find nothing costs 15 us)
-    hipLaunchKernelGGL(k_hpr_decide, dim3(static_cast<uint32_t>(std::min<int64_t>(m, tilted ? 2048 : kHprDecideGrid))), dim3(64),
+    hipLaunchKernelGGL(k_hpr_decide, dim3(static_cast<uint32_t>(std::min<int64_t>(m, force_exact ? kHprDecideGrid : 2048))), dim3(64),
                        0, stream, A, G, L.state.p, decide_todo, undecided, stats, force_exact ? 1 : 0);
-    if (!dbg_before.empty()) {
-      std::vector<uint8_t> after(sm);
-      (void)hipMemcpyAsync(after.data(), L.state.p, sm, hipMemcpyDeviceToHost, stream);
-      (void)hipStreamSynchronize(stream);
-      size_t und = 0, to_vis = 0, to_hid = 0, left = 0;
-      for (size_t k = 0; k < sm; ++k)
-        if (dbg_before[k] == kStUndecided) {
-          ++und;
-          if (after[k] == kStVisible) ++to_vis;
-          else if (after[k] == kStHidden) ++to_hid;
-          else ++left;
-        }
-      fprintf(stderr, "hpr: %d candidates, %zu searched: %zu visible, %zu hidden, %zu to the exact path\n", m, und, to_vis, to_hid, left);
-    }
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
   {
@@ -2351,32 +2211,6 @@ int hpr_finish(pcp_context *ctx, HprLane &L, bool timed) {
   }
   ctx->hpr_stats[8] = n_fine;
   ctx->hpr_stats_pending = true;  // [0..7] are summed from the device tallies when pcp_hpr_stats is called
-  if (std::getenv("PCP_HPR_DEBUG")) {
-    unsigned long long dbg[24];
-    (void)hipMemcpy(dbg, stats, sizeof(dbg), hipMemcpyDeviceToHost);
-    // why candidates left the floating-point path: a point within round-off of the last trial plane / a simplex the
-    // filter could not sign / an emptied polygon that still had an edge of the initial box / searches that gave up
-    // (inner-loop guard, restart cap, non-contiguous clip, more than 64 polygon vertices)
-    {
-      std::vector<unsigned long long> all(kStatWords);
-      (void)hipMemcpy(all.data(), stats, kStatWords * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-      unsigned long long w[14] = {0}, bmax = 0, big = 0, wide = 0, bigsum = 0;
-      for (int c = 1; c <= kStatCopies; ++c) {
-        for (int k = 0; k < 14; ++k) w[k] += all[static_cast<size_t>(c * kStatStride + 9 + k)];
-        bmax = std::max(bmax, all[static_cast<size_t>(c * kStatStride + 28)]);
-        big += all[static_cast<size_t>(c * kStatStride + 29)];
-        wide += all[static_cast<size_t>(c * kStatStride + 30)];
-        bigsum += all[static_cast<size_t>(c * kStatStride + 31)];
-      }
-      (void)bigsum;
-      fprintf(stderr, "hpr: tilt: longest search %llu batches; %llu searches handed on to a wavefront each; %llu passes with a window of > 256 upper cells\n",
-              bmax, big, wide);
-      fprintf(stderr, "hpr: tilt: %llu searches: visible %llu duplicate %llu empty %llu (certified %llu) gave up %llu (same point %llu, step cap %llu, "
-              "no conclusion %llu, pass cap %llu); passes %llu steps %llu batches %llu\n", w[0], w[2], w[3], w[4], w[6], w[5], w[7], w[8], w[9],
-              w[10], w[11], w[12], w[13]);
-    }
-    fprintf(stderr, "hpr: to the exact path: uncertain_left %llu tetra_filter %llu box_cert %llu fail: guard %llu restarts %llu noncontig %llu overflow %llu\n", dbg[10], dbg[11], dbg[12], dbg[14], dbg[15], dbg[16], dbg[17]);
-  }
   return PCP_OK;
 }
 
@@ -2400,8 +2234,6 @@ int hpr_run_range(pcp_context *ctx, int32_t f0, int32_t f1, int32_t lanes, const
   int rc = PCP_OK;
   if (!ctx->hpr_fork) PCP_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->hpr_fork, hipEventDisableTiming));
   LaunchTimer t(ctx, PCP_K_HPR);  // the whole pass as one bracket on the context's stream
-  ctx->hpr_host_wait_s = 0.0;
-  const auto t_pass = std::chrono::steady_clock::now();
   PCP_HIP_TRY(ctx, hipEventRecord(ctx->hpr_fork, ctx->stream));  // (nothing is queued on a lane yet: an early return is safe)
   // every lane holds the scratch of a keyframe whose every point may be a candidate (80 B per map point): where the device
   // has no room for all of them, fewer keyframes are in flight
@@ -2441,13 +2273,11 @@ int hpr_run_range(pcp_context *ctx, int32_t f0, int32_t f1, int32_t lanes, const
   int32_t turn = 0;
   for (int32_t f = f0; f < f1 && rc == PCP_OK; ++f) {
     int32_t pick = -1;
-    const auto t_wait = std::chrono::steady_clock::now();
     for (uint32_t spins = 0; pick < 0 && spins < (1u << 22); ++spins) {
       for (int32_t k = 0; k < lanes && pick < 0; ++k)
         if (arrived(ctx->hpr_lane[(turn + k) % lanes])) pick = (turn + k) % lanes;
       if (pick < 0) __builtin_ia32_pause();
     }
-    ctx->hpr_host_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_wait).count();
     if (pick < 0) pick = turn;  // nothing for a long while: hpr_finish waits for this lane and looks after its stream
     HprLane &L = ctx->hpr_lane[pick];
     turn = (pick + 1) % lanes;
@@ -2481,9 +2311,6 @@ int hpr_run_range(pcp_context *ctx, int32_t f0, int32_t f1, int32_t lanes, const
     }
   }
   for (int32_t k = 0; k < pcp_context::kHprMaxLanes; ++k) ctx->hpr_lane[k].busy = false;
-  if (std::getenv("PCP_HPR_HOST_TIMING"))
-    fprintf(stderr, "hpr: pass of %d keyframes on %d lanes: host %.1f ms, of which %.1f ms waiting for counts\n", f1 - f0, lanes,
-            std::chrono::duration<double>(std::chrono::steady_clock::now() - t_pass).count() * 1e3, ctx->hpr_host_wait_s * 1e3);
   return rc;
 }
 
@@ -2513,13 +2340,8 @@ int pcp_hpr_stats(pcp_context *ctx, int64_t out[10]) {
     unsigned long long hs[9];
     for (int k = 0; k < 9; ++k) {
       hs[k] = hall[static_cast<size_t>(k)];
-      if (k != 8 && k != kStatPacked)
+      if (k != 8)
         for (int c = 1; c <= kStatCopies; ++c) hs[k] += hall[static_cast<size_t>(c * kStatStride + k)];
-    }
-    for (int c = 1; c <= kStatCopies; ++c) {  // the 16-lane passes' work, packed (kStatPacked)
-      const unsigned long long w = hall[static_cast<size_t>(c * kStatStride + kStatPacked)];
-      hs[3] += w & ((1ull << kStatPackedShift) - 1ull);
-      hs[4] += w >> kStatPackedShift;
     }
     ctx->hpr_stats[0] = static_cast<int64_t>(hs[1]);  // visible, as finally classified (the exact path moved its points out of "undecided")
     ctx->hpr_stats[1] = static_cast<int64_t>(hs[0]);  // hidden

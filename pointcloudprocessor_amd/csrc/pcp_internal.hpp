@@ -262,7 +262,6 @@ struct pcp_context {
   static constexpr int kHprMaxLanes = 8;
   pcp::HprLane hpr_lane[kHprMaxLanes];
   int32_t hpr_last_lane = 0;  // whose tallies pcp_hpr_stats reads
-  double hpr_host_wait_s = 0.0;  // host time of the last whole-run pass spent waiting for the keyframes' counts (PCP_HPR_DEBUG prints it)
   hipEvent_t hpr_fork = nullptr, hpr_join[kHprMaxLanes] = {};
   pcp::DevBuf<uint32_t> hull_bits;  // whole run: uint32[(F + 31) / 32][n], bit f & 31 of word (f >> 5, j) = point j (Morton
                                     // order) is a hull vertex of keyframe f

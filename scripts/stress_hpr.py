@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Randomised stress of PCP_CULL_HPR (not collected by pytest): seeds x cloud sizes x cameras x keyframes x flip radii, the
-GPU hull (quick certificate, radial pre-pass, search, exact path) against the oracle's exact quickhull; also with the two
-passes switched off.  Prints one line per case; exit 1 on the first mismatch.   python scripts/stress_hpr.py [cases]"""
+GPU hull (quick certificate, radial pre-pass, search, exact path) against the oracle's exact quickhull; also without the
+quick certificate (PCP_HPR_QUICK=0).  Prints one line per case; exit 1 on the first mismatch.   python scripts/stress_hpr.py [cases]"""
 import os
 import sys
 
@@ -45,7 +45,6 @@ def main():
             refs[f], _ = oc.hpr_frame(ocam, w2c, x, y, z, radius)
         for variant in (0, 1):
             os.environ["PCP_HPR_QUICK"] = "1" if variant == 0 else "0"
-            os.environ["PCP_HPR_RADIAL"] = "1" if variant == 0 else "0"
             with capi.Context(0) as ctx:
                 ctx.set_camera(capi.camera_from_dict(cam), cull)
                 ctx.upload_cloud(x, y, z)
@@ -54,7 +53,7 @@ def main():
                     keep, _, kept = ctx.cull_frame(f)
                     st = ctx.hpr_stats()
                     ok = np.array_equal(keep, refs[f])
-                    print(f"case {case:3d} cam={camname:4s} n={n:8d} R={radius:9.0f} kf={f:3d} passes={'on ' if variant == 0 else 'off'} "
+                    print(f"case {case:3d} cam={camname:4s} n={n:8d} R={radius:9.0f} kf={f:3d} quick={'on ' if variant == 0 else 'off'} "
                           f"candidates={st['candidates']:8d} kept={kept:8d} exact={st['exact_path']:4d} unresolved={st['unresolved']} "
                           f"{'ok' if ok else 'MISMATCH'}", flush=True)
                     if not ok:

@@ -324,8 +324,9 @@ def test_whole_run_bits_in_chunks_of_keyframes(gpu_ctx_factory, oracle):
 def test_whole_run_bits_do_not_depend_on_the_keyframes_in_flight(gpu_ctx_factory, oracle, monkeypatch, lanes):
     """The whole-run hull pass keeps several keyframes in flight on lanes of their own (PCP_HPR_LANES, default 4): with one,
     three (ranges shorter than the lanes, a count that does not divide) and eight lanes the colours are the oracle's, the
-    per-keyframe verdicts read back from the pass's bits equal pcp_cull_frame on a context that never ran the pass, and the
-    16-lane search switched off (PCP_HPR_TILT=0) changes nothing."""
+    per-keyframe verdicts read back from the pass's bits equal pcp_cull_frame on a context that never ran the pass, and
+    sending every candidate to the exact path (PCP_HPR_FORCE_EXACT=1: no quick certificate, radial pass or search in front
+    of it) changes nothing."""
     from pointcloudprocessor_amd import capi, synth
 
     cd = synth.camera_dict("tiny")
@@ -360,7 +361,7 @@ def test_whole_run_bits_do_not_depend_on_the_keyframes_in_flight(gpu_ctx_factory
     for f in (0, 1, 5, F - 1):
         a, b = ctx.cull_frame(f), fresh.cull_frame(f)
         assert np.array_equal(a[0], b[0]) and a[2] == b[2], f
-    monkeypatch.setenv("PCP_HPR_TILT", "0")
+    monkeypatch.setenv("PCP_HPR_FORCE_EXACT", "1")
     again = ctx.colorize()
     assert np.array_equal(again["rgb"], got["rgb"]) and np.array_equal(again["has"], got["has"])
     ctx.close()
