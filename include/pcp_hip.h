@@ -42,7 +42,8 @@ extern "C" {
                                 with its trailing outlier removal over a chunked voxel dilation); pcp_hpr_stats reports
                                 candidates = -1 after a call served from the whole-run bits;
                                 entry points added, no layout changed: pcp_colour_smooth_local / _packed (PCP_K_COLOUR_SMOOTH = 12,
-                                PCP_K_COUNT 13) */
+                                PCP_K_COUNT 13);
+                                entry points added, no layout changed: pcp_upload_image_jpeg / _async (pcp_jpeg_header) */
 
 #define PCP_OK 0
 #define PCP_ERR_INVALID (-1) /* bad argument */
@@ -216,6 +217,42 @@ int pcp_set_image_adjust(pcp_context *ctx, int32_t enable, float saturation_scal
  * was enabled at upload): out_bgr image_height*image_width*3 tightly packed, out_mask image_height*image_width
  * (either nullable) */
 int pcp_download_image(pcp_context *ctx, int32_t frame, uint8_t *out_bgr, uint8_t *out_mask);
+/* A keyframe JPEG, entropy-decoded on the host (host/image_io.hpp jpeg_coefficients) and reconstructed on the device:
+ * dequantisation, libjpeg's islow IDCT, fancy upsampling, the YCbCr->BGR tables -- the pixels of cv::imread (:716) bit for
+ * bit -- then pcp_set_image_adjust's round trip and the texel pack, as pcp_upload_image does with decoded pixels.
+ * Supported: baseline / extended-sequential Huffman, 8 bit, 1 or 3 components, sampling 4:4:4 / 4:2:2 / 4:2:0.
+ *
+ * The blob (little-endian, every section 16-B aligned from the blob's start, offsets in bytes):
+ *   pcp_jpeg_header                       at 0
+ *   quantisation tables  ncomp x 64 uint16, natural order, each component's own table      at quant_off
+ *   block masks          n_blocks uint64: bit n set = natural position n is nonzero         at mask_off
+ *   value offsets        n_blocks uint32: index of the block's first value                  at offset_off
+ *   values               n_values int16: each block's nonzero quantised coefficients in natural order
+ *                        (DC after prediction, truncated to int16 as the decoder does)      at value_off
+ * Blocks are in decode order: for each MCU row, each MCU, each component, its v rows of h blocks (non-interleaved
+ * positions follow from the sampling).  quant_off = 144, mask_off = align16(quant_off + 128 ncomp), offset_off =
+ * align16(mask_off + 8 n_blocks), value_off = align16(offset_off + 4 n_blocks); the blob is value_off + 2 n_values bytes.
+ * The call checks all of it on the host before anything is queued: magic / version, width x height = the camera's image,
+ * ncomp 1 or 3, supported sampling, blocks_* / down_* of every component as the frame size implies, the sections inside
+ * `bytes`, and every block's offset delta equal to the popcount of its mask; otherwise PCP_ERR_INVALID. */
+#define PCP_JPEG_MAGIC 0x4A504350u /* "PCPJ" */
+#define PCP_JPEG_VERSION 1
+typedef struct pcp_jpeg_component {
+  int32_t h, v;                /* sampling factors (component 0: 1x1, 2x1 or 2x2; components 1, 2: 1x1) */
+  int32_t blocks_w, blocks_h;  /* blocks of the component's plane, whole MCUs */
+  int32_t down_w, down_h;      /* real samples: ceil(width * h / hmax), ceil(height * v / vmax) */
+} pcp_jpeg_component;
+typedef struct pcp_jpeg_header {
+  uint32_t magic, version;
+  int32_t width, height, ncomp, reserved; /* reserved: 0 */
+  pcp_jpeg_component comp[3];             /* entries >= ncomp: 0 */
+  int64_t n_blocks, n_values;
+  int64_t quant_off, mask_off, offset_off, value_off;
+} pcp_jpeg_header; /* 144 bytes */
+/* Same call order and lifetime rules as pcp_upload_image / pcp_upload_image_async; `blob` is host memory (pageable or
+ * pinned), `bytes` its size. */
+int pcp_upload_image_jpeg(pcp_context *ctx, int32_t frame, const uint8_t *blob, int64_t bytes);
+int pcp_upload_image_jpeg_async(pcp_context *ctx, int32_t frame, const uint8_t *blob, int64_t bytes);
 /* gray8 segmentation mask (cv::IMREAD_GRAYSCALE, PointCloudProcessor.cpp:775) */
 int pcp_upload_mask(pcp_context *ctx, int32_t frame, const uint8_t *gray, int64_t row_stride_bytes);
 

@@ -271,6 +271,17 @@ class Context:
         """The same from a raw address: pinned host memory or DEVICE memory (e.g. frames all-gathered over xGMI)."""
         self._check(self.lib.pcp_upload_image_async(self.h, C.c_int32(frame), C.c_void_p(ptr), C.c_int64(row_stride_bytes)))
 
+    def upload_image_jpeg(self, frame: int, blob: np.ndarray):
+        """A keyframe JPEG's coefficient blob (host/image_io.hpp jpeg_coefficients, `image_dump <in> <out> coeffs`; layout:
+        pcp_jpeg_header in pcp_hip.h), reconstructed and packed on the device; returns once the texels are written."""
+        blob = np.ascontiguousarray(blob, np.uint8).reshape(-1)
+        self._check(self.lib.pcp_upload_image_jpeg(self.h, C.c_int32(frame), _ptr(blob), C.c_int64(blob.size)))
+
+    def upload_image_jpeg_async(self, frame: int, blob: np.ndarray):
+        """Queues the copy and the kernels only: `blob` must stay alive and unchanged until synchronize()."""
+        assert blob.dtype == np.uint8 and blob.flags.c_contiguous
+        self._check(self.lib.pcp_upload_image_jpeg_async(self.h, C.c_int32(frame), _ptr(blob), C.c_int64(blob.size)))
+
     def set_image_adjust(self, enable: bool = True, saturation_scale: float = 1.0, brightness_scale: float = 1.0):
         """generateColorMap's 8-bit BGR -> HSV -> BGR round trip applied to the images uploaded from now on."""
         self._check(self.lib.pcp_set_image_adjust(self.h, C.c_int32(1 if enable else 0), C.c_float(saturation_scale),

@@ -1363,25 +1363,15 @@ hipError_t preload_colour() {
   hipFuncAttributes a;
   return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_fill_u32));
 }
-}  // namespace pcp
 
-using namespace pcp;
-
-extern "C" {
-
-// Both forms run on the upload stream: copy into the staging buffer, pack kernel (with the HSV round trip when
-// pcp_set_image_adjust enabled it), event.  `bgr` may be a host pointer (pinned for a real overlap) or a device
-// pointer (hipMemcpyDefault: e.g. frames all-gathered over xGMI by the multi-GPU driver).
-// block_bytes > 0: `bgr` is the first of block_frames keyframes (block_stride bytes apart) in pinned host memory; the whole
-// block is copied into the lane's staging buffer by one DMA and every keyframe of it is packed from there.
-static int upload_image_impl(pcp_context *ctx, const char *who, int32_t frame, const uint8_t *bgr, int64_t row_stride_bytes,
-                             bool wait, size_t block_bytes = 0, int64_t block_stride = 0, int32_t block_frames = 1) {
+// Both forms run on the upload stream: copy into the staging buffer, "source -> texels" kernels (with the HSV round trip
+// when pcp_set_image_adjust enabled it), event.  count > 1: a block of keyframes staged together (pcp_upload_images_block).
+int upload_texels(pcp_context *ctx, const char *who, int32_t frame, int32_t count, bool block, bool wait, TexelSource &source) {
   int rc = check_ready(ctx, who, true);
   if (rc != PCP_OK) return rc;
   if ((rc = check_frame(ctx, who, frame)) != PCP_OK) return rc;
+  if ((rc = source.validate(ctx, who)) != PCP_OK) return rc;
   const int32_t w = ctx->dcam.img_w, h = ctx->dcam.img_h;
-  if (!bgr || row_stride_bytes < 3 * static_cast<int64_t>(w))
-    return set_error(ctx, PCP_ERR_INVALID, "%s: NULL image or row stride < 3*width", who);
   const bool fresh = ctx->images.count < static_cast<size_t>(w) * h * static_cast<size_t>(ctx->n_frames) + 4;
   if ((rc = ensure_images(ctx)) != PCP_OK) return rc;
   if (!ctx->upload_stream[0]) {
@@ -1403,10 +1393,10 @@ static int upload_image_impl(pcp_context *ctx, const char *who, int32_t frame, c
   const size_t sf = static_cast<size_t>(frame);
   // a keyframe uploaded again goes to the lane of its previous upload while that one may still be in flight (two
   // lanes writing the same texels would race); otherwise the lanes take turns
-  const int lane = (ctx->image_pending[sf] && block_bytes == 0) ? ctx->image_lane[sf]
-                                                                : static_cast<int>(ctx->upload_turn % pcp_context::kUploadLanes);
-  if (block_bytes > 0)  // a block takes one lane: uploads of its keyframes still in flight on the other lane come first
-    for (int32_t k = 0; k < block_frames; ++k)
+  const int lane = (ctx->image_pending[sf] && !block) ? ctx->image_lane[sf]
+                                                      : static_cast<int>(ctx->upload_turn % pcp_context::kUploadLanes);
+  if (block)  // a block takes one lane: uploads of its keyframes still in flight on the other lane come first
+    for (int32_t k = 0; k < count; ++k)
       if (ctx->image_pending[sf + static_cast<size_t>(k)] && ctx->image_lane[sf + static_cast<size_t>(k)] != lane)
         PCP_HIP_TRY(ctx, hipStreamWaitEvent(ctx->upload_stream[lane], ctx->image_event[sf + static_cast<size_t>(k)], 0));
   // kernels of the compute stream that read or write texels (a colour pass still sampling the previous image of this
@@ -1421,47 +1411,15 @@ static int upload_image_impl(pcp_context *ctx, const char *who, int32_t frame, c
     ctx->lane_must_wait[lane] = false;
   }
   hipStream_t us = ctx->upload_stream[lane];
-  const size_t bytes = static_cast<size_t>(row_stride_bytes) * h;
   const int64_t px = static_cast<int64_t>(w) * h;
-  // Where do the pack kernel's loads go?  Device memory and pinned (device-mapped) host memory are read in place;
-  // pageable host memory goes through the lane's staging buffer.
-  const uint8_t *src = nullptr;
-  if (block_bytes > 0) {
-    PCP_HIP_TRY(ctx, ctx->upload_stage[lane].ensure(block_bytes + 16));
-    PCP_HIP_TRY(ctx, hipMemcpyAsync(ctx->upload_stage[lane].p, bgr, block_bytes, hipMemcpyHostToDevice, us));
-    src = ctx->upload_stage[lane].p;
-  } else {
-    hipPointerAttribute_t attr{};
-    if (hipPointerGetAttributes(&attr, bgr) == hipSuccess &&
-        (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeHost) && attr.devicePointer) {
-      src = static_cast<const uint8_t *>(attr.devicePointer);
-      if (attr.type == hipMemoryTypeDevice) {
-        // bytes produced on the device (a collective on the context's stream): this lane starts after that work
-        PCP_HIP_TRY(ctx, hipEventRecord(ctx->texels_idle, ctx->stream));
-        PCP_HIP_TRY(ctx, hipStreamWaitEvent(us, ctx->texels_idle, 0));
-      }
-    } else {
-      (void)hipGetLastError();  // an unregistered host pointer is not an error here
-    }
-  }
-  if (!src) {
-    PCP_HIP_TRY(ctx, ctx->upload_stage[lane].ensure(bytes + 16));
-    PCP_HIP_TRY(ctx, hipMemcpyAsync(ctx->upload_stage[lane].p, bgr, bytes, hipMemcpyDefault, us));
-    src = ctx->upload_stage[lane].p;
-  }
+  if ((rc = source.stage(ctx, lane, us)) != PCP_OK) return rc;
   const int32_t *tables = ctx->adjust_images ? ctx->hsv_tables.p : static_cast<const int32_t *>(nullptr);
   ++ctx->upload_turn;  // one turn of the lanes per call (a block is one call)
-  for (int32_t k = 0; k < block_frames; ++k) {
+  for (int32_t k = 0; k < count; ++k) {
     const int32_t fk = frame + k;
-    const uint8_t *sk = src + static_cast<int64_t>(k) * block_stride;
     uint32_t *dst = ctx->images.p + static_cast<int64_t>(fk) * px;
     const int32_t clear_mask = ctx->mask_set[fk] ? 0 : 1;
-    if ((w & 15) == 0 && (row_stride_bytes & 15) == 0 && (reinterpret_cast<uintptr_t>(sk) & 15u) == 0)
-      hipLaunchKernelGGL(k_pack_bgr16, dim3(blocks_for(px / 16)), dim3(kBlock), 0, us, sk, row_stride_bytes, w, h, dst,
-                         clear_mask, tables, ctx->saturation_scale, ctx->brightness_scale);
-    else
-      hipLaunchKernelGGL(k_pack_bgr, dim3(blocks_for(px)), dim3(kBlock), 0, us, sk, row_stride_bytes, w, h, dst, clear_mask,
-                         tables, ctx->saturation_scale, ctx->brightness_scale);
+    if ((rc = source.pack(ctx, lane, us, k, dst, clear_mask, tables)) != PCP_OK) return rc;
     PCP_HIP_TRY(ctx, hipGetLastError());
     PCP_HIP_TRY(ctx, hipEventRecord(ctx->image_event[static_cast<size_t>(fk)], us));
     ctx->image_pending[static_cast<size_t>(fk)] = 1;
@@ -1476,6 +1434,79 @@ static int upload_image_impl(pcp_context *ctx, const char *who, int32_t frame, c
   }
   return PCP_OK;
 }
+
+}  // namespace pcp
+
+using namespace pcp;
+
+// Decoded BGR8 rows.  `bgr` may be a host pointer (pinned for a real overlap) or a device pointer (hipMemcpyDefault: e.g.
+// frames all-gathered over xGMI by the multi-GPU driver).  block_bytes > 0: `bgr` is the first of the call's keyframes
+// (block_stride bytes apart) in pinned host memory; the whole block is copied into the lane's staging buffer by one DMA and
+// every keyframe of it is packed from there.
+struct BgrSource final : TexelSource {
+  const uint8_t *bgr;
+  int64_t row_stride_bytes;
+  size_t block_bytes;
+  int64_t block_stride;
+  const uint8_t *src = nullptr;
+  BgrSource(const uint8_t *b, int64_t rs, size_t bb = 0, int64_t bs = 0) : bgr(b), row_stride_bytes(rs), block_bytes(bb), block_stride(bs) {}
+
+  int validate(pcp_context *ctx, const char *who) override {
+    if (!bgr || row_stride_bytes < 3 * static_cast<int64_t>(ctx->dcam.img_w))
+      return set_error(ctx, PCP_ERR_INVALID, "%s: NULL image or row stride < 3*width", who);
+    return PCP_OK;
+  }
+  int stage(pcp_context *ctx, int lane, hipStream_t us) override {
+    const size_t bytes = static_cast<size_t>(row_stride_bytes) * ctx->dcam.img_h;
+    // Where do the pack kernel's loads go?  Device memory and pinned (device-mapped) host memory are read in place;
+    // pageable host memory goes through the lane's staging buffer.
+    src = nullptr;
+    if (block_bytes > 0) {
+      PCP_HIP_TRY(ctx, ctx->upload_stage[lane].ensure(block_bytes + 16));
+      PCP_HIP_TRY(ctx, hipMemcpyAsync(ctx->upload_stage[lane].p, bgr, block_bytes, hipMemcpyHostToDevice, us));
+      src = ctx->upload_stage[lane].p;
+    } else {
+      hipPointerAttribute_t attr{};
+      if (hipPointerGetAttributes(&attr, bgr) == hipSuccess &&
+          (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeHost) && attr.devicePointer) {
+        src = static_cast<const uint8_t *>(attr.devicePointer);
+        if (attr.type == hipMemoryTypeDevice) {
+          // bytes produced on the device (a collective on the context's stream): this lane starts after that work
+          PCP_HIP_TRY(ctx, hipEventRecord(ctx->texels_idle, ctx->stream));
+          PCP_HIP_TRY(ctx, hipStreamWaitEvent(us, ctx->texels_idle, 0));
+        }
+      } else {
+        (void)hipGetLastError();  // an unregistered host pointer is not an error here
+      }
+    }
+    if (!src) {
+      PCP_HIP_TRY(ctx, ctx->upload_stage[lane].ensure(bytes + 16));
+      PCP_HIP_TRY(ctx, hipMemcpyAsync(ctx->upload_stage[lane].p, bgr, bytes, hipMemcpyDefault, us));
+      src = ctx->upload_stage[lane].p;
+    }
+    return PCP_OK;
+  }
+  int pack(pcp_context *ctx, int, hipStream_t us, int32_t k, uint32_t *dst, int32_t clear_mask, const int32_t *tables) override {
+    const int32_t w = ctx->dcam.img_w, h = ctx->dcam.img_h;
+    const int64_t px = static_cast<int64_t>(w) * h;
+    const uint8_t *sk = src + static_cast<int64_t>(k) * block_stride;
+    if ((w & 15) == 0 && (row_stride_bytes & 15) == 0 && (reinterpret_cast<uintptr_t>(sk) & 15u) == 0)
+      hipLaunchKernelGGL(k_pack_bgr16, dim3(blocks_for(px / 16)), dim3(kBlock), 0, us, sk, row_stride_bytes, w, h, dst,
+                         clear_mask, tables, ctx->saturation_scale, ctx->brightness_scale);
+    else
+      hipLaunchKernelGGL(k_pack_bgr, dim3(blocks_for(px)), dim3(kBlock), 0, us, sk, row_stride_bytes, w, h, dst, clear_mask,
+                         tables, ctx->saturation_scale, ctx->brightness_scale);
+    return PCP_OK;
+  }
+};
+
+static int upload_image_impl(pcp_context *ctx, const char *who, int32_t frame, const uint8_t *bgr, int64_t row_stride_bytes,
+                             bool wait, size_t block_bytes = 0, int64_t block_stride = 0, int32_t block_frames = 1) {
+  BgrSource source(bgr, row_stride_bytes, block_bytes, block_stride);
+  return upload_texels(ctx, who, frame, block_frames, block_bytes > 0, wait, source);
+}
+
+extern "C" {
 
 int pcp_upload_image(pcp_context *ctx, int32_t frame, const uint8_t *bgr, int64_t row_stride_bytes) {
   return upload_image_impl(ctx, "pcp_upload_image", frame, bgr, row_stride_bytes, true);

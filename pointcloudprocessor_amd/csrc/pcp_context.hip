@@ -576,7 +576,8 @@ int pcp_create(int32_t device, pcp_context **out) {
     // others cost.
     hipFuncAttributes a;
     const hipError_t pl[] = {hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_up_bbox)), preload_colour(), preload_mls(),
-                             preload_nid(), preload_hpr(), preload_colour_smooth(), preload_match()};
+                             preload_nid(), preload_hpr(), preload_colour_smooth(), preload_match(),
+                             preload_jpeg()};
     for (hipError_t x : pl)
       if (x != hipSuccess && e == hipSuccess) e = x;
   }
@@ -638,6 +639,7 @@ void pcp_destroy(pcp_context *ctx) {
     if (e) (void)hipEventDestroy(e);
   if (ctx->texels_idle) (void)hipEventDestroy(ctx->texels_idle);
   for (auto &b : ctx->upload_stage) b.release();
+  for (auto &b : ctx->jpeg_planes) b.release();
   drain_timing(ctx);
   for (auto e : ctx->event_pool) (void)hipEventDestroy(e);
   ctx->xyz.release();

@@ -191,6 +191,7 @@ struct pcp_context {
   static constexpr int kUploadLanes = 2;
   hipStream_t upload_stream[kUploadLanes] = {nullptr, nullptr};
   pcp::DevBuf<uint8_t> upload_stage[kUploadLanes];
+  pcp::DevBuf<uint8_t> jpeg_planes[kUploadLanes];  // pcp_upload_image_jpeg: the lane's component planes (pcp_jpeg.hip)
   std::vector<hipEvent_t> image_event;   // per keyframe, recorded on its lane after its pack kernel
   std::vector<uint8_t> image_pending;    // 1: the consumer has not yet made its stream wait for image_event[f]
   std::vector<uint8_t> image_lane;       // lane of the keyframe's latest upload
@@ -419,6 +420,18 @@ int drain_timing(pcp_context *ctx);
 // the compute stream is about to touch the texel buffer (pcp_colour.hip)
 int wait_images(pcp_context *ctx, int32_t f0, int32_t f1);
 
+// One image upload call (pcp_colour.hip upload_texels): the lane, event and keyframe bookkeeping is upload_texels'; what
+// turns the caller's source into texels is the TexelSource's.  validate runs first (no device work queued before it
+// succeeds), stage once per call on the lane's stream, pack once per keyframe frame + k of the call.
+struct TexelSource {
+  virtual int validate(pcp_context *ctx, const char *who) = 0;
+  virtual int stage(pcp_context *ctx, int lane, hipStream_t us) = 0;
+  virtual int pack(pcp_context *ctx, int lane, hipStream_t us, int32_t k, uint32_t *dst, int32_t clear_mask,
+                   const int32_t *hsv_tables) = 0;
+};
+// count > 1 only for a block of keyframes staged together (pcp_upload_images_block); wait: synchronise the lane
+int upload_texels(pcp_context *ctx, const char *who, int32_t frame, int32_t count, bool block, bool wait, TexelSource &src);
+
 // ordered compaction of a device byte-flag array (pcp_colour.hip): index list (nullable) + count
 int compact_flags(pcp_context *ctx, const uint8_t *flags, int64_t n, int32_t *out_index, int64_t capacity,
                   int64_t *count);
@@ -441,6 +454,7 @@ int colour_smooth_words(pcp_context *ctx, float radius, const uint32_t *d_in, ui
 int match_table_prepare(pcp_context *ctx);
 void match_table_release(pcp_context *ctx);
 hipError_t preload_match();
+hipError_t preload_jpeg();
 
 inline int64_t div_up(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

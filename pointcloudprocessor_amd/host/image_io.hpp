@@ -9,6 +9,13 @@
 // (jdsample.c h2v1 / h2v2), fixed-point YCbCr->RGB tables (jdcolor.c) [upstream libjpeg 6b /
 // libjpeg-turbo, restated].  tests/test_image_io.py checks the decoder bit for bit against
 // Pillow (libjpeg-turbo) on this image.  Progressive / arithmetic / CMYK files are rejected.
+// Huffman codes of up to 9 bits are decoded with one table lookup (libjpeg's HUFF_LOOKAHEAD), longer ones
+// bit by bit.
+//
+// jpeg_coefficients stops after the entropy decoding: the same parser and scan loop hand each block's
+// quantised coefficients to a blob (layout: pcp_jpeg_header in include/pcp_hip.h) instead of the IDCT, and
+// pcp_upload_image_jpeg reconstructs the pixels on the GPU with the same arithmetic ("Device JPEG
+// reconstruction").  It accepts exactly the files the pixel decoder decodes.
 //
 // PNG: 8 / 16 bit, gray / RGB / palette / alpha, non-interlaced; zlib inflate + the five
 // scanline filters (RFC 2083).  16-bit samples are reduced to their high byte and alpha is
@@ -17,6 +24,8 @@
 
 #include <zlib.h>
 
+#include <algorithm>
+#include <cstddef>
 #include <cstdint>
 #include <cstring>
 #include <fstream>
@@ -30,6 +39,13 @@ struct Image8 {
   int width = 0, height = 0, channels = 0;  // channels: 1 (gray) or 3 (B,G,R)
   std::vector<uint8_t> data;                // tightly packed rows
   bool empty() const { return data.empty(); }
+};
+
+// The entropy-decoded form of a JPEG: the blob pcp_upload_image_jpeg takes (pcp_jpeg_header, include/pcp_hip.h)
+struct JpegCoeffs {
+  int width = 0, height = 0;
+  std::vector<uint8_t> blob;
+  bool empty() const { return blob.empty(); }
 };
 
 namespace detail {
@@ -49,18 +65,49 @@ struct JpegComponent {
   int pred = 0;
 };
 
+constexpr int kHuffLookahead = 9;
+
 struct Huff {
   // canonical code -> symbol by code length (JPEG Annex C / F.2.2.3)
   int mincode[17], maxcode[18], valptr[17];
   uint8_t vals[256];
+  // the next kHuffLookahead bits -> (code length << 8) | symbol for codes of at most that many bits; 0: a longer code
+  uint16_t look[1 << kHuffLookahead];
   bool present = false;
 };
+
+// header of the coefficient blob: pcp_jpeg_header of include/pcp_hip.h, restated field for field (this header
+// does not include the C ABI's)
+struct JpegBlobHeader {
+  uint32_t magic, version;
+  int32_t width, height, ncomp, reserved;
+  int32_t comp[3][6];  // h, v, blocks_w, blocks_h, down_w, down_h
+  int64_t n_blocks, n_values;
+  int64_t quant_off, mask_off, offset_off, value_off;
+};
+static_assert(sizeof(JpegBlobHeader) == 144, "pcp_jpeg_header layout");
+constexpr uint32_t kJpegBlobMagic = 0x4A504350u;  // "PCPJ"
+constexpr uint32_t kJpegBlobVersion = 1;
+inline int64_t align16(int64_t x) { return (x + 15) & ~int64_t(15); }
 
 class JpegDecoder {
  public:
   explicit JpegDecoder(const std::vector<uint8_t> &buf) : d(buf) {}
 
-  bool decode(Image8 &out, bool want_gray) {
+  bool decode(Image8 &out, bool want_gray) { return parse() && finish(out, want_gray); }
+
+  // the entropy-decoded blocks of the same files decode() accepts (sampling checked as upsample() checks it)
+  bool coefficients(JpegCoeffs &out) {
+    coeffs = &out;
+    out = JpegCoeffs{};
+    const bool ok = parse() && sampling_supported() && finish_coefficients(out);
+    if (!ok) out = JpegCoeffs{};
+    coeffs = nullptr;
+    return ok;
+  }
+
+ private:
+  bool parse() {
     if (d.size() < 4 || d[0] != 0xFF || d[1] != 0xD8) return false;
     pos = 2;
     bool have_frame = false;
@@ -92,10 +139,9 @@ class JpegDecoder {
       }
       pos = end;
     }
-    return finish(out, want_gray);
+    return have_frame;
   }
 
- private:
   const std::vector<uint8_t> &d;
   size_t pos = 0;
   int width = 0, height = 0, ncomp = 0, hmax = 1, vmax = 1;
@@ -104,6 +150,10 @@ class JpegDecoder {
   Huff dc[4], ac[4];
   int restart_interval = 0;
   int adobe_transform = -1;
+  bool scanned = false;
+  // coefficients(): blocks go to the blob instead of the IDCT
+  JpegCoeffs *coeffs = nullptr;
+  int64_t n_blocks = 0, n_values = 0, block_at = 0, mask_off = 0, offset_off = 0;
   // bit reader
   uint32_t bitbuf = 0;
   int bitcnt = 0;
@@ -149,7 +199,7 @@ class JpegDecoder {
       comp[c].blocks_h = mcuy * comp[c].v;
       comp[c].down_w = (width * comp[c].h + hmax - 1) / hmax;
       comp[c].down_h = (height * comp[c].v + vmax - 1) / vmax;
-      comp[c].plane.assign(static_cast<size_t>(comp[c].blocks_w) * 8 * comp[c].blocks_h * 8, 0);
+      if (!coeffs) comp[c].plane.assign(static_cast<size_t>(comp[c].blocks_w) * 8 * comp[c].blocks_h * 8, 0);
     }
     return true;
   }
@@ -192,6 +242,17 @@ class JpegDecoder {
         code <<= 1;
       }
       h.maxcode[17] = 0x7fffffff;
+      // lookahead: every kHuffLookahead-bit window that starts with a code of length l <= kHuffLookahead; the shortest
+      // length claims a window first, as the bit loop below returns at the shortest match
+      std::memset(h.look, 0, sizeof(h.look));
+      for (int l = 1; l <= kHuffLookahead; ++l)
+        for (int i = 0; i < counts[l]; ++i) {
+          const int c = h.mincode[l] + i;
+          if (c >= (1 << l)) break;  // (an over-subscribed table: codes the bit loop can never read)
+          const int sh = kHuffLookahead - l;
+          for (int w = c << sh; w < (c + 1) << sh; ++w)
+            if (!h.look[w]) h.look[w] = static_cast<uint16_t>((l << 8) | h.vals[h.valptr[l] + i]);
+        }
       h.present = true;
     }
     return true;
@@ -249,6 +310,13 @@ class JpegDecoder {
     return v;
   }
   int decode_huff(const Huff &h) {
+    if (bitcnt < kHuffLookahead) fill();
+    const int e = h.look[bitbuf >> (32 - kHuffLookahead)];
+    if (e) {
+      bitbuf <<= e >> 8;
+      bitcnt -= e >> 8;
+      return e & 0xff;
+    }
     int code = 0;
     for (int l = 1; l <= 16; ++l) {
       code = (code << 1) | getbits(1);
@@ -411,6 +479,10 @@ class JpegDecoder {
           for (int by = 0; by < comp[c].v; ++by)
             for (int bx = 0; bx < comp[c].h; ++bx) {
               if (!decode_block(comp[c], blk)) return false;
+              if (coeffs) {
+                if (!emit_block(blk)) return false;
+                continue;
+              }
               const int stride = comp[c].blocks_w * 8;
               uint8_t *o = comp[c].plane.data() + static_cast<size_t>((my * comp[c].v + by) * 8) * stride +
                            static_cast<size_t>(mx * comp[c].h + bx) * 8;
@@ -418,6 +490,78 @@ class JpegDecoder {
             }
         if (restart_interval) --todo;
       }
+    scanned = true;
+    return true;
+  }
+
+  // ---- coefficient blob (pcp_jpeg_header, include/pcp_hip.h) ----
+  bool sampling_supported() const {
+    for (int c = 0; c < ncomp; ++c) {
+      const bool full = comp[c].h == hmax && comp[c].v == vmax;
+      const bool h2 = comp[c].h * 2 == hmax && (comp[c].v == vmax || comp[c].v * 2 == vmax);
+      if (!full && !h2) return false;
+    }
+    return true;
+  }
+
+  // the header, quantisation tables and the two per-block sections, sized once the frame header is known
+  void start_blob() {
+    const int mcux = (width + 8 * hmax - 1) / (8 * hmax), mcuy = (height + 8 * vmax - 1) / (8 * vmax);
+    int per_mcu = 0;
+    for (int c = 0; c < ncomp; ++c) per_mcu += comp[c].h * comp[c].v;
+    JpegBlobHeader hd{};
+    hd.magic = kJpegBlobMagic;
+    hd.version = kJpegBlobVersion;
+    hd.width = width;
+    hd.height = height;
+    hd.ncomp = ncomp;
+    for (int c = 0; c < ncomp; ++c) {
+      const int f[6] = {comp[c].h, comp[c].v, comp[c].blocks_w, comp[c].blocks_h, comp[c].down_w, comp[c].down_h};
+      std::memcpy(hd.comp[c], f, sizeof(f));
+    }
+    hd.n_blocks = static_cast<int64_t>(mcux) * mcuy * per_mcu;
+    hd.quant_off = static_cast<int64_t>(sizeof(JpegBlobHeader));
+    hd.mask_off = align16(hd.quant_off + 128 * ncomp);
+    hd.offset_off = align16(hd.mask_off + 8 * hd.n_blocks);
+    hd.value_off = align16(hd.offset_off + 4 * hd.n_blocks);
+    std::vector<uint8_t> &b = coeffs->blob;
+    b.assign(static_cast<size_t>(hd.value_off), 0);
+    b.reserve(static_cast<size_t>(hd.value_off + 2 * 24 * hd.n_blocks));
+    std::memcpy(b.data(), &hd, sizeof(hd));
+    for (int c = 0; c < ncomp; ++c) std::memcpy(b.data() + hd.quant_off + 128 * c, quant[comp[c].tq], 128);
+    n_blocks = hd.n_blocks;
+    mask_off = hd.mask_off;
+    offset_off = hd.offset_off;
+  }
+  // one decoded block (natural order, as the IDCT would take it): its mask, its value offset, its nonzero values
+  bool emit_block(const int16_t blk[64]) {
+    if (block_at == 0 && coeffs->blob.empty()) start_blob();
+    if (block_at >= n_blocks) return false;
+    uint64_t mask = 0;
+    int16_t vals[64];
+    int nz = 0;
+    for (int n = 0; n < 64; ++n)
+      if (blk[n]) {
+        mask |= uint64_t(1) << n;
+        vals[nz++] = blk[n];
+      }
+    if (n_values + nz > int64_t(0xffffffff)) return false;  // value offsets are 32 bit
+    std::vector<uint8_t> &b = coeffs->blob;
+    const uint32_t first = static_cast<uint32_t>(n_values);
+    std::memcpy(b.data() + mask_off + 8 * block_at, &mask, 8);  // (the blob is little-endian, as the host)
+    std::memcpy(b.data() + offset_off + 4 * block_at, &first, 4);
+    const size_t at = b.size();
+    b.resize(at + 2 * static_cast<size_t>(nz));
+    std::memcpy(b.data() + at, vals, 2 * static_cast<size_t>(nz));
+    n_values += nz;
+    ++block_at;
+    return true;
+  }
+  bool finish_coefficients(JpegCoeffs &out) {
+    if (!scanned || out.blob.empty() || block_at != n_blocks) return false;
+    std::memcpy(out.blob.data() + offsetof(JpegBlobHeader, n_values), &n_values, 8);
+    out.width = width;
+    out.height = height;
     return true;
   }
 
@@ -682,6 +826,27 @@ inline bool decode_any(const std::string &path, Image8 &out, bool want_gray) {
 }
 
 }  // namespace detail
+
+// The entropy decoding of a JPEG file's bytes, its blocks handed over as the coefficient blob pcp_upload_image_jpeg
+// reconstructs on the device.  false (and `out` empty) for whatever read_image_bgr would not decode as a JPEG: other
+// formats, progressive / arithmetic files, unsupported sampling, corrupt data.
+inline bool jpeg_coefficients(const std::vector<uint8_t> &buf, JpegCoeffs &out) {
+  out = JpegCoeffs{};
+  if (buf.size() < 4 || buf[0] != 0xFF || buf[1] != 0xD8) return false;
+  try {
+    detail::JpegDecoder dec(buf);
+    return dec.coefficients(out);
+  } catch (const std::exception &) {
+    out = JpegCoeffs{};
+    return false;
+  }
+}
+
+inline JpegCoeffs read_jpeg_coefficients(const std::string &path) {
+  JpegCoeffs c;
+  if (!jpeg_coefficients(detail::read_file(path), c)) c = JpegCoeffs{};
+  return c;
+}
 
 // cv::imread(path): 3-channel BGR; empty image on failure (as cv::Mat::empty())
 inline Image8 read_image_bgr(const std::string &path) {

@@ -11,7 +11,9 @@
 // Differences (this image has no OpenCV):
 //   * images are decoded by host/image_io.hpp: <images_folder><ts>.jpg (baseline JPEG, libjpeg's
 //     arithmetic, bit-exact with Pillow / libjpeg-turbo here) and masks <mask_folder><ts>.png;
-//     <ts>.ppm / <ts>.pgm are accepted when the .jpg / .png is absent.
+//     <ts>.ppm / <ts>.pgm are accepted when the .jpg / .png is absent.  A keyframe JPEG the device path supports is
+//     only entropy-decoded on the host (jpeg_coefficients) and reconstructed on the GPU (pcp_upload_image_jpeg, the
+//     same pixels); any other keyframe file is decoded on the host as before.
 //   * the 8-bit BGR->HSV->BGR round trip of generateColorMap (:722-741, Appendix B5) is applied by the
 //     library while it packs the decoded image (pcp_set_image_adjust: OpenCV 4.2's integer forward routine
 //     exactly, its scalar float backward routine); the NID stage reads the raw pixels, as calibrate.cpp does.
@@ -384,9 +386,10 @@ class Processor {
     if (!keyframes.empty() && decoders) {  // (the decoders are on it already)
       std::unique_lock<std::mutex> lk(decoders->mu);
       decoders->cv.wait(lk, [&] { return decoders->ready[0] != 0; });
-      if (decoders->img[0].empty()) throw std::runtime_error("Failed to read image from: " + keyframes[0].imagePath);
-      img_w = decoders->img[0].width;
-      img_h = decoders->img[0].height;
+      const bool jpg = !decoders->jpg[0].empty();
+      if (!jpg && decoders->img[0].empty()) throw std::runtime_error("Failed to read image from: " + keyframes[0].imagePath);
+      img_w = jpg ? decoders->jpg[0].width : decoders->img[0].width;
+      img_h = jpg ? decoders->jpg[0].height : decoders->img[0].height;
     } else if (!keyframes.empty()) {
       const Image8 first = read_image_bgr(keyframes[0].imagePath);
       if (first.empty()) throw std::runtime_error("Failed to read image from: " + keyframes[0].imagePath);
@@ -476,6 +479,7 @@ class Processor {
   // ahead of their consumer (startDecoders: process() does, while the device comes up): uploadImages then finds them running.
   struct Decoders {
     std::vector<Image8> img, gray;
+    std::vector<JpegCoeffs> jpg;  // keyframes left to the device: img[k] stays empty
     std::vector<uint8_t> ready;
     std::mutex mu;
     std::condition_variable cv;
@@ -484,6 +488,7 @@ class Processor {
     std::vector<std::thread> pool;
   };
   std::unique_ptr<Decoders> decoders;
+  std::vector<uint8_t> path_counted;  // keyframes already counted in images_jpeg_on_device / images_decoded_on_host
 
   void startDecoders() {
     if (decoders) return;
@@ -495,6 +500,7 @@ class Processor {
     threads = static_cast<unsigned>(std::min<size_t>(threads, std::max<size_t>(D.n, 1)));
     D.window = 2 * static_cast<size_t>(threads) + 2;
     D.img.resize(D.n);
+    D.jpg.resize(D.n);
     D.gray.resize(D.n);
     D.ready.assign(D.n, 0);
     auto worker = [this]() {
@@ -508,13 +514,17 @@ class Processor {
           k = W.next++;
         }
         const auto t_dec = PhaseClock::clock::now();
-        Image8 a = read_image_bgr(keyframes[k].imagePath);  // cv::imread, :716
+        // cv::imread, :716: a supported JPEG is entropy-decoded here and reconstructed on the device, anything else decoded here
+        JpegCoeffs co = read_jpeg_coefficients(keyframes[k].imagePath);
+        Image8 a;
+        if (co.empty()) a = read_image_bgr(keyframes[k].imagePath);
         Image8 b;
         if (enableMaskSegmentation) b = read_image_gray(keyframes[k].maskImagePath);  // cv::IMREAD_GRAYSCALE, :775
         g_clock.add("images_decode_thread_seconds", PhaseClock::since(t_dec));  // summed over the decoder threads
         {
           std::lock_guard<std::mutex> lk(W.mu);
           W.img[k] = std::move(a);
+          W.jpg[k] = std::move(co);
           W.gray[k] = std::move(b);
           W.ready[k] = 1;
         }
@@ -546,6 +556,9 @@ class Processor {
     mask_missing.assign(n, 0);
     startDecoders();  // (running already when process() started them ahead)
     Decoders &D = *decoders;
+    g_clock.add("images_jpeg_on_device", 0.0);  // keyframes reconstructed on the device / decoded on the host, each counted
+    g_clock.add("images_decoded_on_host", 0.0);  // once (the NID stage uploads them a second time)
+    path_counted.resize(n, 0);
     try {
       for (size_t k = 0; k < n; ++k) {
         {
@@ -553,11 +566,20 @@ class Processor {
           D.cv.wait(lk, [&] { return D.ready[k] != 0; });
         }
         std::cout << "Reading image from: " << keyframes[k].imagePath << std::endl;
-        if (D.img[k].empty() || D.img[k].width != img_w || D.img[k].height != img_h)
+        const bool on_device = !D.jpg[k].empty();
+        if (on_device ? (D.jpg[k].width != img_w || D.jpg[k].height != img_h)
+                      : (D.img[k].empty() || D.img[k].width != img_w || D.img[k].height != img_h))
           throw std::runtime_error("Failed to read image from: " + keyframes[k].imagePath);
         {
           Phase ph_up("images_upload_calls_s");
-          gpu->uploadImage(static_cast<int>(k), D.img[k].data.data(), static_cast<int64_t>(D.img[k].width) * 3);
+          if (on_device)
+            gpu->uploadImageJpeg(static_cast<int>(k), D.jpg[k]);
+          else
+            gpu->uploadImage(static_cast<int>(k), D.img[k].data.data(), static_cast<int64_t>(D.img[k].width) * 3);
+        }
+        if (!path_counted[k]) {
+          path_counted[k] = 1;
+          g_clock.add(on_device ? "images_jpeg_on_device" : "images_decoded_on_host", 1.0);
         }
         if (enableMaskSegmentation) {
           std::cout << "Reading segment mask image from: " << keyframes[k].maskImagePath << std::endl;
@@ -569,6 +591,7 @@ class Processor {
         {
           std::lock_guard<std::mutex> lk(D.mu);
           D.img[k] = Image8();
+          D.jpg[k] = JpegCoeffs();
           D.gray[k] = Image8();
           D.uploaded = k + 1;
         }

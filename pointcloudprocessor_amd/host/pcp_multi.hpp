@@ -69,6 +69,7 @@ class MultiDevice {
         (void)hipSetDevice(ordinal(static_cast<int>(i / kStageSlots)));
         (void)hipFree(stage_[i]);
       }
+    if (jpeg_pinned_) (void)hipHostFree(jpeg_pinned_);
     dev_.clear();  // the contexts go before their streams
     for (size_t i = 0; i < stream_.size(); ++i) {
       (void)hipSetDevice(ordinal(static_cast<int>(i)));
@@ -135,6 +136,25 @@ class MultiDevice {
   // cv::Mat rgb / grayImg of one keyframe: over PCIe once, to the other GPUs over xGMI
   void uploadImage(int keyframe, const uint8_t *bgr, int64_t step) { replicate(keyframe, bgr, step, cam_.image_height, false); }
   void uploadMask(int keyframe, const uint8_t *gray, int64_t step) { replicate(keyframe, gray, step, cam_.image_height, true); }
+  // a keyframe JPEG's coefficient blob (image_io.hpp JpegCoeffs): to every GPU over PCIe, each reconstructs the pixels itself
+  // (the blob is smaller than the pixels and the reconstruction is cheap: nothing to broadcast).  The blob goes through one
+  // pinned buffer kept for the run: uploaded straight from the decoder's freshly written pageable buffer it took 19 ms per
+  // 4096x3000 keyframe on the upload thread (profiles/jpeg_cli_phases.json), more than the decoders need; the copy into the
+  // pinned buffer and the upload from it take 2.4-2.7 ms.
+  template <class Coeffs>
+  void uploadImageJpeg(int keyframe, const Coeffs &coeffs) {
+    const size_t bytes = coeffs.blob.size();
+    if (bytes > jpeg_pinned_bytes_) {
+      if (jpeg_pinned_) hip(hipHostFree(jpeg_pinned_), "hipHostFree(jpeg blob)");
+      jpeg_pinned_ = nullptr;
+      jpeg_pinned_bytes_ = 0;
+      const size_t cap = bytes + bytes / 4;  // (the blobs of a run differ in size: headroom against re-allocation)
+      hip(hipHostMalloc(reinterpret_cast<void **>(&jpeg_pinned_), cap, hipHostMallocDefault), "hipHostMalloc(jpeg blob)");
+      jpeg_pinned_bytes_ = cap;
+    }
+    std::memcpy(jpeg_pinned_, coeffs.blob.data(), bytes);
+    for (auto &d : dev_) d->check(pcp_upload_image_jpeg(d->get(), keyframe, jpeg_pinned_, static_cast<int64_t>(bytes)));
+  }
 
   // z-buffer MIN pass of every shard over all keyframes + the all-reduce(MIN) across the shards
   void depthPassAll() {
@@ -509,6 +529,8 @@ class MultiDevice {
   std::vector<ncclComm_t> comm_;
   std::vector<uint8_t *> stage_;  // [gpu][slot]
   size_t stage_bytes_ = 0;
+  uint8_t *jpeg_pinned_ = nullptr;  // uploadImageJpeg's pinned copy of the blob
+  size_t jpeg_pinned_bytes_ = 0;
   int stage_next_ = 0, stage_used_ = 0;
   pcp_camera cam_{};
   int64_t n_ = 0;

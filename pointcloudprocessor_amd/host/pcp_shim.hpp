@@ -60,6 +60,16 @@ class Device {
   void uploadImage(int keyframe, const uint8_t *bgr, int64_t step) { check(pcp_upload_image(ctx_, keyframe, bgr, step)); }
   // decoded frames in pinned memory: queues the copy only; the buffer must outlive the next synchronising call
   void uploadImageAsync(int keyframe, const uint8_t *bgr, int64_t step) { check(pcp_upload_image_async(ctx_, keyframe, bgr, step)); }
+  // cv::imread of a keyframe JPEG left to the device: `coeffs.blob` is jpeg_coefficients' blob (host/image_io.hpp JpegCoeffs;
+  // pcp_jpeg_header).  Same rules as uploadImage / uploadImageAsync.
+  template <class Coeffs>
+  void uploadImageJpeg(int keyframe, const Coeffs &coeffs) {
+    check(pcp_upload_image_jpeg(ctx_, keyframe, coeffs.blob.data(), static_cast<int64_t>(coeffs.blob.size())));
+  }
+  template <class Coeffs>
+  void uploadImageJpegAsync(int keyframe, const Coeffs &coeffs) {
+    check(pcp_upload_image_jpeg_async(ctx_, keyframe, coeffs.blob.data(), static_cast<int64_t>(coeffs.blob.size())));
+  }
   // cv::Mat grayImg (CV_8UC1)
   void uploadMask(int keyframe, const uint8_t *gray, int64_t step) { check(pcp_upload_mask(ctx_, keyframe, gray, step)); }
 
