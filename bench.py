@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- Mpoints x frames / s colourised on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline figure needs: set-up, an untimed settle phase, the W warm-up steps, the K timed steps,
+the --dump-outputs files, and the line with `value`, `ms_per_step` and the per-step statistics.  Every other leg below
+(roofline, per-kernel times, the parity gate against the oracle, the side legs) runs only with --full.
 
 A "step" is one pass of the whole hot path (tile masks + z-buffer MIN pass over every keyframe ->
 [all-reduce(MIN) of the depth maps across point shards] -> visibility + colour + scores + top-5 +
@@ -16,7 +20,7 @@ Workload (named in config.workload):
           1024 / N keyframes and the ranks all-gather them over xGMI instead of N uploads of each.
 
 `value` = points x keyframes x steps / wall, with cloud, poses and images resident in HBM when the timed
-region starts (the bench contract).  The same line carries, on rank 0:
+region starts (the bench contract).  With --full the same line carries, on rank 0:
   roofline        k_project_frame on a 40 M-point cloud (763 MiB per launch: outside the Infinity Cache),
                   hipEvents on the launch stream; + the figure on the 10 M-point cloud (cache resident)
   roofline_step   the kernels of the timed step: VALU-issue bound, from the recorded PMC passes
@@ -25,6 +29,9 @@ region starts (the bench contract).  The same line carries, on rank 0:
   camera_ref      the same step with the reference's own camera (4096x3000, PointCloudProcessor.cpp:57-60)
   cpu_baseline    the oracle (CPU restatement, OpenMP, all host cores) on a bounded sample, N = 1 only
   mls, nid        the enableMLS chain and the NID cost, N = 1 only
+  kernels_ms      hipEvents around the kernel groups of one extra, untimed step
+  parity_gate     the oracle's results against the timed legs' (a failing leg makes bench.py exit 1)
+  sharded_legs    N > 1: hidden_points_removal and the smoothing stage over the ranks
 """
 from __future__ import annotations
 
@@ -195,6 +202,9 @@ def parse():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the colours of the last timed step (a fixed sample of at most "
                          f"{DUMP_MAX_POINTS} points: index, rgb, has) as DIR/<name>.npy, float64 / float32")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg: roofline, per-kernel times, the oracle's parity gate, "
+                         "the side legs at N = 1 and the sharded legs at N > 1 (the --no-* and leg-size options below act on these)")
     ap.add_argument("--settle-ms", type=float, default=400.0,
                     help="untimed whole steps before the warm-up until this much time has passed (clock / power state of a fresh box)")
     ap.add_argument("--points", type=int, default=0, help="points per GPU (0: 10 M at N = 1, 50 M / N at N > 1)")
@@ -224,7 +234,7 @@ def parse():
                     help="keyframe groups whose all-reduce overlaps the next depth pass (0 = by the size of the depth maps)")
     ap.add_argument("--verify", action="store_true",
                     help="N > 1: the ranks' shares are slices of ONE seeded map, and after the timed region the gathered "
-                         "colours are compared with a one-GPU run of the whole map on rank 0 (first multi-GPU lease)")
+                         "colours are compared with a one-GPU run of the whole map on rank 0 (with or without --full)")
     ap.add_argument("--match-mode", default="roundtrip", choices=["roundtrip", "identity"],
                     help="pcp_cull_params.match_mode (default: the reference's fp32 round-trip arithmetic)")
     args = ap.parse_args()
@@ -444,13 +454,60 @@ def main():
             verify = {"equal_to_one_gpu_run": same, "points": int(N * world), "keyframes": int(F),
                       "coloured": int(full["has"].sum()), "differing_points": int((ref["rgb"] != full["rgb"]).any(axis=1).sum())}
             del fx, fy, fz
+    if rank == 0:
+        result = {
+            "metric": "Mpoints×frames/sec colorized",
+            "value": round(value, 1),
+            "unit": "Mpoints×frames/s",
+            "n_gpus": world,
+            "steps": steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 3),
+            "step_ms": step_stats,
+            "settle": {"steps": settle_steps, "ms": round(t_settle * 1e3, 1),
+                       "what": "untimed whole steps before the W warm-up steps, so that the timed region starts at the clock "
+                               "the device holds under this load"},
+            "higher_is_better": True,
+            "scaling": "strong" if sharded else "weak",
+            "vs_baseline": None,
+            "dtype": "f32/f64",
+            "data": "synthetic",
+            "config": {
+                "workload": workload,
+                "points_total": N * world,
+                "points_per_gpu": N,
+                "keyframes": F,
+                "camera": args.camera,
+                "match_mode": args.match_mode,
+                "parallelism": f"point-index shards x{world}, all-reduce(MIN) of depth maps",
+            },
+            "coloured_points_rank0": coloured,
+            "tile_pairs_kept": round(eng.ctx.tile_mask_density(), 4),
+            "value_note": "rate of the pruned algorithm: conservative interval tests prove (tile of 64 points, keyframe) pairs certainly "
+                          "rejected by the reference's rule and the passes skip them (tile_pairs_kept = the share that is walked; "
+                          "results equal the unpruned run and the oracle bit for bit); points x keyframes x 20 B / ms_per_step exceeds the "
+                          "HBM peak for that reason.  The bound of the step is vector issue (roofline_step); the HBM roofline claim is "
+                          "made on the unbatched single-keyframe projection kernel k_project_frame (roofline), which is NOT one of the "
+                          "kernels of the timed step: it is what pcp_project_frame / pcp_cull_frame launch per keyframe, timed in a leg "
+                          "of its own on a 40 M-point cloud (SURVEY 8(d): the 60 % claim is made on the unbatched kernel).  `value` is "
+                          "timed with the keyframe images resident in HBM (the bench contract); SURVEY 8(d)(i)'s boundary -- images in "
+                          "pinned host memory -- is value_host_images.  speedup_vs_cpu_baseline compares with the CPU restatement's "
+                          "unpruned loop, which is what the reference runs.  roofline, roofline_step, value_host_images and the CPU "
+                          "baseline are in the line of a --full run.",
+            "setup_s": round(t_setup, 1),
+        }
+        if verify is not None:
+            result["verify"] = verify
+            parity_fail = parity_fail or not verify.get("equal_to_one_gpu_run", True)
+        if args.backend != "nccl":
+            result["rehearsal"] = f"backend {args.backend}: ranks share GPUs, not a measurement"
     # ---- N > 1: hidden_points_removal and the smoothing stage over the ranks (every rank takes part: collectives).  Both
     # need the WHOLE map on every GPU, so they run on a map of their own -- the C3 scene, seeded alike on every rank
     # (--sharded-legs-points / -frames) --: `hpr` = every rank takes the hulls of its block of keyframes on a whole-map
     # context, the verdicts are all-gathered and imported into the rank's index shard (pipeline.HullSharding); `smooth` =
     # StatisticalOutlierRemoval + MovingLeastSquares (NONE) with the queries dealt out by slabs (pipeline.CloudSmooth) ----
     sharded_legs = None
-    if sharded and not args.no_side_legs:
+    if sharded and args.full and not args.no_side_legs:
         sharded_legs = {}
         Ns, Fs = args.sharded_legs_points, min(args.sharded_legs_frames, F)
         sx_, sy_, sz_, _ = synth.make_cloud(Ns, seed=synth.SEED)
@@ -555,15 +612,15 @@ def main():
         del sx_, sy_, sz_
     # ---- per-kernel times of one more step (hipEvents on the launch stream).  Every rank takes the step:
     # with N > 1 it contains the all-reduce, a collective ----
-    eng.ctx.timing_enable(True)
-    eng.ctx.timing_reset()
-    step()
-    fence()
-    kt = {eng.ctx.kernel_name(k): eng.ctx.timing_get(k)
-          for k in (capi.K_TILE_MASK, capi.K_DEPTH, capi.K_COLOUR, capi.K_MISC)}
-    eng.ctx.timing_enable(False)
-    if rank == 0:
-        pairs_kept = round(eng.ctx.tile_mask_density(), 4)
+    if args.full:
+        eng.ctx.timing_enable(True)
+        eng.ctx.timing_reset()
+        step()
+        fence()
+        kt = {eng.ctx.kernel_name(k): eng.ctx.timing_get(k)
+              for k in (capi.K_TILE_MASK, capi.K_DEPTH, capi.K_COLOUR, capi.K_MISC)}
+        eng.ctx.timing_enable(False)
+    if rank == 0 and args.full:
         pmc = read_summary(PMC_SUMMARY)
 
         # ---- roofline leg: the single-keyframe projection kernel, one launch per keyframe ----
@@ -1208,48 +1265,10 @@ def main():
                 cli_e2e = cli_e2e_leg(synth)
             except (OSError, RuntimeError, ImportError, ValueError, KeyError) as e:
                 cli_e2e = {"error": str(e)}
-        result = {
-            "metric": "Mpoints×frames/sec colorized",
-            "value": round(value, 1),
-            "unit": "Mpoints×frames/s",
-            "n_gpus": world,
-            "steps": steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 3),
-            "step_ms": step_stats,
-            "settle": {"steps": settle_steps, "ms": round(t_settle * 1e3, 1),
-                       "what": "untimed whole steps before the W warm-up steps, so that the timed region starts at the clock "
-                               "the device holds under this load"},
-            "higher_is_better": True,
-            "scaling": "strong" if sharded else "weak",
-            "vs_baseline": None,
-            "dtype": "f32/f64",
-            "data": "synthetic",
-            "config": {
-                "workload": workload,
-                "points_total": N * world,
-                "points_per_gpu": N,
-                "keyframes": F,
-                "camera": args.camera,
-                "match_mode": args.match_mode,
-                "parallelism": f"point-index shards x{world}, all-reduce(MIN) of depth maps",
-            },
-            "coloured_points_rank0": coloured,
+        result.update({
             kt_key: kt_ms,
             "kernels_ms_note": "hipEvents around each kernel group of one extra, untimed step; the key reads kernels_ms_timing_pass "
                                "when their sum exceeds ms_per_step (the events serialise the host's enqueue: not a part of the timed step)",
-            "tile_pairs_kept": pairs_kept,
-            "value_note": "rate of the pruned algorithm: conservative interval tests prove (tile of 64 points, keyframe) pairs certainly "
-                          "rejected by the reference's rule and the passes skip them (tile_pairs_kept = the share that is walked; "
-                          "results equal the unpruned run and the oracle bit for bit); points x keyframes x 20 B / ms_per_step exceeds the "
-                          "HBM peak for that reason.  The bound of the step is vector issue (roofline_step); the HBM roofline claim is "
-                          "made on the unbatched single-keyframe projection kernel k_project_frame (roofline), which is NOT one of the "
-                          "kernels of the timed step: it is what pcp_project_frame / pcp_cull_frame launch per keyframe, timed in a leg "
-                          "of its own on a 40 M-point cloud (SURVEY 8(d): the 60 % claim is made on the unbatched kernel).  `value` is "
-                          "timed with the keyframe images resident in HBM (the bench contract); SURVEY 8(d)(i)'s boundary -- images in "
-                          "pinned host memory -- is value_host_images.  speedup_vs_cpu_baseline compares with the CPU restatement's "
-                          "unpruned loop, which is what the reference runs.",
-            "setup_s": round(t_setup, 1),
             "profiles": {"lib_sha256": lib_sha256(), "summaries": SUMMARY_STATE,
                          "what": "the counter summaries read for this line and whether each was collected on the library that ran "
                                  "(stale: derived figures dropped)"},
@@ -1262,12 +1281,9 @@ def main():
             "hpr": hpr,
             "mls": mls,
             "cli_e2e": cli_e2e,
-        }
+        })
         if sharded_legs is not None:
             result["sharded_legs"] = sharded_legs
-        if verify is not None:
-            result["verify"] = verify
-            parity_fail = parity_fail or not verify.get("equal_to_one_gpu_run", True)
         result["parity_gate"] = {
             "ok": not parity_fail,
             "legs": {"colour": None if cpu is None else cpu.get("equal_to_gpu"),
@@ -1275,8 +1291,6 @@ def main():
                      "mls": None if not mls or "cpu_baseline" not in mls else mls["cpu_baseline"].get("equal_to_gpu")},
             "what": "every timed leg's output compared with the oracle's in the same run (colours of the last timed step; "
                     "hull keep masks of every keyframe; MLS rows of a slab's interior); a failing leg makes bench.py exit 1"}
-        if args.backend != "nccl":
-            result["rehearsal"] = f"backend {args.backend}: ranks share GPUs, not a measurement"
         # the two boundaries side by side: `value` is the contract's -- inputs resident in HBM when the
         # timed region starts --, `value_host_images` SURVEY 8(d)(i)'s: keyframes start in pinned host memory
         result["value_resident"] = round(value, 1)
@@ -1295,7 +1309,7 @@ def main():
     os.close(json_fd)
     eng.close()
     if parity_fail:
-        print("bench.py: PARITY GATE FAILED (see parity_gate / cpu_baseline in the line)", file=sys.stderr)
+        print("bench.py: PARITY GATE FAILED (see parity_gate / cpu_baseline / verify in the line)", file=sys.stderr)
         sys.exit(1)
 
 

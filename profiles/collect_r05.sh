@@ -7,7 +7,7 @@ set -e -o pipefail
 TAG=${1:-r05}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out
-BENCH="python3 $R/bench.py --steps 10 --warmup 2 --settle-ms 50 --no-side-legs --no-cpu"
+BENCH="python3 $R/bench.py --full --steps 10 --warmup 2 --settle-ms 50 --no-side-legs --no-cpu"
 cd /tmp && export TMPDIR=/tmp
 # (a) the bench command: kernel trace + stats (without the cache-resident projection launches: the k_project_frame row is then
 # the 40 M-point launches alone) and four counter passes
@@ -22,7 +22,7 @@ echo "pmc fetch done"
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/${TAG}_pmc_write -- $BENCH > $OUT/${TAG}_pmc_write_bench.json 2> $OUT/${TAG}_pmc_write.err
 echo "pmc write done"
 cd $R
-python3 profiles/summarise_pmc.py $OUT/${TAG}_pmc.json "rocprofv3 --pmc {SQ issue counters | SQ wait counters | FETCH_SIZE | WRITE_SIZE} --output-format csv -- python3 bench.py --steps 10 --warmup 2 --settle-ms 50 --no-side-legs --no-cpu (four separate passes)" 10000000 256 40000000 $OUT/${TAG}_pmc_sq $OUT/${TAG}_pmc_sq2 $OUT/${TAG}_pmc_fetch $OUT/${TAG}_pmc_write
+python3 profiles/summarise_pmc.py $OUT/${TAG}_pmc.json "rocprofv3 --pmc {SQ issue counters | SQ wait counters | FETCH_SIZE | WRITE_SIZE} --output-format csv -- python3 bench.py --full --steps 10 --warmup 2 --settle-ms 50 --no-side-legs --no-cpu (four separate passes)" 10000000 256 40000000 $OUT/${TAG}_pmc_sq $OUT/${TAG}_pmc_sq2 $OUT/${TAG}_pmc_fetch $OUT/${TAG}_pmc_write
 python3 profiles/build_stamp.py $OUT/${TAG}_pmc.json > /dev/null
 find $OUT/${TAG}_trace -name "*kernel_stats.csv" -exec cp {} $OUT/${TAG}_bench_kernel_stats.csv \;
 rm -rf $OUT/${TAG}_pmc_sq $OUT/${TAG}_pmc_sq2 $OUT/${TAG}_pmc_fetch $OUT/${TAG}_pmc_write $OUT/${TAG}_trace

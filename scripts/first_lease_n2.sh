@@ -4,7 +4,7 @@
 #
 #   bash scripts/first_lease_n2.sh [N]        (from the repo root; N defaults to 2)
 #
-#  1. bench.py --gpus N --verify under torch.distributed.run: RCCL all-reduce(MIN) of the depth maps, all-gather of the
+#  1. bench.py --full --gpus N --verify under torch.distributed.run: RCCL all-reduce(MIN) of the depth maps, all-gather of the
 #     keyframes over xGMI; the gathered colours must equal a one-GPU run of the same seeded map (verify.equal_to_one_gpu_run).
 #     The same line times the two stages that need the whole map on every GPU (sharded_legs): hidden_points_removal over the
 #     ranks (hulls of each rank's block of keyframes, all-gather of the verdicts on device memory, import into the index
@@ -26,7 +26,7 @@ cd "$R"
 python3 -c "import __graft_entry__ as g; g.build()" > "$OUT/build.log" 2>&1 || { echo '{"ok": false, "stage": "build"}' > "$OUT/verdict.json"; exit 1; }
 
 # 1 -- bench, sharded, verified
-python3 -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port 29555 bench.py \
+python3 -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port 29555 bench.py --full \
   --gpus "$N" --steps 10 --warmup 3 --verify > "$OUT/bench_n$N.json" 2> "$OUT/bench_n$N.err"
 RC_BENCH=$?
 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-side-legs > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"

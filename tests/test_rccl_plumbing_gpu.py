@@ -64,7 +64,7 @@ def test_bench_two_rank_path_runs_to_completion():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29541", os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--points", "200000",
+           "--master-port", "29541", os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--points", "200000",
            "--frames", "8", "--steps", "1", "--warmup", "1", "--roofline-points", "2000000", "--settle-ms", "0", "--verify",
            "--cpu-points", "100000", "--cpu-frames", "2", "--sharded-legs-points", "150000", "--sharded-legs-frames", "5"]
     proc = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=root)
@@ -85,3 +85,25 @@ def test_bench_two_rank_path_runs_to_completion():
     assert legs["smooth"]["smooth_ms"] > 0 and legs["smooth"]["kept"] > 0 and legs["smooth"]["same_mask_on_every_rank"] is True
     # the verdicts travel as bit-packed slices: three rounds (5 keyframes over 2 ranks) of at most n / 8 bytes (+ padding) per rank
     assert 0 < legs["hpr"]["exchange_bytes_per_rank"] <= 3 * (150000 // 8 + 2)
+
+
+def test_plain_bench_two_rank_path_runs_to_completion():
+    """The same launch without --full: the ranks enter the same collectives when the legs after the timed steps are off,
+    and --verify still compares the gathered colours with a one-GPU run."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+           "--master-port", "29543", os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--points", "200000",
+           "--frames", "8", "--steps", "1", "--warmup", "1", "--settle-ms", "0", "--verify"]
+    proc = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=root)
+    assert proc.returncode == 0, proc.stderr[-2000:]
+    lines = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, proc.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["n_gpus"] == 2 and line["value"] > 0 and line["scaling"] == "strong" and "rehearsal" in line
+    assert line["verify"]["equal_to_one_gpu_run"] is True and line["verify"]["coloured"] > 0
+    assert not any(k in line for k in ("roofline", "cpu_baseline", "sharded_legs", "parity_gate", "kernels_ms"))
