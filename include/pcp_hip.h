@@ -43,7 +43,10 @@ extern "C" {
                                 candidates = -1 after a call served from the whole-run bits;
                                 entry points added, no layout changed: pcp_colour_smooth_local / _packed (PCP_K_COLOUR_SMOOTH = 12,
                                 PCP_K_COUNT 13);
-                                entry points added, no layout changed: pcp_upload_image_jpeg / _async (pcp_jpeg_header) */
+                                entry points added, no layout changed: pcp_upload_image_jpeg / _async (pcp_jpeg_header);
+                                entry points added, no layout changed: pcp_set_mls_local_plane / pcp_mls_local_plane_samples
+                                (pcp_mls_params.upsampling accepts PCP_UPSAMPLING_SAMPLE_LOCAL_PLANE; older libraries refuse
+                                it with PCP_ERR_INVALID) */
 
 #define PCP_OK 0
 #define PCP_ERR_INVALID (-1) /* bad argument */
@@ -116,6 +119,16 @@ typedef struct pcp_cull_params {
   double hpr_flip_radius; /* ViewCullingParams::hidden_points_removal_max_z = 90000 (view_culling.hpp:14) */
 } pcp_cull_params;
 
+/* pcp_mls_params.upsampling: pcl::MovingLeastSquares::UpsamplingMethod as CloudSmooth::process selects it
+ * (PCP/src/cloudSmooth.cpp:133-152).  These are this library's codes, not the positions in the reference's enum
+ * (cloudSmooth.hpp:13-19 orders SAMPLE_LOCAL_PLANE 0 .. VOXEL_GRID_DILATION 2); RANDOM_UNIFORM_DENSITY has none (its
+ * samples come from an unseeded generator shared by threads: no run of the reference can be reproduced). */
+#define PCP_UPSAMPLING_NONE 0
+#define PCP_UPSAMPLING_SAMPLE_LOCAL_PLANE 1 /* a disk of samples per fitted point, pcp_set_mls_local_plane */
+#define PCP_UPSAMPLING_VOXEL_GRID_DILATION 3
+/* most samples per axis of the SAMPLE_LOCAL_PLANE table: radius / step <= PCP_MLS_SLP_MAX_RATIO */
+#define PCP_MLS_SLP_MAX_RATIO 512
+
 /* MLSParameters, PCP/include/cloudSmooth.hpp:21-36; values
  * PCP/src/PointCloudProcessor.cpp:67-86. */
 typedef struct pcp_mls_params {
@@ -123,7 +136,7 @@ typedef struct pcp_mls_params {
   double sqr_gauss_param;
   int32_t polynomial_order;
   int32_t compute_normals;
-  int32_t upsampling; /* 0 NONE, 3 VOXEL_GRID_DILATION (cloudSmooth.hpp enum order) */
+  int32_t upsampling; /* PCP_UPSAMPLING_NONE / _SAMPLE_LOCAL_PLANE / _VOXEL_GRID_DILATION (this library's codes) */
   int32_t vgd_iterations;
   float vgd_voxel_size;
   int32_t sor_mean_k;   /* 60  (PointCloudProcessor.cpp:84) */
@@ -140,7 +153,7 @@ enum {
   PCP_K_MLS_FIT = 5,    /* MLS radius search + polynomial fit + projection */
   PCP_K_MISC = 6,       /* fills, compaction, permutation */
   PCP_K_SOR = 7,        /* StatisticalOutlierRemoval kNN mean distance */
-  PCP_K_MLS_VOXEL = 8,  /* VOXEL_GRID_DILATION upsampling */
+  PCP_K_MLS_VOXEL = 8,  /* upsampling emission (VOXEL_GRID_DILATION, SAMPLE_LOCAL_PLANE) */
   PCP_K_TILE_MASK = 9,  /* tile x keyframe visibility masks (conservative culling) */
   PCP_K_NID = 10,       /* NID joint histograms (value + SE(3) tangent gradient) */
   PCP_K_HPR = 11,       /* hidden_points_removal: flip, binning, per-candidate hull membership */
@@ -360,9 +373,26 @@ int pcp_colour_smooth_local_packed(pcp_context *ctx, float radius, const uint32_
 
 /* ---- MLS (CloudSmooth::process, PCP/src/cloudSmooth.cpp:77-185) ---------- */
 /* pcl::MovingLeastSquares on the uploaded cloud (radius search + order-2 fit +
- * SIMPLE projection; upsampling NONE or VOXEL_GRID_DILATION).  Results stay on
- * the device; *out_count = number of output points. */
+ * SIMPLE projection; upsampling NONE, SAMPLE_LOCAL_PLANE or VOXEL_GRID_DILATION).  Results stay on
+ * the device; *out_count = number of output points.
+ * SAMPLE_LOCAL_PLANE: every fitted point (>= 3 neighbours) emits one row per sample (u, v) of the table
+ * pcp_mls_local_plane_samples returns for the context's (radius, step), in table order, projected onto its fitted
+ * polynomial (the plane when the polynomial was not fitted); rows grouped by source point in ascending input index.
+ * Rows = table size x fitted points, < 2^31 and within device memory, else PCP_ERR_NOMEM before any row is allocated. */
 int pcp_mls_process(pcp_context *ctx, const pcp_mls_params *p, int64_t *out_count);
+/* SAMPLE_LOCAL_PLANE's upsampling_radius / upsampling_step (MLSParameters slp_upsampling_radius / _stepsize,
+ * cloudSmooth.hpp:28-29; the reference sets 0.05 / 0.01, PointCloudProcessor.cpp:74-75, which pcp_create sets too).
+ * Both finite and > 0, radius / step <= PCP_MLS_SLP_MAX_RATIO, and both representable as positive finite floats;
+ * else PCP_ERR_INVALID and the setting is unchanged. */
+int pcp_set_mls_local_plane(pcp_context *ctx, double upsampling_radius, double upsampling_step);
+/* The SAMPLE_LOCAL_PLANE table, host only (no context, no GPU): MovingLeastSquares::computeMLSPointNormal's loop
+ *   for (float u = -(float)R; u <= R; u += (float)S) for (float v = -(float)R; v <= R; v += (float)S)
+ *     if (u * u + v * v < R * R) emit(u, v)
+ * restated exactly (fp32 products and sum without fusion, compared in double) [upstream].  The table is neither the
+ * integer lattice nor symmetric: (0.05, 0.01) gives 79 samples.  *out_count = the table's size; up to `capacity`
+ * samples go to out_u / out_v (either nullable) in emission order.  Arguments as pcp_set_mls_local_plane, else
+ * PCP_ERR_INVALID. */
+int pcp_mls_local_plane_samples(double radius, double step, int64_t capacity, float *out_u, float *out_v, int64_t *out_count);
 /* Multi-GPU form: the whole cloud is uploaded on every rank and this rank fits
  * only the queries index_begin <= i < index_end (upsampling NONE).  Outputs as pcp_mls_process. */
 int pcp_mls_process_shard(pcp_context *ctx, const pcp_mls_params *p, int64_t index_begin, int64_t index_end,
@@ -391,7 +421,13 @@ int pcp_mls_fetch(pcp_context *ctx, int64_t capacity, float *out_xyz, float *out
                   int32_t *out_index);
 /* CloudSmooth::process end to end on the device: SOR(sor_mean_k, sor_std_mul) ->
  * MovingLeastSquares (+ upsampling) -> SOR, cloudSmooth.cpp:109-164.  Results through
- * pcp_mls_fetch; out_index refers to the uploaded cloud. */
+ * pcp_mls_fetch; out_index refers to the uploaded cloud.
+ * SAMPLE_LOCAL_PLANE: the fit runs on the first filter's survivors exactly as pcp_mls_process runs on an upload of them
+ * (ascending input index, the same grids), so the rows before the last filter are that call's rows bit for bit; the
+ * survivors of the last filter keep that row order.  The last filter's cost grows with rows x rows thrown off their surface
+ * by broken fits, so the chain refuses with PCP_ERR_RANGE, before that filter runs, more than 2^24 rows, and rows whose box
+ * would force the filter's grid cells beyond 2 * step * sqrt((sor_mean_k + 1) / pi).  The query sharding (_shard, _slab) and the streamed forms
+ * (pcp_mls_stream_begin, pcp_cloud_smooth_stream_begin) refuse SAMPLE_LOCAL_PLANE with PCP_ERR_INVALID. */
 int pcp_cloud_smooth(pcp_context *ctx, const pcp_mls_params *p, int64_t *out_count);
 
 /* CloudSmooth::process WHOLE for clouds whose dilated voxel set exceeds one result (PCP/src/cloudSmooth.cpp:109-164 with the

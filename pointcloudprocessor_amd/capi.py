@@ -63,6 +63,14 @@ MATCH_IDENTITY, MATCH_ROUNDTRIP = 0, 1
 MATCH_RADIUS = 2
 
 
+# MLSParams.upsampling (pcp_hip.h PCP_UPSAMPLING_*: this library's codes, not the reference enum's positions)
+UPSAMPLING_NONE = 0
+UPSAMPLING_SAMPLE_LOCAL_PLANE = 1
+UPSAMPLING_VOXEL_GRID_DILATION = 3
+# SAMPLE_LOCAL_PLANE tables: radius / step <= MLS_SLP_MAX_RATIO (pcp_set_mls_local_plane)
+MLS_SLP_MAX_RATIO = 512
+
+
 class MLSParams(C.Structure):
     _fields_ = [
         ("search_radius", C.c_double),
@@ -129,6 +137,22 @@ def load(build_if_needed: bool = True) -> C.CDLL:
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def mls_local_plane_samples(radius: float, step: float):
+    """(u, v) float32 arrays of the SAMPLE_LOCAL_PLANE table for (radius, step) in emission order
+    (pcp_mls_local_plane_samples: host only, no GPU)."""
+    L = load()
+    n = C.c_int64()
+    rc = L.pcp_mls_local_plane_samples(C.c_double(radius), C.c_double(step), C.c_int64(0), None, None, C.byref(n))
+    if rc != PCP_OK:
+        raise PcpError(rc, f"pcp_mls_local_plane_samples: radius {radius!r}, step {step!r} refused")
+    u = np.empty(n.value, np.float32)
+    v = np.empty(n.value, np.float32)
+    rc = L.pcp_mls_local_plane_samples(C.c_double(radius), C.c_double(step), C.c_int64(n.value), _ptr(u), _ptr(v), C.byref(n))
+    if rc != PCP_OK:
+        raise PcpError(rc, "pcp_mls_local_plane_samples failed")
+    return u, v
 
 
 def default_camera() -> Camera:
@@ -457,6 +481,11 @@ class Context:
         return out, cnt.value
 
     # -- MLS --------------------------------------------------------------
+    def set_mls_local_plane(self, upsampling_radius: float = 0.05, upsampling_step: float = 0.01):
+        """SAMPLE_LOCAL_PLANE's radius and step for the context's later MLS calls (pcp_create sets the reference's
+        0.05 / 0.01, PointCloudProcessor.cpp:74-75)."""
+        self._check(self.lib.pcp_set_mls_local_plane(self.h, C.c_double(upsampling_radius), C.c_double(upsampling_step)))
+
     def mls_process(self, params: MLSParams) -> int:
         cnt = C.c_int64()
         self._check(self.lib.pcp_mls_process(self.h, C.byref(params), C.byref(cnt)))

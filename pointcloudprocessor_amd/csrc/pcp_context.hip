@@ -323,7 +323,7 @@ __global__ __launch_bounds__(kUpBlock) void k_up_gather(const float *__restrict_
   sx[j] = x[i];
   sy[j] = y[i];
   sz[j] = z[i];
-  inv_perm[i] = static_cast<int32_t>(j);
+  if (inv_perm) inv_perm[i] = static_cast<int32_t>(j);
 }
 
 // bounding sphere of `span` consecutive Morton points per workgroup-slice: span = 64 (one wavefront per tile) or
@@ -416,6 +416,86 @@ __global__ __launch_bounds__(kUpBlock) void k_up_deinterleave(const uint32_t *__
   z[i] = __uint_as_float(p[2]);
 }
 
+// The upload's spatial order of n device points (planes dx dy dz, n > 0): the box of the finite coordinates (*mn, *mx;
+// *out_nonfinite = points with a non-finite one), 30-bit Morton keys over that box, a stable LSD radix sort (4 passes of
+// 8 bits); perm[j] = the point at place j, (sx, sy, sz)[j] its coordinates, inv_perm[perm[j]] = j (nullable).  Every
+// uploaded cloud is ordered by it; pcp_cloud_smooth orders the survivors of its first filter by it as an upload of them
+// would be (the SAMPLE_LOCAL_PLANE chain).
+int spatial_order(pcp_context *ctx, const float *dx, const float *dy, const float *dz, int64_t n, int32_t *perm, float *sx,
+                  float *sy, float *sz, int32_t *inv_perm, float mn[3], float mx[3], unsigned long long *out_nonfinite) {
+  hipStream_t st = ctx->stream;
+  const size_t sn = static_cast<size_t>(n);
+  // ---- bounding box ----
+  const uint32_t bb_blocks = std::min<uint32_t>(up_blocks(n), 1024u);
+  DevBuf<float> partial;
+  PCP_HIP_TRY(ctx, partial.ensure(static_cast<size_t>(bb_blocks) * 6));
+  PCP_HIP_TRY(ctx, ctx->s_counter.ensure(4));
+  PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->s_counter.p, 0, 8, st));
+  hipLaunchKernelGGL(k_up_bbox, dim3(bb_blocks), dim3(kUpBlock), 0, st, dx, dy, dz, n, partial.p, ctx->s_counter.p);
+  std::vector<float> hp(static_cast<size_t>(bb_blocks) * 6);
+  unsigned long long nonfinite = 0;
+  PCP_HIP_TRY(ctx, hipMemcpyAsync(hp.data(), partial.p, hp.size() * 4, hipMemcpyDeviceToHost, st));
+  PCP_HIP_TRY(ctx, hipMemcpyAsync(&nonfinite, ctx->s_counter.p, 8, hipMemcpyDeviceToHost, st));
+  PCP_HIP_TRY(ctx, hipStreamSynchronize(st));
+  if (out_nonfinite) *out_nonfinite = nonfinite;
+  partial.release();
+  for (int a = 0; a < 3; ++a) {
+    mn[a] = FLT_MAX;
+    mx[a] = -FLT_MAX;
+  }
+  for (uint32_t b = 0; b < bb_blocks; ++b)
+    for (int a = 0; a < 3; ++a) {
+      mn[a] = std::min(mn[a], hp[static_cast<size_t>(b) * 6 + a]);
+      mx[a] = std::max(mx[a], hp[static_cast<size_t>(b) * 6 + 3 + a]);
+    }
+  float sc[3];
+  for (int a = 0; a < 3; ++a) {
+    if (mn[a] > mx[a]) mn[a] = mx[a] = 0.0f;  // no finite coordinate at all
+    const float ext = mx[a] - mn[a];
+    sc[a] = (ext > 0.0f && ext < FLT_MAX) ? 1023.999f / ext : 0.0f;
+  }
+  // ---- Morton keys + stable LSD radix sort (key, input index) ----
+  const int64_t blocks = up_blocks(n);
+  DevBuf<uint32_t> key_a, key_b;
+  DevBuf<int32_t> val_b, hist;
+  PCP_HIP_TRY(ctx, key_a.ensure(sn + 4));
+  PCP_HIP_TRY(ctx, key_b.ensure(sn + 4));
+  PCP_HIP_TRY(ctx, val_b.ensure(sn + 4));
+  const int64_t hm = 256 * blocks;
+  PCP_HIP_TRY(ctx, hist.ensure(static_cast<size_t>(hm) + 8));
+  const int64_t scan_tiles = std::max<int64_t>(1, (hm + 1 + kScanTile - 1) / kScanTile);
+  PCP_HIP_TRY(ctx, ctx->s_tiles.ensure(static_cast<size_t>(scan_tiles) + 4));
+  hipLaunchKernelGGL(k_up_keys, dim3(up_blocks(n)), dim3(kUpBlock), 0, st, dx, dy, dz, n, mn[0], mn[1], mn[2], sc[0], sc[1],
+                     sc[2], key_a.p, perm);
+  uint32_t *kin = key_a.p, *kout = key_b.p;
+  int32_t *vin = perm, *vout = val_b.p;
+  for (int pass = 0; pass < 4; ++pass) {  // 30 key bits: 4 passes of 8 (an even count: the result lands in perm)
+    const int32_t shift = 8 * pass;
+    hipLaunchKernelGGL(k_up_radix_hist, dim3(static_cast<uint32_t>(blocks)), dim3(kUpBlock), 0, st, kin, n, shift, hist.p, blocks);
+    PCP_HIP_TRY(ctx, hipMemsetAsync(hist.p + hm, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_scan_tile_sums, dim3(static_cast<uint32_t>(scan_tiles)), dim3(kScanBlock), 0, st, hist.p, hm + 1,
+                       ctx->s_tiles.p);
+    hipLaunchKernelGGL(k_scan_tile_offsets, dim3(1), dim3(kScanSingle), 0, st, ctx->s_tiles.p, scan_tiles,
+                       static_cast<unsigned long long *>(nullptr));
+    hipLaunchKernelGGL(k_scan_apply, dim3(static_cast<uint32_t>(scan_tiles)), dim3(kScanBlock), 0, st, hist.p, hm + 1,
+                       ctx->s_tiles.p, hist.p);
+    hipLaunchKernelGGL(k_up_radix_scatter, dim3(static_cast<uint32_t>(blocks)), dim3(kUpBlock), 0, st, kin, vin, n, shift,
+                       hist.p, blocks, kout, vout);
+    std::swap(kin, kout);
+    std::swap(vin, vout);
+  }
+  PCP_HIP_TRY(ctx, hipGetLastError());
+  // ---- Morton-ordered copy ----
+  hipLaunchKernelGGL(k_up_gather, dim3(up_blocks(n)), dim3(kUpBlock), 0, st, dx, dy, dz, perm, n, sx, sy, sz, inv_perm);
+  PCP_HIP_TRY(ctx, hipGetLastError());
+  PCP_HIP_TRY(ctx, hipStreamSynchronize(st));  // (the sort's scratch is freed here)
+  key_a.release();
+  key_b.release();
+  val_b.release();
+  hist.release();
+  return PCP_OK;
+}
+
 // Either (x, y, z) SoA host arrays, or `aos` = n records of `stride` bytes starting with x y z (fp32).
 static int store_cloud(pcp_context *ctx, const float *x, const float *y, const float *z, int64_t n,
                        const void *aos = nullptr, int64_t stride = 0) {
@@ -458,70 +538,18 @@ static int store_cloud(pcp_context *ctx, const float *x, const float *y, const f
     PCP_HIP_TRY(ctx, hipMemcpyAsync(dy, y, sn * 4, hipMemcpyHostToDevice, st));
     PCP_HIP_TRY(ctx, hipMemcpyAsync(dz, z, sn * 4, hipMemcpyHostToDevice, st));
   }
-  // ---- bounding box ----
-  const uint32_t bb_blocks = std::min<uint32_t>(up_blocks(n), 1024u);
-  DevBuf<float> partial;
-  PCP_HIP_TRY(ctx, partial.ensure(static_cast<size_t>(bb_blocks) * 6));
-  PCP_HIP_TRY(ctx, ctx->s_counter.ensure(4));
-  PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->s_counter.p, 0, 8, st));
-  hipLaunchKernelGGL(k_up_bbox, dim3(bb_blocks), dim3(kUpBlock), 0, st, dx, dy, dz, n, partial.p, ctx->s_counter.p);
-  std::vector<float> hp(static_cast<size_t>(bb_blocks) * 6);
+  float mn[3], mx[3];
   unsigned long long nonfinite = 0;
-  PCP_HIP_TRY(ctx, hipMemcpyAsync(hp.data(), partial.p, hp.size() * 4, hipMemcpyDeviceToHost, st));
-  PCP_HIP_TRY(ctx, hipMemcpyAsync(&nonfinite, ctx->s_counter.p, 8, hipMemcpyDeviceToHost, st));
-  PCP_HIP_TRY(ctx, hipStreamSynchronize(st));
-  ctx->nonfinite_points = static_cast<int64_t>(nonfinite);
-  partial.release();
+  PCP_HIP_TRY(ctx, ctx->inv_perm.ensure(plane + 4));
+  if (int rc = spatial_order(ctx, dx, dy, dz, n, ctx->perm.p, ctx->sxyz.p, ctx->sxyz.p + plane, ctx->sxyz.p + 2 * plane,
+                             ctx->inv_perm.p, mn, mx, &nonfinite))
+    return rc;
   raw.release();
-  float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-  for (uint32_t b = 0; b < bb_blocks; ++b)
-    for (int a = 0; a < 3; ++a) {
-      mn[a] = std::min(mn[a], hp[static_cast<size_t>(b) * 6 + a]);
-      mx[a] = std::max(mx[a], hp[static_cast<size_t>(b) * 6 + 3 + a]);
-    }
-  float sc[3];
+  ctx->nonfinite_points = static_cast<int64_t>(nonfinite);
   for (int a = 0; a < 3; ++a) {
-    if (mn[a] > mx[a]) mn[a] = mx[a] = 0.0f;  // no finite coordinate at all
     ctx->host_min[a] = mn[a];
     ctx->host_max[a] = mx[a];
-    const float ext = mx[a] - mn[a];
-    sc[a] = (ext > 0.0f && ext < FLT_MAX) ? 1023.999f / ext : 0.0f;
   }
-  // ---- Morton keys + stable LSD radix sort (key, input index) ----
-  const int64_t blocks = up_blocks(n);
-  DevBuf<uint32_t> key_a, key_b;
-  DevBuf<int32_t> val_b, hist;
-  PCP_HIP_TRY(ctx, key_a.ensure(sn + 4));
-  PCP_HIP_TRY(ctx, key_b.ensure(sn + 4));
-  PCP_HIP_TRY(ctx, val_b.ensure(sn + 4));
-  const int64_t hm = 256 * blocks;
-  PCP_HIP_TRY(ctx, hist.ensure(static_cast<size_t>(hm) + 8));
-  const int64_t scan_tiles = std::max<int64_t>(1, (hm + 1 + kScanTile - 1) / kScanTile);
-  PCP_HIP_TRY(ctx, ctx->s_tiles.ensure(static_cast<size_t>(scan_tiles) + 4));
-  hipLaunchKernelGGL(k_up_keys, dim3(up_blocks(n)), dim3(kUpBlock), 0, st, dx, dy, dz, n, mn[0], mn[1], mn[2], sc[0], sc[1],
-                     sc[2], key_a.p, ctx->perm.p);
-  uint32_t *kin = key_a.p, *kout = key_b.p;
-  int32_t *vin = ctx->perm.p, *vout = val_b.p;
-  for (int pass = 0; pass < 4; ++pass) {  // 30 key bits: 4 passes of 8 (an even count: the result lands in perm)
-    const int32_t shift = 8 * pass;
-    hipLaunchKernelGGL(k_up_radix_hist, dim3(static_cast<uint32_t>(blocks)), dim3(kUpBlock), 0, st, kin, n, shift, hist.p, blocks);
-    PCP_HIP_TRY(ctx, hipMemsetAsync(hist.p + hm, 0, sizeof(int32_t), st));
-    hipLaunchKernelGGL(k_scan_tile_sums, dim3(static_cast<uint32_t>(scan_tiles)), dim3(kScanBlock), 0, st, hist.p, hm + 1,
-                       ctx->s_tiles.p);
-    hipLaunchKernelGGL(k_scan_tile_offsets, dim3(1), dim3(kScanSingle), 0, st, ctx->s_tiles.p, scan_tiles,
-                       static_cast<unsigned long long *>(nullptr));
-    hipLaunchKernelGGL(k_scan_apply, dim3(static_cast<uint32_t>(scan_tiles)), dim3(kScanBlock), 0, st, hist.p, hm + 1,
-                       ctx->s_tiles.p, hist.p);
-    hipLaunchKernelGGL(k_up_radix_scatter, dim3(static_cast<uint32_t>(blocks)), dim3(kUpBlock), 0, st, kin, vin, n, shift,
-                       hist.p, blocks, kout, vout);
-    std::swap(kin, kout);
-    std::swap(vin, vout);
-  }
-  PCP_HIP_TRY(ctx, hipGetLastError());
-  // ---- Morton-ordered copy and the bounding spheres ----
-  PCP_HIP_TRY(ctx, ctx->inv_perm.ensure(plane + 4));
-  hipLaunchKernelGGL(k_up_gather, dim3(up_blocks(n)), dim3(kUpBlock), 0, st, dx, dy, dz, ctx->perm.p, n, ctx->sxyz.p,
-                     ctx->sxyz.p + plane, ctx->sxyz.p + 2 * plane, ctx->inv_perm.p);
   const int64_t tiles = (n + 63) / 64, groups = (tiles + 15) / 16;
   PCP_HIP_TRY(ctx, ctx->tile_sphere.ensure(static_cast<size_t>(tiles + groups) * 4 + 4));
   float4 *sph = reinterpret_cast<float4 *>(ctx->tile_sphere.p);
@@ -532,10 +560,6 @@ static int store_cloud(pcp_context *ctx, const float *x, const float *y, const f
   PCP_HIP_TRY(ctx, hipGetLastError());
   ctx->n_tiles = tiles;
   PCP_HIP_TRY(ctx, hipStreamSynchronize(st));  // the host arrays may be reused by the caller
-  key_a.release();
-  key_b.release();
-  val_b.release();
-  hist.release();
   return PCP_OK;
 }
 
@@ -692,6 +716,8 @@ void pcp_destroy(pcp_context *ctx) {
   ctx->s_kth.release();
   ctx->css_words.release();
   ctx->m_state.release();
+  ctx->slp_table.release();
+  ctx->c_perm.release();
   ctx->m_flag.release();
   ctx->intensity.release();
   for (auto &lane : ctx->hpr_lane) lane.release();

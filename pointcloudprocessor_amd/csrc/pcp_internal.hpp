@@ -279,6 +279,10 @@ struct pcp_context {
   pcp::DevBuf<float> m_tmp;      // 8 floats per input point (xyz, normal, curvature, pad: one 32-byte sector), input order
   pcp::DevBuf<float> s_dist;     // StatisticalOutlierRemoval: mean kNN distance per point
   pcp::DevBuf<double> m_state;   // per-point MLSResult (mean, axes, c_vec ...) for upsampling
+  double slp_radius = 0.05, slp_step = 0.01;  // SAMPLE_LOCAL_PLANE (pcp_set_mls_local_plane; PointCloudProcessor.cpp:74-75)
+  pcp::DevBuf<float> slp_table;  // its sample table, u v interleaved, for slp_table_of (radius, step)
+  double slp_table_of[2] = {0.0, 0.0};
+  pcp::DevBuf<int32_t> c_perm;   // pcp_cloud_smooth SAMPLE_LOCAL_PLANE: spatial order of the first filter's survivors
   pcp::DevBuf<uint8_t> m_flag;   // n
   pcp::DevBuf<double> m_sums;    // SOR statistics
   pcp::DevBuf<int32_t> c_index;  // pcp_cloud_smooth: survivors of the 1st SOR (indices into the uploaded cloud)
@@ -431,6 +435,10 @@ struct TexelSource {
 };
 // count > 1 only for a block of keyframes staged together (pcp_upload_images_block); wait: synchronise the lane
 int upload_texels(pcp_context *ctx, const char *who, int32_t frame, int32_t count, bool block, bool wait, TexelSource &src);
+
+// the upload's spatial order of n > 0 device points (pcp_context.hip): box, Morton keys, stable radix sort, ordered copy
+int spatial_order(pcp_context *ctx, const float *dx, const float *dy, const float *dz, int64_t n, int32_t *perm, float *sx,
+                  float *sy, float *sz, int32_t *inv_perm, float mn[3], float mx[3], unsigned long long *out_nonfinite);
 
 // ordered compaction of a device byte-flag array (pcp_colour.hip): index list (nullable) + count
 int compact_flags(pcp_context *ctx, const uint8_t *flags, int64_t n, int32_t *out_index, int64_t capacity,

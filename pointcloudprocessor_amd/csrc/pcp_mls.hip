@@ -34,6 +34,11 @@ namespace pcp {
 constexpr int kMB = 256;
 constexpr double kMaxGridCells = 536870912.0;      // 2^29: dense table of cell starts
 constexpr double kMaxSparseCells = 34359738368.0;  // 2^35: bitmap (4 GiB) + running popcounts (2 GiB)
+// pcp_cloud_smooth with SAMPLE_LOCAL_PLANE: most rows its trailing outlier removal takes.  Broken fits throw rows off their
+// surface, each such row is a stray of the filter that reads the whole cloud, so the filter's cost grows with rows x strays:
+// 10.2 M rows of a 300 k-point synthetic map 6.7 s, 59 M rows of 1 M points more than 100 s, 602 M rows of C3 more than 140 s
+// 
+constexpr int64_t kSlpChainMaxRows = int64_t(1) << 24;
 
 // cell id and arrival rank of every input point; histogram in `count`.  The views are spatially ordered (Morton copy of
 // the upload, survivors of it), so a wavefront's 64 points fall into a handful of cells: the lanes of one cell share one
@@ -2065,6 +2070,106 @@ __global__ __launch_bounds__(kMB) void k_remap_index(int32_t *__restrict__ index
   if (k < m) index[k] = map[index[k]];
 }
 
+// ---- SAMPLE_LOCAL_PLANE (MovingLeastSquares::computeMLSPointNormal, mls.hpp [upstream]) ----
+// Row r of the emission = sample r % T of the table, projected onto the surface of the fitted point list[r / T]
+// (MLSResult::projectPointSimpleToPolynomialSurface): one lane per row, the T lanes of a point read its state once from
+// cache and write their rows next to each other.
+struct SlpArgs {
+  const double *state;     // kMlsState doubles per point (k_mls_fit)
+  const int32_t *list;     // rank -> point (the ordered compaction of the fit flags)
+  const float2 *table;     // T samples (u, v)
+  const int32_t *map;      // point -> the index the rows carry (nullable: the point itself)
+  uint32_t T, rows;        // rows = T x fitted < 2^31
+  int32_t order_poly;
+  float *xyz, *normal, *curv;  // AoS rows (pcp_mls_fetch's layout)
+  int32_t *index;
+  float *px, *py, *pz;     // nullable: the rows' positions once more as SoA planes (the chain's last filter reads them)
+};
+
+__global__ __launch_bounds__(kMB) void k_slp_emit(SlpArgs a) {
+  const uint32_t r = blockIdx.x * kMB + threadIdx.x;
+  if (r >= a.rows) return;
+  const uint32_t rank = r / a.T, s = r - rank * a.T;
+  const int32_t pt = a.list[rank];
+  const double *st = a.state + static_cast<int64_t>(pt) * kMlsState;
+  const float2 uvf = a.table[s];
+  const double u = uvf.x, v = uvf.y;  // the float table values, widened
+  const double m0 = st[0], m1 = st[1], m2 = st[2];
+  const double n0 = st[3], n1 = st[4], n2 = st[5];
+  const double u0 = st[6], u1 = st[7], u2 = st[8];
+  const double v0 = st[9], v1 = st[10], v2 = st[11];
+  // an invalid plane (st[20] == 0) holds zeros but for mean = the query point: its rows are that point with a zero
+  // normal -- the row NONE emits for it, once per sample
+  double w = 0.0, nx = n0, ny = n1, nz = n2;
+  if (a.order_poly > 1 && st[20] == 2.0 && isfinite(st[12])) {
+    // getPolynomialPartialDerivative(u, v) for order 2, PCL's loop unrolled in its own operation order:
+    // monomials j = (ui, vi) = (0,0) (0,1) (0,2) (1,0) (1,1) (2,0)
+    const double c0 = st[12], c1 = st[13], c2 = st[14], c3 = st[15], c4 = st[16], c5 = st[17];
+    const double up1 = 1.0 * u, up2 = up1 * u;
+    const double vp1 = 1.0 * v, vp2 = vp1 * v;
+    double z = 0.0, zu = 0.0, zv = 0.0;
+    z += 1.0 * 1.0 * c0;
+    z += 1.0 * vp1 * c1;
+    zv += c1 * 1 * 1.0 * 1.0;
+    z += 1.0 * vp2 * c2;
+    zv += c2 * 2 * 1.0 * vp1;
+    z += up1 * 1.0 * c3;
+    zu += c3 * 1 * 1.0 * 1.0;
+    z += up1 * vp1 * c4;
+    zu += c4 * 1 * 1.0 * vp1;
+    zv += c4 * 1 * up1 * 1.0;
+    z += up2 * 1.0 * c5;
+    zu += c5 * 2 * up1 * 1.0;
+    w = z;
+    nx = n0 - (zu * u0 + zv * v0);
+    ny = n1 - (zu * u1 + zv * v1);
+    nz = n2 - (zu * u2 + zv * v2);
+    const double l2 = (nx * nx + ny * ny) + nz * nz;  // Eigen normalize(): divided by the norm when it is > 0
+    if (l2 > 0.0) {
+      const double l = sqrt(l2);
+      nx /= l;
+      ny /= l;
+      nz /= l;
+    }
+  }
+  const float x = static_cast<float>(((m0 + u * u0) + v * v0) + w * n0);
+  const float y = static_cast<float>(((m1 + u * u1) + v * v1) + w * n1);
+  const float zz = static_cast<float>(((m2 + u * u2) + v * v2) + w * n2);
+  const size_t o = static_cast<size_t>(r);
+  a.xyz[3 * o] = x;
+  a.xyz[3 * o + 1] = y;
+  a.xyz[3 * o + 2] = zz;
+  a.normal[3 * o] = static_cast<float>(nx);
+  a.normal[3 * o + 1] = static_cast<float>(ny);
+  a.normal[3 * o + 2] = static_cast<float>(nz);
+  a.curv[o] = static_cast<float>(st[18]);
+  a.index[o] = a.map ? a.map[pt] : pt;
+  if (a.px) {
+    a.px[o] = x;
+    a.py[o] = y;
+    a.pz[o] = zz;
+  }
+}
+
+// the first filter's keep flags (view order) -> flags in the caller's order
+__global__ __launch_bounds__(kMB) void k_flags_to_caller(const uint8_t *__restrict__ flag, const int32_t *__restrict__ remap,
+                                                         int64_t n, uint8_t *__restrict__ out) {
+  const int64_t v = static_cast<int64_t>(blockIdx.x) * kMB + threadIdx.x;
+  if (v < n) out[remap[v]] = flag[v];
+}
+
+// out planes [k] = the caller's point list[k] (x y z planes of the upload in the caller's order)
+__global__ __launch_bounds__(kMB) void k_gather_caller(const float *__restrict__ x, const float *__restrict__ y,
+                                                       const float *__restrict__ z, const int32_t *__restrict__ list, int64_t m,
+                                                       float *__restrict__ ox, float *__restrict__ oy, float *__restrict__ oz) {
+  const int64_t k = static_cast<int64_t>(blockIdx.x) * kMB + threadIdx.x;
+  if (k >= m) return;
+  const int32_t i = list[k];
+  ox[k] = x[i];
+  oy[k] = y[i];
+  oz[k] = z[i];
+}
+
 static inline uint32_t blocks_of(int64_t n) { return static_cast<uint32_t>(std::max<int64_t>(1, div_up(n, kMB))); }
 
 // device-wide exclusive scan of counts[0..m) into out[0..m], out[m] = total
@@ -2611,6 +2716,117 @@ static int voxel_grid_dilation(pcp_context *ctx, const CloudView &cv, const pcp_
   return PCP_OK;
 }
 
+// SAMPLE_LOCAL_PLANE's (radius, step) as pcp_set_mls_local_plane accepts them: PCL loops forever on step <= 0, and the
+// table grows with (radius / step)^2 (at most ~8.2e5 samples at the bound)
+static bool slp_arguments_ok(double radius, double step) {
+  return std::isfinite(radius) && std::isfinite(step) && radius > 0.0 && step > 0.0 && static_cast<float>(step) > 0.0f &&
+         std::isfinite(static_cast<float>(radius)) && radius / step <= static_cast<double>(PCP_MLS_SLP_MAX_RATIO);
+}
+
+// MovingLeastSquares::computeMLSPointNormal's SAMPLE_LOCAL_PLANE loop [upstream]: u and v are floats stepped by the float
+// step, compared with the double radius; the squares and their sum are float operations (no fusion: -ffp-contract=off),
+// the sum is compared with the double radius^2.  Returns the table's size; the first `capacity` samples go to out_u / out_v.
+static int64_t slp_table(double radius, double step, int64_t capacity, float *out_u, float *out_v) {
+  const float r = static_cast<float>(radius), d = static_cast<float>(step);
+  const double rr = radius * radius;
+  int64_t k = 0;
+  for (float u = -r; static_cast<double>(u) <= radius; u += d)
+    for (float v = -r; static_cast<double>(v) <= radius; v += d) {
+      const float uu = u * u;
+      const float vv = v * v;
+      const float sum = uu + vv;
+      if (static_cast<double>(sum) < rr) {
+        if (k < capacity) {
+          if (out_u) out_u[k] = u;
+          if (out_v) out_v[k] = v;
+        }
+        ++k;
+      }
+    }
+  return k;
+}
+
+// the context's table on the device (ctx->slp_table, u v interleaved; rebuilt when the setting changed); *out_T its size
+static int slp_device_table(pcp_context *ctx, int64_t *out_T) {
+  const int64_t T = slp_table(ctx->slp_radius, ctx->slp_step, 0, nullptr, nullptr);
+  *out_T = T;
+  if (ctx->slp_table.p && ctx->slp_table_of[0] == ctx->slp_radius && ctx->slp_table_of[1] == ctx->slp_step) return PCP_OK;
+  std::vector<float> u(static_cast<size_t>(T) + 1), v(static_cast<size_t>(T) + 1), uv(2 * static_cast<size_t>(T) + 2);
+  slp_table(ctx->slp_radius, ctx->slp_step, T, u.data(), v.data());
+  for (int64_t k = 0; k < T; ++k) {
+    uv[2 * static_cast<size_t>(k)] = u[static_cast<size_t>(k)];
+    uv[2 * static_cast<size_t>(k) + 1] = v[static_cast<size_t>(k)];
+  }
+  PCP_HIP_TRY(ctx, ctx->slp_table.ensure(uv.size()));
+  PCP_HIP_TRY(ctx, hipMemcpyAsync(ctx->slp_table.p, uv.data(), uv.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // `uv` lives on this stack frame
+  ctx->slp_table_of[0] = ctx->slp_radius;
+  ctx->slp_table_of[1] = ctx->slp_step;
+  return PCP_OK;
+}
+
+// SAMPLE_LOCAL_PLANE after the fit (ctx->m_flag, ctx->m_state over the view's n points): the fitted points in ascending
+// index (one ordered compaction of the flags), T rows each in table order.  chain: the rows carry ctx->c_index[point]
+// and their positions also go to SoA planes in ctx->c_xyz2 (stride (rows + 3) & ~3) for pcp_cloud_smooth's last filter.
+static int slp_emit(pcp_context *ctx, const pcp_mls_params *p, int64_t n, bool chain, int64_t *out_count) {
+  int64_t T = 0;
+  int rc = slp_device_table(ctx, &T);
+  if (rc != PCP_OK) return rc;
+  PCP_HIP_TRY(ctx, ctx->s_cell.ensure(static_cast<size_t>(n) + 4));
+  int64_t fitted = 0;
+  if ((rc = compact_flags(ctx, ctx->m_flag.p, n, ctx->s_cell.p, n, &fitted)) != PCP_OK) return rc;
+  const double rows_d = static_cast<double>(T) * static_cast<double>(fitted);
+  if (rows_d >= 2147483648.0)
+    return set_error(ctx, PCP_ERR_NOMEM, "pcp_mls_process: SAMPLE_LOCAL_PLANE makes %.0f rows (%lld samples x %lld fitted points), "
+                     "more than the 2^31 one result holds", rows_d, (long long)T, (long long)fitted);
+  const int64_t rows = T * fitted;
+  const size_t sr = static_cast<size_t>(rows);
+  size_t free_b = 0, total_b = 0;
+  PCP_HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
+  // (the memory check of the voxel emission: 78 B per row covers the rows, their compaction by the last filter and its grid)
+  auto short_of_memory = [&]() {
+    return rows_d * 78.0 > static_cast<double>(free_b) + static_cast<double>(ctx->mls_xyz.count) * 4.0 * 2.4;
+  };
+  if (short_of_memory() && ctx->css_next < 0 && !ctx->css_building && ctx->css_dist.p) {
+    ctx->css_dist.release();  // what an ended stream of the whole chain still holds goes first
+    PCP_HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
+  }
+  if (short_of_memory())
+    return set_error(ctx, PCP_ERR_NOMEM, "pcp_mls_process: SAMPLE_LOCAL_PLANE makes %lld rows (%lld samples x %lld fitted points), "
+                     "more than the device memory holds", (long long)rows, (long long)T, (long long)fitted);
+  PCP_HIP_TRY(ctx, ctx->mls_xyz.ensure(3 * sr + 4));
+  PCP_HIP_TRY(ctx, ctx->mls_normal.ensure(3 * sr + 4));
+  PCP_HIP_TRY(ctx, ctx->mls_curv.ensure(sr + 4));
+  PCP_HIP_TRY(ctx, ctx->mls_index.ensure(sr + 4));
+  SlpArgs e{};
+  e.state = ctx->m_state.p;
+  e.list = ctx->s_cell.p;
+  e.table = reinterpret_cast<const float2 *>(ctx->slp_table.p);
+  e.map = chain ? ctx->c_index.p : nullptr;
+  e.T = static_cast<uint32_t>(T);
+  e.rows = static_cast<uint32_t>(rows);
+  e.order_poly = p->polynomial_order;
+  e.xyz = ctx->mls_xyz.p;
+  e.normal = ctx->mls_normal.p;
+  e.curv = ctx->mls_curv.p;
+  e.index = ctx->mls_index.p;
+  if (chain) {
+    const size_t plane = (sr + 3) & ~size_t(3);
+    PCP_HIP_TRY(ctx, ctx->c_xyz2.ensure(3 * plane + 4));
+    e.px = ctx->c_xyz2.p;
+    e.py = ctx->c_xyz2.p + plane;
+    e.pz = ctx->c_xyz2.p + 2 * plane;
+  }
+  if (rows > 0) {
+    LaunchTimer t(ctx, PCP_K_MLS_VOXEL);
+    hipLaunchKernelGGL(k_slp_emit, dim3(blocks_of(rows)), dim3(kMB), 0, ctx->stream, e);
+    PCP_HIP_TRY(ctx, hipGetLastError());
+  }
+  ctx->mls_count = rows;
+  if (out_count) *out_count = rows;
+  return PCP_OK;
+}
+
 // pcl::StatisticalOutlierRemoval / MovingLeastSquares skip non-finite points one by one; this library refuses the cloud
 // (the reference's maps come out of a PCD file of a LiDAR odometry: finite)
 static int require_finite_cloud(pcp_context *ctx, const char *who) {
@@ -2643,8 +2859,9 @@ static int check_mls_params(pcp_context *ctx, const pcp_mls_params *p) {
   if (p->polynomial_order < 0 || p->polynomial_order > 2)
     return set_error(ctx, PCP_ERR_INVALID, "pcp_mls: polynomial_order %d unsupported (0..2; the reference uses 2)",
                      p->polynomial_order);
-  if (p->upsampling != 0 && p->upsampling != 3)
-    return set_error(ctx, PCP_ERR_INVALID, "pcp_mls: upsampling %d unsupported (0 NONE, 3 VOXEL_GRID_DILATION)",
+  if (p->upsampling != PCP_UPSAMPLING_NONE && p->upsampling != PCP_UPSAMPLING_SAMPLE_LOCAL_PLANE &&
+      p->upsampling != PCP_UPSAMPLING_VOXEL_GRID_DILATION)
+    return set_error(ctx, PCP_ERR_INVALID, "pcp_mls: upsampling %d unsupported (0 NONE, 1 SAMPLE_LOCAL_PLANE, 3 VOXEL_GRID_DILATION)",
                      p->upsampling);
   if (p->upsampling == 3 && (!(p->vgd_voxel_size > 0.0f) || p->vgd_iterations < 0 || p->vgd_iterations > 15))
     return set_error(ctx, PCP_ERR_INVALID, "pcp_mls: vgd_voxel_size must be > 0 and vgd_iterations in 0..15");
@@ -2664,7 +2881,8 @@ static int emission_grid(pcp_context *ctx, const CloudView &cv, const pcp_mls_pa
 
 // MovingLeastSquares::process on a cloud view; results in ctx->mls_* (index = view index)
 // keep_rows: leave the fitted rows in ctx->m_tmp (7 floats at the view index mls_index names) instead of gathering them
-// into the result arrays -- pcp_cloud_smooth picks the survivors of its last filter straight from there
+// into the result arrays -- pcp_cloud_smooth picks the survivors of its last filter straight from there.  With
+// SAMPLE_LOCAL_PLANE it selects slp_emit's chain form (indices through ctx->c_index, positions also as SoA planes).
 static int mls_run(pcp_context *ctx, const CloudView &cv, const pcp_mls_params *p, int64_t *out_count,
                    int64_t q_begin = 0, int64_t q_end = -1, bool keep_rows = false, int64_t stream_capacity = 0,
                    int32_t slab = 0, int32_t n_slabs = 1) {
@@ -2704,7 +2922,7 @@ static int mls_run(pcp_context *ctx, const CloudView &cv, const pcp_mls_params *
   a.j_begin = n_slabs > 1 ? (n * slab / n_slabs) / kFitBlock * kFitBlock : 0;
   a.j_end = (n_slabs > 1 && slab + 1 < n_slabs) ? (n * (slab + 1) / n_slabs) / kFitBlock * kFitBlock : n;
   if (n_slabs > 1) PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->m_flag.p, 0, sn, ctx->stream));  // the other slabs' points: no output
-  if (p->upsampling == 3) {
+  if (p->upsampling == PCP_UPSAMPLING_VOXEL_GRID_DILATION || p->upsampling == PCP_UPSAMPLING_SAMPLE_LOCAL_PLANE) {
     PCP_HIP_TRY(ctx, ctx->m_state.ensure(static_cast<size_t>(kMlsState) * sn + 8));
     // points skipped by the fit (< 3 neighbours) must read as "invalid" later
     PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->m_state.p, 0, static_cast<size_t>(kMlsState) * sn * sizeof(double), ctx->stream));
@@ -2738,6 +2956,7 @@ static int mls_run(pcp_context *ctx, const CloudView &cv, const pcp_mls_params *
     return PCP_OK;
   }
   if (p->upsampling == 3) return voxel_grid_dilation(ctx, cv, p, g, out_count);
+  if (p->upsampling == PCP_UPSAMPLING_SAMPLE_LOCAL_PLANE) return slp_emit(ctx, p, n, keep_rows, out_count);
   // points with < 3 neighbours are dropped; output keeps the input order
   PCP_HIP_TRY(ctx, ctx->mls_index.ensure(sn + 4));
   int64_t m = 0;
@@ -3098,6 +3317,39 @@ static int smooth_first_filter(pcp_context *ctx, const pcp_mls_params *p, const 
   PCP_HIP_TRY(ctx, ctx->c_index.ensure(2 * (static_cast<size_t>(cv0.n) + 4)));
   int32_t *c_pos = ctx->c_index.p + static_cast<size_t>(cv0.n) + 4;  // view positions of the survivors
   int64_t n1 = 0;
+  if (p->upsampling == PCP_UPSAMPLING_SAMPLE_LOCAL_PLANE) {
+    // SAMPLE_LOCAL_PLANE's disks follow the sign of each fitted normal, which the order of the fit's sums can flip near a
+    // tie: cloud 1 is made exactly as an upload of the survivors would be -- the survivors in the caller's order, then the
+    // upload's spatial order over their own box -- so that the fit, and with it every row, is pcp_mls_process's on such an
+    // upload bit for bit (the view order of the upload above is not the spatial order of a subset of it)
+    const size_t sn0 = static_cast<size_t>(cv0.n);
+    PCP_HIP_TRY(ctx, ctx->c_mark.ensure(sn0 + 16));
+    hipLaunchKernelGGL(k_flags_to_caller, dim3(blocks_of(cv0.n)), dim3(kMB), 0, ctx->stream, ctx->m_flag.p, cv0.remap, cv0.n,
+                       ctx->c_mark.p);
+    PCP_HIP_TRY(ctx, hipGetLastError());
+    if ((rc = compact_flags(ctx, ctx->c_mark.p, cv0.n, ctx->c_index.p, cv0.n, &n1)) != PCP_OK) return rc;  // the caller's indices
+    if (n1 == 0) return PCP_OK;
+    const size_t plane1 = (static_cast<size_t>(n1) + 3) & ~size_t(3), plane0 = (sn0 + 3) & ~size_t(3);
+    PCP_HIP_TRY(ctx, ctx->c_xyz.ensure(6 * plane1 + 4));
+    PCP_HIP_TRY(ctx, ctx->c_perm.ensure(static_cast<size_t>(n1) + 4));
+    float *u1 = ctx->c_xyz.p + 3 * plane1;  // the survivors in the caller's order (what an upload of them receives)
+    hipLaunchKernelGGL(k_gather_caller, dim3(blocks_of(n1)), dim3(kMB), 0, ctx->stream, ctx->xyz.p, ctx->xyz.p + plane0,
+                       ctx->xyz.p + 2 * plane0, ctx->c_index.p, n1, u1, u1 + plane1, u1 + 2 * plane1);
+    PCP_HIP_TRY(ctx, hipGetLastError());
+    CloudView cv1{};
+    cv1.x = ctx->c_xyz.p;
+    cv1.y = ctx->c_xyz.p + plane1;
+    cv1.z = ctx->c_xyz.p + 2 * plane1;
+    cv1.remap = ctx->c_perm.p;  // place -> survivor rank (= index of the upload)
+    cv1.n = n1;
+    unsigned long long nonfinite = 0;
+    if ((rc = spatial_order(ctx, u1, u1 + plane1, u1 + 2 * plane1, n1, ctx->c_perm.p, ctx->c_xyz.p, ctx->c_xyz.p + plane1,
+                            ctx->c_xyz.p + 2 * plane1, nullptr, cv1.mn, cv1.mx, &nonfinite)) != PCP_OK)
+      return rc;
+    *out_cv1 = cv1;
+    *out_n1 = n1;
+    return PCP_OK;
+  }
   if ((rc = compact_flags(ctx, ctx->m_flag.p, cv0.n, c_pos, cv0.n, &n1)) != PCP_OK) return rc;
   if (n1 == 0) return PCP_OK;
   const size_t plane1 = (static_cast<size_t>(n1) + 3) & ~size_t(3);
@@ -3144,11 +3396,31 @@ int pcp_mls_process(pcp_context *ctx, const pcp_mls_params *p, int64_t *out_coun
   return mls_run(ctx, uploaded_view(ctx), p, out_count);
 }
 
+int pcp_set_mls_local_plane(pcp_context *ctx, double upsampling_radius, double upsampling_step) {
+  if (!ctx) return PCP_ERR_INVALID;
+  if (!slp_arguments_ok(upsampling_radius, upsampling_step))
+    return set_error(ctx, PCP_ERR_INVALID, "pcp_set_mls_local_plane: radius %g and step %g must be finite floats > 0 with "
+                     "radius / step <= %d", upsampling_radius, upsampling_step, PCP_MLS_SLP_MAX_RATIO);
+  ctx->slp_radius = upsampling_radius;
+  ctx->slp_step = upsampling_step;
+  return PCP_OK;
+}
+
+int pcp_mls_local_plane_samples(double radius, double step, int64_t capacity, float *out_u, float *out_v, int64_t *out_count) {
+  if (out_count) *out_count = 0;
+  if (!slp_arguments_ok(radius, step) || capacity < 0) return PCP_ERR_INVALID;
+  const int64_t T = slp_table(radius, step, capacity, out_u, out_v);
+  if (out_count) *out_count = T;
+  return PCP_OK;
+}
+
 int pcp_mls_stream_begin(pcp_context *ctx, const pcp_mls_params *p, int64_t chunk_capacity, int64_t *out_total,
                          int32_t *out_chunks) {
   if (!ctx) return PCP_ERR_INVALID;
   int rc = check_mls_params(ctx, p);
   if (rc != PCP_OK) return rc;
+  if (p->upsampling == PCP_UPSAMPLING_SAMPLE_LOCAL_PLANE)
+    return set_error(ctx, PCP_ERR_INVALID, "pcp_mls_stream_begin: SAMPLE_LOCAL_PLANE (1) is not streamed (pcp_mls_process emits it)");
   if (p->upsampling != 3) return set_error(ctx, PCP_ERR_INVALID, "pcp_mls_stream_begin: upsampling must be VOXEL_GRID_DILATION (3)");
   if (chunk_capacity < 32768 || chunk_capacity >= (int64_t(1) << 31))
     return set_error(ctx, PCP_ERR_INVALID, "pcp_mls_stream_begin: chunk_capacity must be in [32768, 2^31)");
@@ -3202,6 +3474,9 @@ int pcp_mls_process_shard(pcp_context *ctx, const pcp_mls_params *p, int64_t ind
   if (rc != PCP_OK) return rc;
   if (!ctx->xyz.p) return set_error(ctx, PCP_ERR_STATE, "pcp_mls_process_shard: no cloud uploaded");
   if (int rcf = require_finite_cloud(ctx, "pcp_mls_process_shard")) return rcf;
+  if (p->upsampling == PCP_UPSAMPLING_SAMPLE_LOCAL_PLANE)
+    return set_error(ctx, PCP_ERR_INVALID, "pcp_mls_process_shard: SAMPLE_LOCAL_PLANE (1) is not sharded (its disks follow the sign of each "
+                     "point's fitted normal, which a re-ordered fit may flip): run pcp_mls_process");
   if (p->upsampling != 0)
     return set_error(ctx, PCP_ERR_INVALID, "pcp_mls_process_shard: query sharding supports upsampling NONE only");
   if (index_begin < 0 || index_end > ctx->n || index_begin > index_end)
@@ -3217,6 +3492,9 @@ int pcp_mls_process_slab(pcp_context *ctx, const pcp_mls_params *p, int32_t slab
   if (rc != PCP_OK) return rc;
   if (!ctx->xyz.p) return set_error(ctx, PCP_ERR_STATE, "pcp_mls_process_slab: no cloud uploaded");
   if (int rcf = require_finite_cloud(ctx, "pcp_mls_process_slab")) return rcf;
+  if (p->upsampling == PCP_UPSAMPLING_SAMPLE_LOCAL_PLANE)
+    return set_error(ctx, PCP_ERR_INVALID, "pcp_mls_process_slab: SAMPLE_LOCAL_PLANE (1) is not sharded (its disks follow the sign of each "
+                     "point's fitted normal, which a re-ordered fit may flip): run pcp_mls_process");
   if (p->upsampling != 0)
     return set_error(ctx, PCP_ERR_INVALID, "pcp_mls_process_slab: query sharding supports upsampling NONE only");
   if (n_slabs < 1 || slab < 0 || slab >= n_slabs) return set_error(ctx, PCP_ERR_RANGE, "pcp_mls_process_slab: slab %d of %d", slab, n_slabs);
@@ -3360,8 +3638,10 @@ int pcp_cloud_smooth(pcp_context *ctx, const pcp_mls_params *p, int64_t *out_cou
   // MLS (cloudSmooth.cpp:124-154).  Without upsampling the fitted rows stay where the fit wrote them (7 floats per point
   // of cloud 1): the second filter only needs their positions, and the survivors are picked from there at the end.
   const bool plain = p->upsampling == 0;
+  // SAMPLE_LOCAL_PLANE: the emission writes the rows with the caller's indices and their positions as the planes below
+  const bool slp = p->upsampling == PCP_UPSAMPLING_SAMPLE_LOCAL_PLANE;
   int64_t m = 0;
-  if ((rc = mls_run(ctx, cv1, p, &m, 0, -1, /*keep_rows=*/plain)) != PCP_OK) return rc;
+  if ((rc = mls_run(ctx, cv1, p, &m, 0, -1, /*keep_rows=*/plain || slp)) != PCP_OK) return rc;
   if (m == 0) return PCP_OK;
   const size_t plane2 = (static_cast<size_t>(m) + 3) & ~size_t(3);
   PCP_HIP_TRY(ctx, ctx->c_xyz2.ensure(3 * plane2 + 4));
@@ -3371,7 +3651,7 @@ int pcp_cloud_smooth(pcp_context *ctx, const pcp_mls_params *p, int64_t *out_cou
     hipLaunchKernelGGL(k_remap_index_to, dim3(blocks_of(m)), dim3(kMB), 0, ctx->stream, ctx->mls_index.p, m, ctx->c_index.p,
                        row_caller);
     hipLaunchKernelGGL(k_rows_xyz, dim3(blocks_of(m)), dim3(kMB), 0, ctx->stream, ctx->m_tmp.p, ctx->mls_index.p, m, x2, y2, z2);
-  } else {
+  } else if (!slp) {
     // source indices back to the uploaded cloud
     hipLaunchKernelGGL(k_remap_index, dim3(blocks_of(m)), dim3(kMB), 0, ctx->stream, ctx->mls_index.p, m, ctx->c_index.p);
     hipLaunchKernelGGL(k_deinterleave, dim3(blocks_of(m)), dim3(kMB), 0, ctx->stream, ctx->mls_xyz.p, m, x2, y2, z2);
@@ -3380,9 +3660,34 @@ int pcp_cloud_smooth(pcp_context *ctx, const pcp_mls_params *p, int64_t *out_cou
   // 2nd SOR on the MLS output (cloudSmooth.cpp:160-164)
   CloudView cv2;
   if ((rc = view_of(ctx, x2, y2, z2, m, &cv2)) != PCP_OK) return rc;
-  // (the upsampled cloud: every surface patch of vs^2 carries a column of at least 2 it + 1 voxels)
-  const double dens2 = plain ? 0.0 : (2.0 * p->vgd_iterations + 1.0) / (static_cast<double>(p->vgd_voxel_size) * p->vgd_voxel_size);
-  if ((rc = sor_run(ctx, cv2, p->sor_mean_k, p->sor_std_mul, false, 0, 1, true, nullptr, /*clustered=*/!plain, dens2)) != PCP_OK) return rc;
+  // (the voxel-upsampled cloud: every surface patch of vs^2 carries a column of at least 2 it + 1 voxels; the disks of
+  // SAMPLE_LOCAL_PLANE overlap by an amount the input's density decides, so the density probe sizes their grid)
+  if (slp && m > kSlpChainMaxRows)
+    return set_error(ctx, PCP_ERR_RANGE, "pcp_cloud_smooth: SAMPLE_LOCAL_PLANE's %lld rows exceed the %lld the trailing outlier "
+                     "removal takes (pcp_mls_process emits them; DESIGN.md SLP9)", (long long)m, (long long)kSlpChainMaxRows);
+  if (slp) {
+    // A polynomial fitted within the search radius and evaluated out to the disk's radius can throw a row far off its
+    // surface (a near-singular fit: rows hundreds of metres away on the synthetic maps), and the filter's grid must span
+    // every row: past kMaxSparseCells cells its cell grows with the box, every query then walks the rows of 27 oversized
+    // cells, and each far row is a stray that reads the whole cloud (measured: 10 M rows of a 300 k-point map, a 0.26 m cell,
+    // 6.7 s; 59 M rows of 1 M points, more than 100 s).  The chain refuses such rows before that filter: a row's k + 1
+    // nearest lie within ~step * sqrt((k + 1) / pi) inside its own disk, and a box that forces the grid's cell beyond twice
+    // times that is refused.
+    const double c_rows = ctx->slp_step * std::sqrt((p->sor_mean_k + 1.0) / 3.14159265358979);
+    const double c_max = 2.0 * c_rows;
+    const double cells = (static_cast<double>(cv2.mx[0] - cv2.mn[0]) / c_max + 1.0) *
+                         (static_cast<double>(cv2.mx[1] - cv2.mn[1]) / c_max + 1.0) *
+                         (static_cast<double>(cv2.mx[2] - cv2.mn[2]) / c_max + 1.0);
+    if (!(cells <= kMaxSparseCells))
+      return set_error(ctx, PCP_ERR_RANGE, "pcp_cloud_smooth: SAMPLE_LOCAL_PLANE's %lld rows span %.1f x %.1f x %.1f m (a fit thrown "
+                       "far off its surface): the trailing outlier removal would need grid cells above %.3f m; refused",
+                       (long long)m, static_cast<double>(cv2.mx[0] - cv2.mn[0]), static_cast<double>(cv2.mx[1] - cv2.mn[1]),
+                       static_cast<double>(cv2.mx[2] - cv2.mn[2]), c_max);
+  }
+  const bool vgd = !plain && !slp;
+  const double dens2 = vgd ? (2.0 * p->vgd_iterations + 1.0) / (static_cast<double>(p->vgd_voxel_size) * p->vgd_voxel_size) : 0.0;
+  const bool clustered = vgd;
+  if ((rc = sor_run(ctx, cv2, p->sor_mean_k, p->sor_std_mul, false, 0, 1, true, nullptr, clustered, dens2)) != PCP_OK) return rc;
   int64_t kept = 0;
   if (plain) {
     // survivors back in the caller's order (ascending index, as a filter chain on the input cloud leaves them): every
@@ -3497,6 +3802,8 @@ int pcp_cloud_smooth_stream_begin(pcp_context *ctx, const pcp_mls_params *p, int
   if (!ctx) return PCP_ERR_INVALID;
   int rc = check_mls_params(ctx, p);
   if (rc != PCP_OK) return rc;
+  if (p->upsampling == PCP_UPSAMPLING_SAMPLE_LOCAL_PLANE)
+    return set_error(ctx, PCP_ERR_INVALID, "pcp_cloud_smooth_stream_begin: SAMPLE_LOCAL_PLANE (1) is not streamed (pcp_cloud_smooth runs it)");
   if (p->upsampling != 3) return set_error(ctx, PCP_ERR_INVALID, "pcp_cloud_smooth_stream_begin: upsampling must be VOXEL_GRID_DILATION (3)");
   if (chunk_capacity < 4096 || chunk_capacity >= (int64_t(1) << 31))
     return set_error(ctx, PCP_ERR_INVALID, "pcp_cloud_smooth_stream_begin: chunk_capacity must be in [4096, 2^31)");

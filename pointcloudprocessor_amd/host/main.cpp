@@ -25,9 +25,12 @@
 //     zbuffer = view_culling (view_culling.cpp:52-174, the routine north_star names; its call is commented out at :43);
 //     hpr = hidden_points_removal (:266-334), the routine the reference binary actually calls (:46), flip + convex
 //     hull on the GPU; hpr_candidates = only its candidate filter (:276-288), a frustum cull.
-//   * --mlsVoxelSize v, --mlsDilationIterations k, --mlsUpsampling none|vgd (new): the three MLSParameters the reference
+//   * --mlsVoxelSize v, --mlsDilationIterations k, --mlsUpsampling none|slp|vgd (new): the three MLSParameters the reference
 //     hard-codes (upsampling VOXEL_GRID_DILATION, 0.001 m, 4 iterations, PointCloudProcessor.cpp:78-81; the defaults here);
-//     at 1 mm x 4 every input point becomes up to 729 output points.
+//     at 1 mm x 4 every input point becomes up to 729 output points.  slp = SAMPLE_LOCAL_PLANE, the switch's other
+//     deterministic method (cloudSmooth.cpp:133-152): a disk of samples per fitted point; --mlsUpsamplingRadius r and
+//     --mlsUpsamplingStep s (new) are its slp_upsampling_radius / _stepsize (default 0.05 / 0.01, :74-75).  With --gpus N
+//     the slp chain runs on the first GPU (MultiCloudSmooth): the files equal the one-GPU run's.
 //   * --gpus N (new, default 1): the map is sharded by point index over N GPUs of this node (pcp_multi.hpp: one
 //     process, N contexts, RCCL all-reduce(MIN) of the depth maps over xGMI, images broadcast over xGMI); every
 //     output file is identical to the one-GPU run.  The NID refinement sums its joint histograms over the shards
@@ -115,6 +118,7 @@ struct Options {
   float mls_voxel_size = -1.0f;  // < 0: the reference's constants (PointCloudProcessor.cpp:67-86)
   int mls_dilation_iterations = -1;
   int mls_upsampling = -1;
+  double mls_upsampling_radius = 0.05, mls_upsampling_step = 0.01;  // PointCloudProcessor.cpp:74-75
   float smooth_colors_radius = 0.0f;  // 0: smoothColorsWithLocalRegion off (PointCloudProcessor.cpp:597)
 };
 
@@ -155,11 +159,14 @@ static Options parse(int argc, char **argv) {
     else if (a == "--gpus") o.gpus = std::stoi(next());
     else if (a == "--mlsVoxelSize") o.mls_voxel_size = std::stof(next());
     else if (a == "--mlsDilationIterations") o.mls_dilation_iterations = std::stoi(next());
+    else if (a == "--mlsUpsamplingRadius") o.mls_upsampling_radius = std::stod(next());
+    else if (a == "--mlsUpsamplingStep") o.mls_upsampling_step = std::stod(next());
     else if (a == "--mlsUpsampling") {
       const std::string v = next();
-      if (v == "none") o.mls_upsampling = 0;
-      else if (v == "vgd") o.mls_upsampling = 3;
-      else throw std::runtime_error("the argument ('" + v + "') for option '--mlsUpsampling' is invalid (none, vgd)");
+      if (v == "none") o.mls_upsampling = PCP_UPSAMPLING_NONE;
+      else if (v == "slp") o.mls_upsampling = PCP_UPSAMPLING_SAMPLE_LOCAL_PLANE;
+      else if (v == "vgd") o.mls_upsampling = PCP_UPSAMPLING_VOXEL_GRID_DILATION;
+      else throw std::runtime_error("the argument ('" + v + "') for option '--mlsUpsampling' is invalid (none, slp, vgd)");
     }
     else if (a == "--smoothColorsRadius") {
       const std::string v = next();
@@ -329,6 +336,7 @@ class Processor {
       if (opt.mls_dilation_iterations >= 0) mp.vgd_iterations = opt.mls_dilation_iterations;
       if (opt.mls_upsampling >= 0) mp.upsampling = opt.mls_upsampling;
       smooth.initialize(mp);
+      smooth.setLocalPlaneSampling(opt.mls_upsampling_radius, opt.mls_upsampling_step);
       SmoothedCloud s = smooth.processWithOutlierRemoval(crop8.x.data(), crop8.y.data(), crop8.z.data(),
                                                          static_cast<int64_t>(crop8.size()));
       const std::string mlsPath = fs::path(cropPath).stem().string() + "_mls.pcd";  // CWD-relative, sic (B14)

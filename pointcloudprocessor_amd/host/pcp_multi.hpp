@@ -575,12 +575,21 @@ class MultiCloudSmooth {
   MultiCloudSmooth(const MultiCloudSmooth &) = delete;
   MultiCloudSmooth &operator=(const MultiCloudSmooth &) = delete;
   void initialize(const pcp_mls_params &p) { params_ = p; }
+  void setLocalPlaneSampling(double radius, double step) {  // SAMPLE_LOCAL_PLANE (CloudSmooth::setLocalPlaneSampling)
+    slp_radius_ = radius;
+    slp_step_ = step;
+  }
   int size() const { return static_cast<int>(dev_.size()); }
 
   SmoothedCloud processWithOutlierRemoval(const float *x, const float *y, const float *z, int64_t n) {
-    if (size() == 1) {
+    // SAMPLE_LOCAL_PLANE: the whole chain on the first GPU.  Each disk follows the sign of its point's fitted normal, and
+    // an upload of the survivors on the other GPUs re-sorts them: the fit's sums run in another order and a normal near a
+    // tie may flip, mirroring its disk -- the files then differ from the one-GPU run's.
+    if (size() == 1 || params_.upsampling == PCP_UPSAMPLING_SAMPLE_LOCAL_PLANE) {
       dev_[0]->uploadCloud(x, y, z, n);
-      return CloudSmooth(*dev_[0], params_).processWithOutlierRemoval();
+      CloudSmooth cs(*dev_[0], params_);
+      cs.setLocalPlaneSampling(slp_radius_, slp_step_);
+      return cs.processWithOutlierRemoval();
     }
     // SOR 1 (cloudSmooth.cpp:109-116)
     std::vector<int32_t> idx1 = outlierRemoval(x, y, z, n);
@@ -819,6 +828,7 @@ class MultiCloudSmooth {
   std::vector<hipStream_t> stream_;  // N > 1 on real GPUs: RCCL's stream per GPU
   std::vector<ncclComm_t> comm_;
   pcp_mls_params params_;
+  double slp_radius_ = 0.05, slp_step_ = 0.01;
 };
 
 }  // namespace pcp_amd

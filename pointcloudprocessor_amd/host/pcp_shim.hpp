@@ -205,6 +205,12 @@ class CloudSmooth {
   explicit CloudSmooth(Device &dev) : dev_(dev) { pcp_default_mls_params(&params_); }
   CloudSmooth(Device &dev, const pcp_mls_params &p) : dev_(dev), params_(p) {}
   void initialize(const pcp_mls_params &p) { params_ = p; }  // CloudSmooth::initialize(MLSParameters)
+  // MLSParameters slp_upsampling_radius / slp_upsampling_stepsize (cloudSmooth.hpp:28-29; the reference's 0.05 / 0.01,
+  // PointCloudProcessor.cpp:74-75, are the defaults): SAMPLE_LOCAL_PLANE's disk, applied to the context before each run
+  void setLocalPlaneSampling(double radius, double step) {
+    slp_radius_ = radius;
+    slp_step_ = step;
+  }
   // the whole CloudSmooth::process: SOR -> MLS (+ upsampling) -> SOR (cloudSmooth.cpp:109-164)
   SmoothedCloud processWithOutlierRemoval() const { return run(true); }
   // pcl::MovingLeastSquares::process alone
@@ -245,9 +251,10 @@ class CloudSmooth {
     dev_.check(pcp_mls_fetch(dev_.get(), m, s.xyz.data(), s.normal.data(), s.curvature.data(), s.index.data()));
   }
   SmoothedCloud run(bool with_sor) const {
+    dev_.check(pcp_set_mls_local_plane(dev_.get(), slp_radius_, slp_step_));
     int64_t m = 0;
     int rc = with_sor ? pcp_cloud_smooth(dev_.get(), &params_, &m) : pcp_mls_process(dev_.get(), &params_, &m);
-    if (with_sor && rc == PCP_ERR_NOMEM && params_.upsampling == 3) {
+    if (with_sor && rc == PCP_ERR_NOMEM && params_.upsampling == PCP_UPSAMPLING_VOXEL_GRID_DILATION) {
       // more upsampled points than one result holds: the streamed chain, gathered on the host (the caller asked for one cloud)
       SmoothedCloud all;
       processWithOutlierRemovalStreamed(int64_t(1) << 28, [&](const SmoothedCloud &c) {
@@ -271,6 +278,7 @@ class CloudSmooth {
 
   Device &dev_;
   pcp_mls_params params_;
+  double slp_radius_ = 0.05, slp_step_ = 0.01;
 };
 
 }  // namespace pcp_amd

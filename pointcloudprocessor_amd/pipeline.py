@@ -372,17 +372,27 @@ class VisualLiDARCalibration:
 
 
 class CloudSmooth:
-    """CloudSmooth::process: MovingLeastSquares (+ optional SOR brackets)."""
+    """CloudSmooth::process: MovingLeastSquares (+ optional SOR brackets).
+    local_plane=(radius, step): SAMPLE_LOCAL_PLANE's disk (MLSParameters slp_upsampling_radius / _stepsize), applied to
+    the context before every run; None leaves the context's setting (the reference's 0.05 / 0.01 unless changed)."""
 
-    def __init__(self, engine: HipEngine, params: capi.MLSParams | None = None):
+    def __init__(self, engine: HipEngine, params: capi.MLSParams | None = None, local_plane: tuple[float, float] | None = None):
         self.engine = engine
         self.params = params if params is not None else capi.default_mls_params()
+        self.local_plane = local_plane
+
+    def _apply_local_plane(self):
+        if getattr(self, "local_plane", None) is not None:
+            self.engine.ctx.set_mls_local_plane(*self.local_plane)
 
     def process_sharded(self, n_total: int, rank: int, world: int, group=None):
         """MLS (upsampling NONE) with the queries dealt out over `world` ranks by slabs of the stage's own spatial order
         (whole wavefronts: 1 / world of the work whatever order the caller's points come in): every rank holds the whole
         cloud, fits its slab, the variable-length results are all-gathered and merged by source index.
         Returns the full result, in input order, on every rank."""
+        if getattr(self.params, "upsampling", None) == capi.UPSAMPLING_SAMPLE_LOCAL_PLANE:
+            raise ValueError("process_sharded: SAMPLE_LOCAL_PLANE is not sharded (each disk follows the sign of its point's "
+                             "fitted normal, which a re-ordered fit may flip); run process() on one GPU")
         ctx = self.engine.ctx
         local = ctx.mls_fetch(ctx.mls_process_slab(self.params, rank, world))
         if world == 1:
@@ -444,6 +454,7 @@ class CloudSmooth:
         result cannot hold (the reference's VOXEL_GRID_DILATION 1 mm x 4 on a real map) goes through the streamed form and is
         gathered on the host, as the C++ shim does (host/pcp_shim.hpp)."""
         ctx = self.engine.ctx
+        self._apply_local_plane()
         if not with_outlier_removal:
             return ctx.mls_fetch(ctx.mls_process(self.params))
         try:
