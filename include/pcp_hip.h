@@ -46,7 +46,9 @@ extern "C" {
                                 entry points added, no layout changed: pcp_upload_image_jpeg / _async (pcp_jpeg_header);
                                 entry points added, no layout changed: pcp_set_mls_local_plane / pcp_mls_local_plane_samples
                                 (pcp_mls_params.upsampling accepts PCP_UPSAMPLING_SAMPLE_LOCAL_PLANE; older libraries refuse
-                                it with PCP_ERR_INVALID) */
+                                it with PCP_ERR_INVALID);
+                                entry points added, no layout changed: pcp_set_label_fusion / pcp_colour_labels /
+                                pcp_colour_labels_device (fused segmentation labels; off by default) */
 
 #define PCP_OK 0
 #define PCP_ERR_INVALID (-1) /* bad argument */
@@ -351,6 +353,32 @@ int pcp_download_wait_previous(pcp_context *ctx);
 /* device address of the packed per-point result (r | g<<8 | b<<16 | has<<24),
  * valid after pcp_colour_finalise / pcp_colorize, for device-side gathers */
 int pcp_colour_result_device(pcp_context *ctx, void **device_ptr, int64_t *n_words);
+
+/* Fused segmentation labels ("Fused segmentation labels"): one label per map point from the masks of the
+ * point's top-5 views, where the reference writes every point once per keyframe that sees it
+ * (PointCloudProcessor.cpp:533-551, 932-947).  Off by default; with it off every output and every launched kernel is what
+ * it was.  With it on, the colour kernels keep each listed view's mask byte m_k (the texel's top byte) and every colour
+ * result (pcp_colorize, pcp_colorize_from_depth, pcp_colour_finalise) carries a second word per point, for the same list
+ * (s_k, texel_k, f_k), k < M = min(count, 5), that the colour reads:
+ *   views = M,  hits = #{k : m_k == 255},  label = floor(sum m_k S_k / sum S_k),  S_k = s_k * 2^26
+ * in exact integer arithmetic (S_k is an integer for every fp32 score in [2^-3, 2); final_score gives [0.2, 1]); an
+ * unseen point has the word 0.  A single view returns its m, views that are all 255 return 255, and the order of equal
+ * scores does not matter.  A score outside [2^-3, 2) makes the result call return PCP_ERR_RANGE (no labels then).
+ * The result call reads that flag back: with fusion on it waits for its kernels.
+ * Colours and has are bit for bit those of a fusion-off run; pcp_colour_finalise's out_top_rgb stays 0x00RRGGBB.
+ * A colour pass over a keyframe without an uploaded mask (pcp_upload_mask) fails with PCP_ERR_STATE before anything is
+ * launched.  Changing the switch while a top-5 accumulation is live (after pcp_colour_pass, before pcp_colour_reset)
+ * returns PCP_ERR_STATE.  PCP_MATCH_RADIUS is supported: a credited neighbour sample brings its own pixel's mask.  On an
+ * index shard (PCP_DEPTH_BATCHED) the labels are rank-local; the shards' arrays concatenate to the one-GPU result.
+ * pcp_colour_smooth_local leaves the labels alone. */
+int pcp_set_label_fusion(pcp_context *ctx, int32_t enable);
+/* label / hits / views of the latest colour result, n bytes each, all nullable, input order; synchronous.  PCP_ERR_STATE
+ * unless that result was produced with fusion on. */
+int pcp_colour_labels(pcp_context *ctx, uint8_t *out_label, uint8_t *out_hits, uint8_t *out_views);
+/* device address of the packed words label | hits<<8 | views<<16 (n words, input order).  One buffer, NOT double-buffered:
+ * valid until the next colour result begins (a later pcp_colorize / pcp_colorize_from_depth / pcp_colour_finalise
+ * overwrites or invalidates it), so consume it on the context's stream before that call. */
+int pcp_colour_labels_device(pcp_context *ctx, void **device_ptr, int64_t *n_words);
 
 /* PointCloudProcessor::smoothColorsWithLocalRegion(rgbCloud, radius), PointCloudProcessor.cpp:634-703, whose call
  * smoothColorsWithLocalRegion(rgbCloud, 0.1) is commented out at :597 between smoothColors (:596) and

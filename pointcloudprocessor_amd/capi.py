@@ -462,6 +462,26 @@ class Context:
         self._check(self.lib.pcp_colour_result_device(self.h, C.byref(p), C.byref(n)))
         return p.value, n.value
 
+    def set_label_fusion(self, enable: bool = True):
+        """Fused segmentation labels (pcp_hip.h): with it on, every colour result carries label / hits / views per point
+        from the masks of the point's top-5 views.  PCP_ERR_STATE while a top-5 accumulation is live."""
+        self._check(self.lib.pcp_set_label_fusion(self.h, C.c_int32(1 if enable else 0)))
+
+    def colour_labels(self):
+        """dict(label, hits, views): n uint8 each, input order, of the latest colour result (produced with fusion on)."""
+        n = self.n
+        label, hits, views = (np.empty(n, np.uint8) for _ in range(3))
+        self._check(self.lib.pcp_colour_labels(self.h, _ptr(label), _ptr(hits), _ptr(views)))
+        return dict(label=label, hits=hits, views=views)
+
+    def colour_labels_device(self):
+        """(device pointer, n) of the packed words label | hits<<8 | views<<16; valid until the next colour result begins
+        (one buffer, not double-buffered)."""
+        p = C.c_void_p()
+        n = C.c_int64()
+        self._check(self.lib.pcp_colour_labels_device(self.h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
     def colour_smooth_local(self, radius: float) -> int:
         """smoothColorsWithLocalRegion (PointCloudProcessor.cpp:634-703) in place on the colour result; returns the number
         of points with a colour afterwards.  The downloads then return the smoothed words."""

@@ -590,11 +590,18 @@ struct MatchArgs {
   float e2;                   // E^2, rounded up
 };
 
+// label form (pcp_set_label_fusion): the second packed word per point, input order; word[n] is the flag that a score fell
+// outside [2^-3, 2) (Top5::labels).  Null in the colour-only form.
+struct LabelOut {
+  uint32_t *word;
+};
+
 // kMatch: 0 = match mode read from the camera block, else the mode itself (PCP_MATCH_IDENTITY 1 ... see match_constant);
 // 3 = PCP_MATCH_RADIUS: ROUNDTRIP for the points outside A, nothing inserted for the points of A (k_match_fixup), and every
 // kept sample's round-trip displacement counted against E
 // kOneShot: flags == 4 (no top-5 state loaded or stored; packed result written in input order): the usual whole-run call
-template <bool kCommon, int kMatch, bool kOneShot>
+// kLabel: the list keeps the whole texel (its top byte is the view's mask) and the result store adds the label word
+template <bool kCommon, int kMatch, bool kOneShot, bool kLabel = false>
 __global__ __launch_bounds__(kBlock) void k_colour_pass(const float *__restrict__ x, const float *__restrict__ y,
                                                         const float *__restrict__ z, int64_t n, DevCamera cam_in,
                                                         const DevFrame *__restrict__ frames, int32_t f0, int32_t f1,
@@ -603,7 +610,8 @@ __global__ __launch_bounds__(kBlock) void k_colour_pass(const float *__restrict_
                                                         const uint32_t *__restrict__ images, int64_t image_px,
                                                         TopState st, const int32_t *__restrict__ perm,
                                                         uint32_t *__restrict__ rgba, int32_t flags_in,
-                                                        const uint32_t *__restrict__ hull_bits_in, MatchArgs mb) {
+                                                        const uint32_t *__restrict__ hull_bits_in, MatchArgs mb,
+                                                        [[maybe_unused]] LabelOut lab) {
   DevCamera cam = common_camera<kCommon>(cam_in);
   if constexpr (kMatch == 1) cam.match_mode = PCP_MATCH_IDENTITY;
   if constexpr (kMatch == 2 || kMatch == 3) cam.match_mode = PCP_MATCH_ROUNDTRIP;
@@ -666,7 +674,7 @@ __global__ __launch_bounds__(kBlock) void k_colour_pass(const float *__restrict_
         if (keep) {
           // texel = B | G<<8 | R<<16 | mask<<24; its low 24 bits are 0x00RRGGBB (PointCloudProcessor.cpp:760-762)
           const uint32_t texel = images[static_cast<uint64_t>(static_cast<uint32_t>(f)) * static_cast<uint32_t>(image_px) + static_cast<uint32_t>(p.pixel)];
-          t.insert(final_score(sx, sy, sz, fr.px, fr.py, fr.pz), texel & 0xffffffu, f);
+          t.insert(final_score(sx, sy, sz, fr.px, fr.py, fr.pz), kLabel ? texel : texel & 0xffffffu, f);
         }
       }
     }
@@ -686,14 +694,19 @@ __global__ __launch_bounds__(kBlock) void k_colour_pass(const float *__restrict_
   }
   // The packed result, scattered straight into input order: sorted stores un-permuted by a kernel after the pass or by
   // every reader were measured slower ("The result store of the colour pass").
-  if (flags & 4) rgba[static_cast<int64_t>(perm[j])] = t.finalise();
+  if (flags & 4) {
+    const int64_t o = perm[j];
+    rgba[o] = t.finalise();
+    if constexpr (kLabel) {
+      uint32_t bad = 0u;
+      lab.word[o] = t.labels(bad);
+      if (bad) lab.word[n] = 1u;
+    }
+  }
 }
 
 // finalise from stored state (multi-batch runs)
-__global__ __launch_bounds__(kBlock) void k_finalise(int64_t n, TopState st, const int32_t *__restrict__ perm,
-                                                     uint32_t *__restrict__ rgba) {
-  const int64_t j = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-  if (j >= n) return;
+__device__ __forceinline__ Top5 load_top5(const TopState &st, int64_t n, int64_t j) {
   Top5 t;
   t.s0 = st.score[0 * n + j]; t.s1 = st.score[1 * n + j]; t.s2 = st.score[2 * n + j];
   t.s3 = st.score[3 * n + j]; t.s4 = st.score[4 * n + j];
@@ -702,7 +715,26 @@ __global__ __launch_bounds__(kBlock) void k_finalise(int64_t n, TopState st, con
   t.f0 = st.frame[0 * n + j]; t.f1 = st.frame[1 * n + j]; t.f2 = st.frame[2 * n + j];
   t.f3 = st.frame[3 * n + j]; t.f4 = st.frame[4 * n + j];
   t.count = st.count[j];
+  return t;
+}
+__global__ __launch_bounds__(kBlock) void k_finalise(int64_t n, TopState st, const int32_t *__restrict__ perm,
+                                                     uint32_t *__restrict__ rgba) {
+  const int64_t j = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (j >= n) return;
+  const Top5 t = load_top5(st, n, j);
   rgba[static_cast<int64_t>(perm[j])] = t.finalise();  // see k_colour_pass
+}
+// the label form: the state's texels carry the masks
+__global__ __launch_bounds__(kBlock) void k_finalise_labels(int64_t n, TopState st, const int32_t *__restrict__ perm,
+                                                            uint32_t *__restrict__ rgba, LabelOut lab) {
+  const int64_t j = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (j >= n) return;
+  const Top5 t = load_top5(st, n, j);
+  const int64_t o = perm[j];
+  rgba[o] = t.finalise();
+  uint32_t bad = 0u;
+  lab.word[o] = t.labels(bad);
+  if (bad) lab.word[n] = 1u;
 }
 
 // PCP_MATCH_RADIUS fix-up: one lane per point j of A (pcp_match.hip).  The lane starts from the state the colour pass started
@@ -711,6 +743,8 @@ __global__ __launch_bounds__(kBlock) void k_finalise(int64_t n, TopState st, con
 // does (candidate rule, hull bit, keep rule, pixel, fp32 round trip) and inserts it when |p_w - p_j|^2 < f32(1e-5^2).  A
 // (tile, keyframe) pair that the tile mask clears holds no candidate: i is skipped there.  Cost: sum over A of |row(j)| per
 // keyframe -- quadratic in the multiplicity of a duplicated point, as the reference's radius searches are.
+// kLabel: as in k_colour_pass; the credited sample brings the mask of the neighbour's pixel with it.
+template <bool kLabel>
 __global__ __launch_bounds__(kBlock) void k_match_fixup(const float *__restrict__ x, const float *__restrict__ y,
                                                         const float *__restrict__ z, int64_t n, DevCamera cam,
                                                         const DevFrame *__restrict__ frames, int32_t f0, int32_t f1,
@@ -720,7 +754,8 @@ __global__ __launch_bounds__(kBlock) void k_match_fixup(const float *__restrict_
                                                         const int32_t *__restrict__ perm, uint32_t *__restrict__ rgba,
                                                         int32_t flags, const uint32_t *__restrict__ hull_bits,
                                                         const int32_t *__restrict__ list, int64_t na,
-                                                        const int64_t *__restrict__ off, const int32_t *__restrict__ cols) {
+                                                        const int64_t *__restrict__ off, const int32_t *__restrict__ cols,
+                                                        [[maybe_unused]] LabelOut lab) {
   const int64_t a = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (a >= na) return;
   const int64_t j = list[a];
@@ -757,7 +792,7 @@ __global__ __launch_bounds__(kBlock) void k_match_fixup(const float *__restrict_
       float sx = p.xc, sy = p.yc, sz = p.zc;
       if (!roundtrip_sample(cam, fr, qx, qy, qz, sx, sy, sz)) continue;
       const uint32_t texel = images[static_cast<uint64_t>(static_cast<uint32_t>(f)) * static_cast<uint32_t>(image_px) + static_cast<uint32_t>(p.pixel)];
-      t.insert(final_score(sx, sy, sz, fr.px, fr.py, fr.pz), texel & 0xffffffu, f);
+      t.insert(final_score(sx, sy, sz, fr.px, fr.py, fr.pz), kLabel ? texel : texel & 0xffffffu, f);
     }
   }
   if (flags & 2) {
@@ -769,7 +804,29 @@ __global__ __launch_bounds__(kBlock) void k_match_fixup(const float *__restrict_
     st.frame[3 * n + j] = t.f3; st.frame[4 * n + j] = t.f4;
     st.count[j] = t.count;
   }
-  if (flags & 4) rgba[static_cast<int64_t>(perm[j])] = t.finalise();
+  if (flags & 4) {
+    const int64_t o = perm[j];
+    rgba[o] = t.finalise();
+    if constexpr (kLabel) {
+      uint32_t bad = 0u;
+      lab.word[o] = t.labels(bad);
+      if (bad) lab.word[n] = 1u;
+    }
+  }
+}
+
+// the instantiation a colour pass launches (flags == 4: one-shot)
+template <bool kLabel>
+inline auto colour_pass_kernel(bool common, int32_t match_mode, int32_t flags) {
+  auto kernel = k_colour_pass<false, 0, false, kLabel>;
+  if (common && match_mode == PCP_MATCH_IDENTITY)
+    kernel = flags == 4 ? k_colour_pass<true, 1, true, kLabel> : k_colour_pass<true, 1, false, kLabel>;
+  if (common && match_mode == PCP_MATCH_ROUNDTRIP)
+    kernel = flags == 4 ? k_colour_pass<true, 2, true, kLabel> : k_colour_pass<true, 2, false, kLabel>;
+  if (match_mode == PCP_MATCH_RADIUS)
+    kernel = !common ? k_colour_pass<false, 3, false, kLabel>
+                     : flags == 4 ? k_colour_pass<true, 3, true, kLabel> : k_colour_pass<true, 3, false, kLabel>;
+  return kernel;
 }
 
 // ---------------------------------------------------------------------------
@@ -841,6 +898,18 @@ __global__ __launch_bounds__(kBlock) void k_unpack_result(const uint32_t *__rest
   rgb[3 * i + 1] = static_cast<uint8_t>((v >> 8) & 0xffu);
   rgb[3 * i + 2] = static_cast<uint8_t>((v >> 16) & 0xffu);
   has[i] = static_cast<uint8_t>(v >> 24);
+}
+
+// packed label word label | hits<<8 | views<<16  ->  three byte planes (nullable)
+__global__ __launch_bounds__(kBlock) void k_unpack_labels(const uint32_t *__restrict__ packed, int64_t n,
+                                                         uint8_t *__restrict__ label, uint8_t *__restrict__ hits,
+                                                         uint8_t *__restrict__ views) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t v = packed[i];
+  if (label) label[i] = static_cast<uint8_t>(v & 0xffu);
+  if (hits) hits[i] = static_cast<uint8_t>((v >> 8) & 0xffu);
+  if (views) views[i] = static_cast<uint8_t>((v >> 16) & 0xffu);
 }
 
 __global__ __launch_bounds__(kBlock) void k_fill_u32(uint32_t *__restrict__ p, int64_t n, uint32_t v) {
@@ -1908,6 +1977,7 @@ int pcp_colour_reset(pcp_context *ctx) {
   if (!ctx) return PCP_ERR_INVALID;
   ctx->colour_state_live = false;
   ctx->colour_result_live = false;
+  ctx->labels_live = false;
   return PCP_OK;
 }
 
@@ -1924,6 +1994,39 @@ static int begin_result(pcp_context *ctx, uint32_t **dst) {
   return PCP_OK;
 }
 
+// Fused labels: a colour result begins (the previous labels end here) ...
+static int labels_begin(pcp_context *ctx) {
+  ctx->labels_live = false;
+  if (!ctx->label_fusion) return PCP_OK;
+  PCP_HIP_TRY(ctx, ctx->labels.ensure(static_cast<size_t>(ctx->n) + 4));
+  PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->labels.p + ctx->n, 0, 4, ctx->stream));  // the range flag (LabelOut)
+  return PCP_OK;
+}
+
+// ... and ends: the kernels' range flag is read here (one 4-byte readback, which makes a fusion-on result call wait for its
+// kernels): a score outside [2^-3, 2) has no integer S_k, so no label is reported for the run
+static int labels_end(pcp_context *ctx) {
+  if (!ctx->label_fusion) return PCP_OK;
+  uint32_t bad = 0;
+  uint32_t *dst = ctx->readback ? static_cast<uint32_t *>(ctx->readback) : &bad;  // pinned: no staging
+  PCP_HIP_TRY(ctx, hipMemcpyAsync(dst, ctx->labels.p + ctx->n, 4, hipMemcpyDeviceToHost, ctx->stream));
+  PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (*dst != 0)
+    return set_error(ctx, PCP_ERR_RANGE, "label fusion: a view score outside [2^-3, 2) reached the label arithmetic "
+                     "(final_score cannot produce one): no labels for this result");
+  ctx->labels_live = true;
+  return PCP_OK;
+}
+
+// label fusion reads every keyframe's mask: one that was never uploaded ends the call before anything is launched
+static int check_masks(pcp_context *ctx, int32_t frame_begin, int32_t frame_end) {
+  if (!ctx->label_fusion) return PCP_OK;
+  for (int32_t f = frame_begin; f < frame_end; ++f)
+    if (static_cast<size_t>(f) >= ctx->mask_set.size() || !ctx->mask_set[static_cast<size_t>(f)])
+      return set_error(ctx, PCP_ERR_STATE, "pcp_colour_pass: label fusion is on and no mask was uploaded for keyframe %d", f);
+  return PCP_OK;
+}
+
 static int colour_pass_impl(pcp_context *ctx, int32_t frame_begin, int32_t frame_end, bool one_shot,
                             uint32_t *result = nullptr) {
   int rc = check_ready(ctx, "pcp_colour_pass", true);
@@ -1931,6 +2034,7 @@ static int colour_pass_impl(pcp_context *ctx, int32_t frame_begin, int32_t frame
   if (frame_begin < 0 || frame_end > ctx->n_frames || frame_begin > frame_end)
     return set_error(ctx, PCP_ERR_RANGE, "pcp_colour_pass: keyframe range [%d,%d) outside 0..%d", frame_begin, frame_end,
                      ctx->n_frames);
+  if ((rc = check_masks(ctx, frame_begin, frame_end)) != PCP_OK) return rc;
   for (int32_t f = frame_begin; f < frame_end; ++f) {
     if (!ctx->depth.p || !ctx->depth_valid[static_cast<size_t>(f)])
       return set_error(ctx, PCP_ERR_STATE, "pcp_colour_pass: pcp_depth_pass has not covered keyframe %d", f);
@@ -1950,6 +2054,8 @@ static int colour_pass_impl(pcp_context *ctx, int32_t frame_begin, int32_t frame
   if (radius && (rc = match_table_prepare(ctx)) != PCP_OK) return rc;
   if (frame_begin == frame_end) {
     if (one_shot && result) PCP_HIP_TRY(ctx, hipMemsetAsync(result, 0, static_cast<size_t>(ctx->n) * 4, ctx->stream));
+    if (one_shot && ctx->label_fusion)
+      PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->labels.p, 0, static_cast<size_t>(ctx->n) * 4, ctx->stream));
     return PCP_OK;
   }
   const size_t plane = plane_of(ctx);
@@ -1972,23 +2078,21 @@ static int colour_pass_impl(pcp_context *ctx, int32_t frame_begin, int32_t frame
     // tiles (longest-first order: no gain at 1920x1080), and its texel gathers want neighbouring tiles on the same L2
     // (longest-first order at 4096x3000: 1.96 -> 2.18 ms)
     const bool common = is_common_camera(ctx->dcam) && ctx->cull.cull_mode != PCP_CULL_HPR;
-    auto kernel = k_colour_pass<false, 0, false>;
-    if (common && ctx->dcam.match_mode == PCP_MATCH_IDENTITY)
-      kernel = flags == 4 ? k_colour_pass<true, 1, true> : k_colour_pass<true, 1, false>;
-    if (common && ctx->dcam.match_mode == PCP_MATCH_ROUNDTRIP)
-      kernel = flags == 4 ? k_colour_pass<true, 2, true> : k_colour_pass<true, 2, false>;
-    if (radius) kernel = !common ? k_colour_pass<false, 3, false> : flags == 4 ? k_colour_pass<true, 3, true> : k_colour_pass<true, 3, false>;
+    const bool label = ctx->label_fusion;
+    const LabelOut lab{label ? ctx->labels.p : nullptr};
+    auto kernel = label ? colour_pass_kernel<true>(common, ctx->dcam.match_mode, flags)
+                        : colour_pass_kernel<false>(common, ctx->dcam.match_mode, flags);
     hipLaunchKernelGGL(kernel, dim3(blocks_for(ctx->n)), dim3(kBlock), 0, ctx->stream, ctx->sxyz.p, ctx->sxyz.p + plane,
                        ctx->sxyz.p + 2 * plane, ctx->n, ctx->dcam, ctx->frames.p, frame_begin, frame_end, ctx->depth.p,
                        cells_of(ctx), ctx->tile_mask.p, ctx->mask_words, ctx->images.p,
-                       static_cast<int64_t>(ctx->dcam.img_w) * ctx->dcam.img_h, st, ctx->perm.p, result, flags, hull, mb);
+                       static_cast<int64_t>(ctx->dcam.img_w) * ctx->dcam.img_h, st, ctx->perm.p, result, flags, hull, mb, lab);
     PCP_HIP_TRY(ctx, hipGetLastError());
     if (radius && ctx->match_a > 0) {
-      hipLaunchKernelGGL(k_match_fixup, dim3(blocks_for(ctx->match_a)), dim3(kBlock), 0, ctx->stream, ctx->sxyz.p,
+      hipLaunchKernelGGL(label ? k_match_fixup<true> : k_match_fixup<false>, dim3(blocks_for(ctx->match_a)), dim3(kBlock), 0, ctx->stream, ctx->sxyz.p,
                          ctx->sxyz.p + plane, ctx->sxyz.p + 2 * plane, ctx->n, ctx->dcam, ctx->frames.p, frame_begin, frame_end,
                          ctx->depth.p, cells_of(ctx), ctx->tile_mask.p, ctx->mask_words, ctx->images.p,
                          static_cast<int64_t>(ctx->dcam.img_w) * ctx->dcam.img_h, st, ctx->perm.p, result, flags, hull,
-                         ctx->match_list.p, ctx->match_a, ctx->match_off.p, ctx->match_cols.p);
+                         ctx->match_list.p, ctx->match_a, ctx->match_off.p, ctx->match_cols.p, lab);
       PCP_HIP_TRY(ctx, hipGetLastError());
     }
   }
@@ -2040,9 +2144,11 @@ int pcp_colour_finalise(pcp_context *ctx, uint8_t *out_rgb, uint8_t *out_has, in
   const size_t sn = static_cast<size_t>(n);
   uint32_t *result = nullptr;
   if ((rc = begin_result(ctx, &result)) != PCP_OK) return rc;
+  if ((rc = labels_begin(ctx)) != PCP_OK) return rc;
   if (!ctx->colour_state_live && n > 0) {
     // no keyframe processed: empty lists
     PCP_HIP_TRY(ctx, hipMemsetAsync(result, 0, sn * 4, ctx->stream));
+    if (ctx->label_fusion) PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->labels.p, 0, sn * 4, ctx->stream));
     if ((rc = fill_u32(ctx, reinterpret_cast<uint32_t *>(ctx->top_score.p), kTopM * n, 0xbf800000u)) != PCP_OK) return rc;
     PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->top_rgb.p, 0, kTopM * sn * 4, ctx->stream));
     PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->top_frame.p, 0xff, kTopM * sn * 4, ctx->stream));
@@ -2050,9 +2156,15 @@ int pcp_colour_finalise(pcp_context *ctx, uint8_t *out_rgb, uint8_t *out_has, in
   } else if (n > 0) {
     TopState st{ctx->top_score.p, ctx->top_rgb.p, ctx->top_frame.p, ctx->view_count.p};
     LaunchTimer t(ctx, PCP_K_COLOUR);
-    hipLaunchKernelGGL(k_finalise, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, n, st, ctx->perm.p, result);
+    const bool label = ctx->label_fusion;
+    const LabelOut lab{label ? ctx->labels.p : nullptr};
+    if (label)
+      hipLaunchKernelGGL(k_finalise_labels, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, n, st, ctx->perm.p, result, lab);
+    else
+      hipLaunchKernelGGL(k_finalise, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, n, st, ctx->perm.p, result);
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
+  if ((rc = labels_end(ctx)) != PCP_OK) return rc;
   if ((rc = end_result(ctx, out_rgb, out_has)) != PCP_OK) return rc;
   if ((out_count || out_top_score || out_top_rgb || out_top_frame) && n > 0) {
     std::vector<int32_t> perm(sn), cnt;
@@ -2068,6 +2180,9 @@ int pcp_colour_finalise(pcp_context *ctx, uint8_t *out_rgb, uint8_t *out_has, in
     };
     if (out_top_score && (rc = fetch5(ctx->top_score.p, out_top_score)) != PCP_OK) return rc;
     if (out_top_rgb && (rc = fetch5(ctx->top_rgb.p, out_top_rgb)) != PCP_OK) return rc;
+    // the label form keeps each view's mask in the top byte of the state: the caller sees 0x00RRGGBB in both forms
+    if (out_top_rgb && ctx->label_fusion)
+      for (size_t k = 0; k < kTopM * sn; ++k) out_top_rgb[k] &= 0xffffffu;
     if (out_top_frame && (rc = fetch5(ctx->top_frame.p, out_top_frame)) != PCP_OK) return rc;
     if (out_count) {
       cnt.resize(sn);
@@ -2082,11 +2197,14 @@ int pcp_colour_finalise(pcp_context *ctx, uint8_t *out_rgb, uint8_t *out_has, in
 int pcp_colorize(pcp_context *ctx, uint8_t *out_rgb, uint8_t *out_has) {
   int rc = check_ready(ctx, "pcp_colorize", true);
   if (rc != PCP_OK) return rc;
+  if ((rc = check_masks(ctx, 0, ctx->n_frames)) != PCP_OK) return rc;  // (before the depth pass)
   pcp_colour_reset(ctx);
   if ((rc = pcp_depth_pass(ctx, 0, ctx->n_frames)) != PCP_OK) return rc;
   uint32_t *result = nullptr;
   if ((rc = begin_result(ctx, &result)) != PCP_OK) return rc;
+  if ((rc = labels_begin(ctx)) != PCP_OK) return rc;
   if ((rc = colour_pass_impl(ctx, 0, ctx->n_frames, true, result)) != PCP_OK) return rc;
+  if ((rc = labels_end(ctx)) != PCP_OK) return rc;
   return end_result(ctx, out_rgb, out_has);
 }
 
@@ -2096,7 +2214,9 @@ int pcp_colorize_from_depth(pcp_context *ctx, uint8_t *out_rgb, uint8_t *out_has
   pcp_colour_reset(ctx);
   uint32_t *result = nullptr;
   if ((rc = begin_result(ctx, &result)) != PCP_OK) return rc;
+  if ((rc = labels_begin(ctx)) != PCP_OK) return rc;
   if ((rc = colour_pass_impl(ctx, 0, ctx->n_frames, true, result)) != PCP_OK) return rc;
+  if ((rc = labels_end(ctx)) != PCP_OK) return rc;
   return end_result(ctx, out_rgb, out_has);
 }
 
@@ -2185,6 +2305,47 @@ int pcp_colour_result_device(pcp_context *ctx, void **device_ptr, int64_t *n_wor
   if (!ctx->colour_result_live)
     return set_error(ctx, PCP_ERR_STATE, "pcp_colour_result_device: no result (call pcp_colorize / pcp_colour_finalise)");
   if (device_ptr) *device_ptr = ctx->rgba2[ctx->rgba_cur].p;
+  if (n_words) *n_words = ctx->n;
+  return PCP_OK;
+}
+
+int pcp_set_label_fusion(pcp_context *ctx, int32_t enable) {
+  if (!ctx) return PCP_ERR_INVALID;
+  const bool on = enable != 0;
+  if (on != ctx->label_fusion && ctx->colour_state_live)
+    return set_error(ctx, PCP_ERR_STATE, "pcp_set_label_fusion: a top-5 accumulation is live (its lists %s the masks): "
+                     "call pcp_colour_reset first", ctx->label_fusion ? "hold" : "do not hold");
+  ctx->label_fusion = on;
+  return PCP_OK;
+}
+
+int pcp_colour_labels(pcp_context *ctx, uint8_t *out_label, uint8_t *out_hits, uint8_t *out_views) {
+  if (!ctx) return PCP_ERR_INVALID;
+  if (!ctx->labels_live)
+    return set_error(ctx, PCP_ERR_STATE, "pcp_colour_labels: no labels (pcp_set_label_fusion(1), then pcp_colorize / "
+                     "pcp_colorize_from_depth / pcp_colour_finalise)");
+  const int64_t n = ctx->n;
+  if (n == 0 || !(out_label || out_hits || out_views)) return PCP_OK;
+  PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t sn = static_cast<size_t>(n);
+  PCP_HIP_TRY(ctx, ctx->s_keep.ensure(4 * sn + 16));
+  uint8_t *d_label = ctx->s_keep.p, *d_hits = d_label + sn, *d_views = d_hits + sn;
+  hipLaunchKernelGGL(k_unpack_labels, dim3(blocks_for(n)), dim3(kBlock), 0, ctx->stream, ctx->labels.p, n,
+                     out_label ? d_label : nullptr, out_hits ? d_hits : nullptr, out_views ? d_views : nullptr);
+  PCP_HIP_TRY(ctx, hipGetLastError());
+  if (out_label) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_label, d_label, sn, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_hits) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_hits, d_hits, sn, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_views) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_views, d_views, sn, hipMemcpyDeviceToHost, ctx->stream));
+  PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return PCP_OK;
+}
+
+int pcp_colour_labels_device(pcp_context *ctx, void **device_ptr, int64_t *n_words) {
+  if (!ctx) return PCP_ERR_INVALID;
+  if (!ctx->labels_live)
+    return set_error(ctx, PCP_ERR_STATE, "pcp_colour_labels_device: no labels (pcp_set_label_fusion(1), then pcp_colorize / "
+                     "pcp_colorize_from_depth / pcp_colour_finalise)");
+  if (device_ptr) *device_ptr = ctx->labels.p;
   if (n_words) *n_words = ctx->n;
   return PCP_OK;
 }

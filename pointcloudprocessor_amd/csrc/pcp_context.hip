@@ -516,6 +516,7 @@ static int store_cloud(pcp_context *ctx, const float *x, const float *y, const f
   ctx->nid_chunks = 0;
   ctx->colour_state_live = false;
   ctx->colour_result_live = false;
+  ctx->labels_live = false;
   match_table_release(ctx);  // PCP_MATCH_RADIUS: the table belongs to the cloud that is being replaced
   ctx->mls_count = 0;
   ctx->vgd_next = ctx->css_next = -1;  // the streams of the smoothing stage belong to the cloud that is being replaced
@@ -688,6 +689,7 @@ void pcp_destroy(pcp_context *ctx) {
   ctx->view_count.release();
   ctx->rgba2[0].release();
   ctx->rgba2[1].release();
+  ctx->labels.release();
   match_table_release(ctx);
   ctx->match_moved.release();
   for (int k = 0; k < 2; ++k) {
@@ -911,6 +913,7 @@ int pcp_set_camera(pcp_context *ctx, const pcp_camera *cam, const pcp_cull_param
   ctx->hull_valid.clear();
   ctx->colour_state_live = false;
   ctx->colour_result_live = false;
+  ctx->labels_live = false;
   return PCP_OK;
 }
 
@@ -1008,6 +1011,7 @@ int pcp_set_frames(pcp_context *ctx, const pcp_pose *poses, int32_t n_frames, co
   ctx->match_live = false;  // PCP_MATCH_RADIUS: E (and with it R_c) depends on the keyframes
   ctx->colour_state_live = false;
   ctx->colour_result_live = false;
+  ctx->labels_live = false;
   return PCP_OK;
 }
 

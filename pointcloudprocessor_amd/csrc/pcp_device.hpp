@@ -362,6 +362,40 @@ struct Top5 {
     const uint32_t has = (ri | gi | bi) ? 1u : 0u;  // removePointsWithNoColor hpp:238-252
     return ri | (gi << 8) | (bi << 16) | (has << 24);
   }
+  // Fused segmentation label ("Fused segmentation labels"): the list's entries carry the whole texel, whose top
+  // byte m_k is the mask of the view's pixel.  label = floor(sum m_k S_k / sum S_k) with S_k = s_k * 2^26, an integer below
+  // 2^27 for every fp32 score in [2^-3, 2) (the product with a power of two is exact, the ulp of such a score is at least
+  // 2^-26); num < 5 * 255 * 2^27 < 2^38, den < 5 * 2^27 < 2^30.  The quotient is at most 255: eight compare-and-set steps
+  // from the top bit down find it without a 64-bit division.  A score outside the range sets `bad` (the caller reports
+  // PCP_ERR_RANGE).  Packed label | hits<<8 | views<<16; an empty list gives 0.
+  __device__ __forceinline__ uint32_t labels(uint32_t &bad) const {
+    const float ss[5] = {s0, s1, s2, s3, s4};
+    const uint32_t cc[5] = {c0, c1, c2, c3, c4};
+    const int32_t ff[5] = {f0, f1, f2, f3, f4};
+    uint64_t num = 0;
+    uint32_t den = 0u, hits = 0u, views = 0u;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      if (ff[k] >= 0) {
+        const float s = ss[k];
+        if (!(s >= 0x1p-3f && s < 2.0f)) bad = 1u;
+        const uint32_t S = static_cast<uint32_t>(s * 0x1p26f);
+        const uint32_t m = cc[k] >> 24;
+        num += static_cast<uint64_t>(m) * S;
+        den += S;
+        hits += m == 255u ? 1u : 0u;
+        views += 1u;
+      }
+    }
+    if (views == 0u) return 0u;
+    uint32_t q = 0u;
+#pragma unroll
+    for (uint32_t bit = 128u; bit != 0u; bit >>= 1) {
+      const uint32_t t = q | bit;
+      if (static_cast<uint64_t>(t) * den <= num) q = t;
+    }
+    return q | (hits << 8) | (views << 16);
+  }
 };
 
 }  // namespace pcp

@@ -237,6 +237,11 @@ struct pcp_context {
   bool copy_pending[2] = {false, false};
   bool colour_state_live = false;
   bool colour_result_live = false;
+  // fused segmentation labels (pcp_set_label_fusion): label | hits<<8 | views<<16 per point, input order, written next to
+  // the colour word by the label form of the colour kernels; one buffer (not double-buffered); word n is the range flag
+  bool label_fusion = false;
+  bool labels_live = false;
+  pcp::DevBuf<uint32_t> labels;
 
   // PCP_MATCH_RADIUS (pcp_match.hip): the neighbour table within R_c, built by the first colour pass in that mode and
   // dropped by pcp_upload_cloud / pcp_set_frames (E depends on both).  Set A = points whose row holds another point.

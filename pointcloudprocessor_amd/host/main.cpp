@@ -45,6 +45,15 @@
 //     world round trip finds it; radius = PCP_MATCH_RADIUS, every map point within 10 um of the sample, as the reference's
 //     kdtree.radiusSearch does (maps with duplicated points differ).  radius needs the whole map on one GPU: --gpus N > 1
 //     with it is rejected.
+//   * --fuseMasks 0|1 (new, default 0 = the reference's behaviour; needs --mask_image_folder): 1 = one segmentation label
+//     per map point.  The reference appends every keyframe's mask samples to cloudInWorldWithRGBandMask.pcd
+//     (PointCloudProcessor.cpp:533-551, 932-947, "TODO: fix it" at :938): every map point once per keyframe that sees it,
+//     with conflicting labels.  With 1 that file has exactly the rows, in the order, of cloudInWorldWithRGB.pcd -- the map
+//     point's x y z, the same rgb (after --smoothColorsRadius when given; no (255,0,0) override) -- and segmentMask is the
+//     label fused on the GPU from the masks of the point's top-5 views (pcp_set_label_fusion; DESIGN.md "Fused segmentation
+//     labels"); the host concatenation is not built.  A keyframe whose mask is missing throws "Failed to read image from:
+//     <mask path>" (exit -2).  The per-keyframe _rgb-mask.pcd dumps are still written, unless --skip_filtered_dumps 1: the
+//     per-keyframe loop is then skipped altogether.  Works with --gpus N and --matchBack radius.
 #include <cfloat>
 #include <chrono>
 #include <cmath>
@@ -120,6 +129,7 @@ struct Options {
   int mls_upsampling = -1;
   double mls_upsampling_radius = 0.05, mls_upsampling_step = 0.01;  // PointCloudProcessor.cpp:74-75
   float smooth_colors_radius = 0.0f;  // 0: smoothColorsWithLocalRegion off (PointCloudProcessor.cpp:597)
+  bool fuse_masks = false;            // --fuseMasks 1: one fused label per map point in cloudInWorldWithRGBandMask.pcd
 };
 
 static bool parse_bool(const std::string &v) {  // boost::program_options bool semantics
@@ -179,6 +189,12 @@ static Options parse(int argc, char **argv) {
         throw std::runtime_error("the argument ('" + v + "') for option '--smoothColorsRadius' is invalid (0 = off, or 0 < r <= 1)");
       o.smooth_colors_radius = rf;
     }
+    else if (a == "--fuseMasks") {
+      const std::string v = next();
+      if (v != "0" && v != "1")
+        throw std::runtime_error("the argument ('" + v + "') for option '--fuseMasks' is invalid (0, 1)");
+      o.fuse_masks = v == "1";
+    }
     else if (a == "--cull") {
       const std::string v = next();
       if (v == "zbuffer") o.cull_mode = PCP_CULL_ZBUFFER;
@@ -196,6 +212,8 @@ static Options parse(int argc, char **argv) {
   }
   if (o.match_mode == PCP_MATCH_RADIUS && o.gpus > 1)
     throw std::runtime_error("the option '--matchBack radius' needs the whole map on one GPU (--gpus 1)");
+  if (o.fuse_masks && o.maskImageFolder.empty())
+    throw std::runtime_error("the option '--fuseMasks 1' needs the masks (--mask_image_folder)");
   return o;
 }
 
@@ -620,7 +638,14 @@ class Processor {
     std::vector<float> wxyz;
     std::vector<uint8_t> wrgb;
     std::vector<uint16_t> wmask;
-    if (enableMaskSegmentation) {
+    if (opt.fuse_masks) {
+      // every keyframe's mask takes part in the fusion: a missing one ends the run (the reference ends with -2 too, :776-781
+      // and the writer's exception)
+      for (size_t k = 0; k < keyframes.size(); ++k)
+        if (mask_missing[k]) throw std::runtime_error("Failed to read image from: " + keyframes[k].maskImagePath);
+      gpu->setLabelFusion(true);
+    }
+    if (enableMaskSegmentation && !(opt.fuse_masks && opt.skip_filtered_dumps)) {
       for (size_t k = 0; k < keyframes.size(); ++k) {
         VisiblePoints v;
         if (mask_missing[k])  // :779-780: message, empty scanInBodyWithRGBandMask -> PCDWriter throws below (exit -2)
@@ -635,6 +660,7 @@ class Processor {
         if (writeASCII_XYZRGBMask(path, v.xyz_cam.data(), v.rgb.data(), v.mask.data(), v.index.size()) == -1)
           throw std::runtime_error("Couldn't save filtered point cloud to PCD file.");
         std::cout << "Filtered point cloud saved to: " << path << ", the point size is " << v.index.size() << std::endl;
+        if (opt.fuse_masks) continue;  // the fused file has one row per map point: no concatenation
         wxyz.insert(wxyz.end(), v.xyz_world.begin(), v.xyz_world.end());
         wrgb.insert(wrgb.end(), v.rgb.begin(), v.rgb.end());
         wmask.insert(wmask.end(), v.mask.begin(), v.mask.end());
@@ -649,6 +675,11 @@ class Processor {
       Phase ph("colour_smooth_gpu_s");
       gpu->smoothColorsWithLocalRegion(opt.smooth_colors_radius, rgb, has);
     }
+    std::vector<uint8_t> label;
+    if (opt.fuse_masks) {
+      Phase ph("labels_gpu_s");
+      gpu->labels(label);  // of the colour result above; the local smoothing leaves them alone
+    }
     Phase ph_w("final_pcd_write_ascii_s");
     XYZICloud out;
     std::vector<uint8_t> out_rgb;
@@ -656,8 +687,14 @@ class Processor {
       if (has[i]) {
         out.push_back(cloud.x[i], cloud.y[i], cloud.z[i], 0.0f);
         out_rgb.insert(out_rgb.end(), {rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]});
+        if (opt.fuse_masks) {  // the same rows, the map point itself, its fused label
+          wxyz.insert(wxyz.end(), {cloud.x[i], cloud.y[i], cloud.z[i]});
+          wmask.push_back(label[i]);
+        }
       }
+    if (opt.fuse_masks) wrgb = out_rgb;
     if (enableMaskSegmentation && !wmask.empty()) {  // saveColorizedPointCloud(rgbCloud, withMask), :933-960
+      Phase ph_m("mask_pcd_rows_s");  // (inside final_pcd_write_ascii_s)
       const std::string path = opt.outputPath + "cloudInWorldWithRGBandMask.pcd";
       if (writeASCII_XYZRGBMask(path, wxyz.data(), wrgb.data(), wmask.data(), wmask.size()) == -1)
         throw std::runtime_error("Couldn't save colorized and segment colored point cloud.");

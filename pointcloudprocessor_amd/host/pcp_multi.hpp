@@ -254,6 +254,23 @@ class MultiDevice {
     }
   }
 
+  // Fused segmentation labels (Colorizer::setLabelFusion) on every shard: the labels are rank-local like the colours
+  void setLabelFusion(bool enable) {
+    for (int r = 0; r < size(); ++r) device(r).check(pcp_set_label_fusion(device(r).get(), enable ? 1 : 0));
+  }
+  // label / hits / views of every input point after colorize() with fusion on: the shards' arrays, concatenated
+  void labels(std::vector<uint8_t> &label, std::vector<uint8_t> *hits = nullptr, std::vector<uint8_t> *views = nullptr) {
+    const size_t n = static_cast<size_t>(n_);
+    label.resize(n);
+    if (hits) hits->resize(n);
+    if (views) views->resize(n);
+    for (int r = 0; r < size(); ++r) {
+      const int64_t lo = shardBegin(r);
+      device(r).check(pcp_colour_labels(device(r).get(), label.data() + lo, hits ? hits->data() + lo : nullptr,
+                                        views ? views->data() + lo : nullptr));
+    }
+  }
+
   // smoothColorsWithLocalRegion(rgbCloud, radius) (PointCloudProcessor.cpp:634-703) over the colours colorize() returned.
   // One GPU: in place on its result.  N > 1: the index shards hold slices of the map only, so the gathered words are
   // smoothed on a context of GPU 0 that holds the whole map (the hull context when there is one) -- the one-GPU result.

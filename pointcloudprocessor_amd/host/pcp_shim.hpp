@@ -118,6 +118,19 @@ class Colorizer {
     has.resize(n);
     dev_.check(pcp_colorize(dev_.get(), rgb.data(), has.data()));
   }
+  // Fused segmentation labels (pcp_set_label_fusion): where the reference appends every keyframe's mask samples to one
+  // cloud (PointCloudProcessor.cpp:533-551, the TODO at :938), colorize() then also fuses the masks of each point's top-5
+  // views into one label per map point.  Every keyframe needs its mask (Device::uploadMask).  Off by default.
+  void setLabelFusion(bool enable) const { dev_.check(pcp_set_label_fusion(dev_.get(), enable ? 1 : 0)); }
+  // label, hits (views whose mask is 255) and views (<= 5) of every input point, after colorize() with fusion on;
+  // smoothColorsWithLocalRegion leaves them alone
+  void labels(std::vector<uint8_t> &label, std::vector<uint8_t> *hits = nullptr, std::vector<uint8_t> *views = nullptr) const {
+    const size_t n = static_cast<size_t>(dev_.cloudSize());
+    label.resize(n);
+    if (hits) hits->resize(n);
+    if (views) views->resize(n);
+    dev_.check(pcp_colour_labels(dev_.get(), label.data(), hits ? hits->data() : nullptr, views ? views->data() : nullptr));
+  }
   // PointCloudProcessor::smoothColorsWithLocalRegion(rgbCloud, radius), PointCloudProcessor.cpp:634-703 (its call
   // smoothColorsWithLocalRegion(rgbCloud, 0.1) is commented out at :597): in place on the result of colorize(); rgb / has
   // (3 + 1 per input point) receive the smoothed colours and the removePointsWithNoColor flag.  Returns the coloured points.

@@ -91,6 +91,16 @@ class HipEngine:
             self._depth_tensor = (key, torch.as_tensor(_DeviceArray(ptr, n), device=f"cuda:{self.device}"))
         return self._depth_tensor[1]
 
+    def set_label_fusion(self, enable: bool = True):
+        """Fused segmentation labels (pcp_set_label_fusion): every later colour result of this engine carries label / hits /
+        views per point; every keyframe then needs its mask."""
+        self.ctx.set_label_fusion(enable)
+        self.fuse_labels = bool(enable)
+
+    def labels(self):
+        """dict(label, hits, views), uint8[n] each, of the latest colour result (label fusion on)."""
+        return self.ctx.colour_labels()
+
     def colour_from_depth(self, download=True):
         return self.ctx.colorize_from_depth(download=download)
 
@@ -130,8 +140,18 @@ class PointCloudColorizer:
         self.group = group
         self.chunks = chunks
 
-    def run(self, download: bool = True, local_smooth_radius: float = 0.0):
+    def _with_labels(self, out: dict, fuse_labels: bool, download: bool):
+        if fuse_labels and download:
+            out = dict(out, **self.engine.labels())
+        return out
+
+    def run(self, download: bool = True, local_smooth_radius: float = 0.0, fuse_labels: bool = False):
         """Local points' colours: dict(rgb (n,3) uint8, has (n,) uint8).
+
+        fuse_labels: one segmentation label per point from the masks of its top-5 views ("Fused segmentation
+        labels"); the dict gains label, hits, views (n,) uint8 (rank-local, as the colours; without download they stay on
+        the device: engine.ctx.colour_labels_device()).  Every keyframe needs an uploaded mask.  The local colour
+        smoothing leaves them alone.
 
         Multi-rank: the keyframes are split into `chunks` groups (0 = chosen from the size of the maps); the
         all-reduce(MIN) of one group's depth maps (RCCL stream) overlaps the depth pass of the next group.
@@ -144,12 +164,14 @@ class PointCloudColorizer:
         if local_smooth_radius and self.world > 1:
             raise ValueError("local_smooth_radius: the local colour smoothing runs on one rank holding the whole map "
                              "(smooth the gathered words with Context.colour_smooth_local_packed)")
+        if fuse_labels != getattr(self.engine, "fuse_labels", False):
+            self.engine.set_label_fusion(fuse_labels)
         if self.world == 1:
             self.engine.depth_pass()
             out = self.engine.colour_from_depth(download=download)
             if local_smooth_radius:
                 out = self.engine.smooth_colours_local(local_smooth_radius, download=download)
-            return out
+            return self._with_labels(out, fuse_labels, download)
         import torch.distributed as dist
 
         F = self.engine.n_frames
@@ -174,10 +196,11 @@ class PointCloudColorizer:
             import torch
 
             torch.cuda.current_stream().synchronize()
-        return self.engine.colour_from_depth(download=download)
+        return self._with_labels(self.engine.colour_from_depth(download=download), fuse_labels, download)
 
     def gather(self, local: dict, n_total: int):
-        """All-gather the per-shard colours into full-length arrays (every rank)."""
+        """All-gather the per-shard colours (and the fused labels, when `local` holds them) into full-length arrays
+        (every rank)."""
         if self.world == 1:
             return local
         import torch
@@ -185,21 +208,27 @@ class PointCloudColorizer:
 
         sizes = [shard_bounds(n_total, r, self.world) for r in range(self.world)]
         maxn = max(hi - lo for lo, hi in sizes)
-        packed = np.zeros((maxn, 4), np.uint8)
+        extra = [k for k in ("label", "hits", "views") if local.get(k) is not None]
+        packed = np.zeros((maxn, 4 + len(extra)), np.uint8)
         lo, hi = sizes[self.rank]
         packed[: hi - lo, :3] = local["rgb"]
         packed[: hi - lo, 3] = local["has"]
+        for c, k in enumerate(extra):
+            packed[: hi - lo, 4 + c] = local[k]
         dev = "cuda" if dist.get_backend(self.group) == "nccl" else "cpu"
         mine = torch.from_numpy(packed).to(dev)
         outs = [torch.empty_like(mine) for _ in range(self.world)]
         dist.all_gather(outs, mine, group=self.group)
         rgb = np.zeros((n_total, 3), np.uint8)
         has = np.zeros(n_total, np.uint8)
+        more = {k: np.zeros(n_total, np.uint8) for k in extra}
         for r, (lo, hi) in enumerate(sizes):
             a = outs[r].cpu().numpy()
             rgb[lo:hi] = a[: hi - lo, :3]
             has[lo:hi] = a[: hi - lo, 3]
-        return dict(rgb=rgb, has=has)
+            for c, k in enumerate(extra):
+                more[k][lo:hi] = a[: hi - lo, 4 + c]
+        return dict(rgb=rgb, has=has, **more)
 
 
 def keyframe_block(n_frames: int, rank: int, world: int):
