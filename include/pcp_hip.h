@@ -48,7 +48,10 @@ extern "C" {
                                 (pcp_mls_params.upsampling accepts PCP_UPSAMPLING_SAMPLE_LOCAL_PLANE; older libraries refuse
                                 it with PCP_ERR_INVALID);
                                 entry points added, no layout changed: pcp_set_label_fusion / pcp_colour_labels /
-                                pcp_colour_labels_device (fused segmentation labels; off by default) */
+                                pcp_colour_labels_device (fused segmentation labels; off by default);
+                                entry points added, no layout changed: pcp_upload_cloud_from_result, pcp_depth_accum_reset / _merge /
+                                _apply / _device, pcp_cloud_smooth_stream_seek, pcp_colour_compact (streamed colourisation: a
+                                smoothed cloud larger than one upload coloured chunk by chunk; nothing runs unless called) */
 
 #define PCP_OK 0
 #define PCP_ERR_INVALID (-1) /* bad argument */
@@ -187,6 +190,15 @@ int pcp_upload_cloud(pcp_context *ctx, const float *x, const float *y, const flo
 /* AoS upload straight from pcl::PointCloud<PointXYZI>::points.data(): x,y,z are
  * the first three floats of every `stride_bytes` record (32 for PointXYZI). */
 int pcp_upload_cloud_aos(pcp_context *ctx, const void *points, int64_t n, int64_t stride_bytes);
+/* The rows of src's latest smoothing result -- what pcp_mls_fetch returns as out_xyz, from pcp_mls_process*, pcp_cloud_smooth,
+ * pcp_mls_stream_next or pcp_cloud_smooth_stream_next -- become the cloud of dst, device to device: exactly the cloud
+ * pcp_upload_cloud_aos(dst, fetched_xyz, n, 12) builds (same spatial order, tile spheres and resets).  *out_n (nullable) = its
+ * points.  Both contexts on one GPU, else PCP_ERR_INVALID.  dst's stream waits for src's through an event: the caller does not
+ * synchronise src.  With dst != src nothing of src changes (an open stream stays open) and src may produce its next result as
+ * soon as the call returns.  dst == src is allowed: the rows are copied aside, then the upload proceeds as any upload does (the
+ * result and an open stream end).  No smoothing result since src's latest upload: PCP_ERR_STATE.  A result of 0 rows: an empty
+ * cloud, PCP_OK. */
+int pcp_upload_cloud_from_result(pcp_context *dst, pcp_context *src, int64_t *out_n);
 int64_t pcp_cloud_size(const pcp_context *ctx);
 
 /* ---- frames ------------------------------------------------------------- */
@@ -311,6 +323,21 @@ int pcp_depth_pass(pcp_context *ctx, int32_t frame_begin, int32_t frame_end);
  * all-reduce(MIN) across point shards (multi-GPU), and its length in floats */
 int pcp_depth_maps_device(pcp_context *ctx, void **device_ptr, int64_t *n_floats);
 int pcp_download_depth_map(pcp_context *ctx, int32_t frame, float *out_depth_map);
+/* Depth-map accumulator: n_frames*(H/14)*(W/14) floats per context that SURVIVE pcp_upload_cloud* / pcp_upload_cloud_from_result
+ * (pcp_set_camera, pcp_set_frames and pcp_destroy drop them).  The maps are a MIN over all points, so a cloud handed over in
+ * parts -- the chunks of a streamed smoothing chain -- is an index shard in time: merge every part's maps, apply the merged maps
+ * to each part again, and the parts' colour results concatenate to the result of the whole cloud, bit for bit.
+ *   _reset  allocates the buffer and sets every cell to the maps' "far" value (FLT_MAX);
+ *   _merge  accumulator = min(accumulator, the context's maps), all keyframes; every keyframe must have been covered by
+ *           pcp_depth_pass since the latest upload, else PCP_ERR_STATE;
+ *   _apply  overwrites the context's maps with the accumulator; same precondition (the context's own pcp_depth_pass has built
+ *           its tile masks, as on a shard after the all-reduce(MIN));
+ *   _device the buffer's device address and length in floats (for an all-reduce(MIN) across GPUs).
+ * All four return PCP_ERR_STATE under PCP_CULL_HPR (see pcp_depth_maps_device), the last three before _reset. */
+int pcp_depth_accum_reset(pcp_context *ctx);
+int pcp_depth_accum_merge(pcp_context *ctx);
+int pcp_depth_accum_apply(pcp_context *ctx);
+int pcp_depth_accum_device(pcp_context *ctx, void **device_ptr, int64_t *n_floats);
 /* Where the single-keyframe calls (pcp_cull_frame, pcp_frame_visible, pcp_nid_prepare) take a keyframe's depth map
  * from.  PCP_DEPTH_OWN (default): each call builds it from the uploaded points, as ViewCulling::view_culling does.
  * PCP_DEPTH_BATCHED: they use the maps pcp_depth_pass left behind -- for a context that holds one index shard of the
@@ -353,6 +380,13 @@ int pcp_download_wait_previous(pcp_context *ctx);
 /* device address of the packed per-point result (r | g<<8 | b<<16 | has<<24),
  * valid after pcp_colour_finalise / pcp_colorize, for device-side gathers */
 int pcp_colour_result_device(pcp_context *ctx, void **device_ptr, int64_t *n_words);
+/* removePointsWithNoColor (PointCloudProcessor.hpp:238-252) on the device: the rows of the current colour result (after
+ * pcp_colour_smooth_local: the smoothed one) whose has bit is set, in input order.  out_index m rows of the uploaded cloud,
+ * out_xyz 3*m (the uploaded coordinates bit for bit), out_rgb 3*m (r, g, b), out_label m (the fused label); host memory, all
+ * nullable, at most `capacity` rows each.  *out_count = the true count m even when capacity is smaller.  No colour result, or
+ * out_label asked of a result made without label fusion: PCP_ERR_STATE. */
+int pcp_colour_compact(pcp_context *ctx, int64_t capacity, int32_t *out_index, float *out_xyz, uint8_t *out_rgb, uint8_t *out_label,
+                       int64_t *out_count);
 
 /* Fused segmentation labels ("Fused segmentation labels"): one label per map point from the masks of the
  * point's top-5 views, where the reference writes every point once per keyframe that sees it
@@ -482,6 +516,10 @@ int pcp_cloud_smooth_stream_begin(pcp_context *ctx, const pcp_mls_params *p, int
                                   int64_t *out_kept_rows, int32_t *out_chunks);
 int pcp_cloud_smooth_stream_next(pcp_context *ctx, int64_t *out_count);
 int pcp_cloud_smooth_stream_end(pcp_context *ctx);
+/* The chunk the next pcp_cloud_smooth_stream_next emits, 0 <= chunk <= chunks (else PCP_ERR_RANGE); with chunk == chunks that
+ * call returns 0 rows.  Sweep 2 reads stored distances, so a chunk may be emitted any number of times: the stream stays open
+ * after its last chunk until _end, an upload or another smoothing call ends it.  No open stream: PCP_ERR_STATE. */
+int pcp_cloud_smooth_stream_seek(pcp_context *ctx, int32_t chunk);
 /* diagnostic of the last pcp_cloud_smooth_stream_begin: out[0] halo in planes (as finally used, the widest), [1] chunks redone
  * with a wider halo, [2] threshold of the last filter, [3] largest |x displacement| of a row from its voxel (m; over all rows),
  * [4] smallest margin of any chunk (m; > [3] proves the halo), [5] rows computed including halos, [6] the displacement sweep 0's

@@ -259,6 +259,14 @@ class Context:
                                                   C.c_int64(pts.strides[0])))
         self.n = pts.shape[0]
 
+    def upload_cloud_from_result(self, src: "Context") -> int:
+        """The rows of `src`'s latest smoothing result become this context's cloud, device to device
+        (pcp_upload_cloud_from_result); returns the number of points."""
+        n = C.c_int64()
+        self._check(self.lib.pcp_upload_cloud_from_result(self.h, src.h, C.byref(n)))
+        self.n = n.value
+        return n.value
+
     def set_frames(self, poses, T_opt=None):
         poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
         F = len(poses)
@@ -408,6 +416,38 @@ class Context:
         self._check(self.lib.pcp_download_depth_map(self.h, C.c_int32(frame), _ptr(d)))
         return d.reshape(mh, mw)
 
+    # depth-map accumulator: survives the uploads (a chunk of a streamed cloud is an index shard in time)
+    def depth_accum_reset(self):
+        self._check(self.lib.pcp_depth_accum_reset(self.h))
+
+    def depth_accum_merge(self):
+        self._check(self.lib.pcp_depth_accum_merge(self.h))
+
+    def depth_accum_apply(self):
+        self._check(self.lib.pcp_depth_accum_apply(self.h))
+
+    def depth_accum_device(self):
+        p = C.c_void_p()
+        n = C.c_int64()
+        self._check(self.lib.pcp_depth_accum_device(self.h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def colour_compact(self, capacity: int | None = None, want_label: bool = False):
+        """removePointsWithNoColor on the device (pcp_colour_compact): dict(index, xyz, rgb[, label], count) of the rows of
+        the colour result that have a colour, input order; count is the true count even when capacity is smaller."""
+        cap = self.n if capacity is None else capacity
+        idx = np.empty(cap, np.int32)
+        xyz = np.empty((cap, 3), np.float32)
+        rgb = np.empty((cap, 3), np.uint8)
+        label = np.empty(cap, np.uint8) if want_label else None
+        cnt = C.c_int64()
+        self._check(self.lib.pcp_colour_compact(self.h, C.c_int64(cap), _ptr(idx), _ptr(xyz), _ptr(rgb), _ptr(label), C.byref(cnt)))
+        m = min(cnt.value, cap)
+        out = dict(index=idx[:m], xyz=xyz[:m], rgb=rgb[:m], count=cnt.value)
+        if want_label:
+            out["label"] = label[:m]
+        return out
+
     def colour_reset(self):
         self._check(self.lib.pcp_colour_reset(self.h))
 
@@ -553,6 +593,10 @@ class Context:
         """Ends the stream and frees the device memory it holds (pcp_cloud_smooth_stream_end)."""
         self._check(self.lib.pcp_cloud_smooth_stream_end(self.h))
 
+    def cloud_smooth_stream_seek(self, chunk: int):
+        """The chunk the next cloud_smooth_stream_next emits (0 .. chunks; any chunk may be emitted again)."""
+        self._check(self.lib.pcp_cloud_smooth_stream_seek(self.h, C.c_int32(chunk)))
+
     def mls_stream_seek(self, chunk: int):
         self._check(self.lib.pcp_mls_stream_seek(self.h, C.c_int32(chunk)))
 
@@ -580,6 +624,12 @@ class Context:
         idx = np.empty(count, np.int32)
         self._check(self.lib.pcp_mls_fetch(self.h, C.c_int64(count), _ptr(xyz), _ptr(nrm), _ptr(curv), _ptr(idx)))
         return dict(xyz=xyz, normal=nrm, curvature=curv, index=idx)
+
+    def mls_fetch_index(self, count: int) -> np.ndarray:
+        """Only the source indices of the latest smoothing result (4 B per row cross PCIe)."""
+        idx = np.empty(count, np.int32)
+        self._check(self.lib.pcp_mls_fetch(self.h, C.c_int64(count), None, None, None, _ptr(idx)))
+        return idx
 
     def sor(self, mean_k: int = 60, std_mul: float = 0.7):
         keep = np.empty(self.n, np.uint8)

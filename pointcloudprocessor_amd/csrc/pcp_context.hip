@@ -496,13 +496,25 @@ int spatial_order(pcp_context *ctx, const float *dx, const float *dy, const floa
   return PCP_OK;
 }
 
-// Either (x, y, z) SoA host arrays, or `aos` = n records of `stride` bytes starting with x y z (fp32).
+// Either (x, y, z) SoA host arrays, or `aos` = n records of `stride` bytes starting with x y z (fp32).  aos_on_device: the
+// records are device memory of the context's GPU, ready in the order of ctx->stream (pcp_upload_cloud_from_result); copy_aside:
+// they are copied to a buffer of the call's own before anything else touches the context.
 static int store_cloud(pcp_context *ctx, const float *x, const float *y, const float *z, int64_t n,
-                       const void *aos = nullptr, int64_t stride = 0) {
+                       const void *aos = nullptr, int64_t stride = 0, bool aos_on_device = false, bool copy_aside = false) {
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t sn = static_cast<size_t>(n);
   // pad every SoA plane to a multiple of 4 floats so float4 loads stay aligned
   const size_t plane = (sn + 3) & ~size_t(3);
+  DevBuf<uint32_t> raw;
+  struct RawGuard {  // (the early returns below leave no staging buffer behind)
+    DevBuf<uint32_t> &b;
+    ~RawGuard() { b.release(); }
+  } raw_guard{raw};
+  if (aos_on_device && copy_aside && n > 0) {
+    PCP_HIP_TRY(ctx, raw.ensure(static_cast<size_t>(n) * static_cast<size_t>(stride) / 4 + 4));
+    PCP_HIP_TRY(ctx, hipMemcpyAsync(raw.p, aos, static_cast<size_t>(n) * static_cast<size_t>(stride), hipMemcpyDeviceToDevice, ctx->stream));
+    aos = raw.p;
+  }
   PCP_HIP_TRY(ctx, ctx->xyz.ensure(3 * plane + 4));
   PCP_HIP_TRY(ctx, ctx->sxyz.ensure(3 * plane + 4));
   PCP_HIP_TRY(ctx, ctx->perm.ensure(sn + 4));
@@ -519,6 +531,7 @@ static int store_cloud(pcp_context *ctx, const float *x, const float *y, const f
   ctx->labels_live = false;
   match_table_release(ctx);  // PCP_MATCH_RADIUS: the table belongs to the cloud that is being replaced
   ctx->mls_count = 0;
+  ctx->mls_result_live = false;
   ctx->vgd_next = ctx->css_next = -1;  // the streams of the smoothing stage belong to the cloud that is being replaced
   ctx->css_ball = 0.0;
   std::fill(ctx->depth_valid.begin(), ctx->depth_valid.end(), uint8_t(0));
@@ -528,8 +541,11 @@ static int store_cloud(pcp_context *ctx, const float *x, const float *y, const f
   hipStream_t st = ctx->stream;
   float *dx = ctx->xyz.p, *dy = ctx->xyz.p + plane, *dz = ctx->xyz.p + 2 * plane;
   PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->sxyz.p, 0, (3 * plane + 4) * 4, st));  // plane padding reads as zeros
-  DevBuf<uint32_t> raw;
-  if (aos) {
+  if (aos && aos_on_device) {
+    // rows of a smoothing result: taken apart where they lie (the kernel is the device-to-device copy)
+    hipLaunchKernelGGL(k_up_deinterleave, dim3(up_blocks(n)), dim3(kUpBlock), 0, st, static_cast<const uint32_t *>(aos), stride / 4, n,
+                       dx, dy, dz);
+  } else if (aos) {
     // the records cross PCIe as they are and are taken apart on the device
     PCP_HIP_TRY(ctx, raw.ensure(static_cast<size_t>(n) * static_cast<size_t>(stride) / 4 + 4));
     PCP_HIP_TRY(ctx, hipMemcpyAsync(raw.p, aos, static_cast<size_t>(n) * static_cast<size_t>(stride), hipMemcpyHostToDevice, st));
@@ -602,7 +618,7 @@ int pcp_create(int32_t device, pcp_context **out) {
     hipFuncAttributes a;
     const hipError_t pl[] = {hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_up_bbox)), preload_colour(), preload_mls(),
                              preload_nid(), preload_hpr(), preload_colour_smooth(), preload_match(),
-                             preload_jpeg()};
+                             preload_jpeg(), preload_stream_colour()};
     for (hipError_t x : pl)
       if (x != hipSuccess && e == hipSuccess) e = x;
   }
@@ -675,6 +691,9 @@ void pcp_destroy(pcp_context *ctx) {
   ctx->images.release();
   ctx->hsv_tables.release();
   ctx->depth.release();
+  ctx->depth_accum.release();
+  ctx->cc_out.release();
+  if (ctx->handoff) (void)hipEventDestroy(ctx->handoff);
   ctx->depth_sq.release();
   ctx->tile_sphere.release();
   ctx->tile_mask.release();
@@ -911,6 +930,8 @@ int pcp_set_camera(pcp_context *ctx, const pcp_camera *cam, const pcp_cull_param
   ctx->mask_set.assign(ctx->mask_set.size(), 0);
   std::fill(ctx->depth_valid.begin(), ctx->depth_valid.end(), uint8_t(0));
   ctx->hull_valid.clear();
+  ctx->depth_accum.release();  // sized by the camera
+  ctx->depth_accum_live = false;
   ctx->colour_state_live = false;
   ctx->colour_result_live = false;
   ctx->labels_live = false;
@@ -942,6 +963,31 @@ int pcp_upload_cloud_aos(pcp_context *ctx, const void *points, int64_t n, int64_
     z[static_cast<size_t>(i)] = v[2];
   }
   return store_cloud(ctx, x.data(), y.data(), z.data(), n);
+}
+
+int pcp_upload_cloud_from_result(pcp_context *dst, pcp_context *src, int64_t *out_n) {
+  if (!dst || !src) return dst ? set_error(dst, PCP_ERR_INVALID, "pcp_upload_cloud_from_result: NULL source context") : PCP_ERR_INVALID;
+  if (out_n) *out_n = 0;
+  if (dst->device != src->device)
+    return set_error(dst, PCP_ERR_INVALID, "pcp_upload_cloud_from_result: the contexts are on GPUs %d and %d (one GPU only)", dst->device,
+                     src->device);
+  if (!src->mls_result_live)
+    return set_error(dst, PCP_ERR_STATE, "pcp_upload_cloud_from_result: the source context holds no smoothing result (pcp_mls_process*, "
+                     "pcp_cloud_smooth, pcp_mls_stream_next, pcp_cloud_smooth_stream_next since its latest upload)");
+  const int64_t m = src->mls_count;
+  const float *rows = src->mls_xyz.p;
+  if (m > 0 && !rows) return set_error(dst, PCP_ERR_STATE, "pcp_upload_cloud_from_result: the source result has no rows on the device");
+  PCP_HIP_TRY(dst, hipSetDevice(dst->device));
+  if (dst != src && m > 0) {
+    // the rows are ready in the order of src's stream: dst's stream waits for them there, the host does not
+    if (!src->handoff) PCP_HIP_TRY(dst, hipEventCreateWithFlags(&src->handoff, hipEventDisableTiming));
+    PCP_HIP_TRY(dst, hipEventRecord(src->handoff, src->stream));
+    PCP_HIP_TRY(dst, hipStreamWaitEvent(dst->stream, src->handoff, 0));
+  }
+  // (store_cloud returns after dst's stream has drained: src may overwrite its rows as soon as this call is back)
+  const int rc = store_cloud(dst, nullptr, nullptr, nullptr, m, rows, 12, /*aos_on_device=*/true, /*copy_aside=*/dst == src);
+  if (rc == PCP_OK && out_n) *out_n = m;
+  return rc;
 }
 
 int64_t pcp_cloud_size(const pcp_context *ctx) { return ctx ? ctx->n : -1; }
@@ -1008,6 +1054,8 @@ int pcp_set_frames(pcp_context *ctx, const pcp_pose *poses, int32_t n_frames, co
   ctx->mask_set.assign(static_cast<size_t>(n_frames), 0);
   ctx->depth_valid.assign(static_cast<size_t>(n_frames), 0);
   ctx->hull_valid.clear();
+  ctx->depth_accum.release();  // one map per keyframe of the set that is being replaced
+  ctx->depth_accum_live = false;
   ctx->match_live = false;  // PCP_MATCH_RADIUS: E (and with it R_c) depends on the keyframes
   ctx->colour_state_live = false;
   ctx->colour_result_live = false;

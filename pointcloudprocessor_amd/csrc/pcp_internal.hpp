@@ -211,6 +211,10 @@ struct pcp_context {
   pcp::DevBuf<unsigned long long> depth_sq;  // per cell, min of the squared fp64 range (bit pattern) during a depth pass
   std::vector<uint8_t> depth_valid;
   bool depth_from_batch = false;  // pcp_set_depth_source: single-keyframe calls use the batched (merged) maps
+  // pcp_depth_accum_*: the MIN of the maps of every cloud merged since the reset, [n_frames][mh*mw]; outlives the uploads
+  // (a chunk of a streamed cloud is an index shard in time), dropped by pcp_set_camera / pcp_set_frames
+  pcp::DevBuf<uint32_t> depth_accum;
+  bool depth_accum_live = false;
 
   // tiles = wavefront-sized runs of 64 Morton-ordered points: bounding spheres
   // (x, y, z, radius) and the tile x keyframe visibility masks [tile][mask_words]
@@ -308,6 +312,9 @@ struct pcp_context {
   pcp::DevBuf<float> mls_alt_xyz, mls_alt_normal, mls_alt_curv;
   pcp::DevBuf<int32_t> mls_alt_index;
   int64_t mls_count = 0;
+  bool mls_result_live = false;  // a smoothing call has left mls_count rows (0 included) since the latest upload
+  hipEvent_t handoff = nullptr;  // pcp_upload_cloud_from_result: recorded on this (source) context's stream
+  pcp::DevBuf<uint8_t> cc_out;   // pcp_colour_compact: the gathered rows (xyz | rgb | label) before they leave the device
   // pcp_mls_stream_*: the plan of a chunked VOXEL_GRID_DILATION emission (pcp_mls.hip VgdStream; word0, word1, count per chunk)
   std::vector<uint8_t> vgd_blob;
   std::vector<int64_t> vgd_chunks;
@@ -468,6 +475,7 @@ int match_table_prepare(pcp_context *ctx);
 void match_table_release(pcp_context *ctx);
 hipError_t preload_match();
 hipError_t preload_jpeg();
+hipError_t preload_stream_colour();
 
 inline int64_t div_up(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

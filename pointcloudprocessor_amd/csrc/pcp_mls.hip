@@ -2888,6 +2888,7 @@ static int mls_run(pcp_context *ctx, const CloudView &cv, const pcp_mls_params *
                    int32_t slab = 0, int32_t n_slabs = 1) {
   const int64_t n = cv.n;
   ctx->mls_count = 0;
+  ctx->mls_result_live = false;
   ctx->vgd_next = -1;  // a stream of an earlier call rests on the grid and the fits this call replaces
   ctx->css_next = -1;
   if (out_count) *out_count = 0;
@@ -3393,7 +3394,9 @@ int pcp_mls_process(pcp_context *ctx, const pcp_mls_params *p, int64_t *out_coun
   if (!ctx->xyz.p) return set_error(ctx, PCP_ERR_STATE, "pcp_mls_process: no cloud uploaded");
   if (int rcf = require_finite_cloud(ctx, "pcp_mls_process")) return rcf;
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  return mls_run(ctx, uploaded_view(ctx), p, out_count);
+  rc = mls_run(ctx, uploaded_view(ctx), p, out_count);
+  ctx->mls_result_live = rc == PCP_OK;
+  return rc;
 }
 
 int pcp_set_mls_local_plane(pcp_context *ctx, double upsampling_radius, double upsampling_step) {
@@ -3442,8 +3445,10 @@ int pcp_mls_stream_next(pcp_context *ctx, int64_t *out_count) {
     return set_error(ctx, PCP_ERR_STATE, "pcp_mls_stream_next: no stream (call pcp_mls_stream_begin)");
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t k = static_cast<size_t>(ctx->vgd_next) * 3;
+  ctx->mls_result_live = false;
   if (k >= ctx->vgd_chunks.size()) {  // past the last chunk
     ctx->mls_count = 0;
+    ctx->mls_result_live = true;
     return PCP_OK;
   }
   VgdStream S;
@@ -3451,6 +3456,7 @@ int pcp_mls_stream_next(pcp_context *ctx, int64_t *out_count) {
   int64_t m = 0;
   const int rc = vgd_emit(ctx, S, ctx->vgd_chunks[k], ctx->vgd_chunks[k + 1], ctx->vgd_chunks[k + 2], &m);
   if (rc != PCP_OK) return rc;
+  ctx->mls_result_live = true;
   ctx->vgd_next += 1;
   *out_count = m;
   return PCP_OK;
@@ -3483,7 +3489,9 @@ int pcp_mls_process_shard(pcp_context *ctx, const pcp_mls_params *p, int64_t ind
     return set_error(ctx, PCP_ERR_RANGE, "pcp_mls_process_shard: query range [%lld,%lld) outside 0..%lld",
                      (long long)index_begin, (long long)index_end, (long long)ctx->n);
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  return mls_run(ctx, uploaded_view(ctx), p, out_count, index_begin, index_end);
+  rc = mls_run(ctx, uploaded_view(ctx), p, out_count, index_begin, index_end);
+  ctx->mls_result_live = rc == PCP_OK;
+  return rc;
 }
 
 int pcp_mls_process_slab(pcp_context *ctx, const pcp_mls_params *p, int32_t slab, int32_t n_slabs, int64_t *out_count) {
@@ -3499,7 +3507,9 @@ int pcp_mls_process_slab(pcp_context *ctx, const pcp_mls_params *p, int32_t slab
     return set_error(ctx, PCP_ERR_INVALID, "pcp_mls_process_slab: query sharding supports upsampling NONE only");
   if (n_slabs < 1 || slab < 0 || slab >= n_slabs) return set_error(ctx, PCP_ERR_RANGE, "pcp_mls_process_slab: slab %d of %d", slab, n_slabs);
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  return mls_run(ctx, uploaded_view(ctx), p, out_count, 0, -1, false, 0, slab, n_slabs);
+  rc = mls_run(ctx, uploaded_view(ctx), p, out_count, 0, -1, false, 0, slab, n_slabs);
+  ctx->mls_result_live = rc == PCP_OK;
+  return rc;
 }
 
 int pcp_mls_fetch(pcp_context *ctx, int64_t capacity, float *out_xyz, float *out_normal, float *out_curvature,
@@ -3615,8 +3625,16 @@ int pcp_sor_finish(pcp_context *ctx, double std_mul, const double *all_chunk_sum
 // CloudSmooth::process end to end on the device (cloudSmooth.cpp:109-164):
 // SOR -> MovingLeastSquares (+ upsampling) -> SOR.  Results through pcp_mls_fetch;
 // out_index refers to the uploaded cloud.
+static int cloud_smooth_run(pcp_context *ctx, const pcp_mls_params *p, int64_t *out_count);
 int pcp_cloud_smooth(pcp_context *ctx, const pcp_mls_params *p, int64_t *out_count) {
   if (!ctx) return PCP_ERR_INVALID;
+  ctx->mls_result_live = false;
+  const int rc = cloud_smooth_run(ctx, p, out_count);
+  if (rc == PCP_OK) ctx->mls_result_live = true;  // (0 rows included: an empty result is a result)
+  return rc;
+}
+
+static int cloud_smooth_run(pcp_context *ctx, const pcp_mls_params *p, int64_t *out_count) {
   int rc = check_mls_params(ctx, p);
   if (rc != PCP_OK) return rc;
   if (!ctx->xyz.p) return set_error(ctx, PCP_ERR_STATE, "pcp_cloud_smooth: no cloud uploaded");
@@ -4043,13 +4061,17 @@ int pcp_cloud_smooth_stream_next(pcp_context *ctx, int64_t *out_count) {
                      "smoothing call ends a stream)");
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
   ctx->mls_count = 0;
+  ctx->mls_result_live = false;
   SmoothStream st;
   std::memcpy(&st, ctx->css_blob.data(), sizeof(st));
   const std::vector<int64_t> &ch = ctx->css_chunks;
   // (chunks whose every voxel lacks a valid fit have no rows: skipped)
   while (static_cast<size_t>(ctx->css_next) * 5 < ch.size() && ch[static_cast<size_t>(ctx->css_next) * 5 + 4] == 0) ctx->css_next += 1;
   const size_t c = static_cast<size_t>(ctx->css_next);
-  if (c * 5 >= ch.size()) return PCP_OK;  // past the last chunk
+  if (c * 5 >= ch.size()) {  // past the last chunk
+    ctx->mls_result_live = true;
+    return PCP_OK;
+  }
   const int64_t ia = ch[5 * c], ib = ch[5 * c + 1], voxels = ch[5 * c + 2], row0 = ch[5 * c + 3], rows = ch[5 * c + 4];
   const int64_t next_before = ctx->css_next;
   int rc;
@@ -4072,6 +4094,7 @@ int pcp_cloud_smooth_stream_next(pcp_context *ctx, int64_t *out_count) {
   if ((rc = compact_flags(ctx, ctx->m_flag.p, m, ctx->s_cell.p, m, &kept)) != PCP_OK) return rc;
   if (kept != m && (rc = compact_results(ctx, ctx->s_cell.p, m, kept)) != PCP_OK) return rc;
   ctx->mls_count = kept;
+  ctx->mls_result_live = true;
   ctx->css_next = next_before + 1;
   *out_count = kept;
   return PCP_OK;
@@ -4084,6 +4107,18 @@ int pcp_cloud_smooth_stream_end(pcp_context *ctx) {
   ctx->css_next = -1;
   ctx->css_chunks.clear();
   ctx->css_dist.release();
+  return PCP_OK;
+}
+
+int pcp_cloud_smooth_stream_seek(pcp_context *ctx, int32_t chunk) {
+  if (!ctx) return PCP_ERR_INVALID;
+  if (ctx->css_next < 0 || ctx->css_blob.size() != sizeof(SmoothStream))
+    return set_error(ctx, PCP_ERR_STATE, "pcp_cloud_smooth_stream_seek: no stream (call pcp_cloud_smooth_stream_begin; an upload or "
+                     "any other smoothing call ends a stream)");
+  const int64_t chunks = static_cast<int64_t>(ctx->css_chunks.size() / 5);
+  if (chunk < 0 || chunk > chunks)
+    return set_error(ctx, PCP_ERR_RANGE, "pcp_cloud_smooth_stream_seek: chunk %d outside 0..%lld", chunk, (long long)chunks);
+  ctx->css_next = chunk;  // (sweep 2 reads the stored distances: any chunk may be emitted again)
   return PCP_OK;
 }
 

@@ -54,6 +54,14 @@
 //     labels"); the host concatenation is not built.  A keyframe whose mask is missing throws "Failed to read image from:
 //     <mask path>" (exit -2).  The per-keyframe _rgb-mask.pcd dumps are still written, unless --skip_filtered_dumps 1: the
 //     per-keyframe loop is then skipped altogether.  Works with --gpus N and --matchBack radius.
+//   * --streamColour 0|1 (new, default 0; with --enableMLS 1) and --streamChunk voxels (default 2^28): 1 = the smoothed cloud
+//     is never gathered on the host.  The smoothing chain runs in its streamed form and every chunk of it is handed, on the
+//     device, to the colour stage (CloudSmooth::processAndColorizeStreamed; DESIGN.md "Streamed colourisation"): one sweep
+//     merges the chunks' depth maps, a second colours every chunk against the merged maps.  scans-crop_mls.pcd,
+//     cloudInWorldWithRGB.pcd and, with --fuseMasks 1, cloudInWorldWithRGBandMask.pcd are written chunk by chunk and are byte
+//     for byte the files of a --streamColour 0 run; a smoothed cloud of more rows than one upload takes (the reference's
+//     1 mm x 4 on a real map) can only be coloured this way.  One GPU, the z-buffer routine; the per-keyframe dumps, the NID
+//     stage, --matchBack radius, --smoothColorsRadius and masks without --fuseMasks 1 need the whole cloud and are refused.
 #include <cfloat>
 #include <chrono>
 #include <cmath>
@@ -130,6 +138,8 @@ struct Options {
   double mls_upsampling_radius = 0.05, mls_upsampling_step = 0.01;  // PointCloudProcessor.cpp:74-75
   float smooth_colors_radius = 0.0f;  // 0: smoothColorsWithLocalRegion off (PointCloudProcessor.cpp:597)
   bool fuse_masks = false;            // --fuseMasks 1: one fused label per map point in cloudInWorldWithRGBandMask.pcd
+  bool stream_colour = false;         // --streamColour 1: smoothing chain -> colour stage chunk by chunk on the device
+  int64_t stream_chunk = int64_t(1) << 28;  // --streamChunk: voxels per chunk (the capacity of the streamed fallback)
 };
 
 static bool parse_bool(const std::string &v) {  // boost::program_options bool semantics
@@ -195,6 +205,20 @@ static Options parse(int argc, char **argv) {
         throw std::runtime_error("the argument ('" + v + "') for option '--fuseMasks' is invalid (0, 1)");
       o.fuse_masks = v == "1";
     }
+    else if (a == "--streamColour") {
+      const std::string v = next();
+      if (v != "0" && v != "1")
+        throw std::runtime_error("the argument ('" + v + "') for option '--streamColour' is invalid (0, 1)");
+      o.stream_colour = v == "1";
+    }
+    else if (a == "--streamChunk") {
+      const std::string v = next();
+      char *end = nullptr;
+      const long long c = std::strtoll(v.c_str(), &end, 10);
+      if (v.empty() || end != v.c_str() + v.size() || c < 4096 || c >= (1ll << 31))
+        throw std::runtime_error("the argument ('" + v + "') for option '--streamChunk' is invalid (voxels per chunk, 4096 .. 2^31 - 1)");
+      o.stream_chunk = c;
+    }
     else if (a == "--cull") {
       const std::string v = next();
       if (v == "zbuffer") o.cull_mode = PCP_CULL_ZBUFFER;
@@ -214,6 +238,24 @@ static Options parse(int argc, char **argv) {
     throw std::runtime_error("the option '--matchBack radius' needs the whole map on one GPU (--gpus 1)");
   if (o.fuse_masks && o.maskImageFolder.empty())
     throw std::runtime_error("the option '--fuseMasks 1' needs the masks (--mask_image_folder)");
+  if (o.stream_colour) {
+    // every chunk is coloured on its own: what needs the whole smoothed cloud at once is refused here, before any GPU work
+    auto refuse = [](const std::string &what, const std::string &why) {
+      throw std::runtime_error("the option '--streamColour 1' does not work with " + what + " (" + why + ")");
+    };
+    if (!o.enableMLS) refuse("'--enableMLS 0'", "it streams the smoothing chain's chunks into the colour stage");
+    if (!o.skip_filtered_dumps) refuse("'--skip_filtered_dumps 0'", "a per-keyframe dump lists the whole cloud's visible points");
+    if (o.enableNIDOptimize) refuse("'--enableNIDOptimize 1'", "the NID stage reads the whole cloud");
+    if (o.enableInitialGuessManual) refuse("'--enableInitialGuessManual 1'", "the manual guess is not part of this build");
+    if (o.gpus > 1) refuse("'--gpus N' above 1", "the streamed form over several GPUs is not built");
+    if (o.cull_mode == PCP_CULL_HPR) refuse("'--cull hpr'", "a keyframe's hull is taken over the whole cloud");
+    if (o.match_mode == PCP_MATCH_RADIUS) refuse("'--matchBack radius'", "a sample's neighbours may lie in another chunk");
+    if (o.smooth_colors_radius > 0.0f) refuse("'--smoothColorsRadius'", "a point's neighbours may lie in another chunk");
+    if (!o.maskImageFolder.empty() && !o.fuse_masks)
+      refuse("'--mask_image_folder' without '--fuseMasks 1'", "the concatenated mask samples need every keyframe's visible points");
+    if (o.mls_upsampling >= 0 && o.mls_upsampling != PCP_UPSAMPLING_VOXEL_GRID_DILATION)
+      refuse("'--mlsUpsampling' other than vgd", "only VOXEL_GRID_DILATION is streamed");
+  }
   return o;
 }
 
@@ -256,6 +298,10 @@ class Processor {
     selectKeyframes();
     if (!opt.enableNIDOptimize) startDecoders();  // (with the NID stage the first consumer wants the images unadjusted and again later: decoded on demand)
     setupDevice();
+    if (opt.stream_colour) {
+      streamedColourisation();
+      return;
+    }
     if (!opt.skip_filtered_dumps) viewCullingAndSaveFilteredPcds();
     if (opt.enableNIDOptimize)
       applyNIDBasedPoseOptimization();
@@ -276,6 +322,7 @@ class Processor {
   bool images_uploaded = false, images_adjusted = false;
   std::vector<uint8_t> mask_missing;
   std::vector<double> T_camera_lidar_optimized;
+  pcp_mls_params mls_params{};  // --streamColour 1: the chain's parameters, kept for streamedColourisation
 
   void loadImagesAndOdometry() {  // :965-1005
     Phase ph("odometry_s");
@@ -346,13 +393,19 @@ class Processor {
         std::cerr << "Couldn't read file " << cropPath << std::endl;
         return;
       }
-      if (device_thread.joinable()) device_thread.join();  // (one thread at a time creates contexts: pcp_create sets process-wide defaults)
-      MultiCloudSmooth smooth(opt.gpus);  // --gpus N: MLS queries / voxel chunks dealt out over the GPUs (pcp_multi.hpp)
       pcp_mls_params mp;
       pcp_default_mls_params(&mp);  // PointCloudProcessor.cpp:67-86
       if (opt.mls_voxel_size > 0.0f) mp.vgd_voxel_size = opt.mls_voxel_size;
       if (opt.mls_dilation_iterations >= 0) mp.vgd_iterations = opt.mls_dilation_iterations;
       if (opt.mls_upsampling >= 0) mp.upsampling = opt.mls_upsampling;
+      if (opt.stream_colour) {
+        // the chain runs later, chunk by chunk into the colour stage (streamedColourisation): `cloud` is its input here
+        mls_params = mp;
+        cloud = std::move(crop8);
+        return;
+      }
+      if (device_thread.joinable()) device_thread.join();  // (one thread at a time creates contexts: pcp_create sets process-wide defaults)
+      MultiCloudSmooth smooth(opt.gpus);  // --gpus N: MLS queries / voxel chunks dealt out over the GPUs (pcp_multi.hpp)
       smooth.initialize(mp);
       smooth.setLocalPlaneSampling(opt.mls_upsampling_radius, opt.mls_upsampling_step);
       SmoothedCloud s = smooth.processWithOutlierRemoval(crop8.x.data(), crop8.y.data(), crop8.z.data(),
@@ -407,7 +460,8 @@ class Processor {
     if (device_thread.joinable()) device_thread.join();
     if (device_error) std::rethrow_exception(device_error);
     if (!gpu) gpu.reset(new MultiDevice(opt.gpus));
-    gpu->uploadCloud(cloud.x.data(), cloud.y.data(), cloud.z.data(), static_cast<int64_t>(cloud.size()));
+    // (--streamColour 1: the colour context starts with an empty cloud, the chunks arrive from the smoothing context)
+    gpu->uploadCloud(cloud.x.data(), cloud.y.data(), cloud.z.data(), opt.stream_colour ? 0 : static_cast<int64_t>(cloud.size()));
     // image size from the first keyframe image; cull size stays the reference's {4096,3000} (:206,:525)
     if (!keyframes.empty() && decoders) {  // (the decoders are on it already)
       std::unique_lock<std::mutex> lk(decoders->mu);
@@ -436,7 +490,7 @@ class Processor {
     std::vector<pcp_pose> poses;
     for (const auto &k : keyframes) poses.push_back(k.pose);
     gpu->setKeyframes(poses);
-    if (gpu->size() == 1 && opt.match_mode != PCP_MATCH_RADIUS) {
+    if (gpu->size() == 1 && opt.match_mode != PCP_MATCH_RADIUS && !opt.stream_colour) {  // (no chunk sees the whole cloud)
       // the reference credits a sample to EVERY map point within 10 um of it (radiusSearch, :571); --matchBack roundtrip to
       // the sample's own point.  Say so when the map holds points that close together (duplicates of merged scans).
       int64_t close = 0;
@@ -630,6 +684,54 @@ class Processor {
     stopDecoders();
     images_uploaded = true;
     images_adjusted = adjusted;
+  }
+
+  // --streamColour 1: CloudSmooth::process (:139-145) and pcdColorizationAndSmooth (:474-602) chunk by chunk.  The files are
+  // those of the one-shot path: <stem>_mls.pcd (its row count is known when the stream begins), cloudInWorldWithRGB.pcd and,
+  // with --fuseMasks 1, cloudInWorldWithRGBandMask.pcd (bodies to temporaries beside the outputs, headers once the counts are
+  // known).
+  void streamedColourisation() {
+    uploadImages(true);
+    if (opt.fuse_masks) {
+      for (size_t k = 0; k < keyframes.size(); ++k)
+        if (mask_missing[k]) throw std::runtime_error("Failed to read image from: " + keyframes[k].maskImagePath);
+      gpu->setLabelFusion(true);
+    }
+    Phase ph("stream_colour_s");
+    Device smoothing(0);
+    smoothing.uploadCloud(cloud.x.data(), cloud.y.data(), cloud.z.data(), static_cast<int64_t>(cloud.size()));
+    CloudSmooth cs(smoothing, mls_params);
+    cs.setLocalPlaneSampling(opt.mls_upsampling_radius, opt.mls_upsampling_step);
+    const std::string cropPath = opt.outputPath + "scans-crop.pcd";
+    const std::string mlsPath = fs::path(cropPath).stem().string() + "_mls.pcd";  // CWD-relative, sic (B14)
+    const std::string rgbPath = opt.outputPath + "cloudInWorldWithRGB.pcd", maskPath = opt.outputPath + "cloudInWorldWithRGBandMask.pcd";
+    std::unique_ptr<ChunkedAsciiWriter> mls, mask;
+    ChunkedAsciiWriter rgb(rgbPath, ChunkedAsciiWriter::XYZRGB);
+    if (opt.fuse_masks) mask.reset(new ChunkedAsciiWriter(maskPath, ChunkedAsciiWriter::XYZRGBMask));
+    const StreamedColourStats st = cs.processAndColorizeStreamed(
+        gpu->device(0), opt.stream_chunk,
+        [&](const ColouredChunk &c) {
+          rgb.appendColoured(c.xyz.data(), c.rgb.data(), nullptr, c.index.size());
+          if (mask) mask->appendColoured(c.xyz.data(), c.rgb.data(), c.label.data(), c.index.size());
+        },
+        [&](const SmoothedCloud &s, int64_t kept_rows) {
+          if (!mls) mls.reset(new ChunkedAsciiWriter(mlsPath, ChunkedAsciiWriter::PointNormal, kept_rows));
+          mls->appendPointNormal(s.xyz.data(), s.normal.data(), s.curvature.data(), s.curvature.size());
+        },
+        opt.fuse_masks);
+    std::cout << "streamed colour: " << st.chunks << " chunks, " << st.rows << " rows, " << st.coloured << " coloured" << std::endl;
+    g_clock.add("stream_colour_sweep_a_s", st.sweep_a_s);
+    g_clock.add("stream_colour_sweep_b_s", st.sweep_b_s);
+    if (!mls) mls.reset(new ChunkedAsciiWriter(mlsPath, ChunkedAsciiWriter::PointNormal, 0));  // no row: the writer's exception
+    if (mls->finish() == -1) throw std::runtime_error("Couldn't save the smoothed point cloud.");
+    if (mask && mask->rows() > 0) {  // saveColorizedPointCloud(rgbCloud, withMask), :933-960
+      if (mask->finish() == -1) throw std::runtime_error("Couldn't save colorized and segment colored point cloud.");
+      std::cout << "All colored and segment colored cloud saved to: " << maskPath << std::endl;
+    }
+    if (rgb.rows() > 0) {  // :912-929
+      if (rgb.finish() == -1) throw std::runtime_error("Couldn't save colorized point cloud.");
+      std::cout << "All colored cloud saved to: " << rgbPath << std::endl;
+    }
   }
 
   void pcdColorizationAndSmooth() {  // :474-602

@@ -277,15 +277,11 @@ inline std::string header(const char *fields, const char *sizes, const char *typ
     << "\nDATA ascii\n";
   return h.str();
 }
-// Formats rows [0, n) with `row(out, i)` on all host cores (contiguous slices, one buffer per thread) and writes
-// header + slices in order: the bytes are those of a sequential writer, the wall time is not (the reference's
-// PCDWriter::writeASCII formats one value at a time on one thread and dominates its runs at scale).
+// Formats rows [0, n) with `row(out, i)` on all host cores (contiguous slices, one buffer per thread): the slices in order
+// are the bytes of a sequential writer, the wall time is not (the reference's PCDWriter::writeASCII formats one value at a
+// time on one thread and dominates its runs at scale).
 template <class Row>
-inline int write_rows(const std::string &path, const std::string &head, size_t n, size_t bytes_per_row_hint, Row row) {
-  // pcl::PCDWriter::writeASCII (PCL 1.10 pcd_io.hpp) throws pcl::IOException on an empty cloud before touching the
-  // file; PCLException's what() is ": <description>" when no file / function / line is attached.  The reference's
-  // main catches it and exits with -2 (main.cpp:64-68) -- e.g. a keyframe whose mask image is missing.
-  if (n == 0) throw std::runtime_error(": [pcl::PCDWriter::writeASCII] Input point cloud has no data!");
+inline std::vector<std::string> format_rows(size_t n, size_t bytes_per_row_hint, Row row) {
   unsigned threads = std::thread::hardware_concurrency();
   if (const char *e = std::getenv("PCP_WRITER_THREADS")) threads = static_cast<unsigned>(std::max(1, std::atoi(e)));
   threads = std::max(1u, std::min(threads, 32u));
@@ -301,6 +297,17 @@ inline int write_rows(const std::string &path, const std::string &head, size_t n
   for (unsigned t = 1; t < threads; ++t) pool.emplace_back(work, t);
   work(0);
   for (auto &th : pool) th.join();
+  return part;
+}
+inline const char *empty_cloud_message() { return ": [pcl::PCDWriter::writeASCII] Input point cloud has no data!"; }
+// header + the formatted rows
+template <class Row>
+inline int write_rows(const std::string &path, const std::string &head, size_t n, size_t bytes_per_row_hint, Row row) {
+  // pcl::PCDWriter::writeASCII (PCL 1.10 pcd_io.hpp) throws pcl::IOException on an empty cloud before touching the
+  // file; PCLException's what() is ": <description>" when no file / function / line is attached.  The reference's
+  // main catches it and exits with -2 (main.cpp:64-68) -- e.g. a keyframe whose mask image is missing.
+  if (n == 0) throw std::runtime_error(empty_cloud_message());
+  const std::vector<std::string> part = format_rows(n, bytes_per_row_hint, row);
   std::ofstream out(path, std::ios::binary);
   if (!out) return -1;
   out.write(head.data(), static_cast<std::streamsize>(head.size()));
@@ -388,5 +395,117 @@ inline int writeASCII_PointNormal(const std::string &path, const float *xyz, con
                               s += '\n';
                             });
 }
+
+// The same files written chunk by chunk (a cloud that never sits in host memory as a whole): the bytes are those of the
+// one-shot writers above.  The header carries the number of rows, so either the caller knows it up front (`known_rows`: the
+// header goes out first, finish() checks the count) or the rows go to a temporary file beside the output and finish()
+// assembles header + body (no padded header).  An empty file is the one-shot writers' exception, raised by finish().
+class ChunkedAsciiWriter {
+ public:
+  enum Kind { XYZRGB, XYZRGBMask, PointNormal };
+  ChunkedAsciiWriter(const std::string &path, Kind kind, int64_t known_rows = -1)
+      : path_(path), body_path_(known_rows >= 0 ? path : path + ".body.tmp"), kind_(kind), known_(known_rows) {
+    if (known_rows == 0) return;  // (finish() throws before any file is touched, as the one-shot writers do)
+    out_.open(body_path_, std::ios::binary);
+    if (!out_) throw std::runtime_error("Couldn't open " + body_path_);
+    if (known_rows > 0) {
+      const std::string h = head(static_cast<size_t>(known_rows));
+      out_.write(h.data(), static_cast<std::streamsize>(h.size()));
+    }
+  }
+  ~ChunkedAsciiWriter() {
+    if (!done_ && known_ < 0) {  // abandoned (an exception on the way): no temporary left behind
+      out_.close();
+      std::remove(body_path_.c_str());
+    }
+  }
+  ChunkedAsciiWriter(const ChunkedAsciiWriter &) = delete;
+  ChunkedAsciiWriter &operator=(const ChunkedAsciiWriter &) = delete;
+  size_t rows() const { return rows_; }
+
+  // xyz 3 per row; XYZRGB: rgb 3 per row; XYZRGBMask: rgb and label (the segmentMask column) per row
+  void appendColoured(const float *xyz, const uint8_t *rgb, const uint8_t *label, size_t n) {
+    const bool mask = kind_ == XYZRGBMask;
+    write(detail::format_rows(n, mask ? 56 : 48, [=](std::string &s, size_t i) {
+            for (int c = 0; c < 3; ++c) {
+              detail::put_float(s, xyz[3 * i + static_cast<size_t>(c)]);
+              s += ' ';
+            }
+            detail::put_rgb(s, rgb + 3 * i);
+            if (mask) {
+              s += ' ';
+              detail::put_uint(s, label[i]);
+            }
+            s += '\n';
+          }),
+          n);
+  }
+  void appendPointNormal(const float *xyz, const float *normal, const float *curv, size_t n) {
+    write(detail::format_rows(n, 96, [=](std::string &s, size_t i) {
+            for (int c = 0; c < 3; ++c) {
+              detail::put_float(s, xyz[3 * i + static_cast<size_t>(c)]);
+              s += ' ';
+            }
+            for (int c = 0; c < 3; ++c) {
+              detail::put_float(s, normal[3 * i + static_cast<size_t>(c)]);
+              s += ' ';
+            }
+            detail::put_float(s, curv[i]);
+            s += '\n';
+          }),
+          n);
+  }
+  // 0, or -1 when the file could not be written
+  int finish() {
+    done_ = true;
+    if (known_ >= 0) {
+      if (known_ == 0) throw std::runtime_error(detail::empty_cloud_message());
+      out_.close();
+      if (static_cast<int64_t>(rows_) != known_) throw std::runtime_error(path_ + ": " + std::to_string(rows_) + " rows written, " + std::to_string(known_) + " announced");
+      return out_ ? 0 : -1;
+    }
+    out_.close();
+    if (rows_ == 0) {
+      std::remove(body_path_.c_str());
+      throw std::runtime_error(detail::empty_cloud_message());
+    }
+    int rc = -1;
+    {
+      std::ofstream dst(path_, std::ios::binary);
+      std::ifstream src(body_path_, std::ios::binary);
+      if (dst && src && out_) {
+        const std::string h = head(rows_);
+        dst.write(h.data(), static_cast<std::streamsize>(h.size()));
+        std::vector<char> buf(size_t(8) << 20);
+        while (src) {
+          src.read(buf.data(), static_cast<std::streamsize>(buf.size()));
+          dst.write(buf.data(), src.gcount());
+        }
+        rc = dst ? 0 : -1;
+      }
+    }
+    std::remove(body_path_.c_str());
+    return rc;
+  }
+
+ private:
+  std::string head(size_t n) const {
+    switch (kind_) {
+      case XYZRGB: return detail::header("x y z rgb", "4 4 4 4", "F F F U", "1 1 1 1", n);
+      case XYZRGBMask: return detail::header("x y z rgb segmentMask", "4 4 4 4 2", "F F F U U", "1 1 1 1 1", n);
+      default: return detail::header("x y z normal_x normal_y normal_z curvature", "4 4 4 4 4 4 4", "F F F F F F F", "1 1 1 1 1 1 1", n);
+    }
+  }
+  void write(const std::vector<std::string> &part, size_t n) {
+    for (const auto &s : part) out_.write(s.data(), static_cast<std::streamsize>(s.size()));
+    rows_ += n;
+  }
+  std::string path_, body_path_;
+  Kind kind_;
+  int64_t known_;
+  std::ofstream out_;
+  size_t rows_ = 0;
+  bool done_ = false;
+};
 
 }  // namespace pcp_amd

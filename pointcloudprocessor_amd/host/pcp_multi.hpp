@@ -682,9 +682,12 @@ class MultiCloudSmooth {
         voxels = total;
       }
       // The upsampled cloud goes through the host here and back onto every GPU for the last filter: fine up to what one upload
-      // holds.  Beyond that (the reference's 1 mm x 4 on a 10 M-point map makes 2.8e9 rows: 90 GB of host memory, more rows than
-      // a cloud has indices) the whole chain runs in its streamed form on the first GPU -- the same rows, one GPU's 2.7 s
-      // (pcp_cloud_smooth_stream_*; its chunks over several GPUs: DESIGN.md section 8).  PCP_MULTI_STREAM_ABOVE: another limit (tests).
+      // holds.  Beyond that the whole chain runs in its streamed form on the first GPU -- the same rows, one GPU's 2.7 s
+      // (pcp_cloud_smooth_stream_*; its chunks over several GPUs: DESIGN.md section 8) -- which lifts the limit of the SMOOTHING
+      // only: this call still gathers the kept rows into one cloud for the colour stage, whose upload takes fewer than 2^31
+      // points.  The reference's 1 mm x 4 on a 10 M-point map keeps 2.4e9 rows (90 GB of host memory, more rows than a cloud has
+      // indices): the call then ends with an error before the first chunk is fetched, and such a map is coloured chunk by chunk
+      // instead (CloudSmooth::processAndColorizeStreamed, --streamColour 1).  PCP_MULTI_STREAM_ABOVE: another limit (tests).
       int64_t stream_above = int64_t(1) << 30;
       if (const char *e = std::getenv("PCP_MULTI_STREAM_ABOVE")) stream_above = std::max<long long>(1, std::atoll(e));
       if (voxels > stream_above) {
@@ -695,7 +698,7 @@ class MultiCloudSmooth {
           all.normal.insert(all.normal.end(), c.normal.begin(), c.normal.end());
           all.curvature.insert(all.curvature.end(), c.curvature.begin(), c.curvature.end());
           all.index.insert(all.index.end(), c.index.begin(), c.index.end());
-        });
+        }, nullptr, false, kMaxUploadPoints);
         return all;
       }
       for (int32_t c = 0; c < chunks; ++c) {

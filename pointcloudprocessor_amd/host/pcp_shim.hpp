@@ -15,6 +15,7 @@
 #pragma once
 
 #include <algorithm>
+#include <chrono>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -213,6 +214,21 @@ struct SmoothedCloud {  // pcl::PointCloud<pcl::PointNormal> mls_points + corres
   std::vector<int32_t> index;
 };
 
+// One chunk of CloudSmooth::processAndColorizeStreamed: the rows that received a colour (removePointsWithNoColor done)
+struct ColouredChunk {
+  std::vector<int32_t> index;  // source index the smoothing chain reports (the uploaded, unsmoothed cloud)
+  std::vector<float> xyz;      // 3 per row: the smoothed point
+  std::vector<uint8_t> rgb;    // 3 per row
+  std::vector<uint8_t> label;  // fused label per row (label fusion on), else empty
+};
+struct StreamedColourStats {
+  int32_t chunks = 0;
+  int64_t rows = 0, coloured = 0;            // smoothed rows, rows with a colour
+  double sweep_a_s = 0.0, sweep_b_s = 0.0;  // host-clock seconds, the sinks included
+};
+// the largest cloud one upload takes (pcp_upload_cloud*: n < 2^31)
+constexpr int64_t kMaxUploadPoints = (int64_t(1) << 31) - 1;
+
 class CloudSmooth {
  public:
   explicit CloudSmooth(Device &dev) : dev_(dev) { pcp_default_mls_params(&params_); }
@@ -235,13 +251,22 @@ class CloudSmooth {
   // Returns the rows kept.
   // hold_device_memory: leave the stream's distances on the device (4 B per row: 11 GB for a 10 M-point map) for the next call
   // instead of freeing them (pcp_cloud_smooth_stream_end).
+  // max_rows: a caller that gathers the chunks into ONE cloud for a later upload passes kMaxUploadPoints: more kept rows
+  // than that end the call before the first chunk is fetched (the colour stage could not take them; processAndColorizeStreamed
+  // -- `--streamColour 1` on the command line -- colours such a cloud chunk by chunk).
   template <class Sink>
   int64_t processWithOutlierRemovalStreamed(int64_t chunk_capacity, Sink &&sink, int64_t *total_rows = nullptr,
-                                            bool hold_device_memory = false) const {
+                                            bool hold_device_memory = false, int64_t max_rows = -1) const {
     int64_t total = 0, kept = 0;
     int32_t chunks = 0;
     dev_.check(pcp_cloud_smooth_stream_begin(dev_.get(), &params_, chunk_capacity, &total, &kept, &chunks));
     if (total_rows) *total_rows = total;
+    if (max_rows >= 0 && kept > max_rows) {
+      dev_.check(pcp_cloud_smooth_stream_end(dev_.get()));
+      throw std::runtime_error("pcp_hip: the smoothed cloud has " + std::to_string(kept) + " rows, more than one upload takes (" +
+                               std::to_string(max_rows) + "): it cannot be gathered for the colour stage; colour it chunk by chunk "
+                               "(CloudSmooth::processAndColorizeStreamed, --streamColour 1 on the command line)");
+    }
     SmoothedCloud s;
     for (;;) {
       int64_t m = 0;
@@ -252,6 +277,86 @@ class CloudSmooth {
     }
     if (!hold_device_memory) dev_.check(pcp_cloud_smooth_stream_end(dev_.get()));
     return kept;
+  }
+
+  // CloudSmooth::process followed by the colourisation of the smoothed cloud (PointCloudProcessor.cpp:139-145, 474-602) for
+  // clouds whose smoothed rows exceed one upload -- nothing of the smoothed cloud is gathered on the host.  A chunk of the
+  // chain's voxel order is an index shard in time: the depth maps are a MIN over all points and a point's colour depends only
+  // on its own projection, the merged maps and the images, so the chunks' results concatenate to the one-shot result bit for
+  // bit (DESIGN.md "Streamed colourisation").  This object's device holds the cloud to smooth; `colour` is a second context
+  // on the same GPU with camera, keyframes and images (masks and pcp_set_label_fusion for labels) set.  Every chunk reaches
+  // it device to device (pcp_upload_cloud_from_result).
+  //   sweep A  per chunk: depth pass over all keyframes, merged into colour's accumulator; smoothed(chunk, kept_rows) receives
+  //            the chunk's rows -- the <stem>_mls.pcd rows as they come; kept_rows, their total, is known from the start;
+  //   sweep B  the stream rewound: depth pass (tile masks), the accumulator applied, colours, compaction on the device;
+  //            sink(const ColouredChunk &) receives every chunk's coloured rows.
+  template <class Sink, class SmoothedSink>
+  StreamedColourStats processAndColorizeStreamed(Device &colour, int64_t chunk_capacity, Sink &&sink, SmoothedSink &&smoothed,
+                                                 bool fuse_labels = false) const {
+    using clock = std::chrono::steady_clock;
+    pcp_context *src = dev_.get(), *dst = colour.get();
+    StreamedColourStats st;
+    int64_t total = 0, kept = 0;
+    int32_t frames = pcp_frame_count(dst);
+    dev_.check(pcp_set_mls_local_plane(src, slp_radius_, slp_step_));
+    colour.check(pcp_depth_accum_reset(dst));
+    dev_.check(pcp_cloud_smooth_stream_begin(src, &params_, chunk_capacity, &total, &kept, &st.chunks));
+    struct EndStream {  // also on the way out of an exception
+      pcp_context *c;
+      ~EndStream() { (void)pcp_cloud_smooth_stream_end(c); }
+    } end_stream{src};
+    auto t0 = clock::now();
+    SmoothedCloud s;
+    for (int32_t c = 0; c < st.chunks; ++c) {  // (chunks without rows are skipped by _next: the calls left over return 0)
+      int64_t m = 0, n = 0;
+      dev_.check(pcp_cloud_smooth_stream_next(src, &m));
+      if (m == 0) continue;
+      st.rows += m;
+      colour.check(pcp_upload_cloud_from_result(dst, src, &n));
+      colour.check(pcp_depth_pass(dst, 0, frames));
+      colour.check(pcp_depth_accum_merge(dst));
+      fetch(m, s);
+      smoothed(static_cast<const SmoothedCloud &>(s), kept);
+    }
+    colour.check(pcp_synchronize(dst));
+    st.sweep_a_s = std::chrono::duration<double>(clock::now() - t0).count();
+    t0 = clock::now();
+    dev_.check(pcp_cloud_smooth_stream_seek(src, 0));
+    ColouredChunk out;
+    std::vector<int32_t> source;
+    for (int32_t c = 0; c < st.chunks; ++c) {
+      int64_t m = 0, n = 0, coloured = 0;
+      dev_.check(pcp_cloud_smooth_stream_next(src, &m));
+      if (m == 0) continue;
+      colour.check(pcp_upload_cloud_from_result(dst, src, &n));
+      colour.check(pcp_depth_pass(dst, 0, frames));  // builds this chunk's tile masks, as on a shard before the all-reduce(MIN)
+      colour.check(pcp_depth_accum_apply(dst));
+      colour.check(pcp_colorize_from_depth(dst, nullptr, nullptr));
+      const size_t sm = static_cast<size_t>(m);
+      out.index.resize(sm);
+      out.xyz.resize(3 * sm);
+      out.rgb.resize(3 * sm);
+      out.label.resize(fuse_labels ? sm : 0);
+      colour.check(pcp_colour_compact(dst, m, out.index.data(), out.xyz.data(), out.rgb.data(), fuse_labels ? out.label.data() : nullptr,
+                                      &coloured));
+      const size_t sc = static_cast<size_t>(coloured);
+      out.index.resize(sc);
+      out.xyz.resize(3 * sc);
+      out.rgb.resize(3 * sc);
+      out.label.resize(fuse_labels ? sc : 0);
+      st.coloured += coloured;
+      if (coloured == 0) continue;
+      source.resize(sm);
+      dev_.check(pcp_mls_fetch(src, m, nullptr, nullptr, nullptr, source.data()));
+      for (size_t k = 0; k < sc; ++k) out.index[k] = source[static_cast<size_t>(out.index[k])];
+      sink(static_cast<const ColouredChunk &>(out));
+    }
+    st.sweep_b_s = std::chrono::duration<double>(clock::now() - t0).count();
+    return st;
+  }
+  template <class Sink>
+  StreamedColourStats processAndColorizeStreamed(Device &colour, int64_t chunk_capacity, Sink &&sink) const {
+    return processAndColorizeStreamed(colour, chunk_capacity, sink, [](const SmoothedCloud &, int64_t) {});
   }
 
  private:
@@ -270,12 +375,13 @@ class CloudSmooth {
     if (with_sor && rc == PCP_ERR_NOMEM && params_.upsampling == PCP_UPSAMPLING_VOXEL_GRID_DILATION) {
       // more upsampled points than one result holds: the streamed chain, gathered on the host (the caller asked for one cloud)
       SmoothedCloud all;
+      // (as long as the colour stage can take the one cloud: beyond an upload's size the call ends here, before 90 GB are gathered)
       processWithOutlierRemovalStreamed(int64_t(1) << 28, [&](const SmoothedCloud &c) {
         all.xyz.insert(all.xyz.end(), c.xyz.begin(), c.xyz.end());
         all.normal.insert(all.normal.end(), c.normal.begin(), c.normal.end());
         all.curvature.insert(all.curvature.end(), c.curvature.begin(), c.curvature.end());
         all.index.insert(all.index.end(), c.index.begin(), c.index.end());
-      });
+      }, nullptr, false, kMaxUploadPoints);
       return all;
     }
     dev_.check(rc);

@@ -20,6 +20,9 @@ import numpy as np
 from . import capi
 
 
+MAX_UPLOAD_POINTS = (1 << 31) - 1  # pcp_upload_cloud*: n < 2^31
+
+
 def shard_bounds(n: int, rank: int, world: int):
     """Contiguous index range of `rank` (first n % world ranks get one extra point)."""
     base, rem = divmod(n, world)
@@ -491,20 +494,27 @@ class CloudSmooth:
         except capi.PcpError as e:
             if e.code != capi.PCP_ERR_NOMEM or self.params.upsampling != 3:
                 raise
-        parts = list(self.process_streamed(1 << 28))
+        # (one cloud is what the caller asked for: fine as long as a later upload can take it)
+        parts = list(self.process_streamed(1 << 28, max_rows=MAX_UPLOAD_POINTS))
         if not parts:
             return ctx.mls_fetch(0)
         import numpy as np
 
         return {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
 
-    def process_streamed(self, chunk_capacity: int = 1 << 28, hold_device_memory: bool = False):
+    def process_streamed(self, chunk_capacity: int = 1 << 28, hold_device_memory: bool = False, max_rows: int | None = None):
         """The whole CloudSmooth::process through pcp_cloud_smooth_stream_*: yields the survivors of the trailing outlier removal
         chunk by chunk (dicts as mls_fetch returns them), in the order the one-shot form returns them; `self.streamed` holds
-        (rows before the last filter, rows kept, chunks) and the stream's diagnostics."""
+        (rows before the last filter, rows kept, chunks) and the stream's diagnostics.  max_rows: a caller that gathers the
+        chunks into one cloud passes the most it can use; more kept rows raise before the first chunk is fetched."""
         ctx = self.engine.ctx
         total, kept, chunks = ctx.cloud_smooth_stream_begin(self.params, chunk_capacity)
         self.streamed = {"rows": total, "kept": kept, "chunks": chunks, **ctx.cloud_smooth_stream_stats()}
+        if max_rows is not None and kept > max_rows:
+            ctx.cloud_smooth_stream_end()
+            raise ValueError(f"the smoothed cloud has {kept} rows, more than one upload takes ({max_rows}): it cannot be gathered "
+                             "for the colour stage; colour it chunk by chunk (process_and_colourise_streamed, --streamColour 1 on "
+                             "the command line)")
         try:
             while True:
                 m = ctx.cloud_smooth_stream_next()
@@ -514,3 +524,66 @@ class CloudSmooth:
         finally:
             if not hold_device_memory:
                 ctx.cloud_smooth_stream_end()
+
+    def process_and_colourise_streamed(self, colour_engine: HipEngine, chunk_capacity: int = 1 << 28, fuse_labels: bool = False,
+                                       on_smoothed=None, download: bool = True):
+        """CloudSmooth::process followed by the colourisation of the smoothed cloud (PointCloudProcessor.cpp:139-145, 474-602)
+        for clouds whose smoothed rows exceed one upload: the mirror of the C++ shim's processAndColorizeStreamed.  A chunk of
+        the chain's voxel order is an index shard in time -- the depth maps are a MIN over all points and a point's colour
+        depends only on its own projection, the merged maps and the images -- so the chunks' results concatenate to the
+        one-shot result bit for bit ("Streamed colourisation").
+
+        `colour_engine`: a second HipEngine on the same GPU with camera, keyframes and images (masks for fuse_labels) set;
+        every chunk reaches it device to device (pcp_upload_cloud_from_result).
+          sweep A  every chunk: depth pass over all keyframes, merged into the accumulator; on_smoothed(rows) -- the dict
+                   mls_fetch returns -- is called per chunk when given (the <stem>_mls.pcd rows);
+          sweep B  the stream rewound: depth pass (tile masks), the accumulator applied, colours, compaction on the device.
+        Yields one dict per chunk with a coloured row: index (the source index the chain reports), xyz, rgb and, with
+        fuse_labels, label.  download=False: the rows stay on the device and every dict holds only `count`, the chunk's
+        coloured rows (what the device work alone costs).  `self.streamed_colour` holds chunks, rows, coloured and the seconds
+        of both sweeps."""
+        import time
+
+        ctx, col = self.engine.ctx, colour_engine.ctx
+        self._apply_local_plane()
+        col.set_label_fusion(fuse_labels)
+        col.depth_accum_reset()
+        total, kept, chunks = ctx.cloud_smooth_stream_begin(self.params, chunk_capacity)
+        self.streamed = {"rows": total, "kept": kept, "chunks": chunks, **ctx.cloud_smooth_stream_stats()}
+        stats = self.streamed_colour = {"chunks": chunks, "rows": 0, "coloured": 0, "sweep_a_s": 0.0, "sweep_b_s": 0.0}
+        try:
+            t0 = time.perf_counter()
+            for _ in range(chunks):  # (chunks without rows are skipped by _next: the calls left over return 0)
+                m = ctx.cloud_smooth_stream_next()
+                if m == 0:
+                    continue
+                stats["rows"] += m
+                col.upload_cloud_from_result(ctx)
+                col.depth_pass()
+                col.depth_accum_merge()
+                if on_smoothed is not None:
+                    on_smoothed(ctx.mls_fetch(m))
+            col.synchronize()
+            stats["sweep_a_s"] = time.perf_counter() - t0
+            t0 = time.perf_counter()
+            ctx.cloud_smooth_stream_seek(0)
+            for _ in range(chunks):
+                m = ctx.cloud_smooth_stream_next()
+                if m == 0:
+                    continue
+                col.upload_cloud_from_result(ctx)
+                col.depth_pass()  # builds this chunk's tile masks, as on a shard before the all-reduce(MIN)
+                col.depth_accum_apply()
+                col.colorize_from_depth(download=False)
+                out = col.colour_compact(capacity=None if download else 0, want_label=fuse_labels and download)
+                count = out.pop("count")
+                stats["coloured"] += count
+                stats["sweep_b_s"] = time.perf_counter() - t0
+                if count and not download:
+                    yield {"count": count}
+                elif count:
+                    out["index"] = ctx.mls_fetch_index(m)[out["index"]]
+                    yield out
+            stats["sweep_b_s"] = time.perf_counter() - t0
+        finally:
+            ctx.cloud_smooth_stream_end()
