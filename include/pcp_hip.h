@@ -51,7 +51,9 @@ extern "C" {
                                 pcp_colour_labels_device (fused segmentation labels; off by default);
                                 entry points added, no layout changed: pcp_upload_cloud_from_result, pcp_depth_accum_reset / _merge /
                                 _apply / _device, pcp_cloud_smooth_stream_seek, pcp_colour_compact (streamed colourisation: a
-                                smoothed cloud larger than one upload coloured chunk by chunk; nothing runs unless called) */
+                                smoothed cloud larger than one upload coloured chunk by chunk; nothing runs unless called);
+                                entry points added, no layout changed: pcp_ascii_row_bound, pcp_ascii_rows_host, pcp_ascii_rows,
+                                pcp_colour_compact_ascii, pcp_mls_fetch_ascii (the device PCD writer; nothing runs unless called) */
 
 #define PCP_OK 0
 #define PCP_ERR_INVALID (-1) /* bad argument */
@@ -589,7 +591,46 @@ typedef int (*pcp_nid_eval_fn)(void *user, const double T[16], int32_t bins, dou
 int pcp_nid_optimize_with(pcp_context *ctx, pcp_nid_eval_fn eval, void *user, const double T_init[16], int32_t bins,
                           int32_t max_outer_iterations, double T_out[16], double *final_cost, int32_t *evaluations);
 
-/* ---- precondition of the match-back (PointCloudProcessor.cpp:480-482,571) ------------------------------- */
+/* ---- device PCD writer (pcl::PCDWriter::writeASCII, every file the program hands out) --------------------- */
+/* The rows of the ASCII PCD files as text, formatted on the device and downloaded as the bytes that follow the header
+ * ("Device PCD writer"): floats as "%.8g" of the fp32 (ostream precision 8; every NaN prints "nan"), the rgb
+ * column as the packed word 0xff000000 | r<<16 | g<<8 | b and segmentMask as "%u", single spaces, one '\n' per row --
+ * byte for byte what host/pcd_io.hpp's writeASCII_* print.  Opt-in: nothing runs unless one of these is called; a caller
+ * detects support by the symbols (PCP_ABI_VERSION is unchanged). */
+#define PCP_ROWS_XYZI 0        /* x y z intensity                  savePCDFileASCII :135 (scans-crop.pcd), writeASCII :217 (_beforeNID.pcd) */
+#define PCP_ROWS_XYZRGB 1      /* x y z rgb                        writeASCII :920 (cloudInWorldWithRGB.pcd) */
+#define PCP_ROWS_XYZRGBMASK 2  /* x y z rgb segmentMask            writeASCII :542 (_rgb-mask.pcd), :936-954 (cloudInWorldWithRGBandMask.pcd) */
+#define PCP_ROWS_POINTNORMAL 3 /* x y z nx ny nz curvature         pcl::io::savePCDFile, cloudSmooth.cpp:180-181 (<stem>_mls.pcd) */
+/* longest row of a kind in bytes, newline included (60 / 56 / 62 / 105); <0 for an unknown kind.  Host only. */
+int64_t pcp_ascii_row_bound(int32_t kind);
+/* Host only, no context, no GPU: the formatter the kernels use (csrc/pcp_ascii.hpp), run on the CPU -- the way to check it
+ * on every bit pattern.  n rows: f row-major with 4 | 3 | 3 | 7 floats per row (kind order above), rgb 3 bytes per row
+ * (r, g, b; the RGB kinds), mask one uint16 per row (XYZRGBMASK); arrays a kind does not read may be NULL.
+ * *out_bytes (nullable) = the exact byte count of the n rows, always.  capacity below it: PCP_ERR_RANGE and out_text is
+ * left untouched (size the buffer as n * pcp_ascii_row_bound(kind), or call again with the reported count).  Negative n
+ * or capacity, an unknown kind, a missing array: PCP_ERR_INVALID.  n == 0: 0 bytes, PCP_OK.  The message of a failure is
+ * at pcp_last_error(NULL). */
+int pcp_ascii_rows_host(int32_t kind, int64_t n, const float *f, const uint8_t *rgb, const uint16_t *mask, int64_t capacity,
+                        char *out_text, int64_t *out_bytes);
+/* The same rows formatted on the device from host arrays (the sites that hold their rows on the host: scans-crop.pcd :135,
+ * the per-keyframe dumps :217 and :542).  Same arguments and rules; out_text is host memory, pageable or pinned, and is not
+ * retained.  Synchronous. */
+int pcp_ascii_rows(pcp_context *ctx, int32_t kind, int64_t n, const float *f, const uint8_t *rgb, const uint16_t *mask,
+                   int64_t capacity, char *out_text, int64_t *out_bytes);
+/* Rows [first_row, first_row + max_rows) of what pcp_colour_compact would return -- removePointsWithNoColor's survivors
+ * (:598), the final files :917-920 / :936-954 -- as XYZRGB text, or XYZRGBMASK text with the fused label as segmentMask
+ * (with_label != 0).  The kernels read the compaction's index list, the uploaded planes, the packed colour word and the
+ * labels in place; no binary row is materialised.  *out_rows = rows in the window (0 past the end), *out_bytes = their exact
+ * byte count; capacity rules as above.  No colour result, or with_label on a result made without label fusion:
+ * PCP_ERR_STATE.  Negative first_row / max_rows / capacity: PCP_ERR_INVALID.  Every call takes the compaction again. */
+int pcp_colour_compact_ascii(pcp_context *ctx, int32_t with_label, int64_t first_row, int64_t max_rows, int64_t capacity,
+                             char *out_text, int64_t *out_rows, int64_t *out_bytes);
+/* Rows [first_row, first_row + max_rows) of what pcp_mls_fetch would return (xyz, normal, curvature of the latest smoothing
+ * result or stream chunk), as POINTNORMAL text (<stem>_mls.pcd, cloudSmooth.cpp:180-181).  Same rules. */
+int pcp_mls_fetch_ascii(pcp_context *ctx, int64_t first_row, int64_t max_rows, int64_t capacity, char *out_text,
+                        int64_t *out_rows, int64_t *out_bytes);
+
+/* ---- precondition of the match-back(PointCloudProcessor.cpp:480-482,571) ------------------------------- */
 /* Number of map points that have ANOTHER map point closer than `radius` (fp32 squared distance, strict <, as
  * kdtree.radiusSearch compares).  The reference credits a visible sample to every map point within 1e-5 m of the
  * sample's fp32 world position; PCP_MATCH_ROUNDTRIP / _IDENTITY credit the sample's own point only, PCP_MATCH_RADIUS

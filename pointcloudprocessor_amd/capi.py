@@ -155,6 +155,58 @@ def mls_local_plane_samples(radius: float, step: float):
     return u, v
 
 
+# row kinds of the device PCD writer (pcp_ascii_rows*)
+ROWS_XYZI, ROWS_XYZRGB, ROWS_XYZRGBMASK, ROWS_POINTNORMAL = 0, 1, 2, 3
+_ROW_FLOATS = {ROWS_XYZI: 4, ROWS_XYZRGB: 3, ROWS_XYZRGBMASK: 3, ROWS_POINTNORMAL: 7}
+
+
+def ascii_row_bound(kind: int) -> int:
+    """Longest row of a kind in bytes, newline included; negative for an unknown kind (pcp_ascii_row_bound)."""
+    L = load()
+    L.pcp_ascii_row_bound.restype = C.c_int64
+    return int(L.pcp_ascii_row_bound(C.c_int32(kind)))
+
+
+def _ascii_rows_args(kind: int, f, rgb, mask):
+    nf = _ROW_FLOATS.get(kind, 1)
+    f = np.ascontiguousarray(f, np.float32).reshape(-1, nf)
+    rgb = None if rgb is None else np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)
+    mask = None if mask is None else np.ascontiguousarray(mask, np.uint16).reshape(-1)
+    return f, rgb, mask
+
+
+def _ascii_rows_call(fn, check, kind, f, rgb, mask, capacity, out):
+    """Shared by the host and device forms: returns the text as a numpy.uint8 array.  capacity None sizes the buffer by the
+    row bound; out: a caller's uint8 buffer to fill instead (its size is the capacity).  A failure raises PcpError whose
+    `bytes` is the exact byte count the call reported."""
+    f, rgb, mask = _ascii_rows_args(kind, f, rgb, mask)
+    n = f.shape[0]
+    if out is None:
+        cap = max(0, n * ascii_row_bound(kind)) if capacity is None else capacity
+        out = np.empty(max(cap, 0), np.uint8)
+    else:
+        cap = out.size if capacity is None else capacity
+    nbytes = C.c_int64(-1)
+    try:
+        check(fn(C.c_int32(kind), C.c_int64(n), _ptr(f), _ptr(rgb), _ptr(mask), C.c_int64(cap), _ptr(out), C.byref(nbytes)))
+    except PcpError as e:
+        e.bytes = nbytes.value
+        raise
+    return out[: nbytes.value]
+
+
+def ascii_rows_host(kind: int, f, rgb=None, mask=None, capacity: int | None = None, out=None) -> np.ndarray:
+    """PCD ASCII rows formatted on the CPU by the formatter the kernels use (pcp_ascii_rows_host: no context, no GPU).
+    f: n rows of 4 | 3 | 3 | 7 floats, rgb n x 3 bytes, mask n uint16."""
+    L = load()
+
+    def check(rc):
+        if rc != PCP_OK:
+            raise PcpError(rc, L.pcp_last_error(None).decode())
+
+    return _ascii_rows_call(L.pcp_ascii_rows_host, check, kind, f, rgb, mask, capacity, out)
+
+
 def default_camera() -> Camera:
     cam = Camera()
     load().pcp_default_camera(C.byref(cam))
@@ -447,6 +499,40 @@ class Context:
         if want_label:
             out["label"] = label[:m]
         return out
+
+    # -- device PCD writer ---------------------------------------------------
+    def ascii_rows(self, kind: int, f, rgb=None, mask=None, capacity: int | None = None, out=None) -> np.ndarray:
+        """ascii_rows_host's rows formatted on the device (pcp_ascii_rows): the text as a numpy.uint8 array."""
+        fn = lambda *a: self.lib.pcp_ascii_rows(self.h, *a)  # noqa: E731
+        return _ascii_rows_call(fn, self._check, kind, f, rgb, mask, capacity, out)
+
+    def _ascii_window(self, call, bound: int, total_rows: int, first_row: int, max_rows: int | None, capacity: int | None):
+        if max_rows is None:
+            max_rows = max(0, total_rows - first_row)
+        cap = max(0, min(max_rows, max(0, total_rows - first_row))) * bound if capacity is None else capacity
+        out = np.empty(max(cap, 0), np.uint8)
+        rows = C.c_int64(-1)
+        nbytes = C.c_int64(-1)
+        try:
+            self._check(call(C.c_int64(first_row), C.c_int64(max_rows), C.c_int64(cap), _ptr(out), C.byref(rows), C.byref(nbytes)))
+        except PcpError as e:
+            e.bytes = nbytes.value
+            raise
+        return out[: nbytes.value], rows.value
+
+    def colour_compact_ascii(self, with_label: bool = False, first_row: int = 0, max_rows: int | None = None,
+                             capacity: int | None = None):
+        """(text, rows): rows [first_row, first_row + max_rows) of colour_compact() as XYZRGB text, or XYZRGBMASK text with
+        the fused label (pcp_colour_compact_ascii); max_rows None = to the end."""
+        kind = ROWS_XYZRGBMASK if with_label else ROWS_XYZRGB
+        call = lambda *a: self.lib.pcp_colour_compact_ascii(self.h, C.c_int32(1 if with_label else 0), *a)  # noqa: E731
+        return self._ascii_window(call, ascii_row_bound(kind), self.n, first_row, max_rows, capacity)
+
+    def mls_fetch_ascii(self, count: int, first_row: int = 0, max_rows: int | None = None, capacity: int | None = None):
+        """(text, rows): rows [first_row, first_row + max_rows) of mls_fetch(count) as PointNormal text
+        (pcp_mls_fetch_ascii); count = the rows of the latest smoothing result."""
+        call = lambda *a: self.lib.pcp_mls_fetch_ascii(self.h, *a)  # noqa: E731
+        return self._ascii_window(call, ascii_row_bound(ROWS_POINTNORMAL), count, first_row, max_rows, capacity)
 
     def colour_reset(self):
         self._check(self.lib.pcp_colour_reset(self.h))

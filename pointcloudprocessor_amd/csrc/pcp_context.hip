@@ -618,7 +618,7 @@ int pcp_create(int32_t device, pcp_context **out) {
     hipFuncAttributes a;
     const hipError_t pl[] = {hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_up_bbox)), preload_colour(), preload_mls(),
                              preload_nid(), preload_hpr(), preload_colour_smooth(), preload_match(),
-                             preload_jpeg(), preload_stream_colour()};
+                             preload_jpeg(), preload_stream_colour(), preload_ascii()};
     for (hipError_t x : pl)
       if (x != hipSuccess && e == hipSuccess) e = x;
   }
@@ -693,6 +693,10 @@ void pcp_destroy(pcp_context *ctx) {
   ctx->depth.release();
   ctx->depth_accum.release();
   ctx->cc_out.release();
+  ctx->ascii_in.release();
+  ctx->ascii_len.release();
+  ctx->ascii_text.release();
+  ctx->ascii_tiles.release();
   if (ctx->handoff) (void)hipEventDestroy(ctx->handoff);
   ctx->depth_sq.release();
   ctx->tile_sphere.release();

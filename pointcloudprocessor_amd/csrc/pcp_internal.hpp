@@ -315,6 +315,10 @@ struct pcp_context {
   bool mls_result_live = false;  // a smoothing call has left mls_count rows (0 included) since the latest upload
   hipEvent_t handoff = nullptr;  // pcp_upload_cloud_from_result: recorded on this (source) context's stream
   pcp::DevBuf<uint8_t> cc_out;   // pcp_colour_compact: the gathered rows (xyz | rgb | label) before they leave the device
+  // device PCD writer (pcp_ascii.hip): host rows uploaded by pcp_ascii_rows, a length per row, the 64-bit prefix of the tiles'
+  // bytes (+ the window edges), one window of text
+  pcp::DevBuf<uint8_t> ascii_in, ascii_len, ascii_text;
+  pcp::DevBuf<unsigned long long> ascii_tiles;
   // pcp_mls_stream_*: the plan of a chunked VOXEL_GRID_DILATION emission (pcp_mls.hip VgdStream; word0, word1, count per chunk)
   std::vector<uint8_t> vgd_blob;
   std::vector<int64_t> vgd_chunks;
@@ -476,6 +480,11 @@ void match_table_release(pcp_context *ctx);
 hipError_t preload_match();
 hipError_t preload_jpeg();
 hipError_t preload_stream_colour();
+hipError_t preload_ascii();
+
+// removePointsWithNoColor's index list (pcp_stream_colour.hip): the rows of the current colour result whose has bit is set,
+// input order, into ctx->s_cell; *m = their number.  ctx->n > 0 and a live colour result are the caller's to check.
+int colour_compact_indices(pcp_context *ctx, int64_t *m);
 
 inline int64_t div_up(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

@@ -102,6 +102,20 @@ static int maps_current(pcp_context *ctx, const char *who) {
   return PCP_OK;
 }
 
+int colour_compact_indices(pcp_context *ctx, int64_t *m) {
+  const int64_t n = ctx->n;
+  const size_t sn = static_cast<size_t>(n);
+  const uint32_t *packed = ctx->rgba2[ctx->rgba_cur].p;
+  PCP_HIP_TRY(ctx, ctx->s_keep.ensure(4 * sn + 16));
+  PCP_HIP_TRY(ctx, ctx->s_cell.ensure(sn + 4));
+  {
+    LaunchTimer t(ctx, PCP_K_MISC);
+    hipLaunchKernelGGL(k_has_flags, dim3(sc_blocks(n, int64_t(1) << 31)), dim3(kScBlock), 0, ctx->stream, packed, n, ctx->s_keep.p);
+    PCP_HIP_TRY(ctx, hipGetLastError());
+  }
+  return compact_flags(ctx, ctx->s_keep.p, n, ctx->s_cell.p, n, m);
+}
+
 }  // namespace pcp
 
 using namespace pcp;
@@ -166,15 +180,8 @@ int pcp_colour_compact(pcp_context *ctx, int64_t capacity, int32_t *out_index, f
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t sn = static_cast<size_t>(n);
   const uint32_t *packed = ctx->rgba2[ctx->rgba_cur].p;
-  PCP_HIP_TRY(ctx, ctx->s_keep.ensure(4 * sn + 16));
-  PCP_HIP_TRY(ctx, ctx->s_cell.ensure(sn + 4));
-  {
-    LaunchTimer t(ctx, PCP_K_MISC);
-    hipLaunchKernelGGL(k_has_flags, dim3(sc_blocks(n, int64_t(1) << 31)), dim3(kScBlock), 0, ctx->stream, packed, n, ctx->s_keep.p);
-    PCP_HIP_TRY(ctx, hipGetLastError());
-  }
   int64_t m = 0;
-  int rc = compact_flags(ctx, ctx->s_keep.p, n, ctx->s_cell.p, n, &m);
+  int rc = colour_compact_indices(ctx, &m);
   if (rc != PCP_OK) return rc;
   if (out_count) *out_count = m;
   const int64_t take = std::min(m, capacity);

@@ -54,6 +54,11 @@
 //     labels"); the host concatenation is not built.  A keyframe whose mask is missing throws "Failed to read image from:
 //     <mask path>" (exit -2).  The per-keyframe _rgb-mask.pcd dumps are still written, unless --skip_filtered_dumps 1: the
 //     per-keyframe loop is then skipped altogether.  Works with --gpus N and --matchBack radius.
+//   * --deviceWriter 0|1 (new, default 0): 1 = the rows of every ASCII PCD the run writes are formatted on the device and
+//     downloaded as text (DESIGN.md "Device PCD writer"): the final files and <stem>_mls.pcd from the results resident on the
+//     GPU (pcp_colour_compact_ascii, pcp_mls_fetch_ascii; one-shot and --streamColour 1), scans-crop.pcd and the per-keyframe
+//     dumps from the arrays those sites hold (pcp_ascii_rows).  Every file is byte for byte the --deviceWriter 0 file; headers,
+//     names, messages and exit codes are unchanged.  --gpus N > 1 is refused: the resident forms do not exist on index shards.
 //   * --streamColour 0|1 (new, default 0; with --enableMLS 1) and --streamChunk voxels (default 2^28): 1 = the smoothed cloud
 //     is never gathered on the host.  The smoothing chain runs in its streamed form and every chunk of it is handed, on the
 //     device, to the colour stage (CloudSmooth::processAndColorizeStreamed; DESIGN.md "Streamed colourisation"): one sweep
@@ -140,6 +145,7 @@ struct Options {
   bool fuse_masks = false;            // --fuseMasks 1: one fused label per map point in cloudInWorldWithRGBandMask.pcd
   bool stream_colour = false;         // --streamColour 1: smoothing chain -> colour stage chunk by chunk on the device
   int64_t stream_chunk = int64_t(1) << 28;  // --streamChunk: voxels per chunk (the capacity of the streamed fallback)
+  bool device_writer = false;         // --deviceWriter 1: the rows of every ASCII PCD are formatted on the device
 };
 
 static bool parse_bool(const std::string &v) {  // boost::program_options bool semantics
@@ -205,6 +211,12 @@ static Options parse(int argc, char **argv) {
         throw std::runtime_error("the argument ('" + v + "') for option '--fuseMasks' is invalid (0, 1)");
       o.fuse_masks = v == "1";
     }
+    else if (a == "--deviceWriter") {
+      const std::string v = next();
+      if (v != "0" && v != "1")
+        throw std::runtime_error("the argument ('" + v + "') for option '--deviceWriter' is invalid (0, 1)");
+      o.device_writer = v == "1";
+    }
     else if (a == "--streamColour") {
       const std::string v = next();
       if (v != "0" && v != "1")
@@ -238,6 +250,9 @@ static Options parse(int argc, char **argv) {
     throw std::runtime_error("the option '--matchBack radius' needs the whole map on one GPU (--gpus 1)");
   if (o.fuse_masks && o.maskImageFolder.empty())
     throw std::runtime_error("the option '--fuseMasks 1' needs the masks (--mask_image_folder)");
+  if (o.device_writer && o.gpus > 1)  // (before anything is read or written, as --streamColour 1 refuses what it cannot do)
+    throw std::runtime_error("the option '--deviceWriter 1' does not work with '--gpus N' above 1 (the text is formatted from the "
+                             "results resident on one GPU: they do not exist on index shards)");
   if (o.stream_colour) {
     // every chunk is coloured on its own: what needs the whole smoothed cloud at once is refused here, before any GPU work
     auto refuse = [](const std::string &what, const std::string &why) {
@@ -269,7 +284,8 @@ static void usage(std::ostream &os) {
         "  -t [ --output_path ] arg (=.)         Path to save processed output\n"
         "  --enableMLS arg (=0)                  Enable MLS smoothing\n"
         "  --enableNIDOptimize arg (=0)          Enable NID-based camera pose optimization\n"
-        "  --enableInitialGuessManual arg (=0)   Enable manual pickup point based camera pose optimization\n";
+        "  --enableInitialGuessManual arg (=0)   Enable manual pickup point based camera pose optimization\n"
+        "  --deviceWriter arg (=0)               Format the rows of every ASCII PCD on the GPU (same bytes; --gpus 1)\n";
 }
 
 class Processor {
@@ -382,7 +398,10 @@ class Processor {
     std::cout << "Loaded point cloud with " << original.size() << " points." << std::endl;
     std::cout << "Cropped point cloud with " << cropped.size() << " points." << std::endl;
     const std::string cropPath = opt.outputPath + "scans-crop.pcd";  // outputPath must end in '/' (:131)
-    writeASCII_XYZI(cropPath, cropped.x.data(), cropped.y.data(), cropped.z.data(), cropped.intensity.data(), cropped.size());
+    if (opt.device_writer)
+      deviceWriteXYZI(cropPath, cropped.x.data(), cropped.y.data(), cropped.z.data(), cropped.intensity.data(), cropped.size());
+    else
+      writeASCII_XYZI(cropPath, cropped.x.data(), cropped.y.data(), cropped.z.data(), cropped.intensity.data(), cropped.size());
     std::cout << "Cropped point cloud saved to: " << cropPath << std::endl;
     g_clock.add("crop_and_write_ascii_s", PhaseClock::since(t_crop));
     Phase ph_mls(opt.enableMLS ? "enable_mls_stage_s" : "cloud_move_s");
@@ -411,7 +430,29 @@ class Processor {
       SmoothedCloud s = smooth.processWithOutlierRemoval(crop8.x.data(), crop8.y.data(), crop8.z.data(),
                                                          static_cast<int64_t>(crop8.size()));
       const std::string mlsPath = fs::path(cropPath).stem().string() + "_mls.pcd";  // CWD-relative, sic (B14)
-      writeASCII_PointNormal(mlsPath, s.xyz.data(), s.normal.data(), s.curvature.data(), s.curvature.size());
+      if (!opt.device_writer) {
+        writeASCII_PointNormal(mlsPath, s.xyz.data(), s.normal.data(), s.curvature.data(), s.curvature.size());
+      } else if (smooth.resultResident()) {  // the rows are still the smoothing context's result: formatted where they lie
+        ChunkedAsciiWriter w(mlsPath, ChunkedAsciiWriter::PointNormal, static_cast<int64_t>(s.curvature.size()));
+        for (int64_t first = 0;;) {
+          const Device::TextWindow t = smooth.device(0).mlsFetchAscii(first, kTextWindowRows, text_);
+          if (t.rows == 0) break;
+          w.appendText(text_.data(), static_cast<size_t>(t.bytes), static_cast<size_t>(t.rows));
+          first += t.rows;
+        }
+        (void)w.finish();
+      } else {  // (the streamed fallback gathered its chunks on the host)
+        std::vector<float> f(7 * s.curvature.size());
+        for (size_t i = 0; i < s.curvature.size(); ++i) {
+          for (size_t c = 0; c < 3; ++c) {
+            f[7 * i + c] = s.xyz[3 * i + c];
+            f[7 * i + 3 + c] = s.normal[3 * i + c];
+          }
+          f[7 * i + 6] = s.curvature[i];
+        }
+        (void)deviceWriteRows(smooth.device(0), mlsPath, ChunkedAsciiWriter::PointNormal, PCP_ROWS_POINTNORMAL, s.curvature.size(), f.data(),
+                              nullptr, nullptr);
+      }
       cloud.resize(s.curvature.size());
       for (size_t i = 0; i < cloud.size(); ++i) {
         cloud.x[i] = s.xyz[3 * i];
@@ -429,6 +470,62 @@ class Processor {
       cloud = std::move(original);  // the reference reloads the same file (:148)
       std::cout << "Loaded point cloud with " << cloud.size() << " points." << std::endl;
     }
+  }
+
+  // ---- --deviceWriter 1 ----------------------------------------------------------------------------------------------------
+  std::vector<char> text_;  // one window of text, reused by every site
+
+  // the colour context, wherever in process() it is first needed (the crop is written before setupDevice)
+  Device &writerDevice() {
+    if (device_thread.joinable()) device_thread.join();
+    if (device_error) std::rethrow_exception(device_error);
+    if (!gpu) gpu.reset(new MultiDevice(opt.gpus));
+    return gpu->device(0);
+  }
+  // a writeASCII_* site whose rows are host arrays (f row-major): header, then the rows formatted by pcp_ascii_rows window by
+  // window.  0 / -1 and the empty-cloud exception as the host writers.
+  int deviceWriteRows(Device &dev, const std::string &path, ChunkedAsciiWriter::Kind kind, int32_t rows_kind, size_t n, const float *f,
+                      const uint8_t *rgb, const uint16_t *mask) {
+    if (n == 0) throw std::runtime_error(detail::empty_cloud_message());
+    {
+      std::ofstream probe(path, std::ios::binary);  // (the host writers return -1 for a path that cannot be opened)
+      if (!probe) return -1;
+    }
+    const size_t nf = rows_kind == PCP_ROWS_XYZI ? 4 : rows_kind == PCP_ROWS_POINTNORMAL ? 7 : 3;
+    ChunkedAsciiWriter w(path, kind, static_cast<int64_t>(n));
+    for (size_t first = 0; first < n; first += static_cast<size_t>(kTextWindowRows)) {
+      const size_t rows = std::min(n - first, static_cast<size_t>(kTextWindowRows));
+      const int64_t bytes = dev.asciiRows(rows_kind, static_cast<int64_t>(rows), f + nf * first, rgb ? rgb + 3 * first : nullptr,
+                                          mask ? mask + first : nullptr, text_);
+      w.appendText(text_.data(), static_cast<size_t>(bytes), rows);
+    }
+    return w.finish();
+  }
+  int deviceWriteXYZI(const std::string &path, const float *x, const float *y, const float *z, const float *intensity, size_t n) {
+    std::vector<float> f(4 * n);
+    for (size_t i = 0; i < n; ++i) {
+      f[4 * i] = x[i];
+      f[4 * i + 1] = y[i];
+      f[4 * i + 2] = z[i];
+      f[4 * i + 3] = intensity[i];
+    }
+    return deviceWriteRows(writerDevice(), path, ChunkedAsciiWriter::XYZI, PCP_ROWS_XYZI, n, f.data(), nullptr, nullptr);
+  }
+  // a final file from the colour result resident on the device: removePointsWithNoColor's `rows` survivors
+  int deviceWriteColoured(const std::string &path, bool with_label, int64_t rows) {
+    if (rows == 0) throw std::runtime_error(detail::empty_cloud_message());
+    {
+      std::ofstream probe(path, std::ios::binary);
+      if (!probe) return -1;
+    }
+    ChunkedAsciiWriter w(path, with_label ? ChunkedAsciiWriter::XYZRGBMask : ChunkedAsciiWriter::XYZRGB, rows);
+    for (int64_t first = 0;;) {
+      const Device::TextWindow t = gpu->device(0).colourCompactAscii(with_label, first, kTextWindowRows, text_);
+      if (t.rows == 0) break;
+      w.appendText(text_.data(), static_cast<size_t>(t.bytes), static_cast<size_t>(t.rows));
+      first += t.rows;
+    }
+    return w.finish();
   }
 
   void generateResultStorageFolder() {  // :1034-1048
@@ -546,7 +643,8 @@ class Processor {
       }
       const std::string path =
           opt.outputPath + "filtered_pcd/" + std::to_string(keyframes[k].imageTimestamp) + "_beforeNID" + ".pcd";
-      if (writeASCII_XYZI(path, x.data(), y.data(), z.data(), in.data(), kept.size()) == -1)
+      if ((opt.device_writer ? deviceWriteXYZI(path, x.data(), y.data(), z.data(), in.data(), kept.size())
+                             : writeASCII_XYZI(path, x.data(), y.data(), z.data(), in.data(), kept.size())) == -1)
         throw std::runtime_error("Couldn't save filtered point cloud to PCD file.");
       std::cout << "Before NID optimization: view culling pcd saved to: " << path << ", the point size is "
                 << kept.size() << std::endl;
@@ -708,7 +806,17 @@ class Processor {
     std::unique_ptr<ChunkedAsciiWriter> mls, mask;
     ChunkedAsciiWriter rgb(rgbPath, ChunkedAsciiWriter::XYZRGB);
     if (opt.fuse_masks) mask.reset(new ChunkedAsciiWriter(maskPath, ChunkedAsciiWriter::XYZRGBMask));
-    const StreamedColourStats st = cs.processAndColorizeStreamed(
+    const StreamedColourStats st = opt.device_writer ? cs.processAndColorizeStreamedText(
+        gpu->device(0), opt.stream_chunk,
+        [&](const TextRows &t) {
+          if (!t.labelled) rgb.appendText(t.text, t.bytes, t.rows);
+          else if (mask) mask->appendText(t.text, t.bytes, t.rows);
+        },
+        [&](const TextRows &t, int64_t kept_rows) {
+          if (!mls) mls.reset(new ChunkedAsciiWriter(mlsPath, ChunkedAsciiWriter::PointNormal, kept_rows));
+          mls->appendText(t.text, t.bytes, t.rows);
+        },
+        opt.fuse_masks) : cs.processAndColorizeStreamed(
         gpu->device(0), opt.stream_chunk,
         [&](const ColouredChunk &c) {
           rgb.appendColoured(c.xyz.data(), c.rgb.data(), nullptr, c.index.size());
@@ -759,7 +867,9 @@ class Processor {
         Phase ph_w("rgb_mask_dumps_write_ascii_s");
         const std::string path =
             opt.outputPath + "filtered_pcd/" + std::to_string(keyframes[k].imageTimestamp) + "_rgb-mask" + ".pcd";
-        if (writeASCII_XYZRGBMask(path, v.xyz_cam.data(), v.rgb.data(), v.mask.data(), v.index.size()) == -1)
+        if ((opt.device_writer ? deviceWriteRows(gpu->device(0), path, ChunkedAsciiWriter::XYZRGBMask, PCP_ROWS_XYZRGBMASK, v.index.size(),
+                                                 v.xyz_cam.data(), v.rgb.data(), v.mask.data())
+                               : writeASCII_XYZRGBMask(path, v.xyz_cam.data(), v.rgb.data(), v.mask.data(), v.index.size())) == -1)
           throw std::runtime_error("Couldn't save filtered point cloud to PCD file.");
         std::cout << "Filtered point cloud saved to: " << path << ", the point size is " << v.index.size() << std::endl;
         if (opt.fuse_masks) continue;  // the fused file has one row per map point: no concatenation
@@ -783,6 +893,28 @@ class Processor {
       gpu->labels(label);  // of the colour result above; the local smoothing leaves them alone
     }
     Phase ph_w("final_pcd_write_ascii_s");
+    if (opt.device_writer) {
+      // the same two files from the colour result where it lies (after --smoothColorsRadius: the smoothed one): no row is
+      // gathered or formatted on the host; the concatenated mask samples of a run without --fuseMasks are host arrays
+      int64_t coloured = 0;
+      for (size_t i = 0; i < cloud.size(); ++i) coloured += has[i] ? 1 : 0;
+      const bool mask_rows = opt.fuse_masks ? coloured > 0 : !wmask.empty();
+      if (enableMaskSegmentation && mask_rows) {
+        Phase ph_m("mask_pcd_rows_s");
+        const std::string path = opt.outputPath + "cloudInWorldWithRGBandMask.pcd";
+        if ((opt.fuse_masks ? deviceWriteColoured(path, true, coloured)
+                            : deviceWriteRows(gpu->device(0), path, ChunkedAsciiWriter::XYZRGBMask, PCP_ROWS_XYZRGBMASK, wmask.size(),
+                                              wxyz.data(), wrgb.data(), wmask.data())) == -1)
+          throw std::runtime_error("Couldn't save colorized and segment colored point cloud.");
+        std::cout << "All colored and segment colored cloud saved to: " << path << std::endl;
+      }
+      if (coloured > 0) {
+        const std::string path = opt.outputPath + "cloudInWorldWithRGB.pcd";
+        if (deviceWriteColoured(path, false, coloured) == -1) throw std::runtime_error("Couldn't save colorized point cloud.");
+        std::cout << "All colored cloud saved to: " << path << std::endl;
+      }
+      return;
+    }
     XYZICloud out;
     std::vector<uint8_t> out_rgb;
     for (size_t i = 0; i < cloud.size(); ++i)

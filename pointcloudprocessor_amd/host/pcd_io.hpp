@@ -402,7 +402,7 @@ inline int writeASCII_PointNormal(const std::string &path, const float *xyz, con
 // assembles header + body (no padded header).  An empty file is the one-shot writers' exception, raised by finish().
 class ChunkedAsciiWriter {
  public:
-  enum Kind { XYZRGB, XYZRGBMask, PointNormal };
+  enum Kind { XYZRGB, XYZRGBMask, PointNormal, XYZI };
   ChunkedAsciiWriter(const std::string &path, Kind kind, int64_t known_rows = -1)
       : path_(path), body_path_(known_rows >= 0 ? path : path + ".body.tmp"), kind_(kind), known_(known_rows) {
     if (known_rows == 0) return;  // (finish() throws before any file is touched, as the one-shot writers do)
@@ -455,6 +455,12 @@ class ChunkedAsciiWriter {
           }),
           n);
   }
+  // rows that arrive formatted -- the device writer's text (pcp_ascii_rows, pcp_colour_compact_ascii, pcp_mls_fetch_ascii):
+  // `bytes` bytes holding `rows` whole rows of this writer's kind
+  void appendText(const char *text, size_t bytes, size_t rows) {
+    out_.write(text, static_cast<std::streamsize>(bytes));
+    rows_ += rows;
+  }
   // 0, or -1 when the file could not be written
   int finish() {
     done_ = true;
@@ -493,6 +499,7 @@ class ChunkedAsciiWriter {
     switch (kind_) {
       case XYZRGB: return detail::header("x y z rgb", "4 4 4 4", "F F F U", "1 1 1 1", n);
       case XYZRGBMask: return detail::header("x y z rgb segmentMask", "4 4 4 4 2", "F F F U U", "1 1 1 1 1", n);
+      case XYZI: return detail::header("x y z intensity", "4 4 4 4", "F F F F", "1 1 1 1", n);
       default: return detail::header("x y z normal_x normal_y normal_z curvature", "4 4 4 4 4 4 4", "F F F F F F F", "1 1 1 1 1 1 1", n);
     }
   }

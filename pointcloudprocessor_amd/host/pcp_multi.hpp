@@ -597,6 +597,9 @@ class MultiCloudSmooth {
     slp_step_ = step;
   }
   int size() const { return static_cast<int>(dev_.size()); }
+  Device &device(int r) { return *dev_[static_cast<size_t>(r)]; }
+  // the rows of the last processWithOutlierRemoval are still device(0)'s smoothing result (CloudSmooth::resultResident)
+  bool resultResident() const { return resident_; }
 
   SmoothedCloud processWithOutlierRemoval(const float *x, const float *y, const float *z, int64_t n) {
     // SAMPLE_LOCAL_PLANE: the whole chain on the first GPU.  Each disk follows the sign of its point's fitted normal, and
@@ -606,8 +609,11 @@ class MultiCloudSmooth {
       dev_[0]->uploadCloud(x, y, z, n);
       CloudSmooth cs(*dev_[0], params_);
       cs.setLocalPlaneSampling(slp_radius_, slp_step_);
-      return cs.processWithOutlierRemoval();
+      SmoothedCloud one = cs.processWithOutlierRemoval();
+      resident_ = cs.resultResident();
+      return one;
     }
+    resident_ = false;
     // SOR 1 (cloudSmooth.cpp:109-116)
     std::vector<int32_t> idx1 = outlierRemoval(x, y, z, n);
     std::vector<float> cx(idx1.size()), cy(idx1.size()), cz(idx1.size());
@@ -849,6 +855,7 @@ class MultiCloudSmooth {
   std::vector<ncclComm_t> comm_;
   pcp_mls_params params_;
   double slp_radius_ = 0.05, slp_step_ = 0.01;
+  bool resident_ = false;
 };
 
 }  // namespace pcp_amd

@@ -34,6 +34,10 @@ class Device {
   Device(const Device &) = delete;
   Device &operator=(const Device &) = delete;
   pcp_context *get() const { return ctx_; }
+  static void growText(std::vector<char> &text, int64_t rows, int32_t kind) {
+    const size_t need = static_cast<size_t>(rows) * static_cast<size_t>(pcp_ascii_row_bound(kind));
+    if (text.size() < need) text.resize(need);
+  }
   void check(int rc) const {
     if (rc != PCP_OK) throw std::runtime_error(std::string("pcp_hip: ") + pcp_last_error(ctx_));
   }
@@ -73,6 +77,34 @@ class Device {
   }
   // cv::Mat grayImg (CV_8UC1)
   void uploadMask(int keyframe, const uint8_t *gray, int64_t step) { check(pcp_upload_mask(ctx_, keyframe, gray, step)); }
+
+  // ---- device PCD writer: the rows of the ASCII files as text (pcp_hip.h, "device PCD writer").  `text` is the caller's
+  // buffer, grown to the window's bound when it is smaller and never shrunk: a loop over windows reuses it. ----
+  struct TextWindow {
+    int64_t rows = 0, bytes = 0;
+  };
+  // n rows held on the host (pcp_ascii_rows): the writeASCII_* sites whose arrays are host arrays
+  int64_t asciiRows(int32_t kind, int64_t n, const float *f, const uint8_t *rgb, const uint16_t *mask, std::vector<char> &text) const {
+    growText(text, n, kind);
+    int64_t bytes = 0;
+    check(pcp_ascii_rows(ctx_, kind, n, f, rgb, mask, static_cast<int64_t>(text.size()), text.data(), &bytes));
+    return bytes;
+  }
+  // rows [first_row, first_row + max_rows) of removePointsWithNoColor's survivors (pcp_colour_compact_ascii)
+  TextWindow colourCompactAscii(bool with_label, int64_t first_row, int64_t max_rows, std::vector<char> &text) const {
+    growText(text, max_rows, with_label ? PCP_ROWS_XYZRGBMASK : PCP_ROWS_XYZRGB);
+    TextWindow w;
+    check(pcp_colour_compact_ascii(ctx_, with_label ? 1 : 0, first_row, max_rows, static_cast<int64_t>(text.size()), text.data(), &w.rows,
+                                   &w.bytes));
+    return w;
+  }
+  // rows [first_row, first_row + max_rows) of the latest smoothing result (pcp_mls_fetch_ascii)
+  TextWindow mlsFetchAscii(int64_t first_row, int64_t max_rows, std::vector<char> &text) const {
+    growText(text, max_rows, PCP_ROWS_POINTNORMAL);
+    TextWindow w;
+    check(pcp_mls_fetch_ascii(ctx_, first_row, max_rows, static_cast<int64_t>(text.size()), text.data(), &w.rows, &w.bytes));
+    return w;
+  }
 
  private:
   pcp_context *ctx_ = nullptr;
@@ -221,6 +253,14 @@ struct ColouredChunk {
   std::vector<uint8_t> rgb;    // 3 per row
   std::vector<uint8_t> label;  // fused label per row (label fusion on), else empty
 };
+// Formatted rows handed to a text sink (the device writer): `rows` whole rows in `bytes` bytes; the buffer is reused
+struct TextRows {
+  const char *text;
+  size_t bytes, rows;
+  bool labelled;  // coloured rows: XYZRGBMASK text (the fused label as segmentMask) instead of XYZRGB text
+};
+// rows per window of the text forms: bounds the host buffer (105 B x 2^20 for PointNormal rows) whatever the chunk size
+constexpr int64_t kTextWindowRows = int64_t(1) << 20;
 struct StreamedColourStats {
   int32_t chunks = 0;
   int64_t rows = 0, coloured = 0;            // smoothed rows, rows with a colour
@@ -244,6 +284,9 @@ class CloudSmooth {
   SmoothedCloud processWithOutlierRemoval() const { return run(true); }
   // pcl::MovingLeastSquares::process alone
   SmoothedCloud process() const { return run(false); }
+  // the rows the last process* call returned are still the device's smoothing result (Device::mlsFetchAscii reads them); false
+  // after the streamed fallback, which gathers its chunks on the host
+  bool resultResident() const { return resident_; }
   // The whole CloudSmooth::process through the streamed form (pcp_cloud_smooth_stream_begin / _next): any size of upsampled
   // cloud -- the reference's VOXEL_GRID_DILATION 1 mm x 4 (PointCloudProcessor.cpp:78-81) makes ~2.8e9 rows of a 10 M-point
   // map, more than one result holds.  sink(const SmoothedCloud &chunk) receives the survivors of the trailing outlier
@@ -293,6 +336,80 @@ class CloudSmooth {
   template <class Sink, class SmoothedSink>
   StreamedColourStats processAndColorizeStreamed(Device &colour, int64_t chunk_capacity, Sink &&sink, SmoothedSink &&smoothed,
                                                  bool fuse_labels = false) const {
+    pcp_context *src = dev_.get(), *dst = colour.get();
+    SmoothedCloud s;
+    ColouredChunk out;
+    std::vector<int32_t> source;
+    return streamedSweeps(
+        colour, chunk_capacity,
+        [&](int64_t m, int64_t kept) {
+          fetch(m, s);
+          smoothed(static_cast<const SmoothedCloud &>(s), kept);
+        },
+        [&](int64_t m) {
+          int64_t coloured = 0;
+          const size_t sm = static_cast<size_t>(m);
+          out.index.resize(sm);
+          out.xyz.resize(3 * sm);
+          out.rgb.resize(3 * sm);
+          out.label.resize(fuse_labels ? sm : 0);
+          colour.check(pcp_colour_compact(dst, m, out.index.data(), out.xyz.data(), out.rgb.data(), fuse_labels ? out.label.data() : nullptr,
+                                          &coloured));
+          const size_t sc = static_cast<size_t>(coloured);
+          out.index.resize(sc);
+          out.xyz.resize(3 * sc);
+          out.rgb.resize(3 * sc);
+          out.label.resize(fuse_labels ? sc : 0);
+          if (coloured == 0) return coloured;
+          source.resize(sm);
+          dev_.check(pcp_mls_fetch(src, m, nullptr, nullptr, nullptr, source.data()));
+          for (size_t k = 0; k < sc; ++k) out.index[k] = source[static_cast<size_t>(out.index[k])];
+          sink(static_cast<const ColouredChunk &>(out));
+          return coloured;
+        });
+  }
+  // The same two sweeps with the rows delivered as TEXT, formatted on the device (the device PCD writer): smoothed(const
+  // TextRows &, kept_rows) receives each chunk's PointNormal rows in sweep A, sink(const TextRows &) each chunk's coloured rows in
+  // sweep B -- as XYZRGB text and, with fuse_labels, once more as XYZRGBMASK text (labelled) -- in windows of at most
+  // window_rows rows through one reused buffer, so a 2^28-voxel chunk never needs its 12 GB of text at once.  The windows in
+  // order are the bytes the host writers print of the binary sinks' rows.
+  template <class Sink, class SmoothedSink>
+  StreamedColourStats processAndColorizeStreamedText(Device &colour, int64_t chunk_capacity, Sink &&sink, SmoothedSink &&smoothed,
+                                                     bool fuse_labels = false, int64_t window_rows = kTextWindowRows) const {
+    std::vector<char> text;
+    return streamedSweeps(
+        colour, chunk_capacity,
+        [&](int64_t m, int64_t kept) {
+          for (int64_t first = 0; first < m;) {
+            const Device::TextWindow w = dev_.mlsFetchAscii(first, window_rows, text);
+            if (w.rows == 0) break;
+            smoothed(TextRows{text.data(), static_cast<size_t>(w.bytes), static_cast<size_t>(w.rows), false}, kept);
+            first += w.rows;
+          }
+        },
+        [&](int64_t) {
+          int64_t coloured = 0;
+          for (int labelled = 0; labelled <= (fuse_labels ? 1 : 0); ++labelled)
+            for (int64_t first = 0;;) {
+              const Device::TextWindow w = colour.colourCompactAscii(labelled != 0, first, window_rows, text);
+              if (w.rows == 0) break;
+              sink(TextRows{text.data(), static_cast<size_t>(w.bytes), static_cast<size_t>(w.rows), labelled != 0});
+              first += w.rows;
+              if (!labelled) coloured += w.rows;
+            }
+          return coloured;
+        });
+  }
+  template <class Sink>
+  StreamedColourStats processAndColorizeStreamed(Device &colour, int64_t chunk_capacity, Sink &&sink) const {
+    return processAndColorizeStreamed(colour, chunk_capacity, sink, [](const SmoothedCloud &, int64_t) {});
+  }
+
+ private:
+  // the two sweeps of processAndColorizeStreamed: after_a(rows, kept_rows) once per chunk of sweep A (the chunk is this
+  // device's smoothing result), after_b(rows) -> coloured rows once per chunk of sweep B (the chunk is coloured on `colour`)
+  template <class AfterA, class AfterB>
+  StreamedColourStats streamedSweeps(Device &colour, int64_t chunk_capacity, AfterA &&after_a, AfterB &&after_b) const {
     using clock = std::chrono::steady_clock;
     pcp_context *src = dev_.get(), *dst = colour.get();
     StreamedColourStats st;
@@ -306,7 +423,6 @@ class CloudSmooth {
       ~EndStream() { (void)pcp_cloud_smooth_stream_end(c); }
     } end_stream{src};
     auto t0 = clock::now();
-    SmoothedCloud s;
     for (int32_t c = 0; c < st.chunks; ++c) {  // (chunks without rows are skipped by _next: the calls left over return 0)
       int64_t m = 0, n = 0;
       dev_.check(pcp_cloud_smooth_stream_next(src, &m));
@@ -315,51 +431,25 @@ class CloudSmooth {
       colour.check(pcp_upload_cloud_from_result(dst, src, &n));
       colour.check(pcp_depth_pass(dst, 0, frames));
       colour.check(pcp_depth_accum_merge(dst));
-      fetch(m, s);
-      smoothed(static_cast<const SmoothedCloud &>(s), kept);
+      after_a(m, kept);
     }
     colour.check(pcp_synchronize(dst));
     st.sweep_a_s = std::chrono::duration<double>(clock::now() - t0).count();
     t0 = clock::now();
     dev_.check(pcp_cloud_smooth_stream_seek(src, 0));
-    ColouredChunk out;
-    std::vector<int32_t> source;
     for (int32_t c = 0; c < st.chunks; ++c) {
-      int64_t m = 0, n = 0, coloured = 0;
+      int64_t m = 0, n = 0;
       dev_.check(pcp_cloud_smooth_stream_next(src, &m));
       if (m == 0) continue;
       colour.check(pcp_upload_cloud_from_result(dst, src, &n));
       colour.check(pcp_depth_pass(dst, 0, frames));  // builds this chunk's tile masks, as on a shard before the all-reduce(MIN)
       colour.check(pcp_depth_accum_apply(dst));
       colour.check(pcp_colorize_from_depth(dst, nullptr, nullptr));
-      const size_t sm = static_cast<size_t>(m);
-      out.index.resize(sm);
-      out.xyz.resize(3 * sm);
-      out.rgb.resize(3 * sm);
-      out.label.resize(fuse_labels ? sm : 0);
-      colour.check(pcp_colour_compact(dst, m, out.index.data(), out.xyz.data(), out.rgb.data(), fuse_labels ? out.label.data() : nullptr,
-                                      &coloured));
-      const size_t sc = static_cast<size_t>(coloured);
-      out.index.resize(sc);
-      out.xyz.resize(3 * sc);
-      out.rgb.resize(3 * sc);
-      out.label.resize(fuse_labels ? sc : 0);
-      st.coloured += coloured;
-      if (coloured == 0) continue;
-      source.resize(sm);
-      dev_.check(pcp_mls_fetch(src, m, nullptr, nullptr, nullptr, source.data()));
-      for (size_t k = 0; k < sc; ++k) out.index[k] = source[static_cast<size_t>(out.index[k])];
-      sink(static_cast<const ColouredChunk &>(out));
+      st.coloured += after_b(m);
     }
     st.sweep_b_s = std::chrono::duration<double>(clock::now() - t0).count();
     return st;
   }
-  template <class Sink>
-  StreamedColourStats processAndColorizeStreamed(Device &colour, int64_t chunk_capacity, Sink &&sink) const {
-    return processAndColorizeStreamed(colour, chunk_capacity, sink, [](const SmoothedCloud &, int64_t) {});
-  }
-
- private:
   void fetch(int64_t m, SmoothedCloud &s) const {
     const size_t sm = static_cast<size_t>(m);
     s.xyz.resize(3 * sm);
@@ -369,6 +459,7 @@ class CloudSmooth {
     dev_.check(pcp_mls_fetch(dev_.get(), m, s.xyz.data(), s.normal.data(), s.curvature.data(), s.index.data()));
   }
   SmoothedCloud run(bool with_sor) const {
+    resident_ = false;
     dev_.check(pcp_set_mls_local_plane(dev_.get(), slp_radius_, slp_step_));
     int64_t m = 0;
     int rc = with_sor ? pcp_cloud_smooth(dev_.get(), &params_, &m) : pcp_mls_process(dev_.get(), &params_, &m);
@@ -392,10 +483,12 @@ class CloudSmooth {
     s.curvature.resize(sm);
     s.index.resize(sm);
     dev_.check(pcp_mls_fetch(dev_.get(), m, s.xyz.data(), s.normal.data(), s.curvature.data(), s.index.data()));
+    resident_ = true;
     return s;
   }
 
   Device &dev_;
+  mutable bool resident_ = false;
   pcp_mls_params params_;
   double slp_radius_ = 0.05, slp_step_ = 0.01;
 };
