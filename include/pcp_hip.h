@@ -53,7 +53,9 @@ extern "C" {
                                 _apply / _device, pcp_cloud_smooth_stream_seek, pcp_colour_compact (streamed colourisation: a
                                 smoothed cloud larger than one upload coloured chunk by chunk; nothing runs unless called);
                                 entry points added, no layout changed: pcp_ascii_row_bound, pcp_ascii_rows_host, pcp_ascii_rows,
-                                pcp_colour_compact_ascii, pcp_mls_fetch_ascii (the device PCD writer; nothing runs unless called) */
+                                pcp_colour_compact_ascii, pcp_mls_fetch_ascii (the device PCD writer; nothing runs unless called);
+                                entry points added, no layout changed: pcp_ascii_parse_host, pcp_ascii_parse, pcp_ascii_parse_limit
+                                (the device PCD reader; nothing runs unless called) */
 
 #define PCP_OK 0
 #define PCP_ERR_INVALID (-1) /* bad argument */
@@ -629,6 +631,44 @@ int pcp_colour_compact_ascii(pcp_context *ctx, int32_t with_label, int64_t first
  * result or stream chunk), as POINTNORMAL text (<stem>_mls.pcd, cloudSmooth.cpp:180-181).  Same rules. */
 int pcp_mls_fetch_ascii(pcp_context *ctx, int64_t first_row, int64_t max_rows, int64_t capacity, char *out_text,
                         int64_t *out_rows, int64_t *out_bytes);
+
+/* ---- device PCD reader (pcl::io::loadPCDFile of a DATA ascii file: PointCloudProcessor.cpp:112, :148, cloudSmooth.cpp:92) - */
+/* The x y z intensity floats of a window of PCD ASCII rows ("Device PCD reader", DR1-DR8): every value bit for bit
+ * what glibc's strtof returns for its token -- the fp32 nearest the exact decimal value, ties to even, computed on integers --
+ * and so what host/pcd_io.hpp's loadPCDFile returns.  A row ends at '\n'; tokens are separated by space \t \r \v \f; a row
+ * needs `columns` tokens (more are ignored); only the tokens of the columns read are examined, and they must be
+ * [+-]? (D+ ('.' D*)? | '.' D+) ([eE] [+-]? D+)? with at most 19 digits between the first and the last non-zero digit of the
+ * significand and at most 5 exponent digits, or nan / inf / infinity in any case with an optional sign.  Every other row is
+ * BAD (too few tokens, blank, hex floats, "1.5abc", NUL bytes, 20 significant digits, ...), and so is a row of more than
+ * PCP_ASCII_PARSE_MAX_ROW bytes in front of its '\n'.  A bad row is never given a value: the caller hands such a file to
+ * its own reader.  Opt-in: nothing runs unless called; PCP_ABI_VERSION is unchanged, a caller detects support by the symbols. */
+#define PCP_ASCII_PARSE_MAX_ROW 65536 /* bytes of a row in front of its '\n' */
+/* pcp_ascii_parse_limit(which): the sizes the implementation works with (the tests place rows around them); <0: unknown */
+#define PCP_PARSE_LIMIT_ROW 0       /* PCP_ASCII_PARSE_MAX_ROW */
+#define PCP_PARSE_LIMIT_TILE 1      /* bytes of text a workgroup stages into LDS; a longer span is walked in global memory */
+#define PCP_PARSE_LIMIT_PIECE 2     /* bytes per upload piece of a window */
+#define PCP_PARSE_LIMIT_TILE_ROWS 3 /* rows per workgroup */
+#define PCP_PARSE_LIMIT_WINDOW 4    /* bytes per call: 2^31 - 1 (row offsets are 32-bit); a longer window is PCP_ERR_RANGE */
+int64_t pcp_ascii_parse_limit(int32_t which);
+/* Host only, no context, no GPU: the parser the kernels use (csrc/pcp_ascii_parse.hpp), run on the CPU -- the way to check it on
+ * every bit pattern.  The window is text[0, bytes).  columns: scalars per row (sum of COUNT).  col[0..3]: 0-based column of x,
+ * y, z, intensity; col[3] = -1: none (0.0f).  The bytes after the last '\n' are a row only when final_window != 0 and they
+ * hold a non-blank byte; otherwise they stay unconsumed for the caller's next window.
+ * *out_rows = rows parsed: the smallest of max_rows, the rows of the window and the index of the first bad row; out_x / _y /
+ * _z / _intensity [0, *out_rows) are written, the entries behind them left untouched.  *out_consumed = the offset just past
+ * the last parsed row (the start of the bad row when one ends the parse).  *out_bad_row = -1 or the index of the first bad
+ * row; a bad row is not an error (PCP_OK).  NULL outputs, negative bytes or max_rows, columns outside 1..64, a col entry
+ * outside -1..columns-1 (-1 for the intensity only): PCP_ERR_INVALID.  bytes above 2^31 - 1: PCP_ERR_RANGE.  bytes == 0: 0
+ * rows, PCP_OK.  The message of a failure is at pcp_last_error(NULL). */
+int pcp_ascii_parse_host(const char *text, int64_t bytes, int32_t columns, const int32_t col[4], int32_t final_window,
+                         int64_t max_rows, float *out_x, float *out_y, float *out_z, float *out_intensity,
+                         int64_t *out_rows, int64_t *out_consumed, int64_t *out_bad_row);
+/* The same window parsed on the device: same arguments, same results.  text and the outputs are host memory, pageable or
+ * pinned, and are not retained; the window goes up in pieces through pinned staging while the kernels of the piece before
+ * run and the rows of the one before that come down.  Synchronous.  Kernels are timed under PCP_K_MISC. */
+int pcp_ascii_parse(pcp_context *ctx, const char *text, int64_t bytes, int32_t columns, const int32_t col[4], int32_t final_window,
+                    int64_t max_rows, float *out_x, float *out_y, float *out_z, float *out_intensity,
+                    int64_t *out_rows, int64_t *out_consumed, int64_t *out_bad_row);
 
 /* ---- precondition of the match-back(PointCloudProcessor.cpp:480-482,571) ------------------------------- */
 /* Number of map points that have ANOTHER map point closer than `radius` (fp32 squared distance, strict <, as

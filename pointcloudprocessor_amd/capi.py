@@ -207,6 +207,47 @@ def ascii_rows_host(kind: int, f, rgb=None, mask=None, capacity: int | None = No
     return _ascii_rows_call(L.pcp_ascii_rows_host, check, kind, f, rgb, mask, capacity, out)
 
 
+# sizes of the device PCD reader (pcp_ascii_parse_limit)
+PARSE_LIMIT_ROW, PARSE_LIMIT_TILE, PARSE_LIMIT_PIECE, PARSE_LIMIT_TILE_ROWS, PARSE_LIMIT_WINDOW = 0, 1, 2, 3, 4
+
+
+def ascii_parse_limit(which: int) -> int:
+    """A size the device PCD reader works with (pcp_ascii_parse_limit): the longest row, the LDS staging tile, the upload piece,
+    the rows per workgroup, the longest window; negative for an unknown one."""
+    L = load()
+    L.pcp_ascii_parse_limit.restype = C.c_int64
+    return int(L.pcp_ascii_parse_limit(C.c_int32(which)))
+
+
+def _ascii_parse_call(fn, check, text, columns, col, final, max_rows, out):
+    """Shared by the host and device forms: (x, y, z, intensity, consumed, bad_row), the arrays cut to the rows parsed.
+    text: bytes or a uint8 array.  max_rows None: every row of the window.  out: four caller's float32 arrays (of max_rows
+    entries or more) to fill instead of fresh ones."""
+    buf = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, np.uint8).reshape(-1)
+    if max_rows is None:
+        max_rows = int(np.count_nonzero(buf == 10)) + 1
+    if out is None:
+        out = tuple(np.empty(max(max_rows, 0), np.float32) for _ in range(4))
+    carr = None if col is None else (C.c_int32 * 4)(*[int(c) for c in col])
+    rows, consumed, bad = C.c_int64(-1), C.c_int64(-1), C.c_int64(-2)
+    check(fn(_ptr(buf) if buf.size else None, C.c_int64(buf.size), C.c_int32(columns), carr, C.c_int32(1 if final else 0), C.c_int64(max_rows),
+             _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), C.byref(rows), C.byref(consumed), C.byref(bad)))
+    n = rows.value
+    return out[0][:n], out[1][:n], out[2][:n], out[3][:n], consumed.value, bad.value
+
+
+def ascii_parse_host(text, columns: int, col, final: bool = True, max_rows: int | None = None, out=None):
+    """PCD ASCII rows parsed on the CPU by the parser the kernels use (pcp_ascii_parse_host: no context, no GPU).
+    columns: scalars per row; col: the 0-based columns of x, y, z, intensity (-1: no intensity, 0.0)."""
+    L = load()
+
+    def check(rc):
+        if rc != PCP_OK:
+            raise PcpError(rc, L.pcp_last_error(None).decode())
+
+    return _ascii_parse_call(L.pcp_ascii_parse_host, check, text, columns, col, final, max_rows, out)
+
+
 def default_camera() -> Camera:
     cam = Camera()
     load().pcp_default_camera(C.byref(cam))
@@ -533,6 +574,12 @@ class Context:
         (pcp_mls_fetch_ascii); count = the rows of the latest smoothing result."""
         call = lambda *a: self.lib.pcp_mls_fetch_ascii(self.h, *a)  # noqa: E731
         return self._ascii_window(call, ascii_row_bound(ROWS_POINTNORMAL), count, first_row, max_rows, capacity)
+
+    # -- device PCD reader ---------------------------------------------------
+    def ascii_parse(self, text, columns: int, col, final: bool = True, max_rows: int | None = None, out=None):
+        """ascii_parse_host's window parsed on the device (pcp_ascii_parse): (x, y, z, intensity, consumed, bad_row)."""
+        fn = lambda *a: self.lib.pcp_ascii_parse(self.h, *a)  # noqa: E731
+        return _ascii_parse_call(fn, self._check, text, columns, col, final, max_rows, out)
 
     def colour_reset(self):
         self._check(self.lib.pcp_colour_reset(self.h))

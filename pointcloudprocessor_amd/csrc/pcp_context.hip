@@ -618,7 +618,7 @@ int pcp_create(int32_t device, pcp_context **out) {
     hipFuncAttributes a;
     const hipError_t pl[] = {hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_up_bbox)), preload_colour(), preload_mls(),
                              preload_nid(), preload_hpr(), preload_colour_smooth(), preload_match(),
-                             preload_jpeg(), preload_stream_colour(), preload_ascii()};
+                             preload_jpeg(), preload_stream_colour(), preload_ascii(), preload_ascii_parse()};
     for (hipError_t x : pl)
       if (x != hipSuccess && e == hipSuccess) e = x;
   }
@@ -697,6 +697,7 @@ void pcp_destroy(pcp_context *ctx) {
   ctx->ascii_len.release();
   ctx->ascii_text.release();
   ctx->ascii_tiles.release();
+  ascii_parse_release(ctx);
   if (ctx->handoff) (void)hipEventDestroy(ctx->handoff);
   ctx->depth_sq.release();
   ctx->tile_sphere.release();

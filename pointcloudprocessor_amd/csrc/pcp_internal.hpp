@@ -114,6 +114,20 @@ struct DevBuf {
   }
 };
 
+// device PCD reader (pcp_ascii_parse.hip): what one piece of text in flight owns -- pinned staging, the text, the offsets of its
+// '\n' bytes, the tile counts of the scan, four planes of parsed words, the result words (device and pinned) -- and the events
+// that order its upload (staged), its kernels (parsed) and the download of its rows (drained) against the slot's next piece
+struct AsciiParseSlot {
+  void *stage = nullptr, *res_h = nullptr;
+  size_t stage_bytes = 0;
+  DevBuf<uint8_t> text;
+  DevBuf<int32_t> end, tiles;
+  DevBuf<uint32_t> out;
+  DevBuf<unsigned long long> res;
+  hipEvent_t staged = nullptr, parsed = nullptr, drained = nullptr;
+  bool staged_live = false, parsed_live = false, drained_live = false;
+};
+
 // hidden_points_removal: the scratch of ONE keyframe's hull (pcp_hpr.hip).  The keyframes of a run are independent, so the
 // whole-run pass keeps several of them in flight, each on a lane of its own: a stream, the buffers and a pinned readback
 // into which the device publishes the candidates' count and bounds (the one host wait of a keyframe polls it).  Lane 0
@@ -319,6 +333,9 @@ struct pcp_context {
   // bytes (+ the window edges), one window of text
   pcp::DevBuf<uint8_t> ascii_in, ascii_len, ascii_text;
   pcp::DevBuf<unsigned long long> ascii_tiles;
+  // device PCD reader (pcp_ascii_parse.hip): two slots a window's pieces alternate between, an upload and a download stream
+  pcp::AsciiParseSlot parse_slot[2];
+  hipStream_t parse_up = nullptr, parse_down = nullptr;
   // pcp_mls_stream_*: the plan of a chunked VOXEL_GRID_DILATION emission (pcp_mls.hip VgdStream; word0, word1, count per chunk)
   std::vector<uint8_t> vgd_blob;
   std::vector<int64_t> vgd_chunks;
@@ -481,6 +498,8 @@ hipError_t preload_match();
 hipError_t preload_jpeg();
 hipError_t preload_stream_colour();
 hipError_t preload_ascii();
+hipError_t preload_ascii_parse();
+void ascii_parse_release(pcp_context *ctx);  // the reader's slots, streams and events (pcp_destroy)
 
 // removePointsWithNoColor's index list (pcp_stream_colour.hip): the rows of the current colour result whose has bit is set,
 // input order, into ctx->s_cell; *m = their number.  ctx->n > 0 and a live colour result are the caller's to check.

@@ -59,6 +59,12 @@
 //     GPU (pcp_colour_compact_ascii, pcp_mls_fetch_ascii; one-shot and --streamColour 1), scans-crop.pcd and the per-keyframe
 //     dumps from the arrays those sites hold (pcp_ascii_rows).  Every file is byte for byte the --deviceWriter 0 file; headers,
 //     names, messages and exit codes are unchanged.  --gpus N > 1 is refused: the resident forms do not exist on index shards.
+//   * --deviceReader 0|1 (new, default 0): 1 = the rows of the ASCII PCDs the run reads -- the map (-p) and, with --enableMLS 1,
+//     the crop CloudSmooth reads back (cloudSmooth.cpp:92) -- are parsed on the device (pcp_ascii_parse; DESIGN.md "Device PCD
+//     reader"): every float bit for bit the strtof value loadPCDFile returns.  A file the device reader does not take (a row
+//     outside plain decimal text, fewer rows than POINTS) is named on stderr with the row and read by the host reader whole;
+//     binary and binary_compressed maps ignore the flag.  Messages, exit codes, phase keys and every output file are those of
+//     --deviceReader 0.  Works with --gpus N (the first device parses).
 //   * --streamColour 0|1 (new, default 0; with --enableMLS 1) and --streamChunk voxels (default 2^28): 1 = the smoothed cloud
 //     is never gathered on the host.  The smoothing chain runs in its streamed form and every chunk of it is handed, on the
 //     device, to the colour stage (CloudSmooth::processAndColorizeStreamed; DESIGN.md "Streamed colourisation"): one sweep
@@ -87,6 +93,7 @@
 #include "pcd_io.hpp"
 #include "pcp_multi.hpp"
 #include "pcp_shim.hpp"
+#include "pcd_device_reader.hpp"
 
 namespace fs = std::filesystem;
 using namespace pcp_amd;
@@ -146,6 +153,7 @@ struct Options {
   bool stream_colour = false;         // --streamColour 1: smoothing chain -> colour stage chunk by chunk on the device
   int64_t stream_chunk = int64_t(1) << 28;  // --streamChunk: voxels per chunk (the capacity of the streamed fallback)
   bool device_writer = false;         // --deviceWriter 1: the rows of every ASCII PCD are formatted on the device
+  bool device_reader = false;         // --deviceReader 1: the rows of the ASCII PCDs the run reads are parsed on the device
 };
 
 static bool parse_bool(const std::string &v) {  // boost::program_options bool semantics
@@ -217,6 +225,12 @@ static Options parse(int argc, char **argv) {
         throw std::runtime_error("the argument ('" + v + "') for option '--deviceWriter' is invalid (0, 1)");
       o.device_writer = v == "1";
     }
+    else if (a == "--deviceReader") {
+      const std::string v = next();
+      if (v != "0" && v != "1")
+        throw std::runtime_error("the argument ('" + v + "') for option '--deviceReader' is invalid (0, 1)");
+      o.device_reader = v == "1";
+    }
     else if (a == "--streamColour") {
       const std::string v = next();
       if (v != "0" && v != "1")
@@ -285,7 +299,8 @@ static void usage(std::ostream &os) {
         "  --enableMLS arg (=0)                  Enable MLS smoothing\n"
         "  --enableNIDOptimize arg (=0)          Enable NID-based camera pose optimization\n"
         "  --enableInitialGuessManual arg (=0)   Enable manual pickup point based camera pose optimization\n"
-        "  --deviceWriter arg (=0)               Format the rows of every ASCII PCD on the GPU (same bytes; --gpus 1)\n";
+        "  --deviceWriter arg (=0)               Format the rows of every ASCII PCD on the GPU (same bytes; --gpus 1)\n"
+        "  --deviceReader arg (=0)               Parse the rows of the ASCII PCDs that are read on the GPU (same floats)\n";
 }
 
 class Processor {
@@ -380,7 +395,7 @@ class Processor {
     XYZICloud original;
     {
       Phase ph("pcd_read_s");
-      if (loadPCDFile(opt.pointCloudPath, original) == -1) throw std::runtime_error("Couldn't read point cloud file.");
+      if (readPCD(opt.pointCloudPath, original) == -1) throw std::runtime_error("Couldn't read point cloud file.");
     }
     std::cout << "Start crop pcd..." << std::endl;
     // pcl::CropBox with Vector4f(min), Vector4f(max): keep min <= p <= max (fp32 bounds)
@@ -408,7 +423,7 @@ class Processor {
     if (opt.enableMLS) {
       // CloudSmooth re-reads the ASCII crop it was handed (cloudSmooth.cpp:92): 8 significant digits
       XYZICloud crop8;
-      if (loadPCDFile(cropPath, crop8) == -1) {
+      if (readPCD(cropPath, crop8) == -1) {
         std::cerr << "Couldn't read file " << cropPath << std::endl;
         return;
       }
@@ -470,6 +485,18 @@ class Processor {
       cloud = std::move(original);  // the reference reloads the same file (:148)
       std::cout << "Loaded point cloud with " << cloud.size() << " points." << std::endl;
     }
+  }
+
+  // ---- --deviceReader 1 ----------------------------------------------------------------------------------------------------
+  // loadPCDFile, with the rows of an ASCII file parsed on the first device when --deviceReader 1 asks for it; whatever the device
+  // reader does not take goes to the host reader whole, so the return value and the cloud are loadPCDFile's on every file
+  int readPCD(const std::string &path, XYZICloud &into) {
+    if (opt.device_reader) {
+      const DeviceReadResult r = loadPCDFileDevice(path, [this]() -> Device & { return writerDevice(); }, into);
+      if (r.loaded) return 0;
+      if (!r.why.empty()) std::cerr << "--deviceReader 1: " << path << ": " << r.why << "; read by the host reader" << std::endl;
+    }
+    return loadPCDFile(path, into);
   }
 
   // ---- --deviceWriter 1 ----------------------------------------------------------------------------------------------------

@@ -84,12 +84,21 @@ inline bool lzf_decompress(const unsigned char *in, size_t in_len, unsigned char
 }
 }  // namespace detail
 
-inline int loadPCDFile(const std::string &path, XYZICloud &cloud) {
-  std::ifstream in(path, std::ios::binary);
-  if (!in) return -1;
-  std::vector<PcdField> fields;
+// What the header lines say, up to and including the DATA line: the stream is left at the first byte of the data.
+struct PcdHeader {
+  std::vector<PcdField> fields;  // offsets filled in
+  size_t points = 0;             // POINTS, or WIDTH * HEIGHT when POINTS is absent or 0
+  std::string data_mode;         // "ascii" | "binary" | "binary_compressed" | anything else the file says
+  int record_bytes = 0;          // bytes of a binary record
+  int ix = -1, iy = -1, iz = -1, ii = -1;  // index of x y z intensity in `fields` (ii < 0: no intensity)
+};
+
+// 0, or -1 for a header loadPCDFile refuses: no FIELDS or DATA line, no x / y / z, or one of them not a 4-byte float
+inline int readPCDHeader(std::istream &in, PcdHeader &h) {
+  std::vector<PcdField> &fields = h.fields;
   size_t points = 0, width = 0, height = 1;
-  std::string data_mode, line;
+  std::string &data_mode = h.data_mode;
+  std::string line;
   while (std::getline(in, line)) {
     if (!line.empty() && line.back() == '\r') line.pop_back();
     if (line.empty() || line[0] == '#') continue;
@@ -122,7 +131,9 @@ inline int loadPCDFile(const std::string &path, XYZICloud &cloud) {
   }
   if (fields.empty() || data_mode.empty()) return -1;
   if (points == 0) points = width * height;
-  int off = 0, ix = -1, iy = -1, iz = -1, ii = -1;
+  h.points = points;
+  int off = 0;
+  int &ix = h.ix, &iy = h.iy, &iz = h.iz, &ii = h.ii;
   for (size_t k = 0; k < fields.size(); ++k) {
     fields[k].offset = off;
     off += fields[k].size * fields[k].count;
@@ -131,9 +142,23 @@ inline int loadPCDFile(const std::string &path, XYZICloud &cloud) {
     if (fields[k].name == "z") iz = static_cast<int>(k);
     if (fields[k].name == "intensity") ii = static_cast<int>(k);
   }
+  h.record_bytes = off;
   if (ix < 0 || iy < 0 || iz < 0) return -1;
   for (int k : {ix, iy, iz})
     if (fields[static_cast<size_t>(k)].type != 'F' || fields[static_cast<size_t>(k)].size != 4) return -1;
+  return 0;
+}
+
+inline int loadPCDFile(const std::string &path, XYZICloud &cloud) {
+  std::ifstream in(path, std::ios::binary);
+  if (!in) return -1;
+  PcdHeader head;
+  if (readPCDHeader(in, head) == -1) return -1;
+  const std::vector<PcdField> &fields = head.fields;
+  const size_t points = head.points;
+  const std::string &data_mode = head.data_mode;
+  const int off = head.record_bytes, ix = head.ix, iy = head.iy, iz = head.iz, ii = head.ii;
+  std::string line;
   cloud.resize(points);
   if (data_mode == "ascii") {
     // column index of every scalar

@@ -106,6 +106,20 @@ class Device {
     return w;
   }
 
+  // ---- device PCD reader: the x y z intensity floats of a window of PCD ASCII rows (pcp_hip.h, "device PCD reader") ----
+  struct ParsedRows {
+    int64_t rows = 0, consumed = 0, bad_row = -1;
+  };
+  // text[0, bytes): rows of `columns` tokens, x y z intensity at columns col[0..3] (col[3] = -1: none); the arrays hold
+  // max_rows floats (pcp_ascii_parse).  A bad row is not an exception: bad_row names it and the rows in front of it are in.
+  ParsedRows parseAscii(const char *text, int64_t bytes, int32_t columns, const int32_t col[4], bool final_window, int64_t max_rows,
+                        float *x, float *y, float *z, float *intensity) const {
+    ParsedRows r;
+    check(pcp_ascii_parse(ctx_, text, bytes, columns, col, final_window ? 1 : 0, max_rows, x, y, z, intensity, &r.rows, &r.consumed,
+                          &r.bad_row));
+    return r;
+  }
+
  private:
   pcp_context *ctx_ = nullptr;
 };

@@ -15,6 +15,7 @@ TARGETS = {
     "PointCloudProcessor": ["main.cpp"],
     "image_dump": ["image_dump.cpp"],
     "format_selftest": ["format_selftest.cpp"],
+    "parse_selftest": ["parse_selftest.cpp"],  # csrc/pcp_ascii_parse.hpp compiled for the host (CPU only: never a GPU job)
 }
 
 
@@ -23,7 +24,8 @@ def build(force: bool = False) -> dict:
     out = {}
     for name, srcs in TARGETS.items():
         exe = os.path.join(BIN, name)
-        deps = [os.path.join(HOST, s) for s in srcs] + [os.path.join(HOST, "pcp_shim.hpp"), os.path.join(HOST, "pcp_multi.hpp"), os.path.join(HOST, "pcd_io.hpp"), os.path.join(HOST, "image_io.hpp"),
+        deps = [os.path.join(HOST, s) for s in srcs] + [os.path.join(HOST, "pcp_shim.hpp"), os.path.join(HOST, "pcp_multi.hpp"), os.path.join(HOST, "pcd_io.hpp"), os.path.join(HOST, "image_io.hpp"), os.path.join(HOST, "pcd_device_reader.hpp"),
+                                                       os.path.join(_build.CSRC, "pcp_ascii_parse.hpp"), os.path.join(_build.CSRC, "pcp_ascii.hpp"),
                                                        os.path.join(_build.INCLUDE, "pcp_hip.h")]
         deps = [d for d in deps if os.path.exists(d)]
         stale = force or not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps)
