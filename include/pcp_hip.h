@@ -707,6 +707,15 @@ int pcp_sor_distances(pcp_context *ctx, int64_t capacity, float *out_distance);
  * pattern for the division by the configured downsample factor.  Both counts must be 0. */
 int pcp_selftest_arithmetic(pcp_context *ctx, int64_t samples, uint64_t seed, int64_t *mismatches_fp64,
                             int64_t *mismatches_fp32);
+/* diagnostic: three pieces of a (tile, keyframe) visit run in a shorter form than the reference writes (csrc/pcp_visit_forms.hpp):
+ * the distortion with its doublings folded into FMAs, the cell rule with the depth buffer on as four compares against the
+ * map size, and the distance score's fp32 square root without the compiler's range scaling.  This runs the written and the
+ * short form of each on the device and counts disagreements: `samples` pseudo-random float triples through the projection
+ * under the configured coefficients, and EVERY fp32 bit pattern as a quotient of the cell rule (configured cull size and
+ * downsample factor) and as the square root's argument.  All three counts must be 0.  short_distortion: 1 when the configured
+ * p1, p2 let the short distortion run (0: the kernels keep the written form, and the first count compares it with itself). */
+int pcp_selftest_visit_forms(pcp_context *ctx, int64_t samples, uint64_t seed, int64_t *mismatches_uv, int64_t *mismatches_cell,
+                             int64_t *mismatches_sqrt, int32_t *short_distortion);
 
 #ifdef __cplusplus
 }

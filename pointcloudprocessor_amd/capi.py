@@ -908,6 +908,14 @@ class Context:
         self._check(self.lib.pcp_selftest_arithmetic(self.h, C.c_int64(samples), C.c_uint64(seed), C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def selftest_visit_forms(self, samples: int = 1 << 24, seed: int = 1):
+        """(projection, cell rule, square root) mismatches of the visit's short forms against the written ones, and whether
+        the configured p1, p2 let the short distortion run."""
+        a, b, c, f = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int32()
+        self._check(self.lib.pcp_selftest_visit_forms(self.h, C.c_int64(samples), C.c_uint64(seed), C.byref(a), C.byref(b), C.byref(c),
+                                                      C.byref(f)))
+        return a.value, b.value, c.value, bool(f.value)
+
     def tile_masks(self) -> np.ndarray:
         """(tiles, mask_words) uint32: the tile x keyframe masks as the last depth pass left them."""
         t, w = C.c_int64(), C.c_int32()

@@ -45,8 +45,9 @@ __device__ __forceinline__ DevCamera common_camera(const DevCamera &in) {
   }
   return c;
 }
-inline bool is_common_camera(const DevCamera &c) {
-  return c.cull_mode == PCP_CULL_ZBUFFER && c.enable_zbuf == 1 && c.pretest == 1 && c.ds_fast == 1;
+inline bool is_common_camera(const pcp_context *ctx) {
+  const DevCamera &c = ctx->dcam;
+  return c.cull_mode == PCP_CULL_ZBUFFER && c.enable_zbuf == 1 && c.pretest == 1 && c.ds_fast == 1 && ctx->uv_tame;
 }
 
 struct ProjectOut {
@@ -497,12 +498,19 @@ __global__ __launch_bounds__(kBlock) void k_depth_pass(const float *__restrict__
       const int32_t f = (w << 5) + b;
       todo &= todo - 1u;
       const DevFrame &fr = frames[f];
-      const Projected p = project_point(cam, fr.w2c, px, py, pz, ((inside >> b) & 1u) == 0u, finite_sure);
-      const bool in_map = live && p.cell >= 0;
-      const bool cand = live && p.pixel >= 0 && (cam.enable_zbuf ? p.cell >= 0 : p.cell != -1);
-      if (__ballot(cand)) seen |= 1u << b;
+      const auto p = project_visit<true, kCommon>(cam, fr.w2c, px, py, pz, ((inside >> b) & 1u) == 0u, finite_sure);
+      bool in_map, cand;
+      if constexpr (kCommon) {  // the predicates themselves
+        in_map = live && p.map_ok;
+        cand = in_map && p.image_ok;
+      } else {  // project_point's sentinels
+        in_map = live && p.cell >= 0;
+        cand = live && p.pixel >= 0 && (cam.enable_zbuf ? p.cell >= 0 : p.cell != -1);
+      }
+      // (the builtin on the predicate itself: __ballot's int argument takes a lane mask through a register and a compare)
+      if (__builtin_amdgcn_ballot_w64(cand)) seen |= 1u << b;
       settle_held();
-      if (cam.enable_zbuf && __ballot(in_map)) {
+      if (cam.enable_zbuf && __builtin_amdgcn_ballot_w64(in_map)) {
         // wave-level combine: lanes of a tile hit a handful of cells, one atomic per cell suffices.  (Reading the
         // cell's current value first and skipping the square root, the combine and the atomic for points that cannot
         // lower it -- s >= m * m -- was slower, 0.79 -> 0.82 ms: some lane of the wavefront nearly always stays, so the
@@ -612,6 +620,9 @@ __global__ __launch_bounds__(kBlock) void k_colour_pass(const float *__restrict_
                                                         uint32_t *__restrict__ rgba, int32_t flags_in,
                                                         const uint32_t *__restrict__ hull_bits_in, MatchArgs mb,
                                                         [[maybe_unused]] LabelOut lab) {
+  // the visit's short forms (pcp_visit_forms.hpp) in the whole-run call of the default configuration -- one shot, the reference's
+  // round-trip match -- and its label form; the staged, identity and radius forms keep project_point and sqrtf as they were
+  constexpr bool kShort = kCommon && kOneShot && kMatch == 2;
   DevCamera cam = common_camera<kCommon>(cam_in);
   if constexpr (kMatch == 1) cam.match_mode = PCP_MATCH_IDENTITY;
   if constexpr (kMatch == 2 || kMatch == 3) cam.match_mode = PCP_MATCH_ROUNDTRIP;
@@ -651,9 +662,12 @@ __global__ __launch_bounds__(kBlock) void k_colour_pass(const float *__restrict_
       todo &= todo - 1u;
       const DevFrame &fr = frames[f];
       // the refined masks only keep pairs with a candidate lane: the fp32 rejection test cannot skip the wavefront
-      const Projected p = project_point<false>(cam, fr.w2c, px, py, pz, true, finite_sure);
-      const bool cand = live && p.pixel >= 0 && (cam.enable_zbuf ? p.cell >= 0 : p.cell != -1) &&
-                        ((hull_word >> (f & 31)) & 1u);
+      const auto p = project_visit<false, kShort>(cam, fr.w2c, px, py, pz, true, finite_sure);
+      bool cand;
+      if constexpr (kShort)  // the predicates themselves
+        cand = live && p.image_ok && p.map_ok && ((hull_word >> (f & 31)) & 1u);
+      else  // project_point's sentinels
+        cand = live && p.pixel >= 0 && (cam.enable_zbuf ? p.cell >= 0 : p.cell != -1) && ((hull_word >> (f & 31)) & 1u);
       if (cand) {
         // (cells and image_px are below 2^31 -- a cell / pixel index is an int32 --, f is not negative: a 32 x 32-bit product)
         const uint32_t dbits = cam.enable_zbuf ? depth[static_cast<uint64_t>(static_cast<uint32_t>(f)) * static_cast<uint32_t>(cells) + static_cast<uint32_t>(p.cell)] : 0u;
@@ -674,7 +688,7 @@ __global__ __launch_bounds__(kBlock) void k_colour_pass(const float *__restrict_
         if (keep) {
           // texel = B | G<<8 | R<<16 | mask<<24; its low 24 bits are 0x00RRGGBB (PointCloudProcessor.cpp:760-762)
           const uint32_t texel = images[static_cast<uint64_t>(static_cast<uint32_t>(f)) * static_cast<uint32_t>(image_px) + static_cast<uint32_t>(p.pixel)];
-          t.insert(final_score(sx, sy, sz, fr.px, fr.py, fr.pz), kLabel ? texel : texel & 0xffffffu, f);
+          t.insert(final_score<kShort>(sx, sy, sz, fr.px, fr.py, fr.pz), kLabel ? texel : texel & 0xffffffu, f);
         }
       }
     }
@@ -883,6 +897,61 @@ __global__ __launch_bounds__(kBlock) void k_selftest_div32(DevCamera cam, unsign
     }
   }
   if (wrong) atomicAdd(bad, static_cast<unsigned long long>(wrong));
+}
+
+// ---------------------------------------------------------------------------
+// visit-form self-test (pcp_selftest_visit_forms): the written and the short forms of pcp_visit_forms.hpp side by side
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ bool same_bits_f64(double a, double b) {
+  return (a != a && b != b) || __double_as_longlong(a) == __double_as_longlong(b);
+}
+// the projection with the short distortion (what the batched kernels of the common configuration run; `tame` = 0: what they
+// run under coefficients that are not tame, the written form) against the written form, on the float triples of k_selftest_div64
+__global__ __launch_bounds__(kBlock) void k_selftest_uv(DevCamera cam, int32_t tame, int64_t samples, uint64_t seed,
+                                                        unsigned long long *__restrict__ bad) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= samples) return;
+  const uint64_t a = mix64(seed ^ static_cast<uint64_t>(i) * 3u), b = mix64(a);
+  uint32_t bx = static_cast<uint32_t>(a), by = static_cast<uint32_t>(a >> 32), bz = static_cast<uint32_t>(b);
+  const uint32_t mode = static_cast<uint32_t>(b >> 32) & 3u;
+  if (mode != 0u) {
+    const uint32_t span = mode == 1u ? 12u : 40u;
+    bx = (bx & 0x807fffffu) | ((127u - span / 2u + (bx >> 23) % span) << 23);
+    by = (by & 0x807fffffu) | ((127u - span / 2u + (by >> 23) % span) << 23);
+    bz = (bz & 0x807fffffu) | ((127u - span / 2u + (bz >> 23) % span) << 23);
+  }
+  const float xc = __uint_as_float(bx), yc = __uint_as_float(by), zc = fabsf(__uint_as_float(bz));
+  if (!(zc > 0.0f)) return;  // the projection is only entered with z > 0
+  double u0, v0, u1, v1;
+  if (tame)
+    project_uv<true, true>(cam, xc, yc, zc, u0, v0);
+  else
+    project_uv<true, false>(cam, xc, yc, zc, u0, v0);
+  project_uv<true, false>(cam, xc, yc, zc, u1, v1);
+  if (!same_bits_f64(u0, u1) || !same_bits_f64(v0, v1)) atomicAdd(bad, 1ull);
+}
+
+// all 2^32 bit patterns: as a quotient along x, along y and along both (the other axis at cell 0) for the cell rule; as the
+// argument of the distance score's square root
+__global__ __launch_bounds__(kBlock) void k_selftest_cell_sqrt(DevCamera cam, unsigned long long *__restrict__ bad_cell,
+                                                               unsigned long long *__restrict__ bad_sqrt) {
+  const uint32_t lane = blockIdx.x * kBlock + threadIdx.x;
+  uint32_t wrong_cell = 0u, wrong_sqrt = 0u;
+  for (uint32_t k = 0; k < 256u; ++k) {
+    const float q = __uint_as_float((k << 24) | lane);
+    const float qx[3] = {q, 0.5f, q}, qy[3] = {0.5f, q, q};
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+      const int32_t old_cell = vf::map_cell_written(qx[t], qy[t], cam.cull_wf, cam.cull_hf, cam.mw, cam.mh);
+      int32_t cell;
+      const bool ok = vf::map_cell_short(qx[t], qy[t], vf::map_bound(cam.mw), vf::map_bound(cam.mh), cam.mw, cell);
+      if ((ok ? cell : -1) != old_cell) ++wrong_cell;
+    }
+    const float r0 = sqrt_rn(q), r1 = sqrtf(q);
+    if (!((r0 != r0 && r1 != r1) || __float_as_uint(r0) == __float_as_uint(r1))) ++wrong_sqrt;
+  }
+  if (wrong_cell) atomicAdd(bad_cell, static_cast<unsigned long long>(wrong_cell));
+  if (wrong_sqrt) atomicAdd(bad_sqrt, static_cast<unsigned long long>(wrong_sqrt));
 }
 
 // ---------------------------------------------------------------------------
@@ -1718,7 +1787,7 @@ int pcp_project_frame(pcp_context *ctx, int32_t frame, int32_t *out_cell, int32_
   o.zc = out_xyz_cam ? ctx->s_cam.p + 2 * plane : nullptr;
   {
     LaunchTimer t(ctx, PCP_K_PROJECT);
-    hipLaunchKernelGGL(is_common_camera(ctx->dcam) ? k_project_frame<true> : k_project_frame<false>, dim3(blocks_for(div_up(n, 4))), dim3(kBlock), 0, ctx->stream, ctx->sxyz.p,
+    hipLaunchKernelGGL(is_common_camera(ctx) ? k_project_frame<true> : k_project_frame<false>, dim3(blocks_for(div_up(n, 4))), dim3(kBlock), 0, ctx->stream, ctx->sxyz.p,
                        ctx->sxyz.p + plane, ctx->sxyz.p + 2 * plane, n, ctx->dcam,
                        ctx->hframes[static_cast<size_t>(frame)], o);
     PCP_HIP_TRY(ctx, hipGetLastError());
@@ -1905,7 +1974,7 @@ int pcp_depth_pass(pcp_context *ctx, int32_t frame_begin, int32_t frame_end) {
     }
     {
       LaunchTimer t(ctx, PCP_K_DEPTH);
-      hipLaunchKernelGGL(is_common_camera(ctx->dcam) ? k_depth_pass<true> : k_depth_pass<false>,
+      hipLaunchKernelGGL(is_common_camera(ctx) ? k_depth_pass<true> : k_depth_pass<false>,
                          dim3(static_cast<uint32_t>(ctx->n_tiles)), dim3(64), 0, ctx->stream, ctx->sxyz.p,
                          ctx->sxyz.p + plane, ctx->sxyz.p + 2 * plane, ctx->n, ctx->dcam, ctx->frames.p, frame_begin,
                          frame_end, ctx->depth_sq.p, cells, frame_begin, ctx->tile_mask.p, ctx->tile_inside.p,
@@ -2077,7 +2146,7 @@ static int colour_pass_impl(pcp_context *ctx, int32_t frame_begin, int32_t frame
     // the colour pass keeps the cloud order (256-thread workgroups, XCD-chunked): it does not end in a tail of heavy
     // tiles (longest-first order: no gain at 1920x1080), and its texel gathers want neighbouring tiles on the same L2
     // (longest-first order at 4096x3000: 1.96 -> 2.18 ms)
-    const bool common = is_common_camera(ctx->dcam) && ctx->cull.cull_mode != PCP_CULL_HPR;
+    const bool common = is_common_camera(ctx) && ctx->cull.cull_mode != PCP_CULL_HPR;
     const bool label = ctx->label_fusion;
     const LabelOut lab{label ? ctx->labels.p : nullptr};
     auto kernel = label ? colour_pass_kernel<true>(common, ctx->dcam.match_mode, flags)
@@ -2368,6 +2437,29 @@ int pcp_selftest_arithmetic(pcp_context *ctx, int64_t samples, uint64_t seed, in
   PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (mismatches_fp64) *mismatches_fp64 = static_cast<int64_t>(h[0]);
   if (mismatches_fp32) *mismatches_fp32 = static_cast<int64_t>(h[1]);
+  return PCP_OK;
+}
+
+int pcp_selftest_visit_forms(pcp_context *ctx, int64_t samples, uint64_t seed, int64_t *mismatches_uv, int64_t *mismatches_cell,
+                             int64_t *mismatches_sqrt, int32_t *short_distortion) {
+  if (!ctx) return PCP_ERR_INVALID;
+  if (!ctx->have_camera) return set_error(ctx, PCP_ERR_STATE, "pcp_selftest_visit_forms: pcp_set_camera has not been called");
+  PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (samples < 0) return set_error(ctx, PCP_ERR_INVALID, "pcp_selftest_visit_forms: negative sample count");
+  PCP_HIP_TRY(ctx, ctx->s_counter.ensure(4));
+  unsigned long long *bad = ctx->s_counter.p;
+  PCP_HIP_TRY(ctx, hipMemsetAsync(bad, 0, 32, ctx->stream));
+  if (samples > 0)
+    hipLaunchKernelGGL(k_selftest_uv, dim3(blocks_for(samples)), dim3(kBlock), 0, ctx->stream, ctx->dcam, ctx->uv_tame ? 1 : 0, samples, seed, bad);
+  hipLaunchKernelGGL(k_selftest_cell_sqrt, dim3((1u << 24) / kBlock), dim3(kBlock), 0, ctx->stream, ctx->dcam, bad + 1, bad + 2);
+  PCP_HIP_TRY(ctx, hipGetLastError());
+  unsigned long long h[3] = {0, 0, 0};
+  PCP_HIP_TRY(ctx, hipMemcpyAsync(h, bad, 24, hipMemcpyDeviceToHost, ctx->stream));
+  PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (mismatches_uv) *mismatches_uv = static_cast<int64_t>(h[0]);
+  if (mismatches_cell) *mismatches_cell = static_cast<int64_t>(h[1]);
+  if (mismatches_sqrt) *mismatches_sqrt = static_cast<int64_t>(h[2]);
+  if (short_distortion) *short_distortion = ctx->uv_tame ? 1 : 0;
   return PCP_OK;
 }
 

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "pcp_internal.hpp"
+#include "pcp_visit_forms.hpp"
 #include "pcp_scan.hpp"
 
 namespace pcp {
@@ -887,6 +888,8 @@ int pcp_set_camera(pcp_context *ctx, const pcp_camera *cam, const pcp_cull_param
   d.cull_hf = static_cast<float>(cam->cull_height);
   d.mw = cam->cull_width / cp.downsample_factor;
   d.mh = cam->cull_height / cp.downsample_factor;
+  ctx->uv_tame = vf::distortion_is_tame(cam->p1, cam->p2);
+  if (const char *e = std::getenv("PCP_DISABLE_FAST_EXACT")) ctx->uv_tame = (e[0] == '1') ? false : ctx->uv_tame;
   // the kernels of the colour path only know the candidate filter; the hull is a stage of its own (pcp_hpr.hip)
   d.cull_mode = cp.cull_mode == PCP_CULL_HPR ? PCP_CULL_HPR_CANDIDATES : cp.cull_mode;
   d.match_mode = cp.match_mode;

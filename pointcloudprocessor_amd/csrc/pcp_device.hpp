@@ -13,6 +13,7 @@
 #include <cstdint>
 
 #include "pcp_internal.hpp"
+#include "pcp_visit_forms.hpp"
 
 namespace pcp {
 
@@ -56,7 +57,9 @@ __device__ __forceinline__ void divide_xy_by_z(float xc, float yc, float zc, dou
 
 // A3: PinholeProjection::operator() + distort, pinhole.hpp:13-51 (duplicate
 // PointCloudProcessor.hpp:100-123), fp64, left-to-right as written.
-template <bool kShortDiv = true>
+// kShortUV: the distortion in the short form of pcp_visit_forms.hpp (three doublings folded into FMAs): the same bits for tame
+// p1, p2 (pcp_context::uv_tame, a condition of the common configuration, whose batched kernels are the ones that ask for it)
+template <bool kShortDiv = true, bool kShortUV = false>
 __device__ __forceinline__ void project_uv(const DevCamera &c, float xc, float yc, float zc, double &u, double &v,
                                            bool finite_sure = false) {
   double xn, yn;
@@ -69,17 +72,22 @@ __device__ __forceinline__ void project_uv(const DevCamera &c, float xc, float y
     xn = static_cast<double>(xc) / static_cast<double>(zc);
     yn = static_cast<double>(yc) / static_cast<double>(zc);
   }
-  const double x2 = xn * xn;
-  const double y2 = yn * yn;
-  const double r2 = x2 + y2;
-  const double r4 = r2 * r2;
-  const double r6 = r2 * r4;
-  const double rc = ((1.0 + c.k1 * r2) + c.k2 * r4) + c.k3 * r6;
-  const double t1 = (2.0 * xn) * yn;
-  const double t2 = r2 + 2.0 * x2;
-  const double t3 = r2 + 2.0 * y2;
-  const double xd = (rc * xn + c.p1 * t1) + c.p2 * t2;
-  const double yd = (rc * yn + c.p1 * t3) + c.p2 * t1;
+  double xd, yd;
+  if constexpr (kShortUV) {
+    vf::distort_short(vf::Distortion{c.k1, c.k2, c.k3, c.p1, c.p2}, xn, yn, xd, yd);
+  } else {  // (vf::distort_written, in place)
+    const double x2 = xn * xn;
+    const double y2 = yn * yn;
+    const double r2 = x2 + y2;
+    const double r4 = r2 * r2;
+    const double r6 = r2 * r4;
+    const double rc = ((1.0 + c.k1 * r2) + c.k2 * r4) + c.k3 * r6;
+    const double t1 = (2.0 * xn) * yn;
+    const double t2 = r2 + 2.0 * x2;
+    const double t3 = r2 + 2.0 * y2;
+    xd = (rc * xn + c.p1 * t1) + c.p2 * t2;
+    yd = (rc * yn + c.p1 * t3) + c.p2 * t1;
+  }
   u = c.fx * xd + c.cx;
   v = c.fy * yd + c.cy;
 }
@@ -208,6 +216,51 @@ __device__ __forceinline__ Projected project_point(const DevCamera &c, const flo
   return p;
 }
 
+// project_point for the batched passes of the common configuration (z-buffer cull with its depth buffer on, tame p1 / p2; the
+// depth pass and the whole-run colour pass ask for it): the
+// short forms of pcp_visit_forms.hpp, and the two truncation rules as predicates that never become -1 sentinels for the caller
+// to compare with -1 again.  cell / pixel are only meaningful under map_ok / image_ok.
+struct ShortVisit {
+  float xc, yc, zc;
+  int32_t cell, pixel;
+  bool map_ok, image_ok;
+};
+template <bool kPretest>
+__device__ __forceinline__ ShortVisit project_point_short(const DevCamera &c, const float *__restrict__ m, float x, float y, float z,
+                                                          bool pretest_here = true, bool finite_sure = false) {
+  ShortVisit p;
+  xform(m, x, y, z, p.xc, p.yc, p.zc);
+  p.cell = 0;
+  p.pixel = 0;
+  p.map_ok = p.image_ok = false;
+  // z test (B6) and rejection test per lane, the projection for the whole wavefront if any lane needs it: a wave-uniform branch
+  // lets the predicates stay lane masks (across a divergent one they would go through a register and a compare again); the
+  // lanes that fail compute values nobody reads.  kPretest = false (the colour pass over the refined masks: some lane of every
+  // visit is a candidate) has no branch at all.
+  const bool go = p.zc > 0.0f && !(kPretest && pretest_here && c.pretest && surely_rejected(c, p.xc, p.yc, p.zc));
+  if (!kPretest || __builtin_amdgcn_ballot_w64(go)) {
+    double u, v;
+    project_uv<true, true>(c, p.xc, p.yc, p.zc, u, v, finite_sure);
+    // (the map's bounds as fp32 are the same for every visit: the conversions leave the loops; `&`, not `&&`: comparisons
+    // have no side effects, and a short circuit per lane is an exec-mask branch)
+    const bool cell_ok = vf::map_cell_short(div_by_ds(c, static_cast<float>(u)), div_by_ds(c, static_cast<float>(v)), vf::map_bound(c.mw),
+                                            vf::map_bound(c.mh), c.mw, p.cell);
+    p.map_ok = go & cell_ok;
+    p.image_ok = go & (u > -1.0) & (u < c.img_wd) & (v > -1.0) & (v < c.img_hd);  // colour_pixel
+    p.pixel = p.image_ok ? static_cast<int32_t>(v) * c.img_w + static_cast<int32_t>(u) : 0;
+  }
+  return p;
+}
+// kShort ? project_point_short : project_point
+template <bool kPretest, bool kShort>
+__device__ __forceinline__ auto project_visit(const DevCamera &c, const float *__restrict__ m, float x, float y, float z,
+                                              bool pretest_here = true, bool finite_sure = false) {
+  if constexpr (kShort)
+    return project_point_short<kPretest>(c, m, x, y, z, pretest_here, finite_sure);
+  else
+    return project_point<kPretest>(c, m, x, y, z, pretest_here, finite_sure);
+}
+
 // A4 keep rule (view_culling.cpp:135-171).  depth = this keyframe's map.
 __device__ __forceinline__ bool keep_rule(const DevCamera &c, const Projected &p, const uint32_t *__restrict__ depth) {
   if (!c.enable_zbuf) return p.cell != -1;
@@ -261,6 +314,14 @@ __device__ __forceinline__ bool roundtrip_sample_moved(const DevCamera &c, const
   return true;
 }
 
+// RN(sqrt(x)), fp32: the hardware estimate (1 ulp) and the neighbour selection of pcp_visit_forms.hpp for 2^-96 <= x <= FLT_MAX,
+// where the compiler's sqrtf does the same between a range scaling and a class test that have nothing to do there; plain
+// sqrtf for every other x (0, subnormal and tiny, negative, inf, NaN).  pcp_selftest_visit_forms() compares all 2^32 patterns.
+__device__ __forceinline__ float sqrt_rn(float x) {
+  if (vf::sqrt_in_window(x)) return vf::sqrt_from_estimate(x, __builtin_amdgcn_sqrtf(x));
+  return sqrtf(x);
+}
+
 // A6 scores: computeOrientationScore hpp:205-220 (B4 reproduced),
 // computeDistanceScore hpp:222-236, final cpp:588; (xc, yc, zc) is p_c (PCP_MATCH_IDENTITY) or p_c' (PCP_MATCH_ROUNDTRIP).
 //
@@ -270,6 +331,7 @@ __device__ __forceinline__ bool roundtrip_sample_moved(const DevCamera &c, const
 // the reference's cosA within 2.3e-16; the two values of (cosA + 1) / 2 differ by less than 1e-15.  When t - 4e-15 and
 // t + 4e-15 round to the same fp32 number the reference's value rounds to it too; otherwise (1.3e-7 of the samples) and for
 // magnitudes outside [2^-100, 2^100] the square root and the division are taken as written.
+template <bool kShortSqrt = false>
 __device__ __forceinline__ float final_score(float xc, float yc, float zc, double px, double py, double pz) {
   const double dx = static_cast<double>(xc) - px;
   const double dy = static_cast<double>(yc) - py;
@@ -288,7 +350,8 @@ __device__ __forceinline__ float final_score(float xc, float yc, float zc, doubl
     o = static_cast<float>((cosA + 1.0) / 2.0);
   }
   o = 0.2f + 0.8f * o;
-  const float dist = sqrtf((xc * xc + yc * yc) + zc * zc);
+  const float d2 = (xc * xc + yc * yc) + zc * zc;
+  const float dist = kShortSqrt ? sqrt_rn(d2) : sqrtf(d2);
   const float diff = fabsf(dist - 2.0f);
   float nd = diff / 2.0f;
   nd = nd < 1.0f ? nd : 1.0f;

@@ -177,6 +177,8 @@ struct pcp_context {
 
   // configuration
   bool have_camera = false;
+  bool uv_tame = false;  // p1, p2 are in the range the short distortion form is proven for (pcp_visit_forms.hpp): a condition
+                         // of the common configuration, whose batched kernels run that form
   pcp_camera camera{};
   pcp_cull_params cull{};
   pcp::DevCamera dcam{};

@@ -16,6 +16,7 @@ TARGETS = {
     "image_dump": ["image_dump.cpp"],
     "format_selftest": ["format_selftest.cpp"],
     "parse_selftest": ["parse_selftest.cpp"],  # csrc/pcp_ascii_parse.hpp compiled for the host (CPU only: never a GPU job)
+    "visit_forms_selftest": ["visit_forms_selftest.cpp"],  # csrc/pcp_visit_forms.hpp compiled for the host (CPU only)
 }
 
 
@@ -25,7 +26,7 @@ def build(force: bool = False) -> dict:
     for name, srcs in TARGETS.items():
         exe = os.path.join(BIN, name)
         deps = [os.path.join(HOST, s) for s in srcs] + [os.path.join(HOST, "pcp_shim.hpp"), os.path.join(HOST, "pcp_multi.hpp"), os.path.join(HOST, "pcd_io.hpp"), os.path.join(HOST, "image_io.hpp"), os.path.join(HOST, "pcd_device_reader.hpp"),
-                                                       os.path.join(_build.CSRC, "pcp_ascii_parse.hpp"), os.path.join(_build.CSRC, "pcp_ascii.hpp"),
+                                                       os.path.join(_build.CSRC, "pcp_ascii_parse.hpp"), os.path.join(_build.CSRC, "pcp_ascii.hpp"), os.path.join(_build.CSRC, "pcp_visit_forms.hpp"),
                                                        os.path.join(_build.INCLUDE, "pcp_hip.h")]
         deps = [d for d in deps if os.path.exists(d)]
         stale = force or not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps)
@@ -35,7 +36,8 @@ def build(force: bool = False) -> dict:
             multi = ["-D__HIP_PLATFORM_AMD__", "-isystem", os.path.join(ROCM, "include")] if name == "PointCloudProcessor" else []
             multi_libs = ["-L", os.path.join(ROCM, "lib"), "-lrccl", "-lamdhip64", "-Wl,-rpath," + os.path.join(ROCM, "lib")] \
                 if name == "PointCloudProcessor" else []
-            cmd = ["g++", "-std=c++17", "-O2", "-pthread", "-Wall", "-Wextra"] + extra + multi + ["-I", _build.INCLUDE, "-I", HOST] + [
+            # (-ffp-contract=off: the visit forms are checked operation by operation, as the device library is built)
+            cmd = ["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-Wall", "-Wextra"] + extra + multi + ["-I", _build.INCLUDE, "-I", HOST] + [
                 os.path.join(HOST, s) for s in srcs] + ["-L", _build.LIB_DIR, "-lpcp_hip"] + multi_libs + [
                                                         "-lz", "-Wl,-rpath,$ORIGIN/../../lib", "-o", exe]
             proc = subprocess.run(cmd, capture_output=True, text=True)
