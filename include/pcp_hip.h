@@ -55,7 +55,9 @@ extern "C" {
                                 entry points added, no layout changed: pcp_ascii_row_bound, pcp_ascii_rows_host, pcp_ascii_rows,
                                 pcp_colour_compact_ascii, pcp_mls_fetch_ascii (the device PCD writer; nothing runs unless called);
                                 entry points added, no layout changed: pcp_ascii_parse_host, pcp_ascii_parse, pcp_ascii_parse_limit
-                                (the device PCD reader; nothing runs unless called) */
+                                (the device PCD reader; nothing runs unless called);
+                                entry points added, no layout changed: pcp_view_pair_stats / _counters, pcp_exposure_gains,
+                                pcp_set_frame_gains (per-keyframe exposure gains; off by default) */
 
 #define PCP_OK 0
 #define PCP_ERR_INVALID (-1) /* bad argument */
@@ -417,6 +419,43 @@ int pcp_colour_labels(pcp_context *ctx, uint8_t *out_label, uint8_t *out_hits, u
  * valid until the next colour result begins (a later pcp_colorize / pcp_colorize_from_depth / pcp_colour_finalise
  * overwrites or invalidates it), so consume it on the context's stream before that call. */
 int pcp_colour_labels_device(pcp_context *ctx, void **device_ptr, int64_t *n_words);
+
+/* Exposure gains ("Exposure gains", EG1-EG5): one brightness gain per keyframe from the map points that two
+ * keyframes both colour, so that a point's colour no longer jumps where its top-5 list changes by one view (the reference
+ * has one hand-set global brightness, PointCloudProcessor.cpp:726-729, and notes the pairwise idea at RGBCloud.hpp:20-25).
+ * Off by default; with it unused every output and every launched kernel is what it was.
+ *
+ * pcp_view_pair_stats: over every point's list (s_k, c_k, f_k), k < M = min(count, 5), and every ordered pair of distinct
+ * slots a != b with f_a != f_b whose views are both usable -- luma Y = (77 R + 150 G + 29 B + 128) >> 8 of the view's colour
+ * word within [8, 247] --:  n[f_a][f_b] += 1,  sum[f_a][f_b] += Y_a.  Exact integers, independent of the order of
+ * accumulation; n is symmetric.  out_n, out_sum: F x F uint64 each, row-major, HOST memory, either nullable.  Valid while a
+ * top-5 accumulation is live (after pcp_colour_pass, before pcp_colour_reset / a one-shot call / an upload), else
+ * PCP_ERR_STATE; more than 4096 keyframes: PCP_ERR_RANGE.  On an index shard (PCP_DEPTH_BATCHED) the matrices are the
+ * shard's own points': they are ADDITIVE over shards (and over the chunks of a streamed cloud); the caller sums them.
+ * PCP_EXPOSURE_TABLE_LOG2=k (0..10) shrinks the kernel's per-workgroup table to 2^k slots (tests of its overflow path).
+ * pcp_view_pair_stats_counters: of the latest call -- out[0] 64-bit adds to global memory issued when the workgroups'
+ * tables were flushed, [1] adds issued directly because a table was full, [2] wavefront-level partial sums, [3]
+ * workgroups, [4] table slots per workgroup. */
+int pcp_view_pair_stats(pcp_context *ctx, uint64_t *out_n, uint64_t *out_sum);
+int pcp_view_pair_stats_counters(pcp_context *ctx, int64_t out[5]);
+/* Host only, no context, no GPU: the gains of Brown & Lowe's gain compensation from the pair matrices.  Keyframes without
+ * a pair get exactly 1.0; the others minimise
+ *   sum_i sum_j n_ij [ (g_i I_ij - g_j I_ji)^2 / sigma_n^2 + (1 - g_i)^2 / sigma_g^2 ],   I_ij = sum_ij / n_ij  (fp64),
+ * a symmetric positive definite linear system solved by a dense fp64 Cholesky in a fixed order (deterministic; O(F^3)).
+ * sigma_n in luma levels (10 is the usual choice), sigma_g the prior's width (0.1).  The diagonal of the matrices is not read.
+ * PCP_ERR_INVALID: n_frames < 1, a NULL argument, a sigma that is not finite and positive, n not symmetric, or
+ * sum_ij > 255 n_ij.  PCP_ERR_RANGE: n_frames > 4096.  The message is at pcp_last_error(NULL). */
+int pcp_exposure_gains(int32_t n_frames, const uint64_t *n, const uint64_t *sum, double sigma_n, double sigma_g, double *out_gains);
+/* gains == NULL: off.  Otherwise n must be the keyframe count and every gain finite and in (0, 16], else PCP_ERR_INVALID
+ * and the setting is unchanged.  pcp_set_frames clears the gains.  While set, pcp_colour_finalise replaces every listed
+ * view's channel c by  c' = min((int)(fl32(fl32(c) * (float)g_f) + 0.5f), 255)  (fp32, no fusion, the cast truncates) and
+ * then runs its own arithmetic on c' (fp32 sums in list order, division, truncation, has = (r | g | b) != 0): out_rgb,
+ * out_has, the packed result and everything that reads it (pcp_colour_compact*, pcp_colour_smooth_local,
+ * pcp_download_result_packed*).  All gains 1.0 give the bits of a run without gains.  out_top_rgb / out_top_score /
+ * out_top_frame / out_count and the fused labels stay raw.  pcp_colorize and pcp_colorize_from_depth return PCP_ERR_STATE
+ * while gains are set: their kernels keep the lists in registers; use pcp_colour_reset / pcp_colour_pass /
+ * pcp_colour_finalise. */
+int pcp_set_frame_gains(pcp_context *ctx, const double *gains, int32_t n);
 
 /* PointCloudProcessor::smoothColorsWithLocalRegion(rgbCloud, radius), PointCloudProcessor.cpp:634-703, whose call
  * smoothColorsWithLocalRegion(rgbCloud, 0.1) is commented out at :597 between smoothColors (:596) and

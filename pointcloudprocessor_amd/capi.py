@@ -248,6 +248,21 @@ def ascii_parse_host(text, columns: int, col, final: bool = True, max_rows: int 
     return _ascii_parse_call(L.pcp_ascii_parse_host, check, text, columns, col, final, max_rows, out)
 
 
+def exposure_gains(n, sum, sigma_n: float = 10.0, sigma_g: float = 0.1) -> np.ndarray:
+    """One exposure gain per keyframe from the pair matrices of Context.view_pair_stats (pcp_exposure_gains: host only, no
+    context, no GPU).  n, sum: (F, F) uint64.  Keyframes without a pair get exactly 1.0."""
+    L = load()
+    n = np.ascontiguousarray(n, np.uint64)
+    sum = np.ascontiguousarray(sum, np.uint64)
+    if n.ndim != 2 or n.shape[0] != n.shape[1] or sum.shape != n.shape:
+        raise ValueError(f"exposure_gains: two square matrices of one size expected, got {n.shape} and {sum.shape}")
+    out = np.empty(n.shape[0], np.float64)
+    rc = L.pcp_exposure_gains(C.c_int32(n.shape[0]), _ptr(n), _ptr(sum), C.c_double(sigma_n), C.c_double(sigma_g), _ptr(out))
+    if rc != PCP_OK:
+        raise PcpError(rc, L.pcp_last_error(None).decode())
+    return out
+
+
 def default_camera() -> Camera:
     cam = Camera()
     load().pcp_default_camera(C.byref(cam))
@@ -654,6 +669,32 @@ class Context:
         n = C.c_int64()
         self._check(self.lib.pcp_colour_labels_device(self.h, C.byref(p), C.byref(n)))
         return p.value, n.value
+
+    # -- exposure gains ("Exposure gains") -------------------------
+    def view_pair_stats(self):
+        """(n, sum): (F, F) uint64 each -- over the live top-5 lists, the pairs of usable views of one point from two
+        keyframes and the luma sums of the row keyframe's side (pcp_view_pair_stats).  Additive over index shards."""
+        F = self.n_frames
+        n = np.zeros((F, F), np.uint64)
+        s = np.zeros((F, F), np.uint64)
+        self._check(self.lib.pcp_view_pair_stats(self.h, _ptr(n), _ptr(s)))
+        return n, s
+
+    def view_pair_stats_counters(self) -> dict:
+        """What the latest view_pair_stats() issued (pcp_view_pair_stats_counters)."""
+        out = np.zeros(5, np.int64)
+        self._check(self.lib.pcp_view_pair_stats_counters(self.h, _ptr(out)))
+        keys = ("flush_adds", "direct_adds", "wave_partials", "workgroups", "table_slots")
+        return {k: int(v) for k, v in zip(keys, out)}
+
+    def set_frame_gains(self, gains):
+        """One gain per keyframe, applied per listed view by colour_finalise (pcp_set_frame_gains); None switches it off.
+        colorize() / colorize_from_depth() raise PCP_ERR_STATE while gains are set; set_frames clears them."""
+        if gains is None:
+            self._check(self.lib.pcp_set_frame_gains(self.h, None, C.c_int32(0)))
+            return
+        g = np.ascontiguousarray(gains, np.float64).reshape(-1)
+        self._check(self.lib.pcp_set_frame_gains(self.h, _ptr(g), C.c_int32(g.size)))
 
     def colour_smooth_local(self, radius: float) -> int:
         """smoothColorsWithLocalRegion (PointCloudProcessor.cpp:634-703) in place on the colour result; returns the number

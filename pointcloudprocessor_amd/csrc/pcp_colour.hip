@@ -2222,6 +2222,9 @@ int pcp_colour_finalise(pcp_context *ctx, uint8_t *out_rgb, uint8_t *out_has, in
     PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->top_rgb.p, 0, kTopM * sn * 4, ctx->stream));
     PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->top_frame.p, 0xff, kTopM * sn * 4, ctx->stream));
     PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->view_count.p, 0, sn * 4, ctx->stream));
+  } else if (n > 0 && ctx->gains_set) {
+    // exposure gains (pcp_set_frame_gains): a kernel of its own (pcp_exposure.hip); this one keeps its instruction stream
+    if ((rc = finalise_gained(ctx, result)) != PCP_OK) return rc;
   } else if (n > 0) {
     TopState st{ctx->top_score.p, ctx->top_rgb.p, ctx->top_frame.p, ctx->view_count.p};
     LaunchTimer t(ctx, PCP_K_COLOUR);
@@ -2263,9 +2266,17 @@ int pcp_colour_finalise(pcp_context *ctx, uint8_t *out_rgb, uint8_t *out_has, in
   return PCP_OK;
 }
 
+// the one-shot kernels keep their lists in registers: they know nothing of exposure gains
+static int refuse_gains(pcp_context *ctx, const char *who) {
+  if (!ctx->gains_set) return PCP_OK;
+  return set_error(ctx, PCP_ERR_STATE, "%s: exposure gains are set (pcp_set_frame_gains): they apply to pcp_colour_reset / "
+                   "pcp_colour_pass / pcp_colour_finalise; clear them with pcp_set_frame_gains(NULL) for the one-shot call", who);
+}
+
 int pcp_colorize(pcp_context *ctx, uint8_t *out_rgb, uint8_t *out_has) {
   int rc = check_ready(ctx, "pcp_colorize", true);
   if (rc != PCP_OK) return rc;
+  if ((rc = refuse_gains(ctx, "pcp_colorize")) != PCP_OK) return rc;
   if ((rc = check_masks(ctx, 0, ctx->n_frames)) != PCP_OK) return rc;  // (before the depth pass)
   pcp_colour_reset(ctx);
   if ((rc = pcp_depth_pass(ctx, 0, ctx->n_frames)) != PCP_OK) return rc;
@@ -2280,6 +2291,7 @@ int pcp_colorize(pcp_context *ctx, uint8_t *out_rgb, uint8_t *out_has) {
 int pcp_colorize_from_depth(pcp_context *ctx, uint8_t *out_rgb, uint8_t *out_has) {
   int rc = check_ready(ctx, "pcp_colorize_from_depth", true);
   if (rc != PCP_OK) return rc;
+  if ((rc = refuse_gains(ctx, "pcp_colorize_from_depth")) != PCP_OK) return rc;
   pcp_colour_reset(ctx);
   uint32_t *result = nullptr;
   if ((rc = begin_result(ctx, &result)) != PCP_OK) return rc;

@@ -619,7 +619,7 @@ int pcp_create(int32_t device, pcp_context **out) {
     hipFuncAttributes a;
     const hipError_t pl[] = {hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_up_bbox)), preload_colour(), preload_mls(),
                              preload_nid(), preload_hpr(), preload_colour_smooth(), preload_match(),
-                             preload_jpeg(), preload_stream_colour(), preload_ascii(), preload_ascii_parse()};
+                             preload_jpeg(), preload_stream_colour(), preload_ascii(), preload_ascii_parse(), preload_exposure()};
     for (hipError_t x : pl)
       if (x != hipSuccess && e == hipSuccess) e = x;
   }
@@ -715,6 +715,8 @@ void pcp_destroy(pcp_context *ctx) {
   ctx->rgba2[0].release();
   ctx->rgba2[1].release();
   ctx->labels.release();
+  ctx->gains_dev.release();
+  ctx->pair_stats.release();
   match_table_release(ctx);
   ctx->match_moved.release();
   for (int k = 0; k < 2; ++k) {
@@ -1065,6 +1067,7 @@ int pcp_set_frames(pcp_context *ctx, const pcp_pose *poses, int32_t n_frames, co
   ctx->depth_accum.release();  // one map per keyframe of the set that is being replaced
   ctx->depth_accum_live = false;
   ctx->match_live = false;  // PCP_MATCH_RADIUS: E (and with it R_c) depends on the keyframes
+  ctx->gains_set = false;   // exposure gains: one per keyframe of the set that is being replaced
   ctx->colour_state_live = false;
   ctx->colour_result_live = false;
   ctx->labels_live = false;

@@ -262,6 +262,13 @@ struct pcp_context {
   bool label_fusion = false;
   bool labels_live = false;
   pcp::DevBuf<uint32_t> labels;
+  // exposure gains (pcp_exposure.hip): one fp32 gain per keyframe for the gained finalise (pcp_set_frame_gains; dropped by
+  // pcp_set_frames), the pair matrices n | sum | counters of the last pcp_view_pair_stats and its counters on the host
+  bool gains_set = false;
+  pcp::DevBuf<float> gains_dev;
+  pcp::DevBuf<unsigned long long> pair_stats;
+  int64_t pair_counters[5] = {0, 0, 0, 0, 0};
+  bool pair_counters_live = false;
 
   // PCP_MATCH_RADIUS (pcp_match.hip): the neighbour table within R_c, built by the first colour pass in that mode and
   // dropped by pcp_upload_cloud / pcp_set_frames (E depends on both).  Set A = points whose row holds another point.
@@ -501,6 +508,10 @@ hipError_t preload_jpeg();
 hipError_t preload_stream_colour();
 hipError_t preload_ascii();
 hipError_t preload_ascii_parse();
+hipError_t preload_exposure();
+// EG5 (pcp_exposure.hip): the packed result from the live top-5 state under ctx->gains_dev (and the label words with label
+// fusion on); ctx->n > 0, a live state and set gains are the caller's to check
+int finalise_gained(pcp_context *ctx, uint32_t *result);
 void ascii_parse_release(pcp_context *ctx);  // the reader's slots, streams and events (pcp_destroy)
 
 // removePointsWithNoColor's index list (pcp_stream_colour.hip): the rows of the current colour result whose has bit is set,

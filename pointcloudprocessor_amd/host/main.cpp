@@ -73,6 +73,14 @@
 //     for byte the files of a --streamColour 0 run; a smoothed cloud of more rows than one upload takes (the reference's
 //     1 mm x 4 on a real map) can only be coloured this way.  One GPU, the z-buffer routine; the per-keyframe dumps, the NID
 //     stage, --matchBack radius, --smoothColorsRadius and masks without --fuseMasks 1 need the whole cloud and are refused.
+//   * --balanceExposure 0|1 (new, default 0 = the reference's behaviour): 1 = one brightness gain per keyframe, estimated on
+//     the GPU from the map points that two keyframes both colour (DESIGN.md "Exposure gains"; the reference has one hand-set
+//     brightness, PointCloudProcessor.cpp:726-729, and balancing scripts that are run over the keyframe folder beforehand).
+//     The colour stage then runs depth pass, colour pass over all keyframes, the pair statistics and the solve, and a
+//     finalise that applies the gains; <outputPath>exposure_gains.txt lists "<imageTimestamp> <gain>" per keyframe.  Only
+//     cloudInWorldWithRGB.pcd (and the rgb of a --fuseMasks 1 file) changes: the per-keyframe dumps keep the sampled colours.
+//     --gpus N above 1 and --streamColour 1 are refused: the statistics are additive over shards and chunks, but that
+//     exchange is not built.
 #include <cfloat>
 #include <chrono>
 #include <cmath>
@@ -154,6 +162,7 @@ struct Options {
   int64_t stream_chunk = int64_t(1) << 28;  // --streamChunk: voxels per chunk (the capacity of the streamed fallback)
   bool device_writer = false;         // --deviceWriter 1: the rows of every ASCII PCD are formatted on the device
   bool device_reader = false;         // --deviceReader 1: the rows of the ASCII PCDs the run reads are parsed on the device
+  bool balance_exposure = false;      // --balanceExposure 1: per-keyframe exposure gains from co-visible map points
 };
 
 static bool parse_bool(const std::string &v) {  // boost::program_options bool semantics
@@ -231,6 +240,12 @@ static Options parse(int argc, char **argv) {
         throw std::runtime_error("the argument ('" + v + "') for option '--deviceReader' is invalid (0, 1)");
       o.device_reader = v == "1";
     }
+    else if (a == "--balanceExposure") {
+      const std::string v = next();
+      if (v != "0" && v != "1")
+        throw std::runtime_error("the argument ('" + v + "') for option '--balanceExposure' is invalid (0, 1)");
+      o.balance_exposure = v == "1";
+    }
     else if (a == "--streamColour") {
       const std::string v = next();
       if (v != "0" && v != "1")
@@ -267,6 +282,13 @@ static Options parse(int argc, char **argv) {
   if (o.device_writer && o.gpus > 1)  // (before anything is read or written, as --streamColour 1 refuses what it cannot do)
     throw std::runtime_error("the option '--deviceWriter 1' does not work with '--gpus N' above 1 (the text is formatted from the "
                              "results resident on one GPU: they do not exist on index shards)");
+  if (o.balance_exposure) {
+    auto refuse = [](const std::string &what, const std::string &why) {
+      throw std::runtime_error("the option '--balanceExposure 1' does not work with " + what + " (" + why + ")");
+    };
+    if (o.gpus > 1) refuse("'--gpus N' above 1", "the pair statistics of the index shards would have to be summed: not built");
+    if (o.stream_colour) refuse("'--streamColour 1'", "the pair statistics of the chunks would have to be summed: not built");
+  }
   if (o.stream_colour) {
     // every chunk is coloured on its own: what needs the whole smoothed cloud at once is refused here, before any GPU work
     auto refuse = [](const std::string &what, const std::string &why) {
@@ -300,7 +322,8 @@ static void usage(std::ostream &os) {
         "  --enableNIDOptimize arg (=0)          Enable NID-based camera pose optimization\n"
         "  --enableInitialGuessManual arg (=0)   Enable manual pickup point based camera pose optimization\n"
         "  --deviceWriter arg (=0)               Format the rows of every ASCII PCD on the GPU (same bytes; --gpus 1)\n"
-        "  --deviceReader arg (=0)               Parse the rows of the ASCII PCDs that are read on the GPU (same floats)\n";
+        "  --deviceReader arg (=0)               Parse the rows of the ASCII PCDs that are read on the GPU (same floats)\n"
+        "  --balanceExposure arg (=0)            One brightness gain per keyframe from co-visible map points (--gpus 1)\n";
 }
 
 class Processor {
@@ -869,6 +892,25 @@ class Processor {
     }
   }
 
+  // --balanceExposure 1: the staged colour stage with the exposure gains between the colour pass and the finalise, and the
+  // gains on record next to the outputs
+  void colorizeBalanced(std::vector<uint8_t> &rgb, std::vector<uint8_t> &has) {
+    Colorizer col(gpu->device(0));
+    col.accumulate();
+    const std::vector<double> gains = col.balanceExposure();
+    col.finalise(rgb, has);
+    const std::string path = opt.outputPath + "exposure_gains.txt";
+    std::ofstream f(path);
+    for (size_t k = 0; k < keyframes.size(); ++k) {
+      char g[64];
+      std::snprintf(g, sizeof(g), "%.9g", gains[k]);
+      f << std::to_string(keyframes[k].imageTimestamp) << " " << g << "\n";
+    }
+    f.close();
+    if (!f) throw std::runtime_error("Couldn't save the exposure gains.");
+    std::cout << "Exposure gains saved to: " << path << std::endl;
+  }
+
   void pcdColorizationAndSmooth() {  // :474-602
     uploadImages(true);
     std::vector<float> wx, wy, wz;  // cloudInWorldWithRGBandMask
@@ -908,7 +950,10 @@ class Processor {
     std::vector<uint8_t> rgb, has;
     {
       Phase ph("colourise_gpu_s");
-      gpu->colorize(rgb, has);  // smoothColors + removePointsWithNoColor flag
+      if (opt.balance_exposure)
+        colorizeBalanced(rgb, has);
+      else
+        gpu->colorize(rgb, has);  // smoothColors + removePointsWithNoColor flag
     }
     if (opt.smooth_colors_radius > 0.0f) {  // smoothColorsWithLocalRegion(rgbCloud, r), :597
       Phase ph("colour_smooth_gpu_s");

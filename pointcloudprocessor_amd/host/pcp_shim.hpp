@@ -178,6 +178,37 @@ class Colorizer {
     if (views) views->resize(n);
     dev_.check(pcp_colour_labels(dev_.get(), label.data(), hits ? hits->data() : nullptr, views ? views->data() : nullptr));
   }
+  // The staged form of colorize(): accumulate() leaves every point's top-5 list on the device (reset, depth pass, colour pass
+  // over all keyframes), finalise() turns the lists into rgb / has -- the same bits as colorize().  In between the lists can
+  // be read: balanceExposure().
+  void accumulate() const {
+    const int32_t frames = pcp_frame_count(dev_.get());
+    dev_.check(pcp_colour_reset(dev_.get()));
+    dev_.check(pcp_depth_pass(dev_.get(), 0, frames));
+    dev_.check(pcp_colour_pass(dev_.get(), 0, frames));
+  }
+  void finalise(std::vector<uint8_t> &rgb, std::vector<uint8_t> &has) const {
+    const size_t n = static_cast<size_t>(dev_.cloudSize());
+    rgb.resize(3 * n);
+    has.resize(n);
+    dev_.check(pcp_colour_finalise(dev_.get(), rgb.data(), has.data(), nullptr, nullptr, nullptr, nullptr));
+  }
+  // Exposure gains (DESIGN.md "Exposure gains"; the reference's one hand-set brightness is PointCloudProcessor.cpp:726-729, its
+  // pairwise note RGBCloud.hpp:20-25): after accumulate(), the pair statistics of the lists (pcp_view_pair_stats), one gain
+  // per keyframe from them (pcp_exposure_gains) and the gains set for finalise() (pcp_set_frame_gains).  Returns the gains.
+  // colorize() refuses to run while they are set: clearExposureGains().
+  std::vector<double> balanceExposure(double sigma_n = 10.0, double sigma_g = 0.1) const {
+    const int32_t frames = pcp_frame_count(dev_.get());
+    const size_t cells = static_cast<size_t>(frames) * static_cast<size_t>(frames);
+    std::vector<uint64_t> pairs(cells), sums(cells);
+    dev_.check(pcp_view_pair_stats(dev_.get(), pairs.data(), sums.data()));
+    std::vector<double> gains(static_cast<size_t>(frames), 1.0);
+    if (pcp_exposure_gains(frames, pairs.data(), sums.data(), sigma_n, sigma_g, gains.data()) != PCP_OK)
+      throw std::runtime_error(std::string("pcp_exposure_gains: ") + pcp_last_error(nullptr));
+    dev_.check(pcp_set_frame_gains(dev_.get(), gains.data(), frames));
+    return gains;
+  }
+  void clearExposureGains() const { dev_.check(pcp_set_frame_gains(dev_.get(), nullptr, 0)); }
   // PointCloudProcessor::smoothColorsWithLocalRegion(rgbCloud, radius), PointCloudProcessor.cpp:634-703 (its call
   // smoothColorsWithLocalRegion(rgbCloud, 0.1) is commented out at :597): in place on the result of colorize(); rgb / has
   // (3 + 1 per input point) receive the smoothed colours and the removePointsWithNoColor flag.  Returns the coloured points.

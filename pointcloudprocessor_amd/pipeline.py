@@ -136,12 +136,23 @@ class ViewCulling:
 class PointCloudColorizer:
     """pcdColorizationAndSmooth over a (possibly sharded) map."""
 
-    def __init__(self, engine, rank: int = 0, world: int = 1, group=None, chunks: int = 0):
+    def __init__(self, engine, rank: int = 0, world: int = 1, group=None, chunks: int = 0, balance_exposure: bool = False,
+                 exposure_sigma_n: float = 10.0, exposure_sigma_g: float = 0.1):
+        """balance_exposure: one brightness gain per keyframe from the map points that two keyframes both colour
+        ("Exposure gains"), applied per listed view when the colours are finalised; `gains` holds them after
+        run().  Off by default (the reference's behaviour).  The pair statistics are additive over index shards, but their
+        exchange is not built: world > 1 raises ValueError."""
+        if balance_exposure and world > 1:
+            raise ValueError("balance_exposure: the pair statistics of the index shards would have to be summed across ranks, "
+                             "which is not built; run it on one rank holding the whole map")
         self.engine = engine
         self.rank = rank
         self.world = world
         self.group = group
         self.chunks = chunks
+        self.balance_exposure = bool(balance_exposure)
+        self.exposure_sigma = (float(exposure_sigma_n), float(exposure_sigma_g))
+        self.gains = None
 
     def _with_labels(self, out: dict, fuse_labels: bool, download: bool):
         if fuse_labels and download:
@@ -171,7 +182,10 @@ class PointCloudColorizer:
             self.engine.set_label_fusion(fuse_labels)
         if self.world == 1:
             self.engine.depth_pass()
-            out = self.engine.colour_from_depth(download=download)
+            if self.balance_exposure:
+                out = self._colour_balanced(download)
+            else:
+                out = self.engine.colour_from_depth(download=download)
             if local_smooth_radius:
                 out = self.engine.smooth_colours_local(local_smooth_radius, download=download)
             return self._with_labels(out, fuse_labels, download)
@@ -200,6 +214,21 @@ class PointCloudColorizer:
 
             torch.cuda.current_stream().synchronize()
         return self._with_labels(self.engine.colour_from_depth(download=download), fuse_labels, download)
+
+    def _colour_balanced(self, download: bool):
+        """The staged colour stage (the depth maps are there): colour pass over all keyframes, pair statistics, gains, gained
+        finalise.  The gains are cleared again afterwards, so the engine's one-shot calls keep working."""
+        ctx = self.engine.ctx
+        ctx.colour_reset()
+        ctx.colour_pass()
+        n, s = ctx.view_pair_stats()
+        self.gains = capi.exposure_gains(n, s, *self.exposure_sigma)
+        ctx.set_frame_gains(self.gains)
+        try:
+            out = ctx.colour_finalise(download=download)
+        finally:
+            ctx.set_frame_gains(None)
+        return dict(rgb=out["rgb"], has=out["has"])
 
     def gather(self, local: dict, n_total: int):
         """All-gather the per-shard colours (and the fused labels, when `local` holds them) into full-length arrays
