@@ -57,7 +57,9 @@ extern "C" {
                                 entry points added, no layout changed: pcp_ascii_parse_host, pcp_ascii_parse, pcp_ascii_parse_limit
                                 (the device PCD reader; nothing runs unless called);
                                 entry points added, no layout changed: pcp_view_pair_stats / _counters, pcp_exposure_gains,
-                                pcp_set_frame_gains (per-keyframe exposure gains; off by default) */
+                                pcp_set_frame_gains (per-keyframe exposure gains; off by default);
+                                entry points added, no layout changed: pcp_voxel_reduce_begin / _add / _finish / _fetch / _stats / _end,
+                                pcp_voxel_reduce_host (voxel-grid output; nothing runs unless called) */
 
 #define PCP_OK 0
 #define PCP_ERR_INVALID (-1) /* bad argument */
@@ -708,6 +710,55 @@ int pcp_ascii_parse_host(const char *text, int64_t bytes, int32_t columns, const
 int pcp_ascii_parse(pcp_context *ctx, const char *text, int64_t bytes, int32_t columns, const int32_t col[4], int32_t final_window,
                     int64_t max_rows, float *out_x, float *out_y, float *out_z, float *out_intensity,
                     int64_t *out_rows, int64_t *out_consumed, int64_t *out_bad_row);
+
+/* ---- voxel-grid output (pcl::VoxelGrid on the final files; voxelgrid_sampling, PCP/src/vlcal/common/frame_cpu.cpp:360-451) - */
+/* One row per occupied voxel of edge `leaf` -- centroid, mean colour, mean fused label, row count -- accumulated on the
+ * device over any number of colour results: one-shot runs, index shards, the chunks of a streamed cloud (DESIGN.md,
+ * "Voxel-grid output", VG1-VG7).  The rows that enter are those pcp_colour_compact returns (has bit set; after
+ * pcp_colour_smooth_local the smoothed ones), with the uploaded coordinates.  Exact integers throughout, so the result does
+ * not depend on the order of rows, uploads or atomics:
+ *   leaf      fp32, 1e-4 <= leaf <= 1 (else PCP_ERR_INVALID); inv = f32(1.0f / leaf);
+ *   cell      c = (int32)floorf(f32(x * inv)) per axis: the lattice is anchored at the world origin, so shards and chunks
+ *             agree; a non-finite coordinate or |c| >= 2^20 is PCP_ERR_RANGE;
+ *   order     ascending key ((cz + 2^20) << 42) | ((cy + 2^20) << 21) | (cx + 2^20): x fastest, z slowest;
+ *   position  signed 64-bit sum of q = llrint((double)x * 2^32) - corner, corner = llrint((double)c * (double)leaf * 2^32);
+ *             x_out = f32((double)(corner + floor((2 * sum q + n) / (2 n))) * 2^-32);
+ *   colour    r_out = floor(sum r / n), likewise g, b and the label; count = n.  A voxel with n >= 2^24: finish returns
+ *             PCP_ERR_RANGE.
+ * A voxel of one row with |x| >= 2^-9 returns that coordinate bit for bit.  Opt-in: nothing runs unless one of these is
+ * called, PCP_ABI_VERSION is unchanged and a caller detects support by the symbols.  Kernels are timed under PCP_K_MISC.
+ *
+ * The accumulator belongs to the context: it outlives pcp_upload_cloud*, pcp_upload_cloud_from_result, pcp_colour_reset,
+ * pcp_set_frames and pcp_set_camera; only _begin, _end and pcp_destroy drop it.  The sums are local to the context (on an
+ * index shard: to the shard); exchanging them across GPUs is the caller's.
+ * _begin  starts an empty accumulation (dropping a previous one).  initial_slots: slots of the hash table (rounded up to a
+ *         power of two, at least 64; at most 2^31), 0 = sized by the first add; the table doubles as it fills past a half.
+ * _add    adds the rows of the current colour result; *out_rows_added (nullable) = their number.  Needs _begin
+ *         (PCP_ERR_STATE), a live colour result (PCP_ERR_STATE), and no _finish since _begin (PCP_ERR_STATE).  The first add
+ *         fixes whether labels are accumulated, by whether its result was made with label fusion; a later add that disagrees
+ *         is PCP_ERR_STATE.  A failed add leaves the accumulation as it was.  It changes nothing else: the packed colour
+ *         words and pcp_colour_compact's rows are afterwards what they were before.
+ * _finish sorts the occupied voxels by key and computes the rows; *out_voxels (nullable) = their number.  A second call
+ *         returns the same count.
+ * _fetch  rows [first, first + max_rows) of the finished result, every output nullable: out_xyz 3 floats, out_rgb 3 bytes
+ *         (r, g, b), out_label and out_count one each per row; *out_rows = rows in the window (0 past the end).  Before
+ *         _finish, or out_label on an accumulation without labels: PCP_ERR_STATE.  Negative first / max_rows: PCP_ERR_INVALID.
+ * _stats  out[0..5] = rows added, voxels (before _finish: keys that hold rows), table slots, table doublings, per-wavefront
+ *         partial sums issued, global payload adds issued (7 per partial, 8 with labels).  Before _begin: PCP_ERR_STATE.
+ * _end    drops the accumulation and its result. */
+int pcp_voxel_reduce_begin(pcp_context *ctx, float leaf, int64_t initial_slots);
+int pcp_voxel_reduce_add(pcp_context *ctx, int64_t *out_rows_added);
+int pcp_voxel_reduce_finish(pcp_context *ctx, int64_t *out_voxels);
+int pcp_voxel_reduce_fetch(pcp_context *ctx, int64_t first, int64_t max_rows, float *out_xyz, uint8_t *out_rgb, uint8_t *out_label,
+                           uint32_t *out_count, int64_t *out_rows);
+int pcp_voxel_reduce_stats(pcp_context *ctx, int64_t out[6]);
+int pcp_voxel_reduce_end(pcp_context *ctx);
+/* Host only, no context, no GPU: the same reduction of n rows (xyz 3 floats, rgb 3 bytes, label one byte per row; label
+ * nullable: the labels then read 0) by the arithmetic the kernels use (csrc/pcp_voxel_reduce.hpp).  *out_voxels = the occupied
+ * voxels, always; the first min(capacity, voxels) rows are written (outputs nullable).  Leaf and range rules as above; negative
+ * n / capacity, a missing xyz / rgb, out_label without label: PCP_ERR_INVALID.  The message is at pcp_last_error(NULL). */
+int pcp_voxel_reduce_host(float leaf, int64_t n, const float *xyz, const uint8_t *rgb, const uint8_t *label, int64_t capacity,
+                          float *out_xyz, uint8_t *out_rgb, uint8_t *out_label, uint32_t *out_count, int64_t *out_voxels);
 
 /* ---- precondition of the match-back(PointCloudProcessor.cpp:480-482,571) ------------------------------- */
 /* Number of map points that have ANOTHER map point closer than `radius` (fp32 squared distance, strict <, as

@@ -263,6 +263,35 @@ def exposure_gains(n, sum, sigma_n: float = 10.0, sigma_g: float = 0.1) -> np.nd
     return out
 
 
+def voxel_reduce_host(leaf: float, xyz, rgb, label=None, capacity: int | None = None) -> dict:
+    """The voxel-grid output of n coloured rows computed on the CPU by the arithmetic the kernels use (pcp_voxel_reduce_host:
+    no context, no GPU; DESIGN.md "Voxel-grid output").  xyz (n, 3) float32, rgb (n, 3) uint8, label n uint8 or None:
+    dict(xyz, rgb[, label], count, voxels), one row per occupied voxel in key order; voxels is the true count even when
+    capacity is smaller."""
+    L = load()
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    rgb = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)
+    label = None if label is None else np.ascontiguousarray(label, np.uint8).reshape(-1)
+    n = xyz.shape[0]
+    if rgb.shape[0] != n or (label is not None and label.shape[0] != n):
+        raise ValueError("voxel_reduce_host: xyz, rgb and label differ in their number of rows")
+    cap = n if capacity is None else capacity
+    oxyz = np.empty((max(cap, 0), 3), np.float32)
+    orgb = np.empty((max(cap, 0), 3), np.uint8)
+    olab = np.empty(max(cap, 0), np.uint8) if label is not None else None
+    ocnt = np.empty(max(cap, 0), np.uint32)
+    vox = C.c_int64()
+    rc = L.pcp_voxel_reduce_host(C.c_float(leaf), C.c_int64(n), _ptr(xyz), _ptr(rgb), _ptr(label), C.c_int64(cap), _ptr(oxyz), _ptr(orgb),
+                                 _ptr(olab), _ptr(ocnt), C.byref(vox))
+    if rc != PCP_OK:
+        raise PcpError(rc, L.pcp_last_error(None).decode())
+    m = min(vox.value, cap)
+    out = dict(xyz=oxyz[:m], rgb=orgb[:m], count=ocnt[:m], voxels=vox.value)
+    if label is not None:
+        out["label"] = olab[:m]
+    return out
+
+
 def default_camera() -> Camera:
     cam = Camera()
     load().pcp_default_camera(C.byref(cam))
@@ -695,6 +724,51 @@ class Context:
             return
         g = np.ascontiguousarray(gains, np.float64).reshape(-1)
         self._check(self.lib.pcp_set_frame_gains(self.h, _ptr(g), C.c_int32(g.size)))
+
+    # -- voxel-grid output ("Voxel-grid output") ----------------------
+    def voxel_reduce_begin(self, leaf: float, initial_slots: int = 0):
+        """Starts an empty voxel accumulation of edge `leaf` on this context (pcp_voxel_reduce_begin); it outlives uploads,
+        colour resets, set_frames and set_camera."""
+        self._check(self.lib.pcp_voxel_reduce_begin(self.h, C.c_float(leaf), C.c_int64(initial_slots)))
+
+    def voxel_reduce_add(self) -> int:
+        """Adds the coloured rows of the current colour result (those colour_compact() returns); returns their number."""
+        rows = C.c_int64()
+        self._check(self.lib.pcp_voxel_reduce_add(self.h, C.byref(rows)))
+        return rows.value
+
+    def voxel_reduce_finish(self) -> int:
+        """Sorts the occupied voxels by key and computes their rows; returns their number."""
+        vox = C.c_int64()
+        self._check(self.lib.pcp_voxel_reduce_finish(self.h, C.byref(vox)))
+        return vox.value
+
+    def voxel_reduce_fetch(self, first: int = 0, max_rows: int | None = None, want_label: bool = False) -> dict:
+        """dict(xyz, rgb[, label], count) of rows [first, first + max_rows) of the finished result; max_rows None = to the end."""
+        if max_rows is None:
+            max_rows = max(0, self.voxel_reduce_stats()["voxels"] - first)
+        cap = max(max_rows, 0)
+        xyz = np.empty((cap, 3), np.float32)
+        rgb = np.empty((cap, 3), np.uint8)
+        label = np.empty(cap, np.uint8) if want_label else None
+        cnt = np.empty(cap, np.uint32)
+        rows = C.c_int64()
+        self._check(self.lib.pcp_voxel_reduce_fetch(self.h, C.c_int64(first), C.c_int64(max_rows), _ptr(xyz), _ptr(rgb), _ptr(label),
+                                                    _ptr(cnt), C.byref(rows)))
+        m = rows.value
+        out = dict(xyz=xyz[:m], rgb=rgb[:m], count=cnt[:m])
+        if want_label:
+            out["label"] = label[:m]
+        return out
+
+    def voxel_reduce_stats(self) -> dict:
+        out = np.zeros(6, np.int64)
+        self._check(self.lib.pcp_voxel_reduce_stats(self.h, _ptr(out)))
+        keys = ("rows", "voxels", "slots", "growths", "wave_partials", "global_adds")
+        return {k: int(v) for k, v in zip(keys, out)}
+
+    def voxel_reduce_end(self):
+        self._check(self.lib.pcp_voxel_reduce_end(self.h))
 
     def colour_smooth_local(self, radius: float) -> int:
         """smoothColorsWithLocalRegion (PointCloudProcessor.cpp:634-703) in place on the colour result; returns the number

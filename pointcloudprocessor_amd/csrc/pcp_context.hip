@@ -619,7 +619,8 @@ int pcp_create(int32_t device, pcp_context **out) {
     hipFuncAttributes a;
     const hipError_t pl[] = {hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_up_bbox)), preload_colour(), preload_mls(),
                              preload_nid(), preload_hpr(), preload_colour_smooth(), preload_match(),
-                             preload_jpeg(), preload_stream_colour(), preload_ascii(), preload_ascii_parse(), preload_exposure()};
+                             preload_jpeg(), preload_stream_colour(), preload_ascii(), preload_ascii_parse(), preload_exposure(),
+                             preload_voxel_reduce()};
     for (hipError_t x : pl)
       if (x != hipSuccess && e == hipSuccess) e = x;
   }
@@ -717,6 +718,7 @@ void pcp_destroy(pcp_context *ctx) {
   ctx->labels.release();
   ctx->gains_dev.release();
   ctx->pair_stats.release();
+  voxel_reduce_release(ctx);
   match_table_release(ctx);
   ctx->match_moved.release();
   for (int k = 0; k < 2; ++k) {

@@ -163,6 +163,23 @@ struct HprLane {
   }
 };
 
+// voxel-grid output (pcp_voxel_reduce.hip): the accumulator between pcp_voxel_reduce_begin and _end -- an open-addressing table
+// (keys, three position sums and five 32-bit sums per slot), its device scalars, and the rows pcp_voxel_reduce_finish left
+struct VoxelReduce {
+  bool live = false, finished = false;
+  bool labels_fixed = false, with_label = false;  // the first add fixes whether labels are accumulated
+  float leaf = 0.0f;
+  int64_t initial_slots = 0;  // 0: sized by the first add
+  int64_t slots = 0, used = 0;  // used: keys in the table (a failed add may leave keys without rows behind)
+  int64_t keyed = 0;            // keys that hold rows: `used` as the last successful add left it
+  int64_t rows = 0, voxels = 0, growths = 0, partials = 0, atomics = 0;
+  DevBuf<unsigned long long> keys, q, scalars;
+  DevBuf<uint32_t> sums;
+  DevBuf<float> out_xyz;
+  DevBuf<uint8_t> out_rgb, out_label;
+  DevBuf<uint32_t> out_count;
+};
+
 }  // namespace pcp
 
 struct pcp_context {
@@ -269,6 +286,9 @@ struct pcp_context {
   pcp::DevBuf<unsigned long long> pair_stats;
   int64_t pair_counters[5] = {0, 0, 0, 0, 0};
   bool pair_counters_live = false;
+
+  // voxel-grid output: belongs to the context, not to the cloud or the camera (only pcp_voxel_reduce_begin / _end and pcp_destroy drop it)
+  pcp::VoxelReduce voxel_reduce;
 
   // PCP_MATCH_RADIUS (pcp_match.hip): the neighbour table within R_c, built by the first colour pass in that mode and
   // dropped by pcp_upload_cloud / pcp_set_frames (E depends on both).  Set A = points whose row holds another point.
@@ -509,6 +529,8 @@ hipError_t preload_stream_colour();
 hipError_t preload_ascii();
 hipError_t preload_ascii_parse();
 hipError_t preload_exposure();
+hipError_t preload_voxel_reduce();
+void voxel_reduce_release(pcp_context *ctx);  // the accumulator and its result (pcp_destroy)
 // EG5 (pcp_exposure.hip): the packed result from the live top-5 state under ctx->gains_dev (and the label words with label
 // fusion on); ctx->n > 0, a live state and set gains are the caller's to check
 int finalise_gained(pcp_context *ctx, uint32_t *result);

@@ -81,6 +81,18 @@
 //     cloudInWorldWithRGB.pcd (and the rgb of a --fuseMasks 1 file) changes: the per-keyframe dumps keep the sampled colours.
 //     --gpus N above 1 and --streamColour 1 are refused: the statistics are additive over shards and chunks, but that
 //     exchange is not built.
+//   * --outputLeaf L (new, default 0 = off; 1e-4 <= L <= 1) and --skip_full_cloud 0|1 (new, default 0): with L > 0 the run also
+//     writes <outputPath>cloudInWorldWithRGB_voxel.pcd -- one XYZRGB row per occupied voxel of edge L of the coloured cloud:
+//     the centroid and the mean colour of the voxel's rows, in pcl::VoxelGrid's leaf order on a lattice anchored at the world
+//     origin -- and, with --fuseMasks 1, <outputPath>cloudInWorldWithRGBandMask_voxel.pcd with the mean fused label as
+//     segmentMask.  The reduction runs on the GPU over the colour result where it lies (pcp_voxel_reduce_*; DESIGN.md
+//     "Voxel-grid output"), after --smoothColorsRadius when given; in the one-shot path and under --streamColour 1, where
+//     every chunk is added after it is coloured, the files are byte for byte the same.  It is what pcl::VoxelGrid /
+//     voxelgrid_sampling (frame_cpu.cpp:360-451) users run over the full file afterwards.  --skip_full_cloud 1 (needs
+//     --outputLeaf): cloudInWorldWithRGB.pcd / cloudInWorldWithRGBandMask.pcd are neither fetched nor written; under
+//     --streamColour 1 the chunks are then compacted with capacity 0, so only the voxel rows leave the device.  --gpus N
+//     above 1 is refused: the voxel sums of the index shards would have to be added across GPUs, which is not built.  The
+//     voxel files are small and always go through the host writer, --deviceWriter 1 or not.
 #include <cfloat>
 #include <chrono>
 #include <cmath>
@@ -163,6 +175,8 @@ struct Options {
   bool device_writer = false;         // --deviceWriter 1: the rows of every ASCII PCD are formatted on the device
   bool device_reader = false;         // --deviceReader 1: the rows of the ASCII PCDs the run reads are parsed on the device
   bool balance_exposure = false;      // --balanceExposure 1: per-keyframe exposure gains from co-visible map points
+  float output_leaf = 0.0f;           // --outputLeaf L: also write the voxel-grid output at that leaf (0: off)
+  bool skip_full_cloud = false;       // --skip_full_cloud 1: with --outputLeaf, the full-resolution final files are not made
 };
 
 static bool parse_bool(const std::string &v) {  // boost::program_options bool semantics
@@ -246,6 +260,17 @@ static Options parse(int argc, char **argv) {
         throw std::runtime_error("the argument ('" + v + "') for option '--balanceExposure' is invalid (0, 1)");
       o.balance_exposure = v == "1";
     }
+    else if (a == "--outputLeaf") {
+      const std::string v = next();
+      char *end = nullptr;
+      const double l = std::strtod(v.c_str(), &end);
+      const float lf = static_cast<float>(l);
+      // 0 (off) or a leaf the library accepts (finite, 1e-4 <= L <= 1)
+      if (v.empty() || end != v.c_str() + v.size() || !std::isfinite(l) || !(lf == 0.0f || (lf >= 1e-4f && lf <= 1.0f)))
+        throw std::runtime_error("the argument ('" + v + "') for option '--outputLeaf' is invalid (0 = off, or 1e-4 <= L <= 1)");
+      o.output_leaf = lf;
+    }
+    else if (a == "--skip_full_cloud") o.skip_full_cloud = parse_bool(next());
     else if (a == "--streamColour") {
       const std::string v = next();
       if (v != "0" && v != "1")
@@ -282,6 +307,11 @@ static Options parse(int argc, char **argv) {
   if (o.device_writer && o.gpus > 1)  // (before anything is read or written, as --streamColour 1 refuses what it cannot do)
     throw std::runtime_error("the option '--deviceWriter 1' does not work with '--gpus N' above 1 (the text is formatted from the "
                              "results resident on one GPU: they do not exist on index shards)");
+  if (o.skip_full_cloud && !(o.output_leaf > 0.0f))
+    throw std::runtime_error("the option '--skip_full_cloud 1' needs '--outputLeaf' above 0 (without it the run would write no coloured cloud)");
+  if (o.output_leaf > 0.0f && o.gpus > 1)
+    throw std::runtime_error("the option '--outputLeaf' does not work with '--gpus N' above 1 (the voxel sums of the index shards would "
+                             "have to be added across GPUs: not built)");
   if (o.balance_exposure) {
     auto refuse = [](const std::string &what, const std::string &why) {
       throw std::runtime_error("the option '--balanceExposure 1' does not work with " + what + " (" + why + ")");
@@ -321,7 +351,10 @@ static void usage(std::ostream &os) {
         "  --enableMLS arg (=0)                  Enable MLS smoothing\n"
         "  --enableNIDOptimize arg (=0)          Enable NID-based camera pose optimization\n"
         "  --enableInitialGuessManual arg (=0)   Enable manual pickup point based camera pose optimization\n"
-        "  --deviceWriter arg (=0)               Format the rows of every ASCII PCD on the GPU (same bytes; --gpus 1)\n"
+        "  --outputLeaf arg (=0)                 Also write the coloured cloud reduced to one row per voxel of this edge (--gpus 1)\n"
+        "  --skip_full_cloud arg (=0)            With --outputLeaf: do not fetch or write the full-resolution coloured clouds\n"
+        "  --deviceWriter arg (=0)               Format the rows of every ASCII PCD on the GPU (same bytes; --gpus 1;\n"
+        "                                        the --outputLeaf files are small and go through the host writer)\n"
         "  --deviceReader arg (=0)               Parse the rows of the ASCII PCDs that are read on the GPU (same floats)\n"
         "  --balanceExposure arg (=0)            One brightness gain per keyframe from co-visible map points (--gpus 1)\n";
 }
@@ -853,52 +886,102 @@ class Processor {
     const std::string cropPath = opt.outputPath + "scans-crop.pcd";
     const std::string mlsPath = fs::path(cropPath).stem().string() + "_mls.pcd";  // CWD-relative, sic (B14)
     const std::string rgbPath = opt.outputPath + "cloudInWorldWithRGB.pcd", maskPath = opt.outputPath + "cloudInWorldWithRGBandMask.pcd";
-    std::unique_ptr<ChunkedAsciiWriter> mls, mask;
-    ChunkedAsciiWriter rgb(rgbPath, ChunkedAsciiWriter::XYZRGB);
-    if (opt.fuse_masks) mask.reset(new ChunkedAsciiWriter(maskPath, ChunkedAsciiWriter::XYZRGBMask));
+    std::unique_ptr<ChunkedAsciiWriter> mls, mask, rgb;
+    const bool full = !opt.skip_full_cloud;  // (--skip_full_cloud 1: the chunks' rows stay on the device, only the voxel rows leave it)
+    if (full) rgb.reset(new ChunkedAsciiWriter(rgbPath, ChunkedAsciiWriter::XYZRGB));
+    if (full && opt.fuse_masks) mask.reset(new ChunkedAsciiWriter(maskPath, ChunkedAsciiWriter::XYZRGBMask));
     const StreamedColourStats st = opt.device_writer ? cs.processAndColorizeStreamedText(
         gpu->device(0), opt.stream_chunk,
         [&](const TextRows &t) {
-          if (!t.labelled) rgb.appendText(t.text, t.bytes, t.rows);
+          if (!t.labelled) rgb->appendText(t.text, t.bytes, t.rows);
           else if (mask) mask->appendText(t.text, t.bytes, t.rows);
         },
         [&](const TextRows &t, int64_t kept_rows) {
           if (!mls) mls.reset(new ChunkedAsciiWriter(mlsPath, ChunkedAsciiWriter::PointNormal, kept_rows));
           mls->appendText(t.text, t.bytes, t.rows);
         },
-        opt.fuse_masks) : cs.processAndColorizeStreamed(
+        opt.fuse_masks, kTextWindowRows, opt.output_leaf, full) : cs.processAndColorizeStreamed(
         gpu->device(0), opt.stream_chunk,
         [&](const ColouredChunk &c) {
-          rgb.appendColoured(c.xyz.data(), c.rgb.data(), nullptr, c.index.size());
+          rgb->appendColoured(c.xyz.data(), c.rgb.data(), nullptr, c.index.size());
           if (mask) mask->appendColoured(c.xyz.data(), c.rgb.data(), c.label.data(), c.index.size());
         },
         [&](const SmoothedCloud &s, int64_t kept_rows) {
           if (!mls) mls.reset(new ChunkedAsciiWriter(mlsPath, ChunkedAsciiWriter::PointNormal, kept_rows));
           mls->appendPointNormal(s.xyz.data(), s.normal.data(), s.curvature.data(), s.curvature.size());
         },
-        opt.fuse_masks);
+        opt.fuse_masks, opt.output_leaf, full);
     std::cout << "streamed colour: " << st.chunks << " chunks, " << st.rows << " rows, " << st.coloured << " coloured" << std::endl;
     g_clock.add("stream_colour_sweep_a_s", st.sweep_a_s);
     g_clock.add("stream_colour_sweep_b_s", st.sweep_b_s);
+    if (opt.output_leaf > 0.0f) {
+      g_clock.add("voxel_reduce_add_s", st.voxel_add_s);
+      g_clock.add("voxel_reduce_finish_s", st.voxel_finish_s);
+    }
     if (!mls) mls.reset(new ChunkedAsciiWriter(mlsPath, ChunkedAsciiWriter::PointNormal, 0));  // no row: the writer's exception
     if (mls->finish() == -1) throw std::runtime_error("Couldn't save the smoothed point cloud.");
     if (mask && mask->rows() > 0) {  // saveColorizedPointCloud(rgbCloud, withMask), :933-960
       if (mask->finish() == -1) throw std::runtime_error("Couldn't save colorized and segment colored point cloud.");
       std::cout << "All colored and segment colored cloud saved to: " << maskPath << std::endl;
     }
-    if (rgb.rows() > 0) {  // :912-929
-      if (rgb.finish() == -1) throw std::runtime_error("Couldn't save colorized point cloud.");
+    if (rgb && rgb->rows() > 0) {  // :912-929
+      if (rgb->finish() == -1) throw std::runtime_error("Couldn't save colorized point cloud.");
       std::cout << "All colored cloud saved to: " << rgbPath << std::endl;
     }
+    if (opt.output_leaf > 0.0f) writeVoxelFiles();  // (the accumulation was finished after sweep B)
+  }
+
+  // --outputLeaf L: the finished voxel accumulation of the colour context as <out>cloudInWorldWithRGB_voxel.pcd and, with
+  // --fuseMasks 1, <out>cloudInWorldWithRGBandMask_voxel.pcd, through the host writer (the files are small); then dropped
+  void writeVoxelFiles() {
+    Phase ph("voxel_pcd_write_ascii_s");
+    Device &dev = gpu->device(0);
+    const VoxelCloud v = dev.voxelReduceFetch(opt.fuse_masks);
+    dev.voxelReduceEnd();
+    const size_t m = v.count.size();
+    std::cout << "voxel output: leaf " << opt.output_leaf << ", " << m << " voxels" << std::endl;
+    if (m == 0) return;  // (no coloured row: no file, as the full-resolution files)
+    if (opt.fuse_masks) {
+      std::vector<uint16_t> mask(v.label.begin(), v.label.end());
+      const std::string path = opt.outputPath + "cloudInWorldWithRGBandMask_voxel.pcd";
+      if (writeASCII_XYZRGBMask(path, v.xyz.data(), v.rgb.data(), mask.data(), m) == -1)
+        throw std::runtime_error("Couldn't save the voxel-grid colorized and segment colored point cloud.");
+      std::cout << "Voxel-grid colored and segment colored cloud saved to: " << path << std::endl;
+    }
+    std::vector<float> x(m), y(m), z(m);
+    for (size_t i = 0; i < m; ++i) {
+      x[i] = v.xyz[3 * i];
+      y[i] = v.xyz[3 * i + 1];
+      z[i] = v.xyz[3 * i + 2];
+    }
+    const std::string path = opt.outputPath + "cloudInWorldWithRGB_voxel.pcd";
+    if (writeASCII_XYZRGB(path, x.data(), y.data(), z.data(), v.rgb.data(), m) == -1)
+      throw std::runtime_error("Couldn't save the voxel-grid colorized point cloud.");
+    std::cout << "Voxel-grid colored cloud saved to: " << path << std::endl;
+  }
+  // the one-shot path: the colour result that was just made (and smoothed), reduced where it lies
+  void reduceToVoxels() {
+    {
+      Phase ph("voxel_reduce_gpu_s");
+      Device &dev = gpu->device(0);
+      dev.voxelReduceBegin(opt.output_leaf);
+      (void)dev.voxelReduceAdd();
+      (void)dev.voxelReduceFinish();
+    }
+    writeVoxelFiles();
   }
 
   // --balanceExposure 1: the staged colour stage with the exposure gains between the colour pass and the finalise, and the
   // gains on record next to the outputs
-  void colorizeBalanced(std::vector<uint8_t> &rgb, std::vector<uint8_t> &has) {
+  // (fetch = false, --skip_full_cloud 1: the result stays on the device)
+  void colorizeBalanced(std::vector<uint8_t> &rgb, std::vector<uint8_t> &has, bool fetch = true) {
     Colorizer col(gpu->device(0));
     col.accumulate();
     const std::vector<double> gains = col.balanceExposure();
-    col.finalise(rgb, has);
+    if (fetch)
+      col.finalise(rgb, has);
+    else
+      col.finaliseOnDevice();
     const std::string path = opt.outputPath + "exposure_gains.txt";
     std::ofstream f(path);
     for (size_t k = 0; k < keyframes.size(); ++k) {
@@ -941,13 +1024,32 @@ class Processor {
                                : writeASCII_XYZRGBMask(path, v.xyz_cam.data(), v.rgb.data(), v.mask.data(), v.index.size())) == -1)
           throw std::runtime_error("Couldn't save filtered point cloud to PCD file.");
         std::cout << "Filtered point cloud saved to: " << path << ", the point size is " << v.index.size() << std::endl;
-        if (opt.fuse_masks) continue;  // the fused file has one row per map point: no concatenation
+        if (opt.fuse_masks || opt.skip_full_cloud) continue;  // the fused file has one row per map point, and
+                                                              // --skip_full_cloud 1 writes neither: no concatenation
         wxyz.insert(wxyz.end(), v.xyz_world.begin(), v.xyz_world.end());
         wrgb.insert(wrgb.end(), v.rgb.begin(), v.rgb.end());
         wmask.insert(wmask.end(), v.mask.begin(), v.mask.end());
       }
     }
     std::vector<uint8_t> rgb, has;
+    if (opt.skip_full_cloud) {
+      // --skip_full_cloud 1 (one GPU, --outputLeaf given): the same colour result, left on the device; only the voxel rows leave it
+      Device &dev = gpu->device(0);
+      {
+        Phase ph("colourise_gpu_s");
+        if (opt.balance_exposure)
+          colorizeBalanced(rgb, has, false);
+        else
+          dev.check(pcp_colorize(dev.get(), nullptr, nullptr));
+      }
+      if (opt.smooth_colors_radius > 0.0f) {
+        Phase ph("colour_smooth_gpu_s");
+        int64_t coloured = 0;
+        dev.check(pcp_colour_smooth_local(dev.get(), opt.smooth_colors_radius, &coloured));
+      }
+      reduceToVoxels();
+      return;
+    }
     {
       Phase ph("colourise_gpu_s");
       if (opt.balance_exposure)
@@ -959,6 +1061,7 @@ class Processor {
       Phase ph("colour_smooth_gpu_s");
       gpu->smoothColorsWithLocalRegion(opt.smooth_colors_radius, rgb, has);
     }
+    if (opt.output_leaf > 0.0f) reduceToVoxels();  // (of the colour result as it lies on the device now)
     std::vector<uint8_t> label;
     if (opt.fuse_masks) {
       Phase ph("labels_gpu_s");

@@ -25,6 +25,14 @@
 
 namespace pcp_amd {
 
+// The voxel-grid output (pcp_hip.h, "voxel-grid output"): one row per occupied voxel, in key order
+struct VoxelCloud {
+  std::vector<float> xyz;       // 3 per row: the centroid
+  std::vector<uint8_t> rgb;     // 3 per row: the mean colour
+  std::vector<uint8_t> label;   // mean fused label per row (asked for and accumulated), else empty
+  std::vector<uint32_t> count;  // rows of the coloured cloud in the voxel
+};
+
 class Device {
  public:
   explicit Device(int ordinal = 0) {
@@ -105,6 +113,38 @@ class Device {
     check(pcp_mls_fetch_ascii(ctx_, first_row, max_rows, static_cast<int64_t>(text.size()), text.data(), &w.rows, &w.bytes));
     return w;
   }
+
+  // ---- voxel-grid output: what pcl::VoxelGrid at `leaf` (voxelgrid_sampling, frame_cpu.cpp:360-451) makes of the coloured
+  // cloud, accumulated on the device over any number of colour results (pcp_voxel_reduce_*; DESIGN.md "Voxel-grid output") ----
+  void voxelReduceBegin(float leaf, int64_t initial_slots = 0) { check(pcp_voxel_reduce_begin(ctx_, leaf, initial_slots)); }
+  int64_t voxelReduceAdd() {  // the coloured rows of the current colour result; returns their number
+    int64_t rows = 0;
+    check(pcp_voxel_reduce_add(ctx_, &rows));
+    return rows;
+  }
+  int64_t voxelReduceFinish() {
+    int64_t voxels = 0;
+    check(pcp_voxel_reduce_finish(ctx_, &voxels));
+    return voxels;
+  }
+  VoxelCloud voxelReduceFetch(bool with_label) {  // the whole finished result
+    VoxelCloud v;
+    const size_t m = static_cast<size_t>(voxelReduceFinish());
+    v.xyz.resize(3 * m);
+    v.rgb.resize(3 * m);
+    v.label.resize(with_label ? m : 0);
+    v.count.resize(m);
+    int64_t rows = 0;
+    check(pcp_voxel_reduce_fetch(ctx_, 0, static_cast<int64_t>(m), v.xyz.data(), v.rgb.data(), with_label ? v.label.data() : nullptr,
+                                 v.count.data(), &rows));
+    return v;
+  }
+  std::vector<int64_t> voxelReduceStats() const {  // rows, voxels, slots, doublings, wavefront partials, global adds
+    std::vector<int64_t> s(6);
+    check(pcp_voxel_reduce_stats(ctx_, s.data()));
+    return s;
+  }
+  void voxelReduceEnd() { check(pcp_voxel_reduce_end(ctx_)); }
 
   // ---- device PCD reader: the x y z intensity floats of a window of PCD ASCII rows (pcp_hip.h, "device PCD reader") ----
   struct ParsedRows {
@@ -192,6 +232,10 @@ class Colorizer {
     rgb.resize(3 * n);
     has.resize(n);
     dev_.check(pcp_colour_finalise(dev_.get(), rgb.data(), has.data(), nullptr, nullptr, nullptr, nullptr));
+  }
+  // the same result left on the device (for pcp_colour_smooth_local, pcp_colour_compact, pcp_voxel_reduce_add): nothing is fetched
+  void finaliseOnDevice() const {
+    dev_.check(pcp_colour_finalise(dev_.get(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
   }
   // Exposure gains (DESIGN.md "Exposure gains"; the reference's one hand-set brightness is PointCloudProcessor.cpp:726-729, its
   // pairwise note RGBCloud.hpp:20-25): after accumulate(), the pair statistics of the lists (pcp_view_pair_stats), one gain
@@ -310,6 +354,8 @@ struct StreamedColourStats {
   int32_t chunks = 0;
   int64_t rows = 0, coloured = 0;            // smoothed rows, rows with a colour
   double sweep_a_s = 0.0, sweep_b_s = 0.0;  // host-clock seconds, the sinks included
+  int64_t voxels = 0;                       // output_leaf > 0: rows of the voxel-grid output
+  double voxel_add_s = 0.0, voxel_finish_s = 0.0;
 };
 // the largest cloud one upload takes (pcp_upload_cloud*: n < 2^31)
 constexpr int64_t kMaxUploadPoints = (int64_t(1) << 31) - 1;
@@ -378,9 +424,13 @@ class CloudSmooth {
   //            the chunk's rows -- the <stem>_mls.pcd rows as they come; kept_rows, their total, is known from the start;
   //   sweep B  the stream rewound: depth pass (tile masks), the accumulator applied, colours, compaction on the device;
   //            sink(const ColouredChunk &) receives every chunk's coloured rows.
+  // output_leaf > 0: the coloured rows are also reduced on `colour` to one row per occupied voxel of that edge (pcp_voxel_reduce_*):
+  // begin before sweep B, one add per coloured chunk, finish after the sweep; the caller then reads colour.voxelReduceFetch()
+  // and ends it (colour.voxelReduceEnd()).  fetch_rows = false: the chunks are compacted with capacity 0 -- only the count
+  // comes back, the sink is not called -- so with output_leaf nothing but the reduced rows leaves the device.
   template <class Sink, class SmoothedSink>
   StreamedColourStats processAndColorizeStreamed(Device &colour, int64_t chunk_capacity, Sink &&sink, SmoothedSink &&smoothed,
-                                                 bool fuse_labels = false) const {
+                                                 bool fuse_labels = false, float output_leaf = 0.0f, bool fetch_rows = true) const {
     pcp_context *src = dev_.get(), *dst = colour.get();
     SmoothedCloud s;
     ColouredChunk out;
@@ -393,6 +443,10 @@ class CloudSmooth {
         },
         [&](int64_t m) {
           int64_t coloured = 0;
+          if (!fetch_rows) {
+            colour.check(pcp_colour_compact(dst, 0, nullptr, nullptr, nullptr, nullptr, &coloured));
+            return coloured;
+          }
           const size_t sm = static_cast<size_t>(m);
           out.index.resize(sm);
           out.xyz.resize(3 * sm);
@@ -411,7 +465,8 @@ class CloudSmooth {
           for (size_t k = 0; k < sc; ++k) out.index[k] = source[static_cast<size_t>(out.index[k])];
           sink(static_cast<const ColouredChunk &>(out));
           return coloured;
-        });
+        },
+        output_leaf);
   }
   // The same two sweeps with the rows delivered as TEXT, formatted on the device (the device PCD writer): smoothed(const
   // TextRows &, kept_rows) receives each chunk's PointNormal rows in sweep A, sink(const TextRows &) each chunk's coloured rows in
@@ -420,7 +475,8 @@ class CloudSmooth {
   // order are the bytes the host writers print of the binary sinks' rows.
   template <class Sink, class SmoothedSink>
   StreamedColourStats processAndColorizeStreamedText(Device &colour, int64_t chunk_capacity, Sink &&sink, SmoothedSink &&smoothed,
-                                                     bool fuse_labels = false, int64_t window_rows = kTextWindowRows) const {
+                                                     bool fuse_labels = false, int64_t window_rows = kTextWindowRows,
+                                                     float output_leaf = 0.0f, bool fetch_rows = true) const {
     std::vector<char> text;
     return streamedSweeps(
         colour, chunk_capacity,
@@ -434,6 +490,10 @@ class CloudSmooth {
         },
         [&](int64_t) {
           int64_t coloured = 0;
+          if (!fetch_rows) {
+            colour.check(pcp_colour_compact(colour.get(), 0, nullptr, nullptr, nullptr, nullptr, &coloured));
+            return coloured;
+          }
           for (int labelled = 0; labelled <= (fuse_labels ? 1 : 0); ++labelled)
             for (int64_t first = 0;;) {
               const Device::TextWindow w = colour.colourCompactAscii(labelled != 0, first, window_rows, text);
@@ -443,7 +503,8 @@ class CloudSmooth {
               if (!labelled) coloured += w.rows;
             }
           return coloured;
-        });
+        },
+        output_leaf);
   }
   template <class Sink>
   StreamedColourStats processAndColorizeStreamed(Device &colour, int64_t chunk_capacity, Sink &&sink) const {
@@ -454,7 +515,8 @@ class CloudSmooth {
   // the two sweeps of processAndColorizeStreamed: after_a(rows, kept_rows) once per chunk of sweep A (the chunk is this
   // device's smoothing result), after_b(rows) -> coloured rows once per chunk of sweep B (the chunk is coloured on `colour`)
   template <class AfterA, class AfterB>
-  StreamedColourStats streamedSweeps(Device &colour, int64_t chunk_capacity, AfterA &&after_a, AfterB &&after_b) const {
+  StreamedColourStats streamedSweeps(Device &colour, int64_t chunk_capacity, AfterA &&after_a, AfterB &&after_b,
+                                     float output_leaf = 0.0f) const {
     using clock = std::chrono::steady_clock;
     pcp_context *src = dev_.get(), *dst = colour.get();
     StreamedColourStats st;
@@ -481,6 +543,7 @@ class CloudSmooth {
     colour.check(pcp_synchronize(dst));
     st.sweep_a_s = std::chrono::duration<double>(clock::now() - t0).count();
     t0 = clock::now();
+    if (output_leaf > 0.0f) colour.voxelReduceBegin(output_leaf);
     dev_.check(pcp_cloud_smooth_stream_seek(src, 0));
     for (int32_t c = 0; c < st.chunks; ++c) {
       int64_t m = 0, n = 0;
@@ -490,7 +553,18 @@ class CloudSmooth {
       colour.check(pcp_depth_pass(dst, 0, frames));  // builds this chunk's tile masks, as on a shard before the all-reduce(MIN)
       colour.check(pcp_depth_accum_apply(dst));
       colour.check(pcp_colorize_from_depth(dst, nullptr, nullptr));
+      if (output_leaf > 0.0f) {
+        colour.check(pcp_synchronize(dst));  // (the colour pass is asynchronous: the clock below takes the add alone)
+        const auto t1 = clock::now();
+        (void)colour.voxelReduceAdd();
+        st.voxel_add_s += std::chrono::duration<double>(clock::now() - t1).count();
+      }
       st.coloured += after_b(m);
+    }
+    if (output_leaf > 0.0f) {
+      const auto t1 = clock::now();
+      st.voxels = colour.voxelReduceFinish();
+      st.voxel_finish_s = std::chrono::duration<double>(clock::now() - t1).count();
     }
     st.sweep_b_s = std::chrono::duration<double>(clock::now() - t0).count();
     return st;

@@ -159,8 +159,27 @@ class PointCloudColorizer:
             out = dict(out, **self.engine.labels())
         return out
 
-    def run(self, download: bool = True, local_smooth_radius: float = 0.0, fuse_labels: bool = False):
+    def _voxel_output(self, leaf: float, fuse_labels: bool) -> dict:
+        """The voxel-grid output of the colour result that was just made ("Voxel-grid output")."""
+        ctx = self.engine.ctx
+        ctx.voxel_reduce_begin(leaf)
+        try:
+            rows = ctx.voxel_reduce_add()
+            ctx.voxel_reduce_finish()
+            out = ctx.voxel_reduce_fetch(want_label=fuse_labels)
+            out["rows"] = rows
+            return out
+        finally:
+            ctx.voxel_reduce_end()
+
+    def run(self, download: bool = True, local_smooth_radius: float = 0.0, fuse_labels: bool = False, output_leaf: float = 0.0):
         """Local points' colours: dict(rgb (n,3) uint8, has (n,) uint8).
+
+        output_leaf > 0: the dict gains `voxel` -- dict(xyz (m,3) float32, rgb (m,3) uint8, count (m,) uint32, rows, and label
+        (m,) uint8 with fuse_labels): one row per occupied voxel of that edge over the coloured points, reduced on the device
+        (what pcl::VoxelGrid at that leaf makes of the output files; DESIGN.md, "Voxel-grid output").  It reads the colours
+        as they are after the local smoothing.  With download=False only these rows leave the device.  The sums are local to
+        a rank and their exchange is not built: world > 1 raises ValueError.
 
         fuse_labels: one segmentation label per point from the masks of its top-5 views ("Fused segmentation
         labels"); the dict gains label, hits, views (n,) uint8 (rank-local, as the colours; without download they stay on
@@ -178,6 +197,9 @@ class PointCloudColorizer:
         if local_smooth_radius and self.world > 1:
             raise ValueError("local_smooth_radius: the local colour smoothing runs on one rank holding the whole map "
                              "(smooth the gathered words with Context.colour_smooth_local_packed)")
+        if output_leaf and self.world > 1:
+            raise ValueError("output_leaf: the voxel sums of the index shards would have to be added across ranks, which is not "
+                             "built; run it on one rank holding the whole map")
         if fuse_labels != getattr(self.engine, "fuse_labels", False):
             self.engine.set_label_fusion(fuse_labels)
         if self.world == 1:
@@ -188,7 +210,10 @@ class PointCloudColorizer:
                 out = self.engine.colour_from_depth(download=download)
             if local_smooth_radius:
                 out = self.engine.smooth_colours_local(local_smooth_radius, download=download)
-            return self._with_labels(out, fuse_labels, download)
+            out = self._with_labels(out, fuse_labels, download)
+            if output_leaf:
+                out = dict(out, voxel=self._voxel_output(output_leaf, fuse_labels))
+            return out
         import torch.distributed as dist
 
         F = self.engine.n_frames
@@ -555,7 +580,7 @@ class CloudSmooth:
                 ctx.cloud_smooth_stream_end()
 
     def process_and_colourise_streamed(self, colour_engine: HipEngine, chunk_capacity: int = 1 << 28, fuse_labels: bool = False,
-                                       on_smoothed=None, download: bool = True):
+                                       on_smoothed=None, download: bool = True, output_leaf: float = 0.0):
         """CloudSmooth::process followed by the colourisation of the smoothed cloud (PointCloudProcessor.cpp:139-145, 474-602)
         for clouds whose smoothed rows exceed one upload: the mirror of the C++ shim's processAndColorizeStreamed.  A chunk of
         the chain's voxel order is an index shard in time -- the depth maps are a MIN over all points and a point's colour
@@ -570,7 +595,13 @@ class CloudSmooth:
         Yields one dict per chunk with a coloured row: index (the source index the chain reports), xyz, rgb and, with
         fuse_labels, label.  download=False: the rows stay on the device and every dict holds only `count`, the chunk's
         coloured rows (what the device work alone costs).  `self.streamed_colour` holds chunks, rows, coloured and the seconds
-        of both sweeps."""
+        of both sweeps.
+
+        output_leaf > 0: the coloured rows of every chunk are also reduced on the device to one row per occupied voxel of
+        that edge ("Voxel-grid output"): an accumulation begins before sweep B, takes every chunk after it is
+        coloured and is finished after the sweep; `self.voxel_output` then holds dict(xyz, rgb, count[, label]) and
+        `self.streamed_colour` gains voxel_add_s, voxel_finish_s and the accumulator's stats.  With download=False these rows
+        are all that leaves the device."""
         import time
 
         ctx, col = self.engine.ctx, colour_engine.ctx
@@ -595,6 +626,11 @@ class CloudSmooth:
             col.synchronize()
             stats["sweep_a_s"] = time.perf_counter() - t0
             t0 = time.perf_counter()
+            self.voxel_output = None
+            if output_leaf:
+                col.voxel_reduce_begin(output_leaf)
+                stats["voxel_add_s"] = 0.0
+                stats["voxel_add_chunk_s"] = []
             ctx.cloud_smooth_stream_seek(0)
             for _ in range(chunks):
                 m = ctx.cloud_smooth_stream_next()
@@ -604,6 +640,12 @@ class CloudSmooth:
                 col.depth_pass()  # builds this chunk's tile masks, as on a shard before the all-reduce(MIN)
                 col.depth_accum_apply()
                 col.colorize_from_depth(download=False)
+                if output_leaf:
+                    col.synchronize()  # (the colour pass is asynchronous: the clock below takes the add alone)
+                    t1 = time.perf_counter()
+                    col.voxel_reduce_add()
+                    stats["voxel_add_chunk_s"].append(time.perf_counter() - t1)
+                    stats["voxel_add_s"] += stats["voxel_add_chunk_s"][-1]
                 out = col.colour_compact(capacity=None if download else 0, want_label=fuse_labels and download)
                 count = out.pop("count")
                 stats["coloured"] += count
@@ -613,6 +655,14 @@ class CloudSmooth:
                 elif count:
                     out["index"] = ctx.mls_fetch_index(m)[out["index"]]
                     yield out
+            if output_leaf:
+                t1 = time.perf_counter()
+                col.voxel_reduce_finish()
+                self.voxel_output = col.voxel_reduce_fetch(want_label=fuse_labels)
+                stats["voxel_finish_s"] = time.perf_counter() - t1
+                stats["voxel"] = col.voxel_reduce_stats()
             stats["sweep_b_s"] = time.perf_counter() - t0
         finally:
+            if output_leaf:
+                col.voxel_reduce_end()
             ctx.cloud_smooth_stream_end()
