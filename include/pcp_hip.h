@@ -59,7 +59,9 @@ extern "C" {
                                 entry points added, no layout changed: pcp_view_pair_stats / _counters, pcp_exposure_gains,
                                 pcp_set_frame_gains (per-keyframe exposure gains; off by default);
                                 entry points added, no layout changed: pcp_voxel_reduce_begin / _add / _finish / _fetch / _stats / _end,
-                                pcp_voxel_reduce_host (voxel-grid output; nothing runs unless called) */
+                                pcp_voxel_reduce_host (voxel-grid output; nothing runs unless called);
+                                entry points added, no layout changed: pcp_estimate_normals, pcp_normals_fetch,
+                                pcp_normals_moments_host, pcp_frame_geometry (geometry maps; nothing runs unless called) */
 
 #define PCP_OK 0
 #define PCP_ERR_INVALID (-1) /* bad argument */
@@ -759,6 +761,47 @@ int pcp_voxel_reduce_end(pcp_context *ctx);
  * n / capacity, a missing xyz / rgb, out_label without label: PCP_ERR_INVALID.  The message is at pcp_last_error(NULL). */
 int pcp_voxel_reduce_host(float leaf, int64_t n, const float *xyz, const uint8_t *rgb, const uint8_t *label, int64_t capacity,
                           float *out_xyz, uint8_t *out_rgb, uint8_t *out_label, uint32_t *out_count, int64_t *out_voxels);
+
+/* ---- geometry maps (scripts/genNormAndDistanceMask.py: class Crack, generate_norm_masks :200-231, generate_distance_masks :233-266) */
+/* A normal per point of the uploaded map and, per keyframe, the images the crack measurement reads: range, camera position,
+ * camera normal and the index of the point behind every pixel ("Geometry maps", GN1-GN7 and GM1-GM5).  Opt-in:
+ * nothing runs unless one of these is called, PCP_ABI_VERSION is unchanged and a caller detects support by the symbols.
+ * Kernels are timed under PCP_K_MISC.
+ *
+ * pcp_estimate_normals: once per uploaded cloud, in the world frame, over ALL neighbours within `radius`
+ * (0.005 <= radius <= 1, else PCP_ERR_INVALID).  The finite points are queries and candidates; j is a neighbour of i iff
+ * fl32((dx*dx + dy*dy) + dz*dz) <= t with d = fl32(p_j - p_i) and t the largest float with (double)t <= (double)radius^2; a
+ * point is its own neighbour.  Each accepted d is quantised to q = rint(d * 2^20) and the moments about the query -- n,
+ * S1[a] = sum q_a, S2[ab] = sum q_a q_b -- are exact 64-bit sums, so the result does not depend on the order of the
+ * neighbours or of the input.  C_ab = (double)S2_ab - ((double)S1_a * (double)S1_b) / (double)n; the normal is the
+ * eigenvector of C's smallest eigenvalue ev (pcl::eigen33's closed form), curvature = ev / trace(C) (0 when the trace is
+ * <= 0).  The SIGN of the world normal is unspecified.  A point is valid iff it is finite, n >= 3 and the three components
+ * are finite; an invalid point has normal (0, 0, 0) and curvature 0, its neighbour count is reported either way (0 for a
+ * non-finite point).  A point with 2^22 neighbours or more: PCP_ERR_RANGE.  *out_valid (nullable) = valid points.
+ * out_moments (nullable, host): 10 int64 per point in input order: n S1x S1y S1z S2xx xy xz yy yz zz.
+ * The result stays on the device (20 B per point) until the next pcp_upload_cloud* drops it.  Like every call that builds
+ * the search grid, it invalidates an open pcp_mls_stream / pcp_cloud_smooth_stream and a pcp_sor_partial.
+ * pcp_normals_fetch: the result in input order, every output nullable: out_normal 3 floats per point, out_curvature and
+ * out_neighbours one each.  Without an estimate on this cloud: PCP_ERR_STATE.
+ * pcp_normals_moments_host: host only, no context, no GPU: the moments of n <= 65536 points (xyz interleaved) by brute force
+ * over the pairs with the arithmetic the kernel uses (csrc/pcp_normals.hpp).  The message is at pcp_last_error(NULL).
+ *
+ * pcp_frame_geometry: images of image_width x image_height, row-major, every output nullable (host):
+ *   contributors  exactly the points pcp_frame_visible lists for the keyframe (kept by the configured cull, any cull_mode and
+ *                 depth source, and with a colour pixel); the pixel is pcp_project_frame's out_pixel;
+ *   winner        the contributor with the smallest fp32 range (pcp_project_frame's out_range), ties to the lowest input index;
+ *   out_index     the winner's input index, -1 for an empty pixel;  out_range its range;  out_xyz_cam 3 floats per pixel, the
+ *                 camera coordinates pcp_frame_visible returns;  out_normal_cam 3 floats per pixel: R * n_world (R the rotation
+ *                 of the keyframe's fp32 w2c, fp32, x*c0 + (y*c1 + z*c2)), negated when fl32((nx*x + ny*y) + nz*z) > 0 so
+ *                 that it faces the camera; an invalid normal stays (0, 0, 0).  Empty pixels hold 0 in the float images.
+ *   *out_pixels   occupied pixels.
+ * out_normal_cam without pcp_estimate_normals on this cloud: PCP_ERR_STATE.  The images' device buffers (40 B per pixel)
+ * are allocated on first use and freed by pcp_destroy. */
+int pcp_estimate_normals(pcp_context *ctx, float radius, int64_t *out_valid, int64_t *out_moments);
+int pcp_normals_fetch(pcp_context *ctx, float *out_normal, float *out_curvature, int32_t *out_neighbours);
+int pcp_normals_moments_host(float radius, int64_t n, const float *xyz, int64_t *out_moments);
+int pcp_frame_geometry(pcp_context *ctx, int32_t frame, int32_t *out_index, float *out_range, float *out_xyz_cam,
+                       float *out_normal_cam, int64_t *out_pixels);
 
 /* ---- precondition of the match-back(PointCloudProcessor.cpp:480-482,571) ------------------------------- */
 /* Number of map points that have ANOTHER map point closer than `radius` (fp32 squared distance, strict <, as

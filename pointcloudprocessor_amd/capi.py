@@ -292,6 +292,19 @@ def voxel_reduce_host(leaf: float, xyz, rgb, label=None, capacity: int | None = 
     return out
 
 
+def normals_moments_host(radius: float, xyz) -> np.ndarray:
+    """The moments of pcp_estimate_normals computed on the CPU by brute force over the pairs, with the arithmetic the kernel
+    uses (pcp_normals_moments_host: no context, no GPU; DESIGN.md "Geometry maps", GN2-GN4).  xyz (n, 3) float32, n <= 65536:
+    (n, 10) int64 -- n S1x S1y S1z S2xx xy xz yy yz zz per point."""
+    L = load()
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    out = np.zeros((xyz.shape[0], 10), np.int64)
+    rc = L.pcp_normals_moments_host(C.c_float(radius), C.c_int64(xyz.shape[0]), _ptr(xyz), _ptr(out))
+    if rc != PCP_OK:
+        raise PcpError(rc, L.pcp_last_error(None).decode())
+    return out
+
+
 def default_camera() -> Camera:
     cam = Camera()
     load().pcp_default_camera(C.byref(cam))
@@ -339,6 +352,7 @@ class Context:
             raise PcpError(rc, self.lib.pcp_last_error(None).decode())
         self.h = h
         self.n = 0
+        self.normals_radius = None  # radius of the live pcp_estimate_normals result (None: none on this cloud)
         self.n_frames = 0
         self.camera = None
         self.cull = None
@@ -387,11 +401,13 @@ class Context:
         y = np.ascontiguousarray(y, np.float32)
         z = np.ascontiguousarray(z, np.float32)
         assert len(x) == len(y) == len(z)
+        self.normals_radius = None
         self._check(self.lib.pcp_upload_cloud(self.h, _ptr(x), _ptr(y), _ptr(z), C.c_int64(len(x))))
         self.n = len(x)
 
     def upload_cloud_aos(self, pts: np.ndarray):
         pts = np.ascontiguousarray(pts)
+        self.normals_radius = None
         self._check(self.lib.pcp_upload_cloud_aos(self.h, _ptr(pts), C.c_int64(pts.shape[0]),
                                                   C.c_int64(pts.strides[0])))
         self.n = pts.shape[0]
@@ -400,6 +416,7 @@ class Context:
         """The rows of `src`'s latest smoothing result become this context's cloud, device to device
         (pcp_upload_cloud_from_result); returns the number of points."""
         n = C.c_int64()
+        self.normals_radius = None
         self._check(self.lib.pcp_upload_cloud_from_result(self.h, src.h, C.byref(n)))
         self.n = n.value
         return n.value
@@ -769,6 +786,40 @@ class Context:
 
     def voxel_reduce_end(self):
         self._check(self.lib.pcp_voxel_reduce_end(self.h))
+
+    # -- geometry maps ("Geometry maps") ---------------------------------
+    def estimate_normals(self, radius: float, want_moments: bool = False):
+        """A normal, a curvature and a neighbour count per point of the uploaded cloud, kept on the device until the next
+        upload (pcp_estimate_normals).  Returns the number of valid points; with want_moments (valid, moments (n, 10) int64)."""
+        valid = C.c_int64()
+        mom = np.zeros((self.n, 10), np.int64) if want_moments else None
+        self.normals_radius = None
+        self._check(self.lib.pcp_estimate_normals(self.h, C.c_float(radius), C.byref(valid), _ptr(mom)))
+        self.normals_radius = radius
+        return (valid.value, mom) if want_moments else valid.value
+
+    def normals_fetch(self) -> dict:
+        """dict(normal (n, 3) float32, curvature (n,) float32, neighbours (n,) int32) of the last estimate, input order."""
+        nrm = np.zeros((self.n, 3), np.float32)
+        cur = np.zeros(self.n, np.float32)
+        cnt = np.zeros(self.n, np.int32)
+        self._check(self.lib.pcp_normals_fetch(self.h, _ptr(nrm), _ptr(cur), _ptr(cnt)))
+        return dict(normal=nrm, curvature=cur, neighbours=cnt)
+
+    def frame_geometry(self, frame: int, normals: bool = True) -> dict:
+        """The geometry maps of one keyframe at camera resolution (pcp_frame_geometry): dict(index (H, W) int32, -1 = empty,
+        range (H, W) float32, xyz_cam (H, W, 3) float32, pixels = occupied count, and with normals normal_cam (H, W, 3))."""
+        hh, ww = self.camera.image_height, self.camera.image_width
+        idx = np.empty((hh, ww), np.int32)
+        rng = np.empty((hh, ww), np.float32)
+        cam = np.empty((hh, ww, 3), np.float32)
+        nrm = np.empty((hh, ww, 3), np.float32) if normals else None
+        px = C.c_int64()
+        self._check(self.lib.pcp_frame_geometry(self.h, C.c_int32(frame), _ptr(idx), _ptr(rng), _ptr(cam), _ptr(nrm), C.byref(px)))
+        out = dict(index=idx, range=rng, xyz_cam=cam, pixels=px.value)
+        if normals:
+            out["normal_cam"] = nrm
+        return out
 
     def colour_smooth_local(self, radius: float) -> int:
         """smoothColorsWithLocalRegion (PointCloudProcessor.cpp:634-703) in place on the colour result; returns the number

@@ -1493,6 +1493,26 @@ int cull_frame_indices(pcp_context *ctx, int32_t frame, int32_t *d_index, int64_
   return compact_flags(ctx, ctx->s_keep.p, n, d_index, capacity, count);
 }
 
+// the points of one keyframe that the cull keeps and generateColorMap can colour (pcp_frame_visible's list), ascending input
+// indices, into ctx->s_cell; ctx->n > 0
+static int visible_indices(pcp_context *ctx, int32_t frame, int64_t *m) {
+  int rc = single_frame_depth(ctx, frame);
+  if (rc != PCP_OK) return rc;
+  const size_t plane = plane_of(ctx);
+  PCP_HIP_TRY(ctx, ctx->s_cell.ensure(plane + 4));
+  if ((rc = frame_keep_flags(ctx, frame, true)) != PCP_OK) return rc;
+  return compact_flags(ctx, ctx->s_keep.p, ctx->n, ctx->s_cell.p, static_cast<int64_t>(plane), m);
+}
+
+int frame_contributors(pcp_context *ctx, const char *who, int32_t frame, int64_t *m) {
+  *m = 0;
+  int rc = check_ready(ctx, who, true);
+  if (rc != PCP_OK) return rc;
+  if ((rc = check_frame(ctx, who, frame)) != PCP_OK) return rc;
+  if (ctx->n == 0) return PCP_OK;
+  return visible_indices(ctx, frame, m);
+}
+
 }  // namespace pcp
 
 namespace pcp {
@@ -1849,12 +1869,9 @@ int pcp_frame_visible(pcp_context *ctx, int32_t frame, int64_t capacity, int32_t
   if (n == 0) return PCP_OK;
   if ((rc = ensure_images(ctx)) != PCP_OK) return rc;
   if ((rc = wait_images(ctx, frame, frame + 1)) != PCP_OK) return rc;
-  if ((rc = single_frame_depth(ctx, frame)) != PCP_OK) return rc;
-  const size_t plane = plane_of(ctx);
-  PCP_HIP_TRY(ctx, ctx->s_cell.ensure(plane + 4));
-  if ((rc = frame_keep_flags(ctx, frame, true)) != PCP_OK) return rc;
   int64_t m = 0;
-  if ((rc = compact_flags(ctx, ctx->s_keep.p, n, ctx->s_cell.p, static_cast<int64_t>(plane), &m)) != PCP_OK) return rc;
+  if ((rc = visible_indices(ctx, frame, &m)) != PCP_OK) return rc;
+  const size_t plane = plane_of(ctx);
   if (out_count) *out_count = m;
   const int64_t take = std::min(m, capacity);
   if (take == 0) return PCP_OK;

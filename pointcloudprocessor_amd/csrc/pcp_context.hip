@@ -531,6 +531,7 @@ static int store_cloud(pcp_context *ctx, const float *x, const float *y, const f
   ctx->colour_result_live = false;
   ctx->labels_live = false;
   match_table_release(ctx);  // PCP_MATCH_RADIUS: the table belongs to the cloud that is being replaced
+  normals_release(ctx);      // pcp_estimate_normals: so do the normals
   ctx->mls_count = 0;
   ctx->mls_result_live = false;
   ctx->vgd_next = ctx->css_next = -1;  // the streams of the smoothing stage belong to the cloud that is being replaced
@@ -620,7 +621,7 @@ int pcp_create(int32_t device, pcp_context **out) {
     const hipError_t pl[] = {hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_up_bbox)), preload_colour(), preload_mls(),
                              preload_nid(), preload_hpr(), preload_colour_smooth(), preload_match(),
                              preload_jpeg(), preload_stream_colour(), preload_ascii(), preload_ascii_parse(), preload_exposure(),
-                             preload_voxel_reduce()};
+                             preload_voxel_reduce(), preload_normals()};
     for (hipError_t x : pl)
       if (x != hipSuccess && e == hipSuccess) e = x;
   }
@@ -719,6 +720,7 @@ void pcp_destroy(pcp_context *ctx) {
   ctx->gains_dev.release();
   ctx->pair_stats.release();
   voxel_reduce_release(ctx);
+  geometry_release(ctx);
   match_table_release(ctx);
   ctx->match_moved.release();
   for (int k = 0; k < 2; ++k) {

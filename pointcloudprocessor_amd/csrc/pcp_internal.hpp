@@ -290,6 +290,15 @@ struct pcp_context {
   // voxel-grid output: belongs to the context, not to the cloud or the camera (only pcp_voxel_reduce_begin / _end and pcp_destroy drop it)
   pcp::VoxelReduce voxel_reduce;
 
+  // geometry maps (pcp_normals.hip): normal + curvature (float4) and neighbour count per point of the uploaded cloud, input
+  // order, dropped by the uploads; the key image and the four output images of pcp_frame_geometry (allocated on first use)
+  bool gn_live = false;
+  float gn_radius = 0.0f;
+  pcp::DevBuf<float> gn_normal;
+  pcp::DevBuf<int32_t> gn_count;
+  pcp::DevBuf<unsigned long long> gm_keys;
+  pcp::DevBuf<uint32_t> gm_out;  // index | range | xyz_cam (3) | normal_cam (3), W*H words each
+
   // PCP_MATCH_RADIUS (pcp_match.hip): the neighbour table within R_c, built by the first colour pass in that mode and
   // dropped by pcp_upload_cloud / pcp_set_frames (E depends on both).  Set A = points whose row holds another point.
   bool match_live = false;
@@ -531,6 +540,12 @@ hipError_t preload_ascii_parse();
 hipError_t preload_exposure();
 hipError_t preload_voxel_reduce();
 void voxel_reduce_release(pcp_context *ctx);  // the accumulator and its result (pcp_destroy)
+hipError_t preload_normals();
+void normals_release(pcp_context *ctx);   // the normals of the cloud that is being replaced (the uploads)
+void geometry_release(pcp_context *ctx);  // ... and the images of pcp_frame_geometry (pcp_destroy)
+// the list pcp_frame_visible reports for one keyframe (pcp_colour.hip): ascending input indices in ctx->s_cell, *m of them;
+// checks the context and the keyframe as that call does, under the caller's name
+int frame_contributors(pcp_context *ctx, const char *who, int32_t frame, int64_t *m);
 // EG5 (pcp_exposure.hip): the packed result from the live top-5 state under ctx->gains_dev (and the label words with label
 // fusion on); ctx->n > 0, a live state and set gains are the caller's to check
 int finalise_gained(pcp_context *ctx, uint32_t *result);

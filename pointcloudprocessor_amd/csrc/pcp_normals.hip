@@ -1,0 +1,512 @@
+// pcp_normals.hip -- geometry maps on gfx950 ("Geometry maps"): a normal per point of the uploaded map
+// (pcp_estimate_normals, rules GN1-GN7) and the per-pixel range / camera position / camera normal / index images of one
+// keyframe (pcp_frame_geometry, rules GM1-GM5) -- what scripts/genNormAndDistanceMask.py (class Crack, generate_norm_masks
+// :200-231, generate_distance_masks :233-266) scatters on the host, one point at a time, from the per-keyframe clouds.
+//
+// Normals: the finite points are both queries and candidates; j is a neighbour of i iff the fp32 squared distance is <= t
+// (LS2's threshold); each accepted offset is quantised to 2^-20 m and the ten moments about the query are exact int64 sums
+// (pcp_normals.hpp), so they do not depend on the order of the neighbours, the grid or the input order.  The covariance is
+// three fp64 operations per entry, the normal pcl::eigen33's smallest eigenvector (pcp_eigen33.hpp).
+// Search: as the local colour smoothing (pcp_colour_smooth.hip) -- the uniform grid of pcp_mls.hip build_grid (cell >= r,
+// reach <= 2), 16-B records (x, y, z, caller's index) in cell order, one wavefront per work item of up to 64 queries of ONE
+// cell, the candidate rows staged through LDS in tiles and read back as wave-wide broadcasts, one query per lane.
+//
+// Maps: the contributors are the list pcp_frame_visible reports; each issues one 64-bit atomicMin of
+// (range bits << 32 | input index) on its colour pixel, so the nearest point wins, ties go to the lowest index, and the
+// result does not depend on the arrival order.  A resolve kernel, one lane per pixel, writes the four images.
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <new>
+#include <thread>
+#include <vector>
+
+#include "pcp_device.hpp"
+#include "pcp_eigen33.hpp"
+#include "pcp_internal.hpp"
+#include "pcp_normals.hpp"
+
+namespace pcp {
+
+constexpr int kGnBlock = 256;   // the 1-D helper kernels
+constexpr int kGnQ = 64;        // queries per work item: one wavefront, one cell
+constexpr int kGnTile = 512;    // candidate records per LDS tile (8 KiB)
+constexpr int kGnMaxRows = 25;  // (2 reach + 1)^2 rows of neighbouring cells, reach <= 2
+
+static inline uint32_t gn_blocks(int64_t n) { return static_cast<uint32_t>(std::max<int64_t>(1, div_up(n, kGnBlock))); }
+
+// 1 = point j of the sorted copy has three finite coordinates (GN1)
+__global__ __launch_bounds__(kGnBlock) void k_gn_finite(const float *__restrict__ x, const float *__restrict__ y,
+                                                        const float *__restrict__ z, int64_t n, uint8_t *__restrict__ flag) {
+  const int64_t j = static_cast<int64_t>(blockIdx.x) * kGnBlock + threadIdx.x;
+  if (j >= n) return;
+  flag[j] = gn::finite3(x[j], y[j], z[j]) ? 1 : 0;
+}
+
+// the finite points as a view: point k of the view = sorted point pos[k], caller's index perm[pos[k]]
+__global__ __launch_bounds__(kGnBlock) void k_gn_gather(const float *__restrict__ x, const float *__restrict__ y,
+                                                        const float *__restrict__ z, const int32_t *__restrict__ perm,
+                                                        const int32_t *__restrict__ pos, int64_t m, float *__restrict__ vx,
+                                                        float *__restrict__ vy, float *__restrict__ vz,
+                                                        int32_t *__restrict__ vremap) {
+  const int64_t k = static_cast<int64_t>(blockIdx.x) * kGnBlock + threadIdx.x;
+  if (k >= m) return;
+  const int32_t j = pos[k];
+  vx[k] = x[j];
+  vy[k] = y[j];
+  vz[k] = z[j];
+  vremap[k] = perm[j];
+}
+
+// records in cell order: (x, y, z, the caller's index the result goes to)
+__global__ __launch_bounds__(kGnBlock) void k_gn_records(const float *__restrict__ gx, const float *__restrict__ gy,
+                                                         const float *__restrict__ gz, const int32_t *__restrict__ order,
+                                                         const int32_t *__restrict__ remap, int64_t m, uint4 *__restrict__ rec) {
+  const int64_t k = static_cast<int64_t>(blockIdx.x) * kGnBlock + threadIdx.x;
+  if (k >= m) return;
+  rec[k] = make_uint4(__float_as_uint(gx[k]), __float_as_uint(gy[k]), __float_as_uint(gz[k]),
+                      static_cast<uint32_t>(remap[order[k]]));
+}
+
+// place k opens a work item when it is the first place of its cell or kGnQ places after the previous opening
+__global__ __launch_bounds__(kGnBlock) void k_gn_items(const uint4 *__restrict__ rec, int64_t m, GridDesc g,
+                                                       const int32_t *__restrict__ start, uint8_t *__restrict__ flag) {
+  const int64_t k = static_cast<int64_t>(blockIdx.x) * kGnBlock + threadIdx.x;
+  if (k >= m) return;
+  const uint4 r = rec[k];
+  int32_t ix, iy, iz;
+  grid_coords(g, __uint_as_float(r.x), __uint_as_float(r.y), __uint_as_float(r.z), ix, iy, iz);
+  const int64_t first = cell_start(g, start, iz, iy, ix);
+  flag[k] = ((k - first) % kGnQ) == 0 ? 1 : 0;
+}
+
+// one work item: the queries k0 .. k0 + nq - 1 of one cell against the records of the neighbouring cells.
+// tally[0] += valid points, tally[1] = max(tally[1], neighbour count): one atomic of each per wavefront.
+__global__ __launch_bounds__(kGnQ) void k_gn_normals(const uint4 *__restrict__ rec, const int32_t *__restrict__ items, GridDesc g,
+                                                     const int32_t *__restrict__ start, float t, float4 *__restrict__ out_normal,
+                                                     int32_t *__restrict__ out_count, long long *__restrict__ out_moments,
+                                                     unsigned long long *__restrict__ tally) {
+  __shared__ uint4 tile[kGnTile];
+  __shared__ int32_t row_b[kGnMaxRows], row_e[kGnMaxRows];
+  const int32_t k0 = items[blockIdx.x];
+  const int lane = threadIdx.x;
+  int32_t ix, iy, iz;
+  {
+    const uint4 r0 = rec[k0];
+    grid_coords(g, __uint_as_float(r0.x), __uint_as_float(r0.y), __uint_as_float(r0.z), ix, iy, iz);
+  }
+  const int32_t nq = min(kGnQ, cell_start(g, start, iz, iy, ix + 1) - k0);
+  const bool active = lane < nq;
+  const uint4 q = rec[k0 + (active ? lane : 0)];
+  const float qx = __uint_as_float(q.x), qy = __uint_as_float(q.y), qz = __uint_as_float(q.z);
+  const int32_t R = g.reach, side = 2 * R + 1, rows = side * side;
+  if (lane < rows) {
+    const int32_t zz = iz + lane / side - R, yy = iy + lane % side - R;
+    int32_t b = 0, e = 0;
+    if (zz >= 0 && zz < g.nz && yy >= 0 && yy < g.ny) {
+      b = cell_start(g, start, zz, yy, max(ix - R, 0));
+      e = cell_start(g, start, zz, yy, min(ix + R, g.nx - 1) + 1);
+    }
+    row_b[lane] = b;
+    row_e[lane] = e;
+  }
+  __syncthreads();
+  gn::Moments mo;
+  gn::clear(mo);
+  for (int32_t row = 0; row < rows; ++row) {
+    const int32_t b = row_b[row], e = row_e[row];
+    for (int32_t t0 = b; t0 < e; t0 += kGnTile) {
+      const int32_t cnt = min(kGnTile, e - t0);
+      __syncthreads();  // the previous tile has been read by every lane
+      for (int32_t u = lane; u < cnt; u += kGnQ) tile[u] = rec[t0 + u];
+      __syncthreads();
+      if (active) {
+#pragma unroll 4
+        for (int32_t u = 0; u < cnt; ++u) {
+          const uint4 c = tile[u];
+          // every operation rounded on its own (-ffp-contract=off); the S2 terms are 32 x 32 -> 64 multiply-adds
+          gn::visit(mo, __uint_as_float(c.x) - qx, __uint_as_float(c.y) - qy, __uint_as_float(c.z) - qz, t);
+        }
+      }
+    }
+  }
+  // GN5-GN7 (an active query is its own neighbour: n >= 1)
+  float4 res = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  bool valid = false;
+  if (active) {
+    double C[6], ev, nrm[3];
+    gn::covariance(mo, C);
+    smallest_eigenpair(C, ev, nrm);
+    const double trace = (C[0] + C[3]) + C[5];
+    const float nx = static_cast<float>(nrm[0]), ny = static_cast<float>(nrm[1]), nz = static_cast<float>(nrm[2]);
+    valid = mo.n >= gn::kMinNeighbours && gn::finite3(nx, ny, nz);
+    if (valid) res = make_float4(nx, ny, nz, trace > 0.0 ? static_cast<float>(ev / trace) : 0.0f);
+  }
+  const unsigned long long votes = __ballot(valid);
+  uint32_t most = active ? static_cast<uint32_t>(mo.n) : 0u;  // (below 2^31: the cloud's size)
+  for (int o = 32; o >= 1; o >>= 1) most = max(most, static_cast<uint32_t>(__shfl_xor(static_cast<int>(most), o, 64)));
+  if (lane == 0) {
+    if (votes) atomicAdd(tally, static_cast<unsigned long long>(__popcll(votes)));
+    atomicMax(tally + 1, static_cast<unsigned long long>(most));
+  }
+  if (!active) return;
+  const int64_t i = static_cast<int64_t>(q.w);
+  out_normal[i] = res;
+  out_count[i] = static_cast<int32_t>(mo.n);
+  if (out_moments) {
+    int64_t w[gn::kMomentWords];
+    gn::store(mo, w);
+#pragma unroll
+    for (int a = 0; a < gn::kMomentWords; ++a) out_moments[i * gn::kMomentWords + a] = w[a];
+  }
+}
+
+// ---- geometry maps ------------------------------------------------------------------------------------------------------
+constexpr unsigned long long kGmEmpty = ~0ull;
+
+__global__ __launch_bounds__(kGnBlock) void k_gm_clear(unsigned long long *__restrict__ keys, int64_t px) {
+  const int64_t p = static_cast<int64_t>(blockIdx.x) * kGnBlock + threadIdx.x;
+  if (p < px) keys[p] = kGmEmpty;
+}
+
+// GM2: one atomicMin per contributor (the list of pcp_frame_visible: every entry has a colour pixel; the test stays as a bound)
+__global__ __launch_bounds__(kGnBlock) void k_gm_scatter(const float *__restrict__ x, const float *__restrict__ y,
+                                                         const float *__restrict__ z, DevCamera cam, DevFrame fr,
+                                                         const int32_t *__restrict__ index, int64_t m, int64_t px,
+                                                         unsigned long long *__restrict__ keys) {
+  const int64_t k = static_cast<int64_t>(blockIdx.x) * kGnBlock + threadIdx.x;
+  if (k >= m) return;
+  const int32_t i = index[k];
+  const Projected p = project_point(cam, fr.w2c, x[i], y[i], z[i]);
+  if (p.pixel < 0 || p.pixel >= px) return;
+  const float range = static_cast<float>(range64(p.xc, p.yc, p.zc));  // what pcp_project_frame reports; positive: bits order as values
+  atomicMin(keys + p.pixel, (static_cast<unsigned long long>(__float_as_uint(range)) << 32) | static_cast<uint32_t>(i));
+}
+
+// GM3 / GM4: one lane per pixel; *occupied += pixels with a winner (one atomic per wavefront)
+__global__ __launch_bounds__(kGnBlock) void k_gm_resolve(const unsigned long long *__restrict__ keys, int64_t px,
+                                                         const float *__restrict__ x, const float *__restrict__ y,
+                                                         const float *__restrict__ z, DevFrame fr,
+                                                         const float4 *__restrict__ normals, int32_t *__restrict__ out_index,
+                                                         float *__restrict__ out_range, float *__restrict__ out_xyz,
+                                                         float *__restrict__ out_normal, unsigned long long *__restrict__ occupied) {
+  const int64_t p = static_cast<int64_t>(blockIdx.x) * kGnBlock + threadIdx.x;
+  bool hit = false;
+  if (p < px) {
+    const unsigned long long key = keys[p];
+    hit = key != kGmEmpty;
+    int32_t idx = -1;
+    float range = 0.0f, xc = 0.0f, yc = 0.0f, zc = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f;
+    if (hit) {
+      idx = static_cast<int32_t>(static_cast<uint32_t>(key));
+      range = __uint_as_float(static_cast<uint32_t>(key >> 32));
+      xform(fr.w2c, x[idx], y[idx], z[idx], xc, yc, zc);
+      if (normals) {
+        const float4 n = normals[idx];
+        if (n.x != 0.0f || n.y != 0.0f || n.z != 0.0f) {  // (an invalid normal stays (0, 0, 0))
+          const float *m = fr.w2c;  // xform's association without the translation
+          nx = n.x * m[0] + (n.y * m[1] + n.z * m[2]);
+          ny = n.x * m[4] + (n.y * m[5] + n.z * m[6]);
+          nz = n.x * m[8] + (n.y * m[9] + n.z * m[10]);
+          if ((nx * xc + ny * yc) + nz * zc > 0.0f) {  // faces away from the camera
+            nx = -nx;
+            ny = -ny;
+            nz = -nz;
+          }
+        }
+      }
+    }
+    out_index[p] = idx;
+    out_range[p] = range;
+    out_xyz[3 * p + 0] = xc;
+    out_xyz[3 * p + 1] = yc;
+    out_xyz[3 * p + 2] = zc;
+    out_normal[3 * p + 0] = nx;
+    out_normal[3 * p + 1] = ny;
+    out_normal[3 * p + 2] = nz;
+  }
+  const unsigned long long votes = __ballot(hit);
+  if ((threadIdx.x & 63) == 0 && votes) atomicAdd(occupied, static_cast<unsigned long long>(__popcll(votes)));
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------
+// per-call scratch: released when the call returns
+struct GnScratch {
+  DevBuf<uint8_t> flag;
+  DevBuf<int32_t> pos, vremap, items;
+  DevBuf<float> vxyz;
+  DevBuf<uint4> rec;
+  DevBuf<long long> moments;
+  ~GnScratch() {
+    flag.release();
+    pos.release();
+    vremap.release();
+    items.release();
+    vxyz.release();
+    rec.release();
+    moments.release();
+  }
+};
+
+void normals_release(pcp_context *ctx) {
+  ctx->gn_live = false;
+  ctx->gn_normal.release();
+  ctx->gn_count.release();
+}
+
+void geometry_release(pcp_context *ctx) {
+  normals_release(ctx);
+  ctx->gm_keys.release();
+  ctx->gm_out.release();
+}
+
+// the m > 0 finite points of view cv: grid, records in cell order, work items, the moments and the solve
+static int normals_finite(pcp_context *ctx, const CloudView &cv, float radius, float t, GnScratch &s) {
+  const int64_t m = cv.n;
+  // build_grid replaces the grid that an open MLS stream or a pcp_sor_partial rests on (as every call that builds one does)
+  ctx->vgd_next = -1;
+  ctx->css_next = -1;
+  ctx->sor_partial_slab = ctx->sor_partial_slabs = -1;
+  // cell edge: the radius (reach 1), but never finer than ~8 cells per point (as the local colour smoothing)
+  const double vol = std::max<double>(cv.mx[0] - cv.mn[0], 1e-3) * std::max<double>(cv.mx[1] - cv.mn[1], 1e-3) *
+                     std::max<double>(cv.mx[2] - cv.mn[2], 1e-3);
+  const float by_density = static_cast<float>(std::cbrt(vol / (8.0 * static_cast<double>(m))));
+  const float cell = std::max(radius * 1.001f, by_density);
+  GridDesc g;
+  int rc = build_grid(ctx, cv, cell, radius, &g);
+  if (rc != PCP_OK) return rc;
+  if (g.reach < 1 || (2 * g.reach + 1) * (2 * g.reach + 1) > kGnMaxRows)
+    return set_error(ctx, PCP_ERR_INVALID, "pcp_estimate_normals: grid reach %d outside 1..2", g.reach);
+  const size_t gplane = (static_cast<size_t>(m) + 3) & ~size_t(3);
+  PCP_HIP_TRY(ctx, s.rec.ensure(static_cast<size_t>(m) + 4));
+  PCP_HIP_TRY(ctx, s.flag.ensure(static_cast<size_t>(m) + 16));
+  PCP_HIP_TRY(ctx, s.items.ensure(static_cast<size_t>(m) + 4));
+  {
+    LaunchTimer lt(ctx, PCP_K_MISC);
+    hipLaunchKernelGGL(k_gn_records, dim3(gn_blocks(m)), dim3(kGnBlock), 0, ctx->stream, ctx->g_xyz.p, ctx->g_xyz.p + gplane,
+                       ctx->g_xyz.p + 2 * gplane, ctx->g_order.p, cv.remap, m, s.rec.p);
+    hipLaunchKernelGGL(k_gn_items, dim3(gn_blocks(m)), dim3(kGnBlock), 0, ctx->stream, s.rec.p, m, g, ctx->g_start.p, s.flag.p);
+    PCP_HIP_TRY(ctx, hipGetLastError());
+  }
+  int64_t n_items = 0;
+  if ((rc = compact_flags(ctx, s.flag.p, m, s.items.p, m, &n_items)) != PCP_OK) return rc;
+  PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->s_counter.p, 0, 16, ctx->stream));  // (compact_flags left its total there)
+  {
+    LaunchTimer lt(ctx, PCP_K_MISC);
+    if (n_items > 0)
+      hipLaunchKernelGGL(k_gn_normals, dim3(static_cast<uint32_t>(n_items)), dim3(kGnQ), 0, ctx->stream, s.rec.p, s.items.p, g,
+                         ctx->g_start.p, t, reinterpret_cast<float4 *>(ctx->gn_normal.p), ctx->gn_count.p, s.moments.p,
+                         ctx->s_counter.p);
+    PCP_HIP_TRY(ctx, hipGetLastError());
+  }
+  return PCP_OK;
+}
+
+static int estimate_normals(pcp_context *ctx, float radius, int64_t *out_valid, int64_t *out_moments) {
+  const int64_t n = ctx->n;
+  const size_t sn = static_cast<size_t>(n);
+  ctx->gn_live = false;
+  PCP_HIP_TRY(ctx, ctx->gn_normal.ensure(4 * sn + 4));
+  PCP_HIP_TRY(ctx, ctx->gn_count.ensure(sn + 4));
+  // GN7: a point that is not a query (non-finite) keeps normal (0, 0, 0), curvature 0, count 0
+  PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->gn_normal.p, 0, (4 * sn + 4) * 4, ctx->stream));
+  PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->gn_count.p, 0, (sn + 4) * 4, ctx->stream));
+  GnScratch s;
+  if (out_moments) {
+    PCP_HIP_TRY(ctx, s.moments.ensure(sn * gn::kMomentWords + 4));
+    PCP_HIP_TRY(ctx, hipMemsetAsync(s.moments.p, 0, sn * gn::kMomentWords * 8, ctx->stream));
+  }
+  const float t = gn::threshold_of(radius);
+  const size_t plane = (sn + 3) & ~size_t(3);
+  CloudView cv{};
+  cv.x = ctx->sxyz.p;
+  cv.y = ctx->sxyz.p + plane;
+  cv.z = ctx->sxyz.p + 2 * plane;
+  cv.remap = ctx->perm.p;
+  cv.n = n;
+  for (int a = 0; a < 3; ++a) {  // the box of the finite coordinates (a superset of the finite points' box)
+    cv.mn[a] = ctx->host_min[static_cast<size_t>(a)];
+    cv.mx[a] = ctx->host_max[static_cast<size_t>(a)];
+  }
+  if (ctx->nonfinite_points > 0) {
+    // GN1: the grid (which needs finite coordinates) is built over the finite points only
+    PCP_HIP_TRY(ctx, s.flag.ensure(sn + 16));
+    PCP_HIP_TRY(ctx, s.pos.ensure(sn + 4));
+    hipLaunchKernelGGL(k_gn_finite, dim3(gn_blocks(n)), dim3(kGnBlock), 0, ctx->stream, cv.x, cv.y, cv.z, n, s.flag.p);
+    PCP_HIP_TRY(ctx, hipGetLastError());
+    int64_t m = 0;
+    int rc = compact_flags(ctx, s.flag.p, n, s.pos.p, n, &m);
+    if (rc != PCP_OK) return rc;
+    const size_t pm = (static_cast<size_t>(m) + 3) & ~size_t(3);
+    PCP_HIP_TRY(ctx, s.vxyz.ensure(3 * pm + 4));
+    PCP_HIP_TRY(ctx, s.vremap.ensure(static_cast<size_t>(m) + 4));
+    if (m > 0) {
+      hipLaunchKernelGGL(k_gn_gather, dim3(gn_blocks(m)), dim3(kGnBlock), 0, ctx->stream, cv.x, cv.y, cv.z, ctx->perm.p, s.pos.p, m,
+                         s.vxyz.p, s.vxyz.p + pm, s.vxyz.p + 2 * pm, s.vremap.p);
+      PCP_HIP_TRY(ctx, hipGetLastError());
+    }
+    cv.x = s.vxyz.p;
+    cv.y = s.vxyz.p + pm;
+    cv.z = s.vxyz.p + 2 * pm;
+    cv.remap = s.vremap.p;
+    cv.n = m;
+  }
+  PCP_HIP_TRY(ctx, ctx->s_counter.ensure(4));
+  PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->s_counter.p, 0, 16, ctx->stream));
+  if (cv.n > 0) {
+    int rc = normals_finite(ctx, cv, radius, t, s);
+    if (rc != PCP_OK) return rc;
+  }
+  unsigned long long tally[2] = {0, 0};
+  PCP_HIP_TRY(ctx, hipMemcpyAsync(tally, ctx->s_counter.p, 16, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_moments)
+    PCP_HIP_TRY(ctx, hipMemcpyAsync(out_moments, s.moments.p, sn * gn::kMomentWords * 8, hipMemcpyDeviceToHost, ctx->stream));
+  PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (also: the scratch is released on return)
+  // a tiny radius on a large map may take the sparse grid: do not keep its bitmap
+  if (ctx->g_occ.count > (size_t(1) << 25)) {
+    ctx->g_occ.release();
+    ctx->g_occ_rank.release();
+  }
+  if (static_cast<int64_t>(tally[1]) >= gn::kMaxNeighbours)
+    return set_error(ctx, PCP_ERR_RANGE, "pcp_estimate_normals: a point has %llu neighbours within %g (2^22 or more could overflow the moments)",
+                     tally[1], static_cast<double>(radius));
+  ctx->gn_live = true;
+  ctx->gn_radius = radius;
+  if (out_valid) *out_valid = static_cast<int64_t>(tally[0]);
+  return PCP_OK;
+}
+
+// (pcp_create loads every code object of the library up front: see preload_code_objects in pcp_context.hip)
+hipError_t preload_normals() {
+  hipFuncAttributes a;
+  return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_gn_normals));
+}
+
+}  // namespace pcp
+
+using namespace pcp;
+
+extern "C" {
+
+int pcp_estimate_normals(pcp_context *ctx, float radius, int64_t *out_valid, int64_t *out_moments) {
+  if (!ctx) return PCP_ERR_INVALID;
+  if (out_valid) *out_valid = 0;
+  if (!gn::radius_ok(radius))
+    return set_error(ctx, PCP_ERR_INVALID, "pcp_estimate_normals: radius %g outside [0.005, 1]", static_cast<double>(radius));
+  if (!ctx->xyz.p && ctx->n > 0) return set_error(ctx, PCP_ERR_STATE, "pcp_estimate_normals: no cloud uploaded");
+  PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (ctx->n == 0) {
+    ctx->gn_live = true;
+    ctx->gn_radius = radius;
+    return PCP_OK;
+  }
+  return estimate_normals(ctx, radius, out_valid, out_moments);
+}
+
+int pcp_normals_fetch(pcp_context *ctx, float *out_normal, float *out_curvature, int32_t *out_neighbours) {
+  if (!ctx) return PCP_ERR_INVALID;
+  if (!ctx->gn_live) return set_error(ctx, PCP_ERR_STATE, "pcp_normals_fetch: pcp_estimate_normals has not run on this cloud");
+  const int64_t n = ctx->n;
+  if (n == 0) return PCP_OK;
+  PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t sn = static_cast<size_t>(n);
+  std::vector<float> rows;
+  if (out_normal || out_curvature) {
+    try {
+      rows.resize(4 * sn);
+    } catch (const std::bad_alloc &) {
+      return set_error(ctx, PCP_ERR_NOMEM, "pcp_normals_fetch: out of host memory for %lld points", static_cast<long long>(n));
+    }
+    PCP_HIP_TRY(ctx, hipMemcpyAsync(rows.data(), ctx->gn_normal.p, 4 * sn * 4, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (out_neighbours) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_neighbours, ctx->gn_count.p, sn * 4, hipMemcpyDeviceToHost, ctx->stream));
+  PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  for (size_t i = 0; i < sn && !rows.empty(); ++i) {
+    if (out_normal) {
+      out_normal[3 * i + 0] = rows[4 * i + 0];
+      out_normal[3 * i + 1] = rows[4 * i + 1];
+      out_normal[3 * i + 2] = rows[4 * i + 2];
+    }
+    if (out_curvature) out_curvature[i] = rows[4 * i + 3];
+  }
+  return PCP_OK;
+}
+
+int pcp_normals_moments_host(float radius, int64_t n, const float *xyz, int64_t *out_moments) {
+  if (!gn::radius_ok(radius)) {
+    set_global_error("pcp_normals_moments_host: radius %g outside [0.005, 1]", static_cast<double>(radius));
+    return PCP_ERR_INVALID;
+  }
+  if (n < 0 || n > 65536 || (n > 0 && (!xyz || !out_moments))) {
+    set_global_error("pcp_normals_moments_host: n outside 0..65536 or a missing array");
+    return PCP_ERR_INVALID;
+  }
+  const float t = gn::threshold_of(radius);
+  // every query on its own (the rows do not interact): up to 8 host threads share them
+  auto rows = [=](int64_t i0, int64_t i1) {
+    for (int64_t i = i0; i < i1; ++i) {
+      gn::Moments mo;
+      gn::clear(mo);
+      const float qx = xyz[3 * i], qy = xyz[3 * i + 1], qz = xyz[3 * i + 2];
+      if (gn::finite3(qx, qy, qz))
+        for (int64_t j = 0; j < n; ++j) {
+          const float cx = xyz[3 * j], cy = xyz[3 * j + 1], cz = xyz[3 * j + 2];
+          if (gn::finite3(cx, cy, cz)) gn::visit(mo, cx - qx, cy - qy, cz - qz, t);
+        }
+      gn::store(mo, out_moments + i * gn::kMomentWords);
+    }
+  };
+  const int64_t workers = std::max<int64_t>(1, std::min<int64_t>({8, static_cast<int64_t>(std::thread::hardware_concurrency()), n / 1024}));
+  std::vector<std::thread> pool;
+  for (int64_t w = 1; w < workers; ++w) pool.emplace_back(rows, n * w / workers, n * (w + 1) / workers);
+  rows(0, n / workers);
+  for (std::thread &th : pool) th.join();
+  return PCP_OK;
+}
+
+int pcp_frame_geometry(pcp_context *ctx, int32_t frame, int32_t *out_index, float *out_range, float *out_xyz_cam,
+                       float *out_normal_cam, int64_t *out_pixels) {
+  if (!ctx) return PCP_ERR_INVALID;
+  if (out_pixels) *out_pixels = 0;
+  if (out_normal_cam && !ctx->gn_live)
+    return set_error(ctx, PCP_ERR_STATE, "pcp_frame_geometry: normal_cam needs pcp_estimate_normals on this cloud");
+  int64_t m = 0;
+  int rc = frame_contributors(ctx, "pcp_frame_geometry", frame, &m);  // GM1: the list of pcp_frame_visible, in ctx->s_cell
+  if (rc != PCP_OK) return rc;
+  const int64_t px = static_cast<int64_t>(ctx->dcam.img_w) * ctx->dcam.img_h;
+  if (px <= 0) return PCP_OK;
+  const size_t spx = static_cast<size_t>(px);
+  PCP_HIP_TRY(ctx, ctx->gm_keys.ensure(spx + 4));
+  PCP_HIP_TRY(ctx, ctx->gm_out.ensure(8 * spx + 4));
+  PCP_HIP_TRY(ctx, ctx->s_counter.ensure(4));
+  PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->s_counter.p, 0, 8, ctx->stream));
+  const size_t plane = (static_cast<size_t>(ctx->n) + 3) & ~size_t(3);
+  const float *x = ctx->xyz.p, *y = ctx->xyz.p + plane, *z = ctx->xyz.p + 2 * plane;
+  int32_t *d_index = reinterpret_cast<int32_t *>(ctx->gm_out.p);
+  float *d_range = reinterpret_cast<float *>(ctx->gm_out.p + spx);
+  float *d_xyz = reinterpret_cast<float *>(ctx->gm_out.p + 2 * spx);
+  float *d_normal = reinterpret_cast<float *>(ctx->gm_out.p + 5 * spx);
+  const DevFrame &fr = ctx->hframes[static_cast<size_t>(frame)];
+  {
+    LaunchTimer lt(ctx, PCP_K_MISC);
+    hipLaunchKernelGGL(k_gm_clear, dim3(gn_blocks(px)), dim3(kGnBlock), 0, ctx->stream, ctx->gm_keys.p, px);
+    if (m > 0)
+      hipLaunchKernelGGL(k_gm_scatter, dim3(gn_blocks(m)), dim3(kGnBlock), 0, ctx->stream, x, y, z, ctx->dcam, fr, ctx->s_cell.p, m, px,
+                         ctx->gm_keys.p);
+    hipLaunchKernelGGL(k_gm_resolve, dim3(gn_blocks(px)), dim3(kGnBlock), 0, ctx->stream, ctx->gm_keys.p, px, x, y, z, fr,
+                       out_normal_cam ? reinterpret_cast<const float4 *>(ctx->gn_normal.p) : nullptr, d_index, d_range, d_xyz,
+                       d_normal, ctx->s_counter.p);
+    PCP_HIP_TRY(ctx, hipGetLastError());
+  }
+  unsigned long long occupied = 0;
+  PCP_HIP_TRY(ctx, hipMemcpyAsync(&occupied, ctx->s_counter.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_index) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_index, d_index, spx * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_range) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_range, d_range, spx * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_xyz_cam) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_xyz_cam, d_xyz, 3 * spx * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_normal_cam) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_normal_cam, d_normal, 3 * spx * 4, hipMemcpyDeviceToHost, ctx->stream));
+  PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (out_pixels) *out_pixels = static_cast<int64_t>(occupied);
+  return PCP_OK;
+}
+
+}  // extern "C"

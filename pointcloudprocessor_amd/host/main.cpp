@@ -93,6 +93,18 @@
 //     --streamColour 1 the chunks are then compacted with capacity 0, so only the voxel rows leave the device.  --gpus N
 //     above 1 is refused: the voxel sums of the index shards would have to be added across GPUs, which is not built.  The
 //     voxel files are small and always go through the host writer, --deviceWriter 1 or not.
+//   * --geometryMaps 0|1 (new, default 0) and --normalRadius r (new, default 0.1; 0 = no normals): with 1, every selected
+//     keyframe also writes <outputPath>geometry_maps/<imageTimestamp>_range.npy, _xyz.npy, _normal.npy and _index.npy -- the
+//     distance_mask, points_3d_mask and norm_mask that scripts/genNormAndDistanceMask.py (generate_norm_masks :200-231,
+//     generate_distance_masks :233-266) scatters from filtered_pcd/ afterwards, at camera resolution, plus the index of the
+//     map point behind every pixel (NumPy format 1.0, little-endian <f4 / <i4, C order: (H, W), (H, W, 3), (H, W, 3),
+//     (H, W); empty pixels hold 0, index -1).  They are made on the GPU (pcp_estimate_normals once, pcp_frame_geometry per
+//     keyframe; DESIGN.md "Geometry maps") from the raw map, with the poses the colourisation uses (after the NID
+//     stage), by the configured cull: the nearest kept point wins a pixel, and the normals come from the whole map within
+//     --normalRadius (0.005 <= r <= 1) instead of from each keyframe's culled cloud.  --normalRadius 0 writes no _normal
+//     file.  No other output changes.  --gpus N above 1 is refused (an index shard sees only its own points; the per-pixel
+//     keys of the shards would have to be merged across GPUs, which is not built), and so is --enableMLS 1 (the colour
+//     stage then holds the smoothed cloud; maps of it are not built).
 #include <cfloat>
 #include <chrono>
 #include <cmath>
@@ -177,6 +189,8 @@ struct Options {
   bool balance_exposure = false;      // --balanceExposure 1: per-keyframe exposure gains from co-visible map points
   float output_leaf = 0.0f;           // --outputLeaf L: also write the voxel-grid output at that leaf (0: off)
   bool skip_full_cloud = false;       // --skip_full_cloud 1: with --outputLeaf, the full-resolution final files are not made
+  bool geometry_maps = false;         // --geometryMaps 1: per-keyframe range / xyz / normal / index images (geometry_maps/*.npy)
+  float normal_radius = 0.1f;         // --normalRadius r: neighbourhood of the map normals (0: no normals, no _normal file)
 };
 
 static bool parse_bool(const std::string &v) {  // boost::program_options bool semantics
@@ -271,6 +285,15 @@ static Options parse(int argc, char **argv) {
       o.output_leaf = lf;
     }
     else if (a == "--skip_full_cloud") o.skip_full_cloud = parse_bool(next());
+    else if (a == "--geometryMaps") o.geometry_maps = parse_bool(next());
+    else if (a == "--normalRadius") {
+      const std::string v = next();
+      char *end = nullptr;
+      const float r = std::strtof(v.c_str(), &end);
+      if (end == v.c_str() || *end != '\0' || !(r == 0.0f || (r >= 0.005f && r <= 1.0f)))
+        throw std::runtime_error("the argument ('" + v + "') for option '--normalRadius' is invalid (0 = no normals, or 0.005 <= r <= 1)");
+      o.normal_radius = r;
+    }
     else if (a == "--streamColour") {
       const std::string v = next();
       if (v != "0" && v != "1")
@@ -312,6 +335,12 @@ static Options parse(int argc, char **argv) {
   if (o.output_leaf > 0.0f && o.gpus > 1)
     throw std::runtime_error("the option '--outputLeaf' does not work with '--gpus N' above 1 (the voxel sums of the index shards would "
                              "have to be added across GPUs: not built)");
+  if (o.geometry_maps && o.gpus > 1)
+    throw std::runtime_error("the option '--geometryMaps 1' does not work with '--gpus N' above 1 (an index shard sees only its own "
+                             "points: the per-pixel keys of the shards would have to be merged across GPUs, which is not built)");
+  if (o.geometry_maps && o.enableMLS)
+    throw std::runtime_error("the option '--geometryMaps 1' does not work with '--enableMLS 1' (the maps are rendered from the raw "
+                             "map; maps of the smoothed cloud are not built)");
   if (o.balance_exposure) {
     auto refuse = [](const std::string &what, const std::string &why) {
       throw std::runtime_error("the option '--balanceExposure 1' does not work with " + what + " (" + why + ")");
@@ -356,7 +385,9 @@ static void usage(std::ostream &os) {
         "  --deviceWriter arg (=0)               Format the rows of every ASCII PCD on the GPU (same bytes; --gpus 1;\n"
         "                                        the --outputLeaf files are small and go through the host writer)\n"
         "  --deviceReader arg (=0)               Parse the rows of the ASCII PCDs that are read on the GPU (same floats)\n"
-        "  --balanceExposure arg (=0)            One brightness gain per keyframe from co-visible map points (--gpus 1)\n";
+        "  --balanceExposure arg (=0)            One brightness gain per keyframe from co-visible map points (--gpus 1)\n"
+        "  --geometryMaps arg (=0)               Also write range / xyz / normal / index images per keyframe as .npy (--gpus 1)\n"
+        "  --normalRadius arg (=0.1)             With --geometryMaps: neighbourhood of the map normals (0 = no normals)\n";
 }
 
 class Processor {
@@ -394,6 +425,7 @@ class Processor {
       applyNIDBasedPoseOptimization();
     else if (opt.enableInitialGuessManual)
       throw std::runtime_error("the manual initial-guess GUI is not part of this build");
+    if (opt.geometry_maps) writeGeometryMaps();  // (with the poses the colourisation is about to use)
     pcdColorizationAndSmooth();
   }
 
@@ -969,6 +1001,54 @@ class Processor {
       (void)dev.voxelReduceFinish();
     }
     writeVoxelFiles();
+  }
+
+  // one array as a NumPy format 1.0 file: little-endian, C order, the header padded to a multiple of 64 bytes
+  static void writeNpy(const std::string &path, const char *descr, const std::vector<size_t> &shape, const void *data, size_t bytes) {
+    std::string dict = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': (";
+    for (size_t k = 0; k < shape.size(); ++k) dict += std::to_string(shape[k]) + (shape.size() == 1 || k + 1 < shape.size() ? ", " : "");
+    dict += "), }";
+    while ((10 + dict.size() + 1) % 64 != 0) dict += ' ';
+    dict += '\n';
+    std::ofstream f(path, std::ios::binary);
+    const unsigned char head[10] = {0x93, 'N', 'U', 'M', 'P', 'Y', 1, 0, static_cast<unsigned char>(dict.size() & 0xff),
+                                    static_cast<unsigned char>(dict.size() >> 8)};
+    f.write(reinterpret_cast<const char *>(head), sizeof(head));
+    f.write(dict.data(), static_cast<std::streamsize>(dict.size()));
+    f.write(static_cast<const char *>(data), static_cast<std::streamsize>(bytes));
+    f.close();
+    if (!f) throw std::runtime_error("Couldn't save geometry map to: " + path);
+  }
+
+  // --geometryMaps 1: what scripts/genNormAndDistanceMask.py makes of filtered_pcd/ (generate_norm_masks :200-231,
+  // generate_distance_masks :233-266), per selected keyframe, from the map on the device
+  void writeGeometryMaps() {
+    Device &dev = gpu->device(0);
+    const bool normals = opt.normal_radius > 0.0f;
+    if (normals) {
+      Phase ph("normals_gpu_s");
+      const int64_t valid = dev.estimateNormals(opt.normal_radius);
+      std::cout << "map normals: radius " << opt.normal_radius << ", " << valid << " of " << cloud.size() << " points valid" << std::endl;
+    }
+    const fs::path dir(opt.outputPath + "geometry_maps/");
+    if (fs::exists(dir)) fs::remove_all(dir);
+    fs::create_directories(dir);
+    const ViewCulling vc(dev);
+    const size_t w = static_cast<size_t>(img_w), h = static_cast<size_t>(img_h);
+    for (size_t k = 0; k < keyframes.size(); ++k) {
+      GeometryMaps g;
+      {
+        Phase ph("geometry_maps_gpu_s");
+        g = vc.geometryMaps(static_cast<int>(k), img_w, img_h, normals);
+      }
+      Phase ph_w("geometry_maps_write_s");
+      const std::string stem = opt.outputPath + "geometry_maps/" + std::to_string(keyframes[k].imageTimestamp);
+      writeNpy(stem + "_range.npy", "<f4", {h, w}, g.range.data(), g.range.size() * 4);
+      writeNpy(stem + "_xyz.npy", "<f4", {h, w, 3}, g.xyz_cam.data(), g.xyz_cam.size() * 4);
+      if (normals) writeNpy(stem + "_normal.npy", "<f4", {h, w, 3}, g.normal_cam.data(), g.normal_cam.size() * 4);
+      writeNpy(stem + "_index.npy", "<i4", {h, w}, g.index.data(), g.index.size() * 4);
+      std::cout << "Geometry maps saved to: " << stem << "_*.npy, " << g.pixels << " pixels occupied" << std::endl;
+    }
   }
 
   // --balanceExposure 1: the staged colour stage with the exposure gains between the colour pass and the finalise, and the

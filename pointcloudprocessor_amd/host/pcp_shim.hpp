@@ -33,6 +33,16 @@ struct VoxelCloud {
   std::vector<uint32_t> count;  // rows of the coloured cloud in the voxel
 };
 
+// The geometry maps of one keyframe (pcp_hip.h, "geometry maps"): images of `width` x `height`, row-major
+struct GeometryMaps {
+  int32_t width = 0, height = 0;
+  int64_t pixels = 0;              // occupied
+  std::vector<int32_t> index;      // input index of the point behind the pixel, -1: empty
+  std::vector<float> range;        // distance_mask
+  std::vector<float> xyz_cam;      // 3 per pixel: points_3d_mask
+  std::vector<float> normal_cam;   // 3 per pixel: norm_mask (asked for), else empty
+};
+
 class Device {
  public:
   explicit Device(int ordinal = 0) {
@@ -146,6 +156,14 @@ class Device {
   }
   void voxelReduceEnd() { check(pcp_voxel_reduce_end(ctx_)); }
 
+  // ---- geometry maps: a normal per point of the uploaded map, once per upload (pcp_estimate_normals; what
+  // generate_norm_masks estimates per keyframe with Open3D, scripts/genNormAndDistanceMask.py:200-231); returns the valid points
+  int64_t estimateNormals(float radius) {
+    int64_t valid = 0;
+    check(pcp_estimate_normals(ctx_, radius, &valid, nullptr));
+    return valid;
+  }
+
   // ---- device PCD reader: the x y z intensity floats of a window of PCD ASCII rows (pcp_hip.h, "device PCD reader") ----
   struct ParsedRows {
     int64_t rows = 0, consumed = 0, bad_row = -1;
@@ -178,6 +196,22 @@ class ViewCulling {
     for (size_t i = 0; i < keep.size(); ++i)
       if (keep[i]) idx.push_back(static_cast<int32_t>(i));
     return idx;
+  }
+  // the images generate_distance_masks / generate_norm_masks scatter from the culled cloud of one keyframe
+  // (scripts/genNormAndDistanceMask.py:200-266), reduced on the device: the nearest kept point wins a pixel.  with_normals
+  // needs Device::estimateNormals on the uploaded cloud.
+  GeometryMaps geometryMaps(int keyframe, int32_t width, int32_t height, bool with_normals) const {
+    GeometryMaps g;
+    g.width = width;
+    g.height = height;
+    const size_t px = static_cast<size_t>(width) * static_cast<size_t>(height);
+    g.index.resize(px);
+    g.range.resize(px);
+    g.xyz_cam.resize(3 * px);
+    g.normal_cam.resize(with_normals ? 3 * px : 0);
+    dev_.check(pcp_frame_geometry(dev_.get(), keyframe, g.index.data(), g.range.data(), g.xyz_cam.data(),
+                                  with_normals ? g.normal_cam.data() : nullptr, &g.pixels));
+    return g;
   }
 
  private:

@@ -172,6 +172,24 @@ class PointCloudColorizer:
         finally:
             ctx.voxel_reduce_end()
 
+    def geometry_maps(self, frame: int, normal_radius: float = 0.1) -> dict:
+        """The geometry maps of one keyframe at camera resolution, reduced on the device ("Geometry maps"):
+        dict(index (H, W) int32 with -1 for an empty pixel, range (H, W), xyz_cam (H, W, 3), pixels, and -- with
+        normal_radius > 0 -- normal_cam (H, W, 3)): the distance_mask / points_3d_mask / norm_mask of
+        scripts/genNormAndDistanceMask.py, the nearest kept point winning a pixel.  The normals are estimated once per
+        uploaded cloud and radius, over the whole map.
+
+        An index shard sees only its own points, so world > 1 raises ValueError.  (The (range, index) keys of the shards
+        would merge by an all-reduce(MIN) over the key images, the winners' rows then coming from their owners; not built.)"""
+        if self.world > 1:
+            raise ValueError("geometry_maps: an index shard sees only its own points; the per-pixel keys of the shards would "
+                             "have to be merged across ranks (all-reduce MIN), which is not built: run it on one rank "
+                             "holding the whole map")
+        ctx = self.engine.ctx
+        if normal_radius and ctx.normals_radius != normal_radius:  # (None after an upload: the library dropped the estimate)
+            ctx.estimate_normals(normal_radius)
+        return ctx.frame_geometry(frame, normals=bool(normal_radius))
+
     def run(self, download: bool = True, local_smooth_radius: float = 0.0, fuse_labels: bool = False, output_leaf: float = 0.0):
         """Local points' colours: dict(rgb (n,3) uint8, has (n,) uint8).
 
