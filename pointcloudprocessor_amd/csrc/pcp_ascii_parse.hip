@@ -138,11 +138,6 @@ void ascii_parse_release(pcp_context *ctx) {
     if (s.res_h) (void)hipHostFree(s.res_h);
     s.stage = nullptr;
     s.res_h = nullptr;
-    s.text.release();
-    s.end.release();
-    s.tiles.release();
-    s.out.release();
-    s.res.release();
     for (hipEvent_t *e : {&s.staged, &s.parsed, &s.drained}) {
       if (*e) (void)hipEventDestroy(*e);
       *e = nullptr;

@@ -349,13 +349,13 @@ __global__ __launch_bounds__(kBlock) void k_tile_work_hist(const uint32_t *__res
   for (int b = threadIdx.x; b < kWorkBins; b += kBlock)
     if (cnt[b]) atomicAdd(&hist[b], cnt[b]);
 }
-__device__ __forceinline__ int32_t block_exclusive_scan(int32_t v, int32_t *total);
 // hist: the finished histogram; cursor[b] (zeroed): tiles of bin b placed so far
 __global__ __launch_bounds__(kBlock) void k_work_scatter(const int32_t *__restrict__ work, int64_t tiles,
                                                         const int32_t *__restrict__ hist, int32_t *__restrict__ cursor,
                                                         int32_t *__restrict__ order) {
   __shared__ int32_t cnt[kWorkBins];    // local count, then the workgroup's first slot of the bin
   __shared__ int32_t first[kWorkBins];  // number of tiles with more work than the bin
+  __shared__ int32_t ws[kScanBlock / 64];
   for (int b = threadIdx.x; b < kWorkBins; b += kBlock) cnt[b] = 0;
   {
     // heaviest bin first: thread t takes bins kWorkBins - 1 - 4 t ... kWorkBins - 4 - 4 t
@@ -367,7 +367,7 @@ __global__ __launch_bounds__(kBlock) void k_work_scatter(const int32_t *__restri
       mine += h[k];
     }
     int32_t total = 0;
-    int32_t run = block_exclusive_scan(mine, &total);
+    int32_t run = scan_block_exclusive(mine, &total, ws);
 #pragma unroll
     for (int k = 0; k < kPer; ++k) {
       first[kWorkBins - 1 - (static_cast<int>(threadIdx.x) * kPer + k)] = run;
@@ -1093,28 +1093,7 @@ __global__ __launch_bounds__(kBlock) void k_pack_mask(const uint8_t *__restrict_
 
 // ---- ordered compaction of a byte flag array (tile = 1024 flags) -------------
 constexpr int kTile = 1024;
-
-__device__ __forceinline__ int32_t block_exclusive_scan(int32_t v, int32_t *total) {
-  __shared__ int32_t wave_sum[kBlock / 64];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  int32_t incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int32_t t = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += t;
-  }
-  if (lane == 63) wave_sum[wid] = incl;
-  __syncthreads();
-  int32_t base = 0, tot = 0;
-#pragma unroll
-  for (int k = 0; k < kBlock / 64; ++k) {
-    if (k < wid) base += wave_sum[k];
-    tot += wave_sum[k];
-  }
-  __syncthreads();
-  *total = tot;
-  return base + incl - v;
-}
+static_assert(kBlock == kScanBlock, "the compaction kernels scan their workgroup with scan_block_exclusive (pcp_scan.hpp)");
 
 __global__ __launch_bounds__(kBlock) void k_tile_count(const uint8_t *__restrict__ flags, int64_t n,
                                                        int32_t *__restrict__ tile_count) {
@@ -1123,16 +1102,10 @@ __global__ __launch_bounds__(kBlock) void k_tile_count(const uint8_t *__restrict
 #pragma unroll
   for (int k = 0; k < 4; ++k)
     if (base + k < n) c += flags[base + k] ? 1 : 0;
+  __shared__ int32_t ws[kScanBlock / 64];
   int32_t total;
-  (void)block_exclusive_scan(c, &total);
+  (void)scan_block_exclusive(c, &total, ws);
   if (threadIdx.x == 0) tile_count[blockIdx.x] = total;
-}
-
-// single block: exclusive scan of tile counts in place, grand total to *total (scan_single_block, pcp_scan.hpp)
-constexpr int kScanTilesBlock = kScanSingle;
-__global__ __launch_bounds__(kScanTilesBlock) void k_scan_tiles(int32_t *__restrict__ tile_count, int64_t tiles,
-                                                                unsigned long long *__restrict__ total) {
-  scan_single_block(tile_count, tiles, total);
 }
 
 __global__ __launch_bounds__(kBlock) void k_tile_scatter(const uint8_t *__restrict__ flags, int64_t n,
@@ -1146,8 +1119,9 @@ __global__ __launch_bounds__(kBlock) void k_tile_scatter(const uint8_t *__restri
     fl[k] = base + k < n && flags[base + k];
     c += fl[k] ? 1 : 0;
   }
+  __shared__ int32_t ws[kScanBlock / 64];
   int32_t total;
-  int64_t pos = tile_offset[blockIdx.x] + block_exclusive_scan(c, &total);
+  int64_t pos = tile_offset[blockIdx.x] + scan_block_exclusive(c, &total, ws);
 #pragma unroll
   for (int k = 0; k < 4; ++k)
     if (fl[k]) {
@@ -1329,7 +1303,7 @@ int compact_flags(pcp_context *ctx, const uint8_t *flags, int64_t n, int32_t *ou
     LaunchTimer t(ctx, PCP_K_MISC);
     hipLaunchKernelGGL(k_tile_count, dim3(static_cast<uint32_t>(tiles)), dim3(kBlock), 0, ctx->stream, flags, n,
                        ctx->s_tiles.p);
-    hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(kScanTilesBlock), 0, ctx->stream, ctx->s_tiles.p, tiles, ctx->s_counter.p);
+    hipLaunchKernelGGL(k_scan_tile_offsets, dim3(1), dim3(kScanSingle), 0, ctx->stream, ctx->s_tiles.p, tiles, ctx->s_counter.p);
     if (out_index)
       hipLaunchKernelGGL(k_tile_scatter, dim3(static_cast<uint32_t>(tiles)), dim3(kBlock), 0, ctx->stream, flags, n,
                          ctx->s_tiles.p, out_index, capacity);

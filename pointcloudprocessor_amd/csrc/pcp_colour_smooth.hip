@@ -9,13 +9,12 @@
 //     exact 64-bit integer sums, so the result does not depend on the order of the neighbours (LS4);
 //   - every output reads the unsmoothed words (LS5); has = (r | g | b) != 0 afterwards (LS6).
 //
-// Search: the finite points are binned into the uniform grid of the MLS / SOR stages (pcp_mls.hip build_grid; cell >= r,
+// Search: the finite points are binned into the uniform grid of the radius searches (pcp_grid.hip; cell >= r,
 // reach 1) and copied into cell order as 16-B records (x, y, z, word).  One wavefront-sized workgroup takes up to 64
 // queries of ONE cell (one query per lane); their candidates are the 9 rows of 3 neighbouring cells, each a contiguous run
 // of records, staged through LDS in tiles of kLsTile records and read back as wave-wide broadcasts.  A cell of any size is
 // walked tile by tile (an all-duplicate cloud is one cell).  Results are stored in the caller's order.
 #include <algorithm>
-#include <cfloat>
 #include <cmath>
 
 #include "pcp_internal.hpp"
@@ -28,29 +27,6 @@ constexpr int kLsTile = 512;    // candidate records per LDS tile (8 KiB: ~20 on
 constexpr int kLsMaxRows = 25;  // (2 reach + 1)^2 rows of neighbouring cells, reach <= 2
 
 static inline uint32_t ls_blocks(int64_t n) { return static_cast<uint32_t>(std::max<int64_t>(1, div_up(n, kLsBlock))); }
-
-// 1 = point j of the sorted copy has three finite coordinates
-__global__ __launch_bounds__(kLsBlock) void k_ls_finite(const float *__restrict__ x, const float *__restrict__ y,
-                                                        const float *__restrict__ z, int64_t n, uint8_t *__restrict__ flag) {
-  const int64_t j = static_cast<int64_t>(blockIdx.x) * kLsBlock + threadIdx.x;
-  if (j >= n) return;
-  flag[j] = (fabsf(x[j]) <= FLT_MAX && fabsf(y[j]) <= FLT_MAX && fabsf(z[j]) <= FLT_MAX) ? 1 : 0;
-}
-
-// the finite points as a view: point k of the view = sorted point pos[k], caller's index perm[pos[k]]
-__global__ __launch_bounds__(kLsBlock) void k_ls_gather(const float *__restrict__ x, const float *__restrict__ y,
-                                                        const float *__restrict__ z, const int32_t *__restrict__ perm,
-                                                        const int32_t *__restrict__ pos, int64_t m, float *__restrict__ vx,
-                                                        float *__restrict__ vy, float *__restrict__ vz,
-                                                        int32_t *__restrict__ vremap) {
-  const int64_t k = static_cast<int64_t>(blockIdx.x) * kLsBlock + threadIdx.x;
-  if (k >= m) return;
-  const int32_t j = pos[k];
-  vx[k] = x[j];
-  vy[k] = y[j];
-  vz[k] = z[j];
-  vremap[k] = perm[j];
-}
 
 // records in cell order: (x, y, z, unsmoothed word) and the caller's index the result goes to
 __global__ __launch_bounds__(kLsBlock) void k_ls_records(const float *__restrict__ gx, const float *__restrict__ gy,
@@ -161,54 +137,35 @@ __global__ __launch_bounds__(kLsBlock) void k_ls_count_has(const uint32_t *__res
 
 // per-call scratch: released when the call returns (a 10 M-point map holds ~300 MB of it)
 struct LsScratch {
-  DevBuf<uint8_t> flag;
-  DevBuf<int32_t> pos, vremap, dst, items;
-  DevBuf<float> vxyz;
+  FiniteScratch fin;  // (its flags serve the work items once the view is gathered)
+  DevBuf<int32_t> dst, items;
   DevBuf<uint4> rec;
-  ~LsScratch() {
-    flag.release();
-    pos.release();
-    vremap.release();
-    dst.release();
-    items.release();
-    vxyz.release();
-    rec.release();
-  }
 };
 
 // the m > 0 finite points of view cv: grid, records in cell order, work items, the smoothing pass into d_out
 static int smooth_finite(pcp_context *ctx, const CloudView &cv, float radius, float t, const uint32_t *d_in, uint32_t *d_out,
                          LsScratch &s) {
   const int64_t m = cv.n;
-  // build_grid replaces the grid that an open MLS stream or a pcp_sor_partial rests on (as every call that builds one does)
-  ctx->vgd_next = -1;
-  ctx->css_next = -1;
-  ctx->sor_partial_slab = ctx->sor_partial_slabs = -1;
-  // cell edge: the radius (reach 1), but never finer than ~8 cells per point (pcp_close_pairs: a tiny radius on a large
-  // map would otherwise take the finest grid there is; the search is as exact with the coarser cell)
-  const double vol = std::max<double>(cv.mx[0] - cv.mn[0], 1e-3) * std::max<double>(cv.mx[1] - cv.mn[1], 1e-3) *
-                     std::max<double>(cv.mx[2] - cv.mn[2], 1e-3);
-  const float by_density = static_cast<float>(std::cbrt(vol / (8.0 * static_cast<double>(m))));
-  const float cell = std::max(radius * 1.001f, by_density);
   GridDesc g;
-  int rc = build_grid(ctx, cv, cell, radius, &g);
+  int rc = build_radius_grid(ctx, cv, radius, &g);
   if (rc != PCP_OK) return rc;
   if (g.reach < 1 || (2 * g.reach + 1) * (2 * g.reach + 1) > kLsMaxRows)
     return set_error(ctx, PCP_ERR_INVALID, "local colour smoothing: grid reach %d outside 1..2", g.reach);
   const size_t gplane = (static_cast<size_t>(m) + 3) & ~size_t(3);
+  DevBuf<uint8_t> &flag = s.fin.flag;
   PCP_HIP_TRY(ctx, s.rec.ensure(static_cast<size_t>(m) + 4));
   PCP_HIP_TRY(ctx, s.dst.ensure(static_cast<size_t>(m) + 4));
-  PCP_HIP_TRY(ctx, s.flag.ensure(static_cast<size_t>(m) + 16));
+  PCP_HIP_TRY(ctx, flag.ensure(static_cast<size_t>(m) + 16));
   PCP_HIP_TRY(ctx, s.items.ensure(static_cast<size_t>(m) + 4));
   {
     LaunchTimer lt(ctx, PCP_K_COLOUR_SMOOTH);
     hipLaunchKernelGGL(k_ls_records, dim3(ls_blocks(m)), dim3(kLsBlock), 0, ctx->stream, ctx->g_xyz.p, ctx->g_xyz.p + gplane,
                        ctx->g_xyz.p + 2 * gplane, ctx->g_order.p, cv.remap, m, d_in, s.rec.p, s.dst.p);
-    hipLaunchKernelGGL(k_ls_items, dim3(ls_blocks(m)), dim3(kLsBlock), 0, ctx->stream, s.rec.p, m, g, ctx->g_start.p, s.flag.p);
+    hipLaunchKernelGGL(k_ls_items, dim3(ls_blocks(m)), dim3(kLsBlock), 0, ctx->stream, s.rec.p, m, g, ctx->g_start.p, flag.p);
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
   int64_t n_items = 0;
-  if ((rc = compact_flags(ctx, s.flag.p, m, s.items.p, m, &n_items)) != PCP_OK) return rc;
+  if ((rc = compact_flags(ctx, flag.p, m, s.items.p, m, &n_items)) != PCP_OK) return rc;
   {
     LaunchTimer lt(ctx, PCP_K_COLOUR_SMOOTH);
     if (n_items > 0)
@@ -232,45 +189,12 @@ int colour_smooth_words(pcp_context *ctx, float radius, const uint32_t *d_in, ui
   float t = static_cast<float>(r2);
   if (static_cast<double>(t) > r2) t = std::nextafter(t, 0.0f);
   LsScratch s;
-  const size_t sn = static_cast<size_t>(n);
-  const size_t plane = (sn + 3) & ~size_t(3);
-  CloudView cv{};
-  cv.x = ctx->sxyz.p;
-  cv.y = ctx->sxyz.p + plane;
-  cv.z = ctx->sxyz.p + 2 * plane;
-  cv.remap = ctx->perm.p;
-  cv.n = n;
-  for (int a = 0; a < 3; ++a) {  // the box of the finite coordinates (a superset of the finite points' box)
-    cv.mn[a] = ctx->host_min[static_cast<size_t>(a)];
-    cv.mx[a] = ctx->host_max[static_cast<size_t>(a)];
-  }
-  if (ctx->nonfinite_points > 0) {
-    // LS1: the grid (which needs finite coordinates) is built over the finite points only
-    PCP_HIP_TRY(ctx, s.flag.ensure(sn + 16));
-    PCP_HIP_TRY(ctx, s.pos.ensure(sn + 4));
-    hipLaunchKernelGGL(k_ls_finite, dim3(ls_blocks(n)), dim3(kLsBlock), 0, ctx->stream, cv.x, cv.y, cv.z, n, s.flag.p);
-    PCP_HIP_TRY(ctx, hipGetLastError());
-    int64_t m = 0;
-    int rc = compact_flags(ctx, s.flag.p, n, s.pos.p, n, &m);
-    if (rc != PCP_OK) return rc;
-    const size_t pm = (static_cast<size_t>(m) + 3) & ~size_t(3);
-    PCP_HIP_TRY(ctx, s.vxyz.ensure(3 * pm + 4));
-    PCP_HIP_TRY(ctx, s.vremap.ensure(static_cast<size_t>(m) + 4));
-    hipLaunchKernelGGL(k_ls_gather, dim3(ls_blocks(m)), dim3(kLsBlock), 0, ctx->stream, cv.x, cv.y, cv.z, ctx->perm.p, s.pos.p,
-                       m, s.vxyz.p, s.vxyz.p + pm, s.vxyz.p + 2 * pm, s.vremap.p);
-    PCP_HIP_TRY(ctx, hipGetLastError());
-    cv.x = s.vxyz.p;
-    cv.y = s.vxyz.p + pm;
-    cv.z = s.vxyz.p + 2 * pm;
-    cv.remap = s.vremap.p;
-    cv.n = m;
-  }
-  const int64_t m = cv.n;
+  CloudView cv;
+  // LS1: the grid (which needs finite coordinates) is built over the finite points only
+  int rc = finite_view(ctx, /*with_remap=*/true, /*timing_slot=*/-1, s.fin, &cv);
+  if (rc != PCP_OK) return rc;
   PCP_HIP_TRY(ctx, ctx->s_counter.ensure(4));
-  if (m > 0) {
-    int rc = smooth_finite(ctx, cv, radius, t, d_in, d_out, s);
-    if (rc != PCP_OK) return rc;
-  }
+  if (cv.n > 0 && (rc = smooth_finite(ctx, cv, radius, t, d_in, d_out, s)) != PCP_OK) return rc;
   PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->s_counter.p, 0, 8, ctx->stream));
   {
     LaunchTimer lt(ctx, PCP_K_COLOUR_SMOOTH);
@@ -282,11 +206,7 @@ int colour_smooth_words(pcp_context *ctx, float radius, const uint32_t *d_in, ui
   PCP_HIP_TRY(ctx, hipMemcpyAsync(&c, ctx->s_counter.p, 8, hipMemcpyDeviceToHost, ctx->stream));
   PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (also: the scratch is released on return)
   if (out_has_count) *out_has_count = static_cast<int64_t>(c);
-  // a tiny radius on a large map may take the sparse grid: do not keep its bitmap
-  if (ctx->g_occ.count > (size_t(1) << 25)) {
-    ctx->g_occ.release();
-    ctx->g_occ_rank.release();
-  }
+  drop_large_grid_bitmap(ctx);  // (a tiny radius on a large map may take the sparse grid)
   return PCP_OK;
 }
 
@@ -315,10 +235,6 @@ int pcp_colour_smooth_local_packed(pcp_context *ctx, float radius, const uint32_
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
   DevBuf<uint32_t> words;  // the caller's words (host or device memory; in == out allowed)
   PCP_HIP_TRY(ctx, words.ensure(static_cast<size_t>(n) + 4));
-  struct Release {
-    DevBuf<uint32_t> &b;
-    ~Release() { b.release(); }
-  } release{words};
   PCP_HIP_TRY(ctx, hipMemcpyAsync(words.p, in_rgba, static_cast<size_t>(n) * 4, hipMemcpyDefault, ctx->stream));
   int rc = colour_smooth_words(ctx, radius, words.p, words.p, out_has_count);
   if (rc != PCP_OK) return rc;

@@ -439,7 +439,7 @@ int spatial_order(pcp_context *ctx, const float *dx, const float *dy, const floa
   PCP_HIP_TRY(ctx, hipMemcpyAsync(&nonfinite, ctx->s_counter.p, 8, hipMemcpyDeviceToHost, st));
   PCP_HIP_TRY(ctx, hipStreamSynchronize(st));
   if (out_nonfinite) *out_nonfinite = nonfinite;
-  partial.release();
+  partial.release();  // (before the sort's allocations)
   for (int a = 0; a < 3; ++a) {
     mn[a] = FLT_MAX;
     mx[a] = -FLT_MAX;
@@ -464,8 +464,6 @@ int spatial_order(pcp_context *ctx, const float *dx, const float *dy, const floa
   PCP_HIP_TRY(ctx, val_b.ensure(sn + 4));
   const int64_t hm = 256 * blocks;
   PCP_HIP_TRY(ctx, hist.ensure(static_cast<size_t>(hm) + 8));
-  const int64_t scan_tiles = std::max<int64_t>(1, (hm + 1 + kScanTile - 1) / kScanTile);
-  PCP_HIP_TRY(ctx, ctx->s_tiles.ensure(static_cast<size_t>(scan_tiles) + 4));
   hipLaunchKernelGGL(k_up_keys, dim3(up_blocks(n)), dim3(kUpBlock), 0, st, dx, dy, dz, n, mn[0], mn[1], mn[2], sc[0], sc[1],
                      sc[2], key_a.p, perm);
   uint32_t *kin = key_a.p, *kout = key_b.p;
@@ -474,12 +472,7 @@ int spatial_order(pcp_context *ctx, const float *dx, const float *dy, const floa
     const int32_t shift = 8 * pass;
     hipLaunchKernelGGL(k_up_radix_hist, dim3(static_cast<uint32_t>(blocks)), dim3(kUpBlock), 0, st, kin, n, shift, hist.p, blocks);
     PCP_HIP_TRY(ctx, hipMemsetAsync(hist.p + hm, 0, sizeof(int32_t), st));
-    hipLaunchKernelGGL(k_scan_tile_sums, dim3(static_cast<uint32_t>(scan_tiles)), dim3(kScanBlock), 0, st, hist.p, hm + 1,
-                       ctx->s_tiles.p);
-    hipLaunchKernelGGL(k_scan_tile_offsets, dim3(1), dim3(kScanSingle), 0, st, ctx->s_tiles.p, scan_tiles,
-                       static_cast<unsigned long long *>(nullptr));
-    hipLaunchKernelGGL(k_scan_apply, dim3(static_cast<uint32_t>(scan_tiles)), dim3(kScanBlock), 0, st, hist.p, hm + 1,
-                       ctx->s_tiles.p, hist.p);
+    PCP_HIP_TRY(ctx, scan_exclusive(st, hist.p, hm + 1, ctx->s_tiles, nullptr));
     hipLaunchKernelGGL(k_up_radix_scatter, dim3(static_cast<uint32_t>(blocks)), dim3(kUpBlock), 0, st, kin, vin, n, shift,
                        hist.p, blocks, kout, vout);
     std::swap(kin, kout);
@@ -489,11 +482,7 @@ int spatial_order(pcp_context *ctx, const float *dx, const float *dy, const floa
   // ---- Morton-ordered copy ----
   hipLaunchKernelGGL(k_up_gather, dim3(up_blocks(n)), dim3(kUpBlock), 0, st, dx, dy, dz, perm, n, sx, sy, sz, inv_perm);
   PCP_HIP_TRY(ctx, hipGetLastError());
-  PCP_HIP_TRY(ctx, hipStreamSynchronize(st));  // (the sort's scratch is freed here)
-  key_a.release();
-  key_b.release();
-  val_b.release();
-  hist.release();
+  PCP_HIP_TRY(ctx, hipStreamSynchronize(st));  // (the sort's scratch is freed on return)
   return PCP_OK;
 }
 
@@ -506,11 +495,7 @@ static int store_cloud(pcp_context *ctx, const float *x, const float *y, const f
   const size_t sn = static_cast<size_t>(n);
   // pad every SoA plane to a multiple of 4 floats so float4 loads stay aligned
   const size_t plane = (sn + 3) & ~size_t(3);
-  DevBuf<uint32_t> raw;
-  struct RawGuard {  // (the early returns below leave no staging buffer behind)
-    DevBuf<uint32_t> &b;
-    ~RawGuard() { b.release(); }
-  } raw_guard{raw};
+  DevBuf<uint32_t> raw;  // staging of the records
   if (aos_on_device && copy_aside && n > 0) {
     PCP_HIP_TRY(ctx, raw.ensure(static_cast<size_t>(n) * static_cast<size_t>(stride) / 4 + 4));
     PCP_HIP_TRY(ctx, hipMemcpyAsync(raw.p, aos, static_cast<size_t>(n) * static_cast<size_t>(stride), hipMemcpyDeviceToDevice, ctx->stream));
@@ -563,7 +548,7 @@ static int store_cloud(pcp_context *ctx, const float *x, const float *y, const f
   if (int rc = spatial_order(ctx, dx, dy, dz, n, ctx->perm.p, ctx->sxyz.p, ctx->sxyz.p + plane, ctx->sxyz.p + 2 * plane,
                              ctx->inv_perm.p, mn, mx, &nonfinite))
     return rc;
-  raw.release();
+  raw.release();  // (before the spheres' allocation)
   ctx->nonfinite_points = static_cast<int64_t>(nonfinite);
   for (int a = 0; a < 3; ++a) {
     ctx->host_min[a] = mn[a];
@@ -618,7 +603,7 @@ int pcp_create(int32_t device, pcp_context **out) {
     // units are loaded here, where a caller expects set-up time; the first call of every entry point then costs what the
     // others cost.
     hipFuncAttributes a;
-    const hipError_t pl[] = {hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_up_bbox)), preload_colour(), preload_mls(),
+    const hipError_t pl[] = {hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_up_bbox)), preload_colour(), preload_mls(), preload_grid(),
                              preload_nid(), preload_hpr(), preload_colour_smooth(), preload_match(),
                              preload_jpeg(), preload_stream_colour(), preload_ascii(), preload_ascii_parse(), preload_exposure(),
                              preload_voxel_reduce(), preload_normals()};
@@ -682,108 +667,22 @@ void pcp_destroy(pcp_context *ctx) {
   for (auto e : ctx->image_event)
     if (e) (void)hipEventDestroy(e);
   if (ctx->texels_idle) (void)hipEventDestroy(ctx->texels_idle);
-  for (auto &b : ctx->upload_stage) b.release();
-  for (auto &b : ctx->jpeg_planes) b.release();
   drain_timing(ctx);
   for (auto e : ctx->event_pool) (void)hipEventDestroy(e);
-  ctx->xyz.release();
-  ctx->sxyz.release();
-  ctx->perm.release();
-  ctx->inv_perm.release();
-  ctx->frames.release();
-  ctx->images.release();
-  ctx->hsv_tables.release();
-  ctx->depth.release();
-  ctx->depth_accum.release();
-  ctx->cc_out.release();
-  ctx->ascii_in.release();
-  ctx->ascii_len.release();
-  ctx->ascii_text.release();
-  ctx->ascii_tiles.release();
   ascii_parse_release(ctx);
   if (ctx->handoff) (void)hipEventDestroy(ctx->handoff);
-  ctx->depth_sq.release();
-  ctx->tile_sphere.release();
-  ctx->tile_mask.release();
-  ctx->tile_inside.release();
-  ctx->tile_work.release();
-  ctx->tile_order.release();
-  ctx->work_hist.release();
-  ctx->group_mask.release();
-  ctx->top_score.release();
-  ctx->top_rgb.release();
-  ctx->top_frame.release();
-  ctx->view_count.release();
-  ctx->rgba2[0].release();
-  ctx->rgba2[1].release();
-  ctx->labels.release();
-  ctx->gains_dev.release();
-  ctx->pair_stats.release();
-  voxel_reduce_release(ctx);
-  geometry_release(ctx);
-  match_table_release(ctx);
-  ctx->match_moved.release();
   for (int k = 0; k < 2; ++k) {
     if (ctx->result_ready[k]) (void)hipEventDestroy(ctx->result_ready[k]);
     if (ctx->copy_done[k]) (void)hipEventDestroy(ctx->copy_done[k]);
   }
   if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
-  ctx->s_cell.release();
-  ctx->s_pixel.release();
-  ctx->s_range.release();
-  ctx->s_cam.release();
-  ctx->s_keep.release();
-  ctx->s_u32.release();
-  ctx->s_counter.release();
-  ctx->s_tiles.release();
-  ctx->g_cell.release();
-  ctx->g_rank.release();
-  ctx->g_start.release();
-  ctx->g_occ.release();
-  ctx->g_occ_rank.release();
-  ctx->g_order.release();
-  ctx->g_xyz.release();
-  ctx->m_tmp.release();
-  ctx->s_dist.release();
-  ctx->css_dist.release();
-  ctx->s_kth.release();
-  ctx->css_words.release();
-  ctx->m_state.release();
-  ctx->slp_table.release();
-  ctx->c_perm.release();
-  ctx->m_flag.release();
-  ctx->intensity.release();
   for (auto &lane : ctx->hpr_lane) lane.release();
   if (ctx->hpr_fork) (void)hipEventDestroy(ctx->hpr_fork);
   for (auto &e : ctx->hpr_join)
     if (e) (void)hipEventDestroy(e);
-  ctx->hull_bits.release();
-  ctx->nid_pts.release();
-  ctx->nid_chunk_kf.release();
-  ctx->nid_hist.release();
-  ctx->m_sums.release();
-  ctx->c_index.release();
-  ctx->c_xyz.release();
-  ctx->c_mark.release();
-  ctx->c_where.release();
-  ctx->c_xyz2.release();
-  ctx->v_bitmap.release();
-  ctx->v_occ.release();
-  ctx->v_rank.release();
-  ctx->v_plane.release();
-  ctx->v_vox.release();
-  ctx->v_offsets.release();
-  ctx->mls_xyz.release();
-  ctx->mls_normal.release();
-  ctx->mls_curv.release();
-  ctx->mls_index.release();
-  ctx->mls_alt_xyz.release();
-  ctx->mls_alt_normal.release();
-  ctx->mls_alt_curv.release();
-  ctx->mls_alt_index.release();
   if (ctx->readback) (void)hipHostFree(ctx->readback);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
-  delete ctx;
+  delete ctx;  // every DevBuf of the context frees its memory here, with the context's device current
 }
 
 const char *pcp_last_error(const pcp_context *ctx) { return ctx ? ctx->error.c_str() : g_error.c_str(); }

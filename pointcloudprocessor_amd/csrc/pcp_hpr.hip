@@ -1952,19 +1952,6 @@ __global__ __launch_bounds__(kHprBlock) void k_hpr_zero(unsigned long long *__re
 // ------------------------------------------------------------------------------------------------------------------
 static inline uint32_t hpr_blocks(int64_t n) { return static_cast<uint32_t>(std::max<int64_t>(1, div_up(n, kHprBlock))); }
 
-static int hpr_scan(pcp_context *ctx, HprLane &L, int32_t *counts, int64_t entries) {
-  const int64_t tiles = div_up(entries, kScanTile);
-  PCP_HIP_TRY(ctx, L.tiles.ensure(static_cast<size_t>(tiles) + 4));
-  hipLaunchKernelGGL(k_scan_tile_sums, dim3(static_cast<uint32_t>(tiles)), dim3(kScanBlock), 0, L.stream, counts, entries,
-                     L.tiles.p);
-  hipLaunchKernelGGL(k_scan_tile_offsets, dim3(1), dim3(kScanSingle), 0, L.stream, L.tiles.p, tiles,
-                     static_cast<unsigned long long *>(nullptr));
-  hipLaunchKernelGGL(k_scan_apply, dim3(static_cast<uint32_t>(tiles)), dim3(kScanBlock), 0, L.stream, counts, entries,
-                     L.tiles.p, counts);
-  PCP_HIP_TRY(ctx, hipGetLastError());
-  return PCP_OK;
-}
-
 constexpr size_t kStatWords = kStatStride * (1 + kStatCopies);
 static_assert(kStatWords * sizeof(unsigned long long) <= pcp_context::kReadbackBytes, "readback scratch");
 
@@ -2030,7 +2017,6 @@ int hpr_finish(pcp_context *ctx, HprLane &L, bool timed) {
   L.busy = false;
   const int64_t n = ctx->n;
   const size_t cap = static_cast<size_t>(n);
-  int rc = PCP_OK;
   hipStream_t stream = L.stream;
   pcp_context *tctx = timed ? ctx : nullptr;
   const int32_t frame = L.frame;
@@ -2139,7 +2125,7 @@ int hpr_finish(pcp_context *ctx, HprLane &L, bool timed) {
   {
     LaunchTimer t(tctx, PCP_K_HPR);
     hipLaunchKernelGGL(k_hpr_count, dim3(hpr_blocks(m)), dim3(kHprBlock), 0, stream, ga, gb, G, cell, cstart);
-    if ((rc = hpr_scan(ctx, L, cstart, n_fine + 1)) != PCP_OK) return rc;
+    PCP_HIP_TRY(ctx, scan_exclusive(L.stream, cstart, n_fine + 1, L.tiles, nullptr));
     hipLaunchKernelGGL(k_hpr_scatter, dim3(hpr_blocks(m)), dim3(kHprBlock), 0, stream, px, py, pz, rho, cidx, cplace,
                        cell, m, cstart, cursor, sx, sy, sz, sidx, splace, scell,
                        reinterpret_cast<unsigned long long *>(crho), crep);

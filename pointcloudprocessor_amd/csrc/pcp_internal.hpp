@@ -10,6 +10,8 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "pcp_hip.h"
@@ -74,12 +76,15 @@ struct PendingEvent {
   int32_t kernel;
 };
 
-// seconds and bytes of the device allocations of this process (hipMalloc / hipFree inside DevBuf), for diagnostics
+// seconds and bytes of the device allocations the CALLING THREAD has made (hipMalloc / hipFree inside DevBuf), for
+// diagnostics.  One tally per thread: its reader, pcp_cloud_smooth_stream_begin, takes the difference over its own call on
+// its own thread, so it sees that call's allocations and nothing of the contexts other host threads drive (the per-GPU
+// threads of pcp_multi.hpp); a single-threaded caller gets what a process-wide tally gave.
 struct AllocTally {
   double seconds = 0.0, bytes = 0.0;
 };
 inline AllocTally &alloc_tally() {
-  static AllocTally t;
+  static thread_local AllocTally t;
   return t;
 }
 struct AllocClock {
@@ -87,10 +92,25 @@ struct AllocClock {
   ~AllocClock() { alloc_tally().seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
 };
 
+// Device memory, owned: freed by the destructor (on the device that is current then: pcp_destroy sets it before it deletes
+// the context), by release() where memory is to go early, and by ensure() when it has to grow.  Moves, never copies.
 template <typename T>
 struct DevBuf {
   T *p = nullptr;
   size_t count = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  DevBuf(DevBuf &&o) noexcept : p(std::exchange(o.p, nullptr)), count(std::exchange(o.count, 0)) {}
+  DevBuf &operator=(DevBuf &&o) noexcept {
+    if (this != &o) {
+      release();
+      p = std::exchange(o.p, nullptr);
+      count = std::exchange(o.count, 0);
+    }
+    return *this;
+  }
+  ~DevBuf() { release(); }
   hipError_t ensure(size_t n) {
     if (n <= count && p) return hipSuccess;
     AllocClock clk;  // (device allocations cost 20-40 ms per GB on this platform: the diagnostics of the long calls report them)
@@ -113,6 +133,7 @@ struct DevBuf {
     count = 0;
   }
 };
+static_assert(!std::is_copy_constructible_v<DevBuf<float>>, "DevBuf owns its memory");
 
 // device PCD reader (pcp_ascii_parse.hip): what one piece of text in flight owns -- pinned staging, the text, the offsets of its
 // '\n' bytes, the tile counts of the scan, four planes of parsed words, the result words (device and pinned) -- and the events
@@ -147,15 +168,7 @@ struct HprLane {
   uint8_t *d_flags = nullptr;
   uint32_t *hull_plane = nullptr;
   uint32_t bit = 0;
-  void release() {
-    index.release();
-    i32.release();
-    tiles.release();
-    f64.release();
-    cells_d.release();
-    cont.release();
-    state.release();
-    stats.release();
+  void release() {  // (the buffers free themselves)
     if (readback) (void)hipHostFree(readback);
     readback = nullptr;
     if (own_stream) (void)hipStreamDestroy(own_stream);
@@ -410,8 +423,10 @@ struct pcp_context {
 
 namespace pcp {
 
-// ---- the uniform grid of the radius searches (built by pcp_mls.hip build_grid; read by the MLS / SOR kernels and by
-// the local colour smoothing, pcp_colour_smooth.hip) -------------------------------------------------------------------
+// ---- the uniform grid of the radius searches (pcp_grid.hip; read by the MLS / SOR kernels and by the radius stages:
+// local colour smoothing, normals, the neighbour table of PCP_MATCH_RADIUS, pcp_close_pairs) ----------------------------
+constexpr double kMaxGridCells = 536870912.0;      // 2^29: dense table of cell starts
+constexpr double kMaxSparseCells = 34359738368.0;  // 2^35: bitmap (4 GiB) + running popcounts (2 GiB)
 struct GridDesc {
   float minx, miny, minz, inv_cell;
   int32_t nx, ny, nz;
@@ -463,10 +478,33 @@ struct CloudView {
 // geometry_only: just the grid description and a large enough cell table (the density probe of sor_run fills it).
 int build_grid(pcp_context *ctx, const CloudView &cv, float cell, float radius, GridDesc *out, bool geometry_only = false);
 
+// ---- the front end of the stages that search a fixed radius around every point of the uploaded cloud (pcp_grid.hip) ----
+// the uploaded cloud as a view: its Morton-ordered copy and the host box of its finite coordinates; with_remap: results
+// go under the caller's indices (remap = perm), else under Morton indices (remap = nullptr)
+CloudView uploaded_view(const pcp_context *ctx, bool with_remap);
+// per-call scratch of finite_view: released when the call that owns it returns
+struct FiniteScratch {
+  DevBuf<uint8_t> flag;
+  DevBuf<int32_t> pos, vremap;
+  DevBuf<float> vxyz;
+};
+// The finite points of the uploaded cloud as a view (the grid needs finite coordinates).  A cloud without non-finite points:
+// uploaded_view as it is, *pos = nullptr (view and Morton indices are the same).  Otherwise the finite points are flagged, compacted and gathered into `s`:
+// *pos (pos nullable) = view index -> Morton index, remap = view index -> caller's index (with_remap) or nullptr; cv->n
+// may be 0.  timing_slot: the PCP_K_* slot its launches are charged to, or -1 for none.
+int finite_view(pcp_context *ctx, bool with_remap, int32_t timing_slot, FiniteScratch &s, CloudView *cv,
+                const int32_t **pos = nullptr);
+// The grid of a radius stage over cv (cv.n > 0): ends the streams and the pcp_sor_partial that rest on the old grid, then
+// build_grid with cell edge max(radius * 1.001, the edge that gives ~8 cells per point), reach 1.
+int build_radius_grid(pcp_context *ctx, const CloudView &cv, float radius, GridDesc *out);
+// a radius stage may have taken the sparse grid: its bitmap is not kept when it is larger than 2^25 words
+void drop_large_grid_bitmap(pcp_context *ctx);
+
 int set_error(const pcp_context *ctx, int code, const char *fmt, ...);
 // one per translation unit with kernels: forces the runtime to load that unit's code object (pcp_context.hip preload_code_objects)
 hipError_t preload_colour();
 hipError_t preload_mls();
+hipError_t preload_grid();
 hipError_t preload_nid();
 hipError_t preload_hpr();
 hipError_t preload_colour_smooth();
@@ -539,17 +577,15 @@ hipError_t preload_ascii();
 hipError_t preload_ascii_parse();
 hipError_t preload_exposure();
 hipError_t preload_voxel_reduce();
-void voxel_reduce_release(pcp_context *ctx);  // the accumulator and its result (pcp_destroy)
 hipError_t preload_normals();
 void normals_release(pcp_context *ctx);   // the normals of the cloud that is being replaced (the uploads)
-void geometry_release(pcp_context *ctx);  // ... and the images of pcp_frame_geometry (pcp_destroy)
 // the list pcp_frame_visible reports for one keyframe (pcp_colour.hip): ascending input indices in ctx->s_cell, *m of them;
 // checks the context and the keyframe as that call does, under the caller's name
 int frame_contributors(pcp_context *ctx, const char *who, int32_t frame, int64_t *m);
 // EG5 (pcp_exposure.hip): the packed result from the live top-5 state under ctx->gains_dev (and the label words with label
 // fusion on); ctx->n > 0, a live state and set gains are the caller's to check
 int finalise_gained(pcp_context *ctx, uint32_t *result);
-void ascii_parse_release(pcp_context *ctx);  // the reader's slots, streams and events (pcp_destroy)
+void ascii_parse_release(pcp_context *ctx);  // the reader's pinned memory, streams and events (pcp_destroy)
 
 // removePointsWithNoColor's index list (pcp_stream_colour.hip): the rows of the current colour result whose has bit is set,
 // input order, into ctx->s_cell; *m = their number.  ctx->n > 0 and a live colour result are the caller's to check.

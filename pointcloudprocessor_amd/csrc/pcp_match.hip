@@ -9,7 +9,7 @@
 // A, and a point outside A is credited by its own samples only: the colour pass serves it exactly as PCP_MATCH_ROUNDTRIP
 // does, and k_match_fixup (pcp_colour.hip) recomputes, for each point of A, the samples of its row.
 //
-// Build (device): the finite points go into the uniform grid of the radius searches (pcp_mls.hip build_grid; cell >= R_c,
+// Build (device): the finite points go into the uniform grid of the radius searches (pcp_grid.hip; cell >= R_c,
 // reach 1); a count pass, an int64 exclusive scan over the rows of A, and a fill pass that also sorts each row by input index.
 // The table is built at the first colour pass in this mode and lives until the cloud or the keyframes change.
 #include <algorithm>
@@ -31,26 +31,6 @@ __device__ __forceinline__ float mt_sqdist(float ax, float ay, float az, float b
   d2 += dy * dy;
   d2 += dz * dz;
   return d2;
-}
-
-// 1 = Morton point j has three finite coordinates
-__global__ __launch_bounds__(kMtBlock) void k_mt_finite(const float *__restrict__ x, const float *__restrict__ y,
-                                                        const float *__restrict__ z, int64_t n, uint8_t *__restrict__ flag) {
-  const int64_t j = static_cast<int64_t>(blockIdx.x) * kMtBlock + threadIdx.x;
-  if (j >= n) return;
-  flag[j] = (fabsf(x[j]) <= FLT_MAX && fabsf(y[j]) <= FLT_MAX && fabsf(z[j]) <= FLT_MAX) ? 1 : 0;
-}
-
-// the finite points as a view: view point k = Morton point pos[k]
-__global__ __launch_bounds__(kMtBlock) void k_mt_gather(const float *__restrict__ x, const float *__restrict__ y,
-                                                        const float *__restrict__ z, const int32_t *__restrict__ pos, int64_t m,
-                                                        float *__restrict__ vx, float *__restrict__ vy, float *__restrict__ vz) {
-  const int64_t k = static_cast<int64_t>(blockIdx.x) * kMtBlock + threadIdx.x;
-  if (k >= m) return;
-  const int32_t j = pos[k];
-  vx[k] = x[j];
-  vy[k] = y[j];
-  vz[k] = z[j];
 }
 
 // count pass: per view point, the view points within R_c (itself included), stored at its Morton index
@@ -249,17 +229,9 @@ void match_table_release(pcp_context *ctx) {
 
 // per-build scratch, released on return
 struct MtScratch {
-  DevBuf<uint8_t> flag;
-  DevBuf<int32_t> pos, count;
-  DevBuf<float> vxyz;
+  FiniteScratch fin;
+  DevBuf<int32_t> count;
   DevBuf<int64_t> sums;
-  ~MtScratch() {
-    flag.release();
-    pos.release();
-    count.release();
-    vxyz.release();
-    sums.release();
-  }
 };
 
 int match_table_prepare(pcp_context *ctx) {
@@ -292,57 +264,16 @@ int match_table_prepare(pcp_context *ctx) {
   PCP_HIP_TRY(ctx, s.count.ensure(sn + 4));
   PCP_HIP_TRY(ctx, hipMemsetAsync(s.count.p, 0, sn * 4, ctx->stream));  // non-finite points: count 0, not in A
   const size_t plane = (sn + 3) & ~size_t(3);
-  CloudView cv{};
-  cv.x = ctx->sxyz.p;
-  cv.y = ctx->sxyz.p + plane;
-  cv.z = ctx->sxyz.p + 2 * plane;
-  cv.remap = nullptr;
-  cv.n = n;
-  for (int a = 0; a < 3; ++a) {  // the box of the finite coordinates
-    cv.mn[a] = ctx->host_min[static_cast<size_t>(a)];
-    cv.mx[a] = ctx->host_max[static_cast<size_t>(a)];
-  }
-  const int32_t *vpos = nullptr;  // view index -> Morton index (nullptr: the same)
-  if (ctx->nonfinite_points > 0) {
-    // the grid needs finite coordinates; a non-finite point takes no sample and matches nothing
-    PCP_HIP_TRY(ctx, s.flag.ensure(sn + 16));
-    PCP_HIP_TRY(ctx, s.pos.ensure(sn + 4));
-    {
-      LaunchTimer t(ctx, PCP_K_MISC);
-      hipLaunchKernelGGL(k_mt_finite, dim3(mt_blocks(n)), dim3(kMtBlock), 0, ctx->stream, cv.x, cv.y, cv.z, n, s.flag.p);
-      PCP_HIP_TRY(ctx, hipGetLastError());
-    }
-    int64_t m = 0;
-    int rc0 = compact_flags(ctx, s.flag.p, n, s.pos.p, n, &m);
-    if (rc0 != PCP_OK) return rc0;
-    const size_t pm = (static_cast<size_t>(m) + 3) & ~size_t(3);
-    PCP_HIP_TRY(ctx, s.vxyz.ensure(3 * pm + 4));
-    {
-      LaunchTimer t(ctx, PCP_K_MISC);
-      hipLaunchKernelGGL(k_mt_gather, dim3(mt_blocks(m)), dim3(kMtBlock), 0, ctx->stream, cv.x, cv.y, cv.z, s.pos.p, m, s.vxyz.p,
-                         s.vxyz.p + pm, s.vxyz.p + 2 * pm);
-      PCP_HIP_TRY(ctx, hipGetLastError());
-    }
-    cv.x = s.vxyz.p;
-    cv.y = s.vxyz.p + pm;
-    cv.z = s.vxyz.p + 2 * pm;
-    cv.n = m;
-    vpos = s.pos.p;
-  }
+  CloudView cv;
+  const int32_t *vpos;  // view index -> Morton index (nullptr: the same)
+  // the grid needs finite coordinates; a non-finite point takes no sample and matches nothing
+  int rcv = finite_view(ctx, /*with_remap=*/false, PCP_K_MISC, s.fin, &cv, &vpos);
+  if (rcv != PCP_OK) return rcv;
   const int64_t m = cv.n;
   int64_t na = 0;
   GridDesc g{};
   if (m > 1) {
-    // build_grid replaces the grid that an open MLS stream or a pcp_sor_partial rests on (as every call that builds one does)
-    ctx->vgd_next = -1;
-    ctx->css_next = -1;
-    ctx->sor_partial_slab = ctx->sor_partial_slabs = -1;
-    // cell edge: R_c (reach 1), but never finer than ~8 cells per point (as pcp_close_pairs)
-    const double vol = std::max<double>(cv.mx[0] - cv.mn[0], 1e-3) * std::max<double>(cv.mx[1] - cv.mn[1], 1e-3) *
-                       std::max<double>(cv.mx[2] - cv.mn[2], 1e-3);
-    const float by_density = static_cast<float>(std::cbrt(vol / (8.0 * static_cast<double>(m))));
-    const float cell = std::max(static_cast<float>(rc) * 1.001f, by_density);
-    int rcg = build_grid(ctx, cv, cell, static_cast<float>(rc), &g);
+    int rcg = build_radius_grid(ctx, cv, static_cast<float>(rc), &g);
     if (rcg != PCP_OK) return rcg;
     const size_t gplane = (static_cast<size_t>(m) + 3) & ~size_t(3);
     {
@@ -395,11 +326,7 @@ int match_table_prepare(pcp_context *ctx) {
     ctx->match_list.release();
   }
   PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the scratch is released on return)
-  // a large R_c on a sparse map may take the sparse grid: do not keep its bitmap
-  if (ctx->g_occ.count > (size_t(1) << 25)) {
-    ctx->g_occ.release();
-    ctx->g_occ_rank.release();
-  }
+  drop_large_grid_bitmap(ctx);  // (a large R_c on a sparse map may take the sparse grid)
   ctx->match_a = na;
   ctx->match_live = true;
   return PCP_OK;

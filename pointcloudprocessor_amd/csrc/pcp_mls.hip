@@ -4,7 +4,7 @@
 // (PCP/src/cloudSmooth.cpp:124-154, values PCP/src/PointCloudProcessor.cpp:67-86).
 //
 // The kd-tree of the reference is replaced by a uniform grid (cell >= r) built
-// on the device: cell histogram -> exclusive scan -> scatter -> per-cell order
+// on the device (pcp_grid.hip): cell histogram -> exclusive scan -> scatter -> per-cell order
 // fix-up (so results do not depend on atomic arrival order).  Points are then
 // processed in cell order: the 64 lanes of a wavefront sit in one or two cells
 // and walk the same 9 contiguous runs of neighbour candidates, so their loads
@@ -34,105 +34,11 @@
 namespace pcp {
 
 constexpr int kMB = 256;
-constexpr double kMaxGridCells = 536870912.0;      // 2^29: dense table of cell starts
-constexpr double kMaxSparseCells = 34359738368.0;  // 2^35: bitmap (4 GiB) + running popcounts (2 GiB)
 // pcp_cloud_smooth with SAMPLE_LOCAL_PLANE: most rows its trailing outlier removal takes.  Broken fits throw rows off their
 // surface, each such row is a stray of the filter that reads the whole cloud, so the filter's cost grows with rows x strays:
 // 10.2 M rows of a 300 k-point synthetic map 6.7 s, 59 M rows of 1 M points more than 100 s, 602 M rows of C3 more than 140 s
 // 
 constexpr int64_t kSlpChainMaxRows = int64_t(1) << 24;
-
-// cell id and arrival rank of every input point; histogram in `count`.  The views are spatially ordered (Morton copy of
-// the upload, survivors of it), so a wavefront's 64 points fall into a handful of cells: the lanes of one cell share one
-// atomic (ranks by lane, i.e. by index) instead of queueing 64 returning atomics on a few addresses (545 -> 60 us per
-// 10 M points); after kAggRounds distinct cells the remaining lanes go alone (an unordered view would have 64 of them).
-constexpr int kAggRounds = 8;
-__global__ __launch_bounds__(kMB) void k_grid_count(const float *__restrict__ x, const float *__restrict__ y,
-                                                    const float *__restrict__ z, int64_t n, GridDesc g,
-                                                    int32_t *__restrict__ cell, int32_t *__restrict__ rank,
-                                                    int32_t *__restrict__ count) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * kMB + threadIdx.x;
-  int32_t c = -1;
-  if (i < n) {
-    int32_t ix, iy, iz;
-    grid_coords(g, x[i], y[i], z[i], ix, iy, iz);
-    c = (iz * g.ny + iy) * g.nx + ix;
-    cell[i] = c;
-  }
-  const int lane = threadIdx.x & 63;
-  const unsigned long long below = (1ull << lane) - 1ull;
-  bool todo = c >= 0;
-  int32_t r = 0;
-  for (int round = 0; round < kAggRounds; ++round) {
-    const unsigned long long open = __ballot(todo);
-    if (!open) break;
-    const int32_t c0 = __shfl(c, __ffsll(open) - 1, 64);
-    const bool mine = todo && c == c0;
-    const unsigned long long same = __ballot(mine);
-    if (mine) {
-      int32_t base = 0;
-      if ((same & below) == 0) base = atomicAdd(count + c0, static_cast<int32_t>(__popcll(same)));  // lowest lane of the cell
-      base = __builtin_amdgcn_readfirstlane(base);
-      r = base + static_cast<int32_t>(__popcll(same & below));
-      todo = false;
-    }
-  }
-  if (todo) r = atomicAdd(count + c, 1);
-  if (i < n) rank[i] = r;
-}
-
-// Sparse form, step 1: one bit per occupied cell
-__global__ __launch_bounds__(kMB) void k_grid_mark(const float *__restrict__ x, const float *__restrict__ y,
-                                                   const float *__restrict__ z, int64_t n, GridDesc g,
-                                                   unsigned long long *__restrict__ occ) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * kMB + threadIdx.x;
-  if (i >= n) return;
-  int32_t ix, iy, iz;
-  grid_coords(g, x[i], y[i], z[i], ix, iy, iz);
-  const int64_t c = (static_cast<int64_t>(iz) * g.ny + iy) * g.nx + ix;
-  const unsigned long long bit = 1ull << (c & 63);
-  if (!(occ[c >> 6] & bit)) atomicOr(occ + (c >> 6), bit);  // spatially ordered views: most bits are set already
-}
-// step 2: set bits per word (scanned in place into the running popcount)
-__global__ __launch_bounds__(kMB) void k_grid_popc(const unsigned long long *__restrict__ occ, int64_t words,
-                                                   int32_t *__restrict__ count) {
-  const int64_t w = static_cast<int64_t>(blockIdx.x) * kMB + threadIdx.x;
-  if (w < words) count[w] = static_cast<int32_t>(__popcll(occ[w]));
-}
-// step 3: as k_grid_count, with the cell's place among the occupied cells as its id
-__global__ __launch_bounds__(kMB) void k_grid_count_sparse(const float *__restrict__ x, const float *__restrict__ y,
-                                                           const float *__restrict__ z, int64_t n, GridDesc g,
-                                                           int32_t *__restrict__ cell, int32_t *__restrict__ rank,
-                                                           int32_t *__restrict__ count) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * kMB + threadIdx.x;
-  int32_t c = -1;
-  if (i < n) {
-    int32_t ix, iy, iz;
-    grid_coords(g, x[i], y[i], z[i], ix, iy, iz);
-    c = cell_rank(g, (static_cast<int64_t>(iz) * g.ny + iy) * g.nx + ix);
-    cell[i] = c;
-  }
-  const int lane = threadIdx.x & 63;
-  const unsigned long long below = (1ull << lane) - 1ull;
-  bool todo = c >= 0;
-  int32_t r = 0;
-  for (int round = 0; round < kAggRounds; ++round) {
-    const unsigned long long open = __ballot(todo);
-    if (!open) break;
-    const int32_t c0 = __shfl(c, __ffsll(open) - 1, 64);
-    const bool mine = todo && c == c0;
-    const unsigned long long same = __ballot(mine);
-    if (mine) {
-      int32_t base = 0;
-      if ((same & below) == 0) base = atomicAdd(count + c0, static_cast<int32_t>(__popcll(same)));
-      base = __builtin_amdgcn_readfirstlane(base);
-      r = base + static_cast<int32_t>(__popcll(same & below));
-      todo = false;
-    }
-  }
-  if (todo) r = atomicAdd(count + c, 1);
-  if (i < n) rank[i] = r;
-}
 
 // surface-density probe: every `stride`-th point is binned and the cells that receive their first point are counted
 // (the estimate only sizes the SOR grid: any value gives the same, exact, result)
@@ -157,49 +63,6 @@ __global__ __launch_bounds__(kMB) void k_grid_probe(const float *__restrict__ x,
     for (int k = 0; k < kMB / 64; ++k) c += firsts[k];
     if (c) atomicAdd(occupied, static_cast<unsigned long long>(c));
   }
-}
-
-__global__ __launch_bounds__(kMB) void k_grid_scatter(int64_t n, const int32_t *__restrict__ cell,
-                                                      const int32_t *__restrict__ rank,
-                                                      const int32_t *__restrict__ start,
-                                                      int32_t *__restrict__ order) {
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * kMB + threadIdx.x;
-  if (i >= n) return;
-  order[start[cell[i]] + rank[i]] = static_cast<int32_t>(i);
-}
-
-// make the order inside every cell ascending in the input index (deterministic
-// neighbour order), then gather the coordinates into cell order.  One lane per
-// slot p of the scattered array: its point i = order_in[p] counts the members of
-// its cell [b, e) that precede it.  The workgroup's 256 slots sit in LDS, and a
-// cell holds a few dozen points, so nearly every comparison is an LDS read; the
-// parts of a cell outside the window come from memory.  (The first version went
-// through global memory for every member: 1.4 ms per 10 M-point SOR grid.)
-__global__ __launch_bounds__(kMB) void k_grid_order(const float *__restrict__ x, const float *__restrict__ y,
-                                                    const float *__restrict__ z, int64_t n, int64_t plane,
-                                                    const int32_t *__restrict__ cell,
-                                                    const int32_t *__restrict__ start,
-                                                    const int32_t *__restrict__ order_in,
-                                                    int32_t *__restrict__ order_out, float *__restrict__ sxyz) {
-  __shared__ int32_t win[kMB];
-  const int64_t w0 = static_cast<int64_t>(blockIdx.x) * kMB;
-  const int64_t p = w0 + threadIdx.x;
-  const int32_t i = p < n ? order_in[p] : 0x7fffffff;
-  win[threadIdx.x] = i;
-  __syncthreads();
-  if (p >= n) return;
-  const int32_t c = cell[i];
-  const int64_t b = start[c], e = start[c + 1];
-  int32_t before = 0;
-  const int64_t lb = max(b, w0), le = min(e, w0 + kMB);  // the part of the cell inside the window
-  for (int64_t k = b; k < lb; ++k) before += order_in[k] < i ? 1 : 0;
-  for (int64_t k = lb; k < le; ++k) before += win[k - w0] < i ? 1 : 0;
-  for (int64_t k = max(le, b); k < e; ++k) before += order_in[k] < i ? 1 : 0;
-  const int64_t j = b + before;
-  order_out[j] = i;
-  sxyz[j] = x[i];
-  sxyz[plane + j] = y[i];
-  sxyz[2 * plane + j] = z[i];
 }
 
 // mls_rcp, mls_rsqrt and pcl::eigen33's smallest eigenpair: pcp_eigen33.hpp (shared with pcp_normals.hip)
@@ -2086,122 +1949,6 @@ __global__ __launch_bounds__(kMB) void k_gather_caller(const float *__restrict__
 
 static inline uint32_t blocks_of(int64_t n) { return static_cast<uint32_t>(std::max<int64_t>(1, div_up(n, kMB))); }
 
-// device-wide exclusive scan of counts[0..m) into out[0..m], out[m] = total
-static int exclusive_scan(pcp_context *ctx, int32_t *counts, int64_t m) {
-  const int64_t tiles = std::max<int64_t>(1, div_up(m + 1, kScanTile));
-  PCP_HIP_TRY(ctx, ctx->s_tiles.ensure(static_cast<size_t>(tiles) + 4));
-  hipLaunchKernelGGL(k_scan_tile_sums, dim3(static_cast<uint32_t>(tiles)), dim3(kScanBlock), 0, ctx->stream, counts,
-                     m + 1, ctx->s_tiles.p);
-  hipLaunchKernelGGL(k_scan_tile_offsets, dim3(1), dim3(kScanSingle), 0, ctx->stream, ctx->s_tiles.p, tiles,
-                     static_cast<unsigned long long *>(nullptr));
-  hipLaunchKernelGGL(k_scan_apply, dim3(static_cast<uint32_t>(tiles)), dim3(kScanBlock), 0, ctx->stream, counts, m + 1,
-                     ctx->s_tiles.p, counts);
-  PCP_HIP_TRY(ctx, hipGetLastError());
-  return PCP_OK;
-}
-
-// uniform grid over a cloud view, cell edge >= `cell`; fills ctx->g_* (declared in pcp_internal.hpp)
-int build_grid(pcp_context *ctx, const CloudView &cv, float cell, float radius, GridDesc *out, bool geometry_only) {
-  const int64_t n = cv.n;
-  GridDesc g{};
-  const float *mn = cv.mn, *mx = cv.mx;
-  for (int a = 0; a < 3; ++a)
-    if (!(std::fabs(mn[a]) <= FLT_MAX) || !(std::fabs(mx[a]) <= FLT_MAX) || !(cell > 0.0f))
-      return set_error(ctx, PCP_ERR_INVALID, "the smoothing stages need finite coordinates (bounding box %g .. %g on axis %d)",
-                       static_cast<double>(mn[a]), static_cast<double>(mx[a]), a);
-  // Up to kMaxGridCells cells the table of cell starts is dense (one int32 per cell, 2 GiB at most); up to
-  // kMaxSparseCells it holds the occupied cells only, found through a bitmap with running popcounts (GridDesc; 6 GiB at
-  // most).  A box that needs more cells than that at the wanted edge gets a coarser grid: the searches stay exact, every
-  // doubling of the edge multiplies the candidates per query by up to 8 (a map with a stray point kilometres away).
-  // PCP_GRID_SPARSE=1 / 0 forces the sparse / dense form (tests).
-  const char *form_env = std::getenv("PCP_GRID_SPARSE");  // read per call: the tests flip it inside one process
-  const int force_form = form_env ? (form_env[0] == '1' ? 1 : 0) : -1;
-  const double cap = (force_form == 0 || geometry_only) ? kMaxGridCells : kMaxSparseCells;
-  double cells = 0.0;
-  for (int doubling = 0;; ++doubling) {  // bound the table: grow the cell until it fits
-    const double ex = static_cast<double>(mx[0] - mn[0]) / cell + 1.0, ey = static_cast<double>(mx[1] - mn[1]) / cell + 1.0,
-                 ez = static_cast<double>(mx[2] - mn[2]) / cell + 1.0;
-    cells = ex * ey * ez;
-    if (cells <= cap) break;
-    if (doubling > 300) return set_error(ctx, PCP_ERR_INVALID, "no uniform grid fits this cloud's bounding box");
-    cell *= 2.0f;
-  }
-  const bool sparse = !geometry_only && (force_form == 1 || cells > kMaxGridCells);
-  g.minx = mn[0];
-  g.miny = mn[1];
-  g.minz = mn[2];
-  g.inv_cell = 1.0f / cell;
-  g.nx = static_cast<int32_t>(floorf((mx[0] - mn[0]) * g.inv_cell)) + 1;
-  g.ny = static_cast<int32_t>(floorf((mx[1] - mn[1]) * g.inv_cell)) + 1;
-  g.nz = static_cast<int32_t>(floorf((mx[2] - mn[2]) * g.inv_cell)) + 1;
-  g.reach = static_cast<int32_t>(ceilf(radius * g.inv_cell));
-  const int64_t ncell = static_cast<int64_t>(g.nx) * g.ny * g.nz;
-  const size_t sn = static_cast<size_t>(n);
-  const size_t plane = (sn + 3) & ~size_t(3);
-  PCP_HIP_TRY(ctx, ctx->g_cell.ensure(sn + 4));
-  PCP_HIP_TRY(ctx, ctx->g_rank.ensure(sn + 4));
-  PCP_HIP_TRY(ctx, ctx->g_order.ensure(2 * sn + 8));
-  {
-    // k_sor_select<true> reads the planes in 16-byte pieces through one descriptor: a run's ragged end reads up to three
-    // floats past the run -- the next cell's points, the up-to-3 floats of padding behind a plane, the start of the next plane
-    // -- and masks those candidates by their x alone.  What it reads there must never be a NaN bit pattern (inf + NaN would
-    // slip past the mask as NaN): the buffer only ever holds finite coordinates (non-finite clouds are refused) or, right
-    // after an allocation, whatever hipMalloc left -- so a NEW allocation is zeroed once, and the padding stays non-NaN for
-    // the buffer's life.
-    const size_t before = ctx->g_xyz.count;  // (ensure() only ever grows: a changed count is a new allocation)
-    PCP_HIP_TRY(ctx, ctx->g_xyz.ensure(3 * plane + 4));
-    if (ctx->g_xyz.count != before) PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->g_xyz.p, 0, ctx->g_xyz.count * sizeof(float), ctx->stream));
-  }
-  if (geometry_only) {
-    PCP_HIP_TRY(ctx, ctx->g_start.ensure(static_cast<size_t>(ncell) + 8));
-    *out = g;
-    return PCP_OK;
-  }
-  const float *x = cv.x, *y = cv.y, *z = cv.z;
-  int64_t entries = ncell;  // entries of the table of cell starts (+ 1 for the total)
-  if (sparse) {
-    // occupied cells: one bit each; running popcount per word; the table gets one entry per set bit
-    const int64_t words = ncell / 64 + 2;  // the lookups reach cell id ncell (one past the last)
-    PCP_HIP_TRY(ctx, ctx->g_occ.ensure(static_cast<size_t>(words) + 2));
-    PCP_HIP_TRY(ctx, ctx->g_occ_rank.ensure(static_cast<size_t>(words) + 8));
-    PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->g_occ.p, 0, (static_cast<size_t>(words) + 2) * 8, ctx->stream));
-    g.occ = ctx->g_occ.p;
-    g.occ_rank = ctx->g_occ_rank.p;
-    {
-      LaunchTimer t(ctx, PCP_K_MLS_GRID);
-      hipLaunchKernelGGL(k_grid_mark, dim3(blocks_of(n)), dim3(kMB), 0, ctx->stream, x, y, z, n, g, ctx->g_occ.p);
-      hipLaunchKernelGGL(k_grid_popc, dim3(blocks_of(words)), dim3(kMB), 0, ctx->stream, ctx->g_occ.p, words, ctx->g_occ_rank.p);
-      int rc = exclusive_scan(ctx, ctx->g_occ_rank.p, words);
-      if (rc != PCP_OK) return rc;
-    }
-    int32_t occupied = 0;
-    PCP_HIP_TRY(ctx, hipMemcpyAsync(&occupied, ctx->g_occ_rank.p + words, 4, hipMemcpyDeviceToHost, ctx->stream));
-    PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    entries = occupied;
-  }
-  PCP_HIP_TRY(ctx, ctx->g_start.ensure(static_cast<size_t>(entries) + 8));
-  PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->g_start.p, 0, (static_cast<size_t>(entries) + 8) * 4, ctx->stream));
-  {
-    LaunchTimer t(ctx, PCP_K_MLS_GRID);
-    if (sparse)
-      hipLaunchKernelGGL(k_grid_count_sparse, dim3(blocks_of(n)), dim3(kMB), 0, ctx->stream, x, y, z, n, g, ctx->g_cell.p,
-                         ctx->g_rank.p, ctx->g_start.p);
-    else
-      hipLaunchKernelGGL(k_grid_count, dim3(blocks_of(n)), dim3(kMB), 0, ctx->stream, x, y, z, n, g, ctx->g_cell.p,
-                         ctx->g_rank.p, ctx->g_start.p);
-    int rc = exclusive_scan(ctx, ctx->g_start.p, entries);
-    if (rc != PCP_OK) return rc;
-    hipLaunchKernelGGL(k_grid_scatter, dim3(blocks_of(n)), dim3(kMB), 0, ctx->stream, n, ctx->g_cell.p, ctx->g_rank.p,
-                       ctx->g_start.p, ctx->g_order.p + sn + 4);
-    hipLaunchKernelGGL(k_grid_order, dim3(blocks_of(n)), dim3(kMB), 0, ctx->stream, x, y, z, n,
-                       static_cast<int64_t>(plane), ctx->g_cell.p, ctx->g_start.p, ctx->g_order.p + sn + 4,
-                       ctx->g_order.p, ctx->g_xyz.p);
-    PCP_HIP_TRY(ctx, hipGetLastError());
-  }
-  *out = g;
-  return PCP_OK;
-}
-
 // keep the `kept` result rows (of m) that keep_index names, in order.  They go into the context's second set of result
 // buffers, sized like the first (m, not kept), and the sets are swapped: either set then serves the next run without a
 // hipMalloc / hipFree pair (fresh buffers per call cost the enableMLS chain 1.5 ms).
@@ -2293,19 +2040,13 @@ static int vgd_prepare_bricks(pcp_context *ctx, const CloudView &cv, const Voxel
   PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->v_occ.p, 0, static_cast<size_t>(occ_words) * 4, ctx->stream));
   B = brick_desc(ctx, v);
   const int64_t n = cv.n;
-  const int64_t tiles = std::max<int64_t>(1, div_up(occ_words, kScanTile));
-  PCP_HIP_TRY(ctx, ctx->s_tiles.ensure(static_cast<size_t>(tiles) + 16));
   unsigned long long *d_total = reinterpret_cast<unsigned long long *>(ctx->v_plane.p);  // (word 0 until the planes are counted)
   {
     LaunchTimer t(ctx, PCP_K_MLS_VOXEL);
     hipLaunchKernelGGL(k_brick_mark, dim3(blocks_of(n)), dim3(kMB), 0, ctx->stream, cv.x, cv.y, cv.z, n, B, ctx->v_occ.p);
     hipLaunchKernelGGL(k_brick_popc, dim3(scan_grid(div_up(occ_words, kScanBlock))), dim3(kScanBlock), 0, ctx->stream, ctx->v_occ.p,
                        occ_words, ctx->v_rank.p);
-    hipLaunchKernelGGL(k_scan_tile_sums, dim3(scan_grid(tiles)), dim3(kScanBlock), 0, ctx->stream, ctx->v_rank.p, occ_words, ctx->s_tiles.p);
-    hipLaunchKernelGGL(k_scan_tile_offsets, dim3(1), dim3(kScanSingle), 0, ctx->stream, ctx->s_tiles.p, tiles, d_total);
-    hipLaunchKernelGGL(k_scan_apply, dim3(scan_grid(tiles)), dim3(kScanBlock), 0, ctx->stream, ctx->v_rank.p, occ_words, ctx->s_tiles.p,
-                       ctx->v_rank.p);
-    PCP_HIP_TRY(ctx, hipGetLastError());
+    PCP_HIP_TRY(ctx, scan_exclusive(ctx->stream, ctx->v_rank.p, occ_words, ctx->s_tiles, d_total));
   }
   unsigned long long n_bricks = 0;
   {
@@ -2510,10 +2251,7 @@ static int vgd_emit(pcp_context *ctx, const VgdStream &S, int64_t word0, int64_t
     e.block_step = std::max(1, sample_step);
     {
       LaunchTimer t(ctx, PCP_K_MLS_VOXEL);
-      hipLaunchKernelGGL(k_scan_tile_sums, dim3(scan_grid(tiles2)), dim3(kScanBlock), 0, ctx->stream, tile_first, tiles, level2);
-      hipLaunchKernelGGL(k_scan_tile_offsets, dim3(1), dim3(kScanSingle), 0, ctx->stream, level2, tiles2,
-                         static_cast<unsigned long long *>(nullptr));
-      hipLaunchKernelGGL(k_scan_apply, dim3(scan_grid(tiles2)), dim3(kScanBlock), 0, ctx->stream, tile_first, tiles, level2, tile_first);
+      scan_exclusive_launch(ctx->stream, tile_first, tiles, level2, nullptr);  // (its tile sums share s_tiles with the counts)
       if (S.bricks) {
         BrickDesc B = brick_desc(ctx, S.v);
         hipLaunchKernelGGL(k_brick_expand, dim3(static_cast<uint32_t>(std::min<int64_t>(words, int64_t(1) << 20))), dim3(64), 0, ctx->stream, B,
@@ -2748,21 +2486,6 @@ static int require_finite_cloud(pcp_context *ctx, const char *who) {
     return set_error(ctx, PCP_ERR_INVALID, "%s: %lld uploaded points have a NaN or infinite coordinate", who,
                      (long long)ctx->nonfinite_points);
   return PCP_OK;
-}
-
-static CloudView uploaded_view(const pcp_context *ctx) {
-  CloudView cv{};
-  const size_t plane = (static_cast<size_t>(ctx->n) + 3) & ~size_t(3);
-  cv.x = ctx->sxyz.p;
-  cv.y = ctx->sxyz.p + plane;
-  cv.z = ctx->sxyz.p + 2 * plane;
-  cv.remap = ctx->perm.p;
-  cv.n = ctx->n;
-  for (int a = 0; a < 3; ++a) {
-    cv.mn[a] = ctx->host_min[static_cast<size_t>(a)];
-    cv.mx[a] = ctx->host_max[static_cast<size_t>(a)];
-  }
-  return cv;
 }
 
 static int check_mls_params(pcp_context *ctx, const pcp_mls_params *p) {
@@ -3308,7 +3031,7 @@ int pcp_mls_process(pcp_context *ctx, const pcp_mls_params *p, int64_t *out_coun
   if (!ctx->xyz.p) return set_error(ctx, PCP_ERR_STATE, "pcp_mls_process: no cloud uploaded");
   if (int rcf = require_finite_cloud(ctx, "pcp_mls_process")) return rcf;
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  rc = mls_run(ctx, uploaded_view(ctx), p, out_count);
+  rc = mls_run(ctx, uploaded_view(ctx, true), p, out_count);
   ctx->mls_result_live = rc == PCP_OK;
   return rc;
 }
@@ -3346,7 +3069,7 @@ int pcp_mls_stream_begin(pcp_context *ctx, const pcp_mls_params *p, int64_t chun
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
   ctx->vgd_next = -1;
   int64_t total = 0;
-  if ((rc = mls_run(ctx, uploaded_view(ctx), p, &total, 0, -1, false, chunk_capacity)) != PCP_OK) return rc;
+  if ((rc = mls_run(ctx, uploaded_view(ctx, true), p, &total, 0, -1, false, chunk_capacity)) != PCP_OK) return rc;
   if (out_total) *out_total = total;
   if (out_chunks) *out_chunks = static_cast<int32_t>(ctx->vgd_chunks.size() / 3);
   return PCP_OK;
@@ -3403,7 +3126,7 @@ int pcp_mls_process_shard(pcp_context *ctx, const pcp_mls_params *p, int64_t ind
     return set_error(ctx, PCP_ERR_RANGE, "pcp_mls_process_shard: query range [%lld,%lld) outside 0..%lld",
                      (long long)index_begin, (long long)index_end, (long long)ctx->n);
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  rc = mls_run(ctx, uploaded_view(ctx), p, out_count, index_begin, index_end);
+  rc = mls_run(ctx, uploaded_view(ctx, true), p, out_count, index_begin, index_end);
   ctx->mls_result_live = rc == PCP_OK;
   return rc;
 }
@@ -3421,7 +3144,7 @@ int pcp_mls_process_slab(pcp_context *ctx, const pcp_mls_params *p, int32_t slab
     return set_error(ctx, PCP_ERR_INVALID, "pcp_mls_process_slab: query sharding supports upsampling NONE only");
   if (n_slabs < 1 || slab < 0 || slab >= n_slabs) return set_error(ctx, PCP_ERR_RANGE, "pcp_mls_process_slab: slab %d of %d", slab, n_slabs);
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  rc = mls_run(ctx, uploaded_view(ctx), p, out_count, 0, -1, false, 0, slab, n_slabs);
+  rc = mls_run(ctx, uploaded_view(ctx, true), p, out_count, 0, -1, false, 0, slab, n_slabs);
   ctx->mls_result_live = rc == PCP_OK;
   return rc;
 }
@@ -3455,7 +3178,7 @@ int pcp_sor(pcp_context *ctx, int32_t mean_k, double std_mul, uint8_t *out_keep,
   if (n == 0) return PCP_OK;
   ctx->sor_distances_live = false;
   ctx->sor_partial_slab = ctx->sor_partial_slabs = -1;
-  int rc = sor_run(ctx, uploaded_view(ctx), mean_k, std_mul);
+  int rc = sor_run(ctx, uploaded_view(ctx, true), mean_k, std_mul);
   if (rc != PCP_OK) return rc;
   ctx->sor_distances_live = true;
   if (out_kept) {
@@ -3496,7 +3219,7 @@ int pcp_sor_partial(pcp_context *ctx, int32_t mean_k, int32_t slab, int32_t n_sl
   ctx->sor_partial_slab = ctx->sor_partial_slabs = -1;
   if (n == 0) return PCP_OK;
   // (a slab without chunks still builds the grid: pcp_sor_finish reads the cell order from it)
-  if ((rc = sor_run(ctx, uploaded_view(ctx), mean_k, 0.0, false, slab, n_slabs, /*classify=*/false)) != PCP_OK) return rc;
+  if ((rc = sor_run(ctx, uploaded_view(ctx, true), mean_k, 0.0, false, slab, n_slabs, /*classify=*/false)) != PCP_OK) return rc;
   if (c1 > c0)
     PCP_HIP_TRY(ctx, hipMemcpyAsync(out_chunk_sums, ctx->m_sums.p + 4 + 2 * c0, static_cast<size_t>(c1 - c0) * 2 * sizeof(double),
                                     hipMemcpyDefault, ctx->stream));  // host or device memory
@@ -3525,7 +3248,7 @@ int pcp_sor_finish(pcp_context *ctx, double std_mul, const double *all_chunk_sum
   const int64_t c0 = n_chunks * slab / n_slabs, c1 = n_chunks * (slab + 1) / n_slabs;
   const int64_t j0 = c0 * kSorChunk, j1 = std::min<int64_t>(c1 * kSorChunk, n);
   PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->m_flag.p, 0, static_cast<size_t>(n), ctx->stream));
-  if ((rc = sor_classify(ctx, n, uploaded_view(ctx).remap, std_mul, j0, j1)) != PCP_OK) return rc;
+  if ((rc = sor_classify(ctx, n, uploaded_view(ctx, true).remap, std_mul, j0, j1)) != PCP_OK) return rc;
   if (out_kept) {
     int64_t kept = 0;
     if ((rc = compact_flags(ctx, ctx->m_flag.p, n, nullptr, 0, &kept)) != PCP_OK) return rc;
@@ -3560,7 +3283,7 @@ static int cloud_smooth_run(pcp_context *ctx, const pcp_mls_params *p, int64_t *
   ctx->sor_distances_live = false;
   ctx->sor_partial_slab = ctx->sor_partial_slabs = -1;
   if (out_count) *out_count = 0;
-  const CloudView cv0 = uploaded_view(ctx);
+  const CloudView cv0 = uploaded_view(ctx, true);
   if (cv0.n == 0) return PCP_OK;
   CloudView cv1;
   int64_t n1 = 0;
@@ -3754,7 +3477,7 @@ int pcp_cloud_smooth_stream_begin(pcp_context *ctx, const pcp_mls_params *p, int
   if (out_chunks) *out_chunks = 0;
   SmoothStream st{};
   st.p = *p;
-  const CloudView cv0 = uploaded_view(ctx);
+  const CloudView cv0 = uploaded_view(ctx, true);
   struct Building {
     pcp_context *c;
     explicit Building(pcp_context *c_) : c(c_) { c->css_building = true; }
@@ -4061,19 +3784,10 @@ int pcp_close_pairs(pcp_context *ctx, double radius, int64_t *points_with_close_
   if (!(radius > 0.0)) return set_error(ctx, PCP_ERR_INVALID, "pcp_close_pairs: radius must be > 0");
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
   *points_with_close_neighbour = 0;
-  const CloudView cv = uploaded_view(ctx);
+  const CloudView cv = uploaded_view(ctx, true);
   if (cv.n < 2) return PCP_OK;
   GridDesc g;
-  // Cell edge: the radius, but never finer than ~8 cells per point.  A micrometre radius on a map tens of metres across
-  // would otherwise take the finest grid there is (2^35 cells: 6 GiB of bitmap and running popcounts, a 4 GiB memset
-  // and a scan over 2^29 words, all for one count -- ADVICE r2); with the coarser cell the search is as exact (reach =
-  // ceil(radius / cell) = 1, every pair closer than the radius lies in adjacent cells) and the table stays a few
-  // entries per point.
-  const double vol = std::max<double>(cv.mx[0] - cv.mn[0], 1e-3) * std::max<double>(cv.mx[1] - cv.mn[1], 1e-3) *
-                     std::max<double>(cv.mx[2] - cv.mn[2], 1e-3);
-  const float by_density = static_cast<float>(std::cbrt(vol / (8.0 * static_cast<double>(cv.n))));
-  const float cell = std::max(static_cast<float>(radius) * 1.001f, by_density);
-  int rc = build_grid(ctx, cv, cell, static_cast<float>(radius), &g);
+  int rc = build_radius_grid(ctx, cv, static_cast<float>(radius), &g);
   if (rc != PCP_OK) return rc;
   const size_t plane = (static_cast<size_t>(cv.n) + 3) & ~size_t(3);
   PCP_HIP_TRY(ctx, ctx->s_counter.ensure(4));
@@ -4085,11 +3799,7 @@ int pcp_close_pairs(pcp_context *ctx, double radius, int64_t *points_with_close_
   PCP_HIP_TRY(ctx, hipMemcpyAsync(&c, ctx->s_counter.p, 8, hipMemcpyDeviceToHost, ctx->stream));
   PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   *points_with_close_neighbour = static_cast<int64_t>(c);
-  // a micrometre radius takes the finest grid there is: do not keep gigabytes of bitmap for a one-off check
-  if (ctx->g_occ.count > (size_t(1) << 25)) {
-    ctx->g_occ.release();
-    ctx->g_occ_rank.release();
-  }
+  drop_large_grid_bitmap(ctx);
   return PCP_OK;
 }
 

@@ -407,8 +407,7 @@ int pcp_nid_prepare(pcp_context *ctx, int64_t *out_points) {
       if (at > 0)
         PCP_HIP_TRY(ctx, hipMemcpyAsync(bigger.p, ctx->nid_pts.p, static_cast<size_t>(at) * 16, hipMemcpyDeviceToDevice, ctx->stream));
       PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      std::swap(ctx->nid_pts, bigger);
-      bigger.release();
+      std::swap(ctx->nid_pts, bigger);  // (the smaller buffer goes with `bigger`)
       capacity = want;
     }
     if (padded > 0) {

@@ -15,7 +15,6 @@
 // (range bits << 32 | input index) on its colour pixel, so the nearest point wins, ties go to the lowest index, and the
 // result does not depend on the arrival order.  A resolve kernel, one lane per pixel, writes the four images.
 #include <algorithm>
-#include <cfloat>
 #include <cmath>
 #include <new>
 #include <thread>
@@ -34,29 +33,6 @@ constexpr int kGnTile = 512;    // candidate records per LDS tile (8 KiB)
 constexpr int kGnMaxRows = 25;  // (2 reach + 1)^2 rows of neighbouring cells, reach <= 2
 
 static inline uint32_t gn_blocks(int64_t n) { return static_cast<uint32_t>(std::max<int64_t>(1, div_up(n, kGnBlock))); }
-
-// 1 = point j of the sorted copy has three finite coordinates (GN1)
-__global__ __launch_bounds__(kGnBlock) void k_gn_finite(const float *__restrict__ x, const float *__restrict__ y,
-                                                        const float *__restrict__ z, int64_t n, uint8_t *__restrict__ flag) {
-  const int64_t j = static_cast<int64_t>(blockIdx.x) * kGnBlock + threadIdx.x;
-  if (j >= n) return;
-  flag[j] = gn::finite3(x[j], y[j], z[j]) ? 1 : 0;
-}
-
-// the finite points as a view: point k of the view = sorted point pos[k], caller's index perm[pos[k]]
-__global__ __launch_bounds__(kGnBlock) void k_gn_gather(const float *__restrict__ x, const float *__restrict__ y,
-                                                        const float *__restrict__ z, const int32_t *__restrict__ perm,
-                                                        const int32_t *__restrict__ pos, int64_t m, float *__restrict__ vx,
-                                                        float *__restrict__ vy, float *__restrict__ vz,
-                                                        int32_t *__restrict__ vremap) {
-  const int64_t k = static_cast<int64_t>(blockIdx.x) * kGnBlock + threadIdx.x;
-  if (k >= m) return;
-  const int32_t j = pos[k];
-  vx[k] = x[j];
-  vy[k] = y[j];
-  vz[k] = z[j];
-  vremap[k] = perm[j];
-}
 
 // records in cell order: (x, y, z, the caller's index the result goes to)
 __global__ __launch_bounds__(kGnBlock) void k_gn_records(const float *__restrict__ gx, const float *__restrict__ gy,
@@ -232,20 +208,10 @@ __global__ __launch_bounds__(kGnBlock) void k_gm_resolve(const unsigned long lon
 // ---- host side ----------------------------------------------------------------------------------------------------------
 // per-call scratch: released when the call returns
 struct GnScratch {
-  DevBuf<uint8_t> flag;
-  DevBuf<int32_t> pos, vremap, items;
-  DevBuf<float> vxyz;
+  FiniteScratch fin;  // (its flags serve the work items once the view is gathered)
+  DevBuf<int32_t> items;
   DevBuf<uint4> rec;
   DevBuf<long long> moments;
-  ~GnScratch() {
-    flag.release();
-    pos.release();
-    vremap.release();
-    items.release();
-    vxyz.release();
-    rec.release();
-    moments.release();
-  }
 };
 
 void normals_release(pcp_context *ctx) {
@@ -254,42 +220,28 @@ void normals_release(pcp_context *ctx) {
   ctx->gn_count.release();
 }
 
-void geometry_release(pcp_context *ctx) {
-  normals_release(ctx);
-  ctx->gm_keys.release();
-  ctx->gm_out.release();
-}
-
 // the m > 0 finite points of view cv: grid, records in cell order, work items, the moments and the solve
 static int normals_finite(pcp_context *ctx, const CloudView &cv, float radius, float t, GnScratch &s) {
   const int64_t m = cv.n;
-  // build_grid replaces the grid that an open MLS stream or a pcp_sor_partial rests on (as every call that builds one does)
-  ctx->vgd_next = -1;
-  ctx->css_next = -1;
-  ctx->sor_partial_slab = ctx->sor_partial_slabs = -1;
-  // cell edge: the radius (reach 1), but never finer than ~8 cells per point (as the local colour smoothing)
-  const double vol = std::max<double>(cv.mx[0] - cv.mn[0], 1e-3) * std::max<double>(cv.mx[1] - cv.mn[1], 1e-3) *
-                     std::max<double>(cv.mx[2] - cv.mn[2], 1e-3);
-  const float by_density = static_cast<float>(std::cbrt(vol / (8.0 * static_cast<double>(m))));
-  const float cell = std::max(radius * 1.001f, by_density);
   GridDesc g;
-  int rc = build_grid(ctx, cv, cell, radius, &g);
+  int rc = build_radius_grid(ctx, cv, radius, &g);
   if (rc != PCP_OK) return rc;
   if (g.reach < 1 || (2 * g.reach + 1) * (2 * g.reach + 1) > kGnMaxRows)
     return set_error(ctx, PCP_ERR_INVALID, "pcp_estimate_normals: grid reach %d outside 1..2", g.reach);
   const size_t gplane = (static_cast<size_t>(m) + 3) & ~size_t(3);
+  DevBuf<uint8_t> &flag = s.fin.flag;
   PCP_HIP_TRY(ctx, s.rec.ensure(static_cast<size_t>(m) + 4));
-  PCP_HIP_TRY(ctx, s.flag.ensure(static_cast<size_t>(m) + 16));
+  PCP_HIP_TRY(ctx, flag.ensure(static_cast<size_t>(m) + 16));
   PCP_HIP_TRY(ctx, s.items.ensure(static_cast<size_t>(m) + 4));
   {
     LaunchTimer lt(ctx, PCP_K_MISC);
     hipLaunchKernelGGL(k_gn_records, dim3(gn_blocks(m)), dim3(kGnBlock), 0, ctx->stream, ctx->g_xyz.p, ctx->g_xyz.p + gplane,
                        ctx->g_xyz.p + 2 * gplane, ctx->g_order.p, cv.remap, m, s.rec.p);
-    hipLaunchKernelGGL(k_gn_items, dim3(gn_blocks(m)), dim3(kGnBlock), 0, ctx->stream, s.rec.p, m, g, ctx->g_start.p, s.flag.p);
+    hipLaunchKernelGGL(k_gn_items, dim3(gn_blocks(m)), dim3(kGnBlock), 0, ctx->stream, s.rec.p, m, g, ctx->g_start.p, flag.p);
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
   int64_t n_items = 0;
-  if ((rc = compact_flags(ctx, s.flag.p, m, s.items.p, m, &n_items)) != PCP_OK) return rc;
+  if ((rc = compact_flags(ctx, flag.p, m, s.items.p, m, &n_items)) != PCP_OK) return rc;
   PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->s_counter.p, 0, 16, ctx->stream));  // (compact_flags left its total there)
   {
     LaunchTimer lt(ctx, PCP_K_MISC);
@@ -317,56 +269,19 @@ static int estimate_normals(pcp_context *ctx, float radius, int64_t *out_valid, 
     PCP_HIP_TRY(ctx, hipMemsetAsync(s.moments.p, 0, sn * gn::kMomentWords * 8, ctx->stream));
   }
   const float t = gn::threshold_of(radius);
-  const size_t plane = (sn + 3) & ~size_t(3);
-  CloudView cv{};
-  cv.x = ctx->sxyz.p;
-  cv.y = ctx->sxyz.p + plane;
-  cv.z = ctx->sxyz.p + 2 * plane;
-  cv.remap = ctx->perm.p;
-  cv.n = n;
-  for (int a = 0; a < 3; ++a) {  // the box of the finite coordinates (a superset of the finite points' box)
-    cv.mn[a] = ctx->host_min[static_cast<size_t>(a)];
-    cv.mx[a] = ctx->host_max[static_cast<size_t>(a)];
-  }
-  if (ctx->nonfinite_points > 0) {
-    // GN1: the grid (which needs finite coordinates) is built over the finite points only
-    PCP_HIP_TRY(ctx, s.flag.ensure(sn + 16));
-    PCP_HIP_TRY(ctx, s.pos.ensure(sn + 4));
-    hipLaunchKernelGGL(k_gn_finite, dim3(gn_blocks(n)), dim3(kGnBlock), 0, ctx->stream, cv.x, cv.y, cv.z, n, s.flag.p);
-    PCP_HIP_TRY(ctx, hipGetLastError());
-    int64_t m = 0;
-    int rc = compact_flags(ctx, s.flag.p, n, s.pos.p, n, &m);
-    if (rc != PCP_OK) return rc;
-    const size_t pm = (static_cast<size_t>(m) + 3) & ~size_t(3);
-    PCP_HIP_TRY(ctx, s.vxyz.ensure(3 * pm + 4));
-    PCP_HIP_TRY(ctx, s.vremap.ensure(static_cast<size_t>(m) + 4));
-    if (m > 0) {
-      hipLaunchKernelGGL(k_gn_gather, dim3(gn_blocks(m)), dim3(kGnBlock), 0, ctx->stream, cv.x, cv.y, cv.z, ctx->perm.p, s.pos.p, m,
-                         s.vxyz.p, s.vxyz.p + pm, s.vxyz.p + 2 * pm, s.vremap.p);
-      PCP_HIP_TRY(ctx, hipGetLastError());
-    }
-    cv.x = s.vxyz.p;
-    cv.y = s.vxyz.p + pm;
-    cv.z = s.vxyz.p + 2 * pm;
-    cv.remap = s.vremap.p;
-    cv.n = m;
-  }
+  CloudView cv;
+  // GN1: the grid (which needs finite coordinates) is built over the finite points only
+  int rc = finite_view(ctx, /*with_remap=*/true, /*timing_slot=*/-1, s.fin, &cv);
+  if (rc != PCP_OK) return rc;
   PCP_HIP_TRY(ctx, ctx->s_counter.ensure(4));
   PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->s_counter.p, 0, 16, ctx->stream));
-  if (cv.n > 0) {
-    int rc = normals_finite(ctx, cv, radius, t, s);
-    if (rc != PCP_OK) return rc;
-  }
+  if (cv.n > 0 && (rc = normals_finite(ctx, cv, radius, t, s)) != PCP_OK) return rc;
   unsigned long long tally[2] = {0, 0};
   PCP_HIP_TRY(ctx, hipMemcpyAsync(tally, ctx->s_counter.p, 16, hipMemcpyDeviceToHost, ctx->stream));
   if (out_moments)
     PCP_HIP_TRY(ctx, hipMemcpyAsync(out_moments, s.moments.p, sn * gn::kMomentWords * 8, hipMemcpyDeviceToHost, ctx->stream));
   PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (also: the scratch is released on return)
-  // a tiny radius on a large map may take the sparse grid: do not keep its bitmap
-  if (ctx->g_occ.count > (size_t(1) << 25)) {
-    ctx->g_occ.release();
-    ctx->g_occ_rank.release();
-  }
+  drop_large_grid_bitmap(ctx);  // (a tiny radius on a large map may take the sparse grid)
   if (static_cast<int64_t>(tally[1]) >= gn::kMaxNeighbours)
     return set_error(ctx, PCP_ERR_RANGE, "pcp_estimate_normals: a point has %llu neighbours within %g (2^22 or more could overflow the moments)",
                      tally[1], static_cast<double>(radius));

@@ -1,11 +1,13 @@
 // pcp_scan.hpp -- device-wide exclusive prefix sum over int32 counts (three
-// launches: tile sums, single-block scan of the sums, per-tile apply).  Used by
-// the MLS cell binning; 64-wide wavefront scans through __shfl_up.
+// launches: tile sums, single-block scan of the sums, per-tile apply; host side:
+// scan_exclusive at the end of this file).  64-wide wavefront scans through __shfl_up.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "pcp_internal.hpp"
 
 namespace pcp {
 
@@ -150,6 +152,26 @@ static __global__ __launch_bounds__(kScanBlock) void k_scan_apply(const int32_t 
       run += v[k];
     }
   }
+}
+
+// ---- host side: the three launches ---------------------------------------------------------------------------------
+static inline int64_t scan_tiles(int64_t n) { return n > kScanTile ? (n + kScanTile - 1) / kScanTile : 1; }
+
+// Exclusive scan of counts[0..n) in place, queued on `st`; the grand total to *total (device memory; nullable).
+// tile_sums: scan_tiles(n) words of device scratch.
+static inline void scan_exclusive_launch(hipStream_t st, int32_t *counts, int64_t n, int32_t *tile_sums, unsigned long long *total) {
+  const int64_t tiles = scan_tiles(n);
+  hipLaunchKernelGGL(k_scan_tile_sums, dim3(scan_grid(tiles)), dim3(kScanBlock), 0, st, counts, n, tile_sums);
+  hipLaunchKernelGGL(k_scan_tile_offsets, dim3(1), dim3(kScanSingle), 0, st, tile_sums, tiles, total);
+  hipLaunchKernelGGL(k_scan_apply, dim3(scan_grid(tiles)), dim3(kScanBlock), 0, st, counts, n, tile_sums, counts);
+}
+
+// ... with the tile sums in a buffer of the caller's, grown as needed; the launches' error, if any
+static inline hipError_t scan_exclusive(hipStream_t st, int32_t *counts, int64_t n, DevBuf<int32_t> &tile_sums, unsigned long long *total) {
+  const hipError_t e = tile_sums.ensure(static_cast<size_t>(scan_tiles(n)) + 4);
+  if (e != hipSuccess) return e;
+  scan_exclusive_launch(st, counts, n, tile_sums.p, total);
+  return hipGetLastError();
 }
 
 }  // namespace pcp

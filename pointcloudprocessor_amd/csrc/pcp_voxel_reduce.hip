@@ -381,16 +381,7 @@ static int vr_read_scalars(pcp_context *ctx, unsigned long long h[VR_SCALARS]) {
 static int vr_rehash(pcp_context *ctx, int64_t new_slots, bool keep_empty) {
   VoxelReduce &vr = ctx->voxel_reduce;
   DevBuf<unsigned long long> keys, q;
-  DevBuf<uint32_t> sums;
-  struct Guard {  // (an early return frees whichever table is not the accumulator's)
-    DevBuf<unsigned long long> &k, &q;
-    DevBuf<uint32_t> &s;
-    ~Guard() {
-      k.release();
-      q.release();
-      s.release();
-    }
-  } guard{keys, q, sums};
+  DevBuf<uint32_t> sums;  // (whichever table is not the accumulator's is freed on return)
   int rc = vr_clear(ctx, keys, q, sums, new_slots);
   if (rc != PCP_OK) return rc;
   PCP_HIP_TRY(ctx, hipMemsetAsync(vr.scalars.p + VR_USED, 0, 8, ctx->stream));
@@ -426,8 +417,6 @@ static void vr_drop(pcp_context *ctx) {
   vr.slots = vr.used = vr.keyed = vr.rows = vr.voxels = vr.growths = vr.partials = vr.atomics = 0;
   vr.initial_slots = 0;
 }
-
-void voxel_reduce_release(pcp_context *ctx) { vr_drop(ctx); }
 
 }  // namespace pcp
 
@@ -550,17 +539,6 @@ int pcp_voxel_reduce_finish(pcp_context *ctx, int64_t *out_voxels) {
     const size_t cap = static_cast<size_t>(vr.used);
     DevBuf<unsigned long long> key_a, key_b;
     DevBuf<int32_t> val_a, val_b, hist;
-    struct Guard {
-      DevBuf<unsigned long long> &a, &b;
-      DevBuf<int32_t> &c, &d, &e;
-      ~Guard() {
-        a.release();
-        b.release();
-        c.release();
-        d.release();
-        e.release();
-      }
-    } guard{key_a, key_b, val_a, val_b, hist};
     PCP_HIP_TRY(ctx, key_a.ensure(cap + 2));
     PCP_HIP_TRY(ctx, key_b.ensure(cap + 2));
     PCP_HIP_TRY(ctx, val_a.ensure(cap + 4));
@@ -583,8 +561,6 @@ int pcp_voxel_reduce_finish(pcp_context *ctx, int64_t *out_voxels) {
     if (voxels > 0) {
       const int64_t blocks = div_up(voxels, kVrBlock), hm = 256 * blocks;
       PCP_HIP_TRY(ctx, hist.ensure(static_cast<size_t>(hm) + 8));
-      const int64_t scan_tiles = std::max<int64_t>(1, (hm + 1 + kScanTile - 1) / kScanTile);
-      PCP_HIP_TRY(ctx, ctx->s_tiles.ensure(static_cast<size_t>(scan_tiles) + 4));
       unsigned long long *kin = key_a.p, *kout = key_b.p;
       int32_t *vin = val_a.p, *vout = val_b.p;
       hipStream_t st = ctx->stream;
@@ -593,10 +569,7 @@ int pcp_voxel_reduce_finish(pcp_context *ctx, int64_t *out_voxels) {
         const int32_t shift = 8 * pass;
         hipLaunchKernelGGL(k_vr_radix_hist, dim3(static_cast<uint32_t>(blocks)), dim3(kVrBlock), 0, st, kin, voxels, shift, hist.p, blocks);
         PCP_HIP_TRY(ctx, hipMemsetAsync(hist.p + hm, 0, sizeof(int32_t), st));
-        hipLaunchKernelGGL(k_scan_tile_sums, dim3(scan_grid(scan_tiles)), dim3(kScanBlock), 0, st, hist.p, hm + 1, ctx->s_tiles.p);
-        hipLaunchKernelGGL(k_scan_tile_offsets, dim3(1), dim3(kScanSingle), 0, st, ctx->s_tiles.p, scan_tiles,
-                           static_cast<unsigned long long *>(nullptr));
-        hipLaunchKernelGGL(k_scan_apply, dim3(scan_grid(scan_tiles)), dim3(kScanBlock), 0, st, hist.p, hm + 1, ctx->s_tiles.p, hist.p);
+        PCP_HIP_TRY(ctx, scan_exclusive(st, hist.p, hm + 1, ctx->s_tiles, nullptr));
         hipLaunchKernelGGL(k_vr_radix_scatter, dim3(static_cast<uint32_t>(blocks)), dim3(kVrBlock), 0, st, kin, vin, voxels, shift,
                            hist.p, blocks, kout, vout);
         std::swap(kin, kout);
@@ -612,7 +585,7 @@ int pcp_voxel_reduce_finish(pcp_context *ctx, int64_t *out_voxels) {
                          vr.out_xyz.p, vr.out_rgb.p, vr.out_label.p, vr.out_count.p);
       PCP_HIP_TRY(ctx, hipGetLastError());
     }
-    PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the sort's scratch is freed here)
+    PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the sort's scratch is freed at the end of this block)
   }
   vr.voxels = voxels;
   vr.finished = true;

@@ -75,6 +75,36 @@ def test_project_frame_ragged_sizes(gpu_ctx_factory, oracle, small_scene):
             assert np.array_equal(got[k], ref[k]), (n, k)
 
 
+@pytest.mark.parametrize("n", [1, 1023, 1024, 1025, 1024 * 1024 + 1])
+def test_upload_sizes_around_the_scan_tiles(gpu_ctx_factory, oracle, small_scene, n):
+    """The upload's radix sort scans 256 x ceil(n / 256) + 1 counts: one tile of 1024, the tile's edge, and (the last size) more
+    than 1024 tile sums.  Every point's batched result, which reaches it through the sort's permutation, against the oracle."""
+    from pointcloudprocessor_amd import capi, synth
+
+    cd = small_scene["cam"]
+    x, y, z, _ = synth.make_cloud(n, seed=n)
+    poses, imgs = small_scene["poses"][:2], small_scene["images"][:2]
+    ctx = gpu_ctx_factory()
+    ctx.set_camera(cam_struct(capi, cd))
+    ctx.upload_cloud(x, y, z)
+    ctx.set_frames(poses)
+    for f, im in enumerate(imgs):
+        ctx.upload_image(f, im)
+    ctx.depth_pass()
+    ctx.colour_reset()
+    ctx.colour_pass()
+    got = ctx.colour_finalise(want_top=True)
+    ref = oracle.colorize(cam_struct(oracle, cd), oracle.default_cull_params(), x, y, z, poses, imgs, threads=8)
+    for k in ("count", "top_frame", "has"):
+        assert np.array_equal(got[k], ref[k]), k
+    assert n < 1024 or ref["has"].sum() > n // 100
+    ocam, ocp = cam_struct(oracle, cd), oracle.default_cull_params()
+    w2c, _ = oracle.pose_to_matrices(poses[0])
+    p_got, p_ref = ctx.project_frame(0), oracle.project_frame(ocam, ocp, w2c, x, y, z)
+    for k in ("cell", "pixel"):
+        assert np.array_equal(p_got[k], p_ref[k]), k
+
+
 def test_cull_frame_depth_and_keep_exact(gpu_ctx_factory, oracle, small_scene):
     from pointcloudprocessor_amd import capi
 

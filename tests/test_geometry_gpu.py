@@ -93,6 +93,37 @@ def test_all_duplicate_cloud_is_one_cell_and_invalid(gpu_ctx_factory, small_scen
     assert valid == 0 and not out["normal"].any() and not out["curvature"].any() and (out["neighbours"] == 3000).all()
 
 
+def test_all_non_finite_cloud(gpu_ctx_factory, small_scene):
+    ctx = _base(gpu_ctx_factory, small_scene)["ctx"]
+    xyz = np.ones((10, 3), np.float32)
+    xyz[:, 0] = np.nan
+    ctx.upload_cloud(xyz[:, 0], xyz[:, 1], xyz[:, 2])
+    valid, got = ctx.estimate_normals(0.3, want_moments=True)
+    out = ctx.normals_fetch()
+    assert valid == 0 and not got.any()
+    assert not out["normal"].any() and not out["curvature"].any() and not out["neighbours"].any()
+
+
+def test_one_cell_of_65_finite_points_and_a_nan(gpu_ctx_factory, small_scene):
+    """one full work item of 64 queries plus one, through the gathered view of the finite points"""
+    ctx = _base(gpu_ctx_factory, small_scene)["ctx"]
+    rng = np.random.default_rng(65)
+    xyz = np.float32([1.0, -2.0, 0.5]) + rng.random((66, 3)).astype(np.float32) * np.float32(0.05)
+    xyz[40, 1] = np.nan
+    ctx.upload_cloud(xyz[:, 0], xyz[:, 1], xyz[:, 2])
+    valid, got = ctx.estimate_normals(0.3, want_moments=True)
+    mom = ref.moments(0.3, xyz)
+    twin = ref.normals(mom)
+    assert np.array_equal(got, mom) and (mom[np.arange(66) != 40, 0] == 65).all() and not got[40].any()
+    assert valid == int(twin["valid"].sum()) == 65
+    out = ctx.normals_fetch()
+    assert np.array_equal(out["neighbours"], mom[:, 0].astype(np.int32))
+    assert np.array_equal(out["normal"].any(axis=1), twin["valid"])
+    n = out["normal"][twin["valid"]].astype(np.float64)
+    t = twin["normal"][twin["valid"]]
+    assert np.abs(n - t * np.sign((n * t).sum(axis=1))[:, None]).max() <= 1e-4  # (the bar of test_normals_against_eigh)
+
+
 def test_order_independence(gpu_ctx_factory, small_scene):
     b = _base(gpu_ctx_factory, small_scene)
     ctx, xyz = b["ctx"], b["xyz"]

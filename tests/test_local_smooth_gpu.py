@@ -223,6 +223,18 @@ def test_non_finite_points(gpu_ctx_factory):
     assert np.array_equal(out, words[:10]) and cnt == int(((words[:10] >> 24) & 1).sum())
 
 
+def test_one_cell_of_65_finite_points_and_a_nan(gpu_ctx_factory):
+    """one full work item of 64 queries plus one, through the gathered view of the finite points"""
+    rng = np.random.default_rng(65)
+    x, y, z = (np.float32(c) + rng.random(66).astype(np.float32) * np.float32(0.05) for c in (1.0, -2.0, 0.5))
+    y[40] = np.nan
+    words = _words(rng, 66, zero_share=0.0)
+    ctx = gpu_ctx_factory()
+    ctx.upload_cloud(x, y, z)
+    out = _check_packed(ctx, x, y, z, words, 0.1, sample=66)
+    assert out[40] == words[40]
+
+
 def test_radius_rules(gpu_ctx_factory):
     from pointcloudprocessor_amd import capi
 

@@ -208,6 +208,36 @@ def test_no_close_pairs_equals_roundtrip(gpu_ctx_factory):
     ctx.close()
 
 
+def test_non_finite_points_take_no_part(gpu_ctx_factory):
+    """A cloud with non-finite points (2 % of them; all of them; all but one): the table is built over the finite points alone,
+    so these get, bit for bit, what the same cloud without the others gets, and a non-finite point gets nothing."""
+    from pointcloudprocessor_amd import capi
+
+    cd, x, y, z, poses, imgs = _dup_scene(31, n=20_000, frames=4)
+    xyz = np.stack([x, y, z])
+    n = xyz.shape[1]
+    rng = np.random.default_rng(31)
+    ctx = gpu_ctx_factory()
+
+    def state(p):
+        _load(ctx, cam_struct(capi, cd), _cull(capi, capi.MATCH_RADIUS), p[0], p[1], p[2], poses, imgs)
+        return _gpu_state(ctx)
+
+    for bad in (rng.choice(n, n // 50, replace=False), np.arange(n), np.delete(np.arange(n), 1234)):
+        dirty = xyz.copy()
+        dirty[rng.integers(0, 3, len(bad)), bad] = rng.choice(np.float32([np.nan, np.inf, -np.inf]), len(bad))
+        got = state(dirty)
+        assert not got["has"][bad].any() and not got["count"][bad].any()
+        fin = np.setdiff1d(np.arange(n), bad)
+        assert len(fin) == n - len(bad)
+        if len(fin):
+            want = state(xyz[:, fin])
+            _same({k: got[k][fin] for k in KEYS}, want)
+        if len(fin) > 1:
+            assert got["count"][fin].max() > len(poses)  # (credits from other points: the table is in use)
+    ctx.close()
+
+
 def test_shard_context_refused(gpu_ctx_factory, small_scene):
     from pointcloudprocessor_amd import capi
 
