@@ -61,7 +61,9 @@ extern "C" {
                                 entry points added, no layout changed: pcp_voxel_reduce_begin / _add / _finish / _fetch / _stats / _end,
                                 pcp_voxel_reduce_host (voxel-grid output; nothing runs unless called);
                                 entry points added, no layout changed: pcp_estimate_normals, pcp_normals_fetch,
-                                pcp_normals_moments_host, pcp_frame_geometry (geometry maps; nothing runs unless called) */
+                                pcp_normals_moments_host, pcp_frame_geometry (geometry maps; nothing runs unless called);
+                                entry points added, no layout changed: pcp_mask_edt, pcp_mask_edt_frames, pcp_mask_edt_host
+                                (mask distance maps; nothing runs unless called) */
 
 #define PCP_OK 0
 #define PCP_ERR_INVALID (-1) /* bad argument */
@@ -802,6 +804,38 @@ int pcp_normals_fetch(pcp_context *ctx, float *out_normal, float *out_curvature,
 int pcp_normals_moments_host(float radius, int64_t n, const float *xyz, int64_t *out_moments);
 int pcp_frame_geometry(pcp_context *ctx, int32_t frame, int32_t *out_index, float *out_range, float *out_xyz_cam,
                        float *out_normal_cam, int64_t *out_pixels);
+
+/* ---- mask distance maps (scripts/genNormAndDistanceMask.py: class Crack, preprocess :150-198, cv2.threshold :167, */
+/* ---- scipy.ndimage.distance_transform_edt :9,168) ------------------------------------------------------------------ */
+/* Per keyframe, the exact Euclidean distance transform of its mask and the nearest background pixel of every pixel (DESIGN.md,
+ * "Mask distance maps", MD1-MD6).  Opt-in: nothing runs unless one of these is called, PCP_ABI_VERSION is unchanged and a
+ * caller detects support by the symbols.  Kernels are timed under PCP_K_MISC.
+ *
+ * Images of image_width x image_height of the context's camera, row-major, linear index y * W + x.  The mask byte m of a
+ * pixel is the top byte of the keyframe's texel (pcp_upload_mask; what pcp_download_image returns as out_mask).
+ *   threshold    0..255 (the script passes 0), else PCP_ERR_INVALID; a pixel is FOREGROUND iff m > threshold, else BACKGROUND;
+ *   out_d2       uint32 per pixel: the minimum over the background pixels b of (bx - px)^2 + (by - py)^2, the exact integer, 0
+ *                on a background pixel; sqrt((double)d2) is bit for bit what scipy.ndimage.distance_transform_edt(m > threshold)
+ *                returns;
+ *   out_nearest  int32 per pixel: the linear index of a background pixel at that distance -- of several the LOWEST index, i.e.
+ *                the pixel that minimises the 64-bit key (d2 << 32) | index; a background pixel is its own nearest;
+ *   a mask with NO background pixel gives d2 = 0xFFFFFFFF and nearest = -1 everywhere (scipy's result is then meaningless).
+ * Both outputs are host pointers and nullable.  W or H above 16384: PCP_ERR_RANGE (keeps d2 below 2^30 and a row's working
+ * set, 4 B per pixel, inside 64 KB of LDS).  A keyframe outside 0..n_frames-1 (or a negative count): PCP_ERR_RANGE.  A
+ * keyframe without an uploaded mask, no camera or no keyframes: PCP_ERR_STATE.  No cloud is needed.
+ * pcp_mask_edt_frames: keyframes first_frame .. first_frame + count - 1 in one call, `count` images back to back in each
+ * output; a few launches for all of them (chunks of 2^26 pixels), not a few per keyframe.  count 0 does nothing.
+ * Each call waits for the pending image uploads of its keyframes (the mask shares its word with the colour), is synchronous,
+ * and invalidates nothing: the texels, the colour state, the depth maps and every other result stay as they are.  Device
+ * buffers (12 B per pixel of one chunk, plus one bit per pixel) are allocated on first use and freed by pcp_destroy.
+ * pcp_mask_edt_host: host only, no context, no GPU: the same results for a mask of `width` x `height` bytes with rows
+ * row_stride_bytes apart (>= width), by the same arithmetic (csrc/pcp_mask_edt.hpp).  A NULL mask, an empty image or a bad
+ * stride or threshold: PCP_ERR_INVALID; a side above 16384: PCP_ERR_RANGE.  The message is at pcp_last_error(NULL). */
+int pcp_mask_edt(pcp_context *ctx, int32_t frame, int32_t threshold, uint32_t *out_d2, int32_t *out_nearest);
+int pcp_mask_edt_frames(pcp_context *ctx, int32_t first_frame, int32_t count, int32_t threshold, uint32_t *out_d2,
+                        int32_t *out_nearest);
+int pcp_mask_edt_host(int32_t width, int32_t height, const uint8_t *gray, int64_t row_stride_bytes, int32_t threshold,
+                      uint32_t *out_d2, int32_t *out_nearest);
 
 /* ---- precondition of the match-back(PointCloudProcessor.cpp:480-482,571) ------------------------------- */
 /* Number of map points that have ANOTHER map point closer than `radius` (fp32 squared distance, strict <, as

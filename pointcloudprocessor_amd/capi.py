@@ -305,6 +305,26 @@ def normals_moments_host(radius: float, xyz) -> np.ndarray:
     return out
 
 
+def mask_edt_host(gray, threshold: int = 0) -> dict:
+    """The mask distance maps of a (H, W) uint8 mask computed on the CPU with the arithmetic the kernels use
+    (pcp_mask_edt_host: no context, no GPU; DESIGN.md "Mask distance maps").  A row stride above the width is passed on
+    as it is.  dict(d2 (H, W) uint32, nearest (H, W) int32)."""
+    L = load()
+    gray = np.asarray(gray, np.uint8)
+    if gray.ndim != 2:
+        raise ValueError(f"mask_edt_host: a (H, W) mask is needed, got shape {gray.shape}")
+    if gray.size and gray.strides[1] != 1:
+        gray = np.ascontiguousarray(gray)
+    hh, ww = gray.shape
+    d2 = np.empty((hh, ww), np.uint32)
+    nearest = np.empty((hh, ww), np.int32)
+    rc = L.pcp_mask_edt_host(C.c_int32(ww), C.c_int32(hh), _ptr(gray), C.c_int64(gray.strides[0] if gray.size else 0),
+                             C.c_int32(threshold), _ptr(d2), _ptr(nearest))
+    if rc != PCP_OK:
+        raise PcpError(rc, L.pcp_last_error(None).decode())
+    return dict(d2=d2, nearest=nearest)
+
+
 def default_camera() -> Camera:
     cam = Camera()
     load().pcp_default_camera(C.byref(cam))
@@ -819,6 +839,28 @@ class Context:
         out = dict(index=idx, range=rng, xyz_cam=cam, pixels=px.value)
         if normals:
             out["normal_cam"] = nrm
+        return out
+
+    # -- mask distance maps ("Mask distance maps") ------------------------
+    def mask_edt(self, frame: int, threshold: int = 0, want_nearest: bool = True) -> dict:
+        """The exact squared distance from every pixel of the keyframe's mask to the nearest background pixel (mask byte
+        <= threshold) and that pixel's linear index, lowest index among equals (pcp_mask_edt): dict(d2 (H, W) uint32,
+        and with want_nearest nearest (H, W) int32).  A mask without background: d2 0xFFFFFFFF, nearest -1."""
+        out = self.mask_edt_frames(frame, 1, threshold, want_nearest)
+        return {k: v[0] for k, v in out.items()}
+
+    def mask_edt_frames(self, first: int, count: int, threshold: int = 0, want_nearest: bool = True) -> dict:
+        """mask_edt of keyframes first .. first + count - 1 in one call (pcp_mask_edt_frames): dict(d2 (count, H, W) uint32,
+        nearest (count, H, W) int32)."""
+        hh, ww = self.camera.image_height, self.camera.image_width
+        shape = (max(count, 0), hh, ww)
+        d2 = np.empty(shape, np.uint32)
+        nearest = np.empty(shape, np.int32) if want_nearest else None
+        self._check(self.lib.pcp_mask_edt_frames(self.h, C.c_int32(first), C.c_int32(count), C.c_int32(threshold), _ptr(d2),
+                                                 _ptr(nearest)))
+        out = dict(d2=d2)
+        if want_nearest:
+            out["nearest"] = nearest
         return out
 
     def colour_smooth_local(self, radius: float) -> int:

@@ -312,6 +312,12 @@ struct pcp_context {
   pcp::DevBuf<unsigned long long> gm_keys;
   pcp::DevBuf<uint32_t> gm_out;  // index | range | xyz_cam (3) | normal_cam (3), W*H words each
 
+  // mask distance maps (pcp_mask_edt.hip), for one chunk of keyframes, allocated on first use: the background bits of the
+  // column segments, the column words, and the two result images
+  pcp::DevBuf<unsigned long long> md_bits;
+  pcp::DevBuf<uint32_t> md_col, md_d2;
+  pcp::DevBuf<int32_t> md_nearest;
+
   // PCP_MATCH_RADIUS (pcp_match.hip): the neighbour table within R_c, built by the first colour pass in that mode and
   // dropped by pcp_upload_cloud / pcp_set_frames (E depends on both).  Set A = points whose row holds another point.
   bool match_live = false;
@@ -578,6 +584,7 @@ hipError_t preload_ascii_parse();
 hipError_t preload_exposure();
 hipError_t preload_voxel_reduce();
 hipError_t preload_normals();
+hipError_t preload_mask_edt();
 void normals_release(pcp_context *ctx);   // the normals of the cloud that is being replaced (the uploads)
 // the list pcp_frame_visible reports for one keyframe (pcp_colour.hip): ascending input indices in ctx->s_cell, *m of them;
 // checks the context and the keyframe as that call does, under the caller's name

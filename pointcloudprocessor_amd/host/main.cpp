@@ -105,6 +105,15 @@
 //     file.  No other output changes.  --gpus N above 1 is refused (an index shard sees only its own points; the per-pixel
 //     keys of the shards would have to be merged across GPUs, which is not built), and so is --enableMLS 1 (the colour
 //     stage then holds the smoothed cloud; maps of it are not built).
+//   * --crackMaps 0|1 (new, default 0; needs --mask_image_folder) and --crackThreshold t (new, default 0, 0..255): with 1,
+//     every selected keyframe also writes <outputPath>crack_maps/<imageTimestamp>_edt2.npy (<u4, (H, W)) and _nearest.npy
+//     (<i4, (H, W)) -- what scripts/genNormAndDistanceMask.py preprocess() :150-198 computes on the host with cv2.threshold
+//     :167 and scipy.ndimage.distance_transform_edt :168: the exact SQUARED distance from every pixel of the keyframe's mask
+//     to the nearest pixel whose mask byte is <= t (sqrt of it as fp64 is scipy's value bit for bit), and that pixel's
+//     linear index y * W + x, the lowest among equally near ones; a mask without such a pixel holds 0xFFFFFFFF and -1.  Made
+//     on the GPU from the masks the colour stage uploads (pcp_mask_edt_frames; DESIGN.md "Mask distance maps").  A keyframe
+//     whose mask could not be read writes no files.  No other output changes.  --gpus N above 1 is refused (one context
+//     holds every mask: the shards would add nothing).
 #include <cfloat>
 #include <chrono>
 #include <cmath>
@@ -191,6 +200,8 @@ struct Options {
   bool skip_full_cloud = false;       // --skip_full_cloud 1: with --outputLeaf, the full-resolution final files are not made
   bool geometry_maps = false;         // --geometryMaps 1: per-keyframe range / xyz / normal / index images (geometry_maps/*.npy)
   float normal_radius = 0.1f;         // --normalRadius r: neighbourhood of the map normals (0: no normals, no _normal file)
+  bool crack_maps = false;            // --crackMaps 1: per-keyframe mask distance maps (crack_maps/*.npy)
+  int crack_threshold = 0;            // --crackThreshold t: a mask byte above t is foreground
 };
 
 static bool parse_bool(const std::string &v) {  // boost::program_options bool semantics
@@ -294,6 +305,15 @@ static Options parse(int argc, char **argv) {
         throw std::runtime_error("the argument ('" + v + "') for option '--normalRadius' is invalid (0 = no normals, or 0.005 <= r <= 1)");
       o.normal_radius = r;
     }
+    else if (a == "--crackMaps") o.crack_maps = parse_bool(next());
+    else if (a == "--crackThreshold") {
+      const std::string v = next();
+      char *end = nullptr;
+      const long t = std::strtol(v.c_str(), &end, 10);
+      if (end == v.c_str() || *end != '\0' || t < 0 || t > 255)
+        throw std::runtime_error("the argument ('" + v + "') for option '--crackThreshold' is invalid (0..255)");
+      o.crack_threshold = static_cast<int>(t);
+    }
     else if (a == "--streamColour") {
       const std::string v = next();
       if (v != "0" && v != "1")
@@ -338,6 +358,11 @@ static Options parse(int argc, char **argv) {
   if (o.geometry_maps && o.gpus > 1)
     throw std::runtime_error("the option '--geometryMaps 1' does not work with '--gpus N' above 1 (an index shard sees only its own "
                              "points: the per-pixel keys of the shards would have to be merged across GPUs, which is not built)");
+  if (o.crack_maps && o.maskImageFolder.empty())
+    throw std::runtime_error("the option '--crackMaps 1' needs the masks (--mask_image_folder)");
+  if (o.crack_maps && o.gpus > 1)
+    throw std::runtime_error("the option '--crackMaps 1' does not work with '--gpus N' above 1 (the maps are made per keyframe from "
+                             "the masks of one context: index shards would add nothing)");
   if (o.geometry_maps && o.enableMLS)
     throw std::runtime_error("the option '--geometryMaps 1' does not work with '--enableMLS 1' (the maps are rendered from the raw "
                              "map; maps of the smoothed cloud are not built)");
@@ -387,7 +412,9 @@ static void usage(std::ostream &os) {
         "  --deviceReader arg (=0)               Parse the rows of the ASCII PCDs that are read on the GPU (same floats)\n"
         "  --balanceExposure arg (=0)            One brightness gain per keyframe from co-visible map points (--gpus 1)\n"
         "  --geometryMaps arg (=0)               Also write range / xyz / normal / index images per keyframe as .npy (--gpus 1)\n"
-        "  --normalRadius arg (=0.1)             With --geometryMaps: neighbourhood of the map normals (0 = no normals)\n";
+        "  --normalRadius arg (=0.1)             With --geometryMaps: neighbourhood of the map normals (0 = no normals)\n"
+        "  --crackMaps arg (=0)                  Also write the masks' squared distance and nearest-edge images as .npy (-m, --gpus 1)\n"
+        "  --crackThreshold arg (=0)             With --crackMaps: a mask byte above this is foreground (0..255)\n";
 }
 
 class Processor {
@@ -905,6 +932,7 @@ class Processor {
   // known).
   void streamedColourisation() {
     uploadImages(true);
+    if (opt.crack_maps) writeCrackMaps();
     if (opt.fuse_masks) {
       for (size_t k = 0; k < keyframes.size(); ++k)
         if (mask_missing[k]) throw std::runtime_error("Failed to read image from: " + keyframes[k].maskImagePath);
@@ -1051,6 +1079,39 @@ class Processor {
     }
   }
 
+  // --crackMaps 1: what preprocess() of scripts/genNormAndDistanceMask.py (:150-198) gets from cv2.threshold :167 and
+  // distance_transform_edt :168 per mask, from the masks on the device (uploadImages has run); runs of up to 8 keyframes
+  // per call
+  void writeCrackMaps() {
+    Device &dev = gpu->device(0);
+    const fs::path dir(opt.outputPath + "crack_maps/");
+    if (fs::exists(dir)) fs::remove_all(dir);
+    fs::create_directories(dir);
+    const size_t w = static_cast<size_t>(img_w), h = static_cast<size_t>(img_h), px = w * h, n = keyframes.size();
+    for (size_t k0 = 0; k0 < n;) {
+      if (mask_missing[k0]) {
+        std::cout << "Failed to read image from: " << keyframes[k0].maskImagePath << std::endl;
+        ++k0;
+        continue;
+      }
+      size_t k1 = k0 + 1;
+      while (k1 < n && k1 < k0 + 8 && !mask_missing[k1]) ++k1;
+      MaskDistance d;
+      {
+        Phase ph("crack_maps_gpu_s");
+        d = dev.maskDistance(static_cast<int>(k0), static_cast<int>(k1 - k0), img_w, img_h, opt.crack_threshold);
+      }
+      Phase ph_w("crack_maps_write_s");
+      for (size_t k = k0; k < k1; ++k) {
+        const std::string stem = opt.outputPath + "crack_maps/" + std::to_string(keyframes[k].imageTimestamp);
+        writeNpy(stem + "_edt2.npy", "<u4", {h, w}, d.d2.data() + (k - k0) * px, px * 4);
+        writeNpy(stem + "_nearest.npy", "<i4", {h, w}, d.nearest.data() + (k - k0) * px, px * 4);
+        std::cout << "Crack maps saved to: " << stem << "_edt2.npy, " << stem << "_nearest.npy" << std::endl;
+      }
+      k0 = k1;
+    }
+  }
+
   // --balanceExposure 1: the staged colour stage with the exposure gains between the colour pass and the finalise, and the
   // gains on record next to the outputs
   // (fetch = false, --skip_full_cloud 1: the result stays on the device)
@@ -1076,6 +1137,7 @@ class Processor {
 
   void pcdColorizationAndSmooth() {  // :474-602
     uploadImages(true);
+    if (opt.crack_maps) writeCrackMaps();
     std::vector<float> wx, wy, wz;  // cloudInWorldWithRGBandMask
     std::vector<float> wxyz;
     std::vector<uint8_t> wrgb;

@@ -43,6 +43,14 @@ struct GeometryMaps {
   std::vector<float> normal_cam;   // 3 per pixel: norm_mask (asked for), else empty
 };
 
+// The mask distance maps of `count` keyframes (pcp_hip.h, "mask distance maps"): images of `width` x `height`, row-major,
+// one keyframe after the other
+struct MaskDistance {
+  int32_t width = 0, height = 0, count = 0;
+  std::vector<uint32_t> d2;       // exact squared distance to the nearest background pixel (0xFFFFFFFF: the mask has none)
+  std::vector<int32_t> nearest;   // its linear index, the lowest of equally near ones (-1: none); empty when not asked for
+};
+
 class Device {
  public:
   explicit Device(int ordinal = 0) {
@@ -162,6 +170,21 @@ class Device {
     int64_t valid = 0;
     check(pcp_estimate_normals(ctx_, radius, &valid, nullptr));
     return valid;
+  }
+
+  // ---- mask distance maps: the squared Euclidean distance transform of the uploaded masks of keyframes first .. first +
+  // count - 1 and the nearest background pixel (a mask byte above `threshold` is foreground), in one call; what preprocess()
+  // computes per mask with cv2.threshold and scipy's distance_transform_edt (scripts/genNormAndDistanceMask.py:167-169)
+  MaskDistance maskDistance(int first, int count, int32_t width, int32_t height, int threshold = 0, bool with_nearest = true) {
+    MaskDistance d;
+    d.width = width;
+    d.height = height;
+    d.count = count;
+    const size_t px = static_cast<size_t>(width) * static_cast<size_t>(height) * static_cast<size_t>(count > 0 ? count : 0);
+    d.d2.resize(px);
+    d.nearest.resize(with_nearest ? px : 0);
+    check(pcp_mask_edt_frames(ctx_, first, count, threshold, d.d2.data(), with_nearest ? d.nearest.data() : nullptr));
+    return d;
   }
 
   // ---- device PCD reader: the x y z intensity floats of a window of PCD ASCII rows (pcp_hip.h, "device PCD reader") ----
