@@ -63,7 +63,9 @@ extern "C" {
                                 entry points added, no layout changed: pcp_estimate_normals, pcp_normals_fetch,
                                 pcp_normals_moments_host, pcp_frame_geometry (geometry maps; nothing runs unless called);
                                 entry points added, no layout changed: pcp_mask_edt, pcp_mask_edt_frames, pcp_mask_edt_host
-                                (mask distance maps; nothing runs unless called) */
+                                (mask distance maps; nothing runs unless called);
+                                entry points added, no layout changed: pcp_crack_width, pcp_crack_width_host (crack width maps;
+                                nothing runs unless called) */
 
 #define PCP_OK 0
 #define PCP_ERR_INVALID (-1) /* bad argument */
@@ -836,6 +838,50 @@ int pcp_mask_edt_frames(pcp_context *ctx, int32_t first_frame, int32_t count, in
                         int32_t *out_nearest);
 int pcp_mask_edt_host(int32_t width, int32_t height, const uint8_t *gray, int64_t row_stride_bytes, int32_t threshold,
                       uint32_t *out_d2, int32_t *out_nearest);
+
+/* ---- crack width maps (scripts/genNormAndDistanceMask.py: class Crack, compute_skeleton_edge_pts :396-478, ------------ */
+/* ---- find_edges_by_direction / trace_edge :706-762, find_local_plane :601-636, search_3d_edge_points :564-599) -------- */
+/* Per keyframe and per foreground pixel of its mask (a SITE): the two edge points along the exact EDT direction, the plane
+ * of the position image's window around the pixel, and the 3-D distance between the intersections of the two edge rays with
+ * that plane ("Crack width maps", CW1-CW9).  Opt-in: nothing runs unless one of these is called, PCP_ABI_VERSION
+ * is unchanged and a caller detects support by the symbols.  Kernels are timed under PCP_K_MISC.
+ *
+ * Images of image_width x image_height of the context's camera, row-major, linear index y * W + x.
+ *   threshold        0..255: a pixel is foreground iff its mask byte exceeds it (as pcp_mask_edt);
+ *   plane_radius_px  1..181 (the script uses 150): the plane's window is rows [max(0, y-R), min(H, y+R)), columns likewise;
+ *   out_flags    one byte per pixel: bit 0 SITE, 1 CENTRE (d2 >= d2 of every 8-neighbour inside the image), 2 NEAR and 3 FAR
+ *                (the trace towards / away from the nearest background pixel met a background pixel), 4 PLANE (3 members or
+ *                more and a finite normal), 5 RAYS (both edge rays good), 6 WIDTH (= NEAR & FAR & PLANE & RAYS); 0 on
+ *                background; a mask without a background pixel gives SITE only;
+ *   out_edges    4 int32 per pixel: the near and the far edge point, each DOUBLED (E = last foreground pixel + first background
+ *                pixel of the trace, x then y); -1 -1 for a side that is missing;
+ *   out_w2d2     |E_far - E_near|^2 in half-pixel units, 0 unless NEAR and FAR;
+ *   out_width    metres, fp32 of the fp64 norm; 0 without WIDTH;
+ *   out_points   6 floats per pixel: X_near, X_far in camera coordinates; 0 without WIDTH;
+ *   out_plane    4 floats per pixel: the unit normal facing the camera and -n.c; 0 without PLANE;
+ *   out_moments  13 int64 per pixel: n, r[3], S1'[3], S2'[6] (xx xy xz yy yz zz) of the window's members, positions quantised to
+ *                2^-16 m and recentred on the integer centroid r; exact; at every site, 0 on background;
+ *   *out_sites, *out_widths   pixels with SITE / with WIDTH.
+ * pcp_crack_width: every output is a host pointer and nullable.  Runs the keyframe's distance transform and geometry scatter
+ * (no normals) on the device itself, then its own kernels; synchronous; waits for the keyframe's pending uploads like
+ * pcp_mask_edt; invalidates nothing but the scratch images of pcp_mask_edt and pcp_frame_geometry.  No mask for the keyframe,
+ * no cloud, no keyframes or no camera: PCP_ERR_STATE.  A keyframe outside 0..n_frames-1, a side above 16384 or W * H above
+ * 2^26: PCP_ERR_RANGE.  A bad threshold or radius, or NULL params: PCP_ERR_INVALID.  Whole-map contexts only: an index shard
+ * sees only its own points.  Device buffers (80 B per pixel for the tables plus the requested outputs) are allocated on first
+ * use and freed by pcp_destroy.
+ * pcp_crack_width_host: host only, no context, no GPU: flags bits 0-3, edges, w2d2 and moments by the same arithmetic
+ * (csrc/pcp_crack_width.hpp) from a mask of `width` x `height` bytes with rows row_stride_bytes apart and the index and
+ * xyz_cam images pcp_frame_geometry returns.  The message is at pcp_last_error(NULL). */
+typedef struct pcp_crack_params {
+  int32_t threshold;
+  int32_t plane_radius_px;
+} pcp_crack_params;
+int pcp_crack_width(pcp_context *ctx, int32_t frame, const pcp_crack_params *params, uint8_t *out_flags, int32_t *out_edges,
+                    uint32_t *out_w2d2, float *out_width, float *out_points, float *out_plane, int64_t *out_moments,
+                    int64_t *out_sites, int64_t *out_widths);
+int pcp_crack_width_host(int32_t width, int32_t height, const uint8_t *gray, int64_t row_stride_bytes, const int32_t *index_image,
+                         const float *xyz_cam_image, const pcp_crack_params *params, uint8_t *out_flags, int32_t *out_edges,
+                         uint32_t *out_w2d2, int64_t *out_moments);
 
 /* ---- precondition of the match-back(PointCloudProcessor.cpp:480-482,571) ------------------------------- */
 /* Number of map points that have ANOTHER map point closer than `radius` (fp32 squared distance, strict <, as

@@ -325,6 +325,43 @@ def mask_edt_host(gray, threshold: int = 0) -> dict:
     return dict(d2=d2, nearest=nearest)
 
 
+class CrackParams(C.Structure):
+    _fields_ = [("threshold", C.c_int32), ("plane_radius_px", C.c_int32)]
+
+
+# the flag byte of the crack width maps (DESIGN.md "Crack width maps", CW9)
+CW_SITE, CW_CENTRE, CW_NEAR, CW_FAR, CW_PLANE, CW_RAYS, CW_WIDTH = 1, 2, 4, 8, 16, 32, 64
+CW_OUTPUTS = ("flags", "edges", "w2d2", "width", "points", "plane", "moments")
+
+
+def crack_width_host(gray, index, xyz_cam, threshold: int = 0, plane_radius: int = 150) -> dict:
+    """The integer part of the crack width maps computed on the CPU with the arithmetic the kernels use (pcp_crack_width_host:
+    no context, no GPU; DESIGN.md "Crack width maps"): gray (H, W) uint8 mask, index (H, W) int32 and xyz_cam (H, W, 3)
+    float32 as frame_geometry returns them.  dict(flags (H, W) uint8, bits 0-3 only; edges (H, W, 4) int32; w2d2 (H, W)
+    uint32; moments (H, W, 13) int64)."""
+    L = load()
+    gray = np.asarray(gray, np.uint8)
+    if gray.ndim != 2:
+        raise ValueError(f"crack_width_host: a (H, W) mask is needed, got shape {gray.shape}")
+    if gray.size and gray.strides[1] != 1:
+        gray = np.ascontiguousarray(gray)
+    hh, ww = gray.shape
+    index = np.ascontiguousarray(index, np.int32)
+    xyz_cam = np.ascontiguousarray(xyz_cam, np.float32)
+    if index.shape != (hh, ww) or xyz_cam.shape != (hh, ww, 3):
+        raise ValueError(f"crack_width_host: index {index.shape} / xyz_cam {xyz_cam.shape} do not match the mask {gray.shape}")
+    flags = np.empty((hh, ww), np.uint8)
+    edges = np.empty((hh, ww, 4), np.int32)
+    w2d2 = np.empty((hh, ww), np.uint32)
+    moments = np.empty((hh, ww, 13), np.int64)
+    prm = CrackParams(threshold, plane_radius)
+    rc = L.pcp_crack_width_host(C.c_int32(ww), C.c_int32(hh), _ptr(gray), C.c_int64(gray.strides[0] if gray.size else 0), _ptr(index),
+                                _ptr(xyz_cam), C.byref(prm), _ptr(flags), _ptr(edges), _ptr(w2d2), _ptr(moments))
+    if rc != PCP_OK:
+        raise PcpError(rc, L.pcp_last_error(None).decode())
+    return dict(flags=flags, edges=edges, w2d2=w2d2, moments=moments)
+
+
 def default_camera() -> Camera:
     cam = Camera()
     load().pcp_default_camera(C.byref(cam))
@@ -861,6 +898,28 @@ class Context:
         out = dict(d2=d2)
         if want_nearest:
             out["nearest"] = nearest
+        return out
+
+    # -- crack width maps ("Crack width maps") ----------------------------
+    def crack_width(self, frame: int, threshold: int = 0, plane_radius: int = 150,
+                    want=("flags", "edges", "w2d2", "width", "points", "plane")) -> dict:
+        """Per foreground pixel of the keyframe's mask: the two edge points along the EDT direction, the plane of the position
+        image's window and the 3-D width between the edge rays on it (pcp_crack_width).  want: any of CW_OUTPUTS; dict of
+        flags (H, W) uint8, edges (H, W, 4) int32 (doubled, -1 = missing), w2d2 (H, W) uint32, width (H, W) float32 metres,
+        points (H, W, 6) float32, plane (H, W, 4) float32, moments (H, W, 13) int64, plus sites and widths (counts)."""
+        unknown = set(want) - set(CW_OUTPUTS)
+        if unknown:
+            raise ValueError(f"crack_width: unknown outputs {sorted(unknown)}")
+        hh, ww = (self.camera.image_height, self.camera.image_width) if self.camera is not None else (0, 0)  # (the library refuses)
+        spec = dict(flags=((hh, ww), np.uint8), edges=((hh, ww, 4), np.int32), w2d2=((hh, ww), np.uint32), width=((hh, ww), np.float32),
+                    points=((hh, ww, 6), np.float32), plane=((hh, ww, 4), np.float32), moments=((hh, ww, 13), np.int64))
+        arr = {k: (np.empty(*spec[k]) if k in want else None) for k in CW_OUTPUTS}
+        prm = CrackParams(threshold, plane_radius)
+        sites, widths = C.c_int64(), C.c_int64()
+        self._check(self.lib.pcp_crack_width(self.h, C.c_int32(frame), C.byref(prm), *[_ptr(arr[k]) for k in CW_OUTPUTS],
+                                             C.byref(sites), C.byref(widths)))
+        out = {k: v for k, v in arr.items() if v is not None}
+        out["sites"], out["widths"] = sites.value, widths.value
         return out
 
     def colour_smooth_local(self, radius: float) -> int:

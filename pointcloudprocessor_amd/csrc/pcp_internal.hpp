@@ -318,6 +318,14 @@ struct pcp_context {
   pcp::DevBuf<uint32_t> md_col, md_d2;
   pcp::DevBuf<int32_t> md_nearest;
 
+  // crack width maps (pcp_crack_width.hip), allocated on first use: the ten summed-area planes of the origin moments
+  // (modulo 2^64) with the column stage's segment sums behind them, and the outputs a call asked for
+  pcp::DevBuf<unsigned long long> cw_sat;
+  pcp::DevBuf<uint8_t> cw_flags;
+  pcp::DevBuf<int32_t> cw_i32;     // edges (4 per pixel) | w2d2
+  pcp::DevBuf<float> cw_f32;       // plane (4 per pixel) | width | points (6 per pixel)
+  pcp::DevBuf<long long> cw_moments;  // 13 per pixel
+
   // PCP_MATCH_RADIUS (pcp_match.hip): the neighbour table within R_c, built by the first colour pass in that mode and
   // dropped by pcp_upload_cloud / pcp_set_frames (E depends on both).  Set A = points whose row holds another point.
   bool match_live = false;
@@ -585,6 +593,11 @@ hipError_t preload_exposure();
 hipError_t preload_voxel_reduce();
 hipError_t preload_normals();
 hipError_t preload_mask_edt();
+hipError_t preload_crack_width();
+// the device parts of pcp_mask_edt (one keyframe, with nearest) and pcp_frame_geometry under the caller's name: checks and
+// kernels, the results left in md_bits / md_d2 / md_nearest and gm_out / s_counter[0]; no copy, no synchronisation
+int mask_edt_device(pcp_context *ctx, const char *who, int32_t frame, int32_t threshold);
+int frame_geometry_device(pcp_context *ctx, const char *who, int32_t frame, bool with_normals);
 void normals_release(pcp_context *ctx);   // the normals of the cloud that is being replaced (the uploads)
 // the list pcp_frame_visible reports for one keyframe (pcp_colour.hip): ascending input indices in ctx->s_cell, *m of them;
 // checks the context and the keyframe as that call does, under the caller's name

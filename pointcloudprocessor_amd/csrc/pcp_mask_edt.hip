@@ -91,39 +91,52 @@ hipError_t preload_mask_edt() {
   return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_md_rows));
 }
 
-// keyframes [first, first + count) of a checked call: chunks of keyframes, three launches each, the images of a chunk copied
-// to the host behind its kernels
-static int mask_edt_run(pcp_context *ctx, int32_t first, int32_t count, int32_t threshold, uint32_t *out_d2, int32_t *out_nearest) {
+// device memory for `chunk` keyframes per launch
+static int mask_edt_reserve(pcp_context *ctx, int32_t chunk, bool want_nearest) {
   const int32_t w = ctx->dcam.img_w, h = ctx->dcam.img_h;
-  const int64_t px = static_cast<int64_t>(w) * h;
   const int32_t segs = (h + md::kSegmentRows - 1) / md::kSegmentRows;
-  const int32_t chunk = static_cast<int32_t>(std::min<int64_t>({count, std::max<int64_t>(1, kMdChunkPixels / px), 65535}));
-  const size_t cpx = static_cast<size_t>(chunk) * static_cast<size_t>(px);
+  const size_t cpx = static_cast<size_t>(chunk) * static_cast<size_t>(w) * static_cast<size_t>(h);
   PCP_HIP_TRY(ctx, ctx->md_bits.ensure(static_cast<size_t>(chunk) * segs * w + 4));
   PCP_HIP_TRY(ctx, ctx->md_col.ensure(cpx + 4));
   PCP_HIP_TRY(ctx, ctx->md_d2.ensure(cpx + 4));
-  if (out_nearest) PCP_HIP_TRY(ctx, ctx->md_nearest.ensure(cpx + 4));
-  int rc = wait_images(ctx, first, first + count);  // the mask byte shares its word with the colour
+  if (want_nearest) PCP_HIP_TRY(ctx, ctx->md_nearest.ensure(cpx + 4));
+  return PCP_OK;
+}
+
+// the three launches of keyframes [first, first + nf) of one chunk: their results stay in md_bits / md_d2 / md_nearest
+static int mask_edt_launch(pcp_context *ctx, int32_t first, int32_t nf, int32_t threshold, bool want_nearest) {
+  const int32_t w = ctx->dcam.img_w, h = ctx->dcam.img_h;
+  const int64_t px = static_cast<int64_t>(w) * h;
+  const int32_t segs = (h + md::kSegmentRows - 1) / md::kSegmentRows;
+  const dim3 cgrid(static_cast<uint32_t>((w + kMdBlock - 1) / kMdBlock), static_cast<uint32_t>(segs), static_cast<uint32_t>(nf));
+  const uint32_t *texels = ctx->images.p + static_cast<int64_t>(first) * px;
+  {
+    LaunchTimer lt(ctx, PCP_K_MISC);  // column stage
+    hipLaunchKernelGGL(k_md_bits, cgrid, dim3(kMdBlock), 0, ctx->stream, texels, w, h, segs, threshold, ctx->md_bits.p);
+    hipLaunchKernelGGL(k_md_columns, cgrid, dim3(kMdBlock), 0, ctx->stream, ctx->md_bits.p, w, h, segs, ctx->md_col.p);
+    PCP_HIP_TRY(ctx, hipGetLastError());
+  }
+  {
+    LaunchTimer lt(ctx, PCP_K_MISC);  // row stage
+    hipLaunchKernelGGL(k_md_rows, dim3(static_cast<uint32_t>(h), static_cast<uint32_t>(nf)), dim3(kMdBlock),
+                       static_cast<size_t>(w) * sizeof(uint32_t), ctx->stream, ctx->md_col.p, w, h, ctx->md_d2.p,
+                       want_nearest ? ctx->md_nearest.p : static_cast<int32_t *>(nullptr));
+    PCP_HIP_TRY(ctx, hipGetLastError());
+  }
+  return PCP_OK;
+}
+
+// keyframes [first, first + count) of a checked call: chunks of keyframes, three launches each, the images of a chunk copied
+// to the host behind its kernels
+static int mask_edt_run(pcp_context *ctx, int32_t first, int32_t count, int32_t threshold, uint32_t *out_d2, int32_t *out_nearest) {
+  const int64_t px = static_cast<int64_t>(ctx->dcam.img_w) * ctx->dcam.img_h;
+  const int32_t chunk = static_cast<int32_t>(std::min<int64_t>({count, std::max<int64_t>(1, kMdChunkPixels / px), 65535}));
+  int rc = mask_edt_reserve(ctx, chunk, out_nearest != nullptr);
   if (rc != PCP_OK) return rc;
-  const dim3 cgrid(static_cast<uint32_t>((w + kMdBlock - 1) / kMdBlock), static_cast<uint32_t>(segs), 1);
+  if ((rc = wait_images(ctx, first, first + count)) != PCP_OK) return rc;  // the mask byte shares its word with the colour
   for (int32_t f0 = 0; f0 < count; f0 += chunk) {
     const int32_t nf = std::min(chunk, count - f0);
-    const uint32_t *texels = ctx->images.p + static_cast<int64_t>(first + f0) * px;
-    {
-      LaunchTimer lt(ctx, PCP_K_MISC);  // column stage
-      hipLaunchKernelGGL(k_md_bits, dim3(cgrid.x, cgrid.y, static_cast<uint32_t>(nf)), dim3(kMdBlock), 0, ctx->stream, texels, w, h,
-                         segs, threshold, ctx->md_bits.p);
-      hipLaunchKernelGGL(k_md_columns, dim3(cgrid.x, cgrid.y, static_cast<uint32_t>(nf)), dim3(kMdBlock), 0, ctx->stream,
-                         ctx->md_bits.p, w, h, segs, ctx->md_col.p);
-      PCP_HIP_TRY(ctx, hipGetLastError());
-    }
-    {
-      LaunchTimer lt(ctx, PCP_K_MISC);  // row stage
-      hipLaunchKernelGGL(k_md_rows, dim3(static_cast<uint32_t>(h), static_cast<uint32_t>(nf)), dim3(kMdBlock),
-                         static_cast<size_t>(w) * sizeof(uint32_t), ctx->stream, ctx->md_col.p, w, h, ctx->md_d2.p,
-                         out_nearest ? ctx->md_nearest.p : static_cast<int32_t *>(nullptr));
-      PCP_HIP_TRY(ctx, hipGetLastError());
-    }
+    if ((rc = mask_edt_launch(ctx, first + f0, nf, threshold, out_nearest != nullptr)) != PCP_OK) return rc;
     const size_t words = static_cast<size_t>(nf) * static_cast<size_t>(px), at = static_cast<size_t>(f0) * static_cast<size_t>(px);
     if (out_d2) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_d2 + at, ctx->md_d2.p, words * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (out_nearest) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_nearest + at, ctx->md_nearest.p, words * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -132,8 +145,8 @@ static int mask_edt_run(pcp_context *ctx, int32_t first, int32_t count, int32_t 
   return PCP_OK;
 }
 
-static int mask_edt_checked(pcp_context *ctx, const char *who, int32_t first, int32_t count, int32_t threshold, uint32_t *out_d2,
-                            int32_t *out_nearest) {
+// what every call checks before it touches the device
+static int mask_edt_validate(pcp_context *ctx, const char *who, int32_t first, int32_t count, int32_t threshold) {
   if (!ctx) return PCP_ERR_INVALID;
   if (threshold < 0 || threshold > 255) return set_error(ctx, PCP_ERR_INVALID, "%s: threshold %d outside 0..255", who, threshold);
   if (!ctx->have_camera) return set_error(ctx, PCP_ERR_STATE, "%s: pcp_set_camera has not been called", who);
@@ -146,9 +159,28 @@ static int mask_edt_checked(pcp_context *ctx, const char *who, int32_t first, in
   for (int32_t f = first; f < first + count; ++f)
     if (!ctx->images.p || static_cast<size_t>(f) >= ctx->mask_set.size() || !ctx->mask_set[static_cast<size_t>(f)])
       return set_error(ctx, PCP_ERR_STATE, "%s: no mask uploaded for keyframe %d (pcp_upload_mask)", who, f);
-  if (count == 0 || w <= 0 || h <= 0) return PCP_OK;
+  return PCP_OK;
+}
+
+static int mask_edt_checked(pcp_context *ctx, const char *who, int32_t first, int32_t count, int32_t threshold, uint32_t *out_d2,
+                            int32_t *out_nearest) {
+  const int rc = mask_edt_validate(ctx, who, first, count, threshold);
+  if (rc != PCP_OK) return rc;
+  if (count == 0 || ctx->dcam.img_w <= 0 || ctx->dcam.img_h <= 0) return PCP_OK;
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
   return mask_edt_run(ctx, first, count, threshold, out_d2, out_nearest);
+}
+
+// The device part of pcp_mask_edt for one keyframe, for the stages that read the maps where they are (pcp_crack_width.hip):
+// checks under the caller's name, then the kernels; background bits, d2 and nearest of the keyframe stay in md_bits, md_d2
+// and md_nearest.  Nothing is copied and the stream is not synchronised.  The image must not be empty.
+int mask_edt_device(pcp_context *ctx, const char *who, int32_t frame, int32_t threshold) {
+  int rc = mask_edt_validate(ctx, who, frame, 1, threshold);
+  if (rc != PCP_OK) return rc;
+  PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if ((rc = mask_edt_reserve(ctx, 1, true)) != PCP_OK) return rc;
+  if ((rc = wait_images(ctx, frame, frame + 1)) != PCP_OK) return rc;
+  return mask_edt_launch(ctx, frame, 1, threshold, true);
 }
 
 }  // namespace pcp

@@ -291,6 +291,42 @@ static int estimate_normals(pcp_context *ctx, float radius, int64_t *out_valid, 
   return PCP_OK;
 }
 
+// The device part of pcp_frame_geometry, for the stages that read the maps where they are (pcp_crack_width.hip): the checks
+// of frame_contributors under the caller's name, then the three kernels.  The images stay in ctx->gm_out (index | range |
+// xyz_cam | normal_cam), the occupied count in ctx->s_counter[0]; nothing is copied and the stream is not synchronised.
+// with_normals needs a live estimate (the caller's to check).
+int frame_geometry_device(pcp_context *ctx, const char *who, int32_t frame, bool with_normals) {
+  int64_t m = 0;
+  int rc = frame_contributors(ctx, who, frame, &m);  // GM1: the list of pcp_frame_visible, in ctx->s_cell
+  if (rc != PCP_OK) return rc;
+  const int64_t px = static_cast<int64_t>(ctx->dcam.img_w) * ctx->dcam.img_h;
+  if (px <= 0) return PCP_OK;
+  const size_t spx = static_cast<size_t>(px);
+  PCP_HIP_TRY(ctx, ctx->gm_keys.ensure(spx + 4));
+  PCP_HIP_TRY(ctx, ctx->gm_out.ensure(8 * spx + 4));
+  PCP_HIP_TRY(ctx, ctx->s_counter.ensure(4));
+  PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->s_counter.p, 0, 8, ctx->stream));
+  const size_t plane = (static_cast<size_t>(ctx->n) + 3) & ~size_t(3);
+  const float *x = ctx->xyz.p, *y = ctx->xyz.p + plane, *z = ctx->xyz.p + 2 * plane;
+  int32_t *d_index = reinterpret_cast<int32_t *>(ctx->gm_out.p);
+  float *d_range = reinterpret_cast<float *>(ctx->gm_out.p + spx);
+  float *d_xyz = reinterpret_cast<float *>(ctx->gm_out.p + 2 * spx);
+  float *d_normal = reinterpret_cast<float *>(ctx->gm_out.p + 5 * spx);
+  const DevFrame &fr = ctx->hframes[static_cast<size_t>(frame)];
+  {
+    LaunchTimer lt(ctx, PCP_K_MISC);
+    hipLaunchKernelGGL(k_gm_clear, dim3(gn_blocks(px)), dim3(kGnBlock), 0, ctx->stream, ctx->gm_keys.p, px);
+    if (m > 0)
+      hipLaunchKernelGGL(k_gm_scatter, dim3(gn_blocks(m)), dim3(kGnBlock), 0, ctx->stream, x, y, z, ctx->dcam, fr, ctx->s_cell.p, m, px,
+                         ctx->gm_keys.p);
+    hipLaunchKernelGGL(k_gm_resolve, dim3(gn_blocks(px)), dim3(kGnBlock), 0, ctx->stream, ctx->gm_keys.p, px, x, y, z, fr,
+                       with_normals ? reinterpret_cast<const float4 *>(ctx->gn_normal.p) : nullptr, d_index, d_range, d_xyz,
+                       d_normal, ctx->s_counter.p);
+    PCP_HIP_TRY(ctx, hipGetLastError());
+  }
+  return PCP_OK;
+}
+
 // (pcp_create loads every code object of the library up front: see preload_code_objects in pcp_context.hip)
 hipError_t preload_normals() {
   hipFuncAttributes a;
@@ -385,34 +421,15 @@ int pcp_frame_geometry(pcp_context *ctx, int32_t frame, int32_t *out_index, floa
   if (out_pixels) *out_pixels = 0;
   if (out_normal_cam && !ctx->gn_live)
     return set_error(ctx, PCP_ERR_STATE, "pcp_frame_geometry: normal_cam needs pcp_estimate_normals on this cloud");
-  int64_t m = 0;
-  int rc = frame_contributors(ctx, "pcp_frame_geometry", frame, &m);  // GM1: the list of pcp_frame_visible, in ctx->s_cell
+  int rc = frame_geometry_device(ctx, "pcp_frame_geometry", frame, out_normal_cam != nullptr);
   if (rc != PCP_OK) return rc;
   const int64_t px = static_cast<int64_t>(ctx->dcam.img_w) * ctx->dcam.img_h;
   if (px <= 0) return PCP_OK;
   const size_t spx = static_cast<size_t>(px);
-  PCP_HIP_TRY(ctx, ctx->gm_keys.ensure(spx + 4));
-  PCP_HIP_TRY(ctx, ctx->gm_out.ensure(8 * spx + 4));
-  PCP_HIP_TRY(ctx, ctx->s_counter.ensure(4));
-  PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->s_counter.p, 0, 8, ctx->stream));
-  const size_t plane = (static_cast<size_t>(ctx->n) + 3) & ~size_t(3);
-  const float *x = ctx->xyz.p, *y = ctx->xyz.p + plane, *z = ctx->xyz.p + 2 * plane;
-  int32_t *d_index = reinterpret_cast<int32_t *>(ctx->gm_out.p);
-  float *d_range = reinterpret_cast<float *>(ctx->gm_out.p + spx);
-  float *d_xyz = reinterpret_cast<float *>(ctx->gm_out.p + 2 * spx);
-  float *d_normal = reinterpret_cast<float *>(ctx->gm_out.p + 5 * spx);
-  const DevFrame &fr = ctx->hframes[static_cast<size_t>(frame)];
-  {
-    LaunchTimer lt(ctx, PCP_K_MISC);
-    hipLaunchKernelGGL(k_gm_clear, dim3(gn_blocks(px)), dim3(kGnBlock), 0, ctx->stream, ctx->gm_keys.p, px);
-    if (m > 0)
-      hipLaunchKernelGGL(k_gm_scatter, dim3(gn_blocks(m)), dim3(kGnBlock), 0, ctx->stream, x, y, z, ctx->dcam, fr, ctx->s_cell.p, m, px,
-                         ctx->gm_keys.p);
-    hipLaunchKernelGGL(k_gm_resolve, dim3(gn_blocks(px)), dim3(kGnBlock), 0, ctx->stream, ctx->gm_keys.p, px, x, y, z, fr,
-                       out_normal_cam ? reinterpret_cast<const float4 *>(ctx->gn_normal.p) : nullptr, d_index, d_range, d_xyz,
-                       d_normal, ctx->s_counter.p);
-    PCP_HIP_TRY(ctx, hipGetLastError());
-  }
+  const int32_t *d_index = reinterpret_cast<const int32_t *>(ctx->gm_out.p);
+  const float *d_range = reinterpret_cast<const float *>(ctx->gm_out.p + spx);
+  const float *d_xyz = reinterpret_cast<const float *>(ctx->gm_out.p + 2 * spx);
+  const float *d_normal = reinterpret_cast<const float *>(ctx->gm_out.p + 5 * spx);
   unsigned long long occupied = 0;
   PCP_HIP_TRY(ctx, hipMemcpyAsync(&occupied, ctx->s_counter.p, 8, hipMemcpyDeviceToHost, ctx->stream));
   if (out_index) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_index, d_index, spx * 4, hipMemcpyDeviceToHost, ctx->stream));

@@ -114,6 +114,18 @@
 //     on the GPU from the masks the colour stage uploads (pcp_mask_edt_frames; DESIGN.md "Mask distance maps").  A keyframe
 //     whose mask could not be read writes no files.  No other output changes.  --gpus N above 1 is refused (one context
 //     holds every mask: the shards would add nothing).
+//   * --crackWidth 0|1 (new, default 0; needs --mask_image_folder) and --crackPlaneRadius R (new, default 150, 1..181;
+//     --crackThreshold is reused): with 1, every selected keyframe whose mask was read also writes
+//     <outputPath>crack_width/<imageTimestamp>_width.npy (<f4, (H, W), metres), _edges.npy (<i4, (H, W, 4): the near and the
+//     far edge point of the pixel, doubled, -1 = missing), _flags.npy (|u1, (H, W): SITE CENTRE NEAR FAR PLANE RAYS WIDTH from
+//     bit 0) and _points.npy (<f4, (H, W, 6): the two 3-D edge points in camera coordinates) -- the second half of
+//     Crack.process() in scripts/genNormAndDistanceMask.py, compute_skeleton_edge_pts :396-478, for EVERY foreground pixel of
+//     the mask instead of hand-picked skeleton points: the edges along the exact EDT direction (for trace_edge :706-762), the
+//     plane of the position image's window of +-R pixels (find_local_plane :601-636) and the intersection of the edge rays
+//     with it (for the grid search of search_3d_edge_points :564-599).  Made on the GPU from the masks the colour stage
+//     uploads and the raw map (pcp_crack_width; DESIGN.md "Crack width maps"), with the poses the colourisation uses.  The
+//     counts of sites and widths are printed per keyframe.  No other output changes.  --gpus N above 1 and --enableMLS 1 are
+//     refused for the reasons --geometryMaps gives.
 #include <cfloat>
 #include <chrono>
 #include <cmath>
@@ -202,6 +214,8 @@ struct Options {
   float normal_radius = 0.1f;         // --normalRadius r: neighbourhood of the map normals (0: no normals, no _normal file)
   bool crack_maps = false;            // --crackMaps 1: per-keyframe mask distance maps (crack_maps/*.npy)
   int crack_threshold = 0;            // --crackThreshold t: a mask byte above t is foreground
+  bool crack_width = false;           // --crackWidth 1: per-keyframe crack width maps (crack_width/*.npy)
+  int crack_plane_radius = 150;       // --crackPlaneRadius R: half side of the plane's window, pixels
 };
 
 static bool parse_bool(const std::string &v) {  // boost::program_options bool semantics
@@ -314,6 +328,15 @@ static Options parse(int argc, char **argv) {
         throw std::runtime_error("the argument ('" + v + "') for option '--crackThreshold' is invalid (0..255)");
       o.crack_threshold = static_cast<int>(t);
     }
+    else if (a == "--crackWidth") o.crack_width = parse_bool(next());
+    else if (a == "--crackPlaneRadius") {
+      const std::string v = next();
+      char *end = nullptr;
+      const long r = std::strtol(v.c_str(), &end, 10);
+      if (end == v.c_str() || *end != '\0' || r < 1 || r > 181)
+        throw std::runtime_error("the argument ('" + v + "') for option '--crackPlaneRadius' is invalid (1..181)");
+      o.crack_plane_radius = static_cast<int>(r);
+    }
     else if (a == "--streamColour") {
       const std::string v = next();
       if (v != "0" && v != "1")
@@ -363,6 +386,14 @@ static Options parse(int argc, char **argv) {
   if (o.crack_maps && o.gpus > 1)
     throw std::runtime_error("the option '--crackMaps 1' does not work with '--gpus N' above 1 (the maps are made per keyframe from "
                              "the masks of one context: index shards would add nothing)");
+  if (o.crack_width && o.maskImageFolder.empty())
+    throw std::runtime_error("the option '--crackWidth 1' needs the masks (--mask_image_folder)");
+  if (o.crack_width && o.gpus > 1)
+    throw std::runtime_error("the option '--crackWidth 1' does not work with '--gpus N' above 1 (an index shard sees only its own "
+                             "points: the per-pixel keys of the shards would have to be merged across GPUs, which is not built)");
+  if (o.crack_width && o.enableMLS)
+    throw std::runtime_error("the option '--crackWidth 1' does not work with '--enableMLS 1' (the planes are fitted to the raw "
+                             "map; maps of the smoothed cloud are not built)");
   if (o.geometry_maps && o.enableMLS)
     throw std::runtime_error("the option '--geometryMaps 1' does not work with '--enableMLS 1' (the maps are rendered from the raw "
                              "map; maps of the smoothed cloud are not built)");
@@ -414,7 +445,9 @@ static void usage(std::ostream &os) {
         "  --geometryMaps arg (=0)               Also write range / xyz / normal / index images per keyframe as .npy (--gpus 1)\n"
         "  --normalRadius arg (=0.1)             With --geometryMaps: neighbourhood of the map normals (0 = no normals)\n"
         "  --crackMaps arg (=0)                  Also write the masks' squared distance and nearest-edge images as .npy (-m, --gpus 1)\n"
-        "  --crackThreshold arg (=0)             With --crackMaps: a mask byte above this is foreground (0..255)\n";
+        "  --crackThreshold arg (=0)             With --crackMaps / --crackWidth: a mask byte above this is foreground (0..255)\n"
+        "  --crackWidth arg (=0)                 Also write width / edges / flags / points images per keyframe as .npy (-m, --gpus 1)\n"
+        "  --crackPlaneRadius arg (=150)         With --crackWidth: half side of the plane's window in pixels (1..181)\n";
 }
 
 class Processor {
@@ -1112,6 +1145,36 @@ class Processor {
     }
   }
 
+  // --crackWidth 1: the second half of Crack.process() (compute_skeleton_edge_pts, scripts/genNormAndDistanceMask.py
+  // :396-478) at every foreground pixel, per selected keyframe, from the masks and the raw map on the device (uploadImages has
+  // run)
+  void writeCrackWidth() {
+    Device &dev = gpu->device(0);
+    const fs::path dir(opt.outputPath + "crack_width/");
+    if (fs::exists(dir)) fs::remove_all(dir);
+    fs::create_directories(dir);
+    const ViewCulling vc(dev);
+    const size_t w = static_cast<size_t>(img_w), h = static_cast<size_t>(img_h);
+    for (size_t k = 0; k < keyframes.size(); ++k) {
+      if (mask_missing[k]) {
+        std::cout << "Failed to read image from: " << keyframes[k].maskImagePath << std::endl;
+        continue;
+      }
+      CrackWidth c;
+      {
+        Phase ph("crack_width_gpu_s");
+        c = vc.crackWidth(static_cast<int>(k), img_w, img_h, opt.crack_threshold, opt.crack_plane_radius);
+      }
+      Phase ph_w("crack_width_write_s");
+      const std::string stem = opt.outputPath + "crack_width/" + std::to_string(keyframes[k].imageTimestamp);
+      writeNpy(stem + "_width.npy", "<f4", {h, w}, c.width_m.data(), c.width_m.size() * 4);
+      writeNpy(stem + "_edges.npy", "<i4", {h, w, 4}, c.edges.data(), c.edges.size() * 4);
+      writeNpy(stem + "_flags.npy", "|u1", {h, w}, c.flags.data(), c.flags.size());
+      writeNpy(stem + "_points.npy", "<f4", {h, w, 6}, c.points.data(), c.points.size() * 4);
+      std::cout << "Crack width maps saved to: " << stem << "_*.npy, " << c.sites << " sites, " << c.widths << " widths" << std::endl;
+    }
+  }
+
   // --balanceExposure 1: the staged colour stage with the exposure gains between the colour pass and the finalise, and the
   // gains on record next to the outputs
   // (fetch = false, --skip_full_cloud 1: the result stays on the device)
@@ -1138,6 +1201,7 @@ class Processor {
   void pcdColorizationAndSmooth() {  // :474-602
     uploadImages(true);
     if (opt.crack_maps) writeCrackMaps();
+    if (opt.crack_width) writeCrackWidth();
     std::vector<float> wx, wy, wz;  // cloudInWorldWithRGBandMask
     std::vector<float> wxyz;
     std::vector<uint8_t> wrgb;

@@ -51,6 +51,17 @@ struct MaskDistance {
   std::vector<int32_t> nearest;   // its linear index, the lowest of equally near ones (-1: none); empty when not asked for
 };
 
+// The crack width maps of one keyframe (pcp_hip.h, "crack width maps"): images of `width` x `height`, row-major
+struct CrackWidth {
+  int32_t width = 0, height = 0;
+  int64_t sites = 0, widths = 0;   // pixels with the SITE / the WIDTH flag
+  std::vector<uint8_t> flags;      // bit 0 SITE, 1 CENTRE, 2 NEAR, 3 FAR, 4 PLANE, 5 RAYS, 6 WIDTH
+  std::vector<int32_t> edges;      // 4 per pixel: the near and the far edge point, doubled; -1: missing
+  std::vector<float> width_m;      // metres, 0 without WIDTH
+  std::vector<float> points;       // 6 per pixel: the two edge points in camera coordinates
+  std::vector<float> plane;        // 4 per pixel: unit normal facing the camera and -n.c (asked for), else empty
+};
+
 class Device {
  public:
   explicit Device(int ordinal = 0) {
@@ -235,6 +246,25 @@ class ViewCulling {
     dev_.check(pcp_frame_geometry(dev_.get(), keyframe, g.index.data(), g.range.data(), g.xyz_cam.data(),
                                   with_normals ? g.normal_cam.data() : nullptr, &g.pixels));
     return g;
+  }
+  // what compute_skeleton_edge_pts measures at hand-picked skeleton points (scripts/genNormAndDistanceMask.py:396-478), at
+  // every foreground pixel of the keyframe's uploaded mask: edge points along the EDT direction, the local plane of the
+  // position image within +-plane_radius pixels, and the 3-D width between the edge rays on it
+  CrackWidth crackWidth(int keyframe, int32_t width, int32_t height, int threshold = 0, int plane_radius = 150,
+                        bool with_plane = false) const {
+    CrackWidth c;
+    c.width = width;
+    c.height = height;
+    const size_t px = static_cast<size_t>(width) * static_cast<size_t>(height);
+    c.flags.resize(px);
+    c.edges.resize(4 * px);
+    c.width_m.resize(px);
+    c.points.resize(6 * px);
+    c.plane.resize(with_plane ? 4 * px : 0);
+    const pcp_crack_params prm{threshold, plane_radius};
+    dev_.check(pcp_crack_width(dev_.get(), keyframe, &prm, c.flags.data(), c.edges.data(), nullptr, c.width_m.data(), c.points.data(),
+                               with_plane ? c.plane.data() : nullptr, nullptr, &c.sites, &c.widths));
+    return c;
   }
 
  private:

@@ -190,6 +190,22 @@ class PointCloudColorizer:
             ctx.estimate_normals(normal_radius)
         return ctx.frame_geometry(frame, normals=bool(normal_radius))
 
+    def crack_width(self, frame: int, threshold: int = 0, plane_radius: int = 150,
+                    want=("flags", "edges", "w2d2", "width", "points", "plane")) -> dict:
+        """The crack width maps of one keyframe at camera resolution, made on the device ("Crack width maps"): per
+        foreground pixel of the keyframe's mask the two edge points along the EDT direction, the plane of the position
+        image's window of +-plane_radius pixels and the 3-D width between the two edge rays on that plane -- the second half
+        of Crack.process() in scripts/genNormAndDistanceMask.py (compute_skeleton_edge_pts).  See capi.Context.crack_width
+        for the arrays.
+
+        The plane comes from the keyframe's geometry map, and an index shard sees only its own points, so world > 1 raises
+        ValueError.  (The shards' key images would have to be merged first, as for geometry_maps; not built.)"""
+        if self.world > 1:
+            raise ValueError("crack_width: an index shard sees only its own points; the per-pixel keys of the shards would "
+                             "have to be merged across ranks (all-reduce MIN), which is not built: run it on one rank "
+                             "holding the whole map")
+        return self.engine.ctx.crack_width(frame, threshold, plane_radius, want)
+
     def run(self, download: bool = True, local_smooth_radius: float = 0.0, fuse_labels: bool = False, output_leaf: float = 0.0):
         """Local points' colours: dict(rgb (n,3) uint8, has (n,) uint8).
 
