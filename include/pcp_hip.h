@@ -65,7 +65,9 @@ extern "C" {
                                 entry points added, no layout changed: pcp_mask_edt, pcp_mask_edt_frames, pcp_mask_edt_host
                                 (mask distance maps; nothing runs unless called);
                                 entry points added, no layout changed: pcp_crack_width, pcp_crack_width_host (crack width maps;
-                                nothing runs unless called) */
+                                nothing runs unless called);
+                                entry points added, no layout changed: pcp_crack_fuse_begin / _add / _fetch / _end / _host,
+                                pcp_crack_components / _fetch / _host (crack widths on the map; nothing runs unless called) */
 
 #define PCP_OK 0
 #define PCP_ERR_INVALID (-1) /* bad argument */
@@ -882,6 +884,62 @@ int pcp_crack_width(pcp_context *ctx, int32_t frame, const pcp_crack_params *par
 int pcp_crack_width_host(int32_t width, int32_t height, const uint8_t *gray, int64_t row_stride_bytes, const int32_t *index_image,
                          const float *xyz_cam_image, const pcp_crack_params *params, uint8_t *out_flags, int32_t *out_edges,
                          uint32_t *out_w2d2, int64_t *out_moments);
+
+/* ---- crack widths on the map (scripts/genNormAndDistanceMask.py: compute_skeleton_edge_pts :396-478, the result file :476-478) */
+/* The widths pcp_crack_width measures per keyframe, brought back to the map points that see them, and the map's cracks as
+ * connected components of the crack points ("Crack widths on the map", CF1-CF6 and CC1-CC6).  Opt-in: nothing
+ * runs unless one of these is called, PCP_ABI_VERSION is unchanged and a caller detects support by the symbols.  Kernels are
+ * timed under PCP_K_MISC.  Whole-map contexts only: an index shard sees only its own points.
+ *
+ * Fusion.  pcp_crack_fuse_begin creates the accumulation for the uploaded cloud (40 B per point on the device): per point, in
+ * input order, seen = added keyframes that list the point as a contributor (exactly pcp_frame_visible's list), views = those
+ * whose pixel (pcp_project_frame's out_pixel) has WIDTH in pcp_crack_width's flags for the same keyframe and parameters,
+ * centres = those whose pixel also has CENTRE, and over the credited keyframes sum_q, min_q (0xFFFFFFFF without one), max_q of
+ * the quantum q = rint(width * 2^20), ties to even, 2^31 - 1 from 2048 m on, and the q of the keyframe with the smallest
+ * (fp32 range, keyframe).  pcp_crack_fuse_add runs the keyframe's geometry scatter, distance transform and width kernels as
+ * pcp_crack_width does (same checks and returns for the arguments they share; it invalidates what that call invalidates),
+ * keeps the images on the device and adds the keyframe; *out_contributors / *out_credited (nullable) = listed / credited
+ * points.  A keyframe is added once per accumulation: again is PCP_ERR_STATE and changes nothing, as does any failed add.
+ * The final state does not depend on the order of the adds.  pcp_crack_fuse_fetch: all outputs nullable, n each, input order:
+ *   width_mean = (float)(((double)sum_q / (double)views) * 2^-20), width_best = (float)((double)best_q * 2^-20), best_frame the
+ *   keyframe of best_q; 0, 0 and -1 with views = 0.
+ * pcp_crack_fuse_end releases it; pcp_upload_cloud*, pcp_set_camera and pcp_set_frames drop it.  _add, _fetch, _end,
+ * pcp_crack_components and its fetch without a live accumulation: PCP_ERR_STATE.
+ * pcp_crack_fuse_host: host only, no context, no GPU: one keyframe's add on caller-held state arrays of n points by the same
+ * arithmetic (csrc/pcp_crack_fuse.hpp): m contributors (index into the state, pixel y * W + x, positive finite range) against
+ * the width x height flag and width images.  A bad entry: PCP_ERR_INVALID and nothing changed.  Message at pcp_last_error(NULL).
+ *
+ * Cracks.  pcp_crack_components reads the live accumulation: point i is a crack point iff views[i] >= min_views
+ * (1..4096) and its coordinates are finite; crack points i != j are linked iff fl32((dx*dx + dy*dy) + dz*dz) <= t with
+ * d = fl32(p_j - p_i) and t the largest float with (double)t <= (double)radius^2 (pcp_estimate_normals' neighbour rule;
+ * 0.005 <= radius <= 1); out_label (nullable, n, host) = the lowest input index of the point's connected component, -1 for a
+ * point that is no crack point.  *out_crack_points / *out_components (nullable).  Bad parameters: PCP_ERR_INVALID.  Like every
+ * call that builds the search grid it invalidates an open pcp_mls_stream / pcp_cloud_smooth_stream and a pcp_sor_partial.
+ * pcp_crack_components_fetch: rows first .. first + max_rows - 1 of the table of that call, one row per crack, ascending by id
+ * (= label): out_stats 5 int64 per row -- points, sum_w, min_w, max_w over the members' w = floor((2 sum_q + views) /
+ * (2 views)), centre_points = members with centres > 0 -- and out_box 6 floats per row, the exact min x y z and max x y z of
+ * the members' uploaded coordinates.  The table lives until the next _add, _end or drop of the accumulation.
+ * pcp_crack_components_host: host only: the labels of n <= 65536 points (xyz interleaved) by brute force over the pairs. */
+typedef struct pcp_crack_link_params {
+  int32_t min_views;
+  float radius;
+} pcp_crack_link_params;
+int pcp_crack_fuse_begin(pcp_context *ctx);
+int pcp_crack_fuse_add(pcp_context *ctx, int32_t frame, const pcp_crack_params *params, int64_t *out_contributors,
+                       int64_t *out_credited);
+int pcp_crack_fuse_fetch(pcp_context *ctx, float *out_width_mean, float *out_width_best, int32_t *out_best_frame, uint32_t *out_views,
+                         uint32_t *out_seen, uint32_t *out_centres, uint32_t *out_min_q, uint32_t *out_max_q, uint64_t *out_sum_q);
+int pcp_crack_fuse_end(pcp_context *ctx);
+int pcp_crack_fuse_host(int64_t n, uint32_t *seen, uint32_t *views, uint32_t *centres, uint32_t *min_q, uint32_t *max_q,
+                        uint32_t *best_q, uint64_t *sum_q, uint64_t *best_key, int64_t m, const int32_t *index, const int32_t *pixel,
+                        const float *range, int32_t frame, int32_t width, int32_t height, const uint8_t *flags, const float *width_image,
+                        int64_t *out_credited);
+int pcp_crack_components(pcp_context *ctx, const pcp_crack_link_params *p, int32_t *out_label, int64_t *out_crack_points,
+                         int64_t *out_components);
+int pcp_crack_components_fetch(pcp_context *ctx, int64_t first, int64_t max_rows, int32_t *out_id, int64_t *out_stats, float *out_box,
+                               int64_t *out_rows);
+int pcp_crack_components_host(int64_t n, const float *xyz, const uint32_t *views, int32_t min_views, float radius, int32_t *out_label,
+                              int64_t *out_components);
 
 /* ---- precondition of the match-back(PointCloudProcessor.cpp:480-482,571) ------------------------------- */
 /* Number of map points that have ANOTHER map point closer than `radius` (fp32 squared distance, strict <, as

@@ -362,6 +362,66 @@ def crack_width_host(gray, index, xyz_cam, threshold: int = 0, plane_radius: int
     return dict(flags=flags, edges=edges, w2d2=w2d2, moments=moments)
 
 
+class CrackLinkParams(C.Structure):
+    _fields_ = [("min_views", C.c_int32), ("radius", C.c_float)]
+
+
+# the state of the crack widths on the map, one array of n per field (DESIGN.md "Crack widths on the map", CF1-CF6)
+CF_STATE = (("seen", np.uint32), ("views", np.uint32), ("centres", np.uint32), ("min_q", np.uint32), ("max_q", np.uint32),
+            ("best_q", np.uint32), ("sum_q", np.uint64), ("best_key", np.uint64))
+CF_OUTPUTS = (("width_mean", np.float32), ("width_best", np.float32), ("best_frame", np.int32), ("views", np.uint32), ("seen", np.uint32),
+              ("centres", np.uint32), ("min_q", np.uint32), ("max_q", np.uint32), ("sum_q", np.uint64))
+
+
+def crack_fuse_state(n: int) -> dict:
+    """A fresh accumulation of n points as pcp_crack_fuse_begin creates it, for crack_fuse_host."""
+    st = {k: np.zeros(n, t) for k, t in CF_STATE}
+    st["min_q"][:] = 0xFFFFFFFF
+    st["best_key"][:] = 0xFFFFFFFFFFFFFFFF
+    return st
+
+
+def crack_fuse_host(state: dict, index, pixel, range_, frame: int, flags, width) -> int:
+    """One keyframe's add on the CPU with the arithmetic the kernel uses (pcp_crack_fuse_host: no context, no GPU): `state` from
+    crack_fuse_state is updated in place by the m contributors (index into the state, pixel y * W + x, fp32 range) against
+    the (H, W) flags and width images of crack_width.  Returns the number of credited contributors."""
+    L = load()
+    n = len(state["seen"])
+    for k, t in CF_STATE:
+        if state[k].dtype != t or state[k].shape != (n,) or not state[k].flags.c_contiguous:
+            raise ValueError(f"crack_fuse_host: state[{k!r}] is not a contiguous {np.dtype(t).name} array of {n}")
+    index = np.ascontiguousarray(index, np.int32)
+    pixel = np.ascontiguousarray(pixel, np.int32)
+    range_ = np.ascontiguousarray(range_, np.float32)
+    flags = np.ascontiguousarray(flags, np.uint8)
+    width = np.ascontiguousarray(width, np.float32)
+    if flags.ndim != 2 or width.shape != flags.shape or not (index.shape == pixel.shape == range_.shape) or index.ndim != 1:
+        raise ValueError("crack_fuse_host: (H, W) flags and width images and three contributor arrays of one length are needed")
+    hh, ww = flags.shape
+    credited = C.c_int64()
+    rc = L.pcp_crack_fuse_host(C.c_int64(n), *[_ptr(state[k]) for k, _ in CF_STATE], C.c_int64(len(index)), _ptr(index), _ptr(pixel),
+                               _ptr(range_), C.c_int32(frame), C.c_int32(ww), C.c_int32(hh), _ptr(flags), _ptr(width), C.byref(credited))
+    if rc != PCP_OK:
+        raise PcpError(rc, L.pcp_last_error(None).decode())
+    return credited.value
+
+
+def crack_components_host(xyz, views, min_views: int = 1, radius: float = 0.02) -> np.ndarray:
+    """The labels of pcp_crack_components computed on the CPU by brute force over the pairs (pcp_crack_components_host: no
+    context, no GPU): xyz (n, 3) float32, views (n,) uint32, n <= 65536 -> (n,) int32, the lowest index of the point's
+    component, -1 for a point that is no crack point."""
+    L = load()
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    views = np.ascontiguousarray(views, np.uint32)
+    if views.shape != (xyz.shape[0],):
+        raise ValueError(f"crack_components_host: {xyz.shape[0]} views expected, got shape {views.shape}")
+    label = np.empty(xyz.shape[0], np.int32)
+    rc = L.pcp_crack_components_host(C.c_int64(xyz.shape[0]), _ptr(xyz), _ptr(views), C.c_int32(min_views), C.c_float(radius), _ptr(label), None)
+    if rc != PCP_OK:
+        raise PcpError(rc, L.pcp_last_error(None).decode())
+    return label
+
+
 def default_camera() -> Camera:
     cam = Camera()
     load().pcp_default_camera(C.byref(cam))
@@ -921,6 +981,50 @@ class Context:
         out = {k: v for k, v in arr.items() if v is not None}
         out["sites"], out["widths"] = sites.value, widths.value
         return out
+
+    # -- crack widths on the map ("Crack widths on the map") -----------------
+    def crack_fuse_begin(self):
+        """A fresh accumulation for the uploaded cloud (pcp_crack_fuse_begin); the uploads, set_camera and set_frames drop it."""
+        self._check(self.lib.pcp_crack_fuse_begin(self.h))
+
+    def crack_fuse_add(self, frame: int, threshold: int = 0, plane_radius: int = 150) -> tuple[int, int]:
+        """Adds the keyframe's crack widths to the points that see them (pcp_crack_fuse_add): (contributors, credited)."""
+        prm = CrackParams(threshold, plane_radius)
+        m, c = C.c_int64(), C.c_int64()
+        self._check(self.lib.pcp_crack_fuse_add(self.h, C.c_int32(frame), C.byref(prm), C.byref(m), C.byref(c)))
+        return m.value, c.value
+
+    def crack_fuse_fetch(self, want=("width_mean", "width_best", "best_frame", "views", "seen", "centres", "min_q", "max_q", "sum_q")) -> dict:
+        """The accumulated state per map point, input order (pcp_crack_fuse_fetch): any of width_mean / width_best (float32,
+        metres), best_frame (int32, -1 without a view), views / seen / centres / min_q / max_q (uint32), sum_q (uint64)."""
+        names = [k for k, _ in CF_OUTPUTS]
+        unknown = set(want) - set(names)
+        if unknown:
+            raise ValueError(f"crack_fuse_fetch: unknown outputs {sorted(unknown)}")
+        arr = {k: (np.zeros(self.n, t) if k in want else None) for k, t in CF_OUTPUTS}
+        self._check(self.lib.pcp_crack_fuse_fetch(self.h, *[_ptr(arr[k]) for k in names]))
+        return {k: v for k, v in arr.items() if v is not None}
+
+    def crack_fuse_end(self):
+        self._check(self.lib.pcp_crack_fuse_end(self.h))
+
+    def crack_components(self, min_views: int = 1, radius: float = 0.02) -> dict:
+        """The map's cracks from the live accumulation (pcp_crack_components and its fetch): label (n,) int32, the lowest input
+        index of the point's connected component under the link radius, -1 for a point that is no crack point; ids (C,) int32
+        ascending; stats (C, 5) int64: points, sum_w, min_w, max_w, centre_points; box (C, 6) float32: min xyz, max xyz; plus
+        crack_points and components (counts)."""
+        prm = CrackLinkParams(min_views, radius)
+        label = np.empty(self.n, np.int32)
+        pts, comps = C.c_int64(), C.c_int64()
+        self._check(self.lib.pcp_crack_components(self.h, C.byref(prm), _ptr(label), C.byref(pts), C.byref(comps)))
+        rows = comps.value
+        ids = np.empty(rows, np.int32)
+        stats = np.empty((rows, 5), np.int64)
+        box = np.empty((rows, 6), np.float32)
+        got = C.c_int64()
+        self._check(self.lib.pcp_crack_components_fetch(self.h, C.c_int64(0), C.c_int64(rows), _ptr(ids), _ptr(stats), _ptr(box), C.byref(got)))
+        assert got.value == rows, (got.value, rows)
+        return dict(label=label, ids=ids, stats=stats, box=box, crack_points=pts.value, components=rows)
 
     def colour_smooth_local(self, radius: float) -> int:
         """smoothColorsWithLocalRegion (PointCloudProcessor.cpp:634-703) in place on the colour result; returns the number

@@ -517,6 +517,7 @@ static int store_cloud(pcp_context *ctx, const float *x, const float *y, const f
   ctx->labels_live = false;
   match_table_release(ctx);  // PCP_MATCH_RADIUS: the table belongs to the cloud that is being replaced
   normals_release(ctx);      // pcp_estimate_normals: so do the normals
+  crack_fuse_release(ctx);   // pcp_crack_fuse_begin: and the accumulated crack widths
   ctx->mls_count = 0;
   ctx->mls_result_live = false;
   ctx->vgd_next = ctx->css_next = -1;  // the streams of the smoothing stage belong to the cloud that is being replaced
@@ -606,7 +607,7 @@ int pcp_create(int32_t device, pcp_context **out) {
     const hipError_t pl[] = {hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_up_bbox)), preload_colour(), preload_mls(), preload_grid(),
                              preload_nid(), preload_hpr(), preload_colour_smooth(), preload_match(),
                              preload_jpeg(), preload_stream_colour(), preload_ascii(), preload_ascii_parse(), preload_exposure(),
-                             preload_voxel_reduce(), preload_normals(), preload_mask_edt(), preload_crack_width()};
+                             preload_voxel_reduce(), preload_normals(), preload_mask_edt(), preload_crack_width(), preload_crack_fuse()};
     for (hipError_t x : pl)
       if (x != hipSuccess && e == hipSuccess) e = x;
   }
@@ -845,6 +846,7 @@ int pcp_set_camera(pcp_context *ctx, const pcp_camera *cam, const pcp_cull_param
   ctx->hull_valid.clear();
   ctx->depth_accum.release();  // sized by the camera
   ctx->depth_accum_live = false;
+  crack_fuse_release(ctx);  // the accumulated crack widths belong to the camera and the keyframes they were measured with
   ctx->colour_state_live = false;
   ctx->colour_result_live = false;
   ctx->labels_live = false;
@@ -969,6 +971,7 @@ int pcp_set_frames(pcp_context *ctx, const pcp_pose *poses, int32_t n_frames, co
   ctx->hull_valid.clear();
   ctx->depth_accum.release();  // one map per keyframe of the set that is being replaced
   ctx->depth_accum_live = false;
+  crack_fuse_release(ctx);
   ctx->match_live = false;  // PCP_MATCH_RADIUS: E (and with it R_c) depends on the keyframes
   ctx->gains_set = false;   // exposure gains: one per keyframe of the set that is being replaced
   ctx->colour_state_live = false;

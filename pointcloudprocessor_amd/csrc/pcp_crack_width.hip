@@ -224,10 +224,12 @@ hipError_t preload_crack_width() {
 
 static cw::Intrinsics intrinsics_of(const DevCamera &c) { return cw::Intrinsics{c.fx, c.fy, c.cx, c.cy, c.k1, c.k2, c.p1, c.p2, c.k3}; }
 
-// the call's own kernels, after the two stages have left their maps on the device
-static int crack_width_run(pcp_context *ctx, const pcp_crack_params &prm, uint8_t *out_flags, int32_t *out_edges, uint32_t *out_w2d2,
-                           float *out_width, float *out_points, float *out_plane, int64_t *out_moments, int64_t *out_sites,
-                           int64_t *out_widths) {
+// The call's own kernels, after the two stages have left their maps on the device: the device part, for the callers that read
+// the results where they lie (pcp_crack_fuse.hip).  The wanted outputs stay in ctx->cw_flags, cw_i32 (edges | w2d2), cw_f32
+// (plane | width | points) and cw_moments, the two counts in ctx->s_counter[2..3]; nothing is copied, no synchronisation.
+int crack_width_device(pcp_context *ctx, const pcp_crack_params &prm, const CrackWidthWant &want) {
+  const bool out_flags = want.flags, out_edges = want.edges, out_w2d2 = want.w2d2, out_width = want.width, out_points = want.points,
+             out_plane = want.plane, out_moments = want.moments;
   const int32_t w = ctx->dcam.img_w, h = ctx->dcam.img_h;
   const int64_t px = static_cast<int64_t>(w) * h;
   const size_t spx = static_cast<size_t>(px);
@@ -276,19 +278,49 @@ static int crack_width_run(pcp_context *ctx, const pcp_crack_params &prm, uint8_
     hipLaunchKernelGGL(k_cw_sites, dim3(xb, static_cast<uint32_t>(h)), dim3(kCwBlock), 0, ctx->stream, g);
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
+  return PCP_OK;
+}
+
+// ... and with the downloads of pcp_crack_width
+static int crack_width_run(pcp_context *ctx, const pcp_crack_params &prm, uint8_t *out_flags, int32_t *out_edges, uint32_t *out_w2d2,
+                           float *out_width, float *out_points, float *out_plane, int64_t *out_moments, int64_t *out_sites,
+                           int64_t *out_widths) {
+  const CrackWidthWant want{out_flags != nullptr, out_edges != nullptr,  out_w2d2 != nullptr,   out_width != nullptr,
+                            out_points != nullptr, out_plane != nullptr, out_moments != nullptr};
+  const int rc = crack_width_device(ctx, prm, want);
+  if (rc != PCP_OK) return rc;
+  const size_t spx = static_cast<size_t>(ctx->dcam.img_w) * static_cast<size_t>(ctx->dcam.img_h);
+  const unsigned long long *tally = ctx->s_counter.p + 2;
   unsigned long long counts[2] = {0, 0};
   PCP_HIP_TRY(ctx, hipMemcpyAsync(counts, tally, 16, hipMemcpyDeviceToHost, ctx->stream));
-  if (out_flags) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_flags, g.flags, spx, hipMemcpyDeviceToHost, ctx->stream));
-  if (out_edges) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_edges, g.edges, 4 * spx * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (out_w2d2) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_w2d2, g.w2d2, spx * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (out_width) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_width, g.width, spx * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (out_points) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_points, g.points, 6 * spx * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (out_plane) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_plane, g.plane, 4 * spx * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_flags) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_flags, ctx->cw_flags.p, spx, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_edges) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_edges, ctx->cw_i32.p, 4 * spx * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_w2d2) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_w2d2, ctx->cw_i32.p + 4 * spx, spx * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_width) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_width, ctx->cw_f32.p + 4 * spx, spx * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_points) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_points, ctx->cw_f32.p + 5 * spx, 6 * spx * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_plane) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_plane, ctx->cw_f32.p, 4 * spx * 4, hipMemcpyDeviceToHost, ctx->stream));
   if (out_moments)
-    PCP_HIP_TRY(ctx, hipMemcpyAsync(out_moments, g.moments, static_cast<size_t>(cw::kMomentWords) * spx * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PCP_HIP_TRY(ctx, hipMemcpyAsync(out_moments, ctx->cw_moments.p, static_cast<size_t>(cw::kMomentWords) * spx * 8, hipMemcpyDeviceToHost, ctx->stream));
   PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (out_sites) *out_sites = static_cast<int64_t>(counts[0]);
   if (out_widths) *out_widths = static_cast<int64_t>(counts[1]);
+  return PCP_OK;
+}
+
+// the checks of the arguments pcp_crack_width and pcp_crack_fuse_add share, under the caller's name
+int crack_width_check(pcp_context *ctx, const char *who, const pcp_crack_params *params) {
+  if (!params) return set_error(ctx, PCP_ERR_INVALID, "%s: params is NULL", who);
+  if (params->threshold < 0 || params->threshold > 255)
+    return set_error(ctx, PCP_ERR_INVALID, "%s: threshold %d outside 0..255", who, params->threshold);
+  if (!cw::radius_ok(params->plane_radius_px))
+    return set_error(ctx, PCP_ERR_INVALID, "%s: plane_radius_px %d outside %d..%d", who, params->plane_radius_px, cw::kMinRadius,
+                     cw::kMaxRadius);
+  if (ctx->have_camera) {
+    const int64_t w = ctx->dcam.img_w, h = ctx->dcam.img_h;
+    if (w > cw::kMaxSide || h > cw::kMaxSide || w * h > cw::kMaxPixels)
+      return set_error(ctx, PCP_ERR_RANGE, "%s: image %d x %d exceeds %d a side or 2^26 pixels", who, static_cast<int>(w),
+                       static_cast<int>(h), cw::kMaxSide);
+  }
   return PCP_OK;
 }
 
@@ -304,21 +336,10 @@ int pcp_crack_width(pcp_context *ctx, int32_t frame, const pcp_crack_params *par
   if (!ctx) return PCP_ERR_INVALID;
   if (out_sites) *out_sites = 0;
   if (out_widths) *out_widths = 0;
-  if (!params) return set_error(ctx, PCP_ERR_INVALID, "pcp_crack_width: params is NULL");
-  if (params->threshold < 0 || params->threshold > 255)
-    return set_error(ctx, PCP_ERR_INVALID, "pcp_crack_width: threshold %d outside 0..255", params->threshold);
-  if (!cw::radius_ok(params->plane_radius_px))
-    return set_error(ctx, PCP_ERR_INVALID, "pcp_crack_width: plane_radius_px %d outside %d..%d", params->plane_radius_px, cw::kMinRadius,
-                     cw::kMaxRadius);
-  if (ctx->have_camera) {
-    const int64_t w = ctx->dcam.img_w, h = ctx->dcam.img_h;
-    if (w > cw::kMaxSide || h > cw::kMaxSide || w * h > cw::kMaxPixels)
-      return set_error(ctx, PCP_ERR_RANGE, "pcp_crack_width: image %d x %d exceeds %d a side or 2^26 pixels", static_cast<int>(w),
-                       static_cast<int>(h), cw::kMaxSide);
-  }
-  // the geometry scatter first (camera, cloud, keyframes, the keyframe's range), then the distance transform (the mask)
-  int rc = frame_geometry_device(ctx, "pcp_crack_width", frame, /*with_normals=*/false);
+  int rc = crack_width_check(ctx, "pcp_crack_width", params);
   if (rc != PCP_OK) return rc;
+  // the geometry scatter first (camera, cloud, keyframes, the keyframe's range), then the distance transform (the mask)
+  if ((rc = frame_geometry_device(ctx, "pcp_crack_width", frame, /*with_normals=*/false)) != PCP_OK) return rc;
   if (ctx->dcam.img_w <= 0 || ctx->dcam.img_h <= 0) return PCP_OK;
   if ((rc = mask_edt_device(ctx, "pcp_crack_width", frame, params->threshold)) != PCP_OK) return rc;
   return crack_width_run(ctx, *params, out_flags, out_edges, out_w2d2, out_width, out_points, out_plane, out_moments, out_sites, out_widths);

@@ -326,6 +326,20 @@ struct pcp_context {
   pcp::DevBuf<float> cw_f32;       // plane (4 per pixel) | width | points (6 per pixel)
   pcp::DevBuf<long long> cw_moments;  // 13 per pixel
 
+  // crack widths on the map (pcp_crack_fuse.hip): the accumulation between pcp_crack_fuse_begin and _end, SoA planes of n in
+  // input order -- seen | views | centres | min_q | max_q | best_q and sum_q | best_key -- with the keyframes added so far;
+  // dropped by the uploads, pcp_set_camera and pcp_set_frames.  The table of the last pcp_crack_components (ids, 5 integers
+  // and the box as ordered integers per crack) lives until the accumulation changes or ends.
+  bool cf_live = false;
+  pcp::DevBuf<uint32_t> cf_u32;
+  pcp::DevBuf<unsigned long long> cf_u64;
+  std::vector<uint8_t> cf_added;
+  bool cc_live = false;
+  int64_t cc_rows = 0;
+  pcp::DevBuf<int32_t> cc_ids;
+  pcp::DevBuf<unsigned long long> cc_stats;
+  pcp::DevBuf<uint32_t> cc_box;
+
   // PCP_MATCH_RADIUS (pcp_match.hip): the neighbour table within R_c, built by the first colour pass in that mode and
   // dropped by pcp_upload_cloud / pcp_set_frames (E depends on both).  Set A = points whose row holds another point.
   bool match_live = false;
@@ -594,10 +608,19 @@ hipError_t preload_voxel_reduce();
 hipError_t preload_normals();
 hipError_t preload_mask_edt();
 hipError_t preload_crack_width();
+hipError_t preload_crack_fuse();
 // the device parts of pcp_mask_edt (one keyframe, with nearest) and pcp_frame_geometry under the caller's name: checks and
 // kernels, the results left in md_bits / md_d2 / md_nearest and gm_out / s_counter[0]; no copy, no synchronisation
 int mask_edt_device(pcp_context *ctx, const char *who, int32_t frame, int32_t threshold);
-int frame_geometry_device(pcp_context *ctx, const char *who, int32_t frame, bool with_normals);
+// (*out_contributors, nullable: the length of the keyframe's list, which frame_contributors left in ctx->s_cell)
+int frame_geometry_device(pcp_context *ctx, const char *who, int32_t frame, bool with_normals, int64_t *out_contributors = nullptr);
+// the device part of pcp_crack_width after those two (pcp_crack_width.hip), and the checks of its arguments
+struct CrackWidthWant {
+  bool flags, edges, w2d2, width, points, plane, moments;
+};
+int crack_width_check(pcp_context *ctx, const char *who, const pcp_crack_params *params);
+int crack_width_device(pcp_context *ctx, const pcp_crack_params &prm, const CrackWidthWant &want);
+void crack_fuse_release(pcp_context *ctx);  // the accumulation of the crack widths (the uploads, pcp_set_camera, pcp_set_frames)
 void normals_release(pcp_context *ctx);   // the normals of the cloud that is being replaced (the uploads)
 // the list pcp_frame_visible reports for one keyframe (pcp_colour.hip): ascending input indices in ctx->s_cell, *m of them;
 // checks the context and the keyframe as that call does, under the caller's name

@@ -295,10 +295,11 @@ static int estimate_normals(pcp_context *ctx, float radius, int64_t *out_valid, 
 // of frame_contributors under the caller's name, then the three kernels.  The images stay in ctx->gm_out (index | range |
 // xyz_cam | normal_cam), the occupied count in ctx->s_counter[0]; nothing is copied and the stream is not synchronised.
 // with_normals needs a live estimate (the caller's to check).
-int frame_geometry_device(pcp_context *ctx, const char *who, int32_t frame, bool with_normals) {
+int frame_geometry_device(pcp_context *ctx, const char *who, int32_t frame, bool with_normals, int64_t *out_contributors) {
   int64_t m = 0;
   int rc = frame_contributors(ctx, who, frame, &m);  // GM1: the list of pcp_frame_visible, in ctx->s_cell
   if (rc != PCP_OK) return rc;
+  if (out_contributors) *out_contributors = m;
   const int64_t px = static_cast<int64_t>(ctx->dcam.img_w) * ctx->dcam.img_h;
   if (px <= 0) return PCP_OK;
   const size_t spx = static_cast<size_t>(px);

@@ -126,6 +126,19 @@
 //     uploads and the raw map (pcp_crack_width; DESIGN.md "Crack width maps"), with the poses the colourisation uses.  The
 //     counts of sites and widths are printed per keyframe.  No other output changes.  --gpus N above 1 and --enableMLS 1 are
 //     refused for the reasons --geometryMaps gives.
+//   * --crackFuse 0|1 (new, default 0; needs --mask_image_folder), --crackLinkRadius r (new, default 0.02, 0.005..1) and
+//     --crackMinViews v (new, default 1, 1..4096; --crackThreshold and --crackPlaneRadius are reused): with 1, after the
+//     colour stage, the widths of every selected keyframe whose mask was read are brought back to the map points that see them
+//     and the run writes <outputPath>crack_width/map_width.npy (<f4, (n): the mean width in metres over the keyframes that
+//     credit the point, 0 without one), map_width_best.npy (<f4, (n): the width from the nearest such keyframe), map_views.npy
+//     (<u4, (n): their number), map_crack.npy (<i4, (n): the id of the point's crack, -1 for a point outside every crack) and
+//     cracks_3d.json: one record per crack -- the connected components, under the link radius, of the points with v credited
+//     keyframes or more -- with id, points, centre_points, width_mean_mm / width_min_mm / width_max_mm and box_min / box_max.
+//     n is the map's point count, input order.  This is what the per-point records of compute_skeleton_edge_pts (:396-478) and
+//     the result file crack_width_3d_results.json (:476-478) hold for hand-picked pixels, for the whole map and with the
+//     cracks told apart.  Made on the GPU (pcp_crack_fuse_*, pcp_crack_components; DESIGN.md "Crack widths on the map").
+//     With --crackWidth 1 as well a keyframe's width stage runs twice.  No other output changes.  --gpus N above 1 and
+//     --enableMLS 1 are refused for the reasons --geometryMaps gives.
 #include <cfloat>
 #include <chrono>
 #include <cmath>
@@ -216,6 +229,9 @@ struct Options {
   int crack_threshold = 0;            // --crackThreshold t: a mask byte above t is foreground
   bool crack_width = false;           // --crackWidth 1: per-keyframe crack width maps (crack_width/*.npy)
   int crack_plane_radius = 150;       // --crackPlaneRadius R: half side of the plane's window, pixels
+  bool crack_fuse = false;            // --crackFuse 1: the widths on the map and the map's cracks (crack_width/map_*.npy, cracks_3d.json)
+  float crack_link_radius = 0.02f;    // --crackLinkRadius r: crack points this close belong to one crack
+  int crack_min_views = 1;            // --crackMinViews v: credited keyframes a crack point needs
 };
 
 static bool parse_bool(const std::string &v) {  // boost::program_options bool semantics
@@ -337,6 +353,23 @@ static Options parse(int argc, char **argv) {
         throw std::runtime_error("the argument ('" + v + "') for option '--crackPlaneRadius' is invalid (1..181)");
       o.crack_plane_radius = static_cast<int>(r);
     }
+    else if (a == "--crackFuse") o.crack_fuse = parse_bool(next());
+    else if (a == "--crackLinkRadius") {
+      const std::string v = next();
+      char *end = nullptr;
+      const float r = std::strtof(v.c_str(), &end);
+      if (end == v.c_str() || *end != '\0' || !(r >= 0.005f && r <= 1.0f))
+        throw std::runtime_error("the argument ('" + v + "') for option '--crackLinkRadius' is invalid (0.005 <= r <= 1)");
+      o.crack_link_radius = r;
+    }
+    else if (a == "--crackMinViews") {
+      const std::string v = next();
+      char *end = nullptr;
+      const long m = std::strtol(v.c_str(), &end, 10);
+      if (end == v.c_str() || *end != '\0' || m < 1 || m > 4096)
+        throw std::runtime_error("the argument ('" + v + "') for option '--crackMinViews' is invalid (1..4096)");
+      o.crack_min_views = static_cast<int>(m);
+    }
     else if (a == "--streamColour") {
       const std::string v = next();
       if (v != "0" && v != "1")
@@ -394,6 +427,14 @@ static Options parse(int argc, char **argv) {
   if (o.crack_width && o.enableMLS)
     throw std::runtime_error("the option '--crackWidth 1' does not work with '--enableMLS 1' (the planes are fitted to the raw "
                              "map; maps of the smoothed cloud are not built)");
+  if (o.crack_fuse && o.maskImageFolder.empty())
+    throw std::runtime_error("the option '--crackFuse 1' needs the masks (--mask_image_folder)");
+  if (o.crack_fuse && o.gpus > 1)
+    throw std::runtime_error("the option '--crackFuse 1' does not work with '--gpus N' above 1 (an index shard sees only its own "
+                             "points: the per-pixel keys of the shards would have to be merged across GPUs, which is not built)");
+  if (o.crack_fuse && o.enableMLS)
+    throw std::runtime_error("the option '--crackFuse 1' does not work with '--enableMLS 1' (the planes are fitted to the raw "
+                             "map; maps of the smoothed cloud are not built)");
   if (o.geometry_maps && o.enableMLS)
     throw std::runtime_error("the option '--geometryMaps 1' does not work with '--enableMLS 1' (the maps are rendered from the raw "
                              "map; maps of the smoothed cloud are not built)");
@@ -447,7 +488,10 @@ static void usage(std::ostream &os) {
         "  --crackMaps arg (=0)                  Also write the masks' squared distance and nearest-edge images as .npy (-m, --gpus 1)\n"
         "  --crackThreshold arg (=0)             With --crackMaps / --crackWidth: a mask byte above this is foreground (0..255)\n"
         "  --crackWidth arg (=0)                 Also write width / edges / flags / points images per keyframe as .npy (-m, --gpus 1)\n"
-        "  --crackPlaneRadius arg (=150)         With --crackWidth: half side of the plane's window in pixels (1..181)\n";
+        "  --crackPlaneRadius arg (=150)         With --crackWidth / --crackFuse: half side of the plane's window in pixels (1..181)\n"
+        "  --crackFuse arg (=0)                  Also write the fused widths per map point and the map's cracks (-m, --gpus 1)\n"
+        "  --crackLinkRadius arg (=0.02)         With --crackFuse: crack points this close (m) belong to one crack (0.005..1)\n"
+        "  --crackMinViews arg (=1)              With --crackFuse: keyframes with a width that a crack point needs (1..4096)\n";
 }
 
 class Processor {
@@ -1175,6 +1219,56 @@ class Processor {
     }
   }
 
+  // --crackFuse 1: the per-point records of compute_skeleton_edge_pts (scripts/genNormAndDistanceMask.py :396-478) and its
+  // result file (:476-478) for the whole map: the widths of every keyframe brought back to the map points, and the cracks
+  void writeCrackFuse() {
+    Device &dev = gpu->device(0);
+    const fs::path dir(opt.outputPath + "crack_width/");
+    fs::create_directories(dir);  // (--crackWidth 1 has made and filled it)
+    std::vector<int> added;
+    for (size_t k = 0; k < keyframes.size(); ++k) {
+      if (mask_missing[k])
+        std::cout << "Failed to read image from: " << keyframes[k].maskImagePath << std::endl;
+      else
+        added.push_back(static_cast<int>(k));
+    }
+    CrackMap m;
+    {
+      Phase ph("crack_fuse_gpu_s");
+      m = ViewCulling(dev).crackMap(added, static_cast<int64_t>(cloud.size()), opt.crack_threshold, opt.crack_plane_radius,
+                                    opt.crack_min_views, opt.crack_link_radius);
+    }
+    Phase ph_w("crack_fuse_write_s");
+    const size_t n = cloud.size();
+    const std::string stem = opt.outputPath + "crack_width/";
+    writeNpy(stem + "map_width.npy", "<f4", {n}, m.width_mean.data(), n * 4);
+    writeNpy(stem + "map_width_best.npy", "<f4", {n}, m.width_best.data(), n * 4);
+    writeNpy(stem + "map_views.npy", "<u4", {n}, m.views.data(), n * 4);
+    writeNpy(stem + "map_crack.npy", "<i4", {n}, m.label.data(), n * 4);
+    std::ofstream f(stem + "cracks_3d.json");
+    auto num = [](double v) {
+      char b[64];
+      std::snprintf(b, sizeof(b), "%.9g", v);
+      return std::string(b);
+    };
+    const double mm = 1000.0 / 1048576.0;  // quanta of 2^-20 m to millimetres
+    f << "[";
+    for (size_t r = 0; r < m.ids.size(); ++r) {
+      const int64_t *st = m.stats.data() + 5 * r;
+      const float *bx = m.box.data() + 6 * r;
+      f << (r ? ",\n " : "\n ") << "{\"id\": " << m.ids[r] << ", \"points\": " << st[0] << ", \"centre_points\": " << st[4]
+        << ", \"width_mean_mm\": " << num(static_cast<double>(st[1]) / static_cast<double>(st[0]) * mm)
+        << ", \"width_min_mm\": " << num(static_cast<double>(st[2]) * mm) << ", \"width_max_mm\": " << num(static_cast<double>(st[3]) * mm)
+        << ", \"box_min\": [" << num(bx[0]) << ", " << num(bx[1]) << ", " << num(bx[2]) << "], \"box_max\": [" << num(bx[3]) << ", "
+        << num(bx[4]) << ", " << num(bx[5]) << "]}";
+    }
+    f << "\n]\n";
+    f.close();
+    if (!f) throw std::runtime_error("Couldn't save the cracks of the map.");
+    std::cout << "Crack widths on the map saved to: " << stem << "map_*.npy and cracks_3d.json, " << added.size() << " keyframes, " << m.credited
+              << " credited samples, " << m.crack_points << " crack points, " << m.ids.size() << " cracks" << std::endl;
+  }
+
   // --balanceExposure 1: the staged colour stage with the exposure gains between the colour pass and the finalise, and the
   // gains on record next to the outputs
   // (fetch = false, --skip_full_cloud 1: the result stays on the device)
@@ -1254,6 +1348,7 @@ class Processor {
         dev.check(pcp_colour_smooth_local(dev.get(), opt.smooth_colors_radius, &coloured));
       }
       reduceToVoxels();
+      if (opt.crack_fuse) writeCrackFuse();
       return;
     }
     {
@@ -1268,6 +1363,7 @@ class Processor {
       gpu->smoothColorsWithLocalRegion(opt.smooth_colors_radius, rgb, has);
     }
     if (opt.output_leaf > 0.0f) reduceToVoxels();  // (of the colour result as it lies on the device now)
+    if (opt.crack_fuse) writeCrackFuse();           // (it reads the raw map and the masks; the colour result stays as it is)
     std::vector<uint8_t> label;
     if (opt.fuse_masks) {
       Phase ph("labels_gpu_s");

@@ -62,6 +62,19 @@ struct CrackWidth {
   std::vector<float> plane;        // 4 per pixel: unit normal facing the camera and -n.c (asked for), else empty
 };
 
+// The crack widths of a set of keyframes on the map, and the map's cracks (pcp_hip.h, "crack widths on the map"): per map
+// point in input order, and one row per crack, ascending by id
+struct CrackMap {
+  int64_t contributors = 0, credited = 0;  // summed over the added keyframes
+  int64_t crack_points = 0;
+  std::vector<float> width_mean, width_best;  // metres; 0 without a credited keyframe
+  std::vector<uint32_t> views;
+  std::vector<int32_t> label;      // the crack's id (the lowest input index of its points), -1: no crack point
+  std::vector<int32_t> ids;
+  std::vector<int64_t> stats;      // 5 per crack: points, sum_w, min_w, max_w (quanta of 2^-20 m), centre_points
+  std::vector<float> box;          // 6 per crack: min x y z, max x y z
+};
+
 class Device {
  public:
   explicit Device(int ordinal = 0) {
@@ -265,6 +278,42 @@ class ViewCulling {
     dev_.check(pcp_crack_width(dev_.get(), keyframe, &prm, c.flags.data(), c.edges.data(), nullptr, c.width_m.data(), c.points.data(),
                                with_plane ? c.plane.data() : nullptr, nullptr, &c.sites, &c.widths));
     return c;
+  }
+  // crackWidth's widths of the given keyframes brought back to the `points` map points that see them, and the connected
+  // components of the points with min_views credited keyframes or more under the link radius: what the script's result file
+  // (scripts/genNormAndDistanceMask.py:476-478) lists per hand-picked pixel, for the whole map and with the cracks told apart
+  CrackMap crackMap(const std::vector<int> &keyframes, int64_t points, int threshold = 0, int plane_radius = 150, int min_views = 1,
+                    float link_radius = 0.02f) const {
+    CrackMap m;
+    dev_.check(pcp_crack_fuse_begin(dev_.get()));
+    try {
+      const pcp_crack_params prm{threshold, plane_radius};
+      for (int k : keyframes) {
+        int64_t listed = 0, credited = 0;
+        dev_.check(pcp_crack_fuse_add(dev_.get(), k, &prm, &listed, &credited));
+        m.contributors += listed;
+        m.credited += credited;
+      }
+      const size_t n = static_cast<size_t>(points);
+      m.width_mean.resize(n);
+      m.width_best.resize(n);
+      m.views.resize(n);
+      m.label.resize(n);
+      dev_.check(pcp_crack_fuse_fetch(dev_.get(), m.width_mean.data(), m.width_best.data(), nullptr, m.views.data(), nullptr, nullptr,
+                                      nullptr, nullptr, nullptr));
+      const pcp_crack_link_params link{min_views, link_radius};
+      int64_t rows = 0, got = 0;
+      dev_.check(pcp_crack_components(dev_.get(), &link, m.label.data(), &m.crack_points, &rows));
+      m.ids.resize(static_cast<size_t>(rows));
+      m.stats.resize(5 * static_cast<size_t>(rows));
+      m.box.resize(6 * static_cast<size_t>(rows));
+      dev_.check(pcp_crack_components_fetch(dev_.get(), 0, rows, m.ids.data(), m.stats.data(), m.box.data(), &got));
+    } catch (...) {
+      (void)pcp_crack_fuse_end(dev_.get());
+      throw;
+    }
+    dev_.check(pcp_crack_fuse_end(dev_.get()));
+    return m;
   }
 
  private:
