@@ -67,7 +67,9 @@ extern "C" {
                                 entry points added, no layout changed: pcp_crack_width, pcp_crack_width_host (crack width maps;
                                 nothing runs unless called);
                                 entry points added, no layout changed: pcp_crack_fuse_begin / _add / _fetch / _end / _host,
-                                pcp_crack_components / _fetch / _host (crack widths on the map; nothing runs unless called) */
+                                pcp_crack_components / _fetch / _host (crack widths on the map; nothing runs unless called);
+                                entry points added, no layout changed: pcp_crack_lengths / _fetch / _host, pcp_crack_paths_fetch
+                                (crack lengths on the map; nothing runs unless called) */
 
 #define PCP_OK 0
 #define PCP_ERR_INVALID (-1) /* bad argument */
@@ -940,6 +942,40 @@ int pcp_crack_components_fetch(pcp_context *ctx, int64_t first, int64_t max_rows
                                int64_t *out_rows);
 int pcp_crack_components_host(int64_t n, const float *xyz, const uint32_t *views, int32_t min_views, float radius, int32_t *out_label,
                               int64_t *out_components);
+
+/* ---- crack lengths on the map (scripts/genNormAndDistanceMask.py orders a crack only by a 2-D skeleton per keyframe) ---------- */
+/* The length of every crack of the map, its two end points, an ordered 3-D polyline through it and every crack point's arc
+ * position ("Crack lengths on the map", CL1-CL9).  Opt-in: nothing runs unless one of these is called,
+ * PCP_ABI_VERSION is unchanged and a caller detects support by the symbols.  Kernels are timed under PCP_K_MISC.  Whole-map
+ * contexts only.
+ *
+ * pcp_crack_lengths reads the live accumulation under the crack points and links of pcp_crack_components for the same
+ * parameters (same checks and returns; without a live accumulation PCP_ERR_STATE).  A link of squared distance d2 (the fp32
+ * value the link rule compares) weighs w = max(1, isqrt(trunc((double)d2 * 2^40))) units of 2^-20 m; D_s(i) is the least sum
+ * of weights from s to i.  Per crack: s0 = its id (the lowest input index), a = the lowest index among the maxima of D_s0,
+ * b = the lowest index among the maxima of D_a, length_q = D_a(b) (the double sweep: exact on trees, a lower bound of the
+ * diameter otherwise); the path runs from a to b, each point's predecessor the lowest index j linked to it with
+ * D_a(j) + w = D_a(i).  out_pos (nullable, n, host) = D_a(i) for a crack point, 2^64 - 1 for every other point.
+ * *out_cracks / *out_path_points (nullable) = rows of the table / entries of all paths.  The call runs the component stage
+ * for its parameters: afterwards pcp_crack_components_fetch serves the table of these parameters, and the call invalidates
+ * what pcp_crack_components invalidates.  PCP_ERR_DEVICE if a sweep does not settle within as many rounds as there are crack
+ * points plus one (it cannot).
+ * pcp_crack_lengths_fetch: rows first .. first + max_rows - 1 of that call's table, the rows and order of
+ * pcp_crack_components_fetch: out_id, out_rows7 7 int64 per row -- end_a, end_b (input indices), length_q, hops,
+ * path_sum_w, path_min_w, path_max_w over the fused w of the path's points -- and out_offsets (max_rows + 1 capacity; rows + 1
+ * written): entry k = the first entry of row first + k in the path array, the last one the end of the last row fetched.
+ * pcp_crack_paths_fetch: entries first_entry .. of the path array (input indices, a to b, hops + 1 per crack).  All outputs
+ * nullable.  Table and paths live until the next _add, _end or drop of the accumulation.
+ * pcp_crack_lengths_host: host only, no context, no GPU: the same results for n <= 65536 points (xyz interleaved) by brute
+ * force over the pairs and a binary-heap Dijkstra; sum_q (nullable: every w = 0) and views give the fused w.  out_pos n,
+ * out_id n, out_rows7 7 n, out_offsets n + 1, out_path n entries of capacity (all nullable). */
+int pcp_crack_lengths(pcp_context *ctx, const pcp_crack_link_params *p, uint64_t *out_pos, int64_t *out_cracks, int64_t *out_path_points);
+int pcp_crack_lengths_fetch(pcp_context *ctx, int64_t first, int64_t max_rows, int32_t *out_id, int64_t *out_rows7, int64_t *out_offsets,
+                            int64_t *out_rows);
+int pcp_crack_paths_fetch(pcp_context *ctx, int64_t first_entry, int64_t max_entries, int32_t *out_index, int64_t *out_entries);
+int pcp_crack_lengths_host(int64_t n, const float *xyz, const uint32_t *views, int32_t min_views, float radius, const uint64_t *sum_q,
+                           uint64_t *out_pos, int32_t *out_id, int64_t *out_rows7, int64_t *out_offsets, int32_t *out_path,
+                           int64_t *out_cracks, int64_t *out_path_points);
 
 /* ---- precondition of the match-back(PointCloudProcessor.cpp:480-482,571) ------------------------------- */
 /* Number of map points that have ANOTHER map point closer than `radius` (fp32 squared distance, strict <, as

@@ -422,6 +422,38 @@ def crack_components_host(xyz, views, min_views: int = 1, radius: float = 0.02) 
     return label
 
 
+NO_POS = 0xFFFFFFFFFFFFFFFF  # pos of a point that is no crack point (DESIGN.md "Crack lengths on the map", CL5)
+CL_ROW = ("end_a", "end_b", "length_q", "hops", "path_sum_w", "path_min_w", "path_max_w")  # CL7: the columns of rows
+
+
+def crack_lengths_host(xyz, views, min_views: int = 1, radius: float = 0.02, sum_q=None) -> dict:
+    """What Context.crack_lengths returns, computed on the CPU by brute force over the pairs and a binary-heap Dijkstra
+    (pcp_crack_lengths_host: no context, no GPU): xyz (n, 3) float32, views (n,) uint32, sum_q (n,) uint64 or None (every
+    fused width 0), n <= 65536."""
+    L = load()
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    views = np.ascontiguousarray(views, np.uint32)
+    n = xyz.shape[0]
+    if views.shape != (n,):
+        raise ValueError(f"crack_lengths_host: {n} views expected, got shape {views.shape}")
+    if sum_q is not None:
+        sum_q = np.ascontiguousarray(sum_q, np.uint64)
+        if sum_q.shape != (n,):
+            raise ValueError(f"crack_lengths_host: {n} sums expected, got shape {sum_q.shape}")
+    pos = np.empty(n, np.uint64)
+    ids = np.empty(n, np.int32)
+    rows = np.empty((n, 7), np.int64)
+    offsets = np.zeros(n + 1, np.int64)
+    path = np.empty(n, np.int32)
+    cracks, entries = C.c_int64(), C.c_int64()
+    rc = L.pcp_crack_lengths_host(C.c_int64(n), _ptr(xyz), _ptr(views), C.c_int32(min_views), C.c_float(radius), _ptr(sum_q), _ptr(pos),
+                                  _ptr(ids), _ptr(rows), _ptr(offsets), _ptr(path), C.byref(cracks), C.byref(entries))
+    if rc != PCP_OK:
+        raise PcpError(rc, L.pcp_last_error(None).decode())
+    c, e = cracks.value, entries.value
+    return dict(pos=pos, ids=ids[:c].copy(), rows=rows[:c].copy(), offsets=offsets[:c + 1].copy(), path=path[:e].copy(), cracks=c, path_points=e)
+
+
 def default_camera() -> Camera:
     cam = Camera()
     load().pcp_default_camera(C.byref(cam))
@@ -1025,6 +1057,29 @@ class Context:
         self._check(self.lib.pcp_crack_components_fetch(self.h, C.c_int64(0), C.c_int64(rows), _ptr(ids), _ptr(stats), _ptr(box), C.byref(got)))
         assert got.value == rows, (got.value, rows)
         return dict(label=label, ids=ids, stats=stats, box=box, crack_points=pts.value, components=rows)
+
+    # -- crack lengths on the map ("Crack lengths on the map") ----------------
+    def crack_lengths(self, min_views: int = 1, radius: float = 0.02) -> dict:
+        """The length, ends and centreline of every crack of the map from the live accumulation (pcp_crack_lengths and its
+        fetches): pos (n,) uint64, the arc position of a crack point along its crack in units of 2^-20 m, NO_POS for every other
+        point; ids (C,) int32 ascending, the rows of crack_components; rows (C, 7) int64, the columns CL_ROW; offsets (C + 1,)
+        int64 and path (int32 input indices): crack k's polyline from end_a to end_b is path[offsets[k]:offsets[k + 1]]; plus
+        cracks and path_points (counts)."""
+        prm = CrackLinkParams(min_views, radius)
+        pos = np.empty(self.n, np.uint64)
+        cracks, entries = C.c_int64(), C.c_int64()
+        self._check(self.lib.pcp_crack_lengths(self.h, C.byref(prm), _ptr(pos), C.byref(cracks), C.byref(entries)))
+        c, e = cracks.value, entries.value
+        ids = np.empty(c, np.int32)
+        rows = np.empty((c, 7), np.int64)
+        offsets = np.zeros(c + 1, np.int64)
+        path = np.empty(e, np.int32)
+        got = C.c_int64()
+        self._check(self.lib.pcp_crack_lengths_fetch(self.h, C.c_int64(0), C.c_int64(c), _ptr(ids), _ptr(rows), _ptr(offsets), C.byref(got)))
+        assert got.value == c, (got.value, c)
+        self._check(self.lib.pcp_crack_paths_fetch(self.h, C.c_int64(0), C.c_int64(e), _ptr(path), C.byref(got)))
+        assert got.value == e, (got.value, e)
+        return dict(pos=pos, ids=ids, rows=rows, offsets=offsets, path=path, cracks=c, path_points=e)
 
     def colour_smooth_local(self, radius: float) -> int:
         """smoothColorsWithLocalRegion (PointCloudProcessor.cpp:634-703) in place on the colour result; returns the number

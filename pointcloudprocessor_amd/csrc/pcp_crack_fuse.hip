@@ -26,7 +26,6 @@ namespace pcp {
 constexpr int kCfBlock = 256;
 constexpr int kCfU32Planes = 6;  // seen views centres min_q max_q best_q
 constexpr int kCfU64Planes = 2;  // sum_q best_key
-constexpr int kCcStatWords = 5;  // points sum_w min_w max_w centre_points
 
 static inline uint32_t cf_blocks(int64_t n) { return static_cast<uint32_t>(std::max<int64_t>(1, div_up(n, kCfBlock))); }
 
@@ -316,15 +315,8 @@ void crack_fuse_release(pcp_context *ctx) {
   ctx->cc_ids.release();
   ctx->cc_stats.release();
   ctx->cc_box.release();
+  crack_length_release(ctx);
 }
-
-// per-call scratch of pcp_crack_components: released when the call returns
-struct CcScratch {
-  DevBuf<uint8_t> flag;
-  DevBuf<int32_t> list, label, parent, root_of, rank;
-  DevBuf<float> vxyz;
-  DevBuf<uint32_t> box;
-};
 
 // the m > 0 crack points of s.list: view, grid, union, flatten, ranks, table
 static int components_run(pcp_context *ctx, float radius, int64_t m, CcScratch &s, int64_t *out_components) {
@@ -363,6 +355,7 @@ static int components_run(pcp_context *ctx, float radius, int64_t m, CcScratch &
   if (rc != PCP_OK) return rc;
   if (g.reach < 1 || g.reach > 2) return set_error(ctx, PCP_ERR_INVALID, "pcp_crack_components: grid reach %d outside 1..2", g.reach);
   const float *gx = ctx->g_xyz.p, *gy = ctx->g_xyz.p + pm, *gz = ctx->g_xyz.p + 2 * pm;
+  s.grid = g;
   const float t = gn::threshold_of(radius);
   PCP_HIP_TRY(ctx, hipMemsetAsync(s.rank.p, 0, (sm + 8) * 4, ctx->stream));
   {
@@ -395,6 +388,38 @@ static int components_run(pcp_context *ctx, float radius, int64_t m, CcScratch &
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
   *out_components = rows;
+  return PCP_OK;
+}
+
+int crack_link_check(pcp_context *ctx, const char *who, const pcp_crack_link_params *p) {
+  if (!p) return set_error(ctx, PCP_ERR_INVALID, "%s: params is NULL", who);
+  if (!cf::min_views_ok(p->min_views))
+    return set_error(ctx, PCP_ERR_INVALID, "%s: min_views %d outside %d..%d", who, p->min_views, cf::kMinViewsLo, cf::kMinViewsHi);
+  if (!gn::radius_ok(p->radius)) return set_error(ctx, PCP_ERR_INVALID, "%s: radius %g outside [0.005, 1]", who, static_cast<double>(p->radius));
+  if (!ctx->cf_live) return set_error(ctx, PCP_ERR_STATE, "%s: no accumulation (pcp_crack_fuse_begin)", who);
+  return PCP_OK;
+}
+
+int crack_components_run(pcp_context *ctx, const pcp_crack_link_params &p, CcScratch &s, int64_t *out_m, int64_t *out_rows) {
+  const int64_t n = ctx->n;
+  const size_t sn = static_cast<size_t>(n);
+  const size_t plane = (sn + 3) & ~size_t(3);
+  PCP_HIP_TRY(ctx, s.flag.ensure(sn + 16));
+  PCP_HIP_TRY(ctx, s.list.ensure(sn + 4));
+  PCP_HIP_TRY(ctx, s.label.ensure(sn + 4));
+  PCP_HIP_TRY(ctx, hipMemsetAsync(s.label.p, 0xff, sn * 4, ctx->stream));  // CC3: -1 for a point that is no crack point
+  {
+    LaunchTimer lt(ctx, PCP_K_MISC);
+    hipLaunchKernelGGL(k_cc_flag, dim3(cf_blocks(n)), dim3(kCfBlock), 0, ctx->stream, ctx->cf_u32.p + sn, ctx->xyz.p, ctx->xyz.p + plane,
+                       ctx->xyz.p + 2 * plane, n, p.min_views, s.flag.p);
+    PCP_HIP_TRY(ctx, hipGetLastError());
+  }
+  int64_t m = 0, rows = 0;
+  int rc = compact_flags(ctx, s.flag.p, n, s.list.p, n, &m);
+  if (rc != PCP_OK) return rc;
+  if (m > 0 && (rc = components_run(ctx, p.radius, m, s, &rows)) != PCP_OK) return rc;
+  *out_m = m;
+  *out_rows = rows;
   return PCP_OK;
 }
 
@@ -466,6 +491,7 @@ int pcp_crack_fuse_add(pcp_context *ctx, int32_t frame, const pcp_crack_params *
   }
   ctx->cf_added[static_cast<size_t>(frame)] = 1;
   ctx->cc_live = false;  // the table of the last pcp_crack_components describes the state before this keyframe
+  ctx->cl_live = false;  // ... and so do the lengths
   if (out_contributors) *out_contributors = m;
   if (out_credited) *out_credited = static_cast<int64_t>(credited);
   return PCP_OK;
@@ -565,12 +591,8 @@ int pcp_crack_components(pcp_context *ctx, const pcp_crack_link_params *p, int32
   if (!ctx) return PCP_ERR_INVALID;
   if (out_crack_points) *out_crack_points = 0;
   if (out_components) *out_components = 0;
-  if (!p) return set_error(ctx, PCP_ERR_INVALID, "pcp_crack_components: params is NULL");
-  if (!cf::min_views_ok(p->min_views))
-    return set_error(ctx, PCP_ERR_INVALID, "pcp_crack_components: min_views %d outside %d..%d", p->min_views, cf::kMinViewsLo, cf::kMinViewsHi);
-  if (!gn::radius_ok(p->radius))
-    return set_error(ctx, PCP_ERR_INVALID, "pcp_crack_components: radius %g outside [0.005, 1]", static_cast<double>(p->radius));
-  if (!ctx->cf_live) return set_error(ctx, PCP_ERR_STATE, "pcp_crack_components: no accumulation (pcp_crack_fuse_begin)");
+  int rc = crack_link_check(ctx, "pcp_crack_components", p);
+  if (rc != PCP_OK) return rc;
   ctx->cc_live = false;
   ctx->cc_rows = 0;
   const int64_t n = ctx->n;
@@ -580,22 +602,9 @@ int pcp_crack_components(pcp_context *ctx, const pcp_crack_link_params *p, int32
   }
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t sn = static_cast<size_t>(n);
-  const size_t plane = (sn + 3) & ~size_t(3);
   CcScratch s;
-  PCP_HIP_TRY(ctx, s.flag.ensure(sn + 16));
-  PCP_HIP_TRY(ctx, s.list.ensure(sn + 4));
-  PCP_HIP_TRY(ctx, s.label.ensure(sn + 4));
-  PCP_HIP_TRY(ctx, hipMemsetAsync(s.label.p, 0xff, sn * 4, ctx->stream));  // CC3: -1 for a point that is no crack point
-  {
-    LaunchTimer lt(ctx, PCP_K_MISC);
-    hipLaunchKernelGGL(k_cc_flag, dim3(cf_blocks(n)), dim3(kCfBlock), 0, ctx->stream, ctx->cf_u32.p + sn, ctx->xyz.p, ctx->xyz.p + plane,
-                       ctx->xyz.p + 2 * plane, n, p->min_views, s.flag.p);
-    PCP_HIP_TRY(ctx, hipGetLastError());
-  }
   int64_t m = 0, rows = 0;
-  int rc = compact_flags(ctx, s.flag.p, n, s.list.p, n, &m);
-  if (rc != PCP_OK) return rc;
-  if (m > 0 && (rc = components_run(ctx, p->radius, m, s, &rows)) != PCP_OK) return rc;
+  if ((rc = crack_components_run(ctx, *p, s, &m, &rows)) != PCP_OK) return rc;
   if (out_label) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_label, s.label.p, sn * 4, hipMemcpyDeviceToHost, ctx->stream));
   PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (also: the scratch is released on return)
   drop_large_grid_bitmap(ctx);

@@ -339,6 +339,12 @@ struct pcp_context {
   pcp::DevBuf<int32_t> cc_ids;
   pcp::DevBuf<unsigned long long> cc_stats;
   pcp::DevBuf<uint32_t> cc_box;
+  // crack lengths on the map (pcp_crack_length.hip): the table (7 integers per crack), its ids, the path offsets (rows + 1)
+  // and the paths of the last pcp_crack_lengths; they live as long as cc's table does
+  bool cl_live = false;
+  int64_t cl_rows = 0, cl_entries = 0;
+  pcp::DevBuf<int32_t> cl_ids, cl_offsets, cl_path;
+  pcp::DevBuf<long long> cl_table;
 
   // PCP_MATCH_RADIUS (pcp_match.hip): the neighbour table within R_c, built by the first colour pass in that mode and
   // dropped by pcp_upload_cloud / pcp_set_frames (E depends on both).  Set A = points whose row holds another point.
@@ -620,6 +626,25 @@ struct CrackWidthWant {
 };
 int crack_width_check(pcp_context *ctx, const char *who, const pcp_crack_params *params);
 int crack_width_device(pcp_context *ctx, const pcp_crack_params &prm, const CrackWidthWant &want);
+// a row of pcp_crack_components' table (ctx->cc_stats): points sum_w min_w max_w centre_points
+constexpr int kCcStatWords = 5;
+// per-call scratch of the component stage (pcp_crack_fuse.hip), released when the call that owns it returns: the crack points
+// (view index k = input point list[k], ascending), label (n, input order), root_of (view index of k's root), rank (roots
+// before view index k: rank[root_of[k]] is k's row of the table) and the grid the stage left in ctx->g_*
+struct CcScratch {
+  DevBuf<uint8_t> flag;
+  DevBuf<int32_t> list, label, parent, root_of, rank;
+  DevBuf<float> vxyz;
+  DevBuf<uint32_t> box;
+  GridDesc grid;
+};
+// CC1-CC4 on the live accumulation (ctx->n > 0, checked parameters): *m crack points, *rows cracks, the table in ctx->cc_*;
+// queued on ctx->stream and synchronised only as far as the counts need
+int crack_components_run(pcp_context *ctx, const pcp_crack_link_params &p, CcScratch &s, int64_t *m, int64_t *rows);
+// the checks pcp_crack_components makes of its parameters and of the accumulation, under the caller's name
+int crack_link_check(pcp_context *ctx, const char *who, const pcp_crack_link_params *p);
+void crack_length_release(pcp_context *ctx);  // the table and paths of pcp_crack_lengths (with cc's table)
+hipError_t preload_crack_length();
 void crack_fuse_release(pcp_context *ctx);  // the accumulation of the crack widths (the uploads, pcp_set_camera, pcp_set_frames)
 void normals_release(pcp_context *ctx);   // the normals of the cloud that is being replaced (the uploads)
 // the list pcp_frame_visible reports for one keyframe (pcp_colour.hip): ascending input indices in ctx->s_cell, *m of them;

@@ -139,6 +139,15 @@
 //     cracks told apart.  Made on the GPU (pcp_crack_fuse_*, pcp_crack_components; DESIGN.md "Crack widths on the map").
 //     With --crackWidth 1 as well a keyframe's width stage runs twice.  No other output changes.  --gpus N above 1 and
 //     --enableMLS 1 are refused for the reasons --geometryMaps gives.
+//   * --crackLength 0|1 (new, default 0; needs --crackFuse 1 and is refused where that is): with 1 the run also writes
+//     <outputPath>crack_width/map_crack_pos.npy (<u8, (n): the point's arc position along its crack from the crack's end a, in
+//     units of 2^-20 m; 2^64 - 1 for a point outside every crack), crack_paths.npy (<i4: the cracks' centrelines one after the
+//     other, input indices from end a to end b), crack_path_offsets.npy (<i8, (cracks + 1): where each crack's centreline
+//     starts in it) and crack_lengths_3d.json: one record per crack, the cracks and order of cracks_3d.json, with id,
+//     length_m (the geodesic length between the ends over the links of the crack), hops, end_a, end_b, end_a_xyz, end_b_xyz and
+//     path_width_mean_mm / path_width_min_mm / path_width_max_mm over the fused widths of the centreline's points.  The
+//     reference's script orders a crack only by a 2-D skeleton per keyframe.  Made on the GPU (pcp_crack_lengths; DESIGN.md
+//     "Crack lengths on the map").  cracks_3d.json and every other output stay as they are.
 #include <cfloat>
 #include <chrono>
 #include <cmath>
@@ -229,6 +238,7 @@ struct Options {
   int crack_threshold = 0;            // --crackThreshold t: a mask byte above t is foreground
   bool crack_width = false;           // --crackWidth 1: per-keyframe crack width maps (crack_width/*.npy)
   int crack_plane_radius = 150;       // --crackPlaneRadius R: half side of the plane's window, pixels
+  bool crack_length = false;          // --crackLength 1: with --crackFuse, the cracks' lengths, ends and centrelines (crack_width/crack_*)
   bool crack_fuse = false;            // --crackFuse 1: the widths on the map and the map's cracks (crack_width/map_*.npy, cracks_3d.json)
   float crack_link_radius = 0.02f;    // --crackLinkRadius r: crack points this close belong to one crack
   int crack_min_views = 1;            // --crackMinViews v: credited keyframes a crack point needs
@@ -354,6 +364,7 @@ static Options parse(int argc, char **argv) {
       o.crack_plane_radius = static_cast<int>(r);
     }
     else if (a == "--crackFuse") o.crack_fuse = parse_bool(next());
+    else if (a == "--crackLength") o.crack_length = parse_bool(next());
     else if (a == "--crackLinkRadius") {
       const std::string v = next();
       char *end = nullptr;
@@ -427,6 +438,8 @@ static Options parse(int argc, char **argv) {
   if (o.crack_width && o.enableMLS)
     throw std::runtime_error("the option '--crackWidth 1' does not work with '--enableMLS 1' (the planes are fitted to the raw "
                              "map; maps of the smoothed cloud are not built)");
+  if (o.crack_length && !o.crack_fuse)
+    throw std::runtime_error("the option '--crackLength 1' needs the widths on the map (--crackFuse 1)");
   if (o.crack_fuse && o.maskImageFolder.empty())
     throw std::runtime_error("the option '--crackFuse 1' needs the masks (--mask_image_folder)");
   if (o.crack_fuse && o.gpus > 1)
@@ -491,7 +504,8 @@ static void usage(std::ostream &os) {
         "  --crackPlaneRadius arg (=150)         With --crackWidth / --crackFuse: half side of the plane's window in pixels (1..181)\n"
         "  --crackFuse arg (=0)                  Also write the fused widths per map point and the map's cracks (-m, --gpus 1)\n"
         "  --crackLinkRadius arg (=0.02)         With --crackFuse: crack points this close (m) belong to one crack (0.005..1)\n"
-        "  --crackMinViews arg (=1)              With --crackFuse: keyframes with a width that a crack point needs (1..4096)\n";
+        "  --crackMinViews arg (=1)              With --crackFuse: keyframes with a width that a crack point needs (1..4096)\n"
+        "  --crackLength arg (=0)                With --crackFuse: also write every crack's length, ends and centreline\n";
 }
 
 class Processor {
@@ -1233,10 +1247,13 @@ class Processor {
         added.push_back(static_cast<int>(k));
     }
     CrackMap m;
+    CrackLengths cl;
     {
-      Phase ph("crack_fuse_gpu_s");
+      const auto t0 = PhaseClock::clock::now();
       m = ViewCulling(dev).crackMap(added, static_cast<int64_t>(cloud.size()), opt.crack_threshold, opt.crack_plane_radius,
-                                    opt.crack_min_views, opt.crack_link_radius);
+                                    opt.crack_min_views, opt.crack_link_radius, opt.crack_length ? &cl : nullptr);
+      g_clock.add("crack_fuse_gpu_s", PhaseClock::since(t0) - cl.seconds);
+      if (opt.crack_length) g_clock.add("crack_length_gpu_s", cl.seconds);
     }
     Phase ph_w("crack_fuse_write_s");
     const size_t n = cloud.size();
@@ -1267,6 +1284,40 @@ class Processor {
     if (!f) throw std::runtime_error("Couldn't save the cracks of the map.");
     std::cout << "Crack widths on the map saved to: " << stem << "map_*.npy and cracks_3d.json, " << added.size() << " keyframes, " << m.credited
               << " credited samples, " << m.crack_points << " crack points, " << m.ids.size() << " cracks" << std::endl;
+    if (opt.crack_length) writeCrackLengths(cl, stem);
+  }
+
+  // --crackLength 1: every crack's geodesic length, ends and centreline on the map, and every point's arc position
+  void writeCrackLengths(const CrackLengths &c, const std::string &stem) {
+    Phase ph("crack_length_write_s");
+    writeNpy(stem + "map_crack_pos.npy", "<u8", {c.pos.size()}, c.pos.data(), c.pos.size() * 8);
+    writeNpy(stem + "crack_paths.npy", "<i4", {c.path.size()}, c.path.data(), c.path.size() * 4);
+    writeNpy(stem + "crack_path_offsets.npy", "<i8", {c.offsets.size()}, c.offsets.data(), c.offsets.size() * 8);
+    std::ofstream f(stem + "crack_lengths_3d.json");
+    auto num = [](double v) {
+      char b[64];
+      std::snprintf(b, sizeof(b), "%.9g", v);
+      return std::string(b);
+    };
+    const double unit = 1.0 / 1048576.0, mm = 1000.0 / 1048576.0;  // 2^-20 m to metres and to millimetres
+    auto point = [&](int64_t i) {
+      const size_t k = static_cast<size_t>(i);
+      return "[" + num(cloud.x[k]) + ", " + num(cloud.y[k]) + ", " + num(cloud.z[k]) + "]";
+    };
+    f << "[";
+    for (size_t r = 0; r < c.ids.size(); ++r) {
+      const int64_t *row = c.rows.data() + 7 * r;
+      f << (r ? ",\n " : "\n ") << "{\"id\": " << c.ids[r] << ", \"length_m\": " << num(static_cast<double>(row[2]) * unit) << ", \"hops\": " << row[3]
+        << ", \"end_a\": " << row[0] << ", \"end_b\": " << row[1] << ", \"end_a_xyz\": " << point(row[0]) << ", \"end_b_xyz\": " << point(row[1])
+        << ", \"path_width_mean_mm\": " << num(static_cast<double>(row[4]) / static_cast<double>(row[3] + 1) * mm)
+        << ", \"path_width_min_mm\": " << num(static_cast<double>(row[5]) * mm) << ", \"path_width_max_mm\": " << num(static_cast<double>(row[6]) * mm)
+        << "}";
+    }
+    f << "\n]\n";
+    f.close();
+    if (!f) throw std::runtime_error("Couldn't save the crack lengths of the map.");
+    std::cout << "Crack lengths on the map saved to: " << stem << "map_crack_pos.npy, crack_paths.npy, crack_path_offsets.npy and crack_lengths_3d.json, "
+              << c.ids.size() << " cracks, " << c.path.size() << " path points" << std::endl;
   }
 
   // --balanceExposure 1: the staged colour stage with the exposure gains between the colour pass and the finalise, and the

@@ -75,6 +75,17 @@ struct CrackMap {
   std::vector<float> box;          // 6 per crack: min x y z, max x y z
 };
 
+// The lengths of the map's cracks (pcp_hip.h, "crack lengths on the map"): one row per crack, the rows and order of CrackMap,
+// and per map point its arc position along its crack
+struct CrackLengths {
+  std::vector<uint64_t> pos;       // units of 2^-20 m from the crack's end a; 2^64 - 1: no crack point
+  std::vector<int32_t> ids;
+  std::vector<int64_t> rows;       // 7 per crack: end_a, end_b, length_q, hops, path_sum_w, path_min_w, path_max_w
+  std::vector<int64_t> offsets;    // cracks + 1: crack k's polyline is path[offsets[k] .. offsets[k + 1])
+  std::vector<int32_t> path;       // input indices, from end a to end b
+  double seconds = 0.0;            // wall time of the stage (the call and its fetches)
+};
+
 class Device {
  public:
   explicit Device(int ordinal = 0) {
@@ -282,8 +293,9 @@ class ViewCulling {
   // crackWidth's widths of the given keyframes brought back to the `points` map points that see them, and the connected
   // components of the points with min_views credited keyframes or more under the link radius: what the script's result file
   // (scripts/genNormAndDistanceMask.py:476-478) lists per hand-picked pixel, for the whole map and with the cracks told apart
+  // lengths (nullable): also the cracks' lengths, ends and centrelines for the same min_views and link radius
   CrackMap crackMap(const std::vector<int> &keyframes, int64_t points, int threshold = 0, int plane_radius = 150, int min_views = 1,
-                    float link_radius = 0.02f) const {
+                    float link_radius = 0.02f, CrackLengths *lengths = nullptr) const {
     CrackMap m;
     dev_.check(pcp_crack_fuse_begin(dev_.get()));
     try {
@@ -308,12 +320,31 @@ class ViewCulling {
       m.stats.resize(5 * static_cast<size_t>(rows));
       m.box.resize(6 * static_cast<size_t>(rows));
       dev_.check(pcp_crack_components_fetch(dev_.get(), 0, rows, m.ids.data(), m.stats.data(), m.box.data(), &got));
+      if (lengths) *lengths = crackLengths(points, min_views, link_radius);
     } catch (...) {
       (void)pcp_crack_fuse_end(dev_.get());
       throw;
     }
     dev_.check(pcp_crack_fuse_end(dev_.get()));
     return m;
+  }
+  // The geodesic length, the two ends and the ordered polyline of every crack of the live accumulation (between
+  // pcp_crack_fuse_begin and _end; crackMap runs it when asked), and every point's arc position
+  CrackLengths crackLengths(int64_t points, int min_views = 1, float link_radius = 0.02f) const {
+    CrackLengths c;
+    const auto t0 = std::chrono::steady_clock::now();
+    c.pos.resize(static_cast<size_t>(points));
+    const pcp_crack_link_params link{min_views, link_radius};
+    int64_t rows = 0, entries = 0, got = 0;
+    dev_.check(pcp_crack_lengths(dev_.get(), &link, c.pos.data(), &rows, &entries));
+    c.ids.resize(static_cast<size_t>(rows));
+    c.rows.resize(7 * static_cast<size_t>(rows));
+    c.offsets.assign(static_cast<size_t>(rows) + 1, 0);
+    c.path.resize(static_cast<size_t>(entries));
+    dev_.check(pcp_crack_lengths_fetch(dev_.get(), 0, rows, c.ids.data(), c.rows.data(), c.offsets.data(), &got));
+    dev_.check(pcp_crack_paths_fetch(dev_.get(), 0, entries, c.path.data(), &got));
+    c.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return c;
   }
 
  private:

@@ -206,13 +206,18 @@ class PointCloudColorizer:
                              "holding the whole map")
         return self.engine.ctx.crack_width(frame, threshold, plane_radius, want)
 
-    def crack_map(self, frames=None, threshold: int = 0, plane_radius: int = 150, min_views: int = 1, link_radius: float = 0.02) -> dict:
+    def crack_map(self, frames=None, threshold: int = 0, plane_radius: int = 150, min_views: int = 1, link_radius: float = 0.02,
+                  lengths: bool = False) -> dict:
         """The crack widths of the keyframes brought back to the map, and the map's cracks ("Crack widths on the
         map"): begin, one add per keyframe of `frames` (None: all of them), the components, end.  dict of the per-point arrays of
         capi.Context.crack_fuse_fetch (width_mean, width_best, best_frame, views, seen, centres, min_q, max_q, sum_q) and of
         capi.Context.crack_components (label, ids, stats, box, crack_points, components), plus contributors and credited
         (per added keyframe).  This is what compute_skeleton_edge_pts of scripts/genNormAndDistanceMask.py leaves as one
         record per hand-picked pixel, for every map point and with the cracks told apart.
+
+        lengths: the dict gains `lengths`, the dict of capi.Context.crack_lengths for the same min_views and link_radius
+        ("Crack lengths on the map"): per crack a geodesic length, its ends and an ordered polyline, per point
+        its arc position.  Off, the return value is what it was.
 
         An index shard sees only its own points, so world > 1 raises ValueError.  (The shards' key images would have to be
         merged first, as for geometry_maps; not built.)"""
@@ -227,6 +232,8 @@ class PointCloudColorizer:
             counts = [ctx.crack_fuse_add(int(f), threshold, plane_radius) for f in frames]
             out = ctx.crack_fuse_fetch()
             out.update(ctx.crack_components(min_views, link_radius))
+            if lengths:
+                out["lengths"] = ctx.crack_lengths(min_views, link_radius)
             out["contributors"] = [c[0] for c in counts]
             out["credited"] = [c[1] for c in counts]
             return out
