@@ -69,7 +69,9 @@ extern "C" {
                                 entry points added, no layout changed: pcp_crack_fuse_begin / _add / _fetch / _end / _host,
                                 pcp_crack_components / _fetch / _host (crack widths on the map; nothing runs unless called);
                                 entry points added, no layout changed: pcp_crack_lengths / _fetch / _host, pcp_crack_paths_fetch
-                                (crack lengths on the map; nothing runs unless called) */
+                                (crack lengths on the map; nothing runs unless called);
+                                entry points added, no layout changed: pcp_crack_skeleton / _nodes_fetch / _edges_fetch /
+                                _cracks_fetch / _host (crack skeletons on the map; nothing runs unless called) */
 
 #define PCP_OK 0
 #define PCP_ERR_INVALID (-1) /* bad argument */
@@ -976,6 +978,40 @@ int pcp_crack_paths_fetch(pcp_context *ctx, int64_t first_entry, int64_t max_ent
 int pcp_crack_lengths_host(int64_t n, const float *xyz, const uint32_t *views, int32_t min_views, float radius, const uint64_t *sum_q,
                            uint64_t *out_pos, int32_t *out_id, int64_t *out_rows7, int64_t *out_offsets, int32_t *out_path,
                            int64_t *out_cracks, int64_t *out_path_points);
+
+/* ---- crack skeletons on the map (scripts/genNormAndDistanceMask.py preprocess(): pcv.morphology.skeletonize, 2-D, per keyframe) -- */
+/* The level-set diagram of every crack of the map: its branches, junctions and loops ("Crack skeletons on the
+ * map", CS1-CS9).  Opt-in: nothing runs unless one of these is called, PCP_ABI_VERSION is unchanged and a caller detects
+ * support by the symbols.  Kernels are timed under PCP_K_MISC.  Whole-map contexts only.
+ *
+ * pcp_crack_skeleton replaces the per-keyframe 2-D skeleton of the reference's script by one diagram per crack of the map.
+ * It runs pcp_crack_lengths' stage for the parameters (same checks and returns; it leaves the component and length tables of
+ * these parameters behind and invalidates what those calls invalidate), then cuts every crack into bands of its arc
+ * position: step_q = trunc((double)step * 2^20), band(i) = pos[i] / step_q.  step_q must be at least the largest link weight
+ * isqrt(trunc((double)t * 2^40)) of the radius and step at most 16, else PCP_ERR_INVALID; linked points then lie at most one
+ * band apart.  A node is a connected component of the crack points under the links that join two points of one band, its id
+ * the lowest input index among its points; out_node (nullable, n, host) = that id, -1 for a point that is no crack point.
+ * An edge is an unordered pair of nodes with at least one link between their points.  *out_nodes / *out_edges (nullable) =
+ * rows of the two tables.  PCP_ERR_RANGE if a crack point has a coordinate beyond 2^20 m (or the exact coordinate sums of
+ * all crack points could pass 2^62); PCP_ERR_NOMEM if the edge set is still full after 12 doublings.
+ * pcp_crack_skeleton_nodes_fetch: rows first .. of the node table, ascending by id: out_id, out_rows10 10 int64 per row --
+ * crack_row (the row of pcp_crack_components_fetch), band, points, sum_w, min_w, max_w over the members' fused w, sum_qx,
+ * sum_qy, sum_qz (sums of floor((double)x * 2^20) and likewise y, z: the centroid is (sum_q / points) * 2^-20), degree.
+ * pcp_crack_skeleton_edges_fetch: out_rows3 3 int64 per row -- u (the row of the node in the lower band), v (the row of the
+ * other; the bands differ by one), links (linked point pairs between them); unique, ascending by (u, v).
+ * pcp_crack_skeleton_cracks_fetch: the rows and order of pcp_crack_components_fetch, out_rows6 6 int64 per row -- nodes,
+ * edges, ends (degree 1), junctions (degree >= 3), loops = edges - nodes + 1, max_degree.  Replaces what the script's
+ * compute_skeleton_edge_pts leaves to a hand count.  All outputs nullable; the tables live as long as pcp_crack_lengths' do.
+ * pcp_crack_skeleton_host: host only, no context, no GPU: the same results for n <= 65536 points (xyz interleaved) by brute
+ * force over the pairs, a sequential union-find and an ordered map; sum_q (nullable: every w = 0).  out_node n, out_id n,
+ * out_rows10 10 n, out_rows6 6 n of capacity; out_rows3 takes at most edge_capacity rows, *out_edges is the whole count. */
+int pcp_crack_skeleton(pcp_context *ctx, const pcp_crack_link_params *p, float step, int32_t *out_node, int64_t *out_nodes, int64_t *out_edges);
+int pcp_crack_skeleton_nodes_fetch(pcp_context *ctx, int64_t first, int64_t max_rows, int32_t *out_id, int64_t *out_rows10, int64_t *out_rows);
+int pcp_crack_skeleton_edges_fetch(pcp_context *ctx, int64_t first, int64_t max_rows, int64_t *out_rows3, int64_t *out_rows);
+int pcp_crack_skeleton_cracks_fetch(pcp_context *ctx, int64_t first, int64_t max_rows, int64_t *out_rows6, int64_t *out_rows);
+int pcp_crack_skeleton_host(int64_t n, const float *xyz, const uint32_t *views, int32_t min_views, float radius, float step,
+                            const uint64_t *sum_q, int32_t *out_node, int32_t *out_id, int64_t *out_rows10, int64_t edge_capacity,
+                            int64_t *out_rows3, int64_t *out_rows6, int64_t *out_nodes, int64_t *out_edges, int64_t *out_cracks);
 
 /* ---- precondition of the match-back(PointCloudProcessor.cpp:480-482,571) ------------------------------- */
 /* Number of map points that have ANOTHER map point closer than `radius` (fp32 squared distance, strict <, as

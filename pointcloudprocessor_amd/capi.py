@@ -454,6 +454,65 @@ def crack_lengths_host(xyz, views, min_views: int = 1, radius: float = 0.02, sum
     return dict(pos=pos, ids=ids[:c].copy(), rows=rows[:c].copy(), offsets=offsets[:c + 1].copy(), path=path[:e].copy(), cracks=c, path_points=e)
 
 
+CS_NODE = ("crack_row", "band", "points", "sum_w", "min_w", "max_w", "sum_qx", "sum_qy", "sum_qz", "degree")  # CS4: the columns of nodes
+CS_EDGE = ("u", "v", "links")  # CS5
+CS_CRACK = ("nodes", "edges", "ends", "junctions", "loops", "max_degree")  # CS6
+
+
+def crack_skeleton_step(radius: float) -> float:
+    """CS2's default in the host layers: 2 * radius, in fp32"""
+    return float(np.float32(2.0) * np.float32(radius))
+
+
+def crack_skeleton_metres(nodes, edges, cracks) -> dict:
+    """CS7, host arithmetic on the integers of the three tables: centroids (N, 3) fp64 metres = (sum_q / points) * 2^-20 per
+    axis, edge_length_m (E,) = sqrt((dx * dx + dy * dy) + dz * dz) of the two centroids, skeleton_length_m (C,) = the sum of a
+    crack's edge lengths in row order."""
+    nodes, edges = np.asarray(nodes, np.int64).reshape(-1, 10), np.asarray(edges, np.int64).reshape(-1, 3)
+    centroids = (nodes[:, 6:9].astype(np.float64) / nodes[:, 2:3].astype(np.float64)) * 2.0 ** -20
+    d = centroids[edges[:, 1]] - centroids[edges[:, 0]]
+    edge_length = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+    length = np.zeros(len(np.asarray(cracks).reshape(-1, 6)), np.float64)
+    np.add.at(length, nodes[edges[:, 0], 0], edge_length)  # (unbuffered: one addition per edge, in row order)
+    return dict(centroids=centroids, edge_length_m=edge_length, skeleton_length_m=length)
+
+
+def crack_skeleton_host(xyz, views, min_views: int = 1, radius: float = 0.02, step=None, sum_q=None) -> dict:
+    """What Context.crack_skeleton returns, computed on the CPU by brute force over the pairs (pcp_crack_skeleton_host: no
+    context, no GPU): xyz (n, 3) float32, views (n,) uint32, sum_q (n,) uint64 or None (every fused width 0), n <= 65536."""
+    L = load()
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    views = np.ascontiguousarray(views, np.uint32)
+    n = xyz.shape[0]
+    if views.shape != (n,):
+        raise ValueError(f"crack_skeleton_host: {n} views expected, got shape {views.shape}")
+    if sum_q is not None:
+        sum_q = np.ascontiguousarray(sum_q, np.uint64)
+        if sum_q.shape != (n,):
+            raise ValueError(f"crack_skeleton_host: {n} sums expected, got shape {sum_q.shape}")
+    if step is None:
+        step = crack_skeleton_step(radius)
+    node = np.empty(n, np.int32)
+    ids = np.empty(n, np.int32)
+    nodes = np.empty((n, 10), np.int64)
+    cracks = np.empty((n, 6), np.int64)
+    capacity = 4 * n + 16
+    while True:
+        edges = np.empty((capacity, 3), np.int64)
+        kn, ke, kc = C.c_int64(), C.c_int64(), C.c_int64()
+        rc = L.pcp_crack_skeleton_host(C.c_int64(n), _ptr(xyz), _ptr(views), C.c_int32(min_views), C.c_float(radius), C.c_float(step),
+                                       _ptr(sum_q), _ptr(node), _ptr(ids), _ptr(nodes), C.c_int64(capacity), _ptr(edges), _ptr(cracks),
+                                       C.byref(kn), C.byref(ke), C.byref(kc))
+        if rc != PCP_OK:
+            raise PcpError(rc, L.pcp_last_error(None).decode())
+        if ke.value <= capacity:
+            break
+        capacity = ke.value  # (more edges than four per point: once more with room for all)
+    out = dict(node=node, ids=ids[:kn.value].copy(), nodes=nodes[:kn.value].copy(), edges=edges[:ke.value].copy(), cracks=cracks[:kc.value].copy())
+    out.update(crack_skeleton_metres(out["nodes"], out["edges"], out["cracks"]))
+    return out
+
+
 def default_camera() -> Camera:
     cam = Camera()
     load().pcp_default_camera(C.byref(cam))
@@ -1080,6 +1139,34 @@ class Context:
         self._check(self.lib.pcp_crack_paths_fetch(self.h, C.c_int64(0), C.c_int64(e), _ptr(path), C.byref(got)))
         assert got.value == e, (got.value, e)
         return dict(pos=pos, ids=ids, rows=rows, offsets=offsets, path=path, cracks=c, path_points=e)
+
+    # -- crack skeletons on the map ("Crack skeletons on the map") --------------
+    def crack_skeleton(self, min_views: int = 1, radius: float = 0.02, step=None) -> dict:
+        """The level-set diagram of every crack of the map from the live accumulation (pcp_crack_skeleton and its fetches):
+        node (n,) int32, the id of a crack point's node (the lowest input index among its points), -1 for every other point; ids
+        (N,) int32 ascending; nodes (N, 10) int64, the columns CS_NODE; edges (E, 3) int64, the columns CS_EDGE, ascending by
+        (u, v); cracks (C, 6) int64, the columns CS_CRACK, the rows of crack_components; plus centroids (N, 3), edge_length_m
+        (E,) and skeleton_length_m (C,), fp64 metres from the integers.  step: the band width in metres, default 2 * radius."""
+        prm = CrackLinkParams(min_views, radius)
+        if step is None:
+            step = crack_skeleton_step(radius)
+        node = np.empty(self.n, np.int32)
+        kn, ke, got = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(self.lib.pcp_crack_skeleton(self.h, C.byref(prm), C.c_float(step), _ptr(node), C.byref(kn), C.byref(ke)))
+        ids = np.empty(kn.value, np.int32)
+        nodes = np.empty((kn.value, 10), np.int64)
+        edges = np.empty((ke.value, 3), np.int64)
+        self._check(self.lib.pcp_crack_skeleton_nodes_fetch(self.h, C.c_int64(0), C.c_int64(kn.value), _ptr(ids), _ptr(nodes), C.byref(got)))
+        assert got.value == kn.value, (got.value, kn.value)
+        self._check(self.lib.pcp_crack_skeleton_edges_fetch(self.h, C.c_int64(0), C.c_int64(ke.value), _ptr(edges), C.byref(got)))
+        assert got.value == ke.value, (got.value, ke.value)
+        self._check(self.lib.pcp_crack_skeleton_cracks_fetch(self.h, C.c_int64(0), C.c_int64(2 ** 62), None, C.byref(got)))
+        cracks = np.empty((got.value, 6), np.int64)
+        self._check(self.lib.pcp_crack_skeleton_cracks_fetch(self.h, C.c_int64(0), C.c_int64(len(cracks)), _ptr(cracks), C.byref(got)))
+        assert got.value == len(cracks), (got.value, len(cracks))
+        out = dict(node=node, ids=ids, nodes=nodes, edges=edges, cracks=cracks)
+        out.update(crack_skeleton_metres(nodes, edges, cracks))
+        return out
 
     def colour_smooth_local(self, radius: float) -> int:
         """smoothColorsWithLocalRegion (PointCloudProcessor.cpp:634-703) in place on the colour result; returns the number

@@ -99,22 +99,6 @@ __global__ __launch_bounds__(kCfBlock) void k_cc_flag(const uint32_t *__restrict
   flag[i] = cf::crack_point(views[i], min_views, x[i], y[i], z[i]) ? 1 : 0;
 }
 
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = min(v, static_cast<uint32_t>(__shfl_xor(static_cast<int>(v), o, 64)));
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = max(v, static_cast<uint32_t>(__shfl_xor(static_cast<int>(v), o, 64)));
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += static_cast<unsigned long long>(__shfl_xor(static_cast<long long>(v), o, 64));
-  return v;
-}
-
 // the crack points as a view (point k of the view = input point list[k], ascending) and their box as ordered integers:
 // box[0..2] = min, box[3..5] = max, one atomic of each per wavefront
 __global__ __launch_bounds__(kCfBlock) void k_cc_gather(const int32_t *__restrict__ list, int64_t m, const float *__restrict__ x,
@@ -145,39 +129,6 @@ __global__ __launch_bounds__(kCfBlock) void k_cc_gather(const int32_t *__restric
 __global__ __launch_bounds__(kCfBlock) void k_cc_parent_init(int32_t *__restrict__ parent, int64_t m) {
   const int64_t k = static_cast<int64_t>(blockIdx.x) * kCfBlock + threadIdx.x;
   if (k < m) parent[k] = static_cast<int32_t>(k);
-}
-
-// CC5.  parent[v] <= v always and parent words only ever decrease: a root is the lowest index of its tree.  The words are
-// read with relaxed atomic loads at agent scope and written by compare-and-swap only (the L2s of the XCDs are not coherent
-// for plain stores).
-__device__ __forceinline__ int32_t cc_load(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the root of v, halving the path on the way: parent[v]: p -> parent[p] only while it still is p.  v strictly decreases from
-// one round to the next (parent[p] < p < v), so the loop ends after at most v rounds.
-__device__ __forceinline__ int32_t cc_find(int32_t *parent, int32_t v) {
-  for (;;) {
-    const int32_t p = cc_load(parent + v);
-    if (p == v) return v;
-    const int32_t gp = cc_load(parent + p);
-    if (gp == p) return p;
-    atomicCAS(parent + v, p, gp);
-    v = gp;
-  }
-}
-
-// hooks the larger root under the smaller one.  A failed swap means the larger root has been hooked by another lane
-// meanwhile: its root is then below it, so max(a, b) strictly decreases from one round to the next -- at most max(a, b) rounds.
-// No lane ever waits for another one.
-__device__ __forceinline__ void cc_unite(int32_t *parent, int32_t a, int32_t b) {
-  for (;;) {
-    a = cc_find(parent, a);
-    b = cc_find(parent, b);
-    if (a == b) return;
-    const int32_t hi = max(a, b), lo = min(a, b);
-    if (atomicCAS(parent + hi, hi, lo) == hi) return;
-    a = hi;
-    b = lo;
-  }
 }
 
 // CC2: one lane per place s of the cell order; the candidates are the places after s in the rows of the neighbouring cells, so
@@ -349,6 +300,8 @@ static int components_run(pcp_context *ctx, float radius, int64_t m, CcScratch &
   for (int a = 0; a < 3; ++a) {
     cv.mn[a] = cf::value_of(hbox[a]);
     cv.mx[a] = cf::value_of(hbox[3 + a]);
+    s.lo[a] = cv.mn[a];
+    s.hi[a] = cv.mx[a];
   }
   GridDesc g;
   int rc = build_radius_grid(ctx, cv, radius, &g);  // (ends the streams and the pcp_sor_partial that rest on the old grid)

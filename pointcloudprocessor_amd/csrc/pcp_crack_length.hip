@@ -244,14 +244,13 @@ void crack_length_release(pcp_context *ctx) {
   ctx->cl_offsets.release();
   ctx->cl_path.release();
   ctx->cl_table.release();
+  ctx->cs_live = false;  // CS9
+  ctx->cs_node_rows = ctx->cs_crack_rows = 0;
+  ctx->cs_ids.release();
+  ctx->cs_nodes.release();
+  ctx->cs_cracks.release();
+  std::vector<int64_t>().swap(ctx->cs_edges);
 }
-
-// per-call scratch of pcp_crack_lengths beside the component stage's
-struct ClScratch {
-  DevBuf<unsigned long long> dist, far_d, pos;
-  DevBuf<uint32_t> mark, words;  // words[0]: the round in which a distance last fell; words[1]: a walk or an end went wrong
-  DevBuf<int32_t> place_of, row_of, src_place, far_k, end_a, end_b, pred;
-};
 
 // one sweep from src_place: rounds until nothing falls; *round counts on through both sweeps, so that no mark of the first
 // sweep can be mistaken for one of the second
@@ -362,6 +361,20 @@ static int lengths_run(pcp_context *ctx, const CcScratch &cc, ClScratch &s, floa
   return PCP_OK;
 }
 
+int crack_lengths_run(pcp_context *ctx, const pcp_crack_link_params &p, CcScratch &cc, ClScratch &s, bool with_pos, int64_t *m,
+                      int64_t *rows, int64_t *entries) {
+  const size_t sn = static_cast<size_t>(ctx->n);
+  *m = *rows = *entries = 0;
+  int rc = crack_components_run(ctx, p, cc, m, rows);
+  if (rc != PCP_OK) return rc;
+  if (with_pos) {
+    PCP_HIP_TRY(ctx, s.pos.ensure(sn + 4));
+    PCP_HIP_TRY(ctx, hipMemsetAsync(s.pos.p, 0xff, sn * 8, ctx->stream));  // CL5
+  }
+  if (*m > 0) rc = lengths_run(ctx, cc, s, p.radius, *m, *rows, entries);
+  return rc;
+}
+
 }  // namespace pcp
 
 using namespace pcp;
@@ -379,6 +392,7 @@ int pcp_crack_lengths(pcp_context *ctx, const pcp_crack_link_params *p, uint64_t
   ctx->cl_live = false;
   ctx->cl_rows = 0;
   ctx->cl_entries = 0;
+  ctx->cs_live = false;  // CS9: the skeleton's tables live as long as this table
   const int64_t n = ctx->n;
   if (n == 0) {
     ctx->cc_live = ctx->cl_live = true;
@@ -389,12 +403,7 @@ int pcp_crack_lengths(pcp_context *ctx, const pcp_crack_link_params *p, uint64_t
   CcScratch cc;
   ClScratch s;
   int64_t m = 0, rows = 0, entries = 0;
-  if ((rc = crack_components_run(ctx, *p, cc, &m, &rows)) != PCP_OK) return rc;
-  if (out_pos) {
-    PCP_HIP_TRY(ctx, s.pos.ensure(sn + 4));
-    PCP_HIP_TRY(ctx, hipMemsetAsync(s.pos.p, 0xff, sn * 8, ctx->stream));  // CL5
-  }
-  if (m > 0) rc = lengths_run(ctx, cc, s, p->radius, m, rows, &entries);
+  rc = crack_lengths_run(ctx, *p, cc, s, out_pos != nullptr, &m, &rows, &entries);
   if (rc == PCP_OK && out_pos) {
     const hipError_t e = hipMemcpyAsync(out_pos, s.pos.p, sn * 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e != hipSuccess) rc = set_error(ctx, PCP_ERR_DEVICE, "pcp_crack_lengths: the copy of the positions failed: %s", hipGetErrorString(e));

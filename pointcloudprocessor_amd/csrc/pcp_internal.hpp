@@ -345,6 +345,14 @@ struct pcp_context {
   int64_t cl_rows = 0, cl_entries = 0;
   pcp::DevBuf<int32_t> cl_ids, cl_offsets, cl_path;
   pcp::DevBuf<long long> cl_table;
+  // crack skeletons on the map (pcp_crack_skeleton.hip): the node table (10 integers per node) and its ids, the summary (6
+  // integers per crack) and, on the host and ordered, the edges (3 integers each) of the last pcp_crack_skeleton; they live
+  // as long as cl's table does
+  bool cs_live = false;
+  int64_t cs_node_rows = 0, cs_crack_rows = 0;
+  pcp::DevBuf<int32_t> cs_ids;
+  pcp::DevBuf<unsigned long long> cs_nodes, cs_cracks;
+  std::vector<int64_t> cs_edges;
 
   // PCP_MATCH_RADIUS (pcp_match.hip): the neighbour table within R_c, built by the first colour pass in that mode and
   // dropped by pcp_upload_cloud / pcp_set_frames (E depends on both).  Set A = points whose row holds another point.
@@ -637,14 +645,78 @@ struct CcScratch {
   DevBuf<float> vxyz;
   DevBuf<uint32_t> box;
   GridDesc grid;
+  float lo[3], hi[3];  // the box of the crack points as the grid took it (m > 0)
 };
+// CC5.  parent[v] <= v always and parent words only ever decrease: a root is the lowest index of its tree.  The words are
+// read with relaxed atomic loads at agent scope and written by compare-and-swap only (the L2s of the XCDs are not coherent
+// for plain stores).
+__device__ __forceinline__ int32_t cc_load(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// the root of v, halving the path on the way: parent[v]: p -> parent[p] only while it still is p.  v strictly decreases from
+// one round to the next (parent[p] < p < v), so the loop ends after at most v rounds.
+__device__ __forceinline__ int32_t cc_find(int32_t *parent, int32_t v) {
+  for (;;) {
+    const int32_t p = cc_load(parent + v);
+    if (p == v) return v;
+    const int32_t gp = cc_load(parent + p);
+    if (gp == p) return p;
+    atomicCAS(parent + v, p, gp);
+    v = gp;
+  }
+}
+
+// hooks the larger root under the smaller one.  A failed swap means the larger root has been hooked by another lane
+// meanwhile: its root is then below it, so max(a, b) strictly decreases from one round to the next -- at most max(a, b) rounds.
+// No lane ever waits for another one.
+__device__ __forceinline__ void cc_unite(int32_t *parent, int32_t a, int32_t b) {
+  for (;;) {
+    a = cc_find(parent, a);
+    b = cc_find(parent, b);
+    if (a == b) return;
+    const int32_t hi = max(a, b), lo = min(a, b);
+    if (atomicCAS(parent + hi, hi, lo) == hi) return;
+    a = hi;
+    b = lo;
+  }
+}
+
+// reductions over the 64 lanes of a wavefront (every lane gets the result)
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = min(v, static_cast<uint32_t>(__shfl_xor(static_cast<int>(v), o, 64)));
+  return v;
+}
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = max(v, static_cast<uint32_t>(__shfl_xor(static_cast<int>(v), o, 64)));
+  return v;
+}
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += static_cast<unsigned long long>(__shfl_xor(static_cast<long long>(v), o, 64));
+  return v;
+}
 // CC1-CC4 on the live accumulation (ctx->n > 0, checked parameters): *m crack points, *rows cracks, the table in ctx->cc_*;
 // queued on ctx->stream and synchronised only as far as the counts need
 int crack_components_run(pcp_context *ctx, const pcp_crack_link_params &p, CcScratch &s, int64_t *m, int64_t *rows);
 // the checks pcp_crack_components makes of its parameters and of the accumulation, under the caller's name
 int crack_link_check(pcp_context *ctx, const char *who, const pcp_crack_link_params *p);
-void crack_length_release(pcp_context *ctx);  // the table and paths of pcp_crack_lengths (with cc's table)
+void crack_length_release(pcp_context *ctx);  // the table and paths of pcp_crack_lengths (with cc's table), and the skeleton's tables
 hipError_t preload_crack_length();
+// per-call scratch of the length stage beside the component stage's (pcp_crack_length.hip); everything is indexed by the
+// PLACE of a crack point in the grid's cell order.  After crack_lengths_run: dist = D_a, row_of = the crack's row, place_of =
+// view index -> place
+struct ClScratch {
+  DevBuf<unsigned long long> dist, far_d, pos;
+  DevBuf<uint32_t> mark, words;  // words[0]: the round in which a distance last fell; words[1]: a walk or an end went wrong
+  DevBuf<int32_t> place_of, row_of, src_place, far_k, end_a, end_b, pred;
+};
+// CC1-CC4 and CL1-CL7 on the live accumulation (ctx->n > 0, checked parameters): the component stage, then the length stage on
+// its m > 0 crack points; the tables in ctx->cc_* and ctx->cl_*, with_pos: CL5 in s.pos (n, input order).  Queued on
+// ctx->stream; the caller synchronises, drops the large grid bitmap and sets the live flags.
+int crack_lengths_run(pcp_context *ctx, const pcp_crack_link_params &p, CcScratch &cc, ClScratch &s, bool with_pos, int64_t *m,
+                      int64_t *rows, int64_t *entries);
+hipError_t preload_crack_skeleton();
 void crack_fuse_release(pcp_context *ctx);  // the accumulation of the crack widths (the uploads, pcp_set_camera, pcp_set_frames)
 void normals_release(pcp_context *ctx);   // the normals of the cloud that is being replaced (the uploads)
 // the list pcp_frame_visible reports for one keyframe (pcp_colour.hip): ascending input indices in ctx->s_cell, *m of them;

@@ -148,6 +148,15 @@
 //     path_width_mean_mm / path_width_min_mm / path_width_max_mm over the fused widths of the centreline's points.  The
 //     reference's script orders a crack only by a 2-D skeleton per keyframe.  Made on the GPU (pcp_crack_lengths; DESIGN.md
 //     "Crack lengths on the map").  cracks_3d.json and every other output stay as they are.
+//   * --crackSkeleton 0|1 (new, default 0; needs --crackFuse 1 and is refused where that is) and --crackSkeletonStep s (new,
+//     metres, default 0 = twice the link radius; at least the link radius, at most 16): with 1 the run also writes
+//     <outputPath>crack_width/map_crack_node.npy (<i4, (n): the id of the point's node of its crack's skeleton, -1 for a point
+//     outside every crack), crack_nodes.npy (<i8, (nodes, 10): crack_row, band, points, sum_w, min_w, max_w, sum_qx, sum_qy,
+//     sum_qz, degree) with crack_node_ids.npy (<i4, (nodes)), crack_edges.npy (<i8, (edges, 3): u, v, links) and
+//     crack_skeleton_3d.json: one record per crack, the cracks and order of cracks_3d.json, with id, nodes, edges, ends,
+//     junctions, loops, skeleton_length_m and the centroids of its end and junction nodes (end_xyz, junction_xyz).  The
+//     reference's script skeletonises each keyframe's mask in 2-D (preprocess(): pcv.morphology.skeletonize).  Made on the GPU
+//     (pcp_crack_skeleton; DESIGN.md "Crack skeletons on the map").  Every other output stays as it is.
 #include <cfloat>
 #include <chrono>
 #include <cmath>
@@ -239,6 +248,8 @@ struct Options {
   bool crack_width = false;           // --crackWidth 1: per-keyframe crack width maps (crack_width/*.npy)
   int crack_plane_radius = 150;       // --crackPlaneRadius R: half side of the plane's window, pixels
   bool crack_length = false;          // --crackLength 1: with --crackFuse, the cracks' lengths, ends and centrelines (crack_width/crack_*)
+  bool crack_skeleton = false;        // --crackSkeleton 1: with --crackFuse, the cracks' branches, junctions and loops (crack_width/crack_*)
+  float crack_skeleton_step = 0.0f;   // --crackSkeletonStep: the band width in metres (0: twice the link radius)
   bool crack_fuse = false;            // --crackFuse 1: the widths on the map and the map's cracks (crack_width/map_*.npy, cracks_3d.json)
   float crack_link_radius = 0.02f;    // --crackLinkRadius r: crack points this close belong to one crack
   int crack_min_views = 1;            // --crackMinViews v: credited keyframes a crack point needs
@@ -365,6 +376,8 @@ static Options parse(int argc, char **argv) {
     }
     else if (a == "--crackFuse") o.crack_fuse = parse_bool(next());
     else if (a == "--crackLength") o.crack_length = parse_bool(next());
+    else if (a == "--crackSkeleton") o.crack_skeleton = parse_bool(next());
+    else if (a == "--crackSkeletonStep") o.crack_skeleton_step = std::stof(next());
     else if (a == "--crackLinkRadius") {
       const std::string v = next();
       char *end = nullptr;
@@ -440,6 +453,10 @@ static Options parse(int argc, char **argv) {
                              "map; maps of the smoothed cloud are not built)");
   if (o.crack_length && !o.crack_fuse)
     throw std::runtime_error("the option '--crackLength 1' needs the widths on the map (--crackFuse 1)");
+  if (o.crack_skeleton && !o.crack_fuse)
+    throw std::runtime_error("the option '--crackSkeleton 1' needs the widths on the map (--crackFuse 1)");
+  if (o.crack_skeleton && !(o.crack_skeleton_step >= 0.0f && o.crack_skeleton_step <= 16.0f))
+    throw std::runtime_error("the option '--crackSkeletonStep' takes 0 (twice the link radius) or a band width in metres up to 16");
   if (o.crack_fuse && o.maskImageFolder.empty())
     throw std::runtime_error("the option '--crackFuse 1' needs the masks (--mask_image_folder)");
   if (o.crack_fuse && o.gpus > 1)
@@ -505,7 +522,9 @@ static void usage(std::ostream &os) {
         "  --crackFuse arg (=0)                  Also write the fused widths per map point and the map's cracks (-m, --gpus 1)\n"
         "  --crackLinkRadius arg (=0.02)         With --crackFuse: crack points this close (m) belong to one crack (0.005..1)\n"
         "  --crackMinViews arg (=1)              With --crackFuse: keyframes with a width that a crack point needs (1..4096)\n"
-        "  --crackLength arg (=0)                With --crackFuse: also write every crack's length, ends and centreline\n";
+        "  --crackLength arg (=0)                With --crackFuse: also write every crack's length, ends and centreline\n"
+        "  --crackSkeleton arg (=0)              With --crackFuse: also write every crack's skeleton: branches, junctions, loops\n"
+        "  --crackSkeletonStep arg (=0)          With --crackSkeleton: the band width in metres (0: twice the link radius)\n";
 }
 
 class Processor {
@@ -1248,12 +1267,15 @@ class Processor {
     }
     CrackMap m;
     CrackLengths cl;
+    CrackSkeleton sk;
     {
       const auto t0 = PhaseClock::clock::now();
       m = ViewCulling(dev).crackMap(added, static_cast<int64_t>(cloud.size()), opt.crack_threshold, opt.crack_plane_radius,
-                                    opt.crack_min_views, opt.crack_link_radius, opt.crack_length ? &cl : nullptr);
-      g_clock.add("crack_fuse_gpu_s", PhaseClock::since(t0) - cl.seconds);
+                                    opt.crack_min_views, opt.crack_link_radius, opt.crack_length ? &cl : nullptr,
+                                    opt.crack_skeleton ? &sk : nullptr, opt.crack_skeleton_step);
+      g_clock.add("crack_fuse_gpu_s", PhaseClock::since(t0) - cl.seconds - sk.seconds);
       if (opt.crack_length) g_clock.add("crack_length_gpu_s", cl.seconds);
+      if (opt.crack_skeleton) g_clock.add("crack_skeleton_gpu_s", sk.seconds);
     }
     Phase ph_w("crack_fuse_write_s");
     const size_t n = cloud.size();
@@ -1285,6 +1307,44 @@ class Processor {
     std::cout << "Crack widths on the map saved to: " << stem << "map_*.npy and cracks_3d.json, " << added.size() << " keyframes, " << m.credited
               << " credited samples, " << m.crack_points << " crack points, " << m.ids.size() << " cracks" << std::endl;
     if (opt.crack_length) writeCrackLengths(cl, stem);
+    if (opt.crack_skeleton) writeCrackSkeleton(sk, m, stem);
+  }
+
+  // --crackSkeleton 1: every crack's level-set diagram on the map: nodes, edges, ends, junctions, loops and skeleton length
+  void writeCrackSkeleton(const CrackSkeleton &c, const CrackMap &m, const std::string &stem) {
+    Phase ph("crack_skeleton_write_s");
+    const size_t nodes = c.ids.size(), edges = c.edges.size() / 3, cracks = c.cracks.size() / 6;
+    writeNpy(stem + "map_crack_node.npy", "<i4", {c.node.size()}, c.node.data(), c.node.size() * 4);
+    writeNpy(stem + "crack_nodes.npy", "<i8", {nodes, 10}, c.nodes.data(), c.nodes.size() * 8);
+    writeNpy(stem + "crack_node_ids.npy", "<i4", {nodes}, c.ids.data(), nodes * 4);
+    writeNpy(stem + "crack_edges.npy", "<i8", {edges, 3}, c.edges.data(), c.edges.size() * 8);
+    if (cracks != m.ids.size()) throw std::runtime_error("The skeletons' cracks are not those of the map.");
+    auto num = [](double v) {
+      char b[64];
+      std::snprintf(b, sizeof(b), "%.9g", v);
+      return std::string(b);
+    };
+    const std::vector<double> length = c.skeletonLengths();
+    std::vector<std::string> end_xyz(cracks), junction_xyz(cracks);  // the centroids, by ascending node row
+    for (size_t r = 0; r < nodes; ++r) {
+      const int64_t *row = c.nodes.data() + 10 * r;
+      if (row[9] != 1 && row[9] < 3) continue;
+      std::string &list = row[9] == 1 ? end_xyz[static_cast<size_t>(row[0])] : junction_xyz[static_cast<size_t>(row[0])];
+      list += (list.empty() ? "[" : ", [") + num(c.centroid(r, 0)) + ", " + num(c.centroid(r, 1)) + ", " + num(c.centroid(r, 2)) + "]";
+    }
+    std::ofstream f(stem + "crack_skeleton_3d.json");
+    f << "[";
+    for (size_t r = 0; r < cracks; ++r) {
+      const int64_t *row = c.cracks.data() + 6 * r;
+      f << (r ? ",\n " : "\n ") << "{\"id\": " << m.ids[r] << ", \"nodes\": " << row[0] << ", \"edges\": " << row[1] << ", \"ends\": " << row[2]
+        << ", \"junctions\": " << row[3] << ", \"loops\": " << row[4] << ", \"skeleton_length_m\": " << num(length[r]) << ", \"end_xyz\": ["
+        << end_xyz[r] << "], \"junction_xyz\": [" << junction_xyz[r] << "]}";
+    }
+    f << "\n]\n";
+    f.close();
+    if (!f) throw std::runtime_error("Couldn't save the crack skeletons of the map.");
+    std::cout << "Crack skeletons on the map saved to: " << stem << "map_crack_node.npy, crack_nodes.npy, crack_node_ids.npy, crack_edges.npy and "
+              << "crack_skeleton_3d.json, " << cracks << " cracks, " << nodes << " nodes, " << edges << " edges" << std::endl;
   }
 
   // --crackLength 1: every crack's geodesic length, ends and centreline on the map, and every point's arc position

@@ -16,6 +16,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -84,6 +85,35 @@ struct CrackLengths {
   std::vector<int64_t> offsets;    // cracks + 1: crack k's polyline is path[offsets[k] .. offsets[k + 1])
   std::vector<int32_t> path;       // input indices, from end a to end b
   double seconds = 0.0;            // wall time of the stage (the call and its fetches)
+};
+
+// The skeletons of the map's cracks (pcp_hip.h, "crack skeletons on the map"): the level-set diagram of every crack -- nodes,
+// edges and one summary row per crack, the rows and order of CrackMap -- and per map point the id of its node.  The library
+// returns integers only; the metres are host arithmetic on them, here in one place.
+struct CrackSkeleton {
+  std::vector<int32_t> node;       // the id of the point's node (the lowest input index among its points); -1: no crack point
+  std::vector<int32_t> ids;        // per node, ascending
+  std::vector<int64_t> nodes;      // 10 per node: crack_row, band, points, sum_w, min_w, max_w, sum_qx, sum_qy, sum_qz, degree
+  std::vector<int64_t> edges;      // 3 per edge: u (the node row in the lower band), v, links; ascending by (u, v)
+  std::vector<int64_t> cracks;     // 6 per crack: nodes, edges, ends, junctions, loops, max_degree
+  double seconds = 0.0;            // wall time of the stage (the call and its fetches)
+  // a node's centroid on one axis (0..2), metres
+  double centroid(size_t node_row, int axis) const {
+    const int64_t *row = nodes.data() + 10 * node_row;
+    return (static_cast<double>(row[6 + axis]) / static_cast<double>(row[2])) * (1.0 / 1048576.0);
+  }
+  // the distance of an edge's two centroids, metres
+  double edgeLength(size_t edge_row) const {
+    const size_t u = static_cast<size_t>(edges[3 * edge_row]), v = static_cast<size_t>(edges[3 * edge_row + 1]);
+    const double dx = centroid(v, 0) - centroid(u, 0), dy = centroid(v, 1) - centroid(u, 1), dz = centroid(v, 2) - centroid(u, 2);
+    return std::sqrt((dx * dx + dy * dy) + dz * dz);
+  }
+  // per crack the sum of its edges' lengths in row order, metres
+  std::vector<double> skeletonLengths() const {
+    std::vector<double> length(cracks.size() / 6, 0.0);
+    for (size_t e = 0; e < edges.size() / 3; ++e) length[static_cast<size_t>(nodes[10 * static_cast<size_t>(edges[3 * e])])] += edgeLength(e);
+    return length;
+  }
 };
 
 class Device {
@@ -294,8 +324,10 @@ class ViewCulling {
   // components of the points with min_views credited keyframes or more under the link radius: what the script's result file
   // (scripts/genNormAndDistanceMask.py:476-478) lists per hand-picked pixel, for the whole map and with the cracks told apart
   // lengths (nullable): also the cracks' lengths, ends and centrelines for the same min_views and link radius
+  // skeleton (nullable): also the cracks' skeletons for them and the band width skeleton_step (metres; 0: 2 * link_radius)
   CrackMap crackMap(const std::vector<int> &keyframes, int64_t points, int threshold = 0, int plane_radius = 150, int min_views = 1,
-                    float link_radius = 0.02f, CrackLengths *lengths = nullptr) const {
+                    float link_radius = 0.02f, CrackLengths *lengths = nullptr, CrackSkeleton *skeleton = nullptr,
+                    float skeleton_step = 0.0f) const {
     CrackMap m;
     dev_.check(pcp_crack_fuse_begin(dev_.get()));
     try {
@@ -321,6 +353,7 @@ class ViewCulling {
       m.box.resize(6 * static_cast<size_t>(rows));
       dev_.check(pcp_crack_components_fetch(dev_.get(), 0, rows, m.ids.data(), m.stats.data(), m.box.data(), &got));
       if (lengths) *lengths = crackLengths(points, min_views, link_radius);
+      if (skeleton) *skeleton = crackSkeleton(points, min_views, link_radius, skeleton_step);
     } catch (...) {
       (void)pcp_crack_fuse_end(dev_.get());
       throw;
@@ -343,6 +376,27 @@ class ViewCulling {
     c.path.resize(static_cast<size_t>(entries));
     dev_.check(pcp_crack_lengths_fetch(dev_.get(), 0, rows, c.ids.data(), c.rows.data(), c.offsets.data(), &got));
     dev_.check(pcp_crack_paths_fetch(dev_.get(), 0, entries, c.path.data(), &got));
+    c.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return c;
+  }
+  // The level-set diagram of every crack of the live accumulation (between pcp_crack_fuse_begin and _end; crackMap runs it
+  // when asked): what pcv.morphology.skeletonize gives the reference's script per keyframe and in 2-D, once and on the map.
+  // step: the band width in metres, 0 for 2 * link_radius.
+  CrackSkeleton crackSkeleton(int64_t points, int min_views = 1, float link_radius = 0.02f, float step = 0.0f) const {
+    CrackSkeleton c;
+    const auto t0 = std::chrono::steady_clock::now();
+    c.node.resize(static_cast<size_t>(points));
+    const pcp_crack_link_params link{min_views, link_radius};
+    int64_t nodes = 0, edges = 0, cracks = 0, got = 0;
+    dev_.check(pcp_crack_skeleton(dev_.get(), &link, step > 0.0f ? step : 2.0f * link_radius, c.node.data(), &nodes, &edges));
+    dev_.check(pcp_crack_skeleton_cracks_fetch(dev_.get(), 0, INT64_MAX / 2, nullptr, &cracks));
+    c.ids.resize(static_cast<size_t>(nodes));
+    c.nodes.resize(10 * static_cast<size_t>(nodes));
+    c.edges.resize(3 * static_cast<size_t>(edges));
+    c.cracks.resize(6 * static_cast<size_t>(cracks));
+    dev_.check(pcp_crack_skeleton_nodes_fetch(dev_.get(), 0, nodes, c.ids.data(), c.nodes.data(), &got));
+    dev_.check(pcp_crack_skeleton_edges_fetch(dev_.get(), 0, edges, c.edges.data(), &got));
+    dev_.check(pcp_crack_skeleton_cracks_fetch(dev_.get(), 0, cracks, c.cracks.data(), &got));
     c.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return c;
   }

@@ -207,7 +207,7 @@ class PointCloudColorizer:
         return self.engine.ctx.crack_width(frame, threshold, plane_radius, want)
 
     def crack_map(self, frames=None, threshold: int = 0, plane_radius: int = 150, min_views: int = 1, link_radius: float = 0.02,
-                  lengths: bool = False) -> dict:
+                  lengths: bool = False, skeleton: bool = False, skeleton_step=None) -> dict:
         """The crack widths of the keyframes brought back to the map, and the map's cracks ("Crack widths on the
         map"): begin, one add per keyframe of `frames` (None: all of them), the components, end.  dict of the per-point arrays of
         capi.Context.crack_fuse_fetch (width_mean, width_best, best_frame, views, seen, centres, min_q, max_q, sum_q) and of
@@ -218,6 +218,10 @@ class PointCloudColorizer:
         lengths: the dict gains `lengths`, the dict of capi.Context.crack_lengths for the same min_views and link_radius
         ("Crack lengths on the map"): per crack a geodesic length, its ends and an ordered polyline, per point
         its arc position.  Off, the return value is what it was.
+
+        skeleton: the dict gains `skeleton`, the dict of capi.Context.crack_skeleton for the same min_views and link_radius and
+        the band width skeleton_step (metres; None: 2 * link_radius) ("Crack skeletons on the map"): per crack its
+        nodes, edges, ends, junctions, loops and skeleton length.  Off, the return value is what it was.
 
         An index shard sees only its own points, so world > 1 raises ValueError.  (The shards' key images would have to be
         merged first, as for geometry_maps; not built.)"""
@@ -234,6 +238,8 @@ class PointCloudColorizer:
             out.update(ctx.crack_components(min_views, link_radius))
             if lengths:
                 out["lengths"] = ctx.crack_lengths(min_views, link_radius)
+            if skeleton:
+                out["skeleton"] = ctx.crack_skeleton(min_views, link_radius, skeleton_step)
             out["contributors"] = [c[0] for c in counts]
             out["credited"] = [c[1] for c in counts]
             return out
