@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "pcp_internal.hpp"
+#include "pcp_crack_map.hpp"
 #include "pcp_visit_forms.hpp"
 #include "pcp_scan.hpp"
 
@@ -517,7 +518,7 @@ static int store_cloud(pcp_context *ctx, const float *x, const float *y, const f
   ctx->labels_live = false;
   match_table_release(ctx);  // PCP_MATCH_RADIUS: the table belongs to the cloud that is being replaced
   normals_release(ctx);      // pcp_estimate_normals: so do the normals
-  crack_fuse_release(ctx);   // pcp_crack_fuse_begin: and the accumulated crack widths
+  ctx->crack->release();   // pcp_crack_fuse_begin: and the accumulated crack widths
   ctx->mls_count = 0;
   ctx->mls_result_live = false;
   ctx->vgd_next = ctx->css_next = -1;  // the streams of the smoothing stage belong to the cloud that is being replaced
@@ -616,8 +617,10 @@ int pcp_create(int32_t device, pcp_context **out) {
     return PCP_ERR_DEVICE;
   }
   pcp_context *ctx = new (std::nothrow) pcp_context();
-  if (!ctx) {
+  if (ctx) ctx->crack.reset(new (std::nothrow) pcp::CrackMap());
+  if (!ctx || !ctx->crack) {
     set_global_error("pcp_create: out of host memory");
+    delete ctx;
     return PCP_ERR_NOMEM;
   }
   ctx->device = device;
@@ -846,7 +849,7 @@ int pcp_set_camera(pcp_context *ctx, const pcp_camera *cam, const pcp_cull_param
   ctx->hull_valid.clear();
   ctx->depth_accum.release();  // sized by the camera
   ctx->depth_accum_live = false;
-  crack_fuse_release(ctx);  // the accumulated crack widths belong to the camera and the keyframes they were measured with
+  ctx->crack->release();  // the accumulated crack widths belong to the camera and the keyframes they were measured with
   ctx->colour_state_live = false;
   ctx->colour_result_live = false;
   ctx->labels_live = false;
@@ -971,7 +974,7 @@ int pcp_set_frames(pcp_context *ctx, const pcp_pose *poses, int32_t n_frames, co
   ctx->hull_valid.clear();
   ctx->depth_accum.release();  // one map per keyframe of the set that is being replaced
   ctx->depth_accum_live = false;
-  crack_fuse_release(ctx);
+  ctx->crack->release();
   ctx->match_live = false;  // PCP_MATCH_RADIUS: E (and with it R_c) depends on the keyframes
   ctx->gains_set = false;   // exposure gains: one per keyframe of the set that is being replaced
   ctx->colour_state_live = false;

@@ -17,9 +17,9 @@
 #include <vector>
 
 #include "pcp_device.hpp"
-#include "pcp_internal.hpp"
+#include "pcp_crack_map.hpp"
 #include "pcp_scan.hpp"
-#include "pcp_crack_fuse.hpp"
+#include "pcp_crack_length.hpp"
 
 namespace pcp {
 
@@ -142,19 +142,13 @@ __global__ __launch_bounds__(kCfBlock) void k_cc_union(const float *__restrict__
   const int32_t s = static_cast<int32_t>(s64);
   const float qx = gx[s], qy = gy[s], qz = gz[s];
   const int32_t mine = order[s];
-  int32_t ix, iy, iz;
-  grid_coords(g, qx, qy, qz, ix, iy, iz);
-  const int32_t R = g.reach;
-  for (int32_t zz = max(iz - R, 0); zz <= min(iz + R, g.nz - 1); ++zz)
-    for (int32_t yy = max(iy - R, 0); yy <= min(iy + R, g.ny - 1); ++yy) {
-      const int32_t b = cell_start(g, start, zz, yy, max(ix - R, 0));
-      const int32_t e = min(cell_start(g, start, zz, yy, min(ix + R, g.nx - 1) + 1), static_cast<int32_t>(m));
-      for (int32_t c = max(b, s + 1); c < e; ++c)
-        if (cf::linked(gx[c] - qx, gy[c] - qy, gz[c] - qz, t)) cc_unite(parent, mine, order[c]);
-    }
+  crack_walk<true>(g, start, qx, qy, qz, s, m, [&](int32_t c) {
+    if (cl::d2_of(gx[c] - qx, gy[c] - qy, gz[c] - qz) <= t) cc_unite(parent, mine, order[c]);
+  });
 }
 
-// CC3: after the union kernel has ended the forest is final; the walk goes down strictly descending indices
+// CC3 (and CS3, without labels): after the union kernel has ended the forest is final; the walk goes down strictly descending
+// indices.  label nullable.
 __global__ __launch_bounds__(kCfBlock) void k_cc_flatten(const int32_t *__restrict__ parent, const int32_t *__restrict__ list,
                                                          int64_t m, int32_t *__restrict__ root_of, int32_t *__restrict__ is_root,
                                                          int32_t *__restrict__ label) {
@@ -164,7 +158,7 @@ __global__ __launch_bounds__(kCfBlock) void k_cc_flatten(const int32_t *__restri
   for (int32_t p = parent[v]; p != v; p = parent[v]) v = p;  // (p < v)
   root_of[k] = v;
   is_root[k] = v == static_cast<int32_t>(k) ? 1 : 0;
-  label[list[k]] = list[v];
+  if (label) label[list[k]] = list[v];
 }
 
 // CC4: the empty table, and the ids (rank[k] = roots before view index k: the rows ascend by id because the list does)
@@ -217,12 +211,8 @@ __global__ __launch_bounds__(kCfBlock) void k_cc_stats(const float *__restrict__
     centre = u32[2 * n + i] > 0 ? 1 : 0;
     cf::add(b, gx[s], gy[s], gz[s]);
   }
-  const unsigned long long live = __ballot(valid);
-  if (live == 0) return;
-  const int leader = __ffsll(static_cast<long long>(live)) - 1;
-  const int32_t row0 = __shfl(row, leader, 64);
-  const bool shared = __ballot(valid && row == row0) == live;  // (the same for every lane of the wavefront)
-  bool issue = valid;
+  bool shared;
+  const bool issue = wave_row_issuer(valid, row, &shared);
   if (shared) {
     points = wave_sum_u64(points);
     sum_w = wave_sum_u64(sum_w);
@@ -234,7 +224,6 @@ __global__ __launch_bounds__(kCfBlock) void k_cc_stats(const float *__restrict__
       b.lo[a] = wave_min_u32(b.lo[a]);
       b.hi[a] = wave_max_u32(b.hi[a]);
     }
-    issue = static_cast<int>(threadIdx.x & 63) == leader;
   }
   if (!issue) return;
   unsigned long long *st = stats + static_cast<int64_t>(kCcStatWords) * row;
@@ -256,22 +245,26 @@ hipError_t preload_crack_fuse() {
   return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_cc_stats));
 }
 
-void crack_fuse_release(pcp_context *ctx) {
-  ctx->cf_live = false;
-  ctx->cc_live = false;
-  ctx->cc_rows = 0;
-  ctx->cf_added.clear();
-  ctx->cf_u32.release();
-  ctx->cf_u64.release();
-  ctx->cc_ids.release();
-  ctx->cc_stats.release();
-  ctx->cc_box.release();
-  crack_length_release(ctx);
+int crack_label_forest(pcp_context *ctx, const char *who, const char *what, const int32_t *parent, const int32_t *list, int64_t m,
+                       int64_t least, int32_t *root_of, int32_t *rank, int32_t *label, int64_t *roots) {
+  {
+    LaunchTimer lt(ctx, PCP_K_MISC);
+    hipLaunchKernelGGL(k_cc_flatten, dim3(cf_blocks(m)), dim3(kCfBlock), 0, ctx->stream, parent, list, m, root_of, rank, label);
+    PCP_HIP_TRY(ctx, scan_exclusive(ctx->stream, rank, m + 1, ctx->s_tiles, nullptr));  // [m] = the number of roots
+  }
+  int32_t found = 0;
+  PCP_HIP_TRY(ctx, hipMemcpyAsync(&found, rank + m, 4, hipMemcpyDeviceToHost, ctx->stream));
+  PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  *roots = found;
+  if (found < least || found > m)
+    return set_error(ctx, PCP_ERR_DEVICE, "%s: %d %s for %lld crack points, outside %lld..%lld", who, found, what, (long long)m, (long long)least, (long long)m);
+  return PCP_OK;
 }
 
 // the m > 0 crack points of s.list: view, grid, union, flatten, ranks, table
 static int components_run(pcp_context *ctx, float radius, int64_t m, CcScratch &s, int64_t *out_components) {
   const int64_t n = ctx->n;
+  CrackMap &cm = *ctx->crack;
   const size_t sm = static_cast<size_t>(m), pm = (sm + 3) & ~size_t(3);
   const size_t plane = (static_cast<size_t>(n) + 3) & ~size_t(3);
   const float *x = ctx->xyz.p, *y = ctx->xyz.p + plane, *z = ctx->xyz.p + 2 * plane;
@@ -318,26 +311,17 @@ static int components_run(pcp_context *ctx, float radius, int64_t m, CcScratch &
                        t, s.parent.p);
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
+  int64_t rows = 0;
+  if ((rc = crack_label_forest(ctx, "pcp_crack_components", "roots", s.parent.p, s.list.p, m, 1, s.root_of.p, s.rank.p, s.label.p, &rows)) != PCP_OK) return rc;
+  PCP_HIP_TRY(ctx, cm.cc_ids.ensure(static_cast<size_t>(rows) + 4));
+  PCP_HIP_TRY(ctx, cm.cc_stats.ensure(static_cast<size_t>(kCcStatWords) * rows + 4));
+  PCP_HIP_TRY(ctx, cm.cc_box.ensure(6 * static_cast<size_t>(rows) + 4));
   {
     LaunchTimer lt(ctx, PCP_K_MISC);
-    hipLaunchKernelGGL(k_cc_flatten, dim3(cf_blocks(m)), dim3(kCfBlock), 0, ctx->stream, s.parent.p, s.list.p, m, s.root_of.p, s.rank.p,
-                       s.label.p);
-    PCP_HIP_TRY(ctx, scan_exclusive(ctx->stream, s.rank.p, m + 1, ctx->s_tiles, nullptr));  // [m] = the number of roots
-  }
-  int32_t roots = 0;
-  PCP_HIP_TRY(ctx, hipMemcpyAsync(&roots, s.rank.p + m, 4, hipMemcpyDeviceToHost, ctx->stream));
-  PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  const int64_t rows = roots;
-  if (rows < 1 || rows > m) return set_error(ctx, PCP_ERR_DEVICE, "pcp_crack_components: %lld roots for %lld crack points", (long long)rows, (long long)m);
-  PCP_HIP_TRY(ctx, ctx->cc_ids.ensure(static_cast<size_t>(rows) + 4));
-  PCP_HIP_TRY(ctx, ctx->cc_stats.ensure(static_cast<size_t>(kCcStatWords) * rows + 4));
-  PCP_HIP_TRY(ctx, ctx->cc_box.ensure(6 * static_cast<size_t>(rows) + 4));
-  {
-    LaunchTimer lt(ctx, PCP_K_MISC);
-    hipLaunchKernelGGL(k_cc_table_init, dim3(cf_blocks(rows)), dim3(kCfBlock), 0, ctx->stream, ctx->cc_stats.p, ctx->cc_box.p, rows);
-    hipLaunchKernelGGL(k_cc_ids, dim3(cf_blocks(m)), dim3(kCfBlock), 0, ctx->stream, s.root_of.p, s.rank.p, s.list.p, m, ctx->cc_ids.p);
+    hipLaunchKernelGGL(k_cc_table_init, dim3(cf_blocks(rows)), dim3(kCfBlock), 0, ctx->stream, cm.cc_stats.p, cm.cc_box.p, rows);
+    hipLaunchKernelGGL(k_cc_ids, dim3(cf_blocks(m)), dim3(kCfBlock), 0, ctx->stream, s.root_of.p, s.rank.p, s.list.p, m, cm.cc_ids.p);
     hipLaunchKernelGGL(k_cc_stats, dim3(cf_blocks(m)), dim3(kCfBlock), 0, ctx->stream, gx, gy, gz, ctx->g_order.p, m, s.root_of.p,
-                       s.rank.p, s.list.p, n, ctx->cf_u32.p, ctx->cf_u64.p, ctx->cc_stats.p, ctx->cc_box.p);
+                       s.rank.p, s.list.p, n, cm.cf_u32.p, cm.cf_u64.p, cm.cc_stats.p, cm.cc_box.p);
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
   *out_components = rows;
@@ -349,11 +333,11 @@ int crack_link_check(pcp_context *ctx, const char *who, const pcp_crack_link_par
   if (!cf::min_views_ok(p->min_views))
     return set_error(ctx, PCP_ERR_INVALID, "%s: min_views %d outside %d..%d", who, p->min_views, cf::kMinViewsLo, cf::kMinViewsHi);
   if (!gn::radius_ok(p->radius)) return set_error(ctx, PCP_ERR_INVALID, "%s: radius %g outside [0.005, 1]", who, static_cast<double>(p->radius));
-  if (!ctx->cf_live) return set_error(ctx, PCP_ERR_STATE, "%s: no accumulation (pcp_crack_fuse_begin)", who);
+  if (!ctx->crack->readable(CrackMap::kFusion)) return set_error(ctx, PCP_ERR_STATE, "%s: no accumulation (pcp_crack_fuse_begin)", who);
   return PCP_OK;
 }
 
-int crack_components_run(pcp_context *ctx, const pcp_crack_link_params &p, CcScratch &s, int64_t *out_m, int64_t *out_rows) {
+int crack_components_run(pcp_context *ctx, const pcp_crack_link_params &p, CcScratch &s, CrackCounts *c) {
   const int64_t n = ctx->n;
   const size_t sn = static_cast<size_t>(n);
   const size_t plane = (sn + 3) & ~size_t(3);
@@ -363,16 +347,64 @@ int crack_components_run(pcp_context *ctx, const pcp_crack_link_params &p, CcScr
   PCP_HIP_TRY(ctx, hipMemsetAsync(s.label.p, 0xff, sn * 4, ctx->stream));  // CC3: -1 for a point that is no crack point
   {
     LaunchTimer lt(ctx, PCP_K_MISC);
-    hipLaunchKernelGGL(k_cc_flag, dim3(cf_blocks(n)), dim3(kCfBlock), 0, ctx->stream, ctx->cf_u32.p + sn, ctx->xyz.p, ctx->xyz.p + plane,
+    hipLaunchKernelGGL(k_cc_flag, dim3(cf_blocks(n)), dim3(kCfBlock), 0, ctx->stream, ctx->crack->cf_u32.p + sn, ctx->xyz.p, ctx->xyz.p + plane,
                        ctx->xyz.p + 2 * plane, n, p.min_views, s.flag.p);
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
-  int64_t m = 0, rows = 0;
-  int rc = compact_flags(ctx, s.flag.p, n, s.list.p, n, &m);
+  int rc = compact_flags(ctx, s.flag.p, n, s.list.p, n, &c->points);
+  if (rc == PCP_OK && c->points > 0) rc = components_run(ctx, p.radius, c->points, s, &c->cracks);
+  return rc;
+}
+
+// the stages up to `upto` and the copies of the per-point outputs, queued
+static int crack_map_stages(pcp_context *ctx, const pcp_crack_link_params &p, CrackMap::Level upto, uint64_t step_q, const CrackOut &out,
+                            CcScratch &cc, ClScratch &cl, CsScratch &cs, CrackCounts *c) {
+  const size_t sn = static_cast<size_t>(ctx->n);
+  if (out.pos) {  // CL5: 2^64 - 1 for a point that is no crack point
+    PCP_HIP_TRY(ctx, cl.pos.ensure(sn + 4));
+    PCP_HIP_TRY(ctx, hipMemsetAsync(cl.pos.p, 0xff, sn * 8, ctx->stream));
+  }
+  if (out.node) {  // CS3: -1
+    PCP_HIP_TRY(ctx, cs.node.ensure(sn + 4));
+    PCP_HIP_TRY(ctx, hipMemsetAsync(cs.node.p, 0xff, sn * 4, ctx->stream));
+  }
+  int rc = crack_components_run(ctx, p, cc, c);
+  if (rc == PCP_OK && upto >= CrackMap::kLengths && c->points > 0) rc = crack_lengths_run(ctx, p, cc, cl, c);
+  if (rc == PCP_OK && upto >= CrackMap::kSkeleton && c->points > 0) rc = crack_skeleton_run(ctx, p, step_q, cc, cl, cs, c);
   if (rc != PCP_OK) return rc;
-  if (m > 0 && (rc = components_run(ctx, p.radius, m, s, &rows)) != PCP_OK) return rc;
-  *out_m = m;
-  *out_rows = rows;
+  if (out.label) PCP_HIP_TRY(ctx, hipMemcpyAsync(out.label, cc.label.p, sn * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (out.pos) PCP_HIP_TRY(ctx, hipMemcpyAsync(out.pos, cl.pos.p, sn * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (out.node) PCP_HIP_TRY(ctx, hipMemcpyAsync(out.node, cs.node.p, sn * 4, hipMemcpyDeviceToHost, ctx->stream));
+  return PCP_OK;
+}
+
+int crack_map_run(pcp_context *ctx, const pcp_crack_link_params &p, CrackMap::Level upto, uint64_t step_q, const CrackOut &out,
+                  CrackCounts *c) {
+  CrackMap &cm = *ctx->crack;
+  *c = CrackCounts();
+  cm.replacing(upto);
+  if (ctx->n == 0) {
+    cm.hold(upto, *c);
+    return PCP_OK;
+  }
+  PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  CcScratch cc;
+  ClScratch cl;
+  CsScratch cs;
+  const int rc = crack_map_stages(ctx, p, upto, step_q, out, cc, cl, cs, c);
+  const hipError_t e = hipStreamSynchronize(ctx->stream);  // (also: the scratch is released on return)
+  drop_large_grid_bitmap(ctx);
+  if (rc != PCP_OK) return rc;
+  PCP_HIP_TRY(ctx, e);
+  cm.hold(upto, *c);
+  return PCP_OK;
+}
+
+int crack_window(pcp_context *ctx, const char *who, CrackMap::Level l, int64_t first, int64_t max_rows, int64_t have, int64_t *rows) {
+  static const char *const maker[] = {"pcp_crack_fuse_begin", "pcp_crack_components", "pcp_crack_lengths", "pcp_crack_skeleton"};
+  if (first < 0 || max_rows < 0) return set_error(ctx, PCP_ERR_INVALID, "%s: negative first or max_rows", who);
+  if (!ctx->crack->readable(l)) return set_error(ctx, PCP_ERR_STATE, "%s: no table (%s on the accumulation as it is)", who, maker[l]);
+  *rows = std::max<int64_t>(0, std::min(max_rows, have - first));
   return PCP_OK;
 }
 
@@ -386,23 +418,24 @@ int pcp_crack_fuse_begin(pcp_context *ctx) {
   if (!ctx) return PCP_ERR_INVALID;
   if (!ctx->xyz.p && ctx->n > 0) return set_error(ctx, PCP_ERR_STATE, "pcp_crack_fuse_begin: no cloud uploaded");
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  crack_fuse_release(ctx);
+  CrackMap &cm = *ctx->crack;
+  cm.release();
   const int64_t n = ctx->n;
   const size_t sn = static_cast<size_t>(n);
-  PCP_HIP_TRY(ctx, ctx->cf_u32.ensure(kCfU32Planes * sn + 4));
-  PCP_HIP_TRY(ctx, ctx->cf_u64.ensure(kCfU64Planes * sn + 4));
+  PCP_HIP_TRY(ctx, cm.cf_u32.ensure(kCfU32Planes * sn + 4));
+  PCP_HIP_TRY(ctx, cm.cf_u64.ensure(kCfU64Planes * sn + 4));
   try {
-    ctx->cf_added.assign(static_cast<size_t>(std::max<int32_t>(ctx->n_frames, 0)), 0);
+    cm.cf_added.assign(static_cast<size_t>(std::max<int32_t>(ctx->n_frames, 0)), 0);
   } catch (const std::bad_alloc &) {
     return set_error(ctx, PCP_ERR_NOMEM, "pcp_crack_fuse_begin: out of host memory for %d keyframes", ctx->n_frames);
   }
   if (n > 0) {
     LaunchTimer lt(ctx, PCP_K_MISC);
-    hipLaunchKernelGGL(k_cf_init, dim3(cf_blocks(n)), dim3(kCfBlock), 0, ctx->stream, ctx->cf_u32.p, ctx->cf_u64.p, n);
+    hipLaunchKernelGGL(k_cf_init, dim3(cf_blocks(n)), dim3(kCfBlock), 0, ctx->stream, cm.cf_u32.p, cm.cf_u64.p, n);
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
   PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->cf_live = true;
+  cm.begin();
   return PCP_OK;
 }
 
@@ -413,8 +446,9 @@ int pcp_crack_fuse_add(pcp_context *ctx, int32_t frame, const pcp_crack_params *
   if (out_credited) *out_credited = 0;
   int rc = crack_width_check(ctx, "pcp_crack_fuse_add", params);
   if (rc != PCP_OK) return rc;
-  if (!ctx->cf_live) return set_error(ctx, PCP_ERR_STATE, "pcp_crack_fuse_add: no accumulation (pcp_crack_fuse_begin on this cloud, camera and keyframes)");
-  if (frame >= 0 && static_cast<size_t>(frame) < ctx->cf_added.size() && ctx->cf_added[static_cast<size_t>(frame)])
+  CrackMap &cm = *ctx->crack;
+  if (!cm.readable(CrackMap::kFusion)) return set_error(ctx, PCP_ERR_STATE, "pcp_crack_fuse_add: no accumulation (pcp_crack_fuse_begin on this cloud, camera and keyframes)");
+  if (frame >= 0 && static_cast<size_t>(frame) < cm.cf_added.size() && cm.cf_added[static_cast<size_t>(frame)])
     return set_error(ctx, PCP_ERR_STATE, "pcp_crack_fuse_add: keyframe %d has been added to this accumulation", frame);
   // as pcp_crack_width: the geometry scatter (camera, cloud, keyframes, the keyframe's range), the distance transform (the mask),
   // the width kernels; the flag and width images stay in ctx->cw_flags and ctx->cw_f32
@@ -436,15 +470,14 @@ int pcp_crack_fuse_add(pcp_context *ctx, int32_t frame, const pcp_crack_params *
       LaunchTimer lt(ctx, PCP_K_MISC);
       hipLaunchKernelGGL(k_cf_gather, dim3(cf_blocks(m)), dim3(kCfBlock), 0, ctx->stream, ctx->xyz.p, ctx->xyz.p + plane,
                          ctx->xyz.p + 2 * plane, ctx->dcam, ctx->hframes[static_cast<size_t>(frame)], ctx->s_cell.p, m, px,
-                         ctx->cw_flags.p, ctx->cw_f32.p + 4 * spx, frame, ctx->n, ctx->cf_u32.p, ctx->cf_u64.p, tally);
+                         ctx->cw_flags.p, ctx->cw_f32.p + 4 * spx, frame, ctx->n, cm.cf_u32.p, cm.cf_u64.p, tally);
       PCP_HIP_TRY(ctx, hipGetLastError());
     }
     PCP_HIP_TRY(ctx, hipMemcpyAsync(&credited, tally, 8, hipMemcpyDeviceToHost, ctx->stream));
     PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
-  ctx->cf_added[static_cast<size_t>(frame)] = 1;
-  ctx->cc_live = false;  // the table of the last pcp_crack_components describes the state before this keyframe
-  ctx->cl_live = false;  // ... and so do the lengths
+  cm.cf_added[static_cast<size_t>(frame)] = 1;
+  cm.changed();
   if (out_contributors) *out_contributors = m;
   if (out_credited) *out_credited = static_cast<int64_t>(credited);
   return PCP_OK;
@@ -453,7 +486,7 @@ int pcp_crack_fuse_add(pcp_context *ctx, int32_t frame, const pcp_crack_params *
 int pcp_crack_fuse_fetch(pcp_context *ctx, float *out_width_mean, float *out_width_best, int32_t *out_best_frame, uint32_t *out_views,
                          uint32_t *out_seen, uint32_t *out_centres, uint32_t *out_min_q, uint32_t *out_max_q, uint64_t *out_sum_q) {
   if (!ctx) return PCP_ERR_INVALID;
-  if (!ctx->cf_live) return set_error(ctx, PCP_ERR_STATE, "pcp_crack_fuse_fetch: no accumulation (pcp_crack_fuse_begin)");
+  if (!ctx->crack->readable(CrackMap::kFusion)) return set_error(ctx, PCP_ERR_STATE, "pcp_crack_fuse_fetch: no accumulation (pcp_crack_fuse_begin)");
   const int64_t n = ctx->n;
   if (n == 0) return PCP_OK;
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -472,8 +505,8 @@ int pcp_crack_fuse_fetch(pcp_context *ctx, float *out_width_mean, float *out_wid
   }
   uint32_t *views = out_views ? out_views : (own_views.empty() ? nullptr : own_views.data());
   uint64_t *sum_q = out_sum_q ? out_sum_q : (own_sum.empty() ? nullptr : own_sum.data());
-  const uint32_t *u32 = ctx->cf_u32.p;
-  const unsigned long long *u64 = ctx->cf_u64.p;
+  const uint32_t *u32 = ctx->crack->cf_u32.p;
+  const unsigned long long *u64 = ctx->crack->cf_u64.p;
   hipStream_t st = ctx->stream;
   if (out_seen) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_seen, u32, sn * 4, hipMemcpyDeviceToHost, st));
   if (views) PCP_HIP_TRY(ctx, hipMemcpyAsync(views, u32 + sn, sn * 4, hipMemcpyDeviceToHost, st));
@@ -494,10 +527,10 @@ int pcp_crack_fuse_fetch(pcp_context *ctx, float *out_width_mean, float *out_wid
 
 int pcp_crack_fuse_end(pcp_context *ctx) {
   if (!ctx) return PCP_ERR_INVALID;
-  if (!ctx->cf_live) return set_error(ctx, PCP_ERR_STATE, "pcp_crack_fuse_end: no accumulation (pcp_crack_fuse_begin)");
+  if (!ctx->crack->readable(CrackMap::kFusion)) return set_error(ctx, PCP_ERR_STATE, "pcp_crack_fuse_end: no accumulation (pcp_crack_fuse_begin)");
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
   PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  crack_fuse_release(ctx);
+  ctx->crack->release();
   return PCP_OK;
 }
 
@@ -546,25 +579,12 @@ int pcp_crack_components(pcp_context *ctx, const pcp_crack_link_params *p, int32
   if (out_components) *out_components = 0;
   int rc = crack_link_check(ctx, "pcp_crack_components", p);
   if (rc != PCP_OK) return rc;
-  ctx->cc_live = false;
-  ctx->cc_rows = 0;
-  const int64_t n = ctx->n;
-  if (n == 0) {
-    ctx->cc_live = true;
-    return PCP_OK;
-  }
-  PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t sn = static_cast<size_t>(n);
-  CcScratch s;
-  int64_t m = 0, rows = 0;
-  if ((rc = crack_components_run(ctx, *p, s, &m, &rows)) != PCP_OK) return rc;
-  if (out_label) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_label, s.label.p, sn * 4, hipMemcpyDeviceToHost, ctx->stream));
-  PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (also: the scratch is released on return)
-  drop_large_grid_bitmap(ctx);
-  ctx->cc_rows = rows;
-  ctx->cc_live = true;
-  if (out_crack_points) *out_crack_points = m;
-  if (out_components) *out_components = rows;
+  CrackOut out;
+  out.label = out_label;
+  CrackCounts c;
+  if ((rc = crack_map_run(ctx, *p, CrackMap::kComponents, 0, out, &c)) != PCP_OK) return rc;
+  if (out_crack_points) *out_crack_points = c.points;
+  if (out_components) *out_components = c.cracks;
   return PCP_OK;
 }
 
@@ -572,11 +592,10 @@ int pcp_crack_components_fetch(pcp_context *ctx, int64_t first, int64_t max_rows
                                int64_t *out_rows) {
   if (!ctx) return PCP_ERR_INVALID;
   if (out_rows) *out_rows = 0;
-  if (first < 0 || max_rows < 0) return set_error(ctx, PCP_ERR_INVALID, "pcp_crack_components_fetch: negative first or max_rows");
-  if (!ctx->cf_live || !ctx->cc_live)
-    return set_error(ctx, PCP_ERR_STATE, "pcp_crack_components_fetch: no table (pcp_crack_components on the accumulation as it is)");
-  const int64_t rows = std::max<int64_t>(0, std::min(max_rows, ctx->cc_rows - first));
-  if (rows == 0) return PCP_OK;
+  const CrackMap &cm = *ctx->crack;
+  int64_t rows = 0;
+  const int rc = crack_window(ctx, "pcp_crack_components_fetch", CrackMap::kComponents, first, max_rows, cm.cc_rows, &rows);
+  if (rc != PCP_OK || rows == 0) return rc;
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t sr = static_cast<size_t>(rows), sf = static_cast<size_t>(first);
   std::vector<uint32_t> box;
@@ -585,10 +604,10 @@ int pcp_crack_components_fetch(pcp_context *ctx, int64_t first, int64_t max_rows
   } catch (const std::bad_alloc &) {
     return set_error(ctx, PCP_ERR_NOMEM, "pcp_crack_components_fetch: out of host memory for %lld rows", static_cast<long long>(rows));
   }
-  if (out_id) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_id, ctx->cc_ids.p + sf, sr * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_id) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_id, cm.cc_ids.p + sf, sr * 4, hipMemcpyDeviceToHost, ctx->stream));
   if (out_stats)
-    PCP_HIP_TRY(ctx, hipMemcpyAsync(out_stats, ctx->cc_stats.p + kCcStatWords * sf, kCcStatWords * sr * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (out_box) PCP_HIP_TRY(ctx, hipMemcpyAsync(box.data(), ctx->cc_box.p + 6 * sf, 6 * sr * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PCP_HIP_TRY(ctx, hipMemcpyAsync(out_stats, cm.cc_stats.p + kCcStatWords * sf, kCcStatWords * sr * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_box) PCP_HIP_TRY(ctx, hipMemcpyAsync(box.data(), cm.cc_box.p + 6 * sf, 6 * sr * 4, hipMemcpyDeviceToHost, ctx->stream));
   PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   for (size_t k = 0; k < box.size(); ++k) out_box[k] = cf::value_of(box[k]);
   if (out_rows) *out_rows = rows;

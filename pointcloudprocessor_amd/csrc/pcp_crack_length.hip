@@ -2,7 +2,7 @@
 // pcp_crack_components a geodesic length, its two ends and an ordered polyline through it, per crack point its arc position.
 // The reference's script orders a crack only by a 2-D skeleton per keyframe (scripts/genNormAndDistanceMask.py :396-478).
 //
-// The stage runs the component stage for its parameters (crack_components_run, pcp_crack_fuse.hip) and keeps that call's
+// The stage runs after the component stage for its parameters (crack_map_run, pcp_crack_fuse.hip) on that call's
 // scratch: the crack points in cell order, the grid, the roots and their ranks.  Everything here is indexed by the PLACE of a
 // crack point in the cell order, so that the neighbours a lane visits lie next to each other in every array.
 // Two sweeps (from the label of every crack, then from the farthest point found) are label-correcting relaxations with
@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "pcp_device.hpp"
-#include "pcp_internal.hpp"
+#include "pcp_crack_map.hpp"
 #include "pcp_scan.hpp"
 #include "pcp_crack_length.hpp"
 
@@ -78,27 +78,18 @@ __global__ __launch_bounds__(kClBlock) void k_cl_relax(const float *__restrict__
     const int32_t s = static_cast<int32_t>(s64);
     const unsigned long long ds = cl_load(dist + s);
     const float qx = gx[s], qy = gy[s], qz = gz[s];
-    int32_t ix, iy, iz;
-    grid_coords(g, qx, qy, qz, ix, iy, iz);
-    const int32_t R = g.reach;
-    for (int32_t zz = max(iz - R, 0); zz <= min(iz + R, g.nz - 1); ++zz)
-      for (int32_t yy = max(iy - R, 0); yy <= min(iy + R, g.ny - 1); ++yy) {
-        const int32_t b = max(cell_start(g, start, zz, yy, max(ix - R, 0)), 0);
-        const int32_t e = min(cell_start(g, start, zz, yy, min(ix + R, g.nx - 1) + 1), static_cast<int32_t>(m));
-        for (int32_t c = b; c < e; ++c) {
-          if (c == s) continue;
-          const float d2 = cl::d2_of(gx[c] - qx, gy[c] - qy, gz[c] - qz);
-          if (!(d2 <= t)) continue;
-          const unsigned long long dc = cl_load(dist + c);
-          if (ds + 1 >= dc) continue;  // every weight is at least 1: nothing to lower, and no square root to take
-          const unsigned long long nd = ds + cl::weight(d2);
-          if (nd >= dc) continue;
-          if (atomicMin(dist + c, nd) > nd) {
-            atomicMax(mark + c, round);
-            lowered = true;
-          }
-        }
+    crack_walk<false>(g, start, qx, qy, qz, s, m, [&](int32_t c) {
+      const float d2 = cl::d2_of(gx[c] - qx, gy[c] - qy, gz[c] - qz);
+      if (!(d2 <= t)) return;
+      const unsigned long long dc = cl_load(dist + c);
+      if (ds + 1 >= dc) return;  // every weight is at least 1: nothing to lower, and no square root to take
+      const unsigned long long nd = ds + cl::weight(d2);
+      if (nd >= dc) return;
+      if (atomicMin(dist + c, nd) > nd) {
+        atomicMax(mark + c, round);
+        lowered = true;
       }
+    });
   }
   if (__ballot(lowered) && (threadIdx.x & 63) == 0) atomicMax(fell, round);
 }
@@ -150,25 +141,15 @@ __global__ __launch_bounds__(kClBlock) void k_cl_pred(const float *__restrict__ 
   int32_t best_k = -1, best_place = -1;
   if (ds != 0) {
     const float qx = gx[s], qy = gy[s], qz = gz[s];
-    int32_t ix, iy, iz;
-    grid_coords(g, qx, qy, qz, ix, iy, iz);
-    const int32_t R = g.reach;
-    for (int32_t zz = max(iz - R, 0); zz <= min(iz + R, g.nz - 1); ++zz)
-      for (int32_t yy = max(iy - R, 0); yy <= min(iy + R, g.ny - 1); ++yy) {
-        const int32_t b = max(cell_start(g, start, zz, yy, max(ix - R, 0)), 0);
-        const int32_t e = min(cell_start(g, start, zz, yy, min(ix + R, g.nx - 1) + 1), static_cast<int32_t>(m));
-        for (int32_t c = b; c < e; ++c) {
-          if (c == s) continue;
-          const float d2 = cl::d2_of(gx[c] - qx, gy[c] - qy, gz[c] - qz);
-          if (!(d2 <= t)) continue;
-          if (!cl::pred_ok(dist[c], cl::weight(d2), ds)) continue;
-          const int32_t k = order[c];
-          if (cl::pred_better(k, best_k)) {
-            best_k = k;
-            best_place = c;
-          }
-        }
+    crack_walk<false>(g, start, qx, qy, qz, s, m, [&](int32_t c) {
+      const float d2 = cl::d2_of(gx[c] - qx, gy[c] - qy, gz[c] - qz);
+      if (!(d2 <= t) || !cl::pred_ok(dist[c], cl::weight(d2), ds)) return;
+      const int32_t k = order[c];
+      if (cl::pred_better(k, best_k)) {
+        best_k = k;
+        best_place = c;
       }
+    });
   }
   pred[s] = best_place;
 }
@@ -236,22 +217,6 @@ hipError_t preload_crack_length() {
   return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_cl_relax));
 }
 
-void crack_length_release(pcp_context *ctx) {
-  ctx->cl_live = false;
-  ctx->cl_rows = 0;
-  ctx->cl_entries = 0;
-  ctx->cl_ids.release();
-  ctx->cl_offsets.release();
-  ctx->cl_path.release();
-  ctx->cl_table.release();
-  ctx->cs_live = false;  // CS9
-  ctx->cs_node_rows = ctx->cs_crack_rows = 0;
-  ctx->cs_ids.release();
-  ctx->cs_nodes.release();
-  ctx->cs_cracks.release();
-  std::vector<int64_t>().swap(ctx->cs_edges);
-}
-
 // one sweep from src_place: rounds until nothing falls; *round counts on through both sweeps, so that no mark of the first
 // sweep can be mistaken for one of the second
 static int sweep(pcp_context *ctx, const CcScratch &cc, ClScratch &s, int64_t m, int64_t rows, float t, uint32_t *round) {
@@ -291,12 +256,14 @@ static int sweep(pcp_context *ctx, const CcScratch &cc, ClScratch &s, int64_t m,
   return PCP_OK;
 }
 
-// the m > 0 crack points and rows > 0 cracks the component stage left in cc and ctx->g_*
-static int lengths_run(pcp_context *ctx, const CcScratch &cc, ClScratch &s, float radius, int64_t m, int64_t rows, int64_t *out_entries) {
+// the m > 0 crack points and rows > 0 cracks the component stage left in cc and ctx->g_*; CL5 into s.pos where the caller made it
+int crack_lengths_run(pcp_context *ctx, const pcp_crack_link_params &p, const CcScratch &cc, ClScratch &s, CrackCounts *c) {
+  CrackMap &cm = *ctx->crack;
+  const int64_t m = c->points, rows = c->cracks;
   const size_t sm = static_cast<size_t>(m), sr = static_cast<size_t>(rows);
   const size_t pm = (sm + 3) & ~size_t(3);
   const float *gx = ctx->g_xyz.p, *gy = ctx->g_xyz.p + pm, *gz = ctx->g_xyz.p + 2 * pm;
-  const float t = gn::threshold_of(radius);
+  const float t = gn::threshold_of(p.radius);
   if (2 * static_cast<uint64_t>(m) + 8 > 0xffffffffull) return set_error(ctx, PCP_ERR_INVALID, "pcp_crack_lengths: %lld crack points are too many", (long long)m);
   PCP_HIP_TRY(ctx, s.dist.ensure(sm + 4));
   PCP_HIP_TRY(ctx, s.mark.ensure(sm + 4));
@@ -306,12 +273,12 @@ static int lengths_run(pcp_context *ctx, const CcScratch &cc, ClScratch &s, floa
   PCP_HIP_TRY(ctx, s.pred.ensure(sm + 4));
   PCP_HIP_TRY(ctx, s.far_d.ensure(sr + 4));
   for (DevBuf<int32_t> *b : {&s.src_place, &s.far_k, &s.end_a, &s.end_b}) PCP_HIP_TRY(ctx, b->ensure(sr + 4));
-  PCP_HIP_TRY(ctx, ctx->cl_ids.ensure(sr + 4));
-  PCP_HIP_TRY(ctx, ctx->cl_offsets.ensure(sr + 8));
-  PCP_HIP_TRY(ctx, ctx->cl_table.ensure(static_cast<size_t>(cl::kRowWords) * sr + 4));
+  PCP_HIP_TRY(ctx, cm.cl_ids.ensure(sr + 4));
+  PCP_HIP_TRY(ctx, cm.cl_offsets.ensure(sr + 8));
+  PCP_HIP_TRY(ctx, cm.cl_table.ensure(static_cast<size_t>(cl::kRowWords) * sr + 4));
   PCP_HIP_TRY(ctx, hipMemsetAsync(s.mark.p, 0, sm * 4, ctx->stream));  // round 0: before every round of this call
   PCP_HIP_TRY(ctx, hipMemsetAsync(s.words.p, 0, 16, ctx->stream));
-  PCP_HIP_TRY(ctx, hipMemcpyAsync(ctx->cl_ids.p, ctx->cc_ids.p, sr * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  PCP_HIP_TRY(ctx, hipMemcpyAsync(cm.cl_ids.p, cm.cc_ids.p, sr * 4, hipMemcpyDeviceToDevice, ctx->stream));
   {
     LaunchTimer lt(ctx, PCP_K_MISC);
     hipLaunchKernelGGL(k_cl_rows, dim3(cl_blocks(m)), dim3(kClBlock), 0, ctx->stream, ctx->g_order.p, cc.root_of.p, cc.rank.p, m, s.place_of.p,
@@ -334,45 +301,31 @@ static int lengths_run(pcp_context *ctx, const CcScratch &cc, ClScratch &s, floa
                        s.src_place.p, s.words.p + 1);
     hipLaunchKernelGGL(k_cl_pred, dim3(cl_blocks(m)), dim3(kClBlock), 0, ctx->stream, gx, gy, gz, ctx->g_order.p, m, cc.grid, ctx->g_start.p, t,
                        s.dist.p, s.pred.p);
-    PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->cl_offsets.p, 0, (sr + 8) * 4, ctx->stream));
+    PCP_HIP_TRY(ctx, hipMemsetAsync(cm.cl_offsets.p, 0, (sr + 8) * 4, ctx->stream));
     hipLaunchKernelGGL(k_cl_walk<false>, dim3(cl_blocks(rows)), dim3(kClBlock), 0, ctx->stream, s.end_a.p, s.end_b.p, s.place_of.p, s.pred.p,
-                       ctx->cc_stats.p, rows, m, ctx->cl_offsets.p, nullptr, nullptr, nullptr, ctx->n, nullptr, nullptr, nullptr, nullptr,
+                       cm.cc_stats.p, rows, m, cm.cl_offsets.p, nullptr, nullptr, nullptr, ctx->n, nullptr, nullptr, nullptr, nullptr,
                        s.words.p + 1);
     PCP_HIP_TRY(ctx, hipGetLastError());
-    PCP_HIP_TRY(ctx, scan_exclusive(ctx->stream, ctx->cl_offsets.p, rows + 1, ctx->s_tiles, nullptr));  // [rows] = all entries
+    PCP_HIP_TRY(ctx, scan_exclusive(ctx->stream, cm.cl_offsets.p, rows + 1, ctx->s_tiles, nullptr));  // [rows] = all entries
   }
   int32_t entries = 0;
   uint32_t bad = 0;
-  PCP_HIP_TRY(ctx, hipMemcpyAsync(&entries, ctx->cl_offsets.p + rows, 4, hipMemcpyDeviceToHost, ctx->stream));
+  PCP_HIP_TRY(ctx, hipMemcpyAsync(&entries, cm.cl_offsets.p + rows, 4, hipMemcpyDeviceToHost, ctx->stream));
   PCP_HIP_TRY(ctx, hipMemcpyAsync(&bad, s.words.p + 1, 4, hipMemcpyDeviceToHost, ctx->stream));
   PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (bad || entries < rows || entries > m)
     return set_error(ctx, PCP_ERR_DEVICE, "pcp_crack_lengths: %d path entries for %lld cracks of %lld points (flag %u)", entries, (long long)rows, (long long)m, bad);
-  PCP_HIP_TRY(ctx, ctx->cl_path.ensure(static_cast<size_t>(entries) + 4));
+  PCP_HIP_TRY(ctx, cm.cl_path.ensure(static_cast<size_t>(entries) + 4));
   {
     LaunchTimer lt(ctx, PCP_K_MISC);
     hipLaunchKernelGGL(k_cl_walk<true>, dim3(cl_blocks(rows)), dim3(kClBlock), 0, ctx->stream, s.end_a.p, s.end_b.p, s.place_of.p, s.pred.p,
-                       ctx->cc_stats.p, rows, m, ctx->cl_offsets.p, ctx->g_order.p, cc.list.p, s.dist.p, ctx->n, ctx->cf_u32.p, ctx->cf_u64.p,
-                       ctx->cl_path.p, ctx->cl_table.p, s.words.p + 1);
+                       cm.cc_stats.p, rows, m, cm.cl_offsets.p, ctx->g_order.p, cc.list.p, s.dist.p, ctx->n, cm.cf_u32.p, cm.cf_u64.p,
+                       cm.cl_path.p, cm.cl_table.p, s.words.p + 1);
     if (s.pos.p) hipLaunchKernelGGL(k_cl_pos, dim3(cl_blocks(m)), dim3(kClBlock), 0, ctx->stream, s.dist.p, ctx->g_order.p, cc.list.p, m, s.pos.p);
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
-  *out_entries = entries;
+  c->entries = entries;
   return PCP_OK;
-}
-
-int crack_lengths_run(pcp_context *ctx, const pcp_crack_link_params &p, CcScratch &cc, ClScratch &s, bool with_pos, int64_t *m,
-                      int64_t *rows, int64_t *entries) {
-  const size_t sn = static_cast<size_t>(ctx->n);
-  *m = *rows = *entries = 0;
-  int rc = crack_components_run(ctx, p, cc, m, rows);
-  if (rc != PCP_OK) return rc;
-  if (with_pos) {
-    PCP_HIP_TRY(ctx, s.pos.ensure(sn + 4));
-    PCP_HIP_TRY(ctx, hipMemsetAsync(s.pos.p, 0xff, sn * 8, ctx->stream));  // CL5
-  }
-  if (*m > 0) rc = lengths_run(ctx, cc, s, p.radius, *m, *rows, entries);
-  return rc;
 }
 
 }  // namespace pcp
@@ -387,38 +340,12 @@ int pcp_crack_lengths(pcp_context *ctx, const pcp_crack_link_params *p, uint64_t
   if (out_path_points) *out_path_points = 0;
   int rc = crack_link_check(ctx, "pcp_crack_lengths", p);
   if (rc != PCP_OK) return rc;
-  ctx->cc_live = false;
-  ctx->cc_rows = 0;
-  ctx->cl_live = false;
-  ctx->cl_rows = 0;
-  ctx->cl_entries = 0;
-  ctx->cs_live = false;  // CS9: the skeleton's tables live as long as this table
-  const int64_t n = ctx->n;
-  if (n == 0) {
-    ctx->cc_live = ctx->cl_live = true;
-    return PCP_OK;
-  }
-  PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t sn = static_cast<size_t>(n);
-  CcScratch cc;
-  ClScratch s;
-  int64_t m = 0, rows = 0, entries = 0;
-  rc = crack_lengths_run(ctx, *p, cc, s, out_pos != nullptr, &m, &rows, &entries);
-  if (rc == PCP_OK && out_pos) {
-    const hipError_t e = hipMemcpyAsync(out_pos, s.pos.p, sn * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e != hipSuccess) rc = set_error(ctx, PCP_ERR_DEVICE, "pcp_crack_lengths: the copy of the positions failed: %s", hipGetErrorString(e));
-  }
-  const hipError_t e = hipStreamSynchronize(ctx->stream);  // (also: the scratch is released on return)
-  drop_large_grid_bitmap(ctx);
-  if (rc != PCP_OK) return rc;
-  PCP_HIP_TRY(ctx, e);
-  ctx->cc_rows = rows;
-  ctx->cc_live = true;
-  ctx->cl_rows = rows;
-  ctx->cl_entries = entries;
-  ctx->cl_live = true;
-  if (out_cracks) *out_cracks = rows;
-  if (out_path_points) *out_path_points = entries;
+  CrackOut out;
+  out.pos = out_pos;
+  CrackCounts c;
+  if ((rc = crack_map_run(ctx, *p, CrackMap::kLengths, 0, out, &c)) != PCP_OK) return rc;
+  if (out_cracks) *out_cracks = c.cracks;
+  if (out_path_points) *out_path_points = c.entries;
   return PCP_OK;
 }
 
@@ -426,19 +353,19 @@ int pcp_crack_lengths_fetch(pcp_context *ctx, int64_t first, int64_t max_rows, i
                             int64_t *out_rows) {
   if (!ctx) return PCP_ERR_INVALID;
   if (out_rows) *out_rows = 0;
-  if (first < 0 || max_rows < 0) return set_error(ctx, PCP_ERR_INVALID, "pcp_crack_lengths_fetch: negative first or max_rows");
-  if (!ctx->cf_live || !ctx->cl_live)
-    return set_error(ctx, PCP_ERR_STATE, "pcp_crack_lengths_fetch: no table (pcp_crack_lengths on the accumulation as it is)");
-  const int64_t rows = std::max<int64_t>(0, std::min(max_rows, ctx->cl_rows - first));
+  const CrackMap &cm = *ctx->crack;
+  int64_t rows = 0;
+  const int rc = crack_window(ctx, "pcp_crack_lengths_fetch", CrackMap::kLengths, first, max_rows, cm.cl_rows, &rows);
+  if (rc != PCP_OK) return rc;
   if (rows == 0) {  // no row: entry 0 is still where row `first` starts (the end of the paths from the last row on)
     if (out_offsets) {
       int32_t at = 0;
-      if (first < ctx->cl_rows) {
+      if (first < cm.cl_rows) {
         PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-        PCP_HIP_TRY(ctx, hipMemcpyAsync(&at, ctx->cl_offsets.p + first, 4, hipMemcpyDeviceToHost, ctx->stream));
+        PCP_HIP_TRY(ctx, hipMemcpyAsync(&at, cm.cl_offsets.p + first, 4, hipMemcpyDeviceToHost, ctx->stream));
         PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
       }
-      out_offsets[0] = first < ctx->cl_rows ? at : ctx->cl_entries;
+      out_offsets[0] = first < cm.cl_rows ? at : cm.cl_entries;
     }
     return PCP_OK;
   }
@@ -450,10 +377,10 @@ int pcp_crack_lengths_fetch(pcp_context *ctx, int64_t first, int64_t max_rows, i
   } catch (const std::bad_alloc &) {
     return set_error(ctx, PCP_ERR_NOMEM, "pcp_crack_lengths_fetch: out of host memory for %lld rows", static_cast<long long>(rows));
   }
-  if (out_id) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_id, ctx->cl_ids.p + sf, sr * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_id) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_id, cm.cl_ids.p + sf, sr * 4, hipMemcpyDeviceToHost, ctx->stream));
   if (out_rows7)
-    PCP_HIP_TRY(ctx, hipMemcpyAsync(out_rows7, ctx->cl_table.p + cl::kRowWords * sf, cl::kRowWords * sr * 8, hipMemcpyDeviceToHost, ctx->stream));
-  if (out_offsets) PCP_HIP_TRY(ctx, hipMemcpyAsync(off.data(), ctx->cl_offsets.p + sf, (sr + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PCP_HIP_TRY(ctx, hipMemcpyAsync(out_rows7, cm.cl_table.p + cl::kRowWords * sf, cl::kRowWords * sr * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_offsets) PCP_HIP_TRY(ctx, hipMemcpyAsync(off.data(), cm.cl_offsets.p + sf, (sr + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
   PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   for (size_t k = 0; k < off.size(); ++k) out_offsets[k] = off[k];
   if (out_rows) *out_rows = rows;
@@ -463,14 +390,13 @@ int pcp_crack_lengths_fetch(pcp_context *ctx, int64_t first, int64_t max_rows, i
 int pcp_crack_paths_fetch(pcp_context *ctx, int64_t first_entry, int64_t max_entries, int32_t *out_index, int64_t *out_entries) {
   if (!ctx) return PCP_ERR_INVALID;
   if (out_entries) *out_entries = 0;
-  if (first_entry < 0 || max_entries < 0) return set_error(ctx, PCP_ERR_INVALID, "pcp_crack_paths_fetch: negative first_entry or max_entries");
-  if (!ctx->cf_live || !ctx->cl_live)
-    return set_error(ctx, PCP_ERR_STATE, "pcp_crack_paths_fetch: no paths (pcp_crack_lengths on the accumulation as it is)");
-  const int64_t entries = std::max<int64_t>(0, std::min(max_entries, ctx->cl_entries - first_entry));
-  if (entries == 0) return PCP_OK;
+  const CrackMap &cm = *ctx->crack;
+  int64_t entries = 0;
+  const int rc = crack_window(ctx, "pcp_crack_paths_fetch", CrackMap::kLengths, first_entry, max_entries, cm.cl_entries, &entries);
+  if (rc != PCP_OK || entries == 0) return rc;
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (out_index)
-    PCP_HIP_TRY(ctx, hipMemcpyAsync(out_index, ctx->cl_path.p + first_entry, static_cast<size_t>(entries) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PCP_HIP_TRY(ctx, hipMemcpyAsync(out_index, cm.cl_path.p + first_entry, static_cast<size_t>(entries) * 4, hipMemcpyDeviceToHost, ctx->stream));
   PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (out_entries) *out_entries = entries;
   return PCP_OK;

@@ -3,7 +3,7 @@
 // loops.  The reference's script gets as far as a 2-D skeleton per keyframe (pcv.morphology.skeletonize in preprocess() of
 // scripts/genNormAndDistanceMask.py).
 //
-// The stage runs the length stage for its parameters (crack_lengths_run, pcp_crack_length.hip) and keeps that call's scratch:
+// The stage runs after the length stage for its parameters (crack_map_run, pcp_crack_fuse.hip) on that call's scratch:
 // D_a, the crack's row and the grid, all indexed by the PLACE of a crack point in the cell order.  A band kernel cuts the
 // cracks at equal steps of D_a; the component stage's union walk, restricted to links inside a band, makes the nodes
 // (flatten, scan, ids as there); a statistics kernel fills one row per node with integer atomics, merged per wavefront where
@@ -18,7 +18,7 @@
 #include <vector>
 
 #include "pcp_device.hpp"
-#include "pcp_internal.hpp"
+#include "pcp_crack_map.hpp"
 #include "pcp_scan.hpp"
 #include "pcp_crack_skeleton.hpp"
 
@@ -59,27 +59,9 @@ __global__ __launch_bounds__(kCsBlock) void k_cs_union(const float *__restrict__
   const int32_t s = static_cast<int32_t>(s64);
   const float qx = gx[s], qy = gy[s], qz = gz[s];
   const int32_t mine = order[s], my_band = band[s];
-  int32_t ix, iy, iz;
-  grid_coords(g, qx, qy, qz, ix, iy, iz);
-  const int32_t R = g.reach;
-  for (int32_t zz = max(iz - R, 0); zz <= min(iz + R, g.nz - 1); ++zz)
-    for (int32_t yy = max(iy - R, 0); yy <= min(iy + R, g.ny - 1); ++yy) {
-      const int32_t b = cell_start(g, start, zz, yy, max(ix - R, 0));
-      const int32_t e = min(cell_start(g, start, zz, yy, min(ix + R, g.nx - 1) + 1), static_cast<int32_t>(m));
-      for (int32_t c = max(b, s + 1); c < e; ++c)
-        if (band[c] == my_band && cf::linked(gx[c] - qx, gy[c] - qy, gz[c] - qz, t)) cc_unite(parent, mine, order[c]);
-    }
-}
-
-// after the union kernel has ended the forest is final; the walk goes down strictly descending indices
-__global__ __launch_bounds__(kCsBlock) void k_cs_flatten(const int32_t *__restrict__ parent, int64_t m, int32_t *__restrict__ root_of,
-                                                         int32_t *__restrict__ is_root) {
-  const int64_t k = static_cast<int64_t>(blockIdx.x) * kCsBlock + threadIdx.x;
-  if (k >= m) return;
-  int32_t v = static_cast<int32_t>(k);
-  for (int32_t p = parent[v]; p != v; p = parent[v]) v = p;  // (p < v)
-  root_of[k] = v;
-  is_root[k] = v == static_cast<int32_t>(k) ? 1 : 0;
+  crack_walk<true>(g, start, qx, qy, qz, s, m, [&](int32_t c) {
+    if (band[c] == my_band && cl::d2_of(gx[c] - qx, gy[c] - qy, gz[c] - qz) <= t) cc_unite(parent, mine, order[c]);
+  });
 }
 
 // one lane per view index k (rank[k] = roots before k: the rows ascend by id because the list does): the row of k's node by
@@ -128,12 +110,8 @@ __global__ __launch_bounds__(kCsBlock) void k_cs_nodes(const float *__restrict__
     sy = static_cast<unsigned long long>(cs::quant(gy[s]));
     sz = static_cast<unsigned long long>(cs::quant(gz[s]));
   }
-  const unsigned long long live = __ballot(valid);
-  if (live == 0) return;
-  const int leader = __ffsll(static_cast<long long>(live)) - 1;
-  const int32_t row0 = __shfl(row, leader, 64);
-  const bool shared = __ballot(valid && row == row0) == live;  // (the same for every lane of the wavefront)
-  bool issue = valid;
+  bool shared;
+  const bool issue = wave_row_issuer(valid, row, &shared);
   if (shared) {
     points = wave_sum_u64(points);
     sum_w = wave_sum_u64(sum_w);
@@ -142,7 +120,6 @@ __global__ __launch_bounds__(kCsBlock) void k_cs_nodes(const float *__restrict__
     sz = wave_sum_u64(sz);
     min_w = wave_min_u32(min_w);
     max_w = wave_max_u32(max_w);
-    issue = static_cast<int>(threadIdx.x & 63) == leader;
   }
   if (!issue) return;
   unsigned long long *st = table + static_cast<int64_t>(cs::kNodeWords) * row;
@@ -209,31 +186,23 @@ __global__ __launch_bounds__(kCsBlock) void k_cs_edges(const float *__restrict__
   const int32_t my_node = node_row[s], my_band = band[s];
   uint64_t last = cs::kNoKey;
   uint32_t hits = 0;
-  int32_t ix, iy, iz;
-  grid_coords(g, qx, qy, qz, ix, iy, iz);
-  const int32_t R = g.reach;
-  for (int32_t zz = max(iz - R, 0); zz <= min(iz + R, g.nz - 1); ++zz)
-    for (int32_t yy = max(iy - R, 0); yy <= min(iy + R, g.ny - 1); ++yy) {
-      const int32_t b = cell_start(g, start, zz, yy, max(ix - R, 0));
-      const int32_t e = min(cell_start(g, start, zz, yy, min(ix + R, g.nx - 1) + 1), static_cast<int32_t>(m));
-      for (int32_t c = max(b, s + 1); c < e; ++c) {
-        const int32_t other = node_row[c];
-        if (other == my_node || !cf::linked(gx[c] - qx, gy[c] - qy, gz[c] - qz, t)) continue;
-        const int32_t its_band = band[c];
-        if (its_band != my_band + 1 && my_band != its_band + 1) {  // (cannot be: CS2)
-          atomicMax(words + CS_BAD, 1u);
-          continue;
-        }
-        const uint64_t key = my_band < its_band ? cs::edge_key(my_node, other) : cs::edge_key(other, my_node);
-        if (key == last) {
-          ++hits;
-          continue;
-        }
-        if (hits) cs_add(keys, links, mask, last, hits, words);
-        last = key;
-        hits = 1;
-      }
+  crack_walk<true>(g, start, qx, qy, qz, s, m, [&](int32_t c) {
+    const int32_t other = node_row[c];
+    if (other == my_node || !(cl::d2_of(gx[c] - qx, gy[c] - qy, gz[c] - qz) <= t)) return;
+    const int32_t its_band = band[c];
+    if (its_band != my_band + 1 && my_band != its_band + 1) {  // (cannot be: CS2)
+      atomicMax(words + CS_BAD, 1u);
+      return;
     }
+    const uint64_t key = my_band < its_band ? cs::edge_key(my_node, other) : cs::edge_key(other, my_node);
+    if (key == last) {
+      ++hits;
+      return;
+    }
+    if (hits) cs_add(keys, links, mask, last, hits, words);
+    last = key;
+    hits = 1;
+  });
   if (hits) cs_add(keys, links, mask, last, hits, words);
 }
 
@@ -307,13 +276,6 @@ hipError_t preload_crack_skeleton() {
   return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_cs_edges));
 }
 
-// per-call scratch of pcp_crack_skeleton beside the two stages' it runs
-struct CsScratch {
-  DevBuf<int32_t> band, parent, root_of, rank, node_row, node;
-  DevBuf<unsigned long long> keys, edges;
-  DevBuf<uint32_t> links, words;
-};
-
 // a compacted slot of the edge set, as k_cs_compact writes it
 struct CsRec {
   unsigned long long key, links;
@@ -329,19 +291,26 @@ static int64_t first_slots(int64_t node_rows) {
 }
 
 // the m > 0 crack points and rows > 0 cracks the length stage left in cc, cl and ctx->g_*
-static int skeleton_run(pcp_context *ctx, const CcScratch &cc, const ClScratch &cl, CsScratch &s, float radius, uint64_t step_q, int64_t m,
-                        int64_t rows, int64_t *out_nodes, int64_t *out_edges) {
+int crack_skeleton_run(pcp_context *ctx, const pcp_crack_link_params &p, uint64_t step_q, const CcScratch &cc, const ClScratch &cl, CsScratch &s,
+                       CrackCounts *c) {
+  CrackMap &cm = *ctx->crack;
+  const int64_t m = c->points, rows = c->cracks;
+  float largest = 0.0f;
+  for (int a = 0; a < 3; ++a) largest = std::max(largest, std::max(fabsf(cc.lo[a]), fabsf(cc.hi[a])));
+  if (!cs::coord_ok(largest) || !cs::sums_fit(m, largest))  // CS4
+    return set_error(ctx, PCP_ERR_RANGE, "pcp_crack_skeleton: a crack point has a coordinate of %g m (beyond 2^20 m, or too large for exact sums over %lld points)",
+                     static_cast<double>(largest), (long long)m);
   const size_t sm = static_cast<size_t>(m), sr = static_cast<size_t>(rows);
   const size_t pm = (sm + 3) & ~size_t(3);
   const float *gx = ctx->g_xyz.p, *gy = ctx->g_xyz.p + pm, *gz = ctx->g_xyz.p + 2 * pm;
-  const float t = gn::threshold_of(radius);
+  const float t = gn::threshold_of(p.radius);
   for (DevBuf<int32_t> *b : {&s.band, &s.parent, &s.root_of, &s.node_row}) PCP_HIP_TRY(ctx, b->ensure(sm + 4));
   PCP_HIP_TRY(ctx, s.rank.ensure(sm + 8));
   PCP_HIP_TRY(ctx, s.words.ensure(CS_WORDS));
-  PCP_HIP_TRY(ctx, ctx->cs_cracks.ensure(static_cast<size_t>(cs::kCrackWords) * sr + 4));
+  PCP_HIP_TRY(ctx, cm.cs_cracks.ensure(static_cast<size_t>(cs::kCrackWords) * sr + 4));
   PCP_HIP_TRY(ctx, hipMemsetAsync(s.rank.p, 0, (sm + 8) * 4, ctx->stream));
   PCP_HIP_TRY(ctx, hipMemsetAsync(s.words.p, 0, CS_WORDS * 4, ctx->stream));
-  PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->cs_cracks.p, 0, cs::kCrackWords * sr * 8, ctx->stream));
+  PCP_HIP_TRY(ctx, hipMemsetAsync(cm.cs_cracks.p, 0, cs::kCrackWords * sr * 8, ctx->stream));
   {
     LaunchTimer lt(ctx, PCP_K_MISC);
     hipLaunchKernelGGL(k_cs_band, dim3(cs_blocks(m)), dim3(kCsBlock), 0, ctx->stream, cl.dist.p, m, static_cast<unsigned long long>(step_q),
@@ -354,29 +323,22 @@ static int skeleton_run(pcp_context *ctx, const CcScratch &cc, const ClScratch &
                        ctx->g_start.p, t, s.parent.p);
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
-  {
-    LaunchTimer lt(ctx, PCP_K_MISC);
-    hipLaunchKernelGGL(k_cs_flatten, dim3(cs_blocks(m)), dim3(kCsBlock), 0, ctx->stream, s.parent.p, m, s.root_of.p, s.rank.p);
-    PCP_HIP_TRY(ctx, scan_exclusive(ctx->stream, s.rank.p, m + 1, ctx->s_tiles, nullptr));  // [m] = the number of roots
-  }
-  int32_t roots = 0;
-  PCP_HIP_TRY(ctx, hipMemcpyAsync(&roots, s.rank.p + m, 4, hipMemcpyDeviceToHost, ctx->stream));
-  PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  const int64_t nodes = roots;
-  if (nodes < rows || nodes > m) return set_error(ctx, PCP_ERR_DEVICE, "pcp_crack_skeleton: %lld nodes for %lld cracks of %lld points", (long long)nodes, (long long)rows, (long long)m);
+  int64_t nodes = 0;
+  int rc = crack_label_forest(ctx, "pcp_crack_skeleton", "nodes", s.parent.p, nullptr, m, rows, s.root_of.p, s.rank.p, nullptr, &nodes);
+  if (rc != PCP_OK) return rc;
   const size_t sk = static_cast<size_t>(nodes);
-  PCP_HIP_TRY(ctx, ctx->cs_ids.ensure(sk + 4));
-  PCP_HIP_TRY(ctx, ctx->cs_nodes.ensure(static_cast<size_t>(cs::kNodeWords) * sk + 4));
+  PCP_HIP_TRY(ctx, cm.cs_ids.ensure(sk + 4));
+  PCP_HIP_TRY(ctx, cm.cs_nodes.ensure(static_cast<size_t>(cs::kNodeWords) * sk + 4));
   {
     LaunchTimer lt(ctx, PCP_K_MISC);
     hipLaunchKernelGGL(k_cs_ids, dim3(cs_blocks(m)), dim3(kCsBlock), 0, ctx->stream, s.root_of.p, s.rank.p, cc.list.p, cl.place_of.p, cl.row_of.p,
-                       s.band.p, m, s.node_row.p, s.node.p, ctx->cs_ids.p, ctx->cs_nodes.p);
+                       s.band.p, m, s.node_row.p, s.node.p, cm.cs_ids.p, cm.cs_nodes.p);
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
   {
     LaunchTimer lt(ctx, PCP_K_MISC);
     hipLaunchKernelGGL(k_cs_nodes, dim3(cs_blocks(m)), dim3(kCsBlock), 0, ctx->stream, gx, gy, gz, ctx->g_order.p, m, s.node_row.p, cc.list.p,
-                       ctx->n, ctx->cf_u32.p, ctx->cf_u64.p, ctx->cs_nodes.p);
+                       ctx->n, cm.cf_u32.p, cm.cf_u64.p, cm.cs_nodes.p);
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
   // CS8: the edge walk on a set sized from the nodes; a full set is doubled and the walk run again
@@ -411,7 +373,7 @@ static int skeleton_run(pcp_context *ctx, const CcScratch &cc, const ClScratch &
   std::vector<CsRec> rec;
   try {
     rec.resize(static_cast<size_t>(edges));
-    ctx->cs_edges.resize(static_cast<size_t>(cs::kEdgeWords) * static_cast<size_t>(edges));
+    cm.cs_edges.resize(static_cast<size_t>(cs::kEdgeWords) * static_cast<size_t>(edges));
   } catch (const std::bad_alloc &) {
     return set_error(ctx, PCP_ERR_NOMEM, "pcp_crack_skeleton: out of host memory for %lld edges", (long long)edges);
   }
@@ -421,12 +383,12 @@ static int skeleton_run(pcp_context *ctx, const CcScratch &cc, const ClScratch &
     if (edges > 0) {
       hipLaunchKernelGGL(k_cs_compact, dim3(cs_blocks(slots)), dim3(kCsBlock), 0, ctx->stream, s.keys.p, s.links.p, slots, edges, s.edges.p,
                          s.words.p);
-      hipLaunchKernelGGL(k_cs_degree, dim3(cs_blocks(edges)), dim3(kCsBlock), 0, ctx->stream, s.edges.p, edges, nodes, rows, ctx->cs_nodes.p,
-                         ctx->cs_cracks.p, s.words.p);
+      hipLaunchKernelGGL(k_cs_degree, dim3(cs_blocks(edges)), dim3(kCsBlock), 0, ctx->stream, s.edges.p, edges, nodes, rows, cm.cs_nodes.p,
+                         cm.cs_cracks.p, s.words.p);
     }
-    hipLaunchKernelGGL(k_cs_summary, dim3(cs_blocks(nodes)), dim3(kCsBlock), 0, ctx->stream, ctx->cs_nodes.p, nodes, rows, ctx->cs_cracks.p,
+    hipLaunchKernelGGL(k_cs_summary, dim3(cs_blocks(nodes)), dim3(kCsBlock), 0, ctx->stream, cm.cs_nodes.p, nodes, rows, cm.cs_cracks.p,
                        s.words.p);
-    hipLaunchKernelGGL(k_cs_loops, dim3(cs_blocks(rows)), dim3(kCsBlock), 0, ctx->stream, ctx->cs_cracks.p, rows, s.words.p);
+    hipLaunchKernelGGL(k_cs_loops, dim3(cs_blocks(rows)), dim3(kCsBlock), 0, ctx->stream, cm.cs_cracks.p, rows, s.words.p);
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
   if (edges > 0) PCP_HIP_TRY(ctx, hipMemcpyAsync(rec.data(), s.edges.p, 16 * static_cast<size_t>(edges), hipMemcpyDeviceToHost, ctx->stream));
@@ -438,12 +400,12 @@ static int skeleton_run(pcp_context *ctx, const CcScratch &cc, const ClScratch &
   // CS5: the rows ascend by (u, v) -- the keys order as the pairs do, and they are unique
   std::sort(rec.begin(), rec.end(), [](const CsRec &a, const CsRec &b) { return a.key < b.key; });
   for (size_t e = 0; e < rec.size(); ++e) {
-    ctx->cs_edges[3 * e] = cs::key_u(rec[e].key);
-    ctx->cs_edges[3 * e + 1] = cs::key_v(rec[e].key);
-    ctx->cs_edges[3 * e + 2] = static_cast<int64_t>(rec[e].links);
+    cm.cs_edges[3 * e] = cs::key_u(rec[e].key);
+    cm.cs_edges[3 * e + 1] = cs::key_v(rec[e].key);
+    cm.cs_edges[3 * e + 2] = static_cast<int64_t>(rec[e].links);
   }
-  *out_nodes = nodes;
-  *out_edges = edges;
+  c->nodes = nodes;
+  c->edges = edges;
   return PCP_OK;
 }
 
@@ -463,68 +425,12 @@ int pcp_crack_skeleton(pcp_context *ctx, const pcp_crack_link_params *p, float s
   if (!cs::step_ok(step, t))
     return set_error(ctx, PCP_ERR_INVALID, "pcp_crack_skeleton: step %g outside [%g, 16] (the longest link of radius %g)", static_cast<double>(step),
                      static_cast<double>(cs::w_max_of(t)) * cl::kMetresPerUnit, static_cast<double>(p->radius));
-  const uint64_t step_q = cs::step_q_of(step);
-  ctx->cc_live = false;
-  ctx->cc_rows = 0;
-  ctx->cl_live = false;
-  ctx->cl_rows = 0;
-  ctx->cl_entries = 0;
-  ctx->cs_live = false;
-  ctx->cs_node_rows = ctx->cs_crack_rows = 0;
-  ctx->cs_edges.clear();
-  const int64_t n = ctx->n;
-  if (n == 0) {
-    ctx->cc_live = ctx->cl_live = ctx->cs_live = true;
-    return PCP_OK;
-  }
-  PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t sn = static_cast<size_t>(n);
-  CcScratch cc;
-  ClScratch cl;
-  CsScratch s;
-  int64_t m = 0, rows = 0, entries = 0, nodes = 0, edges = 0;
-  rc = crack_lengths_run(ctx, *p, cc, cl, false, &m, &rows, &entries);
-  if (rc == PCP_OK && out_node) {
-    hipError_t e = s.node.ensure(sn + 4);
-    if (e == hipSuccess) e = hipMemsetAsync(s.node.p, 0xff, sn * 4, ctx->stream);  // CS3: -1 for a point that is no crack point
-    if (e != hipSuccess) rc = set_error(ctx, e == hipErrorOutOfMemory ? PCP_ERR_NOMEM : PCP_ERR_DEVICE, "pcp_crack_skeleton: the node array: %s", hipGetErrorString(e));
-  }
-  if (rc == PCP_OK && m > 0) {
-    float largest = 0.0f;
-    for (int a = 0; a < 3; ++a) largest = std::max(largest, std::max(fabsf(cc.lo[a]), fabsf(cc.hi[a])));
-    if (!cs::coord_ok(largest) || !cs::sums_fit(m, largest))  // CS4
-      rc = set_error(ctx, PCP_ERR_RANGE, "pcp_crack_skeleton: a crack point has a coordinate of %g m (beyond 2^20 m, or too large for exact sums over %lld points)",
-                     static_cast<double>(largest), (long long)m);
-    else
-      rc = skeleton_run(ctx, cc, cl, s, p->radius, step_q, m, rows, &nodes, &edges);
-  }
-  if (rc == PCP_OK && out_node) {
-    const hipError_t e = hipMemcpyAsync(out_node, s.node.p, sn * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e != hipSuccess) rc = set_error(ctx, PCP_ERR_DEVICE, "pcp_crack_skeleton: the copy of the nodes failed: %s", hipGetErrorString(e));
-  }
-  const hipError_t e = hipStreamSynchronize(ctx->stream);  // (also: the scratch is released on return)
-  drop_large_grid_bitmap(ctx);
-  if (rc != PCP_OK) return rc;
-  PCP_HIP_TRY(ctx, e);
-  ctx->cc_rows = rows;
-  ctx->cc_live = true;
-  ctx->cl_rows = rows;
-  ctx->cl_entries = entries;
-  ctx->cl_live = true;
-  ctx->cs_node_rows = nodes;
-  ctx->cs_crack_rows = rows;
-  ctx->cs_live = true;
-  if (out_nodes) *out_nodes = nodes;
-  if (out_edges) *out_edges = edges;
-  return PCP_OK;
-}
-
-// the window [first, first + max_rows) of a table of `have` rows, after the checks the three fetches share
-static int cs_window(pcp_context *ctx, const char *who, int64_t first, int64_t max_rows, int64_t have, int64_t *rows) {
-  if (first < 0 || max_rows < 0) return set_error(ctx, PCP_ERR_INVALID, "%s: negative first or max_rows", who);
-  if (!ctx->cf_live || !ctx->cl_live || !ctx->cs_live)
-    return set_error(ctx, PCP_ERR_STATE, "%s: no table (pcp_crack_skeleton on the accumulation as it is)", who);
-  *rows = std::max<int64_t>(0, std::min(max_rows, have - first));
+  CrackOut out;
+  out.node = out_node;
+  CrackCounts c;
+  if ((rc = crack_map_run(ctx, *p, CrackMap::kSkeleton, cs::step_q_of(step), out, &c)) != PCP_OK) return rc;
+  if (out_nodes) *out_nodes = c.nodes;
+  if (out_edges) *out_edges = c.edges;
   return PCP_OK;
 }
 
@@ -532,13 +438,13 @@ int pcp_crack_skeleton_nodes_fetch(pcp_context *ctx, int64_t first, int64_t max_
   if (!ctx) return PCP_ERR_INVALID;
   if (out_rows) *out_rows = 0;
   int64_t rows = 0;
-  const int rc = cs_window(ctx, "pcp_crack_skeleton_nodes_fetch", first, max_rows, ctx->cs_node_rows, &rows);
+  const int rc = crack_window(ctx, "pcp_crack_skeleton_nodes_fetch", CrackMap::kSkeleton, first, max_rows, ctx->crack->cs_node_rows, &rows);
   if (rc != PCP_OK || rows == 0) return rc;
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t sr = static_cast<size_t>(rows), sf = static_cast<size_t>(first);
-  if (out_id) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_id, ctx->cs_ids.p + sf, sr * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_id) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_id, ctx->crack->cs_ids.p + sf, sr * 4, hipMemcpyDeviceToHost, ctx->stream));
   if (out_rows10)
-    PCP_HIP_TRY(ctx, hipMemcpyAsync(out_rows10, ctx->cs_nodes.p + cs::kNodeWords * sf, cs::kNodeWords * sr * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PCP_HIP_TRY(ctx, hipMemcpyAsync(out_rows10, ctx->crack->cs_nodes.p + cs::kNodeWords * sf, cs::kNodeWords * sr * 8, hipMemcpyDeviceToHost, ctx->stream));
   PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (out_rows) *out_rows = rows;
   return PCP_OK;
@@ -548,9 +454,9 @@ int pcp_crack_skeleton_edges_fetch(pcp_context *ctx, int64_t first, int64_t max_
   if (!ctx) return PCP_ERR_INVALID;
   if (out_rows) *out_rows = 0;
   int64_t rows = 0;
-  const int rc = cs_window(ctx, "pcp_crack_skeleton_edges_fetch", first, max_rows, static_cast<int64_t>(ctx->cs_edges.size() / cs::kEdgeWords), &rows);
+  const int rc = crack_window(ctx, "pcp_crack_skeleton_edges_fetch", CrackMap::kSkeleton, first, max_rows, static_cast<int64_t>(ctx->crack->cs_edges.size() / cs::kEdgeWords), &rows);
   if (rc != PCP_OK || rows == 0) return rc;
-  if (out_rows3) std::copy(ctx->cs_edges.begin() + cs::kEdgeWords * first, ctx->cs_edges.begin() + cs::kEdgeWords * (first + rows), out_rows3);
+  if (out_rows3) std::copy(ctx->crack->cs_edges.begin() + cs::kEdgeWords * first, ctx->crack->cs_edges.begin() + cs::kEdgeWords * (first + rows), out_rows3);
   if (out_rows) *out_rows = rows;
   return PCP_OK;
 }
@@ -559,12 +465,12 @@ int pcp_crack_skeleton_cracks_fetch(pcp_context *ctx, int64_t first, int64_t max
   if (!ctx) return PCP_ERR_INVALID;
   if (out_rows) *out_rows = 0;
   int64_t rows = 0;
-  const int rc = cs_window(ctx, "pcp_crack_skeleton_cracks_fetch", first, max_rows, ctx->cs_crack_rows, &rows);
+  const int rc = crack_window(ctx, "pcp_crack_skeleton_cracks_fetch", CrackMap::kSkeleton, first, max_rows, ctx->crack->cs_crack_rows, &rows);
   if (rc != PCP_OK || rows == 0) return rc;
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t sr = static_cast<size_t>(rows), sf = static_cast<size_t>(first);
   if (out_rows6)
-    PCP_HIP_TRY(ctx, hipMemcpyAsync(out_rows6, ctx->cs_cracks.p + cs::kCrackWords * sf, cs::kCrackWords * sr * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PCP_HIP_TRY(ctx, hipMemcpyAsync(out_rows6, ctx->crack->cs_cracks.p + cs::kCrackWords * sf, cs::kCrackWords * sr * 8, hipMemcpyDeviceToHost, ctx->stream));
   PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (out_rows) *out_rows = rows;
   return PCP_OK;

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "pcp_internal.hpp"
+#include "pcp_crack_map.hpp"
 #include "pcp_eigen33.hpp"
 #include "pcp_crack_width.hpp"
 

@@ -9,6 +9,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <type_traits>
 #include <utility>
@@ -193,6 +194,8 @@ struct VoxelReduce {
   DevBuf<uint32_t> out_count;
 };
 
+struct CrackMap;  // (the crack chain's header)
+
 }  // namespace pcp
 
 struct pcp_context {
@@ -318,7 +321,7 @@ struct pcp_context {
   pcp::DevBuf<uint32_t> md_col, md_d2;
   pcp::DevBuf<int32_t> md_nearest;
 
-  // crack width maps (pcp_crack_width.hip), allocated on first use: the ten summed-area planes of the origin moments
+  // crack width maps (the per-keyframe width unit), allocated on first use: the ten summed-area planes of the origin moments
   // (modulo 2^64) with the column stage's segment sums behind them, and the outputs a call asked for
   pcp::DevBuf<unsigned long long> cw_sat;
   pcp::DevBuf<uint8_t> cw_flags;
@@ -326,33 +329,9 @@ struct pcp_context {
   pcp::DevBuf<float> cw_f32;       // plane (4 per pixel) | width | points (6 per pixel)
   pcp::DevBuf<long long> cw_moments;  // 13 per pixel
 
-  // crack widths on the map (pcp_crack_fuse.hip): the accumulation between pcp_crack_fuse_begin and _end, SoA planes of n in
-  // input order -- seen | views | centres | min_q | max_q | best_q and sum_q | best_key -- with the keyframes added so far;
-  // dropped by the uploads, pcp_set_camera and pcp_set_frames.  The table of the last pcp_crack_components (ids, 5 integers
-  // and the box as ordered integers per crack) lives until the accumulation changes or ends.
-  bool cf_live = false;
-  pcp::DevBuf<uint32_t> cf_u32;
-  pcp::DevBuf<unsigned long long> cf_u64;
-  std::vector<uint8_t> cf_added;
-  bool cc_live = false;
-  int64_t cc_rows = 0;
-  pcp::DevBuf<int32_t> cc_ids;
-  pcp::DevBuf<unsigned long long> cc_stats;
-  pcp::DevBuf<uint32_t> cc_box;
-  // crack lengths on the map (pcp_crack_length.hip): the table (7 integers per crack), its ids, the path offsets (rows + 1)
-  // and the paths of the last pcp_crack_lengths; they live as long as cc's table does
-  bool cl_live = false;
-  int64_t cl_rows = 0, cl_entries = 0;
-  pcp::DevBuf<int32_t> cl_ids, cl_offsets, cl_path;
-  pcp::DevBuf<long long> cl_table;
-  // crack skeletons on the map (pcp_crack_skeleton.hip): the node table (10 integers per node) and its ids, the summary (6
-  // integers per crack) and, on the host and ordered, the edges (3 integers each) of the last pcp_crack_skeleton; they live
-  // as long as cl's table does
-  bool cs_live = false;
-  int64_t cs_node_rows = 0, cs_crack_rows = 0;
-  pcp::DevBuf<int32_t> cs_ids;
-  pcp::DevBuf<unsigned long long> cs_nodes, cs_cracks;
-  std::vector<int64_t> cs_edges;
+  // the crack chain on the map -- the fused widths and the tables of the cracks' components, lengths and skeletons -- with its
+  // lifetime rules: pcp::CrackMap, defined in the chain's own header and allocated by pcp_create
+  std::unique_ptr<pcp::CrackMap> crack;
 
   // PCP_MATCH_RADIUS (pcp_match.hip): the neighbour table within R_c, built by the first colour pass in that mode and
   // dropped by pcp_upload_cloud / pcp_set_frames (E depends on both).  Set A = points whose row holds another point.
@@ -621,65 +600,11 @@ hipError_t preload_exposure();
 hipError_t preload_voxel_reduce();
 hipError_t preload_normals();
 hipError_t preload_mask_edt();
-hipError_t preload_crack_width();
-hipError_t preload_crack_fuse();
 // the device parts of pcp_mask_edt (one keyframe, with nearest) and pcp_frame_geometry under the caller's name: checks and
 // kernels, the results left in md_bits / md_d2 / md_nearest and gm_out / s_counter[0]; no copy, no synchronisation
 int mask_edt_device(pcp_context *ctx, const char *who, int32_t frame, int32_t threshold);
 // (*out_contributors, nullable: the length of the keyframe's list, which frame_contributors left in ctx->s_cell)
 int frame_geometry_device(pcp_context *ctx, const char *who, int32_t frame, bool with_normals, int64_t *out_contributors = nullptr);
-// the device part of pcp_crack_width after those two (pcp_crack_width.hip), and the checks of its arguments
-struct CrackWidthWant {
-  bool flags, edges, w2d2, width, points, plane, moments;
-};
-int crack_width_check(pcp_context *ctx, const char *who, const pcp_crack_params *params);
-int crack_width_device(pcp_context *ctx, const pcp_crack_params &prm, const CrackWidthWant &want);
-// a row of pcp_crack_components' table (ctx->cc_stats): points sum_w min_w max_w centre_points
-constexpr int kCcStatWords = 5;
-// per-call scratch of the component stage (pcp_crack_fuse.hip), released when the call that owns it returns: the crack points
-// (view index k = input point list[k], ascending), label (n, input order), root_of (view index of k's root), rank (roots
-// before view index k: rank[root_of[k]] is k's row of the table) and the grid the stage left in ctx->g_*
-struct CcScratch {
-  DevBuf<uint8_t> flag;
-  DevBuf<int32_t> list, label, parent, root_of, rank;
-  DevBuf<float> vxyz;
-  DevBuf<uint32_t> box;
-  GridDesc grid;
-  float lo[3], hi[3];  // the box of the crack points as the grid took it (m > 0)
-};
-// CC5.  parent[v] <= v always and parent words only ever decrease: a root is the lowest index of its tree.  The words are
-// read with relaxed atomic loads at agent scope and written by compare-and-swap only (the L2s of the XCDs are not coherent
-// for plain stores).
-__device__ __forceinline__ int32_t cc_load(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the root of v, halving the path on the way: parent[v]: p -> parent[p] only while it still is p.  v strictly decreases from
-// one round to the next (parent[p] < p < v), so the loop ends after at most v rounds.
-__device__ __forceinline__ int32_t cc_find(int32_t *parent, int32_t v) {
-  for (;;) {
-    const int32_t p = cc_load(parent + v);
-    if (p == v) return v;
-    const int32_t gp = cc_load(parent + p);
-    if (gp == p) return p;
-    atomicCAS(parent + v, p, gp);
-    v = gp;
-  }
-}
-
-// hooks the larger root under the smaller one.  A failed swap means the larger root has been hooked by another lane
-// meanwhile: its root is then below it, so max(a, b) strictly decreases from one round to the next -- at most max(a, b) rounds.
-// No lane ever waits for another one.
-__device__ __forceinline__ void cc_unite(int32_t *parent, int32_t a, int32_t b) {
-  for (;;) {
-    a = cc_find(parent, a);
-    b = cc_find(parent, b);
-    if (a == b) return;
-    const int32_t hi = max(a, b), lo = min(a, b);
-    if (atomicCAS(parent + hi, hi, lo) == hi) return;
-    a = hi;
-    b = lo;
-  }
-}
-
 // reductions over the 64 lanes of a wavefront (every lane gets the result)
 __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
 #pragma unroll
@@ -696,28 +621,6 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
   for (int o = 32; o >= 1; o >>= 1) v += static_cast<unsigned long long>(__shfl_xor(static_cast<long long>(v), o, 64));
   return v;
 }
-// CC1-CC4 on the live accumulation (ctx->n > 0, checked parameters): *m crack points, *rows cracks, the table in ctx->cc_*;
-// queued on ctx->stream and synchronised only as far as the counts need
-int crack_components_run(pcp_context *ctx, const pcp_crack_link_params &p, CcScratch &s, int64_t *m, int64_t *rows);
-// the checks pcp_crack_components makes of its parameters and of the accumulation, under the caller's name
-int crack_link_check(pcp_context *ctx, const char *who, const pcp_crack_link_params *p);
-void crack_length_release(pcp_context *ctx);  // the table and paths of pcp_crack_lengths (with cc's table), and the skeleton's tables
-hipError_t preload_crack_length();
-// per-call scratch of the length stage beside the component stage's (pcp_crack_length.hip); everything is indexed by the
-// PLACE of a crack point in the grid's cell order.  After crack_lengths_run: dist = D_a, row_of = the crack's row, place_of =
-// view index -> place
-struct ClScratch {
-  DevBuf<unsigned long long> dist, far_d, pos;
-  DevBuf<uint32_t> mark, words;  // words[0]: the round in which a distance last fell; words[1]: a walk or an end went wrong
-  DevBuf<int32_t> place_of, row_of, src_place, far_k, end_a, end_b, pred;
-};
-// CC1-CC4 and CL1-CL7 on the live accumulation (ctx->n > 0, checked parameters): the component stage, then the length stage on
-// its m > 0 crack points; the tables in ctx->cc_* and ctx->cl_*, with_pos: CL5 in s.pos (n, input order).  Queued on
-// ctx->stream; the caller synchronises, drops the large grid bitmap and sets the live flags.
-int crack_lengths_run(pcp_context *ctx, const pcp_crack_link_params &p, CcScratch &cc, ClScratch &s, bool with_pos, int64_t *m,
-                      int64_t *rows, int64_t *entries);
-hipError_t preload_crack_skeleton();
-void crack_fuse_release(pcp_context *ctx);  // the accumulation of the crack widths (the uploads, pcp_set_camera, pcp_set_frames)
 void normals_release(pcp_context *ctx);   // the normals of the cloud that is being replaced (the uploads)
 // the list pcp_frame_visible reports for one keyframe (pcp_colour.hip): ascending input indices in ctx->s_cell, *m of them;
 // checks the context and the keyframe as that call does, under the caller's name
