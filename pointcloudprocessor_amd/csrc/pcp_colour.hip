@@ -487,9 +487,9 @@ __global__ __launch_bounds__(kBlock) void k_depth_pass(const float *__restrict__
   };
   for (int32_t w = f0 >> 5; w <= (f1 - 1) >> 5; ++w) {
     const uint32_t in_range = range_bits(w, f0, f1);
-    uint32_t todo = in_range;
-    if (tile_mask) todo &= tile_mask[tile * words + w];
-    todo = __builtin_amdgcn_readfirstlane(todo);
+    // the tile's mask word, kept for the store below: this wavefront is the only writer of its tile's words during the pass
+    const uint32_t word = tile_mask ? __builtin_amdgcn_readfirstlane(tile_mask[tile * words + w]) : 0xffffffffu;
+    uint32_t todo = in_range & word;
     // pairs whose tile images inside the acceptance box: the fp32 rejection test is skipped (it could not reject)
     const uint32_t inside = tile_inside ? __builtin_amdgcn_readfirstlane(tile_inside[tile * words + w]) : 0u;
     uint32_t seen = 0u;  // keyframes in which some lane can be coloured
@@ -540,10 +540,7 @@ __global__ __launch_bounds__(kBlock) void k_depth_pass(const float *__restrict__
       }
     }
     // drop the pairs in which no lane is a colouring candidate: the colour pass skips them
-    if (tile_mask && lane == 0 && live) {
-      uint32_t *dst = tile_mask + tile * words + w;
-      *dst = (*dst & ~in_range) | seen;
-    }
+    if (tile_mask && lane == 0 && live) tile_mask[tile * words + w] = (word & ~in_range) | seen;
   }
   settle_held();
 }
