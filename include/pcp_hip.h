@@ -71,7 +71,10 @@ extern "C" {
                                 entry points added, no layout changed: pcp_crack_lengths / _fetch / _host, pcp_crack_paths_fetch
                                 (crack lengths on the map; nothing runs unless called);
                                 entry points added, no layout changed: pcp_crack_skeleton / _nodes_fetch / _edges_fetch /
-                                _cracks_fetch / _host (crack skeletons on the map; nothing runs unless called) */
+                                _cracks_fetch / _host (crack skeletons on the map; nothing runs unless called);
+                                entry points added, no layout changed: pcp_ortho_begin / _add / _add_packed / _finish / _fetch /
+                                _stats / _end, pcp_ortho_host, pcp_ortho_fit_frame_host (orthographic maps; nothing runs unless
+                                called) */
 
 #define PCP_OK 0
 #define PCP_ERR_INVALID (-1) /* bad argument */
@@ -771,6 +774,85 @@ int pcp_voxel_reduce_end(pcp_context *ctx);
  * n / capacity, a missing xyz / rgb, out_label without label: PCP_ERR_INVALID.  The message is at pcp_last_error(NULL). */
 int pcp_voxel_reduce_host(float leaf, int64_t n, const float *xyz, const uint8_t *rgb, const uint8_t *label, int64_t capacity,
                           float *out_xyz, uint8_t *out_rgb, uint8_t *out_label, uint32_t *out_count, int64_t *out_voxels);
+
+/* ---- orthographic maps (no counterpart in the reference, which stops at per-keyframe perspective pictures: ------------- */
+/* ---- scripts/genNormAndDistanceMask.py visualize_skeleton_edge_pts, save_results) ----------------------------------- */
+/* One metric picture of the coloured cloud -- colour, depth, point index, fused label at a fixed number of metres per pixel
+ * -- accumulated on the device over any number of colour results: one-shot runs, the chunks of a streamed cloud (DESIGN.md,
+ * "Orthographic maps", OM1-OM8).  Opt-in: nothing runs unless one of these is called, PCP_ABI_VERSION is unchanged and a
+ * caller detects support by the symbols.  Kernels are timed under PCP_K_MISC.
+ *   frame     origin o, axes u (image x, to the right), v (image y, down), n (viewing direction, into the scene), gsd in
+ *             metres per pixel (1e-4 <= gsd <= 1; inv = f32(1.0f / gsd)), width and height in 1..16384 with width * height
+ *             <= 2^26, a depth window d_min < d_max.  A non-finite value, a gsd outside its range, an empty raster or window,
+ *             or axes that are not orthonormal and right-handed (u x v = n) within 1e-3: PCP_ERR_INVALID.  A raster past the
+ *             limits: PCP_ERR_RANGE, and the message names the gsd at which the same extent fits.
+ *   point     fp32, every operation rounded: d = p - o; s = d.u, t = d.v, depth = d.n with d.c = dx*cx + (dy*cy + dz*cz);
+ *             a = s * inv, b = t * inv.  A row contributes iff its has bit is set, its coordinates are finite,
+ *             0 <= a < (float)width, 0 <= b < (float)height (compared in float) and d_min <= depth <= d_max; its pixel is
+ *             (int32)floorf(b) * width + (int32)floorf(a).  A depth of -0 counts as +0.
+ *   winner    per pixel the contributor with the smallest depth, ties to the lowest GLOBAL index g = index_base + row.  Because
+ *             the global index is part of the comparison the result does not depend on the order of the adds, of the rows or
+ *             of the atomics: a cloud added in pieces gives the bytes of the same cloud added at once.  The global index
+ *             ranges of the adds must be DISJOINT; two rows with one global index give one of their payloads, unspecified
+ *             which.  index_base < 0 or index_base + pcp_cloud_size > 2^32 - 1: PCP_ERR_RANGE.
+ * The accumulator (12 B per pixel) belongs to the context: it outlives pcp_upload_cloud*, pcp_upload_cloud_from_result,
+ * pcp_colour_reset, pcp_set_frames and pcp_set_camera; only _begin, _end and pcp_destroy drop it.
+ * _begin      starts an empty map of the frame (dropping a previous one).
+ * _add        adds the rows of the current colour result with the uploaded coordinates -- the rows pcp_colour_compact returns;
+ *             *out_contributors (nullable) = the rows that fell inside the raster and the window.  Needs _begin, a live colour
+ *             result and no _finish since _begin (each PCP_ERR_STATE).  The first add fixes whether labels are held, by
+ *             whether its result was made with label fusion; a later add that disagrees is PCP_ERR_STATE.  A failed add leaves
+ *             the map as it was.  It changes nothing else: the packed colour words and pcp_colour_compact's rows are
+ *             afterwards what they were before.
+ * _add_packed the same for pcp_cloud_size words r | g<<8 | b<<16 | has<<24 of the caller's, in host memory or device memory of
+ *             the context's GPU, over the uploaded cloud (no colour result needed): a layer that is not the colour, e.g. a
+ *             width heat map.  The label is 0; it counts as an add without labels.
+ * _finish     fill_radius_px R in 0..1024 (else PCP_ERR_INVALID).  R = 0: the map is what the adds left.  R > 0: an empty pixel
+ *             whose nearest occupied pixel lies within d2 <= R^2 (the exact distance transform of pcp_mask_edt with the
+ *             occupied pixels as its background; of several equally near pixels the one with the lowest linear index) takes
+ *             that pixel's index, depth and payload.  *out_occupied, *out_filled (nullable) = pixels with a contributor of
+ *             their own, pixels filled.  A map without an occupied pixel stays empty.  A second call returns the same counts
+ *             (with another R: that R's); an add after a finish is PCP_ERR_STATE.  The fill's scratch (16 B per pixel) is freed
+ *             on return; the source image (4 B per pixel) stays until _end.
+ * _fetch      the layers, row-major height x width, every output a nullable host pointer: out_index uint32 global index
+ *             (0xFFFFFFFF when empty), out_depth fp32 (0 when empty), out_rgb 3 bytes (r, g, b), out_label the fused label,
+ *             out_status 0 empty / 1 direct / 2 filled, out_source int32 linear index of the pixel the values come from
+ *             (itself when direct, -1 when empty).  Before _finish, or out_label on a map that holds no labels: PCP_ERR_STATE.
+ * _stats      out[0..5] = contributors, atomics issued, occupied, filled (both as of the last _finish), adds, pixels.  Before
+ *             _begin: PCP_ERR_STATE.
+ * _end        drops the map. */
+typedef struct pcp_ortho_frame {
+  float o[3], u[3], v[3], n[3];
+  float gsd;
+  int32_t width, height;
+  float d_min, d_max;
+} pcp_ortho_frame;
+int pcp_ortho_begin(pcp_context *ctx, const pcp_ortho_frame *frame);
+int pcp_ortho_add(pcp_context *ctx, int64_t index_base, int64_t *out_contributors);
+int pcp_ortho_add_packed(pcp_context *ctx, const uint32_t *rgba, int64_t index_base, int64_t *out_contributors);
+int pcp_ortho_finish(pcp_context *ctx, int32_t fill_radius_px, int64_t *out_occupied, int64_t *out_filled);
+int pcp_ortho_fetch(pcp_context *ctx, uint32_t *out_index, float *out_depth, uint8_t *out_rgb, uint8_t *out_label,
+                    uint8_t *out_status, int32_t *out_source);
+int pcp_ortho_stats(pcp_context *ctx, int64_t out[6]);
+int pcp_ortho_end(pcp_context *ctx);
+/* Host only, no context, no GPU: the same layers from n rows (xyz 3 floats, rgb 3 bytes; label and has one byte per row,
+ * both nullable: label 0, every has bit set) with global indices index_base + row, by the arithmetic the kernels use
+ * (csrc/pcp_ortho.hpp): a sequential minimum per pixel and pcp_mask_edt_host for the fill.  Outputs as _fetch's, all
+ * nullable; the three counts as _add's and _finish's.  Frame, radius and index rules as above.  The message is at
+ * pcp_last_error(NULL). */
+int pcp_ortho_host(const pcp_ortho_frame *frame, int64_t n, const float *xyz, const uint8_t *rgb, const uint8_t *label,
+                   const uint8_t *has, int64_t index_base, int32_t fill_radius_px, uint32_t *out_index, float *out_depth,
+                   uint8_t *out_rgb, uint8_t *out_label, uint8_t *out_status, int32_t *out_source, int64_t *out_contributors,
+                   int64_t *out_occupied, int64_t *out_filled);
+/* Host only, fp64: a frame that looks straight at the rows with `has` set (NULL: all rows).  n is the eigenvector of the
+ * smallest eigenvalue of their covariance (pcl::eigen33's closed form), signed so that `viewer` (3 doubles, e.g. the mean
+ * camera centre) has negative depth -- with viewer NULL so that n's largest component is negative; u the eigenvector of the
+ * largest eigenvalue with its largest component positive; v = n x u.  The origin lies on the fitted plane (the depth layer is
+ * the relief off that plane), one pixel outside the rows' bounding rectangle; width and height are that rectangle plus two
+ * pixels; d_min, d_max the rows' depth range widened by one gsd.  Every such row is a contributor of the frame.  Fewer than 3
+ * rows, a gsd outside [1e-4, 1] or a non-finite result: PCP_ERR_INVALID; a size past the limits: PCP_ERR_RANGE, the gsd that
+ * fits in the message (pcp_last_error(NULL)). */
+int pcp_ortho_fit_frame_host(int64_t n, const float *xyz, const uint8_t *has, const double *viewer, float gsd, pcp_ortho_frame *out);
 
 /* ---- geometry maps (scripts/genNormAndDistanceMask.py: class Crack, generate_norm_masks :200-231, generate_distance_masks :233-266) */
 /* A normal per point of the uploaded map and, per keyframe, the images the crack measurement reads: range, camera position,

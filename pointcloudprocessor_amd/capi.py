@@ -292,6 +292,79 @@ def voxel_reduce_host(leaf: float, xyz, rgb, label=None, capacity: int | None = 
     return out
 
 
+class OrthoFrame(C.Structure):
+    """pcp_ortho_frame: origin, axes u (image x) / v (image y, down) / n (viewing direction), metres per pixel, raster size
+    and depth window of an orthographic map ("Orthographic maps", OM1)."""
+    _fields_ = [("o", C.c_float * 3), ("u", C.c_float * 3), ("v", C.c_float * 3), ("n", C.c_float * 3), ("gsd", C.c_float),
+                ("width", C.c_int32), ("height", C.c_int32), ("d_min", C.c_float), ("d_max", C.c_float)]
+
+    def as_dict(self) -> dict:
+        return dict(o=[float(x) for x in self.o], u=[float(x) for x in self.u], v=[float(x) for x in self.v], n=[float(x) for x in self.n],
+                    gsd=float(self.gsd), width=int(self.width), height=int(self.height), d_min=float(self.d_min), d_max=float(self.d_max))
+
+
+def ortho_frame(frame) -> OrthoFrame:
+    """An OrthoFrame from a dict(o, u, v, n, gsd, width, height, d_min, d_max) (or a copy of one); the values go through
+    float32 as the library takes them."""
+    if isinstance(frame, OrthoFrame):
+        frame = frame.as_dict()
+    f = OrthoFrame()
+    for k in ("o", "u", "v", "n"):
+        vals = np.asarray(frame[k], np.float32).reshape(3)
+        setattr(f, k, (C.c_float * 3)(*[float(x) for x in vals]))
+    f.gsd = float(np.float32(frame["gsd"]))
+    f.width, f.height = int(frame["width"]), int(frame["height"])
+    f.d_min, f.d_max = float(np.float32(frame["d_min"])), float(np.float32(frame["d_max"]))
+    return f
+
+
+def ortho_host(frame, xyz, rgb, label=None, has=None, index_base: int = 0, fill_radius: int = 0) -> dict:
+    """The orthographic map of n rows computed on the CPU by the arithmetic the kernels use (pcp_ortho_host: no context, no
+    GPU; DESIGN.md "Orthographic maps", OM8).  xyz (n, 3) float32, rgb (n, 3) uint8, label / has n uint8 or None:
+    dict(index, depth, rgb[, label], status, source, contributors, occupied, filled)."""
+    L = load()
+    f = ortho_frame(frame)
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    rgb = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)
+    label = None if label is None else np.ascontiguousarray(label, np.uint8).reshape(-1)
+    has = None if has is None else np.ascontiguousarray(has, np.uint8).reshape(-1)
+    n = xyz.shape[0]
+    if rgb.shape[0] != n or (label is not None and label.shape[0] != n) or (has is not None and has.shape[0] != n):
+        raise ValueError("ortho_host: xyz, rgb, label and has differ in their number of rows")
+    h, w = max(int(f.height), 0), max(int(f.width), 0)
+    big = w > 16384 or h > 16384 or w * h > (1 << 26)  # (refused by the library: nothing to allocate)
+    shape = (0, 0) if big else (h, w)
+    out = dict(index=np.empty(shape, np.uint32), depth=np.empty(shape, np.float32), rgb=np.empty(shape + (3,), np.uint8),
+               status=np.empty(shape, np.uint8), source=np.empty(shape, np.int32))
+    olab = np.empty(shape, np.uint8) if label is not None else None
+    cnt, occ, fil = C.c_int64(), C.c_int64(), C.c_int64()
+    rc = L.pcp_ortho_host(C.byref(f), C.c_int64(n), _ptr(xyz), _ptr(rgb), _ptr(label), _ptr(has), C.c_int64(index_base),
+                          C.c_int32(fill_radius), _ptr(out["index"]), _ptr(out["depth"]), _ptr(out["rgb"]), _ptr(olab),
+                          _ptr(out["status"]), _ptr(out["source"]), C.byref(cnt), C.byref(occ), C.byref(fil))
+    if rc != PCP_OK:
+        raise PcpError(rc, L.pcp_last_error(None).decode())
+    if label is not None:
+        out["label"] = olab
+    out.update(contributors=cnt.value, occupied=occ.value, filled=fil.value)
+    return out
+
+
+def ortho_fit_frame_host(xyz, gsd: float, has=None, viewer=None) -> OrthoFrame:
+    """A frame that looks straight at the rows (pcp_ortho_fit_frame_host: host only, fp64): the plane of their covariance's
+    smallest eigenvalue, n signed away from `viewer` (3 numbers; None: largest component negative)."""
+    L = load()
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    has = None if has is None else np.ascontiguousarray(has, np.uint8).reshape(-1)
+    if has is not None and has.shape[0] != xyz.shape[0]:
+        raise ValueError("ortho_fit_frame_host: xyz and has differ in their number of rows")
+    viewer = None if viewer is None else np.ascontiguousarray(viewer, np.float64).reshape(3)
+    f = OrthoFrame()
+    rc = L.pcp_ortho_fit_frame_host(C.c_int64(xyz.shape[0]), _ptr(xyz), _ptr(has), _ptr(viewer), C.c_float(gsd), C.byref(f))
+    if rc != PCP_OK:
+        raise PcpError(rc, L.pcp_last_error(None).decode())
+    return f
+
+
 def normals_moments_host(radius: float, xyz) -> np.ndarray:
     """The moments of pcp_estimate_normals computed on the CPU by brute force over the pairs, with the arithmetic the kernel
     uses (pcp_normals_moments_host: no context, no GPU; DESIGN.md "Geometry maps", GN2-GN4).  xyz (n, 3) float32, n <= 65536:
@@ -994,6 +1067,68 @@ class Context:
 
     def voxel_reduce_end(self):
         self._check(self.lib.pcp_voxel_reduce_end(self.h))
+
+    # -- orthographic maps ("Orthographic maps") -------------------------
+    def ortho_begin(self, frame):
+        """Starts an empty orthographic map of `frame` (an OrthoFrame, or a dict of its fields) on this context
+        (pcp_ortho_begin); it outlives uploads, colour resets, set_frames and set_camera."""
+        f = ortho_frame(frame)
+        self._check(self.lib.pcp_ortho_begin(self.h, C.byref(f)))
+        self._ortho_frame = f  # (only of a begin the library took: a refused one leaves the live map, and its frame, as they were)
+
+    def ortho_add(self, index_base: int = 0) -> int:
+        """Adds the coloured rows of the current colour result under the global indices index_base + row; returns the
+        number of contributors (rows inside the raster and the depth window)."""
+        rows = C.c_int64()
+        self._check(self.lib.pcp_ortho_add(self.h, C.c_int64(index_base), C.byref(rows)))
+        return rows.value
+
+    def ortho_add_packed(self, rgba, index_base: int = 0) -> int:
+        """Adds the uploaded cloud with the caller's words r | g<<8 | b<<16 | has<<24 (n of them: a numpy array, or an int
+        that is a device pointer of this context's GPU); the label is 0.  Returns the number of contributors."""
+        rows = C.c_int64()
+        if isinstance(rgba, int):
+            words = C.c_void_p(rgba)
+        else:
+            keep = np.ascontiguousarray(rgba, np.uint32).reshape(-1)
+            if keep.size != self.n:
+                raise ValueError(f"ortho_add_packed: {self.n} words expected, got shape {keep.shape}")
+            words = _ptr(keep)
+        self._check(self.lib.pcp_ortho_add_packed(self.h, words, C.c_int64(index_base), C.byref(rows)))
+        return rows.value
+
+    def ortho_finish(self, fill_radius: int = 0) -> tuple[int, int]:
+        """Ends the adds; fill_radius > 0 fills empty pixels from their nearest occupied pixel within that many pixels.
+        Returns (occupied, filled)."""
+        occ, fil = C.c_int64(), C.c_int64()
+        self._check(self.lib.pcp_ortho_finish(self.h, C.c_int32(fill_radius), C.byref(occ), C.byref(fil)))
+        return occ.value, fil.value
+
+    def ortho_fetch(self, want_label: bool = False) -> dict:
+        """dict(index, depth, rgb[, label], status, source) of the finished map, each (H, W) (rgb (H, W, 3))."""
+        f = getattr(self, "_ortho_frame", None)
+        if f is None:  # no map was ever begun on this context: the library says so
+            self._check(self.lib.pcp_ortho_fetch(self.h, None, None, None, None, None, None))
+            raise PcpError(PCP_ERR_STATE, "ortho_fetch: no map")
+        h, w = int(f.height), int(f.width)
+        out = dict(index=np.empty((h, w), np.uint32), depth=np.empty((h, w), np.float32), rgb=np.empty((h, w, 3), np.uint8),
+                   status=np.empty((h, w), np.uint8), source=np.empty((h, w), np.int32))
+        label = np.empty((h, w), np.uint8) if want_label else None
+        self._check(self.lib.pcp_ortho_fetch(self.h, _ptr(out["index"]), _ptr(out["depth"]), _ptr(out["rgb"]), _ptr(label),
+                                             _ptr(out["status"]), _ptr(out["source"])))
+        if want_label:
+            out["label"] = label
+        return out
+
+    def ortho_stats(self) -> dict:
+        out = np.zeros(6, np.int64)
+        self._check(self.lib.pcp_ortho_stats(self.h, _ptr(out)))
+        keys = ("contributors", "atomics", "occupied", "filled", "adds", "pixels")
+        return {k: int(v) for k, v in zip(keys, out)}
+
+    def ortho_end(self):
+        self._check(self.lib.pcp_ortho_end(self.h))
+        self._ortho_frame = None
 
     # -- geometry maps (DESIGN.md, "Geometry maps") ---------------------------------
     def estimate_normals(self, radius: float, want_moments: bool = False):

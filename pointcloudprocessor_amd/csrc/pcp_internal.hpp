@@ -194,6 +194,19 @@ struct VoxelReduce {
   DevBuf<uint32_t> out_count;
 };
 
+// orthographic maps (pcp_ortho.hip): the accumulator between pcp_ortho_begin and _end -- the frame, the key image and the
+// payload image (12 B per pixel), its device scalars, and the source image pcp_ortho_finish left
+struct OrthoMap {
+  bool live = false, finished = false;
+  bool labels_fixed = false, with_label = false;  // the first add fixes whether labels are held
+  pcp_ortho_frame frame{};
+  int32_t fill_radius = 0;
+  int64_t contributors = 0, atomics = 0, occupied = 0, filled = 0, adds = 0;
+  DevBuf<unsigned long long> keys, scalars;
+  DevBuf<uint32_t> payload;
+  DevBuf<int32_t> source;  // per pixel: the pixel its values come from (-1: empty), after _finish
+};
+
 struct CrackMap;  // (the crack chain's header)
 
 }  // namespace pcp
@@ -305,6 +318,8 @@ struct pcp_context {
 
   // voxel-grid output: belongs to the context, not to the cloud or the camera (only pcp_voxel_reduce_begin / _end and pcp_destroy drop it)
   pcp::VoxelReduce voxel_reduce;
+  // orthographic maps: the same lifetime (only pcp_ortho_begin / _end and pcp_destroy drop it)
+  pcp::OrthoMap ortho;
 
   // geometry maps (pcp_normals.hip): normal + curvature (float4) and neighbour count per point of the uploaded cloud, input
   // order, dropped by the uploads; the key image and the four output images of pcp_frame_geometry (allocated on first use)
@@ -600,9 +615,15 @@ hipError_t preload_exposure();
 hipError_t preload_voxel_reduce();
 hipError_t preload_normals();
 hipError_t preload_mask_edt();
+hipError_t preload_ortho();
 // the device parts of pcp_mask_edt (one keyframe, with nearest) and pcp_frame_geometry under the caller's name: checks and
 // kernels, the results left in md_bits / md_d2 / md_nearest and gm_out / s_counter[0]; no copy, no synchronisation
 int mask_edt_device(pcp_context *ctx, const char *who, int32_t frame, int32_t threshold);
+// k_md_columns and k_md_rows on a caller's bit image of one w x h picture (bit j of word [s][x] = pixel (x, 64 s + j) is
+// background; segs = ceil(h / 64)): column words into `col`, then d2 and nearest (nullable), w * h words each, all device
+// memory of the caller's (pcp_ortho.hip fills a map through them).  Queues on ctx->stream; no checks, no synchronisation.
+int mask_edt_of_bits(pcp_context *ctx, const unsigned long long *bits, int32_t w, int32_t h, int32_t segs, uint32_t *col,
+                     uint32_t *out_d2, int32_t *out_nearest);
 // (*out_contributors, nullable: the length of the keyframe's list, which frame_contributors left in ctx->s_cell)
 int frame_geometry_device(pcp_context *ctx, const char *who, int32_t frame, bool with_normals, int64_t *out_contributors = nullptr);
 // reductions over the 64 lanes of a wavefront (every lane gets the result)

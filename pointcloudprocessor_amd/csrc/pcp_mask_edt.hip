@@ -183,6 +183,24 @@ int mask_edt_device(pcp_context *ctx, const char *who, int32_t frame, int32_t th
   return mask_edt_launch(ctx, frame, 1, threshold, true);
 }
 
+// the column and row stages on a bit image that another stage built (pcp_internal.hpp)
+int mask_edt_of_bits(pcp_context *ctx, const unsigned long long *bits, int32_t w, int32_t h, int32_t segs, uint32_t *col,
+                     uint32_t *out_d2, int32_t *out_nearest) {
+  {
+    LaunchTimer lt(ctx, PCP_K_MISC);
+    hipLaunchKernelGGL(k_md_columns, dim3(static_cast<uint32_t>((w + kMdBlock - 1) / kMdBlock), static_cast<uint32_t>(segs), 1u),
+                       dim3(kMdBlock), 0, ctx->stream, bits, w, h, segs, col);
+    PCP_HIP_TRY(ctx, hipGetLastError());
+  }
+  {
+    LaunchTimer lt(ctx, PCP_K_MISC);
+    hipLaunchKernelGGL(k_md_rows, dim3(static_cast<uint32_t>(h), 1u), dim3(kMdBlock), static_cast<size_t>(w) * sizeof(uint32_t),
+                       ctx->stream, col, w, h, out_d2, out_nearest);
+    PCP_HIP_TRY(ctx, hipGetLastError());
+  }
+  return PCP_OK;
+}
+
 }  // namespace pcp
 
 using namespace pcp;

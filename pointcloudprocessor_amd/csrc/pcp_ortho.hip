@@ -1,0 +1,719 @@
+// pcp_ortho.hip -- orthographic maps of the coloured cloud ("Orthographic maps", OM1-OM8): one metric picture of
+// the surface at a fixed number of metres per pixel -- colour, depth, point index, fused label -- accumulated on the device
+// over any number of colour results (one-shot runs, the chunks of the streamed chain).  Per pixel the nearest contributor
+// wins through one 64-bit atomicMin on (ord(depth) << 32 | global index), the reduction of k_gm_scatter; a second pass with
+// plain stores writes the winners' payload; the optional fill takes empty pixels from their nearest occupied one through the
+// exact distance transform of pcp_mask_edt.hip.  The arithmetic is pcp_ortho.hpp's, shared with pcp_ortho_host.
+// Opt-in: nothing here runs unless one of its entry points is called.
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <new>
+#include <vector>
+
+#include "pcp_internal.hpp"
+#include "pcp_mask_edt.hpp"
+#include "pcp_ortho.hpp"
+
+namespace pcp {
+
+constexpr int kOrBlock = 256;
+constexpr int64_t kOrMaxGrid = 4096;  // workgroups of the grid-stride passes
+// device scalars of the accumulator
+enum { OR_CONTRIBUTORS = 0, OR_ATOMICS, OR_OCCUPIED, OR_FILLED, OR_SCALARS };
+
+// the contributor of lane j of the upload's spatial order (sxyz / perm: the uploaded coordinates; the packed word of the
+// input-order result): its pixel (-1: none), key, input row and word
+__device__ __forceinline__ int32_t or_contributor(int64_t j, int64_t n, const float *__restrict__ sx, const float *__restrict__ sy,
+                                                  const float *__restrict__ sz, const int32_t *__restrict__ perm,
+                                                  const uint32_t *__restrict__ packed, const om::Frame &f, uint32_t index_base,
+                                                  unsigned long long *key, int32_t *row, uint32_t *word) {
+  *key = om::kEmptyKey;
+  if (j >= n) return -1;
+  const int32_t i = perm[j];
+  const uint32_t w = packed[i];
+  if (!(w >> 24)) return -1;
+  int32_t pixel;
+  uint32_t depth_bits;
+  if (!om::project(f, sx[j], sy[j], sz[j], &pixel, &depth_bits)) return -1;
+  *row = i;
+  *word = w;
+  *key = om::key_of(depth_bits, index_base + static_cast<uint32_t>(i));
+  return pixel;
+}
+
+// OM3.  One lane per row.  Equal pixels of neighbouring lanes are merged before the atomic: a lane without a contributor joins
+// the run of the nearest lane below that has one (and brings the empty key, the minimum's identity); the smallest key of a run
+// of equal pixels is found by a segmented suffix minimum (six shuffle steps) and the run's first lane issues the one atomic.
+// (One atomic per contributor instead: the same add 0.71 -> 1.99 ms where 200 points share a pixel, profiles/ortho_probe.md.)
+__global__ __launch_bounds__(kOrBlock) void k_or_scatter(int64_t n, const float *__restrict__ sx, const float *__restrict__ sy,
+                                                         const float *__restrict__ sz, const int32_t *__restrict__ perm,
+                                                         const uint32_t *__restrict__ packed, om::Frame f, uint32_t index_base,
+                                                         unsigned long long *__restrict__ keys, unsigned long long *__restrict__ scalars) {
+  const int lane = static_cast<int>(threadIdx.x & 63u);
+  uint32_t contributors = 0u, atomics = 0u;
+  for (int64_t base = static_cast<int64_t>(blockIdx.x) * kOrBlock; base < n; base += static_cast<int64_t>(gridDim.x) * kOrBlock) {
+    unsigned long long key;
+    int32_t row = 0;
+    uint32_t word = 0u;
+    const int32_t pixel = or_contributor(base + threadIdx.x, n, sx, sy, sz, perm, packed, f, index_base, &key, &row, &word);
+    contributors += pixel >= 0 ? 1u : 0u;
+    const unsigned long long with = __ballot(pixel >= 0);
+    if (!with) continue;  // (the same in every lane of the wavefront)
+    const unsigned long long below = with & ((1ull << lane) - 1ull);
+    const int src = (pixel < 0 && below) ? 63 - __clzll(static_cast<long long>(below)) : lane;
+    const int32_t run_pixel = __shfl(pixel, src, 64);
+    const int32_t before = __shfl_up(run_pixel, 1, 64);
+    const bool head = lane == 0 || before != run_pixel;
+    const unsigned long long heads = __ballot(head);
+    const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
+    const int run_end = above ? lane + (__ffsll(above) - 1) : 63;  // last lane of this lane's run
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const unsigned long long other = __shfl_down(key, d, 64);
+      if (lane + d <= run_end) key = other < key ? other : key;
+    }
+    if (head && run_pixel >= 0) {  // (such a head is a lane with a contributor of its own: pixel == run_pixel)
+      atomicMin(keys + run_pixel, key);
+      atomics += 1u;
+    }
+  }
+  const unsigned long long both = wave_sum_u64((static_cast<unsigned long long>(atomics) << 32) | contributors);  // (n < 2^31 rows)
+  if (lane == 0 && both) {
+    atomicAdd(scalars + OR_CONTRIBUTORS, both & 0xffffffffull);
+    atomicAdd(scalars + OR_ATOMICS, both >> 32);
+  }
+}
+
+// OM4.  The same contributors, after the scatter: the one whose key is its pixel's key stores the payload word.  No atomics.
+template <bool kLabel>
+__global__ __launch_bounds__(kOrBlock) void k_or_payload(int64_t n, const float *__restrict__ sx, const float *__restrict__ sy,
+                                                         const float *__restrict__ sz, const int32_t *__restrict__ perm,
+                                                         const uint32_t *__restrict__ packed,
+                                                         [[maybe_unused]] const uint32_t *__restrict__ labels, om::Frame f,
+                                                         uint32_t index_base, const unsigned long long *__restrict__ keys,
+                                                         uint32_t *__restrict__ payload) {
+  for (int64_t base = static_cast<int64_t>(blockIdx.x) * kOrBlock; base < n; base += static_cast<int64_t>(gridDim.x) * kOrBlock) {
+    unsigned long long key;
+    int32_t row = 0;
+    uint32_t word = 0u;
+    const int32_t pixel = or_contributor(base + threadIdx.x, n, sx, sy, sz, perm, packed, f, index_base, &key, &row, &word);
+    if (pixel < 0 || keys[pixel] != key) continue;
+    uint32_t label = 0u;
+    if constexpr (kLabel) label = labels[row] & 0xffu;
+    payload[pixel] = om::payload_of(word, label);
+  }
+}
+
+// OM6.  The bit image k_md_columns reads, from the key image: one lane per (column, segment of 64 rows); bit j of the word =
+// pixel (x, 64 * s + j) is occupied (the distance transform's background); rows past the map stay 0.
+__global__ __launch_bounds__(kOrBlock) void k_or_bits(const unsigned long long *__restrict__ keys, int32_t w, int32_t h, int32_t segs,
+                                                      unsigned long long *__restrict__ bits) {
+  const int32_t x = static_cast<int32_t>(blockIdx.x) * kOrBlock + static_cast<int32_t>(threadIdx.x);
+  if (x >= w) return;
+  const int32_t s = static_cast<int32_t>(blockIdx.y);
+  if (s >= segs) return;
+  const int32_t y0 = s * md::kSegmentRows, y1 = min(h, y0 + md::kSegmentRows);
+  unsigned long long m = 0;
+  for (int32_t y = y0; y < y1; ++y)
+    if (keys[static_cast<int64_t>(y) * w + x] != om::kEmptyKey) m |= 1ull << (y - y0);
+  bits[static_cast<int64_t>(s) * w + x] = m;
+}
+
+// OM6.  The pixel every pixel takes its values from: itself when occupied, its nearest occupied pixel when that lies within
+// the radius (d2 / nearest: the distance transform; nullptr with radius 0), else -1.  Counts both kinds.
+__global__ __launch_bounds__(kOrBlock) void k_or_source(const unsigned long long *__restrict__ keys, const uint32_t *__restrict__ d2,
+                                                        const int32_t *__restrict__ nearest, int64_t pixels, int32_t radius,
+                                                        int32_t *__restrict__ source, unsigned long long *__restrict__ scalars) {
+  uint32_t occupied = 0u, filled = 0u;
+  for (int64_t p = static_cast<int64_t>(blockIdx.x) * kOrBlock + threadIdx.x; p < pixels; p += static_cast<int64_t>(gridDim.x) * kOrBlock) {
+    int32_t src;
+    if (keys[p] != om::kEmptyKey) {
+      src = static_cast<int32_t>(p);
+      occupied += 1u;
+    } else {
+      src = d2 ? om::fill_source(d2[p], nearest[p], radius) : -1;
+      filled += src >= 0 ? 1u : 0u;
+    }
+    source[p] = src;
+  }
+  const unsigned long long both = wave_sum_u64((static_cast<unsigned long long>(filled) << 32) | occupied);  // (< 2^32 pixels each)
+  if ((threadIdx.x & 63u) == 0u && both) {
+    atomicAdd(scalars + OR_OCCUPIED, both & 0xffffffffull);
+    atomicAdd(scalars + OR_FILLED, both >> 32);
+  }
+}
+
+// OM7.  The layers a fetch asked for (nullptr: not asked), gathered through the source image.
+__global__ __launch_bounds__(kOrBlock) void k_or_layers(int64_t pixels, const int32_t *__restrict__ source,
+                                                        const unsigned long long *__restrict__ keys, const uint32_t *__restrict__ payload,
+                                                        uint32_t *__restrict__ out_index, float *__restrict__ out_depth,
+                                                        uint8_t *__restrict__ out_rgb, uint8_t *__restrict__ out_label,
+                                                        uint8_t *__restrict__ out_status) {
+  for (int64_t p = static_cast<int64_t>(blockIdx.x) * kOrBlock + threadIdx.x; p < pixels; p += static_cast<int64_t>(gridDim.x) * kOrBlock) {
+    const int32_t src = source[p];
+    uint32_t index = om::kNoIndex, word = 0u;
+    float depth = 0.0f;
+    if (src >= 0) {
+      const unsigned long long key = keys[src];
+      index = om::key_index(key);
+      depth = om::key_depth(key);
+      word = payload[src];
+    }
+    if (out_index) out_index[p] = index;
+    if (out_depth) out_depth[p] = depth;
+    if (out_rgb) {
+      out_rgb[3 * p] = static_cast<uint8_t>(word);
+      out_rgb[3 * p + 1] = static_cast<uint8_t>(word >> 8);
+      out_rgb[3 * p + 2] = static_cast<uint8_t>(word >> 16);
+    }
+    if (out_label) out_label[p] = static_cast<uint8_t>(word >> 24);
+    if (out_status) out_status[p] = src < 0 ? 0 : (src == p ? 1 : 2);
+  }
+}
+
+hipError_t preload_ortho() {
+  hipFuncAttributes a;
+  return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_or_source));
+}
+
+static inline uint32_t or_blocks(int64_t n) {
+  return static_cast<uint32_t>(std::max<int64_t>(1, std::min<int64_t>(div_up(n, kOrBlock), kOrMaxGrid)));
+}
+
+static om::Frame or_frame(const pcp_ortho_frame &c) {
+  om::Frame f;
+  for (int a = 0; a < 3; ++a) {
+    f.o[a] = c.o[a];
+    f.u[a] = c.u[a];
+    f.v[a] = c.v[a];
+    f.n[a] = c.n[a];
+  }
+  f.inv = om::inverse_gsd(c.gsd);
+  f.w = c.width;
+  f.h = c.height;
+  f.wf = static_cast<float>(c.width);
+  f.hf = static_cast<float>(c.height);
+  f.d_min = c.d_min;
+  f.d_max = c.d_max;
+  return f;
+}
+
+// OM1 for either form; msg receives the refusal
+static int or_check_frame(const char *who, const pcp_ortho_frame *fr, char *msg, size_t cap) {
+  const char *why = "";
+  double fit = 0.0;
+  const int bad = om::frame_check(fr->o, fr->u, fr->v, fr->n, fr->gsd, fr->width, fr->height, fr->d_min, fr->d_max, &why, &fit);
+  if (bad == 1) {
+    std::snprintf(msg, cap, "%s: %s", who, why);
+    return PCP_ERR_INVALID;
+  }
+  if (bad == 2) {
+    std::snprintf(msg, cap, "%s: raster %d x %d at gsd %g: %s; the same extent fits at gsd %.6g", who, fr->width, fr->height,
+                  static_cast<double>(fr->gsd), why, fit);
+    return PCP_ERR_RANGE;
+  }
+  return PCP_OK;
+}
+
+static void or_drop(pcp_context *ctx) {
+  OrthoMap &m = ctx->ortho;
+  m.keys.release();
+  m.payload.release();
+  m.source.release();
+  m.scalars.release();
+  m.live = m.finished = m.labels_fixed = m.with_label = false;
+  m.contributors = m.atomics = m.occupied = m.filled = m.adds = 0;
+  m.fill_radius = 0;
+}
+
+// the two passes of an add over the uploaded cloud with the words `packed` (device, input order) and `labels` (nullable)
+static int or_add_words(pcp_context *ctx, const uint32_t *packed, const uint32_t *labels, uint32_t index_base, int64_t *out_contributors) {
+  OrthoMap &m = ctx->ortho;
+  const int64_t n = ctx->n;
+  const size_t plane = (static_cast<size_t>(n) + 3) & ~size_t(3);
+  const float *sx = ctx->sxyz.p, *sy = sx + plane, *sz = sy + plane;
+  const om::Frame f = or_frame(m.frame);
+  PCP_HIP_TRY(ctx, hipMemsetAsync(m.scalars.p, 0, 2 * 8, ctx->stream));  // contributors, atomics
+  {
+    LaunchTimer t(ctx, PCP_K_MISC);
+    hipLaunchKernelGGL(k_or_scatter, dim3(or_blocks(n)), dim3(kOrBlock), 0, ctx->stream, n, sx, sy, sz, ctx->perm.p, packed, f,
+                       index_base, m.keys.p, m.scalars.p);
+    PCP_HIP_TRY(ctx, hipGetLastError());
+  }
+  {
+    LaunchTimer t(ctx, PCP_K_MISC);
+    if (labels)
+      hipLaunchKernelGGL(k_or_payload<true>, dim3(or_blocks(n)), dim3(kOrBlock), 0, ctx->stream, n, sx, sy, sz, ctx->perm.p, packed, labels,
+                         f, index_base, m.keys.p, m.payload.p);
+    else
+      hipLaunchKernelGGL(k_or_payload<false>, dim3(or_blocks(n)), dim3(kOrBlock), 0, ctx->stream, n, sx, sy, sz, ctx->perm.p, packed,
+                         static_cast<const uint32_t *>(nullptr), f, index_base, m.keys.p, m.payload.p);
+    PCP_HIP_TRY(ctx, hipGetLastError());
+  }
+  unsigned long long h[2];
+  PCP_HIP_TRY(ctx, hipMemcpyAsync(h, m.scalars.p, 2 * 8, hipMemcpyDeviceToHost, ctx->stream));
+  PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  m.contributors += static_cast<int64_t>(h[OR_CONTRIBUTORS]);
+  m.atomics += static_cast<int64_t>(h[OR_ATOMICS]);
+  if (out_contributors) *out_contributors = static_cast<int64_t>(h[OR_CONTRIBUTORS]);
+  return PCP_OK;
+}
+
+// what both adds check before they touch the device
+static int or_add_check(pcp_context *ctx, const char *who, int64_t index_base, bool with_label) {
+  const OrthoMap &m = ctx->ortho;
+  if (!m.live) return set_error(ctx, PCP_ERR_STATE, "%s: no accumulation (call pcp_ortho_begin)", who);
+  if (m.finished) return set_error(ctx, PCP_ERR_STATE, "%s: the accumulation is finished (pcp_ortho_begin starts the next)", who);
+  if (index_base < 0 || index_base > om::kMaxIndexEnd - ctx->n)  // (index_base + n > 2^32 - 1, without the sum: it may overflow)
+    return set_error(ctx, PCP_ERR_RANGE, "%s: index_base %lld with %lld rows: global indices outside 0 .. 2^32 - 2", who,
+                     static_cast<long long>(index_base), static_cast<long long>(ctx->n));
+  if (m.labels_fixed && with_label != m.with_label)
+    return set_error(ctx, PCP_ERR_STATE, "%s: this add comes %s fused labels, the accumulation's first came %s them", who,
+                     with_label ? "with" : "without", m.with_label ? "with" : "without");
+  return PCP_OK;
+}
+
+// ---- pcp_ortho_fit_frame_host: the eigenpairs of a symmetric 3 x 3 matrix by pcp_eigen33.hpp's closed form, on the host ----
+static void or_roots2(double b, double c, double r[3]) {
+  double d = b * b - 4.0 * c;
+  if (d < 0.0) d = 0.0;
+  const double sd = std::sqrt(d);
+  r[0] = 0.0;
+  r[1] = 0.5 * (b - sd);
+  r[2] = 0.5 * (b + sd);
+}
+// m = xx xy xz yy yz zz scaled to a largest magnitude of 1: its roots ascending
+static void or_roots3(const double a[6], double r[3]) {
+  const double a00 = a[0], a01 = a[1], a02 = a[2], a11 = a[3], a12 = a[4], a22 = a[5];
+  const double c0 = a00 * a11 * a22 + 2.0 * a01 * a02 * a12 - a00 * a12 * a12 - a11 * a02 * a02 - a22 * a01 * a01;
+  const double c1 = a00 * a11 - a01 * a01 + a00 * a22 - a02 * a02 + a11 * a22 - a12 * a12;
+  const double c2 = a00 + a11 + a22;
+  if (std::fabs(c0) < DBL_EPSILON) return or_roots2(c2, c1, r);
+  const double inv3 = 1.0 / 3.0, sqrt3 = std::sqrt(3.0);
+  const double c2_3 = c2 * inv3;
+  double a_3 = (c1 - c2 * c2_3) * inv3;
+  if (a_3 > 0.0) a_3 = 0.0;
+  const double half_b = 0.5 * (c0 + c2_3 * (2.0 * c2_3 * c2_3 - c1));
+  double q = half_b * half_b + a_3 * a_3 * a_3;
+  if (q > 0.0) q = 0.0;
+  const double rho = std::sqrt(-a_3), theta = std::atan2(std::sqrt(-q), half_b) * inv3;
+  const double ct = std::cos(theta), st = std::sin(theta);
+  r[0] = c2_3 + 2.0 * rho * ct;
+  r[1] = c2_3 - rho * (ct + sqrt3 * st);
+  r[2] = c2_3 - rho * (ct - sqrt3 * st);
+  std::sort(r, r + 3);
+  if (r[0] <= 0.0) or_roots2(c2, c1, r);
+}
+// the unit eigenvector of root r: the longest cross product of two rows of (A - r I)
+static void or_eigenvector(const double a[6], double r, double v[3]) {
+  const double a01 = a[1], a02 = a[2], a12 = a[4];
+  const double s00 = a[0] - r, s11 = a[3] - r, s22 = a[5] - r;
+  const double k[3][3] = {{a01 * a12 - a02 * s11, a02 * a01 - s00 * a12, s00 * s11 - a01 * a01},
+                          {a01 * s22 - a02 * a12, a02 * a02 - s00 * s22, s00 * a12 - a01 * a02},
+                          {s11 * s22 - a12 * a12, a12 * a02 - a01 * s22, a01 * a12 - s11 * a02}};
+  int best = 0;
+  double len[3];
+  for (int i = 0; i < 3; ++i) {
+    len[i] = (k[i][0] * k[i][0] + k[i][1] * k[i][1]) + k[i][2] * k[i][2];
+    if (len[i] > len[best]) best = i;
+  }
+  const double inv = 1.0 / std::sqrt(len[best]);
+  for (int c = 0; c < 3; ++c) v[c] = k[best][c] * inv;
+}
+static int or_largest_component(const double v[3]) {
+  int b = 0;
+  for (int c = 1; c < 3; ++c)
+    if (std::fabs(v[c]) > std::fabs(v[b])) b = c;
+  return b;
+}
+
+}  // namespace pcp
+
+using namespace pcp;
+
+extern "C" {
+
+int pcp_ortho_begin(pcp_context *ctx, const pcp_ortho_frame *frame) {
+  if (!ctx) return PCP_ERR_INVALID;
+  if (!frame) return set_error(ctx, PCP_ERR_INVALID, "pcp_ortho_begin: NULL frame");
+  char msg[320];
+  const int rc = or_check_frame("pcp_ortho_begin", frame, msg, sizeof msg);
+  if (rc != PCP_OK) return set_error(ctx, rc, "%s", msg);
+  PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  or_drop(ctx);
+  OrthoMap &m = ctx->ortho;
+  const size_t px = static_cast<size_t>(frame->width) * static_cast<size_t>(frame->height);
+  PCP_HIP_TRY(ctx, m.keys.ensure(px + 2));
+  PCP_HIP_TRY(ctx, m.payload.ensure(px + 4));
+  PCP_HIP_TRY(ctx, m.scalars.ensure(OR_SCALARS));
+  PCP_HIP_TRY(ctx, hipMemsetAsync(m.keys.p, 0xff, px * 8, ctx->stream));  // the empty key is all ones
+  PCP_HIP_TRY(ctx, hipMemsetAsync(m.payload.p, 0, px * 4, ctx->stream));
+  PCP_HIP_TRY(ctx, hipMemsetAsync(m.scalars.p, 0, OR_SCALARS * 8, ctx->stream));
+  m.frame = *frame;
+  m.live = true;
+  return PCP_OK;
+}
+
+int pcp_ortho_add(pcp_context *ctx, int64_t index_base, int64_t *out_contributors) {
+  if (!ctx) return PCP_ERR_INVALID;
+  if (out_contributors) *out_contributors = 0;
+  OrthoMap &m = ctx->ortho;
+  const bool with_label = ctx->labels_live;
+  if (m.live && !m.finished && !ctx->colour_result_live)
+    return set_error(ctx, PCP_ERR_STATE, "pcp_ortho_add: no colour result (call pcp_colorize / pcp_colorize_from_depth / pcp_colour_finalise)");
+  int rc = or_add_check(ctx, "pcp_ortho_add", index_base, with_label);
+  if (rc != PCP_OK) return rc;
+  if (ctx->n > 0) {
+    PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = or_add_words(ctx, ctx->rgba2[ctx->rgba_cur].p, with_label ? ctx->labels.p : nullptr, static_cast<uint32_t>(index_base),
+                      out_contributors);
+    if (rc != PCP_OK) return rc;
+  }
+  m.labels_fixed = true;
+  m.with_label = with_label;
+  m.adds += 1;
+  return PCP_OK;
+}
+
+int pcp_ortho_add_packed(pcp_context *ctx, const uint32_t *rgba, int64_t index_base, int64_t *out_contributors) {
+  if (!ctx) return PCP_ERR_INVALID;
+  if (out_contributors) *out_contributors = 0;
+  OrthoMap &m = ctx->ortho;
+  int rc = or_add_check(ctx, "pcp_ortho_add_packed", index_base, false);
+  if (rc != PCP_OK) return rc;
+  if (ctx->n > 0) {
+    if (!ctx->sxyz.p) return set_error(ctx, PCP_ERR_STATE, "pcp_ortho_add_packed: no cloud uploaded");
+    if (!rgba) return set_error(ctx, PCP_ERR_INVALID, "pcp_ortho_add_packed: NULL words");
+    PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    DevBuf<uint32_t> words;  // the caller's words (host or device memory)
+    PCP_HIP_TRY(ctx, words.ensure(static_cast<size_t>(ctx->n) + 4));
+    PCP_HIP_TRY(ctx, hipMemcpyAsync(words.p, rgba, static_cast<size_t>(ctx->n) * 4, hipMemcpyDefault, ctx->stream));
+    rc = or_add_words(ctx, words.p, nullptr, static_cast<uint32_t>(index_base), out_contributors);  // (synchronises: words may go)
+    if (rc != PCP_OK) return rc;
+  }
+  m.labels_fixed = true;
+  m.with_label = false;
+  m.adds += 1;
+  return PCP_OK;
+}
+
+int pcp_ortho_finish(pcp_context *ctx, int32_t fill_radius_px, int64_t *out_occupied, int64_t *out_filled) {
+  if (!ctx) return PCP_ERR_INVALID;
+  if (out_occupied) *out_occupied = 0;
+  if (out_filled) *out_filled = 0;
+  OrthoMap &m = ctx->ortho;
+  if (!m.live) return set_error(ctx, PCP_ERR_STATE, "pcp_ortho_finish: no accumulation (call pcp_ortho_begin)");
+  if (fill_radius_px < 0 || fill_radius_px > om::kMaxFill)
+    return set_error(ctx, PCP_ERR_INVALID, "pcp_ortho_finish: fill radius %d outside 0..%d pixels", fill_radius_px, om::kMaxFill);
+  if (!(m.finished && fill_radius_px == m.fill_radius)) {  // (the key image stays as the adds left it: any radius can follow)
+    PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int32_t w = m.frame.width, h = m.frame.height;
+    const int64_t px = static_cast<int64_t>(w) * h;
+    const int32_t segs = (h + md::kSegmentRows - 1) / md::kSegmentRows;
+    PCP_HIP_TRY(ctx, m.source.ensure(static_cast<size_t>(px) + 4));
+    // the fill's scratch is its own (the mask distance maps keep theirs) and goes when this call returns
+    DevBuf<unsigned long long> bits;
+    DevBuf<uint32_t> col, d2;
+    DevBuf<int32_t> nearest;
+    if (fill_radius_px > 0) {
+      PCP_HIP_TRY(ctx, bits.ensure(static_cast<size_t>(segs) * w + 4));
+      PCP_HIP_TRY(ctx, col.ensure(static_cast<size_t>(px) + 4));
+      PCP_HIP_TRY(ctx, d2.ensure(static_cast<size_t>(px) + 4));
+      PCP_HIP_TRY(ctx, nearest.ensure(static_cast<size_t>(px) + 4));
+      {
+        LaunchTimer t(ctx, PCP_K_MISC);
+        hipLaunchKernelGGL(k_or_bits, dim3(static_cast<uint32_t>((w + kOrBlock - 1) / kOrBlock), static_cast<uint32_t>(segs)), dim3(kOrBlock), 0,
+                           ctx->stream, m.keys.p, w, h, segs, bits.p);
+        PCP_HIP_TRY(ctx, hipGetLastError());
+      }
+      const int rc = mask_edt_of_bits(ctx, bits.p, w, h, segs, col.p, d2.p, nearest.p);
+      if (rc != PCP_OK) return rc;
+    }
+    PCP_HIP_TRY(ctx, hipMemsetAsync(m.scalars.p + OR_OCCUPIED, 0, 2 * 8, ctx->stream));  // occupied, filled
+    {
+      LaunchTimer t(ctx, PCP_K_MISC);
+      hipLaunchKernelGGL(k_or_source, dim3(or_blocks(px)), dim3(kOrBlock), 0, ctx->stream, m.keys.p,
+                         fill_radius_px > 0 ? d2.p : static_cast<const uint32_t *>(nullptr),
+                         fill_radius_px > 0 ? nearest.p : static_cast<const int32_t *>(nullptr), px, fill_radius_px, m.source.p, m.scalars.p);
+      PCP_HIP_TRY(ctx, hipGetLastError());
+    }
+    unsigned long long hs[2];
+    PCP_HIP_TRY(ctx, hipMemcpyAsync(hs, m.scalars.p + OR_OCCUPIED, 2 * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    m.occupied = static_cast<int64_t>(hs[0]);
+    m.filled = static_cast<int64_t>(hs[1]);
+    m.fill_radius = fill_radius_px;
+    m.finished = true;
+  }
+  if (out_occupied) *out_occupied = m.occupied;
+  if (out_filled) *out_filled = m.filled;
+  return PCP_OK;
+}
+
+int pcp_ortho_fetch(pcp_context *ctx, uint32_t *out_index, float *out_depth, uint8_t *out_rgb, uint8_t *out_label, uint8_t *out_status,
+                    int32_t *out_source) {
+  if (!ctx) return PCP_ERR_INVALID;
+  OrthoMap &m = ctx->ortho;
+  if (!m.live) return set_error(ctx, PCP_ERR_STATE, "pcp_ortho_fetch: no accumulation (call pcp_ortho_begin)");
+  if (!m.finished) return set_error(ctx, PCP_ERR_STATE, "pcp_ortho_fetch: pcp_ortho_finish has not run");
+  if (out_label && !m.with_label)
+    return set_error(ctx, PCP_ERR_STATE, "pcp_ortho_fetch: out_label asked of an accumulation that holds no labels (pcp_set_label_fusion)");
+  if (!(out_index || out_depth || out_rgb || out_label || out_status || out_source)) return PCP_OK;
+  PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t px = static_cast<size_t>(m.frame.width) * static_cast<size_t>(m.frame.height);
+  DevBuf<uint32_t> d_index;
+  DevBuf<float> d_depth;
+  DevBuf<uint8_t> d_rgb, d_label, d_status;
+  if (out_index) PCP_HIP_TRY(ctx, d_index.ensure(px + 4));
+  if (out_depth) PCP_HIP_TRY(ctx, d_depth.ensure(px + 4));
+  if (out_rgb) PCP_HIP_TRY(ctx, d_rgb.ensure(3 * px + 16));
+  if (out_label) PCP_HIP_TRY(ctx, d_label.ensure(px + 16));
+  if (out_status) PCP_HIP_TRY(ctx, d_status.ensure(px + 16));
+  if (out_index || out_depth || out_rgb || out_label || out_status) {
+    LaunchTimer t(ctx, PCP_K_MISC);
+    hipLaunchKernelGGL(k_or_layers, dim3(or_blocks(static_cast<int64_t>(px))), dim3(kOrBlock), 0, ctx->stream, static_cast<int64_t>(px),
+                       m.source.p, m.keys.p, m.payload.p, d_index.p, d_depth.p, d_rgb.p, d_label.p, d_status.p);
+    PCP_HIP_TRY(ctx, hipGetLastError());
+  }
+  if (out_index) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_index, d_index.p, 4 * px, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_depth) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_depth, d_depth.p, 4 * px, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_rgb) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_rgb, d_rgb.p, 3 * px, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_label) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_label, d_label.p, px, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_status) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_status, d_status.p, px, hipMemcpyDeviceToHost, ctx->stream));
+  if (out_source) PCP_HIP_TRY(ctx, hipMemcpyAsync(out_source, m.source.p, 4 * px, hipMemcpyDeviceToHost, ctx->stream));
+  PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the layers' device copies are freed on return)
+  return PCP_OK;
+}
+
+int pcp_ortho_stats(pcp_context *ctx, int64_t out[6]) {
+  if (!ctx || !out) return PCP_ERR_INVALID;
+  const OrthoMap &m = ctx->ortho;
+  if (!m.live) return set_error(ctx, PCP_ERR_STATE, "pcp_ortho_stats: no accumulation (call pcp_ortho_begin)");
+  out[0] = m.contributors;
+  out[1] = m.atomics;
+  out[2] = m.occupied;
+  out[3] = m.filled;
+  out[4] = m.adds;
+  out[5] = static_cast<int64_t>(m.frame.width) * m.frame.height;
+  return PCP_OK;
+}
+
+int pcp_ortho_end(pcp_context *ctx) {
+  if (!ctx) return PCP_ERR_INVALID;
+  (void)hipSetDevice(ctx->device);
+  (void)hipStreamSynchronize(ctx->stream);
+  or_drop(ctx);
+  return PCP_OK;
+}
+
+int pcp_ortho_host(const pcp_ortho_frame *frame, int64_t n, const float *xyz, const uint8_t *rgb, const uint8_t *label, const uint8_t *has,
+                   int64_t index_base, int32_t fill_radius_px, uint32_t *out_index, float *out_depth, uint8_t *out_rgb, uint8_t *out_label,
+                   uint8_t *out_status, int32_t *out_source, int64_t *out_contributors, int64_t *out_occupied, int64_t *out_filled) {
+  if (out_contributors) *out_contributors = 0;
+  if (out_occupied) *out_occupied = 0;
+  if (out_filled) *out_filled = 0;
+  if (!frame || n < 0 || (n > 0 && (!xyz || !rgb))) {
+    set_global_error("pcp_ortho_host: NULL frame, negative n or a missing xyz / rgb");
+    return PCP_ERR_INVALID;
+  }
+  char msg[320];
+  const int rc = or_check_frame("pcp_ortho_host", frame, msg, sizeof msg);
+  if (rc != PCP_OK) {
+    set_global_error("%s", msg);
+    return rc;
+  }
+  if (fill_radius_px < 0 || fill_radius_px > om::kMaxFill) {
+    set_global_error("pcp_ortho_host: fill radius %d outside 0..%d pixels", fill_radius_px, om::kMaxFill);
+    return PCP_ERR_INVALID;
+  }
+  if (index_base < 0 || index_base > om::kMaxIndexEnd - n) {  // (index_base + n > 2^32 - 1, without the sum: it may overflow)
+    set_global_error("pcp_ortho_host: index_base %lld with %lld rows: global indices outside 0 .. 2^32 - 2",
+                     static_cast<long long>(index_base), static_cast<long long>(n));
+    return PCP_ERR_RANGE;
+  }
+  const om::Frame f = or_frame(*frame);
+  const int32_t w = frame->width, h = frame->height;
+  const size_t px = static_cast<size_t>(w) * static_cast<size_t>(h);
+  std::vector<unsigned long long> keys;
+  std::vector<uint32_t> payload, d2;
+  std::vector<int32_t> nearest;
+  std::vector<uint8_t> gray;
+  try {
+    keys.assign(px, om::kEmptyKey);
+    payload.assign(px, 0u);
+    if (fill_radius_px > 0) {
+      d2.resize(px);
+      nearest.resize(px);
+      gray.resize(px);
+    }
+  } catch (const std::bad_alloc &) {
+    set_global_error("pcp_ortho_host: out of host memory for %d x %d pixels", w, h);
+    return PCP_ERR_NOMEM;
+  }
+  int64_t contributors = 0;
+  for (int64_t i = 0; i < n; ++i) {  // OM3 and OM4 in one sequential pass: a strictly smaller key takes the pixel
+    if (has && !has[i]) continue;
+    int32_t pixel;
+    uint32_t depth_bits;
+    if (!om::project(f, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], &pixel, &depth_bits)) continue;
+    contributors += 1;
+    const unsigned long long key = om::key_of(depth_bits, static_cast<uint32_t>(index_base + i));
+    if (key < keys[static_cast<size_t>(pixel)]) {
+      keys[static_cast<size_t>(pixel)] = key;
+      const uint32_t word = rgb[3 * i] | (static_cast<uint32_t>(rgb[3 * i + 1]) << 8) | (static_cast<uint32_t>(rgb[3 * i + 2]) << 16);
+      payload[static_cast<size_t>(pixel)] = om::payload_of(word, label ? label[i] : 0u);
+    }
+  }
+  if (fill_radius_px > 0) {  // OM6: occupied pixels are the distance transform's background
+    for (size_t p = 0; p < px; ++p) gray[p] = keys[p] != om::kEmptyKey ? 0 : 255;
+    const int erc = pcp_mask_edt_host(w, h, gray.data(), w, 0, d2.data(), nearest.data());
+    if (erc != PCP_OK) return erc;
+  }
+  int64_t occupied = 0, filled = 0;
+  for (size_t p = 0; p < px; ++p) {
+    int32_t src;
+    if (keys[p] != om::kEmptyKey) {
+      src = static_cast<int32_t>(p);
+      occupied += 1;
+    } else {
+      src = fill_radius_px > 0 ? om::fill_source(d2[p], nearest[p], fill_radius_px) : -1;
+      filled += src >= 0 ? 1 : 0;
+    }
+    uint32_t index = om::kNoIndex, word = 0u;
+    float depth = 0.0f;
+    if (src >= 0) {
+      index = om::key_index(keys[static_cast<size_t>(src)]);
+      depth = om::key_depth(keys[static_cast<size_t>(src)]);
+      word = payload[static_cast<size_t>(src)];
+    }
+    if (out_index) out_index[p] = index;
+    if (out_depth) out_depth[p] = depth;
+    if (out_rgb)
+      for (int c = 0; c < 3; ++c) out_rgb[3 * p + c] = static_cast<uint8_t>(word >> (8 * c));
+    if (out_label) out_label[p] = static_cast<uint8_t>(word >> 24);
+    if (out_status) out_status[p] = src < 0 ? 0 : (static_cast<size_t>(src) == p ? 1 : 2);
+    if (out_source) out_source[p] = src;
+  }
+  if (out_contributors) *out_contributors = contributors;
+  if (out_occupied) *out_occupied = occupied;
+  if (out_filled) *out_filled = filled;
+  return PCP_OK;
+}
+
+int pcp_ortho_fit_frame_host(int64_t n, const float *xyz, const uint8_t *has, const double *viewer, float gsd, pcp_ortho_frame *out) {
+  if (n < 0 || (n > 0 && !xyz) || !out) {
+    set_global_error("pcp_ortho_fit_frame_host: negative n, NULL xyz or NULL frame");
+    return PCP_ERR_INVALID;
+  }
+  if (!(std::isfinite(gsd) && gsd >= 1e-4f && gsd <= 1.0f)) {
+    set_global_error("pcp_ortho_fit_frame_host: gsd %g outside [1e-4, 1]", static_cast<double>(gsd));
+    return PCP_ERR_INVALID;
+  }
+  // centroid, then the covariance about it
+  int64_t rows = 0;
+  double c[3] = {0.0, 0.0, 0.0};
+  for (int64_t i = 0; i < n; ++i) {
+    if (has && !has[i]) continue;
+    rows += 1;
+    for (int a = 0; a < 3; ++a) c[a] += static_cast<double>(xyz[3 * i + a]);
+  }
+  if (rows < 3) {
+    set_global_error("pcp_ortho_fit_frame_host: %lld rows, a plane needs 3", static_cast<long long>(rows));
+    return PCP_ERR_INVALID;
+  }
+  for (int a = 0; a < 3; ++a) c[a] /= static_cast<double>(rows);
+  double m[6] = {0, 0, 0, 0, 0, 0};
+  for (int64_t i = 0; i < n; ++i) {
+    if (has && !has[i]) continue;
+    const double d[3] = {xyz[3 * i] - c[0], xyz[3 * i + 1] - c[1], xyz[3 * i + 2] - c[2]};
+    m[0] += d[0] * d[0];
+    m[1] += d[0] * d[1];
+    m[2] += d[0] * d[2];
+    m[3] += d[1] * d[1];
+    m[4] += d[1] * d[2];
+    m[5] += d[2] * d[2];
+  }
+  double scale = 0.0;
+  for (int k = 0; k < 6; ++k) {
+    m[k] /= static_cast<double>(rows);
+    scale = std::fmax(scale, std::fabs(m[k]));
+  }
+  if (!(scale > DBL_MIN)) scale = 1.0;  // (also takes a NaN on to the finite check below)
+  double a[6], r[3], nn[3], uu[3];
+  for (int k = 0; k < 6; ++k) a[k] = m[k] / scale;
+  or_roots3(a, r);
+  or_eigenvector(a, r[0], nn);
+  or_eigenvector(a, r[2], uu);
+  // signs: the viewer in front of the plane (negative depth), else n's largest component negative; u's largest positive
+  bool flip;
+  if (viewer)
+    flip = ((viewer[0] - c[0]) * nn[0] + (viewer[1] - c[1]) * nn[1]) + (viewer[2] - c[2]) * nn[2] > 0.0;
+  else
+    flip = nn[or_largest_component(nn)] > 0.0;
+  if (flip)
+    for (int k = 0; k < 3; ++k) nn[k] = -nn[k];
+  // (u made exactly orthogonal to n: the two closed-form vectors agree to rounding only)
+  const double un = uu[0] * nn[0] + uu[1] * nn[1] + uu[2] * nn[2];
+  for (int k = 0; k < 3; ++k) uu[k] -= un * nn[k];
+  const double ul = std::sqrt(uu[0] * uu[0] + uu[1] * uu[1] + uu[2] * uu[2]);
+  for (int k = 0; k < 3; ++k) uu[k] /= ul;
+  if (uu[or_largest_component(uu)] < 0.0)
+    for (int k = 0; k < 3; ++k) uu[k] = -uu[k];
+  const double vv[3] = {nn[1] * uu[2] - nn[2] * uu[1], nn[2] * uu[0] - nn[0] * uu[2], nn[0] * uu[1] - nn[1] * uu[0]};
+  // the rows' bounding rectangle on the plane through the centroid
+  double s0 = INFINITY, s1 = -INFINITY, t0 = INFINITY, t1 = -INFINITY;
+  for (int64_t i = 0; i < n; ++i) {
+    if (has && !has[i]) continue;
+    const double d[3] = {xyz[3 * i] - c[0], xyz[3 * i + 1] - c[1], xyz[3 * i + 2] - c[2]};
+    const double s = d[0] * uu[0] + d[1] * uu[1] + d[2] * uu[2], t = d[0] * vv[0] + d[1] * vv[1] + d[2] * vv[2];
+    s0 = std::fmin(s0, s);
+    s1 = std::fmax(s1, s);
+    t0 = std::fmin(t0, t);
+    t1 = std::fmax(t1, t);
+  }
+  const double g = static_cast<double>(gsd);
+  pcp_ortho_frame fr;
+  bool finite = std::isfinite(s0) && std::isfinite(s1) && std::isfinite(t0) && std::isfinite(t1);
+  for (int k = 0; k < 3; ++k) {
+    fr.o[k] = static_cast<float>(c[k] + (s0 - g) * uu[k] + (t0 - g) * vv[k]);  // one pixel outside the rectangle
+    fr.u[k] = static_cast<float>(uu[k]);
+    fr.v[k] = static_cast<float>(vv[k]);
+    fr.n[k] = static_cast<float>(nn[k]);
+    finite = finite && std::isfinite(fr.o[k]) && std::isfinite(fr.u[k]) && std::isfinite(fr.v[k]) && std::isfinite(fr.n[k]);
+  }
+  if (!finite) {
+    set_global_error("pcp_ortho_fit_frame_host: the fit is not finite (a non-finite row, or rows that span no plane)");
+    return PCP_ERR_INVALID;
+  }
+  fr.gsd = gsd;
+  const double wd = std::floor((s1 - s0) / g) + 3.0, hd = std::floor((t1 - t0) / g) + 3.0;  // the rectangle plus two pixels
+  if (wd > om::kMaxSide || hd > om::kMaxSide || wd * hd > static_cast<double>(om::kMaxPixels)) {
+    const double fit = om::fit_gsd(s1 - s0, t1 - t0, 3.0);
+    set_global_error("pcp_ortho_fit_frame_host: %.0f x %.0f pixels at gsd %g exceed 16384 a side or 2^26 pixels; the same extent fits at gsd %.6g",
+                     wd, hd, g, fit);
+    return PCP_ERR_RANGE;
+  }
+  fr.width = static_cast<int32_t>(wd);
+  fr.height = static_cast<int32_t>(hd);
+  // the depth window: the rows' range in the frame's own fp32 arithmetic (OM2), widened by one gsd
+  om::Frame f = or_frame(fr);
+  float dlo = INFINITY, dhi = -INFINITY;
+  for (int64_t i = 0; i < n; ++i) {
+    if (has && !has[i]) continue;
+    const float d[3] = {xyz[3 * i] - f.o[0], xyz[3 * i + 1] - f.o[1], xyz[3 * i + 2] - f.o[2]};
+    const float depth = om::dot3(d, f.n);
+    dlo = std::fmin(dlo, depth);
+    dhi = std::fmax(dhi, depth);
+  }
+  fr.d_min = dlo - gsd;
+  fr.d_max = dhi + gsd;
+  if (!(std::isfinite(fr.d_min) && std::isfinite(fr.d_max))) {
+    set_global_error("pcp_ortho_fit_frame_host: the depth range is not finite");
+    return PCP_ERR_INVALID;
+  }
+  *out = fr;
+  return PCP_OK;
+}
+
+}  // extern "C"

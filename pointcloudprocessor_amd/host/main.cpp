@@ -157,6 +157,22 @@
 //     junctions, loops, skeleton_length_m and the centroids of its end and junction nodes (end_xyz, junction_xyz).  The
 //     reference's script skeletonises each keyframe's mask in 2-D (preprocess(): pcv.morphology.skeletonize).  Made on the GPU
 //     (pcp_crack_skeleton; DESIGN.md "Crack skeletons on the map").  Every other output stays as it is.
+//   * --orthoMap 0|1 (new, default 0), --orthoGsd g (new, default 0.01, metres per pixel, 1e-4..1), --orthoFill R (new, default
+//     0, pixels, 0..1024) and --orthoFrame auto|ox,oy,oz,ux,uy,uz,vx,vy,vz (new, default auto): with 1 the run also writes one
+//     orthographic picture of the coloured cloud, <outputPath>ortho/ortho_rgb.npy (|u1, (H, W, 3)), ortho_depth.npy (<f4,
+//     (H, W): the depth along the viewing direction, 0 on an empty pixel), ortho_index.npy (<u4, (H, W): the row of the
+//     coloured cloud's point behind the pixel -- of the map, or of the smoothed cloud with --enableMLS 1 -- 0xFFFFFFFF on an
+//     empty pixel), ortho_status.npy (|u1: 0 empty, 1 direct, 2 filled from the nearest occupied pixel within R) and
+//     ortho_frame.json (o, u, v, n, gsd, width, height, d_min, d_max: pixel (col, row) at depth d is the world point
+//     o + (col + 0.5) gsd u + (row + 0.5) gsd v + d n).  With --fuseMasks 1 also ortho_label.npy (|u1), with --crackFuse 1
+//     also ortho_width.npy (<f4: map_width.npy[index]) and ortho_crack.npy (<i4: map_crack.npy[index], -1 on an empty pixel).
+//     auto: the plane fitted to the finite points of the map the run read (with --enableMLS 1: of the crop the chain
+//     smooths), seen from the side of the mean keyframe position; nine numbers: origin, image x and image y axes as given,
+//     n = u x v, the raster sized to hold the map's points on the positive side of the origin, the depth window unbounded.
+//     The reference stops at per-keyframe perspective pictures (visualize_skeleton_edge_pts, save_results of
+//     scripts/genNormAndDistanceMask.py).  Made on the GPU (pcp_ortho_*; DESIGN.md "Orthographic maps"); works with
+//     --enableMLS 1 and with --enableMLS 1 --streamColour 1, where the chunks are added as they are coloured.  No other output
+//     changes.  --gpus N above 1 is refused (the shards' key images would merge by an all-reduce(MIN), which is not built).
 #include <cfloat>
 #include <chrono>
 #include <cmath>
@@ -253,6 +269,10 @@ struct Options {
   bool crack_fuse = false;            // --crackFuse 1: the widths on the map and the map's cracks (crack_width/map_*.npy, cracks_3d.json)
   float crack_link_radius = 0.02f;    // --crackLinkRadius r: crack points this close belong to one crack
   int crack_min_views = 1;            // --crackMinViews v: credited keyframes a crack point needs
+  bool ortho_map = false;             // --orthoMap 1: one orthographic picture of the coloured cloud (ortho/ortho_*.npy, ortho_frame.json)
+  float ortho_gsd = 0.01f;            // --orthoGsd g: metres per pixel
+  int ortho_fill = 0;                 // --orthoFill R: empty pixels take their nearest occupied pixel within R pixels
+  std::vector<float> ortho_frame;     // --orthoFrame: empty = auto, else origin, u, v (9 numbers)
 };
 
 static bool parse_bool(const std::string &v) {  // boost::program_options bool semantics
@@ -375,6 +395,42 @@ static Options parse(int argc, char **argv) {
       o.crack_plane_radius = static_cast<int>(r);
     }
     else if (a == "--crackFuse") o.crack_fuse = parse_bool(next());
+    else if (a == "--orthoMap") o.ortho_map = parse_bool(next());
+    else if (a == "--orthoGsd") {
+      const std::string v = next();
+      try {
+        o.ortho_gsd = std::stof(v);
+      } catch (const std::exception &) {
+        o.ortho_gsd = -1.0f;
+      }
+      if (!(o.ortho_gsd >= 1e-4f && o.ortho_gsd <= 1.0f))
+        throw std::runtime_error("the argument ('" + v + "') for option '--orthoGsd' is invalid (1e-4 <= g <= 1)");
+    } else if (a == "--orthoFill") {
+      const std::string v = next();
+      try {
+        o.ortho_fill = std::stoi(v);
+      } catch (const std::exception &) {
+        o.ortho_fill = -1;
+      }
+      if (o.ortho_fill < 0 || o.ortho_fill > 1024)
+        throw std::runtime_error("the argument ('" + v + "') for option '--orthoFill' is invalid (0..1024 pixels)");
+    } else if (a == "--orthoFrame") {
+      const std::string v = next();
+      o.ortho_frame.clear();
+      if (v != "auto") {
+        std::istringstream is(v);
+        std::string tok;
+        bool ok = true;
+        while (std::getline(is, tok, ','))
+          try {
+            o.ortho_frame.push_back(std::stof(tok));
+          } catch (const std::exception &) {
+            ok = false;
+          }
+        if (!ok || o.ortho_frame.size() != 9)
+          throw std::runtime_error("the argument ('" + v + "') for option '--orthoFrame' is invalid (auto, or ox,oy,oz,ux,uy,uz,vx,vy,vz)");
+      }
+    }
     else if (a == "--crackLength") o.crack_length = parse_bool(next());
     else if (a == "--crackSkeleton") o.crack_skeleton = parse_bool(next());
     else if (a == "--crackSkeletonStep") o.crack_skeleton_step = std::stof(next());
@@ -435,6 +491,9 @@ static Options parse(int argc, char **argv) {
   if (o.output_leaf > 0.0f && o.gpus > 1)
     throw std::runtime_error("the option '--outputLeaf' does not work with '--gpus N' above 1 (the voxel sums of the index shards would "
                              "have to be added across GPUs: not built)");
+  if (o.ortho_map && o.gpus > 1)
+    throw std::runtime_error("the option '--orthoMap 1' does not work with '--gpus N' above 1 (an index shard sees only its own "
+                             "points; the shards' key images would merge by an all-reduce(MIN), which is not built)");
   if (o.geometry_maps && o.gpus > 1)
     throw std::runtime_error("the option '--geometryMaps 1' does not work with '--gpus N' above 1 (an index shard sees only its own "
                              "points: the per-pixel keys of the shards would have to be merged across GPUs, which is not built)");
@@ -524,6 +583,10 @@ static void usage(std::ostream &os) {
         "  --crackMinViews arg (=1)              With --crackFuse: keyframes with a width that a crack point needs (1..4096)\n"
         "  --crackLength arg (=0)                With --crackFuse: also write every crack's length, ends and centreline\n"
         "  --crackSkeleton arg (=0)              With --crackFuse: also write every crack's skeleton: branches, junctions, loops\n"
+        "  --orthoMap arg (=0)                   Also write one orthographic picture of the coloured cloud as .npy (--gpus 1)\n"
+        "  --orthoGsd arg (=0.01)                With --orthoMap: metres per pixel (1e-4..1)\n"
+        "  --orthoFill arg (=0)                  With --orthoMap: fill empty pixels from the nearest occupied one within R pixels\n"
+        "  --orthoFrame arg (=auto)              With --orthoMap: auto (fitted plane), or ox,oy,oz,ux,uy,uz,vx,vy,vz\n"
         "  --crackSkeletonStep arg (=0)          With --crackSkeleton: the band width in metres (0: twice the link radius)\n";
 }
 
@@ -579,6 +642,9 @@ class Processor {
   std::vector<uint8_t> mask_missing;
   std::vector<double> T_camera_lidar_optimized;
   pcp_mls_params mls_params{};  // --streamColour 1: the chain's parameters, kept for streamedColourisation
+  std::vector<float> ortho_fit_xyz;    // --orthoMap 1 with --enableMLS 1 (one-shot): the crop the chain smoothed, for the frame
+  std::vector<uint32_t> ortho_index;   // --orthoMap 1: the index layer, for the crack layers --crackFuse 1 adds
+  pcp_ortho_frame ortho_frame_used{};
 
   void loadImagesAndOdometry() {  // :965-1005
     Phase ph("odometry_s");
@@ -662,6 +728,14 @@ class Processor {
         mls_params = mp;
         cloud = std::move(crop8);
         return;
+      }
+      if (opt.ortho_map) {  // (the frame is fitted to the map the run read, as the streamed form fits it)
+        ortho_fit_xyz.resize(3 * crop8.size());
+        for (size_t i = 0; i < crop8.size(); ++i) {
+          ortho_fit_xyz[3 * i] = crop8.x[i];
+          ortho_fit_xyz[3 * i + 1] = crop8.y[i];
+          ortho_fit_xyz[3 * i + 2] = crop8.z[i];
+        }
       }
       if (device_thread.joinable()) device_thread.join();  // (one thread at a time creates contexts: pcp_create sets process-wide defaults)
       MultiCloudSmooth smooth(opt.gpus);  // --gpus N: MLS queries / voxel chunks dealt out over the GPUs (pcp_multi.hpp)
@@ -1053,6 +1127,10 @@ class Processor {
     smoothing.uploadCloud(cloud.x.data(), cloud.y.data(), cloud.z.data(), static_cast<int64_t>(cloud.size()));
     CloudSmooth cs(smoothing, mls_params);
     cs.setLocalPlaneSampling(opt.mls_upsampling_radius, opt.mls_upsampling_step);
+    if (opt.ortho_map) {  // every chunk is added to the map as it is coloured
+      gpu->device(0).orthoBegin(orthoFrame());
+      cs.setOrthoAccumulate(true);
+    }
     const std::string cropPath = opt.outputPath + "scans-crop.pcd";
     const std::string mlsPath = fs::path(cropPath).stem().string() + "_mls.pcd";  // CWD-relative, sic (B14)
     const std::string rgbPath = opt.outputPath + "cloudInWorldWithRGB.pcd", maskPath = opt.outputPath + "cloudInWorldWithRGBandMask.pcd";
@@ -1087,6 +1165,10 @@ class Processor {
     if (opt.output_leaf > 0.0f) {
       g_clock.add("voxel_reduce_add_s", st.voxel_add_s);
       g_clock.add("voxel_reduce_finish_s", st.voxel_finish_s);
+    }
+    if (opt.ortho_map) {
+      g_clock.add("ortho_add_s", st.ortho_add_s);
+      writeOrthoFiles();
     }
     if (!mls) mls.reset(new ChunkedAsciiWriter(mlsPath, ChunkedAsciiWriter::PointNormal, 0));  // no row: the writer's exception
     if (mls->finish() == -1) throw std::runtime_error("Couldn't save the smoothed point cloud.");
@@ -1308,6 +1390,118 @@ class Processor {
               << " credited samples, " << m.crack_points << " crack points, " << m.ids.size() << " cracks" << std::endl;
     if (opt.crack_length) writeCrackLengths(cl, stem);
     if (opt.crack_skeleton) writeCrackSkeleton(sk, m, stem);
+    if (opt.ortho_map) {  // the widths and the cracks drawn on the orthographic map: map_width[index], map_crack[index]
+      const size_t h = static_cast<size_t>(ortho_frame_used.height), w = static_cast<size_t>(ortho_frame_used.width);
+      std::vector<float> width(ortho_index.size(), 0.0f);
+      std::vector<int32_t> crack(ortho_index.size(), -1);
+      // (the index layer names rows of the map the crack chain ran on: --crackFuse 1 is refused with --enableMLS 1)
+      for (size_t p = 0; p < ortho_index.size(); ++p) {
+        if (ortho_index[p] == 0xFFFFFFFFu) continue;
+        if (ortho_index[p] >= n)
+          throw std::runtime_error("the orthographic map's index layer names row " + std::to_string(ortho_index[p]) + " of a map of " +
+                                   std::to_string(n) + " points: the crack layers cannot be drawn");
+        width[p] = m.width_mean[ortho_index[p]];
+        crack[p] = m.label[ortho_index[p]];
+      }
+      writeNpy(opt.outputPath + "ortho/ortho_width.npy", "<f4", {h, w}, width.data(), width.size() * 4);
+      writeNpy(opt.outputPath + "ortho/ortho_crack.npy", "<i4", {h, w}, crack.data(), crack.size() * 4);
+      std::cout << "Orthographic crack layers saved to: " << opt.outputPath << "ortho/ortho_width.npy, ortho_crack.npy" << std::endl;
+    }
+  }
+
+  // --orthoMap 1: the frame.  auto: the plane fitted to the finite points of the map the run read, seen from the side of the
+  // mean keyframe position.  Nine numbers: o, u, v as given, n = u x v, the raster sized to hold the map's points on the
+  // positive side of the origin (one spare pixel: the library rounds in fp32), the depth window unbounded.
+  pcp_ortho_frame orthoFrame() {
+    Phase ph("ortho_frame_s");
+    const bool own = !ortho_fit_xyz.empty();
+    const size_t n = own ? ortho_fit_xyz.size() / 3 : cloud.size();
+    auto at = [&](size_t i, int a) { return own ? ortho_fit_xyz[3 * i + static_cast<size_t>(a)] : (a == 0 ? cloud.x[i] : a == 1 ? cloud.y[i] : cloud.z[i]); };
+    pcp_ortho_frame f{};
+    if (opt.ortho_frame.empty()) {
+      std::vector<float> xyz(3 * n);
+      std::vector<uint8_t> finite(n);
+      for (size_t i = 0; i < n; ++i) {
+        for (int a = 0; a < 3; ++a) xyz[3 * i + static_cast<size_t>(a)] = at(i, a);
+        finite[i] = std::isfinite(xyz[3 * i]) && std::isfinite(xyz[3 * i + 1]) && std::isfinite(xyz[3 * i + 2]) ? 1 : 0;
+      }
+      double viewer[3] = {0.0, 0.0, 0.0};
+      for (const Frame &k : keyframes) {
+        viewer[0] += k.pose.x / static_cast<double>(keyframes.size());
+        viewer[1] += k.pose.y / static_cast<double>(keyframes.size());
+        viewer[2] += k.pose.z / static_cast<double>(keyframes.size());
+      }
+      f = Device::orthoFitFrame(static_cast<int64_t>(n), xyz.data(), finite.data(), keyframes.empty() ? nullptr : viewer, opt.ortho_gsd);
+    } else {
+      const float *v = opt.ortho_frame.data();
+      for (int a = 0; a < 3; ++a) {
+        f.o[a] = v[a];
+        f.u[a] = v[3 + a];
+        f.v[a] = v[6 + a];
+      }
+      f.n[0] = f.u[1] * f.v[2] - f.u[2] * f.v[1];
+      f.n[1] = f.u[2] * f.v[0] - f.u[0] * f.v[2];
+      f.n[2] = f.u[0] * f.v[1] - f.u[1] * f.v[0];
+      f.gsd = opt.ortho_gsd;
+      f.d_min = -FLT_MAX;
+      f.d_max = FLT_MAX;
+      double smax = 0.0, tmax = 0.0;
+      for (size_t i = 0; i < n; ++i) {
+        const double d[3] = {at(i, 0) - static_cast<double>(f.o[0]), at(i, 1) - static_cast<double>(f.o[1]), at(i, 2) - static_cast<double>(f.o[2])};
+        if (!std::isfinite(d[0]) || !std::isfinite(d[1]) || !std::isfinite(d[2])) continue;
+        smax = std::max(smax, d[0] * f.u[0] + d[1] * f.u[1] + d[2] * f.u[2]);
+        tmax = std::max(tmax, d[0] * f.v[0] + d[1] * f.v[1] + d[2] * f.v[2]);
+      }
+      f.width = static_cast<int32_t>(std::min(1e9, std::floor(smax / opt.ortho_gsd) + 2.0));
+      f.height = static_cast<int32_t>(std::min(1e9, std::floor(tmax / opt.ortho_gsd) + 2.0));
+    }
+    ortho_frame_used = f;
+    return f;
+  }
+  // the one-shot path: the colour result that was just made (and smoothed), drawn where it lies
+  void writeOrthoMap() {
+    {
+      Phase ph("ortho_gpu_s");
+      Device &dev = gpu->device(0);
+      dev.orthoBegin(orthoFrame());
+      (void)dev.orthoAdd(0);
+    }
+    writeOrthoFiles();
+  }
+  // the map begun on the colour context, finished with --orthoFill, as <out>ortho/ortho_*.npy and ortho_frame.json; then dropped
+  void writeOrthoFiles() {
+    Device &dev = gpu->device(0);
+    OrthoMap m;
+    {
+      Phase ph("ortho_finish_gpu_s");
+      m = dev.orthoFetch(opt.ortho_fill, opt.fuse_masks);
+      dev.orthoEnd();
+    }
+    Phase ph_w("ortho_write_s");
+    const std::string stem = opt.outputPath + "ortho/";
+    fs::create_directories(fs::path(stem));
+    const size_t h = static_cast<size_t>(m.frame.height), w = static_cast<size_t>(m.frame.width);
+    writeNpy(stem + "ortho_rgb.npy", "|u1", {h, w, 3}, m.rgb.data(), m.rgb.size());
+    writeNpy(stem + "ortho_depth.npy", "<f4", {h, w}, m.depth.data(), m.depth.size() * 4);
+    writeNpy(stem + "ortho_index.npy", "<u4", {h, w}, m.index.data(), m.index.size() * 4);
+    writeNpy(stem + "ortho_status.npy", "|u1", {h, w}, m.status.data(), m.status.size());
+    if (opt.fuse_masks) writeNpy(stem + "ortho_label.npy", "|u1", {h, w}, m.label.data(), m.label.size());
+    std::ofstream f(stem + "ortho_frame.json");
+    auto num = [](double v) {
+      char b[64];
+      std::snprintf(b, sizeof(b), "%.9g", v);
+      return std::string(b);
+    };
+    auto vec = [&](const float *v) { return "[" + num(v[0]) + ", " + num(v[1]) + ", " + num(v[2]) + "]"; };
+    f << "{\"o\": " << vec(m.frame.o) << ", \"u\": " << vec(m.frame.u) << ", \"v\": " << vec(m.frame.v) << ", \"n\": " << vec(m.frame.n)
+      << ", \"gsd\": " << num(m.frame.gsd) << ", \"width\": " << m.frame.width << ", \"height\": " << m.frame.height
+      << ", \"d_min\": " << num(m.frame.d_min) << ", \"d_max\": " << num(m.frame.d_max) << ", \"fill_radius\": " << opt.ortho_fill
+      << ", \"contributors\": " << m.contributors << ", \"occupied\": " << m.occupied << ", \"filled\": " << m.filled << "}\n";
+    f.close();
+    if (!f) throw std::runtime_error("Couldn't save the orthographic map's frame.");
+    std::cout << "Orthographic map saved to: " << stem << "ortho_*.npy and ortho_frame.json, " << m.frame.width << " x " << m.frame.height
+              << " pixels, " << m.occupied << " occupied, " << m.filled << " filled" << std::endl;
+    if (opt.crack_fuse) ortho_index = std::move(m.index);
   }
 
   // --crackSkeleton 1: every crack's level-set diagram on the map: nodes, edges, ends, junctions, loops and skeleton length
@@ -1459,6 +1653,7 @@ class Processor {
         dev.check(pcp_colour_smooth_local(dev.get(), opt.smooth_colors_radius, &coloured));
       }
       reduceToVoxels();
+      if (opt.ortho_map) writeOrthoMap();
       if (opt.crack_fuse) writeCrackFuse();
       return;
     }
@@ -1474,6 +1669,7 @@ class Processor {
       gpu->smoothColorsWithLocalRegion(opt.smooth_colors_radius, rgb, has);
     }
     if (opt.output_leaf > 0.0f) reduceToVoxels();  // (of the colour result as it lies on the device now)
+    if (opt.ortho_map) writeOrthoMap();             // (likewise; before --crackFuse, whose layers it gathers by the index layer)
     if (opt.crack_fuse) writeCrackFuse();           // (it reads the raw map and the masks; the colour result stays as it is)
     std::vector<uint8_t> label;
     if (opt.fuse_masks) {

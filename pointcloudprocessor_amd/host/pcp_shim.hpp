@@ -34,6 +34,18 @@ struct VoxelCloud {
   std::vector<uint32_t> count;  // rows of the coloured cloud in the voxel
 };
 
+// An orthographic map (pcp_hip.h, "orthographic maps"): layers of frame.width x frame.height, row-major
+struct OrthoMap {
+  pcp_ortho_frame frame{};
+  int64_t contributors = 0, occupied = 0, filled = 0;
+  std::vector<uint32_t> index;   // global index of the point behind the pixel, 0xFFFFFFFF: empty
+  std::vector<float> depth;      // its depth along n, 0 when empty
+  std::vector<uint8_t> rgb;      // 3 per pixel
+  std::vector<uint8_t> label;    // fused label per pixel (asked for and held), else empty
+  std::vector<uint8_t> status;   // 0 empty, 1 direct, 2 filled
+  std::vector<int32_t> source;   // linear index of the pixel the values come from, -1: empty
+};
+
 // The geometry maps of one keyframe (pcp_hip.h, "geometry maps"): images of `width` x `height`, row-major
 struct GeometryMaps {
   int32_t width = 0, height = 0;
@@ -229,6 +241,54 @@ class Device {
   }
   void voxelReduceEnd() { check(pcp_voxel_reduce_end(ctx_)); }
 
+  // ---- orthographic maps: one metric picture of the coloured cloud, accumulated on the device over any number of colour
+  // results (pcp_ortho_*; DESIGN.md "Orthographic maps") ----
+  void orthoBegin(const pcp_ortho_frame &frame) {
+    check(pcp_ortho_begin(ctx_, &frame));
+    ortho_frame_ = frame;  // (only of a begin the library took: a refused one leaves the live map, and its frame, as they were)
+  }
+  int64_t orthoAdd(int64_t index_base = 0) {  // the coloured rows of the current colour result; returns the contributors
+    int64_t rows = 0;
+    check(pcp_ortho_add(ctx_, index_base, &rows));
+    return rows;
+  }
+  int64_t orthoAddPacked(const uint32_t *rgba, int64_t index_base = 0) {  // cloudSize() words r | g<<8 | b<<16 | has<<24
+    int64_t rows = 0;
+    check(pcp_ortho_add_packed(ctx_, rgba, index_base, &rows));
+    return rows;
+  }
+  // finish (fill_radius_px > 0: empty pixels take their nearest occupied pixel within it) and fetch every layer
+  // (the layers are sized by the frame of the last orthoBegin that succeeded on this Device: the live map's)
+  OrthoMap orthoFetch(int32_t fill_radius_px, bool with_label) {
+    OrthoMap m;
+    const pcp_ortho_frame &frame = m.frame = ortho_frame_;
+    check(pcp_ortho_finish(ctx_, fill_radius_px, &m.occupied, &m.filled));
+    m.contributors = orthoStats()[0];
+    const size_t px = static_cast<size_t>(frame.width) * static_cast<size_t>(frame.height);
+    m.index.resize(px);
+    m.depth.resize(px);
+    m.rgb.resize(3 * px);
+    m.label.resize(with_label ? px : 0);
+    m.status.resize(px);
+    m.source.resize(px);
+    check(pcp_ortho_fetch(ctx_, m.index.data(), m.depth.data(), m.rgb.data(), with_label ? m.label.data() : nullptr, m.status.data(),
+                          m.source.data()));
+    return m;
+  }
+  std::vector<int64_t> orthoStats() const {  // contributors, atomics issued, occupied, filled, adds, pixels
+    std::vector<int64_t> s(6);
+    check(pcp_ortho_stats(ctx_, s.data()));
+    return s;
+  }
+  void orthoEnd() { check(pcp_ortho_end(ctx_)); }
+  // the frame that looks straight at n rows (xyz interleaved; has nullable) from the side of `viewer` (3 doubles, nullable)
+  static pcp_ortho_frame orthoFitFrame(int64_t n, const float *xyz, const uint8_t *has, const double *viewer, float gsd) {
+    pcp_ortho_frame f{};
+    if (pcp_ortho_fit_frame_host(n, xyz, has, viewer, gsd, &f) != PCP_OK)
+      throw std::runtime_error(std::string("pcp_hip: ") + pcp_last_error(nullptr));
+    return f;
+  }
+
   // ---- geometry maps: a normal per point of the uploaded map, once per upload (pcp_estimate_normals; what
   // generate_norm_masks estimates per keyframe with Open3D, scripts/genNormAndDistanceMask.py:200-231); returns the valid points
   int64_t estimateNormals(float radius) {
@@ -268,6 +328,7 @@ class Device {
 
  private:
   pcp_context *ctx_ = nullptr;
+  pcp_ortho_frame ortho_frame_{};  // of the live orthographic map
 };
 
 // vlcal::ViewCulling with the z-buffer routine (view_culling.cpp:52-174)
@@ -454,6 +515,17 @@ class Colorizer {
     has.resize(n);
     dev_.check(pcp_colour_finalise(dev_.get(), rgb.data(), has.data(), nullptr, nullptr, nullptr, nullptr));
   }
+  // One orthographic picture of the colour result colorize() / finalise() left on the device (DESIGN.md "Orthographic maps"):
+  // begin, one add under the input indices, finish with the fill radius, fetch, end.  with_label: after a run with label fusion.
+  OrthoMap orthoMap(const pcp_ortho_frame &frame, int32_t fill_radius_px = 0, bool with_label = false) const {
+    dev_.orthoBegin(frame);
+    struct End {  // also on the way out of an exception
+      Device &d;
+      ~End() { (void)pcp_ortho_end(d.get()); }
+    } end{dev_};
+    (void)dev_.orthoAdd(0);
+    return dev_.orthoFetch(fill_radius_px, with_label);
+  }
   // the same result left on the device (for pcp_colour_smooth_local, pcp_colour_compact, pcp_voxel_reduce_add): nothing is fetched
   void finaliseOnDevice() const {
     dev_.check(pcp_colour_finalise(dev_.get(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
@@ -577,6 +649,7 @@ struct StreamedColourStats {
   double sweep_a_s = 0.0, sweep_b_s = 0.0;  // host-clock seconds, the sinks included
   int64_t voxels = 0;                       // output_leaf > 0: rows of the voxel-grid output
   double voxel_add_s = 0.0, voxel_finish_s = 0.0;
+  double ortho_add_s = 0.0;                 // setOrthoAccumulate(true): the chunks' pcp_ortho_add calls
 };
 // the largest cloud one upload takes (pcp_upload_cloud*: n < 2^31)
 constexpr int64_t kMaxUploadPoints = (int64_t(1) << 31) - 1;
@@ -592,6 +665,10 @@ class CloudSmooth {
     slp_radius_ = radius;
     slp_step_ = step;
   }
+  // processAndColorizeStreamed*: every chunk, once coloured, is also added to the orthographic map the caller has begun on the
+  // colour device (Device::orthoBegin), under index_base = the rows of the chunks before it -- its rows' places in the
+  // concatenated smoothed cloud; the caller finishes, fetches and ends the map after the call (Device::orthoFetch / orthoEnd)
+  void setOrthoAccumulate(bool on) { ortho_accumulate_ = on; }
   // the whole CloudSmooth::process: SOR -> MLS (+ upsampling) -> SOR (cloudSmooth.cpp:109-164)
   SmoothedCloud processWithOutlierRemoval() const { return run(true); }
   // pcl::MovingLeastSquares::process alone
@@ -766,6 +843,7 @@ class CloudSmooth {
     t0 = clock::now();
     if (output_leaf > 0.0f) colour.voxelReduceBegin(output_leaf);
     dev_.check(pcp_cloud_smooth_stream_seek(src, 0));
+    int64_t rows_before = 0;
     for (int32_t c = 0; c < st.chunks; ++c) {
       int64_t m = 0, n = 0;
       dev_.check(pcp_cloud_smooth_stream_next(src, &m));
@@ -780,6 +858,13 @@ class CloudSmooth {
         (void)colour.voxelReduceAdd();
         st.voxel_add_s += std::chrono::duration<double>(clock::now() - t1).count();
       }
+      if (ortho_accumulate_) {
+        colour.check(pcp_synchronize(dst));
+        const auto t1 = clock::now();
+        (void)colour.orthoAdd(rows_before);
+        st.ortho_add_s += std::chrono::duration<double>(clock::now() - t1).count();
+      }
+      rows_before += m;
       st.coloured += after_b(m);
     }
     if (output_leaf > 0.0f) {
@@ -831,6 +916,7 @@ class CloudSmooth {
   mutable bool resident_ = false;
   pcp_mls_params params_;
   double slp_radius_ = 0.05, slp_step_ = 0.01;
+  bool ortho_accumulate_ = false;
 };
 
 }  // namespace pcp_amd

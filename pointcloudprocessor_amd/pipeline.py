@@ -172,6 +172,52 @@ class PointCloudColorizer:
         finally:
             ctx.voxel_reduce_end()
 
+    def ortho_map(self, frame="auto", gsd: float = 0.01, fill_radius: int = 0, crack_map: dict | None = None, xyz=None,
+                  viewer=None) -> dict:
+        """One orthographic picture of the colour result run() left on the device ("Orthographic maps"): dict(index
+        (H, W) uint32 with 0xFFFFFFFF for an empty pixel, depth (H, W), rgb (H, W, 3), status (H, W) 0 empty / 1 direct /
+        2 filled, source (H, W), frame (the dict that takes a pixel back to world coordinates), occupied, filled,
+        contributors, and label (H, W) when the run fused labels).  The nearest coloured point wins a pixel; fill_radius > 0
+        fills empty pixels from their nearest occupied pixel within that many pixels.
+
+        frame: a dict(o, u, v, n, gsd, width, height, d_min, d_max), or "auto": the plane fitted on the host
+        (capi.ortho_fit_frame_host) to the coloured rows of `xyz` -- the uploaded map as the caller holds it, (n, 3) or
+        (x, y, z); nothing of it is kept here -- at `gsd` metres per pixel, seen from the side of `viewer` (3 numbers, e.g.
+        the mean keyframe position; None: n's largest component negative).
+        crack_map: the dict crack_map() returned (None: the one its last call on this object left, when it is of this
+        cloud's size): the result gains width (H, W) float32 and crack (H, W) int32, gathered on the host as width_mean[index]
+        and label[index], 0 and -1 on empty pixels.
+
+        An index shard sees only its own points, so world > 1 raises ValueError.  (The shards' key images would merge by an
+        all-reduce(MIN); not built.)"""
+        if self.world > 1:
+            raise ValueError("ortho_map: an index shard sees only its own points; the per-pixel keys of the shards would "
+                             "have to be merged across ranks (all-reduce MIN), which is not built: run it on one rank "
+                             "holding the whole map")
+        ctx = self.engine.ctx
+        if isinstance(frame, str):
+            if frame != "auto":
+                raise ValueError(f"ortho_map: frame {frame!r} is neither a dict nor \"auto\"")
+            xyz = _rows_xyz("ortho_map", xyz, ctx.n)
+            has = (ctx.download_result_packed() >> 24).astype("uint8")
+            frame = capi.ortho_fit_frame_host(xyz, gsd, has=has, viewer=viewer)
+        fuse_labels = bool(getattr(self.engine, "fuse_labels", False))
+        ctx.ortho_begin(frame)
+        try:
+            contributors = ctx.ortho_add(0)
+            occupied, filled = ctx.ortho_finish(fill_radius)
+            out = ctx.ortho_fetch(want_label=fuse_labels)
+        finally:
+            ctx.ortho_end()
+        out.update(frame=capi.ortho_frame(frame).as_dict(), contributors=contributors, occupied=occupied, filled=filled)
+        if crack_map is None:
+            crack_map = getattr(self, "last_crack_map", None)
+            if crack_map is not None and len(crack_map["label"]) != ctx.n:
+                crack_map = None  # (of a cloud that has been replaced)
+        if crack_map is not None:
+            out.update(ortho_crack_layers(out["index"], crack_map["width_mean"], crack_map["label"]))
+        return out
+
     def geometry_maps(self, frame: int, normal_radius: float = 0.1) -> dict:
         """The geometry maps of one keyframe at camera resolution, reduced on the device ("Geometry maps"):
         dict(index (H, W) int32 with -1 for an empty pixel, range (H, W), xyz_cam (H, W, 3), pixels, and -- with
@@ -242,6 +288,7 @@ class PointCloudColorizer:
                 out["skeleton"] = ctx.crack_skeleton(min_views, link_radius, skeleton_step)
             out["contributors"] = [c[0] for c in counts]
             out["credited"] = [c[1] for c in counts]
+            self.last_crack_map = dict(width_mean=out["width_mean"], label=out["label"])  # (ortho_map draws them)
             return out
         finally:
             ctx.crack_fuse_end()
@@ -360,6 +407,31 @@ class PointCloudColorizer:
             for c, k in enumerate(extra):
                 more[k][lo:hi] = a[: hi - lo, 4 + c]
         return dict(rgb=rgb, has=has, **more)
+
+
+def _rows_xyz(who: str, xyz, n: int | None = None):
+    """the map an "auto" orthographic frame is fitted to, as (rows, 3) float32: given as that, or as (x, y, z)"""
+    import numpy as np
+
+    if xyz is None:
+        raise ValueError(f"{who}: frame \"auto\" is fitted to the map: pass it as xyz (or pass a frame dict)")
+    if isinstance(xyz, (tuple, list)) and len(xyz) == 3 and np.ndim(xyz[0]) == 1:
+        xyz = np.stack([np.asarray(a, np.float32) for a in xyz], axis=1)
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    if n is not None and len(xyz) != n:
+        raise ValueError(f"{who}: xyz has {len(xyz)} rows, the uploaded cloud {n}")
+    return xyz
+
+
+def ortho_crack_layers(index, map_width, map_crack) -> dict:
+    """width (H, W) float32 and crack (H, W) int32 of an orthographic map from its index layer and the per-point arrays of the
+    crack chain on the map: map_width[index] and map_crack[index], 0 and -1 on empty pixels."""
+    import numpy as np
+
+    empty = index == np.uint32(0xFFFFFFFF)
+    at = np.where(empty, 0, index).astype(np.int64)
+    return dict(width=np.where(empty, np.float32(0), np.asarray(map_width, np.float32)[at]).astype(np.float32),
+                crack=np.where(empty, -1, np.asarray(map_crack, np.int32)[at]).astype(np.int32))
 
 
 def keyframe_block(n_frames: int, rank: int, world: int):
@@ -654,7 +726,7 @@ class CloudSmooth:
                 ctx.cloud_smooth_stream_end()
 
     def process_and_colourise_streamed(self, colour_engine: HipEngine, chunk_capacity: int = 1 << 28, fuse_labels: bool = False,
-                                       on_smoothed=None, download: bool = True, output_leaf: float = 0.0):
+                                       on_smoothed=None, download: bool = True, output_leaf: float = 0.0, ortho: dict | None = None):
         """CloudSmooth::process followed by the colourisation of the smoothed cloud (PointCloudProcessor.cpp:139-145, 474-602)
         for clouds whose smoothed rows exceed one upload: the mirror of the C++ shim's processAndColorizeStreamed.  A chunk of
         the chain's voxel order is an index shard in time -- the depth maps are a MIN over all points and a point's colour
@@ -675,7 +747,34 @@ class CloudSmooth:
         that edge ("Voxel-grid output"): an accumulation begins before sweep B, takes every chunk after it is
         coloured and is finished after the sweep; `self.voxel_output` then holds dict(xyz, rgb, count[, label]) and
         `self.streamed_colour` gains voxel_add_s, voxel_finish_s and the accumulator's stats.  With download=False these rows
-        are all that leaves the device."""
+        are all that leaves the device.
+
+        ortho: dict(frame, gsd, fill_radius[, xyz, viewer]) -- one orthographic map of all the coloured rows (DESIGN.md,
+        "Orthographic maps"): the frame is resolved and the map begun on `colour_engine` before any other work (a bad frame or
+        a gsd too fine for the extent is refused at once), every chunk is added after it is coloured under index_base = the
+        rows of the chunks before it (the row's place in the concatenated smoothed cloud), the map is finished and fetched
+        after sweep B; `self.ortho_output` then holds the layers, the frame and the counts, and `self.streamed_colour` gains
+        ortho_add_s and ortho_finish_s.  frame "auto" (the default): fitted on the host to `xyz`, the raw map the caller
+        uploaded to this engine ((n, 3) or (x, y, z)) -- the same surface up to the chain's dilation -- seen from the side
+        of `viewer` (3 numbers, e.g. the mean keyframe position).  Works with download=False: the map is then, with the voxel
+        rows, all that leaves."""
+        ctx, col = self.engine.ctx, colour_engine.ctx
+        if ortho is not None:
+            frame = ortho.get("frame", "auto")
+            if isinstance(frame, str):
+                if frame != "auto":
+                    raise ValueError(f"ortho: frame {frame!r} is neither a dict nor \"auto\"")
+                frame = capi.ortho_fit_frame_host(_rows_xyz("ortho", ortho.get("xyz")), ortho.get("gsd", 0.01), viewer=ortho.get("viewer"))
+            col.ortho_begin(frame)  # (the map outlives the chunks' uploads; ended below whatever happens)
+        try:
+            yield from self._streamed_sweeps(colour_engine, chunk_capacity, fuse_labels, on_smoothed, download, output_leaf,
+                                             ortho, frame if ortho is not None else None)
+        finally:
+            if ortho is not None:
+                col.ortho_end()
+
+    def _streamed_sweeps(self, colour_engine, chunk_capacity, fuse_labels, on_smoothed, download, output_leaf, ortho, frame):
+        """the two sweeps of process_and_colourise_streamed; `frame`: of the orthographic map begun on colour_engine"""
         import time
 
         ctx, col = self.engine.ctx, colour_engine.ctx
@@ -700,7 +799,10 @@ class CloudSmooth:
             col.synchronize()
             stats["sweep_a_s"] = time.perf_counter() - t0
             t0 = time.perf_counter()
-            self.voxel_output = None
+            self.voxel_output = self.ortho_output = None
+            if ortho is not None:
+                stats["ortho_add_s"] = 0.0
+                rows_before = 0
             if output_leaf:
                 col.voxel_reduce_begin(output_leaf)
                 stats["voxel_add_s"] = 0.0
@@ -720,6 +822,12 @@ class CloudSmooth:
                     col.voxel_reduce_add()
                     stats["voxel_add_chunk_s"].append(time.perf_counter() - t1)
                     stats["voxel_add_s"] += stats["voxel_add_chunk_s"][-1]
+                if ortho is not None:
+                    col.synchronize()
+                    t1 = time.perf_counter()
+                    col.ortho_add(rows_before)
+                    stats["ortho_add_s"] += time.perf_counter() - t1
+                    rows_before += m
                 out = col.colour_compact(capacity=None if download else 0, want_label=fuse_labels and download)
                 count = out.pop("count")
                 stats["coloured"] += count
@@ -735,6 +843,14 @@ class CloudSmooth:
                 self.voxel_output = col.voxel_reduce_fetch(want_label=fuse_labels)
                 stats["voxel_finish_s"] = time.perf_counter() - t1
                 stats["voxel"] = col.voxel_reduce_stats()
+            if ortho is not None:
+                t1 = time.perf_counter()
+                occupied, filled = col.ortho_finish(int(ortho.get("fill_radius", 0)))
+                self.ortho_output = col.ortho_fetch(want_label=fuse_labels)
+                stats["ortho_finish_s"] = time.perf_counter() - t1
+                stats["ortho"] = col.ortho_stats()
+                self.ortho_output.update(frame=capi.ortho_frame(frame).as_dict(), occupied=occupied, filled=filled,
+                                         contributors=stats["ortho"]["contributors"])
             stats["sweep_b_s"] = time.perf_counter() - t0
         finally:
             if output_leaf:
