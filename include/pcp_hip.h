@@ -74,7 +74,10 @@ extern "C" {
                                 _cracks_fetch / _host (crack skeletons on the map; nothing runs unless called);
                                 entry points added, no layout changed: pcp_ortho_begin / _add / _add_packed / _finish / _fetch /
                                 _stats / _end, pcp_ortho_host, pcp_ortho_fit_frame_host (orthographic maps; nothing runs unless
-                                called) */
+                                called);
+                                entry points added, no layout changed: pcp_default_balance_params, pcp_set_image_balance,
+                                pcp_image_balance, pcp_image_balance_host, pcp_gamma_table_host (keyframe colour balance at upload;
+                                off by default) */
 
 #define PCP_OK 0
 #define PCP_ERR_INVALID (-1) /* bad argument */
@@ -853,6 +856,52 @@ int pcp_ortho_host(const pcp_ortho_frame *frame, int64_t n, const float *xyz, co
  * rows, a gsd outside [1e-4, 1] or a non-finite result: PCP_ERR_INVALID; a size past the limits: PCP_ERR_RANGE, the gsd that
  * fits in the message (pcp_last_error(NULL)). */
 int pcp_ortho_fit_frame_host(int64_t n, const float *xyz, const uint8_t *has, const double *viewer, float gsd, pcp_ortho_frame *out);
+
+/* ---- keyframe colour balance (scripts/image_color_balance_autonomous.py, scripts/image_color_balance.py) */
+/* CLAHE on a lightness channel and a gamma table, applied on the device to every keyframe as it is uploaded instead of being
+ * run over the keyframe folder beforehand and written back as new JPEGs ("Image balance", IB1-IB9).  Opt-in:
+ * off by default, nothing runs unless pcp_set_image_balance turns it on, PCP_ABI_VERSION is unchanged and a caller detects
+ * support by the symbols.  pcp_image_balance's kernels are timed under PCP_K_MISC.
+ *
+ * Stated differences from the scripts: the lightness channel is V of the 8-bit BGR -> HSV conversion pcp_set_image_adjust
+ * uses, not L of 8-bit Lab (apply_clahe, image_color_balance_autonomous.py:17-23 and image_color_balance.py:34-40: cvtColor
+ * BGR2LAB, clahe.apply(l), merge, LAB2BGR), and the balanced pixels are never re-encoded as JPEG (cv2.imwrite,
+ * image_color_balance_autonomous.py:110, image_color_balance.py:81).  Parity with OpenCV's pixels is unpinned. */
+#define PCP_BALANCE_CLAHE 1 /* steps 1-3: V -> CLAHE -> back to BGR (apply_clahe, image_color_balance_autonomous.py:100) */
+#define PCP_BALANCE_GAMMA 2 /* step 4: the table on B, G, R (adjust_gamma, image_color_balance_autonomous.py:25-28, :103) */
+typedef struct pcp_balance_params {
+  int32_t stages;           /* PCP_BALANCE_* bits; 0 = off */
+  int32_t tiles_x, tiles_y; /* tileGridSize, each 1..16 */
+  float clip_limit;         /* clipLimit; <= 0: no clipping */
+  float gamma;              /* adjust_gamma's gamma, > 0; 1 = identity table */
+} pcp_balance_params;
+/* image_color_balance_autonomous.py:116-120 main(): clip 1.0, tiles 8 x 8, gamma 0.8, both stages (image_color_balance.py:74,77:
+ * clip 3.0, gamma 1.1) */
+void pcp_default_balance_params(pcp_balance_params *p);
+/* Applies to images uploaded afterwards through pcp_upload_image[_async], pcp_upload_images_block and
+ * pcp_upload_image_jpeg[_async], like pcp_set_image_adjust: the texels of a keyframe uploaded with balance on are, bit for
+ * bit, those of the same upload with balance off from the image pcp_image_balance_host produces; pcp_set_image_adjust's
+ * round trip, when enabled, comes after the balance, and the mask byte is untouched.  NULL or stages == 0: off.  Tiles
+ * outside 1..16, gamma <= 0, a non-finite value or unknown stage bits: PCP_ERR_INVALID and the setting is unchanged.  With
+ * CLAHE on, an upload to a camera whose image the tile grid cannot be reflected over (see below) returns PCP_ERR_RANGE. */
+int pcp_set_image_balance(pcp_context *ctx, const pcp_balance_params *params);
+/* Host only, no context, no GPU: w x h BGR8 rows in, w x h tightly packed BGR8 out (out_bgr nullable), by the arithmetic the
+ * kernels use (csrc/pcp_image_balance.hpp).  out_hist (nullable): the raw per-tile V histograms before clipping,
+ * tiles_y * tiles_x * 256; out_lut (nullable): the per-tile tables, tiles_y * tiles_x * 256 bytes; both written only with
+ * PCP_BALANCE_CLAHE.  When w % tiles_x or h % tiles_y is not 0 the image counts as extended to the right by
+ * tiles_x - w % tiles_x columns and at the bottom by tiles_y - h % tiles_y rows (a side that divides evenly by a whole
+ * tiles_x / tiles_y, as OpenCV does), read through BORDER_REFLECT_101; an extension >= w or >= h: PCP_ERR_RANGE.  Bad
+ * parameters (as above), w or h < 1, a NULL image or a row stride < 3 w: PCP_ERR_INVALID.  Message at pcp_last_error(NULL). */
+int pcp_image_balance_host(const pcp_balance_params *params, int32_t w, int32_t h, const uint8_t *bgr, int64_t row_stride_bytes,
+                           uint8_t *out_bgr, uint32_t *out_hist, uint8_t *out_lut);
+/* The same on the device for an arbitrary image, independent of the camera and of pcp_set_image_balance / _adjust: the pack,
+ * histogram, table and apply kernels the upload path runs, on scratch texels, and an unpack.  Synchronous; it waits for
+ * uploads in flight.  Same arguments, outputs and returns as the host form. */
+int pcp_image_balance(pcp_context *ctx, const pcp_balance_params *params, int32_t w, int32_t h, const uint8_t *bgr,
+                      int64_t row_stride_bytes, uint8_t *out_bgr, uint32_t *out_hist, uint8_t *out_lut);
+/* adjust_gamma (image_color_balance_autonomous.py:25-28): table[i] = (uint8)(pow(i / 255.0, 1.0 / gamma) * 255.0), fp64, truncated.  gamma <= 0 or not
+ * finite: PCP_ERR_INVALID. */
+int pcp_gamma_table_host(float gamma, uint8_t out[256]);
 
 /* ---- geometry maps (scripts/genNormAndDistanceMask.py: class Crack, generate_norm_masks :200-231, generate_distance_masks :233-266) */
 /* A normal per point of the uploaded map and, per keyframe, the images the crack measurement reads: range, camera position,

@@ -129,7 +129,7 @@ def load(build_if_needed: bool = True) -> C.CDLL:
     L.pcp_frame_count.argtypes = [C.c_void_p]
     L.pcp_destroy.restype = None
     L.pcp_destroy.argtypes = [C.c_void_p]
-    for name in ("pcp_default_camera", "pcp_default_cull_params", "pcp_default_mls_params"):
+    for name in ("pcp_default_camera", "pcp_default_cull_params", "pcp_default_mls_params", "pcp_default_balance_params"):
         getattr(L, name).restype = None
     _lib = L
     return L
@@ -396,6 +396,83 @@ def mask_edt_host(gray, threshold: int = 0) -> dict:
     if rc != PCP_OK:
         raise PcpError(rc, L.pcp_last_error(None).decode())
     return dict(d2=d2, nearest=nearest)
+
+
+class BalanceParams(C.Structure):
+    """pcp_balance_params (20 bytes): stages (BALANCE_CLAHE | BALANCE_GAMMA), tiles, clip limit, gamma"""
+    _fields_ = [("stages", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("clip_limit", C.c_float), ("gamma", C.c_float)]
+
+
+BALANCE_CLAHE, BALANCE_GAMMA = 1, 2
+
+
+def balance_params(stages: int | None = None, tiles=None, clip_limit: float | None = None, gamma: float | None = None) -> BalanceParams:
+    """pcp_default_balance_params (the autonomous script's main(): both stages, 8 x 8 tiles, clip 1.0, gamma 0.8) with the
+    given fields replaced; tiles = (tiles_x, tiles_y)."""
+    p = BalanceParams()
+    load().pcp_default_balance_params(C.byref(p))
+    if stages is not None:
+        p.stages = int(stages)
+    if tiles is not None:
+        p.tiles_x, p.tiles_y = int(tiles[0]), int(tiles[1])
+    if clip_limit is not None:
+        p.clip_limit = float(clip_limit)
+    if gamma is not None:
+        p.gamma = float(gamma)
+    return p
+
+
+def _as_balance(balance) -> BalanceParams | None:
+    """None / False: off; True: the defaults; a dict: balance_params(**dict); a BalanceParams as it is"""
+    if balance is None or balance is False:
+        return None
+    if balance is True:
+        return balance_params()
+    if isinstance(balance, dict):
+        return balance_params(**balance)
+    return balance
+
+
+def _balance_call(fn, who, head, params, bgr, want_stages: bool):
+    bgr = np.asarray(bgr, np.uint8)
+    if bgr.ndim != 3 or bgr.shape[2] != 3:
+        raise ValueError(f"{who}: a (H, W, 3) BGR image is needed, got shape {bgr.shape}")
+    if bgr.size and (bgr.strides[2] != 1 or bgr.strides[1] != 3):
+        bgr = np.ascontiguousarray(bgr)
+    hh, ww = bgr.shape[:2]
+    p = _as_balance(params) or BalanceParams()
+    out = np.empty((hh, ww, 3), np.uint8)
+    tiles = max(p.tiles_x, 0) * max(p.tiles_y, 0) if (p.stages & BALANCE_CLAHE) and want_stages else 0
+    hist = np.zeros((tiles, 256), np.uint32) if tiles else None
+    lut = np.zeros((tiles, 256), np.uint8) if tiles else None
+    rc = fn(*head, C.byref(p), C.c_int32(ww), C.c_int32(hh), _ptr(bgr), C.c_int64(bgr.strides[0] if bgr.size else 0), _ptr(out),
+            _ptr(hist), _ptr(lut))
+    res = dict(bgr=out)
+    if tiles:
+        res["hist"] = hist.reshape(p.tiles_y, p.tiles_x, 256)
+        res["lut"] = lut.reshape(p.tiles_y, p.tiles_x, 256)
+    return rc, res
+
+
+def image_balance_host(bgr, params=True, stages: bool = False):
+    """The keyframe colour balance of a (H, W, 3) BGR image on the CPU with the arithmetic the kernels use
+    (pcp_image_balance_host: no context, no GPU; DESIGN.md "Image balance").  Returns the balanced (H, W, 3) image, or with
+    stages=True dict(bgr, hist (tiles_y, tiles_x, 256) uint32, lut (tiles_y, tiles_x, 256) uint8) (hist, lut with CLAHE only)."""
+    L = load()
+    rc, res = _balance_call(L.pcp_image_balance_host, "image_balance_host", (), params, bgr, True)
+    if rc != PCP_OK:
+        raise PcpError(rc, L.pcp_last_error(None).decode())
+    return res if stages else res["bgr"]
+
+
+def gamma_table_host(gamma: float) -> np.ndarray:
+    """adjust_gamma's 256-byte table (pcp_gamma_table_host)."""
+    L = load()
+    out = np.empty(256, np.uint8)
+    rc = L.pcp_gamma_table_host(C.c_float(gamma), _ptr(out))
+    if rc != PCP_OK:
+        raise PcpError(rc, L.pcp_last_error(None).decode())
+    return out
 
 
 class CrackParams(C.Structure):
@@ -753,6 +830,20 @@ class Context:
         """generateColorMap's 8-bit BGR -> HSV -> BGR round trip applied to the images uploaded from now on."""
         self._check(self.lib.pcp_set_image_adjust(self.h, C.c_int32(1 if enable else 0), C.c_float(saturation_scale),
                                                   C.c_float(brightness_scale)))
+
+    def set_image_balance(self, balance=True):
+        """The keyframe colour balance (CLAHE on V, gamma table) applied on the device to the images uploaded from now on,
+        before set_image_adjust's round trip (pcp_set_image_balance).  True: the defaults; a dict of balance_params()'s
+        arguments; a BalanceParams; None / False: off."""
+        p = _as_balance(balance)
+        self._check(self.lib.pcp_set_image_balance(self.h, C.byref(p) if p is not None else None))
+
+    def image_balance(self, bgr, params=True, stages: bool = False):
+        """image_balance_host's computation on the device, by the kernels the upload path runs (pcp_image_balance);
+        independent of the camera and of set_image_balance / set_image_adjust.  Same returns."""
+        rc, res = _balance_call(self.lib.pcp_image_balance, "image_balance", (self.h,), params, bgr, True)
+        self._check(rc)
+        return res if stages else res["bgr"]
 
     def download_image(self, frame: int):
         """(bgr (H, W, 3), mask (H, W)) of one keyframe as the kernels sample it."""

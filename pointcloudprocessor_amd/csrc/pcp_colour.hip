@@ -1493,6 +1493,28 @@ hipError_t preload_colour() {
   return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_fill_u32));
 }
 
+// the pack kernel for decoded BGR8 rows at sk (device-readable), on stream s
+void pack_bgr_texels(hipStream_t s, const uint8_t *sk, int64_t row_stride_bytes, int32_t w, int32_t h, uint32_t *dst, int32_t clear_mask,
+                     const int32_t *tables, float sat_scale, float val_scale) {
+  const int64_t px = static_cast<int64_t>(w) * h;
+  if ((w & 15) == 0 && (row_stride_bytes & 15) == 0 && (reinterpret_cast<uintptr_t>(sk) & 15u) == 0)
+    hipLaunchKernelGGL(k_pack_bgr16, dim3(blocks_for(px / 16)), dim3(kBlock), 0, s, sk, row_stride_bytes, w, h, dst, clear_mask, tables,
+                       sat_scale, val_scale);
+  else
+    hipLaunchKernelGGL(k_pack_bgr, dim3(blocks_for(px)), dim3(kBlock), 0, s, sk, row_stride_bytes, w, h, dst, clear_mask, tables,
+                       sat_scale, val_scale);
+}
+
+int ensure_hsv_tables(pcp_context *ctx) {
+  if (ctx->hsv_tables.p) return PCP_OK;
+  int32_t tab[512];
+  hsv_build_tables(tab, tab + 256);
+  PCP_HIP_TRY(ctx, ctx->hsv_tables.ensure(512));
+  PCP_HIP_TRY(ctx, hipMemcpyAsync(ctx->hsv_tables.p, tab, sizeof(tab), hipMemcpyHostToDevice, ctx->stream));
+  PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // `tab` lives on this stack frame
+  return PCP_OK;
+}
+
 // Both forms run on the upload stream: copy into the staging buffer, "source -> texels" kernels (with the HSV round trip
 // when pcp_set_image_adjust enabled it), event.  count > 1: a block of keyframes staged together (pcp_upload_images_block).
 int upload_texels(pcp_context *ctx, const char *who, int32_t frame, int32_t count, bool block, bool wait, TexelSource &source) {
@@ -1501,6 +1523,8 @@ int upload_texels(pcp_context *ctx, const char *who, int32_t frame, int32_t coun
   if ((rc = check_frame(ctx, who, frame)) != PCP_OK) return rc;
   if ((rc = source.validate(ctx, who)) != PCP_OK) return rc;
   const int32_t w = ctx->dcam.img_w, h = ctx->dcam.img_h;
+  const bool balance = ctx->balance.stages != 0;  // pcp_set_image_balance: in place on the texels, after the source's pack kernel
+  if (balance && (rc = balance_check(ctx, who, ctx->balance, w, h)) != PCP_OK) return rc;
   const bool fresh = ctx->images.count < static_cast<size_t>(w) * h * static_cast<size_t>(ctx->n_frames) + 4;
   if ((rc = ensure_images(ctx)) != PCP_OK) return rc;
   if (!ctx->upload_stream[0]) {
@@ -1543,12 +1567,28 @@ int upload_texels(pcp_context *ctx, const char *who, int32_t frame, int32_t coun
   const int64_t px = static_cast<int64_t>(w) * h;
   if ((rc = source.stage(ctx, lane, us)) != PCP_OK) return rc;
   const int32_t *tables = ctx->adjust_images ? ctx->hsv_tables.p : static_cast<const int32_t *>(nullptr);
+  BalanceRun run{};
+  if (balance) {  // IB9: the adjust round trip moves behind the balance, into its apply kernel
+    run.params = ctx->balance;
+    run.gamma_host = ctx->balance_gamma;
+    run.gamma_stale = ctx->balance_lane_seq[lane] != ctx->balance_seq;
+    run.hsv_tables = ctx->hsv_tables.p;
+    run.adjust = ctx->adjust_images;
+    run.sat_scale = ctx->saturation_scale;
+    run.val_scale = ctx->brightness_scale;
+    if ((rc = balance_scratch(ctx, lane, us)) != PCP_OK) return rc;
+  }
   ++ctx->upload_turn;  // one turn of the lanes per call (a block is one call)
   for (int32_t k = 0; k < count; ++k) {
     const int32_t fk = frame + k;
     uint32_t *dst = ctx->images.p + static_cast<int64_t>(fk) * px;
     const int32_t clear_mask = ctx->mask_set[fk] ? 0 : 1;
-    if ((rc = source.pack(ctx, lane, us, k, dst, clear_mask, tables)) != PCP_OK) return rc;
+    if ((rc = source.pack(ctx, lane, us, k, dst, clear_mask, balance ? nullptr : tables)) != PCP_OK) return rc;
+    if (balance) {
+      if ((rc = balance_texels(ctx, lane, us, run, w, h, dst)) != PCP_OK) return rc;
+      run.gamma_stale = false;
+      ctx->balance_lane_seq[lane] = ctx->balance_seq;
+    }
     PCP_HIP_TRY(ctx, hipGetLastError());
     PCP_HIP_TRY(ctx, hipEventRecord(ctx->image_event[static_cast<size_t>(fk)], us));
     ctx->image_pending[static_cast<size_t>(fk)] = 1;
@@ -1616,15 +1656,8 @@ struct BgrSource final : TexelSource {
     return PCP_OK;
   }
   int pack(pcp_context *ctx, int, hipStream_t us, int32_t k, uint32_t *dst, int32_t clear_mask, const int32_t *tables) override {
-    const int32_t w = ctx->dcam.img_w, h = ctx->dcam.img_h;
-    const int64_t px = static_cast<int64_t>(w) * h;
-    const uint8_t *sk = src + static_cast<int64_t>(k) * block_stride;
-    if ((w & 15) == 0 && (row_stride_bytes & 15) == 0 && (reinterpret_cast<uintptr_t>(sk) & 15u) == 0)
-      hipLaunchKernelGGL(k_pack_bgr16, dim3(blocks_for(px / 16)), dim3(kBlock), 0, us, sk, row_stride_bytes, w, h, dst,
-                         clear_mask, tables, ctx->saturation_scale, ctx->brightness_scale);
-    else
-      hipLaunchKernelGGL(k_pack_bgr, dim3(blocks_for(px)), dim3(kBlock), 0, us, sk, row_stride_bytes, w, h, dst, clear_mask,
-                         tables, ctx->saturation_scale, ctx->brightness_scale);
+    pack_bgr_texels(us, src + static_cast<int64_t>(k) * block_stride, row_stride_bytes, ctx->dcam.img_w, ctx->dcam.img_h, dst, clear_mask,
+                    tables, ctx->saturation_scale, ctx->brightness_scale);
     return PCP_OK;
   }
 };
@@ -1693,12 +1726,9 @@ int pcp_set_image_adjust(pcp_context *ctx, int32_t enable, float saturation_scal
   if (!(saturation_scale >= 0.0f) || !(brightness_scale >= 0.0f))
     return set_error(ctx, PCP_ERR_INVALID, "pcp_set_image_adjust: scales must be >= 0");
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (enable && !ctx->hsv_tables.p) {
-    int32_t tab[512];
-    hsv_build_tables(tab, tab + 256);
-    PCP_HIP_TRY(ctx, ctx->hsv_tables.ensure(512));
-    PCP_HIP_TRY(ctx, hipMemcpyAsync(ctx->hsv_tables.p, tab, sizeof(tab), hipMemcpyHostToDevice, ctx->stream));
-    PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // `tab` lives on this stack frame
+  if (enable) {
+    const int rc = ensure_hsv_tables(ctx);
+    if (rc != PCP_OK) return rc;
   }
   ctx->adjust_images = enable != 0;
   ctx->saturation_scale = saturation_scale;

@@ -13,8 +13,14 @@
 //   saturate_cast<uchar>(c * 255.f).
 #pragma once
 
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#define PCP_HSV_HD __host__ __device__ __forceinline__
+#else
+#define PCP_HSV_HD inline
+#endif
 
+#include <cmath>
 #include <cstdint>
 
 namespace pcp {
@@ -30,15 +36,18 @@ inline void hsv_build_tables(int32_t sdiv[256], int32_t hdiv180[256]) {
   }
 }
 
-__device__ __forceinline__ uint32_t sat_u8_from_float(float x) {  // cv::saturate_cast<uchar>(float): cvRound, clamp
+PCP_HSV_HD uint32_t sat_u8_from_float(float x) {  // cv::saturate_cast<uchar>(float): cvRound, clamp
+#if defined(__HIP_DEVICE_COMPILE__)
   const int v = __float2int_rn(x);
+#else  // the host form (pcp_image_balance.hpp's CPU twin): the same value, clamped before the conversion can overflow
+  const int v = x >= 256.0f ? 256 : (x <= -1.0f ? -1 : static_cast<int>(__builtin_rintf(x)));
+#endif
   return static_cast<uint32_t>(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
 
-// b, g, r in / out (0..255)
-__device__ __forceinline__ void hsv_round_trip(const int32_t *__restrict__ sdiv, const int32_t *__restrict__ hdiv180,
-                                               float sat_scale, float val_scale, uint32_t &b8, uint32_t &g8,
-                                               uint32_t &r8) {
+// The forward half: b, g, r (0..255) -> H (0..180), S and V (0..255) as RGB2HSV_b stores them
+PCP_HSV_HD void hsv_forward(const int32_t *__restrict__ sdiv, const int32_t *__restrict__ hdiv180, uint32_t b8, uint32_t g8,
+                            uint32_t r8, uint32_t &H, uint32_t &S8, uint32_t &V8) {
   const int b = static_cast<int>(b8), g = static_cast<int>(g8), r = static_cast<int>(r8);
   // ---- RGB2HSV_b (bidx = 0: BGR input, hrange = 180)
   int v = b > g ? b : g;
@@ -51,11 +60,13 @@ __device__ __forceinline__ void hsv_round_trip(const int32_t *__restrict__ sdiv,
   int h = (vr & (g - b)) + (~vr & ((vg & (b - r + 2 * diff)) + ((~vg) & (r - g + 4 * diff))));
   h = (h * hdiv180[diff] + (1 << (kHsvShift - 1))) >> kHsvShift;
   h += h < 0 ? 180 : 0;
-  const uint32_t H = static_cast<uint32_t>(h < 0 ? 0 : (h > 255 ? 255 : h));  // saturate_cast<uchar>(h)
-  // ---- hsv.at<Vec3b>[1] = saturate_cast<uchar>(S * saturation_scale), [2] likewise (:733-734)
-  const uint32_t S = sat_u8_from_float(static_cast<float>(s & 0xff) * sat_scale);
-  const uint32_t V = sat_u8_from_float(static_cast<float>(v) * val_scale);
-  // ---- HSV2RGB_b -> HSV2RGB_native (hscale = 6.f / 180)
+  H = static_cast<uint32_t>(h < 0 ? 0 : (h > 255 ? 255 : h));  // saturate_cast<uchar>(h)
+  S8 = static_cast<uint32_t>(s & 0xff);
+  V8 = static_cast<uint32_t>(v);
+}
+
+// The backward half: HSV2RGB_b -> HSV2RGB_native (hscale = 6.f / 180) of H, S, V bytes
+PCP_HSV_HD void hsv_backward(uint32_t H, uint32_t S, uint32_t V, uint32_t &b8, uint32_t &g8, uint32_t &r8) {
   float fh = static_cast<float>(H);
   const float fs = static_cast<float>(S) * (1.0f / 255.0f);
   const float fv = static_cast<float>(V) * (1.0f / 255.0f);
@@ -89,6 +100,17 @@ __device__ __forceinline__ void hsv_round_trip(const int32_t *__restrict__ sdiv,
   b8 = sat_u8_from_float(fb * 255.0f);
   g8 = sat_u8_from_float(fg * 255.0f);
   r8 = sat_u8_from_float(fr * 255.0f);
+}
+
+// b, g, r in / out (0..255)
+PCP_HSV_HD void hsv_round_trip(const int32_t *__restrict__ sdiv, const int32_t *__restrict__ hdiv180, float sat_scale,
+                               float val_scale, uint32_t &b8, uint32_t &g8, uint32_t &r8) {
+  uint32_t H, s, v;
+  hsv_forward(sdiv, hdiv180, b8, g8, r8, H, s, v);
+  // ---- hsv.at<Vec3b>[1] = saturate_cast<uchar>(S * saturation_scale), [2] likewise (:733-734)
+  const uint32_t S = sat_u8_from_float(static_cast<float>(s) * sat_scale);
+  const uint32_t V = sat_u8_from_float(static_cast<float>(v) * val_scale);
+  hsv_backward(H, S, V, b8, g8, r8);
 }
 
 }  // namespace pcp

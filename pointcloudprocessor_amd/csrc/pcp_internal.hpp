@@ -267,6 +267,16 @@ struct pcp_context {
   bool adjust_images = false;
   float saturation_scale = 1.0f, brightness_scale = 1.0f;
   pcp::DevBuf<int32_t> hsv_tables;  // sdiv_table[256], hdiv_table180[256] (OpenCV RGB2HSV_b)
+  // pcp_set_image_balance: CLAHE on V and a gamma table, in place on the packed texels behind the lane's pack kernel
+  // (pcp_image_balance.hip).  The scratch is the lane's own: two lanes in flight never share it.
+  pcp_balance_params balance{};     // stages == 0: off
+  uint8_t balance_gamma[256] = {};  // IB8, built by pcp_set_image_balance
+  uint64_t balance_seq = 0;         // settings so far: a lane copies the gamma table again when its own copy is older
+  uint64_t balance_lane_seq[kUploadLanes] = {0, 0};
+  pcp::DevBuf<uint32_t> balance_hist[kUploadLanes];  // [16 * 16][256] per-tile histograms, left zeroed by k_balance_lut
+  pcp::DevBuf<uint8_t> balance_lut[kUploadLanes];    // [16 * 16][256] per-tile tables, then the gamma table's 256 bytes
+  pcp::DevBuf<uint32_t> balance_image;               // pcp_image_balance: its scratch texels
+  pcp::DevBuf<uint8_t> balance_bytes;                // pcp_image_balance: its BGR rows in and out
 
   // depth maps [n_frames][mh*mw] as uint view of positive floats
   pcp::DevBuf<uint32_t> depth;
@@ -578,6 +588,29 @@ struct TexelSource {
   virtual int pack(pcp_context *ctx, int lane, hipStream_t us, int32_t k, uint32_t *dst, int32_t clear_mask,
                    const int32_t *hsv_tables) = 0;
 };
+// the pack kernel for decoded BGR8 rows (pcp_colour.hip: k_pack_bgr16 where rows and width allow, else k_pack_bgr), and the
+// OpenCV tables of the HSV conversion on the device
+void pack_bgr_texels(hipStream_t s, const uint8_t *src, int64_t row_stride_bytes, int32_t w, int32_t h, uint32_t *dst, int32_t clear_mask,
+                     const int32_t *hsv_tables, float sat_scale, float val_scale);
+int ensure_hsv_tables(pcp_context *ctx);
+
+// The image balance of one keyframe's texels, in place, on a lane's stream with that lane's scratch (pcp_image_balance.hip).
+struct BalanceRun {
+  pcp_balance_params params;
+  const uint8_t *gamma_host;   // 256 bytes, copied to the lane when gamma_stale
+  bool gamma_stale;
+  const int32_t *hsv_tables;   // device; needed with PCP_BALANCE_CLAHE or adjust
+  bool adjust;                 // IB9: pcp_set_image_adjust's round trip last
+  float sat_scale, val_scale;
+  bool timed;                  // PCP_K_MISC (the context's stream only)
+  uint32_t *out_hist;          // host, nullable: the raw histograms
+  uint8_t *out_lut;            // host, nullable
+};
+int balance_check(pcp_context *ctx, const char *who, const pcp_balance_params &p, int32_t w, int32_t h);  // IB3's refusal
+int balance_scratch(pcp_context *ctx, int lane, hipStream_t s);
+int balance_texels(pcp_context *ctx, int lane, hipStream_t s, const BalanceRun &run, int32_t w, int32_t h, uint32_t *texels);
+hipError_t preload_image_balance();
+
 // count > 1 only for a block of keyframes staged together (pcp_upload_images_block); wait: synchronise the lane
 int upload_texels(pcp_context *ctx, const char *who, int32_t frame, int32_t count, bool block, bool wait, TexelSource &src);
 

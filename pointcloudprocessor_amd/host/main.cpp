@@ -157,6 +157,17 @@
 //     junctions, loops, skeleton_length_m and the centroids of its end and junction nodes (end_xyz, junction_xyz).  The
 //     reference's script skeletonises each keyframe's mask in 2-D (preprocess(): pcv.morphology.skeletonize).  Made on the GPU
 //     (pcp_crack_skeleton; DESIGN.md "Crack skeletons on the map").  Every other output stays as it is.
+//   * --balanceImages 0|1 (new, default 0 = the reference's behaviour), --claheClip c (new, default 1.0; 0 = no clipping),
+//     --claheTiles x,y (new, default 8,8, each 1..16) and --balanceGamma g (new, default 0.8; 1 = identity table): with 1,
+//     every keyframe is colour-balanced on the GPU as it is uploaded -- CLAHE on a lightness channel, then a gamma table --
+//     which the reference does beforehand by running scripts/image_color_balance_autonomous.py (clip 1.0, gamma 0.8: the
+//     defaults here) or scripts/image_color_balance.py (--claheClip 3 --balanceGamma 1.1) over the keyframe folder and
+//     pointing -i at the rewritten JPEGs (pcp_set_image_balance; DESIGN.md "Image balance").  Two stated differences: the
+//     lightness channel is V of the 8-bit HSV conversion generateColorMap uses, not L of 8-bit Lab, and the balanced
+//     pixels are never re-encoded as JPEG.  The balance comes before generateColorMap's HSV round trip, and the NID stage
+//     sees the balanced keyframes too, as it does when the folder was balanced.  The three value flags without
+//     --balanceImages 1 are errors.  Works with every cull and match mode, --gpus N (every GPU balances its own copy of the
+//     same pixels), --streamColour 1, --balanceExposure 1 and the device JPEG path.
 //   * --orthoMap 0|1 (new, default 0), --orthoGsd g (new, default 0.01, metres per pixel, 1e-4..1), --orthoFill R (new, default
 //     0, pixels, 0..1024) and --orthoFrame auto|ox,oy,oz,ux,uy,uz,vx,vy,vz (new, default auto): with 1 the run also writes one
 //     orthographic picture of the coloured cloud, <outputPath>ortho/ortho_rgb.npy (|u1, (H, W, 3)), ortho_depth.npy (<f4,
@@ -269,6 +280,11 @@ struct Options {
   bool crack_fuse = false;            // --crackFuse 1: the widths on the map and the map's cracks (crack_width/map_*.npy, cracks_3d.json)
   float crack_link_radius = 0.02f;    // --crackLinkRadius r: crack points this close belong to one crack
   int crack_min_views = 1;            // --crackMinViews v: credited keyframes a crack point needs
+  bool balance_images = false;        // --balanceImages 1: CLAHE + gamma on every keyframe at upload
+  float clahe_clip = 1.0f;            // --claheClip c (0: no clipping)
+  int clahe_tiles_x = 8, clahe_tiles_y = 8;  // --claheTiles x,y
+  float balance_gamma = 0.8f;         // --balanceGamma g
+  std::string balance_value_flag;     // the first of the three value flags given (an error without --balanceImages 1)
   bool ortho_map = false;             // --orthoMap 1: one orthographic picture of the coloured cloud (ortho/ortho_*.npy, ortho_frame.json)
   float ortho_gsd = 0.01f;            // --orthoGsd g: metres per pixel
   int ortho_fill = 0;                 // --orthoFill R: empty pixels take their nearest occupied pixel within R pixels
@@ -355,6 +371,41 @@ static Options parse(int argc, char **argv) {
       if (v != "0" && v != "1")
         throw std::runtime_error("the argument ('" + v + "') for option '--balanceExposure' is invalid (0, 1)");
       o.balance_exposure = v == "1";
+    }
+    else if (a == "--balanceImages") {
+      const std::string v = next();
+      if (v != "0" && v != "1")
+        throw std::runtime_error("the argument ('" + v + "') for option '--balanceImages' is invalid (0, 1)");
+      o.balance_images = v == "1";
+    }
+    else if (a == "--claheClip") {
+      const std::string v = next();
+      char *end = nullptr;
+      const float c = std::strtof(v.c_str(), &end);
+      if (v.empty() || end != v.c_str() + v.size() || !std::isfinite(c) || c < 0.0f)
+        throw std::runtime_error("the argument ('" + v + "') for option '--claheClip' is invalid (0 = no clipping, or c > 0)");
+      o.clahe_clip = c;
+      if (o.balance_value_flag.empty()) o.balance_value_flag = a;
+    }
+    else if (a == "--claheTiles") {
+      const std::string v = next();
+      char *end = nullptr, *end2 = nullptr;
+      const long tx = std::strtol(v.c_str(), &end, 10);
+      const long ty = (end != v.c_str() && *end == ',') ? std::strtol(end + 1, &end2, 10) : 0;
+      if (end == v.c_str() || *end != ',' || end2 == end + 1 || !end2 || *end2 != '\0' || tx < 1 || tx > 16 || ty < 1 || ty > 16)
+        throw std::runtime_error("the argument ('" + v + "') for option '--claheTiles' is invalid (x,y with 1..16 each)");
+      o.clahe_tiles_x = static_cast<int>(tx);
+      o.clahe_tiles_y = static_cast<int>(ty);
+      if (o.balance_value_flag.empty()) o.balance_value_flag = a;
+    }
+    else if (a == "--balanceGamma") {
+      const std::string v = next();
+      char *end = nullptr;
+      const float g = std::strtof(v.c_str(), &end);
+      if (v.empty() || end != v.c_str() + v.size() || !std::isfinite(g) || !(g > 0.0f))
+        throw std::runtime_error("the argument ('" + v + "') for option '--balanceGamma' is invalid (g > 0; 1 = identity)");
+      o.balance_gamma = g;
+      if (o.balance_value_flag.empty()) o.balance_value_flag = a;
     }
     else if (a == "--outputLeaf") {
       const std::string v = next();
@@ -527,6 +578,8 @@ static Options parse(int argc, char **argv) {
   if (o.geometry_maps && o.enableMLS)
     throw std::runtime_error("the option '--geometryMaps 1' does not work with '--enableMLS 1' (the maps are rendered from the raw "
                              "map; maps of the smoothed cloud are not built)");
+  if (!o.balance_images && !o.balance_value_flag.empty())
+    throw std::runtime_error("the option '" + o.balance_value_flag + "' needs '--balanceImages 1'");
   if (o.balance_exposure) {
     auto refuse = [](const std::string &what, const std::string &why) {
       throw std::runtime_error("the option '--balanceExposure 1' does not work with " + what + " (" + why + ")");
@@ -572,6 +625,10 @@ static void usage(std::ostream &os) {
         "                                        the --outputLeaf files are small and go through the host writer)\n"
         "  --deviceReader arg (=0)               Parse the rows of the ASCII PCDs that are read on the GPU (same floats)\n"
         "  --balanceExposure arg (=0)            One brightness gain per keyframe from co-visible map points (--gpus 1)\n"
+        "  --balanceImages arg (=0)              Colour-balance every keyframe on the GPU at upload: CLAHE on V, then a gamma table\n"
+        "  --claheClip arg (=1)                  With --balanceImages: CLAHE clip limit (0 = no clipping)\n"
+        "  --claheTiles arg (=8,8)               With --balanceImages: CLAHE tile grid x,y (1..16 each)\n"
+        "  --balanceGamma arg (=0.8)             With --balanceImages: gamma of the table (1 = identity)\n"
         "  --geometryMaps arg (=0)               Also write range / xyz / normal / index images per keyframe as .npy (--gpus 1)\n"
         "  --normalRadius arg (=0.1)             With --geometryMaps: neighbourhood of the map normals (0 = no normals)\n"
         "  --crackMaps arg (=0)                  Also write the masks' squared distance and nearest-edge images as .npy (-m, --gpus 1)\n"
@@ -1056,6 +1113,15 @@ class Processor {
     }
     Phase ph_all("images_decode_and_upload_wall_s");  // decoders on the host threads, uploads on this one, overlapped
     gpu->setImageAdjust(adjusted);  // cvtColor(BGR2HSV) ... cvtColor(HSV2BGR), :722-741, fused into the upload
+    if (opt.balance_images) {  // scripts/image_color_balance_autonomous.py over the keyframe folder, on the texels instead
+      pcp_balance_params bp;
+      pcp_default_balance_params(&bp);
+      bp.tiles_x = opt.clahe_tiles_x;
+      bp.tiles_y = opt.clahe_tiles_y;
+      bp.clip_limit = opt.clahe_clip;
+      bp.gamma = opt.balance_gamma;
+      gpu->setImageBalance(&bp);
+    }
     const size_t n = keyframes.size();
     mask_missing.assign(n, 0);
     startDecoders();  // (running already when process() started them ahead)

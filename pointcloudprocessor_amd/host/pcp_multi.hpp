@@ -133,6 +133,10 @@ class MultiDevice {
   void setImageAdjust(bool enable, float saturation_scale = 1.0f, float brightness_scale = 1.0f) {
     for (auto &d : dev_) d->setImageAdjust(enable, saturation_scale, brightness_scale);
   }
+  // every GPU balances its own copy of the same pixels: the shards agree by construction
+  void setImageBalance(const pcp_balance_params *params) {
+    for (auto &d : dev_) d->setImageBalance(params);
+  }
   // cv::Mat rgb / grayImg of one keyframe: over PCIe once, to the other GPUs over xGMI
   void uploadImage(int keyframe, const uint8_t *bgr, int64_t step) { replicate(keyframe, bgr, step, cam_.image_height, false); }
   void uploadMask(int keyframe, const uint8_t *gray, int64_t step) { replicate(keyframe, gray, step, cam_.image_height, true); }

@@ -164,6 +164,9 @@ class Device {
   void setImageAdjust(bool enable, float saturation_scale = 1.0f, float brightness_scale = 1.0f) {
     check(pcp_set_image_adjust(ctx_, enable ? 1 : 0, saturation_scale, brightness_scale));
   }
+  // scripts/image_color_balance_autonomous.py / image_color_balance.py (apply_clahe, adjust_gamma) run over the keyframe folder,
+  // done by the library on every image uploaded from now on, before setImageAdjust's round trip; nullptr: off
+  void setImageBalance(const pcp_balance_params *params) { check(pcp_set_image_balance(ctx_, params)); }
   // cv::Mat rgb (CV_8UC3; after the HSV round trip unless setImageAdjust(true)): data, step
   void uploadImage(int keyframe, const uint8_t *bgr, int64_t step) { check(pcp_upload_image(ctx_, keyframe, bgr, step)); }
   // decoded frames in pinned memory: queues the copy only; the buffer must outlive the next synchronising call

@@ -52,8 +52,12 @@ class HipEngine:
     def upload_cloud(self, x, y, z):
         self.ctx.upload_cloud(x, y, z)
 
-    def set_keyframes(self, poses, images=None, masks=None, T_opt=None):
+    def set_keyframes(self, poses, images=None, masks=None, T_opt=None, balance="keep"):
+        """balance: the keyframe colour balance of the images uploaded from now on (capi.Context.set_image_balance: True for
+        the defaults, a dict of capi.balance_params()'s arguments, None for off); "keep" leaves the context's setting."""
         self.ctx.set_frames(poses, T_opt)
+        if not (isinstance(balance, str) and balance == "keep"):
+            self.ctx.set_image_balance(balance)
         if images is not None:
             for f, im in enumerate(images):
                 self.ctx.upload_image(f, im)
