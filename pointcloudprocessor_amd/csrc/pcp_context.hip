@@ -521,7 +521,7 @@ static int store_cloud(pcp_context *ctx, const float *x, const float *y, const f
   ctx->crack->release();   // pcp_crack_fuse_begin: and the accumulated crack widths
   ctx->mls_count = 0;
   ctx->mls_result_live = false;
-  ctx->vgd_next = ctx->css_next = -1;  // the streams of the smoothing stage belong to the cloud that is being replaced
+  end_smoothing_streams(ctx);  // the streams of the smoothing stage belong to the cloud that is being replaced
   ctx->css_ball = 0.0;
   std::fill(ctx->depth_valid.begin(), ctx->depth_valid.end(), uint8_t(0));
   ctx->hull_valid.clear();

@@ -332,8 +332,7 @@ int finite_view(pcp_context *ctx, bool with_remap, int32_t timing_slot, FiniteSc
 
 int build_radius_grid(pcp_context *ctx, const CloudView &cv, float radius, GridDesc *out) {
   // build_grid replaces the grid that an open MLS stream or a pcp_sor_partial rests on (as every call that builds one does)
-  ctx->vgd_next = -1;
-  ctx->css_next = -1;
+  end_smoothing_streams(ctx);
   ctx->sor_partial_slab = ctx->sor_partial_slabs = -1;
   // Cell edge: the radius, but never finer than ~8 cells per point.  A micrometre radius on a map tens of metres across
   // would otherwise take the finest grid there is (2^35 cells: 6 GiB of bitmap and running popcounts, a 4 GiB memset

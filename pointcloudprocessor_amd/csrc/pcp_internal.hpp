@@ -209,6 +209,91 @@ struct OrthoMap {
 
 struct CrackMap;  // (the crack chain's header)
 
+// ---- the uniform grid of the radius searches (pcp_grid.hip; read by the MLS / SOR kernels and by the radius stages:
+// local colour smoothing, normals, the neighbour table of PCP_MATCH_RADIUS, pcp_close_pairs) ----------------------------
+constexpr double kMaxGridCells = 536870912.0;      // 2^29: dense table of cell starts
+constexpr double kMaxSparseCells = 34359738368.0;  // 2^35: bitmap (4 GiB) + running popcounts (2 GiB)
+struct GridDesc {
+  float minx, miny, minz, inv_cell;
+  int32_t nx, ny, nz;
+  int32_t reach;  // cells to visit on each side: ceil(r / cell)
+  // Sparse form (nullptr: dense form, the table of cell starts has one entry per cell).  Grids of more than 2^29 cells keep
+  // table entries for the OCCUPIED cells only; a bitmap with one bit per cell and the running popcount per 64-bit word
+  // give the number of occupied cells before a cell -- its place in the table (1.5 bits per cell instead of 32).
+  const unsigned long long *occ;
+  const int32_t *occ_rank;
+};
+
+// a cloud on the device the smoothing stages operate on (the uploaded map, or an
+// intermediate of pcp_cloud_smooth); mn/mx = its bounding box
+struct CloudView {
+  const float *x, *y, *z;
+  int64_t n;
+  float mn[3], mx[3];
+  // nullptr, or view index -> caller's point index: the uploaded map is walked through its
+  // Morton-ordered copy (cell binning then permutes nearby memory only) and results are
+  // reported under the caller's indices
+  const int32_t *remap;
+};
+
+// ---- the two streams of the smoothing stage (pcp_mls.hip) ----------------------------------------------------------------
+// the voxel grid of VOXEL_GRID_DILATION over a cloud's box (MLSVoxelGrid; voxel_of and the kernels are pcp_mls.hip's)
+struct VoxelDesc {
+  float bminx, bminy, bminz, vs;
+  int32_t NX, NY, NZ, it;
+  int64_t words;  // 32-bit words of the bitmap
+};
+
+// what an emission of dilated voxels needs beside the voxel set itself (ctx->v_*) and the fits (ctx->m_state)
+struct VgdStream {
+  VoxelDesc v;
+  GridDesc g;            // the grid the emission searches (occ / occ_rank: ctx->g_occ, ctx->g_occ_rank)
+  const int32_t *remap;  // the view's (ctx->perm, ctx->c_perm or nullptr)
+  size_t plane;
+  int32_t order_poly;
+  int32_t bricks;         // 1: the voxel set is in bricks (chunks are runs of strips), 0: dense bitmap (runs of words)
+  int32_t NBX, NBY, NBZ;
+};
+// a chunk of an emission: bitmap words (dense form; word0 a multiple of the scan tile) or strips (brick form) [word0, word1)
+struct VgdChunk {
+  int64_t word0, word1, voxels;
+};
+
+// pcp_cloud_smooth_stream_*: the whole chain with the trailing outlier removal over the chunked emission
+struct SmoothStream {
+  pcp_mls_params p;
+  VgdStream S;
+  CloudView cv1;  // the survivors of the first filter (planes in ctx->c_xyz)
+  int64_t total_rows, kept_rows, rows_computed;
+  double threshold, max_dx, min_margin;
+  int32_t halo, redone;
+  double sampled_dx;  // the largest displacement sweep 0 saw on its sample of the voxels (sizes the halo; max_dx proves it)
+  double seconds[4];  // host clock of _begin: first filter + fit + voxel set, device allocations (inside the other three), sweep 0, sweep 1 + threshold
+  double alloc_bytes;  // device memory allocated during _begin
+};
+// a chunk of the chain: whole planes [first_plane, last_plane] of the first voxel axis; its result rows are [row0, row0 + rows)
+// of the upsampled cloud (and of ctx->css_dist)
+struct ChainChunk {
+  int64_t first_plane, last_plane, voxels, row0, rows;
+};
+
+// One stream: what it emits from, its chunks, the chunk its next _next emits.  Open: _next and _seek serve it.  Ended: a call
+// replaced what it rests on (end_emission_stream / end_smoothing_streams below say which), or its own _end did; the chain's
+// numbers stay readable for pcp_cloud_smooth_stream_stats.  Building: inside pcp_cloud_smooth_stream_begin (the chain only).
+enum class StreamPhase { None, Building, Open, Ended };
+template <typename Stream, typename Chunk>
+struct StreamState {
+  StreamPhase phase = StreamPhase::None;
+  Stream of{};
+  std::vector<Chunk> chunks;
+  int64_t next = 0;
+  bool open() const { return phase == StreamPhase::Open; }
+  bool idle() const { return phase == StreamPhase::None || phase == StreamPhase::Ended; }  // neither open nor being built
+  void end() {
+    if (open()) phase = StreamPhase::Ended;
+  }
+};
+
 }  // namespace pcp
 
 struct pcp_context {
@@ -433,20 +518,14 @@ struct pcp_context {
   // device PCD reader (pcp_ascii_parse.hip): two slots a window's pieces alternate between, an upload and a download stream
   pcp::AsciiParseSlot parse_slot[2];
   hipStream_t parse_up = nullptr, parse_down = nullptr;
-  // pcp_mls_stream_*: the plan of a chunked VOXEL_GRID_DILATION emission (pcp_mls.hip VgdStream; word0, word1, count per chunk)
-  std::vector<uint8_t> vgd_blob;
-  std::vector<int64_t> vgd_chunks;
-  int64_t vgd_next = -1;
-  // pcp_cloud_smooth_stream_*: the whole chain with the trailing outlier removal over the chunked emission (pcp_mls.hip
-  // SmoothStream; per chunk: first plane, last plane, voxels, first result row, result rows)
-  std::vector<uint8_t> css_blob;
-  std::vector<int64_t> css_chunks;
-  int64_t css_next = -1;
+  // pcp_mls_stream_*: the plan of a chunked VOXEL_GRID_DILATION emission
+  pcp::StreamState<pcp::VgdStream, pcp::VgdChunk> emission;
+  // pcp_cloud_smooth_stream_*: the whole chain with the trailing outlier removal over the chunked emission
+  pcp::StreamState<pcp::SmoothStream, pcp::ChainChunk> chain;
   pcp::DevBuf<float> css_dist;      // mean kNN distance of EVERY row of the dilated cloud (4 B x ~3.8e9 at C3)
   pcp::DevBuf<float> s_kth;         // per row of a chunk: bound of the squared distance to its (k + 1)-th nearest
   pcp::DevBuf<uint32_t> css_words;  // device scalars of the stream (max displacement, margins, counts)
-  bool css_building = false;        // inside pcp_cloud_smooth_stream_begin
-  double css_ball = 0.0;            // the trailing filter's ball, in (k + 1) rows by the voxel structure's density bound, as the last chunks left it (0: default)
+  double css_ball = 0.0;            // the chain's alone: the trailing filter's ball, in (k + 1) rows by the voxel structure's density bound, as the last chunks left it (0: default); outlives a stream, reset by an upload
   double sor_redo_fraction = 0.0;  // diagnostic: share of points the SOR selection kernel handed to the heap kernel
 
   // NID stage (section 8 f1): per-point intensity, per-keyframe culled clouds in camera
@@ -469,21 +548,7 @@ struct pcp_context {
 
 namespace pcp {
 
-// ---- the uniform grid of the radius searches (pcp_grid.hip; read by the MLS / SOR kernels and by the radius stages:
-// local colour smoothing, normals, the neighbour table of PCP_MATCH_RADIUS, pcp_close_pairs) ----------------------------
-constexpr double kMaxGridCells = 536870912.0;      // 2^29: dense table of cell starts
-constexpr double kMaxSparseCells = 34359738368.0;  // 2^35: bitmap (4 GiB) + running popcounts (2 GiB)
-struct GridDesc {
-  float minx, miny, minz, inv_cell;
-  int32_t nx, ny, nz;
-  int32_t reach;  // cells to visit on each side: ceil(r / cell)
-  // Sparse form (nullptr: dense form, the table of cell starts has one entry per cell).  Grids of more than 2^29 cells keep
-  // table entries for the OCCUPIED cells only; a bitmap with one bit per cell and the running popcount per 64-bit word
-  // give the number of occupied cells before a cell -- its place in the table (1.5 bits per cell instead of 32).
-  const unsigned long long *occ;
-  const int32_t *occ_rank;
-};
-
+// ---- the grid's device side (GridDesc is above the context) ----
 // number of occupied cells before cell c (sparse form)
 __device__ __forceinline__ int32_t cell_rank(const GridDesc &g, int64_t c) {
   const unsigned long long bits = g.occ[c >> 6];
@@ -506,23 +571,21 @@ __device__ __forceinline__ void grid_coords(const GridDesc &g, float x, float y,
   iz = min(max(static_cast<int32_t>(floorf((z - g.minz) * g.inv_cell)), 0), g.nz - 1);
 }
 
-// a cloud on the device the smoothing stages operate on (the uploaded map, or an
-// intermediate of pcp_cloud_smooth); mn/mx = its bounding box
-struct CloudView {
-  const float *x, *y, *z;
-  int64_t n;
-  float mn[3], mx[3];
-  // nullptr, or view index -> caller's point index: the uploaded map is walked through its
-  // Morton-ordered copy (cell binning then permutes nearby memory only) and results are
-  // reported under the caller's indices
-  const int32_t *remap;
-};
-
 // uniform grid over a cloud view, cell edge >= `cell`, reach = ceil(radius / cell): the table of cell starts in
 // ctx->g_start, the view's points in cell order in ctx->g_order (view indices; ascending inside a cell) and ctx->g_xyz
 // (SoA planes of (n + 3) & ~3 floats).  Coordinates must be finite.
 // geometry_only: just the grid description and a large enough cell table (the density probe of sor_run fills it).
 int build_grid(pcp_context *ctx, const CloudView &cv, float cell, float radius, GridDesc *out, bool geometry_only = false);
+// Which call ends which stream.  The emission stream searches the context's grid: a call that rebuilds the grid ends it (the
+// outlier removal: sor_run).  The chain rebuilds its grid per chunk but rests on the cloud, the first filter's survivors and
+// the fits: a call that replaces those ends both (an upload: store_cloud; a fit: mls_run), and so does every radius stage
+// (build_radius_grid).  build_grid itself ends neither: the chain's own chunks go through it.  pcp_cloud_smooth_stream_end ends
+// the chain alone; the two _begin calls end the other kind through the fit they run.
+inline void end_emission_stream(pcp_context *ctx) { ctx->emission.end(); }
+inline void end_smoothing_streams(pcp_context *ctx) {
+  ctx->emission.end();
+  ctx->chain.end();
+}
 
 // ---- the front end of the stages that search a fixed radius around every point of the uploaded cloud (pcp_grid.hip) ----
 // the uploaded cloud as a view: its Morton-ordered copy and the host box of its finite coordinates; with_remap: results

@@ -476,13 +476,8 @@ __global__ __launch_bounds__(kMB) void k_mls_gather(const float *__restrict__ tm
 // index is ascending PCL key, so the output order is the reference's.  k dilations
 // of a voxel are the (2k+1)^3 cube around it (restricted to non-negative indices,
 // Appendix B16), which every input point stamps directly with atomicOr.
+// (VoxelDesc: pcp_internal.hpp)
 // ---------------------------------------------------------------------------
-struct VoxelDesc {
-  float bminx, bminy, bminz, vs;
-  int32_t NX, NY, NZ, it;
-  int64_t words;  // 32-bit words of the bitmap
-};
-
 __device__ __forceinline__ void voxel_of(const VoxelDesc &v, float x, float y, float z, int32_t &ix, int32_t &iy,
                                          int32_t &iz) {
   // MLSVoxelGrid::getCellIndex: (p - bounding_min) / voxel_size in fp32, truncated
@@ -1987,15 +1982,7 @@ static int compact_results(pcp_context *ctx, const int32_t *keep_index, int64_t 
 // form emits the whole range; pcp_mls_stream_* emit it in chunks, which is how a voxel set above 2^31 points, or above
 // what the device can hold as output (78 B per point), is produced at all: the reference's own configuration (1 mm
 // voxels, 4 dilations, PointCloudProcessor.cpp:78-81) makes ~3.8e9 points of the 10 M-point C3 map.
-struct VgdStream {  // plain data: kept in ctx->vgd_blob between pcp_mls_stream_begin and _next
-  VoxelDesc v;
-  GridDesc g;
-  const int32_t *remap;
-  size_t plane;
-  int32_t order_poly;
-  int32_t bricks;         // 1: the voxel set is in bricks (chunks are runs of strips), 0: dense bitmap (runs of words)
-  int32_t NBX, NBY, NBZ;
-};
+// (VgdStream, VgdChunk: pcp_internal.hpp)
 
 // PCP_VGD_DENSE=1: the dense bitmap of rounds 2-3 (one bit per voxel of the bounding box); results identical
 static bool vgd_dense_form() {
@@ -2087,16 +2074,12 @@ static int vgd_prepare_bricks(pcp_context *ctx, const CloudView &cv, const Voxel
 // chunks of the brick form = maximal runs of whole strips that hold at most `capacity` voxels (a strip alone holds at most
 // 16 NZ): whole planes while they fit; where a boundary falls inside a plane, that plane's strip counts are fetched
 static int vgd_plan_bricks(pcp_context *ctx, const VoxelDesc &v, int32_t NBY, const std::vector<unsigned long long> &plane_counts,
-                           int64_t capacity, std::vector<int64_t> *chunks) {
+                           int64_t capacity, std::vector<VgdChunk> *chunks) {
   chunks->clear();
   std::vector<int32_t> strip(static_cast<size_t>(NBY));
   int64_t s_begin = 0, cnt = 0;
   auto close = [&](int64_t s_end) {
-    if (cnt > 0) {
-      chunks->push_back(s_begin);
-      chunks->push_back(s_end);
-      chunks->push_back(cnt);
-    }
+    if (cnt > 0) chunks->push_back({s_begin, s_end, cnt});
     s_begin = s_end;
     cnt = 0;
   };
@@ -2181,18 +2164,27 @@ static int vgd_prepare(pcp_context *ctx, const CloudView &cv, const pcp_mls_para
   return PCP_OK;
 }
 
-// the voxels of bitmap words [word0, word1) (word0 a multiple of kScanTile), `count` of them: results in ctx->mls_*
-// sample_step > 0: nothing is emitted -- one workgroup of voxels in `sample_step` is projected for max_dx alone (*out_m = 0)
-// positions_only: the rows' positions alone (ctx->mls_xyz; the other result arrays are left as they are)
-static int vgd_emit(pcp_context *ctx, const VgdStream &S, int64_t word0, int64_t word1, int64_t count, int64_t *out_m,
-                    uint32_t *max_dx = nullptr, int32_t sample_step = 0, bool positions_only = false) {
+// a dilated voxel's corner lies within sqrt(3) * (it + 1) voxels of the point that stamped it (1 % + 1 um of
+// slack for the fp32 roundings of getCellIndex / getPosition)
+static float vgd_dmax(int32_t iterations, float voxel_size) {
+  return static_cast<float>(1.7321 * (iterations + 1) * static_cast<double>(voxel_size) * 1.01 + 1e-6);
+}
+
+struct VgdEmit {
+  uint32_t *max_dx = nullptr;   // device word: the largest |x of a row - x of its voxel position| so far (float bits)
+  int32_t sample_step = 0;      // > 0: nothing is emitted -- one workgroup of voxels in `sample_step` is projected for max_dx alone (*out_m = 0)
+  bool positions_only = false;  // the rows' positions alone (ctx->mls_xyz; the other result arrays are left as they are)
+};
+// the voxels of one chunk: results in ctx->mls_*
+static int vgd_emit(pcp_context *ctx, const VgdStream &S, const VgdChunk &chunk, int64_t *out_m, const VgdEmit &rq = {}) {
+  const int64_t word0 = chunk.word0, word1 = chunk.word1, count = chunk.voxels;
   const size_t st = static_cast<size_t>(count);
   size_t free_b = 0, total_b = 0;
   PCP_HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
   auto short_of_memory = [&]() {
     return static_cast<double>(st) * 78.0 > static_cast<double>(free_b) + static_cast<double>(ctx->mls_xyz.count) * 4.0 * 2.4;
   };
-  if (short_of_memory() && ctx->css_next < 0 && !ctx->css_building && ctx->css_dist.p) {
+  if (short_of_memory() && ctx->chain.idle() && ctx->css_dist.p) {
     // the memory an ended stream of the whole chain still holds (4 B per row of its upsampled cloud) goes first
     ctx->css_dist.release();
     PCP_HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
@@ -2200,9 +2192,9 @@ static int vgd_emit(pcp_context *ctx, const VgdStream &S, int64_t word0, int64_t
   if (short_of_memory())
     return set_error(ctx, PCP_ERR_NOMEM, "pcp_mls_process: %lld upsampled points do not fit the device memory "
                      "(pcp_mls_stream_begin / _next emit them in chunks)", (long long)count);
-  if (sample_step == 0) {  // (a dry run stores nothing)
+  if (rq.sample_step == 0) {  // (a dry run stores nothing)
     PCP_HIP_TRY(ctx, ctx->mls_xyz.ensure(3 * st + 4));
-    if (!positions_only) {
+    if (!rq.positions_only) {
       PCP_HIP_TRY(ctx, ctx->mls_normal.ensure(3 * st + 4));
       PCP_HIP_TRY(ctx, ctx->mls_curv.ensure(st + 4));
       PCP_HIP_TRY(ctx, ctx->mls_index.ensure(st + 4));
@@ -2232,9 +2224,7 @@ static int vgd_emit(pcp_context *ctx, const VgdStream &S, int64_t word0, int64_t
     e.remap = S.remap;
     e.start = ctx->g_start.p;
     e.g = S.g;
-    // a dilated voxel's corner lies within sqrt(3) * (it + 1) voxels of the point that stamped it (1 % + 1 um of
-    // slack for the fp32 roundings of getCellIndex / getPosition)
-    e.dmax = static_cast<float>(1.7321 * (S.v.it + 1) * static_cast<double>(S.v.vs) * 1.01 + 1e-6);
+    e.dmax = vgd_dmax(S.v.it, S.v.vs);
     e.vox = ctx->v_vox.p;
     e.total = count;
     e.state = ctx->m_state.p;
@@ -2246,9 +2236,9 @@ static int vgd_emit(pcp_context *ctx, const VgdStream &S, int64_t word0, int64_t
     e.curv = ctx->mls_curv.p;
     e.index = ctx->mls_index.p;
     e.valid = ctx->m_flag.p;
-    e.max_dx = max_dx;
-    e.dry = sample_step > 0 ? 1 : (positions_only ? 2 : 0);
-    e.block_step = std::max(1, sample_step);
+    e.max_dx = rq.max_dx;
+    e.dry = rq.sample_step > 0 ? 1 : (rq.positions_only ? 2 : 0);
+    e.block_step = std::max(1, rq.sample_step);
     {
       LaunchTimer t(ctx, PCP_K_MLS_VOXEL);
       scan_exclusive_launch(ctx->stream, tile_first, tiles, level2, nullptr);  // (its tile sums share s_tiles with the counts)
@@ -2263,7 +2253,7 @@ static int vgd_emit(pcp_context *ctx, const VgdStream &S, int64_t word0, int64_t
       hipLaunchKernelGGL(k_voxel_emit, dim3(static_cast<uint32_t>(div_up(div_up(count, kMB), e.block_step))), dim3(kMB), 0, ctx->stream, e);
       PCP_HIP_TRY(ctx, hipGetLastError());
     }
-    if (sample_step > 0) {
+    if (rq.sample_step > 0) {
       ctx->mls_count = 0;
       if (out_m) *out_m = 0;
       return PCP_OK;
@@ -2275,11 +2265,11 @@ static int vgd_emit(pcp_context *ctx, const VgdStream &S, int64_t word0, int64_t
     if (rc != PCP_OK) return rc;
     if (kept != count) {
       LaunchTimer t(ctx, PCP_K_MLS_VOXEL);
-      if ((rc = compact_results(ctx, ctx->s_cell.p, count, kept, positions_only)) != PCP_OK) return rc;
+      if ((rc = compact_results(ctx, ctx->s_cell.p, count, kept, rq.positions_only)) != PCP_OK) return rc;
       m = kept;
     }
   }
-  ctx->mls_count = positions_only ? 0 : m;  // (nothing to fetch from a positions-only emission)
+  ctx->mls_count = rq.positions_only ? 0 : m;  // (nothing to fetch from a positions-only emission)
   if (out_m) *out_m = m;
   return PCP_OK;
 }
@@ -2298,7 +2288,7 @@ static VgdStream vgd_stream_of(const CloudView &cv, const pcp_mls_params *p, con
 // counts the dilated voxel set in the form that fits -- bricks unless PCP_VGD_DENSE=1 or the grid is taller than the brick
 // form handles -- and cuts it into chunks of at most `capacity` voxels (capacity <= 0: one chunk)
 static int vgd_count_and_plan(pcp_context *ctx, const CloudView &cv, const pcp_mls_params *p, const GridDesc &g, int64_t capacity,
-                              VgdStream *out_S, std::vector<int64_t> *chunks, unsigned long long *out_total) {
+                              VgdStream *out_S, std::vector<VgdChunk> *chunks, unsigned long long *out_total) {
   VoxelDesc v{};
   int rc = vgd_describe(ctx, cv, p, &v);
   if (rc != PCP_OK) return rc;
@@ -2320,7 +2310,7 @@ static int vgd_count_and_plan(pcp_context *ctx, const CloudView &cv, const pcp_m
       // a strip holds up to 16 NZ voxels and is never split: where one alone exceeds the capacity (a solid block of points
       // and a capacity near the 32 768 minimum) the dense form, whose unit is 32 768 keys, takes over
       bool ok = true;
-      for (size_t k = 2; k < chunks->size(); k += 3) ok = ok && (*chunks)[k] <= cap;
+      for (const VgdChunk &c : *chunks) ok = ok && c.voxels <= cap;
       if (ok) return PCP_OK;
       chunks->clear();
     }
@@ -2335,11 +2325,7 @@ static int vgd_count_and_plan(pcp_context *ctx, const CloudView &cv, const pcp_m
   for (int64_t t = 0; t <= tiles; ++t) {
     const int64_t c = t < tiles ? tile_counts[static_cast<size_t>(t)] : 0;
     if (t == tiles || (cnt + c > cap && t > t0)) {
-      if (cnt > 0) {
-        chunks->push_back(t0 * kScanTile);
-        chunks->push_back(std::min<int64_t>(t * kScanTile, v.words));
-        chunks->push_back(cnt);
-      }
+      if (cnt > 0) chunks->push_back({t0 * kScanTile, std::min<int64_t>(t * kScanTile, v.words), cnt});
       t0 = t;
       cnt = 0;
     }
@@ -2351,7 +2337,7 @@ static int vgd_count_and_plan(pcp_context *ctx, const CloudView &cv, const pcp_m
 static int voxel_grid_dilation(pcp_context *ctx, const CloudView &cv, const pcp_mls_params *p, const GridDesc &g,
                                int64_t *out_count) {
   VgdStream S{};
-  std::vector<int64_t> chunks;
+  std::vector<VgdChunk> chunks;
   unsigned long long total = 0;
   int rc = vgd_count_and_plan(ctx, cv, p, g, 0, &S, &chunks, &total);
   if (rc != PCP_OK) return rc;
@@ -2359,11 +2345,8 @@ static int voxel_grid_dilation(pcp_context *ctx, const CloudView &cv, const pcp_
     return set_error(ctx, PCP_ERR_NOMEM, "pcp_mls_process: %llu dilated voxels exceed the 2^31 points one result holds "
                      "(pcp_mls_stream_begin / _next emit them in chunks)", total);
   int64_t m = 0;
-  if (chunks.empty()) {  // an empty set: the result buffers still have to exist
-    if ((rc = vgd_emit(ctx, S, 0, 0, 0, &m)) != PCP_OK) return rc;
-  } else if ((rc = vgd_emit(ctx, S, chunks[0], chunks[1], chunks[2], &m)) != PCP_OK) {
-    return rc;
-  }
+  // (an empty set: the result buffers still have to exist)
+  if ((rc = vgd_emit(ctx, S, chunks.empty() ? VgdChunk{0, 0, 0} : chunks[0], &m)) != PCP_OK) return rc;
   if (out_count) *out_count = m;
   return PCP_OK;
 }
@@ -2439,7 +2422,7 @@ static int slp_emit(pcp_context *ctx, const pcp_mls_params *p, int64_t n, bool c
   auto short_of_memory = [&]() {
     return rows_d * 78.0 > static_cast<double>(free_b) + static_cast<double>(ctx->mls_xyz.count) * 4.0 * 2.4;
   };
-  if (short_of_memory() && ctx->css_next < 0 && !ctx->css_building && ctx->css_dist.p) {
+  if (short_of_memory() && ctx->chain.idle() && ctx->css_dist.p) {
     ctx->css_dist.release();  // what an ended stream of the whole chain still holds goes first
     PCP_HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
   }
@@ -2505,37 +2488,80 @@ static int check_mls_params(pcp_context *ctx, const pcp_mls_params *p) {
   return PCP_OK;
 }
 
-// the grid the emission of the dilated voxels searches the nearest input point in (see mls_run); leaves *g alone when the
-// fit's own grid serves (PCP_VGD_GRID=fit, or cells of 2 dmax would not be finer)
-static int emission_grid(pcp_context *ctx, const CloudView &cv, const pcp_mls_params *p, GridDesc *g) {
-  const char *ge = std::getenv("PCP_VGD_GRID");
-  if (ge && ge[0] == 'f') return PCP_OK;
-  const float dmax = static_cast<float>(1.7321 * (p->vgd_iterations + 1) * static_cast<double>(p->vgd_voxel_size) * 1.01 + 1e-6);
-  const float cell_emit = 2.0f * dmax;  // measured at C3: 439 ms of emission (1.5 dmax: 449, 3: 474, 1: 604; the fit's grid: 543)
-  if (cell_emit < static_cast<float>(p->search_radius)) return build_grid(ctx, cv, cell_emit, cell_emit, g);
+// What every smoothing call checks before it touches the context, in the order the calls have always reported it: the
+// parameters; for the streams the upsampling mode and the chunk capacity; the cloud (uploaded, finite); for the sharded calls
+// the upsampling mode; for the chain its filters' mean_k; then the context's device is made current.
+enum class Upsamplings { Any, NoneOnly, VgdOnly };  // NoneOnly: the sharded calls, VgdOnly: the streams
+struct SmoothingEntry {
+  Upsamplings accepts = Upsamplings::Any;
+  bool chain = false;  // the whole chain (its outlier removals need sor_mean_k)
+  int64_t min_capacity = 0, capacity = 0;  // the streams
+};
+static int enter_smoothing(pcp_context *ctx, const char *who, const pcp_mls_params *p, const SmoothingEntry &e = {}) {
+  int rc = check_mls_params(ctx, p);
+  if (rc != PCP_OK) return rc;
+  const bool slp = p->upsampling == PCP_UPSAMPLING_SAMPLE_LOCAL_PLANE;
+  if (e.accepts == Upsamplings::VgdOnly) {
+    if (slp)
+      return set_error(ctx, PCP_ERR_INVALID, "%s: SAMPLE_LOCAL_PLANE (1) is not streamed (%s)", who,
+                       e.chain ? "pcp_cloud_smooth runs it" : "pcp_mls_process emits it");
+    if (p->upsampling != 3) return set_error(ctx, PCP_ERR_INVALID, "%s: upsampling must be VOXEL_GRID_DILATION (3)", who);
+    if (e.capacity < e.min_capacity || e.capacity >= (int64_t(1) << 31))
+      return set_error(ctx, PCP_ERR_INVALID, "%s: chunk_capacity must be in [%lld, 2^31)", who, (long long)e.min_capacity);
+  }
+  if (!ctx->xyz.p) return set_error(ctx, PCP_ERR_STATE, "%s: no cloud uploaded", who);
+  if ((rc = require_finite_cloud(ctx, who)) != PCP_OK) return rc;
+  if (e.accepts == Upsamplings::NoneOnly) {
+    if (slp)
+      return set_error(ctx, PCP_ERR_INVALID, "%s: SAMPLE_LOCAL_PLANE (1) is not sharded (its disks follow the sign of each "
+                       "point's fitted normal, which a re-ordered fit may flip): run pcp_mls_process", who);
+    if (p->upsampling != 0) return set_error(ctx, PCP_ERR_INVALID, "%s: query sharding supports upsampling NONE only", who);
+  }
+  if (e.chain && (p->sor_mean_k < 1 || p->sor_mean_k > 254))
+    return set_error(ctx, PCP_ERR_INVALID, "%s: sor_mean_k %d out of range (1..254)", who, p->sor_mean_k);
+  PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
   return PCP_OK;
 }
 
+// the fit's grid: cell edge 0.1 % above r: two points closer than r then differ by < 1 in every cell
+// coordinate even with the fp32 slop of the cell assignment, so reach 1 suffices
+static int fit_grid(pcp_context *ctx, const CloudView &cv, const pcp_mls_params *p, GridDesc *g) {
+  return build_grid(ctx, cv, static_cast<float>(p->search_radius) * 1.001f, static_cast<float>(p->search_radius), g);
+}
+
+// The grid the emission of the dilated voxels searches the nearest input point in (see mls_run): cells of 2 dmax where that
+// is finer than the fit's grid, else the fit's grid (PCP_VGD_GRID=fit: always; results identical).  fit_grid_stands: *g is
+// the fit's grid and the context's tables are its tables (right after the fit), so it is left alone where it serves; the
+// streamed chain builds it again (the outlier removal of a chunk overwrote the tables).
+static int emission_grid(pcp_context *ctx, const CloudView &cv, const pcp_mls_params *p, bool fit_grid_stands, GridDesc *g) {
+  const char *ge = std::getenv("PCP_VGD_GRID");
+  // measured at C3: 439 ms of emission (1.5 dmax: 449, 3: 474, 1: 604; the fit's grid: 543)
+  const float cell_emit = 2.0f * vgd_dmax(p->vgd_iterations, p->vgd_voxel_size);
+  if (!(ge && ge[0] == 'f') && cell_emit < static_cast<float>(p->search_radius)) return build_grid(ctx, cv, cell_emit, cell_emit, g);
+  return fit_grid_stands ? PCP_OK : fit_grid(ctx, cv, p, g);
+}
+
 // MovingLeastSquares::process on a cloud view; results in ctx->mls_* (index = view index)
-// keep_rows: leave the fitted rows in ctx->m_tmp (7 floats at the view index mls_index names) instead of gathering them
-// into the result arrays -- pcp_cloud_smooth picks the survivors of its last filter straight from there.  With
-// SAMPLE_LOCAL_PLANE it selects slp_emit's chain form (indices through ctx->c_index, positions also as SoA planes).
-static int mls_run(pcp_context *ctx, const CloudView &cv, const pcp_mls_params *p, int64_t *out_count,
-                   int64_t q_begin = 0, int64_t q_end = -1, bool keep_rows = false, int64_t stream_capacity = 0,
-                   int32_t slab = 0, int32_t n_slabs = 1) {
+struct MlsRequest {
+  int64_t q_begin = 0, q_end = -1;  // the queries: caller's indices [q_begin, q_end) (-1: to the last point)
+  // leave the fitted rows in ctx->m_tmp (7 floats at the view index mls_index names) instead of gathering them
+  // into the result arrays -- pcp_cloud_smooth picks the survivors of its last filter straight from there.  With
+  // SAMPLE_LOCAL_PLANE it selects slp_emit's chain form (indices through ctx->c_index, positions also as SoA planes).
+  bool keep_rows = false;
+  int64_t stream_capacity = 0;  // > 0 (VOXEL_GRID_DILATION): nothing is emitted, ctx->emission opens with chunks of at most this many voxels
+  int32_t slab = 0, n_slabs = 1;  // the queries: a slab of the cell order
+};
+static int mls_run(pcp_context *ctx, const CloudView &cv, const pcp_mls_params *p, int64_t *out_count, const MlsRequest &rq = {}) {
   const int64_t n = cv.n;
   ctx->mls_count = 0;
   ctx->mls_result_live = false;
-  ctx->vgd_next = -1;  // a stream of an earlier call rests on the grid and the fits this call replaces
-  ctx->css_next = -1;
+  end_smoothing_streams(ctx);  // a stream of an earlier call rests on the grid and the fits this call replaces
   if (out_count) *out_count = 0;
   if (n == 0) return PCP_OK;
   const size_t sn = static_cast<size_t>(n);
   const size_t plane = (sn + 3) & ~size_t(3);
   GridDesc g;
-  // cell edge 0.1 % above r: two points closer than r then differ by < 1 in every cell
-  // coordinate even with the fp32 slop of the cell assignment, so reach 1 suffices
-  int rc = build_grid(ctx, cv, static_cast<float>(p->search_radius) * 1.001f, static_cast<float>(p->search_radius), &g);
+  int rc = fit_grid(ctx, cv, p, &g);
   if (rc != PCP_OK) return rc;
   PCP_HIP_TRY(ctx, ctx->m_tmp.ensure(kRowStride * sn + 8));
   PCP_HIP_TRY(ctx, ctx->m_flag.ensure(sn + 16));
@@ -2554,12 +2580,12 @@ static int mls_run(pcp_context *ctx, const CloudView &cv, const pcp_mls_params *
   a.tmp = ctx->m_tmp.p;
   a.flag = ctx->m_flag.p;
   a.state = nullptr;
-  a.q_begin = static_cast<int32_t>(q_begin);
-  a.q_end = static_cast<int32_t>(q_end < 0 ? n : q_end);
+  a.q_begin = static_cast<int32_t>(rq.q_begin);
+  a.q_end = static_cast<int32_t>(rq.q_end < 0 ? n : rq.q_end);
   // a slab of the cell order (whole wavefronts: the deal divides the work whatever the caller's point order is)
-  a.j_begin = n_slabs > 1 ? (n * slab / n_slabs) / kFitBlock * kFitBlock : 0;
-  a.j_end = (n_slabs > 1 && slab + 1 < n_slabs) ? (n * (slab + 1) / n_slabs) / kFitBlock * kFitBlock : n;
-  if (n_slabs > 1) PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->m_flag.p, 0, sn, ctx->stream));  // the other slabs' points: no output
+  a.j_begin = rq.n_slabs > 1 ? (n * rq.slab / rq.n_slabs) / kFitBlock * kFitBlock : 0;
+  a.j_end = (rq.n_slabs > 1 && rq.slab + 1 < rq.n_slabs) ? (n * (rq.slab + 1) / rq.n_slabs) / kFitBlock * kFitBlock : n;
+  if (rq.n_slabs > 1) PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->m_flag.p, 0, sn, ctx->stream));  // the other slabs' points: no output
   if (p->upsampling == PCP_UPSAMPLING_VOXEL_GRID_DILATION || p->upsampling == PCP_UPSAMPLING_SAMPLE_LOCAL_PLANE) {
     PCP_HIP_TRY(ctx, ctx->m_state.ensure(static_cast<size_t>(kMlsState) * sn + 8));
     // points skipped by the fit (< 3 neighbours) must read as "invalid" later
@@ -2580,21 +2606,20 @@ static int mls_run(pcp_context *ctx, const CloudView &cv, const pcp_mls_params *
     // dilation, < 9 mm for the reference's 1 mm x 4): the fit's own grid (3 cm cells) makes that ~85 candidates per voxel,
     // a grid with cells of 2 dmax ~25 -- the fit is done (its results sit under the input indices), so the cell tables are
     // rebuilt for the emission.  PCP_VGD_GRID=fit keeps the fit's grid (results identical).
-    if ((rc = emission_grid(ctx, cv, p, &g)) != PCP_OK) return rc;
+    if ((rc = emission_grid(ctx, cv, p, /*fit_grid_stands=*/true, &g)) != PCP_OK) return rc;
   }
-  if (p->upsampling == 3 && stream_capacity > 0) {
+  if (p->upsampling == 3 && rq.stream_capacity > 0) {
     // pcp_mls_stream_begin: count the voxel set and cut its key range into chunks (whole strips of the brick form, whole
     // tiles of the dense one)
-    VgdStream S{};
     unsigned long long total = 0;
-    if ((rc = vgd_count_and_plan(ctx, cv, p, g, stream_capacity, &S, &ctx->vgd_chunks, &total)) != PCP_OK) return rc;
-    ctx->vgd_blob.assign(reinterpret_cast<const uint8_t *>(&S), reinterpret_cast<const uint8_t *>(&S) + sizeof(S));
-    ctx->vgd_next = 0;
+    if ((rc = vgd_count_and_plan(ctx, cv, p, g, rq.stream_capacity, &ctx->emission.of, &ctx->emission.chunks, &total)) != PCP_OK) return rc;
+    ctx->emission.next = 0;
+    ctx->emission.phase = StreamPhase::Open;
     if (out_count) *out_count = static_cast<int64_t>(total);
     return PCP_OK;
   }
   if (p->upsampling == 3) return voxel_grid_dilation(ctx, cv, p, g, out_count);
-  if (p->upsampling == PCP_UPSAMPLING_SAMPLE_LOCAL_PLANE) return slp_emit(ctx, p, n, keep_rows, out_count);
+  if (p->upsampling == PCP_UPSAMPLING_SAMPLE_LOCAL_PLANE) return slp_emit(ctx, p, n, rq.keep_rows, out_count);
   // points with < 3 neighbours are dropped; output keeps the input order
   PCP_HIP_TRY(ctx, ctx->mls_index.ensure(sn + 4));
   int64_t m = 0;
@@ -2602,7 +2627,7 @@ static int mls_run(pcp_context *ctx, const CloudView &cv, const pcp_mls_params *
   PCP_HIP_TRY(ctx, ctx->mls_xyz.ensure(3 * static_cast<size_t>(m) + 4));
   PCP_HIP_TRY(ctx, ctx->mls_normal.ensure(3 * static_cast<size_t>(m) + 4));
   PCP_HIP_TRY(ctx, ctx->mls_curv.ensure(static_cast<size_t>(m) + 4));
-  if (m > 0 && !keep_rows) {
+  if (m > 0 && !rq.keep_rows) {
     LaunchTimer t(ctx, PCP_K_MLS_FIT);
     hipLaunchKernelGGL(k_mls_gather, dim3(blocks_of(m)), dim3(kMB), 0, ctx->stream, ctx->m_tmp.p, ctx->mls_index.p, m,
                        ctx->mls_xyz.p, ctx->mls_normal.p, ctx->mls_curv.p);
@@ -2614,21 +2639,31 @@ static int mls_run(pcp_context *ctx, const CloudView &cv, const pcp_mls_params *
 }
 
 // StatisticalOutlierRemoval on a cloud view: keep flags in ctx->m_flag (view order)
-// view_order: distances and keep flags under the view's own indices (ctx->m_flag[view index]) instead of the caller's
-// Slabs (pcp_sor_partial / pcp_sor_finish): the places [chunk c0, chunk c1) of the cell order are this GPU's queries (see
-// k_sor_stats); `classify` false stops after the chunk sums (they sit in ctx->m_sums from double 4 on).
 static int sor_classify(pcp_context *ctx, int64_t n, const int32_t *remap, double std_mul, int64_t j_begin, int64_t j_end);
-// clustered: the cloud is an upsampled one (VOXEL_GRID_DILATION): the selection takes its shape for clustered distances
-// area_density > 0: points per unit area of the cloud's surface, known from how the cloud was made (the upsampled clouds: at
-// least 2 it + 1 voxels of a column per vs^2) -- the ball is sized from it instead of from the density probe
-static int sor_run(pcp_context *ctx, const CloudView &cv, int32_t mean_k, double std_mul, bool view_order = false,
-                   int32_t slab = 0, int32_t n_slabs = 1, bool classify = true, float *kth = nullptr, bool clustered = false,
-                   double area_density = 0.0, int64_t row_begin = 0, int64_t row_end = -1) {
+struct SorRequest {
+  int32_t mean_k;
+  double std_mul;
+  bool view_order = false;  // distances and keep flags under the view's own indices (ctx->m_flag[view index]) instead of the caller's
+  // Slabs (pcp_sor_partial / pcp_sor_finish): the places [chunk c0, chunk c1) of the cell order are this GPU's queries (see
+  // k_sor_stats); `classify` false stops after the chunk sums (they sit in ctx->m_sums from double 4 on).
+  int32_t slab = 0, n_slabs = 1;
+  bool classify = true;
+  float *kth = nullptr;    // per row (device, nullable): bound of the squared distance to its (k + 1)-th nearest
+  bool clustered = false;  // the cloud is an upsampled one (VOXEL_GRID_DILATION): the selection takes its shape for clustered distances
+  // area_density > 0: points per unit area of the cloud's surface, known from how the cloud was made (the upsampled clouds: at
+  // least 2 it + 1 voxels of a column per vs^2) -- the selection's ball is sized from it, to `ball` * (k + 1) points, instead
+  // of from the density probe
+  double area_density = 0.0, ball = 1.2;
+  int64_t row_begin = 0, row_end = -1;  // the caller's indices whose distances are wanted (-1: to the last; see k_sor_select)
+};
+static int sor_run(pcp_context *ctx, const CloudView &cv, const SorRequest &rq) {
+  const int32_t mean_k = rq.mean_k, slab = rq.slab, n_slabs = rq.n_slabs;
+  bool clustered = rq.clustered;
   if (const char *ce = std::getenv("PCP_SOR_CLUSTERED")) clustered = ce[0] == '1';  // (tests: either shape on any cloud)
-  const int32_t *remap = view_order ? nullptr : cv.remap;
+  const int32_t *remap = rq.view_order ? nullptr : cv.remap;
   const int64_t n = cv.n;
   if (n == 0) return PCP_OK;
-  ctx->vgd_next = -1;  // (pcp_mls_stream_next searches the grid this call rebuilds; pcp_cloud_smooth_stream_* rebuild theirs per chunk)
+  end_emission_stream(ctx);  // (pcp_mls_stream_next searches the grid this call rebuilds; pcp_cloud_smooth_stream_* rebuild theirs per chunk)
   const int64_t n_chunks = div_up(n, kSorChunk);
   const int64_t c0 = n_chunks * slab / n_slabs, c1 = n_chunks * (slab + 1) / n_slabs;
   const int64_t q_begin = c0 * kSorChunk, q_end = std::min<int64_t>(c1 * kSorChunk, n);  // places of the cell order
@@ -2643,16 +2678,16 @@ static int sor_run(pcp_context *ctx, const CloudView &cv, int32_t mean_k, double
   if (!(cell > 1e-4f)) cell = 1e-4f;
   GridDesc g;
   int rc = PCP_OK;
-  if (area_density > 0.0) {
+  if (rq.area_density > 0.0) {
     // The density is known.  (The probe below reads the upsampled clouds 3.5x too thin -- their ball then held ~320 points
     // instead of ~90 and the outlier removal of the reference's 425 M-row cloud took 566 ms; sized from the voxel structure:
     // profiles/r05_vgd_sor_ball.log.)
     // (the density handed in is a lower bound -- tilted and noisy sheets carry more voxels per area --: 1.2 (k + 1) points by
     // the bound leave 0.05 % of the 425 M rows to the wavefront kernel; 1.5: 414 ms, 1.2: 385, 1.0: 354, 0.8: 331)
-    // (the streamed chain moves it from chunk to chunk by the share of rows the selection flagged: ctx->css_ball)
-    double ball = ctx->css_building && ctx->css_ball > 0.0 ? ctx->css_ball : 1.2;
+    // (the streamed chain moves it from chunk to chunk by the share of rows the selection flagged: its rq.ball)
+    double ball = rq.ball;
     if (const char *e = std::getenv("PCP_SOR_BALL")) ball = atof(e);
-    double final_cell = std::sqrt(ball * (mean_k + 1) / (3.14159265358979 * area_density));
+    double final_cell = std::sqrt(ball * (mean_k + 1) / (3.14159265358979 * rq.area_density));
     if (!(final_cell > 1e-7) || !(final_cell < 1e30)) final_cell = static_cast<double>(cell);
     // (cells of the ball's radius: as below)
     rc = build_grid(ctx, cv, static_cast<float>(final_cell), static_cast<float>(final_cell * 0.9999), &g);
@@ -2727,8 +2762,8 @@ static int sor_run(pcp_context *ctx, const CloudView &cv, int32_t mean_k, double
       if (clustered) sel = one_descriptor ? k_sor_select<true, 64, 32> : k_sor_select<false, 64, 32>;
       hipLaunchKernelGGL(sel, dim3(static_cast<uint32_t>(div_up(q_end - q_begin, kSelWave))), dim3(kSelWave), 0, ctx->stream,
                          ctx->g_xyz.p, ctx->g_xyz.p + plane, ctx->g_xyz.p + 2 * plane, ctx->g_order.p, remap,
-                         ctx->g_start.p, n, g, mean_k, dist, ctx->m_flag.p, q_begin, q_end, kth, static_cast<int32_t>(row_begin),
-                         static_cast<int32_t>(row_end < 0 ? n : row_end));
+                         ctx->g_start.p, n, g, mean_k, dist, ctx->m_flag.p, q_begin, q_end, rq.kth, static_cast<int32_t>(rq.row_begin),
+                         static_cast<int32_t>(rq.row_end < 0 ? n : rq.row_end));
       PCP_HIP_TRY(ctx, hipGetLastError());
     }
     int64_t redo = 0;
@@ -2751,7 +2786,7 @@ static int sor_run(pcp_context *ctx, const CloudView &cv, int32_t mean_k, double
       if (wave)
         hipLaunchKernelGGL(k_sor_wave, dim3(static_cast<uint32_t>(redo)), dim3(kSelWave), 0, ctx->stream, ctx->g_xyz.p,
                            ctx->g_xyz.p + plane, ctx->g_xyz.p + 2 * plane, ctx->g_order.p, remap, ctx->g_start.p, n, g, mean_k,
-                           dist, ctx->m_flag.p, ctx->s_cell.p, redo, kth, tally);
+                           dist, ctx->m_flag.p, ctx->s_cell.p, redo, rq.kth, tally);
       if (tally) {
         unsigned long long h[2 * 48];
         PCP_HIP_TRY(ctx, hipMemcpyAsync(h, tally, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
@@ -2765,7 +2800,7 @@ static int sor_run(pcp_context *ctx, const CloudView &cv, int32_t mean_k, double
       hipLaunchKernelGGL(k_sor_mean_distance, dim3(static_cast<uint32_t>(div_up(redo, kSorBlock))), dim3(kSorBlock), heap_lds,
                          ctx->stream, ctx->g_xyz.p, ctx->g_xyz.p + plane, ctx->g_xyz.p + 2 * plane, ctx->g_order.p,
                          remap, ctx->g_start.p, n, g, mean_k, dist, ctx->s_cell.p, redo,
-                         wave ? ctx->m_flag.p : static_cast<const uint8_t *>(nullptr), kth);
+                         wave ? ctx->m_flag.p : static_cast<const uint8_t *>(nullptr), rq.kth);
       PCP_HIP_TRY(ctx, hipGetLastError());
     }
   } else {
@@ -2774,7 +2809,7 @@ static int sor_run(pcp_context *ctx, const CloudView &cv, int32_t mean_k, double
     hipLaunchKernelGGL(k_sor_mean_distance, dim3(static_cast<uint32_t>(div_up(n, kSorBlock))), dim3(kSorBlock), heap_lds,
                        ctx->stream, ctx->g_xyz.p, ctx->g_xyz.p + plane, ctx->g_xyz.p + 2 * plane, ctx->g_order.p,
                        remap, ctx->g_start.p, n, g, mean_k, dist, static_cast<const int32_t *>(nullptr), int64_t(0),
-                       static_cast<const uint8_t *>(nullptr), kth);
+                       static_cast<const uint8_t *>(nullptr), rq.kth);
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
   {
@@ -2785,7 +2820,7 @@ static int sor_run(pcp_context *ctx, const CloudView &cv, int32_t mean_k, double
                          remap, n, c0, ctx->m_sums.p + 4);
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
-  return classify ? sor_classify(ctx, n, remap, std_mul, q_begin, q_end) : PCP_OK;
+  return rq.classify ? sor_classify(ctx, n, remap, rq.std_mul, q_begin, q_end) : PCP_OK;
 }
 
 // threshold from the chunk sums of the WHOLE cloud (ctx->m_sums), keep flags (ctx->m_flag, zero elsewhere) of the points
@@ -2885,27 +2920,6 @@ __global__ __launch_bounds__(kMB) void k_rows_margin(const float *__restrict__ x
   if ((threadIdx.x & 63) == 0) atomicMin(min_key, k);
 }
 
-struct SmoothStream {  // plain data, kept in ctx->css_blob between pcp_cloud_smooth_stream_begin and _next
-  pcp_mls_params p;
-  VgdStream S;
-  CloudView cv1;  // the survivors of the first filter (planes in ctx->c_xyz)
-  int64_t total_rows, kept_rows, rows_computed;
-  double threshold, max_dx, min_margin;
-  int32_t halo, redone;
-  double sampled_dx;  // the largest displacement sweep 0 saw on its sample of the voxels (sizes the halo; max_dx proves it)
-  double seconds[4];  // host clock of _begin: first filter + fit + voxel set, device allocations (inside the other three), sweep 0, sweep 1 + threshold
-  double alloc_bytes;  // device memory allocated during _begin
-};
-
-// the grid the emission searches, rebuilt (the outlier removal of a chunk overwrites it): the same call sequence as mls_run's
-static int stream_grid(pcp_context *ctx, const CloudView &cv, const pcp_mls_params *p, GridDesc *g) {
-  const char *ge = std::getenv("PCP_VGD_GRID");
-  const float dmax = static_cast<float>(1.7321 * (p->vgd_iterations + 1) * static_cast<double>(p->vgd_voxel_size) * 1.01 + 1e-6);
-  const float cell_emit = 2.0f * dmax;
-  if (!(ge && ge[0] == 'f') && cell_emit < static_cast<float>(p->search_radius)) return build_grid(ctx, cv, cell_emit, cell_emit, g);
-  return build_grid(ctx, cv, static_cast<float>(p->search_radius) * 1.001f, static_cast<float>(p->search_radius), g);
-}
-
 // bounding box of three device planes -> view
 static int view_of(pcp_context *ctx, const float *x, const float *y, const float *z, int64_t n, CloudView *cv) {
   cv->x = x;
@@ -2951,7 +2965,7 @@ static int view_of(pcp_context *ctx, const float *x, const float *y, const float
 static int smooth_first_filter(pcp_context *ctx, const pcp_mls_params *p, const CloudView &cv0, CloudView *out_cv1, int64_t *out_n1) {
   int rc;
   *out_n1 = 0;
-  if ((rc = sor_run(ctx, cv0, p->sor_mean_k, p->sor_std_mul, /*view_order=*/true)) != PCP_OK) return rc;
+  if ((rc = sor_run(ctx, cv0, {.mean_k = p->sor_mean_k, .std_mul = p->sor_std_mul, .view_order = true})) != PCP_OK) return rc;
   PCP_HIP_TRY(ctx, ctx->c_index.ensure(2 * (static_cast<size_t>(cv0.n) + 4)));
   int32_t *c_pos = ctx->c_index.p + static_cast<size_t>(cv0.n) + 4;  // view positions of the survivors
   int64_t n1 = 0;
@@ -3026,11 +3040,8 @@ extern "C" {
 
 int pcp_mls_process(pcp_context *ctx, const pcp_mls_params *p, int64_t *out_count) {
   if (!ctx) return PCP_ERR_INVALID;
-  int rc = check_mls_params(ctx, p);
+  int rc = enter_smoothing(ctx, "pcp_mls_process", p);
   if (rc != PCP_OK) return rc;
-  if (!ctx->xyz.p) return set_error(ctx, PCP_ERR_STATE, "pcp_mls_process: no cloud uploaded");
-  if (int rcf = require_finite_cloud(ctx, "pcp_mls_process")) return rcf;
-  PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
   rc = mls_run(ctx, uploaded_view(ctx, true), p, out_count);
   ctx->mls_result_live = rc == PCP_OK;
   return rc;
@@ -3057,94 +3068,64 @@ int pcp_mls_local_plane_samples(double radius, double step, int64_t capacity, fl
 int pcp_mls_stream_begin(pcp_context *ctx, const pcp_mls_params *p, int64_t chunk_capacity, int64_t *out_total,
                          int32_t *out_chunks) {
   if (!ctx) return PCP_ERR_INVALID;
-  int rc = check_mls_params(ctx, p);
+  int rc = enter_smoothing(ctx, "pcp_mls_stream_begin", p, {.accepts = Upsamplings::VgdOnly, .min_capacity = 32768, .capacity = chunk_capacity});
   if (rc != PCP_OK) return rc;
-  if (p->upsampling == PCP_UPSAMPLING_SAMPLE_LOCAL_PLANE)
-    return set_error(ctx, PCP_ERR_INVALID, "pcp_mls_stream_begin: SAMPLE_LOCAL_PLANE (1) is not streamed (pcp_mls_process emits it)");
-  if (p->upsampling != 3) return set_error(ctx, PCP_ERR_INVALID, "pcp_mls_stream_begin: upsampling must be VOXEL_GRID_DILATION (3)");
-  if (chunk_capacity < 32768 || chunk_capacity >= (int64_t(1) << 31))
-    return set_error(ctx, PCP_ERR_INVALID, "pcp_mls_stream_begin: chunk_capacity must be in [32768, 2^31)");
-  if (!ctx->xyz.p) return set_error(ctx, PCP_ERR_STATE, "pcp_mls_stream_begin: no cloud uploaded");
-  if (int rcf = require_finite_cloud(ctx, "pcp_mls_stream_begin")) return rcf;
-  PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  ctx->vgd_next = -1;
   int64_t total = 0;
-  if ((rc = mls_run(ctx, uploaded_view(ctx, true), p, &total, 0, -1, false, chunk_capacity)) != PCP_OK) return rc;
+  if ((rc = mls_run(ctx, uploaded_view(ctx, true), p, &total, {.stream_capacity = chunk_capacity})) != PCP_OK) return rc;
   if (out_total) *out_total = total;
-  if (out_chunks) *out_chunks = static_cast<int32_t>(ctx->vgd_chunks.size() / 3);
+  if (out_chunks) *out_chunks = static_cast<int32_t>(ctx->emission.chunks.size());
   return PCP_OK;
 }
 
 int pcp_mls_stream_next(pcp_context *ctx, int64_t *out_count) {
   if (!ctx || !out_count) return PCP_ERR_INVALID;
   *out_count = 0;
-  if (ctx->vgd_next < 0 || ctx->vgd_blob.size() != sizeof(VgdStream))
-    return set_error(ctx, PCP_ERR_STATE, "pcp_mls_stream_next: no stream (call pcp_mls_stream_begin)");
+  if (!ctx->emission.open()) return set_error(ctx, PCP_ERR_STATE, "pcp_mls_stream_next: no stream (call pcp_mls_stream_begin)");
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t k = static_cast<size_t>(ctx->vgd_next) * 3;
   ctx->mls_result_live = false;
-  if (k >= ctx->vgd_chunks.size()) {  // past the last chunk
+  if (ctx->emission.next >= static_cast<int64_t>(ctx->emission.chunks.size())) {  // past the last chunk
     ctx->mls_count = 0;
     ctx->mls_result_live = true;
     return PCP_OK;
   }
-  VgdStream S;
-  std::memcpy(&S, ctx->vgd_blob.data(), sizeof(S));
   int64_t m = 0;
-  const int rc = vgd_emit(ctx, S, ctx->vgd_chunks[k], ctx->vgd_chunks[k + 1], ctx->vgd_chunks[k + 2], &m);
+  const int rc = vgd_emit(ctx, ctx->emission.of, ctx->emission.chunks[static_cast<size_t>(ctx->emission.next)], &m);
   if (rc != PCP_OK) return rc;
   ctx->mls_result_live = true;
-  ctx->vgd_next += 1;
+  ctx->emission.next += 1;
   *out_count = m;
   return PCP_OK;
 }
 
 int pcp_mls_stream_seek(pcp_context *ctx, int32_t chunk) {
   if (!ctx) return PCP_ERR_INVALID;
-  if (ctx->vgd_next < 0 || ctx->vgd_blob.empty())
-    return set_error(ctx, PCP_ERR_STATE, "pcp_mls_stream_seek: no stream (call pcp_mls_stream_begin)");
-  const int64_t chunks = static_cast<int64_t>(ctx->vgd_chunks.size() / 3);
+  if (!ctx->emission.open()) return set_error(ctx, PCP_ERR_STATE, "pcp_mls_stream_seek: no stream (call pcp_mls_stream_begin)");
+  const int64_t chunks = static_cast<int64_t>(ctx->emission.chunks.size());
   if (chunk < 0 || chunk > chunks)
     return set_error(ctx, PCP_ERR_RANGE, "pcp_mls_stream_seek: chunk %d outside 0..%lld", chunk, (long long)chunks);
-  ctx->vgd_next = chunk;
+  ctx->emission.next = chunk;
   return PCP_OK;
 }
 
 int pcp_mls_process_shard(pcp_context *ctx, const pcp_mls_params *p, int64_t index_begin, int64_t index_end,
                           int64_t *out_count) {
   if (!ctx) return PCP_ERR_INVALID;
-  int rc = check_mls_params(ctx, p);
+  int rc = enter_smoothing(ctx, "pcp_mls_process_shard", p, {.accepts = Upsamplings::NoneOnly});
   if (rc != PCP_OK) return rc;
-  if (!ctx->xyz.p) return set_error(ctx, PCP_ERR_STATE, "pcp_mls_process_shard: no cloud uploaded");
-  if (int rcf = require_finite_cloud(ctx, "pcp_mls_process_shard")) return rcf;
-  if (p->upsampling == PCP_UPSAMPLING_SAMPLE_LOCAL_PLANE)
-    return set_error(ctx, PCP_ERR_INVALID, "pcp_mls_process_shard: SAMPLE_LOCAL_PLANE (1) is not sharded (its disks follow the sign of each "
-                     "point's fitted normal, which a re-ordered fit may flip): run pcp_mls_process");
-  if (p->upsampling != 0)
-    return set_error(ctx, PCP_ERR_INVALID, "pcp_mls_process_shard: query sharding supports upsampling NONE only");
   if (index_begin < 0 || index_end > ctx->n || index_begin > index_end)
     return set_error(ctx, PCP_ERR_RANGE, "pcp_mls_process_shard: query range [%lld,%lld) outside 0..%lld",
                      (long long)index_begin, (long long)index_end, (long long)ctx->n);
-  PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  rc = mls_run(ctx, uploaded_view(ctx, true), p, out_count, index_begin, index_end);
+  rc = mls_run(ctx, uploaded_view(ctx, true), p, out_count, {.q_begin = index_begin, .q_end = index_end});
   ctx->mls_result_live = rc == PCP_OK;
   return rc;
 }
 
 int pcp_mls_process_slab(pcp_context *ctx, const pcp_mls_params *p, int32_t slab, int32_t n_slabs, int64_t *out_count) {
   if (!ctx) return PCP_ERR_INVALID;
-  int rc = check_mls_params(ctx, p);
+  int rc = enter_smoothing(ctx, "pcp_mls_process_slab", p, {.accepts = Upsamplings::NoneOnly});
   if (rc != PCP_OK) return rc;
-  if (!ctx->xyz.p) return set_error(ctx, PCP_ERR_STATE, "pcp_mls_process_slab: no cloud uploaded");
-  if (int rcf = require_finite_cloud(ctx, "pcp_mls_process_slab")) return rcf;
-  if (p->upsampling == PCP_UPSAMPLING_SAMPLE_LOCAL_PLANE)
-    return set_error(ctx, PCP_ERR_INVALID, "pcp_mls_process_slab: SAMPLE_LOCAL_PLANE (1) is not sharded (its disks follow the sign of each "
-                     "point's fitted normal, which a re-ordered fit may flip): run pcp_mls_process");
-  if (p->upsampling != 0)
-    return set_error(ctx, PCP_ERR_INVALID, "pcp_mls_process_slab: query sharding supports upsampling NONE only");
   if (n_slabs < 1 || slab < 0 || slab >= n_slabs) return set_error(ctx, PCP_ERR_RANGE, "pcp_mls_process_slab: slab %d of %d", slab, n_slabs);
-  PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  rc = mls_run(ctx, uploaded_view(ctx, true), p, out_count, 0, -1, false, 0, slab, n_slabs);
+  rc = mls_run(ctx, uploaded_view(ctx, true), p, out_count, {.slab = slab, .n_slabs = n_slabs});
   ctx->mls_result_live = rc == PCP_OK;
   return rc;
 }
@@ -3178,7 +3159,7 @@ int pcp_sor(pcp_context *ctx, int32_t mean_k, double std_mul, uint8_t *out_keep,
   if (n == 0) return PCP_OK;
   ctx->sor_distances_live = false;
   ctx->sor_partial_slab = ctx->sor_partial_slabs = -1;
-  int rc = sor_run(ctx, uploaded_view(ctx, true), mean_k, std_mul);
+  int rc = sor_run(ctx, uploaded_view(ctx, true), {.mean_k = mean_k, .std_mul = std_mul});
   if (rc != PCP_OK) return rc;
   ctx->sor_distances_live = true;
   if (out_kept) {
@@ -3219,7 +3200,8 @@ int pcp_sor_partial(pcp_context *ctx, int32_t mean_k, int32_t slab, int32_t n_sl
   ctx->sor_partial_slab = ctx->sor_partial_slabs = -1;
   if (n == 0) return PCP_OK;
   // (a slab without chunks still builds the grid: pcp_sor_finish reads the cell order from it)
-  if ((rc = sor_run(ctx, uploaded_view(ctx, true), mean_k, 0.0, false, slab, n_slabs, /*classify=*/false)) != PCP_OK) return rc;
+  rc = sor_run(ctx, uploaded_view(ctx, true), {.mean_k = mean_k, .std_mul = 0.0, .slab = slab, .n_slabs = n_slabs, .classify = false});
+  if (rc != PCP_OK) return rc;
   if (c1 > c0)
     PCP_HIP_TRY(ctx, hipMemcpyAsync(out_chunk_sums, ctx->m_sums.p + 4 + 2 * c0, static_cast<size_t>(c1 - c0) * 2 * sizeof(double),
                                     hipMemcpyDefault, ctx->stream));  // host or device memory
@@ -3272,13 +3254,8 @@ int pcp_cloud_smooth(pcp_context *ctx, const pcp_mls_params *p, int64_t *out_cou
 }
 
 static int cloud_smooth_run(pcp_context *ctx, const pcp_mls_params *p, int64_t *out_count) {
-  int rc = check_mls_params(ctx, p);
+  int rc = enter_smoothing(ctx, "pcp_cloud_smooth", p, {.chain = true});
   if (rc != PCP_OK) return rc;
-  if (!ctx->xyz.p) return set_error(ctx, PCP_ERR_STATE, "pcp_cloud_smooth: no cloud uploaded");
-  if (int rcf = require_finite_cloud(ctx, "pcp_cloud_smooth")) return rcf;
-  if (p->sor_mean_k < 1 || p->sor_mean_k > 254)
-    return set_error(ctx, PCP_ERR_INVALID, "pcp_cloud_smooth: sor_mean_k %d out of range (1..254)", p->sor_mean_k);
-  PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
   ctx->mls_count = 0;
   ctx->sor_distances_live = false;
   ctx->sor_partial_slab = ctx->sor_partial_slabs = -1;
@@ -3296,7 +3273,7 @@ static int cloud_smooth_run(pcp_context *ctx, const pcp_mls_params *p, int64_t *
   // SAMPLE_LOCAL_PLANE: the emission writes the rows with the caller's indices and their positions as the planes below
   const bool slp = p->upsampling == PCP_UPSAMPLING_SAMPLE_LOCAL_PLANE;
   int64_t m = 0;
-  if ((rc = mls_run(ctx, cv1, p, &m, 0, -1, /*keep_rows=*/plain || slp)) != PCP_OK) return rc;
+  if ((rc = mls_run(ctx, cv1, p, &m, {.keep_rows = plain || slp})) != PCP_OK) return rc;
   if (m == 0) return PCP_OK;
   const size_t plane2 = (static_cast<size_t>(m) + 3) & ~size_t(3);
   PCP_HIP_TRY(ctx, ctx->c_xyz2.ensure(3 * plane2 + 4));
@@ -3341,8 +3318,8 @@ static int cloud_smooth_run(pcp_context *ctx, const pcp_mls_params *p, int64_t *
   }
   const bool vgd = !plain && !slp;
   const double dens2 = vgd ? (2.0 * p->vgd_iterations + 1.0) / (static_cast<double>(p->vgd_voxel_size) * p->vgd_voxel_size) : 0.0;
-  const bool clustered = vgd;
-  if ((rc = sor_run(ctx, cv2, p->sor_mean_k, p->sor_std_mul, false, 0, 1, true, nullptr, clustered, dens2)) != PCP_OK) return rc;
+  rc = sor_run(ctx, cv2, {.mean_k = p->sor_mean_k, .std_mul = p->sor_std_mul, .clustered = vgd, .area_density = dens2});
+  if (rc != PCP_OK) return rc;
   int64_t kept = 0;
   if (plain) {
     // survivors back in the caller's order (ascending index, as a filter chain on the input cloud leaves them): every
@@ -3399,7 +3376,9 @@ static int css_rows_distances(pcp_context *ctx, SmoothStream &st, const float *r
   if ((rc = view_of(ctx, x2, y2, z2, m, &cv2)) != PCP_OK) return rc;
   PCP_HIP_TRY(ctx, ctx->s_kth.ensure(static_cast<size_t>(m) + 8));
   const double dens2 = (2.0 * st.p.vgd_iterations + 1.0) / (static_cast<double>(st.p.vgd_voxel_size) * st.p.vgd_voxel_size);
-  if ((rc = sor_run(ctx, cv2, st.p.sor_mean_k, st.p.sor_std_mul, false, 0, 1, /*classify=*/false, ctx->s_kth.p, /*clustered=*/true, dens2, r0, r1)) != PCP_OK) return rc;
+  rc = sor_run(ctx, cv2, {.mean_k = st.p.sor_mean_k, .std_mul = st.p.sor_std_mul, .classify = false, .kth = ctx->s_kth.p, .clustered = true,
+                          .area_density = dens2, .ball = ctx->css_ball, .row_begin = r0, .row_end = r1});
+  if (rc != PCP_OK) return rc;
   // MLSVoxelGrid::getPosition of the first missing plane on either side (fp32, as k_voxel_emit forms it)
   const float xl = static_cast<float>(ea - 1) * st.S.v.vs + st.S.v.bminx, xh = static_cast<float>(eb + 1) * st.S.v.vs + st.S.v.bminx;
   PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->css_words.p + 1, 0xff, 4, ctx->stream));
@@ -3416,12 +3395,15 @@ static int css_rows_distances(pcp_context *ctx, SmoothStream &st, const float *r
   return PCP_OK;
 }
 
-// Sweep 1 of one chunk: the voxels of planes [ia, ib] emitted together with `H` planes on either side, the mean k-NN
-// distances of every emitted row, the chunk's own rows' distances into css_dist at row0.  *out_rows = the chunk's own rows,
+// a chunk's own voxels as an emission: the strips of its planes (the brick form keeps NBY strips per plane)
+static VgdChunk chain_strips(const ChainChunk &c, int64_t NBY) { return {c.first_plane * NBY, (c.last_plane + 1) * NBY, c.voxels}; }
+
+// Sweep 1 of one chunk: the voxels of its planes emitted together with `H` planes on either side, the mean k-NN
+// distances of every emitted row, the chunk's own rows' distances into css_dist at its row0.  *out_rows = the chunk's own rows,
 // *out_margin as above, *out_ext_rows = rows computed.
-static int css_sweep1_chunk(pcp_context *ctx, SmoothStream &st, const std::vector<unsigned long long> &planes, int64_t ia, int64_t ib,
-                            int64_t H, int64_t row0, int64_t *out_rows, float *out_margin, int64_t *out_ext_rows) {
-  const int64_t NX = st.S.v.NX, NBY = st.S.NBY;
+static int css_sweep1_chunk(pcp_context *ctx, SmoothStream &st, const std::vector<unsigned long long> &planes, const ChainChunk &chunk,
+                            int64_t H, int64_t *out_rows, float *out_margin, int64_t *out_ext_rows) {
+  const int64_t NX = st.S.v.NX, NBY = st.S.NBY, ia = chunk.first_plane, ib = chunk.last_plane;
   const int64_t ea = std::max<int64_t>(0, ia - H), eb = std::min<int64_t>(NX - 1, ib + H);
   *out_margin = INFINITY;
   unsigned long long a = 0, core = 0, ext = 0;
@@ -3435,11 +3417,10 @@ static int css_sweep1_chunk(pcp_context *ctx, SmoothStream &st, const std::vecto
     return set_error(ctx, PCP_ERR_RANGE, "pcp_cloud_smooth_stream_begin: a chunk and its halo hold %llu voxels (2^31 is the limit of one "
                      "emission): use a smaller chunk_capacity", ext);
   int rc;
-  GridDesc g;
-  if ((rc = stream_grid(ctx, st.cv1, &st.p, &g)) != PCP_OK) return rc;
-  st.S.g = g;
+  if ((rc = emission_grid(ctx, st.cv1, &st.p, /*fit_grid_stands=*/false, &st.S.g)) != PCP_OK) return rc;
   int64_t m = 0;
-  if ((rc = vgd_emit(ctx, st.S, ea * NBY, (eb + 1) * NBY, static_cast<int64_t>(ext), &m, ctx->css_words.p, 0, /*positions_only=*/true)) != PCP_OK) return rc;
+  rc = vgd_emit(ctx, st.S, {ea * NBY, (eb + 1) * NBY, static_cast<int64_t>(ext)}, &m, {.max_dx = ctx->css_words.p, .positions_only = true});
+  if (rc != PCP_OK) return rc;
   // the chunk's own rows inside the (compacted, order-preserving) emission: voxels without a valid fit give no row
   int64_t r0 = 0, r1 = 0;
   if (a > 0 && (rc = compact_flags(ctx, ctx->m_flag.p, static_cast<int64_t>(a), nullptr, 0, &r0)) != PCP_OK) return rc;
@@ -3447,42 +3428,17 @@ static int css_sweep1_chunk(pcp_context *ctx, SmoothStream &st, const std::vecto
   *out_rows = r1 - r0;
   *out_ext_rows = m;
   if (r1 == r0) return PCP_OK;
-  return css_rows_distances(ctx, st, ctx->mls_xyz.p, m, r0, r1, ea, eb, row0, out_margin);
+  return css_rows_distances(ctx, st, ctx->mls_xyz.p, m, r0, r1, ea, eb, chunk.row0, out_margin);
 }
 
 }  // namespace pcp
 
-int pcp_cloud_smooth_stream_begin(pcp_context *ctx, const pcp_mls_params *p, int64_t chunk_capacity, int64_t *out_total_rows,
-                                  int64_t *out_kept_rows, int32_t *out_chunks) {
-  if (!ctx) return PCP_ERR_INVALID;
-  int rc = check_mls_params(ctx, p);
-  if (rc != PCP_OK) return rc;
-  if (p->upsampling == PCP_UPSAMPLING_SAMPLE_LOCAL_PLANE)
-    return set_error(ctx, PCP_ERR_INVALID, "pcp_cloud_smooth_stream_begin: SAMPLE_LOCAL_PLANE (1) is not streamed (pcp_cloud_smooth runs it)");
-  if (p->upsampling != 3) return set_error(ctx, PCP_ERR_INVALID, "pcp_cloud_smooth_stream_begin: upsampling must be VOXEL_GRID_DILATION (3)");
-  if (chunk_capacity < 4096 || chunk_capacity >= (int64_t(1) << 31))
-    return set_error(ctx, PCP_ERR_INVALID, "pcp_cloud_smooth_stream_begin: chunk_capacity must be in [4096, 2^31)");
-  if (!ctx->xyz.p) return set_error(ctx, PCP_ERR_STATE, "pcp_cloud_smooth_stream_begin: no cloud uploaded");
-  if (int rcf = require_finite_cloud(ctx, "pcp_cloud_smooth_stream_begin")) return rcf;
-  if (p->sor_mean_k < 1 || p->sor_mean_k > 254)
-    return set_error(ctx, PCP_ERR_INVALID, "pcp_cloud_smooth_stream_begin: sor_mean_k %d out of range (1..254)", p->sor_mean_k);
-  PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  ctx->mls_count = 0;
-  ctx->css_next = -1;
-  ctx->css_chunks.clear();
-  ctx->sor_distances_live = false;
-  ctx->sor_partial_slab = ctx->sor_partial_slabs = -1;
-  if (out_total_rows) *out_total_rows = 0;
-  if (out_kept_rows) *out_kept_rows = 0;
-  if (out_chunks) *out_chunks = 0;
-  SmoothStream st{};
-  st.p = *p;
+// pcp_cloud_smooth_stream_begin between its checks and the opening of the stream (the chain is in its Building phase): the
+// first filter, the fits, the voxel set, the chunks (ctx->chain.chunks, empty on entry) and sweeps 0 and 1; what the stream
+// keeps beside the chunks goes into `st` (st.p set by the caller)
+static int chain_build(pcp_context *ctx, const pcp_mls_params *p, int64_t chunk_capacity, SmoothStream &st) {
+  int rc;
   const CloudView cv0 = uploaded_view(ctx, true);
-  struct Building {
-    pcp_context *c;
-    explicit Building(pcp_context *c_) : c(c_) { c->css_building = true; }
-    ~Building() { c->css_building = false; }
-  } building(ctx);
   auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const AllocTally alloc_before = alloc_tally();
   double t_mark = now();
@@ -3491,28 +3447,18 @@ int pcp_cloud_smooth_stream_begin(pcp_context *ctx, const pcp_mls_params *p, int
     st.seconds[k] += t - t_mark;
     t_mark = t;
   };
-  auto publish = [&]() {
-    ctx->css_blob.assign(reinterpret_cast<const uint8_t *>(&st), reinterpret_cast<const uint8_t *>(&st) + sizeof(st));
-    ctx->css_next = 0;
-  };
-  if (cv0.n == 0) {
-    publish();
-    return PCP_OK;
-  }
+  if (cv0.n == 0) return PCP_OK;
   int64_t n1 = 0;
   if ((rc = smooth_first_filter(ctx, p, cv0, &st.cv1, &n1)) != PCP_OK) return rc;
-  if (n1 == 0) {
-    publish();
-    return PCP_OK;
-  }
+  if (n1 == 0) return PCP_OK;
   // the fits and the dilated voxel set (counted per plane of the first axis), as pcp_mls_stream_begin leaves them
   int64_t total_voxels = 0;
   // (the strip-wise chunk plan of that call is not used -- the chain cuts by whole planes --: its capacity is set so that
   // the brick form is never left for a strip's sake)
-  if ((rc = mls_run(ctx, st.cv1, p, &total_voxels, 0, -1, false, (int64_t(1) << 31) - 1)) != PCP_OK) return rc;
-  if (ctx->vgd_blob.size() != sizeof(VgdStream)) return set_error(ctx, PCP_ERR_STATE, "pcp_cloud_smooth_stream_begin: no voxel set");
-  std::memcpy(&st.S, ctx->vgd_blob.data(), sizeof(VgdStream));
-  ctx->vgd_next = -1;  // (that stream's own chunk plan is not used)
+  if ((rc = mls_run(ctx, st.cv1, p, &total_voxels, {.stream_capacity = (int64_t(1) << 31) - 1})) != PCP_OK) return rc;
+  if (!ctx->emission.open()) return set_error(ctx, PCP_ERR_STATE, "pcp_cloud_smooth_stream_begin: no voxel set");
+  st.S = ctx->emission.of;
+  end_emission_stream(ctx);  // (that stream's own chunk plan is not used)
   if (!st.S.bricks)
     return set_error(ctx, PCP_ERR_INVALID, "pcp_cloud_smooth_stream_begin: the voxel set is in its dense form (PCP_VGD_DENSE=1, or a grid taller "
                      "than the brick form handles); the streamed chain cuts the brick form by planes");
@@ -3521,7 +3467,7 @@ int pcp_cloud_smooth_stream_begin(pcp_context *ctx, const pcp_mls_params *p, int
   PCP_HIP_TRY(ctx, hipMemcpyAsync(planes.data(), ctx->v_plane.p, planes.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
   PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   // chunks = maximal runs of whole planes that hold at most chunk_capacity voxels
-  std::vector<int64_t> &ch = ctx->css_chunks;  // per chunk: ia, ib, voxels, row0, rows
+  std::vector<ChainChunk> &ch = ctx->chain.chunks;
   {
     int64_t ia = -1;
     unsigned long long cnt = 0;
@@ -3531,16 +3477,16 @@ int pcp_cloud_smooth_stream_begin(pcp_context *ctx, const pcp_mls_params *p, int
         return set_error(ctx, PCP_ERR_RANGE, "pcp_cloud_smooth_stream_begin: plane %lld of the voxel grid holds %llu voxels, more than "
                          "chunk_capacity %lld", (long long)ix, c, (long long)chunk_capacity);
       if (ia >= 0 && cnt + c > static_cast<unsigned long long>(chunk_capacity)) {
-        ch.insert(ch.end(), {ia, ix - 1, static_cast<int64_t>(cnt), 0, 0});
+        ch.push_back({ia, ix - 1, static_cast<int64_t>(cnt), 0, 0});
         ia = -1;
         cnt = 0;
       }
       if (c > 0 && ia < 0) ia = ix;
       cnt += c;
     }
-    if (ia >= 0 && cnt > 0) ch.insert(ch.end(), {ia, NX - 1, static_cast<int64_t>(cnt), 0, 0});
+    if (ia >= 0 && cnt > 0) ch.push_back({ia, NX - 1, static_cast<int64_t>(cnt), 0, 0});
   }
-  const size_t n_chunks = ch.size() / 5;
+  const size_t n_chunks = ch.size();
   PCP_HIP_TRY(ctx, ctx->css_dist.ensure(static_cast<size_t>(total_voxels) + 8));
   PCP_HIP_TRY(ctx, ctx->css_words.ensure(32));
   PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->css_words.p, 0, 32 * 4, ctx->stream));
@@ -3553,14 +3499,11 @@ int pcp_cloud_smooth_stream_begin(pcp_context *ctx, const pcp_mls_params *p, int
   // has to size the halo well enough that the check passes: it projects a sample of the voxels (one workgroup in
   // kCssSample, nothing stored: a tenth of an emission; emitting every chunk for D alone was 16 % of the chain).
   constexpr int32_t kCssSample = 8;
-  {
-    GridDesc g;
-    if ((rc = stream_grid(ctx, st.cv1, &st.p, &g)) != PCP_OK) return rc;
-    st.S.g = g;
-    for (size_t c = 0; c < n_chunks; ++c) {
-      int64_t m0 = 0;
-      if ((rc = vgd_emit(ctx, st.S, ch[5 * c] * st.S.NBY, (ch[5 * c + 1] + 1) * st.S.NBY, ch[5 * c + 2], &m0, ctx->css_words.p, kCssSample)) != PCP_OK) return rc;
-    }
+  if ((rc = emission_grid(ctx, st.cv1, &st.p, /*fit_grid_stands=*/false, &st.S.g)) != PCP_OK) return rc;
+  for (const ChainChunk &c : ch) {
+    int64_t m0 = 0;
+    rc = vgd_emit(ctx, st.S, chain_strips(c, st.S.NBY), &m0, {.max_dx = ctx->css_words.p, .sample_step = kCssSample});
+    if (rc != PCP_OK) return rc;
   }
   auto read_max_dx = [&](double *out) -> int {
     uint32_t dx_bits = 0;
@@ -3586,12 +3529,12 @@ int pcp_cloud_smooth_stream_begin(pcp_context *ctx, const pcp_mls_params *p, int
     // they were allocated several times over -- 206 GB of hipMalloc in a first call on the 10 M-point map, 1.8 of its 4.1 s
     // (a device allocation costs 20-40 ms per GB here; pcp_cloud_smooth_stream_stats [9], [12]).
     unsigned long long most = 0, most_own = 0;  // voxels of the largest chunk with its halo / on its own
-    for (size_t c = 0; c < n_chunks; ++c) {
-      const int64_t ea = std::max<int64_t>(0, ch[5 * c] - H), eb = std::min<int64_t>(NX - 1, ch[5 * c + 1] + H);
+    for (const ChainChunk &c : ch) {
+      const int64_t ea = std::max<int64_t>(0, c.first_plane - H), eb = std::min<int64_t>(NX - 1, c.last_plane + H);
       unsigned long long e = 0;
       for (int64_t ix = ea; ix <= eb; ++ix) e += planes[static_cast<size_t>(ix)];
       most = std::max(most, e);
-      most_own = std::max(most_own, static_cast<unsigned long long>(ch[5 * c + 2]));
+      most_own = std::max(most_own, static_cast<unsigned long long>(c.voxels));
     }
     if (most < (1ull << 31)) {  // (beyond: css_sweep1_chunk reports the chunk that is too large)
       const size_t n = static_cast<size_t>(most), plane = (n + 3) & ~size_t(3), own = static_cast<size_t>(most_own);
@@ -3630,9 +3573,9 @@ int pcp_cloud_smooth_stream_begin(pcp_context *ctx, const pcp_mls_params *p, int
   if (!(ctx->css_ball > 0.0)) ctx->css_ball = 1.2;
   for (size_t c = 0; c < n_chunks; ++c) {
     int64_t rows = 0, ext_rows = 0;
-    if ((rc = css_sweep1_chunk(ctx, st, planes, ch[5 * c], ch[5 * c + 1], H, row0, &rows, &margin[c], &ext_rows)) != PCP_OK) return rc;
-    ch[5 * c + 3] = row0;
-    ch[5 * c + 4] = rows;
+    ch[c].row0 = row0;
+    if ((rc = css_sweep1_chunk(ctx, st, planes, ch[c], H, &rows, &margin[c], &ext_rows)) != PCP_OK) return rc;
+    ch[c].rows = rows;
     row0 += rows;
     st.rows_computed += ext_rows;
     if (rows > 0) {
@@ -3654,13 +3597,13 @@ int pcp_cloud_smooth_stream_begin(pcp_context *ctx, const pcp_mls_params *p, int
                                      "(margin %g m against a displacement of %g m with every plane emitted)", c, (double)margin[c], st.max_dx);
       Hc = std::max(2 * Hc, Hc < H_needed ? H_needed : 0);
       int64_t rows = 0, ext_rows = 0;
-      if ((rc = css_sweep1_chunk(ctx, st, planes, ch[5 * c], ch[5 * c + 1], Hc, ch[5 * c + 3], &rows, &margin[c], &ext_rows)) != PCP_OK) return rc;
-      if (rows != ch[5 * c + 4]) return set_error(ctx, PCP_ERR_STATE, "pcp_cloud_smooth_stream_begin: chunk %zu changed its rows", c);
+      if ((rc = css_sweep1_chunk(ctx, st, planes, ch[c], Hc, &rows, &margin[c], &ext_rows)) != PCP_OK) return rc;
+      if (rows != ch[c].rows) return set_error(ctx, PCP_ERR_STATE, "pcp_cloud_smooth_stream_begin: chunk %zu changed its rows", c);
       st.redone += 1;
       st.rows_computed += ext_rows;
       st.halo = static_cast<int32_t>(std::max<int64_t>(st.halo, std::min<int64_t>(Hc, NX)));
     }
-    if (ch[5 * c + 4] > 0) st.min_margin = std::min(st.min_margin, static_cast<double>(margin[c]));
+    if (ch[c].rows > 0) st.min_margin = std::min(st.min_margin, static_cast<double>(margin[c]));
   }
   if (st.total_rows > 0) {
     // mean + mul * stddev over ALL rows in row order (chunks of kSorChunk rows, fixed trees: the same on every run)
@@ -3683,48 +3626,72 @@ int pcp_cloud_smooth_stream_begin(pcp_context *ctx, const pcp_mls_params *p, int
   lap(3);
   st.seconds[1] = alloc_tally().seconds - alloc_before.seconds;
   st.alloc_bytes = alloc_tally().bytes - alloc_before.bytes;
-  publish();
+  return PCP_OK;
+}
+
+int pcp_cloud_smooth_stream_begin(pcp_context *ctx, const pcp_mls_params *p, int64_t chunk_capacity, int64_t *out_total_rows,
+                                  int64_t *out_kept_rows, int32_t *out_chunks) {
+  if (!ctx) return PCP_ERR_INVALID;
+  int rc = enter_smoothing(ctx, "pcp_cloud_smooth_stream_begin", p,
+                           {.accepts = Upsamplings::VgdOnly, .chain = true, .min_capacity = 4096, .capacity = chunk_capacity});
+  if (rc != PCP_OK) return rc;
+  ctx->mls_count = 0;
+  ctx->sor_distances_live = false;
+  ctx->sor_partial_slab = ctx->sor_partial_slabs = -1;
+  if (out_total_rows) *out_total_rows = 0;
+  if (out_kept_rows) *out_kept_rows = 0;
+  if (out_chunks) *out_chunks = 0;
+  // The stream of an earlier call is over from here on.  A call that fails leaves no stream: the numbers of the last stream
+  // built, if there was one, stay readable.
+  const StreamPhase failed = ctx->chain.phase == StreamPhase::None ? StreamPhase::None : StreamPhase::Ended;
+  ctx->chain.phase = StreamPhase::Building;
+  ctx->chain.chunks.clear();
+  SmoothStream st{};
+  st.p = *p;
+  if ((rc = chain_build(ctx, p, chunk_capacity, st)) != PCP_OK) {
+    ctx->chain.phase = failed;
+    return rc;
+  }
+  ctx->chain.of = st;
+  ctx->chain.next = 0;
+  ctx->chain.phase = StreamPhase::Open;
   if (out_total_rows) *out_total_rows = st.total_rows;
   if (out_kept_rows) *out_kept_rows = st.kept_rows;
-  if (out_chunks) *out_chunks = static_cast<int32_t>(n_chunks);
+  if (out_chunks) *out_chunks = static_cast<int32_t>(ctx->chain.chunks.size());
   return PCP_OK;
 }
 
 int pcp_cloud_smooth_stream_next(pcp_context *ctx, int64_t *out_count) {
   if (!ctx || !out_count) return PCP_ERR_INVALID;
   *out_count = 0;
-  if (ctx->css_next < 0 || ctx->css_blob.size() != sizeof(SmoothStream))
+  if (!ctx->chain.open())
     return set_error(ctx, PCP_ERR_STATE, "pcp_cloud_smooth_stream_next: no stream (call pcp_cloud_smooth_stream_begin; any other "
                      "smoothing call ends a stream)");
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
   ctx->mls_count = 0;
   ctx->mls_result_live = false;
-  SmoothStream st;
-  std::memcpy(&st, ctx->css_blob.data(), sizeof(st));
-  const std::vector<int64_t> &ch = ctx->css_chunks;
+  const SmoothStream &st = ctx->chain.of;
+  const std::vector<ChainChunk> &ch = ctx->chain.chunks;
   // (chunks whose every voxel lacks a valid fit have no rows: skipped)
-  while (static_cast<size_t>(ctx->css_next) * 5 < ch.size() && ch[static_cast<size_t>(ctx->css_next) * 5 + 4] == 0) ctx->css_next += 1;
-  const size_t c = static_cast<size_t>(ctx->css_next);
-  if (c * 5 >= ch.size()) {  // past the last chunk
+  while (static_cast<size_t>(ctx->chain.next) < ch.size() && ch[static_cast<size_t>(ctx->chain.next)].rows == 0) ctx->chain.next += 1;
+  const size_t c = static_cast<size_t>(ctx->chain.next);
+  if (c >= ch.size()) {  // past the last chunk
     ctx->mls_result_live = true;
     return PCP_OK;
   }
-  const int64_t ia = ch[5 * c], ib = ch[5 * c + 1], voxels = ch[5 * c + 2], row0 = ch[5 * c + 3], rows = ch[5 * c + 4];
-  const int64_t next_before = ctx->css_next;
   int rc;
   double *d_thr = reinterpret_cast<double *>(ctx->css_words.p + 8);
-  GridDesc g;
-  if ((rc = stream_grid(ctx, st.cv1, &st.p, &g)) != PCP_OK) return rc;  // (build_grid does not go through mls_run: the stream stays)
-  st.S.g = g;
+  VgdStream S = st.S;
+  if ((rc = emission_grid(ctx, st.cv1, &st.p, /*fit_grid_stands=*/false, &S.g)) != PCP_OK) return rc;  // (build_grid does not go through mls_run: the stream stays)
   int64_t m = 0;
-  if ((rc = vgd_emit(ctx, st.S, ia * st.S.NBY, (ib + 1) * st.S.NBY, voxels, &m)) != PCP_OK) return rc;
-  if (m != rows) return set_error(ctx, PCP_ERR_STATE, "pcp_cloud_smooth_stream_next: chunk %zu emitted %lld rows, sweep 1 saw %lld", c,
-                                  (long long)m, (long long)rows);
+  if ((rc = vgd_emit(ctx, S, chain_strips(ch[c], S.NBY), &m)) != PCP_OK) return rc;
+  if (m != ch[c].rows) return set_error(ctx, PCP_ERR_STATE, "pcp_cloud_smooth_stream_next: chunk %zu emitted %lld rows, sweep 1 saw %lld", c,
+                                        (long long)m, (long long)ch[c].rows);
   // source indices back to the uploaded cloud (ctx->c_index: the caller's indices of cloud 1), keep flags by the stored distance
   PCP_HIP_TRY(ctx, hipMemcpyAsync(d_thr, &st.threshold, 8, hipMemcpyHostToDevice, ctx->stream));
   hipLaunchKernelGGL(k_remap_index, dim3(blocks_of(m)), dim3(kMB), 0, ctx->stream, ctx->mls_index.p, m, ctx->c_index.p);
   hipLaunchKernelGGL(k_rows_classify, dim3(static_cast<uint32_t>(std::min<int64_t>(div_up(m, kMB), 1 << 16))), dim3(kMB), 0, ctx->stream,
-                     ctx->css_dist.p + row0, m, d_thr, ctx->m_flag.p, static_cast<unsigned long long *>(nullptr));
+                     ctx->css_dist.p + ch[c].row0, m, d_thr, ctx->m_flag.p, static_cast<unsigned long long *>(nullptr));
   PCP_HIP_TRY(ctx, hipGetLastError());
   int64_t kept = 0;
   PCP_HIP_TRY(ctx, ctx->s_cell.ensure(static_cast<size_t>(m) + 4));
@@ -3732,7 +3699,7 @@ int pcp_cloud_smooth_stream_next(pcp_context *ctx, int64_t *out_count) {
   if (kept != m && (rc = compact_results(ctx, ctx->s_cell.p, m, kept)) != PCP_OK) return rc;
   ctx->mls_count = kept;
   ctx->mls_result_live = true;
-  ctx->css_next = next_before + 1;
+  ctx->chain.next += 1;
   *out_count = kept;
   return PCP_OK;
 }
@@ -3741,29 +3708,29 @@ int pcp_cloud_smooth_stream_end(pcp_context *ctx) {
   if (!ctx) return PCP_ERR_INVALID;
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
   PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->css_next = -1;
-  ctx->css_chunks.clear();
+  ctx->chain.end();
+  ctx->chain.chunks.clear();
   ctx->css_dist.release();
   return PCP_OK;
 }
 
 int pcp_cloud_smooth_stream_seek(pcp_context *ctx, int32_t chunk) {
   if (!ctx) return PCP_ERR_INVALID;
-  if (ctx->css_next < 0 || ctx->css_blob.size() != sizeof(SmoothStream))
+  if (!ctx->chain.open())
     return set_error(ctx, PCP_ERR_STATE, "pcp_cloud_smooth_stream_seek: no stream (call pcp_cloud_smooth_stream_begin; an upload or "
                      "any other smoothing call ends a stream)");
-  const int64_t chunks = static_cast<int64_t>(ctx->css_chunks.size() / 5);
+  const int64_t chunks = static_cast<int64_t>(ctx->chain.chunks.size());
   if (chunk < 0 || chunk > chunks)
     return set_error(ctx, PCP_ERR_RANGE, "pcp_cloud_smooth_stream_seek: chunk %d outside 0..%lld", chunk, (long long)chunks);
-  ctx->css_next = chunk;  // (sweep 2 reads the stored distances: any chunk may be emitted again)
+  ctx->chain.next = chunk;  // (sweep 2 reads the stored distances: any chunk may be emitted again)
   return PCP_OK;
 }
 
 int pcp_cloud_smooth_stream_stats(pcp_context *ctx, double out[13]) {
   if (!ctx || !out) return PCP_ERR_INVALID;
-  if (ctx->css_blob.size() != sizeof(SmoothStream)) return set_error(ctx, PCP_ERR_STATE, "pcp_cloud_smooth_stream_stats: no stream");
-  SmoothStream st;
-  std::memcpy(&st, ctx->css_blob.data(), sizeof(st));
+  // (the numbers of the last stream built, open or ended)
+  if (ctx->chain.phase == StreamPhase::None) return set_error(ctx, PCP_ERR_STATE, "pcp_cloud_smooth_stream_stats: no stream");
+  const SmoothStream &st = ctx->chain.of;
   out[0] = st.halo;
   out[1] = st.redone;
   out[2] = st.threshold;
