@@ -77,7 +77,9 @@ extern "C" {
                                 called);
                                 entry points added, no layout changed: pcp_default_balance_params, pcp_set_image_balance,
                                 pcp_image_balance, pcp_image_balance_host, pcp_gamma_table_host (keyframe colour balance at upload;
-                                off by default) */
+                                off by default);
+                                entry points added, no layout changed: pcp_ortho_texture, pcp_ortho_texture_points_host
+                                (orthophotos; nothing runs unless called) */
 
 #define PCP_OK 0
 #define PCP_ERR_INVALID (-1) /* bad argument */
@@ -856,6 +858,49 @@ int pcp_ortho_host(const pcp_ortho_frame *frame, int64_t n, const float *xyz, co
  * rows, a gsd outside [1e-4, 1] or a non-finite result: PCP_ERR_INVALID; a size past the limits: PCP_ERR_RANGE, the gsd that
  * fits in the message (pcp_last_error(NULL)). */
 int pcp_ortho_fit_frame_host(int64_t n, const float *xyz, const uint8_t *has, const double *viewer, float gsd, pcp_ortho_frame *out);
+
+/* ---- orthophotos (no counterpart in the reference: scripts/genNormAndDistanceMask.py stops at per-keyframe pictures) ---- */
+/* The finished orthographic map, walked at a finer pitch and coloured straight from the keyframe images: behind every fine
+ * pixel a surface point (the map's depth, optionally interpolated), coloured by the rules the map points are coloured by --
+ * projection, z-buffer keep rule against the context's depth maps, score, top-5 ("Orthophotos", OT1-OT9).  The mask
+ * layer brings the keyframes' crack masks onto the metric raster at image resolution.  Opt-in: nothing runs unless called,
+ * PCP_ABI_VERSION is unchanged and a caller detects support by the symbols.  The kernel is timed under PCP_K_MISC.
+ *   state     a live, finished map (pcp_ortho_finish); camera and keyframes set and every keyframe's image uploaded;
+ *             PCP_CULL_ZBUFFER with the depth buffer on; every keyframe's depth map valid since the latest upload (the
+ *             precondition of pcp_depth_accum_merge; after pcp_depth_accum_apply the merged maps count).  Else PCP_ERR_STATE,
+ *             and the message names what is missing.  The call waits for pending image uploads and changes nothing it reads.
+ *   raster    scale k in 1..16 fine pixels per ortho pixel and axis; the rectangle x0, y0, w, h in ORTHO pixels inside the map
+ *             (w == 0 && h == 0 with x0 == y0 == 0: the whole map); views M in 1..5; max_step finite and > 0: else
+ *             PCP_ERR_INVALID.  More than 2^28 fine pixels: PCP_ERR_RANGE, the message names the largest k that fits the
+ *             rectangle.  More than 32 766 keyframes: PCP_ERR_RANGE.
+ *   point     fine pixel (X, Y) of the output is (Xg, Yg) = (x0 k + X, y0 k + Y) of the whole fine raster; its parent is ortho
+ *             pixel (Xg / k, Yg / k).  No source there: no surface.  Depth: the parent's, or with `interpolate` the bilinear
+ *             depth between the parent and its neighbours towards the fine pixel (fp32, every operation rounded), taken only
+ *             if every neighbour read lies inside the map, has a source and differs from the parent's depth by at most
+ *             max_step.  Position: o + ((s u + t v) + d n) with s = ((float)Xg + 0.5f) * (gsd / (float)k), t alike.
+ *   colour    keyframes ascending; a view is listed iff the point passes the keep rule and lies in the image; score as under
+ *             PCP_MATCH_IDENTITY; sorted by descending score, ties to the lower keyframe.  The colour is the fp32 score-weighted
+ *             mean of the first min(count, M) entries, truncated (M = 5: the reference's rule; M = 1: the sharpest).  With
+ *             pcp_set_frame_gains in force every listed view's channels pass through the gain first.
+ * Outputs, each a nullable host pointer, row-major (h k) x (w k): out_rgb 3 bytes (r, g, b); out_mask the mask byte of the best
+ * view's texel (0 where that keyframe has no mask); out_status 0 no surface / 1 textured / 2 surface that no view lists;
+ * out_view int16 keyframe of the best view (-1 when not textured); out_count min(listed views, 255); out_counts[0..3] = surface
+ * pixels, textured, unseen, and the (tile of 16 x 16 fine pixels, keyframe) pairs the tile test skipped.  Pixels that are not
+ * textured have rgb 0, mask 0, view -1.  Scratch: at most 8 B per fine pixel, freed on return. */
+typedef struct pcp_ortho_texture_params {
+  int32_t scale;        /* k: fine pixels per ortho pixel and axis, 1..16 */
+  int32_t x0, y0, w, h; /* rectangle in ORTHO pixels; w == 0 && h == 0: the whole raster */
+  int32_t views;        /* M: listed views that enter the colour, 1..5 (1 = sharpest, 5 = the reference's rule) */
+  int32_t interpolate;  /* 0: an ortho pixel's depth for its k*k fine pixels; 1: the bilinear depth */
+  float max_step;       /* interpolate only across depth differences <= max_step metres (> 0, finite) */
+} pcp_ortho_texture_params;
+int pcp_ortho_texture(pcp_context *ctx, const pcp_ortho_texture_params *params, uint8_t *out_rgb, uint8_t *out_mask,
+                      uint8_t *out_status, int16_t *out_view, uint8_t *out_count, int64_t out_counts[4]);
+/* Host only, no context, no GPU: the surface points alone ("raster" and "point" above) from a map's frame, source image and
+ * depth layer as pcp_ortho_fetch / pcp_ortho_host return them.  out_xyz 3 floats per fine pixel (0 where there is no surface),
+ * out_ok 1 where a surface exists; both nullable.  The message is at pcp_last_error(NULL). */
+int pcp_ortho_texture_points_host(const pcp_ortho_frame *frame, const pcp_ortho_texture_params *params, const int32_t *source,
+                                  const float *depth, float *out_xyz, uint8_t *out_ok);
 
 /* ---- keyframe colour balance (scripts/image_color_balance_autonomous.py, scripts/image_color_balance.py) */
 /* CLAHE on a lightness channel and a gamma table, applied on the device to every keyframe as it is uploaded instead of being

@@ -365,6 +365,46 @@ def ortho_fit_frame_host(xyz, gsd: float, has=None, viewer=None) -> OrthoFrame:
     return f
 
 
+class OrthoTextureParams(C.Structure):
+    """pcp_ortho_texture_params (DESIGN.md, "Orthophotos", OT2)."""
+    _fields_ = [("scale", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("views", C.c_int32),
+                ("interpolate", C.c_int32), ("max_step", C.c_float)]
+
+
+def ortho_texture_params(scale: int, views: int = 1, interpolate: bool = True, max_step: float = 0.05, rect=None) -> OrthoTextureParams:
+    """rect: (x0, y0, w, h) in ortho pixels, or None for the whole raster"""
+    x0, y0, w, h = (0, 0, 0, 0) if rect is None else (int(v) for v in rect)
+    return OrthoTextureParams(int(scale), x0, y0, w, h, int(views), 1 if interpolate else 0, float(max_step))
+
+
+def _ortho_texture_shape(frame: OrthoFrame, p: OrthoTextureParams) -> tuple[int, int]:
+    """(h k, w k) of the call's output; (0, 0) for parameters the library refuses (nothing to allocate)"""
+    w, h = (int(frame.width), int(frame.height)) if p.w == 0 and p.h == 0 else (int(p.w), int(p.h))
+    k = int(p.scale)
+    if not (1 <= k <= 16 and w >= 1 and h >= 1 and w * h * k * k <= (1 << 28)):
+        return 0, 0
+    return h * k, w * k
+
+
+def ortho_texture_points_host(frame, source, depth, scale: int, interpolate: bool = True, max_step: float = 0.05, rect=None) -> dict:
+    """The surface points behind the fine pixels of an orthophoto, computed on the CPU by the arithmetic the kernel uses
+    (pcp_ortho_texture_points_host: no context, no GPU; DESIGN.md "Orthophotos", OT2, OT3, OT9).  source / depth: the map's
+    (H, W) layers as ortho_fetch / ortho_host return them.  dict(xyz (h k, w k, 3) float32, ok (h k, w k) uint8)."""
+    L = load()
+    f = ortho_frame(frame)
+    p = ortho_texture_params(scale, 1, interpolate, max_step, rect)
+    source = np.ascontiguousarray(source, np.int32)
+    depth = np.ascontiguousarray(depth, np.float32)
+    if source.size != int(f.width) * int(f.height) or depth.size != source.size:
+        raise ValueError("ortho_texture_points_host: source and depth are the map's height x width layers")
+    fh, fw = _ortho_texture_shape(f, p)
+    out = dict(xyz=np.empty((fh, fw, 3), np.float32), ok=np.empty((fh, fw), np.uint8))
+    rc = L.pcp_ortho_texture_points_host(C.byref(f), C.byref(p), _ptr(source), _ptr(depth), _ptr(out["xyz"]), _ptr(out["ok"]))
+    if rc != PCP_OK:
+        raise PcpError(rc, L.pcp_last_error(None).decode())
+    return out
+
+
 def normals_moments_host(radius: float, xyz) -> np.ndarray:
     """The moments of pcp_estimate_normals computed on the CPU by brute force over the pairs, with the arithmetic the kernel
     uses (pcp_normals_moments_host: no context, no GPU; DESIGN.md "Geometry maps", GN2-GN4).  xyz (n, 3) float32, n <= 65536:
@@ -1220,6 +1260,21 @@ class Context:
     def ortho_end(self):
         self._check(self.lib.pcp_ortho_end(self.h))
         self._ortho_frame = None
+
+    def ortho_texture(self, scale: int, views: int = 1, interpolate: bool = True, max_step: float = 0.05, rect=None) -> dict:
+        """The orthophoto of the finished map at `scale` fine pixels per ortho pixel and axis, coloured straight from the
+        keyframe images (pcp_ortho_texture; DESIGN.md, "Orthophotos").  rect: (x0, y0, w, h) in ortho pixels, None: the whole
+        raster.  dict(rgb (h k, w k, 3), mask, status, view (int16), count, surface, textured, unseen, skipped_pairs)."""
+        p = ortho_texture_params(scale, views, interpolate, max_step, rect)
+        f = getattr(self, "_ortho_frame", None)
+        fh, fw = _ortho_texture_shape(f, p) if f is not None else (0, 0)
+        out = dict(rgb=np.empty((fh, fw, 3), np.uint8), mask=np.empty((fh, fw), np.uint8), status=np.empty((fh, fw), np.uint8),
+                   view=np.empty((fh, fw), np.int16), count=np.empty((fh, fw), np.uint8))
+        counts = np.zeros(4, np.int64)
+        self._check(self.lib.pcp_ortho_texture(self.h, C.byref(p), _ptr(out["rgb"]), _ptr(out["mask"]), _ptr(out["status"]),
+                                               _ptr(out["view"]), _ptr(out["count"]), _ptr(counts)))
+        out.update(surface=int(counts[0]), textured=int(counts[1]), unseen=int(counts[2]), skipped_pairs=int(counts[3]))
+        return out
 
     # -- geometry maps (DESIGN.md, "Geometry maps") ---------------------------------
     def estimate_normals(self, radius: float, want_moments: bool = False):

@@ -360,6 +360,15 @@ __device__ __forceinline__ float final_score(float xc, float yc, float zc, doubl
   return static_cast<float>(static_cast<double>(o + d) / 2.0);
 }
 
+// EG5: a channel under its view's gain -- fl32 product, fl32 sum with 0.5, truncation, clamp (no fusion: -ffp-contract=off);
+// the gained finalise (pcp_exposure.hip) and the orthophoto (pcp_ortho_texture.hip) pass every listed view's channels through it
+__device__ __forceinline__ uint32_t gained_channel(uint32_t c, float g) {
+  float v = static_cast<float>(c) * g;
+  v = v + 0.5f;
+  const int32_t i = static_cast<int32_t>(v);
+  return static_cast<uint32_t>(i < 255 ? i : 255);
+}
+
 // Per-point top-5 held in registers across the keyframe loop (A8).  Streaming
 // equivalent of "append all, std::sort descending, take 5" with ties -> lower
 // keyframe index (B8): keyframes arrive ascending, a new entry goes behind equals.

@@ -136,15 +136,7 @@ __global__ __launch_bounds__(kExBlock) void k_pair_stats(int64_t n, const uint32
   if (threadIdx.x == 3) atomicAdd(counters + 3, 1ull);
 }
 
-// EG5: a channel under its view's gain -- fl32 product, fl32 sum with 0.5, truncation, clamp (no fusion: -ffp-contract=off)
-__device__ __forceinline__ uint32_t gained_channel(uint32_t c, float g) {
-  float v = static_cast<float>(c) * g;
-  v = v + 0.5f;
-  const int32_t i = static_cast<int32_t>(v);
-  return static_cast<uint32_t>(i < 255 ? i : 255);
-}
-
-// Top5::finalise over the gained channels; the label form also writes the label word, from the raw state (Top5::labels)
+// Top5::finalise over the gained channels (gained_channel: pcp_device.hpp); the label form also writes the label word, from the raw state (Top5::labels)
 template <bool kLabel>
 __global__ __launch_bounds__(kExBlock) void k_finalise_gained(int64_t n, const float *__restrict__ score, const uint32_t *__restrict__ rgb,
                                                               const int32_t *__restrict__ frame, const int32_t *__restrict__ count,

@@ -712,6 +712,7 @@ hipError_t preload_voxel_reduce();
 hipError_t preload_normals();
 hipError_t preload_mask_edt();
 hipError_t preload_ortho();
+hipError_t preload_ortho_texture();
 // the device parts of pcp_mask_edt (one keyframe, with nearest) and pcp_frame_geometry under the caller's name: checks and
 // kernels, the results left in md_bits / md_d2 / md_nearest and gm_out / s_counter[0]; no copy, no synchronisation
 int mask_edt_device(pcp_context *ctx, const char *who, int32_t frame, int32_t threshold);

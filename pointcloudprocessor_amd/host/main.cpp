@@ -184,6 +184,18 @@
 //     scripts/genNormAndDistanceMask.py).  Made on the GPU (pcp_ortho_*; DESIGN.md "Orthographic maps"); works with
 //     --enableMLS 1 and with --enableMLS 1 --streamColour 1, where the chunks are added as they are coloured.  No other output
 //     changes.  --gpus N above 1 is refused (the shards' key images would merge by an all-reduce(MIN), which is not built).
+//   * --orthoTexture k (new, default 0 = off, 1..16), --orthoTextureViews m (new, default 1, 1..5), --orthoTextureInterp 0|1 (new,
+//     default 1) and --orthoTextureStep s (new, default 0.05, metres): with --orthoMap 1 the run also writes the orthophoto of
+//     that map, k fine pixels per map pixel and axis, coloured straight from the keyframe images instead of from one map point
+//     per pixel: <outputPath>ortho/ortho_photo_rgb.npy (|u1, (H k, W k, 3)), ortho_photo_mask.npy (|u1: the crack mask of the best
+//     view at image resolution, 0 without masks), ortho_photo_view.npy (<i2: the keyframe of the best view, -1 where nothing is
+//     textured), ortho_photo_status.npy (|u1: 0 no surface, 1 textured, 2 surface no keyframe sees) and ortho_photo.json (scale,
+//     views, interpolate, max_step, the fine gsd, width, height and the counts).  m = 1 takes the sharpest view, m = 5 the
+//     reference's weighted mean of five.  A raster of more than 2^28 fine pixels is textured in bands of map rows.  Made on the
+//     GPU (pcp_ortho_texture; DESIGN.md "Orthophotos"); works in the one-shot and in the --streamColour 1 form, where it runs
+//     after the last chunk on the merged depth maps.  The other ortho files are byte for byte what they are without the flag.
+//     Refused: without --orthoMap 1, with --gpus N above 1 and with --cull hpr / hpr_candidates (no depth maps to test a
+//     surface point against); the three value flags without --orthoTexture are errors.
 #include <cfloat>
 #include <chrono>
 #include <cmath>
@@ -289,6 +301,11 @@ struct Options {
   float ortho_gsd = 0.01f;            // --orthoGsd g: metres per pixel
   int ortho_fill = 0;                 // --orthoFill R: empty pixels take their nearest occupied pixel within R pixels
   std::vector<float> ortho_frame;     // --orthoFrame: empty = auto, else origin, u, v (9 numbers)
+  int ortho_texture = 0;              // --orthoTexture k: the orthophoto of that map, k fine pixels per pixel and axis (0: off)
+  int ortho_texture_views = 1;        // --orthoTextureViews m: listed views that enter a colour
+  bool ortho_texture_interp = true;   // --orthoTextureInterp: bilinear depth between map pixels
+  float ortho_texture_step = 0.05f;   // --orthoTextureStep s: ... only across depth steps up to s metres
+  bool ortho_texture_value_flag = false;  // one of the three value flags was given
 };
 
 static bool parse_bool(const std::string &v) {  // boost::program_options bool semantics
@@ -482,6 +499,29 @@ static Options parse(int argc, char **argv) {
           throw std::runtime_error("the argument ('" + v + "') for option '--orthoFrame' is invalid (auto, or ox,oy,oz,ux,uy,uz,vx,vy,vz)");
       }
     }
+    else if (a == "--orthoTexture" || a == "--orthoTextureViews") {
+      const std::string v = next();
+      const bool scale = a == "--orthoTexture";
+      char *end = nullptr;
+      const long k = std::strtol(v.c_str(), &end, 10);
+      if (end == v.c_str() || *end != '\0' || k < (scale ? 0 : 1) || k > (scale ? 16 : 5))
+        throw std::runtime_error("the argument ('" + v + "') for option '" + a + "' is invalid (" + (scale ? "0 = off, 1..16" : "1..5") + ")");
+      (scale ? o.ortho_texture : o.ortho_texture_views) = static_cast<int>(k);
+      if (!scale) o.ortho_texture_value_flag = true;
+    } else if (a == "--orthoTextureInterp") {
+      o.ortho_texture_interp = parse_bool(next());
+      o.ortho_texture_value_flag = true;
+    } else if (a == "--orthoTextureStep") {
+      const std::string v = next();
+      try {
+        o.ortho_texture_step = std::stof(v);
+      } catch (const std::exception &) {
+        o.ortho_texture_step = -1.0f;
+      }
+      if (!(o.ortho_texture_step > 0.0f && std::isfinite(o.ortho_texture_step)))
+        throw std::runtime_error("the argument ('" + v + "') for option '--orthoTextureStep' is invalid (metres, above 0)");
+      o.ortho_texture_value_flag = true;
+    }
     else if (a == "--crackLength") o.crack_length = parse_bool(next());
     else if (a == "--crackSkeleton") o.crack_skeleton = parse_bool(next());
     else if (a == "--crackSkeletonStep") o.crack_skeleton_step = std::stof(next());
@@ -542,6 +582,16 @@ static Options parse(int argc, char **argv) {
   if (o.output_leaf > 0.0f && o.gpus > 1)
     throw std::runtime_error("the option '--outputLeaf' does not work with '--gpus N' above 1 (the voxel sums of the index shards would "
                              "have to be added across GPUs: not built)");
+  if (o.ortho_texture_value_flag && !o.ortho_texture)
+    throw std::runtime_error("the options '--orthoTextureViews', '--orthoTextureInterp' and '--orthoTextureStep' need '--orthoTexture k' (k in 1..16)");
+  if (o.ortho_texture && !o.ortho_map)
+    throw std::runtime_error("the option '--orthoTexture' needs '--orthoMap 1' (the orthophoto is that map at a finer pitch)");
+  if (o.ortho_texture && o.gpus > 1)
+    throw std::runtime_error("the option '--orthoTexture' does not work with '--gpus N' above 1 (an index shard holds the depth maps "
+                             "and the map of its own points only)");
+  if (o.ortho_texture && o.cull_mode != PCP_CULL_ZBUFFER)
+    throw std::runtime_error("the option '--orthoTexture' does not work with '--cull hpr' or '--cull hpr_candidates' (a surface point is "
+                             "kept or dropped by the depth maps, which only '--cull zbuffer' makes)");
   if (o.ortho_map && o.gpus > 1)
     throw std::runtime_error("the option '--orthoMap 1' does not work with '--gpus N' above 1 (an index shard sees only its own "
                              "points; the shards' key images would merge by an all-reduce(MIN), which is not built)");
@@ -644,6 +694,10 @@ static void usage(std::ostream &os) {
         "  --orthoGsd arg (=0.01)                With --orthoMap: metres per pixel (1e-4..1)\n"
         "  --orthoFill arg (=0)                  With --orthoMap: fill empty pixels from the nearest occupied one within R pixels\n"
         "  --orthoFrame arg (=auto)              With --orthoMap: auto (fitted plane), or ox,oy,oz,ux,uy,uz,vx,vy,vz\n"
+        "  --orthoTexture arg (=0)               With --orthoMap: also the orthophoto, k fine pixels per pixel, from the keyframe images (1..16)\n"
+        "  --orthoTextureViews arg (=1)          With --orthoTexture: views that enter a colour (1 = sharpest, 5 = the reference's mean)\n"
+        "  --orthoTextureInterp arg (=1)         With --orthoTexture: bilinear depth between map pixels\n"
+        "  --orthoTextureStep arg (=0.05)        With --orthoTexture: ... across depth steps up to this many metres\n"
         "  --crackSkeletonStep arg (=0)          With --crackSkeleton: the band width in metres (0: twice the link radius)\n";
 }
 
@@ -1290,17 +1344,20 @@ class Processor {
   }
 
   // one array as a NumPy format 1.0 file: little-endian, C order, the header padded to a multiple of 64 bytes
-  static void writeNpy(const std::string &path, const char *descr, const std::vector<size_t> &shape, const void *data, size_t bytes) {
+  static void writeNpyHead(std::ofstream &f, const char *descr, const std::vector<size_t> &shape) {
     std::string dict = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': (";
     for (size_t k = 0; k < shape.size(); ++k) dict += std::to_string(shape[k]) + (shape.size() == 1 || k + 1 < shape.size() ? ", " : "");
     dict += "), }";
     while ((10 + dict.size() + 1) % 64 != 0) dict += ' ';
     dict += '\n';
-    std::ofstream f(path, std::ios::binary);
     const unsigned char head[10] = {0x93, 'N', 'U', 'M', 'P', 'Y', 1, 0, static_cast<unsigned char>(dict.size() & 0xff),
                                     static_cast<unsigned char>(dict.size() >> 8)};
     f.write(reinterpret_cast<const char *>(head), sizeof(head));
     f.write(dict.data(), static_cast<std::streamsize>(dict.size()));
+  }
+  static void writeNpy(const std::string &path, const char *descr, const std::vector<size_t> &shape, const void *data, size_t bytes) {
+    std::ofstream f(path, std::ios::binary);
+    writeNpyHead(f, descr, shape);
     f.write(static_cast<const char *>(data), static_cast<std::streamsize>(bytes));
     f.close();
     if (!f) throw std::runtime_error("Couldn't save geometry map to: " + path);
@@ -1541,7 +1598,14 @@ class Processor {
     {
       Phase ph("ortho_finish_gpu_s");
       m = dev.orthoFetch(opt.ortho_fill, opt.fuse_masks);
-      dev.orthoEnd();
+      if (!opt.ortho_texture) dev.orthoEnd();
+    }
+    if (opt.ortho_texture) {
+      struct End {  // also on the way out of an exception
+        Device &d;
+        ~End() { (void)pcp_ortho_end(d.get()); }
+      } end{dev};
+      writeOrthoPhoto(dev, m.frame);
     }
     Phase ph_w("ortho_write_s");
     const std::string stem = opt.outputPath + "ortho/";
@@ -1568,6 +1632,61 @@ class Processor {
     std::cout << "Orthographic map saved to: " << stem << "ortho_*.npy and ortho_frame.json, " << m.frame.width << " x " << m.frame.height
               << " pixels, " << m.occupied << " occupied, " << m.filled << " filled" << std::endl;
     if (opt.crack_fuse) ortho_index = std::move(m.index);
+  }
+
+  // --orthoTexture k: the orthophoto of the finished map on `dev`, as <out>ortho/ortho_photo_*.npy and ortho_photo.json.  One call
+  // of at most 2^28 fine pixels covers a band of whole map rows; the bands' rows are appended to the files in order.
+  void writeOrthoPhoto(Device &dev, const pcp_ortho_frame &frame) {
+    Phase ph("ortho_texture_s");
+    const std::string stem = opt.outputPath + "ortho/";
+    fs::create_directories(fs::path(stem));
+    const int64_t k = opt.ortho_texture, W = frame.width, H = frame.height;
+    const size_t fh = static_cast<size_t>(H * k), fw = static_cast<size_t>(W * k);
+    const int64_t band = std::min<int64_t>(H, (int64_t(1) << 28) / (W * k * k));  // (W <= 16384, k <= 16: at least 64 rows)
+    std::ofstream rgb(stem + "ortho_photo_rgb.npy", std::ios::binary), mask(stem + "ortho_photo_mask.npy", std::ios::binary),
+        view(stem + "ortho_photo_view.npy", std::ios::binary), status(stem + "ortho_photo_status.npy", std::ios::binary);
+    writeNpyHead(rgb, "|u1", {fh, fw, 3});
+    writeNpyHead(mask, "|u1", {fh, fw});
+    writeNpyHead(view, "<i2", {fh, fw});
+    writeNpyHead(status, "|u1", {fh, fw});
+    int64_t surface = 0, textured = 0, unseen = 0, skipped = 0, calls = 0;
+    for (int64_t y0 = 0; y0 < H; y0 += band, ++calls) {
+      pcp_ortho_texture_params p{};
+      p.scale = static_cast<int32_t>(k);
+      p.x0 = 0;
+      p.y0 = static_cast<int32_t>(y0);
+      p.w = static_cast<int32_t>(W);
+      p.h = static_cast<int32_t>(std::min(band, H - y0));
+      p.views = opt.ortho_texture_views;
+      p.interpolate = opt.ortho_texture_interp ? 1 : 0;
+      p.max_step = opt.ortho_texture_step;
+      const OrthoPhoto part = dev.orthoTexture(p);
+      rgb.write(reinterpret_cast<const char *>(part.rgb.data()), static_cast<std::streamsize>(part.rgb.size()));
+      mask.write(reinterpret_cast<const char *>(part.mask.data()), static_cast<std::streamsize>(part.mask.size()));
+      view.write(reinterpret_cast<const char *>(part.view.data()), static_cast<std::streamsize>(part.view.size() * 2));
+      status.write(reinterpret_cast<const char *>(part.status.data()), static_cast<std::streamsize>(part.status.size()));
+      surface += part.surface;
+      textured += part.textured;
+      unseen += part.unseen;
+      skipped += part.skipped_pairs;
+    }
+    rgb.close();
+    mask.close();
+    view.close();
+    status.close();
+    if (!rgb || !mask || !view || !status) throw std::runtime_error("Couldn't save the orthophoto to: " + stem);
+    std::ofstream f(stem + "ortho_photo.json");
+    char gsd[64], step[64];
+    std::snprintf(gsd, sizeof(gsd), "%.9g", static_cast<double>(frame.gsd / static_cast<float>(k)));
+    std::snprintf(step, sizeof(step), "%.9g", static_cast<double>(opt.ortho_texture_step));
+    f << "{\"scale\": " << k << ", \"views\": " << opt.ortho_texture_views << ", \"interpolate\": " << (opt.ortho_texture_interp ? 1 : 0)
+      << ", \"max_step\": " << step << ", \"gsd\": " << gsd << ", \"width\": " << fw << ", \"height\": " << fh << ", \"calls\": " << calls
+      << ", \"surface\": " << surface << ", \"textured\": " << textured << ", \"unseen\": " << unseen << ", \"skipped_pairs\": " << skipped
+      << "}\n";
+    f.close();
+    if (!f) throw std::runtime_error("Couldn't save the orthophoto's description.");
+    std::cout << "Orthophoto saved to: " << stem << "ortho_photo_*.npy and ortho_photo.json, " << fw << " x " << fh << " pixels, " << textured
+              << " textured, " << unseen << " unseen" << std::endl;
   }
 
   // --crackSkeleton 1: every crack's level-set diagram on the map: nodes, edges, ends, junctions, loops and skeleton length

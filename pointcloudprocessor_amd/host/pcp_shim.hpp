@@ -46,6 +46,17 @@ struct OrthoMap {
   std::vector<int32_t> source;   // linear index of the pixel the values come from, -1: empty
 };
 
+// An orthophoto (pcp_hip.h, "orthophotos"): layers of `width` x `height` fine pixels, row-major, of the rectangle the call asked for
+struct OrthoPhoto {
+  int32_t width = 0, height = 0;
+  int64_t surface = 0, textured = 0, unseen = 0, skipped_pairs = 0;
+  std::vector<uint8_t> rgb;     // 3 per fine pixel, from the keyframe images
+  std::vector<uint8_t> mask;    // the mask byte of the best view's texel
+  std::vector<uint8_t> status;  // 0 no surface, 1 textured, 2 surface that no view lists
+  std::vector<int16_t> view;    // keyframe of the best view, -1: not textured
+  std::vector<uint8_t> count;   // listed views, at most 255
+};
+
 // The geometry maps of one keyframe (pcp_hip.h, "geometry maps"): images of `width` x `height`, row-major
 struct GeometryMaps {
   int32_t width = 0, height = 0;
@@ -284,6 +295,32 @@ class Device {
     return s;
   }
   void orthoEnd() { check(pcp_ortho_end(ctx_)); }
+  // The orthophoto of the live, finished map (pcp_ortho_texture; DESIGN.md "Orthophotos"): p.scale fine pixels per ortho pixel
+  // and axis over the rectangle p names (w == 0 && h == 0: the whole raster), coloured straight from the keyframe images under
+  // the depth maps the context holds.  (Sized by the frame of the last orthoBegin that succeeded on this Device; parameters the
+  // library refuses get no layers and its refusal.)
+  OrthoPhoto orthoTexture(const pcp_ortho_texture_params &p) {
+    OrthoPhoto ph;
+    const int64_t w = (p.w == 0 && p.h == 0) ? ortho_frame_.width : p.w, h = (p.w == 0 && p.h == 0) ? ortho_frame_.height : p.h;
+    const int64_t k = p.scale;
+    if (k >= 1 && k <= 16 && w >= 1 && h >= 1 && w * h * k * k <= (int64_t(1) << 28)) {
+      ph.width = static_cast<int32_t>(w * k);
+      ph.height = static_cast<int32_t>(h * k);
+    }
+    const size_t px = static_cast<size_t>(ph.width) * static_cast<size_t>(ph.height);
+    ph.rgb.resize(3 * px);
+    ph.mask.resize(px);
+    ph.status.resize(px);
+    ph.view.resize(px);
+    ph.count.resize(px);
+    int64_t counts[4] = {0, 0, 0, 0};
+    check(pcp_ortho_texture(ctx_, &p, ph.rgb.data(), ph.mask.data(), ph.status.data(), ph.view.data(), ph.count.data(), counts));
+    ph.surface = counts[0];
+    ph.textured = counts[1];
+    ph.unseen = counts[2];
+    ph.skipped_pairs = counts[3];
+    return ph;
+  }
   // the frame that looks straight at n rows (xyz interleaved; has nullable) from the side of `viewer` (3 doubles, nullable)
   static pcp_ortho_frame orthoFitFrame(int64_t n, const float *xyz, const uint8_t *has, const double *viewer, float gsd) {
     pcp_ortho_frame f{};
@@ -520,14 +557,18 @@ class Colorizer {
   }
   // One orthographic picture of the colour result colorize() / finalise() left on the device (DESIGN.md "Orthographic maps"):
   // begin, one add under the input indices, finish with the fill radius, fetch, end.  with_label: after a run with label fusion.
-  OrthoMap orthoMap(const pcp_ortho_frame &frame, int32_t fill_radius_px = 0, bool with_label = false) const {
+  // texture / photo (both or neither): the orthophoto of the finished map under these parameters, before the map ends.
+  OrthoMap orthoMap(const pcp_ortho_frame &frame, int32_t fill_radius_px = 0, bool with_label = false,
+                    const pcp_ortho_texture_params *texture = nullptr, OrthoPhoto *photo = nullptr) const {
     dev_.orthoBegin(frame);
     struct End {  // also on the way out of an exception
       Device &d;
       ~End() { (void)pcp_ortho_end(d.get()); }
     } end{dev_};
     (void)dev_.orthoAdd(0);
-    return dev_.orthoFetch(fill_radius_px, with_label);
+    OrthoMap m = dev_.orthoFetch(fill_radius_px, with_label);
+    if (texture && photo) *photo = dev_.orthoTexture(*texture);
+    return m;
   }
   // the same result left on the device (for pcp_colour_smooth_local, pcp_colour_compact, pcp_voxel_reduce_add): nothing is fetched
   void finaliseOnDevice() const {

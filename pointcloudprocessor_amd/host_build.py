@@ -20,6 +20,7 @@ TARGETS = {
     "voxel_reduce_selftest": ["voxel_reduce_selftest.cpp"],  # csrc/pcp_voxel_reduce.hpp compiled for the host (CPU only)
     "normals_selftest": ["normals_selftest.cpp"],  # csrc/pcp_normals.hpp compiled for the host (CPU only)
     "ortho_selftest": ["ortho_selftest.cpp"],  # csrc/pcp_ortho.hpp compiled for the host (CPU only)
+    "ortho_texture_selftest": ["ortho_texture_selftest.cpp"],  # csrc/pcp_ortho_texture.hpp compiled for the host (CPU only)
     "crack_width_selftest": ["crack_width_selftest.cpp"],  # csrc/pcp_crack_width.hpp compiled for the host (CPU only)
     "crack_fuse_selftest": ["crack_fuse_selftest.cpp"],  # csrc/pcp_crack_fuse.hpp compiled for the host (CPU only)
     "crack_length_selftest": ["crack_length_selftest.cpp"],  # csrc/pcp_crack_length.hpp compiled for the host (CPU only)
@@ -34,7 +35,7 @@ def build(force: bool = False) -> dict:
     for name, srcs in TARGETS.items():
         exe = os.path.join(BIN, name)
         deps = [os.path.join(HOST, s) for s in srcs] + [os.path.join(HOST, "pcp_shim.hpp"), os.path.join(HOST, "pcp_multi.hpp"), os.path.join(HOST, "pcd_io.hpp"), os.path.join(HOST, "image_io.hpp"), os.path.join(HOST, "pcd_device_reader.hpp"),
-                                                       os.path.join(_build.CSRC, "pcp_ascii_parse.hpp"), os.path.join(_build.CSRC, "pcp_ascii.hpp"), os.path.join(_build.CSRC, "pcp_visit_forms.hpp"), os.path.join(_build.CSRC, "pcp_voxel_reduce.hpp"), os.path.join(_build.CSRC, "pcp_normals.hpp"), os.path.join(_build.CSRC, "pcp_ortho.hpp"), os.path.join(_build.CSRC, "pcp_crack_width.hpp"), os.path.join(_build.CSRC, "pcp_crack_fuse.hpp"), os.path.join(_build.CSRC, "pcp_crack_length.hpp"), os.path.join(_build.CSRC, "pcp_crack_skeleton.hpp"), os.path.join(_build.CSRC, "pcp_image_balance.hpp"), os.path.join(_build.CSRC, "pcp_hsv.hpp"),
+                                                       os.path.join(_build.CSRC, "pcp_ascii_parse.hpp"), os.path.join(_build.CSRC, "pcp_ascii.hpp"), os.path.join(_build.CSRC, "pcp_visit_forms.hpp"), os.path.join(_build.CSRC, "pcp_voxel_reduce.hpp"), os.path.join(_build.CSRC, "pcp_normals.hpp"), os.path.join(_build.CSRC, "pcp_ortho.hpp"), os.path.join(_build.CSRC, "pcp_ortho_texture.hpp"), os.path.join(_build.CSRC, "pcp_crack_width.hpp"), os.path.join(_build.CSRC, "pcp_crack_fuse.hpp"), os.path.join(_build.CSRC, "pcp_crack_length.hpp"), os.path.join(_build.CSRC, "pcp_crack_skeleton.hpp"), os.path.join(_build.CSRC, "pcp_image_balance.hpp"), os.path.join(_build.CSRC, "pcp_hsv.hpp"),
                                                        os.path.join(_build.INCLUDE, "pcp_hip.h")]
         deps = [d for d in deps if os.path.exists(d)]
         stale = force or not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps)

@@ -177,7 +177,7 @@ class PointCloudColorizer:
             ctx.voxel_reduce_end()
 
     def ortho_map(self, frame="auto", gsd: float = 0.01, fill_radius: int = 0, crack_map: dict | None = None, xyz=None,
-                  viewer=None) -> dict:
+                  viewer=None, texture: dict | None = None) -> dict:
         """One orthographic picture of the colour result run() left on the device ("Orthographic maps"): dict(index
         (H, W) uint32 with 0xFFFFFFFF for an empty pixel, depth (H, W), rgb (H, W, 3), status (H, W) 0 empty / 1 direct /
         2 filled, source (H, W), frame (the dict that takes a pixel back to world coordinates), occupied, filled,
@@ -191,6 +191,10 @@ class PointCloudColorizer:
         crack_map: the dict crack_map() returned (None: the one its last call on this object left, when it is of this
         cloud's size): the result gains width (H, W) float32 and crack (H, W) int32, gathered on the host as width_mean[index]
         and label[index], 0 and -1 on empty pixels.
+        texture: dict(scale[, views, interpolate, max_step]) -- the result gains photo, the orthophoto of the finished map at
+        `scale` fine pixels per pixel and axis, coloured straight from the keyframe images ("Orthophotos"): dict(rgb
+        (H scale, W scale, 3), mask, status, view, count, surface, textured, unseen, skipped_pairs).  It runs after the
+        finish and the fetch, before the map ends, on the depth maps run() left.
 
         An index shard sees only its own points, so world > 1 raises ValueError.  (The shards' key images would merge by an
         all-reduce(MIN); not built.)"""
@@ -198,6 +202,7 @@ class PointCloudColorizer:
             raise ValueError("ortho_map: an index shard sees only its own points; the per-pixel keys of the shards would "
                              "have to be merged across ranks (all-reduce MIN), which is not built: run it on one rank "
                              "holding the whole map")
+        texture = ortho_texture_request("ortho_map", texture)
         ctx = self.engine.ctx
         if isinstance(frame, str):
             if frame != "auto":
@@ -211,6 +216,8 @@ class PointCloudColorizer:
             contributors = ctx.ortho_add(0)
             occupied, filled = ctx.ortho_finish(fill_radius)
             out = ctx.ortho_fetch(want_label=fuse_labels)
+            if texture is not None:
+                out["photo"] = ctx.ortho_texture(**texture)
         finally:
             ctx.ortho_end()
         out.update(frame=capi.ortho_frame(frame).as_dict(), contributors=contributors, occupied=occupied, filled=filled)
@@ -425,6 +432,17 @@ def _rows_xyz(who: str, xyz, n: int | None = None):
     if n is not None and len(xyz) != n:
         raise ValueError(f"{who}: xyz has {len(xyz)} rows, the uploaded cloud {n}")
     return xyz
+
+
+def ortho_texture_request(who: str, texture: dict | None) -> dict | None:
+    """the keyword arguments of capi.Context.ortho_texture from a texture=dict(scale[, views, interpolate, max_step])"""
+    if texture is None:
+        return None
+    unknown = set(texture) - {"scale", "views", "interpolate", "max_step"}
+    if unknown or "scale" not in texture:
+        raise ValueError(f"{who}: texture is dict(scale[, views, interpolate, max_step]), got {sorted(texture)}")
+    return dict(scale=int(texture["scale"]), views=int(texture.get("views", 1)), interpolate=bool(texture.get("interpolate", True)),
+                max_step=float(texture.get("max_step", 0.05)))
 
 
 def ortho_crack_layers(index, map_width, map_crack) -> dict:
@@ -753,7 +771,7 @@ class CloudSmooth:
         `self.streamed_colour` gains voxel_add_s, voxel_finish_s and the accumulator's stats.  With download=False these rows
         are all that leaves the device.
 
-        ortho: dict(frame, gsd, fill_radius[, xyz, viewer]) -- one orthographic map of all the coloured rows (DESIGN.md,
+        ortho: dict(frame, gsd, fill_radius[, xyz, viewer, texture]) -- one orthographic map of all the coloured rows (DESIGN.md,
         "Orthographic maps"): the frame is resolved and the map begun on `colour_engine` before any other work (a bad frame or
         a gsd too fine for the extent is refused at once), every chunk is added after it is coloured under index_base = the
         rows of the chunks before it (the row's place in the concatenated smoothed cloud), the map is finished and fetched
@@ -761,8 +779,11 @@ class CloudSmooth:
         ortho_add_s and ortho_finish_s.  frame "auto" (the default): fitted on the host to `xyz`, the raw map the caller
         uploaded to this engine ((n, 3) or (x, y, z)) -- the same surface up to the chain's dilation -- seen from the side
         of `viewer` (3 numbers, e.g. the mean keyframe position).  Works with download=False: the map is then, with the voxel
-        rows, all that leaves."""
+        rows, all that leaves.  texture: dict(scale[, views, interpolate, max_step]) -- `self.ortho_output` gains photo, the
+        orthophoto of the finished map ("Orthophotos"), textured after the last chunk on the merged depth maps
+        (None when no chunk held a row)."""
         ctx, col = self.engine.ctx, colour_engine.ctx
+        ortho_texture_request("ortho", None if ortho is None else ortho.get("texture"))  # (a bad request is refused before any work)
         if ortho is not None:
             frame = ortho.get("frame", "auto")
             if isinstance(frame, str):
@@ -852,6 +873,11 @@ class CloudSmooth:
                 occupied, filled = col.ortho_finish(int(ortho.get("fill_radius", 0)))
                 self.ortho_output = col.ortho_fetch(want_label=fuse_labels)
                 stats["ortho_finish_s"] = time.perf_counter() - t1
+                texture = ortho_texture_request("ortho", ortho.get("texture"))
+                if texture is not None:  # (the colour engine holds the last chunk's cloud under the merged maps)
+                    t1 = time.perf_counter()
+                    self.ortho_output["photo"] = col.ortho_texture(**texture) if rows_before else None
+                    stats["ortho_texture_s"] = time.perf_counter() - t1
                 stats["ortho"] = col.ortho_stats()
                 self.ortho_output.update(frame=capi.ortho_frame(frame).as_dict(), occupied=occupied, filled=filled,
                                          contributors=stats["ortho"]["contributors"])
