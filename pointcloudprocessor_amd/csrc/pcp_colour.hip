@@ -397,62 +397,82 @@ __global__ __launch_bounds__(kBlock) void k_depth_pass(const float *__restrict__
     if (held_at && held_bits < held_seen) atomicMin(held_at, held_bits);
     held_at = nullptr;
   };
-  for (int32_t w = f0 >> 5; w <= (f1 - 1) >> 5; ++w) {
-    const uint32_t in_range = range_bits(w, f0, f1);
-    // the tile's mask word, kept for the store below: this wavefront is the only writer of its tile's words during the pass
-    const uint32_t word = tile_mask ? __builtin_amdgcn_readfirstlane(tile_mask[tile * words + w]) : 0xffffffffu;
-    uint32_t todo = in_range & word;
+  // The tile's mask words of the range are loaded once, lane l holding word wbase + l (chunks of 64 words: 2048 keyframes), and
+  // only the words with a keyframe to visit are walked: a load per word was a memory round trip per 32 keyframes in front of
+  // every word's visits -- 8 in a row per tile at 256 keyframes -- while the keyframes that see a tile sit in one or two words.
+  const int32_t w_last = (f1 - 1) >> 5;
+  for (int32_t wbase = f0 >> 5; wbase <= w_last; wbase += 64) {
+    const int32_t my_w = wbase + lane;
+    const bool have_w = my_w <= w_last;
+    // kept for the store below: this wavefront is the only writer of its tile's words during the pass
+    uint32_t my_word = 0xffffffffu;
+    if (tile_mask && have_w) my_word = tile_mask[tile * words + my_w];
     // pairs whose tile images inside the acceptance box: the fp32 rejection test is skipped (it could not reject)
-    const uint32_t inside = tile_inside ? __builtin_amdgcn_readfirstlane(tile_inside[tile * words + w]) : 0u;
-    uint32_t seen = 0u;  // keyframes in which some lane can be coloured
-    while (todo) {
-      const int32_t b = __builtin_ctz(todo);
-      const int32_t f = (w << 5) + b;
-      todo &= todo - 1u;
-      const DevFrame &fr = frames[f];
-      const auto p = project_visit<true, kCommon>(cam, fr.w2c, px, py, pz, ((inside >> b) & 1u) == 0u, finite_sure);
-      bool in_map, cand;
-      if constexpr (kCommon) {  // the predicates themselves
-        in_map = live && p.map_ok;
-        cand = in_map && p.image_ok;
-      } else {  // project_point's sentinels
-        in_map = live && p.cell >= 0;
-        cand = live && p.pixel >= 0 && (cam.enable_zbuf ? p.cell >= 0 : p.cell != -1);
-      }
-      // (the builtin on the predicate itself: __ballot's int argument takes a lane mask through a register and a compare)
-      if (__builtin_amdgcn_ballot_w64(cand)) seen |= 1u << b;
-      settle_held();
-      if (cam.enable_zbuf && __builtin_amdgcn_ballot_w64(in_map)) {
-        // wave-level combine: lanes of a tile hit a handful of cells, one atomic per cell suffices.  (Reading the
-        // cell's current value first and skipping the square root, the combine and the atomic for points that cannot
-        // lower it -- s >= m * m -- was slower, 0.79 -> 0.82 ms: some lane of the wavefront nearly always stays, so the
-        // wavefront pays for the whole path anyway, plus the extra gather.)
-        unsigned long long *map = depth + static_cast<uint64_t>(static_cast<uint32_t>(f - depth_first_frame)) * static_cast<uint32_t>(cells);
-        // the table elects by the upper half of s's bit pattern (monotone in s): lanes of a cell that tie there (ranges
-        // within 1e-6 of each other) all go to the map, which settles them in full precision
-        unsigned long long key = ~0ull, sbits = 0ull;
-        if (in_map) {
-          sbits = static_cast<unsigned long long>(__double_as_longlong(sumsq64(p.xc, p.yc, p.zc)));
-          key = (static_cast<unsigned long long>(static_cast<uint32_t>(p.cell)) << 32) | (sbits >> 32);
+    uint32_t my_inside = 0u;
+    if (tile_inside && have_w) my_inside = tile_inside[tile * words + my_w];
+    const uint32_t my_range = have_w ? range_bits(my_w, f0, f1) : 0u;
+    const bool walked = (my_word & my_range) != 0u;  // this lane's word has a keyframe to visit
+    for (unsigned long long walk = __builtin_amdgcn_ballot_w64(walked); walk; walk &= walk - 1ull) {
+      const int32_t wl = __builtin_ctzll(walk);
+      const int32_t w = wbase + wl;
+      const uint32_t in_range = range_bits(w, f0, f1);
+      const uint32_t word = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int32_t>(my_word), wl));
+      uint32_t todo = in_range & word;
+      const uint32_t inside = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int32_t>(my_inside), wl));
+      uint32_t seen = 0u;  // keyframes in which some lane can be coloured
+      while (todo) {
+        const int32_t b = __builtin_ctz(todo);
+        const int32_t f = (w << 5) + b;
+        todo &= todo - 1u;
+        const DevFrame &fr = frames[f];
+        const auto p = project_visit<true, kCommon>(cam, fr.w2c, px, py, pz, ((inside >> b) & 1u) == 0u, finite_sure);
+        bool in_map, cand;
+        if constexpr (kCommon) {  // the predicates themselves
+          in_map = live && p.map_ok;
+          cand = in_map && p.image_ok;
+        } else {  // project_point's sentinels
+          in_map = live && p.cell >= 0;
+          cand = live && p.pixel >= 0 && (cam.enable_zbuf ? p.cell >= 0 : p.cell != -1);
         }
-        tbl[lane] = ~0ull;
-        __builtin_amdgcn_wave_barrier();
-        if (in_map) atomicMin(&tbl[p.cell & 63], key);
-        __builtin_amdgcn_wave_barrier();
-        if (in_map) {
-          const unsigned long long got = tbl[p.cell & 63];
-          // winner of its cell, or a cell that lost its slot to a smaller cell id
-          if (got == key || static_cast<uint32_t>(got >> 32) != static_cast<uint32_t>(p.cell)) {
-            held_at = map + p.cell;
-            held_bits = sbits;
-            held_seen = *held_at;  // (possibly stale, hence >= the cell's value: the read filters most atomics)
+        // (the builtin on the predicate itself: __ballot's int argument takes a lane mask through a register and a compare)
+        if (__builtin_amdgcn_ballot_w64(cand)) seen |= 1u << b;
+        settle_held();
+        if (cam.enable_zbuf && __builtin_amdgcn_ballot_w64(in_map)) {
+          // wave-level combine: lanes of a tile hit a handful of cells, one atomic per cell suffices.  (Reading the
+          // cell's current value first and skipping the square root, the combine and the atomic for points that cannot
+          // lower it -- s >= m * m -- was slower, 0.79 -> 0.82 ms: some lane of the wavefront nearly always stays, so the
+          // wavefront pays for the whole path anyway, plus the extra gather.)
+          unsigned long long *map = depth + static_cast<uint64_t>(static_cast<uint32_t>(f - depth_first_frame)) * static_cast<uint32_t>(cells);
+          // the table elects by the upper half of s's bit pattern (monotone in s): lanes of a cell that tie there (ranges
+          // within 1e-6 of each other) all go to the map, which settles them in full precision
+          unsigned long long key = ~0ull, sbits = 0ull;
+          if (in_map) {
+            sbits = static_cast<unsigned long long>(__double_as_longlong(sumsq64(p.xc, p.yc, p.zc)));
+            key = (static_cast<unsigned long long>(static_cast<uint32_t>(p.cell)) << 32) | (sbits >> 32);
           }
+          tbl[lane] = ~0ull;
+          __builtin_amdgcn_wave_barrier();
+          if (in_map) atomicMin(&tbl[p.cell & 63], key);
+          __builtin_amdgcn_wave_barrier();
+          if (in_map) {
+            const unsigned long long got = tbl[p.cell & 63];
+            // winner of its cell, or a cell that lost its slot to a smaller cell id
+            if (got == key || static_cast<uint32_t>(got >> 32) != static_cast<uint32_t>(p.cell)) {
+              held_at = map + p.cell;
+              held_bits = sbits;
+              held_seen = *held_at;  // (possibly stale, hence >= the cell's value: the read filters most atomics)
+            }
+          }
+          __builtin_amdgcn_wave_barrier();
         }
-        __builtin_amdgcn_wave_barrier();
       }
+      // drop the pairs in which no lane is a colouring candidate: the colour pass skips them
+      // (into the owning lane: a compare and a select per walked word; ROCm 7's clang has no writelane builtin)
+      if (lane == wl) my_word = (word & ~in_range) | seen;
     }
-    // drop the pairs in which no lane is a colouring candidate: the colour pass skips them
-    if (tile_mask && lane == 0 && live) tile_mask[tile * words + w] = (word & ~in_range) | seen;
+    // one store per chunk, by the lanes whose word was walked (a word that was not walked holds no keyframe of the range
+    // to drop: it is unchanged).  The words belong to the tile, not to the lanes' points: a lane past the cloud stores its word too.
+    if (tile_mask && walked) tile_mask[tile * words + my_w] = my_word;
   }
   settle_held();
 }
@@ -626,6 +646,67 @@ __global__ __launch_bounds__(kBlock) void k_colour_pass(const float *__restrict_
       if (bad) lab.word[n] = 1u;
     }
   }
+}
+
+// k_colour_pass<true, 2, true, false> -- the whole-run call of the bench and the CLI: common configuration, round-trip match, one
+// shot, no labels -- for a range of at most 64 mask words (2048 keyframes), with the depth pass's walk of the tile's words: one
+// load of them (lane l holds word (f0 >> 5) + l, masked to the range), a ballot, and only the words that keep a keyframe are walked.
+// The word loop of k_colour_pass waits for a (scalar) load per word whether the word keeps anything or not: colour pass 0.698 ->
+// 0.690 ms at C3 (profiles/mask_preload_probe.md).  106 SGPRs with 4 spilled, 61 VGPRs, no scratch, 7 waves; that form: 106 with
+// 7 spilled, 61, none, 7.  A kernel of its own and the visit written out a second time: the registers of every k_colour_pass form
+// are pinned by tests/test_label_fusion_cpu.py, and neither a further template parameter nor a shared helper is certain to leave
+// them as they are.  The visit, Top5 and the result store are those of that form to the letter -- change both or neither.
+__global__ __launch_bounds__(kBlock) void k_colour_pass_preload(const float *__restrict__ x, const float *__restrict__ y,
+                                                                const float *__restrict__ z, int64_t n, DevCamera cam_in,
+                                                                const DevFrame *__restrict__ frames, int32_t f0, int32_t f1,
+                                                                const uint32_t *__restrict__ depth, int64_t cells,
+                                                                const uint32_t *__restrict__ tile_mask, int32_t words,
+                                                                const uint32_t *__restrict__ images, int64_t image_px,
+                                                                const int32_t *__restrict__ perm, uint32_t *__restrict__ rgba) {
+  DevCamera cam = common_camera<true>(cam_in);
+  cam.match_mode = PCP_MATCH_ROUNDTRIP;
+  const int lane = threadIdx.x & 63;
+  const int64_t j = static_cast<int64_t>(xcd_chunked_block()) * kBlock + threadIdx.x;
+  const bool live = j < n;
+  // a wavefront wholly past the cloud (tail of a 256-thread workgroup) has no tile: its mask words do not exist
+  if (!__ballot(live)) return;
+  const float px = live ? x[j] : 0.0f, py = live ? y[j] : 0.0f, pz = live ? z[j] : 0.0f;
+  const int64_t tile = __builtin_amdgcn_readfirstlane(static_cast<int32_t>(j >> 6));
+  // every camera coordinate of this wavefront is finite (divide_xy_by_z)
+  const bool finite_sure = cam.frames_bounded != 0 && __all(fabsf(px) <= 0x1p40f && fabsf(py) <= 0x1p40f && fabsf(pz) <= 0x1p40f);
+  Top5 t;
+  t.init();
+  const int32_t wbase = f0 >> 5, my_w = wbase + lane;  // the host launches this kernel for ((f1 - 1) >> 5) - wbase < 64 only
+  uint32_t my_todo = 0u;
+  if (my_w <= (f1 - 1) >> 5) my_todo = range_bits(my_w, f0, f1) & tile_mask[tile * words + my_w];
+  for (unsigned long long walk = __builtin_amdgcn_ballot_w64(my_todo != 0u); walk; walk &= walk - 1ull) {
+    const int32_t wl = __builtin_ctzll(walk);
+    const int32_t w = wbase + wl;
+    uint32_t todo = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int32_t>(my_todo), wl));
+    while (todo) {
+      const int32_t f = (w << 5) + __builtin_ctz(todo);
+      todo &= todo - 1u;
+      const DevFrame &fr = frames[f];
+      // the refined masks only keep pairs with a candidate lane: the fp32 rejection test cannot skip the wavefront
+      const auto p = project_visit<false, true>(cam, fr.w2c, px, py, pz, true, finite_sure);
+      const bool cand = live && p.image_ok && p.map_ok;
+      if (cand) {
+        const uint32_t dbits = cam.enable_zbuf ? depth[static_cast<uint64_t>(static_cast<uint32_t>(f)) * static_cast<uint32_t>(cells) + static_cast<uint32_t>(p.cell)] : 0u;
+        // A4 keep rule (view_culling.cpp:135-171)
+        bool keep = true;
+        if (cam.enable_zbuf) keep = keep_by_depth(p.xc, p.yc, p.zc, static_cast<double>(__uint_as_float(dbits)) + cam.slack);
+        float sx = p.xc, sy = p.yc, sz = p.zc;
+        if (cam.match_mode == PCP_MATCH_ROUNDTRIP && keep) keep = roundtrip_sample(cam, fr, px, py, pz, sx, sy, sz);
+        // only samples that pass the keep rule fetch their texel (see k_colour_pass)
+        if (keep) {
+          const uint32_t texel = images[static_cast<uint64_t>(static_cast<uint32_t>(f)) * static_cast<uint32_t>(image_px) + static_cast<uint32_t>(p.pixel)];
+          t.insert(final_score<true>(sx, sy, sz, fr.px, fr.py, fr.pz), texel & 0xffffffu, f);
+        }
+      }
+    }
+  }
+  if (!live) return;
+  rgba[perm[j]] = t.finalise();  // scattered straight into input order, see k_colour_pass
 }
 
 // finalise from stored state (multi-batch runs)
@@ -2081,10 +2162,20 @@ static int colour_pass_impl(pcp_context *ctx, int32_t frame_begin, int32_t frame
     const LabelOut lab{label ? ctx->labels.p : nullptr};
     auto kernel = label ? colour_pass_kernel<true>(common, ctx->dcam.match_mode, flags)
                         : colour_pass_kernel<false>(common, ctx->dcam.match_mode, flags);
-    hipLaunchKernelGGL(kernel, dim3(blocks_for(ctx->n)), dim3(kBlock), 0, ctx->stream, ctx->sxyz.p, ctx->sxyz.p + plane,
-                       ctx->sxyz.p + 2 * plane, ctx->n, ctx->dcam, ctx->frames.p, frame_begin, frame_end, ctx->depth.p,
-                       cells_of(ctx), ctx->tile_mask.p, ctx->mask_words, ctx->images.p,
-                       static_cast<int64_t>(ctx->dcam.img_w) * ctx->dcam.img_h, st, ctx->perm.p, result, flags, hull, mb, lab);
+    // the whole-run call of the default configuration over at most 64 mask words: the form that loads a tile's words once;
+    // wider ranges (more than 2048 keyframes) keep k_colour_pass<true, 2, true, false>
+    if (common && ctx->dcam.match_mode == PCP_MATCH_ROUNDTRIP && flags == 4 && !label && ctx->tile_mask.p &&
+        ((frame_end - 1) >> 5) - (frame_begin >> 5) < 64) {
+      hipLaunchKernelGGL(k_colour_pass_preload, dim3(blocks_for(ctx->n)), dim3(kBlock), 0, ctx->stream, ctx->sxyz.p,
+                         ctx->sxyz.p + plane, ctx->sxyz.p + 2 * plane, ctx->n, ctx->dcam, ctx->frames.p, frame_begin, frame_end,
+                         ctx->depth.p, cells_of(ctx), ctx->tile_mask.p, ctx->mask_words, ctx->images.p,
+                         static_cast<int64_t>(ctx->dcam.img_w) * ctx->dcam.img_h, ctx->perm.p, result);
+    } else {
+      hipLaunchKernelGGL(kernel, dim3(blocks_for(ctx->n)), dim3(kBlock), 0, ctx->stream, ctx->sxyz.p, ctx->sxyz.p + plane,
+                         ctx->sxyz.p + 2 * plane, ctx->n, ctx->dcam, ctx->frames.p, frame_begin, frame_end, ctx->depth.p,
+                         cells_of(ctx), ctx->tile_mask.p, ctx->mask_words, ctx->images.p,
+                         static_cast<int64_t>(ctx->dcam.img_w) * ctx->dcam.img_h, st, ctx->perm.p, result, flags, hull, mb, lab);
+    }
     PCP_HIP_TRY(ctx, hipGetLastError());
     if (radius && ctx->match_a > 0) {
       hipLaunchKernelGGL(label ? k_match_fixup<true> : k_match_fixup<false>, dim3(blocks_for(ctx->match_a)), dim3(kBlock), 0, ctx->stream, ctx->sxyz.p,
