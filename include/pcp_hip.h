@@ -1235,6 +1235,13 @@ int pcp_selftest_arithmetic(pcp_context *ctx, int64_t samples, uint64_t seed, in
  * p1, p2 let the short distortion run (0: the kernels keep the written form, and the first count compares it with itself). */
 int pcp_selftest_visit_forms(pcp_context *ctx, int64_t samples, uint64_t seed, int64_t *mismatches_uv, int64_t *mismatches_cell,
                              int64_t *mismatches_sqrt, int32_t *short_distortion);
+/* diagnostic: under a camera whose k3 is a zero and whose other constants are in a proven range (csrc/pcp_visit_forms.hpp,
+ * k3_term_droppable), the batched passes of the default configuration leave the k3 term out of the distortion polynomial.  This runs
+ * the written projection and the form those passes run under the configured camera on the device, on `samples` pseudo-random
+ * float triples (all exponents, z > 0) and on a grid of extreme ones (depths down to 2^-149 under ordinary, huge and non-finite
+ * x, y), and counts the triples whose verdicts of the two truncation rules, cell, pixel or -- where a rule accepts -- (u, v)
+ * differ.  The count must be 0.  term_dropped: 1 when the configured camera lets the term go (0: the passes keep it). */
+int pcp_selftest_k3_term(pcp_context *ctx, int64_t samples, uint64_t seed, int64_t *mismatches, int32_t *term_dropped);
 
 #ifdef __cplusplus
 }

@@ -1710,6 +1710,13 @@ class Context:
                                                       C.byref(f)))
         return a.value, b.value, c.value, bool(f.value)
 
+    def selftest_k3_term(self, samples: int = 1 << 24, seed: int = 1):
+        """(mismatches of the batched passes' projection form against the written one, whether the configured camera lets
+        the k3 term go)."""
+        a, f = C.c_int64(), C.c_int32()
+        self._check(self.lib.pcp_selftest_k3_term(self.h, C.c_int64(samples), C.c_uint64(seed), C.byref(a), C.byref(f)))
+        return a.value, bool(f.value)
+
     def tile_masks(self) -> np.ndarray:
         """(tiles, mask_words) uint32: the tile x keyframe masks as the last depth pass left them."""
         t, w = C.c_int64(), C.c_int32()

@@ -176,6 +176,9 @@ __global__ __launch_bounds__(kBlock) void k_group_mask_flat(const float4 *__rest
 // every lane looped over its own number of surviving keyframes; a wavefront per group with all its words: 9 768
 // wavefronts at C3, barely more than the chip holds at once, the longest deciding the kernel).  The verdicts are
 // gathered with wave ballots; the 16 lanes of slot 0 own their tiles' mask words.
+// kInside = false: nobody reads the tiles' `inside` words (their one reader, the depth pass, runs without its rejection test in the
+// common configuration): inside_mask is null, and the second ballot and its bit assembly per round are not compiled in.
+template <bool kInside>
 __global__ __launch_bounds__(kBlock) void k_tile_mask_dense(const float4 *__restrict__ spheres, int64_t tiles,
                                                             DevCamera cam, const DevFrame *__restrict__ frames,
                                                             int32_t n_frames, int32_t w0, int32_t w1, int32_t words,
@@ -198,7 +201,8 @@ __global__ __launch_bounds__(kBlock) void k_tile_mask_dense(const float4 *__rest
   // keyframes in which the whole group images inside the box: every tile keeps the pair (and skips the pre-test) unexamined
   const uint32_t whole = __builtin_amdgcn_readfirstlane(group_inside[group * words + w]) & todo;
   todo &= ~whole;
-  uint32_t word = whole, inside = whole;
+  uint32_t word = whole;
+  [[maybe_unused]] uint32_t inside = whole;
   if (todo) {
     const float4 sph = spheres[have ? tile : tiles - 1];
     while (todo) {
@@ -211,19 +215,23 @@ __global__ __launch_bounds__(kBlock) void k_tile_mask_dense(const float4 *__rest
       const int32_t b = slot == 0 ? bit[0] : slot == 1 ? bit[1] : slot == 2 ? bit[2] : bit[3];
       int cls = 1;
       if (b >= 0 && have) cls = cull_enabled ? tile_classify(cam, frames[(w << 5) + b], sph) : 0;
-      const unsigned long long keep = __ballot(cls != 1), ins = __ballot(cls == 2);
+      const unsigned long long keep = __ballot(cls != 1);
+      [[maybe_unused]] unsigned long long ins = 0ull;
+      if constexpr (kInside) ins = __ballot(cls == 2);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         if (bit[k] >= 0) {
           word |= static_cast<uint32_t>((keep >> (k * 16 + t)) & 1ull) << bit[k];
-          inside |= static_cast<uint32_t>((ins >> (k * 16 + t)) & 1ull) << bit[k];
+          if constexpr (kInside) inside |= static_cast<uint32_t>((ins >> (k * 16 + t)) & 1ull) << bit[k];
         }
       }
     }
   }
   if (slot == 0 && have) {
     tile_mask[tile * words + w] = word;
-    if (inside_mask) inside_mask[tile * words + w] = inside;
+    if constexpr (kInside) {
+      if (inside_mask) inside_mask[tile * words + w] = inside;
+    }
   }
 }
 
@@ -360,7 +368,11 @@ __device__ __forceinline__ uint32_t range_bits(int32_t w, int32_t f0, int32_t f1
 // kCommon: the configuration every batched run of the CLI and the bench uses (z-buffer cull with its depth buffer on, fp32
 // rejection test and exact short divisions enabled) is compiled with those switches as constants -- the mode fields, the
 // hidden_points_removal bounds and the branches on them leave the scalar register file (see common_camera).
-template <bool kCommon>
+// kK3 = false (common configuration only): the camera's k3 term is left out of the distortion (pcp_context::k3_dropped,
+// pcp_visit_forms.hpp distort_short<false>).
+// The common configuration runs without the rejection test, so nothing reads the tiles' `inside` words there: tile_inside is
+// null (the host passes none and k_tile_mask_dense builds none) and neither loaded nor broadcast.
+template <bool kCommon, bool kK3 = true>
 __global__ __launch_bounds__(kBlock) void k_depth_pass(const float *__restrict__ x, const float *__restrict__ y,
                                                        const float *__restrict__ z, int64_t n, DevCamera cam_in,
                                                        const DevFrame *__restrict__ frames, int32_t f0, int32_t f1,
@@ -408,8 +420,10 @@ __global__ __launch_bounds__(kBlock) void k_depth_pass(const float *__restrict__
     uint32_t my_word = 0xffffffffu;
     if (tile_mask && have_w) my_word = tile_mask[tile * words + my_w];
     // pairs whose tile images inside the acceptance box: the fp32 rejection test is skipped (it could not reject)
-    uint32_t my_inside = 0u;
-    if (tile_inside && have_w) my_inside = tile_inside[tile * words + my_w];
+    [[maybe_unused]] uint32_t my_inside = 0u;
+    if constexpr (!kCommon) {
+      if (tile_inside && have_w) my_inside = tile_inside[tile * words + my_w];
+    }
     const uint32_t my_range = have_w ? range_bits(my_w, f0, f1) : 0u;
     const bool walked = (my_word & my_range) != 0u;  // this lane's word has a keyframe to visit
     for (unsigned long long walk = __builtin_amdgcn_ballot_w64(walked); walk; walk &= walk - 1ull) {
@@ -418,14 +432,20 @@ __global__ __launch_bounds__(kBlock) void k_depth_pass(const float *__restrict__
       const uint32_t in_range = range_bits(w, f0, f1);
       const uint32_t word = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int32_t>(my_word), wl));
       uint32_t todo = in_range & word;
-      const uint32_t inside = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int32_t>(my_inside), wl));
+      [[maybe_unused]] uint32_t inside = 0u;
+      if constexpr (!kCommon) inside = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int32_t>(my_inside), wl));
       uint32_t seen = 0u;  // keyframes in which some lane can be coloured
       while (todo) {
         const int32_t b = __builtin_ctz(todo);
         const int32_t f = (w << 5) + b;
         todo &= todo - 1u;
         const DevFrame &fr = frames[f];
-        const auto p = project_visit<true, kCommon>(cam, fr.w2c, px, py, pz, ((inside >> b) & 1u) == 0u, finite_sure);
+        const auto p = [&] {
+          if constexpr (kCommon)
+            return project_point_batched<true, kK3>(cam, fr.w2c, px, py, pz, true, finite_sure);
+          else
+            return project_visit<true, false>(cam, fr.w2c, px, py, pz, ((inside >> b) & 1u) == 0u, finite_sure);
+        }();
         bool in_map, cand;
         if constexpr (kCommon) {  // the predicates themselves
           in_map = live && p.map_ok;
@@ -447,7 +467,13 @@ __global__ __launch_bounds__(kBlock) void k_depth_pass(const float *__restrict__
           // within 1e-6 of each other) all go to the map, which settles them in full precision
           unsigned long long key = ~0ull, sbits = 0ull;
           if (in_map) {
-            sbits = static_cast<unsigned long long>(__double_as_longlong(sumsq64(p.xc, p.yc, p.zc)));
+            // (the common configuration's visit hands back the coordinates as its projection promoted them: no second conversion)
+            double s;
+            if constexpr (kCommon)
+              s = (p.X * p.X + p.Y * p.Y) + p.Z * p.Z;
+            else
+              s = sumsq64(p.xc, p.yc, p.zc);
+            sbits = static_cast<unsigned long long>(__double_as_longlong(s));
             key = (static_cast<unsigned long long>(static_cast<uint32_t>(p.cell)) << 32) | (sbits >> 32);
           }
           tbl[lane] = ~0ull;
@@ -656,6 +682,9 @@ __global__ __launch_bounds__(kBlock) void k_colour_pass(const float *__restrict_
 // 7 spilled, 61, none, 7.  A kernel of its own and the visit written out a second time: the registers of every k_colour_pass form
 // are pinned by tests/test_label_fusion_cpu.py, and neither a further template parameter nor a shared helper is certain to leave
 // them as they are.  The visit, Top5 and the result store are those of that form to the letter -- change both or neither.
+// kK3 = false: the camera's k3 term is left out of the distortion (pcp_context::k3_dropped, pcp_visit_forms.hpp distort_short<false>)
+// -- the one place where this visit and that of k_colour_pass<true, 2, true, false> differ.
+template <bool kK3>
 __global__ __launch_bounds__(kBlock) void k_colour_pass_preload(const float *__restrict__ x, const float *__restrict__ y,
                                                                 const float *__restrict__ z, int64_t n, DevCamera cam_in,
                                                                 const DevFrame *__restrict__ frames, int32_t f0, int32_t f1,
@@ -688,7 +717,7 @@ __global__ __launch_bounds__(kBlock) void k_colour_pass_preload(const float *__r
       todo &= todo - 1u;
       const DevFrame &fr = frames[f];
       // the refined masks only keep pairs with a candidate lane: the fp32 rejection test cannot skip the wavefront
-      const auto p = project_visit<false, true>(cam, fr.w2c, px, py, pz, true, finite_sure);
+      const auto p = project_point_batched<false, kK3>(cam, fr.w2c, px, py, pz, true, finite_sure);
       const bool cand = live && p.image_ok && p.map_ok;
       if (cand) {
         const uint32_t dbits = cam.enable_zbuf ? depth[static_cast<uint64_t>(static_cast<uint32_t>(f)) * static_cast<uint32_t>(cells) + static_cast<uint32_t>(p.cell)] : 0u;
@@ -919,6 +948,68 @@ __global__ __launch_bounds__(kBlock) void k_selftest_uv(DevCamera cam, int32_t t
     project_uv<true, false>(cam, xc, yc, zc, u0, v0);
   project_uv<true, false>(cam, xc, yc, zc, u1, v1);
   if (!same_bits_f64(u0, u1) || !same_bits_f64(v0, v1)) atomicAdd(bad, 1ull);
+}
+
+// k3-term self-test (pcp_selftest_k3_term): the written projection against the form the batched kernels of the common configuration
+// run under the configured camera -- the short distortion without the k3 term where pcp_set_camera allows it (`form` 2), with it
+// (1), or the written one (0) -- on the float triples of k_selftest_div64 and, behind them, on a grid of extreme triples: tiny
+// depths under ordinary, huge and non-finite x and y, where r6 overflows.  What is compared is what a visit makes of (u, v): the
+// verdicts of both truncation rules, the cell and the pixel under them, and u, v bit for bit where the written form accepts a lane.
+constexpr int kK3EdgeXY = 14, kK3EdgeZ = 8;
+constexpr int64_t kK3Edges = int64_t(kK3EdgeXY) * kK3EdgeXY * kK3EdgeZ;
+__device__ __forceinline__ float k3_edge_xy(int k) {
+  const float t[kK3EdgeXY] = {0.0f, -0.0f, 1.0f, -1.0f, 0.5f, -0.75f, 0x1p-100f, 0x1p-149f, FLT_MAX, -FLT_MAX, 0x1p60f, -0x1p-30f,
+                              __builtin_inff(), __builtin_nanf("")};
+  return t[k];
+}
+__device__ __forceinline__ float k3_edge_z(int k) {
+  const float t[kK3EdgeZ] = {0x1p-100f, 0x1p-101f, 0x1p-126f, 0x1p-149f, 0x1p-57f, 0x1p-85f, 1.0f, __builtin_inff()};
+  return t[k];
+}
+__global__ __launch_bounds__(kBlock) void k_selftest_k3(DevCamera cam, int32_t form, int64_t samples, uint64_t seed,
+                                                        unsigned long long *__restrict__ bad) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= samples + kK3Edges) return;
+  float xc, yc, zc;
+  if (i < samples) {
+    const uint64_t a = mix64(seed ^ static_cast<uint64_t>(i) * 3u), b = mix64(a);
+    uint32_t bx = static_cast<uint32_t>(a), by = static_cast<uint32_t>(a >> 32), bz = static_cast<uint32_t>(b);
+    const uint32_t mode = static_cast<uint32_t>(b >> 32) & 3u;
+    if (mode != 0u) {
+      const uint32_t span = mode == 1u ? 12u : 40u;
+      bx = (bx & 0x807fffffu) | ((127u - span / 2u + (bx >> 23) % span) << 23);
+      by = (by & 0x807fffffu) | ((127u - span / 2u + (by >> 23) % span) << 23);
+      bz = (bz & 0x807fffffu) | ((127u - span / 2u + (bz >> 23) % span) << 23);
+    }
+    xc = __uint_as_float(bx), yc = __uint_as_float(by), zc = fabsf(__uint_as_float(bz));
+  } else {
+    const int e = static_cast<int>(i - samples);
+    xc = k3_edge_xy(e % kK3EdgeXY), yc = k3_edge_xy((e / kK3EdgeXY) % kK3EdgeXY), zc = k3_edge_z(e / (kK3EdgeXY * kK3EdgeXY));
+  }
+  if (!(zc > 0.0f)) return;  // the projection is only entered with z > 0
+  double u0, v0, u1, v1;
+  if (form == 2)
+    project_uv_batched<false>(cam, xc, yc, zc, xc, yc, zc, u0, v0);
+  else if (form == 1)
+    project_uv_batched<true>(cam, xc, yc, zc, xc, yc, zc, u0, v0);
+  else
+    project_uv<true, false>(cam, xc, yc, zc, u0, v0);
+  project_uv<true, false>(cam, xc, yc, zc, u1, v1);
+  // what project_point_short makes of (u, v)
+  auto verdicts = [&](double u, double v, int32_t &cell, int32_t &pixel, bool &map_ok, bool &image_ok) {
+    map_ok = vf::map_cell_short(div_by_ds(cam, static_cast<float>(u)), div_by_ds(cam, static_cast<float>(v)), vf::map_bound(cam.mw),
+                                vf::map_bound(cam.mh), cam.mw, cell);
+    image_ok = (u > -1.0) & (u < cam.img_wd) & (v > -1.0) & (v < cam.img_hd);
+    pixel = image_ok ? static_cast<int32_t>(v) * cam.img_w + static_cast<int32_t>(u) : 0;
+    if (!map_ok) cell = 0;
+  };
+  int32_t c0, p0, c1, p1;
+  bool m0, i0, m1, i1;
+  verdicts(u0, v0, c0, p0, m0, i0);
+  verdicts(u1, v1, c1, p1, m1, i1);
+  bool same = m0 == m1 && i0 == i1 && c0 == c1 && p0 == p1;
+  if (m1 || i1) same = same && same_bits_f64(u0, u1) && same_bits_f64(v0, v1);
+  if (!same) atomicAdd(bad, 1ull);
 }
 
 // all 2^32 bit patterns: as a quotient along x, along y and along both (the other axis at cell 0) for the cell rule; as the
@@ -1943,9 +2034,11 @@ int pcp_depth_pass(pcp_context *ctx, int32_t frame_begin, int32_t frame_end) {
                          w0, w1, ctx->mask_words, ctx->group_mask.p, group_inside, cull_tiles ? 1 : 0, ctx->work_hist.p,
                          2 * kWorkBins, z_maps ? reinterpret_cast<unsigned long long *>(ctx->depth_sq.p) : nullptr,
                          z_maps ? map_cells : int64_t(0));
-      hipLaunchKernelGGL(k_tile_mask_dense, dim3(static_cast<uint32_t>(div_up(groups * (w1 - w0), kBlock / 64))), dim3(kBlock),
+      // the tiles' `inside` words only where the depth pass reads them (its rejection test: not in the common configuration)
+      uint32_t *tile_inside = is_common_camera(ctx) ? nullptr : ctx->tile_inside.p;
+      hipLaunchKernelGGL(tile_inside ? k_tile_mask_dense<true> : k_tile_mask_dense<false>, dim3(static_cast<uint32_t>(div_up(groups * (w1 - w0), kBlock / 64))), dim3(kBlock),
                          0, ctx->stream, tile_sph, ctx->n_tiles, ctx->dcam, ctx->frames.p, ctx->n_frames, w0, w1,
-                         ctx->mask_words, ctx->group_mask.p, group_inside, ctx->tile_mask.p, ctx->tile_inside.p, cull_tiles ? 1 : 0);
+                         ctx->mask_words, ctx->group_mask.p, group_inside, ctx->tile_mask.p, tile_inside, cull_tiles ? 1 : 0);
       // longest-work-first order of the tiles for this pass
       if ((rc = sort_tiles_by_work(ctx, w0, w1, ctx->tile_order.p)) != PCP_OK) return rc;
       ctx->tile_order_live = true;
@@ -1985,11 +2078,13 @@ int pcp_depth_pass(pcp_context *ctx, int32_t frame_begin, int32_t frame_end) {
     }
     {
       LaunchTimer t(ctx, PCP_K_DEPTH);
-      hipLaunchKernelGGL(is_common_camera(ctx) ? k_depth_pass<true> : k_depth_pass<false>,
+      const bool common = is_common_camera(ctx);
+      auto kernel = !common ? k_depth_pass<false> : ctx->k3_dropped ? k_depth_pass<true, false> : k_depth_pass<true>;
+      hipLaunchKernelGGL(kernel,
                          dim3(static_cast<uint32_t>(ctx->n_tiles)), dim3(64), 0, ctx->stream, ctx->sxyz.p,
                          ctx->sxyz.p + plane, ctx->sxyz.p + 2 * plane, ctx->n, ctx->dcam, ctx->frames.p, frame_begin,
-                         frame_end, ctx->depth_sq.p, cells, frame_begin, ctx->tile_mask.p, ctx->tile_inside.p,
-                         ctx->mask_words, ctx->tile_order.p);
+                         frame_end, ctx->depth_sq.p, cells, frame_begin, ctx->tile_mask.p,
+                         common ? static_cast<const uint32_t *>(nullptr) : ctx->tile_inside.p, ctx->mask_words, ctx->tile_order.p);
       if (z_maps)
         hipLaunchKernelGGL(k_depth_finish, dim3(static_cast<uint32_t>(std::min<int64_t>(div_up(map_cells, kBlock), 4096))),
                            dim3(kBlock), 0, ctx->stream, ctx->depth_sq.p, map_cells,
@@ -2166,7 +2261,7 @@ static int colour_pass_impl(pcp_context *ctx, int32_t frame_begin, int32_t frame
     // wider ranges (more than 2048 keyframes) keep k_colour_pass<true, 2, true, false>
     if (common && ctx->dcam.match_mode == PCP_MATCH_ROUNDTRIP && flags == 4 && !label && ctx->tile_mask.p &&
         ((frame_end - 1) >> 5) - (frame_begin >> 5) < 64) {
-      hipLaunchKernelGGL(k_colour_pass_preload, dim3(blocks_for(ctx->n)), dim3(kBlock), 0, ctx->stream, ctx->sxyz.p,
+      hipLaunchKernelGGL(ctx->k3_dropped ? k_colour_pass_preload<false> : k_colour_pass_preload<true>, dim3(blocks_for(ctx->n)), dim3(kBlock), 0, ctx->stream, ctx->sxyz.p,
                          ctx->sxyz.p + plane, ctx->sxyz.p + 2 * plane, ctx->n, ctx->dcam, ctx->frames.p, frame_begin, frame_end,
                          ctx->depth.p, cells_of(ctx), ctx->tile_mask.p, ctx->mask_words, ctx->images.p,
                          static_cast<int64_t>(ctx->dcam.img_w) * ctx->dcam.img_h, ctx->perm.p, result);
@@ -2493,6 +2588,25 @@ int pcp_selftest_visit_forms(pcp_context *ctx, int64_t samples, uint64_t seed, i
   if (mismatches_cell) *mismatches_cell = static_cast<int64_t>(h[1]);
   if (mismatches_sqrt) *mismatches_sqrt = static_cast<int64_t>(h[2]);
   if (short_distortion) *short_distortion = ctx->uv_tame ? 1 : 0;
+  return PCP_OK;
+}
+
+int pcp_selftest_k3_term(pcp_context *ctx, int64_t samples, uint64_t seed, int64_t *mismatches, int32_t *term_dropped) {
+  if (!ctx) return PCP_ERR_INVALID;
+  if (!ctx->have_camera) return set_error(ctx, PCP_ERR_STATE, "pcp_selftest_k3_term: pcp_set_camera has not been called");
+  PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (samples < 0) return set_error(ctx, PCP_ERR_INVALID, "pcp_selftest_k3_term: negative sample count");
+  PCP_HIP_TRY(ctx, ctx->s_counter.ensure(4));
+  unsigned long long *bad = ctx->s_counter.p;
+  PCP_HIP_TRY(ctx, hipMemsetAsync(bad, 0, 8, ctx->stream));
+  hipLaunchKernelGGL(k_selftest_k3, dim3(blocks_for(samples + kK3Edges)), dim3(kBlock), 0, ctx->stream, ctx->dcam,
+                     ctx->k3_dropped ? 2 : ctx->uv_tame ? 1 : 0, samples, seed, bad);
+  PCP_HIP_TRY(ctx, hipGetLastError());
+  unsigned long long h = 0;
+  PCP_HIP_TRY(ctx, hipMemcpyAsync(&h, bad, 8, hipMemcpyDeviceToHost, ctx->stream));
+  PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (mismatches) *mismatches = static_cast<int64_t>(h);
+  if (term_dropped) *term_dropped = ctx->k3_dropped ? 1 : 0;
   return PCP_OK;
 }
 

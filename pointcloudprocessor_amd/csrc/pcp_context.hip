@@ -799,6 +799,9 @@ int pcp_set_camera(pcp_context *ctx, const pcp_camera *cam, const pcp_cull_param
   d.mh = cam->cull_height / cp.downsample_factor;
   ctx->uv_tame = vf::distortion_is_tame(cam->p1, cam->p2);
   if (const char *e = std::getenv("PCP_DISABLE_FAST_EXACT")) ctx->uv_tame = (e[0] == '1') ? false : ctx->uv_tame;
+  // a zero k3 whose term the short form may leave out (the condition of distort_short<false>); else the term stays
+  ctx->k3_dropped = ctx->uv_tame && vf::k3_term_droppable(vf::Distortion{cam->k1, cam->k2, cam->k3, cam->p1, cam->p2}, cam->fx,
+                                                          cam->fy, cam->cx, cam->cy);
   // the kernels of the colour path only know the candidate filter; the hull is a stage of its own (pcp_hpr.hip)
   d.cull_mode = cp.cull_mode == PCP_CULL_HPR ? PCP_CULL_HPR_CANDIDATES : cp.cull_mode;
   d.match_mode = cp.match_mode;

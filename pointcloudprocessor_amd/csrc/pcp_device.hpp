@@ -217,7 +217,7 @@ __device__ __forceinline__ Projected project_point(const DevCamera &c, const flo
 }
 
 // project_point for the batched passes of the common configuration (z-buffer cull with its depth buffer on, tame p1 / p2; the
-// depth pass and the whole-run colour pass ask for it): the
+// whole-run k_colour_pass forms ask for it; the depth pass and k_colour_pass_preload run project_point_batched below): the
 // short forms of pcp_visit_forms.hpp, and the two truncation rules as predicates that never become -1 sentinels for the caller
 // to compare with -1 again.  cell / pixel are only meaningful under map_ok / image_ok.
 struct ShortVisit {
@@ -259,6 +259,75 @@ __device__ __forceinline__ auto project_visit(const DevCamera &c, const float *_
     return project_point_short<kPretest>(c, m, x, y, z, pretest_here, finite_sure);
   else
     return project_point<kPretest>(c, m, x, y, z, pretest_here, finite_sure);
+}
+
+// project_point_short for the two kernels a whole run of the common configuration spends its time in (k_depth_pass<true, ...> and
+// k_colour_pass_preload): the same arithmetic, with
+//   kK3 = false: distort_short without the k3 term (pcp_visit_forms.hpp), for a camera with pcp_context::k3_dropped;
+//   X, Y, Z: the camera coordinates as the projection promoted them, handed back -- the depth pass's squared range takes them
+//   from here instead of converting the three floats again.
+// Written out beside project_point_short / project_uv / divide_xy_by_z, not folded into them: those are inlined into every
+// k_colour_pass form, whose instructions are pinned (tests/test_label_fusion_cpu.py), and sharing the text moved them.
+struct BatchedVisit {
+  float xc, yc, zc;
+  double X, Y, Z;
+  int32_t cell, pixel;
+  bool map_ok, image_ok;
+};
+// (u, v) of the promoted camera coordinates (X, Y, Z) = (xc, yc, zc): divide_xy_by_z on them (the common configuration has
+// ds_fast = 1: project_uv's other branch is not here), the short distortion, the pinhole
+template <bool kK3>
+__device__ __forceinline__ void project_uv_batched(const DevCamera &c, float xc, float yc, float zc, double X, double Y, double Z,
+                                                   double &u, double &v, bool finite_sure = false) {
+  double xn, yn;
+  auto divide = [&](bool sure) {
+    if (sure || (xc - xc) + (yc - yc) + (zc - zc) == 0.0f) {  // all three finite
+      double r = __builtin_amdgcn_rcp(Z);
+      double e = __builtin_fma(-Z, r, 1.0);
+      r = __builtin_fma(r, e, r);
+      e = __builtin_fma(-Z, r, 1.0);
+      r = __builtin_fma(r, e, r);
+      const double qx = X * r, qy = Y * r;
+      const double rx = __builtin_fma(-Z, qx, X), ry = __builtin_fma(-Z, qy, Y);
+      xn = __builtin_fma(rx, r, qx);
+      yn = __builtin_fma(ry, r, qy);
+    } else {
+      xn = X / Z;
+      yn = Y / Z;
+    }
+  };
+  if (finite_sure)  // (two copies of the sequence: a scalar branch instead of a test per lane)
+    divide(true);
+  else
+    divide(false);
+  double xd, yd;
+  vf::distort_short<kK3>(vf::Distortion{c.k1, c.k2, c.k3, c.p1, c.p2}, xn, yn, xd, yd);
+  u = c.fx * xd + c.cx;
+  v = c.fy * yd + c.cy;
+}
+template <bool kPretest, bool kK3>
+__device__ __forceinline__ BatchedVisit project_point_batched(const DevCamera &c, const float *__restrict__ m, float x, float y, float z,
+                                                              bool pretest_here = true, bool finite_sure = false) {
+  BatchedVisit p;
+  xform(m, x, y, z, p.xc, p.yc, p.zc);
+  p.cell = 0;
+  p.pixel = 0;
+  p.map_ok = p.image_ok = false;
+  p.X = p.xc;
+  p.Y = p.yc;
+  p.Z = p.zc;
+  // (see project_point_short for the wave-uniform branch)
+  const bool go = p.zc > 0.0f && !(kPretest && pretest_here && c.pretest && surely_rejected(c, p.xc, p.yc, p.zc));
+  if (!kPretest || __builtin_amdgcn_ballot_w64(go)) {
+    double u, v;
+    project_uv_batched<kK3>(c, p.xc, p.yc, p.zc, p.X, p.Y, p.Z, u, v, finite_sure);
+    const bool cell_ok = vf::map_cell_short(div_by_ds(c, static_cast<float>(u)), div_by_ds(c, static_cast<float>(v)), vf::map_bound(c.mw),
+                                            vf::map_bound(c.mh), c.mw, p.cell);
+    p.map_ok = go & cell_ok;
+    p.image_ok = go & (u > -1.0) & (u < c.img_wd) & (v > -1.0) & (v < c.img_hd);  // colour_pixel
+    p.pixel = p.image_ok ? static_cast<int32_t>(v) * c.img_w + static_cast<int32_t>(u) : 0;
+  }
+  return p;
 }
 
 // A4 keep rule (view_culling.cpp:135-171).  depth = this keyframe's map.

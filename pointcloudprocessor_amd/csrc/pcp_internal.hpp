@@ -310,6 +310,9 @@ struct pcp_context {
   bool have_camera = false;
   bool uv_tame = false;  // p1, p2 are in the range the short distortion form is proven for (pcp_visit_forms.hpp): a condition
                          // of the common configuration, whose batched kernels run that form
+  bool k3_dropped = false;  // k3 is a zero and the other constants are in the range for which the short form without the k3
+                            // term is proven to give the same verdicts (pcp_visit_forms.hpp): the batched kernels of the common
+                            // configuration run that form; any other camera keeps the term and stays in the common configuration
   pcp_camera camera{};
   pcp_cull_params cull{};
   pcp::DevCamera dcam{};

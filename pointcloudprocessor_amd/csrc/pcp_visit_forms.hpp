@@ -58,13 +58,39 @@ PCP_VF_HD void distort_written(const Distortion &c, double xn, double yn, double
 // zero the written addition of the same two terms returns.  Non-finite values: doubling maps inf to inf and NaN to NaN, so every
 // operation below sees an infinity or a NaN exactly where the written one does and produces the same class (inf - inf and
 // 0 inf are NaN in both); NaN payloads are not observable (every later use is a comparison).
+//
+// kK3 = false: without the k3 term -- r6, k3 r6 and the last addition of rc, three instructions -- for a camera whose k3 is a zero
+// (the reference's own constants, every camera of synth.py) and whose other constants pass k3_term_droppable() below, which
+// pcp_set_camera turns into pcp_context::k3_dropped; any other camera keeps the term.  The lane's VERDICTS are the same -- u and v
+// bit for bit wherever the written form accepts a lane, and a rejection by both truncation rules wherever it rejects one.
+// With S = RN(RN(1 + k1 r2) + RN(k2 r4)), the rc of this form, and k3 = +-0:
+//   a. r6 finite: k3 r6 = +-0 and S + (+-0) = S unless S = -0, which it never is: a sum is -0 only when both terms are, and
+//      RN(1 + t) is not (1 is not -0; an exact 0 rounds to +0).  S infinite or NaN: unchanged by the addition.  Same bits.
+//   b. r2 NaN (xn or yn NaN, or inf - inf on the way): rc is NaN in both forms.
+//   c. r6 = inf.  The written form has k3 r6 = 0 inf = NaN, so u and v are NaN and both rules reject the lane; this form must
+//      reject it too.  r6 = inf needs r2^3 >= 2^1024 (1 - 2^-54), r2 >= 2^341.3, so M = max(|xn|, |yn|) >= 2^170 (r2 <= 2 M^2 (1 +
+//      2^-52)), or xn / yn infinite.  If S is not finite (r2 or r4 infinite -- k2 inf is +-inf, 0 inf NaN -- or the sum overflowed),
+//      rc xn and rc yn are infinite or NaN, and an infinity or a NaN stays one through every later multiply, add and FMA (inf 0 and
+//      inf - inf are NaN): u and v are not finite, rejected.  Else every value below is finite, M <= 2^277 (see the ranges above), and
+//      say |xn| = M (for |yn| = M read yd, b, p1 t3, fy, cy).  Under k3_term_droppable() -- k1, k2, p1, p2 each 0 or of
+//      magnitude in [2^-60, 2^60], |fx|, |fy| in [2^-20, 2^40], |cx|, |cy| <= 2^40 -- and with every operation's relative
+//      error below 2^-52 (nothing here is near the subnormal range):
+//        k2 != 0:          |k2 r4| >= 2^-61 M^4 against |1 + k1 r2| <= 2^62 M^2, a factor 2^-123 M^2 >= 2^217:  |S| >= 2^-62 M^4
+//        k2 = 0, k1 != 0:  k2 r4 = +-0, |k1 r2| >= 2^-61 M^2 against 1:                                          |S| >= 2^-62 M^2
+//        k1 = k2 = 0:      S = 1, and the condition then asks for p1 = p2 = 0: a = b = +-0, p2 t2 = +-0, xd = xn exactly
+//      In the first two |S xn| >= 2^-63 M^3 (or it overflows: see above) against |2 a| <= 2^62 M^2 and |p2 t2| <= 2^63 M^2
+//      (t2 <= 4 M^2 (1 + 2^-51)), together below 2^64 M^2: smaller by 2^-127 M >= 2^43, so |xd| >= 2^-64 M^3 >= 2^446; in the third
+//      |xd| = M >= 2^170.  Then |fx xd| >= 2^150 against |cx| <= 2^40: |u| >= 2^149 or infinite, outside every image and, as fp32
+//      an infinity, outside every map (div_by_ds, cell_of_quotient).  Rejected by both rules on the strength of u alone.
+// (k1 = k2 = 0 with a tangential term is left out: xd = xn (1 + 2 p1 yn) + p2 t2 can cancel.  Such a camera keeps the term.)
+template <bool kK3 = true>
 PCP_VF_HD void distort_short(const Distortion &c, double xn, double yn, double &xd, double &yd) {
   const double x2 = xn * xn;
   const double y2 = yn * yn;
   const double r2 = x2 + y2;
   const double r4 = r2 * r2;
-  const double r6 = r2 * r4;
-  const double rc = ((1.0 + c.k1 * r2) + c.k2 * r4) + c.k3 * r6;
+  const double r6 = r2 * r4;  // (unused without the term)
+  const double rc = kK3 ? ((1.0 + c.k1 * r2) + c.k2 * r4) + c.k3 * r6 : (1.0 + c.k1 * r2) + c.k2 * r4;
   const double w = xn * yn;
   const double a = c.p1 * w, b = c.p2 * w;
   const double t2 = PCP_VF_FMA(2.0, x2, r2);
@@ -78,6 +104,21 @@ PCP_VF_HD bool tame_coefficient(double p) {
   return p == 0.0 || (m >= 0x1p-400 && m <= 0x1p400);  // NaN: false
 }
 PCP_VF_HD bool distortion_is_tame(double p1, double p2) { return tame_coefficient(p1) && tame_coefficient(p2); }
+
+// the condition of distort_short<false> (case c of its proof); NaNs fail every comparison
+PCP_VF_HD bool magnitude_within(double p, double lo, double hi) {
+  const double m = p < 0.0 ? -p : p;
+  return m >= lo && m <= hi;
+}
+PCP_VF_HD bool k3_term_droppable(const Distortion &c, double fx, double fy, double cx, double cy) {
+  const bool zero_or_mid[4] = {c.k1 == 0.0 || magnitude_within(c.k1, 0x1p-60, 0x1p60), c.k2 == 0.0 || magnitude_within(c.k2, 0x1p-60, 0x1p60),
+                               c.p1 == 0.0 || magnitude_within(c.p1, 0x1p-60, 0x1p60), c.p2 == 0.0 || magnitude_within(c.p2, 0x1p-60, 0x1p60)};
+  const bool radial = c.k1 != 0.0 || c.k2 != 0.0;       // a leading coefficient, or ...
+  const bool plain = c.p1 == 0.0 && c.p2 == 0.0;        // ... no distortion at all
+  return c.k3 == 0.0 && zero_or_mid[0] && zero_or_mid[1] && zero_or_mid[2] && zero_or_mid[3] && (radial || plain) &&
+         magnitude_within(fx, 0x1p-20, 0x1p40) && magnitude_within(fy, 0x1p-20, 0x1p40) && magnitude_within(cx, 0.0, 0x1p40) &&
+         magnitude_within(cy, 0.0, 0x1p40);
+}
 
 // ---- 2. cell of the depth map from the two fp32 quotients (view_culling.cpp:86-90, :116, :155), depth buffer on -------------
 // written: each axis against the FULL cull size (sic), C truncation, then against the map (mw = cull_w / ds, mh likewise).

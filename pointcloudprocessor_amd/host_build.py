@@ -17,6 +17,7 @@ TARGETS = {
     "format_selftest": ["format_selftest.cpp"],
     "parse_selftest": ["parse_selftest.cpp"],  # csrc/pcp_ascii_parse.hpp compiled for the host (CPU only: never a GPU job)
     "visit_forms_selftest": ["visit_forms_selftest.cpp"],  # csrc/pcp_visit_forms.hpp compiled for the host (CPU only)
+    "k3_term_selftest": ["k3_term_selftest.cpp"],  # csrc/pcp_visit_forms.hpp, the form without the k3 term (CPU only)
     "voxel_reduce_selftest": ["voxel_reduce_selftest.cpp"],  # csrc/pcp_voxel_reduce.hpp compiled for the host (CPU only)
     "normals_selftest": ["normals_selftest.cpp"],  # csrc/pcp_normals.hpp compiled for the host (CPU only)
     "ortho_selftest": ["ortho_selftest.cpp"],  # csrc/pcp_ortho.hpp compiled for the host (CPU only)
