@@ -79,7 +79,9 @@ extern "C" {
                                 pcp_image_balance, pcp_image_balance_host, pcp_gamma_table_host (keyframe colour balance at upload;
                                 off by default);
                                 entry points added, no layout changed: pcp_ortho_texture, pcp_ortho_texture_points_host
-                                (orthophotos; nothing runs unless called) */
+                                (orthophotos; nothing runs unless called);
+                                entry points added, no layout changed: pcp_facets / _fetch / _host, pcp_facet_plane_host,
+                                pcp_ortho_add_facet (planar facets of the map; nothing runs unless called) */
 
 #define PCP_OK 0
 #define PCP_ERR_INVALID (-1) /* bad argument */
@@ -1188,6 +1190,51 @@ int pcp_crack_skeleton_cracks_fetch(pcp_context *ctx, int64_t first, int64_t max
 int pcp_crack_skeleton_host(int64_t n, const float *xyz, const uint32_t *views, int32_t min_views, float radius, float step,
                             const uint64_t *sum_q, int32_t *out_node, int32_t *out_id, int64_t *out_rows10, int64_t edge_capacity,
                             int64_t *out_rows3, int64_t *out_rows6, int64_t *out_nodes, int64_t *out_edges, int64_t *out_cracks);
+
+/* ---- planar facets of the map (the reference's scripts stop at per-keyframe pictures: no step partitions the map) ---------- */
+/* The faces of the structure as connected components of the map points under a symmetric integer link, one row of exact
+ * integers per face, its plane, and an orthographic map restricted to one face ("Planar facets", FA1-FA9).
+ * Opt-in: nothing runs unless one of these is called, PCP_ABI_VERSION is unchanged and a caller detects support by the
+ * symbols.  Kernels are timed under PCP_K_MISC.  Whole-map contexts only: an index shard sees only its own points.
+ *
+ * pcp_facets reads the uploaded cloud and the live estimate of pcp_estimate_normals (without one: PCP_ERR_STATE).  Point i is a
+ * facet point iff its coordinates are finite, its stored normal is valid (not (0, 0, 0)) and its stored curvature <=
+ * max_curvature (0 <= max_curvature <= 1).  N = rint(normal * 2^14) per component.  Facet points i != j are linked iff
+ *   (a) fl32((dx*dx + dy*dy) + dz*dz) <= t with d = fl32(p_j - p_i) and t the largest float with (double)t <= link_radius^2
+ *       (pcp_estimate_normals' neighbour rule; 0.005 <= link_radius <= 1),
+ *   (b) |N_i . N_j| >= ceil(cos(angle_deg) * 2^28)   (0 < angle_deg <= 45; the normals' sign is unspecified), and
+ *   (c) |N_i . q| and |N_j . q| <= floor(plane_tol * 2^34) with q = rint(d * 2^20)   (1e-4 <= plane_tol <= 0.1 metres),
+ * all in exact 64-bit integers.  A facet is a connected component of the links with at least min_points members
+ * (1..2^24); its id is the lowest input index among them.  out_label (nullable, n, host) = the id of the point's facet, -1 for
+ * a point in none.  *out_facet_points / *out_components / *out_facets (nullable) = facet points, components of any size, facets.
+ * Bad parameters: PCP_ERR_INVALID.  A facet with points * (D * 4096 + 1)^2 >= 2^62, D the largest extent of its box:
+ * PCP_ERR_RANGE, the message names the facet.  Like every call that builds the search grid it invalidates an open
+ * pcp_mls_stream / pcp_cloud_smooth_stream and a pcp_sor_partial.  Labels and table live until the next pcp_facets,
+ * pcp_estimate_normals or pcp_upload_cloud*; a failed call leaves none.
+ * pcp_facets_fetch: rows first .. first + max_rows - 1 of the table, one row per facet, ascending by id: out_id, out_rows10 10
+ * int64 per row -- points, S1 x y z, S2 xx xy xz yy yz zz of Q = rint(fl32(p - p_root) * 2^12) over the members, p_root the
+ * coordinates of point id -- and out_box 6 floats per row, the exact min x y z and max x y z of the members.  All outputs
+ * nullable.  Without a table: PCP_ERR_STATE.  Negative first / max_rows: PCP_ERR_INVALID.
+ * pcp_facets_host: host only, no context, no GPU: the same results for n <= 65536 points (xyz and normal interleaved) by brute
+ * force over the pairs and a sequential union-find; out_label n, out_id n, out_rows10 10 n, out_box 6 n of capacity (all
+ * nullable).  pcp_facet_plane_host: host only, fp64, the plane of one row: out_plane = centroid root + (S1 / points) * 2^-12,
+ * the unit eigenvector of the smallest eigenvalue ev of S2 - S1 S1^T / points by pcl::eigen33's closed form, signed so that its
+ * largest component is positive ((0, 0, 0) when the members span no plane), and rms = sqrt(max(ev, 0) / points) * 2^-12 metres.
+ * points < 1 or a NULL argument: PCP_ERR_INVALID.  Messages of the two at pcp_last_error(NULL).
+ * pcp_ortho_add_facet: pcp_ortho_add (same checks and returns) restricted to the rows whose facet label equals facet_id; the
+ * colour and fused-label layers are kept.  Without live facets: PCP_ERR_STATE; facet_id outside 0 .. n - 1: PCP_ERR_RANGE. */
+typedef struct pcp_facet_params {
+  float link_radius, angle_deg, plane_tol, max_curvature;
+  int32_t min_points;
+} pcp_facet_params;
+int pcp_facets(pcp_context *ctx, const pcp_facet_params *params, int32_t *out_label, int64_t *out_facet_points, int64_t *out_components,
+               int64_t *out_facets);
+int pcp_facets_fetch(pcp_context *ctx, int64_t first, int64_t max_rows, int32_t *out_id, int64_t *out_rows10, float *out_box,
+                     int64_t *out_rows);
+int pcp_facets_host(int64_t n, const float *xyz, const float *normal, const float *curvature, const pcp_facet_params *params,
+                    int32_t *out_label, int32_t *out_id, int64_t *out_rows10, float *out_box, int64_t *out_facets);
+int pcp_facet_plane_host(const float root[3], const int64_t row10[10], double out_plane[7]);
+int pcp_ortho_add_facet(pcp_context *ctx, int32_t facet_id, int64_t index_base, int64_t *out_contributors);
 
 /* ---- precondition of the match-back(PointCloudProcessor.cpp:480-482,571) ------------------------------- */
 /* Number of map points that have ANOTHER map point closer than `radius` (fp32 squared distance, strict <, as

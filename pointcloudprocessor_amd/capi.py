@@ -612,6 +612,57 @@ def crack_components_host(xyz, views, min_views: int = 1, radius: float = 0.02) 
     return label
 
 
+class FacetParams(C.Structure):
+    """pcp_facet_params (DESIGN.md, "Planar facets", FA2-FA5)."""
+    _fields_ = [("link_radius", C.c_float), ("angle_deg", C.c_float), ("plane_tol", C.c_float), ("max_curvature", C.c_float),
+                ("min_points", C.c_int32)]
+
+
+FA_ROW = ("points", "s1x", "s1y", "s1z", "s2xx", "s2xy", "s2xz", "s2yy", "s2yz", "s2zz")  # FA6: the columns of rows
+FA_PLANE = ("cx", "cy", "cz", "nx", "ny", "nz", "rms")  # FA7: the columns of facet_plane_host
+
+
+def facets_host(xyz, normal, curvature, link_radius: float = 0.1, angle_deg: float = 10.0, plane_tol: float = 0.01,
+                max_curvature: float = 0.02, min_points: int = 1000) -> dict:
+    """The facets of n <= 65536 points computed on the CPU by brute force over the pairs (pcp_facets_host: no context, no GPU):
+    xyz, normal (n, 3) float32, curvature (n,) float32 -> dict(label (n,) int32, the lowest index of the point's facet, -1 for a
+    point in none; ids (F,) int32 ascending; rows (F, 10) int64, the columns FA_ROW; box (F, 6) float32: min xyz, max xyz)."""
+    L = load()
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    normal = np.ascontiguousarray(normal, np.float32).reshape(-1, 3)
+    curvature = np.ascontiguousarray(curvature, np.float32).reshape(-1)
+    n = xyz.shape[0]
+    if normal.shape[0] != n or curvature.shape[0] != n:
+        raise ValueError("facets_host: xyz, normal and curvature differ in their number of rows")
+    prm = FacetParams(link_radius, angle_deg, plane_tol, max_curvature, min_points)
+    cap = min(n, 65536)  # (more rows are refused by the library: nothing to allocate)
+    label = np.empty(n, np.int32)
+    ids = np.empty(cap, np.int32)
+    rows = np.empty((cap, 10), np.int64)
+    box = np.empty((cap, 6), np.float32)
+    got = C.c_int64()
+    rc = L.pcp_facets_host(C.c_int64(n), _ptr(xyz), _ptr(normal), _ptr(curvature), C.byref(prm), _ptr(label), _ptr(ids), _ptr(rows),
+                           _ptr(box), C.byref(got))
+    if rc != PCP_OK:
+        raise PcpError(rc, L.pcp_last_error(None).decode())
+    f = got.value
+    return dict(label=label, ids=ids[:f].copy(), rows=rows[:f].copy(), box=box[:f].copy())
+
+
+def facet_plane_host(root, row) -> np.ndarray:
+    """The plane of one facet from its integers (pcp_facet_plane_host: host only, fp64): root = the coordinates of the facet's
+    id point (3 float32), row = its 10 integers -> (7,) float64, the columns FA_PLANE (centroid, unit normal with its largest
+    component positive, rms in metres)."""
+    L = load()
+    root = np.ascontiguousarray(root, np.float32).reshape(3)
+    row = np.ascontiguousarray(row, np.int64).reshape(10)
+    out = np.empty(7, np.float64)
+    rc = L.pcp_facet_plane_host(_ptr(root), _ptr(row), _ptr(out))
+    if rc != PCP_OK:
+        raise PcpError(rc, L.pcp_last_error(None).decode())
+    return out
+
+
 NO_POS = 0xFFFFFFFFFFFFFFFF  # pos of a point that is no crack point (DESIGN.md "Crack lengths on the map", CL5)
 CL_ROW = ("end_a", "end_b", "length_q", "hops", "path_sum_w", "path_min_w", "path_max_w")  # CL7: the columns of rows
 
@@ -1214,6 +1265,13 @@ class Context:
         self._check(self.lib.pcp_ortho_add(self.h, C.c_int64(index_base), C.byref(rows)))
         return rows.value
 
+    def ortho_add_facet(self, facet_id: int, index_base: int = 0) -> int:
+        """ortho_add restricted to the rows whose facet label (the last facets call) is facet_id: the colour and fused-label
+        layers are kept (pcp_ortho_add_facet).  Returns the number of contributors."""
+        rows = C.c_int64()
+        self._check(self.lib.pcp_ortho_add_facet(self.h, C.c_int32(facet_id), C.c_int64(index_base), C.byref(rows)))
+        return rows.value
+
     def ortho_add_packed(self, rgba, index_base: int = 0) -> int:
         """Adds the uploaded cloud with the caller's words r | g<<8 | b<<16 | has<<24 (n of them: a numpy array, or an int
         that is a device pointer of this context's GPU); the label is 0.  Returns the number of contributors."""
@@ -1309,6 +1367,34 @@ class Context:
         if normals:
             out["normal_cam"] = nrm
         return out
+
+    # -- planar facets ("Planar facets") -----------------------------------
+    def facets(self, link_radius: float = 0.1, angle_deg: float = 10.0, plane_tol: float = 0.01, max_curvature: float = 0.02,
+               min_points: int = 1000) -> dict:
+        """The planar facets of the uploaded cloud under the live normals (pcp_facets and its fetch): label (n,) int32, the
+        lowest input index of the point's facet, -1 for a point in none; ids (F,) int32 ascending; rows (F, 10) int64, the
+        columns FA_ROW; box (F, 6) float32: min xyz, max xyz; plus facet_points, components and facets (counts)."""
+        prm = FacetParams(link_radius, angle_deg, plane_tol, max_curvature, min_points)
+        label = np.empty(self.n, np.int32)
+        pts, comps, fac = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(self.lib.pcp_facets(self.h, C.byref(prm), _ptr(label), C.byref(pts), C.byref(comps), C.byref(fac)))
+        out = self.facets_fetch(0, fac.value)
+        assert len(out["ids"]) == fac.value, (len(out["ids"]), fac.value)
+        out.update(label=label, facet_points=pts.value, components=comps.value, facets=fac.value)
+        return out
+
+    def facets_fetch(self, first: int = 0, max_rows: int = 1 << 24) -> dict:
+        """Rows first .. first + max_rows - 1 of the last facets call's table (pcp_facets_fetch): dict(ids, rows, box)."""
+        have = C.c_int64()
+        self._check(self.lib.pcp_facets_fetch(self.h, C.c_int64(first), C.c_int64(max_rows), None, None, None, C.byref(have)))
+        rows = have.value
+        ids = np.empty(rows, np.int32)
+        tab = np.empty((rows, 10), np.int64)
+        box = np.empty((rows, 6), np.float32)
+        got = C.c_int64()
+        self._check(self.lib.pcp_facets_fetch(self.h, C.c_int64(first), C.c_int64(rows), _ptr(ids), _ptr(tab), _ptr(box), C.byref(got)))
+        assert got.value == rows, (got.value, rows)
+        return dict(ids=ids, rows=tab, box=box)
 
     # -- mask distance maps (DESIGN.md, "Mask distance maps") ------------------------
     def mask_edt(self, frame: int, threshold: int = 0, want_nearest: bool = True) -> dict:

@@ -209,6 +209,22 @@ struct OrthoMap {
 
 struct CrackMap;  // (the crack chain's header)
 
+// planar facets (pcp_facets.hip): the labels (n, input order; -1: in no facet) and the table of the last pcp_facets -- ids,
+// ten integers (points S1 S2) and the box as ordered integers per facet, ascending by id.  FA9: dropped by the next
+// pcp_facets, pcp_estimate_normals and the uploads.
+struct Facets {
+  bool live = false;
+  int64_t rows = 0;
+  DevBuf<int32_t> label, ids;
+  DevBuf<long long> table;
+  DevBuf<uint32_t> box;
+  void release() {
+    live = false;
+    rows = 0;
+    label.release(), ids.release(), table.release(), box.release();
+  }
+};
+
 // ---- the uniform grid of the radius searches (pcp_grid.hip; read by the MLS / SOR kernels and by the radius stages:
 // local colour smoothing, normals, the neighbour table of PCP_MATCH_RADIUS, pcp_close_pairs) ----------------------------
 constexpr double kMaxGridCells = 536870912.0;      // 2^29: dense table of cell starts
@@ -427,6 +443,8 @@ struct pcp_context {
   pcp::DevBuf<int32_t> gn_count;
   pcp::DevBuf<unsigned long long> gm_keys;
   pcp::DevBuf<uint32_t> gm_out;  // index | range | xyz_cam (3) | normal_cam (3), W*H words each
+  // planar facets of the map: made from the cloud and the normals above, and dropped with either
+  pcp::Facets facets;
 
   // mask distance maps (pcp_mask_edt.hip), for one chunk of keyframes, allocated on first use: the background bits of the
   // column segments, the column words, and the two result images
@@ -716,6 +734,7 @@ hipError_t preload_normals();
 hipError_t preload_mask_edt();
 hipError_t preload_ortho();
 hipError_t preload_ortho_texture();
+hipError_t preload_facets();
 // the device parts of pcp_mask_edt (one keyframe, with nearest) and pcp_frame_geometry under the caller's name: checks and
 // kernels, the results left in md_bits / md_d2 / md_nearest and gm_out / s_counter[0]; no copy, no synchronisation
 int mask_edt_device(pcp_context *ctx, const char *who, int32_t frame, int32_t threshold);

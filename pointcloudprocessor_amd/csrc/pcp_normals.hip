@@ -216,6 +216,7 @@ struct GnScratch {
 
 void normals_release(pcp_context *ctx) {
   ctx->gn_live = false;
+  ctx->facets.release();  // FA9: the facets are made from these normals
   ctx->gn_normal.release();
   ctx->gn_count.release();
 }
@@ -347,6 +348,7 @@ int pcp_estimate_normals(pcp_context *ctx, float radius, int64_t *out_valid, int
     return set_error(ctx, PCP_ERR_INVALID, "pcp_estimate_normals: radius %g outside [0.005, 1]", static_cast<double>(radius));
   if (!ctx->xyz.p && ctx->n > 0) return set_error(ctx, PCP_ERR_STATE, "pcp_estimate_normals: no cloud uploaded");
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->facets.release();  // FA9: a new estimate ends the facets of the old one
   if (ctx->n == 0) {
     ctx->gn_live = true;
     ctx->gn_radius = radius;

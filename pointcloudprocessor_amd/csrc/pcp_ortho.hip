@@ -11,6 +11,7 @@
 #include <new>
 #include <vector>
 
+#include "pcp_eigen33_host.hpp"
 #include "pcp_internal.hpp"
 #include "pcp_mask_edt.hpp"
 #include "pcp_ortho.hpp"
@@ -23,14 +24,20 @@ constexpr int64_t kOrMaxGrid = 4096;  // workgroups of the grid-stride passes
 enum { OR_CONTRIBUTORS = 0, OR_ATOMICS, OR_OCCUPIED, OR_FILLED, OR_SCALARS };
 
 // the contributor of lane j of the upload's spatial order (sxyz / perm: the uploaded coordinates; the packed word of the
-// input-order result): its pixel (-1: none), key, input row and word
+// input-order result): its pixel (-1: none), key, input row and word.  kFacet (pcp_ortho_add_facet): only the rows whose
+// facet label (input order) is facet_id contribute.
+template <bool kFacet>
 __device__ __forceinline__ int32_t or_contributor(int64_t j, int64_t n, const float *__restrict__ sx, const float *__restrict__ sy,
                                                   const float *__restrict__ sz, const int32_t *__restrict__ perm,
-                                                  const uint32_t *__restrict__ packed, const om::Frame &f, uint32_t index_base,
+                                                  const uint32_t *__restrict__ packed, [[maybe_unused]] const int32_t *__restrict__ facet,
+                                                  [[maybe_unused]] int32_t facet_id, const om::Frame &f, uint32_t index_base,
                                                   unsigned long long *key, int32_t *row, uint32_t *word) {
   *key = om::kEmptyKey;
   if (j >= n) return -1;
   const int32_t i = perm[j];
+  if constexpr (kFacet) {
+    if (facet[i] != facet_id) return -1;
+  }
   const uint32_t w = packed[i];
   if (!(w >> 24)) return -1;
   int32_t pixel;
@@ -46,9 +53,11 @@ __device__ __forceinline__ int32_t or_contributor(int64_t j, int64_t n, const fl
 // the run of the nearest lane below that has one (and brings the empty key, the minimum's identity); the smallest key of a run
 // of equal pixels is found by a segmented suffix minimum (six shuffle steps) and the run's first lane issues the one atomic.
 // (One atomic per contributor instead: the same add 0.71 -> 1.99 ms where 200 points share a pixel, profiles/ortho_probe.md.)
+template <bool kFacet>
 __global__ __launch_bounds__(kOrBlock) void k_or_scatter(int64_t n, const float *__restrict__ sx, const float *__restrict__ sy,
                                                          const float *__restrict__ sz, const int32_t *__restrict__ perm,
-                                                         const uint32_t *__restrict__ packed, om::Frame f, uint32_t index_base,
+                                                         const uint32_t *__restrict__ packed, const int32_t *__restrict__ facet,
+                                                         int32_t facet_id, om::Frame f, uint32_t index_base,
                                                          unsigned long long *__restrict__ keys, unsigned long long *__restrict__ scalars) {
   const int lane = static_cast<int>(threadIdx.x & 63u);
   uint32_t contributors = 0u, atomics = 0u;
@@ -56,7 +65,7 @@ __global__ __launch_bounds__(kOrBlock) void k_or_scatter(int64_t n, const float 
     unsigned long long key;
     int32_t row = 0;
     uint32_t word = 0u;
-    const int32_t pixel = or_contributor(base + threadIdx.x, n, sx, sy, sz, perm, packed, f, index_base, &key, &row, &word);
+    const int32_t pixel = or_contributor<kFacet>(base + threadIdx.x, n, sx, sy, sz, perm, packed, facet, facet_id, f, index_base, &key, &row, &word);
     contributors += pixel >= 0 ? 1u : 0u;
     const unsigned long long with = __ballot(pixel >= 0);
     if (!with) continue;  // (the same in every lane of the wavefront)
@@ -86,18 +95,19 @@ __global__ __launch_bounds__(kOrBlock) void k_or_scatter(int64_t n, const float 
 }
 
 // OM4.  The same contributors, after the scatter: the one whose key is its pixel's key stores the payload word.  No atomics.
-template <bool kLabel>
+template <bool kLabel, bool kFacet>
 __global__ __launch_bounds__(kOrBlock) void k_or_payload(int64_t n, const float *__restrict__ sx, const float *__restrict__ sy,
                                                          const float *__restrict__ sz, const int32_t *__restrict__ perm,
                                                          const uint32_t *__restrict__ packed,
-                                                         [[maybe_unused]] const uint32_t *__restrict__ labels, om::Frame f,
+                                                         [[maybe_unused]] const uint32_t *__restrict__ labels,
+                                                         const int32_t *__restrict__ facet, int32_t facet_id, om::Frame f,
                                                          uint32_t index_base, const unsigned long long *__restrict__ keys,
                                                          uint32_t *__restrict__ payload) {
   for (int64_t base = static_cast<int64_t>(blockIdx.x) * kOrBlock; base < n; base += static_cast<int64_t>(gridDim.x) * kOrBlock) {
     unsigned long long key;
     int32_t row = 0;
     uint32_t word = 0u;
-    const int32_t pixel = or_contributor(base + threadIdx.x, n, sx, sy, sz, perm, packed, f, index_base, &key, &row, &word);
+    const int32_t pixel = or_contributor<kFacet>(base + threadIdx.x, n, sx, sy, sz, perm, packed, facet, facet_id, f, index_base, &key, &row, &word);
     if (pixel < 0 || keys[pixel] != key) continue;
     uint32_t label = 0u;
     if constexpr (kLabel) label = labels[row] & 0xffu;
@@ -227,8 +237,11 @@ static void or_drop(pcp_context *ctx) {
   m.fill_radius = 0;
 }
 
-// the two passes of an add over the uploaded cloud with the words `packed` (device, input order) and `labels` (nullable)
-static int or_add_words(pcp_context *ctx, const uint32_t *packed, const uint32_t *labels, uint32_t index_base, int64_t *out_contributors) {
+// the two passes of an add over the uploaded cloud with the words `packed` (device, input order) and `labels` (nullable);
+// facet (nullable; device, input order): only the rows labelled facet_id
+template <bool kFacet>
+static int or_add_words(pcp_context *ctx, const uint32_t *packed, const uint32_t *labels, const int32_t *facet, int32_t facet_id,
+                        uint32_t index_base, int64_t *out_contributors) {
   OrthoMap &m = ctx->ortho;
   const int64_t n = ctx->n;
   const size_t plane = (static_cast<size_t>(n) + 3) & ~size_t(3);
@@ -237,18 +250,18 @@ static int or_add_words(pcp_context *ctx, const uint32_t *packed, const uint32_t
   PCP_HIP_TRY(ctx, hipMemsetAsync(m.scalars.p, 0, 2 * 8, ctx->stream));  // contributors, atomics
   {
     LaunchTimer t(ctx, PCP_K_MISC);
-    hipLaunchKernelGGL(k_or_scatter, dim3(or_blocks(n)), dim3(kOrBlock), 0, ctx->stream, n, sx, sy, sz, ctx->perm.p, packed, f,
-                       index_base, m.keys.p, m.scalars.p);
+    hipLaunchKernelGGL(k_or_scatter<kFacet>, dim3(or_blocks(n)), dim3(kOrBlock), 0, ctx->stream, n, sx, sy, sz, ctx->perm.p, packed, facet,
+                       facet_id, f, index_base, m.keys.p, m.scalars.p);
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
   {
     LaunchTimer t(ctx, PCP_K_MISC);
     if (labels)
-      hipLaunchKernelGGL(k_or_payload<true>, dim3(or_blocks(n)), dim3(kOrBlock), 0, ctx->stream, n, sx, sy, sz, ctx->perm.p, packed, labels,
-                         f, index_base, m.keys.p, m.payload.p);
+      hipLaunchKernelGGL((k_or_payload<true, kFacet>), dim3(or_blocks(n)), dim3(kOrBlock), 0, ctx->stream, n, sx, sy, sz, ctx->perm.p, packed,
+                         labels, facet, facet_id, f, index_base, m.keys.p, m.payload.p);
     else
-      hipLaunchKernelGGL(k_or_payload<false>, dim3(or_blocks(n)), dim3(kOrBlock), 0, ctx->stream, n, sx, sy, sz, ctx->perm.p, packed,
-                         static_cast<const uint32_t *>(nullptr), f, index_base, m.keys.p, m.payload.p);
+      hipLaunchKernelGGL((k_or_payload<false, kFacet>), dim3(or_blocks(n)), dim3(kOrBlock), 0, ctx->stream, n, sx, sy, sz, ctx->perm.p, packed,
+                         static_cast<const uint32_t *>(nullptr), facet, facet_id, f, index_base, m.keys.p, m.payload.p);
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
   unsigned long long h[2];
@@ -274,59 +287,10 @@ static int or_add_check(pcp_context *ctx, const char *who, int64_t index_base, b
   return PCP_OK;
 }
 
-// ---- pcp_ortho_fit_frame_host: the eigenpairs of a symmetric 3 x 3 matrix by pcp_eigen33.hpp's closed form, on the host ----
-static void or_roots2(double b, double c, double r[3]) {
-  double d = b * b - 4.0 * c;
-  if (d < 0.0) d = 0.0;
-  const double sd = std::sqrt(d);
-  r[0] = 0.0;
-  r[1] = 0.5 * (b - sd);
-  r[2] = 0.5 * (b + sd);
-}
-// m = xx xy xz yy yz zz scaled to a largest magnitude of 1: its roots ascending
-static void or_roots3(const double a[6], double r[3]) {
-  const double a00 = a[0], a01 = a[1], a02 = a[2], a11 = a[3], a12 = a[4], a22 = a[5];
-  const double c0 = a00 * a11 * a22 + 2.0 * a01 * a02 * a12 - a00 * a12 * a12 - a11 * a02 * a02 - a22 * a01 * a01;
-  const double c1 = a00 * a11 - a01 * a01 + a00 * a22 - a02 * a02 + a11 * a22 - a12 * a12;
-  const double c2 = a00 + a11 + a22;
-  if (std::fabs(c0) < DBL_EPSILON) return or_roots2(c2, c1, r);
-  const double inv3 = 1.0 / 3.0, sqrt3 = std::sqrt(3.0);
-  const double c2_3 = c2 * inv3;
-  double a_3 = (c1 - c2 * c2_3) * inv3;
-  if (a_3 > 0.0) a_3 = 0.0;
-  const double half_b = 0.5 * (c0 + c2_3 * (2.0 * c2_3 * c2_3 - c1));
-  double q = half_b * half_b + a_3 * a_3 * a_3;
-  if (q > 0.0) q = 0.0;
-  const double rho = std::sqrt(-a_3), theta = std::atan2(std::sqrt(-q), half_b) * inv3;
-  const double ct = std::cos(theta), st = std::sin(theta);
-  r[0] = c2_3 + 2.0 * rho * ct;
-  r[1] = c2_3 - rho * (ct + sqrt3 * st);
-  r[2] = c2_3 - rho * (ct - sqrt3 * st);
-  std::sort(r, r + 3);
-  if (r[0] <= 0.0) or_roots2(c2, c1, r);
-}
-// the unit eigenvector of root r: the longest cross product of two rows of (A - r I)
-static void or_eigenvector(const double a[6], double r, double v[3]) {
-  const double a01 = a[1], a02 = a[2], a12 = a[4];
-  const double s00 = a[0] - r, s11 = a[3] - r, s22 = a[5] - r;
-  const double k[3][3] = {{a01 * a12 - a02 * s11, a02 * a01 - s00 * a12, s00 * s11 - a01 * a01},
-                          {a01 * s22 - a02 * a12, a02 * a02 - s00 * s22, s00 * a12 - a01 * a02},
-                          {s11 * s22 - a12 * a12, a12 * a02 - a01 * s22, a01 * a12 - s11 * a02}};
-  int best = 0;
-  double len[3];
-  for (int i = 0; i < 3; ++i) {
-    len[i] = (k[i][0] * k[i][0] + k[i][1] * k[i][1]) + k[i][2] * k[i][2];
-    if (len[i] > len[best]) best = i;
-  }
-  const double inv = 1.0 / std::sqrt(len[best]);
-  for (int c = 0; c < 3; ++c) v[c] = k[best][c] * inv;
-}
-static int or_largest_component(const double v[3]) {
-  int b = 0;
-  for (int c = 1; c < 3; ++c)
-    if (std::fabs(v[c]) > std::fabs(v[b])) b = c;
-  return b;
-}
+// ---- pcp_ortho_fit_frame_host: the eigenpairs of a symmetric 3 x 3 matrix by pcp_eigen33_host.hpp's closed form ----
+static void or_roots3(const double a[6], double r[3]) { eig::roots3(a, r); }
+static void or_eigenvector(const double a[6], double r, double v[3]) { eig::eigenvector(a, r, v); }
+static int or_largest_component(const double v[3]) { return eig::largest_component(v); }
 
 }  // namespace pcp
 
@@ -366,10 +330,32 @@ int pcp_ortho_add(pcp_context *ctx, int64_t index_base, int64_t *out_contributor
   if (rc != PCP_OK) return rc;
   if (ctx->n > 0) {
     PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    rc = or_add_words(ctx, ctx->rgba2[ctx->rgba_cur].p, with_label ? ctx->labels.p : nullptr, static_cast<uint32_t>(index_base),
-                      out_contributors);
+    rc = or_add_words<false>(ctx, ctx->rgba2[ctx->rgba_cur].p, with_label ? ctx->labels.p : nullptr, nullptr, 0, static_cast<uint32_t>(index_base),
+                             out_contributors);
     if (rc != PCP_OK) return rc;
   }
+  m.labels_fixed = true;
+  m.with_label = with_label;
+  m.adds += 1;
+  return PCP_OK;
+}
+
+int pcp_ortho_add_facet(pcp_context *ctx, int32_t facet_id, int64_t index_base, int64_t *out_contributors) {
+  if (!ctx) return PCP_ERR_INVALID;
+  if (out_contributors) *out_contributors = 0;
+  OrthoMap &m = ctx->ortho;
+  const bool with_label = ctx->labels_live;
+  if (m.live && !m.finished && !ctx->colour_result_live)
+    return set_error(ctx, PCP_ERR_STATE, "pcp_ortho_add_facet: no colour result (call pcp_colorize / pcp_colorize_from_depth / pcp_colour_finalise)");
+  int rc = or_add_check(ctx, "pcp_ortho_add_facet", index_base, with_label);
+  if (rc != PCP_OK) return rc;
+  if (!ctx->facets.live) return set_error(ctx, PCP_ERR_STATE, "pcp_ortho_add_facet: no facets (pcp_facets on this cloud and these normals)");
+  if (facet_id < 0 || facet_id >= ctx->n)
+    return set_error(ctx, PCP_ERR_RANGE, "pcp_ortho_add_facet: facet %d outside 0 .. %lld", facet_id, static_cast<long long>(ctx->n) - 1);
+  PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  rc = or_add_words<true>(ctx, ctx->rgba2[ctx->rgba_cur].p, with_label ? ctx->labels.p : nullptr, ctx->facets.label.p, facet_id,
+                          static_cast<uint32_t>(index_base), out_contributors);
+  if (rc != PCP_OK) return rc;
   m.labels_fixed = true;
   m.with_label = with_label;
   m.adds += 1;
@@ -389,7 +375,7 @@ int pcp_ortho_add_packed(pcp_context *ctx, const uint32_t *rgba, int64_t index_b
     DevBuf<uint32_t> words;  // the caller's words (host or device memory)
     PCP_HIP_TRY(ctx, words.ensure(static_cast<size_t>(ctx->n) + 4));
     PCP_HIP_TRY(ctx, hipMemcpyAsync(words.p, rgba, static_cast<size_t>(ctx->n) * 4, hipMemcpyDefault, ctx->stream));
-    rc = or_add_words(ctx, words.p, nullptr, static_cast<uint32_t>(index_base), out_contributors);  // (synchronises: words may go)
+    rc = or_add_words<false>(ctx, words.p, nullptr, nullptr, 0, static_cast<uint32_t>(index_base), out_contributors);  // (synchronises: words may go)
     if (rc != PCP_OK) return rc;
   }
   m.labels_fixed = true;

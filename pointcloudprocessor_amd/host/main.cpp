@@ -196,6 +196,22 @@
 //     after the last chunk on the merged depth maps.  The other ortho files are byte for byte what they are without the flag.
 //     Refused: without --orthoMap 1, with --gpus N above 1 and with --cull hpr / hpr_candidates (no depth maps to test a
 //     surface point against); the three value flags without --orthoTexture are errors.
+//   * --facets 0|1 (new, default 0), --facetRadius r (new, default 0.1, 0.005..1), --facetAngle deg (new, default 10, 0..45),
+//     --facetPlaneTol m (new, default 0.01, 1e-4..0.1), --facetMaxCurvature c (new, default 0.02, 0..1), --facetMinPoints k (new,
+//     default 1000, 1..2^24), --facetMaxRms m (new, default 0.01) and --normalRadius as above (not 0): with 1 the run also
+//     partitions the map into the faces of the structure and writes <outputPath>facets/facet_label.npy (<i4, one per map point:
+//     the id of the point's facet -- the lowest row among its points -- or -1) and facets.json (per facet id, points, centroid,
+//     normal, rms, planar, box_min, box_max; numbers as %.9g).  Two points share a facet when a chain of links joins them: closer
+//     than r, normals within the angle, each within the plane tolerance of the other's tangent plane; a facet is planar when
+//     the rms distance of its points to its own plane is at most --facetMaxRms.  With --orthoMap 1 --orthoFrame facets the run
+//     writes one directory <outputPath>ortho/facet_<row>/ per planar facet (row: its place in facets.json), each holding what
+//     ortho/ holds otherwise, on a frame fitted to the facet's own points and drawn from the facet's own points only; there is
+//     no whole-map ortho/ortho_*.npy then (and no ortho_width / ortho_crack layer).  With --crackFuse 1 every crack of
+//     cracks_3d.json gains "facet", the most frequent facet id among its points (ties to the lowest id, -1 when none has
+//     one); without --facets 1 the file is byte for byte what it was.  Made on the GPU (pcp_facets, pcp_ortho_add_facet;
+//     DESIGN.md "Planar facets").  Refused: --gpus N above 1, --enableMLS 1, --streamColour 1, --normalRadius 0, and
+//     --orthoFrame facets without --facets 1.
+#include <algorithm>
 #include <cfloat>
 #include <chrono>
 #include <cmath>
@@ -205,6 +221,7 @@
 #include <fstream>
 #include <iostream>
 #include <malloc.h>
+#include <map>
 #include <memory>
 #include <sstream>
 #include <thread>
@@ -306,6 +323,10 @@ struct Options {
   bool ortho_texture_interp = true;   // --orthoTextureInterp: bilinear depth between map pixels
   float ortho_texture_step = 0.05f;   // --orthoTextureStep s: ... only across depth steps up to s metres
   bool ortho_texture_value_flag = false;  // one of the three value flags was given
+  bool facets = false;                // --facets 1: the planar facets of the map (facets/facet_label.npy, facets.json)
+  bool ortho_by_facet = false;        // --orthoFrame facets: one orthographic map per planar facet (ortho/facet_<row>/)
+  pcp_facet_params facet{0.1f, 10.0f, 0.01f, 0.02f, 1000};  // --facetRadius / --facetAngle / --facetPlaneTol / --facetMaxCurvature / --facetMinPoints
+  float facet_max_rms = 0.01f;        // --facetMaxRms m: a facet is planar up to this rms distance to its plane
 };
 
 static bool parse_bool(const std::string &v) {  // boost::program_options bool semantics
@@ -444,6 +465,38 @@ static Options parse(int argc, char **argv) {
         throw std::runtime_error("the argument ('" + v + "') for option '--normalRadius' is invalid (0 = no normals, or 0.005 <= r <= 1)");
       o.normal_radius = r;
     }
+    else if (a == "--facets") o.facets = parse_bool(next());
+    else if (a == "--facetRadius" || a == "--facetAngle" || a == "--facetPlaneTol" || a == "--facetMaxCurvature" || a == "--facetMaxRms") {
+      const std::string v = next();
+      char *end = nullptr;
+      const float r = std::strtof(v.c_str(), &end);
+      const bool parsed = end != v.c_str() && *end == '\0';
+      struct Rule {
+        const char *flag;
+        float *to;
+        float lo, hi;
+        bool lo_open;
+        const char *range;
+      } rules[] = {{"--facetRadius", &o.facet.link_radius, 0.005f, 1.0f, false, "0.005 <= r <= 1"},
+                   {"--facetAngle", &o.facet.angle_deg, 0.0f, 45.0f, true, "0 < degrees <= 45"},
+                   {"--facetPlaneTol", &o.facet.plane_tol, 1e-4f, 0.1f, false, "1e-4 <= metres <= 0.1"},
+                   {"--facetMaxCurvature", &o.facet.max_curvature, 0.0f, 1.0f, false, "0 <= c <= 1"},
+                   {"--facetMaxRms", &o.facet_max_rms, 0.0f, 1e6f, false, "metres, >= 0"}};
+      for (const Rule &k : rules) {
+        if (a != k.flag) continue;
+        if (!parsed || !(r >= k.lo && r <= k.hi) || (k.lo_open && r == k.lo))
+          throw std::runtime_error("the argument ('" + v + "') for option '" + a + "' is invalid (" + k.range + ")");
+        *k.to = r;
+      }
+    }
+    else if (a == "--facetMinPoints") {
+      const std::string v = next();
+      char *end = nullptr;
+      const long k = std::strtol(v.c_str(), &end, 10);
+      if (end == v.c_str() || *end != '\0' || k < 1 || k > (1L << 24))
+        throw std::runtime_error("the argument ('" + v + "') for option '--facetMinPoints' is invalid (1..16777216)");
+      o.facet.min_points = static_cast<int32_t>(k);
+    }
     else if (a == "--crackMaps") o.crack_maps = parse_bool(next());
     else if (a == "--crackThreshold") {
       const std::string v = next();
@@ -485,7 +538,8 @@ static Options parse(int argc, char **argv) {
     } else if (a == "--orthoFrame") {
       const std::string v = next();
       o.ortho_frame.clear();
-      if (v != "auto") {
+      o.ortho_by_facet = v == "facets";
+      if (v != "auto" && v != "facets") {
         std::istringstream is(v);
         std::string tok;
         bool ok = true;
@@ -496,7 +550,7 @@ static Options parse(int argc, char **argv) {
             ok = false;
           }
         if (!ok || o.ortho_frame.size() != 9)
-          throw std::runtime_error("the argument ('" + v + "') for option '--orthoFrame' is invalid (auto, or ox,oy,oz,ux,uy,uz,vx,vy,vz)");
+          throw std::runtime_error("the argument ('" + v + "') for option '--orthoFrame' is invalid (auto, facets, or ox,oy,oz,ux,uy,uz,vx,vy,vz)");
       }
     }
     else if (a == "--orthoTexture" || a == "--orthoTextureViews") {
@@ -628,6 +682,18 @@ static Options parse(int argc, char **argv) {
   if (o.geometry_maps && o.enableMLS)
     throw std::runtime_error("the option '--geometryMaps 1' does not work with '--enableMLS 1' (the maps are rendered from the raw "
                              "map; maps of the smoothed cloud are not built)");
+  if (o.ortho_by_facet && !o.facets)
+    throw std::runtime_error("the option '--orthoFrame facets' needs the facets of the map (--facets 1)");
+  if (o.facets && o.gpus > 1)
+    throw std::runtime_error("the option '--facets 1' does not work with '--gpus N' above 1 (an index shard sees only its own "
+                             "points: the forests of the shards would have to be united across GPUs, which is not built)");
+  if (o.facets && o.stream_colour)
+    throw std::runtime_error("the option '--facets 1' does not work with '--streamColour 1' (a facet's points may lie in another chunk)");
+  if (o.facets && o.enableMLS)
+    throw std::runtime_error("the option '--facets 1' does not work with '--enableMLS 1' (the facets are those of the raw map; "
+                             "facets of the smoothed cloud are not built)");
+  if (o.facets && o.normal_radius == 0.0f)
+    throw std::runtime_error("the option '--facets 1' needs the map normals ('--normalRadius 0' turns them off)");
   if (!o.balance_images && !o.balance_value_flag.empty())
     throw std::runtime_error("the option '" + o.balance_value_flag + "' needs '--balanceImages 1'");
   if (o.balance_exposure) {
@@ -693,12 +759,19 @@ static void usage(std::ostream &os) {
         "  --orthoMap arg (=0)                   Also write one orthographic picture of the coloured cloud as .npy (--gpus 1)\n"
         "  --orthoGsd arg (=0.01)                With --orthoMap: metres per pixel (1e-4..1)\n"
         "  --orthoFill arg (=0)                  With --orthoMap: fill empty pixels from the nearest occupied one within R pixels\n"
-        "  --orthoFrame arg (=auto)              With --orthoMap: auto (fitted plane), or ox,oy,oz,ux,uy,uz,vx,vy,vz\n"
+        "  --orthoFrame arg (=auto)              With --orthoMap: auto (fitted plane), facets (one map per planar facet), or ox,oy,oz,ux,uy,uz,vx,vy,vz\n"
         "  --orthoTexture arg (=0)               With --orthoMap: also the orthophoto, k fine pixels per pixel, from the keyframe images (1..16)\n"
         "  --orthoTextureViews arg (=1)          With --orthoTexture: views that enter a colour (1 = sharpest, 5 = the reference's mean)\n"
         "  --orthoTextureInterp arg (=1)         With --orthoTexture: bilinear depth between map pixels\n"
         "  --orthoTextureStep arg (=0.05)        With --orthoTexture: ... across depth steps up to this many metres\n"
-        "  --crackSkeletonStep arg (=0)          With --crackSkeleton: the band width in metres (0: twice the link radius)\n";
+        "  --crackSkeletonStep arg (=0)          With --crackSkeleton: the band width in metres (0: twice the link radius)\n"
+        "  --facets arg (=0)                     Also write the planar facets of the map: a label per point and one record per facet (--gpus 1)\n"
+        "  --facetRadius arg (=0.1)              With --facets: points this close (m) may be linked (0.005..1)\n"
+        "  --facetAngle arg (=10)                With --facets: ... when their normals differ by at most this many degrees (0..45)\n"
+        "  --facetPlaneTol arg (=0.01)           With --facets: ... and each lies this close (m) to the other's tangent plane (1e-4..0.1)\n"
+        "  --facetMaxCurvature arg (=0.02)       With --facets: points of a larger curvature take no part (0..1)\n"
+        "  --facetMinPoints arg (=1000)          With --facets: a facet has at least this many points\n"
+        "  --facetMaxRms arg (=0.01)             With --facets: a facet is planar up to this rms distance (m) to its plane\n";
 }
 
 class Processor {
@@ -755,6 +828,7 @@ class Processor {
   pcp_mls_params mls_params{};  // --streamColour 1: the chain's parameters, kept for streamedColourisation
   std::vector<float> ortho_fit_xyz;    // --orthoMap 1 with --enableMLS 1 (one-shot): the crop the chain smoothed, for the frame
   std::vector<uint32_t> ortho_index;   // --orthoMap 1: the index layer, for the crack layers --crackFuse 1 adds
+  Facets facets_;                      // --facets 1: the partition, for the per-facet maps and the cracks' "facet"
   pcp_ortho_frame ortho_frame_used{};
 
   void loadImagesAndOdometry() {  // :965-1005
@@ -1489,6 +1563,21 @@ class Processor {
     writeNpy(stem + "map_width_best.npy", "<f4", {n}, m.width_best.data(), n * 4);
     writeNpy(stem + "map_views.npy", "<u4", {n}, m.views.data(), n * 4);
     writeNpy(stem + "map_crack.npy", "<i4", {n}, m.label.data(), n * 4);
+    // --facets 1: the most frequent facet id among a crack's points, ties to the lowest id, -1 when none has one
+    std::vector<int32_t> crack_facet(m.ids.size(), -1);
+    if (opt.facets) {
+      std::vector<std::map<int32_t, int64_t>> votes(m.ids.size());
+      for (size_t i = 0; i < n; ++i) {
+        if (m.label[i] < 0 || facets_.label[i] < 0) continue;
+        const size_t r = static_cast<size_t>(std::lower_bound(m.ids.begin(), m.ids.end(), m.label[i]) - m.ids.begin());
+        votes[r][facets_.label[i]] += 1;
+      }
+      for (size_t r = 0; r < votes.size(); ++r) {
+        int64_t most = 0;
+        for (const auto &kv : votes[r])  // (ascending ids: a tie keeps the lowest)
+          if (kv.second > most) most = kv.second, crack_facet[r] = kv.first;
+      }
+    }
     std::ofstream f(stem + "cracks_3d.json");
     auto num = [](double v) {
       char b[64];
@@ -1504,7 +1593,9 @@ class Processor {
         << ", \"width_mean_mm\": " << num(static_cast<double>(st[1]) / static_cast<double>(st[0]) * mm)
         << ", \"width_min_mm\": " << num(static_cast<double>(st[2]) * mm) << ", \"width_max_mm\": " << num(static_cast<double>(st[3]) * mm)
         << ", \"box_min\": [" << num(bx[0]) << ", " << num(bx[1]) << ", " << num(bx[2]) << "], \"box_max\": [" << num(bx[3]) << ", "
-        << num(bx[4]) << ", " << num(bx[5]) << "]}";
+        << num(bx[4]) << ", " << num(bx[5]) << "]";
+      if (opt.facets) f << ", \"facet\": " << crack_facet[r];
+      f << "}";
     }
     f << "\n]\n";
     f.close();
@@ -1513,7 +1604,7 @@ class Processor {
               << " credited samples, " << m.crack_points << " crack points, " << m.ids.size() << " cracks" << std::endl;
     if (opt.crack_length) writeCrackLengths(cl, stem);
     if (opt.crack_skeleton) writeCrackSkeleton(sk, m, stem);
-    if (opt.ortho_map) {  // the widths and the cracks drawn on the orthographic map: map_width[index], map_crack[index]
+    if (opt.ortho_map && !opt.ortho_by_facet) {  // the widths and the cracks drawn on the orthographic map: map_width[index], map_crack[index]
       const size_t h = static_cast<size_t>(ortho_frame_used.height), w = static_cast<size_t>(ortho_frame_used.width);
       std::vector<float> width(ortho_index.size(), 0.0f);
       std::vector<int32_t> crack(ortho_index.size(), -1);
@@ -1530,6 +1621,83 @@ class Processor {
       writeNpy(opt.outputPath + "ortho/ortho_crack.npy", "<i4", {h, w}, crack.data(), crack.size() * 4);
       std::cout << "Orthographic crack layers saved to: " << opt.outputPath << "ortho/ortho_width.npy, ortho_crack.npy" << std::endl;
     }
+  }
+
+  // --facets 1: the faces of the structure (DESIGN.md "Planar facets"): the map normals, the partition, the planes from the integers
+  void writeFacets() {
+    Device &dev = gpu->device(0);
+    {
+      Phase ph("facets_gpu_s");
+      const int64_t valid = dev.estimateNormals(opt.normal_radius);
+      std::cout << "map normals: radius " << opt.normal_radius << ", " << valid << " of " << cloud.size() << " points valid" << std::endl;
+      facets_ = dev.facets(opt.facet);
+    }
+    Phase ph_w("facets_write_s");
+    facets_.planes([&](int32_t id, int a) { const size_t i = static_cast<size_t>(id); return a == 0 ? cloud.x[i] : a == 1 ? cloud.y[i] : cloud.z[i]; },
+                   static_cast<double>(opt.facet_max_rms));
+    const std::string stem = opt.outputPath + "facets/";
+    fs::create_directories(fs::path(stem));
+    writeNpy(stem + "facet_label.npy", "<i4", {cloud.size()}, facets_.label.data(), cloud.size() * 4);
+    std::ofstream f(stem + "facets.json");
+    auto num = [](double v) {
+      char b[64];
+      std::snprintf(b, sizeof(b), "%.9g", v);
+      return std::string(b);
+    };
+    size_t planar = 0;
+    f << "[";
+    for (size_t r = 0; r < facets_.ids.size(); ++r) {
+      const double *pl = facets_.plane.data() + 7 * r;
+      const float *bx = facets_.box.data() + 6 * r;
+      planar += facets_.planar[r];
+      f << (r ? ",\n " : "\n ") << "{\"id\": " << facets_.ids[r] << ", \"points\": " << facets_.rows[10 * r] << ", \"centroid\": [" << num(pl[0]) << ", "
+        << num(pl[1]) << ", " << num(pl[2]) << "], \"normal\": [" << num(pl[3]) << ", " << num(pl[4]) << ", " << num(pl[5]) << "], \"rms\": "
+        << num(pl[6]) << ", \"planar\": " << (facets_.planar[r] ? "true" : "false") << ", \"box_min\": [" << num(bx[0]) << ", " << num(bx[1]) << ", "
+        << num(bx[2]) << "], \"box_max\": [" << num(bx[3]) << ", " << num(bx[4]) << ", " << num(bx[5]) << "]}";
+    }
+    f << "\n]\n";
+    f.close();
+    if (!f) throw std::runtime_error("Couldn't save the facets of the map.");
+    std::cout << "Facets saved to: " << stem << "facet_label.npy and facets.json, " << facets_.facet_points << " facet points, " << facets_.components
+              << " components, " << facets_.ids.size() << " facets, " << planar << " planar" << std::endl;
+  }
+
+  // --orthoMap 1 --orthoFrame facets: one map per planar facet, on a frame fitted to the facet's own points (seen from the mean
+  // keyframe position) and drawn from those points only, into <out>ortho/facet_<row>/
+  void writeOrthoMapsByFacet() {
+    Device &dev = gpu->device(0);
+    const size_t n = cloud.size();
+    std::vector<float> xyz(3 * n);
+    for (size_t i = 0; i < n; ++i) {
+      xyz[3 * i] = cloud.x[i];
+      xyz[3 * i + 1] = cloud.y[i];
+      xyz[3 * i + 2] = cloud.z[i];
+    }
+    double viewer[3] = {0.0, 0.0, 0.0};
+    for (const Frame &k : keyframes) {
+      viewer[0] += k.pose.x / static_cast<double>(keyframes.size());
+      viewer[1] += k.pose.y / static_cast<double>(keyframes.size());
+      viewer[2] += k.pose.z / static_cast<double>(keyframes.size());
+    }
+    std::vector<uint8_t> member(n);
+    size_t maps = 0;
+    for (size_t r = 0; r < facets_.ids.size(); ++r) {
+      if (!facets_.planar[r]) continue;
+      const int32_t id = facets_.ids[r];
+      {
+        Phase ph("ortho_frame_s");
+        for (size_t i = 0; i < n; ++i) member[i] = facets_.label[i] == id ? 1 : 0;
+        ortho_frame_used = Device::orthoFitFrame(static_cast<int64_t>(n), xyz.data(), member.data(), keyframes.empty() ? nullptr : viewer, opt.ortho_gsd);
+      }
+      {
+        Phase ph("ortho_gpu_s");
+        dev.orthoBegin(ortho_frame_used);
+        (void)dev.orthoAddFacet(id, 0);
+      }
+      writeOrthoFiles(opt.outputPath + "ortho/facet_" + std::to_string(r) + "/");
+      ++maps;
+    }
+    std::cout << "Orthographic maps by facet: " << maps << " planar facets of " << facets_.ids.size() << std::endl;
   }
 
   // --orthoMap 1: the frame.  auto: the plane fitted to the finite points of the map the run read, seen from the side of the
@@ -1592,7 +1760,8 @@ class Processor {
     writeOrthoFiles();
   }
   // the map begun on the colour context, finished with --orthoFill, as <out>ortho/ortho_*.npy and ortho_frame.json; then dropped
-  void writeOrthoFiles() {
+  void writeOrthoFiles(const std::string &stem_in = std::string()) {
+    const std::string stem = stem_in.empty() ? opt.outputPath + "ortho/" : stem_in;
     Device &dev = gpu->device(0);
     OrthoMap m;
     {
@@ -1605,10 +1774,9 @@ class Processor {
         Device &d;
         ~End() { (void)pcp_ortho_end(d.get()); }
       } end{dev};
-      writeOrthoPhoto(dev, m.frame);
+      writeOrthoPhoto(dev, m.frame, stem);
     }
     Phase ph_w("ortho_write_s");
-    const std::string stem = opt.outputPath + "ortho/";
     fs::create_directories(fs::path(stem));
     const size_t h = static_cast<size_t>(m.frame.height), w = static_cast<size_t>(m.frame.width);
     writeNpy(stem + "ortho_rgb.npy", "|u1", {h, w, 3}, m.rgb.data(), m.rgb.size());
@@ -1636,9 +1804,8 @@ class Processor {
 
   // --orthoTexture k: the orthophoto of the finished map on `dev`, as <out>ortho/ortho_photo_*.npy and ortho_photo.json.  One call
   // of at most 2^28 fine pixels covers a band of whole map rows; the bands' rows are appended to the files in order.
-  void writeOrthoPhoto(Device &dev, const pcp_ortho_frame &frame) {
+  void writeOrthoPhoto(Device &dev, const pcp_ortho_frame &frame, const std::string &stem) {
     Phase ph("ortho_texture_s");
-    const std::string stem = opt.outputPath + "ortho/";
     fs::create_directories(fs::path(stem));
     const int64_t k = opt.ortho_texture, W = frame.width, H = frame.height;
     const size_t fh = static_cast<size_t>(H * k), fw = static_cast<size_t>(W * k);
@@ -1838,7 +2005,8 @@ class Processor {
         dev.check(pcp_colour_smooth_local(dev.get(), opt.smooth_colors_radius, &coloured));
       }
       reduceToVoxels();
-      if (opt.ortho_map) writeOrthoMap();
+      if (opt.facets) writeFacets();
+      if (opt.ortho_map) opt.ortho_by_facet ? writeOrthoMapsByFacet() : writeOrthoMap();
       if (opt.crack_fuse) writeCrackFuse();
       return;
     }
@@ -1854,7 +2022,8 @@ class Processor {
       gpu->smoothColorsWithLocalRegion(opt.smooth_colors_radius, rgb, has);
     }
     if (opt.output_leaf > 0.0f) reduceToVoxels();  // (of the colour result as it lies on the device now)
-    if (opt.ortho_map) writeOrthoMap();             // (likewise; before --crackFuse, whose layers it gathers by the index layer)
+    if (opt.facets) writeFacets();                  // (it reads the raw map; the colour result stays as it is)
+    if (opt.ortho_map) opt.ortho_by_facet ? writeOrthoMapsByFacet() : writeOrthoMap();  // (likewise; before --crackFuse, whose layers it gathers by the index layer)
     if (opt.crack_fuse) writeCrackFuse();           // (it reads the raw map and the masks; the colour result stays as it is)
     std::vector<uint8_t> label;
     if (opt.fuse_masks) {

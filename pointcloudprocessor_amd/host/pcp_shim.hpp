@@ -88,6 +88,30 @@ struct CrackWidth {
 
 // The crack widths of a set of keyframes on the map, and the map's cracks (pcp_hip.h, "crack widths on the map"): per map
 // point in input order, and one row per crack, ascending by id
+// planar facets of the map (Device::facets; DESIGN.md, "Planar facets"): one row per face of the structure
+struct Facets {
+  int64_t facet_points = 0, components = 0;
+  std::vector<int32_t> label;   // per map point: the facet's id (the lowest input index of its points), -1: in no facet
+  std::vector<int32_t> ids;     // ascending
+  std::vector<int64_t> rows;    // 10 per facet: points, S1 x y z, S2 xx xy xz yy yz zz of rint((p - p_id) * 2^12)
+  std::vector<float> box;       // 6 per facet: min x y z, max x y z
+  std::vector<double> plane;    // 7 per facet: centroid, unit normal, rms in metres (filled by planes())
+  std::vector<uint8_t> planar;  // per facet: rms <= max_rms and a normal that exists
+  // the planes from the integers (pcp_facet_plane_host); root(id, a) = coordinate a of map point id
+  template <typename Root>
+  void planes(Root root, double max_rms) {
+    plane.assign(7 * ids.size(), 0.0);
+    planar.assign(ids.size(), 0);
+    for (size_t r = 0; r < ids.size(); ++r) {
+      const float at[3] = {root(ids[r], 0), root(ids[r], 1), root(ids[r], 2)};
+      if (pcp_facet_plane_host(at, rows.data() + 10 * r, plane.data() + 7 * r) != PCP_OK)
+        throw std::runtime_error(std::string("pcp_hip: ") + pcp_last_error(nullptr));
+      const double *pl = plane.data() + 7 * r;
+      planar[r] = pl[6] <= max_rms && (pl[3] != 0.0 || pl[4] != 0.0 || pl[5] != 0.0) ? 1 : 0;
+    }
+  }
+};
+
 struct CrackMap {
   int64_t contributors = 0, credited = 0;  // summed over the added keyframes
   int64_t crack_points = 0;
@@ -266,6 +290,11 @@ class Device {
     check(pcp_ortho_add(ctx_, index_base, &rows));
     return rows;
   }
+  int64_t orthoAddFacet(int32_t facet_id, int64_t index_base = 0) {  // orthoAdd restricted to the rows of one facet of the last facets()
+    int64_t rows = 0;
+    check(pcp_ortho_add_facet(ctx_, facet_id, index_base, &rows));
+    return rows;
+  }
   int64_t orthoAddPacked(const uint32_t *rgba, int64_t index_base = 0) {  // cloudSize() words r | g<<8 | b<<16 | has<<24
     int64_t rows = 0;
     check(pcp_ortho_add_packed(ctx_, rgba, index_base, &rows));
@@ -335,6 +364,20 @@ class Device {
     int64_t valid = 0;
     check(pcp_estimate_normals(ctx_, radius, &valid, nullptr));
     return valid;
+  }
+
+  // ---- planar facets: the faces of the uploaded map under the live normals (pcp_facets and its fetch); needs estimateNormals
+  Facets facets(const pcp_facet_params &p) {
+    Facets f;
+    f.label.resize(static_cast<size_t>(cloudSize()));
+    int64_t rows = 0, got = 0;
+    check(pcp_facets(ctx_, &p, f.label.data(), &f.facet_points, &f.components, &rows));
+    f.ids.resize(static_cast<size_t>(rows));
+    f.rows.resize(10 * static_cast<size_t>(rows));
+    f.box.resize(6 * static_cast<size_t>(rows));
+    check(pcp_facets_fetch(ctx_, 0, rows, f.ids.data(), f.rows.data(), f.box.data(), &got));
+    if (got != rows) throw std::runtime_error("pcp_hip: pcp_facets_fetch returned " + std::to_string(got) + " of " + std::to_string(rows) + " rows");
+    return f;
   }
 
   // ---- mask distance maps: the squared Euclidean distance transform of the uploaded masks of keyframes first .. first +

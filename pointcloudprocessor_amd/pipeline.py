@@ -56,6 +56,10 @@ class HipEngine:
         """balance: the keyframe colour balance of the images uploaded from now on (capi.Context.set_image_balance: True for
         the defaults, a dict of capi.balance_params()'s arguments, None for off); "keep" leaves the context's setting."""
         self.ctx.set_frames(poses, T_opt)
+        import numpy as np
+
+        pos = np.asarray(poses, np.float64).reshape(-1, 7)[:, :3]
+        self.mean_keyframe_position = pos.mean(axis=0) if len(pos) else None  # (the viewer of ortho_maps_by_facet's frames)
         if not (isinstance(balance, str) and balance == "keep"):
             self.ctx.set_image_balance(balance)
         if images is not None:
@@ -228,6 +232,83 @@ class PointCloudColorizer:
         if crack_map is not None:
             out.update(ortho_crack_layers(out["index"], crack_map["width_mean"], crack_map["label"]))
         return out
+
+    def facets(self, xyz=None, normal_radius: float = 0.1, link_radius: float = 0.1, angle_deg: float = 10.0, plane_tol: float = 0.01,
+               max_curvature: float = 0.02, min_points: int = 1000, max_rms: float = 0.01) -> dict:
+        """The planar facets of the uploaded map ("Planar facets"): the connected components of the map points
+        under a link of distance, normal angle and mutual plane distance, one per face of the structure.  The normals are
+        estimated at normal_radius when none of that radius are live.  dict of capi.Context.facets (label, ids, rows, box,
+        facet_points, components, facets) plus, per facet, plane (F, 7) float64 -- the columns capi.FA_PLANE: centroid, unit
+        normal, rms in metres, from capi.facet_plane_host -- and planar (F,) bool: rms <= max_rms and a normal that exists.
+        The global test is what stops chaining: a facet that runs round a curved surface has a large rms and is flagged.
+
+        xyz: the uploaded map as the caller holds it, (n, 3) or (x, y, z) -- a facet's integers are relative to its root point,
+        whose coordinates are read from it; nothing of it is kept here.
+
+        An index shard sees only its own points, so world > 1 raises ValueError.  (The forests of the shards would have to be
+        united across the cells that two ranks share; not built.)"""
+        import numpy as np
+
+        if self.world > 1:
+            raise ValueError("facets: an index shard sees only its own points; the union-find forests of the shards would have "
+                             "to be united across ranks, which is not built: run it on one rank holding the whole map")
+        ctx = self.engine.ctx
+        xyz = _rows_xyz("facets", xyz, ctx.n) if xyz is not None else None
+        if xyz is None:
+            raise ValueError("facets: the planes are taken about each facet's root point: pass the uploaded map as xyz")
+        if ctx.normals_radius != normal_radius:  # (None after an upload: the library dropped the estimate)
+            ctx.estimate_normals(normal_radius)
+        out = ctx.facets(link_radius, angle_deg, plane_tol, max_curvature, min_points)
+        plane = np.zeros((len(out["ids"]), 7), np.float64)
+        for r, (fid, row) in enumerate(zip(out["ids"], out["rows"])):
+            plane[r] = capi.facet_plane_host(xyz[fid], row)
+        out["plane"] = plane
+        out["planar"] = (plane[:, 6] <= max_rms) & (np.abs(plane[:, 3:6]).max(axis=1, initial=0.0) > 0) if len(plane) else np.zeros(0, bool)
+        self.last_facets = out
+        return out
+
+    def ortho_maps_by_facet(self, gsd: float, xyz=None, facets: dict | None = None, fill_radius: int = 0, viewer=None,
+                            texture: dict | None = None) -> list:
+        """One orthographic map per planar facet of the colour result run() left on the device: for every planar row of
+        `facets` (the dict facets() returned; None: the one its last call on this object left) a frame fitted on the host to
+        the facet's points (capi.ortho_fit_frame_host with has = (label == id)) at `gsd` metres per pixel, seen from `viewer`
+        (None: the mean keyframe position), then begin / ortho_add_facet / finish / fetch / end.  Only the facet's own rows
+        are drawn: a wall that crosses the frame's window does not show as a line.  A list, in the table's order, of the
+        dicts ortho_map returns, each with facet (its id) and row (its row of the table).  texture: as ortho_map's.
+
+        An index shard sees only its own points, so world > 1 raises ValueError."""
+        import numpy as np
+
+        if self.world > 1:
+            raise ValueError("ortho_maps_by_facet: an index shard sees only its own points; the per-pixel keys of the shards "
+                             "would have to be merged across ranks (all-reduce MIN), which is not built: run it on one rank "
+                             "holding the whole map")
+        texture = ortho_texture_request("ortho_maps_by_facet", texture)
+        ctx = self.engine.ctx
+        facets = getattr(self, "last_facets", None) if facets is None else facets
+        if facets is None or len(facets["label"]) != ctx.n:
+            raise ValueError("ortho_maps_by_facet: no facets of this cloud (call facets() first)")
+        xyz = _rows_xyz("ortho_maps_by_facet", xyz, ctx.n)
+        if viewer is None:
+            viewer = getattr(self.engine, "mean_keyframe_position", None)
+        fuse_labels = bool(getattr(self.engine, "fuse_labels", False))
+        maps = []
+        for row in np.flatnonzero(facets["planar"]):
+            fid = int(facets["ids"][row])
+            frame = capi.ortho_fit_frame_host(xyz, gsd, has=(facets["label"] == fid).astype(np.uint8), viewer=viewer)
+            ctx.ortho_begin(frame)
+            try:
+                contributors = ctx.ortho_add_facet(fid, 0)
+                occupied, filled = ctx.ortho_finish(fill_radius)
+                out = ctx.ortho_fetch(want_label=fuse_labels)
+                if texture is not None:
+                    out["photo"] = ctx.ortho_texture(**texture)
+            finally:
+                ctx.ortho_end()
+            out.update(frame=capi.ortho_frame(frame).as_dict(), contributors=contributors, occupied=occupied, filled=filled, facet=fid,
+                       row=int(row))
+            maps.append(out)
+        return maps
 
     def geometry_maps(self, frame: int, normal_radius: float = 0.1) -> dict:
         """The geometry maps of one keyframe at camera resolution, reduced on the device ("Geometry maps"):
