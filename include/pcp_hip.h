@@ -1259,6 +1259,13 @@ int pcp_tile_mask_density(pcp_context *ctx, double *kept_fraction);
 /* diagnostic: the (tile, keyframe) masks themselves, tiles x mask_words uint32 (bit f & 31 of word f >> 5); either
  * output may be NULL to query the sizes */
 int pcp_tile_masks(pcp_context *ctx, int64_t *tiles, int32_t *mask_words, uint32_t *out_words);
+/* diagnostic: the order of the uploaded cloud, out_perm[j] = the input index of the point at sorted place j (n int32; a tile is
+ * the 64 consecutive places 64 t .. 64 t + 63, a group 16 consecutive tiles).  Synchronises and copies. */
+int pcp_cloud_order(pcp_context *ctx, int32_t *out_perm);
+/* diagnostic: the bounds the tile masks are built from, 8 floats per bound: centre x y z and radius of the bounding sphere, then
+ * the half-extents hx hy hz of the world-axis box about the same centre and a zero.  *tiles bounds of tiles come first, the
+ * (*tiles + 15) / 16 bounds of the groups behind them; either output may be NULL to query the size.  Synchronises and copies. */
+int pcp_tile_bounds(pcp_context *ctx, int64_t *tiles, float *out8);
 /* diagnostic: share of the points of the last pcp_sor / pcp_cloud_smooth SOR pass that the selection kernel handed
  * to the heap kernel (fewer than mean_k + 1 neighbours within one grid cell, or a crowded boundary bin) */
 int pcp_sor_redo_fraction(pcp_context *ctx, double *fraction);

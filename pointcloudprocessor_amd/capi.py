@@ -1811,5 +1811,20 @@ class Context:
         self._check(self.lib.pcp_tile_masks(self.h, None, None, _ptr(out)))
         return out
 
+    def cloud_order(self) -> np.ndarray:
+        """(n,) int32: the input index of the point at every sorted place (tile t = places 64 t .. 64 t + 63)."""
+        out = np.empty(int(self.lib.pcp_cloud_size(self.h)), np.int32)
+        self._check(self.lib.pcp_cloud_order(self.h, _ptr(out)))
+        return out
+
+    def tile_bounds(self) -> tuple[np.ndarray, np.ndarray]:
+        """(tiles, 8) and (groups, 8) float32: centre, radius, half-extents, 0 of every tile and of every group of 16 tiles."""
+        t = C.c_int64()
+        self._check(self.lib.pcp_tile_bounds(self.h, C.byref(t), None))
+        groups = (t.value + 15) // 16
+        out = np.empty((t.value + groups, 8), np.float32)
+        self._check(self.lib.pcp_tile_bounds(self.h, None, _ptr(out)))
+        return out[:t.value], out[t.value:]
+
     def kernel_name(self, kernel_id: int) -> str:
         return self.lib.pcp_kernel_name(C.c_int32(kernel_id)).decode()

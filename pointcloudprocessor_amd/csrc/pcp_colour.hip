@@ -128,10 +128,10 @@ __global__ __launch_bounds__(kBlock) void k_project_frame(const float *__restric
 
 // ---------------------------------------------------------------------------
 // K0: tile x keyframe visibility masks.  A tile is 64 consecutive Morton-ordered
-// points = one wavefront of the batched kernels; its bounding sphere is computed
-// at upload.  Bit f of tile_mask[tile][f >> 5] is CLEARED only when every point of
-// the tile is certain to be rejected by the reference in keyframe f: tile_classify
-// (pcp_tile_classify.hpp) proves it; anything else keeps the bit.
+// points = one wavefront of the batched kernels; its bounds (sphere and box, two
+// float4) are computed at upload.  Bit f of tile_mask[tile][f >> 5] is CLEARED only
+// when every point of the tile is certain to be rejected by the reference in keyframe
+// f: tile_classify_box (pcp_tile_classify.hpp) proves it; anything else keeps the bit.
 // ---------------------------------------------------------------------------
 // Two launches: first the spheres of groups of 16 tiles against every keyframe, then the tiles, which only test
 // keyframes their group survived -- most groups are rejected as a whole.
@@ -140,7 +140,7 @@ constexpr int kTileGroup = 16;
 // Group level, flat form: one lane per (group, keyframe); the 32 lanes of a half wavefront are the bits of one mask
 // word, gathered by a ballot.  (A lane per (group, word) gives 1 224 wavefronts at C3, each looping over
 // 32 keyframes: barely more than one wavefront per SIMD, 48 us of pure latency; this form has 32 times the lanes.)
-__global__ __launch_bounds__(kBlock) void k_group_mask_flat(const float4 *__restrict__ spheres, int64_t groups, DevCamera cam,
+__global__ __launch_bounds__(kBlock) void k_group_mask_flat(const float4 *__restrict__ bounds, int64_t groups, DevCamera cam,
                                                             const DevFrame *__restrict__ frames, int32_t n_frames,
                                                             int32_t w0, int32_t w1, int32_t words,
                                                             uint32_t *__restrict__ group_mask,
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(kBlock) void k_group_mask_flat(const float4 *__rest
   const int32_t w = w0 + static_cast<int32_t>(gw - group * nw);
   const int32_t f = (w << 5) + static_cast<int32_t>(idx & 31);
   int cls = 1;
-  if (live && f < n_frames) cls = cull_enabled ? tile_classify(cam, frames[f], spheres[group]) : 0;
+  if (live && f < n_frames) cls = cull_enabled ? tile_classify_box(cam, frames[f], bounds[2 * group], bounds[2 * group + 1]) : 0;
   // a group that images wholly inside the acceptance box (and in front of the camera): none of its tiles can be rejected
   // -- a tile's interval image contains the images of its points, which lie in the box -- so the tile level has nothing to
   // decide for that pair
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(kBlock) void k_group_mask_flat(const float4 *__rest
 // kInside = false: nobody reads the tiles' `inside` words (their one reader, the depth pass, runs without its rejection test in the
 // common configuration): inside_mask is null, and the second ballot and its bit assembly per round are not compiled in.
 template <bool kInside>
-__global__ __launch_bounds__(kBlock) void k_tile_mask_dense(const float4 *__restrict__ spheres, int64_t tiles,
+__global__ __launch_bounds__(kBlock) void k_tile_mask_dense(const float4 *__restrict__ bounds, int64_t tiles,
                                                             DevCamera cam, const DevFrame *__restrict__ frames,
                                                             int32_t n_frames, int32_t w0, int32_t w1, int32_t words,
                                                             const uint32_t *__restrict__ group_mask,
@@ -204,7 +204,8 @@ __global__ __launch_bounds__(kBlock) void k_tile_mask_dense(const float4 *__rest
   uint32_t word = whole;
   [[maybe_unused]] uint32_t inside = whole;
   if (todo) {
-    const float4 sph = spheres[have ? tile : tiles - 1];
+    const int64_t bt = have ? tile : tiles - 1;
+    const float4 sph = bounds[2 * bt], ext = bounds[2 * bt + 1];
     while (todo) {
       int32_t bit[4];
 #pragma unroll
@@ -214,7 +215,7 @@ __global__ __launch_bounds__(kBlock) void k_tile_mask_dense(const float4 *__rest
       }
       const int32_t b = slot == 0 ? bit[0] : slot == 1 ? bit[1] : slot == 2 ? bit[2] : bit[3];
       int cls = 1;
-      if (b >= 0 && have) cls = cull_enabled ? tile_classify(cam, frames[(w << 5) + b], sph) : 0;
+      if (b >= 0 && have) cls = cull_enabled ? tile_classify_box(cam, frames[(w << 5) + b], sph, ext) : 0;
       const unsigned long long keep = __ballot(cls != 1);
       [[maybe_unused]] unsigned long long ins = 0ull;
       if constexpr (kInside) ins = __ballot(cls == 2);
@@ -381,8 +382,8 @@ __global__ __launch_bounds__(kBlock) void k_depth_pass(const float *__restrict__
                                                        const uint32_t *__restrict__ tile_inside, int32_t words,
                                                        const int32_t *__restrict__ tile_order) {
   DevCamera cam = common_camera<kCommon>(cam_in);
-  // The fp32 rejection test only pays where whole wavefronts fail it.  Behind the tile masks few do -- a quarter of the visits of a
-  // C3 step hold no candidate at all (5.62 % of the pairs survive the tile level, 4.24 % this pass's refinement below) -- and every
+  // The fp32 rejection test only pays where whole wavefronts fail it.  Behind the tile masks few do -- a fifth of the visits of a
+  // C3 step hold no candidate at all (5.29 % of the pairs survive the tile level, 4.24 % this pass's refinement below) -- and every
   // other visit outside the `inside` pairs paid its 45 instructions for nothing:
   // depth pass 0.635 -> 0.568 ms without it.  (The other configurations keep it, among them the single-keyframe calls, which
   // have no masks.)
@@ -2025,19 +2026,19 @@ int pcp_depth_pass(pcp_context *ctx, int32_t frame_begin, int32_t frame_end) {
     {
       LaunchTimer t(ctx, PCP_K_TILE_MASK);
       const int64_t groups = div_up(ctx->n_tiles, kTileGroup);
-      const float4 *tile_sph = reinterpret_cast<const float4 *>(ctx->tile_sphere.p);
+      const float4 *tile_bnd = reinterpret_cast<const float4 *>(ctx->tile_bounds.p);
       const size_t gwords = static_cast<size_t>(groups) * ctx->mask_words;
       PCP_HIP_TRY(ctx, ctx->group_mask.ensure(2 * gwords + 8));  // keep bits | "wholly inside" bits
       uint32_t *group_inside = ctx->group_mask.p + gwords + 4;
       hipLaunchKernelGGL(k_group_mask_flat, dim3(std::max(blocks_for(groups * (w1 - w0) * 32), blocks_for(2 * kWorkBins))),
-                         dim3(kBlock), 0, ctx->stream, tile_sph + ctx->n_tiles, groups, ctx->dcam, ctx->frames.p, ctx->n_frames,
+                         dim3(kBlock), 0, ctx->stream, tile_bnd + 2 * ctx->n_tiles, groups, ctx->dcam, ctx->frames.p, ctx->n_frames,
                          w0, w1, ctx->mask_words, ctx->group_mask.p, group_inside, cull_tiles ? 1 : 0, ctx->work_hist.p,
                          2 * kWorkBins, z_maps ? reinterpret_cast<unsigned long long *>(ctx->depth_sq.p) : nullptr,
                          z_maps ? map_cells : int64_t(0));
       // the tiles' `inside` words only where the depth pass reads them (its rejection test: not in the common configuration)
       uint32_t *tile_inside = is_common_camera(ctx) ? nullptr : ctx->tile_inside.p;
       hipLaunchKernelGGL(tile_inside ? k_tile_mask_dense<true> : k_tile_mask_dense<false>, dim3(static_cast<uint32_t>(div_up(groups * (w1 - w0), kBlock / 64))), dim3(kBlock),
-                         0, ctx->stream, tile_sph, ctx->n_tiles, ctx->dcam, ctx->frames.p, ctx->n_frames, w0, w1,
+                         0, ctx->stream, tile_bnd, ctx->n_tiles, ctx->dcam, ctx->frames.p, ctx->n_frames, w0, w1,
                          ctx->mask_words, ctx->group_mask.p, group_inside, ctx->tile_mask.p, tile_inside, cull_tiles ? 1 : 0);
       // longest-work-first order of the tiles for this pass
       if ((rc = sort_tiles_by_work(ctx, w0, w1, ctx->tile_order.p)) != PCP_OK) return rc;
@@ -2492,6 +2493,28 @@ int pcp_tile_masks(pcp_context *ctx, int64_t *tiles, int32_t *mask_words, uint32
   if (out_words) {
     PCP_HIP_TRY(ctx, hipMemcpyAsync(out_words, ctx->tile_mask.p, static_cast<size_t>(ctx->n_tiles) * ctx->mask_words * 4,
                                     hipMemcpyDeviceToHost, ctx->stream));
+    PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return PCP_OK;
+}
+
+int pcp_cloud_order(pcp_context *ctx, int32_t *out_perm) {
+  if (!ctx || !out_perm) return PCP_ERR_INVALID;
+  if (ctx->n == 0) return set_error(ctx, PCP_ERR_STATE, "pcp_cloud_order: no cloud (call pcp_upload_cloud)");
+  PCP_HIP_TRY(ctx, hipMemcpyAsync(out_perm, ctx->perm.p, static_cast<size_t>(ctx->n) * 4, hipMemcpyDeviceToHost, ctx->stream));
+  PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return PCP_OK;
+}
+
+int pcp_tile_bounds(pcp_context *ctx, int64_t *tiles, float *out8) {
+  if (!ctx) return PCP_ERR_INVALID;
+  if (ctx->n == 0 || ctx->n_tiles == 0 || !ctx->tile_bounds.p)
+    return set_error(ctx, PCP_ERR_STATE, "pcp_tile_bounds: no cloud (call pcp_upload_cloud)");
+  if (tiles) *tiles = ctx->n_tiles;
+  if (out8) {
+    const int64_t groups = div_up(ctx->n_tiles, kTileGroup);
+    PCP_HIP_TRY(ctx, hipMemcpyAsync(out8, ctx->tile_bounds.p, static_cast<size_t>(ctx->n_tiles + groups) * 8 * 4, hipMemcpyDeviceToHost,
+                                    ctx->stream));
     PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
   return PCP_OK;

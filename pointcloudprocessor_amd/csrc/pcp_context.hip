@@ -328,17 +328,19 @@ __global__ __launch_bounds__(kUpBlock) void k_up_gather(const float *__restrict_
   if (inv_perm) inv_perm[i] = static_cast<int32_t>(j);
 }
 
-// bounding sphere of `span` consecutive Morton points per workgroup-slice: span = 64 (one wavefront per tile) or
-// 1024 (one workgroup per group of 16 tiles).  Centre = box centre rounded to fp32, radius = largest member
-// distance to that fp32 centre (fp64), inflated by 1e-6 and rounded up: it dominates every member's distance.
+// bounds of `span` consecutive sorted points per workgroup-slice: span = 64 (one wavefront per tile) or
+// 1024 (one workgroup per group of 16 tiles).  Two float4 per bound: {centre, radius} and {half-extents, 0}.  Centre = box
+// centre rounded to fp32, radius = largest member distance to that fp32 centre (fp64), half-extent h_a = largest |p_a - c_a|
+// (fp32 minus fp32: exact in fp64), each inflated by 1e-6 and rounded up: they dominate every member's.  A tile is a patch of a
+// surface: its box is flat where the sphere is round (pcp_tile_classify.hpp, tile_classify_box).
 template <int kSpan>
-__global__ __launch_bounds__(kUpBlock) void k_up_spheres(const float *__restrict__ sx, const float *__restrict__ sy,
+__global__ __launch_bounds__(kUpBlock) void k_up_bounds(const float *__restrict__ sx, const float *__restrict__ sy,
                                                         const float *__restrict__ sz, int64_t n,
                                                         float4 *__restrict__ out, int64_t count) {
   constexpr int kLanes = kSpan >= kUpBlock ? kUpBlock : kSpan;  // lanes cooperating on one sphere
   constexpr int kPer = kSpan / kLanes;                           // points per lane
   constexpr int kSpheresPerBlock = kUpBlock / kLanes;
-  __shared__ double red[7][kUpBlock / 64];
+  __shared__ double red[10][kUpBlock / 64];
   const int sub = threadIdx.x / kLanes, l = threadIdx.x % kLanes;
   const int64_t sphere = static_cast<int64_t>(blockIdx.x) * kSpheresPerBlock + sub;
   const int64_t b = sphere * kSpan;
@@ -382,7 +384,7 @@ __global__ __launch_bounds__(kUpBlock) void k_up_spheres(const float *__restrict
   float c[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) c[a] = static_cast<float>(0.5 * (lo[a] + hi[a]));
-  double r2 = 0.0;
+  double r2 = 0.0, h[3] = {0.0, 0.0, 0.0};
 #pragma unroll
   for (int q = 0; q < kPer; ++q)
     if (have[q]) {
@@ -390,17 +392,33 @@ __global__ __launch_bounds__(kUpBlock) void k_up_spheres(const float *__restrict
       const double dy = static_cast<double>(py[q]) - static_cast<double>(c[1]);
       const double dz = static_cast<double>(pz[q]) - static_cast<double>(c[2]);
       r2 = fmax(r2, (dx * dx + dy * dy) + dz * dz);  // fmax drops NaN members: they never project anyway
+      h[0] = fmax(h[0], fabs(dx));
+      h[1] = fmax(h[1], fabs(dy));
+      h[2] = fmax(h[2], fabs(dz));
     }
-  for (int o = (kLanes < 64 ? kLanes : 64) / 2; o >= 1; o >>= 1) r2 = fmax(r2, __shfl_xor(r2, o, 64));
+  for (int o = (kLanes < 64 ? kLanes : 64) / 2; o >= 1; o >>= 1) {
+    r2 = fmax(r2, __shfl_xor(r2, o, 64));
+#pragma unroll
+    for (int a = 0; a < 3; ++a) h[a] = fmax(h[a], __shfl_xor(h[a], o, 64));
+  }
   if (kLanes > 64) {
-    if ((threadIdx.x & 63) == 0) red[6][threadIdx.x >> 6] = r2;
+    if ((threadIdx.x & 63) == 0) {
+      red[6][threadIdx.x >> 6] = r2;
+      for (int a = 0; a < 3; ++a) red[7 + a][threadIdx.x >> 6] = h[a];
+    }
     __syncthreads();
-    for (int k = 0; k < kUpBlock / 64; ++k) r2 = fmax(r2, red[6][k]);
+    for (int k = 0; k < kUpBlock / 64; ++k) {
+      r2 = fmax(r2, red[6][k]);
+      for (int a = 0; a < 3; ++a) h[a] = fmax(h[a], red[7 + a][k]);
+    }
   }
   if (l == 0 && sphere < count) {
-    float r = static_cast<float>(sqrt(r2) * (1.0 + 1e-6));
-    r = isfinite(r) ? __uint_as_float(__float_as_uint(r) + 1u) : r;  // next float up
-    out[sphere] = make_float4(c[0], c[1], c[2], r);
+    const auto up = [](double v) {  // inflated, and the next float up
+      const float r = static_cast<float>(v * (1.0 + 1e-6));
+      return isfinite(r) ? __uint_as_float(__float_as_uint(r) + 1u) : r;
+    };
+    out[2 * sphere] = make_float4(c[0], c[1], c[2], up(sqrt(r2)));
+    out[2 * sphere + 1] = make_float4(up(h[0]), up(h[1]), up(h[2]), 0.0f);
   }
 }
 
@@ -550,19 +568,19 @@ static int store_cloud(pcp_context *ctx, const float *x, const float *y, const f
   if (int rc = spatial_order(ctx, dx, dy, dz, n, ctx->perm.p, ctx->sxyz.p, ctx->sxyz.p + plane, ctx->sxyz.p + 2 * plane,
                              ctx->inv_perm.p, mn, mx, &nonfinite))
     return rc;
-  raw.release();  // (before the spheres' allocation)
+  raw.release();  // (before the bounds' allocation)
   ctx->nonfinite_points = static_cast<int64_t>(nonfinite);
   for (int a = 0; a < 3; ++a) {
     ctx->host_min[a] = mn[a];
     ctx->host_max[a] = mx[a];
   }
   const int64_t tiles = (n + 63) / 64, groups = (tiles + 15) / 16;
-  PCP_HIP_TRY(ctx, ctx->tile_sphere.ensure(static_cast<size_t>(tiles + groups) * 4 + 4));
-  float4 *sph = reinterpret_cast<float4 *>(ctx->tile_sphere.p);
-  hipLaunchKernelGGL(k_up_spheres<64>, dim3(static_cast<uint32_t>((tiles + 3) / 4)), dim3(kUpBlock), 0, st, ctx->sxyz.p,
+  PCP_HIP_TRY(ctx, ctx->tile_bounds.ensure(static_cast<size_t>(tiles + groups) * 8 + 4));
+  float4 *sph = reinterpret_cast<float4 *>(ctx->tile_bounds.p);
+  hipLaunchKernelGGL(k_up_bounds<64>, dim3(static_cast<uint32_t>((tiles + 3) / 4)), dim3(kUpBlock), 0, st, ctx->sxyz.p,
                      ctx->sxyz.p + plane, ctx->sxyz.p + 2 * plane, n, sph, tiles);
-  hipLaunchKernelGGL(k_up_spheres<1024>, dim3(static_cast<uint32_t>(groups)), dim3(kUpBlock), 0, st, ctx->sxyz.p,
-                     ctx->sxyz.p + plane, ctx->sxyz.p + 2 * plane, n, sph + tiles, groups);
+  hipLaunchKernelGGL(k_up_bounds<1024>, dim3(static_cast<uint32_t>(groups)), dim3(kUpBlock), 0, st, ctx->sxyz.p,
+                     ctx->sxyz.p + plane, ctx->sxyz.p + 2 * plane, n, sph + 2 * tiles, groups);
   PCP_HIP_TRY(ctx, hipGetLastError());
   ctx->n_tiles = tiles;
   PCP_HIP_TRY(ctx, hipStreamSynchronize(st));  // the host arrays may be reused by the caller

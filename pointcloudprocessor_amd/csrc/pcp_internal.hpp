@@ -392,10 +392,11 @@ struct pcp_context {
   pcp::DevBuf<uint32_t> depth_accum;
   bool depth_accum_live = false;
 
-  // tiles = wavefront-sized runs of 64 Morton-ordered points: bounding spheres
-  // (x, y, z, radius) and the tile x keyframe visibility masks [tile][mask_words]
+  // tiles = wavefront-sized runs of 64 sorted points: bounds, two float4 each, (x, y, z, radius) of the bounding sphere and
+  // (hx, hy, hz, 0), the half-extents of the world-axis box about the same centre, the groups of 16 tiles behind the tiles;
+  // and the tile x keyframe visibility masks [tile][mask_words]
   int64_t n_tiles = 0;
-  pcp::DevBuf<float> tile_sphere;
+  pcp::DevBuf<float> tile_bounds;
   pcp::DevBuf<uint32_t> tile_mask, group_mask;
   pcp::DevBuf<uint32_t> tile_inside;  // pairs whose whole tile images inside the acceptance box (a hint: skip the pre-test)
   int32_t mask_words = 0;

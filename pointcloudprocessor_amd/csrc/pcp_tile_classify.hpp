@@ -1,5 +1,6 @@
 // pcp_tile_classify.hpp -- the conservative verdict on a bounding sphere against one keyframe, shared by the tile masks of the
-// colour path (pcp_colour.hip, K0) and the keyframe lists of the orthophoto's tiles (pcp_ortho_texture.hip, OT7).
+// colour path (pcp_colour.hip, K0: tile_classify_box, the sphere and the tile's box) and the keyframe lists of the orthophoto's
+// tiles (pcp_ortho_texture.hip, OT7: tile_classify).
 //
 // A (sphere, keyframe) pair is REJECTED only when every point inside the sphere is certain to be rejected by the reference
 // in that keyframe, proved in fp64 with outward-padded interval arithmetic:
@@ -13,6 +14,7 @@
 #pragma once
 
 #include "pcp_device.hpp"
+#include "pcp_tile_box.hpp"
 
 namespace pcp {
 
@@ -89,6 +91,57 @@ __device__ __forceinline__ int tile_classify(const DevCamera &c, const DevFrame 
   v.lo += c.cy; v.hi += c.cy;
   if (!isfinite(u.lo + u.hi + v.lo + v.hi)) return 0;
   // the box already carries a 0.5 px margin (pcp_set_camera)
+  if (u.hi < static_cast<double>(c.u_lo) || u.lo > static_cast<double>(c.u_hi) ||
+      v.hi < static_cast<double>(c.v_lo) || v.lo > static_cast<double>(c.v_hi))
+    return 1;
+  return (u.lo > static_cast<double>(c.u_lo) + 1.0 && u.hi < static_cast<double>(c.u_hi) - 1.0 &&
+          v.lo > static_cast<double>(c.v_lo) + 1.0 && v.hi < static_cast<double>(c.v_hi) - 1.0)
+             ? 2
+             : 0;
+}
+
+// The same verdict on a tile that also knows the half-extents h of its world-axis box about the sphere's centre (the tiles
+// and groups of an uploaded cloud, pcp_context.hip k_up_bounds).  The only difference from tile_classify is the inflation of the
+// three camera coordinates, one per row r of the matrix instead of one for all (pcp_tile_box.hpp tile_inflation, with the
+// soundness argument):
+//   rho_r = min(rho, (sum_j |m_rj| h_j) (1 + 1e-6) + 1e-6 mag),   rho and mag as above,
+// because |(M (p - c))_r| <= sum_j |m_rj| |p_j - c_j| <= sum_j |m_rj| h_j for every member p, and the sphere's bound holds for
+// every row as before.  The intervals are X +- rho_0, Y +- rho_1, Z +- rho_2; both z tests and the reciprocal use rho_2.  From
+// there on the interval image is tile_classify's, so the verdicts keep their meaning: 2 still says that every point of the tile
+// images inside the box, and the group-level shortcut of the mask kernels stays valid.
+// (tile_classify keeps its text: pcp_ortho_texture.hip calls it with spheres of its own.)
+__device__ __forceinline__ int tile_classify_box(const DevCamera &c, const DevFrame &fr, float4 sph, float4 ext) {
+  const double cx = sph.x, cy = sph.y, cz = sph.z;
+  const float *m = fr.w2c;
+  const double X = (m[0] * cx + m[1] * cy) + (m[2] * cz + m[3]);
+  const double Y = (m[4] * cx + m[5] * cy) + (m[6] * cz + m[7]);
+  const double Z = (m[8] * cx + m[9] * cy) + (m[10] * cz + m[11]);
+  const TileInflation inf = tile_inflation(m, fr.norm_bound, cx, cy, cz, sph.w, ext.x, ext.y, ext.z);
+  const double rho = inf.sphere, rx = inf.row[0], ry = inf.row[1], rz = inf.row[2];
+  if (!(rho >= 0.0) || !isfinite(X + Y + Z + rho)) return 0;
+  if (Z + rz <= 0.0) return 1;   // (a) entirely behind the camera
+  if (Z - rz <= 0.0) return 0;  // straddles z = 0: no bound on x / z
+  const Interval zi{Z - rz, Z + rz};
+  if (!(zi.lo >= 1e-290)) return 0;  // (a subnormal depth: no reciprocal estimate, no verdict)
+  const Interval iz{iv_rcp_pos(zi.hi) * (1.0 - 1e-13), iv_rcp_pos(zi.lo) * (1.0 + 1e-13)};
+  const Interval xn = iv_pad(iv_mul_by_pos(Interval{X - rx, X + rx}, iz));
+  const Interval yn = iv_pad(iv_mul_by_pos(Interval{Y - ry, Y + ry}, iz));
+  const Interval x2 = iv_sqr(xn), y2 = iv_sqr(yn);
+  const Interval r2 = iv_add(x2, y2);
+  const Interval r4 = iv_mul_pos(r2, r2);
+  const Interval r6 = iv_mul_pos(r2, r4);
+  Interval rc = iv_add(iv_add(iv_scale(c.k1, r2), iv_scale(c.k2, r4)), iv_scale(c.k3, r6));
+  rc.lo += 1.0;
+  rc.hi += 1.0;
+  const Interval t1 = iv_scale(2.0, iv_mul(xn, yn));
+  const Interval t2 = iv_add(r2, iv_scale(2.0, x2));
+  const Interval t3 = iv_add(r2, iv_scale(2.0, y2));
+  const Interval xd = iv_pad(iv_add(iv_add(iv_mul(rc, xn), iv_scale(c.p1, t1)), iv_scale(c.p2, t2)));
+  const Interval yd = iv_pad(iv_add(iv_add(iv_mul(rc, yn), iv_scale(c.p1, t3)), iv_scale(c.p2, t1)));
+  Interval u = iv_pad(iv_scale(c.fx, xd)), v = iv_pad(iv_scale(c.fy, yd));
+  u.lo += c.cx; u.hi += c.cx;
+  v.lo += c.cy; v.hi += c.cy;
+  if (!isfinite(u.lo + u.hi + v.lo + v.hi)) return 0;
   if (u.hi < static_cast<double>(c.u_lo) || u.lo > static_cast<double>(c.u_hi) ||
       v.hi < static_cast<double>(c.v_lo) || v.lo > static_cast<double>(c.v_hi))
     return 1;
