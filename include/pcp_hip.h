@@ -81,7 +81,9 @@ extern "C" {
                                 entry points added, no layout changed: pcp_ortho_texture, pcp_ortho_texture_points_host
                                 (orthophotos; nothing runs unless called);
                                 entry points added, no layout changed: pcp_facets / _fetch / _host, pcp_facet_plane_host,
-                                pcp_ortho_add_facet (planar facets of the map; nothing runs unless called) */
+                                pcp_ortho_add_facet (planar facets of the map; nothing runs unless called);
+                                entry points added, no layout changed: pcp_ortho_begin_cyl, pcp_ortho_cyl_host, pcp_cyl_angle_host,
+                                pcp_cyl_fit_host (cylindrical facets and their unrolled maps; nothing runs unless called) */
 
 #define PCP_OK 0
 #define PCP_ERR_INVALID (-1) /* bad argument */
@@ -1235,6 +1237,55 @@ int pcp_facets_host(int64_t n, const float *xyz, const float *normal, const floa
                     int32_t *out_label, int32_t *out_id, int64_t *out_rows10, float *out_box, int64_t *out_facets);
 int pcp_facet_plane_host(const float root[3], const int64_t row10[10], double out_plane[7]);
 int pcp_ortho_add_facet(pcp_context *ctx, int32_t facet_id, int64_t index_base, int64_t *out_contributors);
+
+/* ---- cylindrical facets (no counterpart in the reference: its pictures are per-keyframe perspective views) ----------------- */
+/* A second kind of frame for the orthographic maps: a cylinder, unrolled along its arc ("Cylindrical facets",
+ * CY1-CY9).  Image x runs along the arc R theta, image y along the axis, both at gsd metres per pixel; the depth layer is the
+ * radial deviation side (rho - R) from the cylinder.  Opt-in: nothing runs unless one of these is called, PCP_ABI_VERSION is
+ * unchanged and a caller detects support by the symbols.  Kernels are timed under PCP_K_MISC.
+ *   frame     c a point of the axis (row coordinate h = 0), a the unit axis (rows run along +a), e and b unit and perpendicular
+ *             to a and to each other (theta = 0 along e, pi/2 along b), radius R in [0.05, 1000] metres, gsd in [1e-4, 1],
+ *             width x height >= 1 x 1, d_min < d_max, side +1 (seen from inside, depth grows outward) or -1 (from outside).
+ *             A non-finite value, a value outside these ranges, axes (e, b, a) that are not orthonormal with e x b = side a
+ *             within 1e-3, or width gsd > 2 pi R + gsd: PCP_ERR_INVALID.  A raster past 16384 a side or 2^26 pixels:
+ *             PCP_ERR_RANGE, the message names the gsd at which the same extent fits.
+ *   point     d = fl32(p - c); s = d.e, t = d.b, h = d.a in fp32 (pcp_ortho's association); in fp64, every operation rounded on
+ *             its own: rho = sqrt(s s + t t), theta in [0, 2 pi] by a fixed sequence of operations (no libm; CY3), arc = R theta;
+ *             x = (float)(arc inv), y = fl32(h inv) with inv = fl32(1 / gsd); depth = (float)(side (rho - R)).  A row contributes
+ *             iff its has bit is set, its coordinates are finite, rho > 0, 0 <= x < W, 0 <= y < H (in float) and
+ *             d_min <= depth <= d_max; its pixel is (floor(x), floor(y)).  The map does not wrap across the seam theta = 0 | 2 pi.
+ * pcp_ortho_begin_cyl starts the accumulator of pcp_ortho_begin under such a frame; either begin drops the live map of either
+ * kind, a refused one leaves it.  pcp_ortho_add / _add_facet / _add_packed / _finish / _fetch / _stats / _end work on either kind,
+ * with the same keys, merge, payload, fill and layers.  pcp_ortho_texture on a cylinder's map: PCP_ERR_STATE (orthophotos of
+ * unrolled maps are not built).
+ * pcp_ortho_cyl_host: pcp_ortho_host under a cylinder's frame, bit for bit what the device gives.
+ * pcp_cyl_angle_host: theta of n pairs (s, t) of doubles by the same sequence (host only; (0, 0) gives a NaN).
+ * pcp_cyl_fit_host: host only, fp64, closed form: the cylinder of the rows whose has byte is set (NULL: all), whose coordinates
+ * are finite and whose normal (3 floats per row) is finite and not (0, 0, 0), and the frame that unrolls them so that every such
+ * row contributes.  Axis: the eigenvector of the smallest eigenvalue of the normals' scatter, signed so that its largest component
+ * is negative; centre and R: the algebraic circle through the rows projected along the axis; side +1 iff viewer (3 doubles,
+ * nullable) lies within R of the axis; the seam in the longest empty stretch of 4096 angle bins (a ring whose longest stretch is
+ * shorter than two pixels is closed: width = ceil(2 pi R / gsd)).  out_stats (nullable): rows used, rms, least and greatest of
+ * rho - R, the occupied arc in radians, the three eigenvalues of the normals' scatter ascending.  Fewer than 16 rows, parallel
+ * normals, R outside [0.05, 1000], a raster past the limits: PCP_ERR_RANGE.  Messages of the three at pcp_last_error(NULL). */
+typedef struct pcp_cyl_frame {
+  float c[3];        /* a point of the axis: where row coordinate h = 0 */
+  float a[3];        /* unit axis: image y (rows) runs along +a */
+  float e[3], b[3];  /* unit, perpendicular to a and to each other: theta = 0 along e, pi/2 along b */
+  float radius;      /* R, metres */
+  float gsd;
+  int32_t width, height;
+  float d_min, d_max;
+  int32_t side;      /* +1: seen from inside (depth grows outward), -1: seen from outside */
+} pcp_cyl_frame;
+int pcp_ortho_begin_cyl(pcp_context *ctx, const pcp_cyl_frame *frame);
+int pcp_ortho_cyl_host(const pcp_cyl_frame *frame, int64_t n, const float *xyz, const uint8_t *rgb, const uint8_t *label,
+                       const uint8_t *has, int64_t index_base, int32_t fill_radius_px, uint32_t *out_index, float *out_depth,
+                       uint8_t *out_rgb, uint8_t *out_label, uint8_t *out_status, int32_t *out_source, int64_t *out_contributors,
+                       int64_t *out_occupied, int64_t *out_filled);
+int pcp_cyl_angle_host(int64_t n, const double *s, const double *t, double *out_theta);
+int pcp_cyl_fit_host(int64_t n, const float *xyz, const float *normal, const uint8_t *has, const double *viewer, float gsd,
+                     pcp_cyl_frame *out, double out_stats[8]);
 
 /* ---- precondition of the match-back(PointCloudProcessor.cpp:480-482,571) ------------------------------- */
 /* Number of map points that have ANOTHER map point closer than `radius` (fp32 squared distance, strict <, as

@@ -365,6 +365,103 @@ def ortho_fit_frame_host(xyz, gsd: float, has=None, viewer=None) -> OrthoFrame:
     return f
 
 
+class CylFrame(C.Structure):
+    """pcp_cyl_frame: a point c of the axis, the unit axis a (image y), e / b (theta = 0 / pi/2), radius, metres per pixel,
+    raster size, depth window and side of a cylinder's unrolled map ("Cylindrical facets", CY1)."""
+    _fields_ = [("c", C.c_float * 3), ("a", C.c_float * 3), ("e", C.c_float * 3), ("b", C.c_float * 3), ("radius", C.c_float),
+                ("gsd", C.c_float), ("width", C.c_int32), ("height", C.c_int32), ("d_min", C.c_float), ("d_max", C.c_float),
+                ("side", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        return dict(c=[float(x) for x in self.c], a=[float(x) for x in self.a], e=[float(x) for x in self.e], b=[float(x) for x in self.b],
+                    radius=float(self.radius), gsd=float(self.gsd), width=int(self.width), height=int(self.height),
+                    d_min=float(self.d_min), d_max=float(self.d_max), side=int(self.side))
+
+
+CY_STATS = ("rows", "rms", "dev_min", "dev_max", "arc", "ev0", "ev1", "ev2")  # pcp_cyl_fit_host's out_stats
+
+
+def cyl_frame(frame) -> CylFrame:
+    """A CylFrame from a dict(c, a, e, b, radius, gsd, width, height, d_min, d_max, side) (or a copy of one); the values go
+    through float32 as the library takes them."""
+    if isinstance(frame, CylFrame):
+        frame = frame.as_dict()
+    f = CylFrame()
+    for k in ("c", "a", "e", "b"):
+        vals = np.asarray(frame[k], np.float32).reshape(3)
+        setattr(f, k, (C.c_float * 3)(*[float(x) for x in vals]))
+    f.radius = float(np.float32(frame["radius"]))
+    f.gsd = float(np.float32(frame["gsd"]))
+    f.width, f.height = int(frame["width"]), int(frame["height"])
+    f.d_min, f.d_max = float(np.float32(frame["d_min"])), float(np.float32(frame["d_max"]))
+    f.side = int(frame["side"])
+    return f
+
+
+def ortho_cyl_host(frame, xyz, rgb, label=None, has=None, index_base: int = 0, fill_radius: int = 0) -> dict:
+    """ortho_host under a cylinder's frame (pcp_ortho_cyl_host: no context, no GPU; DESIGN.md "Cylindrical facets", CY5): the
+    same arguments and the same dict."""
+    L = load()
+    f = cyl_frame(frame)
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    rgb = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)
+    label = None if label is None else np.ascontiguousarray(label, np.uint8).reshape(-1)
+    has = None if has is None else np.ascontiguousarray(has, np.uint8).reshape(-1)
+    n = xyz.shape[0]
+    if rgb.shape[0] != n or (label is not None and label.shape[0] != n) or (has is not None and has.shape[0] != n):
+        raise ValueError("ortho_cyl_host: xyz, rgb, label and has differ in their number of rows")
+    h, w = max(int(f.height), 0), max(int(f.width), 0)
+    big = w > 16384 or h > 16384 or w * h > (1 << 26)  # (refused by the library: nothing to allocate)
+    shape = (0, 0) if big else (h, w)
+    out = dict(index=np.empty(shape, np.uint32), depth=np.empty(shape, np.float32), rgb=np.empty(shape + (3,), np.uint8),
+               status=np.empty(shape, np.uint8), source=np.empty(shape, np.int32))
+    olab = np.empty(shape, np.uint8) if label is not None else None
+    cnt, occ, fil = C.c_int64(), C.c_int64(), C.c_int64()
+    rc = L.pcp_ortho_cyl_host(C.byref(f), C.c_int64(n), _ptr(xyz), _ptr(rgb), _ptr(label), _ptr(has), C.c_int64(index_base),
+                              C.c_int32(fill_radius), _ptr(out["index"]), _ptr(out["depth"]), _ptr(out["rgb"]), _ptr(olab),
+                              _ptr(out["status"]), _ptr(out["source"]), C.byref(cnt), C.byref(occ), C.byref(fil))
+    if rc != PCP_OK:
+        raise PcpError(rc, L.pcp_last_error(None).decode())
+    if label is not None:
+        out["label"] = olab
+    out.update(contributors=cnt.value, occupied=occ.value, filled=fil.value)
+    return out
+
+
+def cyl_angle_host(s, t) -> np.ndarray:
+    """theta in [0, 2 pi] of the pairs (s, t) of doubles by the kernels' fixed sequence of fp64 operations (pcp_cyl_angle_host;
+    DESIGN.md "Cylindrical facets", CY3)."""
+    L = load()
+    s = np.ascontiguousarray(s, np.float64).reshape(-1)
+    t = np.ascontiguousarray(t, np.float64).reshape(-1)
+    if s.shape != t.shape:
+        raise ValueError("cyl_angle_host: s and t differ in their number of rows")
+    out = np.empty(s.shape, np.float64)
+    rc = L.pcp_cyl_angle_host(C.c_int64(s.size), _ptr(s), _ptr(t), _ptr(out))
+    if rc != PCP_OK:
+        raise PcpError(rc, L.pcp_last_error(None).decode())
+    return out
+
+
+def cyl_fit_host(xyz, normal, gsd: float, has=None, viewer=None) -> tuple[CylFrame, dict]:
+    """The cylinder of the rows that have a valid normal and the frame that unrolls them (pcp_cyl_fit_host: host only, fp64,
+    closed form; DESIGN.md "Cylindrical facets", CY6).  Returns (CylFrame, dict of CY_STATS)."""
+    L = load()
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    normal = np.ascontiguousarray(normal, np.float32).reshape(-1, 3)
+    has = None if has is None else np.ascontiguousarray(has, np.uint8).reshape(-1)
+    if normal.shape[0] != xyz.shape[0] or (has is not None and has.shape[0] != xyz.shape[0]):
+        raise ValueError("cyl_fit_host: xyz, normal and has differ in their number of rows")
+    viewer = None if viewer is None else np.ascontiguousarray(viewer, np.float64).reshape(3)
+    f = CylFrame()
+    stats = np.zeros(8, np.float64)
+    rc = L.pcp_cyl_fit_host(C.c_int64(xyz.shape[0]), _ptr(xyz), _ptr(normal), _ptr(has), _ptr(viewer), C.c_float(gsd), C.byref(f),
+                            _ptr(stats))
+    if rc != PCP_OK:
+        raise PcpError(rc, L.pcp_last_error(None).decode())
+    return f, {k: (int(v) if k == "rows" else float(v)) for k, v in zip(CY_STATS, stats)}
+
+
 class OrthoTextureParams(C.Structure):
     """pcp_ortho_texture_params (DESIGN.md, "Orthophotos", OT2)."""
     _fields_ = [("scale", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("views", C.c_int32),
@@ -1257,6 +1354,13 @@ class Context:
         f = ortho_frame(frame)
         self._check(self.lib.pcp_ortho_begin(self.h, C.byref(f)))
         self._ortho_frame = f  # (only of a begin the library took: a refused one leaves the live map, and its frame, as they were)
+
+    def ortho_begin_cyl(self, frame):
+        """Starts an empty unrolled map of the cylinder `frame` (a CylFrame, or a dict of its fields) on this context
+        (pcp_ortho_begin_cyl; DESIGN.md, "Cylindrical facets"); the adds, finish, fetch, stats and end are ortho_begin's."""
+        f = cyl_frame(frame)
+        self._check(self.lib.pcp_ortho_begin_cyl(self.h, C.byref(f)))
+        self._ortho_frame = f  # (the shape of the last begin the library took, of either kind)
 
     def ortho_add(self, index_base: int = 0) -> int:
         """Adds the coloured rows of the current colour result under the global indices index_base + row; returns the

@@ -200,6 +200,8 @@ struct OrthoMap {
   bool live = false, finished = false;
   bool labels_fixed = false, with_label = false;  // the first add fixes whether labels are held
   pcp_ortho_frame frame{};
+  bool cyl = false;           // begun by pcp_ortho_begin_cyl: cyl_frame holds, and frame only its gsd, width and height
+  pcp_cyl_frame cyl_frame{};
   int32_t fill_radius = 0;
   int64_t contributors = 0, atomics = 0, occupied = 0, filled = 0, adds = 0;
   DevBuf<unsigned long long> keys, scalars;

@@ -3,18 +3,22 @@
 // over any number of colour results (one-shot runs, the chunks of the streamed chain).  Per pixel the nearest contributor
 // wins through one 64-bit atomicMin on (ord(depth) << 32 | global index), the reduction of k_gm_scatter; a second pass with
 // plain stores writes the winners' payload; the optional fill takes empty pixels from their nearest occupied one through the
-// exact distance transform of pcp_mask_edt.hip.  The arithmetic is pcp_ortho.hpp's, shared with pcp_ortho_host.
+// exact distance transform of pcp_mask_edt.hip.  The arithmetic is pcp_ortho.hpp's, shared with pcp_ortho_host.  A second
+// kind of frame, a cylinder unrolled along its arc ("Cylindrical facets", CY1-CY9; pcp_ortho_cyl.hpp), differs in
+// the pixel alone: pcp_ortho_begin_cyl, pcp_ortho_cyl_host and the closed-form fit pcp_cyl_fit_host.
 // Opt-in: nothing here runs unless one of its entry points is called.
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "pcp_eigen33_host.hpp"
 #include "pcp_internal.hpp"
 #include "pcp_mask_edt.hpp"
 #include "pcp_ortho.hpp"
+#include "pcp_ortho_cyl.hpp"
 
 namespace pcp {
 
@@ -25,12 +29,16 @@ enum { OR_CONTRIBUTORS = 0, OR_ATOMICS, OR_OCCUPIED, OR_FILLED, OR_SCALARS };
 
 // the contributor of lane j of the upload's spatial order (sxyz / perm: the uploaded coordinates; the packed word of the
 // input-order result): its pixel (-1: none), key, input row and word.  kFacet (pcp_ortho_add_facet): only the rows whose
-// facet label (input order) is facet_id contribute.
-template <bool kFacet>
+// facet label (input order) is facet_id contribute.  kCyl (pcp_ortho_begin_cyl): the frame is a cylinder's and the pixel
+// comes from pcp_ortho_cyl.hpp (CY2); everything after the pixel is the same.
+template <bool kCyl>
+using OrFrame = std::conditional_t<kCyl, cy::Frame, om::Frame>;
+
+template <bool kFacet, bool kCyl>
 __device__ __forceinline__ int32_t or_contributor(int64_t j, int64_t n, const float *__restrict__ sx, const float *__restrict__ sy,
                                                   const float *__restrict__ sz, const int32_t *__restrict__ perm,
                                                   const uint32_t *__restrict__ packed, [[maybe_unused]] const int32_t *__restrict__ facet,
-                                                  [[maybe_unused]] int32_t facet_id, const om::Frame &f, uint32_t index_base,
+                                                  [[maybe_unused]] int32_t facet_id, const OrFrame<kCyl> &f, uint32_t index_base,
                                                   unsigned long long *key, int32_t *row, uint32_t *word) {
   *key = om::kEmptyKey;
   if (j >= n) return -1;
@@ -42,7 +50,11 @@ __device__ __forceinline__ int32_t or_contributor(int64_t j, int64_t n, const fl
   if (!(w >> 24)) return -1;
   int32_t pixel;
   uint32_t depth_bits;
-  if (!om::project(f, sx[j], sy[j], sz[j], &pixel, &depth_bits)) return -1;
+  if constexpr (kCyl) {
+    if (!cy::project(f, sx[j], sy[j], sz[j], &pixel, &depth_bits)) return -1;
+  } else {
+    if (!om::project(f, sx[j], sy[j], sz[j], &pixel, &depth_bits)) return -1;
+  }
   *row = i;
   *word = w;
   *key = om::key_of(depth_bits, index_base + static_cast<uint32_t>(i));
@@ -53,11 +65,11 @@ __device__ __forceinline__ int32_t or_contributor(int64_t j, int64_t n, const fl
 // the run of the nearest lane below that has one (and brings the empty key, the minimum's identity); the smallest key of a run
 // of equal pixels is found by a segmented suffix minimum (six shuffle steps) and the run's first lane issues the one atomic.
 // (One atomic per contributor instead: the same add 0.71 -> 1.99 ms where 200 points share a pixel, profiles/ortho_probe.md.)
-template <bool kFacet>
+template <bool kFacet, bool kCyl>
 __global__ __launch_bounds__(kOrBlock) void k_or_scatter(int64_t n, const float *__restrict__ sx, const float *__restrict__ sy,
                                                          const float *__restrict__ sz, const int32_t *__restrict__ perm,
                                                          const uint32_t *__restrict__ packed, const int32_t *__restrict__ facet,
-                                                         int32_t facet_id, om::Frame f, uint32_t index_base,
+                                                         int32_t facet_id, OrFrame<kCyl> f, uint32_t index_base,
                                                          unsigned long long *__restrict__ keys, unsigned long long *__restrict__ scalars) {
   const int lane = static_cast<int>(threadIdx.x & 63u);
   uint32_t contributors = 0u, atomics = 0u;
@@ -65,7 +77,7 @@ __global__ __launch_bounds__(kOrBlock) void k_or_scatter(int64_t n, const float 
     unsigned long long key;
     int32_t row = 0;
     uint32_t word = 0u;
-    const int32_t pixel = or_contributor<kFacet>(base + threadIdx.x, n, sx, sy, sz, perm, packed, facet, facet_id, f, index_base, &key, &row, &word);
+    const int32_t pixel = or_contributor<kFacet, kCyl>(base + threadIdx.x, n, sx, sy, sz, perm, packed, facet, facet_id, f, index_base, &key, &row, &word);
     contributors += pixel >= 0 ? 1u : 0u;
     const unsigned long long with = __ballot(pixel >= 0);
     if (!with) continue;  // (the same in every lane of the wavefront)
@@ -95,19 +107,19 @@ __global__ __launch_bounds__(kOrBlock) void k_or_scatter(int64_t n, const float 
 }
 
 // OM4.  The same contributors, after the scatter: the one whose key is its pixel's key stores the payload word.  No atomics.
-template <bool kLabel, bool kFacet>
+template <bool kLabel, bool kFacet, bool kCyl>
 __global__ __launch_bounds__(kOrBlock) void k_or_payload(int64_t n, const float *__restrict__ sx, const float *__restrict__ sy,
                                                          const float *__restrict__ sz, const int32_t *__restrict__ perm,
                                                          const uint32_t *__restrict__ packed,
                                                          [[maybe_unused]] const uint32_t *__restrict__ labels,
-                                                         const int32_t *__restrict__ facet, int32_t facet_id, om::Frame f,
+                                                         const int32_t *__restrict__ facet, int32_t facet_id, OrFrame<kCyl> f,
                                                          uint32_t index_base, const unsigned long long *__restrict__ keys,
                                                          uint32_t *__restrict__ payload) {
   for (int64_t base = static_cast<int64_t>(blockIdx.x) * kOrBlock; base < n; base += static_cast<int64_t>(gridDim.x) * kOrBlock) {
     unsigned long long key;
     int32_t row = 0;
     uint32_t word = 0u;
-    const int32_t pixel = or_contributor<kFacet>(base + threadIdx.x, n, sx, sy, sz, perm, packed, facet, facet_id, f, index_base, &key, &row, &word);
+    const int32_t pixel = or_contributor<kFacet, kCyl>(base + threadIdx.x, n, sx, sy, sz, perm, packed, facet, facet_id, f, index_base, &key, &row, &word);
     if (pixel < 0 || keys[pixel] != key) continue;
     uint32_t label = 0u;
     if constexpr (kLabel) label = labels[row] & 0xffu;
@@ -209,11 +221,49 @@ static om::Frame or_frame(const pcp_ortho_frame &c) {
   return f;
 }
 
+static cy::Frame or_cyl_frame(const pcp_cyl_frame &c) {
+  cy::Frame f;
+  for (int k = 0; k < 3; ++k) {
+    f.c[k] = c.c[k];
+    f.a[k] = c.a[k];
+    f.e[k] = c.e[k];
+    f.b[k] = c.b[k];
+  }
+  f.inv = om::inverse_gsd(c.gsd);
+  f.w = c.width;
+  f.h = c.height;
+  f.wf = static_cast<float>(c.width);
+  f.hf = static_cast<float>(c.height);
+  f.d_min = c.d_min;
+  f.d_max = c.d_max;
+  f.R = static_cast<double>(c.radius);
+  f.side = static_cast<double>(c.side);
+  return f;
+}
+
 // OM1 for either form; msg receives the refusal
 static int or_check_frame(const char *who, const pcp_ortho_frame *fr, char *msg, size_t cap) {
   const char *why = "";
   double fit = 0.0;
   const int bad = om::frame_check(fr->o, fr->u, fr->v, fr->n, fr->gsd, fr->width, fr->height, fr->d_min, fr->d_max, &why, &fit);
+  if (bad == 1) {
+    std::snprintf(msg, cap, "%s: %s", who, why);
+    return PCP_ERR_INVALID;
+  }
+  if (bad == 2) {
+    std::snprintf(msg, cap, "%s: raster %d x %d at gsd %g: %s; the same extent fits at gsd %.6g", who, fr->width, fr->height,
+                  static_cast<double>(fr->gsd), why, fit);
+    return PCP_ERR_RANGE;
+  }
+  return PCP_OK;
+}
+
+// CY1, the same way
+static int or_check_cyl_frame(const char *who, const pcp_cyl_frame *fr, char *msg, size_t cap) {
+  const char *why = "";
+  double fit = 0.0;
+  const int bad = cy::frame_check(fr->c, fr->a, fr->e, fr->b, fr->radius, fr->gsd, fr->width, fr->height, fr->d_min, fr->d_max, fr->side,
+                                  &why, &fit);
   if (bad == 1) {
     std::snprintf(msg, cap, "%s: %s", who, why);
     return PCP_ERR_INVALID;
@@ -232,35 +282,49 @@ static void or_drop(pcp_context *ctx) {
   m.payload.release();
   m.source.release();
   m.scalars.release();
-  m.live = m.finished = m.labels_fixed = m.with_label = false;
+  m.live = m.finished = m.labels_fixed = m.with_label = m.cyl = false;
   m.contributors = m.atomics = m.occupied = m.filled = m.adds = 0;
   m.fill_radius = 0;
 }
 
+// what either begin does once its frame is accepted: drops the live map and starts an empty one of w x h pixels
+static int or_start(pcp_context *ctx, int32_t w, int32_t h) {
+  PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  or_drop(ctx);
+  OrthoMap &m = ctx->ortho;
+  const size_t px = static_cast<size_t>(w) * static_cast<size_t>(h);
+  PCP_HIP_TRY(ctx, m.keys.ensure(px + 2));
+  PCP_HIP_TRY(ctx, m.payload.ensure(px + 4));
+  PCP_HIP_TRY(ctx, m.scalars.ensure(OR_SCALARS));
+  PCP_HIP_TRY(ctx, hipMemsetAsync(m.keys.p, 0xff, px * 8, ctx->stream));  // the empty key is all ones
+  PCP_HIP_TRY(ctx, hipMemsetAsync(m.payload.p, 0, px * 4, ctx->stream));
+  PCP_HIP_TRY(ctx, hipMemsetAsync(m.scalars.p, 0, OR_SCALARS * 8, ctx->stream));
+  return PCP_OK;
+}
+
 // the two passes of an add over the uploaded cloud with the words `packed` (device, input order) and `labels` (nullable);
 // facet (nullable; device, input order): only the rows labelled facet_id
-template <bool kFacet>
-static int or_add_words(pcp_context *ctx, const uint32_t *packed, const uint32_t *labels, const int32_t *facet, int32_t facet_id,
-                        uint32_t index_base, int64_t *out_contributors) {
+template <bool kFacet, bool kCyl>
+static int or_add_passes(pcp_context *ctx, const OrFrame<kCyl> &f, const uint32_t *packed, const uint32_t *labels, const int32_t *facet,
+                         int32_t facet_id, uint32_t index_base, int64_t *out_contributors) {
   OrthoMap &m = ctx->ortho;
   const int64_t n = ctx->n;
   const size_t plane = (static_cast<size_t>(n) + 3) & ~size_t(3);
   const float *sx = ctx->sxyz.p, *sy = sx + plane, *sz = sy + plane;
-  const om::Frame f = or_frame(m.frame);
   PCP_HIP_TRY(ctx, hipMemsetAsync(m.scalars.p, 0, 2 * 8, ctx->stream));  // contributors, atomics
   {
     LaunchTimer t(ctx, PCP_K_MISC);
-    hipLaunchKernelGGL(k_or_scatter<kFacet>, dim3(or_blocks(n)), dim3(kOrBlock), 0, ctx->stream, n, sx, sy, sz, ctx->perm.p, packed, facet,
+    hipLaunchKernelGGL((k_or_scatter<kFacet, kCyl>), dim3(or_blocks(n)), dim3(kOrBlock), 0, ctx->stream, n, sx, sy, sz, ctx->perm.p, packed, facet,
                        facet_id, f, index_base, m.keys.p, m.scalars.p);
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
   {
     LaunchTimer t(ctx, PCP_K_MISC);
     if (labels)
-      hipLaunchKernelGGL((k_or_payload<true, kFacet>), dim3(or_blocks(n)), dim3(kOrBlock), 0, ctx->stream, n, sx, sy, sz, ctx->perm.p, packed,
+      hipLaunchKernelGGL((k_or_payload<true, kFacet, kCyl>), dim3(or_blocks(n)), dim3(kOrBlock), 0, ctx->stream, n, sx, sy, sz, ctx->perm.p, packed,
                          labels, facet, facet_id, f, index_base, m.keys.p, m.payload.p);
     else
-      hipLaunchKernelGGL((k_or_payload<false, kFacet>), dim3(or_blocks(n)), dim3(kOrBlock), 0, ctx->stream, n, sx, sy, sz, ctx->perm.p, packed,
+      hipLaunchKernelGGL((k_or_payload<false, kFacet, kCyl>), dim3(or_blocks(n)), dim3(kOrBlock), 0, ctx->stream, n, sx, sy, sz, ctx->perm.p, packed,
                          static_cast<const uint32_t *>(nullptr), facet, facet_id, f, index_base, m.keys.p, m.payload.p);
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
@@ -271,6 +335,14 @@ static int or_add_words(pcp_context *ctx, const uint32_t *packed, const uint32_t
   m.atomics += static_cast<int64_t>(h[OR_ATOMICS]);
   if (out_contributors) *out_contributors = static_cast<int64_t>(h[OR_CONTRIBUTORS]);
   return PCP_OK;
+}
+
+template <bool kFacet>
+static int or_add_words(pcp_context *ctx, const uint32_t *packed, const uint32_t *labels, const int32_t *facet, int32_t facet_id,
+                        uint32_t index_base, int64_t *out_contributors) {
+  const OrthoMap &m = ctx->ortho;
+  if (m.cyl) return or_add_passes<kFacet, true>(ctx, or_cyl_frame(m.cyl_frame), packed, labels, facet, facet_id, index_base, out_contributors);
+  return or_add_passes<kFacet, false>(ctx, or_frame(m.frame), packed, labels, facet, facet_id, index_base, out_contributors);
 }
 
 // what both adds check before they touch the device
@@ -304,17 +376,29 @@ int pcp_ortho_begin(pcp_context *ctx, const pcp_ortho_frame *frame) {
   char msg[320];
   const int rc = or_check_frame("pcp_ortho_begin", frame, msg, sizeof msg);
   if (rc != PCP_OK) return set_error(ctx, rc, "%s", msg);
-  PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  or_drop(ctx);
+  const int brc = or_start(ctx, frame->width, frame->height);
+  if (brc != PCP_OK) return brc;
   OrthoMap &m = ctx->ortho;
-  const size_t px = static_cast<size_t>(frame->width) * static_cast<size_t>(frame->height);
-  PCP_HIP_TRY(ctx, m.keys.ensure(px + 2));
-  PCP_HIP_TRY(ctx, m.payload.ensure(px + 4));
-  PCP_HIP_TRY(ctx, m.scalars.ensure(OR_SCALARS));
-  PCP_HIP_TRY(ctx, hipMemsetAsync(m.keys.p, 0xff, px * 8, ctx->stream));  // the empty key is all ones
-  PCP_HIP_TRY(ctx, hipMemsetAsync(m.payload.p, 0, px * 4, ctx->stream));
-  PCP_HIP_TRY(ctx, hipMemsetAsync(m.scalars.p, 0, OR_SCALARS * 8, ctx->stream));
   m.frame = *frame;
+  m.live = true;
+  return PCP_OK;
+}
+
+int pcp_ortho_begin_cyl(pcp_context *ctx, const pcp_cyl_frame *frame) {
+  if (!ctx) return PCP_ERR_INVALID;
+  if (!frame) return set_error(ctx, PCP_ERR_INVALID, "pcp_ortho_begin_cyl: NULL frame");
+  char msg[320];
+  const int rc = or_check_cyl_frame("pcp_ortho_begin_cyl", frame, msg, sizeof msg);
+  if (rc != PCP_OK) return set_error(ctx, rc, "%s", msg);
+  const int brc = or_start(ctx, frame->width, frame->height);
+  if (brc != PCP_OK) return brc;
+  OrthoMap &m = ctx->ortho;
+  m.frame = pcp_ortho_frame{};  // (finish, fetch and stats read the raster from here)
+  m.frame.gsd = frame->gsd;
+  m.frame.width = frame->width;
+  m.frame.height = frame->height;
+  m.cyl_frame = *frame;
+  m.cyl = true;
   m.live = true;
   return PCP_OK;
 }
@@ -493,33 +577,31 @@ int pcp_ortho_end(pcp_context *ctx) {
   return PCP_OK;
 }
 
-int pcp_ortho_host(const pcp_ortho_frame *frame, int64_t n, const float *xyz, const uint8_t *rgb, const uint8_t *label, const uint8_t *has,
-                   int64_t index_base, int32_t fill_radius_px, uint32_t *out_index, float *out_depth, uint8_t *out_rgb, uint8_t *out_label,
-                   uint8_t *out_status, int32_t *out_source, int64_t *out_contributors, int64_t *out_occupied, int64_t *out_filled) {
-  if (out_contributors) *out_contributors = 0;
-  if (out_occupied) *out_occupied = 0;
-  if (out_filled) *out_filled = 0;
-  if (!frame || n < 0 || (n > 0 && (!xyz || !rgb))) {
-    set_global_error("pcp_ortho_host: NULL frame, negative n or a missing xyz / rgb");
-    return PCP_ERR_INVALID;
-  }
-  char msg[320];
-  const int rc = or_check_frame("pcp_ortho_host", frame, msg, sizeof msg);
-  if (rc != PCP_OK) {
-    set_global_error("%s", msg);
-    return rc;
-  }
+}  // extern "C"
+
+static inline bool or_project(const om::Frame &f, float x, float y, float z, int32_t *pixel, uint32_t *depth_bits) {
+  return om::project(f, x, y, z, pixel, depth_bits);
+}
+static inline bool or_project(const cy::Frame &f, float x, float y, float z, int32_t *pixel, uint32_t *depth_bits) {
+  return cy::project(f, x, y, z, pixel, depth_bits);
+}
+
+// the CPU form of a whole map under an accepted frame of either kind (pcp_ortho_host, pcp_ortho_cyl_host)
+template <class FrameT>
+static int or_host_map(const char *who, const FrameT &f, int64_t n, const float *xyz, const uint8_t *rgb, const uint8_t *label,
+                       const uint8_t *has, int64_t index_base, int32_t fill_radius_px, uint32_t *out_index, float *out_depth,
+                       uint8_t *out_rgb, uint8_t *out_label, uint8_t *out_status, int32_t *out_source, int64_t *out_contributors,
+                       int64_t *out_occupied, int64_t *out_filled) {
   if (fill_radius_px < 0 || fill_radius_px > om::kMaxFill) {
-    set_global_error("pcp_ortho_host: fill radius %d outside 0..%d pixels", fill_radius_px, om::kMaxFill);
+    set_global_error("%s: fill radius %d outside 0..%d pixels", who, fill_radius_px, om::kMaxFill);
     return PCP_ERR_INVALID;
   }
   if (index_base < 0 || index_base > om::kMaxIndexEnd - n) {  // (index_base + n > 2^32 - 1, without the sum: it may overflow)
-    set_global_error("pcp_ortho_host: index_base %lld with %lld rows: global indices outside 0 .. 2^32 - 2",
+    set_global_error("%s: index_base %lld with %lld rows: global indices outside 0 .. 2^32 - 2", who,
                      static_cast<long long>(index_base), static_cast<long long>(n));
     return PCP_ERR_RANGE;
   }
-  const om::Frame f = or_frame(*frame);
-  const int32_t w = frame->width, h = frame->height;
+  const int32_t w = f.w, h = f.h;
   const size_t px = static_cast<size_t>(w) * static_cast<size_t>(h);
   std::vector<unsigned long long> keys;
   std::vector<uint32_t> payload, d2;
@@ -534,7 +616,7 @@ int pcp_ortho_host(const pcp_ortho_frame *frame, int64_t n, const float *xyz, co
       gray.resize(px);
     }
   } catch (const std::bad_alloc &) {
-    set_global_error("pcp_ortho_host: out of host memory for %d x %d pixels", w, h);
+    set_global_error("%s: out of host memory for %d x %d pixels", who, w, h);
     return PCP_ERR_NOMEM;
   }
   int64_t contributors = 0;
@@ -542,7 +624,7 @@ int pcp_ortho_host(const pcp_ortho_frame *frame, int64_t n, const float *xyz, co
     if (has && !has[i]) continue;
     int32_t pixel;
     uint32_t depth_bits;
-    if (!om::project(f, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], &pixel, &depth_bits)) continue;
+    if (!or_project(f, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], &pixel, &depth_bits)) continue;
     contributors += 1;
     const unsigned long long key = om::key_of(depth_bits, static_cast<uint32_t>(index_base + i));
     if (key < keys[static_cast<size_t>(pixel)]) {
@@ -585,6 +667,300 @@ int pcp_ortho_host(const pcp_ortho_frame *frame, int64_t n, const float *xyz, co
   if (out_occupied) *out_occupied = occupied;
   if (out_filled) *out_filled = filled;
   return PCP_OK;
+}
+
+// CY6: the closed-form cylinder of the rows that have a valid normal, and the frame that unrolls them
+static int cy_fit(int64_t n, const float *xyz, const float *normal, const uint8_t *has, const double *viewer, float gsd, pcp_cyl_frame *out,
+                  double *stats) {
+  const char *who = "pcp_cyl_fit_host";
+  auto dot = [](const double *p, const double *q) { return p[0] * q[0] + p[1] * q[1] + p[2] * q[2]; };
+  auto cross = [](const double *p, const double *q, double *r) {
+    r[0] = p[1] * q[2] - p[2] * q[1];
+    r[1] = p[2] * q[0] - p[0] * q[2];
+    r[2] = p[0] * q[1] - p[1] * q[0];
+  };
+  // 1. the rows
+  std::vector<int64_t> rows;
+  try {
+    for (int64_t i = 0; i < n; ++i) {
+      if (has && !has[i]) continue;
+      const float *p = xyz + 3 * i, *q = normal + 3 * i;
+      if (!(std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]) && std::isfinite(q[0]) && std::isfinite(q[1]) && std::isfinite(q[2])))
+        continue;
+      if (q[0] == 0.0f && q[1] == 0.0f && q[2] == 0.0f) continue;
+      rows.push_back(i);
+    }
+  } catch (const std::bad_alloc &) {
+    set_global_error("%s: out of host memory for %lld rows", who, static_cast<long long>(n));
+    return PCP_ERR_NOMEM;
+  }
+  const double cnt = static_cast<double>(rows.size());
+  if (rows.size() < 16) {
+    set_global_error("%s: %lld rows with a valid normal, a cylinder needs 16", who, static_cast<long long>(rows.size()));
+    return PCP_ERR_RANGE;
+  }
+  // 2. the axis: the direction the normals have least of
+  double m[6] = {0, 0, 0, 0, 0, 0}, cen[3] = {0, 0, 0};
+  for (const int64_t i : rows) {
+    const double q[3] = {normal[3 * i], normal[3 * i + 1], normal[3 * i + 2]};
+    m[0] += q[0] * q[0];
+    m[1] += q[0] * q[1];
+    m[2] += q[0] * q[2];
+    m[3] += q[1] * q[1];
+    m[4] += q[1] * q[2];
+    m[5] += q[2] * q[2];
+    for (int k = 0; k < 3; ++k) cen[k] += static_cast<double>(xyz[3 * i + k]);
+  }
+  double scale = 0.0;
+  for (int k = 0; k < 6; ++k) {
+    m[k] /= cnt;
+    scale = std::fmax(scale, std::fabs(m[k]));
+  }
+  for (int k = 0; k < 3; ++k) cen[k] /= cnt;
+  double sm[6], ev[3], a[3];
+  for (int k = 0; k < 6; ++k) sm[k] = m[k] / scale;
+  or_roots3(sm, ev);
+  if (!(ev[1] > 1e-4 * ev[2])) {
+    set_global_error("%s: no direction: the normals are parallel (second eigenvalue %.3g of %.3g), a plane and not a cylinder", who,
+                     ev[1] * scale, ev[2] * scale);
+    return PCP_ERR_RANGE;
+  }
+  or_eigenvector(sm, ev[0], a);
+  if (a[or_largest_component(a)] > 0.0)  // 5. rows run along +a, downwards in the picture: a's largest component is negative
+    for (int k = 0; k < 3; ++k) a[k] = -a[k];
+  // the fit's basis: e0 from the world axis a has least of, g0 = a x e0
+  int least = 0;
+  for (int k = 1; k < 3; ++k)
+    if (std::fabs(a[k]) < std::fabs(a[least])) least = k;
+  double e0[3], g0[3];
+  for (int k = 0; k < 3; ++k) e0[k] = (k == least ? 1.0 : 0.0) - a[least] * a[k];
+  const double el = std::sqrt(dot(e0, e0));
+  for (int k = 0; k < 3; ++k) e0[k] /= el;
+  cross(a, e0, g0);
+  // 3. Kasa's circle through the rows projected along the axis, about their centroid
+  double A[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+  for (const int64_t i : rows) {
+    const double d[3] = {xyz[3 * i] - cen[0], xyz[3 * i + 1] - cen[1], xyz[3 * i + 2] - cen[2]};
+    const double u = dot(d, e0), v = dot(d, g0), z = u * u + v * v;
+    A[0][0] += u * u;
+    A[0][1] += u * v;
+    A[0][2] += u;
+    A[1][1] += v * v;
+    A[1][2] += v;
+    A[0][3] -= u * z;
+    A[1][3] -= v * z;
+    A[2][3] -= z;
+  }
+  A[1][0] = A[0][1];
+  A[2][0] = A[0][2];
+  A[2][1] = A[1][2];
+  A[2][2] = cnt;
+  for (int col = 0; col < 3; ++col) {  // Gaussian elimination with partial pivoting
+    int piv = col;
+    for (int r = col + 1; r < 3; ++r)
+      if (std::fabs(A[r][col]) > std::fabs(A[piv][col])) piv = r;
+    for (int k = 0; k < 4; ++k) std::swap(A[col][k], A[piv][k]);
+    for (int r = col + 1; r < 3; ++r) {
+      const double f = A[r][col] / A[col][col];
+      for (int k = col; k < 4; ++k) A[r][k] -= f * A[col][k];
+    }
+  }
+  double sol[3];
+  for (int r = 2; r >= 0; --r) {
+    double s = A[r][3];
+    for (int k = r + 1; k < 3; ++k) s -= A[r][k] * sol[k];
+    sol[r] = s / A[r][r];
+  }
+  const double uc = -0.5 * sol[0], vc = -0.5 * sol[1];
+  const double R = std::sqrt(uc * uc + vc * vc - sol[2]);
+  if (!(R >= static_cast<double>(cy::kMinRadius) && R <= static_cast<double>(cy::kMaxRadius))) {
+    set_global_error("%s: fitted radius %.6g outside [0.05, 1000] metres", who, R);
+    return PCP_ERR_RANGE;
+  }
+  double c0[3];
+  for (int k = 0; k < 3; ++k) c0[k] = cen[k] + uc * e0[k] + vc * g0[k];
+  // 4. the side: a viewer within R of the axis looks from inside
+  int32_t side = -1;
+  if (viewer) {
+    const double w[3] = {viewer[0] - c0[0], viewer[1] - c0[1], viewer[2] - c0[2]};
+    const double wa = dot(w, a);
+    if (dot(w, w) - wa * wa <= R * R) side = 1;
+  }
+  double b0[3];
+  for (int k = 0; k < 3; ++k) b0[k] = static_cast<double>(side) * g0[k];
+  // 6. the seam, and the statistics
+  constexpr int kBins = 4096;
+  std::vector<uint8_t> occ(kBins, 0);
+  const double bin_width = cy::kTwoPi / kBins, g = static_cast<double>(gsd);
+  double h0 = INFINITY, h1 = -INFINITY, dev0 = INFINITY, dev1 = -INFINITY, sq = 0.0;
+  for (const int64_t i : rows) {
+    const double d[3] = {xyz[3 * i] - c0[0], xyz[3 * i + 1] - c0[1], xyz[3 * i + 2] - c0[2]};
+    const double s = dot(d, e0), t = dot(d, b0), hh = dot(d, a);
+    const double rho = std::sqrt(s * s + t * t), dev = rho - R;
+    sq += dev * dev;
+    dev0 = std::fmin(dev0, dev);
+    dev1 = std::fmax(dev1, dev);
+    h0 = std::fmin(h0, hh);
+    h1 = std::fmax(h1, hh);
+    if (rho > 0.0) occ[static_cast<size_t>(std::min(kBins - 1, static_cast<int>(std::floor(cy::angle(s, t) / bin_width))))] = 1;
+  }
+  int first = 0;
+  while (first < kBins && !occ[static_cast<size_t>(first)]) ++first;
+  int best = 0, best_next = 0, run = 0;
+  for (int k = 1; k <= kBins && first < kBins; ++k) {  // from the lowest occupied bin once round: every run ends at an occupied bin
+    const int pos = (first + k) % kBins;
+    if (!occ[static_cast<size_t>(pos)]) {
+      ++run;
+    } else {
+      if (run > best) {
+        best = run;
+        best_next = pos;
+      }
+      run = 0;
+    }
+  }
+  const double gap = best * bin_width;
+  const bool closed = gap * R < 2.0 * g;  // no room for the margins: the ring is closed and the seam stays at e0
+  double e[3], b[3];
+  if (closed) {
+    for (int k = 0; k < 3; ++k) e[k] = e0[k];
+  } else {
+    const double seam = best_next * bin_width - g / R;
+    const double cs = std::cos(seam), sn = std::sin(seam);
+    for (int k = 0; k < 3; ++k) e[k] = cs * e0[k] + sn * b0[k];
+  }
+  cross(a, e, b);
+  for (int k = 0; k < 3; ++k) b[k] *= static_cast<double>(side);
+  // 7. the raster and the window, in the frame's own arithmetic (CY2)
+  pcp_cyl_frame fr;
+  bool finite = std::isfinite(h0) && std::isfinite(h1) && std::isfinite(sq);
+  for (int k = 0; k < 3; ++k) {
+    fr.c[k] = static_cast<float>(c0[k] + (h0 - g) * a[k]);  // one pixel above the first row
+    fr.a[k] = static_cast<float>(a[k]);
+    fr.e[k] = static_cast<float>(e[k]);
+    fr.b[k] = static_cast<float>(b[k]);
+    finite = finite && std::isfinite(fr.c[k]) && std::isfinite(fr.a[k]) && std::isfinite(fr.e[k]) && std::isfinite(fr.b[k]);
+  }
+  if (!finite) {
+    set_global_error("%s: the fit is not finite", who);
+    return PCP_ERR_RANGE;
+  }
+  fr.radius = static_cast<float>(R);
+  fr.gsd = gsd;
+  fr.side = side;
+  fr.width = fr.height = 1;
+  fr.d_min = 0.0f;
+  fr.d_max = 1.0f;
+  const cy::Frame f = or_cyl_frame(fr);
+  float x1 = 0.0f, y1 = 0.0f, dlo = INFINITY, dhi = -INFINITY;
+  for (const int64_t i : rows) {
+    float x, y, depth;
+    if (!cy::coords(f, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], &x, &y, &depth)) continue;
+    x1 = std::fmax(x1, x);
+    y1 = std::fmax(y1, y);
+    dlo = std::fmin(dlo, depth);
+    dhi = std::fmax(dhi, depth);
+  }
+  const double around = cy::kTwoPi * static_cast<double>(fr.radius);
+  // (a closed ring: one column more when a row's x reaches the width, unless CY1's circumference rule forbids it -- theta
+  // within a rounding of 2 pi on a wide raster: that row then lies outside the map, the stated exception to "every row")
+  double wd = closed ? std::fmax(std::ceil(around / g), std::floor(static_cast<double>(x1)) + 1.0) : std::floor(static_cast<double>(x1)) + 2.0;
+  if (closed && wd * g > around + g) wd = std::ceil(around / g);
+  const double hd = std::floor(static_cast<double>(y1)) + 2.0;
+  if (!(wd <= om::kMaxSide && hd <= om::kMaxSide && wd * hd <= static_cast<double>(om::kMaxPixels))) {
+    const double fit = om::fit_gsd(closed ? around : around - gap * R, h1 - h0, 3.0);
+    set_global_error("%s: %.0f x %.0f pixels at gsd %g exceed 16384 a side or 2^26 pixels; the same extent fits at gsd %.6g", who, wd, hd, g, fit);
+    return PCP_ERR_RANGE;
+  }
+  fr.width = static_cast<int32_t>(wd);
+  fr.height = static_cast<int32_t>(hd);
+  fr.d_min = dlo - gsd;
+  fr.d_max = dhi + gsd;
+  char msg[320];
+  const int rc = or_check_cyl_frame(who, &fr, msg, sizeof msg);
+  if (rc != PCP_OK) {
+    set_global_error("%s (the fitted frame)", msg);
+    return PCP_ERR_RANGE;
+  }
+  *out = fr;
+  if (stats) {
+    stats[0] = cnt;
+    stats[1] = std::sqrt(sq / cnt);
+    stats[2] = dev0;
+    stats[3] = dev1;
+    stats[4] = cy::kTwoPi - gap;
+    for (int k = 0; k < 3; ++k) stats[5 + k] = ev[k] * scale;
+  }
+  return PCP_OK;
+}
+
+extern "C" {
+
+int pcp_ortho_host(const pcp_ortho_frame *frame, int64_t n, const float *xyz, const uint8_t *rgb, const uint8_t *label, const uint8_t *has,
+                   int64_t index_base, int32_t fill_radius_px, uint32_t *out_index, float *out_depth, uint8_t *out_rgb, uint8_t *out_label,
+                   uint8_t *out_status, int32_t *out_source, int64_t *out_contributors, int64_t *out_occupied, int64_t *out_filled) {
+  if (out_contributors) *out_contributors = 0;
+  if (out_occupied) *out_occupied = 0;
+  if (out_filled) *out_filled = 0;
+  if (!frame || n < 0 || (n > 0 && (!xyz || !rgb))) {
+    set_global_error("pcp_ortho_host: NULL frame, negative n or a missing xyz / rgb");
+    return PCP_ERR_INVALID;
+  }
+  char msg[320];
+  const int rc = or_check_frame("pcp_ortho_host", frame, msg, sizeof msg);
+  if (rc != PCP_OK) {
+    set_global_error("%s", msg);
+    return rc;
+  }
+  return or_host_map("pcp_ortho_host", or_frame(*frame), n, xyz, rgb, label, has, index_base, fill_radius_px, out_index, out_depth, out_rgb,
+                     out_label, out_status, out_source, out_contributors, out_occupied, out_filled);
+}
+
+int pcp_ortho_cyl_host(const pcp_cyl_frame *frame, int64_t n, const float *xyz, const uint8_t *rgb, const uint8_t *label, const uint8_t *has,
+                       int64_t index_base, int32_t fill_radius_px, uint32_t *out_index, float *out_depth, uint8_t *out_rgb,
+                       uint8_t *out_label, uint8_t *out_status, int32_t *out_source, int64_t *out_contributors, int64_t *out_occupied,
+                       int64_t *out_filled) {
+  if (out_contributors) *out_contributors = 0;
+  if (out_occupied) *out_occupied = 0;
+  if (out_filled) *out_filled = 0;
+  if (!frame || n < 0 || (n > 0 && (!xyz || !rgb))) {
+    set_global_error("pcp_ortho_cyl_host: NULL frame, negative n or a missing xyz / rgb");
+    return PCP_ERR_INVALID;
+  }
+  char msg[320];
+  const int rc = or_check_cyl_frame("pcp_ortho_cyl_host", frame, msg, sizeof msg);
+  if (rc != PCP_OK) {
+    set_global_error("%s", msg);
+    return rc;
+  }
+  return or_host_map("pcp_ortho_cyl_host", or_cyl_frame(*frame), n, xyz, rgb, label, has, index_base, fill_radius_px, out_index, out_depth,
+                     out_rgb, out_label, out_status, out_source, out_contributors, out_occupied, out_filled);
+}
+
+int pcp_cyl_angle_host(int64_t n, const double *s, const double *t, double *out_theta) {
+  if (n < 0 || (n > 0 && (!s || !t || !out_theta))) {
+    set_global_error("pcp_cyl_angle_host: negative n or a NULL array");
+    return PCP_ERR_INVALID;
+  }
+  for (int64_t i = 0; i < n; ++i) out_theta[i] = cy::angle(s[i], t[i]);
+  return PCP_OK;
+}
+
+int pcp_cyl_fit_host(int64_t n, const float *xyz, const float *normal, const uint8_t *has, const double *viewer, float gsd,
+                     pcp_cyl_frame *out, double out_stats[8]) {
+  if (n < 0 || (n > 0 && (!xyz || !normal)) || !out) {
+    set_global_error("pcp_cyl_fit_host: negative n, NULL xyz, NULL normal or NULL frame");
+    return PCP_ERR_INVALID;
+  }
+  if (!(std::isfinite(gsd) && gsd >= 1e-4f && gsd <= 1.0f)) {
+    set_global_error("pcp_cyl_fit_host: gsd %g outside [1e-4, 1]", static_cast<double>(gsd));
+    return PCP_ERR_INVALID;
+  }
+  if (viewer && !(std::isfinite(viewer[0]) && std::isfinite(viewer[1]) && std::isfinite(viewer[2]))) {
+    set_global_error("pcp_cyl_fit_host: the viewer is not finite");
+    return PCP_ERR_INVALID;
+  }
+  return cy_fit(n, xyz, normal, has, viewer, gsd, out, out_stats);
 }
 
 int pcp_ortho_fit_frame_host(int64_t n, const float *xyz, const uint8_t *has, const double *viewer, float gsd, pcp_ortho_frame *out) {

@@ -214,6 +214,9 @@ int pcp_ortho_texture(pcp_context *ctx, const pcp_ortho_texture_params *params, 
   // OT1
   const OrthoMap &m = ctx->ortho;
   if (!m.live) return set_error(ctx, PCP_ERR_STATE, "pcp_ortho_texture: no orthographic map (call pcp_ortho_begin)");
+  if (m.cyl)  // CY4
+    return set_error(ctx, PCP_ERR_STATE, "pcp_ortho_texture: the live map is a cylinder's unrolled map (pcp_ortho_begin_cyl); orthophotos "
+                     "of unrolled maps are not built");
   if (!m.finished) return set_error(ctx, PCP_ERR_STATE, "pcp_ortho_texture: pcp_ortho_finish has not run");
   if (!ctx->have_camera) return set_error(ctx, PCP_ERR_STATE, "pcp_ortho_texture: pcp_set_camera has not been called");
   const int32_t F = ctx->n_frames;

@@ -211,6 +211,16 @@
 //     one); without --facets 1 the file is byte for byte what it was.  Made on the GPU (pcp_facets, pcp_ortho_add_facet;
 //     DESIGN.md "Planar facets").  Refused: --gpus N above 1, --enableMLS 1, --streamColour 1, --normalRadius 0, and
 //     --orthoFrame facets without --facets 1.
+//   * --facetCylinders 0|1 (new, default 0; needs --facets 1): with 1 every facet that is not planar is fitted a cylinder from
+//     its points and their normals (closed form: the axis from the normals' scatter, the algebraic circle across it); every
+//     record of facets.json gains "kind" (0 neither, 1 planar, 2 cylindrical: fitted with an rms of rho - R of at most
+//     --facetMaxRms) and, where the fit succeeded, "cylinder" (c, a, e, b, radius, gsd, width, height, d_min, d_max, side, rows,
+//     rms, dev_min, dev_max, arc, eigenvalues; numbers as %.9g).  With --orthoMap 1 --orthoFrame facets the run writes one
+//     directory ortho/facet_<row>/ per cylindrical facet too: the facet unrolled along its arc, x along the arc and y along
+//     the axis at --orthoGsd metres per pixel both ways, the depth layer the radial deviation from the cylinder; its
+//     ortho_frame.json carries "kind": "cylinder" and the cylinder's frame.  Under --orthoTexture k the planar facets are
+//     textured and each cylindrical one is named on stderr as skipped.  Without the flag every file is byte for byte what it
+//     was.  Made on the GPU (pcp_ortho_begin_cyl; DESIGN.md "Cylindrical facets").
 #include <algorithm>
 #include <cfloat>
 #include <chrono>
@@ -327,6 +337,7 @@ struct Options {
   bool ortho_by_facet = false;        // --orthoFrame facets: one orthographic map per planar facet (ortho/facet_<row>/)
   pcp_facet_params facet{0.1f, 10.0f, 0.01f, 0.02f, 1000};  // --facetRadius / --facetAngle / --facetPlaneTol / --facetMaxCurvature / --facetMinPoints
   float facet_max_rms = 0.01f;        // --facetMaxRms m: a facet is planar up to this rms distance to its plane
+  bool facet_cylinders = false;       // --facetCylinders 1: fit a cylinder to every facet that is not planar; unrolled maps of those that are one
 };
 
 static bool parse_bool(const std::string &v) {  // boost::program_options bool semantics
@@ -466,6 +477,7 @@ static Options parse(int argc, char **argv) {
       o.normal_radius = r;
     }
     else if (a == "--facets") o.facets = parse_bool(next());
+    else if (a == "--facetCylinders") o.facet_cylinders = parse_bool(next());
     else if (a == "--facetRadius" || a == "--facetAngle" || a == "--facetPlaneTol" || a == "--facetMaxCurvature" || a == "--facetMaxRms") {
       const std::string v = next();
       char *end = nullptr;
@@ -684,6 +696,8 @@ static Options parse(int argc, char **argv) {
                              "map; maps of the smoothed cloud are not built)");
   if (o.ortho_by_facet && !o.facets)
     throw std::runtime_error("the option '--orthoFrame facets' needs the facets of the map (--facets 1)");
+  if (o.facet_cylinders && !o.facets)
+    throw std::runtime_error("the option '--facetCylinders 1' needs the facets of the map (--facets 1)");
   if (o.facets && o.gpus > 1)
     throw std::runtime_error("the option '--facets 1' does not work with '--gpus N' above 1 (an index shard sees only its own "
                              "points: the forests of the shards would have to be united across GPUs, which is not built)");
@@ -771,7 +785,8 @@ static void usage(std::ostream &os) {
         "  --facetPlaneTol arg (=0.01)           With --facets: ... and each lies this close (m) to the other's tangent plane (1e-4..0.1)\n"
         "  --facetMaxCurvature arg (=0.02)       With --facets: points of a larger curvature take no part (0..1)\n"
         "  --facetMinPoints arg (=1000)          With --facets: a facet has at least this many points\n"
-        "  --facetMaxRms arg (=0.01)             With --facets: a facet is planar up to this rms distance (m) to its plane\n";
+        "  --facetMaxRms arg (=0.01)             With --facets: a facet is planar up to this rms distance (m) to its plane\n"
+        "  --facetCylinders arg (=0)             With --facets: fit a cylinder to every facet that is not planar; with --orthoFrame facets unroll those that are one\n";
 }
 
 class Processor {
@@ -829,6 +844,9 @@ class Processor {
   std::vector<float> ortho_fit_xyz;    // --orthoMap 1 with --enableMLS 1 (one-shot): the crop the chain smoothed, for the frame
   std::vector<uint32_t> ortho_index;   // --orthoMap 1: the index layer, for the crack layers --crackFuse 1 adds
   Facets facets_;                      // --facets 1: the partition, for the per-facet maps and the cracks' "facet"
+  std::vector<uint8_t> facet_kind_;    // --facetCylinders 1, per facet: 0 neither, 1 planar, 2 cylindrical
+  std::vector<pcp_cyl_frame> facet_cyl_;  // --facetCylinders 1, per facet: the fitted cylinder's frame at --orthoGsd (where the fit succeeded)
+  std::vector<float> map_normals_;     // --facetCylinders 1: the map normals the cylinders are fitted from (3 per point)
   pcp_ortho_frame ortho_frame_used{};
 
   void loadImagesAndOdometry() {  // :965-1005
@@ -1644,7 +1662,36 @@ class Processor {
       std::snprintf(b, sizeof(b), "%.9g", v);
       return std::string(b);
     };
-    size_t planar = 0;
+    size_t planar = 0, cylindrical = 0;
+    // --facetCylinders 1: the cylinder of every facet that is not planar, from its points and their normals
+    facet_cyl_.assign(opt.facet_cylinders ? facets_.ids.size() : 0, pcp_cyl_frame{});
+    std::vector<pcp_cyl_frame> &cyl = facet_cyl_;  // (kept: writeOrthoMapsByFacet unrolls the cylindrical facets through these frames)
+    std::vector<double> cyl_stats(8 * cyl.size(), 0.0);
+    std::vector<uint8_t> fitted(cyl.size(), 0);
+    if (opt.facet_cylinders) {
+      const size_t n = cloud.size();
+      map_normals_.assign(3 * n, 0.0f);
+      if (pcp_normals_fetch(dev.get(), map_normals_.data(), nullptr, nullptr) != PCP_OK)
+        throw std::runtime_error(std::string("pcp_hip: ") + pcp_last_error(dev.get()));
+      const std::vector<float> xyz = interleavedMap();
+      double viewer[3];
+      const bool seen = meanKeyframePosition(viewer);
+      std::vector<uint8_t> member(n);
+      facet_kind_.assign(facets_.ids.size(), 0);
+      for (size_t r = 0; r < facets_.ids.size(); ++r) {
+        if (facets_.planar[r]) {
+          facet_kind_[r] = 1;
+          continue;
+        }
+        for (size_t i = 0; i < n; ++i) member[i] = facets_.label[i] == facets_.ids[r] ? 1 : 0;
+        std::string why;
+        fitted[r] = Device::orthoFitCylinder(static_cast<int64_t>(n), xyz.data(), map_normals_.data(), member.data(), seen ? viewer : nullptr,
+                                             opt.ortho_gsd, &cyl[r], cyl_stats.data() + 8 * r, &why) ? 1 : 0;
+        if (!fitted[r]) std::cout << "facet " << facets_.ids[r] << ": no cylinder (" << why << ")" << std::endl;
+        if (fitted[r] && cyl_stats[8 * r + 1] <= static_cast<double>(opt.facet_max_rms)) facet_kind_[r] = 2, ++cylindrical;
+      }
+    }
+    auto vec3 = [&](const float *v) { return "[" + num(v[0]) + ", " + num(v[1]) + ", " + num(v[2]) + "]"; };
     f << "[";
     for (size_t r = 0; r < facets_.ids.size(); ++r) {
       const double *pl = facets_.plane.data() + 7 * r;
@@ -1653,19 +1700,34 @@ class Processor {
       f << (r ? ",\n " : "\n ") << "{\"id\": " << facets_.ids[r] << ", \"points\": " << facets_.rows[10 * r] << ", \"centroid\": [" << num(pl[0]) << ", "
         << num(pl[1]) << ", " << num(pl[2]) << "], \"normal\": [" << num(pl[3]) << ", " << num(pl[4]) << ", " << num(pl[5]) << "], \"rms\": "
         << num(pl[6]) << ", \"planar\": " << (facets_.planar[r] ? "true" : "false") << ", \"box_min\": [" << num(bx[0]) << ", " << num(bx[1]) << ", "
-        << num(bx[2]) << "], \"box_max\": [" << num(bx[3]) << ", " << num(bx[4]) << ", " << num(bx[5]) << "]}";
+        << num(bx[2]) << "], \"box_max\": [" << num(bx[3]) << ", " << num(bx[4]) << ", " << num(bx[5]) << "]";
+      if (opt.facet_cylinders) {
+        f << ", \"kind\": " << static_cast<int>(facet_kind_[r]);
+        if (fitted[r]) {
+          const pcp_cyl_frame &c = cyl[r];
+          const double *st = cyl_stats.data() + 8 * r;
+          f << ", \"cylinder\": {\"c\": " << vec3(c.c) << ", \"a\": " << vec3(c.a) << ", \"e\": " << vec3(c.e) << ", \"b\": " << vec3(c.b)
+            << ", \"radius\": " << num(c.radius) << ", \"gsd\": " << num(c.gsd) << ", \"width\": " << c.width << ", \"height\": " << c.height
+            << ", \"d_min\": " << num(c.d_min) << ", \"d_max\": " << num(c.d_max) << ", \"side\": " << c.side
+            << ", \"rows\": " << static_cast<long long>(st[0]) << ", \"rms\": " << num(st[1]) << ", \"dev_min\": " << num(st[2])
+            << ", \"dev_max\": " << num(st[3]) << ", \"arc\": " << num(st[4]) << ", \"eigenvalues\": [" << num(st[5]) << ", " << num(st[6])
+            << ", " << num(st[7]) << "]}";
+        }
+      }
+      f << "}";
     }
     f << "\n]\n";
     f.close();
     if (!f) throw std::runtime_error("Couldn't save the facets of the map.");
+    if (opt.facet_cylinders) std::cout << "Cylindrical facets: " << cylindrical << " of " << facets_.ids.size() - planar << " that are not planar" << std::endl;
     std::cout << "Facets saved to: " << stem << "facet_label.npy and facets.json, " << facets_.facet_points << " facet points, " << facets_.components
               << " components, " << facets_.ids.size() << " facets, " << planar << " planar" << std::endl;
   }
 
   // --orthoMap 1 --orthoFrame facets: one map per planar facet, on a frame fitted to the facet's own points (seen from the mean
   // keyframe position) and drawn from those points only, into <out>ortho/facet_<row>/
-  void writeOrthoMapsByFacet() {
-    Device &dev = gpu->device(0);
+  // the map the run read as interleaved rows, and the mean keyframe position (false: no keyframes)
+  std::vector<float> interleavedMap() const {
     const size_t n = cloud.size();
     std::vector<float> xyz(3 * n);
     for (size_t i = 0; i < n; ++i) {
@@ -1673,15 +1735,42 @@ class Processor {
       xyz[3 * i + 1] = cloud.y[i];
       xyz[3 * i + 2] = cloud.z[i];
     }
-    double viewer[3] = {0.0, 0.0, 0.0};
+    return xyz;
+  }
+  bool meanKeyframePosition(double viewer[3]) const {
+    viewer[0] = viewer[1] = viewer[2] = 0.0;
     for (const Frame &k : keyframes) {
       viewer[0] += k.pose.x / static_cast<double>(keyframes.size());
       viewer[1] += k.pose.y / static_cast<double>(keyframes.size());
       viewer[2] += k.pose.z / static_cast<double>(keyframes.size());
     }
+    return !keyframes.empty();
+  }
+
+  void writeOrthoMapsByFacet() {
+    Device &dev = gpu->device(0);
+    const size_t n = cloud.size();
+    const std::vector<float> xyz = interleavedMap();
+    double viewer[3];
+    (void)meanKeyframePosition(viewer);
     std::vector<uint8_t> member(n);
-    size_t maps = 0;
+    size_t maps = 0, unrolled = 0;
     for (size_t r = 0; r < facets_.ids.size(); ++r) {
+      if (opt.facet_cylinders && facet_kind_[r] == 2) {  // the facet unrolled through its cylinder (DESIGN.md "Cylindrical facets")
+        const int32_t id = facets_.ids[r];
+        const pcp_cyl_frame &cf = facet_cyl_[r];  // (the frame facets.json records: fitted once, in writeFacets)
+        {
+          Phase ph("ortho_gpu_s");
+          dev.orthoBeginCyl(cf);
+          (void)dev.orthoAddFacet(id, 0);
+        }
+        if (opt.ortho_texture)
+          std::cerr << "facet " << id << " (ortho/facet_" << r << "/): cylindrical, skipped by --orthoTexture (orthophotos of unrolled maps are not built)"
+                    << std::endl;
+        writeOrthoFiles(opt.outputPath + "ortho/facet_" + std::to_string(r) + "/", &cf);
+        ++unrolled;
+        continue;
+      }
       if (!facets_.planar[r]) continue;
       const int32_t id = facets_.ids[r];
       {
@@ -1698,6 +1787,7 @@ class Processor {
       ++maps;
     }
     std::cout << "Orthographic maps by facet: " << maps << " planar facets of " << facets_.ids.size() << std::endl;
+    if (opt.facet_cylinders) std::cout << "Unrolled maps by facet: " << unrolled << " cylindrical facets of " << facets_.ids.size() << std::endl;
   }
 
   // --orthoMap 1: the frame.  auto: the plane fitted to the finite points of the map the run read, seen from the side of the
@@ -1760,16 +1850,17 @@ class Processor {
     writeOrthoFiles();
   }
   // the map begun on the colour context, finished with --orthoFill, as <out>ortho/ortho_*.npy and ortho_frame.json; then dropped
-  void writeOrthoFiles(const std::string &stem_in = std::string()) {
+  // (cyl: the map was begun under this cylinder's frame -- no orthophoto, and ortho_frame.json holds the cylinder)
+  void writeOrthoFiles(const std::string &stem_in = std::string(), const pcp_cyl_frame *cyl = nullptr) {
     const std::string stem = stem_in.empty() ? opt.outputPath + "ortho/" : stem_in;
     Device &dev = gpu->device(0);
     OrthoMap m;
     {
       Phase ph("ortho_finish_gpu_s");
       m = dev.orthoFetch(opt.ortho_fill, opt.fuse_masks);
-      if (!opt.ortho_texture) dev.orthoEnd();
+      if (!opt.ortho_texture || cyl) dev.orthoEnd();
     }
-    if (opt.ortho_texture) {
+    if (opt.ortho_texture && !cyl) {
       struct End {  // also on the way out of an exception
         Device &d;
         ~End() { (void)pcp_ortho_end(d.get()); }
@@ -1791,10 +1882,17 @@ class Processor {
       return std::string(b);
     };
     auto vec = [&](const float *v) { return "[" + num(v[0]) + ", " + num(v[1]) + ", " + num(v[2]) + "]"; };
-    f << "{\"o\": " << vec(m.frame.o) << ", \"u\": " << vec(m.frame.u) << ", \"v\": " << vec(m.frame.v) << ", \"n\": " << vec(m.frame.n)
-      << ", \"gsd\": " << num(m.frame.gsd) << ", \"width\": " << m.frame.width << ", \"height\": " << m.frame.height
-      << ", \"d_min\": " << num(m.frame.d_min) << ", \"d_max\": " << num(m.frame.d_max) << ", \"fill_radius\": " << opt.ortho_fill
-      << ", \"contributors\": " << m.contributors << ", \"occupied\": " << m.occupied << ", \"filled\": " << m.filled << "}\n";
+    if (cyl)
+      f << "{\"kind\": \"cylinder\", \"c\": " << vec(cyl->c) << ", \"a\": " << vec(cyl->a) << ", \"e\": " << vec(cyl->e) << ", \"b\": " << vec(cyl->b)
+        << ", \"radius\": " << num(cyl->radius) << ", \"side\": " << cyl->side << ", \"gsd\": " << num(cyl->gsd) << ", \"width\": " << cyl->width
+        << ", \"height\": " << cyl->height << ", \"d_min\": " << num(cyl->d_min) << ", \"d_max\": " << num(cyl->d_max)
+        << ", \"fill_radius\": " << opt.ortho_fill << ", \"contributors\": " << m.contributors << ", \"occupied\": " << m.occupied
+        << ", \"filled\": " << m.filled << "}\n";
+    else
+      f << "{\"o\": " << vec(m.frame.o) << ", \"u\": " << vec(m.frame.u) << ", \"v\": " << vec(m.frame.v) << ", \"n\": " << vec(m.frame.n)
+        << ", \"gsd\": " << num(m.frame.gsd) << ", \"width\": " << m.frame.width << ", \"height\": " << m.frame.height
+        << ", \"d_min\": " << num(m.frame.d_min) << ", \"d_max\": " << num(m.frame.d_max) << ", \"fill_radius\": " << opt.ortho_fill
+        << ", \"contributors\": " << m.contributors << ", \"occupied\": " << m.occupied << ", \"filled\": " << m.filled << "}\n";
     f.close();
     if (!f) throw std::runtime_error("Couldn't save the orthographic map's frame.");
     std::cout << "Orthographic map saved to: " << stem << "ortho_*.npy and ortho_frame.json, " << m.frame.width << " x " << m.frame.height

@@ -285,6 +285,15 @@ class Device {
     check(pcp_ortho_begin(ctx_, &frame));
     ortho_frame_ = frame;  // (only of a begin the library took: a refused one leaves the live map, and its frame, as they were)
   }
+  // the same accumulator under a cylinder's frame, unrolled along its arc (pcp_ortho_begin_cyl; DESIGN.md "Cylindrical facets"):
+  // the adds, orthoFetch, orthoStats and orthoEnd work on either kind; orthoTexture is refused on this one
+  void orthoBeginCyl(const pcp_cyl_frame &frame) {
+    check(pcp_ortho_begin_cyl(ctx_, &frame));
+    ortho_frame_ = pcp_ortho_frame{};  // (orthoFetch sizes its layers by the raster of the last begin the library took)
+    ortho_frame_.gsd = frame.gsd;
+    ortho_frame_.width = frame.width;
+    ortho_frame_.height = frame.height;
+  }
   int64_t orthoAdd(int64_t index_base = 0) {  // the coloured rows of the current colour result; returns the contributors
     int64_t rows = 0;
     check(pcp_ortho_add(ctx_, index_base, &rows));
@@ -356,6 +365,17 @@ class Device {
     if (pcp_ortho_fit_frame_host(n, xyz, has, viewer, gsd, &f) != PCP_OK)
       throw std::runtime_error(std::string("pcp_hip: ") + pcp_last_error(nullptr));
     return f;
+  }
+  // the cylinder of the rows that have a valid normal (3 floats per row) and the frame that unrolls them (pcp_cyl_fit_host);
+  // stats (nullable, 8 doubles): rows, rms, least and greatest rho - R, occupied arc, the normals' three eigenvalues.  false: the
+  // rows are no cylinder this fit can give (PCP_ERR_RANGE; *why, nullable, receives the message); anything else throws
+  static bool orthoFitCylinder(int64_t n, const float *xyz, const float *normal, const uint8_t *has, const double *viewer, float gsd,
+                               pcp_cyl_frame *out, double *stats = nullptr, std::string *why = nullptr) {
+    const int rc = pcp_cyl_fit_host(n, xyz, normal, has, viewer, gsd, out, stats);
+    if (rc == PCP_OK) return true;
+    if (rc != PCP_ERR_RANGE) throw std::runtime_error(std::string("pcp_hip: ") + pcp_last_error(nullptr));
+    if (why) *why = pcp_last_error(nullptr);
+    return false;
   }
 
   // ---- geometry maps: a normal per point of the uploaded map, once per upload (pcp_estimate_normals; what

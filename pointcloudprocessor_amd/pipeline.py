@@ -234,7 +234,8 @@ class PointCloudColorizer:
         return out
 
     def facets(self, xyz=None, normal_radius: float = 0.1, link_radius: float = 0.1, angle_deg: float = 10.0, plane_tol: float = 0.01,
-               max_curvature: float = 0.02, min_points: int = 1000, max_rms: float = 0.01) -> dict:
+               max_curvature: float = 0.02, min_points: int = 1000, max_rms: float = 0.01, cylinders: bool = False,
+               cylinder_gsd: float = 0.01, viewer=None) -> dict:
         """The planar facets of the uploaded map ("Planar facets"): the connected components of the map points
         under a link of distance, normal angle and mutual plane distance, one per face of the structure.  The normals are
         estimated at normal_radius when none of that radius are live.  dict of capi.Context.facets (label, ids, rows, box,
@@ -244,6 +245,11 @@ class PointCloudColorizer:
 
         xyz: the uploaded map as the caller holds it, (n, 3) or (x, y, z) -- a facet's integers are relative to its root point,
         whose coordinates are read from it; nothing of it is kept here.
+
+        cylinders ("Cylindrical facets"): every facet that is not planar is fitted a cylinder from its points and
+        their normals (capi.cyl_fit_host at cylinder_gsd, seen from `viewer`; None: the mean keyframe position), and the dict
+        gains cylinder -- a list per facet of None (planar, or the fit was refused) or dict(frame, stats) -- and kind (F,) uint8:
+        0 neither, 1 planar, 2 cylindrical (not planar, fitted, rms <= max_rms).  Without it the dict is what it always was.
 
         An index shard sees only its own points, so world > 1 raises ValueError.  (The forests of the shards would have to be
         united across the cells that two ranks share; not built.)"""
@@ -264,17 +270,39 @@ class PointCloudColorizer:
             plane[r] = capi.facet_plane_host(xyz[fid], row)
         out["plane"] = plane
         out["planar"] = (plane[:, 6] <= max_rms) & (np.abs(plane[:, 3:6]).max(axis=1, initial=0.0) > 0) if len(plane) else np.zeros(0, bool)
+        if cylinders:
+            if viewer is None:
+                viewer = getattr(self.engine, "mean_keyframe_position", None)
+            normal = ctx.normals_fetch()["normal"]
+            out["cylinder"] = [None] * len(out["ids"])
+            out["kind"] = out["planar"].astype(np.uint8)
+            for r in np.flatnonzero(~out["planar"]):
+                try:
+                    frame, stats = capi.cyl_fit_host(xyz, normal, cylinder_gsd, has=(out["label"] == out["ids"][r]).astype(np.uint8),
+                                                     viewer=viewer)
+                except capi.PcpError as e:
+                    if e.code != capi.PCP_ERR_RANGE:  # (RANGE: the facet is no cylinder this fit can give; anything else is a fault)
+                        raise
+                    continue
+                out["cylinder"][r] = dict(frame=frame.as_dict(), stats=stats)
+                if stats["rms"] <= max_rms:
+                    out["kind"][r] = 2
         self.last_facets = out
         return out
 
     def ortho_maps_by_facet(self, gsd: float, xyz=None, facets: dict | None = None, fill_radius: int = 0, viewer=None,
-                            texture: dict | None = None) -> list:
+                            texture: dict | None = None, cylinders: bool = False) -> list:
         """One orthographic map per planar facet of the colour result run() left on the device: for every planar row of
         `facets` (the dict facets() returned; None: the one its last call on this object left) a frame fitted on the host to
         the facet's points (capi.ortho_fit_frame_host with has = (label == id)) at `gsd` metres per pixel, seen from `viewer`
         (None: the mean keyframe position), then begin / ortho_add_facet / finish / fetch / end.  Only the facet's own rows
         are drawn: a wall that crosses the frame's window does not show as a line.  A list, in the table's order, of the
         dicts ortho_map returns, each with facet (its id) and row (its row of the table).  texture: as ortho_map's.
+
+        cylinders ("Cylindrical facets"): the cylindrical facets of a facets(..., cylinders=True) are drawn too, each
+        unrolled through a cylinder fitted at `gsd` from the facet's points and the live normals (ctx.normals_fetch), and every
+        map's dict carries kind (1 planar, 2 cylindrical).  texture is applied to the planar facets only: orthophotos of
+        unrolled maps are not built.
 
         An index shard sees only its own points, so world > 1 raises ValueError."""
         import numpy as np
@@ -293,20 +321,35 @@ class PointCloudColorizer:
             viewer = getattr(self.engine, "mean_keyframe_position", None)
         fuse_labels = bool(getattr(self.engine, "fuse_labels", False))
         maps = []
-        for row in np.flatnonzero(facets["planar"]):
+        if cylinders:
+            if "kind" not in facets:
+                raise ValueError("ortho_maps_by_facet: cylinders asked of facets without them (call facets(..., cylinders=True))")
+            kinds = np.asarray(facets["kind"])
+            normal = ctx.normals_fetch()["normal"] if (kinds == 2).any() else None
+        else:
+            kinds = np.asarray(facets["planar"]).astype(np.uint8)
+        for row in np.flatnonzero(kinds > 0):
             fid = int(facets["ids"][row])
-            frame = capi.ortho_fit_frame_host(xyz, gsd, has=(facets["label"] == fid).astype(np.uint8), viewer=viewer)
-            ctx.ortho_begin(frame)
+            member = (facets["label"] == fid).astype(np.uint8)
+            if kinds[row] == 1:
+                frame = capi.ortho_fit_frame_host(xyz, gsd, has=member, viewer=viewer)
+                ctx.ortho_begin(frame)
+                frame = capi.ortho_frame(frame).as_dict()
+            else:
+                frame, _ = capi.cyl_fit_host(xyz, normal, gsd, has=member, viewer=viewer)
+                ctx.ortho_begin_cyl(frame)
+                frame = frame.as_dict()
             try:
                 contributors = ctx.ortho_add_facet(fid, 0)
                 occupied, filled = ctx.ortho_finish(fill_radius)
                 out = ctx.ortho_fetch(want_label=fuse_labels)
-                if texture is not None:
+                if texture is not None and kinds[row] == 1:
                     out["photo"] = ctx.ortho_texture(**texture)
             finally:
                 ctx.ortho_end()
-            out.update(frame=capi.ortho_frame(frame).as_dict(), contributors=contributors, occupied=occupied, filled=filled, facet=fid,
-                       row=int(row))
+            out.update(frame=frame, contributors=contributors, occupied=occupied, filled=filled, facet=fid, row=int(row))
+            if cylinders:
+                out["kind"] = int(kinds[row])
             maps.append(out)
         return maps
 
