@@ -83,7 +83,9 @@ extern "C" {
                                 entry points added, no layout changed: pcp_facets / _fetch / _host, pcp_facet_plane_host,
                                 pcp_ortho_add_facet (planar facets of the map; nothing runs unless called);
                                 entry points added, no layout changed: pcp_ortho_begin_cyl, pcp_ortho_cyl_host, pcp_cyl_angle_host,
-                                pcp_cyl_fit_host (cylindrical facets and their unrolled maps; nothing runs unless called) */
+                                pcp_cyl_fit_host (cylindrical facets and their unrolled maps; nothing runs unless called);
+                                entry points added, no layout changed: pcp_ortho_texture_cyl, pcp_ortho_texture_points_cyl_host,
+                                pcp_cyl_sincos_host (orthophotos of unrolled maps; nothing runs unless called) */
 
 #define PCP_OK 0
 #define PCP_ERR_INVALID (-1) /* bad argument */
@@ -1257,7 +1259,7 @@ int pcp_ortho_add_facet(pcp_context *ctx, int32_t facet_id, int64_t index_base, 
  * pcp_ortho_begin_cyl starts the accumulator of pcp_ortho_begin under such a frame; either begin drops the live map of either
  * kind, a refused one leaves it.  pcp_ortho_add / _add_facet / _add_packed / _finish / _fetch / _stats / _end work on either kind,
  * with the same keys, merge, payload, fill and layers.  pcp_ortho_texture on a cylinder's map: PCP_ERR_STATE (orthophotos of
- * unrolled maps are not built).
+ * unrolled maps are not built by that call: pcp_ortho_texture_cyl, below).
  * pcp_ortho_cyl_host: pcp_ortho_host under a cylinder's frame, bit for bit what the device gives.
  * pcp_cyl_angle_host: theta of n pairs (s, t) of doubles by the same sequence (host only; (0, 0) gives a NaN).
  * pcp_cyl_fit_host: host only, fp64, closed form: the cylinder of the rows whose has byte is set (NULL: all), whose coordinates
@@ -1286,6 +1288,21 @@ int pcp_ortho_cyl_host(const pcp_cyl_frame *frame, int64_t n, const float *xyz, 
 int pcp_cyl_angle_host(int64_t n, const double *s, const double *t, double *out_theta);
 int pcp_cyl_fit_host(int64_t n, const float *xyz, const float *normal, const uint8_t *has, const double *viewer, float gsd,
                      pcp_cyl_frame *out, double out_stats[8]);
+/* Orthophotos of unrolled maps ("Orthophotos of unrolled maps", CT1-CT8): pcp_ortho_texture for the finished map of
+ * pcp_ortho_begin_cyl.  Same parameters, layers, counts, checks and check order as pcp_ortho_texture; a live planar map is
+ * PCP_ERR_STATE (pcp_ortho_texture is its call).  Only the surface point differs, the inverse of "pixel" above in fp64:
+ *   xf = (Xg + 0.5) / k, yf likewise; arc = xf / inv, hh = yf / inv; theta = arc / R; rho = R + side d (d: the depth behind the
+ *   fine pixel, as pcp_ortho_texture finds it; the interpolation does not wrap across the seam); rho <= 0: no surface (status 0);
+ *   p = (float)(c + ((rho cos theta) e + (rho sin theta) b + hh a)), sine and cosine by one fixed sequence of fp64 operations.
+ * Reads the map, the depth maps and the keyframe images, writes none of them.  Kernel time under PCP_K_MISC.
+ * pcp_ortho_texture_points_cyl_host: pcp_ortho_texture_points_host under a cylinder's frame (host only; out_ok 0 and xyz 0
+ * where there is no surface).  pcp_cyl_sincos_host: the sine and cosine of n angles in [0, 64) by that sequence (host only);
+ * a negative n, a NULL array or an angle outside [0, 64) or not finite: PCP_ERR_INVALID.  Messages at pcp_last_error(NULL). */
+int pcp_ortho_texture_cyl(pcp_context *ctx, const pcp_ortho_texture_params *params, uint8_t *out_rgb, uint8_t *out_mask,
+                          uint8_t *out_status, int16_t *out_view, uint8_t *out_count, int64_t out_counts[4]);
+int pcp_ortho_texture_points_cyl_host(const pcp_cyl_frame *frame, const pcp_ortho_texture_params *params, const int32_t *source,
+                                      const float *depth, float *out_xyz, uint8_t *out_ok);
+int pcp_cyl_sincos_host(int64_t n, const double *theta, double *out_sin, double *out_cos);
 
 /* ---- precondition of the match-back(PointCloudProcessor.cpp:480-482,571) ------------------------------- */
 /* Number of map points that have ANOTHER map point closer than `radius` (fp32 squared distance, strict <, as

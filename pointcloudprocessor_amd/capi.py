@@ -502,6 +502,36 @@ def ortho_texture_points_host(frame, source, depth, scale: int, interpolate: boo
     return out
 
 
+def ortho_texture_points_cyl_host(frame, source, depth, scale: int, interpolate: bool = True, max_step: float = 0.05, rect=None) -> dict:
+    """ortho_texture_points_host under a cylinder's frame (pcp_ortho_texture_points_cyl_host: no context, no GPU; DESIGN.md
+    "Orthophotos of unrolled maps", CT2, CT5): the same arguments and the same dict; ok is 0 where rho <= 0 too."""
+    L = load()
+    f = cyl_frame(frame)
+    p = ortho_texture_params(scale, 1, interpolate, max_step, rect)
+    source = np.ascontiguousarray(source, np.int32)
+    depth = np.ascontiguousarray(depth, np.float32)
+    if source.size != int(f.width) * int(f.height) or depth.size != source.size:
+        raise ValueError("ortho_texture_points_cyl_host: source and depth are the map's height x width layers")
+    fh, fw = _ortho_texture_shape(f, p)
+    out = dict(xyz=np.empty((fh, fw, 3), np.float32), ok=np.empty((fh, fw), np.uint8))
+    rc = L.pcp_ortho_texture_points_cyl_host(C.byref(f), C.byref(p), _ptr(source), _ptr(depth), _ptr(out["xyz"]), _ptr(out["ok"]))
+    if rc != PCP_OK:
+        raise PcpError(rc, L.pcp_last_error(None).decode())
+    return out
+
+
+def cyl_sincos_host(theta) -> tuple[np.ndarray, np.ndarray]:
+    """(sin, cos) of the angles theta in [0, 64) by the kernels' fixed sequence of fp64 operations (pcp_cyl_sincos_host; DESIGN.md
+    "Orthophotos of unrolled maps", CT1)."""
+    L = load()
+    theta = np.ascontiguousarray(theta, np.float64).reshape(-1)
+    s, c = np.empty(theta.shape, np.float64), np.empty(theta.shape, np.float64)
+    rc = L.pcp_cyl_sincos_host(C.c_int64(theta.size), _ptr(theta), _ptr(s), _ptr(c))
+    if rc != PCP_OK:
+        raise PcpError(rc, L.pcp_last_error(None).decode())
+    return s, c
+
+
 def normals_moments_host(radius: float, xyz) -> np.ndarray:
     """The moments of pcp_estimate_normals computed on the CPU by brute force over the pairs, with the arithmetic the kernel
     uses (pcp_normals_moments_host: no context, no GPU; DESIGN.md "Geometry maps", GN2-GN4).  xyz (n, 3) float32, n <= 65536:
@@ -1427,16 +1457,24 @@ class Context:
         """The orthophoto of the finished map at `scale` fine pixels per ortho pixel and axis, coloured straight from the
         keyframe images (pcp_ortho_texture; DESIGN.md, "Orthophotos").  rect: (x0, y0, w, h) in ortho pixels, None: the whole
         raster.  dict(rgb (h k, w k, 3), mask, status, view (int16), count, surface, textured, unseen, skipped_pairs)."""
+        return self._ortho_texture(self.lib.pcp_ortho_texture, scale, views, interpolate, max_step, rect)
+
+    def _ortho_texture(self, fn, scale, views, interpolate, max_step, rect) -> dict:
         p = ortho_texture_params(scale, views, interpolate, max_step, rect)
         f = getattr(self, "_ortho_frame", None)
         fh, fw = _ortho_texture_shape(f, p) if f is not None else (0, 0)
         out = dict(rgb=np.empty((fh, fw, 3), np.uint8), mask=np.empty((fh, fw), np.uint8), status=np.empty((fh, fw), np.uint8),
                    view=np.empty((fh, fw), np.int16), count=np.empty((fh, fw), np.uint8))
         counts = np.zeros(4, np.int64)
-        self._check(self.lib.pcp_ortho_texture(self.h, C.byref(p), _ptr(out["rgb"]), _ptr(out["mask"]), _ptr(out["status"]),
-                                               _ptr(out["view"]), _ptr(out["count"]), _ptr(counts)))
+        self._check(fn(self.h, C.byref(p), _ptr(out["rgb"]), _ptr(out["mask"]), _ptr(out["status"]), _ptr(out["view"]),
+                       _ptr(out["count"]), _ptr(counts)))
         out.update(surface=int(counts[0]), textured=int(counts[1]), unseen=int(counts[2]), skipped_pairs=int(counts[3]))
         return out
+
+    def ortho_texture_cyl(self, scale: int, views: int = 1, interpolate: bool = True, max_step: float = 0.05, rect=None) -> dict:
+        """ortho_texture for the finished unrolled map of a cylinder (pcp_ortho_texture_cyl; DESIGN.md, "Orthophotos of unrolled
+        maps"): the same keywords and the same dict.  A planar map is refused, as ortho_texture refuses a cylinder's."""
+        return self._ortho_texture(self.lib.pcp_ortho_texture_cyl, scale, views, interpolate, max_step, rect)
 
     # -- geometry maps (DESIGN.md, "Geometry maps") ---------------------------------
     def estimate_normals(self, radius: float, want_moments: bool = False):

@@ -221,25 +221,7 @@ static om::Frame or_frame(const pcp_ortho_frame &c) {
   return f;
 }
 
-static cy::Frame or_cyl_frame(const pcp_cyl_frame &c) {
-  cy::Frame f;
-  for (int k = 0; k < 3; ++k) {
-    f.c[k] = c.c[k];
-    f.a[k] = c.a[k];
-    f.e[k] = c.e[k];
-    f.b[k] = c.b[k];
-  }
-  f.inv = om::inverse_gsd(c.gsd);
-  f.w = c.width;
-  f.h = c.height;
-  f.wf = static_cast<float>(c.width);
-  f.hf = static_cast<float>(c.height);
-  f.d_min = c.d_min;
-  f.d_max = c.d_max;
-  f.R = static_cast<double>(c.radius);
-  f.side = static_cast<double>(c.side);
-  return f;
-}
+static cy::Frame or_cyl_frame(const pcp_cyl_frame &c) { return cy::make_frame(c); }
 
 // OM1 for either form; msg receives the refusal
 static int or_check_frame(const char *who, const pcp_ortho_frame *fr, char *msg, size_t cap) {

@@ -2,6 +2,8 @@
 // facets", CY1-CY9), one copy for the kernels (pcp_ortho.hip), the CPU form (pcp_ortho_cyl_host), the fit
 // (pcp_cyl_fit_host) and host/ortho_cyl_selftest.cpp.  Built with -ffp-contract=off: every product, sum, quotient and root
 // below is rounded on its own, in the width its operands have.  Everything after the pixel is pcp_ortho.hpp's.
+// The way back, from a fine pixel of an orthophoto to its surface point ("Orthophotos of unrolled maps", CT1-CT2), is here
+// too: one copy for k_ortho_texture<true>, pcp_ortho_texture_points_cyl_host and host/ortho_cyl_texture_selftest.cpp.
 #pragma once
 
 #include "pcp_ortho.hpp"
@@ -85,6 +87,81 @@ PCP_OM_HD bool project(const Frame &f, float px, float py, float pz, int32_t *pi
   const uint32_t db = om::float_bits(depth);
   *depth_bits = (db & 0x7fffffffu) ? db : 0u;
   return true;
+}
+
+// CT1 ("Orthophotos of unrolled maps"): sine and cosine of 0 <= theta < 64 by one fixed sequence of fp64 operations:
+// the nearest multiple k of pi/2, r = theta - k pi/2, both series to r^17 / r^16 by Horner, and the unfolding over k & 3.
+// Each coefficient is one correctly rounded quotient (every factorial up to 17! is an exact double).
+constexpr double kTwoOverPi = 0x1.45f306dc9c883p-1;  // the double nearest 2 / pi
+PCP_OM_HD void sincos(double theta, double *s, double *c) {
+  const int k = static_cast<int>(theta * kTwoOverPi + 0.5);
+  const double r = theta - static_cast<double>(k) * kPi2;
+  const double z = r * r;
+  double S = 1.0 / 355687428096000.0;
+  S = S * z + -1.0 / 1307674368000.0;
+  S = S * z + 1.0 / 6227020800.0;
+  S = S * z + -1.0 / 39916800.0;
+  S = S * z + 1.0 / 362880.0;
+  S = S * z + -1.0 / 5040.0;
+  S = S * z + 1.0 / 120.0;
+  S = S * z + -1.0 / 6.0;
+  S = S * z + 1.0;
+  S = r * S;
+  double C = 1.0 / 20922789888000.0;
+  C = C * z + -1.0 / 87178291200.0;
+  C = C * z + 1.0 / 479001600.0;
+  C = C * z + -1.0 / 3628800.0;
+  C = C * z + 1.0 / 40320.0;
+  C = C * z + -1.0 / 720.0;
+  C = C * z + 1.0 / 24.0;
+  C = C * z + -1.0 / 2.0;
+  C = C * z + 1.0;
+  switch (k & 3) {
+    case 0: *s = S; *c = C; break;
+    case 1: *s = C; *c = -S; break;
+    case 2: *s = -S; *c = -C; break;
+    default: *s = -C; *c = S; break;
+  }
+}
+
+// CT2, the inverse of CY2: the position of the surface point of fine pixel (Xg, Yg) at scale k and depth d, fp64 from the
+// frame's fp32 values and rounded to float once per coordinate.  xf / inv undoes CY2's x = arc inv.  false: rho <= 0, no surface.
+PCP_OM_HD bool surface_point(const Frame &f, int32_t k, int32_t Xg, int32_t Yg, float d, float p[3]) {
+  const double kd = static_cast<double>(k), inv = static_cast<double>(f.inv);
+  const double xf = (static_cast<double>(Xg) + 0.5) / kd, yf = (static_cast<double>(Yg) + 0.5) / kd;
+  const double arc = xf / inv, hh = yf / inv;
+  const double theta = arc / f.R;
+  const double rho = f.R + f.side * static_cast<double>(d);
+  if (!(rho > 0.0)) return false;
+  double s, c;
+  sincos(theta, &s, &c);
+  const double rc = rho * c, rs = rho * s;
+  for (int a = 0; a < 3; ++a)
+    p[a] = static_cast<float>(static_cast<double>(f.c[a]) +
+                              ((rc * static_cast<double>(f.e[a]) + rs * static_cast<double>(f.b[a])) + hh * static_cast<double>(f.a[a])));
+  return true;
+}
+
+// the frame as the kernels take it, from a pcp_cyl_frame (CY1)
+template <class CFrame>
+inline Frame make_frame(const CFrame &c) {
+  Frame f;
+  for (int k = 0; k < 3; ++k) {
+    f.c[k] = c.c[k];
+    f.a[k] = c.a[k];
+    f.e[k] = c.e[k];
+    f.b[k] = c.b[k];
+  }
+  f.inv = om::inverse_gsd(c.gsd);
+  f.w = c.width;
+  f.h = c.height;
+  f.wf = static_cast<float>(c.width);
+  f.hf = static_cast<float>(c.height);
+  f.d_min = c.d_min;
+  f.d_max = c.d_max;
+  f.R = static_cast<double>(c.radius);
+  f.side = static_cast<double>(c.side);
+  return f;
 }
 
 // CY1, host only, with om::frame_check's codes.  0: fine; 1: a non-finite value, a gsd outside [1e-4, 1], a radius outside

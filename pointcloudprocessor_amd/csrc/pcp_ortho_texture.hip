@@ -3,12 +3,15 @@
 // code the colour pass runs on map points: project_point, keep_rule against the context's depth maps, final_score,
 // Top5.  One lane per fine pixel, one 16 x 16 tile per workgroup; the keyframe loop is wave-uniform, and before it the
 // workgroup lists the keyframes that can see its tile at all (tile_classify on the tile's bounding sphere).
-// Opt-in: nothing here runs unless pcp_ortho_texture is called.  Build with -ffp-contract=off (see pcp_device.hpp).
+// A cylinder's unrolled map ("Orthophotos of unrolled maps", CT1-CT8) differs in the surface point alone (pcp_ortho_cyl.hpp).
+// Opt-in: nothing here runs unless pcp_ortho_texture or pcp_ortho_texture_cyl is called.  Build with -ffp-contract=off (see
+// pcp_device.hpp).
 #include <algorithm>
 #include <cmath>
 #include <new>
 
 #include "pcp_device.hpp"
+#include "pcp_ortho_cyl.hpp"
 #include "pcp_ortho_texture.hpp"
 #include "pcp_tile_classify.hpp"
 
@@ -20,10 +23,14 @@ constexpr int kOtWaves = kOtBlock / 64;
 constexpr int kOtMaxWords = (ot::kMaxFrames + 31) / 32;
 enum { OT_SURFACE = 0, OT_TEXTURED, OT_UNSEEN, OT_SKIPPED, OT_SCALARS };
 
-// the finished map as the kernel reads it
-struct OtMap {
+// the finished map as the kernel reads it: a plane's frame, or a cylinder's (kCyl, CT4)
+struct OtPlane {
   float o[3], u[3], v[3], n[3];
   float gsd;
+};
+template <bool kCyl>
+struct OtMap {
+  std::conditional_t<kCyl, cy::Frame, OtPlane> f;
   int32_t W, H;
   const int32_t *source;
   const unsigned long long *keys;
@@ -54,7 +61,9 @@ __device__ __forceinline__ uint32_t ot_gained(uint32_t c, int32_t f, const float
 }
 
 // OT3-OT7.  Lane (lx, ly) of workgroup (bx, by) is fine pixel (16 bx + lx, 16 by + ly) of the call's raster.
-__global__ __launch_bounds__(kOtBlock) void k_ortho_texture(ot::Raster r, OtMap m, DevCamera cam, const DevFrame *__restrict__ frames,
+// kCyl: the surface point is CT2's, and a pixel whose rho is not above 0 has no surface; all else is the same.
+template <bool kCyl>
+__global__ __launch_bounds__(kOtBlock) void k_ortho_texture(ot::Raster r, OtMap<kCyl> m, DevCamera cam, const DevFrame *__restrict__ frames,
                                                             int32_t n_frames, const uint32_t *__restrict__ depth, int64_t cells,
                                                             const uint32_t *__restrict__ images, int64_t image_px,
                                                             const float *__restrict__ gains, int32_t views, OtOut out,
@@ -74,7 +83,11 @@ __global__ __launch_bounds__(kOtBlock) void k_ortho_texture(ot::Raster r, OtMap 
     const int32_t Xg = r.x0 * r.k + X, Yg = r.y0 * r.k + Y;
     float d;
     surface = ot::surface_depth(r, m.W, m.H, m.source, [&](int32_t s) { return om::key_depth(m.keys[s]); }, Xg, Yg, &d);
-    if (surface) ot::surface_point(m.o, m.u, m.v, m.n, m.gsd, r.k, Xg, Yg, d, p);
+    if constexpr (kCyl) {
+      if (surface) surface = cy::surface_point(m.f, r.k, Xg, Yg, d, p);
+    } else {
+      if (surface) ot::surface_point(m.f.o, m.f.u, m.f.v, m.f.n, m.f.gsd, r.k, Xg, Yg, d, p);
+    }
   }
   // OT7: the tile's bounding sphere -- the centre of its surface points' box, the largest distance from it
   {
@@ -180,7 +193,8 @@ __global__ __launch_bounds__(kOtBlock) void k_ortho_texture(ot::Raster r, OtMap 
 
 hipError_t preload_ortho_texture() {
   hipFuncAttributes a;
-  return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_ortho_texture));
+  const hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_ortho_texture<false>));
+  return e != hipSuccess ? e : hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_ortho_texture<true>));
 }
 
 // OT2 for either form: the resolved raster, or the refusal in msg
@@ -200,43 +214,42 @@ static int ot_check_raster(const char *who, int32_t W, int32_t H, const pcp_orth
   return PCP_OK;
 }
 
-}  // namespace pcp
-
-using namespace pcp;
-
-extern "C" {
-
-int pcp_ortho_texture(pcp_context *ctx, const pcp_ortho_texture_params *params, uint8_t *out_rgb, uint8_t *out_mask, uint8_t *out_status,
-                      int16_t *out_view, uint8_t *out_count, int64_t out_counts[4]) {
+// pcp_ortho_texture (kCyl false) and pcp_ortho_texture_cyl (true): OT1's checks in OT1's order, OT2, the launch, the copies
+template <bool kCyl>
+static int ot_texture(pcp_context *ctx, const char *who, const pcp_ortho_texture_params *params, uint8_t *out_rgb, uint8_t *out_mask,
+                      uint8_t *out_status, int16_t *out_view, uint8_t *out_count, int64_t out_counts[4]) {
   if (!ctx) return PCP_ERR_INVALID;
   if (out_counts) out_counts[0] = out_counts[1] = out_counts[2] = out_counts[3] = 0;
-  if (!params) return set_error(ctx, PCP_ERR_INVALID, "pcp_ortho_texture: NULL params");
+  if (!params) return set_error(ctx, PCP_ERR_INVALID, "%s: NULL params", who);
   // OT1
   const OrthoMap &m = ctx->ortho;
-  if (!m.live) return set_error(ctx, PCP_ERR_STATE, "pcp_ortho_texture: no orthographic map (call pcp_ortho_begin)");
-  if (m.cyl)  // CY4
+  if (!m.live) return set_error(ctx, PCP_ERR_STATE, "%s: no orthographic map (call pcp_ortho_begin)", who);
+  if (!kCyl && m.cyl)  // CY4, CT5
     return set_error(ctx, PCP_ERR_STATE, "pcp_ortho_texture: the live map is a cylinder's unrolled map (pcp_ortho_begin_cyl); orthophotos "
-                     "of unrolled maps are not built");
-  if (!m.finished) return set_error(ctx, PCP_ERR_STATE, "pcp_ortho_texture: pcp_ortho_finish has not run");
-  if (!ctx->have_camera) return set_error(ctx, PCP_ERR_STATE, "pcp_ortho_texture: pcp_set_camera has not been called");
+                     "of unrolled maps are not built by this call (pcp_ortho_texture_cyl builds them)");
+  if (kCyl && !m.cyl)
+    return set_error(ctx, PCP_ERR_STATE, "pcp_ortho_texture_cyl: the live map is a plane's (pcp_ortho_begin); pcp_ortho_texture builds "
+                     "its orthophoto");
+  if (!m.finished) return set_error(ctx, PCP_ERR_STATE, "%s: pcp_ortho_finish has not run", who);
+  if (!ctx->have_camera) return set_error(ctx, PCP_ERR_STATE, "%s: pcp_set_camera has not been called", who);
   const int32_t F = ctx->n_frames;
-  if (F <= 0) return set_error(ctx, PCP_ERR_STATE, "pcp_ortho_texture: pcp_set_frames has not been called");
+  if (F <= 0) return set_error(ctx, PCP_ERR_STATE, "%s: pcp_set_frames has not been called", who);
   if (F > ot::kMaxFrames)  // (OT2, with the keyframes: before their images are asked for)
-    return set_error(ctx, PCP_ERR_RANGE, "pcp_ortho_texture: %d keyframes, the view layer (int16) names at most %d", F, ot::kMaxFrames);
+    return set_error(ctx, PCP_ERR_RANGE, "%s: %d keyframes, the view layer (int16) names at most %d", who, F, ot::kMaxFrames);
   if (ctx->dcam.cull_mode != PCP_CULL_ZBUFFER || !ctx->dcam.enable_zbuf)
-    return set_error(ctx, PCP_ERR_STATE, "pcp_ortho_texture: needs PCP_CULL_ZBUFFER with the depth buffer on (a surface point is kept "
-                     "or dropped by the depth maps; PCP_CULL_HPR* has none)");
+    return set_error(ctx, PCP_ERR_STATE, "%s: needs PCP_CULL_ZBUFFER with the depth buffer on (a surface point is kept or dropped by "
+                     "the depth maps; PCP_CULL_HPR* has none)", who);
   for (size_t f = 0; f < static_cast<size_t>(F); ++f)
     if (!ctx->images.p || f >= ctx->image_set.size() || !ctx->image_set[f])
-      return set_error(ctx, PCP_ERR_STATE, "pcp_ortho_texture: no image uploaded for keyframe %d", static_cast<int>(f));
+      return set_error(ctx, PCP_ERR_STATE, "%s: no image uploaded for keyframe %d", who, static_cast<int>(f));
   for (size_t f = 0; f < static_cast<size_t>(F); ++f)
     if (!ctx->depth.p || f >= ctx->depth_valid.size() || !ctx->depth_valid[f])
-      return set_error(ctx, PCP_ERR_STATE, "pcp_ortho_texture: pcp_depth_pass has not covered keyframe %d since the latest upload",
+      return set_error(ctx, PCP_ERR_STATE, "%s: pcp_depth_pass has not covered keyframe %d since the latest upload", who,
                        static_cast<int>(f));
   // OT2
   ot::Raster r{};
   char msg[320];
-  const int rc = ot_check_raster("pcp_ortho_texture", m.frame.width, m.frame.height, *params, &r, msg, sizeof msg);
+  const int rc = ot_check_raster(who, m.frame.width, m.frame.height, *params, &r, msg, sizeof msg);
   if (rc != PCP_OK) return set_error(ctx, rc, "%s", msg);
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int wrc = wait_images(ctx, 0, F);
@@ -254,14 +267,18 @@ int pcp_ortho_texture(pcp_context *ctx, const pcp_ortho_texture_params *params, 
   if (out_view) PCP_HIP_TRY(ctx, d_view.ensure(px));
   PCP_HIP_TRY(ctx, d_scalars.ensure(OT_SCALARS));
   PCP_HIP_TRY(ctx, hipMemsetAsync(d_scalars.p, 0, OT_SCALARS * 8, ctx->stream));
-  OtMap dm;
-  for (int a = 0; a < 3; ++a) {
-    dm.o[a] = m.frame.o[a];
-    dm.u[a] = m.frame.u[a];
-    dm.v[a] = m.frame.v[a];
-    dm.n[a] = m.frame.n[a];
+  OtMap<kCyl> dm;
+  if constexpr (kCyl) {
+    dm.f = cy::make_frame(m.cyl_frame);
+  } else {
+    for (int a = 0; a < 3; ++a) {
+      dm.f.o[a] = m.frame.o[a];
+      dm.f.u[a] = m.frame.u[a];
+      dm.f.v[a] = m.frame.v[a];
+      dm.f.n[a] = m.frame.n[a];
+    }
+    dm.f.gsd = m.frame.gsd;
   }
-  dm.gsd = m.frame.gsd;
   dm.W = m.frame.width;
   dm.H = m.frame.height;
   dm.source = m.source.p;
@@ -270,7 +287,7 @@ int pcp_ortho_texture(pcp_context *ctx, const pcp_ortho_texture_params *params, 
   {
     LaunchTimer t(ctx, PCP_K_MISC);
     const dim3 grid(static_cast<uint32_t>(div_up(fw, kOtTile)), static_cast<uint32_t>(div_up(fh, kOtTile)));
-    hipLaunchKernelGGL(k_ortho_texture, grid, dim3(kOtBlock), 0, ctx->stream, r, dm, ctx->dcam, ctx->frames.p, F, ctx->depth.p,
+    hipLaunchKernelGGL(k_ortho_texture<kCyl>, grid, dim3(kOtBlock), 0, ctx->stream, r, dm, ctx->dcam, ctx->frames.p, F, ctx->depth.p,
                        static_cast<int64_t>(ctx->dcam.mw) * ctx->dcam.mh, ctx->images.p,
                        static_cast<int64_t>(ctx->dcam.img_w) * ctx->dcam.img_h, ctx->gains_set ? ctx->gains_dev.p : static_cast<const float *>(nullptr),
                        params->views, out, d_scalars.p);
@@ -287,6 +304,22 @@ int pcp_ortho_texture(pcp_context *ctx, const pcp_ortho_texture_params *params, 
   if (out_counts)
     for (int k = 0; k < OT_SCALARS; ++k) out_counts[k] = static_cast<int64_t>(h[k]);
   return PCP_OK;
+}
+
+}  // namespace pcp
+
+using namespace pcp;
+
+extern "C" {
+
+int pcp_ortho_texture(pcp_context *ctx, const pcp_ortho_texture_params *params, uint8_t *out_rgb, uint8_t *out_mask, uint8_t *out_status,
+                      int16_t *out_view, uint8_t *out_count, int64_t out_counts[4]) {
+  return ot_texture<false>(ctx, "pcp_ortho_texture", params, out_rgb, out_mask, out_status, out_view, out_count, out_counts);
+}
+
+int pcp_ortho_texture_cyl(pcp_context *ctx, const pcp_ortho_texture_params *params, uint8_t *out_rgb, uint8_t *out_mask, uint8_t *out_status,
+                          int16_t *out_view, uint8_t *out_count, int64_t out_counts[4]) {
+  return ot_texture<true>(ctx, "pcp_ortho_texture_cyl", params, out_rgb, out_mask, out_status, out_view, out_count, out_counts);
 }
 
 int pcp_ortho_texture_points_host(const pcp_ortho_frame *frame, const pcp_ortho_texture_params *params, const int32_t *source,
@@ -329,6 +362,64 @@ int pcp_ortho_texture_points_host(const pcp_ortho_frame *frame, const pcp_ortho_
         for (int a = 0; a < 3; ++a) out_xyz[3 * at + a] = p[a];
       if (out_ok) out_ok[at] = ok ? 1 : 0;
     }
+  return PCP_OK;
+}
+
+int pcp_ortho_texture_points_cyl_host(const pcp_cyl_frame *frame, const pcp_ortho_texture_params *params, const int32_t *source,
+                                      const float *depth, float *out_xyz, uint8_t *out_ok) {
+  const char *who = "pcp_ortho_texture_points_cyl_host";
+  if (!frame || !params || !source || !depth) {
+    set_global_error("%s: NULL frame, params, source or depth", who);
+    return PCP_ERR_INVALID;
+  }
+  const char *why = "";
+  double fit = 0.0;
+  const int bad = cy::frame_check(frame->c, frame->a, frame->e, frame->b, frame->radius, frame->gsd, frame->width, frame->height,
+                                  frame->d_min, frame->d_max, frame->side, &why, &fit);
+  if (bad) {
+    set_global_error("%s: %s", who, why);
+    return bad == 1 ? PCP_ERR_INVALID : PCP_ERR_RANGE;
+  }
+  ot::Raster r{};
+  char msg[320];
+  const int rc = ot_check_raster(who, frame->width, frame->height, *params, &r, msg, sizeof msg);
+  if (rc != PCP_OK) {
+    set_global_error("%s", msg);
+    return rc;
+  }
+  const int32_t W = frame->width, H = frame->height, fw = r.w * r.k, fh = r.h * r.k;
+  const int64_t map_px = static_cast<int64_t>(W) * H;
+  for (int64_t q = 0; q < map_px; ++q)
+    if (source[q] >= map_px) {
+      set_global_error("%s: source[%lld] = %d names no pixel of the %d x %d map", who, static_cast<long long>(q), source[q], W, H);
+      return PCP_ERR_INVALID;
+    }
+  const cy::Frame f = cy::make_frame(*frame);
+  for (int32_t Y = 0; Y < fh; ++Y)
+    for (int32_t X = 0; X < fw; ++X) {
+      const int32_t Xg = r.x0 * r.k + X, Yg = r.y0 * r.k + Y;
+      float d = 0.0f, p[3] = {0.0f, 0.0f, 0.0f};
+      bool ok = ot::surface_depth(r, W, H, source, [&](int32_t s) { return depth[s]; }, Xg, Yg, &d);
+      if (ok) ok = cy::surface_point(f, r.k, Xg, Yg, d, p);  // (false: rho <= 0, p stays 0)
+      const int64_t at = static_cast<int64_t>(Y) * fw + X;
+      if (out_xyz)
+        for (int a = 0; a < 3; ++a) out_xyz[3 * at + a] = p[a];
+      if (out_ok) out_ok[at] = ok ? 1 : 0;
+    }
+  return PCP_OK;
+}
+
+int pcp_cyl_sincos_host(int64_t n, const double *theta, double *out_sin, double *out_cos) {
+  if (n < 0 || (n > 0 && (!theta || !out_sin || !out_cos))) {
+    set_global_error("pcp_cyl_sincos_host: negative n or a NULL array");
+    return PCP_ERR_INVALID;
+  }
+  for (int64_t i = 0; i < n; ++i)
+    if (!(theta[i] >= 0.0 && theta[i] < 64.0)) {  // (a NaN fails both)
+      set_global_error("pcp_cyl_sincos_host: theta[%lld] = %g is outside [0, 64) or not finite", static_cast<long long>(i), theta[i]);
+      return PCP_ERR_INVALID;
+    }
+  for (int64_t i = 0; i < n; ++i) cy::sincos(theta[i], out_sin + i, out_cos + i);
   return PCP_OK;
 }
 

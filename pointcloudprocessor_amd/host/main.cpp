@@ -221,6 +221,11 @@
 //     ortho_frame.json carries "kind": "cylinder" and the cylinder's frame.  Under --orthoTexture k the planar facets are
 //     textured and each cylindrical one is named on stderr as skipped.  Without the flag every file is byte for byte what it
 //     was.  Made on the GPU (pcp_ortho_begin_cyl; DESIGN.md "Cylindrical facets").
+//   * --orthoTextureCylinders 0|1 (new, default 0; needs --orthoTexture k, --facetCylinders 1 and --orthoFrame facets, refused by
+//     name without any of them): with 1 every cylindrical facet's directory gains ortho_photo_rgb / mask / view / status.npy and
+//     ortho_photo.json in the planar facets' format, banded the same way, and no facet is named as skipped.  Made on the GPU
+//     (pcp_ortho_texture_cyl; DESIGN.md "Orthophotos of unrolled maps").  Without the flag every file, byte and message is what
+//     it was.
 #include <algorithm>
 #include <cfloat>
 #include <chrono>
@@ -332,6 +337,7 @@ struct Options {
   int ortho_texture_views = 1;        // --orthoTextureViews m: listed views that enter a colour
   bool ortho_texture_interp = true;   // --orthoTextureInterp: bilinear depth between map pixels
   float ortho_texture_step = 0.05f;   // --orthoTextureStep s: ... only across depth steps up to s metres
+  bool ortho_texture_cylinders = false;  // --orthoTextureCylinders 1: the orthophoto of every cylindrical facet's unrolled map too
   bool ortho_texture_value_flag = false;  // one of the three value flags was given
   bool facets = false;                // --facets 1: the planar facets of the map (facets/facet_label.npy, facets.json)
   bool ortho_by_facet = false;        // --orthoFrame facets: one orthographic map per planar facet (ortho/facet_<row>/)
@@ -478,6 +484,7 @@ static Options parse(int argc, char **argv) {
     }
     else if (a == "--facets") o.facets = parse_bool(next());
     else if (a == "--facetCylinders") o.facet_cylinders = parse_bool(next());
+    else if (a == "--orthoTextureCylinders") o.ortho_texture_cylinders = parse_bool(next());
     else if (a == "--facetRadius" || a == "--facetAngle" || a == "--facetPlaneTol" || a == "--facetMaxCurvature" || a == "--facetMaxRms") {
       const std::string v = next();
       char *end = nullptr;
@@ -648,6 +655,9 @@ static Options parse(int argc, char **argv) {
   if (o.output_leaf > 0.0f && o.gpus > 1)
     throw std::runtime_error("the option '--outputLeaf' does not work with '--gpus N' above 1 (the voxel sums of the index shards would "
                              "have to be added across GPUs: not built)");
+  if (o.ortho_texture_cylinders && !(o.ortho_texture && o.facet_cylinders && o.ortho_by_facet))
+    throw std::runtime_error("the option '--orthoTextureCylinders 1' needs '--orthoTexture k' (k in 1..16), '--facetCylinders 1' and "
+                             "'--orthoFrame facets' (it textures the unrolled maps those three write)");
   if (o.ortho_texture_value_flag && !o.ortho_texture)
     throw std::runtime_error("the options '--orthoTextureViews', '--orthoTextureInterp' and '--orthoTextureStep' need '--orthoTexture k' (k in 1..16)");
   if (o.ortho_texture && !o.ortho_map)
@@ -786,7 +796,8 @@ static void usage(std::ostream &os) {
         "  --facetMaxCurvature arg (=0.02)       With --facets: points of a larger curvature take no part (0..1)\n"
         "  --facetMinPoints arg (=1000)          With --facets: a facet has at least this many points\n"
         "  --facetMaxRms arg (=0.01)             With --facets: a facet is planar up to this rms distance (m) to its plane\n"
-        "  --facetCylinders arg (=0)             With --facets: fit a cylinder to every facet that is not planar; with --orthoFrame facets unroll those that are one\n";
+        "  --facetCylinders arg (=0)             With --facets: fit a cylinder to every facet that is not planar; with --orthoFrame facets unroll those that are one\n"
+        "  --orthoTextureCylinders arg (=0)      With --orthoTexture, --facetCylinders and --orthoFrame facets: also the orthophoto of every unrolled map\n";
 }
 
 class Processor {
@@ -1764,7 +1775,7 @@ class Processor {
           dev.orthoBeginCyl(cf);
           (void)dev.orthoAddFacet(id, 0);
         }
-        if (opt.ortho_texture)
+        if (opt.ortho_texture && !opt.ortho_texture_cylinders)
           std::cerr << "facet " << id << " (ortho/facet_" << r << "/): cylindrical, skipped by --orthoTexture (orthophotos of unrolled maps are not built)"
                     << std::endl;
         writeOrthoFiles(opt.outputPath + "ortho/facet_" + std::to_string(r) + "/", &cf);
@@ -1850,22 +1861,24 @@ class Processor {
     writeOrthoFiles();
   }
   // the map begun on the colour context, finished with --orthoFill, as <out>ortho/ortho_*.npy and ortho_frame.json; then dropped
-  // (cyl: the map was begun under this cylinder's frame -- no orthophoto, and ortho_frame.json holds the cylinder)
+  // (cyl: the map was begun under this cylinder's frame -- ortho_frame.json holds the cylinder, and the orthophoto is made only
+  // under --orthoTextureCylinders 1)
   void writeOrthoFiles(const std::string &stem_in = std::string(), const pcp_cyl_frame *cyl = nullptr) {
     const std::string stem = stem_in.empty() ? opt.outputPath + "ortho/" : stem_in;
     Device &dev = gpu->device(0);
+    const bool photo = opt.ortho_texture && (!cyl || opt.ortho_texture_cylinders);
     OrthoMap m;
     {
       Phase ph("ortho_finish_gpu_s");
       m = dev.orthoFetch(opt.ortho_fill, opt.fuse_masks);
-      if (!opt.ortho_texture || cyl) dev.orthoEnd();
+      if (!photo) dev.orthoEnd();
     }
-    if (opt.ortho_texture && !cyl) {
+    if (photo) {
       struct End {  // also on the way out of an exception
         Device &d;
         ~End() { (void)pcp_ortho_end(d.get()); }
       } end{dev};
-      writeOrthoPhoto(dev, m.frame, stem);
+      writeOrthoPhoto(dev, m.frame, stem, cyl != nullptr);
     }
     Phase ph_w("ortho_write_s");
     fs::create_directories(fs::path(stem));
@@ -1902,7 +1915,8 @@ class Processor {
 
   // --orthoTexture k: the orthophoto of the finished map on `dev`, as <out>ortho/ortho_photo_*.npy and ortho_photo.json.  One call
   // of at most 2^28 fine pixels covers a band of whole map rows; the bands' rows are appended to the files in order.
-  void writeOrthoPhoto(Device &dev, const pcp_ortho_frame &frame, const std::string &stem) {
+  // cyl: the map is a cylinder's unrolled one (--orthoTextureCylinders 1): the same files by pcp_ortho_texture_cyl.
+  void writeOrthoPhoto(Device &dev, const pcp_ortho_frame &frame, const std::string &stem, bool cyl = false) {
     Phase ph("ortho_texture_s");
     fs::create_directories(fs::path(stem));
     const int64_t k = opt.ortho_texture, W = frame.width, H = frame.height;
@@ -1925,7 +1939,7 @@ class Processor {
       p.views = opt.ortho_texture_views;
       p.interpolate = opt.ortho_texture_interp ? 1 : 0;
       p.max_step = opt.ortho_texture_step;
-      const OrthoPhoto part = dev.orthoTexture(p);
+      const OrthoPhoto part = cyl ? dev.orthoTextureCyl(p) : dev.orthoTexture(p);
       rgb.write(reinterpret_cast<const char *>(part.rgb.data()), static_cast<std::streamsize>(part.rgb.size()));
       mask.write(reinterpret_cast<const char *>(part.mask.data()), static_cast<std::streamsize>(part.mask.size()));
       view.write(reinterpret_cast<const char *>(part.view.data()), static_cast<std::streamsize>(part.view.size() * 2));

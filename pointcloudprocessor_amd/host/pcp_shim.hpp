@@ -286,7 +286,7 @@ class Device {
     ortho_frame_ = frame;  // (only of a begin the library took: a refused one leaves the live map, and its frame, as they were)
   }
   // the same accumulator under a cylinder's frame, unrolled along its arc (pcp_ortho_begin_cyl; DESIGN.md "Cylindrical facets"):
-  // the adds, orthoFetch, orthoStats and orthoEnd work on either kind; orthoTexture is refused on this one
+  // the adds, orthoFetch, orthoStats and orthoEnd work on either kind; orthoTexture is refused on this one, orthoTextureCyl is its call
   void orthoBeginCyl(const pcp_cyl_frame &frame) {
     check(pcp_ortho_begin_cyl(ctx_, &frame));
     ortho_frame_ = pcp_ortho_frame{};  // (orthoFetch sizes its layers by the raster of the last begin the library took)
@@ -337,7 +337,10 @@ class Device {
   // and axis over the rectangle p names (w == 0 && h == 0: the whole raster), coloured straight from the keyframe images under
   // the depth maps the context holds.  (Sized by the frame of the last orthoBegin that succeeded on this Device; parameters the
   // library refuses get no layers and its refusal.)
-  OrthoPhoto orthoTexture(const pcp_ortho_texture_params &p) {
+  OrthoPhoto orthoTexture(const pcp_ortho_texture_params &p) { return orthoTextureBy(pcp_ortho_texture, p); }
+  // the same of a cylinder's unrolled map (pcp_ortho_texture_cyl; DESIGN.md "Orthophotos of unrolled maps"): after orthoBeginCyl
+  OrthoPhoto orthoTextureCyl(const pcp_ortho_texture_params &p) { return orthoTextureBy(pcp_ortho_texture_cyl, p); }
+  OrthoPhoto orthoTextureBy(decltype(&pcp_ortho_texture) call, const pcp_ortho_texture_params &p) {
     OrthoPhoto ph;
     const int64_t w = (p.w == 0 && p.h == 0) ? ortho_frame_.width : p.w, h = (p.w == 0 && p.h == 0) ? ortho_frame_.height : p.h;
     const int64_t k = p.scale;
@@ -352,7 +355,7 @@ class Device {
     ph.view.resize(px);
     ph.count.resize(px);
     int64_t counts[4] = {0, 0, 0, 0};
-    check(pcp_ortho_texture(ctx_, &p, ph.rgb.data(), ph.mask.data(), ph.status.data(), ph.view.data(), ph.count.data(), counts));
+    check(call(ctx_, &p, ph.rgb.data(), ph.mask.data(), ph.status.data(), ph.view.data(), ph.count.data(), counts));
     ph.surface = counts[0];
     ph.textured = counts[1];
     ph.unseen = counts[2];

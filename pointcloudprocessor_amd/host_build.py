@@ -28,6 +28,7 @@ TARGETS = {
     "crack_skeleton_selftest": ["crack_skeleton_selftest.cpp"],  # csrc/pcp_crack_skeleton.hpp compiled for the host (CPU only)
     "image_balance_selftest": ["image_balance_selftest.cpp"],  # csrc/pcp_image_balance.hpp compiled for the host (CPU only)
     "ortho_cyl_selftest": ["ortho_cyl_selftest.cpp"],  # csrc/pcp_ortho_cyl.hpp compiled for the host (CPU only)
+    "ortho_cyl_texture_selftest": ["ortho_cyl_texture_selftest.cpp"],  # csrc/pcp_ortho_cyl.hpp's way back, pixel to point (CPU only)
     "facets_selftest": ["facets_selftest.cpp"],  # csrc/pcp_facets.hpp compiled for the host (CPU only)
     "tile_bounds_selftest": ["tile_bounds_selftest.cpp"],  # csrc/pcp_tile_box.hpp compiled for the host (CPU only)
 }

@@ -291,7 +291,7 @@ class PointCloudColorizer:
         return out
 
     def ortho_maps_by_facet(self, gsd: float, xyz=None, facets: dict | None = None, fill_radius: int = 0, viewer=None,
-                            texture: dict | None = None, cylinders: bool = False) -> list:
+                            texture: dict | None = None, cylinders: bool = False, texture_cylinders: bool = False) -> list:
         """One orthographic map per planar facet of the colour result run() left on the device: for every planar row of
         `facets` (the dict facets() returned; None: the one its last call on this object left) a frame fitted on the host to
         the facet's points (capi.ortho_fit_frame_host with has = (label == id)) at `gsd` metres per pixel, seen from `viewer`
@@ -301,8 +301,9 @@ class PointCloudColorizer:
 
         cylinders ("Cylindrical facets"): the cylindrical facets of a facets(..., cylinders=True) are drawn too, each
         unrolled through a cylinder fitted at `gsd` from the facet's points and the live normals (ctx.normals_fetch), and every
-        map's dict carries kind (1 planar, 2 cylindrical).  texture is applied to the planar facets only: orthophotos of
-        unrolled maps are not built.
+        map's dict carries kind (1 planar, 2 cylindrical).  texture is applied to the planar facets only, unless
+        texture_cylinders is given too ("Orthophotos of unrolled maps"): then the cylindrical maps gain photo as
+        well, by ctx.ortho_texture_cyl with the same request.  texture_cylinders needs both texture and cylinders.
 
         An index shard sees only its own points, so world > 1 raises ValueError."""
         import numpy as np
@@ -312,6 +313,9 @@ class PointCloudColorizer:
                              "would have to be merged across ranks (all-reduce MIN), which is not built: run it on one rank "
                              "holding the whole map")
         texture = ortho_texture_request("ortho_maps_by_facet", texture)
+        if texture_cylinders and (texture is None or not cylinders):
+            raise ValueError("ortho_maps_by_facet: texture_cylinders needs texture (the request) and cylinders=True (the maps it "
+                             "textures)")
         ctx = self.engine.ctx
         facets = getattr(self, "last_facets", None) if facets is None else facets
         if facets is None or len(facets["label"]) != ctx.n:
@@ -345,6 +349,8 @@ class PointCloudColorizer:
                 out = ctx.ortho_fetch(want_label=fuse_labels)
                 if texture is not None and kinds[row] == 1:
                     out["photo"] = ctx.ortho_texture(**texture)
+                elif texture_cylinders and kinds[row] == 2:
+                    out["photo"] = ctx.ortho_texture_cyl(**texture)
             finally:
                 ctx.ortho_end()
             out.update(frame=frame, contributors=contributors, occupied=occupied, filled=filled, facet=fid, row=int(row))
