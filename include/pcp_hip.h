@@ -628,7 +628,10 @@ int pcp_sor_finish(pcp_context *ctx, double std_mul, const double *all_chunk_sum
 int pcp_upload_intensity(pcp_context *ctx, const float *intensity, int64_t n);
 /* Builds every keyframe's NID input on the device: its z-buffer-culled points in camera
  * coordinates with intensity (the content of <ts>_beforeNID.pcd, PointCloudProcessor.cpp:178-224).
- * Needs camera, cloud, intensity, keyframes and images. */
+ * Needs camera, cloud, intensity, keyframes and images.
+ * Repeat it after pcp_set_camera, pcp_set_frames, any pcp_upload_cloud* and pcp_upload_intensity: each of them drops what
+ * it built, and the pcp_nid_* calls below then return PCP_ERR_STATE.  The images are read at every evaluation: a
+ * pcp_upload_image* after it needs no repeat. */
 int pcp_nid_prepare(pcp_context *ctx, int64_t *out_points);
 /* MultiNIDCost at T = T_camera_lidar (4x4 row-major fp64): sum over keyframes of NIDCost
  * (nid_cost.hpp:42-116), and its gradient in the SE(3) tangent of T * exp(delta),

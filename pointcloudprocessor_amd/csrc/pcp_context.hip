@@ -530,7 +530,7 @@ static int store_cloud(pcp_context *ctx, const float *x, const float *y, const f
   ctx->n_tiles = 0;
   ctx->tile_order_live = false;
   ctx->have_intensity = false;
-  ctx->nid_chunks = 0;
+  nid_release(ctx);
   ctx->colour_state_live = false;
   ctx->colour_result_live = false;
   ctx->labels_live = false;
@@ -871,6 +871,7 @@ int pcp_set_camera(pcp_context *ctx, const pcp_camera *cam, const pcp_cull_param
   ctx->depth_accum.release();  // sized by the camera
   ctx->depth_accum_live = false;
   ctx->crack->release();  // the accumulated crack widths belong to the camera and the keyframes they were measured with
+  nid_release(ctx);       // the NID stage's points were culled through the previous camera
   ctx->colour_state_live = false;
   ctx->colour_result_live = false;
   ctx->labels_live = false;
@@ -998,6 +999,7 @@ int pcp_set_frames(pcp_context *ctx, const pcp_pose *poses, int32_t n_frames, co
   ctx->crack->release();
   ctx->match_live = false;  // PCP_MATCH_RADIUS: E (and with it R_c) depends on the keyframes
   ctx->gains_set = false;   // exposure gains: one per keyframe of the set that is being replaced
+  nid_release(ctx);         // the NID stage's points are in the camera frames of the set that is being replaced
   ctx->colour_state_live = false;
   ctx->colour_result_live = false;
   ctx->labels_live = false;

@@ -610,6 +610,16 @@ inline void end_smoothing_streams(pcp_context *ctx) {
   ctx->emission.end();
   ctx->chain.end();
 }
+// The NID stage's prepared state (the gathered camera-frame points, their chunks, the histograms) belongs to the cloud, the
+// intensities, the keyframes and the camera it was gathered with: a call that replaces one of them drops it (store_cloud,
+// pcp_upload_intensity, pcp_set_frames, pcp_set_camera), and the evaluation calls refuse until pcp_nid_prepare ran again.
+// Not the images (read live at every evaluation) and not the depth source or accumulator (set before the prepare).
+inline void nid_release(pcp_context *ctx) {
+  ctx->nid_frames = 0;
+  ctx->nid_chunks = 0;
+  ctx->nid_points = 0;
+  ctx->nid_hist_bins = 0;
+}
 
 // ---- the front end of the stages that search a fixed radius around every point of the uploaded cloud (pcp_grid.hip) ----
 // the uploaded cloud as a view: its Morton-ordered copy and the host box of its finite coordinates; with_remap: results

@@ -369,7 +369,7 @@ int pcp_upload_intensity(pcp_context *ctx, const float *intensity, int64_t n) {
     PCP_HIP_TRY(ctx, hipMemcpyAsync(ctx->intensity.p, intensity, static_cast<size_t>(n) * 4, hipMemcpyHostToDevice, ctx->stream));
   PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   ctx->have_intensity = true;
-  ctx->nid_chunks = 0;
+  nid_release(ctx);
   return PCP_OK;
 }
 
