@@ -85,7 +85,9 @@ extern "C" {
                                 entry points added, no layout changed: pcp_ortho_begin_cyl, pcp_ortho_cyl_host, pcp_cyl_angle_host,
                                 pcp_cyl_fit_host (cylindrical facets and their unrolled maps; nothing runs unless called);
                                 entry points added, no layout changed: pcp_ortho_texture_cyl, pcp_ortho_texture_points_cyl_host,
-                                pcp_cyl_sincos_host (orthophotos of unrolled maps; nothing runs unless called) */
+                                pcp_cyl_sincos_host (orthophotos of unrolled maps; nothing runs unless called);
+                                entry points added, no layout changed: pcp_crack_directions / _fetch / _host, pcp_crack_axis_host
+                                (crack directions on the map; nothing runs unless called) */
 
 #define PCP_OK 0
 #define PCP_ERR_INVALID (-1) /* bad argument */
@@ -1197,6 +1199,43 @@ int pcp_crack_skeleton_cracks_fetch(pcp_context *ctx, int64_t first, int64_t max
 int pcp_crack_skeleton_host(int64_t n, const float *xyz, const uint32_t *views, int32_t min_views, float radius, float step,
                             const uint64_t *sum_q, int32_t *out_node, int32_t *out_id, int64_t *out_rows10, int64_t edge_capacity,
                             int64_t *out_rows3, int64_t *out_rows6, int64_t *out_nodes, int64_t *out_edges, int64_t *out_cracks);
+
+/* ---- crack directions on the map (scripts/evalSkeletonDirection.py only blurs one keyframe's 2-D skeleton and shows it) ------ */
+/* Which way every crack of the map runs: a tangent per crack point and the sums per crack from which the host takes the
+ * crack's axis ("Crack directions on the map", CD1-CD9).  Opt-in: nothing runs unless one of these is called,
+ * PCP_ABI_VERSION is unchanged and a caller detects support by the symbols.  The kernel is timed under PCP_K_MISC.  Whole-map
+ * contexts only.
+ *
+ * pcp_crack_directions reads the live accumulation under the crack points and links of pcp_crack_components for the same
+ * parameters (same checks and returns; without a live accumulation PCP_ERR_STATE).  It runs the component stage: afterwards
+ * pcp_crack_components_fetch serves the table of these parameters, the tables of pcp_crack_lengths and pcp_crack_skeleton are
+ * kept, and the call invalidates what pcp_crack_components invalidates.  Per crack point i, over its linked points j, the
+ * offset d = fl32(p_j - p_i) is quantised to q = rint(d * 2^20) per axis (ties to even) and ten exact int64 moments are
+ * summed: n (the links), S1 x y z, S2 xx xy xz yy yz zz -- a function of the set of links alone.  A point with 2^22 links or
+ * more: PCP_ERR_RANGE.  With C the covariance of the moments (pcp_estimate_normals' three fp64 operations per entry) and l1
+ * its largest eigenvalue, the tangent is valid iff n >= 2 and l1 > 0: the unit eigenvector of l1 taken in fp64, its component
+ * of largest magnitude positive (ties: the lowest axis), stored as fp32; anisotropy = (float)(l1 / trace(C)), 1 on a line and
+ * about 1/2 on a flat isotropic patch.  Otherwise tangent and anisotropy are zeros.  out_tangent 3 n, out_anisotropy n,
+ * out_links n, out_moments 10 n: host, nullable, input order, zeros for a point that is no crack point.  *out_crack_points /
+ * *out_cracks (nullable).
+ * pcp_crack_directions_fetch: rows first .. first + max_rows - 1 of that call's table, the rows and order of
+ * pcp_crack_components_fetch: out_id and out_rows20, 20 int64 per row -- for each of the ten moment words in the order above
+ * the sum over the crack's members as (lo, hi): lo = the sum of (v & 0xffffffff), hi = the sum of (v >> 32) (arithmetic), the
+ * value hi * 2^32 + lo.  Word 0 is the number of ordered links L; the three S1 sums are exactly zero (every link is counted
+ * from both ends with opposite offsets).  The table lives until the next _add, _end or drop of the accumulation; later
+ * pcp_crack_components / _lengths / _skeleton keep it.
+ * pcp_crack_directions_host: host only, no context, no GPU: the same results for n <= 65536 points (xyz interleaved) by brute
+ * force over the pairs; out_id n and out_rows20 20 n of capacity (all outputs nullable).
+ * pcp_crack_axis_host: host only, fp64: out5 = L, the unit eigenvector of the largest eigenvalue of S2 / L under the sign rule
+ * above, and its anisotropy, the words rebuilt as (double)hi * 2^32 + (double)lo.  L < 2 or a zero largest eigenvalue: axis
+ * (0, 0, 0) and anisotropy 0.  A NULL argument: PCP_ERR_INVALID. */
+int pcp_crack_directions(pcp_context *ctx, const pcp_crack_link_params *p, float *out_tangent, float *out_anisotropy, int32_t *out_links,
+                         int64_t *out_moments, int64_t *out_crack_points, int64_t *out_cracks);
+int pcp_crack_directions_fetch(pcp_context *ctx, int64_t first, int64_t max_rows, int32_t *out_id, int64_t *out_rows20, int64_t *out_rows);
+int pcp_crack_directions_host(int64_t n, const float *xyz, const uint32_t *views, int32_t min_views, float radius, float *out_tangent,
+                              float *out_anisotropy, int32_t *out_links, int64_t *out_moments, int32_t *out_id, int64_t *out_rows20,
+                              int64_t *out_cracks);
+int pcp_crack_axis_host(const int64_t row20[20], double out5[5]);
 
 /* ---- planar facets of the map (the reference's scripts stop at per-keyframe pictures: no step partitions the map) ---------- */
 /* The faces of the structure as connected components of the map points under a symmetric integer link, one row of exact

@@ -822,6 +822,49 @@ def crack_lengths_host(xyz, views, min_views: int = 1, radius: float = 0.02, sum
     return dict(pos=pos, ids=ids[:c].copy(), rows=rows[:c].copy(), offsets=offsets[:c + 1].copy(), path=path[:e].copy(), cracks=c, path_points=e)
 
 
+CD_WORD = ("links", "s1x", "s1y", "s1z", "s2xx", "s2xy", "s2xz", "s2yy", "s2yz", "s2zz")  # CD2: the moment words; CD4: a row holds (lo, hi) of each
+
+
+def crack_axis_host(rows) -> dict:
+    """CD5 on the rows of crack_directions (pcp_crack_axis_host: host only, fp64): rows (C, 20) int64 -> dict(link_count (C,)
+    float64, the ordered links of every crack; axis (C, 3) float64, the unit direction of the crack with its largest component
+    positive, zeros where there is none; axis_anisotropy (C,) float64)."""
+    L = load()
+    rows = np.ascontiguousarray(rows, np.int64).reshape(-1, 20)
+    out = np.zeros((rows.shape[0], 5), np.float64)
+    for k in range(rows.shape[0]):
+        rc = L.pcp_crack_axis_host(_ptr(rows[k]), _ptr(out[k]))
+        if rc != PCP_OK:
+            raise PcpError(rc, L.pcp_last_error(None).decode())
+    return dict(link_count=out[:, 0].copy(), axis=out[:, 1:4].copy(), axis_anisotropy=out[:, 4].copy())
+
+
+def crack_directions_host(xyz, views, min_views: int = 1, radius: float = 0.02) -> dict:
+    """What Context.crack_directions returns (with the moments, without the labels), computed on the CPU by brute force over the
+    pairs (pcp_crack_directions_host: no context, no GPU): xyz (n, 3) float32, views (n,) uint32, n <= 65536."""
+    L = load()
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    views = np.ascontiguousarray(views, np.uint32)
+    n = xyz.shape[0]
+    if views.shape != (n,):
+        raise ValueError(f"crack_directions_host: {n} views expected, got shape {views.shape}")
+    tangent = np.zeros((n, 3), np.float32)
+    anisotropy = np.zeros(n, np.float32)
+    links = np.zeros(n, np.int32)
+    moments = np.zeros((n, 10), np.int64)
+    ids = np.empty(n, np.int32)
+    rows = np.empty((n, 20), np.int64)
+    cracks = C.c_int64()
+    rc = L.pcp_crack_directions_host(C.c_int64(n), _ptr(xyz), _ptr(views), C.c_int32(min_views), C.c_float(radius), _ptr(tangent),
+                                     _ptr(anisotropy), _ptr(links), _ptr(moments), _ptr(ids), _ptr(rows), C.byref(cracks))
+    if rc != PCP_OK:
+        raise PcpError(rc, L.pcp_last_error(None).decode())
+    c = cracks.value
+    out = dict(tangent=tangent, anisotropy=anisotropy, links=links, moments=moments, ids=ids[:c].copy(), rows=rows[:c].copy(), cracks=c)
+    out.update(crack_axis_host(out["rows"]))
+    return out
+
+
 CS_NODE = ("crack_row", "band", "points", "sum_w", "min_w", "max_w", "sum_qx", "sum_qy", "sum_qz", "degree")  # CS4: the columns of nodes
 CS_EDGE = ("u", "v", "links")  # CS5
 CS_CRACK = ("nodes", "edges", "ends", "junctions", "loops", "max_degree")  # CS6
@@ -1648,6 +1691,34 @@ class Context:
         self._check(self.lib.pcp_crack_paths_fetch(self.h, C.c_int64(0), C.c_int64(e), _ptr(path), C.byref(got)))
         assert got.value == e, (got.value, e)
         return dict(pos=pos, ids=ids, rows=rows, offsets=offsets, path=path, cracks=c, path_points=e)
+
+    # -- crack directions on the map ("Crack directions on the map") -------------
+    def crack_directions(self, min_views: int = 1, radius: float = 0.02, want_moments: bool = False) -> dict:
+        """Which way every crack of the map runs, from the live accumulation (pcp_crack_directions and its fetch): tangent
+        (n, 3) float32, the unit direction of the crack at a crack point with its largest component positive, and anisotropy
+        (n,) float32 (1 on a line), zeros where there is none; links (n,) int32; with want_moments moments (n, 10) int64, the
+        columns CD_WORD; ids (C,) int32 ascending, the rows of crack_components; rows (C, 20) int64, (lo, hi) of the summed
+        words; per crack, through crack_axis_host, axis (C, 3), axis_anisotropy (C,) and link_count (C,) float64; plus
+        crack_points and cracks (counts)."""
+        prm = CrackLinkParams(min_views, radius)
+        tangent = np.empty((self.n, 3), np.float32)
+        anisotropy = np.empty(self.n, np.float32)
+        links = np.empty(self.n, np.int32)
+        moments = np.empty((self.n, 10), np.int64) if want_moments else None
+        pts, cracks = C.c_int64(), C.c_int64()
+        self._check(self.lib.pcp_crack_directions(self.h, C.byref(prm), _ptr(tangent), _ptr(anisotropy), _ptr(links), _ptr(moments),
+                                                  C.byref(pts), C.byref(cracks)))
+        c = cracks.value
+        ids = np.empty(c, np.int32)
+        rows = np.empty((c, 20), np.int64)
+        got = C.c_int64()
+        self._check(self.lib.pcp_crack_directions_fetch(self.h, C.c_int64(0), C.c_int64(c), _ptr(ids), _ptr(rows), C.byref(got)))
+        assert got.value == c, (got.value, c)
+        out = dict(tangent=tangent, anisotropy=anisotropy, links=links, ids=ids, rows=rows, crack_points=pts.value, cracks=c)
+        if want_moments:
+            out["moments"] = moments
+        out.update(crack_axis_host(rows))
+        return out
 
     # -- crack skeletons on the map (DESIGN.md, "Crack skeletons on the map") --------------
     def crack_skeleton(self, min_views: int = 1, radius: float = 0.02, step=None) -> dict:

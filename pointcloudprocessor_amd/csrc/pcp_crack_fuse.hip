@@ -401,7 +401,8 @@ int crack_map_run(pcp_context *ctx, const pcp_crack_link_params &p, CrackMap::Le
 }
 
 int crack_window(pcp_context *ctx, const char *who, CrackMap::Level l, int64_t first, int64_t max_rows, int64_t have, int64_t *rows) {
-  static const char *const maker[] = {"pcp_crack_fuse_begin", "pcp_crack_components", "pcp_crack_lengths", "pcp_crack_skeleton"};
+  static const char *const maker[] = {"pcp_crack_fuse_begin", "pcp_crack_components", "pcp_crack_lengths", "pcp_crack_skeleton",
+                                      "pcp_crack_directions"};
   if (first < 0 || max_rows < 0) return set_error(ctx, PCP_ERR_INVALID, "%s: negative first or max_rows", who);
   if (!ctx->crack->readable(l)) return set_error(ctx, PCP_ERR_STATE, "%s: no table (%s on the accumulation as it is)", who, maker[l]);
   *rows = std::max<int64_t>(0, std::min(max_rows, have - first));

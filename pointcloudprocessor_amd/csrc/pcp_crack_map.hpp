@@ -9,26 +9,28 @@ namespace pcp {
 
 // ---- the chain's results in the context (ctx->crack) ----------------------------------------------------------------------
 // Four levels, each made from the one below: the fusion (pcp_crack_fuse_begin .. _end), and the tables of the last
-// pcp_crack_components, pcp_crack_lengths and pcp_crack_skeleton.  A level is live or not; only the member functions below
-// change that, and every fetch asks readable().
+// pcp_crack_components, pcp_crack_lengths and pcp_crack_skeleton; and one side level made from the components, the directions
+// of the last pcp_crack_directions (CD6).  A level is live or not; only the member functions below change that, and every fetch
+// asks readable().
 //
-//   event                                   fusion      components   lengths + paths   skeleton
-//   pcp_crack_fuse_begin                    new, empty  dropped      dropped           dropped
-//   pcp_crack_fuse_add (success)            updated     invalid      invalid           invalid
-//   pcp_crack_components                    -           replaced     KEPT              KEPT
-//   pcp_crack_lengths                       -           replaced     replaced          invalid
-//   pcp_crack_skeleton                      -           replaced     replaced          replaced
+//   event                                   fusion      components   lengths + paths   skeleton    directions
+//   pcp_crack_fuse_begin                    new, empty  dropped      dropped           dropped     dropped
+//   pcp_crack_fuse_add (success)            updated     invalid      invalid           invalid     invalid
+//   pcp_crack_components                    -           replaced     KEPT              KEPT        KEPT
+//   pcp_crack_lengths                       -           replaced     replaced          invalid     KEPT
+//   pcp_crack_skeleton                      -           replaced     replaced          replaced    KEPT
+//   pcp_crack_directions                    -           replaced     KEPT              KEPT        replaced
 //   pcp_crack_fuse_end, the cloud uploads,
-//   pcp_set_camera, pcp_set_frames          dropped     dropped      dropped           dropped
+//   pcp_set_camera, pcp_set_frames          dropped     dropped      dropped           dropped     dropped
 //
 // A call that fails after its parameter checks leaves the levels it was about to replace invalid; on a context with n == 0 it
-// succeeds and leaves them live with zero rows.  So the lengths and the skeleton outlive a pcp_crack_components with other
-// parameters: they describe the accumulation, not the components table.
+// succeeds and leaves them live with zero rows.  So the lengths, the skeleton and the directions outlive a pcp_crack_components
+// with other parameters: they describe the accumulation, not the components table.
 struct CrackCounts {
   int64_t points = 0, cracks = 0, entries = 0, nodes = 0, edges = 0;
 };
 struct CrackMap {
-  enum Level { kFusion = 0, kComponents, kLengths, kSkeleton };
+  enum Level { kFusion = 0, kComponents, kLengths, kSkeleton, kDirections };
   // fusion: SoA planes of n in input order -- seen | views | centres | min_q | max_q | best_q and sum_q | best_key -- and the
   // keyframes added so far
   DevBuf<uint32_t> cf_u32;
@@ -49,10 +51,16 @@ struct CrackMap {
   DevBuf<int32_t> cs_ids;
   DevBuf<unsigned long long> cs_nodes, cs_cracks;
   std::vector<int64_t> cs_edges;
+  // directions: the ids and cd::kRowWords integers per crack
+  int64_t cd_rows = 0;
+  DevBuf<int32_t> cd_ids;
+  DevBuf<unsigned long long> cd_table;
 
-  bool readable(Level l) const { return cf_live && (l == kFusion || (l == kComponents ? cc_live : l == kLengths ? cl_live : cs_live)); }
+  bool readable(Level l) const {
+    return cf_live && (l == kFusion || (l == kComponents ? cc_live : l == kLengths ? cl_live : l == kSkeleton ? cs_live : cd_live));
+  }
   void begin() { set_live(kFusion, kFusion, true); }                  // (after release(): an empty accumulation)
-  void changed() { set_live(kComponents, kSkeleton, false); }         // a keyframe was added: every table describes the state before it
+  void changed() { set_live(kComponents, kSkeleton, false), cd_live = false; }  // a keyframe was added: every table describes the state before it
   void replacing(Level upto) {  // a call is about to make the tables up to `upto`; new lengths also end the skeleton made from the old ones
     set_live(kComponents, upto == kComponents ? kComponents : kSkeleton, false);
     hold_counts(upto, CrackCounts());
@@ -62,8 +70,12 @@ struct CrackMap {
     hold_counts(upto, c);
     set_live(kComponents, upto, true);
   }
+  void replacing_directions() { cd_live = false, cd_rows = 0; }  // pcp_crack_directions, beside replacing(kComponents) ...
+  void hold_directions(int64_t rows) { cd_rows = rows, cd_live = true; }  // ... and beside hold(kComponents, ..)
   void release() {  // everything dropped, memory released
     set_live(kFusion, kSkeleton, false);
+    replacing_directions();
+    cd_ids.release(), cd_table.release();
     hold_counts(kSkeleton, CrackCounts());
     cf_added.clear();
     cf_u32.release(), cf_u64.release();
@@ -74,7 +86,7 @@ struct CrackMap {
   }
 
  private:
-  bool cf_live{false}, cc_live{false}, cl_live{false}, cs_live{false};
+  bool cf_live{false}, cc_live{false}, cl_live{false}, cs_live{false}, cd_live{false};
   void set_live(Level a, Level b, bool v) {
     if (a <= kFusion && kFusion <= b) cf_live = v;
     if (a <= kComponents && kComponents <= b) cc_live = v;
@@ -115,6 +127,14 @@ struct CsScratch {
   DevBuf<unsigned long long> keys, edges;
   DevBuf<uint32_t> links, words;
 };
+// direction stage: tangent (3 n) | anisotropy (n) in f32, links (n) and moments (10 n, nullable), all in input order and zero
+// for a point that is no crack point; words[0]: a point with gn::kMaxNeighbours links or more
+struct CdScratch {
+  DevBuf<float> f32;
+  DevBuf<int32_t> links;
+  DevBuf<long long> moments;
+  DevBuf<uint32_t> words;
+};
 
 // ---- the stages (ctx->n > 0, checked parameters, a live fusion); queued on ctx->stream and synchronised only as far as
 // their counts need.  Each runs on what the one before left in the scratch and in ctx->g_*. -----------------------------------
@@ -154,6 +174,7 @@ hipError_t preload_crack_width();
 hipError_t preload_crack_fuse();
 hipError_t preload_crack_length();
 hipError_t preload_crack_skeleton();
+hipError_t preload_crack_direction();
 
 // ---- the links of a crack point --------------------------------------------------------------------------------------------
 // visit(c) for the candidate places c of place s (query coordinates q, m places in the cell order): the rows of the

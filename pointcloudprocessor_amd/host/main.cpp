@@ -157,6 +157,19 @@
 //     junctions, loops, skeleton_length_m and the centroids of its end and junction nodes (end_xyz, junction_xyz).  The
 //     reference's script skeletonises each keyframe's mask in 2-D (preprocess(): pcv.morphology.skeletonize).  Made on the GPU
 //     (pcp_crack_skeleton; DESIGN.md "Crack skeletons on the map").  Every other output stays as it is.
+//   * --crackDirection 0|1 (new, default 0; needs --crackFuse 1 and is refused where that is) and --crackUp x,y,z (new, default
+//     0,0,1: finite, not zero, normalised in fp64): with 1 the run also writes <outputPath>crack_width/map_tangent.npy (<f4,
+//     (n, 3): the unit direction of the point's crack at the point, from the covariance of its links, its largest component
+//     positive; zeros for a point with fewer than two links or outside every crack), map_anisotropy.npy (<f4, (n): 1 where the
+//     links lie on a line, about 1/2 on a flat patch, 0 without a tangent) and crack_directions_3d.json: one record per crack,
+//     the cracks and order of cracks_3d.json, with id, links (ordered: every link counts from both ends), axis (the unit
+//     direction of the whole crack, zeros when it has none), anisotropy, inclination_deg = acos|axis . up| (0..90) and class:
+//     vertical below 22.5, horizontal above 67.5, else diagonal; none without an axis.  With --facets 1 also facet (as in
+//     cracks_3d.json), facet_kind (plane, cylinder, none), for a plane out_of_plane_deg = asin|axis . normal|, and for a
+//     cylinder --facetCylinders 1 fitted to_axis_deg = acos|axis . a| with cylinder_class: longitudinal below 22.5,
+//     circumferential above 67.5, else diagonal.  The reference only blurs one keyframe's 2-D skeleton and shows it
+//     (scripts/evalSkeletonDirection.py).  Made on the GPU (pcp_crack_directions; DESIGN.md "Crack directions on the map").
+//     Every other output stays as it is.
 //   * --balanceImages 0|1 (new, default 0 = the reference's behaviour), --claheClip c (new, default 1.0; 0 = no clipping),
 //     --claheTiles x,y (new, default 8,8, each 1..16) and --balanceGamma g (new, default 0.8; 1 = identity table): with 1,
 //     every keyframe is colour-balanced on the GPU as it is uploaded -- CLAHE on a lightness channel, then a gamma table --
@@ -321,6 +334,8 @@ struct Options {
   bool crack_length = false;          // --crackLength 1: with --crackFuse, the cracks' lengths, ends and centrelines (crack_width/crack_*)
   bool crack_skeleton = false;        // --crackSkeleton 1: with --crackFuse, the cracks' branches, junctions and loops (crack_width/crack_*)
   float crack_skeleton_step = 0.0f;   // --crackSkeletonStep: the band width in metres (0: twice the link radius)
+  bool crack_direction = false;       // --crackDirection 1: with --crackFuse, the cracks' tangents and axes (crack_width/map_tangent.npy, ...)
+  double crack_up[3] = {0.0, 0.0, 1.0};  // --crackUp x,y,z: what vertical means (unit)
   bool crack_fuse = false;            // --crackFuse 1: the widths on the map and the map's cracks (crack_width/map_*.npy, cracks_3d.json)
   float crack_link_radius = 0.02f;    // --crackLinkRadius r: crack points this close belong to one crack
   int crack_min_views = 1;            // --crackMinViews v: credited keyframes a crack point needs
@@ -598,6 +613,23 @@ static Options parse(int argc, char **argv) {
     else if (a == "--crackLength") o.crack_length = parse_bool(next());
     else if (a == "--crackSkeleton") o.crack_skeleton = parse_bool(next());
     else if (a == "--crackSkeletonStep") o.crack_skeleton_step = std::stof(next());
+    else if (a == "--crackDirection") o.crack_direction = parse_bool(next());
+    else if (a == "--crackUp") {
+      const std::string v = next();
+      double u[3] = {0.0, 0.0, 0.0};
+      const char *at = v.c_str();
+      bool ok = !v.empty();
+      for (int k = 0; k < 3 && ok; ++k) {
+        char *end = nullptr;
+        u[k] = std::strtod(at, &end);
+        ok = end != at && std::isfinite(u[k]) && *end == (k < 2 ? ',' : '\0');
+        at = end + 1;
+      }
+      const double len = ok ? std::sqrt((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]) : 0.0;
+      if (!ok || !(len > 0.0) || !std::isfinite(len))
+        throw std::runtime_error("the argument ('" + v + "') for option '--crackUp' is invalid (x,y,z: finite and not zero)");
+      for (int k = 0; k < 3; ++k) o.crack_up[k] = u[k] / len;
+    }
     else if (a == "--crackLinkRadius") {
       const std::string v = next();
       char *end = nullptr;
@@ -691,6 +723,8 @@ static Options parse(int argc, char **argv) {
     throw std::runtime_error("the option '--crackLength 1' needs the widths on the map (--crackFuse 1)");
   if (o.crack_skeleton && !o.crack_fuse)
     throw std::runtime_error("the option '--crackSkeleton 1' needs the widths on the map (--crackFuse 1)");
+  if (o.crack_direction && !o.crack_fuse)
+    throw std::runtime_error("the option '--crackDirection 1' needs the widths on the map (--crackFuse 1)");
   if (o.crack_skeleton && !(o.crack_skeleton_step >= 0.0f && o.crack_skeleton_step <= 16.0f))
     throw std::runtime_error("the option '--crackSkeletonStep' takes 0 (twice the link radius) or a band width in metres up to 16");
   if (o.crack_fuse && o.maskImageFolder.empty())
@@ -780,6 +814,8 @@ static void usage(std::ostream &os) {
         "  --crackMinViews arg (=1)              With --crackFuse: keyframes with a width that a crack point needs (1..4096)\n"
         "  --crackLength arg (=0)                With --crackFuse: also write every crack's length, ends and centreline\n"
         "  --crackSkeleton arg (=0)              With --crackFuse: also write every crack's skeleton: branches, junctions, loops\n"
+        "  --crackDirection arg (=0)             With --crackFuse: also write every crack point's tangent and every crack's axis and class\n"
+        "  --crackUp arg (=0,0,1)                With --crackDirection: the vertical x,y,z (finite, not zero)\n"
         "  --orthoMap arg (=0)                   Also write one orthographic picture of the coloured cloud as .npy (--gpus 1)\n"
         "  --orthoGsd arg (=0.01)                With --orthoMap: metres per pixel (1e-4..1)\n"
         "  --orthoFill arg (=0)                  With --orthoMap: fill empty pixels from the nearest occupied one within R pixels\n"
@@ -1576,12 +1612,14 @@ class Processor {
     CrackMap m;
     CrackLengths cl;
     CrackSkeleton sk;
+    CrackDirections cdir;
     {
       const auto t0 = PhaseClock::clock::now();
       m = ViewCulling(dev).crackMap(added, static_cast<int64_t>(cloud.size()), opt.crack_threshold, opt.crack_plane_radius,
                                     opt.crack_min_views, opt.crack_link_radius, opt.crack_length ? &cl : nullptr,
-                                    opt.crack_skeleton ? &sk : nullptr, opt.crack_skeleton_step);
-      g_clock.add("crack_fuse_gpu_s", PhaseClock::since(t0) - cl.seconds - sk.seconds);
+                                    opt.crack_skeleton ? &sk : nullptr, opt.crack_skeleton_step, opt.crack_direction ? &cdir : nullptr);
+      g_clock.add("crack_fuse_gpu_s", PhaseClock::since(t0) - cl.seconds - sk.seconds - cdir.seconds);
+      if (opt.crack_direction) g_clock.add("crack_direction_gpu_s", cdir.seconds);
       if (opt.crack_length) g_clock.add("crack_length_gpu_s", cl.seconds);
       if (opt.crack_skeleton) g_clock.add("crack_skeleton_gpu_s", sk.seconds);
     }
@@ -1633,6 +1671,7 @@ class Processor {
               << " credited samples, " << m.crack_points << " crack points, " << m.ids.size() << " cracks" << std::endl;
     if (opt.crack_length) writeCrackLengths(cl, stem);
     if (opt.crack_skeleton) writeCrackSkeleton(sk, m, stem);
+    if (opt.crack_direction) writeCrackDirections(cdir, crack_facet, stem);
     if (opt.ortho_map && !opt.ortho_by_facet) {  // the widths and the cracks drawn on the orthographic map: map_width[index], map_crack[index]
       const size_t h = static_cast<size_t>(ortho_frame_used.height), w = static_cast<size_t>(ortho_frame_used.width);
       std::vector<float> width(ortho_index.size(), 0.0f);
@@ -2003,6 +2042,57 @@ class Processor {
     if (!f) throw std::runtime_error("Couldn't save the crack skeletons of the map.");
     std::cout << "Crack skeletons on the map saved to: " << stem << "map_crack_node.npy, crack_nodes.npy, crack_node_ids.npy, crack_edges.npy and "
               << "crack_skeleton_3d.json, " << cracks << " cracks, " << nodes << " nodes, " << edges << " edges" << std::endl;
+  }
+
+  // --crackDirection 1: every crack point's tangent, and every crack's axis against the vertical and against its facet
+  void writeCrackDirections(const CrackDirections &c, const std::vector<int32_t> &crack_facet, const std::string &stem) {
+    Phase ph("crack_direction_write_s");
+    const size_t n = c.anisotropy.size();
+    writeNpy(stem + "map_tangent.npy", "<f4", {n, 3}, c.tangent.data(), 3 * n * 4);
+    writeNpy(stem + "map_anisotropy.npy", "<f4", {n}, c.anisotropy.data(), n * 4);
+    std::ofstream f(stem + "crack_directions_3d.json");
+    auto num = [](double v) {
+      char b[64];
+      std::snprintf(b, sizeof(b), "%.9g", v);
+      return std::string(b);
+    };
+    const double deg = 180.0 / 3.14159265358979323846;
+    auto cosine = [](const double *a, double bx, double by, double bz) {  // |a . b| of two unit vectors, at most 1
+      return std::min(1.0, std::fabs((a[0] * bx + a[1] * by) + a[2] * bz));
+    };
+    f << "[";
+    for (size_t r = 0; r < c.ids.size(); ++r) {
+      const double *ax = c.axis.data() + 5 * r;
+      const bool has = ax[1] != 0.0 || ax[2] != 0.0 || ax[3] != 0.0;
+      const double incl = has ? std::acos(cosine(ax + 1, opt.crack_up[0], opt.crack_up[1], opt.crack_up[2])) * deg : 0.0;
+      f << (r ? ",\n " : "\n ") << "{\"id\": " << c.ids[r] << ", \"links\": " << static_cast<long long>(ax[0]) << ", \"axis\": [" << num(ax[1]) << ", "
+        << num(ax[2]) << ", " << num(ax[3]) << "], \"anisotropy\": " << num(ax[4]) << ", \"inclination_deg\": " << num(incl) << ", \"class\": \""
+        << (!has ? "none" : incl < 22.5 ? "vertical" : incl > 67.5 ? "horizontal" : "diagonal") << "\"";
+      if (opt.facets) {
+        const int32_t id = crack_facet[r];
+        const size_t fr = id < 0 ? facets_.ids.size() : static_cast<size_t>(std::lower_bound(facets_.ids.begin(), facets_.ids.end(), id) - facets_.ids.begin());
+        const bool known = fr < facets_.ids.size() && facets_.ids[fr] == id;
+        const bool plane = known && facets_.planar[fr];
+        const bool cylinder = known && !plane && opt.facet_cylinders && fr < facet_kind_.size() && facet_kind_[fr] == 2;
+        f << ", \"facet\": " << id << ", \"facet_kind\": \"" << (plane ? "plane" : cylinder ? "cylinder" : "none") << "\"";
+        if (plane && has) {
+          const double *pl = facets_.plane.data() + 7 * fr;
+          f << ", \"out_of_plane_deg\": " << num(std::asin(cosine(ax + 1, pl[3], pl[4], pl[5])) * deg);
+        }
+        if (cylinder && has) {
+          const pcp_cyl_frame &cy = facet_cyl_[fr];
+          const double to_axis = std::acos(cosine(ax + 1, cy.a[0], cy.a[1], cy.a[2])) * deg;
+          f << ", \"to_axis_deg\": " << num(to_axis) << ", \"cylinder_class\": \""
+            << (to_axis < 22.5 ? "longitudinal" : to_axis > 67.5 ? "circumferential" : "diagonal") << "\"";
+        }
+      }
+      f << "}";
+    }
+    f << "\n]\n";
+    f.close();
+    if (!f) throw std::runtime_error("Couldn't save the crack directions of the map.");
+    std::cout << "Crack directions on the map saved to: " << stem << "map_tangent.npy, map_anisotropy.npy and crack_directions_3d.json, "
+              << c.ids.size() << " cracks" << std::endl;
   }
 
   // --crackLength 1: every crack's geodesic length, ends and centreline on the map, and every point's arc position

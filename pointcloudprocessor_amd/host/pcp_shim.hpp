@@ -134,6 +134,18 @@ struct CrackLengths {
   double seconds = 0.0;            // wall time of the stage (the call and its fetches)
 };
 
+// The directions of the map's cracks (pcp_hip.h, "crack directions on the map"): per map point the tangent of its crack there,
+// per crack -- the rows and order of CrackMap -- the sums the axis is taken from, and the axis (pcp_crack_axis_host)
+struct CrackDirections {
+  std::vector<float> tangent;      // 3 per point: unit, the largest component positive; zeros: none (fewer than two links)
+  std::vector<float> anisotropy;   // l1 / trace of the point's link covariance: 1 on a line; 0: none
+  std::vector<int32_t> links;      // the point's links
+  std::vector<int32_t> ids;
+  std::vector<int64_t> rows;       // 20 per crack: (lo, hi) of the summed links, S1 x y z, S2 xx xy xz yy yz zz
+  std::vector<double> axis;        // 5 per crack: ordered links, the unit axis (zeros: none), its anisotropy
+  double seconds = 0.0;            // wall time of the stage (the call, its fetch and the axes)
+};
+
 // The skeletons of the map's cracks (pcp_hip.h, "crack skeletons on the map"): the level-set diagram of every crack -- nodes,
 // edges and one summary row per crack, the rows and order of CrackMap -- and per map point the id of its node.  The library
 // returns integers only; the metres are host arithmetic on them, here in one place.
@@ -492,9 +504,10 @@ class ViewCulling {
   // (scripts/genNormAndDistanceMask.py:476-478) lists per hand-picked pixel, for the whole map and with the cracks told apart
   // lengths (nullable): also the cracks' lengths, ends and centrelines for the same min_views and link radius
   // skeleton (nullable): also the cracks' skeletons for them and the band width skeleton_step (metres; 0: 2 * link_radius)
+  // directions (nullable): also the cracks' directions for the same min_views and link radius
   CrackMap crackMap(const std::vector<int> &keyframes, int64_t points, int threshold = 0, int plane_radius = 150, int min_views = 1,
                     float link_radius = 0.02f, CrackLengths *lengths = nullptr, CrackSkeleton *skeleton = nullptr,
-                    float skeleton_step = 0.0f) const {
+                    float skeleton_step = 0.0f, CrackDirections *directions = nullptr) const {
     CrackMap m;
     dev_.check(pcp_crack_fuse_begin(dev_.get()));
     try {
@@ -519,6 +532,7 @@ class ViewCulling {
       m.stats.resize(5 * static_cast<size_t>(rows));
       m.box.resize(6 * static_cast<size_t>(rows));
       dev_.check(pcp_crack_components_fetch(dev_.get(), 0, rows, m.ids.data(), m.stats.data(), m.box.data(), &got));
+      if (directions) *directions = crackDirections(points, min_views, link_radius);  // (it leaves the same component table)
       if (lengths) *lengths = crackLengths(points, min_views, link_radius);
       if (skeleton) *skeleton = crackSkeleton(points, min_views, link_radius, skeleton_step);
     } catch (...) {
@@ -543,6 +557,26 @@ class ViewCulling {
     c.path.resize(static_cast<size_t>(entries));
     dev_.check(pcp_crack_lengths_fetch(dev_.get(), 0, rows, c.ids.data(), c.rows.data(), c.offsets.data(), &got));
     dev_.check(pcp_crack_paths_fetch(dev_.get(), 0, entries, c.path.data(), &got));
+    c.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return c;
+  }
+  // Which way every crack of the live accumulation runs (between pcp_crack_fuse_begin and _end; crackMap runs it when asked):
+  // a tangent per crack point and an axis per crack, where scripts/evalSkeletonDirection.py blurs one keyframe's 2-D skeleton
+  CrackDirections crackDirections(int64_t points, int min_views = 1, float link_radius = 0.02f) const {
+    CrackDirections c;
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t n = static_cast<size_t>(points);
+    c.tangent.resize(3 * n);
+    c.anisotropy.resize(n);
+    c.links.resize(n);
+    const pcp_crack_link_params link{min_views, link_radius};
+    int64_t crack_points = 0, rows = 0, got = 0;
+    dev_.check(pcp_crack_directions(dev_.get(), &link, c.tangent.data(), c.anisotropy.data(), c.links.data(), nullptr, &crack_points, &rows));
+    c.ids.resize(static_cast<size_t>(rows));
+    c.rows.resize(20 * static_cast<size_t>(rows));
+    c.axis.assign(5 * static_cast<size_t>(rows), 0.0);
+    dev_.check(pcp_crack_directions_fetch(dev_.get(), 0, rows, c.ids.data(), c.rows.data(), &got));
+    for (size_t r = 0; r < static_cast<size_t>(rows); ++r) dev_.check(pcp_crack_axis_host(c.rows.data() + 20 * r, c.axis.data() + 5 * r));
     c.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return c;
   }

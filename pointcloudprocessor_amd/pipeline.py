@@ -394,7 +394,7 @@ class PointCloudColorizer:
         return self.engine.ctx.crack_width(frame, threshold, plane_radius, want)
 
     def crack_map(self, frames=None, threshold: int = 0, plane_radius: int = 150, min_views: int = 1, link_radius: float = 0.02,
-                  lengths: bool = False, skeleton: bool = False, skeleton_step=None) -> dict:
+                  lengths: bool = False, skeleton: bool = False, skeleton_step=None, directions: bool = False, up=(0.0, 0.0, 1.0)) -> dict:
         """The crack widths of the keyframes brought back to the map, and the map's cracks ("Crack widths on the
         map"): begin, one add per keyframe of `frames` (None: all of them), the components, end.  dict of the per-point arrays of
         capi.Context.crack_fuse_fetch (width_mean, width_best, best_frame, views, seen, centres, min_q, max_q, sum_q) and of
@@ -410,12 +410,20 @@ class PointCloudColorizer:
         the band width skeleton_step (metres; None: 2 * link_radius) ("Crack skeletons on the map"): per crack its
         nodes, edges, ends, junctions, loops and skeleton length.  Off, the return value is what it was.
 
+        directions: the dict gains `directions`, the dict of capi.Context.crack_directions for the same min_views and
+        link_radius ("Crack directions on the map"): per point the tangent of its crack and its anisotropy, per
+        crack the axis, plus inclination_deg = acos|axis . up| (0..90) and cls (vertical below 22.5, horizontal above 67.5, else
+        diagonal; none without an axis) against the vertical `up` (finite, not zero).  Off, the return value is what it was.
+
         An index shard sees only its own points, so world > 1 raises ValueError.  (The shards' key images would have to be
         merged first, as for geometry_maps; not built.)"""
         if self.world > 1:
             raise ValueError("crack_map: an index shard sees only its own points; the per-pixel keys of the shards would "
                              "have to be merged across ranks (all-reduce MIN), which is not built: run it on one rank "
                              "holding the whole map")
+        up = np.asarray(up, np.float64).reshape(-1)
+        if directions and not (up.shape == (3,) and np.isfinite(up).all() and np.linalg.norm(up) > 0.0):
+            raise ValueError("crack_map: up must be three finite numbers, not all zero")
         ctx = self.engine.ctx
         frames = range(ctx.n_frames) if frames is None else frames
         ctx.crack_fuse_begin()
@@ -423,6 +431,14 @@ class PointCloudColorizer:
             counts = [ctx.crack_fuse_add(int(f), threshold, plane_radius) for f in frames]
             out = ctx.crack_fuse_fetch()
             out.update(ctx.crack_components(min_views, link_radius))
+            if directions:  # (it leaves the same component table)
+                d = ctx.crack_directions(min_views, link_radius)
+                has = d["axis"].any(axis=1)
+                incl = np.degrees(np.arccos(np.minimum(1.0, np.abs(d["axis"] @ (up / np.linalg.norm(up))))))
+                d["inclination_deg"] = np.where(has, incl, 0.0)
+                d["cls"] = ["none" if not h else "vertical" if a < 22.5 else "horizontal" if a > 67.5 else "diagonal"
+                            for h, a in zip(has.tolist(), incl.tolist())]
+                out["directions"] = d
             if lengths:
                 out["lengths"] = ctx.crack_lengths(min_views, link_radius)
             if skeleton:
