@@ -87,7 +87,9 @@ extern "C" {
                                 entry points added, no layout changed: pcp_ortho_texture_cyl, pcp_ortho_texture_points_cyl_host,
                                 pcp_cyl_sincos_host (orthophotos of unrolled maps; nothing runs unless called);
                                 entry points added, no layout changed: pcp_crack_directions / _fetch / _host, pcp_crack_axis_host
-                                (crack directions on the map; nothing runs unless called) */
+                                (crack directions on the map; nothing runs unless called);
+                                entry points added, no layout changed: pcp_ortho_defects / _fetch / _table / _host
+                                (surface defects on ortho maps; nothing runs unless called) */
 
 #define PCP_OK 0
 #define PCP_ERR_INVALID (-1) /* bad argument */
@@ -1345,6 +1347,59 @@ int pcp_ortho_texture_cyl(pcp_context *ctx, const pcp_ortho_texture_params *para
 int pcp_ortho_texture_points_cyl_host(const pcp_cyl_frame *frame, const pcp_ortho_texture_params *params, const int32_t *source,
                                       const float *depth, float *out_xyz, uint8_t *out_ok);
 int pcp_cyl_sincos_host(int64_t n, const double *theta, double *out_sin, double *out_cos);
+
+/* ---- surface defects on ortho maps (no counterpart in the reference) ------------------------------------------------ */
+/* The depth layer of a finished map is the deviation of the surface from the frame's own surface: the plane of a facet's
+ * frame, or the fitted cylinder of an unrolled map.  This stage turns it into a signed deviation image against a local
+ * reference surface, the pixels beyond a threshold into 8-connected regions of one class, and every kept region into one row
+ * of integers ("Surface defects on ortho maps", SD1-SD9).  Opt-in: nothing runs unless one of these is called,
+ * PCP_ABI_VERSION is unchanged and a caller detects support by the symbols.  Kernels are timed under PCP_K_MISC.  The map is
+ * never modified.
+ *   params    threshold in metres, finite, 2^-20 <= t <= 1; window_px W in 0..1024; refine 0 or 1, and 1 needs W > 0;
+ *             min_support >= 1 (read only when W > 0); min_pixels >= 1; classes bit 0 hollows, bit 1 bulges, not 0.  Anything
+ *             else: PCP_ERR_INVALID with a message that names the field.  The parameters are checked before the state.
+ *   state     a live, finished map of either kind (pcp_ortho_finish); otherwise PCP_ERR_STATE.
+ *   pixel     surface iff its status is 1 or 2 and its depth is finite with |depth| <= 512 m; its quantum
+ *             q = llrint((double)depth * 2^20); T = llrint((double)threshold * 2^20).  Pixels refused for their depth are
+ *             counted and treated as empty.
+ *   W = 0     dev = q; hollow (class 1) iff q >= T, bulge (class 2) iff q <= -T.
+ *   W > 0     S, n: sum of q and count of the surface pixels in rows r-W..r+W, columns c-W..c+W clipped to the raster (no
+ *             wrap across a cylinder's seam); n < min_support: unsupported (class 0, dev 0, counted); else e = q n - S,
+ *             dev = e / n truncated, hollow iff e >= T n, bulge iff e <= -T n.
+ *   refine    a second pass over the surface pixels whose first-pass class (every class bit on) is 0: a pixel whose second
+ *             count reaches min_support takes S, n, e, dev and class from it, any other keeps the first pass's and is
+ *             counted.  The classes mask is applied after the last pass.
+ *   regions   8-connected pixels of one class; fewer than min_pixels pixels: dropped (region 0; class and dev kept); the kept
+ *             ones are numbered 1..N in ascending order of their lowest linear pixel index.
+ *   row       16 int64: class, pixels, pixels of status 1, sum |dev|, max |dev|, its pixel (the lowest among equals), col
+ *             min, col max, row min, row max, sum col, sum row, open pixels (on the raster's edge, or with a 4-neighbour that
+ *             is no surface pixel), first pixel, pixels on the first pass's reference, 0.
+ *   out[8]    regions kept, regions dropped, hollow pixels, bulge pixels, unsupported pixels, pixels refused for their depth,
+ *             pixels on the first pass's reference, surface pixels.
+ * Depth grows away from the viewer in both kinds of frame, so a hollow is material missing and a bulge material towards the
+ * viewer.  The library returns integers only: area = pixels gsd^2, volume = sum |dev| 2^-20 gsd^2, depth = max |dev| 2^-20.
+ * pcp_ortho_defects_fetch: the H x W layers (each nullable): dev in quanta, class, region id.  pcp_ortho_defects_table: rows
+ * first .. first + max_rows - 1 (out_rows16 nullable: *out_rows alone says how many there are from `first`).  The results
+ * belong to the live map: replaced by the next pcp_ortho_defects, dropped by pcp_ortho_finish, either begin, pcp_ortho_end and
+ * pcp_destroy; a refused call leaves them; without results both fetches are PCP_ERR_STATE.
+ * pcp_ortho_defects_host: the same from the depth and status layers of a map (pcp_ortho_fetch / pcp_ortho_host), on the CPU by
+ * the same arithmetic (csrc/pcp_ortho_defects.hpp), bit for bit what the device gives; width, height 1..16384 and at most 2^26
+ * pixels; outputs nullable but out; at most max_rows rows are written, *out_rows is their whole number.  Messages at
+ * pcp_last_error(NULL). */
+typedef struct pcp_ortho_defect_params {
+  float threshold;     /* metres */
+  int32_t window_px;   /* W: 0 = against the frame's own surface */
+  int32_t refine;      /* 0 or 1 */
+  int32_t min_support; /* surface pixels a window needs */
+  int32_t min_pixels;  /* pixels a region needs to be kept */
+  int32_t classes;     /* bit 0 hollows, bit 1 bulges */
+} pcp_ortho_defect_params;
+int pcp_ortho_defects(pcp_context *ctx, const pcp_ortho_defect_params *params, int64_t out[8]);
+int pcp_ortho_defects_fetch(pcp_context *ctx, int32_t *out_dev, uint8_t *out_class, int32_t *out_region);
+int pcp_ortho_defects_table(pcp_context *ctx, int64_t first, int64_t max_rows, int64_t *out_rows16, int64_t *out_rows);
+int pcp_ortho_defects_host(int32_t width, int32_t height, const float *depth, const uint8_t *status,
+                           const pcp_ortho_defect_params *params, int64_t out[8], int32_t *out_dev, uint8_t *out_class,
+                           int32_t *out_region, int64_t *out_rows16, int64_t max_rows, int64_t *out_rows);
 
 /* ---- precondition of the match-back(PointCloudProcessor.cpp:480-482,571) ------------------------------- */
 /* Number of map points that have ANOTHER map point closer than `radius` (fp32 squared distance, strict <, as

@@ -349,6 +349,52 @@ def ortho_host(frame, xyz, rgb, label=None, has=None, index_base: int = 0, fill_
     return out
 
 
+class OrthoDefectParams(C.Structure):
+    """pcp_ortho_defect_params (DESIGN.md, "Surface defects on ortho maps", SD1)."""
+    _fields_ = [("threshold", C.c_float), ("window_px", C.c_int32), ("refine", C.c_int32), ("min_support", C.c_int32),
+                ("min_pixels", C.c_int32), ("classes", C.c_int32)]
+
+
+DEFECT_OUT = ("kept", "dropped", "hollow_pixels", "bulge_pixels", "unsupported", "refused", "first_pass", "surface")
+DEFECT_ROW = ("class", "pixels", "measured", "sum_dev", "max_dev", "max_pixel", "col_min", "col_max", "row_min", "row_max", "sum_col",
+              "sum_row", "open", "first_pixel", "first_pass", "zero")
+DEFECT_HOLLOW, DEFECT_BULGE = 1, 2
+
+
+def ortho_defect_params(threshold: float = 0.002, window: int = 0, refine: bool = False, min_support: int = 1, min_pixels: int = 1,
+                        classes: int = 3) -> OrthoDefectParams:
+    return OrthoDefectParams(float(np.float32(threshold)), int(window), int(refine), int(min_support), int(min_pixels), int(classes))
+
+
+def ortho_defects_host(depth, status, threshold: float = 0.002, window: int = 0, refine: bool = False, min_support: int = 1,
+                       min_pixels: int = 1, classes: int = 3) -> dict:
+    """The surface defects of a map's (H, W) depth and status layers computed on the CPU by the arithmetic the kernels use
+    (pcp_ortho_defects_host: no context, no GPU; DESIGN.md "Surface defects on ortho maps", SD9):
+    dict(out (8 int64, DEFECT_OUT), dev int32, cls uint8, region int32, rows (N, 16) int64 (DEFECT_ROW))."""
+    L = load()
+    depth = np.ascontiguousarray(depth, np.float32)
+    status = np.ascontiguousarray(status, np.uint8)
+    if depth.ndim != 2 or status.shape != depth.shape:
+        raise ValueError("ortho_defects_host: depth and status are a map's height x width layers")
+    h, w = depth.shape
+    p = ortho_defect_params(threshold, window, refine, min_support, min_pixels, classes)
+    out = np.zeros(8, np.int64)
+    res = dict(out=out, dev=np.empty((h, w), np.int32), cls=np.empty((h, w), np.uint8), region=np.empty((h, w), np.int32))
+    n = C.c_int64()
+    rows = np.zeros((4096, 16), np.int64)  # (a second call only where a raster keeps more regions than this)
+    for _ in range(2):
+        rc = L.pcp_ortho_defects_host(C.c_int32(w), C.c_int32(h), _ptr(depth), _ptr(status), C.byref(p), _ptr(out), _ptr(res["dev"]),
+                                      _ptr(res["cls"]), _ptr(res["region"]), _ptr(rows), C.c_int64(len(rows)), C.byref(n))
+        if rc != PCP_OK:
+            raise PcpError(rc, L.pcp_last_error(None).decode())
+        if n.value <= len(rows):
+            break
+        rows = np.zeros((n.value, 16), np.int64)
+    rows = rows[:n.value].copy()
+    res["rows"] = rows
+    return res
+
+
 def ortho_fit_frame_host(xyz, gsd: float, has=None, viewer=None) -> OrthoFrame:
     """A frame that looks straight at the rows (pcp_ortho_fit_frame_host: host only, fp64): the plane of their covariance's
     smallest eigenvalue, n signed away from `viewer` (3 numbers; None: largest component negative)."""
@@ -1495,6 +1541,41 @@ class Context:
     def ortho_end(self):
         self._check(self.lib.pcp_ortho_end(self.h))
         self._ortho_frame = None
+
+    # -- surface defects on ortho maps ("Surface defects on ortho maps") ---
+    def ortho_defects(self, threshold: float = 0.002, window: int = 0, refine: bool = False, min_support: int = 1, min_pixels: int = 1,
+                      classes: int = 3) -> dict:
+        """The surface defects of the live, finished map (pcp_ortho_defects): hollows and bulges of its depth layer beyond
+        `threshold` metres against the mean of a (2 window + 1)-pixel square (window 0: against the frame's own surface).
+        Returns the eight counts (DEFECT_OUT); the layers and the table stay on the device for ortho_defects_fetch / _table."""
+        p = ortho_defect_params(threshold, window, refine, min_support, min_pixels, classes)
+        out = np.zeros(8, np.int64)
+        self._check(self.lib.pcp_ortho_defects(self.h, C.byref(p), _ptr(out)))
+        return {k: int(v) for k, v in zip(DEFECT_OUT, out)}
+
+    def ortho_defects_fetch(self) -> dict:
+        """dict(dev int32 in quanta of 2^-20 m, cls uint8 (0, 1 hollow, 2 bulge), region int32 (0: none)), each (H, W)."""
+        f = getattr(self, "_ortho_frame", None)
+        if f is None:  # no map was ever begun on this context: the library says so
+            self._check(self.lib.pcp_ortho_defects_fetch(self.h, None, None, None))
+            raise PcpError(PCP_ERR_STATE, "ortho_defects_fetch: no map")
+        self._check(self.lib.pcp_ortho_defects_fetch(self.h, None, None, None))  # (the state, before anything is allocated)
+        h, w = int(f.height), int(f.width)
+        out = dict(dev=np.empty((h, w), np.int32), cls=np.empty((h, w), np.uint8), region=np.empty((h, w), np.int32))
+        self._check(self.lib.pcp_ortho_defects_fetch(self.h, _ptr(out["dev"]), _ptr(out["cls"]), _ptr(out["region"])))
+        return out
+
+    def ortho_defects_table(self, first: int = 0, max_rows: int | None = None) -> np.ndarray:
+        """Rows first .. first + max_rows - 1 (None: every row from `first`) of the last ortho_defects call's table
+        (pcp_ortho_defects_table): (rows, 16) int64, the columns of DEFECT_ROW."""
+        have = C.c_int64()
+        self._check(self.lib.pcp_ortho_defects_table(self.h, C.c_int64(first), C.c_int64((1 << 62) if max_rows is None else max_rows), None,
+                                                     C.byref(have)))
+        rows = np.zeros((have.value, 16), np.int64)
+        if have.value:
+            got = C.c_int64()
+            self._check(self.lib.pcp_ortho_defects_table(self.h, C.c_int64(first), C.c_int64(have.value), _ptr(rows), C.byref(got)))
+        return rows
 
     def ortho_texture(self, scale: int, views: int = 1, interpolate: bool = True, max_step: float = 0.05, rect=None) -> dict:
         """The orthophoto of the finished map at `scale` fine pixels per ortho pixel and axis, coloured straight from the

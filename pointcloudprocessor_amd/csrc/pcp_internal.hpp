@@ -209,6 +209,22 @@ struct OrthoMap {
   DevBuf<int32_t> source;  // per pixel: the pixel its values come from (-1: empty), after _finish
 };
 
+// surface defects of the live, finished map (pcp_ortho_defects.hip): the three layers, the table (16 words per kept region)
+// and the counts of the last pcp_ortho_defects.  SD8: replaced by the next one; dropped by _finish, either begin, _end.
+struct OrthoDefects {
+  bool live = false;
+  int64_t rows = 0;
+  int64_t out[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  DevBuf<int32_t> dev, region;
+  DevBuf<uint8_t> cls;
+  DevBuf<unsigned long long> table;
+  void release() {
+    live = false;
+    rows = 0;
+    dev.release(), region.release(), cls.release(), table.release();
+  }
+};
+
 struct CrackMap;  // (the crack chain's header)
 
 // planar facets (pcp_facets.hip): the labels (n, input order; -1: in no facet) and the table of the last pcp_facets -- ids,
@@ -437,6 +453,7 @@ struct pcp_context {
   pcp::VoxelReduce voxel_reduce;
   // orthographic maps: the same lifetime (only pcp_ortho_begin / _end and pcp_destroy drop it)
   pcp::OrthoMap ortho;
+  pcp::OrthoDefects ortho_defects;
 
   // geometry maps (pcp_normals.hip): normal + curvature (float4) and neighbour count per point of the uploaded cloud, input
   // order, dropped by the uploads; the key image and the four output images of pcp_frame_geometry (allocated on first use)
@@ -748,6 +765,7 @@ hipError_t preload_mask_edt();
 hipError_t preload_ortho();
 hipError_t preload_ortho_texture();
 hipError_t preload_facets();
+hipError_t preload_ortho_defects();
 // the device parts of pcp_mask_edt (one keyframe, with nearest) and pcp_frame_geometry under the caller's name: checks and
 // kernels, the results left in md_bits / md_d2 / md_nearest and gm_out / s_counter[0]; no copy, no synchronisation
 int mask_edt_device(pcp_context *ctx, const char *who, int32_t frame, int32_t threshold);

@@ -260,6 +260,7 @@ static int or_check_cyl_frame(const char *who, const pcp_cyl_frame *fr, char *ms
 
 static void or_drop(pcp_context *ctx) {
   OrthoMap &m = ctx->ortho;
+  ctx->ortho_defects.release();  // SD8: the defects belong to the live map
   m.keys.release();
   m.payload.release();
   m.source.release();
@@ -458,6 +459,7 @@ int pcp_ortho_finish(pcp_context *ctx, int32_t fill_radius_px, int64_t *out_occu
   if (!m.live) return set_error(ctx, PCP_ERR_STATE, "pcp_ortho_finish: no accumulation (call pcp_ortho_begin)");
   if (fill_radius_px < 0 || fill_radius_px > om::kMaxFill)
     return set_error(ctx, PCP_ERR_INVALID, "pcp_ortho_finish: fill radius %d outside 0..%d pixels", fill_radius_px, om::kMaxFill);
+  ctx->ortho_defects.release();  // SD8: every accepted finish drops the defects of the map
   if (!(m.finished && fill_radius_px == m.fill_radius)) {  // (the key image stays as the adds left it: any radius can follow)
     PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int32_t w = m.frame.width, h = m.frame.height;

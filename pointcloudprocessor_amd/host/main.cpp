@@ -181,6 +181,16 @@
 //     sees the balanced keyframes too, as it does when the folder was balanced.  The three value flags without
 //     --balanceImages 1 are errors.  Works with every cull and match mode, --gpus N (every GPU balances its own copy of the
 //     same pixels), --streamColour 1, --balanceExposure 1 and the device JPEG path.
+//   * --orthoDefects 0|1 (new, default 0; needs --orthoMap 1, refused by name without it and with --gpus N above 1) with
+//     --defectThreshold t (default 0.002 m, 2^-20..1), --defectWindow W (default 0 pixels, 0..1024; 0: against the frame's own
+//     surface), --defectRefine 0|1 (default 0; needs W > 0), --defectMinSupport k (default 1), --defectMinPixels k (default 1)
+//     and --defectClasses hollow|bulge|both (default both), each refused by name without --orthoDefects 1: beside the other
+//     layers of ortho/ and of every ortho/facet_<row>/ (planar and unrolled) the run writes ortho_defect_dev.npy (<i4: the
+//     signed deviation in quanta of 2^-20 m), ortho_defect_class.npy (|u1: 0, 1 hollow, 2 bulge), ortho_defect_region.npy (<i4:
+//     0, or the region's id) and defects.json (the parameters, the eight counts, and per kept region its kind, pixels, area_m2,
+//     volume_m3, depth_m and its pixel, box, centroid, measured_fraction, open_pixels, first_pass_pixels and the raw row of 16
+//     integers; numbers as %.9g).  No counterpart in the reference.  Made on the GPU (pcp_ortho_defects; DESIGN.md "Surface
+//     defects on ortho maps").  Without the flag every file is byte for byte what it was.
 //   * --orthoMap 0|1 (new, default 0), --orthoGsd g (new, default 0.01, metres per pixel, 1e-4..1), --orthoFill R (new, default
 //     0, pixels, 0..1024) and --orthoFrame auto|ox,oy,oz,ux,uy,uz,vx,vy,vz (new, default auto): with 1 the run also writes one
 //     orthographic picture of the coloured cloud, <outputPath>ortho/ortho_rgb.npy (|u1, (H, W, 3)), ortho_depth.npy (<f4,
@@ -355,6 +365,9 @@ struct Options {
   bool ortho_texture_cylinders = false;  // --orthoTextureCylinders 1: the orthophoto of every cylindrical facet's unrolled map too
   bool ortho_texture_value_flag = false;  // one of the three value flags was given
   bool facets = false;                // --facets 1: the planar facets of the map (facets/facet_label.npy, facets.json)
+  bool ortho_defects = false;         // --orthoDefects 1: the surface defects of every orthographic map written (ortho_defect_*.npy, defects.json)
+  pcp_ortho_defect_params defect{0.002f, 0, 0, 1, 1, 3};  // --defectThreshold / Window / Refine / MinSupport / MinPixels / Classes
+  bool defect_value_flag = false;     // one of the --defect* values was given
   bool ortho_by_facet = false;        // --orthoFrame facets: one orthographic map per planar facet (ortho/facet_<row>/)
   pcp_facet_params facet{0.1f, 10.0f, 0.01f, 0.02f, 1000};  // --facetRadius / --facetAngle / --facetPlaneTol / --facetMaxCurvature / --facetMinPoints
   float facet_max_rms = 0.01f;        // --facetMaxRms m: a facet is planar up to this rms distance to its plane
@@ -551,6 +564,36 @@ static Options parse(int argc, char **argv) {
     }
     else if (a == "--crackFuse") o.crack_fuse = parse_bool(next());
     else if (a == "--orthoMap") o.ortho_map = parse_bool(next());
+    else if (a == "--orthoDefects") o.ortho_defects = parse_bool(next());
+    else if (a == "--defectThreshold") {
+      const std::string v = next();
+      try {
+        o.defect.threshold = std::stof(v);
+      } catch (const std::exception &) {
+        o.defect.threshold = -1.0f;
+      }
+      if (!(o.defect.threshold >= 0x1p-20f && o.defect.threshold <= 1.0f))
+        throw std::runtime_error("the argument ('" + v + "') for option '--defectThreshold' is invalid (2^-20 <= t <= 1 metres)");
+      o.defect_value_flag = true;
+    } else if (a == "--defectWindow" || a == "--defectMinSupport" || a == "--defectMinPixels") {
+      const std::string v = next();
+      char *end = nullptr;
+      const long k = std::strtol(v.c_str(), &end, 10);
+      const bool window = a == "--defectWindow";
+      if (end == v.c_str() || *end != '\0' || k < (window ? 0 : 1) || k > (window ? 1024 : 2147483647L))
+        throw std::runtime_error("the argument ('" + v + "') for option '" + a + "' is invalid (" + (window ? "0..1024 pixels" : "1 or more") + ")");
+      (window ? o.defect.window_px : a == "--defectMinSupport" ? o.defect.min_support : o.defect.min_pixels) = static_cast<int32_t>(k);
+      o.defect_value_flag = true;
+    } else if (a == "--defectRefine") {
+      o.defect.refine = parse_bool(next()) ? 1 : 0;
+      o.defect_value_flag = true;
+    } else if (a == "--defectClasses") {
+      const std::string v = next();
+      if (v != "hollow" && v != "bulge" && v != "both")
+        throw std::runtime_error("the argument ('" + v + "') for option '--defectClasses' is invalid (hollow, bulge or both)");
+      o.defect.classes = v == "hollow" ? 1 : v == "bulge" ? 2 : 3;
+      o.defect_value_flag = true;
+    }
     else if (a == "--orthoGsd") {
       const std::string v = next();
       try {
@@ -694,6 +737,16 @@ static Options parse(int argc, char **argv) {
     throw std::runtime_error("the options '--orthoTextureViews', '--orthoTextureInterp' and '--orthoTextureStep' need '--orthoTexture k' (k in 1..16)");
   if (o.ortho_texture && !o.ortho_map)
     throw std::runtime_error("the option '--orthoTexture' needs '--orthoMap 1' (the orthophoto is that map at a finer pitch)");
+  if (o.defect_value_flag && !o.ortho_defects)
+    throw std::runtime_error("the options '--defectThreshold', '--defectWindow', '--defectRefine', '--defectMinSupport', '--defectMinPixels' and "
+                             "'--defectClasses' need '--orthoDefects 1'");
+  if (o.ortho_defects && !o.ortho_map)
+    throw std::runtime_error("the option '--orthoDefects 1' needs '--orthoMap 1' (the defects are read from that map's depth layer)");
+  if (o.ortho_defects && o.gpus > 1)
+    throw std::runtime_error("the option '--orthoDefects 1' does not work with '--gpus N' above 1 (the orthographic map it reads is "
+                             "not built on index shards)");
+  if (o.ortho_defects && o.defect.refine && o.defect.window_px == 0)
+    throw std::runtime_error("the option '--defectRefine 1' needs '--defectWindow W' above 0 (it refines the window's reference)");
   if (o.ortho_texture && o.gpus > 1)
     throw std::runtime_error("the option '--orthoTexture' does not work with '--gpus N' above 1 (an index shard holds the depth maps "
                              "and the map of its own points only)");
@@ -820,6 +873,13 @@ static void usage(std::ostream &os) {
         "  --orthoGsd arg (=0.01)                With --orthoMap: metres per pixel (1e-4..1)\n"
         "  --orthoFill arg (=0)                  With --orthoMap: fill empty pixels from the nearest occupied one within R pixels\n"
         "  --orthoFrame arg (=auto)              With --orthoMap: auto (fitted plane), facets (one map per planar facet), or ox,oy,oz,ux,uy,uz,vx,vy,vz\n"
+        "  --orthoDefects arg (=0)               With --orthoMap: also the surface defects of every map written (hollows, bulges: area, depth, volume)\n"
+        "  --defectThreshold arg (=0.002)        With --orthoDefects: metres of deviation that make a defect (2^-20..1)\n"
+        "  --defectWindow arg (=0)               With --orthoDefects: half side W of the reference window in pixels (0: against the frame's own surface)\n"
+        "  --defectRefine arg (=0)               With --defectWindow: a second reference from the pixels the first pass left unclassed\n"
+        "  --defectMinSupport arg (=1)           With --defectWindow: surface pixels a window needs\n"
+        "  --defectMinPixels arg (=1)            With --orthoDefects: pixels a region needs to be kept\n"
+        "  --defectClasses arg (=both)           With --orthoDefects: hollow, bulge or both\n"
         "  --orthoTexture arg (=0)               With --orthoMap: also the orthophoto, k fine pixels per pixel, from the keyframe images (1..16)\n"
         "  --orthoTextureViews arg (=1)          With --orthoTexture: views that enter a colour (1 = sharpest, 5 = the reference's mean)\n"
         "  --orthoTextureInterp arg (=1)         With --orthoTexture: bilinear depth between map pixels\n"
@@ -1910,6 +1970,10 @@ class Processor {
     {
       Phase ph("ortho_finish_gpu_s");
       m = dev.orthoFetch(opt.ortho_fill, opt.fuse_masks);
+      if (!photo && !opt.ortho_defects) dev.orthoEnd();
+    }
+    if (opt.ortho_defects) {  // (on the finished map, before it ends)
+      writeOrthoDefects(dev, m.frame, stem);
       if (!photo) dev.orthoEnd();
     }
     if (photo) {
@@ -1950,6 +2014,54 @@ class Processor {
     std::cout << "Orthographic map saved to: " << stem << "ortho_*.npy and ortho_frame.json, " << m.frame.width << " x " << m.frame.height
               << " pixels, " << m.occupied << " occupied, " << m.filled << " filled" << std::endl;
     if (opt.crack_fuse) ortho_index = std::move(m.index);
+  }
+
+  // --orthoDefects 1: the surface defects of the finished map on `dev` (DESIGN.md "Surface defects on ortho maps"), as
+  // <stem>ortho_defect_dev.npy (quanta of 2^-20 m), ortho_defect_class.npy, ortho_defect_region.npy and defects.json: the
+  // parameters, the counts and one object per kept region with the metres derived from the library's integers
+  void writeOrthoDefects(Device &dev, const pcp_ortho_frame &frame, const std::string &stem) {
+    OrthoDefects d;
+    {
+      Phase ph("ortho_defects_gpu_s");
+      d = dev.orthoDefects(opt.defect);
+      dev.orthoDefectsFetch(d);
+    }
+    Phase ph_w("ortho_defects_write_s");
+    fs::create_directories(fs::path(stem));
+    const size_t h = static_cast<size_t>(frame.height), w = static_cast<size_t>(frame.width);
+    writeNpy(stem + "ortho_defect_dev.npy", "<i4", {h, w}, d.dev.data(), d.dev.size() * 4);
+    writeNpy(stem + "ortho_defect_class.npy", "|u1", {h, w}, d.cls.data(), d.cls.size());
+    writeNpy(stem + "ortho_defect_region.npy", "<i4", {h, w}, d.region.data(), d.region.size() * 4);
+    auto num = [](double v) {
+      char b[64];
+      std::snprintf(b, sizeof(b), "%.9g", v);
+      return std::string(b);
+    };
+    const double g = static_cast<double>(frame.gsd), q = 1.0 / 1048576.0;
+    std::ofstream f(stem + "defects.json");
+    f << "{\"threshold\": " << num(opt.defect.threshold) << ", \"window\": " << opt.defect.window_px << ", \"refine\": " << opt.defect.refine
+      << ", \"min_support\": " << opt.defect.min_support << ", \"min_pixels\": " << opt.defect.min_pixels << ", \"classes\": " << opt.defect.classes
+      << ", \"gsd\": " << num(g) << ", \"width\": " << frame.width << ", \"height\": " << frame.height << ", \"counts\": [";
+    for (int k = 0; k < 8; ++k) f << (k ? ", " : "") << d.counts[k];
+    f << "], \"regions\": [";
+    const size_t rows = d.rows.size() / 16;
+    for (size_t r = 0; r < rows; ++r) {
+      const int64_t *t = d.rows.data() + 16 * r;
+      const double px = static_cast<double>(t[1]);
+      f << (r ? ",\n " : "\n ") << "{\"id\": " << r + 1 << ", \"kind\": \"" << (t[0] == 1 ? "hollow" : "bulge") << "\", \"pixels\": " << t[1]
+        << ", \"area_m2\": " << num(px * g * g) << ", \"volume_m3\": " << num(static_cast<double>(t[3]) * q * g * g) << ", \"depth_m\": "
+        << num(static_cast<double>(t[4]) * q) << ", \"depth_px\": [" << t[5] % frame.width << ", " << t[5] / frame.width << "], \"box_px\": ["
+        << t[6] << ", " << t[8] << ", " << t[7] << ", " << t[9] << "], \"centroid_px\": [" << num(static_cast<double>(t[10]) / px) << ", "
+        << num(static_cast<double>(t[11]) / px) << "], \"measured_fraction\": " << num(static_cast<double>(t[2]) / px) << ", \"open_pixels\": "
+        << t[12] << ", \"first_pass_pixels\": " << t[14] << ", \"row\": [";
+      for (int k = 0; k < 16; ++k) f << (k ? ", " : "") << t[k];
+      f << "]}";
+    }
+    f << (rows ? "\n]}\n" : "]}\n");
+    f.close();
+    if (!f) throw std::runtime_error("Couldn't save the surface defects of the orthographic map.");
+    std::cout << "Surface defects saved to: " << stem << "ortho_defect_*.npy and defects.json, " << d.counts[0] << " regions kept, " << d.counts[1]
+              << " dropped, " << d.counts[2] << " hollow and " << d.counts[3] << " bulge pixels" << std::endl;
   }
 
   // --orthoTexture k: the orthophoto of the finished map on `dev`, as <out>ortho/ortho_photo_*.npy and ortho_photo.json.  One call

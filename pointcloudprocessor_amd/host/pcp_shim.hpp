@@ -35,6 +35,16 @@ struct VoxelCloud {
 };
 
 // An orthographic map (pcp_hip.h, "orthographic maps"): layers of frame.width x frame.height, row-major
+// surface defects of a finished orthographic map (DESIGN.md "Surface defects on ortho maps"): the eight counts, the layers
+// and 16 integers per kept region (pcp_hip.h)
+struct OrthoDefects {
+  int64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // kept, dropped, hollow px, bulge px, unsupported, refused, first pass, surface
+  std::vector<int32_t> dev;     // quanta of 2^-20 m
+  std::vector<uint8_t> cls;     // 0, 1 hollow, 2 bulge
+  std::vector<int32_t> region;  // 0: none, else 1..kept
+  std::vector<int64_t> rows;    // 16 per kept region
+};
+
 struct OrthoMap {
   pcp_ortho_frame frame{};
   int64_t contributors = 0, occupied = 0, filled = 0;
@@ -345,6 +355,24 @@ class Device {
     return s;
   }
   void orthoEnd() { check(pcp_ortho_end(ctx_)); }
+  // The surface defects of the live, finished map (pcp_ortho_defects): the counts; the layers and the table stay on the device
+  // for orthoDefectsFetch, which sizes them by the frame of the last orthoBegin that succeeded on this Device.
+  OrthoDefects orthoDefects(const pcp_ortho_defect_params &p) {
+    OrthoDefects d;
+    check(pcp_ortho_defects(ctx_, &p, d.counts));
+    return d;
+  }
+  void orthoDefectsFetch(OrthoDefects &d) {
+    const size_t px = static_cast<size_t>(ortho_frame_.width) * static_cast<size_t>(ortho_frame_.height);
+    d.dev.resize(px);
+    d.cls.resize(px);
+    d.region.resize(px);
+    check(pcp_ortho_defects_fetch(ctx_, d.dev.data(), d.cls.data(), d.region.data()));
+    int64_t rows = 0;
+    check(pcp_ortho_defects_table(ctx_, 0, int64_t(1) << 40, nullptr, &rows));
+    d.rows.assign(static_cast<size_t>(16 * rows), 0);
+    if (rows) check(pcp_ortho_defects_table(ctx_, 0, rows, d.rows.data(), &rows));
+  }
   // The orthophoto of the live, finished map (pcp_ortho_texture; DESIGN.md "Orthophotos"): p.scale fine pixels per ortho pixel
   // and axis over the rectangle p names (w == 0 && h == 0: the whole raster), coloured straight from the keyframe images under
   // the depth maps the context holds.  (Sized by the frame of the last orthoBegin that succeeded on this Device; parameters the

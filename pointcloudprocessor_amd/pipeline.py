@@ -181,7 +181,7 @@ class PointCloudColorizer:
             ctx.voxel_reduce_end()
 
     def ortho_map(self, frame="auto", gsd: float = 0.01, fill_radius: int = 0, crack_map: dict | None = None, xyz=None,
-                  viewer=None, texture: dict | None = None) -> dict:
+                  viewer=None, texture: dict | None = None, defects: dict | None = None) -> dict:
         """One orthographic picture of the colour result run() left on the device ("Orthographic maps"): dict(index
         (H, W) uint32 with 0xFFFFFFFF for an empty pixel, depth (H, W), rgb (H, W, 3), status (H, W) 0 empty / 1 direct /
         2 filled, source (H, W), frame (the dict that takes a pixel back to world coordinates), occupied, filled,
@@ -199,6 +199,10 @@ class PointCloudColorizer:
         `scale` fine pixels per pixel and axis, coloured straight from the keyframe images ("Orthophotos"): dict(rgb
         (H scale, W scale, 3), mask, status, view, count, surface, textured, unseen, skipped_pairs).  It runs after the
         finish and the fetch, before the map ends, on the depth maps run() left.
+        defects: dict(threshold[, window, refine, min_support, min_pixels, classes]) -- the result gains defect_dev (H, W) int32
+        in quanta of 2^-20 m, defect_class (H, W) uint8 (1 hollow, 2 bulge), defect_region (H, W) int32 and defects, a list of
+        dicts per kept region with area_m2, volume_m3, depth_m, centroid_px, measured_fraction, open_pixels and the raw row
+        ("Surface defects on ortho maps").  It runs on the finished map, before the map ends.
 
         An index shard sees only its own points, so world > 1 raises ValueError.  (The shards' key images would merge by an
         all-reduce(MIN); not built.)"""
@@ -207,6 +211,7 @@ class PointCloudColorizer:
                              "have to be merged across ranks (all-reduce MIN), which is not built: run it on one rank "
                              "holding the whole map")
         texture = ortho_texture_request("ortho_map", texture)
+        defects = ortho_defects_request("ortho_map", defects)
         ctx = self.engine.ctx
         if isinstance(frame, str):
             if frame != "auto":
@@ -222,6 +227,8 @@ class PointCloudColorizer:
             out = ctx.ortho_fetch(want_label=fuse_labels)
             if texture is not None:
                 out["photo"] = ctx.ortho_texture(**texture)
+            if defects is not None:
+                out.update(ortho_defect_layers(ctx, defects, capi.ortho_frame(frame).gsd))
         finally:
             ctx.ortho_end()
         out.update(frame=capi.ortho_frame(frame).as_dict(), contributors=contributors, occupied=occupied, filled=filled)
@@ -291,7 +298,8 @@ class PointCloudColorizer:
         return out
 
     def ortho_maps_by_facet(self, gsd: float, xyz=None, facets: dict | None = None, fill_radius: int = 0, viewer=None,
-                            texture: dict | None = None, cylinders: bool = False, texture_cylinders: bool = False) -> list:
+                            texture: dict | None = None, cylinders: bool = False, texture_cylinders: bool = False,
+                            defects: dict | None = None) -> list:
         """One orthographic map per planar facet of the colour result run() left on the device: for every planar row of
         `facets` (the dict facets() returned; None: the one its last call on this object left) a frame fitted on the host to
         the facet's points (capi.ortho_fit_frame_host with has = (label == id)) at `gsd` metres per pixel, seen from `viewer`
@@ -304,6 +312,8 @@ class PointCloudColorizer:
         map's dict carries kind (1 planar, 2 cylindrical).  texture is applied to the planar facets only, unless
         texture_cylinders is given too ("Orthophotos of unrolled maps"): then the cylindrical maps gain photo as
         well, by ctx.ortho_texture_cyl with the same request.  texture_cylinders needs both texture and cylinders.
+        defects: as ortho_map's, on every map drawn, planar and cylindrical (on a cylinder the depth layer is the radial
+        deviation from the fitted cylinder); every region's dict carries facet, the id of its facet.
 
         An index shard sees only its own points, so world > 1 raises ValueError."""
         import numpy as np
@@ -313,6 +323,7 @@ class PointCloudColorizer:
                              "would have to be merged across ranks (all-reduce MIN), which is not built: run it on one rank "
                              "holding the whole map")
         texture = ortho_texture_request("ortho_maps_by_facet", texture)
+        defects = ortho_defects_request("ortho_maps_by_facet", defects)
         if texture_cylinders and (texture is None or not cylinders):
             raise ValueError("ortho_maps_by_facet: texture_cylinders needs texture (the request) and cylinders=True (the maps it "
                              "textures)")
@@ -351,6 +362,8 @@ class PointCloudColorizer:
                     out["photo"] = ctx.ortho_texture(**texture)
                 elif texture_cylinders and kinds[row] == 2:
                     out["photo"] = ctx.ortho_texture_cyl(**texture)
+                if defects is not None:
+                    out.update(ortho_defect_layers(ctx, defects, frame["gsd"], facet=fid))
             finally:
                 ctx.ortho_end()
             out.update(frame=frame, contributors=contributors, occupied=occupied, filled=filled, facet=fid, row=int(row))
@@ -589,6 +602,40 @@ def ortho_texture_request(who: str, texture: dict | None) -> dict | None:
         raise ValueError(f"{who}: texture is dict(scale[, views, interpolate, max_step]), got {sorted(texture)}")
     return dict(scale=int(texture["scale"]), views=int(texture.get("views", 1)), interpolate=bool(texture.get("interpolate", True)),
                 max_step=float(texture.get("max_step", 0.05)))
+
+
+def ortho_defects_request(who: str, defects: dict | None) -> dict | None:
+    """the keyword arguments of capi.Context.ortho_defects from a defects=dict(threshold[, window, refine, min_support,
+    min_pixels, classes])"""
+    if defects is None:
+        return None
+    known = ("threshold", "window", "refine", "min_support", "min_pixels", "classes")
+    extra = sorted(set(defects) - set(known))
+    if extra or "threshold" not in defects:
+        raise ValueError(f"{who}: defects is dict(threshold[, window, refine, min_support, min_pixels, classes]); got {sorted(defects)}")
+    return {k: defects[k] for k in known if k in defects}
+
+
+def ortho_defect_layers(ctx, request: dict, gsd: float, facet: int | None = None) -> dict:
+    """defect_dev / defect_class / defect_region and the list `defects` of the live, finished map of `ctx` (capi.Context
+    .ortho_defects, _fetch, _table): the library's integers, and per region the metres derived from them on the host"""
+    counts = ctx.ortho_defects(**request)
+    layers = ctx.ortho_defects_fetch()
+    rows = ctx.ortho_defects_table()
+    width = layers["dev"].shape[1]
+    quantum, g2 = 2.0 ** -20, float(gsd) * float(gsd)
+    found = []
+    for r in rows:
+        d = dict(zip(capi.DEFECT_ROW, (int(v) for v in r)))
+        item = dict(kind="hollow" if d["class"] == capi.DEFECT_HOLLOW else "bulge", pixels=d["pixels"], area_m2=d["pixels"] * g2,
+                    volume_m3=d["sum_dev"] * quantum * g2, depth_m=d["max_dev"] * quantum,
+                    depth_px=(d["max_pixel"] % width, d["max_pixel"] // width), box_px=(d["col_min"], d["row_min"], d["col_max"], d["row_max"]),
+                    centroid_px=(d["sum_col"] / d["pixels"], d["sum_row"] / d["pixels"]), measured_fraction=d["measured"] / d["pixels"],
+                    open_pixels=d["open"], first_pass_pixels=d["first_pass"], row=[int(v) for v in r])
+        if facet is not None:
+            item["facet"] = int(facet)
+        found.append(item)
+    return dict(defect_dev=layers["dev"], defect_class=layers["cls"], defect_region=layers["region"], defects=found, defect_counts=counts)
 
 
 def ortho_crack_layers(index, map_width, map_crack) -> dict:
