@@ -88,6 +88,9 @@ extern "C" {
                                 pcp_cyl_sincos_host (orthophotos of unrolled maps; nothing runs unless called);
                                 entry points added, no layout changed: pcp_crack_directions / _fetch / _host, pcp_crack_axis_host
                                 (crack directions on the map; nothing runs unless called);
+                                entry points added, no layout changed: pcp_crack_branches / _fetch / _host,
+                                pcp_crack_branch_edges_fetch / _cracks_fetch, pcp_crack_branch_lengths_host (crack branches on the
+                                map; nothing runs unless called);
                                 entry points added, no layout changed: pcp_ortho_defects / _fetch / _table / _host
                                 (surface defects on ortho maps; nothing runs unless called) */
 
@@ -1238,6 +1241,57 @@ int pcp_crack_directions_host(int64_t n, const float *xyz, const uint32_t *views
                               float *out_anisotropy, int32_t *out_links, int64_t *out_moments, int32_t *out_id, int64_t *out_rows20,
                               int64_t *out_cracks);
 int pcp_crack_axis_host(const int64_t row20[20], double out5[5]);
+
+/* ---- crack branches on the map (the reference's scripts never take a skeleton apart: an inspector's record goes arm by arm) -- */
+/* The diagram of pcp_crack_skeleton cut at its junctions into branches, short spurs pruned, and one exact integer record per
+ * branch ("Crack branches on the map", CB1-CB9).  Opt-in: nothing runs unless one of these is called,
+ * PCP_ABI_VERSION is unchanged and a caller detects support by the symbols.  Kernels are timed under PCP_K_MISC.  Whole-map
+ * contexts only.
+ *
+ * pcp_crack_branches (CB1-CB4, CB9) runs pcp_crack_skeleton's stage for the parameters and step (same checks and returns; it
+ * leaves the component, length and skeleton tables of these parameters behind, keeps the table of pcp_crack_directions and
+ * invalidates what pcp_crack_skeleton invalidates).  prune (metres): prune_q = trunc((double)prune * 2^20); 0 <= prune <= 1024
+ * or PCP_ERR_INVALID (a NaN included); 0 prunes nothing.  In a set K of nodes with the edges between them a node of degree >= 3
+ * is a junction; the branches are the connected components of the other nodes under the edges between two of them (paths or
+ * cycles), a branch's attachments are its edges to junctions (0, 1 or 2), an edge between two junctions is a bridge.  The whole
+ * diagram is decomposed once; a branch with exactly one attachment and nodes * step_q < prune_q that holds neither node[end_a]
+ * nor node[end_b] of its crack (pcp_crack_lengths_fetch) is a spur.  One round: the final branches are the decomposition of the
+ * nodes outside spurs, whatever their size; a junction left with two kept edges is an ordinary node.  A branch's id is the
+ * lowest input index among its points.  out_branch (nullable, n, host) = that id, -1 for a point that is no crack point, -2
+ * for a point of a kept junction, -3 for a point of a pruned node.  *out_branches / *out_pruned_branches (nullable).  A crack
+ * point with 2^22 links or more inside its branch: PCP_ERR_RANGE.
+ * pcp_crack_branches_fetch (CB5, CB6): rows first .. of the branch table, ascending by id: out_id; out_rows15 15 int64 per row
+ * -- crack_row, nodes, edges_inside, attachments, junction_u, junction_v (the node rows of the junctions attached to, the lower
+ * first; junction_v = -1 with one attachment, both -1 with none), points, sum_w, min_w, max_w (the fused w of the members),
+ * pos_min, pos_max (pcp_crack_lengths' pos), sum_qx, sum_qy, sum_qz (as pcp_crack_skeleton_nodes_fetch); out_moments20 20 int64
+ * per row -- the ten moment words of pcp_crack_directions_fetch as (lo, hi), summed over the ordered links whose two points
+ * lie in this branch: pcp_crack_axis_host on such a row gives the branch's axis and anisotropy.  The S1 sums are exactly zero.
+ * pcp_crack_branch_edges_fetch (CB7): one int32 per row of pcp_crack_skeleton_edges_fetch: the branch row of the edge (an edge
+ * to a junction belongs to the branch of its other end), -1 for a bridge, -2 for an edge with a pruned end.
+ * pcp_crack_branch_cracks_fetch (CB7): the rows and order of pcp_crack_components_fetch, out_rows7 7 int64 per row -- branches,
+ * bridges, junctions_kept, ends_kept (kept nodes of degree 1 among the kept edges), pruned_branches, pruned_nodes,
+ * pruned_points.  All outputs nullable; the tables live until the next pcp_crack_lengths, pcp_crack_skeleton, _add, _end or
+ * drop of the accumulation; pcp_crack_components and pcp_crack_directions keep them.
+ * pcp_crack_branches_host: host only, no context, no GPU: the same results for n <= 65536 points (xyz interleaved) by brute
+ * force over the pairs; sum_q (nullable: every w = 0).  out_branch n, out_id n, out_rows15 15 n, out_moments20 20 n, out_rows7
+ * 7 n of capacity; out_edge_branch takes at most edge_capacity rows, *out_edges is the whole count.
+ * pcp_crack_branch_lengths_host (CB8): host only, fp64, the one expression every host layer uses: from the node and edge tables
+ * of pcp_crack_skeleton and the edge_branch of pcp_crack_branch_edges_fetch, out_length_m[b] = the sum, in edge-row order and
+ * one addition after the other, of the lengths of the edges with edge_branch == b (an edge's length is the distance of its two
+ * nodes' centroids (sum_q / points) * 2^-20), out_kept_length_m[c] = the same over crack c's edges with edge_branch >= -1.  A
+ * row that names a node, a branch or a crack that is not there, or a node without a point: PCP_ERR_INVALID. */
+int pcp_crack_branches(pcp_context *ctx, const pcp_crack_link_params *p, float step, float prune, int32_t *out_branch, int64_t *out_branches,
+                       int64_t *out_pruned_branches);
+int pcp_crack_branches_fetch(pcp_context *ctx, int64_t first, int64_t max_rows, int32_t *out_id, int64_t *out_rows15, int64_t *out_moments20,
+                             int64_t *out_rows);
+int pcp_crack_branch_edges_fetch(pcp_context *ctx, int64_t first, int64_t max_rows, int32_t *out_edge_branch, int64_t *out_rows);
+int pcp_crack_branch_cracks_fetch(pcp_context *ctx, int64_t first, int64_t max_rows, int64_t *out_rows7, int64_t *out_rows);
+int pcp_crack_branch_lengths_host(int64_t nodes, const int64_t *rows10, int64_t edges, const int64_t *rows3, const int32_t *edge_branch,
+                                  int64_t branches, int64_t cracks, double *out_length_m, double *out_kept_length_m);
+int pcp_crack_branches_host(int64_t n, const float *xyz, const uint32_t *views, int32_t min_views, float radius, float step, float prune,
+                            const uint64_t *sum_q, int32_t *out_branch, int32_t *out_id, int64_t *out_rows15, int64_t *out_moments20,
+                            int64_t edge_capacity, int32_t *out_edge_branch, int64_t *out_rows7, int64_t *out_branches, int64_t *out_edges,
+                            int64_t *out_cracks);
 
 /* ---- planar facets of the map (the reference's scripts stop at per-keyframe pictures: no step partitions the map) ---------- */
 /* The faces of the structure as connected components of the map points under a symmetric integer link, one row of exact

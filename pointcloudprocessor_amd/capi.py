@@ -970,6 +970,76 @@ def crack_skeleton_host(xyz, views, min_views: int = 1, radius: float = 0.02, st
     return out
 
 
+CB_ROW = ("crack_row", "nodes", "edges_inside", "attachments", "junction_u", "junction_v", "points", "sum_w", "min_w", "max_w",
+          "pos_min", "pos_max", "sum_qx", "sum_qy", "sum_qz")  # CB5: the columns of rows
+CB_CRACK = ("branches", "bridges", "junctions_kept", "ends_kept", "pruned_branches", "pruned_nodes", "pruned_points")  # CB7
+CB_NO_POINT, CB_JUNCTION, CB_PRUNED = -1, -2, -3  # CB4: branch[] of a point outside every branch
+CB_BRIDGE, CB_EDGE_PRUNED = -1, -2  # CB7: edge_branch[] of an edge outside every branch
+
+
+def crack_branches_metres(rows, moments, edge_branch, nodes, edges, cracks) -> dict:
+    """CB8 and the other host arithmetic on the integers of the branch tables: length_m (B,) = the sum, in edge-row order and
+    one addition after the other, of CS7's edge lengths over the edges of the branch; kept_length_m (C,) = the same over a
+    crack's edges that have no pruned end; centroid (B, 3) = (sum_q / points) * 2^-20; mean_width (B,) = (sum_w / points) * 2^-20
+    metres; axis (B, 3), anisotropy (B,) and link_count (B,) by crack_axis_host on the moments."""
+    rows = np.asarray(rows, np.int64).reshape(-1, 15)
+    nodes, edges = np.asarray(nodes, np.int64).reshape(-1, 10), np.asarray(edges, np.int64).reshape(-1, 3)
+    edge_branch = np.asarray(edge_branch, np.int32).reshape(-1)
+    nodes, edges, edge_branch = np.ascontiguousarray(nodes), np.ascontiguousarray(edges), np.ascontiguousarray(edge_branch)
+    length = np.zeros(len(rows), np.float64)
+    kept = np.zeros(len(np.asarray(cracks).reshape(-1, 7)), np.float64)
+    L = load()
+    rc = L.pcp_crack_branch_lengths_host(C.c_int64(len(nodes)), _ptr(nodes), C.c_int64(len(edges)), _ptr(edges), _ptr(edge_branch),
+                                         C.c_int64(len(length)), C.c_int64(len(kept)), _ptr(length), _ptr(kept))  # CB8, the one expression
+    if rc != PCP_OK:
+        raise PcpError(rc, L.pcp_last_error(None).decode())
+    points = rows[:, 6:7].astype(np.float64)
+    axes = crack_axis_host(moments)
+    return dict(length_m=length, kept_length_m=kept, centroid=(rows[:, 12:15].astype(np.float64) / points) * 2.0 ** -20,
+                mean_width=(rows[:, 7].astype(np.float64) / points[:, 0]) * 2.0 ** -20, axis=axes["axis"],
+                anisotropy=axes["axis_anisotropy"], link_count=axes["link_count"])
+
+
+def crack_branches_host(xyz, views, min_views: int = 1, radius: float = 0.02, step=None, prune: float = 0.0, sum_q=None) -> dict:
+    """What Context.crack_branches returns, computed on the CPU by brute force over the pairs (pcp_crack_branches_host and
+    pcp_crack_skeleton_host: no context, no GPU): xyz (n, 3) float32, views (n,) uint32, sum_q (n,) uint64 or None (every
+    fused width 0), n <= 65536."""
+    L = load()
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    views = np.ascontiguousarray(views, np.uint32)
+    n = xyz.shape[0]
+    if views.shape != (n,):
+        raise ValueError(f"crack_branches_host: {n} views expected, got shape {views.shape}")
+    if sum_q is not None:
+        sum_q = np.ascontiguousarray(sum_q, np.uint64)
+        if sum_q.shape != (n,):
+            raise ValueError(f"crack_branches_host: {n} sums expected, got shape {sum_q.shape}")
+    if step is None:
+        step = crack_skeleton_step(radius)
+    branch = np.empty(n, np.int32)
+    ids = np.empty(n, np.int32)
+    rows = np.empty((n, 15), np.int64)
+    moments = np.empty((n, 20), np.int64)
+    cracks = np.empty((n, 7), np.int64)
+    capacity = 4 * n + 16
+    while True:
+        edge_branch = np.empty(capacity, np.int32)
+        kb, ke, kc = C.c_int64(), C.c_int64(), C.c_int64()
+        rc = L.pcp_crack_branches_host(C.c_int64(n), _ptr(xyz), _ptr(views), C.c_int32(min_views), C.c_float(radius), C.c_float(step),
+                                       C.c_float(prune), _ptr(sum_q), _ptr(branch), _ptr(ids), _ptr(rows), _ptr(moments), C.c_int64(capacity),
+                                       _ptr(edge_branch), _ptr(cracks), C.byref(kb), C.byref(ke), C.byref(kc))
+        if rc != PCP_OK:
+            raise PcpError(rc, L.pcp_last_error(None).decode())
+        if ke.value <= capacity:
+            break
+        capacity = ke.value  # (more edges than four per point: once more with room for all)
+    out = dict(branch=branch, ids=ids[:kb.value].copy(), rows=rows[:kb.value].copy(), moments=moments[:kb.value].copy(),
+               edge_branch=edge_branch[:ke.value].copy(), cracks=cracks[:kc.value].copy())
+    sk = crack_skeleton_host(xyz, views, min_views, radius, step, sum_q)
+    out.update(crack_branches_metres(out["rows"], out["moments"], out["edge_branch"], sk["nodes"], sk["edges"], out["cracks"]))
+    return out
+
+
 def default_camera() -> Camera:
     cam = Camera()
     load().pcp_default_camera(C.byref(cam))
@@ -1827,6 +1897,45 @@ class Context:
         assert got.value == len(cracks), (got.value, len(cracks))
         out = dict(node=node, ids=ids, nodes=nodes, edges=edges, cracks=cracks)
         out.update(crack_skeleton_metres(nodes, edges, cracks))
+        return out
+
+    # -- crack branches on the map ("Crack branches on the map") ----------------
+    def crack_branches(self, min_views: int = 1, radius: float = 0.02, step=None, prune: float = 0.0) -> dict:
+        """Every crack of the map arm by arm, from the live accumulation (pcp_crack_branches and its fetches): the diagram of
+        crack_skeleton cut at its junctions, branches with one attachment and fewer than prune / step nodes pruned (metres; 0
+        prunes nothing).  branch (n,) int32, the id of a crack point's branch (the lowest input index among its points), -1 for
+        a point that is no crack point, -2 on a kept junction, -3 on a pruned node; ids (B,) int32 ascending; rows (B, 15) int64,
+        the columns CB_ROW; moments (B, 20) int64, the rows of crack_directions restricted to the links inside a branch;
+        edge_branch (E,) int32 per edge of crack_skeleton (-1 a bridge, -2 an edge with a pruned end); cracks (C, 7) int64, the
+        columns CB_CRACK, the rows of crack_components; plus what crack_branches_metres makes of them: length_m,
+        kept_length_m, centroid, mean_width, axis, anisotropy, link_count.  It leaves the tables crack_skeleton leaves."""
+        prm = CrackLinkParams(min_views, radius)
+        if step is None:
+            step = crack_skeleton_step(radius)
+        branch = np.empty(self.n, np.int32)
+        kb, kp, got = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(self.lib.pcp_crack_branches(self.h, C.byref(prm), C.c_float(step), C.c_float(prune), _ptr(branch), C.byref(kb), C.byref(kp)))
+        ids = np.empty(kb.value, np.int32)
+        rows = np.empty((kb.value, 15), np.int64)
+        moments = np.empty((kb.value, 20), np.int64)
+        self._check(self.lib.pcp_crack_branches_fetch(self.h, C.c_int64(0), C.c_int64(kb.value), _ptr(ids), _ptr(rows), _ptr(moments), C.byref(got)))
+        assert got.value == kb.value, (got.value, kb.value)
+        self._check(self.lib.pcp_crack_branch_edges_fetch(self.h, C.c_int64(0), C.c_int64(2 ** 62), None, C.byref(got)))
+        edge_branch = np.empty(got.value, np.int32)
+        self._check(self.lib.pcp_crack_branch_edges_fetch(self.h, C.c_int64(0), C.c_int64(len(edge_branch)), _ptr(edge_branch), C.byref(got)))
+        assert got.value == len(edge_branch), (got.value, len(edge_branch))
+        self._check(self.lib.pcp_crack_branch_cracks_fetch(self.h, C.c_int64(0), C.c_int64(2 ** 62), None, C.byref(got)))
+        cracks = np.empty((got.value, 7), np.int64)
+        self._check(self.lib.pcp_crack_branch_cracks_fetch(self.h, C.c_int64(0), C.c_int64(len(cracks)), _ptr(cracks), C.byref(got)))
+        assert got.value == len(cracks), (got.value, len(cracks))
+        edges = np.empty((len(edge_branch), 3), np.int64)
+        self._check(self.lib.pcp_crack_skeleton_nodes_fetch(self.h, C.c_int64(0), C.c_int64(2 ** 62), None, None, C.byref(got)))
+        nodes = np.empty((got.value, 10), np.int64)
+        self._check(self.lib.pcp_crack_skeleton_nodes_fetch(self.h, C.c_int64(0), C.c_int64(len(nodes)), None, _ptr(nodes), C.byref(got)))
+        self._check(self.lib.pcp_crack_skeleton_edges_fetch(self.h, C.c_int64(0), C.c_int64(len(edges)), _ptr(edges), C.byref(got)))
+        assert got.value == len(edges), (got.value, len(edges))
+        out = dict(branch=branch, ids=ids, rows=rows, moments=moments, edge_branch=edge_branch, cracks=cracks, pruned_branches=kp.value)
+        out.update(crack_branches_metres(rows, moments, edge_branch, nodes, edges, cracks))
         return out
 
     def colour_smooth_local(self, radius: float) -> int:

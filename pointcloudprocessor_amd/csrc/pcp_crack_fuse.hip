@@ -358,7 +358,7 @@ int crack_components_run(pcp_context *ctx, const pcp_crack_link_params &p, CcScr
 
 // the stages up to `upto` and the copies of the per-point outputs, queued
 static int crack_map_stages(pcp_context *ctx, const pcp_crack_link_params &p, CrackMap::Level upto, uint64_t step_q, const CrackOut &out,
-                            CcScratch &cc, ClScratch &cl, CsScratch &cs, CrackCounts *c) {
+                            CcScratch &cc, ClScratch &cl, CsScratch &cs, CbScratch &cb, uint64_t prune_q, CrackCounts *c) {
   const size_t sn = static_cast<size_t>(ctx->n);
   if (out.pos) {  // CL5: 2^64 - 1 for a point that is no crack point
     PCP_HIP_TRY(ctx, cl.pos.ensure(sn + 4));
@@ -368,18 +368,24 @@ static int crack_map_stages(pcp_context *ctx, const pcp_crack_link_params &p, Cr
     PCP_HIP_TRY(ctx, cs.node.ensure(sn + 4));
     PCP_HIP_TRY(ctx, hipMemsetAsync(cs.node.p, 0xff, sn * 4, ctx->stream));
   }
+  if (out.branch) {  // CB4: -1
+    PCP_HIP_TRY(ctx, cb.branch.ensure(sn + 4));
+    PCP_HIP_TRY(ctx, hipMemsetAsync(cb.branch.p, 0xff, sn * 4, ctx->stream));
+  }
   int rc = crack_components_run(ctx, p, cc, c);
   if (rc == PCP_OK && upto >= CrackMap::kLengths && c->points > 0) rc = crack_lengths_run(ctx, p, cc, cl, c);
   if (rc == PCP_OK && upto >= CrackMap::kSkeleton && c->points > 0) rc = crack_skeleton_run(ctx, p, step_q, cc, cl, cs, c);
+  if (rc == PCP_OK && upto == CrackMap::kBranches && c->points > 0) rc = crack_branches_run(ctx, p, step_q, prune_q, cc, cl, cs, cb, c);
   if (rc != PCP_OK) return rc;
   if (out.label) PCP_HIP_TRY(ctx, hipMemcpyAsync(out.label, cc.label.p, sn * 4, hipMemcpyDeviceToHost, ctx->stream));
   if (out.pos) PCP_HIP_TRY(ctx, hipMemcpyAsync(out.pos, cl.pos.p, sn * 8, hipMemcpyDeviceToHost, ctx->stream));
   if (out.node) PCP_HIP_TRY(ctx, hipMemcpyAsync(out.node, cs.node.p, sn * 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (out.branch) PCP_HIP_TRY(ctx, hipMemcpyAsync(out.branch, cb.branch.p, sn * 4, hipMemcpyDeviceToHost, ctx->stream));
   return PCP_OK;
 }
 
 int crack_map_run(pcp_context *ctx, const pcp_crack_link_params &p, CrackMap::Level upto, uint64_t step_q, const CrackOut &out,
-                  CrackCounts *c) {
+                  CrackCounts *c, uint64_t prune_q) {
   CrackMap &cm = *ctx->crack;
   *c = CrackCounts();
   cm.replacing(upto);
@@ -391,7 +397,8 @@ int crack_map_run(pcp_context *ctx, const pcp_crack_link_params &p, CrackMap::Le
   CcScratch cc;
   ClScratch cl;
   CsScratch cs;
-  const int rc = crack_map_stages(ctx, p, upto, step_q, out, cc, cl, cs, c);
+  CbScratch cb;
+  const int rc = crack_map_stages(ctx, p, upto, step_q, out, cc, cl, cs, cb, prune_q, c);
   const hipError_t e = hipStreamSynchronize(ctx->stream);  // (also: the scratch is released on return)
   drop_large_grid_bitmap(ctx);
   if (rc != PCP_OK) return rc;
@@ -402,7 +409,7 @@ int crack_map_run(pcp_context *ctx, const pcp_crack_link_params &p, CrackMap::Le
 
 int crack_window(pcp_context *ctx, const char *who, CrackMap::Level l, int64_t first, int64_t max_rows, int64_t have, int64_t *rows) {
   static const char *const maker[] = {"pcp_crack_fuse_begin", "pcp_crack_components", "pcp_crack_lengths", "pcp_crack_skeleton",
-                                      "pcp_crack_directions"};
+                                      "pcp_crack_directions", "pcp_crack_branches"};
   if (first < 0 || max_rows < 0) return set_error(ctx, PCP_ERR_INVALID, "%s: negative first or max_rows", who);
   if (!ctx->crack->readable(l)) return set_error(ctx, PCP_ERR_STATE, "%s: no table (%s on the accumulation as it is)", who, maker[l]);
   *rows = std::max<int64_t>(0, std::min(max_rows, have - first));

@@ -8,29 +8,30 @@
 namespace pcp {
 
 // ---- the chain's results in the context (ctx->crack) ----------------------------------------------------------------------
-// Four levels, each made from the one below: the fusion (pcp_crack_fuse_begin .. _end), and the tables of the last
-// pcp_crack_components, pcp_crack_lengths and pcp_crack_skeleton; and one side level made from the components, the directions
-// of the last pcp_crack_directions (CD6).  A level is live or not; only the member functions below change that, and every fetch
-// asks readable().
+// Five levels, each made from the one below: the fusion (pcp_crack_fuse_begin .. _end), and the tables of the last
+// pcp_crack_components, pcp_crack_lengths, pcp_crack_skeleton and pcp_crack_branches (CB9); and one side level made from the
+// components, the directions of the last pcp_crack_directions (CD6).  A level is live or not; only the member functions below
+// change that, and every fetch asks readable().
 //
-//   event                                   fusion      components   lengths + paths   skeleton    directions
-//   pcp_crack_fuse_begin                    new, empty  dropped      dropped           dropped     dropped
-//   pcp_crack_fuse_add (success)            updated     invalid      invalid           invalid     invalid
-//   pcp_crack_components                    -           replaced     KEPT              KEPT        KEPT
-//   pcp_crack_lengths                       -           replaced     replaced          invalid     KEPT
-//   pcp_crack_skeleton                      -           replaced     replaced          replaced    KEPT
-//   pcp_crack_directions                    -           replaced     KEPT              KEPT        replaced
+//   event                                   fusion      components   lengths + paths   skeleton    branches    directions
+//   pcp_crack_fuse_begin                    new, empty  dropped      dropped           dropped     dropped     dropped
+//   pcp_crack_fuse_add (success)            updated     invalid      invalid           invalid     invalid     invalid
+//   pcp_crack_components                    -           replaced     KEPT              KEPT        KEPT        KEPT
+//   pcp_crack_lengths                       -           replaced     replaced          invalid     invalid     KEPT
+//   pcp_crack_skeleton                      -           replaced     replaced          replaced    invalid     KEPT
+//   pcp_crack_branches                      -           replaced     replaced          replaced    replaced    KEPT
+//   pcp_crack_directions                    -           replaced     KEPT              KEPT        KEPT        replaced
 //   pcp_crack_fuse_end, the cloud uploads,
-//   pcp_set_camera, pcp_set_frames          dropped     dropped      dropped           dropped     dropped
+//   pcp_set_camera, pcp_set_frames          dropped     dropped      dropped           dropped     dropped     dropped
 //
 // A call that fails after its parameter checks leaves the levels it was about to replace invalid; on a context with n == 0 it
-// succeeds and leaves them live with zero rows.  So the lengths, the skeleton and the directions outlive a pcp_crack_components
-// with other parameters: they describe the accumulation, not the components table.
+// succeeds and leaves them live with zero rows.  So the lengths, the skeleton, the branches and the directions outlive a
+// pcp_crack_components with other parameters: they describe the accumulation, not the components table.
 struct CrackCounts {
-  int64_t points = 0, cracks = 0, entries = 0, nodes = 0, edges = 0;
+  int64_t points = 0, cracks = 0, entries = 0, nodes = 0, edges = 0, branches = 0, pruned_branches = 0;
 };
 struct CrackMap {
-  enum Level { kFusion = 0, kComponents, kLengths, kSkeleton, kDirections };
+  enum Level { kFusion = 0, kComponents, kLengths, kSkeleton, kDirections, kBranches };  // (kBranches last: it is made from kSkeleton)
   // fusion: SoA planes of n in input order -- seen | views | centres | min_q | max_q | best_q and sum_q | best_key -- and the
   // keyframes added so far
   DevBuf<uint32_t> cf_u32;
@@ -55,20 +56,29 @@ struct CrackMap {
   int64_t cd_rows = 0;
   DevBuf<int32_t> cd_ids;
   DevBuf<unsigned long long> cd_table;
+  // branches: the ids, cb::kRowWords integers and cd::kRowWords moment words per branch; on the host the branch of every
+  // edge of cs_edges and cb::kCrackWords integers per crack
+  int64_t cb_rows = 0;
+  DevBuf<int32_t> cb_ids;
+  DevBuf<unsigned long long> cb_table, cb_moments;
+  std::vector<int32_t> cb_edge_branch;
+  std::vector<int64_t> cb_cracks;
 
   bool readable(Level l) const {
-    return cf_live && (l == kFusion || (l == kComponents ? cc_live : l == kLengths ? cl_live : l == kSkeleton ? cs_live : cd_live));
+    return cf_live && (l == kFusion || (l == kComponents ? cc_live : l == kLengths ? cl_live : l == kSkeleton ? cs_live : l == kBranches ? cb_live : cd_live));
   }
   void begin() { set_live(kFusion, kFusion, true); }                  // (after release(): an empty accumulation)
-  void changed() { set_live(kComponents, kSkeleton, false), cd_live = false; }  // a keyframe was added: every table describes the state before it
-  void replacing(Level upto) {  // a call is about to make the tables up to `upto`; new lengths also end the skeleton made from the old ones
+  void changed() { set_live(kComponents, kSkeleton, false), cd_live = cb_live = false; }  // a keyframe was added: every table describes the state before it
+  void replacing(Level upto) {  // a call is about to make the tables up to `upto`; new lengths also end the skeleton and the branches made from the old ones
     set_live(kComponents, upto == kComponents ? kComponents : kSkeleton, false);
     hold_counts(upto, CrackCounts());
-    if (upto == kSkeleton) cs_edges.clear();
+    if (upto == kSkeleton || upto == kBranches) cs_edges.clear();
+    if (upto != kComponents) cb_live = false, cb_rows = 0, cb_edge_branch.clear(), cb_cracks.clear();
   }
   void hold(Level upto, const CrackCounts &c) {  // ... and has made them
     hold_counts(upto, c);
     set_live(kComponents, upto, true);
+    if (upto == kBranches) cb_rows = c.branches, cb_live = true;
   }
   void replacing_directions() { cd_live = false, cd_rows = 0; }  // pcp_crack_directions, beside replacing(kComponents) ...
   void hold_directions(int64_t rows) { cd_rows = rows, cd_live = true; }  // ... and beside hold(kComponents, ..)
@@ -76,6 +86,10 @@ struct CrackMap {
     set_live(kFusion, kSkeleton, false);
     replacing_directions();
     cd_ids.release(), cd_table.release();
+    cb_live = false, cb_rows = 0;
+    cb_ids.release(), cb_table.release(), cb_moments.release();
+    std::vector<int32_t>().swap(cb_edge_branch);
+    std::vector<int64_t>().swap(cb_cracks);
     hold_counts(kSkeleton, CrackCounts());
     cf_added.clear();
     cf_u32.release(), cf_u64.release();
@@ -86,7 +100,7 @@ struct CrackMap {
   }
 
  private:
-  bool cf_live{false}, cc_live{false}, cl_live{false}, cs_live{false}, cd_live{false};
+  bool cf_live{false}, cc_live{false}, cl_live{false}, cs_live{false}, cd_live{false}, cb_live{false};
   void set_live(Level a, Level b, bool v) {
     if (a <= kFusion && kFusion <= b) cf_live = v;
     if (a <= kComponents && kComponents <= b) cc_live = v;
@@ -135,6 +149,14 @@ struct CdScratch {
   DevBuf<long long> moments;
   DevBuf<uint32_t> words;
 };
+// branch stage: gather = (crack_row, points) per node and then the node rows of node[end_a], node[end_b] per crack, for the
+// host's graph part; node_branch = per node row the branch row, -2 or -3, from it; brow = the same per place; branch (nullable)
+// = CB4 (n, input order); words[0]: a point with gn::kMaxNeighbours links or more, words[1]: something that cannot be
+struct CbScratch {
+  DevBuf<long long> gather;
+  DevBuf<int32_t> node_branch, brow, branch;
+  DevBuf<uint32_t> words;
+};
 
 // ---- the stages (ctx->n > 0, checked parameters, a live fusion); queued on ctx->stream and synchronised only as far as
 // their counts need.  Each runs on what the one before left in the scratch and in ctx->g_*. -----------------------------------
@@ -145,15 +167,19 @@ int crack_lengths_run(pcp_context *ctx, const pcp_crack_link_params &p, const Cc
 // CS1-CS8 on c->points > 0 crack points, after CS4's check of the box: the tables in cs_*, c->nodes, c->edges
 int crack_skeleton_run(pcp_context *ctx, const pcp_crack_link_params &p, uint64_t step_q, const CcScratch &cc, const ClScratch &cl,
                        CsScratch &cs, CrackCounts *c);
-// The body of pcp_crack_components, pcp_crack_lengths and pcp_crack_skeleton after their own parameter checks: the stages up
-// to `upto`, the per-point outputs asked for (host arrays of n, nullable), and the state rules above.
+// CB1-CB9 on c->points > 0 crack points, after the skeleton stage: the tables in cb_*, c->branches, c->pruned_branches
+int crack_branches_run(pcp_context *ctx, const pcp_crack_link_params &p, uint64_t step_q, uint64_t prune_q, const CcScratch &cc,
+                       const ClScratch &cl, const CsScratch &cs, CbScratch &cb, CrackCounts *c);
+// The body of pcp_crack_components, pcp_crack_lengths, pcp_crack_skeleton and pcp_crack_branches after their own parameter
+// checks: the stages up to `upto`, the per-point outputs asked for (host arrays of n, nullable), and the state rules above.
 struct CrackOut {
   int32_t *label = nullptr;
   uint64_t *pos = nullptr;
   int32_t *node = nullptr;
+  int32_t *branch = nullptr;
 };
 int crack_map_run(pcp_context *ctx, const pcp_crack_link_params &p, CrackMap::Level upto, uint64_t step_q, const CrackOut &out,
-                  CrackCounts *c);
+                  CrackCounts *c, uint64_t prune_q = 0);
 // the checks the three make of the link parameters and of the accumulation, under the caller's name
 int crack_link_check(pcp_context *ctx, const char *who, const pcp_crack_link_params *p);
 // The forest in parent (m > 0 view indices) made a labelling: flatten (label nullable: label[list[k]] = list[root of k]), the
@@ -175,6 +201,7 @@ hipError_t preload_crack_fuse();
 hipError_t preload_crack_length();
 hipError_t preload_crack_skeleton();
 hipError_t preload_crack_direction();
+hipError_t preload_crack_branch();
 
 // ---- the links of a crack point --------------------------------------------------------------------------------------------
 // visit(c) for the candidate places c of place s (query coordinates q, m places in the cell order): the rows of the

@@ -66,11 +66,13 @@ struct HostResult {
 
 enum Brute { kBruteOk = 0, kBruteRange = 1, kBruteLoops = 2 };
 
-// xyz: n x 3; views, sum_q (nullable: every fused width 0): n.  Host only; quadratic in the crack points.
+// xyz: n x 3; views, sum_q (nullable: every fused width 0): n.  Host only; quadratic in the crack points.  lengths (nullable):
+// takes the length stage's result the skeleton was made from (the branch stage reads its ends and pos).
 inline Brute skeleton_brute(int64_t n, const float *xyz, const uint32_t *views, const uint64_t *sum_q, int32_t min_views, float t,
-                            uint64_t step_q, HostResult &out) {
+                            uint64_t step_q, HostResult &out, cl::HostResult *lengths = nullptr) {
   const size_t sn = static_cast<size_t>(n);
-  cl::HostResult len;
+  cl::HostResult own;
+  cl::HostResult &len = lengths ? *lengths : own;
   cl::lengths_brute(n, xyz, views, sum_q, min_views, t, len);  // CS1: pos, and the ids of the cracks in table order
   std::vector<int32_t> list;
   for (int64_t i = 0; i < n; ++i)

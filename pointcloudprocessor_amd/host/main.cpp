@@ -170,6 +170,20 @@
 //     circumferential above 67.5, else diagonal.  The reference only blurs one keyframe's 2-D skeleton and shows it
 //     (scripts/evalSkeletonDirection.py).  Made on the GPU (pcp_crack_directions; DESIGN.md "Crack directions on the map").
 //     Every other output stays as it is.
+//   * --crackBranches 0|1 (new, default 0; needs --crackFuse 1 and is refused where that is) and --crackPrune p (new, metres,
+//     default twice the skeleton's band width; 0 .. 1024): with 1 the run also makes the skeleton (--crackSkeletonStep; not its
+//     files unless --crackSkeleton 1 asks) and writes <outputPath>crack_width/map_crack_branch.npy (<i4, (n): the id of the
+//     point's branch, -1 outside every crack, -2 on a kept junction, -3 on a pruned spur), crack_branches.npy (<i8, (rows, 15):
+//     crack_row, nodes, edges_inside, attachments, junction_u, junction_v, points, sum_w, min_w, max_w, pos_min, pos_max, sum_qx,
+//     sum_qy, sum_qz) with crack_branch_ids.npy (<i4, (rows)), crack_branch_moments.npy (<i8, (rows, 20)) and
+//     crack_branches_3d.json: one record per crack, the cracks and order of cracks_3d.json, with id, branch_count (the
+//     table's word `branches`: the key is the list's), bridges, junctions_kept, ends_kept, pruned_branches, pruned_nodes,
+//     pruned_points, kept_length_m and the list branches: per branch id,
+//     points, length_m, mean_width, min_width, max_width (metres), arc_from_m, arc_to_m (where along the crack it lies),
+//     attachments, centroid and the direction fields of crack_directions_3d.json for the branch's own axis (axis, anisotropy,
+//     inclination_deg, class against --crackUp; with --facets 1 the crack's facet, facet_kind, out_of_plane_deg, and on a fitted
+//     cylinder to_axis_deg and cylinder_class).  The reference never takes a skeleton apart.  Made on the GPU
+//     (pcp_crack_branches; DESIGN.md "Crack branches on the map").  Every other output stays as it is.
 //   * --balanceImages 0|1 (new, default 0 = the reference's behaviour), --claheClip c (new, default 1.0; 0 = no clipping),
 //     --claheTiles x,y (new, default 8,8, each 1..16) and --balanceGamma g (new, default 0.8; 1 = identity table): with 1,
 //     every keyframe is colour-balanced on the GPU as it is uploaded -- CLAHE on a lightness channel, then a gamma table --
@@ -346,6 +360,9 @@ struct Options {
   float crack_skeleton_step = 0.0f;   // --crackSkeletonStep: the band width in metres (0: twice the link radius)
   bool crack_direction = false;       // --crackDirection 1: with --crackFuse, the cracks' tangents and axes (crack_width/map_tangent.npy, ...)
   double crack_up[3] = {0.0, 0.0, 1.0};  // --crackUp x,y,z: what vertical means (unit)
+  bool crack_branches = false;        // --crackBranches 1: with --crackFuse, the cracks arm by arm (crack_width/crack_branch*, map_crack_branch.npy)
+  float crack_prune = -1.0f;          // --crackPrune p: spurs of fewer than p metres of bands go (below 0: twice the band width)
+  bool crack_prune_given = false;
   bool crack_fuse = false;            // --crackFuse 1: the widths on the map and the map's cracks (crack_width/map_*.npy, cracks_3d.json)
   float crack_link_radius = 0.02f;    // --crackLinkRadius r: crack points this close belong to one crack
   int crack_min_views = 1;            // --crackMinViews v: credited keyframes a crack point needs
@@ -657,6 +674,8 @@ static Options parse(int argc, char **argv) {
     else if (a == "--crackSkeleton") o.crack_skeleton = parse_bool(next());
     else if (a == "--crackSkeletonStep") o.crack_skeleton_step = std::stof(next());
     else if (a == "--crackDirection") o.crack_direction = parse_bool(next());
+    else if (a == "--crackBranches") o.crack_branches = parse_bool(next());
+    else if (a == "--crackPrune") o.crack_prune = std::stof(next()), o.crack_prune_given = true;
     else if (a == "--crackUp") {
       const std::string v = next();
       double u[3] = {0.0, 0.0, 0.0};
@@ -778,6 +797,12 @@ static Options parse(int argc, char **argv) {
     throw std::runtime_error("the option '--crackSkeleton 1' needs the widths on the map (--crackFuse 1)");
   if (o.crack_direction && !o.crack_fuse)
     throw std::runtime_error("the option '--crackDirection 1' needs the widths on the map (--crackFuse 1)");
+  if (o.crack_branches && !o.crack_fuse)
+    throw std::runtime_error("the option '--crackBranches 1' needs the widths on the map (--crackFuse 1)");
+  if (o.crack_prune_given && !(o.crack_prune >= 0.0f && o.crack_prune <= 1024.0f))
+    throw std::runtime_error("the option '--crackPrune' takes a length in metres from 0 (nothing is pruned) to 1024");
+  if (o.crack_branches && !(o.crack_skeleton_step >= 0.0f && o.crack_skeleton_step <= 16.0f))
+    throw std::runtime_error("the option '--crackSkeletonStep' takes 0 (twice the link radius) or a band width in metres up to 16");
   if (o.crack_skeleton && !(o.crack_skeleton_step >= 0.0f && o.crack_skeleton_step <= 16.0f))
     throw std::runtime_error("the option '--crackSkeletonStep' takes 0 (twice the link radius) or a band width in metres up to 16");
   if (o.crack_fuse && o.maskImageFolder.empty())
@@ -869,6 +894,8 @@ static void usage(std::ostream &os) {
         "  --crackSkeleton arg (=0)              With --crackFuse: also write every crack's skeleton: branches, junctions, loops\n"
         "  --crackDirection arg (=0)             With --crackFuse: also write every crack point's tangent and every crack's axis and class\n"
         "  --crackUp arg (=0,0,1)                With --crackDirection: the vertical x,y,z (finite, not zero)\n"
+        "  --crackBranches arg (=0)              With --crackFuse: also write every crack arm by arm: branches, spurs pruned, lengths, widths, axes\n"
+        "  --crackPrune arg (=2 band widths)     With --crackBranches: one-attachment branches of fewer metres of bands are pruned (0 .. 1024)\n"
         "  --orthoMap arg (=0)                   Also write one orthographic picture of the coloured cloud as .npy (--gpus 1)\n"
         "  --orthoGsd arg (=0.01)                With --orthoMap: metres per pixel (1e-4..1)\n"
         "  --orthoFill arg (=0)                  With --orthoMap: fill empty pixels from the nearest occupied one within R pixels\n"
@@ -1673,12 +1700,15 @@ class Processor {
     CrackLengths cl;
     CrackSkeleton sk;
     CrackDirections cdir;
+    CrackBranches cbr;
     {
       const auto t0 = PhaseClock::clock::now();
       m = ViewCulling(dev).crackMap(added, static_cast<int64_t>(cloud.size()), opt.crack_threshold, opt.crack_plane_radius,
                                     opt.crack_min_views, opt.crack_link_radius, opt.crack_length ? &cl : nullptr,
-                                    opt.crack_skeleton ? &sk : nullptr, opt.crack_skeleton_step, opt.crack_direction ? &cdir : nullptr);
-      g_clock.add("crack_fuse_gpu_s", PhaseClock::since(t0) - cl.seconds - sk.seconds - cdir.seconds);
+                                    opt.crack_skeleton ? &sk : nullptr, opt.crack_skeleton_step, opt.crack_direction ? &cdir : nullptr,
+                                    opt.crack_branches ? &cbr : nullptr, opt.crack_prune);
+      g_clock.add("crack_fuse_gpu_s", PhaseClock::since(t0) - cl.seconds - sk.seconds - cdir.seconds - cbr.seconds);
+      if (opt.crack_branches) g_clock.add("crack_branches_gpu_s", cbr.seconds);
       if (opt.crack_direction) g_clock.add("crack_direction_gpu_s", cdir.seconds);
       if (opt.crack_length) g_clock.add("crack_length_gpu_s", cl.seconds);
       if (opt.crack_skeleton) g_clock.add("crack_skeleton_gpu_s", sk.seconds);
@@ -1732,6 +1762,7 @@ class Processor {
     if (opt.crack_length) writeCrackLengths(cl, stem);
     if (opt.crack_skeleton) writeCrackSkeleton(sk, m, stem);
     if (opt.crack_direction) writeCrackDirections(cdir, crack_facet, stem);
+    if (opt.crack_branches) writeCrackBranches(cbr, m, crack_facet, stem);
     if (opt.ortho_map && !opt.ortho_by_facet) {  // the widths and the cracks drawn on the orthographic map: map_width[index], map_crack[index]
       const size_t h = static_cast<size_t>(ortho_frame_used.height), w = static_cast<size_t>(ortho_frame_used.width);
       std::vector<float> width(ortho_index.size(), 0.0f);
@@ -2156,13 +2187,11 @@ class Processor {
               << "crack_skeleton_3d.json, " << cracks << " cracks, " << nodes << " nodes, " << edges << " edges" << std::endl;
   }
 
-  // --crackDirection 1: every crack point's tangent, and every crack's axis against the vertical and against its facet
-  void writeCrackDirections(const CrackDirections &c, const std::vector<int32_t> &crack_facet, const std::string &stem) {
-    Phase ph("crack_direction_write_s");
-    const size_t n = c.anisotropy.size();
-    writeNpy(stem + "map_tangent.npy", "<f4", {n, 3}, c.tangent.data(), 3 * n * 4);
-    writeNpy(stem + "map_anisotropy.npy", "<f4", {n}, c.anisotropy.data(), n * 4);
-    std::ofstream f(stem + "crack_directions_3d.json");
+  // The direction fields of a record of crack_directions_3d.json and of a branch of crack_branches_3d.json, from the five
+  // doubles of pcp_crack_axis_host (ax: links, the unit axis, its anisotropy) and the facet of the crack (with --facets 1):
+  // "axis": .., "anisotropy": .., "inclination_deg": .., "class": ".." and then "facet", "facet_kind", "out_of_plane_deg",
+  // "to_axis_deg", "cylinder_class" where they apply
+  std::string directionFields(const double *ax, int32_t facet_id) const {
     auto num = [](double v) {
       char b[64];
       std::snprintf(b, sizeof(b), "%.9g", v);
@@ -2172,33 +2201,87 @@ class Processor {
     auto cosine = [](const double *a, double bx, double by, double bz) {  // |a . b| of two unit vectors, at most 1
       return std::min(1.0, std::fabs((a[0] * bx + a[1] * by) + a[2] * bz));
     };
+    std::ostringstream f;
+    const bool has = ax[1] != 0.0 || ax[2] != 0.0 || ax[3] != 0.0;
+    const double incl = has ? std::acos(cosine(ax + 1, opt.crack_up[0], opt.crack_up[1], opt.crack_up[2])) * deg : 0.0;
+    f << "\"axis\": [" << num(ax[1]) << ", " << num(ax[2]) << ", " << num(ax[3]) << "], \"anisotropy\": " << num(ax[4]) << ", \"inclination_deg\": "
+      << num(incl) << ", \"class\": \"" << (!has ? "none" : incl < 22.5 ? "vertical" : incl > 67.5 ? "horizontal" : "diagonal") << "\"";
+    if (opt.facets) {
+      const int32_t id = facet_id;
+      const size_t fr = id < 0 ? facets_.ids.size() : static_cast<size_t>(std::lower_bound(facets_.ids.begin(), facets_.ids.end(), id) - facets_.ids.begin());
+      const bool known = fr < facets_.ids.size() && facets_.ids[fr] == id;
+      const bool plane = known && facets_.planar[fr];
+      const bool cylinder = known && !plane && opt.facet_cylinders && fr < facet_kind_.size() && facet_kind_[fr] == 2;
+      f << ", \"facet\": " << id << ", \"facet_kind\": \"" << (plane ? "plane" : cylinder ? "cylinder" : "none") << "\"";
+      if (plane && has) {
+        const double *pl = facets_.plane.data() + 7 * fr;
+        f << ", \"out_of_plane_deg\": " << num(std::asin(cosine(ax + 1, pl[3], pl[4], pl[5])) * deg);
+      }
+      if (cylinder && has) {
+        const pcp_cyl_frame &cy = facet_cyl_[fr];
+        const double to_axis = std::acos(cosine(ax + 1, cy.a[0], cy.a[1], cy.a[2])) * deg;
+        f << ", \"to_axis_deg\": " << num(to_axis) << ", \"cylinder_class\": \""
+          << (to_axis < 22.5 ? "longitudinal" : to_axis > 67.5 ? "circumferential" : "diagonal") << "\"";
+      }
+    }
+    return f.str();
+  }
+
+  // --crackBranches 1: every crack arm by arm: the branch of every point, the tables, and one record per crack with its branches
+  void writeCrackBranches(const CrackBranches &c, const CrackMap &m, const std::vector<int32_t> &crack_facet, const std::string &stem) {
+    Phase ph("crack_branches_write_s");
+    const size_t rows = c.ids.size(), cracks = c.cracks.size() / 7;
+    writeNpy(stem + "map_crack_branch.npy", "<i4", {c.branch.size()}, c.branch.data(), c.branch.size() * 4);
+    writeNpy(stem + "crack_branches.npy", "<i8", {rows, 15}, c.rows.data(), c.rows.size() * 8);
+    writeNpy(stem + "crack_branch_ids.npy", "<i4", {rows}, c.ids.data(), rows * 4);
+    writeNpy(stem + "crack_branch_moments.npy", "<i8", {rows, 20}, c.moments.data(), c.moments.size() * 8);
+    if (cracks != m.ids.size()) throw std::runtime_error("The branches' cracks are not those of the map.");
+    auto num = [](double v) {
+      char b[64];
+      std::snprintf(b, sizeof(b), "%.9g", v);
+      return std::string(b);
+    };
+    const double unit = 1.0 / 1048576.0;  // quanta of 2^-20 m to metres
+    std::vector<std::string> list(cracks);  // the branches of every crack, by ascending branch row
+    for (size_t b = 0; b < rows; ++b) {
+      const int64_t *row = c.rows.data() + 15 * b;
+      const size_t r = static_cast<size_t>(row[0]);
+      std::string &s = list[r];
+      s += (s.empty() ? "\n  {" : ",\n  {");
+      s += "\"id\": " + std::to_string(c.ids[b]) + ", \"points\": " + std::to_string(row[6]) + ", \"length_m\": " + num(c.length_m[b]) +
+           ", \"mean_width\": " + num(c.meanWidth(b)) + ", \"min_width\": " + num(static_cast<double>(row[8]) * unit) + ", \"max_width\": " +
+           num(static_cast<double>(row[9]) * unit) + ", \"arc_from_m\": " + num(static_cast<double>(row[10]) * unit) + ", \"arc_to_m\": " +
+           num(static_cast<double>(row[11]) * unit) + ", \"attachments\": " + std::to_string(row[3]) + ", \"centroid\": [" + num(c.centroid(b, 0)) +
+           ", " + num(c.centroid(b, 1)) + ", " + num(c.centroid(b, 2)) + "], " + directionFields(c.axis.data() + 5 * b, crack_facet[r]) + "}";
+    }
+    std::ofstream f(stem + "crack_branches_3d.json");
+    f << "[";
+    for (size_t r = 0; r < cracks; ++r) {
+      const int64_t *row = c.cracks.data() + 7 * r;
+      f << (r ? ",\n " : "\n ") << "{\"id\": " << m.ids[r] << ", \"branch_count\": " << row[0] << ", \"bridges\": " << row[1] << ", \"junctions_kept\": "
+        << row[2] << ", \"ends_kept\": " << row[3] << ", \"pruned_branches\": " << row[4] << ", \"pruned_nodes\": " << row[5]
+        << ", \"pruned_points\": " << row[6] << ", \"kept_length_m\": " << num(c.kept_length_m[r]) << ", \"branches\": [" << list[r] << "]}";
+    }
+    f << "\n]\n";
+    f.close();
+    if (!f) throw std::runtime_error("Couldn't save the crack branches of the map.");
+    std::cout << "Crack branches on the map saved to: " << stem << "map_crack_branch.npy, crack_branches.npy, crack_branch_ids.npy, "
+              << "crack_branch_moments.npy and crack_branches_3d.json, " << cracks << " cracks, " << rows << " branches, " << c.pruned_branches
+              << " pruned (step " << num(c.step) << " m, prune " << num(c.prune) << " m)" << std::endl;
+  }
+
+  // --crackDirection 1: every crack point's tangent, and every crack's axis against the vertical and against its facet
+  void writeCrackDirections(const CrackDirections &c, const std::vector<int32_t> &crack_facet, const std::string &stem) {
+    Phase ph("crack_direction_write_s");
+    const size_t n = c.anisotropy.size();
+    writeNpy(stem + "map_tangent.npy", "<f4", {n, 3}, c.tangent.data(), 3 * n * 4);
+    writeNpy(stem + "map_anisotropy.npy", "<f4", {n}, c.anisotropy.data(), n * 4);
+    std::ofstream f(stem + "crack_directions_3d.json");
     f << "[";
     for (size_t r = 0; r < c.ids.size(); ++r) {
       const double *ax = c.axis.data() + 5 * r;
-      const bool has = ax[1] != 0.0 || ax[2] != 0.0 || ax[3] != 0.0;
-      const double incl = has ? std::acos(cosine(ax + 1, opt.crack_up[0], opt.crack_up[1], opt.crack_up[2])) * deg : 0.0;
-      f << (r ? ",\n " : "\n ") << "{\"id\": " << c.ids[r] << ", \"links\": " << static_cast<long long>(ax[0]) << ", \"axis\": [" << num(ax[1]) << ", "
-        << num(ax[2]) << ", " << num(ax[3]) << "], \"anisotropy\": " << num(ax[4]) << ", \"inclination_deg\": " << num(incl) << ", \"class\": \""
-        << (!has ? "none" : incl < 22.5 ? "vertical" : incl > 67.5 ? "horizontal" : "diagonal") << "\"";
-      if (opt.facets) {
-        const int32_t id = crack_facet[r];
-        const size_t fr = id < 0 ? facets_.ids.size() : static_cast<size_t>(std::lower_bound(facets_.ids.begin(), facets_.ids.end(), id) - facets_.ids.begin());
-        const bool known = fr < facets_.ids.size() && facets_.ids[fr] == id;
-        const bool plane = known && facets_.planar[fr];
-        const bool cylinder = known && !plane && opt.facet_cylinders && fr < facet_kind_.size() && facet_kind_[fr] == 2;
-        f << ", \"facet\": " << id << ", \"facet_kind\": \"" << (plane ? "plane" : cylinder ? "cylinder" : "none") << "\"";
-        if (plane && has) {
-          const double *pl = facets_.plane.data() + 7 * fr;
-          f << ", \"out_of_plane_deg\": " << num(std::asin(cosine(ax + 1, pl[3], pl[4], pl[5])) * deg);
-        }
-        if (cylinder && has) {
-          const pcp_cyl_frame &cy = facet_cyl_[fr];
-          const double to_axis = std::acos(cosine(ax + 1, cy.a[0], cy.a[1], cy.a[2])) * deg;
-          f << ", \"to_axis_deg\": " << num(to_axis) << ", \"cylinder_class\": \""
-            << (to_axis < 22.5 ? "longitudinal" : to_axis > 67.5 ? "circumferential" : "diagonal") << "\"";
-        }
-      }
-      f << "}";
+      f << (r ? ",\n " : "\n ") << "{\"id\": " << c.ids[r] << ", \"links\": " << static_cast<long long>(ax[0]) << ", "
+        << directionFields(ax, opt.facets ? crack_facet[r] : -1) << "}";
     }
     f << "\n]\n";
     f.close();

@@ -185,6 +185,31 @@ struct CrackSkeleton {
   }
 };
 
+// The branches of the map's cracks (pcp_hip.h, "crack branches on the map"): the skeleton cut at its junctions, short spurs
+// pruned, one row per branch, and per map point the id of its branch.  The library returns integers; the lengths are
+// pcp_crack_branch_lengths_host's, the axes pcp_crack_axis_host's.
+struct CrackBranches {
+  std::vector<int32_t> branch;       // the id of the point's branch; -1: no crack point, -2: a kept junction, -3: pruned
+  std::vector<int32_t> ids;          // per branch, ascending
+  std::vector<int64_t> rows;         // 15 per branch: crack_row nodes edges_inside attachments junction_u junction_v points sum_w
+                                     // min_w max_w pos_min pos_max sum_qx sum_qy sum_qz
+  std::vector<int64_t> moments;      // 20 per branch: (lo, hi) of the links inside it
+  std::vector<int32_t> edge_branch;  // per edge of the skeleton: the branch row; -1: a bridge, -2: an edge with a pruned end
+  std::vector<int64_t> cracks;       // 7 per crack: branches bridges junctions_kept ends_kept pruned_branches pruned_nodes pruned_points
+  std::vector<double> axis;          // 5 per branch: ordered links, the unit axis (zeros: none), its anisotropy
+  std::vector<double> length_m;      // per branch
+  std::vector<double> kept_length_m; // per crack
+  float step = 0.0f, prune = 0.0f;   // as the stage took them
+  int64_t pruned_branches = 0;
+  double seconds = 0.0;              // wall time of the stage (the call, its fetches, the lengths and the axes)
+  // a branch's centroid on one axis (0..2), metres
+  double centroid(size_t row, int axis_) const {
+    return (static_cast<double>(rows[15 * row + 12 + static_cast<size_t>(axis_)]) / static_cast<double>(rows[15 * row + 6])) * (1.0 / 1048576.0);
+  }
+  // the mean fused width of a branch's points, metres
+  double meanWidth(size_t row) const { return (static_cast<double>(rows[15 * row + 7]) / static_cast<double>(rows[15 * row + 6])) * (1.0 / 1048576.0); }
+};
+
 class Device {
  public:
   explicit Device(int ordinal = 0) {
@@ -533,9 +558,11 @@ class ViewCulling {
   // lengths (nullable): also the cracks' lengths, ends and centrelines for the same min_views and link radius
   // skeleton (nullable): also the cracks' skeletons for them and the band width skeleton_step (metres; 0: 2 * link_radius)
   // directions (nullable): also the cracks' directions for the same min_views and link radius
+  // branches (nullable): also the cracks' branches for them, skeleton_step and the bound prune (metres; below 0: twice the band width)
   CrackMap crackMap(const std::vector<int> &keyframes, int64_t points, int threshold = 0, int plane_radius = 150, int min_views = 1,
                     float link_radius = 0.02f, CrackLengths *lengths = nullptr, CrackSkeleton *skeleton = nullptr,
-                    float skeleton_step = 0.0f, CrackDirections *directions = nullptr) const {
+                    float skeleton_step = 0.0f, CrackDirections *directions = nullptr, CrackBranches *branches = nullptr,
+                    float prune = -1.0f) const {
     CrackMap m;
     dev_.check(pcp_crack_fuse_begin(dev_.get()));
     try {
@@ -563,6 +590,7 @@ class ViewCulling {
       if (directions) *directions = crackDirections(points, min_views, link_radius);  // (it leaves the same component table)
       if (lengths) *lengths = crackLengths(points, min_views, link_radius);
       if (skeleton) *skeleton = crackSkeleton(points, min_views, link_radius, skeleton_step);
+      if (branches) *branches = crackBranches(points, min_views, link_radius, skeleton_step, prune);  // (it leaves the same three tables)
     } catch (...) {
       (void)pcp_crack_fuse_end(dev_.get());
       throw;
@@ -626,6 +654,43 @@ class ViewCulling {
     dev_.check(pcp_crack_skeleton_nodes_fetch(dev_.get(), 0, nodes, c.ids.data(), c.nodes.data(), &got));
     dev_.check(pcp_crack_skeleton_edges_fetch(dev_.get(), 0, edges, c.edges.data(), &got));
     dev_.check(pcp_crack_skeleton_cracks_fetch(dev_.get(), 0, cracks, c.cracks.data(), &got));
+    c.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return c;
+  }
+  // Every crack of the live accumulation arm by arm (between pcp_crack_fuse_begin and _end; crackMap runs it when asked): the
+  // diagram of crackSkeleton cut at its junctions, branches with one attachment and nodes * step < prune pruned.  step: the
+  // band width in metres, 0 for 2 * link_radius; prune: metres, below 0 for twice the band width.
+  CrackBranches crackBranches(int64_t points, int min_views = 1, float link_radius = 0.02f, float step = 0.0f, float prune = -1.0f) const {
+    CrackBranches c;
+    const auto t0 = std::chrono::steady_clock::now();
+    c.branch.resize(static_cast<size_t>(points));
+    c.step = step > 0.0f ? step : 2.0f * link_radius;
+    c.prune = prune >= 0.0f ? prune : 2.0f * c.step;
+    const pcp_crack_link_params link{min_views, link_radius};
+    int64_t rows = 0, nodes = 0, edges = 0, cracks = 0, got = 0;
+    dev_.check(pcp_crack_branches(dev_.get(), &link, c.step, c.prune, c.branch.data(), &rows, &c.pruned_branches));
+    dev_.check(pcp_crack_branch_edges_fetch(dev_.get(), 0, INT64_MAX / 2, nullptr, &edges));
+    dev_.check(pcp_crack_branch_cracks_fetch(dev_.get(), 0, INT64_MAX / 2, nullptr, &cracks));
+    dev_.check(pcp_crack_skeleton_nodes_fetch(dev_.get(), 0, INT64_MAX / 2, nullptr, nullptr, &nodes));
+    const size_t sb = static_cast<size_t>(rows), se = static_cast<size_t>(edges), sc = static_cast<size_t>(cracks);
+    c.ids.resize(sb);
+    c.rows.resize(15 * sb);
+    c.moments.resize(20 * sb);
+    c.edge_branch.resize(se);
+    c.cracks.resize(7 * sc);
+    c.axis.assign(5 * sb, 0.0);
+    c.length_m.assign(sb, 0.0);
+    c.kept_length_m.assign(sc, 0.0);
+    std::vector<int64_t> node_rows(10 * static_cast<size_t>(nodes)), edge_rows(3 * se);
+    dev_.check(pcp_crack_branches_fetch(dev_.get(), 0, rows, c.ids.data(), c.rows.data(), c.moments.data(), &got));
+    dev_.check(pcp_crack_branch_edges_fetch(dev_.get(), 0, edges, c.edge_branch.data(), &got));
+    dev_.check(pcp_crack_branch_cracks_fetch(dev_.get(), 0, cracks, c.cracks.data(), &got));
+    dev_.check(pcp_crack_skeleton_nodes_fetch(dev_.get(), 0, nodes, nullptr, node_rows.data(), &got));
+    dev_.check(pcp_crack_skeleton_edges_fetch(dev_.get(), 0, edges, edge_rows.data(), &got));
+    if (pcp_crack_branch_lengths_host(nodes, node_rows.data(), edges, edge_rows.data(), c.edge_branch.data(), rows, cracks, c.length_m.data(),
+                                      c.kept_length_m.data()) != PCP_OK)
+      throw std::runtime_error(std::string("pcp_hip: ") + pcp_last_error(nullptr));
+    for (size_t r = 0; r < sb; ++r) dev_.check(pcp_crack_axis_host(c.moments.data() + 20 * r, c.axis.data() + 5 * r));
     c.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return c;
   }

@@ -27,6 +27,7 @@ TARGETS = {
     "crack_length_selftest": ["crack_length_selftest.cpp"],  # csrc/pcp_crack_length.hpp compiled for the host (CPU only)
     "crack_skeleton_selftest": ["crack_skeleton_selftest.cpp"],  # csrc/pcp_crack_skeleton.hpp compiled for the host (CPU only)
     "crack_direction_selftest": ["crack_direction_selftest.cpp"],  # csrc/pcp_crack_direction.hpp compiled for the host (CPU only)
+    "crack_branch_selftest": ["crack_branch_selftest.cpp"],  # csrc/pcp_crack_branch.hpp compiled for the host (CPU only)
     "image_balance_selftest": ["image_balance_selftest.cpp"],  # csrc/pcp_image_balance.hpp compiled for the host (CPU only)
     "ortho_cyl_selftest": ["ortho_cyl_selftest.cpp"],  # csrc/pcp_ortho_cyl.hpp compiled for the host (CPU only)
     "ortho_cyl_texture_selftest": ["ortho_cyl_texture_selftest.cpp"],  # csrc/pcp_ortho_cyl.hpp's way back, pixel to point (CPU only)
@@ -42,7 +43,7 @@ def build(force: bool = False) -> dict:
     for name, srcs in TARGETS.items():
         exe = os.path.join(BIN, name)
         deps = [os.path.join(HOST, s) for s in srcs] + [os.path.join(HOST, "pcp_shim.hpp"), os.path.join(HOST, "pcp_multi.hpp"), os.path.join(HOST, "pcd_io.hpp"), os.path.join(HOST, "image_io.hpp"), os.path.join(HOST, "pcd_device_reader.hpp"),
-                                                       os.path.join(_build.CSRC, "pcp_ascii_parse.hpp"), os.path.join(_build.CSRC, "pcp_ascii.hpp"), os.path.join(_build.CSRC, "pcp_visit_forms.hpp"), os.path.join(_build.CSRC, "pcp_voxel_reduce.hpp"), os.path.join(_build.CSRC, "pcp_normals.hpp"), os.path.join(_build.CSRC, "pcp_ortho.hpp"), os.path.join(_build.CSRC, "pcp_ortho_cyl.hpp"), os.path.join(_build.CSRC, "pcp_ortho_texture.hpp"), os.path.join(_build.CSRC, "pcp_ortho_defects.hpp"), os.path.join(_build.CSRC, "pcp_crack_width.hpp"), os.path.join(_build.CSRC, "pcp_crack_fuse.hpp"), os.path.join(_build.CSRC, "pcp_crack_length.hpp"), os.path.join(_build.CSRC, "pcp_crack_skeleton.hpp"), os.path.join(_build.CSRC, "pcp_crack_direction.hpp"), os.path.join(_build.CSRC, "pcp_image_balance.hpp"), os.path.join(_build.CSRC, "pcp_hsv.hpp"), os.path.join(_build.CSRC, "pcp_facets.hpp"), os.path.join(_build.CSRC, "pcp_eigen33_host.hpp"), os.path.join(_build.CSRC, "pcp_tile_box.hpp"),
+                                                       os.path.join(_build.CSRC, "pcp_ascii_parse.hpp"), os.path.join(_build.CSRC, "pcp_ascii.hpp"), os.path.join(_build.CSRC, "pcp_visit_forms.hpp"), os.path.join(_build.CSRC, "pcp_voxel_reduce.hpp"), os.path.join(_build.CSRC, "pcp_normals.hpp"), os.path.join(_build.CSRC, "pcp_ortho.hpp"), os.path.join(_build.CSRC, "pcp_ortho_cyl.hpp"), os.path.join(_build.CSRC, "pcp_ortho_texture.hpp"), os.path.join(_build.CSRC, "pcp_ortho_defects.hpp"), os.path.join(_build.CSRC, "pcp_crack_width.hpp"), os.path.join(_build.CSRC, "pcp_crack_fuse.hpp"), os.path.join(_build.CSRC, "pcp_crack_length.hpp"), os.path.join(_build.CSRC, "pcp_crack_skeleton.hpp"), os.path.join(_build.CSRC, "pcp_crack_direction.hpp"), os.path.join(_build.CSRC, "pcp_crack_branch.hpp"), os.path.join(_build.CSRC, "pcp_image_balance.hpp"), os.path.join(_build.CSRC, "pcp_hsv.hpp"), os.path.join(_build.CSRC, "pcp_facets.hpp"), os.path.join(_build.CSRC, "pcp_eigen33_host.hpp"), os.path.join(_build.CSRC, "pcp_tile_box.hpp"),
                                                        os.path.join(_build.INCLUDE, "pcp_hip.h")]
         deps = [d for d in deps if os.path.exists(d)]
         stale = force or not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps)

@@ -407,7 +407,8 @@ class PointCloudColorizer:
         return self.engine.ctx.crack_width(frame, threshold, plane_radius, want)
 
     def crack_map(self, frames=None, threshold: int = 0, plane_radius: int = 150, min_views: int = 1, link_radius: float = 0.02,
-                  lengths: bool = False, skeleton: bool = False, skeleton_step=None, directions: bool = False, up=(0.0, 0.0, 1.0)) -> dict:
+                  lengths: bool = False, skeleton: bool = False, skeleton_step=None, directions: bool = False, up=(0.0, 0.0, 1.0),
+                  branches: bool = False, prune=None) -> dict:
         """The crack widths of the keyframes brought back to the map, and the map's cracks ("Crack widths on the
         map"): begin, one add per keyframe of `frames` (None: all of them), the components, end.  dict of the per-point arrays of
         capi.Context.crack_fuse_fetch (width_mean, width_best, best_frame, views, seen, centres, min_q, max_q, sum_q) and of
@@ -427,6 +428,11 @@ class PointCloudColorizer:
         link_radius ("Crack directions on the map"): per point the tangent of its crack and its anisotropy, per
         crack the axis, plus inclination_deg = acos|axis . up| (0..90) and cls (vertical below 22.5, horizontal above 67.5, else
         diagonal; none without an axis) against the vertical `up` (finite, not zero).  Off, the return value is what it was.
+
+        branches: the dict gains `branches`, the dict of capi.Context.crack_branches for the same min_views, link_radius and
+        skeleton_step and the bound `prune` (metres; None: twice the band width) ("Crack branches on the map"): the
+        cracks arm by arm, short spurs pruned, per branch its points, widths, length and axis.  Off, the return value is what it
+        was.
 
         An index shard sees only its own points, so world > 1 raises ValueError.  (The shards' key images would have to be
         merged first, as for geometry_maps; not built.)"""
@@ -456,6 +462,9 @@ class PointCloudColorizer:
                 out["lengths"] = ctx.crack_lengths(min_views, link_radius)
             if skeleton:
                 out["skeleton"] = ctx.crack_skeleton(min_views, link_radius, skeleton_step)
+            if branches:  # (it leaves the same skeleton, length and component tables)
+                step = capi.crack_skeleton_step(link_radius) if skeleton_step is None else skeleton_step
+                out["branches"] = ctx.crack_branches(min_views, link_radius, step, 2.0 * step if prune is None else prune)
             out["contributors"] = [c[0] for c in counts]
             out["credited"] = [c[1] for c in counts]
             self.last_crack_map = dict(width_mean=out["width_mean"], label=out["label"])  # (ortho_map draws them)
