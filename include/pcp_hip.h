@@ -92,7 +92,10 @@ extern "C" {
                                 pcp_crack_branch_edges_fetch / _cracks_fetch, pcp_crack_branch_lengths_host (crack branches on the
                                 map; nothing runs unless called);
                                 entry points added, no layout changed: pcp_ortho_defects / _fetch / _table / _host
-                                (surface defects on ortho maps; nothing runs unless called) */
+                                (surface defects on ortho maps; nothing runs unless called);
+                                entry points added, no layout changed: pcp_default_compare_params, pcp_compare_set_base,
+                                pcp_compare / _fetch / _host / _end (map comparison with an earlier survey; nothing runs unless
+                                called) */
 
 #define PCP_OK 0
 #define PCP_ERR_INVALID (-1) /* bad argument */
@@ -1004,6 +1007,60 @@ int pcp_normals_fetch(pcp_context *ctx, float *out_normal, float *out_curvature,
 int pcp_normals_moments_host(float radius, int64_t n, const float *xyz, int64_t *out_moments);
 int pcp_frame_geometry(pcp_context *ctx, int32_t frame, int32_t *out_index, float *out_range, float *out_xyz_cam,
                        float *out_normal_cam, int64_t *out_pixels);
+
+/* ---- map comparison (no counterpart in the reference; the method is Lague et al.'s M3C2) ---------------------------------- */
+/* Per point of the uploaded map (the current survey), the signed distance along its normal to an earlier survey of the same
+ * structure (the base), with a level of detection from the two epochs' scatter ("Map comparison", MC1-MC9).  Opt-in:
+ * nothing runs unless one of these is called, PCP_ABI_VERSION is unchanged and a caller detects support by the symbols.
+ * Kernels are timed under PCP_K_MISC.  Whole-map contexts only; no streamed form.
+ *
+ * pcp_compare_set_base: the base, n_base host rows of stride_bytes (a multiple of 4, >= 12) with xyz first; copied to the
+ * device, non-finite rows left out.  It replaces an earlier base (and ends its result) and stays across pcp_upload_cloud*
+ * until pcp_compare_end or pcp_destroy.  n_base == 0 is allowed.  n + n_base <= 2^31 - 64.
+ * pcp_compare: core points are the map points with three finite coordinates and a valid normal (three finite components,
+ * each |n_a| <= 1, not all zero) -- `normals` (host, 3 floats per point, input order) or, when NULL, the live estimate of
+ * pcp_estimate_normals (without one: PCP_ERR_STATE).  The normal is oriented by orient_mode (0: kept; 1: towards the point
+ * orient; 2: along the vector orient; flipped iff fl32((nx*vx + ny*vy) + nz*vz) < 0 with v = fl32(orient - p) or orient),
+ * then N_a = rint(n_a * 2^11), N2 = N.N (N2 == 0: not a core point).  In each epoch (A the map, B the base) point j is a
+ * candidate of core point i iff, with d = fl32(p_j - p_i), q = rint(d * 2^20), h = q.N, Q2 = q.q:
+ *   fl32((dx*dx + dy*dy) + dz*dz) <= t   (t the largest float with (double)t <= (double)s^2,
+ *                                         s = nextafterf(fl32(sqrt((double)rc^2 + (double)L^2)), +inf)),
+ *   h*h <= L2*N2 and Q2*N2 - h*h <= rc2*N2   (rc2 = floor((rc * 2^20)^2), L2 = floor((L * 2^20)^2), int64).
+ * 0.005 <= cyl_radius, 0.005 <= cyl_half_length, s <= 0.5, reg_error finite and >= 0, min_points >= 2, orient_mode 0..2:
+ * else PCP_ERR_INVALID.  Per epoch n, S1 = sum h, S2a = sum (h*h mod 2^32), S2b = sum (h*h div 2^32) are exact int64 sums
+ * (an epoch with 2^22 candidates or more at one point: PCP_ERR_RANGE).  In fp64, every operation rounded on its own:
+ *   S2 = (double)S2a + 4294967296.0 * (double)S2b;  scale = sqrt((double)N2) * 1048576.0;
+ *   distance = ((double)S1A / nA - (double)S1B / nB) / scale;  var = (S2 - (S1 * S1) / n) / (n - 1.0) (below 0: 0);
+ *   lod = 1.96 * sqrt(varA / nA + varB / nB) / scale + (double)reg_error.
+ * Positive: the map's surface lies nearer the oriented side than the base's (deposit, bulge); negative: loss, spall.
+ * status: 0 not a core point; 1 nB < min_points (no counterpart; distance and lod 0); 2 nA < min_points; 3 measured,
+ * |distance| <= lod (compared in fp64); 4 significant, positive; 5 significant, negative.  Tests in that order.
+ * out_stats (nullable): core points (status != 0), measured (3..5), significant positive, significant negative, no
+ * counterpart, too few own points, most candidates of one epoch at one point, 0.
+ * The result stays on the device (85 B per point) until the next pcp_upload_cloud* drops it.  Like every call that builds the
+ * search grid, pcp_compare invalidates an open pcp_mls_stream / pcp_cloud_smooth_stream and a pcp_sor_partial; it touches
+ * nothing else.  Without a cloud or a base: PCP_ERR_STATE.  Base points without a counterpart on the map are found by a second
+ * run with the roles swapped (not built).
+ * pcp_compare_fetch: the result in input order, every output nullable: distance, lod (float), status (uint8), 8 int64 sums
+ * (nA S1A S2aA S2bA nB S1B S2aB S2bB) and the 3 int32 of N per point.  Without a result: PCP_ERR_STATE.
+ * pcp_compare_host: host only, no context, no GPU: the same by brute force over the pairs with the arithmetic the kernel
+ * uses (csrc/pcp_compare.hpp); n, n_base <= 65536, xyz / normals / base_xyz interleaved.  The message is at
+ * pcp_last_error(NULL).
+ * pcp_compare_end: drops the base and the result. */
+typedef struct pcp_compare_params {
+  float cyl_radius, cyl_half_length, reg_error;
+  int32_t min_points, orient_mode;
+  float orient[3];
+} pcp_compare_params;
+void pcp_default_compare_params(pcp_compare_params *p); /* 0.03, 0.05, 0, 5, mode 0 */
+int pcp_compare_set_base(pcp_context *ctx, const void *points, int64_t n_base, int64_t stride_bytes);
+int pcp_compare(pcp_context *ctx, const pcp_compare_params *p, const float *normals, int64_t out_stats[8]);
+int pcp_compare_fetch(pcp_context *ctx, float *out_distance, float *out_lod, uint8_t *out_status, int64_t *out_sums8,
+                      int32_t *out_direction3);
+int pcp_compare_host(const pcp_compare_params *p, int64_t n, const float *xyz, const float *normals, int64_t n_base,
+                     const float *base_xyz, float *out_distance, float *out_lod, uint8_t *out_status, int64_t *out_sums8,
+                     int32_t *out_direction3, int64_t out_stats[8]);
+int pcp_compare_end(pcp_context *ctx);
 
 /* ---- mask distance maps (scripts/genNormAndDistanceMask.py: class Crack, preprocess :150-198, cv2.threshold :167, */
 /* ---- scipy.ndimage.distance_transform_edt :9,168) ------------------------------------------------------------------ */

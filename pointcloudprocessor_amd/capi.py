@@ -591,6 +591,53 @@ def normals_moments_host(radius: float, xyz) -> np.ndarray:
     return out
 
 
+class CompareParams(C.Structure):
+    """pcp_compare_params (DESIGN.md, "Map comparison", MC2-MC6)."""
+    _fields_ = [("cyl_radius", C.c_float), ("cyl_half_length", C.c_float), ("reg_error", C.c_float), ("min_points", C.c_int32),
+                ("orient_mode", C.c_int32), ("orient", C.c_float * 3)]
+
+
+MC_SUMS = ("nA", "s1A", "s2aA", "s2bA", "nB", "s1B", "s2aB", "s2bB")  # MC4: the columns of sums
+MC_STATS = ("core", "measured", "positive", "negative", "no_counterpart", "too_few_own", "most_candidates", "reserved")
+MC_NOT_CORE, MC_NO_COUNTERPART, MC_TOO_FEW_OWN, MC_MEASURED, MC_POSITIVE, MC_NEGATIVE = range(6)  # MC6: the status byte
+
+
+def compare_params(radius: float = 0.03, half_length: float = 0.05, reg_error: float = 0.0, min_points: int = 5,
+                   orient_mode: int = 0, orient=(0.0, 0.0, 0.0)) -> CompareParams:
+    orient = np.asarray(orient, np.float32).reshape(3)
+    return CompareParams(radius, half_length, reg_error, min_points, orient_mode, (C.c_float * 3)(*[float(v) for v in orient]))
+
+
+def _compare_outputs(n: int) -> dict:
+    return dict(distance=np.zeros(n, np.float32), lod=np.zeros(n, np.float32), status=np.zeros(n, np.uint8),
+                sums=np.zeros((n, 8), np.int64), direction=np.zeros((n, 3), np.int32))
+
+
+def compare_host(xyz, normals, base_xyz, radius: float = 0.03, half_length: float = 0.05, reg_error: float = 0.0,
+                 min_points: int = 5, orient_mode: int = 0, orient=(0.0, 0.0, 0.0)) -> dict:
+    """The map comparison of n <= 65536 map points against n_base <= 65536 base rows computed on the CPU by brute force over
+    the pairs with the arithmetic the kernel uses (pcp_compare_host: no context, no GPU; DESIGN.md "Map comparison").  xyz,
+    normals (n, 3) float32, base_xyz (n_base, 3) float32 -> dict(distance, lod (n,) float32, status (n,) uint8, sums (n, 8)
+    int64 with the columns MC_SUMS, direction (n, 3) int32, stats (8,) int64 with the entries MC_STATS)."""
+    L = load()
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    base_xyz = np.ascontiguousarray(base_xyz, np.float32).reshape(-1, 3)
+    n = xyz.shape[0]
+    if normals.shape[0] != n:
+        raise ValueError("compare_host: xyz and normals differ in their number of rows")
+    prm = compare_params(radius, half_length, reg_error, min_points, orient_mode, orient)
+    out = _compare_outputs(min(n, 65536))  # (more rows are refused by the library: nothing to allocate)
+    stats = np.zeros(8, np.int64)
+    rc = L.pcp_compare_host(C.byref(prm), C.c_int64(n), _ptr(xyz), _ptr(normals), C.c_int64(base_xyz.shape[0]), _ptr(base_xyz),
+                            _ptr(out["distance"]), _ptr(out["lod"]), _ptr(out["status"]), _ptr(out["sums"]), _ptr(out["direction"]),
+                            _ptr(stats))
+    if rc != PCP_OK:
+        raise PcpError(rc, L.pcp_last_error(None).decode())
+    out["stats"] = stats
+    return out
+
+
 def mask_edt_host(gray, threshold: int = 0) -> dict:
     """The mask distance maps of a (H, W) uint8 mask computed on the CPU with the arithmetic the kernels use
     (pcp_mask_edt_host: no context, no GPU; DESIGN.md "Mask distance maps").  A row stride above the width is passed on
@@ -1703,6 +1750,44 @@ class Context:
         if normals:
             out["normal_cam"] = nrm
         return out
+
+    # -- map comparison ("Map comparison") ---------------------------------
+    def compare_set_base(self, base_xyz):
+        """The earlier survey the map is compared with: (n_base, >= 3) float32 rows, xyz first (pcp_compare_set_base).  Kept
+        across uploads until compare_end or close; a second call replaces the first."""
+        base = np.ascontiguousarray(base_xyz, np.float32)
+        if base.ndim != 2 or base.shape[1] < 3:
+            base = base.reshape(-1, 3)
+        stride = 4 * base.shape[1]
+        self._check(self.lib.pcp_compare_set_base(self.h, _ptr(base), C.c_int64(base.shape[0]), C.c_int64(stride)))
+
+    def compare(self, radius: float = 0.03, half_length: float = 0.05, reg_error: float = 0.0, min_points: int = 5,
+                orient_mode: int = 0, orient=(0.0, 0.0, 0.0), normals=None) -> dict:
+        """The signed distance of every core point of the uploaded cloud to the base along its oriented normal, with its level
+        of detection (pcp_compare and its fetch): dict(distance, lod (n,) float32, status (n,) uint8, sums (n, 8) int64 with the
+        columns MC_SUMS, direction (n, 3) int32, stats (8,) int64 with the entries MC_STATS).  normals: (n, 3) float32, or
+        None for the live estimate of estimate_normals."""
+        if normals is not None:
+            normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+            if normals.shape[0] != self.n:
+                raise ValueError("compare: normals must hold one row per point of the uploaded cloud")
+        prm = compare_params(radius, half_length, reg_error, min_points, orient_mode, orient)
+        stats = np.zeros(8, np.int64)
+        self._check(self.lib.pcp_compare(self.h, C.byref(prm), _ptr(normals), _ptr(stats)))
+        out = self.compare_fetch()
+        out["stats"] = stats
+        return out
+
+    def compare_fetch(self) -> dict:
+        """The arrays of the last compare, input order (pcp_compare_fetch)."""
+        out = _compare_outputs(self.n)
+        self._check(self.lib.pcp_compare_fetch(self.h, _ptr(out["distance"]), _ptr(out["lod"]), _ptr(out["status"]),
+                                               _ptr(out["sums"]), _ptr(out["direction"])))
+        return out
+
+    def compare_end(self):
+        """Drops the base and the result (pcp_compare_end)."""
+        self._check(self.lib.pcp_compare_end(self.h))
 
     # -- planar facets (DESIGN.md, "Planar facets") -----------------------------------
     def facets(self, link_radius: float = 0.1, angle_deg: float = 10.0, plane_tol: float = 0.01, max_curvature: float = 0.02,

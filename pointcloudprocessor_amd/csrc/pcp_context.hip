@@ -536,6 +536,7 @@ static int store_cloud(pcp_context *ctx, const float *x, const float *y, const f
   ctx->labels_live = false;
   match_table_release(ctx);  // PCP_MATCH_RADIUS: the table belongs to the cloud that is being replaced
   normals_release(ctx);      // pcp_estimate_normals: so do the normals
+  ctx->compare.release_result();  // pcp_compare: and the comparison's result (MC8: the base stays)
   ctx->crack->release();   // pcp_crack_fuse_begin: and the accumulated crack widths
   ctx->mls_count = 0;
   ctx->mls_result_live = false;
@@ -626,7 +627,7 @@ int pcp_create(int32_t device, pcp_context **out) {
     const hipError_t pl[] = {hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_up_bbox)), preload_colour(), preload_mls(), preload_grid(),
                              preload_nid(), preload_hpr(), preload_colour_smooth(), preload_match(),
                              preload_jpeg(), preload_stream_colour(), preload_ascii(), preload_ascii_parse(), preload_exposure(),
-                             preload_voxel_reduce(), preload_normals(), preload_mask_edt(), preload_ortho(), preload_ortho_texture(), preload_ortho_defects(), preload_facets(), preload_crack_width(), preload_crack_fuse(), preload_crack_length(), preload_crack_skeleton(), preload_crack_direction(), preload_crack_branch(), preload_image_balance()};
+                             preload_voxel_reduce(), preload_normals(), preload_mask_edt(), preload_ortho(), preload_ortho_texture(), preload_ortho_defects(), preload_compare(), preload_facets(), preload_crack_width(), preload_crack_fuse(), preload_crack_length(), preload_crack_skeleton(), preload_crack_direction(), preload_crack_branch(), preload_image_balance()};
     for (hipError_t x : pl)
       if (x != hipSuccess && e == hipSuccess) e = x;
   }

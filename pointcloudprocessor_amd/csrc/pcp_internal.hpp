@@ -258,6 +258,34 @@ struct GridDesc {
   const int32_t *occ_rank;
 };
 
+// ---- map comparison (pcp_compare.hip; DESIGN.md "Map comparison", MC8): the base survey and the last result ----------------
+// The base (its finite rows as SoA planes and their tags: the caller's row with the epoch bit) lives from pcp_compare_set_base to
+// pcp_compare_end or pcp_destroy; the result (input order of the map) from pcp_compare to the next upload.
+struct CompareState {
+  bool base_live = false, result_live = false;
+  int64_t n_base = 0, m_base = 0;  // rows handed in, finite rows kept
+  float mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};  // box of the finite rows
+  DevBuf<float> base_xyz;      // planes of (m_base + 3) & ~3 floats
+  DevBuf<uint32_t> base_tag;
+  int64_t n = 0;               // points of the result
+  DevBuf<float> distance, lod;
+  DevBuf<uint8_t> status;
+  DevBuf<long long> sums;      // 8 per point
+  DevBuf<int32_t> direction;   // 3 per point
+  int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  void release_result() {
+    result_live = false;
+    n = 0;
+    distance.release(), lod.release(), status.release(), sums.release(), direction.release();
+  }
+  void release() {
+    release_result();
+    base_live = false;
+    n_base = m_base = 0;
+    base_xyz.release(), base_tag.release();
+  }
+};
+
 // a cloud on the device the smoothing stages operate on (the uploaded map, or an
 // intermediate of pcp_cloud_smooth); mn/mx = its bounding box
 struct CloudView {
@@ -465,6 +493,9 @@ struct pcp_context {
   pcp::DevBuf<uint32_t> gm_out;  // index | range | xyz_cam (3) | normal_cam (3), W*H words each
   // planar facets of the map: made from the cloud and the normals above, and dropped with either
   pcp::Facets facets;
+
+  // map comparison: the base survey (kept across uploads) and the last result (dropped by the uploads)
+  pcp::CompareState compare;
 
   // mask distance maps (pcp_mask_edt.hip), for one chunk of keyframes, allocated on first use: the background bits of the
   // column segments, the column words, and the two result images
@@ -766,6 +797,7 @@ hipError_t preload_ortho();
 hipError_t preload_ortho_texture();
 hipError_t preload_facets();
 hipError_t preload_ortho_defects();
+hipError_t preload_compare();
 // the device parts of pcp_mask_edt (one keyframe, with nearest) and pcp_frame_geometry under the caller's name: checks and
 // kernels, the results left in md_bits / md_d2 / md_nearest and gm_out / s_counter[0]; no copy, no synchronisation
 int mask_edt_device(pcp_context *ctx, const char *who, int32_t frame, int32_t threshold);

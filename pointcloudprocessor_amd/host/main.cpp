@@ -263,6 +263,20 @@
 //     ortho_photo.json in the planar facets' format, banded the same way, and no facet is named as skipped.  Made on the GPU
 //     (pcp_ortho_texture_cyl; DESIGN.md "Orthophotos of unrolled maps").  Without the flag every file, byte and message is what
 //     it was.
+//   * --compareMap base.pcd (new, default none), --compareRadius rc (new, default 0.03, at least 0.005), --compareDepth L (new,
+//     default 0.05, at least 0.005; sqrt(rc^2 + L^2) at most 0.5), --compareMinPoints k (new, default 5, at least 2),
+//     --compareRegError e (new, default 0, metres) and --normalRadius as above (not 0): the run also compares the map with the
+//     earlier survey in base.pcd and writes <outputPath>compare/distance.npy (<f4, one per map point: the signed distance in
+//     metres along the point's normal, turned towards the mean keyframe position, from the base's surface to the map's inside a
+//     cylinder of radius rc and half length L; positive: deposit, bulge, movement towards the viewer), lod.npy (<f4: the level of
+//     detection, 1.96 standard errors of the difference plus e), status.npy (|u1: 0 no core point, 1 no counterpart in the base,
+//     2 too few map points, 3 measured and within lod, 4 significant positive, 5 significant negative) and compare.json (the
+//     parameters, the eight counts of pcp_compare, and the number, mean and extremes of the significant distances; numbers as
+//     %.9g).  With --orthoMap 1 every map directory (ortho/, ortho/facet_<row>/) gains change.npy (<f4: distance.npy[index], 0
+//     on an empty pixel) and change_status.npy (|u1: status.npy[index]).  Base points the map has no counterpart for (surface
+//     that disappeared) are found by a second run with the two files swapped.  Made on the GPU (pcp_compare; DESIGN.md "Map
+//     comparison").  Refused: --gpus N above 1, --enableMLS 1, --streamColour 1, --normalRadius 0.  Without the flag every file,
+//     byte and message is what it was.
 #include <algorithm>
 #include <cfloat>
 #include <chrono>
@@ -389,6 +403,8 @@ struct Options {
   pcp_facet_params facet{0.1f, 10.0f, 0.01f, 0.02f, 1000};  // --facetRadius / --facetAngle / --facetPlaneTol / --facetMaxCurvature / --facetMinPoints
   float facet_max_rms = 0.01f;        // --facetMaxRms m: a facet is planar up to this rms distance to its plane
   bool facet_cylinders = false;       // --facetCylinders 1: fit a cylinder to every facet that is not planar; unrolled maps of those that are one
+  std::string compare_map;            // --compareMap base.pcd: compare the map with this earlier survey (compare/*.npy, compare.json)
+  pcp_compare_params compare{0.03f, 0.05f, 0.0f, 5, 0, {0.0f, 0.0f, 0.0f}};  // --compareRadius / --compareDepth / --compareRegError / --compareMinPoints
 };
 
 static bool parse_bool(const std::string &v) {  // boost::program_options bool semantics
@@ -560,6 +576,24 @@ static Options parse(int argc, char **argv) {
       if (end == v.c_str() || *end != '\0' || k < 1 || k > (1L << 24))
         throw std::runtime_error("the argument ('" + v + "') for option '--facetMinPoints' is invalid (1..16777216)");
       o.facet.min_points = static_cast<int32_t>(k);
+    }
+    else if (a == "--compareMap") o.compare_map = next();
+    else if (a == "--compareRadius" || a == "--compareDepth" || a == "--compareRegError") {
+      const std::string v = next();
+      char *end = nullptr;
+      const float r = std::strtof(v.c_str(), &end);
+      const bool extent = a != "--compareRegError";
+      if (end == v.c_str() || *end != '\0' || !std::isfinite(r) || (extent ? r < 0.005f || r > 0.5f : r < 0.0f))
+        throw std::runtime_error("the argument ('" + v + "') for option '" + a + "' is invalid (" + (extent ? "0.005..0.5" : "0 or more") + ")");
+      (a == "--compareRadius" ? o.compare.cyl_radius : a == "--compareDepth" ? o.compare.cyl_half_length : o.compare.reg_error) = r;
+    }
+    else if (a == "--compareMinPoints") {
+      const std::string v = next();
+      char *end = nullptr;
+      const long k = std::strtol(v.c_str(), &end, 10);
+      if (end == v.c_str() || *end != '\0' || k < 2 || k > (1L << 22))
+        throw std::runtime_error("the argument ('" + v + "') for option '--compareMinPoints' is invalid (2..4194304)");
+      o.compare.min_points = static_cast<int32_t>(k);
     }
     else if (a == "--crackMaps") o.crack_maps = parse_bool(next());
     else if (a == "--crackThreshold") {
@@ -830,6 +864,16 @@ static Options parse(int argc, char **argv) {
                              "facets of the smoothed cloud are not built)");
   if (o.facets && o.normal_radius == 0.0f)
     throw std::runtime_error("the option '--facets 1' needs the map normals ('--normalRadius 0' turns them off)");
+  if (!o.compare_map.empty() && o.gpus > 1)
+    throw std::runtime_error("the option '--compareMap' does not work with '--gpus N' above 1 (an index shard sees only its own "
+                             "points; a comparison across shards is not built)");
+  if (!o.compare_map.empty() && o.stream_colour)
+    throw std::runtime_error("the option '--compareMap' does not work with '--streamColour 1' (a point's candidates may lie in another chunk)");
+  if (!o.compare_map.empty() && o.enableMLS)
+    throw std::runtime_error("the option '--compareMap' does not work with '--enableMLS 1' (the comparison is that of the raw map; "
+                             "a comparison of the smoothed cloud is not built)");
+  if (!o.compare_map.empty() && o.normal_radius == 0.0f)
+    throw std::runtime_error("the option '--compareMap' needs the map normals ('--normalRadius 0' turns them off)");
   if (!o.balance_images && !o.balance_value_flag.empty())
     throw std::runtime_error("the option '" + o.balance_value_flag + "' needs '--balanceImages 1'");
   if (o.balance_exposure) {
@@ -920,7 +964,12 @@ static void usage(std::ostream &os) {
         "  --facetMinPoints arg (=1000)          With --facets: a facet has at least this many points\n"
         "  --facetMaxRms arg (=0.01)             With --facets: a facet is planar up to this rms distance (m) to its plane\n"
         "  --facetCylinders arg (=0)             With --facets: fit a cylinder to every facet that is not planar; with --orthoFrame facets unroll those that are one\n"
-        "  --orthoTextureCylinders arg (=0)      With --orthoTexture, --facetCylinders and --orthoFrame facets: also the orthophoto of every unrolled map\n";
+        "  --orthoTextureCylinders arg (=0)      With --orthoTexture, --facetCylinders and --orthoFrame facets: also the orthophoto of every unrolled map\n"
+        "  --compareMap arg                      Also compare the map with this earlier survey (PCD): signed distance, level of detection and status per point (--gpus 1)\n"
+        "  --compareRadius arg (=0.03)           With --compareMap: radius (m) of the cylinder along a point's normal (0.005..0.5)\n"
+        "  --compareDepth arg (=0.05)            With --compareMap: half length (m) of that cylinder (0.005..0.5; sqrt(radius^2 + depth^2) at most 0.5)\n"
+        "  --compareMinPoints arg (=5)           With --compareMap: a distance needs this many points of each survey in the cylinder (2 or more)\n"
+        "  --compareRegError arg (=0)            With --compareMap: registration error (m) added to the level of detection\n";
 }
 
 class Processor {
@@ -977,6 +1026,7 @@ class Processor {
   pcp_mls_params mls_params{};  // --streamColour 1: the chain's parameters, kept for streamedColourisation
   std::vector<float> ortho_fit_xyz;    // --orthoMap 1 with --enableMLS 1 (one-shot): the crop the chain smoothed, for the frame
   std::vector<uint32_t> ortho_index;   // --orthoMap 1: the index layer, for the crack layers --crackFuse 1 adds
+  MapComparison compare_;              // --compareMap: the per-point result, for the maps' change layers
   Facets facets_;                      // --facets 1: the partition, for the per-facet maps and the cracks' "facet"
   std::vector<uint8_t> facet_kind_;    // --facetCylinders 1, per facet: 0 neither, 1 planar, 2 cylindrical
   std::vector<pcp_cyl_frame> facet_cyl_;  // --facetCylinders 1, per facet: the fitted cylinder's frame at --orthoGsd (where the fit succeeded)
@@ -1782,6 +1832,73 @@ class Processor {
     }
   }
 
+  // --compareMap base.pcd: the map against an earlier survey (DESIGN.md "Map comparison"): the map normals, turned towards the
+  // mean keyframe position (kept as they are without keyframes), the comparison, the three arrays and compare.json
+  void writeCompare() {
+    Device &dev = gpu->device(0);
+    XYZICloud base;
+    {
+      Phase ph("compare_read_s");
+      if (readPCD(opt.compare_map, base) == -1) throw std::runtime_error("Couldn't read the base point cloud file: " + opt.compare_map);
+    }
+    std::vector<float> rows(3 * base.size());
+    for (size_t j = 0; j < base.size(); ++j) {
+      rows[3 * j] = base.x[j];
+      rows[3 * j + 1] = base.y[j];
+      rows[3 * j + 2] = base.z[j];
+    }
+    pcp_compare_params p = opt.compare;
+    double viewer[3];
+    if (meanKeyframePosition(viewer)) {
+      p.orient_mode = 1;
+      for (int a = 0; a < 3; ++a) p.orient[a] = static_cast<float>(viewer[a]);
+    }
+    {
+      Phase ph("compare_gpu_s");
+      const int64_t valid = dev.estimateNormals(opt.normal_radius);
+      std::cout << "map normals: radius " << opt.normal_radius << ", " << valid << " of " << cloud.size() << " points valid" << std::endl;
+      compare_ = dev.compareMap(p, rows.data(), static_cast<int64_t>(base.size()));
+    }
+    Phase ph_w("compare_write_s");
+    const std::string stem = opt.outputPath + "compare/";
+    fs::create_directories(fs::path(stem));
+    const size_t n = cloud.size();
+    writeNpy(stem + "distance.npy", "<f4", {n}, compare_.distance.data(), n * 4);
+    writeNpy(stem + "lod.npy", "<f4", {n}, compare_.lod.data(), n * 4);
+    writeNpy(stem + "status.npy", "|u1", {n}, compare_.status.data(), n);
+    auto num = [](double v) {
+      char b[64];
+      std::snprintf(b, sizeof(b), "%.9g", v);
+      return std::string(b);
+    };
+    int64_t significant = 0;
+    double sum = 0.0, lo = 0.0, hi = 0.0;
+    for (size_t i = 0; i < n; ++i) {
+      if (compare_.status[i] < 4) continue;
+      const double d = compare_.distance[i];
+      lo = significant ? std::min(lo, d) : d;
+      hi = significant ? std::max(hi, d) : d;
+      sum += d;
+      ++significant;
+    }
+    std::ofstream f(stem + "compare.json");
+    f << "{\"base\": " << base.size() << ", \"points\": " << n << ", \"radius\": " << num(p.cyl_radius) << ", \"half_length\": " << num(p.cyl_half_length)
+      << ", \"reg_error\": " << num(p.reg_error) << ", \"min_points\": " << p.min_points << ", \"normal_radius\": " << num(opt.normal_radius)
+      << ", \"orient_mode\": " << p.orient_mode << ", \"viewer\": [" << num(p.orient[0]) << ", " << num(p.orient[1]) << ", " << num(p.orient[2])
+      << "], \"stats\": [";
+    for (int k = 0; k < 8; ++k) f << (k ? ", " : "") << compare_.stats[k];
+    f << "], \"core\": " << compare_.stats[0] << ", \"measured\": " << compare_.stats[1] << ", \"positive\": " << compare_.stats[2]
+      << ", \"negative\": " << compare_.stats[3] << ", \"no_counterpart\": " << compare_.stats[4] << ", \"too_few_own\": " << compare_.stats[5]
+      << ", \"most_candidates\": " << compare_.stats[6] << ", \"significant\": " << significant << ", \"significant_mean\": "
+      << num(significant ? sum / static_cast<double>(significant) : 0.0) << ", \"significant_min\": " << num(lo) << ", \"significant_max\": " << num(hi)
+      << "}\n";
+    f.close();
+    if (!f) throw std::runtime_error("Couldn't save the comparison of the map.");
+    std::cout << "Map comparison saved to: " << stem << "distance.npy, lod.npy, status.npy and compare.json, " << compare_.stats[1] << " of "
+              << compare_.stats[0] << " core points measured, " << compare_.stats[2] << " significant positive, " << compare_.stats[3]
+              << " negative, " << compare_.stats[4] << " without a counterpart" << std::endl;
+  }
+
   // --facets 1: the faces of the structure (DESIGN.md "Planar facets"): the map normals, the partition, the planes from the integers
   void writeFacets() {
     Device &dev = gpu->device(0);
@@ -2044,6 +2161,21 @@ class Processor {
     if (!f) throw std::runtime_error("Couldn't save the orthographic map's frame.");
     std::cout << "Orthographic map saved to: " << stem << "ortho_*.npy and ortho_frame.json, " << m.frame.width << " x " << m.frame.height
               << " pixels, " << m.occupied << " occupied, " << m.filled << " filled" << std::endl;
+    if (!opt.compare_map.empty()) {  // the comparison drawn on the map: distance[index], status[index]
+      std::vector<float> change(m.index.size(), 0.0f);
+      std::vector<uint8_t> change_status(m.index.size(), 0);
+      for (size_t p = 0; p < m.index.size(); ++p) {
+        if (m.index[p] == 0xFFFFFFFFu) continue;
+        if (m.index[p] >= compare_.status.size())
+          throw std::runtime_error("the orthographic map's index layer names row " + std::to_string(m.index[p]) + " of a map of " +
+                                   std::to_string(compare_.status.size()) + " points: the change layers cannot be drawn");
+        change[p] = compare_.distance[m.index[p]];
+        change_status[p] = compare_.status[m.index[p]];
+      }
+      writeNpy(stem + "change.npy", "<f4", {h, w}, change.data(), change.size() * 4);
+      writeNpy(stem + "change_status.npy", "|u1", {h, w}, change_status.data(), change_status.size());
+      std::cout << "Orthographic change layers saved to: " << stem << "change.npy, change_status.npy" << std::endl;
+    }
     if (opt.crack_fuse) ortho_index = std::move(m.index);
   }
 
@@ -2402,6 +2534,7 @@ class Processor {
         dev.check(pcp_colour_smooth_local(dev.get(), opt.smooth_colors_radius, &coloured));
       }
       reduceToVoxels();
+      if (!opt.compare_map.empty()) writeCompare();
       if (opt.facets) writeFacets();
       if (opt.ortho_map) opt.ortho_by_facet ? writeOrthoMapsByFacet() : writeOrthoMap();
       if (opt.crack_fuse) writeCrackFuse();
@@ -2419,6 +2552,7 @@ class Processor {
       gpu->smoothColorsWithLocalRegion(opt.smooth_colors_radius, rgb, has);
     }
     if (opt.output_leaf > 0.0f) reduceToVoxels();  // (of the colour result as it lies on the device now)
+    if (!opt.compare_map.empty()) writeCompare();   // (it reads the raw map; before --facets, whose partition ends with a new estimate of the normals)
     if (opt.facets) writeFacets();                  // (it reads the raw map; the colour result stays as it is)
     if (opt.ortho_map) opt.ortho_by_facet ? writeOrthoMapsByFacet() : writeOrthoMap();  // (likewise; before --crackFuse, whose layers it gathers by the index layer)
     if (opt.crack_fuse) writeCrackFuse();           // (it reads the raw map and the masks; the colour result stays as it is)

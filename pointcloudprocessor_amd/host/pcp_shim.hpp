@@ -99,6 +99,13 @@ struct CrackWidth {
 // The crack widths of a set of keyframes on the map, and the map's cracks (pcp_hip.h, "crack widths on the map"): per map
 // point in input order, and one row per crack, ascending by id
 // planar facets of the map (Device::facets; DESIGN.md, "Planar facets"): one row per face of the structure
+// what pcp_compare leaves per point of the uploaded map (DESIGN.md "Map comparison")
+struct MapComparison {
+  std::vector<float> distance, lod;  // metres; 0 where status < 3
+  std::vector<uint8_t> status;       // MC6
+  int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+
 struct Facets {
   int64_t facet_points = 0, components = 0;
   std::vector<int32_t> label;   // per map point: the facet's id (the lowest input index of its points), -1: in no facet
@@ -452,6 +459,24 @@ class Device {
     int64_t valid = 0;
     check(pcp_estimate_normals(ctx_, radius, &valid, nullptr));
     return valid;
+  }
+
+  // ---- map comparison: the uploaded map against `n_base` interleaved xyz rows of an earlier survey under the live normals
+  // (pcp_compare_set_base, pcp_compare and its fetch; the base is dropped again); needs estimateNormals
+  MapComparison compareMap(const pcp_compare_params &p, const float *base_xyz, int64_t n_base) {
+    MapComparison m;
+    const size_t n = static_cast<size_t>(cloudSize());
+    m.distance.resize(n);
+    m.lod.resize(n);
+    m.status.resize(n);
+    check(pcp_compare_set_base(ctx_, base_xyz, n_base, 12));
+    struct End {  // also on the way out of an exception
+      pcp_context *c;
+      ~End() { (void)pcp_compare_end(c); }
+    } end{ctx_};
+    check(pcp_compare(ctx_, &p, nullptr, m.stats));
+    check(pcp_compare_fetch(ctx_, m.distance.data(), m.lod.data(), m.status.data(), nullptr, nullptr));
+    return m;
   }
 
   // ---- planar facets: the faces of the uploaded map under the live normals (pcp_facets and its fetch); needs estimateNormals

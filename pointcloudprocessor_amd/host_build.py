@@ -20,6 +20,7 @@ TARGETS = {
     "k3_term_selftest": ["k3_term_selftest.cpp"],  # csrc/pcp_visit_forms.hpp, the form without the k3 term (CPU only)
     "voxel_reduce_selftest": ["voxel_reduce_selftest.cpp"],  # csrc/pcp_voxel_reduce.hpp compiled for the host (CPU only)
     "normals_selftest": ["normals_selftest.cpp"],  # csrc/pcp_normals.hpp compiled for the host (CPU only)
+    "compare_selftest": ["compare_selftest.cpp"],  # csrc/pcp_compare.hpp compiled for the host (CPU only)
     "ortho_selftest": ["ortho_selftest.cpp"],  # csrc/pcp_ortho.hpp compiled for the host (CPU only)
     "ortho_texture_selftest": ["ortho_texture_selftest.cpp"],  # csrc/pcp_ortho_texture.hpp compiled for the host (CPU only)
     "crack_width_selftest": ["crack_width_selftest.cpp"],  # csrc/pcp_crack_width.hpp compiled for the host (CPU only)

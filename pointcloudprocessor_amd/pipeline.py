@@ -60,6 +60,7 @@ class HipEngine:
 
         pos = np.asarray(poses, np.float64).reshape(-1, 7)[:, :3]
         self.mean_keyframe_position = pos.mean(axis=0) if len(pos) else None  # (the viewer of ortho_maps_by_facet's frames)
+        self.keyframe_positions = pos  # (compare_map's default viewer is their mean)
         if not (isinstance(balance, str) and balance == "keep"):
             self.ctx.set_image_balance(balance)
         if images is not None:
@@ -390,6 +391,42 @@ class PointCloudColorizer:
             ctx.estimate_normals(normal_radius)
         return ctx.frame_geometry(frame, normals=bool(normal_radius))
 
+    def compare_map(self, base_xyz, normal_radius: float = 0.1, radius: float = 0.03, half_length: float = 0.05, min_points: int = 5,
+                    reg_error: float = 0.0, viewer=None, normals=None) -> dict:
+        """The uploaded map against an earlier survey of the same structure ("Map comparison"): per map point the
+        signed distance along its normal to the points of base_xyz ((n_base, 3), or (x, y, z)) inside a cylinder of `radius` and
+        +-half_length, and the level of detection from the two epochs' scatter (Lague et al.'s M3C2).  Positive: the map lies
+        nearer the viewer than the base (deposit, bulge), negative: loss.  The normals are `normals` ((n, 3) float32), or the
+        map's own, estimated at normal_radius when none of that radius are live, and are turned towards `viewer` (None: the
+        fp64 mean of the keyframes' positions, each divided by their number and summed in order, rounded to float32; without
+        keyframes the normals keep their sign).  dict of capi.Context.compare: distance, lod, status, sums, direction, stats.
+        The base stays on the device until capi.Context.compare_end.  Base points the map has no counterpart for are found by
+        a second run with the roles swapped.
+
+        An index shard sees only its own points, so world > 1 raises ValueError."""
+        import numpy as np
+
+        if self.world > 1:
+            raise ValueError("compare_map: an index shard sees only its own points; the candidates of a point near a shard's edge "
+                             "lie with another rank, which is not built: run it on one rank holding the whole map")
+        ctx = self.engine.ctx
+        if isinstance(base_xyz, (tuple, list)) and len(base_xyz) == 3 and np.ndim(base_xyz[0]) == 1:
+            base_xyz = np.stack([np.asarray(a, np.float32) for a in base_xyz], axis=1)
+        base = np.asarray(base_xyz, np.float32).reshape(-1, 3)
+        if viewer is None:
+            poses = getattr(self.engine, "keyframe_positions", None)
+            if poses is not None and len(poses):
+                viewer = [0.0, 0.0, 0.0]
+                for p in poses:  # (the order of operations of the host program's mean)
+                    for a in range(3):
+                        viewer[a] += float(p[a]) / float(len(poses))
+        if normals is None and ctx.normals_radius != normal_radius:  # (None after an upload: the library dropped the estimate)
+            ctx.estimate_normals(normal_radius)
+        ctx.compare_set_base(base)
+        if viewer is None:
+            return ctx.compare(radius, half_length, reg_error, min_points, 0, (0.0, 0.0, 0.0), normals)
+        return ctx.compare(radius, half_length, reg_error, min_points, 1, tuple(np.asarray(viewer, np.float64).astype(np.float32)), normals)
+
     def crack_width(self, frame: int, threshold: int = 0, plane_radius: int = 150,
                     want=("flags", "edges", "w2d2", "width", "points", "plane")) -> dict:
         """The crack width maps of one keyframe at camera resolution, made on the device ("Crack width maps"): per
@@ -656,6 +693,17 @@ def ortho_crack_layers(index, map_width, map_crack) -> dict:
     at = np.where(empty, 0, index).astype(np.int64)
     return dict(width=np.where(empty, np.float32(0), np.asarray(map_width, np.float32)[at]).astype(np.float32),
                 crack=np.where(empty, -1, np.asarray(map_crack, np.int32)[at]).astype(np.int32))
+
+
+def ortho_change_layers(index, distance, status) -> dict:
+    """change (H, W) float32 and change_status (H, W) uint8 of an orthographic map from its index layer and the per-point arrays
+    of the map comparison: distance[index] and status[index], 0 on empty pixels."""
+    import numpy as np
+
+    empty = index == np.uint32(0xFFFFFFFF)
+    at = np.where(empty, 0, index).astype(np.int64)
+    return dict(change=np.where(empty, np.float32(0), np.asarray(distance, np.float32)[at]).astype(np.float32),
+                change_status=np.where(empty, 0, np.asarray(status, np.uint8)[at]).astype(np.uint8))
 
 
 def keyframe_block(n_frames: int, rank: int, world: int):
