@@ -9,128 +9,73 @@
 //     exact 64-bit integer sums, so the result does not depend on the order of the neighbours (LS4);
 //   - every output reads the unsmoothed words (LS5); has = (r | g | b) != 0 afterwards (LS6).
 //
-// Search: the finite points are binned into the uniform grid of the radius searches (pcp_grid.hip; cell >= r,
-// reach 1) and copied into cell order as 16-B records (x, y, z, word).  One wavefront-sized workgroup takes up to 64
-// queries of ONE cell (one query per lane); their candidates are the 9 rows of 3 neighbouring cells, each a contiguous run
-// of records, staged through LDS in tiles of kLsTile records and read back as wave-wide broadcasts.  A cell of any size is
-// walked tile by tile (an all-duplicate cloud is one cell).  Results are stored in the caller's order.
+// Search: the cell-wave search of pcp_cell_search.hpp over the finite points, the record's word the unsmoothed colour word.
+// Results are stored in the caller's order.
 #include <algorithm>
 #include <cmath>
 
+#include "pcp_cell_search.hpp"
 #include "pcp_internal.hpp"
 
 namespace pcp {
 
-constexpr int kLsBlock = 256;   // the 1-D helper kernels
-constexpr int kLsQ = 64;        // queries per work item: one wavefront, one cell
-constexpr int kLsTile = 512;    // candidate records per LDS tile (8 KiB: ~20 one-wave workgroups per CU hide the LDS latency)
-constexpr int kLsMaxRows = 25;  // (2 reach + 1)^2 rows of neighbouring cells, reach <= 2
+// the record's word is the unsmoothed colour word; dst[k] = the caller's index the result of place k goes to
+struct LsStage {
+  const int32_t *remap;
+  const uint32_t *words;
+  int32_t *dst;
+  __device__ uint32_t word(int64_t k, int32_t v) const {
+    const int32_t i = remap[v];
+    dst[k] = i;
+    return words[i];
+  }
+  __device__ bool opens(uint32_t) const { return true; }
+};
 
-static inline uint32_t ls_blocks(int64_t n) { return static_cast<uint32_t>(std::max<int64_t>(1, div_up(n, kLsBlock))); }
-
-// records in cell order: (x, y, z, unsmoothed word) and the caller's index the result goes to
-__global__ __launch_bounds__(kLsBlock) void k_ls_records(const float *__restrict__ gx, const float *__restrict__ gy,
-                                                         const float *__restrict__ gz, const int32_t *__restrict__ order,
-                                                         const int32_t *__restrict__ remap, int64_t m,
-                                                         const uint32_t *__restrict__ words, uint4 *__restrict__ rec,
-                                                         int32_t *__restrict__ dst) {
-  const int64_t k = static_cast<int64_t>(blockIdx.x) * kLsBlock + threadIdx.x;
-  if (k >= m) return;
-  const int32_t i = remap[order[k]];
-  rec[k] = make_uint4(__float_as_uint(gx[k]), __float_as_uint(gy[k]), __float_as_uint(gz[k]), words[i]);
-  dst[k] = i;
-}
-
-// place k opens a work item when it is the first place of its cell or kLsQ places after the previous opening
-__global__ __launch_bounds__(kLsBlock) void k_ls_items(const uint4 *__restrict__ rec, int64_t m, GridDesc g,
-                                                       const int32_t *__restrict__ start, uint8_t *__restrict__ flag) {
-  const int64_t k = static_cast<int64_t>(blockIdx.x) * kLsBlock + threadIdx.x;
-  if (k >= m) return;
-  const uint4 r = rec[k];
-  int32_t ix, iy, iz;
-  grid_coords(g, __uint_as_float(r.x), __uint_as_float(r.y), __uint_as_float(r.z), ix, iy, iz);
-  const int64_t first = cell_start(g, start, iz, iy, ix);
-  flag[k] = ((k - first) % kLsQ) == 0 ? 1 : 0;
-}
-
-// one work item: the queries k0 .. k0 + nq - 1 of one cell against the records of the neighbouring cells
-__global__ __launch_bounds__(kLsQ) void k_ls_smooth(const uint4 *__restrict__ rec, const int32_t *__restrict__ dst,
-                                                    const int32_t *__restrict__ items, GridDesc g,
-                                                    const int32_t *__restrict__ start, float t, uint32_t *__restrict__ out) {
-  __shared__ uint4 tile[kLsTile];
-  __shared__ int32_t row_b[kLsMaxRows], row_e[kLsMaxRows];
-  const int32_t k0 = items[blockIdx.x];
+// one work item: the queries k0 .. k0 + n - 1 of one cell against the records of the neighbouring cells
+__global__ __launch_bounds__(kCellQ) void k_ls_smooth(const uint4 *__restrict__ rec, const int32_t *__restrict__ dst,
+                                                      const int32_t *__restrict__ items, GridDesc g,
+                                                      const int32_t *__restrict__ start, float t, uint32_t *__restrict__ out) {
+  const CellItem it = cell_open(rec, items, g, start);
   const int lane = threadIdx.x;
-  int32_t ix, iy, iz;
-  {
-    const uint4 r0 = rec[k0];
-    grid_coords(g, __uint_as_float(r0.x), __uint_as_float(r0.y), __uint_as_float(r0.z), ix, iy, iz);
-  }
-  const int32_t nq = min(kLsQ, cell_start(g, start, iz, iy, ix + 1) - k0);
-  const bool active = lane < nq;
-  const uint4 q = rec[k0 + (active ? lane : 0)];
-  const float qx = __uint_as_float(q.x), qy = __uint_as_float(q.y), qz = __uint_as_float(q.z);
-  const int32_t R = g.reach, side = 2 * R + 1, rows = side * side;
-  if (lane < rows) {
-    const int32_t zz = iz + lane / side - R, yy = iy + lane % side - R;
-    int32_t b = 0, e = 0;
-    if (zz >= 0 && zz < g.nz && yy >= 0 && yy < g.ny) {
-      b = cell_start(g, start, zz, yy, max(ix - R, 0));
-      e = cell_start(g, start, zz, yy, min(ix + R, g.nx - 1) + 1);
-    }
-    row_b[lane] = b;
-    row_e[lane] = e;
-  }
-  __syncthreads();
+  const bool active = lane < it.n;
+  const float qx = __uint_as_float(it.q.x), qy = __uint_as_float(it.q.y), qz = __uint_as_float(it.q.z);
   // m_j <= 2^24 and c_j <= 255: every product fits 32 bits, the sums stay below 2^63 for fewer than 2^31 points
   uint64_t sm = 0, sr = 0, sg = 0, sb = 0;
-  for (int32_t row = 0; row < rows; ++row) {
-    const int32_t b = row_b[row], e = row_e[row];
-    for (int32_t t0 = b; t0 < e; t0 += kLsTile) {
-      const int32_t cnt = min(kLsTile, e - t0);
-      __syncthreads();  // the previous tile has been read by every lane
-      for (int32_t u = lane; u < cnt; u += kLsQ) tile[u] = rec[t0 + u];
-      __syncthreads();
-      if (active) {
-#pragma unroll 4
-        for (int32_t u = 0; u < cnt; ++u) {
-          const uint4 c = tile[u];
-          const float dx = __uint_as_float(c.x) - qx, dy = __uint_as_float(c.y) - qy, dz = __uint_as_float(c.z) - qz;
-          const float d2 = (dx * dx + dy * dy) + dz * dz;  // every operation rounded on its own (-ffp-contract=off)
-          if (d2 <= t) {
-            const float w = 1.0f / (1.0f + d2);
-            const uint32_t mw = static_cast<uint32_t>(w * 16777216.0f);  // exact: w is a multiple of 2^-24 in [0.5, 1]
-            sm += mw;
-            sr += mw * (c.w & 0xffu);
-            sg += mw * ((c.w >> 8) & 0xffu);
-            sb += mw * ((c.w >> 16) & 0xffu);
-          }
-        }
-      }
+  cell_walk(rec, g, start, it, active, [&](const uint4 &c) {
+    const float dx = __uint_as_float(c.x) - qx, dy = __uint_as_float(c.y) - qy, dz = __uint_as_float(c.z) - qz;
+    const float d2 = (dx * dx + dy * dy) + dz * dz;  // every operation rounded on its own (-ffp-contract=off)
+    if (d2 <= t) {
+      const float w = 1.0f / (1.0f + d2);
+      const uint32_t mw = static_cast<uint32_t>(w * 16777216.0f);  // exact: w is a multiple of 2^-24 in [0.5, 1]
+      sm += mw;
+      sr += mw * (c.w & 0xffu);
+      sg += mw * ((c.w >> 8) & 0xffu);
+      sb += mw * ((c.w >> 16) & 0xffu);
     }
-  }
+  });
   if (!active) return;
   // sm >= 2^24: the query is its own neighbour (d2 = 0, w = 1)
   const uint32_t r = static_cast<uint32_t>(sr / sm), gg = static_cast<uint32_t>(sg / sm), bb = static_cast<uint32_t>(sb / sm);
   const uint32_t has = (r | gg | bb) != 0u ? 1u : 0u;
-  out[dst[k0 + lane]] = r | (gg << 8) | (bb << 16) | (has << 24);
+  out[dst[it.k0 + lane]] = r | (gg << 8) | (bb << 16) | (has << 24);
 }
 
 // words with the has bit set: a grid-stride loop, one atomic per workgroup (one per wavefront on a single address
 // queued up in its L2 channel: 1.9 ms for 10 M words)
 constexpr uint32_t kLsCountBlocks = 1024;
-__global__ __launch_bounds__(kLsBlock) void k_ls_count_has(const uint32_t *__restrict__ words, int64_t n,
-                                                           unsigned long long *__restrict__ count) {
-  __shared__ uint32_t part[kLsBlock / 64];
+__global__ __launch_bounds__(kCellBlock) void k_ls_count_has(const uint32_t *__restrict__ words, int64_t n,
+                                                             unsigned long long *__restrict__ count) {
+  __shared__ uint32_t part[kCellBlock / 64];
   uint32_t c = 0;
-  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kLsBlock + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * kLsBlock)
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kCellBlock + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * kCellBlock)
     c += (words[i] >> 24) & 1u;
   for (int o = 32; o >= 1; o >>= 1) c += __shfl_xor(c, o, 64);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
   __syncthreads();
   if (threadIdx.x == 0) {
     unsigned long long t = 0;
-    for (int w = 0; w < kLsBlock / 64; ++w) t += part[w];
+    for (int w = 0; w < kCellBlock / 64; ++w) t += part[w];
     if (t) atomicAdd(count, t);
   }
 }
@@ -138,39 +83,24 @@ __global__ __launch_bounds__(kLsBlock) void k_ls_count_has(const uint32_t *__res
 // per-call scratch: released when the call returns (a 10 M-point map holds ~300 MB of it)
 struct LsScratch {
   FiniteScratch fin;  // (its flags serve the work items once the view is gathered)
-  DevBuf<int32_t> dst, items;
-  DevBuf<uint4> rec;
+  CellSearch search;
+  DevBuf<int32_t> dst;
 };
 
-// the m > 0 finite points of view cv: grid, records in cell order, work items, the smoothing pass into d_out
+// the m > 0 finite points of view cv: the search's records and work items, the smoothing pass into d_out
 static int smooth_finite(pcp_context *ctx, const CloudView &cv, float radius, float t, const uint32_t *d_in, uint32_t *d_out,
                          LsScratch &s) {
   const int64_t m = cv.n;
-  GridDesc g;
-  int rc = build_radius_grid(ctx, cv, radius, &g);
-  if (rc != PCP_OK) return rc;
-  if (g.reach < 1 || (2 * g.reach + 1) * (2 * g.reach + 1) > kLsMaxRows)
-    return set_error(ctx, PCP_ERR_INVALID, "local colour smoothing: grid reach %d outside 1..2", g.reach);
-  const size_t gplane = (static_cast<size_t>(m) + 3) & ~size_t(3);
-  DevBuf<uint8_t> &flag = s.fin.flag;
-  PCP_HIP_TRY(ctx, s.rec.ensure(static_cast<size_t>(m) + 4));
+  CellSearch &cs = s.search;
   PCP_HIP_TRY(ctx, s.dst.ensure(static_cast<size_t>(m) + 4));
-  PCP_HIP_TRY(ctx, flag.ensure(static_cast<size_t>(m) + 16));
-  PCP_HIP_TRY(ctx, s.items.ensure(static_cast<size_t>(m) + 4));
+  int rc = cell_search_prepare(ctx, cv, radius, "local colour smoothing", PCP_K_COLOUR_SMOOTH, LsStage{cv.remap, d_in, s.dst.p}, m,
+                               s.fin.flag, cs);
+  if (rc != PCP_OK) return rc;
   {
     LaunchTimer lt(ctx, PCP_K_COLOUR_SMOOTH);
-    hipLaunchKernelGGL(k_ls_records, dim3(ls_blocks(m)), dim3(kLsBlock), 0, ctx->stream, ctx->g_xyz.p, ctx->g_xyz.p + gplane,
-                       ctx->g_xyz.p + 2 * gplane, ctx->g_order.p, cv.remap, m, d_in, s.rec.p, s.dst.p);
-    hipLaunchKernelGGL(k_ls_items, dim3(ls_blocks(m)), dim3(kLsBlock), 0, ctx->stream, s.rec.p, m, g, ctx->g_start.p, flag.p);
-    PCP_HIP_TRY(ctx, hipGetLastError());
-  }
-  int64_t n_items = 0;
-  if ((rc = compact_flags(ctx, flag.p, m, s.items.p, m, &n_items)) != PCP_OK) return rc;
-  {
-    LaunchTimer lt(ctx, PCP_K_COLOUR_SMOOTH);
-    if (n_items > 0)
-      hipLaunchKernelGGL(k_ls_smooth, dim3(static_cast<uint32_t>(n_items)), dim3(kLsQ), 0, ctx->stream, s.rec.p, s.dst.p,
-                         s.items.p, g, ctx->g_start.p, t, d_out);
+    if (cs.n_items > 0)
+      hipLaunchKernelGGL(k_ls_smooth, dim3(static_cast<uint32_t>(cs.n_items)), dim3(kCellQ), 0, ctx->stream, cs.rec.p, s.dst.p,
+                         cs.items.p, cs.g, ctx->g_start.p, t, d_out);
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
   return PCP_OK;
@@ -198,7 +128,7 @@ int colour_smooth_words(pcp_context *ctx, float radius, const uint32_t *d_in, ui
   PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->s_counter.p, 0, 8, ctx->stream));
   {
     LaunchTimer lt(ctx, PCP_K_COLOUR_SMOOTH);
-    hipLaunchKernelGGL(k_ls_count_has, dim3(std::min(ls_blocks(n), kLsCountBlocks)), dim3(kLsBlock), 0, ctx->stream, d_out, n,
+    hipLaunchKernelGGL(k_ls_count_has, dim3(std::min(cell_blocks(n), kLsCountBlocks)), dim3(kCellBlock), 0, ctx->stream, d_out, n,
                        ctx->s_counter.p);
     PCP_HIP_TRY(ctx, hipGetLastError());
   }

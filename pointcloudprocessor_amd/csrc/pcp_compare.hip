@@ -2,18 +2,18 @@
 // signed distance along its oriented normal to an earlier survey (the base) inside a cylinder, with a level of detection from
 // the two epochs' scatter (Lague et al.'s M3C2).  The rule is pcp_compare.hpp's: exact int64 sums over the candidates of each
 // epoch, a fixed fp64 finish.
-// Search: as the normals (pcp_normals.hip) -- ONE uniform grid (build_radius_grid, cell >= search radius, reach <= 2) over both
-// clouds, the map's finite points first and the base's finite rows after them, 16-B records (x, y, z, the caller's index with
-// the epoch in the top bit) in cell order.  The grid keeps the view's order inside a cell, so a cell's map records come before
-// its base records: a work item is up to 64 MAP records of one cell, opened on map records only, one wavefront each.  The
-// records of the neighbouring cells are staged through LDS in tiles and read back as wave-wide broadcasts, one query per lane;
-// both epochs are accumulated in the same walk, selected by the (wave-uniform) epoch bit.  MC5 / MC6 finish in the same kernel.
+// Search: the cell-wave search of pcp_cell_search.hpp over ONE grid (cell >= search radius) for both clouds, the map's finite
+// points first and the base's finite rows after them, the record's word the caller's index with the epoch in the top bit.
+// The grid keeps the view's order inside a cell, so a cell's map records come before its base records: a work item is up to
+// 64 MAP records of one cell, opened on map records only.  Both epochs are accumulated in the same walk, selected by the
+// (wave-uniform) epoch bit.  MC5 / MC6 finish in the same kernel.
 #include <algorithm>
 #include <cmath>
 #include <new>
 #include <thread>
 #include <vector>
 
+#include "pcp_cell_search.hpp"
 #include "pcp_device.hpp"
 #include "pcp_internal.hpp"
 #include "pcp_normals.hpp"
@@ -21,23 +21,17 @@
 
 namespace pcp {
 
-constexpr int kMcBlock = 256;   // the 1-D helper kernels
-constexpr int kMcQ = 64;        // queries per work item: one wavefront, one cell
-constexpr int kMcTile = 512;    // candidate records per LDS tile (8 KiB)
-constexpr int kMcMaxRows = 25;  // (2 reach + 1)^2 rows of neighbouring cells, reach <= 2
 constexpr uint32_t kMcEpochBit = 0x80000000u;
 constexpr int64_t kMcMaxPoints = (int64_t(1) << 31) - 64;  // MC9: n + n_base
 
-static inline uint32_t mc_blocks(int64_t n) { return static_cast<uint32_t>(std::max<int64_t>(1, div_up(n, kMcBlock))); }
-
 // the two clouds as one view: the map's finite points (tag = caller's index), then the base's finite rows (tag has the epoch bit)
-__global__ __launch_bounds__(kMcBlock) void k_mc_concat(const float *__restrict__ ax, const float *__restrict__ ay,
-                                                        const float *__restrict__ az, const int32_t *__restrict__ aremap,
-                                                        int64_t ma, const float *__restrict__ bx, const float *__restrict__ by,
-                                                        const float *__restrict__ bz, const uint32_t *__restrict__ btag, int64_t mb,
-                                                        float *__restrict__ cx, float *__restrict__ cy, float *__restrict__ cz,
-                                                        uint32_t *__restrict__ ctag) {
-  const int64_t k = static_cast<int64_t>(blockIdx.x) * kMcBlock + threadIdx.x;
+__global__ __launch_bounds__(kCellBlock) void k_mc_concat(const float *__restrict__ ax, const float *__restrict__ ay,
+                                                          const float *__restrict__ az, const int32_t *__restrict__ aremap,
+                                                          int64_t ma, const float *__restrict__ bx, const float *__restrict__ by,
+                                                          const float *__restrict__ bz, const uint32_t *__restrict__ btag, int64_t mb,
+                                                          float *__restrict__ cx, float *__restrict__ cy, float *__restrict__ cz,
+                                                          uint32_t *__restrict__ ctag) {
+  const int64_t k = static_cast<int64_t>(blockIdx.x) * kCellBlock + threadIdx.x;
   if (k >= ma + mb) return;
   if (k < ma) {
     cx[k] = ax[k];
@@ -53,45 +47,26 @@ __global__ __launch_bounds__(kMcBlock) void k_mc_concat(const float *__restrict_
   }
 }
 
-// records in cell order; place k opens a work item when it is a map record and a multiple of kMcQ places after its cell's first
-// place (a cell's map records come first)
-__global__ __launch_bounds__(kMcBlock) void k_mc_records(const float *__restrict__ gx, const float *__restrict__ gy,
-                                                         const float *__restrict__ gz, const int32_t *__restrict__ order,
-                                                         const uint32_t *__restrict__ tag, int64_t m, GridDesc g,
-                                                         const int32_t *__restrict__ start, uint4 *__restrict__ rec,
-                                                         uint8_t *__restrict__ flag) {
-  const int64_t k = static_cast<int64_t>(blockIdx.x) * kMcBlock + threadIdx.x;
-  if (k >= m) return;
-  const float x = gx[k], y = gy[k], z = gz[k];
-  const uint32_t w = tag[order[k]];
-  rec[k] = make_uint4(__float_as_uint(x), __float_as_uint(y), __float_as_uint(z), w);
-  int32_t ix, iy, iz;
-  grid_coords(g, x, y, z, ix, iy, iz);
-  const int64_t first = cell_start(g, start, iz, iy, ix);
-  flag[k] = (!(w & kMcEpochBit) && ((k - first) % kMcQ) == 0) ? 1 : 0;
-}
+// the record's word is the tag; only a map record opens a work item (a cell's map records come first)
+struct McStage {
+  const uint32_t *tag;
+  __device__ uint32_t word(int64_t, int32_t v) const { return tag[v]; }
+  __device__ bool opens(uint32_t w) const { return !(w & kMcEpochBit); }
+};
 
-// one work item: the map records k0 .. of one cell (up to kMcQ) against the records of the neighbouring cells.
+// one work item: the map records k0 .. of one cell (up to kCellQ) against the records of the neighbouring cells.
 // tally[0..5] += core, measured, positive, negative, no counterpart, too few own; tally[6] = max(candidates of one epoch):
 // one atomic per counter per wavefront.
-__global__ __launch_bounds__(kMcQ) void k_mc_compare(const uint4 *__restrict__ rec, const int32_t *__restrict__ items, GridDesc g,
-                                                     const int32_t *__restrict__ start, mc::Rule rule,
-                                                     const float *__restrict__ normals, int32_t normal_stride,
-                                                     float *__restrict__ out_distance, float *__restrict__ out_lod,
-                                                     uint8_t *__restrict__ out_status, long long *__restrict__ out_sums,
-                                                     int32_t *__restrict__ out_direction, unsigned long long *__restrict__ tally) {
-  __shared__ uint4 tile[kMcTile];
-  __shared__ int32_t row_b[kMcMaxRows], row_e[kMcMaxRows];
-  const int32_t k0 = items[blockIdx.x];
+__global__ __launch_bounds__(kCellQ) void k_mc_compare(const uint4 *__restrict__ rec, const int32_t *__restrict__ items, GridDesc g,
+                                                       const int32_t *__restrict__ start, mc::Rule rule,
+                                                       const float *__restrict__ normals, int32_t normal_stride,
+                                                       float *__restrict__ out_distance, float *__restrict__ out_lod,
+                                                       uint8_t *__restrict__ out_status, long long *__restrict__ out_sums,
+                                                       int32_t *__restrict__ out_direction, unsigned long long *__restrict__ tally) {
+  const CellItem it = cell_open(rec, items, g, start);
   const int lane = threadIdx.x;
-  int32_t ix, iy, iz;
-  {
-    const uint4 r0 = rec[k0];
-    grid_coords(g, __uint_as_float(r0.x), __uint_as_float(r0.y), __uint_as_float(r0.z), ix, iy, iz);
-  }
-  const int32_t in_cell = min(kMcQ, cell_start(g, start, iz, iy, ix + 1) - k0);
-  const uint4 q = rec[k0 + (lane < in_cell ? lane : 0)];
-  const bool query = lane < in_cell && !(q.w & kMcEpochBit);  // (the cell's base records follow its map records)
+  const uint4 q = it.q;
+  const bool query = lane < it.n && !(q.w & kMcEpochBit);  // (the cell's base records follow its map records)
   const float qx = __uint_as_float(q.x), qy = __uint_as_float(q.y), qz = __uint_as_float(q.z);
   const int64_t i = static_cast<int64_t>(q.w & ~kMcEpochBit);
   mc::Direction dir{};
@@ -100,38 +75,13 @@ __global__ __launch_bounds__(kMcQ) void k_mc_compare(const uint4 *__restrict__ r
     const float *nrm = normals + i * normal_stride;
     core = mc::direction(rule, qx, qy, qz, nrm[0], nrm[1], nrm[2], dir);
   }
-  const int32_t R = g.reach, side = 2 * R + 1, rows = side * side;
-  if (lane < rows) {
-    const int32_t zz = iz + lane / side - R, yy = iy + lane % side - R;
-    int32_t b = 0, e = 0;
-    if (zz >= 0 && zz < g.nz && yy >= 0 && yy < g.ny) {
-      b = cell_start(g, start, zz, yy, max(ix - R, 0));
-      e = cell_start(g, start, zz, yy, min(ix + R, g.nx - 1) + 1);
-    }
-    row_b[lane] = b;
-    row_e[lane] = e;
-  }
-  __syncthreads();
   mc::Sums su;
   mc::clear(su);
   const float t = rule.t;
-  for (int32_t row = 0; row < rows; ++row) {
-    const int32_t b = row_b[row], e = row_e[row];
-    for (int32_t t0 = b; t0 < e; t0 += kMcTile) {
-      const int32_t cnt = min(kMcTile, e - t0);
-      __syncthreads();  // the previous tile has been read by every lane
-      for (int32_t u = lane; u < cnt; u += kMcQ) tile[u] = rec[t0 + u];
-      __syncthreads();
-      if (core) {
-#pragma unroll 4
-        for (int32_t u = 0; u < cnt; ++u) {
-          const uint4 c = tile[u];
-          // every operation rounded on its own (-ffp-contract=off); the integer part is 32 x 32 -> 64 multiply-adds
-          mc::visit(su, dir, t, __uint_as_float(c.x) - qx, __uint_as_float(c.y) - qy, __uint_as_float(c.z) - qz, c.w >> 31);
-        }
-      }
-    }
-  }
+  cell_walk(rec, g, start, it, core, [&](const uint4 &c) {
+    // every operation rounded on its own (-ffp-contract=off); the integer part is 32 x 32 -> 64 multiply-adds
+    mc::visit(su, dir, t, __uint_as_float(c.x) - qx, __uint_as_float(c.y) - qy, __uint_as_float(c.z) - qz, c.w >> 31);
+  });
   // MC5 / MC6 (a core point is its own candidate in epoch A: nA >= 1)
   mc::Result res;
   res.distance = res.lod = 0.0f;
@@ -170,8 +120,7 @@ struct McScratch {
   DevBuf<float> cxyz, normals;
   DevBuf<uint32_t> ctag;
   DevBuf<uint8_t> flag;
-  DevBuf<int32_t> items;
-  DevBuf<uint4> rec;
+  CellSearch search;
 };
 
 static int rule_of(const pcp_context *ctx, const char *who, const pcp_compare_params *p, mc::Rule *rule) {
@@ -196,7 +145,7 @@ static int compare_finite(pcp_context *ctx, const CloudView &cv, const mc::Rule 
   PCP_HIP_TRY(ctx, s.ctag.ensure(static_cast<size_t>(m) + 4));
   {
     LaunchTimer lt(ctx, PCP_K_MISC);
-    hipLaunchKernelGGL(k_mc_concat, dim3(mc_blocks(m)), dim3(kMcBlock), 0, ctx->stream, cv.x, cv.y, cv.z, cv.remap, ma, cs.base_xyz.p,
+    hipLaunchKernelGGL(k_mc_concat, dim3(cell_blocks(m)), dim3(kCellBlock), 0, ctx->stream, cv.x, cv.y, cv.z, cv.remap, ma, cs.base_xyz.p,
                        cs.base_xyz.p + pb, cs.base_xyz.p + 2 * pb, cs.base_tag.p, mb, s.cxyz.p, s.cxyz.p + pm, s.cxyz.p + 2 * pm,
                        s.ctag.p);
     PCP_HIP_TRY(ctx, hipGetLastError());
@@ -211,29 +160,16 @@ static int compare_finite(pcp_context *ctx, const CloudView &cv, const mc::Rule 
     both.mn[a] = mb > 0 ? std::min(cv.mn[a], cs.mn[a]) : cv.mn[a];
     both.mx[a] = mb > 0 ? std::max(cv.mx[a], cs.mx[a]) : cv.mx[a];
   }
-  GridDesc g;
-  int rc = build_radius_grid(ctx, both, rule.search_radius, &g);
+  CellSearch &search = s.search;
+  int rc = cell_search_prepare(ctx, both, rule.search_radius, "pcp_compare", PCP_K_MISC, McStage{s.ctag.p}, ma, s.flag, search);
   if (rc != PCP_OK) return rc;
-  if (g.reach < 1 || (2 * g.reach + 1) * (2 * g.reach + 1) > kMcMaxRows)
-    return set_error(ctx, PCP_ERR_INVALID, "pcp_compare: grid reach %d outside 1..2", g.reach);
-  PCP_HIP_TRY(ctx, s.rec.ensure(static_cast<size_t>(m) + 4));
-  PCP_HIP_TRY(ctx, s.flag.ensure(static_cast<size_t>(m) + 16));
-  PCP_HIP_TRY(ctx, s.items.ensure(static_cast<size_t>(ma) + 4));
-  {
-    LaunchTimer lt(ctx, PCP_K_MISC);
-    hipLaunchKernelGGL(k_mc_records, dim3(mc_blocks(m)), dim3(kMcBlock), 0, ctx->stream, ctx->g_xyz.p, ctx->g_xyz.p + pm,
-                       ctx->g_xyz.p + 2 * pm, ctx->g_order.p, s.ctag.p, m, g, ctx->g_start.p, s.rec.p, s.flag.p);
-    PCP_HIP_TRY(ctx, hipGetLastError());
-  }
-  int64_t n_items = 0;
-  if ((rc = compact_flags(ctx, s.flag.p, m, s.items.p, ma, &n_items)) != PCP_OK) return rc;
   PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->s_counter.p, 0, 64, ctx->stream));  // (compact_flags left its total there)
   {
     LaunchTimer lt(ctx, PCP_K_MISC);
-    if (n_items > 0)
-      hipLaunchKernelGGL(k_mc_compare, dim3(static_cast<uint32_t>(n_items)), dim3(kMcQ), 0, ctx->stream, s.rec.p, s.items.p, g,
-                         ctx->g_start.p, rule, d_normals, normal_stride, cs.distance.p, cs.lod.p, cs.status.p, cs.sums.p,
-                         cs.direction.p, ctx->s_counter.p);
+    if (search.n_items > 0)
+      hipLaunchKernelGGL(k_mc_compare, dim3(static_cast<uint32_t>(search.n_items)), dim3(kCellQ), 0, ctx->stream, search.rec.p,
+                         search.items.p, search.g, ctx->g_start.p, rule, d_normals, normal_stride, cs.distance.p, cs.lod.p,
+                         cs.status.p, cs.sums.p, cs.direction.p, ctx->s_counter.p);
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
   return PCP_OK;

@@ -2,9 +2,9 @@
 //
 // build_grid bins a cloud view into cells on the device: cell histogram -> exclusive scan -> scatter -> per-cell order
 // fix-up (so results do not depend on atomic arrival order).  It serves the MLS / SOR stages (pcp_mls.hip) and, through the
-// front end below, the stages that search a fixed radius around every point of the uploaded cloud: local colour smoothing
-// (pcp_colour_smooth.hip), normals (pcp_normals.hip), the neighbour table of PCP_MATCH_RADIUS (pcp_match.hip) and
-// pcp_close_pairs.  The front end: the uploaded cloud as a view (uploaded_view), its finite points as a view where it has
+// front end below, the stages that search a fixed radius around every point of the uploaded cloud: local colour smoothing,
+// normals and map comparison, whose search is written once in pcp_cell_search.hpp (a wavefront per cell), and the neighbour
+// table of PCP_MATCH_RADIUS (pcp_match.hip) and pcp_close_pairs, which walk the cells per lane.  The front end: the uploaded cloud as a view (uploaded_view), its finite points as a view where it has
 // others (finite_view: the grid needs finite coordinates), the grid with a density-limited cell (build_radius_grid) and
 // the rule that a huge sparse bitmap is not kept (drop_large_grid_bitmap).
 #include <algorithm>

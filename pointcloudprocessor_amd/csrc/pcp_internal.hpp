@@ -243,8 +243,9 @@ struct Facets {
   }
 };
 
-// ---- the uniform grid of the radius searches (pcp_grid.hip; read by the MLS / SOR kernels and by the radius stages:
-// local colour smoothing, normals, the neighbour table of PCP_MATCH_RADIUS, pcp_close_pairs) ----------------------------
+// ---- the uniform grid of the radius searches (pcp_grid.hip; read by the MLS / SOR kernels, by the cell-wave search of
+// local colour smoothing, normals and map comparison (pcp_cell_search.hpp), and by the per-lane walks of the neighbour table
+// of PCP_MATCH_RADIUS and pcp_close_pairs) ---------------------------------------------------------------------------------
 constexpr double kMaxGridCells = 536870912.0;      // 2^29: dense table of cell starts
 constexpr double kMaxSparseCells = 34359738368.0;  // 2^35: bitmap (4 GiB) + running popcounts (2 GiB)
 struct GridDesc {

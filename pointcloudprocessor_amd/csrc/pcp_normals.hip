@@ -7,9 +7,7 @@
 // (LS2's threshold); each accepted offset is quantised to 2^-20 m and the ten moments about the query are exact int64 sums
 // (pcp_normals.hpp), so they do not depend on the order of the neighbours, the grid or the input order.  The covariance is
 // three fp64 operations per entry, the normal pcl::eigen33's smallest eigenvector (pcp_eigen33.hpp).
-// Search: as the local colour smoothing (pcp_colour_smooth.hip) -- the uniform grid of pcp_mls.hip build_grid (cell >= r,
-// reach <= 2), 16-B records (x, y, z, caller's index) in cell order, one wavefront per work item of up to 64 queries of ONE
-// cell, the candidate rows staged through LDS in tiles and read back as wave-wide broadcasts, one query per lane.
+// Search: the cell-wave search of pcp_cell_search.hpp over the finite points, the record's word the caller's index.
 //
 // Maps: the contributors are the list pcp_frame_visible reports; each issues one 64-bit atomicMin of
 // (range bits << 32 | input index) on its colour pixel, so the nearest point wins, ties go to the lowest index, and the
@@ -20,6 +18,7 @@
 #include <thread>
 #include <vector>
 
+#include "pcp_cell_search.hpp"
 #include "pcp_device.hpp"
 #include "pcp_eigen33.hpp"
 #include "pcp_internal.hpp"
@@ -27,85 +26,30 @@
 
 namespace pcp {
 
-constexpr int kGnBlock = 256;   // the 1-D helper kernels
-constexpr int kGnQ = 64;        // queries per work item: one wavefront, one cell
-constexpr int kGnTile = 512;    // candidate records per LDS tile (8 KiB)
-constexpr int kGnMaxRows = 25;  // (2 reach + 1)^2 rows of neighbouring cells, reach <= 2
+// the record's word is the caller's index the result goes to
+struct GnStage {
+  const int32_t *remap;
+  __device__ uint32_t word(int64_t, int32_t v) const { return static_cast<uint32_t>(remap[v]); }
+  __device__ bool opens(uint32_t) const { return true; }
+};
 
-static inline uint32_t gn_blocks(int64_t n) { return static_cast<uint32_t>(std::max<int64_t>(1, div_up(n, kGnBlock))); }
-
-// records in cell order: (x, y, z, the caller's index the result goes to)
-__global__ __launch_bounds__(kGnBlock) void k_gn_records(const float *__restrict__ gx, const float *__restrict__ gy,
-                                                         const float *__restrict__ gz, const int32_t *__restrict__ order,
-                                                         const int32_t *__restrict__ remap, int64_t m, uint4 *__restrict__ rec) {
-  const int64_t k = static_cast<int64_t>(blockIdx.x) * kGnBlock + threadIdx.x;
-  if (k >= m) return;
-  rec[k] = make_uint4(__float_as_uint(gx[k]), __float_as_uint(gy[k]), __float_as_uint(gz[k]),
-                      static_cast<uint32_t>(remap[order[k]]));
-}
-
-// place k opens a work item when it is the first place of its cell or kGnQ places after the previous opening
-__global__ __launch_bounds__(kGnBlock) void k_gn_items(const uint4 *__restrict__ rec, int64_t m, GridDesc g,
-                                                       const int32_t *__restrict__ start, uint8_t *__restrict__ flag) {
-  const int64_t k = static_cast<int64_t>(blockIdx.x) * kGnBlock + threadIdx.x;
-  if (k >= m) return;
-  const uint4 r = rec[k];
-  int32_t ix, iy, iz;
-  grid_coords(g, __uint_as_float(r.x), __uint_as_float(r.y), __uint_as_float(r.z), ix, iy, iz);
-  const int64_t first = cell_start(g, start, iz, iy, ix);
-  flag[k] = ((k - first) % kGnQ) == 0 ? 1 : 0;
-}
-
-// one work item: the queries k0 .. k0 + nq - 1 of one cell against the records of the neighbouring cells.
+// one work item: the queries k0 .. k0 + n - 1 of one cell against the records of the neighbouring cells.
 // tally[0] += valid points, tally[1] = max(tally[1], neighbour count): one atomic of each per wavefront.
-__global__ __launch_bounds__(kGnQ) void k_gn_normals(const uint4 *__restrict__ rec, const int32_t *__restrict__ items, GridDesc g,
-                                                     const int32_t *__restrict__ start, float t, float4 *__restrict__ out_normal,
-                                                     int32_t *__restrict__ out_count, long long *__restrict__ out_moments,
-                                                     unsigned long long *__restrict__ tally) {
-  __shared__ uint4 tile[kGnTile];
-  __shared__ int32_t row_b[kGnMaxRows], row_e[kGnMaxRows];
-  const int32_t k0 = items[blockIdx.x];
+__global__ __launch_bounds__(kCellQ) void k_gn_normals(const uint4 *__restrict__ rec, const int32_t *__restrict__ items, GridDesc g,
+                                                       const int32_t *__restrict__ start, float t, float4 *__restrict__ out_normal,
+                                                       int32_t *__restrict__ out_count, long long *__restrict__ out_moments,
+                                                       unsigned long long *__restrict__ tally) {
+  const CellItem it = cell_open(rec, items, g, start);
   const int lane = threadIdx.x;
-  int32_t ix, iy, iz;
-  {
-    const uint4 r0 = rec[k0];
-    grid_coords(g, __uint_as_float(r0.x), __uint_as_float(r0.y), __uint_as_float(r0.z), ix, iy, iz);
-  }
-  const int32_t nq = min(kGnQ, cell_start(g, start, iz, iy, ix + 1) - k0);
-  const bool active = lane < nq;
-  const uint4 q = rec[k0 + (active ? lane : 0)];
+  const bool active = lane < it.n;
+  const uint4 q = it.q;
   const float qx = __uint_as_float(q.x), qy = __uint_as_float(q.y), qz = __uint_as_float(q.z);
-  const int32_t R = g.reach, side = 2 * R + 1, rows = side * side;
-  if (lane < rows) {
-    const int32_t zz = iz + lane / side - R, yy = iy + lane % side - R;
-    int32_t b = 0, e = 0;
-    if (zz >= 0 && zz < g.nz && yy >= 0 && yy < g.ny) {
-      b = cell_start(g, start, zz, yy, max(ix - R, 0));
-      e = cell_start(g, start, zz, yy, min(ix + R, g.nx - 1) + 1);
-    }
-    row_b[lane] = b;
-    row_e[lane] = e;
-  }
-  __syncthreads();
   gn::Moments mo;
   gn::clear(mo);
-  for (int32_t row = 0; row < rows; ++row) {
-    const int32_t b = row_b[row], e = row_e[row];
-    for (int32_t t0 = b; t0 < e; t0 += kGnTile) {
-      const int32_t cnt = min(kGnTile, e - t0);
-      __syncthreads();  // the previous tile has been read by every lane
-      for (int32_t u = lane; u < cnt; u += kGnQ) tile[u] = rec[t0 + u];
-      __syncthreads();
-      if (active) {
-#pragma unroll 4
-        for (int32_t u = 0; u < cnt; ++u) {
-          const uint4 c = tile[u];
-          // every operation rounded on its own (-ffp-contract=off); the S2 terms are 32 x 32 -> 64 multiply-adds
-          gn::visit(mo, __uint_as_float(c.x) - qx, __uint_as_float(c.y) - qy, __uint_as_float(c.z) - qz, t);
-        }
-      }
-    }
-  }
+  cell_walk(rec, g, start, it, active, [&](const uint4 &c) {
+    // every operation rounded on its own (-ffp-contract=off); the S2 terms are 32 x 32 -> 64 multiply-adds
+    gn::visit(mo, __uint_as_float(c.x) - qx, __uint_as_float(c.y) - qy, __uint_as_float(c.z) - qz, t);
+  });
   // GN5-GN7 (an active query is its own neighbour: n >= 1)
   float4 res = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   bool valid = false;
@@ -140,17 +84,17 @@ __global__ __launch_bounds__(kGnQ) void k_gn_normals(const uint4 *__restrict__ r
 // ---- geometry maps ------------------------------------------------------------------------------------------------------
 constexpr unsigned long long kGmEmpty = ~0ull;
 
-__global__ __launch_bounds__(kGnBlock) void k_gm_clear(unsigned long long *__restrict__ keys, int64_t px) {
-  const int64_t p = static_cast<int64_t>(blockIdx.x) * kGnBlock + threadIdx.x;
+__global__ __launch_bounds__(kCellBlock) void k_gm_clear(unsigned long long *__restrict__ keys, int64_t px) {
+  const int64_t p = static_cast<int64_t>(blockIdx.x) * kCellBlock + threadIdx.x;
   if (p < px) keys[p] = kGmEmpty;
 }
 
 // GM2: one atomicMin per contributor (the list of pcp_frame_visible: every entry has a colour pixel; the test stays as a bound)
-__global__ __launch_bounds__(kGnBlock) void k_gm_scatter(const float *__restrict__ x, const float *__restrict__ y,
-                                                         const float *__restrict__ z, DevCamera cam, DevFrame fr,
-                                                         const int32_t *__restrict__ index, int64_t m, int64_t px,
-                                                         unsigned long long *__restrict__ keys) {
-  const int64_t k = static_cast<int64_t>(blockIdx.x) * kGnBlock + threadIdx.x;
+__global__ __launch_bounds__(kCellBlock) void k_gm_scatter(const float *__restrict__ x, const float *__restrict__ y,
+                                                           const float *__restrict__ z, DevCamera cam, DevFrame fr,
+                                                           const int32_t *__restrict__ index, int64_t m, int64_t px,
+                                                           unsigned long long *__restrict__ keys) {
+  const int64_t k = static_cast<int64_t>(blockIdx.x) * kCellBlock + threadIdx.x;
   if (k >= m) return;
   const int32_t i = index[k];
   const Projected p = project_point(cam, fr.w2c, x[i], y[i], z[i]);
@@ -160,13 +104,13 @@ __global__ __launch_bounds__(kGnBlock) void k_gm_scatter(const float *__restrict
 }
 
 // GM3 / GM4: one lane per pixel; *occupied += pixels with a winner (one atomic per wavefront)
-__global__ __launch_bounds__(kGnBlock) void k_gm_resolve(const unsigned long long *__restrict__ keys, int64_t px,
-                                                         const float *__restrict__ x, const float *__restrict__ y,
-                                                         const float *__restrict__ z, DevFrame fr,
-                                                         const float4 *__restrict__ normals, int32_t *__restrict__ out_index,
-                                                         float *__restrict__ out_range, float *__restrict__ out_xyz,
-                                                         float *__restrict__ out_normal, unsigned long long *__restrict__ occupied) {
-  const int64_t p = static_cast<int64_t>(blockIdx.x) * kGnBlock + threadIdx.x;
+__global__ __launch_bounds__(kCellBlock) void k_gm_resolve(const unsigned long long *__restrict__ keys, int64_t px,
+                                                           const float *__restrict__ x, const float *__restrict__ y,
+                                                           const float *__restrict__ z, DevFrame fr,
+                                                           const float4 *__restrict__ normals, int32_t *__restrict__ out_index,
+                                                           float *__restrict__ out_range, float *__restrict__ out_xyz,
+                                                           float *__restrict__ out_normal, unsigned long long *__restrict__ occupied) {
+  const int64_t p = static_cast<int64_t>(blockIdx.x) * kCellBlock + threadIdx.x;
   bool hit = false;
   if (p < px) {
     const unsigned long long key = keys[p];
@@ -209,8 +153,7 @@ __global__ __launch_bounds__(kGnBlock) void k_gm_resolve(const unsigned long lon
 // per-call scratch: released when the call returns
 struct GnScratch {
   FiniteScratch fin;  // (its flags serve the work items once the view is gathered)
-  DevBuf<int32_t> items;
-  DevBuf<uint4> rec;
+  CellSearch search;
   DevBuf<long long> moments;
 };
 
@@ -221,34 +164,17 @@ void normals_release(pcp_context *ctx) {
   ctx->gn_count.release();
 }
 
-// the m > 0 finite points of view cv: grid, records in cell order, work items, the moments and the solve
+// the m > 0 finite points of view cv: the search's records and work items, the moments and the solve
 static int normals_finite(pcp_context *ctx, const CloudView &cv, float radius, float t, GnScratch &s) {
-  const int64_t m = cv.n;
-  GridDesc g;
-  int rc = build_radius_grid(ctx, cv, radius, &g);
+  CellSearch &cs = s.search;
+  int rc = cell_search_prepare(ctx, cv, radius, "pcp_estimate_normals", PCP_K_MISC, GnStage{cv.remap}, cv.n, s.fin.flag, cs);
   if (rc != PCP_OK) return rc;
-  if (g.reach < 1 || (2 * g.reach + 1) * (2 * g.reach + 1) > kGnMaxRows)
-    return set_error(ctx, PCP_ERR_INVALID, "pcp_estimate_normals: grid reach %d outside 1..2", g.reach);
-  const size_t gplane = (static_cast<size_t>(m) + 3) & ~size_t(3);
-  DevBuf<uint8_t> &flag = s.fin.flag;
-  PCP_HIP_TRY(ctx, s.rec.ensure(static_cast<size_t>(m) + 4));
-  PCP_HIP_TRY(ctx, flag.ensure(static_cast<size_t>(m) + 16));
-  PCP_HIP_TRY(ctx, s.items.ensure(static_cast<size_t>(m) + 4));
-  {
-    LaunchTimer lt(ctx, PCP_K_MISC);
-    hipLaunchKernelGGL(k_gn_records, dim3(gn_blocks(m)), dim3(kGnBlock), 0, ctx->stream, ctx->g_xyz.p, ctx->g_xyz.p + gplane,
-                       ctx->g_xyz.p + 2 * gplane, ctx->g_order.p, cv.remap, m, s.rec.p);
-    hipLaunchKernelGGL(k_gn_items, dim3(gn_blocks(m)), dim3(kGnBlock), 0, ctx->stream, s.rec.p, m, g, ctx->g_start.p, flag.p);
-    PCP_HIP_TRY(ctx, hipGetLastError());
-  }
-  int64_t n_items = 0;
-  if ((rc = compact_flags(ctx, flag.p, m, s.items.p, m, &n_items)) != PCP_OK) return rc;
   PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->s_counter.p, 0, 16, ctx->stream));  // (compact_flags left its total there)
   {
     LaunchTimer lt(ctx, PCP_K_MISC);
-    if (n_items > 0)
-      hipLaunchKernelGGL(k_gn_normals, dim3(static_cast<uint32_t>(n_items)), dim3(kGnQ), 0, ctx->stream, s.rec.p, s.items.p, g,
-                         ctx->g_start.p, t, reinterpret_cast<float4 *>(ctx->gn_normal.p), ctx->gn_count.p, s.moments.p,
+    if (cs.n_items > 0)
+      hipLaunchKernelGGL(k_gn_normals, dim3(static_cast<uint32_t>(cs.n_items)), dim3(kCellQ), 0, ctx->stream, cs.rec.p, cs.items.p,
+                         cs.g, ctx->g_start.p, t, reinterpret_cast<float4 *>(ctx->gn_normal.p), ctx->gn_count.p, s.moments.p,
                          ctx->s_counter.p);
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
@@ -317,11 +243,11 @@ int frame_geometry_device(pcp_context *ctx, const char *who, int32_t frame, bool
   const DevFrame &fr = ctx->hframes[static_cast<size_t>(frame)];
   {
     LaunchTimer lt(ctx, PCP_K_MISC);
-    hipLaunchKernelGGL(k_gm_clear, dim3(gn_blocks(px)), dim3(kGnBlock), 0, ctx->stream, ctx->gm_keys.p, px);
+    hipLaunchKernelGGL(k_gm_clear, dim3(cell_blocks(px)), dim3(kCellBlock), 0, ctx->stream, ctx->gm_keys.p, px);
     if (m > 0)
-      hipLaunchKernelGGL(k_gm_scatter, dim3(gn_blocks(m)), dim3(kGnBlock), 0, ctx->stream, x, y, z, ctx->dcam, fr, ctx->s_cell.p, m, px,
+      hipLaunchKernelGGL(k_gm_scatter, dim3(cell_blocks(m)), dim3(kCellBlock), 0, ctx->stream, x, y, z, ctx->dcam, fr, ctx->s_cell.p, m, px,
                          ctx->gm_keys.p);
-    hipLaunchKernelGGL(k_gm_resolve, dim3(gn_blocks(px)), dim3(kGnBlock), 0, ctx->stream, ctx->gm_keys.p, px, x, y, z, fr,
+    hipLaunchKernelGGL(k_gm_resolve, dim3(cell_blocks(px)), dim3(kCellBlock), 0, ctx->stream, ctx->gm_keys.p, px, x, y, z, fr,
                        with_normals ? reinterpret_cast<const float4 *>(ctx->gn_normal.p) : nullptr, d_index, d_range, d_xyz,
                        d_normal, ctx->s_counter.p);
     PCP_HIP_TRY(ctx, hipGetLastError());
