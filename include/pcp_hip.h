@@ -1572,6 +1572,19 @@ int pcp_selftest_visit_forms(pcp_context *ctx, int64_t samples, uint64_t seed, i
  * x, y), and counts the triples whose verdicts of the two truncation rules, cell, pixel or -- where a rule accepts -- (u, v)
  * differ.  The count must be 0.  term_dropped: 1 when the configured camera lets the term go (0: the passes keep it). */
 int pcp_selftest_k3_term(pcp_context *ctx, int64_t samples, uint64_t seed, int64_t *mismatches, int32_t *term_dropped);
+/* diagnostic: the plane of four stages is the eigenvector of the smallest eigenvalue of a symmetric 3 x 3 matrix, found in
+ * closed form (pcl::eigen33) by device-only code that rests on two short fp64 reciprocal sequences (csrc/pcp_eigen33.hpp).  This
+ * runs that code on the caller's inputs, one lane per item, and returns what it returns, NaNs and infinities included:
+ * n matrices as 6 n doubles in the order xx xy xz yy yz zz -> out_ev[n] (the eigenvalue) and out_vec[3 n] (its unit vector, three
+ * NaNs where the cross products of two rows are zero or rounding noise: no plane is defined); m arguments -> out_rcp[m] and out_rsqrt[m] (1 / x and 1 / sqrt(x) to two
+ * ulp for normal x with a normal result; zero, a negative argument of the root, infinities and NaN give non-finite values).
+ * form 0: the code as the map normals compile it, without floating-point contraction -- which is also how the crack-width
+ * plane and the crack tangent are built, so this form stands for those two units as well.  form 1: as the MLS fit compiles it,
+ * with contraction.  Needs no camera and no cloud and changes no state of the context.  PCP_ERR_INVALID: another form, a
+ * negative count or one above 2^27, a NULL array with a count above 0.  The caller compares with a reference of its own
+ * (tests/test_eigen33_gpu.py: mpmath at 50 digits). */
+int pcp_selftest_eigen33(pcp_context *ctx, int32_t form, int64_t n, const double *matrices, double *out_ev, double *out_vec, int64_t m,
+                         const double *args, double *out_rcp, double *out_rsqrt);
 
 #ifdef __cplusplus
 }

@@ -2291,6 +2291,19 @@ class Context:
         self._check(self.lib.pcp_selftest_k3_term(self.h, C.c_int64(samples), C.c_uint64(seed), C.byref(a), C.byref(f)))
         return a.value, bool(f.value)
 
+    def selftest_eigen33(self, form: int, matrices=None, args=None):
+        """The device's smallest_eigenpair, mls_rcp and mls_rsqrt on the caller's inputs (pcp_selftest_eigen33).  matrices
+        (n, 6) float64 in the order xx xy xz yy yz zz, args (m,) float64, either may be None; form 0 = built without
+        contraction (map normals, crack width, crack direction), 1 = with (MLS fit).  Returns (ev (n,), vec (n, 3), rcp (m,),
+        rsqrt (m,)), NaNs and infinities as the device produced them."""
+        mat = np.zeros((0, 6)) if matrices is None else np.ascontiguousarray(matrices, np.float64).reshape(-1, 6)
+        arg = np.zeros(0) if args is None else np.ascontiguousarray(args, np.float64).reshape(-1)
+        n, m = len(mat), len(arg)
+        ev, vec, rcp, rsq = np.zeros(n), np.zeros((n, 3)), np.zeros(m), np.zeros(m)
+        self._check(self.lib.pcp_selftest_eigen33(self.h, C.c_int32(form), C.c_int64(n), _ptr(mat), _ptr(ev), _ptr(vec), C.c_int64(m),
+                                                  _ptr(arg), _ptr(rcp), _ptr(rsq)))
+        return ev, vec, rcp, rsq
+
     def tile_masks(self) -> np.ndarray:
         """(tiles, mask_words) uint32: the tile x keyframe masks as the last depth pass left them."""
         t, w = C.c_int64(), C.c_int32()

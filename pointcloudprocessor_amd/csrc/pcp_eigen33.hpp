@@ -1,7 +1,9 @@
 // pcp_eigen33.hpp -- pcl::eigen33's smallest eigenpair in closed form and the two fp64 reciprocals it rests on, for the
-// kernels that fit a plane to a neighbourhood: the MLS fit (pcp_mls.hip) and the map normals (pcp_normals.hip).  Device
-// only.  Floating-point contraction is the includer's: pcp_mls.hip allows it (tolerance-gated stage), pcp_normals.hip
-// is built without.
+// kernels that fit a plane to a neighbourhood: the MLS fit (pcp_mls.hip), the map normals (pcp_normals.hip), the crack-width
+// plane (pcp_crack_width.hip) and the crack tangent (pcp_crack_direction.hip).  Device only.  Floating-point contraction is
+// the includer's: pcp_mls.hip allows it (tolerance-gated stage), the other three are built without.
+// pcp_selftest_eigen33 (pcp_eigen33_selftest.hpp) runs these functions on a caller's input in both compilations;
+// tests/test_eigen33_gpu.py holds them to mpmath at 50 digits, tests/_eigen33_ref.py is the plain fp64 restatement.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -15,6 +17,8 @@ namespace pcp {
 // residual correction and the special-case fix-ups of the IEEE sequences (~8 instead of ~28 instructions).  For the fit's own
 // arithmetic (tolerance-gated against the oracle: 3 um, 1e-4), whose operands are covariances, lengths and pivots -- normal
 // numbers; zero, negative and non-finite arguments give infinities / NaNs that the callers' guards (ok, isfinite) catch as before.
+// Measured on 2^k (1 + f), k in [-1000, 1000] (10^6 arguments, both signs for 1 / x): mls_rcp returned the correctly rounded
+// value every time, mls_rsqrt is within 1 ulp of it (the test's bar is the 2 ulp claimed here).
 __device__ __forceinline__ double mls_rcp(double x) {
   double r = __builtin_amdgcn_rcp(x);
   double e = __builtin_fma(-x, r, 1.0);
@@ -43,6 +47,9 @@ __device__ __forceinline__ void swap2(double &a, double &b) {
   a = b;
   b = t;
 }
+
+// the longest cross product of two rows of A - r0 I counts as a direction above this multiple of the squared largest entry
+constexpr double kCrossNoise = 256.0 * DBL_EPSILON;
 
 // (inlined: as a call it cost the kernel 96 bytes of scratch per lane and a save / restore around it -- fit 4.25 -> 4.12 ms)
 __device__ __forceinline__ void smallest_eigenpair(const double m[6] /* xx xy xz yy yz zz */, double &ev, double n[3]) {
@@ -95,7 +102,16 @@ __device__ __forceinline__ void smallest_eigenpair(const double m[6] /* xx xy xz
   if (l2 > l) {
     vx = k2x; vy = k2y; vz = k2z; l = l2;
   }
-  const double inv_len = mls_rsqrt(l);  // (l == 0: infinity, the components NaN as with the division by zero)
+  // A cross product at the rounding of its own terms is no direction.  Each component is a difference of two products of
+  // entries of A - r0 I, which carry the error of r0 (a few ulp of the trace) and their own roundings: below ~50 ulp of the
+  // squared largest entry the longest cross product is noise, and its unit vector need not lie anywhere near the null space
+  // (a neighbourhood of two distinct positions, an exact needle l0 = l1: residual |A n - ev n| / l2 of order 1, reported as a
+  // valid normal; tests/test_eigen33_cpu.py, profiles/eigen33_selftest.md).  Such a vector is NaN like that of l == 0, which
+  // the callers' guards (isfinite) already catch.  Where a plane is defined the ratio is above 1e-5 -- (l1 - l0) / l2 of the
+  // neighbourhood, within a factor of 9 -- and nothing changes; quantised lines (1e-11 and more) keep their normal too.
+  double big = fmax(fmax(fmax(fabs(s00), fabs(s11)), fmax(fabs(s22), fabs(a01))), fmax(fabs(a02), fabs(a12)));
+  big *= big;
+  const double inv_len = l > (kCrossNoise * kCrossNoise) * (big * big) ? mls_rsqrt(l) : NAN;  // (l == 0 and l NaN: NaN as before)
   n[0] = vx * inv_len;
   n[1] = vy * inv_len;
   n[2] = vz * inv_len;

@@ -30,6 +30,7 @@
 #pragma clang fp contract(fast)
 
 #include "pcp_eigen33.hpp"  // (after the pragma: the closed form contracts here as it did when its text stood in this file)
+#include "pcp_eigen33_selftest.hpp"
 
 namespace pcp {
 
@@ -429,6 +430,18 @@ __global__ __launch_bounds__(kFitBlock) void k_mls_fit(MlsArgs a) {
     st[20] = fitted ? 2.0 : 1.0;  // 0 invalid, 1 valid plane only, 2 polynomial fitted
     st[21] = 0.0;
   }
+}
+
+// pcp_selftest_eigen33, form 1: the solver and the two reciprocals as k_mls_fit above compiles them (under the contraction
+// pragma at the top of this file), one lane per item
+__global__ __launch_bounds__(kMB) void k_selftest_eigen33_contracted(Eigen33SelftestArgs a) {
+  eigen33_selftest_lane(a, static_cast<int64_t>(blockIdx.x) * kMB + threadIdx.x);
+}
+
+void selftest_eigen33_launch_contracted(const Eigen33SelftestArgs &a, hipStream_t stream) {
+  const int64_t lanes = std::max(a.n, a.m);
+  if (lanes > 0)
+    hipLaunchKernelGGL(k_selftest_eigen33_contracted, dim3(static_cast<uint32_t>((lanes + kMB - 1) / kMB)), dim3(kMB), 0, stream, a);
 }
 
 // pcp_close_pairs: per point, is there ANOTHER map point closer than r (fp32 L2_Simple distance, strict <)?

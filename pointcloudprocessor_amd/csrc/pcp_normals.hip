@@ -21,6 +21,7 @@
 #include "pcp_cell_search.hpp"
 #include "pcp_device.hpp"
 #include "pcp_eigen33.hpp"
+#include "pcp_eigen33_selftest.hpp"
 #include "pcp_internal.hpp"
 #include "pcp_normals.hpp"
 
@@ -79,6 +80,13 @@ __global__ __launch_bounds__(kCellQ) void k_gn_normals(const uint4 *__restrict__
 #pragma unroll
     for (int a = 0; a < gn::kMomentWords; ++a) out_moments[i * gn::kMomentWords + a] = w[a];
   }
+}
+
+// pcp_selftest_eigen33, form 0: the solver and the two reciprocals as k_gn_normals above compiles them (no contraction: the
+// flags of the build; pcp_crack_width.hip and pcp_crack_direction.hip include the same text under the same flags), one lane
+// per item
+__global__ __launch_bounds__(kCellBlock) void k_selftest_eigen33_plain(Eigen33SelftestArgs a) {
+  eigen33_selftest_lane(a, static_cast<int64_t>(blockIdx.x) * kCellBlock + threadIdx.x);
 }
 
 // ---- geometry maps ------------------------------------------------------------------------------------------------------
@@ -309,6 +317,51 @@ int pcp_normals_fetch(pcp_context *ctx, float *out_normal, float *out_curvature,
     }
     if (out_curvature) out_curvature[i] = rows[4 * i + 3];
   }
+  return PCP_OK;
+}
+
+int pcp_selftest_eigen33(pcp_context *ctx, int32_t form, int64_t n, const double *matrices, double *out_ev, double *out_vec, int64_t m,
+                         const double *args, double *out_rcp, double *out_rsqrt) {
+  if (!ctx) return PCP_ERR_INVALID;
+  if (form != 0 && form != 1) return set_error(ctx, PCP_ERR_INVALID, "pcp_selftest_eigen33: form %d is neither 0 nor 1", static_cast<int>(form));
+  constexpr int64_t kMost = int64_t(1) << 27;  // (the grid of one launch and a few GB of scratch)
+  if (n < 0 || m < 0 || n > kMost || m > kMost)
+    return set_error(ctx, PCP_ERR_INVALID, "pcp_selftest_eigen33: a count outside 0..2^27 (%lld matrices, %lld arguments)",
+                     static_cast<long long>(n), static_cast<long long>(m));
+  if (n > 0 && (!matrices || !out_ev || !out_vec)) return set_error(ctx, PCP_ERR_INVALID, "pcp_selftest_eigen33: %lld matrices and a missing array", static_cast<long long>(n));
+  if (m > 0 && (!args || !out_rcp || !out_rsqrt)) return set_error(ctx, PCP_ERR_INVALID, "pcp_selftest_eigen33: %lld arguments and a missing array", static_cast<long long>(m));
+  if (n == 0 && m == 0) return PCP_OK;
+  PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // per-call scratch, released on return: in (6 n | m), out (n | 3 n | m | m); nothing of the context's is touched
+  const size_t sn = static_cast<size_t>(n), sm = static_cast<size_t>(m);
+  DevBuf<double> in, out;
+  PCP_HIP_TRY(ctx, in.ensure(6 * sn + sm));
+  PCP_HIP_TRY(ctx, out.ensure(4 * sn + 2 * sm));
+  if (n > 0) PCP_HIP_TRY(ctx, hipMemcpyAsync(in.p, matrices, 6 * sn * 8, hipMemcpyHostToDevice, ctx->stream));
+  if (m > 0) PCP_HIP_TRY(ctx, hipMemcpyAsync(in.p + 6 * sn, args, sm * 8, hipMemcpyHostToDevice, ctx->stream));
+  Eigen33SelftestArgs a;
+  a.mat = in.p;
+  a.ev = out.p;
+  a.vec = out.p + sn;
+  a.n = n;
+  a.arg = in.p + 6 * sn;
+  a.rcp = out.p + 4 * sn;
+  a.rsqrt = out.p + 4 * sn + sm;
+  a.m = m;
+  if (form == 0)
+    hipLaunchKernelGGL(k_selftest_eigen33_plain, dim3(cell_blocks(std::max(n, m))), dim3(kCellBlock), 0, ctx->stream, a);
+  else
+    selftest_eigen33_launch_contracted(a, ctx->stream);
+  PCP_HIP_TRY(ctx, hipGetLastError());
+  if (n > 0) {
+    PCP_HIP_TRY(ctx, hipMemcpyAsync(out_ev, a.ev, sn * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PCP_HIP_TRY(ctx, hipMemcpyAsync(out_vec, a.vec, 3 * sn * 8, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (m > 0) {
+    PCP_HIP_TRY(ctx, hipMemcpyAsync(out_rcp, a.rcp, sm * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PCP_HIP_TRY(ctx, hipMemcpyAsync(out_rsqrt, a.rsqrt, sm * 8, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return PCP_OK;
 }
 
