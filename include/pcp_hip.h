@@ -95,6 +95,10 @@ extern "C" {
                                 (surface defects on ortho maps; nothing runs unless called);
                                 entry points added, no layout changed: pcp_default_compare_params, pcp_compare_set_base,
                                 pcp_compare / _fetch / _host / _end (map comparison with an earlier survey; nothing runs unless
+                                called);
+                                entry points added, no layout changed: pcp_default_register_params, pcp_compare_register /
+                                _register_sums / _register_host, pcp_compare_base_transform, pcp_compare_set_base_transform,
+                                pcp_register_solve_host (registration of the earlier survey onto the map; nothing runs unless
                                 called) */
 
 #define PCP_OK 0
@@ -1061,6 +1065,63 @@ int pcp_compare_host(const pcp_compare_params *p, int64_t n, const float *xyz, c
                      const float *base_xyz, float *out_distance, float *out_lod, uint8_t *out_status, int64_t *out_sums8,
                      int32_t *out_direction3, int64_t out_stats[8]);
 int pcp_compare_end(pcp_context *ctx);
+
+/* ---- map registration (no counterpart in the reference; the method is point-to-plane ICP, Chen & Medioni 1992) ------------- */
+/* Fine registration of the base of the map comparison onto the uploaded map, before pcp_compare measures the change
+ * ("Map registration", RG1-RG9).  Opt-in: nothing runs unless one of these is called, PCP_ABI_VERSION is unchanged
+ * and a caller detects support by the symbols.  Kernels are timed under PCP_K_MISC.  Whole-map contexts only.
+ *
+ * State: the context keeps the base's original rows and a rigid transform T, the identity after pcp_compare_set_base:
+ * x' = R (x - c) + c + t with R from a unit quaternion (fp64), c the midpoint of the box of the base's finite rows,
+ * (min + max) * 0.5 per axis in fp64, and ell half that box's diagonal (1 for a box without extent).  The rows pcp_compare
+ * sees are fl32 of that, computed in fp64 from the ORIGINAL rows in a fixed order (csrc/pcp_register.hpp, apply); with T the
+ * identity they are the original bytes.  A call that changes T drops a compare result.
+ * pcp_compare_register_sums: one evaluation at the current T.  Queries: the finite base rows whose row index is a multiple
+ * of sample_stride.  The partner of row b' is the finite map point p_j with the least fl32((dx*dx + dy*dy) + dz*dz), d =
+ * fl32(p_j - b'), ties to the lowest index, if that is <= t (t the largest float with (double)t <= (double)match_radius^2);
+ * no partner, or a partner whose normal is invalid (as in pcp_compare), is no pair.  `normals` as in pcp_compare.  With N_a
+ * = rint(n_a * 2^11), q = rint(d * 2^20), h = q.N, N2 = N.N, u_a = rint((b'_a - c_a) * 2^8) and g = (u x N, N), the pair
+ * counts iff h*h <= tau2 * N2, tau2 = floor((max_plane_distance * 2^20)^2).  Its thirty terms -- g_a g_b (a <= b, row by
+ * row), g_a h, h h, N2, 1 -- are summed over all pairs, term k as out_sums60[2 k] = sum of (term mod 2^32) and
+ * out_sums60[2 k + 1] = sum of (term div 2^32, arithmetic).  0.005 <= match_radius <= 0.5, 0 < max_plane_distance <=
+ * match_radius, sample_stride >= 1, 1 <= max_iterations <= 1000, min_pairs >= 1, 0 <= tolerance <= 1, 0 < cond_tol < 1: else
+ * PCP_ERR_INVALID.  A base whose current box reaches beyond |u_a| = 2^18 (1024 m from c): PCP_ERR_RANGE.  Without a cloud,
+ * a base or normals: PCP_ERR_STATE.  Like every call that builds the search grid it invalidates an open pcp_mls_stream /
+ * pcp_cloud_smooth_stream and a pcp_sor_partial; it touches nothing else.
+ * pcp_register_solve_host: host only.  The update from the sums in fp64, every operation rounded on its own: the 6 x 6
+ * normal equations with the rotation columns scaled by 1 / (2^19 ell) and the others by 2^-11, cyclic Jacobi (12 sweeps,
+ * pairs p < q row by row, t = sign / (|theta| + sqrt(theta^2 + 1))), the solution in the span of the eigenvectors with
+ * lambda_k > 0 and lambda_k >= cond_tol * lambda_max; *out_dof their number.  out_update7: omega (rad), dt (m), and rms =
+ * sqrt(sum h^2 / sum N2) / 2^20 (m).  out_eigenvalues6 in the order of the diagonal.  Outputs nullable.
+ * pcp_compare_register: the loop.  Per iteration: the sums at T; fewer than min_pairs pairs ends it with status 2 and T as
+ * it was before that iteration; else the update is composed onto T (quaternion normalise(1, omega / 2), renormalised) and
+ * the loop ends with status 0 when |omega| ell and |dt| are both below tolerance, or with status 1 after max_iterations.
+ * out_T16: row-major 4 x 4.  out_log: max_iterations rows of 5 doubles (pairs, rms, dof, |omega| ell, |dt|), zeros after the
+ * last.  out_status: the status, the rows written.  The rms of the last row is what a caller may pass as reg_error; nothing
+ * applies it.  An error leaves T as it was.
+ * pcp_compare_base_transform: T as a 4 x 4, the pivot, ell (each nullable).  pcp_compare_set_base_transform: a caller's rigid
+ * 4 x 4 (last row 0 0 0 1, rotation orthonormal to 1e-9, det > 0: else PCP_ERR_INVALID); the identity restores the original
+ * bytes.  Both need a base (PCP_ERR_STATE).
+ * pcp_compare_register_host: host only, no context, no GPU: the same by brute force over the pairs with the arithmetic the
+ * kernels use; n, n_base <= 65536, arrays interleaved.  T_in16 NULL: the identity.  run_loop 0: one evaluation at T_in
+ * (out_sums60); else the loop from T_in (out_sums60: the last evaluation).  out_rows (nullable): the 3 n_base current rows
+ * at the final T.  It also asserts the ranges of every pair in 128-bit arithmetic.  The message is at pcp_last_error(NULL). */
+typedef struct pcp_register_params {
+  float match_radius, max_plane_distance;
+  int32_t sample_stride, max_iterations, min_pairs;
+  double tolerance, cond_tol;
+} pcp_register_params;
+void pcp_default_register_params(pcp_register_params *p); /* 0.05, 0.02, 1, 20, 100, 1e-5, 6.2e-3 */
+int pcp_compare_register_sums(pcp_context *ctx, const pcp_register_params *p, const float *normals, int64_t *out_sums60);
+int pcp_register_solve_host(const int64_t *sums60, double ell, double cond_tol, double *out_update7, double *out_eigenvalues6,
+                            int32_t *out_dof);
+int pcp_compare_register(pcp_context *ctx, const pcp_register_params *p, const float *normals, double *out_T16, double *out_log,
+                         int32_t *out_status);
+int pcp_compare_base_transform(pcp_context *ctx, double *out_T16, double *out_pivot3, double *out_ell);
+int pcp_compare_set_base_transform(pcp_context *ctx, const double *T16);
+int pcp_compare_register_host(const pcp_register_params *p, int64_t n, const float *xyz, const float *normals, int64_t n_base,
+                              const float *base_xyz, const double *T_in16, int32_t run_loop, int64_t *out_sums60, double *out_T16,
+                              double *out_log, int32_t *out_status, float *out_rows);
 
 /* ---- mask distance maps (scripts/genNormAndDistanceMask.py: class Crack, preprocess :150-198, cv2.threshold :167, */
 /* ---- scipy.ndimage.distance_transform_edt :9,168) ------------------------------------------------------------------ */

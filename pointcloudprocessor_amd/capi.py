@@ -638,6 +638,69 @@ def compare_host(xyz, normals, base_xyz, radius: float = 0.03, half_length: floa
     return out
 
 
+class RegisterParams(C.Structure):
+    """pcp_register_params (DESIGN.md, "Map registration", RG3-RG7)."""
+    _fields_ = [("match_radius", C.c_float), ("max_plane_distance", C.c_float), ("sample_stride", C.c_int32),
+                ("max_iterations", C.c_int32), ("min_pairs", C.c_int32), ("tolerance", C.c_double), ("cond_tol", C.c_double)]
+
+
+RG_TERMS = tuple(f"g{a}g{b}" for a in range(6) for b in range(a, 6)) + tuple(f"g{a}h" for a in range(6)) + ("hh", "N2", "one")  # RG5
+RG_LOG = ("pairs", "rms", "dof", "rotation", "shift")  # RG8: the columns of the log
+RG_CONVERGED, RG_ITERATION_LIMIT, RG_TOO_FEW_PAIRS = range(3)  # RG8: the status
+RG_DEFAULT_COND_TOL = 6.2e-3
+
+
+def register_params(match_radius: float = 0.05, max_plane_distance: float = 0.02, sample_stride: int = 1, max_iterations: int = 20,
+                    min_pairs: int = 100, tolerance: float = 1e-5, cond_tol: float = RG_DEFAULT_COND_TOL) -> RegisterParams:
+    return RegisterParams(match_radius, max_plane_distance, sample_stride, max_iterations, min_pairs, tolerance, cond_tol)
+
+
+def _register_result(T, log, status) -> dict:
+    rows = int(status[1])
+    log = log[:rows].copy()
+    return dict(T=T, log=log, status=int(status[0]), iterations=rows, rms=float(log[-1, 1]) if rows else 0.0,
+                dof=int(log[-1, 2]) if rows else 0, pairs=int(log[-1, 0]) if rows else 0)
+
+
+def register_solve_host(sums60, ell: float, cond_tol: float = RG_DEFAULT_COND_TOL) -> dict:
+    """RG6 for 60 int64 words of sums (pcp_register_solve_host: host only): dict(omega (3,), dt (3,), rms, eigenvalues (6,),
+    dof)."""
+    L = load()
+    sums = np.ascontiguousarray(sums60, np.int64).reshape(60)
+    upd, eig, dof = np.zeros(7, np.float64), np.zeros(6, np.float64), C.c_int32()
+    rc = L.pcp_register_solve_host(_ptr(sums), C.c_double(ell), C.c_double(cond_tol), _ptr(upd), _ptr(eig), C.byref(dof))
+    if rc != PCP_OK:
+        raise PcpError(rc, L.pcp_last_error(None).decode())
+    return dict(omega=upd[:3].copy(), dt=upd[3:6].copy(), rms=float(upd[6]), eigenvalues=eig, dof=dof.value)
+
+
+def compare_register_host(xyz, normals, base_xyz, T_in=None, loop: bool = True, **params) -> dict:
+    """The registration of n_base <= 65536 base rows onto n <= 65536 map points on the CPU by brute force over the pairs with
+    the arithmetic the kernels use (pcp_compare_register_host: no context, no GPU; DESIGN.md "Map registration").  loop False:
+    one evaluation at T_in (None: the identity) -> dict(sums (60,) int64, T, rows); else the loop from T_in -> also log, status,
+    iterations, rms, dof, pairs.  params: those of register_params."""
+    L = load()
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    base_xyz = np.ascontiguousarray(base_xyz, np.float32).reshape(-1, 3)
+    if normals.shape[0] != xyz.shape[0]:
+        raise ValueError("compare_register_host: xyz and normals differ in their number of rows")
+    prm = register_params(**params)
+    T_in = None if T_in is None else np.ascontiguousarray(T_in, np.float64).reshape(16)
+    sums, T = np.zeros(60, np.int64), np.zeros((4, 4), np.float64)
+    log, status = np.zeros((max(1, min(prm.max_iterations, 1000)), 5), np.float64), np.zeros(2, np.int32)
+    rows = np.zeros((min(base_xyz.shape[0], 65536), 3), np.float32)
+    rc = L.pcp_compare_register_host(C.byref(prm), C.c_int64(xyz.shape[0]), _ptr(xyz), _ptr(normals), C.c_int64(base_xyz.shape[0]),
+                                     _ptr(base_xyz), _ptr(T_in), C.c_int32(1 if loop else 0), _ptr(sums), _ptr(T), _ptr(log),
+                                     _ptr(status), _ptr(rows))
+    if rc != PCP_OK:
+        raise PcpError(rc, L.pcp_last_error(None).decode())
+    out = _register_result(T, log, status) if loop else dict(T=T)
+    out["sums"] = sums
+    out["rows"] = rows
+    return out
+
+
 def mask_edt_host(gray, threshold: int = 0) -> dict:
     """The mask distance maps of a (H, W) uint8 mask computed on the CPU with the arithmetic the kernels use
     (pcp_mask_edt_host: no context, no GPU; DESIGN.md "Mask distance maps").  A row stride above the width is passed on
@@ -1788,6 +1851,47 @@ class Context:
     def compare_end(self):
         """Drops the base and the result (pcp_compare_end)."""
         self._check(self.lib.pcp_compare_end(self.h))
+
+    # -- map registration (DESIGN.md, "Map registration") -----------------------------
+    def _register_normals(self, who, normals):
+        if normals is None:
+            return None
+        normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        if normals.shape[0] != self.n:
+            raise ValueError(f"{who}: normals must hold one row per point of the uploaded cloud")
+        return normals
+
+    def compare_register_sums(self, normals=None, **params):
+        """One evaluation of the registration's sums at the base's current transform (pcp_compare_register_sums): (60,) int64,
+        term k of RG_TERMS in words 2 k (low parts) and 2 k + 1 (high parts).  params: those of register_params."""
+        normals = self._register_normals("compare_register_sums", normals)
+        prm = register_params(**params)
+        sums = np.zeros(60, np.int64)
+        self._check(self.lib.pcp_compare_register_sums(self.h, C.byref(prm), _ptr(normals), _ptr(sums)))
+        return sums
+
+    def compare_register(self, normals=None, **params) -> dict:
+        """Brings the base onto the uploaded cloud by point-to-plane ICP from its current transform (pcp_compare_register):
+        dict(T (4, 4) float64, log (iterations, 5) float64 with the columns RG_LOG, status, iterations, rms, dof, pairs of the
+        last iteration).  The rms is what a caller may pass to compare as reg_error."""
+        normals = self._register_normals("compare_register", normals)
+        prm = register_params(**params)
+        T = np.zeros((4, 4), np.float64)
+        log, status = np.zeros((max(1, min(prm.max_iterations, 1000)), 5), np.float64), np.zeros(2, np.int32)
+        self._check(self.lib.pcp_compare_register(self.h, C.byref(prm), _ptr(normals), _ptr(T), _ptr(log), _ptr(status)))
+        return _register_result(T, log, status)
+
+    def compare_base_transform(self) -> dict:
+        """The base's current transform (pcp_compare_base_transform): dict(T (4, 4) float64, pivot (3,), ell)."""
+        T, pivot, ell = np.zeros((4, 4), np.float64), np.zeros(3, np.float64), C.c_double()
+        self._check(self.lib.pcp_compare_base_transform(self.h, _ptr(T), _ptr(pivot), C.byref(ell)))
+        return dict(T=T, pivot=pivot, ell=ell.value)
+
+    def compare_set_base_transform(self, T):
+        """Sets the base's transform to a caller's rigid 4 x 4; the identity restores the original rows
+        (pcp_compare_set_base_transform)."""
+        T = np.ascontiguousarray(T, np.float64).reshape(16)
+        self._check(self.lib.pcp_compare_set_base_transform(self.h, _ptr(T)))
 
     # -- planar facets (DESIGN.md, "Planar facets") -----------------------------------
     def facets(self, link_radius: float = 0.1, angle_deg: float = 10.0, plane_tol: float = 0.01, max_curvature: float = 0.02,

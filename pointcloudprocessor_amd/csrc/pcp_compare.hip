@@ -255,6 +255,7 @@ int pcp_compare_set_base(pcp_context *ctx, const void *points, int64_t n_base, i
   CompareState &cs = ctx->compare;
   cs.base_live = false;
   cs.result_live = false;  // (a result belongs to the base it was made with)
+  cs.reg.live = false;     // (RG1: so does a registration; the transform starts again at the identity)
   // MC3: non-finite rows are never candidates -- they are left out here; the tag keeps the caller's row
   std::vector<float> planes;
   std::vector<uint32_t> tag;

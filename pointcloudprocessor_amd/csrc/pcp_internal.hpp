@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "pcp_hip.h"
+#include "pcp_register.hpp"
 
 namespace pcp {
 
@@ -259,10 +260,27 @@ struct GridDesc {
   const int32_t *occ_rank;
 };
 
+// ---- map registration (pcp_register.hip; DESIGN.md "Map registration", RG1): the transform of the comparison's base; made by the first registration call after
+// pcp_compare_set_base, which resets it.  While it is live, base_xyz and the box hold the CURRENT rows (the original rows
+// under T) and base0 the original ones.
+struct RegisterState {
+  bool live = false;
+  rg::Transform T{{1.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+  double c[3] = {0, 0, 0}, ell = 1.0;           // the pivot and the scale of the original box
+  float mn0[3] = {0, 0, 0}, mx0[3] = {0, 0, 0};  // the original box
+  DevBuf<float> base0;                           // the original planes
+  DevBuf<unsigned long long> words;              // the partial slots, the folded sums, the box of a transform
+  void release() {
+    live = false;
+    base0.release(), words.release();
+  }
+};
+
 // ---- map comparison (pcp_compare.hip; DESIGN.md "Map comparison", MC8): the base survey and the last result ----------------
 // The base (its finite rows as SoA planes and their tags: the caller's row with the epoch bit) lives from pcp_compare_set_base to
 // pcp_compare_end or pcp_destroy; the result (input order of the map) from pcp_compare to the next upload.
 struct CompareState {
+  RegisterState reg;
   bool base_live = false, result_live = false;
   int64_t n_base = 0, m_base = 0;  // rows handed in, finite rows kept
   float mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};  // box of the finite rows
@@ -284,6 +302,7 @@ struct CompareState {
     base_live = false;
     n_base = m_base = 0;
     base_xyz.release(), base_tag.release();
+    reg.release();
   }
 };
 
@@ -799,6 +818,7 @@ hipError_t preload_ortho_texture();
 hipError_t preload_facets();
 hipError_t preload_ortho_defects();
 hipError_t preload_compare();
+hipError_t preload_register();
 // the device parts of pcp_mask_edt (one keyframe, with nearest) and pcp_frame_geometry under the caller's name: checks and
 // kernels, the results left in md_bits / md_d2 / md_nearest and gm_out / s_counter[0]; no copy, no synchronisation
 int mask_edt_device(pcp_context *ctx, const char *who, int32_t frame, int32_t threshold);

@@ -277,6 +277,15 @@
 //     that disappeared) are found by a second run with the two files swapped.  Made on the GPU (pcp_compare; DESIGN.md "Map
 //     comparison").  Refused: --gpus N above 1, --enableMLS 1, --streamColour 1, --normalRadius 0.  Without the flag every file,
 //     byte and message is what it was.
+//   * --compareRegister 1 (new, default 0; needs --compareMap), --registerRadius r (new, default 0.05, 0.005..0.5),
+//     --registerMaxDistance d (new, default 0.02, above 0 and at most r), --registerStride k (new, default 1) and
+//     --registerIterations i (new, default 20, 1..1000): before the comparison the base is brought onto the map by point-to-plane
+//     ICP under the map's normals, and the run also writes <outputPath>compare/registration.json (the 4 x 4 base -> map, the
+//     parameters, the log with one row per iteration -- pairs, rms, dof, the update's rotation and shift in metres --, the
+//     status -- 0 converged, 1 iteration limit, 2 too few pairs --, and the pairs, dof and rms of the last iteration; numbers
+//     as %.17g) and compare/base_transform.txt (four rows of %.17g).  The rms is what --compareRegError may be given in a second
+//     run; nothing applies it.  Made on the GPU (pcp_compare_register; DESIGN.md "Map registration").  Refused: the flag
+//     without --compareMap, and with it what --compareMap refuses.  Without the flag every file, byte and message is what it was.
 #include <algorithm>
 #include <cfloat>
 #include <chrono>
@@ -405,6 +414,9 @@ struct Options {
   bool facet_cylinders = false;       // --facetCylinders 1: fit a cylinder to every facet that is not planar; unrolled maps of those that are one
   std::string compare_map;            // --compareMap base.pcd: compare the map with this earlier survey (compare/*.npy, compare.json)
   pcp_compare_params compare{0.03f, 0.05f, 0.0f, 5, 0, {0.0f, 0.0f, 0.0f}};  // --compareRadius / --compareDepth / --compareRegError / --compareMinPoints
+  bool compare_register = false;      // --compareRegister 1: bring the base onto the map first (compare/registration.json, base_transform.txt)
+  pcp_register_params reg{0.05f, 0.02f, 1, 20, 100, 1e-5, 6.2e-3};  // --registerRadius / --registerMaxDistance / --registerStride / --registerIterations
+  std::string register_value_flag;    // the first --register* value flag seen (it needs --compareRegister 1)
 };
 
 static bool parse_bool(const std::string &v) {  // boost::program_options bool semantics
@@ -594,6 +606,27 @@ static Options parse(int argc, char **argv) {
       if (end == v.c_str() || *end != '\0' || k < 2 || k > (1L << 22))
         throw std::runtime_error("the argument ('" + v + "') for option '--compareMinPoints' is invalid (2..4194304)");
       o.compare.min_points = static_cast<int32_t>(k);
+    }
+    else if (a == "--compareRegister") o.compare_register = parse_bool(next());
+    else if (a == "--registerRadius" || a == "--registerMaxDistance") {
+      const std::string v = next();
+      char *end = nullptr;
+      const float r = std::strtof(v.c_str(), &end);
+      const bool radius = a == "--registerRadius";
+      if (end == v.c_str() || *end != '\0' || !std::isfinite(r) || (radius ? r < 0.005f || r > 0.5f : r <= 0.0f || r > 0.5f))
+        throw std::runtime_error("the argument ('" + v + "') for option '" + a + "' is invalid (" + (radius ? "0.005..0.5" : "above 0, at most 0.5") + ")");
+      (radius ? o.reg.match_radius : o.reg.max_plane_distance) = r;
+      if (o.register_value_flag.empty()) o.register_value_flag = a;
+    }
+    else if (a == "--registerStride" || a == "--registerIterations") {
+      const std::string v = next();
+      char *end = nullptr;
+      const long k = std::strtol(v.c_str(), &end, 10);
+      const bool stride = a == "--registerStride";
+      if (end == v.c_str() || *end != '\0' || k < 1 || k > (stride ? (1L << 30) : 1000L))
+        throw std::runtime_error("the argument ('" + v + "') for option '" + a + "' is invalid (" + (stride ? "1 or more" : "1..1000") + ")");
+      (stride ? o.reg.sample_stride : o.reg.max_iterations) = static_cast<int32_t>(k);
+      if (o.register_value_flag.empty()) o.register_value_flag = a;
     }
     else if (a == "--crackMaps") o.crack_maps = parse_bool(next());
     else if (a == "--crackThreshold") {
@@ -864,6 +897,20 @@ static Options parse(int argc, char **argv) {
                              "facets of the smoothed cloud are not built)");
   if (o.facets && o.normal_radius == 0.0f)
     throw std::runtime_error("the option '--facets 1' needs the map normals ('--normalRadius 0' turns them off)");
+  if (!o.compare_register && !o.register_value_flag.empty())
+    throw std::runtime_error("the option '" + o.register_value_flag + "' needs '--compareRegister 1'");
+  if (o.compare_register && o.compare_map.empty())
+    throw std::runtime_error("the option '--compareRegister 1' needs '--compareMap' (the base it brings onto the map)");
+  if (o.compare_register && o.gpus > 1)
+    throw std::runtime_error("the option '--compareRegister 1' does not work with '--gpus N' above 1 (an index shard sees only its own "
+                             "points; a registration across shards is not built)");
+  if (o.compare_register && o.stream_colour)
+    throw std::runtime_error("the option '--compareRegister 1' does not work with '--streamColour 1' (a row's partner may lie in another chunk)");
+  if (o.compare_register && o.enableMLS)
+    throw std::runtime_error("the option '--compareRegister 1' does not work with '--enableMLS 1' (the registration is onto the raw map; "
+                             "one onto the smoothed cloud is not built)");
+  if (o.compare_register && o.reg.max_plane_distance > o.reg.match_radius)
+    throw std::runtime_error("the argument for option '--registerMaxDistance' is invalid (above '--registerRadius')");
   if (!o.compare_map.empty() && o.gpus > 1)
     throw std::runtime_error("the option '--compareMap' does not work with '--gpus N' above 1 (an index shard sees only its own "
                              "points; a comparison across shards is not built)");
@@ -969,7 +1016,12 @@ static void usage(std::ostream &os) {
         "  --compareRadius arg (=0.03)           With --compareMap: radius (m) of the cylinder along a point's normal (0.005..0.5)\n"
         "  --compareDepth arg (=0.05)            With --compareMap: half length (m) of that cylinder (0.005..0.5; sqrt(radius^2 + depth^2) at most 0.5)\n"
         "  --compareMinPoints arg (=5)           With --compareMap: a distance needs this many points of each survey in the cylinder (2 or more)\n"
-        "  --compareRegError arg (=0)            With --compareMap: registration error (m) added to the level of detection\n";
+        "  --compareRegError arg (=0)            With --compareMap: registration error (m) added to the level of detection\n"
+        "  --compareRegister arg (=0)            With --compareMap: first bring the survey onto the map by point-to-plane ICP (compare/registration.json, base_transform.txt)\n"
+        "  --registerRadius arg (=0.05)          With --compareRegister 1: a row's partner is its nearest map point within this radius (m, 0.005..0.5)\n"
+        "  --registerMaxDistance arg (=0.02)     With --compareRegister 1: pairs further apart than this along the normal (m) are left out of the fit\n"
+        "  --registerStride arg (=1)             With --compareRegister 1: every k-th row of the survey is a query\n"
+        "  --registerIterations arg (=20)        With --compareRegister 1: at most this many iterations (1..1000)\n";
 }
 
 class Processor {
@@ -1027,6 +1079,7 @@ class Processor {
   std::vector<float> ortho_fit_xyz;    // --orthoMap 1 with --enableMLS 1 (one-shot): the crop the chain smoothed, for the frame
   std::vector<uint32_t> ortho_index;   // --orthoMap 1: the index layer, for the crack layers --crackFuse 1 adds
   MapComparison compare_;              // --compareMap: the per-point result, for the maps' change layers
+  Registration registration_;          // --compareRegister 1: what was written to compare/registration.json
   Facets facets_;                      // --facets 1: the partition, for the per-facet maps and the cracks' "facet"
   std::vector<uint8_t> facet_kind_;    // --facetCylinders 1, per facet: 0 neither, 1 planar, 2 cylindrical
   std::vector<pcp_cyl_frame> facet_cyl_;  // --facetCylinders 1, per facet: the fitted cylinder's frame at --orthoGsd (where the fit succeeded)
@@ -1857,7 +1910,7 @@ class Processor {
       Phase ph("compare_gpu_s");
       const int64_t valid = dev.estimateNormals(opt.normal_radius);
       std::cout << "map normals: radius " << opt.normal_radius << ", " << valid << " of " << cloud.size() << " points valid" << std::endl;
-      compare_ = dev.compareMap(p, rows.data(), static_cast<int64_t>(base.size()));
+      compare_ = dev.compareMap(p, rows.data(), static_cast<int64_t>(base.size()), opt.compare_register ? &opt.reg : nullptr, &registration_);
     }
     Phase ph_w("compare_write_s");
     const std::string stem = opt.outputPath + "compare/";
@@ -1894,9 +1947,43 @@ class Processor {
       << "}\n";
     f.close();
     if (!f) throw std::runtime_error("Couldn't save the comparison of the map.");
+    if (opt.compare_register) writeRegistration(stem, base.size());
     std::cout << "Map comparison saved to: " << stem << "distance.npy, lod.npy, status.npy and compare.json, " << compare_.stats[1] << " of "
               << compare_.stats[0] << " core points measured, " << compare_.stats[2] << " significant positive, " << compare_.stats[3]
               << " negative, " << compare_.stats[4] << " without a counterpart" << std::endl;
+  }
+
+  // --compareRegister 1: what the registration found (DESIGN.md "Map registration", RG8), beside the comparison made after it
+  void writeRegistration(const std::string &stem, size_t base_rows) {
+    const Registration &r = registration_;
+    auto num = [](double v) {
+      char b[64];
+      std::snprintf(b, sizeof(b), "%.17g", v);
+      return std::string(b);
+    };
+    std::ofstream t(stem + "base_transform.txt");
+    for (int a = 0; a < 4; ++a) t << num(r.T[4 * a]) << " " << num(r.T[4 * a + 1]) << " " << num(r.T[4 * a + 2]) << " " << num(r.T[4 * a + 3]) << "\n";
+    t.close();
+    std::ofstream f(stem + "registration.json");
+    f << "{\"base\": " << base_rows << ", \"match_radius\": " << num(opt.reg.match_radius) << ", \"max_plane_distance\": " << num(opt.reg.max_plane_distance)
+      << ", \"sample_stride\": " << opt.reg.sample_stride << ", \"max_iterations\": " << opt.reg.max_iterations << ", \"min_pairs\": " << opt.reg.min_pairs
+      << ", \"tolerance\": " << num(opt.reg.tolerance) << ", \"cond_tol\": " << num(opt.reg.cond_tol) << ", \"normal_radius\": " << num(opt.normal_radius)
+      << ", \"T\": [";
+    for (int a = 0; a < 4; ++a)
+      f << (a ? ", " : "") << "[" << num(r.T[4 * a]) << ", " << num(r.T[4 * a + 1]) << ", " << num(r.T[4 * a + 2]) << ", " << num(r.T[4 * a + 3]) << "]";
+    f << "], \"log\": [";
+    for (int32_t k = 0; k < r.iterations; ++k) {
+      const double *row = r.log.data() + 5 * static_cast<size_t>(k);
+      f << (k ? ", " : "") << "[" << num(row[0]) << ", " << num(row[1]) << ", " << num(row[2]) << ", " << num(row[3]) << ", " << num(row[4]) << "]";
+    }
+    f << "], \"status\": " << r.status << ", \"iterations\": " << r.iterations << ", \"pairs\": " << r.pairs << ", \"dof\": " << r.dof
+      << ", \"rms\": " << num(r.rms) << "}\n";
+    f.close();
+    if (!t || !f) throw std::runtime_error("Couldn't save the registration of the base.");
+    static const char *const names[] = {"converged", "iteration limit", "too few pairs"};
+    std::cout << "Base registration saved to: " << stem << "registration.json and base_transform.txt, " << names[r.status < 0 || r.status > 2 ? 1 : r.status]
+              << " after " << r.iterations << " iterations, " << r.pairs << " pairs, " << r.dof << " of 6 components, rms " << r.rms
+              << " m (a candidate for --compareRegError)" << std::endl;
   }
 
   // --facets 1: the faces of the structure (DESIGN.md "Planar facets"): the map normals, the partition, the planes from the integers

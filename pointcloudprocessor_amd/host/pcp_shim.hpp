@@ -106,6 +106,15 @@ struct MapComparison {
   int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
+// what pcp_compare_register leaves (DESIGN.md "Map registration", RG8)
+struct Registration {
+  double T[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};  // row-major: base -> map
+  std::vector<double> log;  // 5 per iteration: pairs, rms, dof, |omega| ell, |dt|
+  int32_t status = 0, iterations = 0, dof = 0;
+  int64_t pairs = 0;
+  double rms = 0.0;  // of the last iteration, metres: what a caller may pass as reg_error
+};
+
 struct Facets {
   int64_t facet_points = 0, components = 0;
   std::vector<int32_t> label;   // per map point: the facet's id (the lowest input index of its points), -1: in no facet
@@ -463,7 +472,28 @@ class Device {
 
   // ---- map comparison: the uploaded map against `n_base` interleaved xyz rows of an earlier survey under the live normals
   // (pcp_compare_set_base, pcp_compare and its fetch; the base is dropped again); needs estimateNormals
-  MapComparison compareMap(const pcp_compare_params &p, const float *base_xyz, int64_t n_base) {
+  // ---- map registration: the base that pcp_compare_set_base left, brought onto the uploaded map under the live normals
+  // (pcp_compare_register); needs estimateNormals and a base
+  Registration registerBase(const pcp_register_params &p) {
+    Registration r;
+    r.log.assign(5 * static_cast<size_t>(p.max_iterations > 0 ? p.max_iterations : 1), 0.0);
+    int32_t st[2] = {0, 0};
+    check(pcp_compare_register(ctx_, &p, nullptr, r.T, r.log.data(), st));
+    r.status = st[0];
+    r.iterations = st[1];
+    r.log.resize(5 * static_cast<size_t>(st[1]));
+    if (st[1] > 0) {
+      const double *last = r.log.data() + 5 * static_cast<size_t>(st[1] - 1);
+      r.pairs = static_cast<int64_t>(last[0]);
+      r.rms = last[1];
+      r.dof = static_cast<int32_t>(last[2]);
+    }
+    return r;
+  }
+
+  // (reg: the base is registered onto the map first, *registration filled)
+  MapComparison compareMap(const pcp_compare_params &p, const float *base_xyz, int64_t n_base, const pcp_register_params *reg = nullptr,
+                           Registration *registration = nullptr) {
     MapComparison m;
     const size_t n = static_cast<size_t>(cloudSize());
     m.distance.resize(n);
@@ -474,6 +504,10 @@ class Device {
       pcp_context *c;
       ~End() { (void)pcp_compare_end(c); }
     } end{ctx_};
+    if (reg) {
+      Registration r = registerBase(*reg);
+      if (registration) *registration = std::move(r);
+    }
     check(pcp_compare(ctx_, &p, nullptr, m.stats));
     check(pcp_compare_fetch(ctx_, m.distance.data(), m.lod.data(), m.status.data(), nullptr, nullptr));
     return m;

@@ -21,6 +21,7 @@ TARGETS = {
     "voxel_reduce_selftest": ["voxel_reduce_selftest.cpp"],  # csrc/pcp_voxel_reduce.hpp compiled for the host (CPU only)
     "normals_selftest": ["normals_selftest.cpp"],  # csrc/pcp_normals.hpp compiled for the host (CPU only)
     "compare_selftest": ["compare_selftest.cpp"],  # csrc/pcp_compare.hpp compiled for the host (CPU only)
+    "register_selftest": ["register_selftest.cpp"],  # csrc/pcp_register.hpp compiled for the host (CPU only)
     "ortho_selftest": ["ortho_selftest.cpp"],  # csrc/pcp_ortho.hpp compiled for the host (CPU only)
     "ortho_texture_selftest": ["ortho_texture_selftest.cpp"],  # csrc/pcp_ortho_texture.hpp compiled for the host (CPU only)
     "crack_width_selftest": ["crack_width_selftest.cpp"],  # csrc/pcp_crack_width.hpp compiled for the host (CPU only)

@@ -400,8 +400,9 @@ class PointCloudColorizer:
         map's own, estimated at normal_radius when none of that radius are live, and are turned towards `viewer` (None: the
         fp64 mean of the keyframes' positions, each divided by their number and summed in order, rounded to float32; without
         keyframes the normals keep their sign).  dict of capi.Context.compare: distance, lod, status, sums, direction, stats.
-        The base stays on the device until capi.Context.compare_end.  Base points the map has no counterpart for are found by
-        a second run with the roles swapped.
+        The base stays on the device until capi.Context.compare_end; base_xyz None compares against the base that is there
+        (register_base's, under the transform it found).  Base points the map has no counterpart for are found by a second run
+        with the roles swapped.
 
         An index shard sees only its own points, so world > 1 raises ValueError."""
         import numpy as np
@@ -412,7 +413,7 @@ class PointCloudColorizer:
         ctx = self.engine.ctx
         if isinstance(base_xyz, (tuple, list)) and len(base_xyz) == 3 and np.ndim(base_xyz[0]) == 1:
             base_xyz = np.stack([np.asarray(a, np.float32) for a in base_xyz], axis=1)
-        base = np.asarray(base_xyz, np.float32).reshape(-1, 3)
+        base = None if base_xyz is None else np.asarray(base_xyz, np.float32).reshape(-1, 3)
         if viewer is None:
             poses = getattr(self.engine, "keyframe_positions", None)
             if poses is not None and len(poses):
@@ -422,10 +423,36 @@ class PointCloudColorizer:
                         viewer[a] += float(p[a]) / float(len(poses))
         if normals is None and ctx.normals_radius != normal_radius:  # (None after an upload: the library dropped the estimate)
             ctx.estimate_normals(normal_radius)
-        ctx.compare_set_base(base)
+        if base is not None:  # (None: the base that register_base left, under its transform)
+            ctx.compare_set_base(base)
         if viewer is None:
             return ctx.compare(radius, half_length, reg_error, min_points, 0, (0.0, 0.0, 0.0), normals)
         return ctx.compare(radius, half_length, reg_error, min_points, 1, tuple(np.asarray(viewer, np.float64).astype(np.float32)), normals)
+
+    def register_base(self, base_xyz, normal_radius: float = 0.1, normals=None, **params) -> dict:
+        """Brings an earlier survey onto the uploaded map by point-to-plane ICP before it is compared ("Map
+        registration"): base_xyz ((n_base, 3), or (x, y, z)) becomes the base of the comparison and is moved rigidly until its
+        rows lie on the planes of their nearest map points.  The normals are `normals` ((n, 3) float32), or the map's own,
+        estimated at normal_radius when none of that radius are live, exactly as compare_map does.  params: those of
+        capi.register_params (match_radius, max_plane_distance, sample_stride, max_iterations, min_pairs, tolerance, cond_tol).
+        dict of capi.Context.compare_register: T (4, 4) base -> map, log, status, iterations, rms, dof, pairs.  The base and its
+        transform stay on the device: compare_map(None, ...) then compares against the registered base.  The rms is a
+        candidate for compare_map's reg_error; nothing applies it.
+
+        An index shard sees only its own points, so world > 1 raises ValueError."""
+        import numpy as np
+
+        if self.world > 1:
+            raise ValueError("register_base: an index shard sees only its own points; the partner of a row near a shard's edge "
+                             "lies with another rank, which is not built: run it on one rank holding the whole map")
+        ctx = self.engine.ctx
+        if isinstance(base_xyz, (tuple, list)) and len(base_xyz) == 3 and np.ndim(base_xyz[0]) == 1:
+            base_xyz = np.stack([np.asarray(a, np.float32) for a in base_xyz], axis=1)
+        base = np.asarray(base_xyz, np.float32).reshape(-1, 3)
+        if normals is None and ctx.normals_radius != normal_radius:  # (None after an upload: the library dropped the estimate)
+            ctx.estimate_normals(normal_radius)
+        ctx.compare_set_base(base)
+        return ctx.compare_register(normals=normals, **params)
 
     def crack_width(self, frame: int, threshold: int = 0, plane_radius: int = 150,
                     want=("flags", "edges", "w2d2", "width", "points", "plane")) -> dict:
