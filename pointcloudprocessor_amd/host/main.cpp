@@ -4,6 +4,8 @@
 // reference binary (PCP/src/main.cpp:7-71, PCP/src/PointCloudProcessor.cpp:1007-1032):
 //   --point_cloud_path/-p --odometry_path/-o --images_folder/-i --mask_image_folder/-m
 //   --output_path/-t --enableMLS --enableNIDOptimize --enableInitialGuessManual --help/-h
+// Every flag, with its range, default, error text and help line, is one row of the table in host/cli_options.hpp; the
+// refusals of flag combinations are the ordered list below it.  What follows describes what the flags make the program write.
 // Stages kept on the host: odometry parsing (:965-1005), keyframe selection (:1050-1075,
 // hpp:151-191), trajectory crop (:92-136), PCD reading / ASCII writing.  Hot path on the
 // GPU through pcp_shim.hpp.
@@ -304,6 +306,7 @@
 #include <mutex>
 #include <condition_variable>
 
+#include "cli_options.hpp"
 #include "image_io.hpp"
 #include "pcd_io.hpp"
 #include "pcp_multi.hpp"
@@ -349,680 +352,6 @@ struct Frame {  // FrameData (PCP/include/FrameData.hpp:89-126)
   double imageTimestamp = 0;
   pcp_pose pose{};
 };
-
-struct Options {
-  std::string pointCloudPath, odometryPath, imagesFolder, maskImageFolder, outputPath = ".";
-  bool have_p = false, have_o = false, have_i = false;
-  bool enableMLS = false, enableNIDOptimize = false, enableInitialGuessManual = false;
-  bool help = false;
-  bool skip_filtered_dumps = false;
-  int gpus = 1;
-  int cull_mode = PCP_CULL_ZBUFFER;
-  int match_mode = PCP_MATCH_ROUNDTRIP;
-  float mls_voxel_size = -1.0f;  // < 0: the reference's constants (PointCloudProcessor.cpp:67-86)
-  int mls_dilation_iterations = -1;
-  int mls_upsampling = -1;
-  double mls_upsampling_radius = 0.05, mls_upsampling_step = 0.01;  // PointCloudProcessor.cpp:74-75
-  float smooth_colors_radius = 0.0f;  // 0: smoothColorsWithLocalRegion off (PointCloudProcessor.cpp:597)
-  bool fuse_masks = false;            // --fuseMasks 1: one fused label per map point in cloudInWorldWithRGBandMask.pcd
-  bool stream_colour = false;         // --streamColour 1: smoothing chain -> colour stage chunk by chunk on the device
-  int64_t stream_chunk = int64_t(1) << 28;  // --streamChunk: voxels per chunk (the capacity of the streamed fallback)
-  bool device_writer = false;         // --deviceWriter 1: the rows of every ASCII PCD are formatted on the device
-  bool device_reader = false;         // --deviceReader 1: the rows of the ASCII PCDs the run reads are parsed on the device
-  bool balance_exposure = false;      // --balanceExposure 1: per-keyframe exposure gains from co-visible map points
-  float output_leaf = 0.0f;           // --outputLeaf L: also write the voxel-grid output at that leaf (0: off)
-  bool skip_full_cloud = false;       // --skip_full_cloud 1: with --outputLeaf, the full-resolution final files are not made
-  bool geometry_maps = false;         // --geometryMaps 1: per-keyframe range / xyz / normal / index images (geometry_maps/*.npy)
-  float normal_radius = 0.1f;         // --normalRadius r: neighbourhood of the map normals (0: no normals, no _normal file)
-  bool crack_maps = false;            // --crackMaps 1: per-keyframe mask distance maps (crack_maps/*.npy)
-  int crack_threshold = 0;            // --crackThreshold t: a mask byte above t is foreground
-  bool crack_width = false;           // --crackWidth 1: per-keyframe crack width maps (crack_width/*.npy)
-  int crack_plane_radius = 150;       // --crackPlaneRadius R: half side of the plane's window, pixels
-  bool crack_length = false;          // --crackLength 1: with --crackFuse, the cracks' lengths, ends and centrelines (crack_width/crack_*)
-  bool crack_skeleton = false;        // --crackSkeleton 1: with --crackFuse, the cracks' branches, junctions and loops (crack_width/crack_*)
-  float crack_skeleton_step = 0.0f;   // --crackSkeletonStep: the band width in metres (0: twice the link radius)
-  bool crack_direction = false;       // --crackDirection 1: with --crackFuse, the cracks' tangents and axes (crack_width/map_tangent.npy, ...)
-  double crack_up[3] = {0.0, 0.0, 1.0};  // --crackUp x,y,z: what vertical means (unit)
-  bool crack_branches = false;        // --crackBranches 1: with --crackFuse, the cracks arm by arm (crack_width/crack_branch*, map_crack_branch.npy)
-  float crack_prune = -1.0f;          // --crackPrune p: spurs of fewer than p metres of bands go (below 0: twice the band width)
-  bool crack_prune_given = false;
-  bool crack_fuse = false;            // --crackFuse 1: the widths on the map and the map's cracks (crack_width/map_*.npy, cracks_3d.json)
-  float crack_link_radius = 0.02f;    // --crackLinkRadius r: crack points this close belong to one crack
-  int crack_min_views = 1;            // --crackMinViews v: credited keyframes a crack point needs
-  bool balance_images = false;        // --balanceImages 1: CLAHE + gamma on every keyframe at upload
-  float clahe_clip = 1.0f;            // --claheClip c (0: no clipping)
-  int clahe_tiles_x = 8, clahe_tiles_y = 8;  // --claheTiles x,y
-  float balance_gamma = 0.8f;         // --balanceGamma g
-  std::string balance_value_flag;     // the first of the three value flags given (an error without --balanceImages 1)
-  bool ortho_map = false;             // --orthoMap 1: one orthographic picture of the coloured cloud (ortho/ortho_*.npy, ortho_frame.json)
-  float ortho_gsd = 0.01f;            // --orthoGsd g: metres per pixel
-  int ortho_fill = 0;                 // --orthoFill R: empty pixels take their nearest occupied pixel within R pixels
-  std::vector<float> ortho_frame;     // --orthoFrame: empty = auto, else origin, u, v (9 numbers)
-  int ortho_texture = 0;              // --orthoTexture k: the orthophoto of that map, k fine pixels per pixel and axis (0: off)
-  int ortho_texture_views = 1;        // --orthoTextureViews m: listed views that enter a colour
-  bool ortho_texture_interp = true;   // --orthoTextureInterp: bilinear depth between map pixels
-  float ortho_texture_step = 0.05f;   // --orthoTextureStep s: ... only across depth steps up to s metres
-  bool ortho_texture_cylinders = false;  // --orthoTextureCylinders 1: the orthophoto of every cylindrical facet's unrolled map too
-  bool ortho_texture_value_flag = false;  // one of the three value flags was given
-  bool facets = false;                // --facets 1: the planar facets of the map (facets/facet_label.npy, facets.json)
-  bool ortho_defects = false;         // --orthoDefects 1: the surface defects of every orthographic map written (ortho_defect_*.npy, defects.json)
-  pcp_ortho_defect_params defect{0.002f, 0, 0, 1, 1, 3};  // --defectThreshold / Window / Refine / MinSupport / MinPixels / Classes
-  bool defect_value_flag = false;     // one of the --defect* values was given
-  bool ortho_by_facet = false;        // --orthoFrame facets: one orthographic map per planar facet (ortho/facet_<row>/)
-  pcp_facet_params facet{0.1f, 10.0f, 0.01f, 0.02f, 1000};  // --facetRadius / --facetAngle / --facetPlaneTol / --facetMaxCurvature / --facetMinPoints
-  float facet_max_rms = 0.01f;        // --facetMaxRms m: a facet is planar up to this rms distance to its plane
-  bool facet_cylinders = false;       // --facetCylinders 1: fit a cylinder to every facet that is not planar; unrolled maps of those that are one
-  std::string compare_map;            // --compareMap base.pcd: compare the map with this earlier survey (compare/*.npy, compare.json)
-  pcp_compare_params compare{0.03f, 0.05f, 0.0f, 5, 0, {0.0f, 0.0f, 0.0f}};  // --compareRadius / --compareDepth / --compareRegError / --compareMinPoints
-  bool compare_register = false;      // --compareRegister 1: bring the base onto the map first (compare/registration.json, base_transform.txt)
-  pcp_register_params reg{0.05f, 0.02f, 1, 20, 100, 1e-5, 6.2e-3};  // --registerRadius / --registerMaxDistance / --registerStride / --registerIterations
-  std::string register_value_flag;    // the first --register* value flag seen (it needs --compareRegister 1)
-};
-
-static bool parse_bool(const std::string &v) {  // boost::program_options bool semantics
-  std::string s;
-  for (char c : v) s += static_cast<char>(std::tolower(c));
-  if (s == "1" || s == "true" || s == "yes" || s == "on") return true;
-  if (s == "0" || s == "false" || s == "no" || s == "off") return false;
-  throw std::runtime_error("the argument ('" + v + "') for a boolean option is invalid");
-}
-
-static Options parse(int argc, char **argv) {
-  Options o;
-  for (int k = 1; k < argc; ++k) {
-    std::string a = argv[k], val;
-    bool has_val = false;
-    const size_t eq = a.find('=');
-    if (a.rfind("--", 0) == 0 && eq != std::string::npos) {
-      val = a.substr(eq + 1);
-      a = a.substr(0, eq);
-      has_val = true;
-    }
-    auto next = [&]() -> std::string {
-      if (has_val) return val;
-      if (k + 1 >= argc) throw std::runtime_error("the required argument for option '" + a + "' is missing");
-      return argv[++k];
-    };
-    if (a == "--help" || a == "-h") o.help = true;
-    else if (a == "--point_cloud_path" || a == "-p") { o.pointCloudPath = next(); o.have_p = true; }
-    else if (a == "--odometry_path" || a == "-o") { o.odometryPath = next(); o.have_o = true; }
-    else if (a == "--images_folder" || a == "-i") { o.imagesFolder = next(); o.have_i = true; }
-    else if (a == "--mask_image_folder" || a == "-m") o.maskImageFolder = next();
-    else if (a == "--output_path" || a == "-t") o.outputPath = next();
-    else if (a == "--enableMLS") o.enableMLS = parse_bool(next());
-    else if (a == "--enableNIDOptimize") o.enableNIDOptimize = parse_bool(next());
-    else if (a == "--enableInitialGuessManual") o.enableInitialGuessManual = parse_bool(next());
-    else if (a == "--skip_filtered_dumps") o.skip_filtered_dumps = parse_bool(next());
-    else if (a == "--gpus") o.gpus = std::stoi(next());
-    else if (a == "--mlsVoxelSize") o.mls_voxel_size = std::stof(next());
-    else if (a == "--mlsDilationIterations") o.mls_dilation_iterations = std::stoi(next());
-    else if (a == "--mlsUpsamplingRadius") o.mls_upsampling_radius = std::stod(next());
-    else if (a == "--mlsUpsamplingStep") o.mls_upsampling_step = std::stod(next());
-    else if (a == "--mlsUpsampling") {
-      const std::string v = next();
-      if (v == "none") o.mls_upsampling = PCP_UPSAMPLING_NONE;
-      else if (v == "slp") o.mls_upsampling = PCP_UPSAMPLING_SAMPLE_LOCAL_PLANE;
-      else if (v == "vgd") o.mls_upsampling = PCP_UPSAMPLING_VOXEL_GRID_DILATION;
-      else throw std::runtime_error("the argument ('" + v + "') for option '--mlsUpsampling' is invalid (none, slp, vgd)");
-    }
-    else if (a == "--smoothColorsRadius") {
-      const std::string v = next();
-      const char *s = v.c_str();
-      char *end = nullptr;
-      const double r = std::strtod(s, &end);
-      const float rf = static_cast<float>(r);
-      // 0 (off) or a radius the library accepts (finite, 0 < r <= 1)
-      if (v.empty() || end != s + v.size() || !std::isfinite(r) || !(rf == 0.0f || (rf > 0.0f && rf <= 1.0f)))
-        throw std::runtime_error("the argument ('" + v + "') for option '--smoothColorsRadius' is invalid (0 = off, or 0 < r <= 1)");
-      o.smooth_colors_radius = rf;
-    }
-    else if (a == "--fuseMasks") {
-      const std::string v = next();
-      if (v != "0" && v != "1")
-        throw std::runtime_error("the argument ('" + v + "') for option '--fuseMasks' is invalid (0, 1)");
-      o.fuse_masks = v == "1";
-    }
-    else if (a == "--deviceWriter") {
-      const std::string v = next();
-      if (v != "0" && v != "1")
-        throw std::runtime_error("the argument ('" + v + "') for option '--deviceWriter' is invalid (0, 1)");
-      o.device_writer = v == "1";
-    }
-    else if (a == "--deviceReader") {
-      const std::string v = next();
-      if (v != "0" && v != "1")
-        throw std::runtime_error("the argument ('" + v + "') for option '--deviceReader' is invalid (0, 1)");
-      o.device_reader = v == "1";
-    }
-    else if (a == "--balanceExposure") {
-      const std::string v = next();
-      if (v != "0" && v != "1")
-        throw std::runtime_error("the argument ('" + v + "') for option '--balanceExposure' is invalid (0, 1)");
-      o.balance_exposure = v == "1";
-    }
-    else if (a == "--balanceImages") {
-      const std::string v = next();
-      if (v != "0" && v != "1")
-        throw std::runtime_error("the argument ('" + v + "') for option '--balanceImages' is invalid (0, 1)");
-      o.balance_images = v == "1";
-    }
-    else if (a == "--claheClip") {
-      const std::string v = next();
-      char *end = nullptr;
-      const float c = std::strtof(v.c_str(), &end);
-      if (v.empty() || end != v.c_str() + v.size() || !std::isfinite(c) || c < 0.0f)
-        throw std::runtime_error("the argument ('" + v + "') for option '--claheClip' is invalid (0 = no clipping, or c > 0)");
-      o.clahe_clip = c;
-      if (o.balance_value_flag.empty()) o.balance_value_flag = a;
-    }
-    else if (a == "--claheTiles") {
-      const std::string v = next();
-      char *end = nullptr, *end2 = nullptr;
-      const long tx = std::strtol(v.c_str(), &end, 10);
-      const long ty = (end != v.c_str() && *end == ',') ? std::strtol(end + 1, &end2, 10) : 0;
-      if (end == v.c_str() || *end != ',' || end2 == end + 1 || !end2 || *end2 != '\0' || tx < 1 || tx > 16 || ty < 1 || ty > 16)
-        throw std::runtime_error("the argument ('" + v + "') for option '--claheTiles' is invalid (x,y with 1..16 each)");
-      o.clahe_tiles_x = static_cast<int>(tx);
-      o.clahe_tiles_y = static_cast<int>(ty);
-      if (o.balance_value_flag.empty()) o.balance_value_flag = a;
-    }
-    else if (a == "--balanceGamma") {
-      const std::string v = next();
-      char *end = nullptr;
-      const float g = std::strtof(v.c_str(), &end);
-      if (v.empty() || end != v.c_str() + v.size() || !std::isfinite(g) || !(g > 0.0f))
-        throw std::runtime_error("the argument ('" + v + "') for option '--balanceGamma' is invalid (g > 0; 1 = identity)");
-      o.balance_gamma = g;
-      if (o.balance_value_flag.empty()) o.balance_value_flag = a;
-    }
-    else if (a == "--outputLeaf") {
-      const std::string v = next();
-      char *end = nullptr;
-      const double l = std::strtod(v.c_str(), &end);
-      const float lf = static_cast<float>(l);
-      // 0 (off) or a leaf the library accepts (finite, 1e-4 <= L <= 1)
-      if (v.empty() || end != v.c_str() + v.size() || !std::isfinite(l) || !(lf == 0.0f || (lf >= 1e-4f && lf <= 1.0f)))
-        throw std::runtime_error("the argument ('" + v + "') for option '--outputLeaf' is invalid (0 = off, or 1e-4 <= L <= 1)");
-      o.output_leaf = lf;
-    }
-    else if (a == "--skip_full_cloud") o.skip_full_cloud = parse_bool(next());
-    else if (a == "--geometryMaps") o.geometry_maps = parse_bool(next());
-    else if (a == "--normalRadius") {
-      const std::string v = next();
-      char *end = nullptr;
-      const float r = std::strtof(v.c_str(), &end);
-      if (end == v.c_str() || *end != '\0' || !(r == 0.0f || (r >= 0.005f && r <= 1.0f)))
-        throw std::runtime_error("the argument ('" + v + "') for option '--normalRadius' is invalid (0 = no normals, or 0.005 <= r <= 1)");
-      o.normal_radius = r;
-    }
-    else if (a == "--facets") o.facets = parse_bool(next());
-    else if (a == "--facetCylinders") o.facet_cylinders = parse_bool(next());
-    else if (a == "--orthoTextureCylinders") o.ortho_texture_cylinders = parse_bool(next());
-    else if (a == "--facetRadius" || a == "--facetAngle" || a == "--facetPlaneTol" || a == "--facetMaxCurvature" || a == "--facetMaxRms") {
-      const std::string v = next();
-      char *end = nullptr;
-      const float r = std::strtof(v.c_str(), &end);
-      const bool parsed = end != v.c_str() && *end == '\0';
-      struct Rule {
-        const char *flag;
-        float *to;
-        float lo, hi;
-        bool lo_open;
-        const char *range;
-      } rules[] = {{"--facetRadius", &o.facet.link_radius, 0.005f, 1.0f, false, "0.005 <= r <= 1"},
-                   {"--facetAngle", &o.facet.angle_deg, 0.0f, 45.0f, true, "0 < degrees <= 45"},
-                   {"--facetPlaneTol", &o.facet.plane_tol, 1e-4f, 0.1f, false, "1e-4 <= metres <= 0.1"},
-                   {"--facetMaxCurvature", &o.facet.max_curvature, 0.0f, 1.0f, false, "0 <= c <= 1"},
-                   {"--facetMaxRms", &o.facet_max_rms, 0.0f, 1e6f, false, "metres, >= 0"}};
-      for (const Rule &k : rules) {
-        if (a != k.flag) continue;
-        if (!parsed || !(r >= k.lo && r <= k.hi) || (k.lo_open && r == k.lo))
-          throw std::runtime_error("the argument ('" + v + "') for option '" + a + "' is invalid (" + k.range + ")");
-        *k.to = r;
-      }
-    }
-    else if (a == "--facetMinPoints") {
-      const std::string v = next();
-      char *end = nullptr;
-      const long k = std::strtol(v.c_str(), &end, 10);
-      if (end == v.c_str() || *end != '\0' || k < 1 || k > (1L << 24))
-        throw std::runtime_error("the argument ('" + v + "') for option '--facetMinPoints' is invalid (1..16777216)");
-      o.facet.min_points = static_cast<int32_t>(k);
-    }
-    else if (a == "--compareMap") o.compare_map = next();
-    else if (a == "--compareRadius" || a == "--compareDepth" || a == "--compareRegError") {
-      const std::string v = next();
-      char *end = nullptr;
-      const float r = std::strtof(v.c_str(), &end);
-      const bool extent = a != "--compareRegError";
-      if (end == v.c_str() || *end != '\0' || !std::isfinite(r) || (extent ? r < 0.005f || r > 0.5f : r < 0.0f))
-        throw std::runtime_error("the argument ('" + v + "') for option '" + a + "' is invalid (" + (extent ? "0.005..0.5" : "0 or more") + ")");
-      (a == "--compareRadius" ? o.compare.cyl_radius : a == "--compareDepth" ? o.compare.cyl_half_length : o.compare.reg_error) = r;
-    }
-    else if (a == "--compareMinPoints") {
-      const std::string v = next();
-      char *end = nullptr;
-      const long k = std::strtol(v.c_str(), &end, 10);
-      if (end == v.c_str() || *end != '\0' || k < 2 || k > (1L << 22))
-        throw std::runtime_error("the argument ('" + v + "') for option '--compareMinPoints' is invalid (2..4194304)");
-      o.compare.min_points = static_cast<int32_t>(k);
-    }
-    else if (a == "--compareRegister") o.compare_register = parse_bool(next());
-    else if (a == "--registerRadius" || a == "--registerMaxDistance") {
-      const std::string v = next();
-      char *end = nullptr;
-      const float r = std::strtof(v.c_str(), &end);
-      const bool radius = a == "--registerRadius";
-      if (end == v.c_str() || *end != '\0' || !std::isfinite(r) || (radius ? r < 0.005f || r > 0.5f : r <= 0.0f || r > 0.5f))
-        throw std::runtime_error("the argument ('" + v + "') for option '" + a + "' is invalid (" + (radius ? "0.005..0.5" : "above 0, at most 0.5") + ")");
-      (radius ? o.reg.match_radius : o.reg.max_plane_distance) = r;
-      if (o.register_value_flag.empty()) o.register_value_flag = a;
-    }
-    else if (a == "--registerStride" || a == "--registerIterations") {
-      const std::string v = next();
-      char *end = nullptr;
-      const long k = std::strtol(v.c_str(), &end, 10);
-      const bool stride = a == "--registerStride";
-      if (end == v.c_str() || *end != '\0' || k < 1 || k > (stride ? (1L << 30) : 1000L))
-        throw std::runtime_error("the argument ('" + v + "') for option '" + a + "' is invalid (" + (stride ? "1 or more" : "1..1000") + ")");
-      (stride ? o.reg.sample_stride : o.reg.max_iterations) = static_cast<int32_t>(k);
-      if (o.register_value_flag.empty()) o.register_value_flag = a;
-    }
-    else if (a == "--crackMaps") o.crack_maps = parse_bool(next());
-    else if (a == "--crackThreshold") {
-      const std::string v = next();
-      char *end = nullptr;
-      const long t = std::strtol(v.c_str(), &end, 10);
-      if (end == v.c_str() || *end != '\0' || t < 0 || t > 255)
-        throw std::runtime_error("the argument ('" + v + "') for option '--crackThreshold' is invalid (0..255)");
-      o.crack_threshold = static_cast<int>(t);
-    }
-    else if (a == "--crackWidth") o.crack_width = parse_bool(next());
-    else if (a == "--crackPlaneRadius") {
-      const std::string v = next();
-      char *end = nullptr;
-      const long r = std::strtol(v.c_str(), &end, 10);
-      if (end == v.c_str() || *end != '\0' || r < 1 || r > 181)
-        throw std::runtime_error("the argument ('" + v + "') for option '--crackPlaneRadius' is invalid (1..181)");
-      o.crack_plane_radius = static_cast<int>(r);
-    }
-    else if (a == "--crackFuse") o.crack_fuse = parse_bool(next());
-    else if (a == "--orthoMap") o.ortho_map = parse_bool(next());
-    else if (a == "--orthoDefects") o.ortho_defects = parse_bool(next());
-    else if (a == "--defectThreshold") {
-      const std::string v = next();
-      try {
-        o.defect.threshold = std::stof(v);
-      } catch (const std::exception &) {
-        o.defect.threshold = -1.0f;
-      }
-      if (!(o.defect.threshold >= 0x1p-20f && o.defect.threshold <= 1.0f))
-        throw std::runtime_error("the argument ('" + v + "') for option '--defectThreshold' is invalid (2^-20 <= t <= 1 metres)");
-      o.defect_value_flag = true;
-    } else if (a == "--defectWindow" || a == "--defectMinSupport" || a == "--defectMinPixels") {
-      const std::string v = next();
-      char *end = nullptr;
-      const long k = std::strtol(v.c_str(), &end, 10);
-      const bool window = a == "--defectWindow";
-      if (end == v.c_str() || *end != '\0' || k < (window ? 0 : 1) || k > (window ? 1024 : 2147483647L))
-        throw std::runtime_error("the argument ('" + v + "') for option '" + a + "' is invalid (" + (window ? "0..1024 pixels" : "1 or more") + ")");
-      (window ? o.defect.window_px : a == "--defectMinSupport" ? o.defect.min_support : o.defect.min_pixels) = static_cast<int32_t>(k);
-      o.defect_value_flag = true;
-    } else if (a == "--defectRefine") {
-      o.defect.refine = parse_bool(next()) ? 1 : 0;
-      o.defect_value_flag = true;
-    } else if (a == "--defectClasses") {
-      const std::string v = next();
-      if (v != "hollow" && v != "bulge" && v != "both")
-        throw std::runtime_error("the argument ('" + v + "') for option '--defectClasses' is invalid (hollow, bulge or both)");
-      o.defect.classes = v == "hollow" ? 1 : v == "bulge" ? 2 : 3;
-      o.defect_value_flag = true;
-    }
-    else if (a == "--orthoGsd") {
-      const std::string v = next();
-      try {
-        o.ortho_gsd = std::stof(v);
-      } catch (const std::exception &) {
-        o.ortho_gsd = -1.0f;
-      }
-      if (!(o.ortho_gsd >= 1e-4f && o.ortho_gsd <= 1.0f))
-        throw std::runtime_error("the argument ('" + v + "') for option '--orthoGsd' is invalid (1e-4 <= g <= 1)");
-    } else if (a == "--orthoFill") {
-      const std::string v = next();
-      try {
-        o.ortho_fill = std::stoi(v);
-      } catch (const std::exception &) {
-        o.ortho_fill = -1;
-      }
-      if (o.ortho_fill < 0 || o.ortho_fill > 1024)
-        throw std::runtime_error("the argument ('" + v + "') for option '--orthoFill' is invalid (0..1024 pixels)");
-    } else if (a == "--orthoFrame") {
-      const std::string v = next();
-      o.ortho_frame.clear();
-      o.ortho_by_facet = v == "facets";
-      if (v != "auto" && v != "facets") {
-        std::istringstream is(v);
-        std::string tok;
-        bool ok = true;
-        while (std::getline(is, tok, ','))
-          try {
-            o.ortho_frame.push_back(std::stof(tok));
-          } catch (const std::exception &) {
-            ok = false;
-          }
-        if (!ok || o.ortho_frame.size() != 9)
-          throw std::runtime_error("the argument ('" + v + "') for option '--orthoFrame' is invalid (auto, facets, or ox,oy,oz,ux,uy,uz,vx,vy,vz)");
-      }
-    }
-    else if (a == "--orthoTexture" || a == "--orthoTextureViews") {
-      const std::string v = next();
-      const bool scale = a == "--orthoTexture";
-      char *end = nullptr;
-      const long k = std::strtol(v.c_str(), &end, 10);
-      if (end == v.c_str() || *end != '\0' || k < (scale ? 0 : 1) || k > (scale ? 16 : 5))
-        throw std::runtime_error("the argument ('" + v + "') for option '" + a + "' is invalid (" + (scale ? "0 = off, 1..16" : "1..5") + ")");
-      (scale ? o.ortho_texture : o.ortho_texture_views) = static_cast<int>(k);
-      if (!scale) o.ortho_texture_value_flag = true;
-    } else if (a == "--orthoTextureInterp") {
-      o.ortho_texture_interp = parse_bool(next());
-      o.ortho_texture_value_flag = true;
-    } else if (a == "--orthoTextureStep") {
-      const std::string v = next();
-      try {
-        o.ortho_texture_step = std::stof(v);
-      } catch (const std::exception &) {
-        o.ortho_texture_step = -1.0f;
-      }
-      if (!(o.ortho_texture_step > 0.0f && std::isfinite(o.ortho_texture_step)))
-        throw std::runtime_error("the argument ('" + v + "') for option '--orthoTextureStep' is invalid (metres, above 0)");
-      o.ortho_texture_value_flag = true;
-    }
-    else if (a == "--crackLength") o.crack_length = parse_bool(next());
-    else if (a == "--crackSkeleton") o.crack_skeleton = parse_bool(next());
-    else if (a == "--crackSkeletonStep") o.crack_skeleton_step = std::stof(next());
-    else if (a == "--crackDirection") o.crack_direction = parse_bool(next());
-    else if (a == "--crackBranches") o.crack_branches = parse_bool(next());
-    else if (a == "--crackPrune") o.crack_prune = std::stof(next()), o.crack_prune_given = true;
-    else if (a == "--crackUp") {
-      const std::string v = next();
-      double u[3] = {0.0, 0.0, 0.0};
-      const char *at = v.c_str();
-      bool ok = !v.empty();
-      for (int k = 0; k < 3 && ok; ++k) {
-        char *end = nullptr;
-        u[k] = std::strtod(at, &end);
-        ok = end != at && std::isfinite(u[k]) && *end == (k < 2 ? ',' : '\0');
-        at = end + 1;
-      }
-      const double len = ok ? std::sqrt((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]) : 0.0;
-      if (!ok || !(len > 0.0) || !std::isfinite(len))
-        throw std::runtime_error("the argument ('" + v + "') for option '--crackUp' is invalid (x,y,z: finite and not zero)");
-      for (int k = 0; k < 3; ++k) o.crack_up[k] = u[k] / len;
-    }
-    else if (a == "--crackLinkRadius") {
-      const std::string v = next();
-      char *end = nullptr;
-      const float r = std::strtof(v.c_str(), &end);
-      if (end == v.c_str() || *end != '\0' || !(r >= 0.005f && r <= 1.0f))
-        throw std::runtime_error("the argument ('" + v + "') for option '--crackLinkRadius' is invalid (0.005 <= r <= 1)");
-      o.crack_link_radius = r;
-    }
-    else if (a == "--crackMinViews") {
-      const std::string v = next();
-      char *end = nullptr;
-      const long m = std::strtol(v.c_str(), &end, 10);
-      if (end == v.c_str() || *end != '\0' || m < 1 || m > 4096)
-        throw std::runtime_error("the argument ('" + v + "') for option '--crackMinViews' is invalid (1..4096)");
-      o.crack_min_views = static_cast<int>(m);
-    }
-    else if (a == "--streamColour") {
-      const std::string v = next();
-      if (v != "0" && v != "1")
-        throw std::runtime_error("the argument ('" + v + "') for option '--streamColour' is invalid (0, 1)");
-      o.stream_colour = v == "1";
-    }
-    else if (a == "--streamChunk") {
-      const std::string v = next();
-      char *end = nullptr;
-      const long long c = std::strtoll(v.c_str(), &end, 10);
-      if (v.empty() || end != v.c_str() + v.size() || c < 4096 || c >= (1ll << 31))
-        throw std::runtime_error("the argument ('" + v + "') for option '--streamChunk' is invalid (voxels per chunk, 4096 .. 2^31 - 1)");
-      o.stream_chunk = c;
-    }
-    else if (a == "--cull") {
-      const std::string v = next();
-      if (v == "zbuffer") o.cull_mode = PCP_CULL_ZBUFFER;
-      else if (v == "hpr") o.cull_mode = PCP_CULL_HPR;
-      else if (v == "hpr_candidates") o.cull_mode = PCP_CULL_HPR_CANDIDATES;
-      else throw std::runtime_error("the argument ('" + v + "') for option '--cull' is invalid (zbuffer, hpr, hpr_candidates)");
-    }
-    else if (a == "--matchBack") {
-      const std::string v = next();
-      if (v == "roundtrip") o.match_mode = PCP_MATCH_ROUNDTRIP;
-      else if (v == "radius") o.match_mode = PCP_MATCH_RADIUS;
-      else throw std::runtime_error("the argument ('" + v + "') for option '--matchBack' is invalid (roundtrip, radius)");
-    }
-    else throw std::runtime_error("unrecognised option '" + a + "'");
-  }
-  if (o.match_mode == PCP_MATCH_RADIUS && o.gpus > 1)
-    throw std::runtime_error("the option '--matchBack radius' needs the whole map on one GPU (--gpus 1)");
-  if (o.fuse_masks && o.maskImageFolder.empty())
-    throw std::runtime_error("the option '--fuseMasks 1' needs the masks (--mask_image_folder)");
-  if (o.device_writer && o.gpus > 1)  // (before anything is read or written, as --streamColour 1 refuses what it cannot do)
-    throw std::runtime_error("the option '--deviceWriter 1' does not work with '--gpus N' above 1 (the text is formatted from the "
-                             "results resident on one GPU: they do not exist on index shards)");
-  if (o.skip_full_cloud && !(o.output_leaf > 0.0f))
-    throw std::runtime_error("the option '--skip_full_cloud 1' needs '--outputLeaf' above 0 (without it the run would write no coloured cloud)");
-  if (o.output_leaf > 0.0f && o.gpus > 1)
-    throw std::runtime_error("the option '--outputLeaf' does not work with '--gpus N' above 1 (the voxel sums of the index shards would "
-                             "have to be added across GPUs: not built)");
-  if (o.ortho_texture_cylinders && !(o.ortho_texture && o.facet_cylinders && o.ortho_by_facet))
-    throw std::runtime_error("the option '--orthoTextureCylinders 1' needs '--orthoTexture k' (k in 1..16), '--facetCylinders 1' and "
-                             "'--orthoFrame facets' (it textures the unrolled maps those three write)");
-  if (o.ortho_texture_value_flag && !o.ortho_texture)
-    throw std::runtime_error("the options '--orthoTextureViews', '--orthoTextureInterp' and '--orthoTextureStep' need '--orthoTexture k' (k in 1..16)");
-  if (o.ortho_texture && !o.ortho_map)
-    throw std::runtime_error("the option '--orthoTexture' needs '--orthoMap 1' (the orthophoto is that map at a finer pitch)");
-  if (o.defect_value_flag && !o.ortho_defects)
-    throw std::runtime_error("the options '--defectThreshold', '--defectWindow', '--defectRefine', '--defectMinSupport', '--defectMinPixels' and "
-                             "'--defectClasses' need '--orthoDefects 1'");
-  if (o.ortho_defects && !o.ortho_map)
-    throw std::runtime_error("the option '--orthoDefects 1' needs '--orthoMap 1' (the defects are read from that map's depth layer)");
-  if (o.ortho_defects && o.gpus > 1)
-    throw std::runtime_error("the option '--orthoDefects 1' does not work with '--gpus N' above 1 (the orthographic map it reads is "
-                             "not built on index shards)");
-  if (o.ortho_defects && o.defect.refine && o.defect.window_px == 0)
-    throw std::runtime_error("the option '--defectRefine 1' needs '--defectWindow W' above 0 (it refines the window's reference)");
-  if (o.ortho_texture && o.gpus > 1)
-    throw std::runtime_error("the option '--orthoTexture' does not work with '--gpus N' above 1 (an index shard holds the depth maps "
-                             "and the map of its own points only)");
-  if (o.ortho_texture && o.cull_mode != PCP_CULL_ZBUFFER)
-    throw std::runtime_error("the option '--orthoTexture' does not work with '--cull hpr' or '--cull hpr_candidates' (a surface point is "
-                             "kept or dropped by the depth maps, which only '--cull zbuffer' makes)");
-  if (o.ortho_map && o.gpus > 1)
-    throw std::runtime_error("the option '--orthoMap 1' does not work with '--gpus N' above 1 (an index shard sees only its own "
-                             "points; the shards' key images would merge by an all-reduce(MIN), which is not built)");
-  if (o.geometry_maps && o.gpus > 1)
-    throw std::runtime_error("the option '--geometryMaps 1' does not work with '--gpus N' above 1 (an index shard sees only its own "
-                             "points: the per-pixel keys of the shards would have to be merged across GPUs, which is not built)");
-  if (o.crack_maps && o.maskImageFolder.empty())
-    throw std::runtime_error("the option '--crackMaps 1' needs the masks (--mask_image_folder)");
-  if (o.crack_maps && o.gpus > 1)
-    throw std::runtime_error("the option '--crackMaps 1' does not work with '--gpus N' above 1 (the maps are made per keyframe from "
-                             "the masks of one context: index shards would add nothing)");
-  if (o.crack_width && o.maskImageFolder.empty())
-    throw std::runtime_error("the option '--crackWidth 1' needs the masks (--mask_image_folder)");
-  if (o.crack_width && o.gpus > 1)
-    throw std::runtime_error("the option '--crackWidth 1' does not work with '--gpus N' above 1 (an index shard sees only its own "
-                             "points: the per-pixel keys of the shards would have to be merged across GPUs, which is not built)");
-  if (o.crack_width && o.enableMLS)
-    throw std::runtime_error("the option '--crackWidth 1' does not work with '--enableMLS 1' (the planes are fitted to the raw "
-                             "map; maps of the smoothed cloud are not built)");
-  if (o.crack_length && !o.crack_fuse)
-    throw std::runtime_error("the option '--crackLength 1' needs the widths on the map (--crackFuse 1)");
-  if (o.crack_skeleton && !o.crack_fuse)
-    throw std::runtime_error("the option '--crackSkeleton 1' needs the widths on the map (--crackFuse 1)");
-  if (o.crack_direction && !o.crack_fuse)
-    throw std::runtime_error("the option '--crackDirection 1' needs the widths on the map (--crackFuse 1)");
-  if (o.crack_branches && !o.crack_fuse)
-    throw std::runtime_error("the option '--crackBranches 1' needs the widths on the map (--crackFuse 1)");
-  if (o.crack_prune_given && !(o.crack_prune >= 0.0f && o.crack_prune <= 1024.0f))
-    throw std::runtime_error("the option '--crackPrune' takes a length in metres from 0 (nothing is pruned) to 1024");
-  if (o.crack_branches && !(o.crack_skeleton_step >= 0.0f && o.crack_skeleton_step <= 16.0f))
-    throw std::runtime_error("the option '--crackSkeletonStep' takes 0 (twice the link radius) or a band width in metres up to 16");
-  if (o.crack_skeleton && !(o.crack_skeleton_step >= 0.0f && o.crack_skeleton_step <= 16.0f))
-    throw std::runtime_error("the option '--crackSkeletonStep' takes 0 (twice the link radius) or a band width in metres up to 16");
-  if (o.crack_fuse && o.maskImageFolder.empty())
-    throw std::runtime_error("the option '--crackFuse 1' needs the masks (--mask_image_folder)");
-  if (o.crack_fuse && o.gpus > 1)
-    throw std::runtime_error("the option '--crackFuse 1' does not work with '--gpus N' above 1 (an index shard sees only its own "
-                             "points: the per-pixel keys of the shards would have to be merged across GPUs, which is not built)");
-  if (o.crack_fuse && o.enableMLS)
-    throw std::runtime_error("the option '--crackFuse 1' does not work with '--enableMLS 1' (the planes are fitted to the raw "
-                             "map; maps of the smoothed cloud are not built)");
-  if (o.geometry_maps && o.enableMLS)
-    throw std::runtime_error("the option '--geometryMaps 1' does not work with '--enableMLS 1' (the maps are rendered from the raw "
-                             "map; maps of the smoothed cloud are not built)");
-  if (o.ortho_by_facet && !o.facets)
-    throw std::runtime_error("the option '--orthoFrame facets' needs the facets of the map (--facets 1)");
-  if (o.facet_cylinders && !o.facets)
-    throw std::runtime_error("the option '--facetCylinders 1' needs the facets of the map (--facets 1)");
-  if (o.facets && o.gpus > 1)
-    throw std::runtime_error("the option '--facets 1' does not work with '--gpus N' above 1 (an index shard sees only its own "
-                             "points: the forests of the shards would have to be united across GPUs, which is not built)");
-  if (o.facets && o.stream_colour)
-    throw std::runtime_error("the option '--facets 1' does not work with '--streamColour 1' (a facet's points may lie in another chunk)");
-  if (o.facets && o.enableMLS)
-    throw std::runtime_error("the option '--facets 1' does not work with '--enableMLS 1' (the facets are those of the raw map; "
-                             "facets of the smoothed cloud are not built)");
-  if (o.facets && o.normal_radius == 0.0f)
-    throw std::runtime_error("the option '--facets 1' needs the map normals ('--normalRadius 0' turns them off)");
-  if (!o.compare_register && !o.register_value_flag.empty())
-    throw std::runtime_error("the option '" + o.register_value_flag + "' needs '--compareRegister 1'");
-  if (o.compare_register && o.compare_map.empty())
-    throw std::runtime_error("the option '--compareRegister 1' needs '--compareMap' (the base it brings onto the map)");
-  if (o.compare_register && o.gpus > 1)
-    throw std::runtime_error("the option '--compareRegister 1' does not work with '--gpus N' above 1 (an index shard sees only its own "
-                             "points; a registration across shards is not built)");
-  if (o.compare_register && o.stream_colour)
-    throw std::runtime_error("the option '--compareRegister 1' does not work with '--streamColour 1' (a row's partner may lie in another chunk)");
-  if (o.compare_register && o.enableMLS)
-    throw std::runtime_error("the option '--compareRegister 1' does not work with '--enableMLS 1' (the registration is onto the raw map; "
-                             "one onto the smoothed cloud is not built)");
-  if (o.compare_register && o.reg.max_plane_distance > o.reg.match_radius)
-    throw std::runtime_error("the argument for option '--registerMaxDistance' is invalid (above '--registerRadius')");
-  if (!o.compare_map.empty() && o.gpus > 1)
-    throw std::runtime_error("the option '--compareMap' does not work with '--gpus N' above 1 (an index shard sees only its own "
-                             "points; a comparison across shards is not built)");
-  if (!o.compare_map.empty() && o.stream_colour)
-    throw std::runtime_error("the option '--compareMap' does not work with '--streamColour 1' (a point's candidates may lie in another chunk)");
-  if (!o.compare_map.empty() && o.enableMLS)
-    throw std::runtime_error("the option '--compareMap' does not work with '--enableMLS 1' (the comparison is that of the raw map; "
-                             "a comparison of the smoothed cloud is not built)");
-  if (!o.compare_map.empty() && o.normal_radius == 0.0f)
-    throw std::runtime_error("the option '--compareMap' needs the map normals ('--normalRadius 0' turns them off)");
-  if (!o.balance_images && !o.balance_value_flag.empty())
-    throw std::runtime_error("the option '" + o.balance_value_flag + "' needs '--balanceImages 1'");
-  if (o.balance_exposure) {
-    auto refuse = [](const std::string &what, const std::string &why) {
-      throw std::runtime_error("the option '--balanceExposure 1' does not work with " + what + " (" + why + ")");
-    };
-    if (o.gpus > 1) refuse("'--gpus N' above 1", "the pair statistics of the index shards would have to be summed: not built");
-    if (o.stream_colour) refuse("'--streamColour 1'", "the pair statistics of the chunks would have to be summed: not built");
-  }
-  if (o.stream_colour) {
-    // every chunk is coloured on its own: what needs the whole smoothed cloud at once is refused here, before any GPU work
-    auto refuse = [](const std::string &what, const std::string &why) {
-      throw std::runtime_error("the option '--streamColour 1' does not work with " + what + " (" + why + ")");
-    };
-    if (!o.enableMLS) refuse("'--enableMLS 0'", "it streams the smoothing chain's chunks into the colour stage");
-    if (!o.skip_filtered_dumps) refuse("'--skip_filtered_dumps 0'", "a per-keyframe dump lists the whole cloud's visible points");
-    if (o.enableNIDOptimize) refuse("'--enableNIDOptimize 1'", "the NID stage reads the whole cloud");
-    if (o.enableInitialGuessManual) refuse("'--enableInitialGuessManual 1'", "the manual guess is not part of this build");
-    if (o.gpus > 1) refuse("'--gpus N' above 1", "the streamed form over several GPUs is not built");
-    if (o.cull_mode == PCP_CULL_HPR) refuse("'--cull hpr'", "a keyframe's hull is taken over the whole cloud");
-    if (o.match_mode == PCP_MATCH_RADIUS) refuse("'--matchBack radius'", "a sample's neighbours may lie in another chunk");
-    if (o.smooth_colors_radius > 0.0f) refuse("'--smoothColorsRadius'", "a point's neighbours may lie in another chunk");
-    if (!o.maskImageFolder.empty() && !o.fuse_masks)
-      refuse("'--mask_image_folder' without '--fuseMasks 1'", "the concatenated mask samples need every keyframe's visible points");
-    if (o.mls_upsampling >= 0 && o.mls_upsampling != PCP_UPSAMPLING_VOXEL_GRID_DILATION)
-      refuse("'--mlsUpsampling' other than vgd", "only VOXEL_GRID_DILATION is streamed");
-  }
-  return o;
-}
-
-static void usage(std::ostream &os) {
-  os << "Allowed options:\n"
-        "  -h [ --help ]                         Produce help message\n"
-        "  -p [ --point_cloud_path ] arg         Path to the point cloud data file\n"
-        "  -o [ --odometry_path ] arg            Path to odometry data file\n"
-        "  -i [ --images_folder ] arg            Path to directory containing images\n"
-        "  -m [ --mask_image_folder ] arg        Path to directory for segmented images\n"
-        "  -t [ --output_path ] arg (=.)         Path to save processed output\n"
-        "  --enableMLS arg (=0)                  Enable MLS smoothing\n"
-        "  --enableNIDOptimize arg (=0)          Enable NID-based camera pose optimization\n"
-        "  --enableInitialGuessManual arg (=0)   Enable manual pickup point based camera pose optimization\n"
-        "  --outputLeaf arg (=0)                 Also write the coloured cloud reduced to one row per voxel of this edge (--gpus 1)\n"
-        "  --skip_full_cloud arg (=0)            With --outputLeaf: do not fetch or write the full-resolution coloured clouds\n"
-        "  --deviceWriter arg (=0)               Format the rows of every ASCII PCD on the GPU (same bytes; --gpus 1;\n"
-        "                                        the --outputLeaf files are small and go through the host writer)\n"
-        "  --deviceReader arg (=0)               Parse the rows of the ASCII PCDs that are read on the GPU (same floats)\n"
-        "  --balanceExposure arg (=0)            One brightness gain per keyframe from co-visible map points (--gpus 1)\n"
-        "  --balanceImages arg (=0)              Colour-balance every keyframe on the GPU at upload: CLAHE on V, then a gamma table\n"
-        "  --claheClip arg (=1)                  With --balanceImages: CLAHE clip limit (0 = no clipping)\n"
-        "  --claheTiles arg (=8,8)               With --balanceImages: CLAHE tile grid x,y (1..16 each)\n"
-        "  --balanceGamma arg (=0.8)             With --balanceImages: gamma of the table (1 = identity)\n"
-        "  --geometryMaps arg (=0)               Also write range / xyz / normal / index images per keyframe as .npy (--gpus 1)\n"
-        "  --normalRadius arg (=0.1)             With --geometryMaps: neighbourhood of the map normals (0 = no normals)\n"
-        "  --crackMaps arg (=0)                  Also write the masks' squared distance and nearest-edge images as .npy (-m, --gpus 1)\n"
-        "  --crackThreshold arg (=0)             With --crackMaps / --crackWidth: a mask byte above this is foreground (0..255)\n"
-        "  --crackWidth arg (=0)                 Also write width / edges / flags / points images per keyframe as .npy (-m, --gpus 1)\n"
-        "  --crackPlaneRadius arg (=150)         With --crackWidth / --crackFuse: half side of the plane's window in pixels (1..181)\n"
-        "  --crackFuse arg (=0)                  Also write the fused widths per map point and the map's cracks (-m, --gpus 1)\n"
-        "  --crackLinkRadius arg (=0.02)         With --crackFuse: crack points this close (m) belong to one crack (0.005..1)\n"
-        "  --crackMinViews arg (=1)              With --crackFuse: keyframes with a width that a crack point needs (1..4096)\n"
-        "  --crackLength arg (=0)                With --crackFuse: also write every crack's length, ends and centreline\n"
-        "  --crackSkeleton arg (=0)              With --crackFuse: also write every crack's skeleton: branches, junctions, loops\n"
-        "  --crackDirection arg (=0)             With --crackFuse: also write every crack point's tangent and every crack's axis and class\n"
-        "  --crackUp arg (=0,0,1)                With --crackDirection: the vertical x,y,z (finite, not zero)\n"
-        "  --crackBranches arg (=0)              With --crackFuse: also write every crack arm by arm: branches, spurs pruned, lengths, widths, axes\n"
-        "  --crackPrune arg (=2 band widths)     With --crackBranches: one-attachment branches of fewer metres of bands are pruned (0 .. 1024)\n"
-        "  --orthoMap arg (=0)                   Also write one orthographic picture of the coloured cloud as .npy (--gpus 1)\n"
-        "  --orthoGsd arg (=0.01)                With --orthoMap: metres per pixel (1e-4..1)\n"
-        "  --orthoFill arg (=0)                  With --orthoMap: fill empty pixels from the nearest occupied one within R pixels\n"
-        "  --orthoFrame arg (=auto)              With --orthoMap: auto (fitted plane), facets (one map per planar facet), or ox,oy,oz,ux,uy,uz,vx,vy,vz\n"
-        "  --orthoDefects arg (=0)               With --orthoMap: also the surface defects of every map written (hollows, bulges: area, depth, volume)\n"
-        "  --defectThreshold arg (=0.002)        With --orthoDefects: metres of deviation that make a defect (2^-20..1)\n"
-        "  --defectWindow arg (=0)               With --orthoDefects: half side W of the reference window in pixels (0: against the frame's own surface)\n"
-        "  --defectRefine arg (=0)               With --defectWindow: a second reference from the pixels the first pass left unclassed\n"
-        "  --defectMinSupport arg (=1)           With --defectWindow: surface pixels a window needs\n"
-        "  --defectMinPixels arg (=1)            With --orthoDefects: pixels a region needs to be kept\n"
-        "  --defectClasses arg (=both)           With --orthoDefects: hollow, bulge or both\n"
-        "  --orthoTexture arg (=0)               With --orthoMap: also the orthophoto, k fine pixels per pixel, from the keyframe images (1..16)\n"
-        "  --orthoTextureViews arg (=1)          With --orthoTexture: views that enter a colour (1 = sharpest, 5 = the reference's mean)\n"
-        "  --orthoTextureInterp arg (=1)         With --orthoTexture: bilinear depth between map pixels\n"
-        "  --orthoTextureStep arg (=0.05)        With --orthoTexture: ... across depth steps up to this many metres\n"
-        "  --crackSkeletonStep arg (=0)          With --crackSkeleton: the band width in metres (0: twice the link radius)\n"
-        "  --facets arg (=0)                     Also write the planar facets of the map: a label per point and one record per facet (--gpus 1)\n"
-        "  --facetRadius arg (=0.1)              With --facets: points this close (m) may be linked (0.005..1)\n"
-        "  --facetAngle arg (=10)                With --facets: ... when their normals differ by at most this many degrees (0..45)\n"
-        "  --facetPlaneTol arg (=0.01)           With --facets: ... and each lies this close (m) to the other's tangent plane (1e-4..0.1)\n"
-        "  --facetMaxCurvature arg (=0.02)       With --facets: points of a larger curvature take no part (0..1)\n"
-        "  --facetMinPoints arg (=1000)          With --facets: a facet has at least this many points\n"
-        "  --facetMaxRms arg (=0.01)             With --facets: a facet is planar up to this rms distance (m) to its plane\n"
-        "  --facetCylinders arg (=0)             With --facets: fit a cylinder to every facet that is not planar; with --orthoFrame facets unroll those that are one\n"
-        "  --orthoTextureCylinders arg (=0)      With --orthoTexture, --facetCylinders and --orthoFrame facets: also the orthophoto of every unrolled map\n"
-        "  --compareMap arg                      Also compare the map with this earlier survey (PCD): signed distance, level of detection and status per point (--gpus 1)\n"
-        "  --compareRadius arg (=0.03)           With --compareMap: radius (m) of the cylinder along a point's normal (0.005..0.5)\n"
-        "  --compareDepth arg (=0.05)            With --compareMap: half length (m) of that cylinder (0.005..0.5; sqrt(radius^2 + depth^2) at most 0.5)\n"
-        "  --compareMinPoints arg (=5)           With --compareMap: a distance needs this many points of each survey in the cylinder (2 or more)\n"
-        "  --compareRegError arg (=0)            With --compareMap: registration error (m) added to the level of detection\n"
-        "  --compareRegister arg (=0)            With --compareMap: first bring the survey onto the map by point-to-plane ICP (compare/registration.json, base_transform.txt)\n"
-        "  --registerRadius arg (=0.05)          With --compareRegister 1: a row's partner is its nearest map point within this radius (m, 0.005..0.5)\n"
-        "  --registerMaxDistance arg (=0.02)     With --compareRegister 1: pairs further apart than this along the normal (m) are left out of the fit\n"
-        "  --registerStride arg (=1)             With --compareRegister 1: every k-th row of the survey is a query\n"
-        "  --registerIterations arg (=20)        With --compareRegister 1: at most this many iterations (1..1000)\n";
-}
 
 class Processor {
  public:

@@ -1,6 +1,7 @@
 """g++ build of the C++ host side above the C ABI (pointcloudprocessor_amd/host/)."""
 from __future__ import annotations
 
+import glob
 import os
 import subprocess
 
@@ -36,7 +37,14 @@ TARGETS = {
     "ortho_defects_selftest": ["ortho_defects_selftest.cpp"],  # csrc/pcp_ortho_defects.hpp compiled for the host (CPU only)
     "facets_selftest": ["facets_selftest.cpp"],  # csrc/pcp_facets.hpp compiled for the host (CPU only)
     "tile_bounds_selftest": ["tile_bounds_selftest.cpp"],  # csrc/pcp_tile_box.hpp compiled for the host (CPU only)
+    "options_probe": ["options_probe.cpp"],  # host/cli_options.hpp: parses command lines from stdin (CPU only: never a GPU job)
 }
+
+
+def header_deps() -> list:
+    """The headers every target is taken to depend on: all of host/ and csrc/, and the C ABI."""
+    return sorted(glob.glob(os.path.join(HOST, "*.hpp"))) + sorted(glob.glob(os.path.join(_build.CSRC, "*.hpp"))) + [
+        os.path.join(_build.INCLUDE, "pcp_hip.h")]
 
 
 def build(force: bool = False) -> dict:
@@ -44,10 +52,7 @@ def build(force: bool = False) -> dict:
     out = {}
     for name, srcs in TARGETS.items():
         exe = os.path.join(BIN, name)
-        deps = [os.path.join(HOST, s) for s in srcs] + [os.path.join(HOST, "pcp_shim.hpp"), os.path.join(HOST, "pcp_multi.hpp"), os.path.join(HOST, "pcd_io.hpp"), os.path.join(HOST, "image_io.hpp"), os.path.join(HOST, "pcd_device_reader.hpp"),
-                                                       os.path.join(_build.CSRC, "pcp_ascii_parse.hpp"), os.path.join(_build.CSRC, "pcp_ascii.hpp"), os.path.join(_build.CSRC, "pcp_visit_forms.hpp"), os.path.join(_build.CSRC, "pcp_voxel_reduce.hpp"), os.path.join(_build.CSRC, "pcp_normals.hpp"), os.path.join(_build.CSRC, "pcp_ortho.hpp"), os.path.join(_build.CSRC, "pcp_ortho_cyl.hpp"), os.path.join(_build.CSRC, "pcp_ortho_texture.hpp"), os.path.join(_build.CSRC, "pcp_ortho_defects.hpp"), os.path.join(_build.CSRC, "pcp_crack_width.hpp"), os.path.join(_build.CSRC, "pcp_crack_fuse.hpp"), os.path.join(_build.CSRC, "pcp_crack_length.hpp"), os.path.join(_build.CSRC, "pcp_crack_skeleton.hpp"), os.path.join(_build.CSRC, "pcp_crack_direction.hpp"), os.path.join(_build.CSRC, "pcp_crack_branch.hpp"), os.path.join(_build.CSRC, "pcp_image_balance.hpp"), os.path.join(_build.CSRC, "pcp_hsv.hpp"), os.path.join(_build.CSRC, "pcp_facets.hpp"), os.path.join(_build.CSRC, "pcp_eigen33_host.hpp"), os.path.join(_build.CSRC, "pcp_tile_box.hpp"),
-                                                       os.path.join(_build.INCLUDE, "pcp_hip.h")]
-        deps = [d for d in deps if os.path.exists(d)]
+        deps = [os.path.join(HOST, s) for s in srcs] + header_deps()
         stale = force or not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps)
         if stale:
             extra = os.environ.get("PCP_HOST_CXXFLAGS", "").split()  # e.g. -fsanitize=address,undefined (CPU-side checks)
