@@ -20,6 +20,7 @@
 #include <cfloat>
 #include <cstdlib>
 
+#include "pcp_colour_defer.hpp"
 #include "pcp_device.hpp"
 #include "pcp_hsv.hpp"
 #include "pcp_scan.hpp"
@@ -675,6 +676,8 @@ __global__ __launch_bounds__(kBlock) void k_colour_pass(const float *__restrict_
   }
 }
 
+// (Since k_colour_pass_deferred, below, this kernel runs where a 32-bit texel index does not span the range and under
+// PCP_COLOUR_DEFER=0; the tests run the two side by side.)
 // k_colour_pass<true, 2, true, false> -- the whole-run call of the bench and the CLI: common configuration, round-trip match, one
 // shot, no labels -- for a range of at most 64 mask words (2048 keyframes), with the depth pass's walk of the tile's words: one
 // load of them (lane l holds word (f0 >> 5) + l, masked to the range), a ballot, and only the words that keep a keyframe are walked.
@@ -737,6 +740,81 @@ __global__ __launch_bounds__(kBlock) void k_colour_pass_preload(const float *__r
   }
   if (!live) return;
   rgba[perm[j]] = t.finalise();  // scattered straight into input order, see k_colour_pass
+}
+
+// k_colour_pass_preload with the texel fetches taken out of the visit.  That kernel fetches a texel for every kept sample --
+// nearly every one a 64-B sector of its own -- while only the five best of a point reach the result: on the bench's scene more
+// than half of the fetched texels are evicted from the list again or never enter it (profiles/deferred_texel_probe.md).  A
+// texel's value decides nothing in the walk, so here the list holds (score, 32-bit texel index) pairs (Top5Deferred), and when
+// the walk is over each lane gathers the texels of its occupied slots, all issued before the first is used, and finishes as
+// Top5::finalise() does.  The same texels in the same list: the same bits.
+// The index is (f - f0) * image_px + pixel, the low word of the offset that kernel computes: the host launches this kernel only
+// where (f1 - f0) * image_px <= 2^32 (deferred_index_fits, pcp_colour_defer.hpp) and k_colour_pass_preload otherwise or under
+// PCP_COLOUR_DEFER=0.  The walk and the visit up to the keep rule are those of k_colour_pass_preload to the letter.
+template <bool kK3>
+__global__ __launch_bounds__(kBlock) void k_colour_pass_deferred(const float *__restrict__ x, const float *__restrict__ y,
+                                                                 const float *__restrict__ z, int64_t n, DevCamera cam_in,
+                                                                 const DevFrame *__restrict__ frames, int32_t f0, int32_t f1,
+                                                                 const uint32_t *__restrict__ depth, int64_t cells,
+                                                                 const uint32_t *__restrict__ tile_mask, int32_t words,
+                                                                 const uint32_t *__restrict__ images, int64_t image_px,
+                                                                 const int32_t *__restrict__ perm, uint32_t *__restrict__ rgba) {
+  DevCamera cam = common_camera<true>(cam_in);
+  cam.match_mode = PCP_MATCH_ROUNDTRIP;
+  const int lane = threadIdx.x & 63;
+  const int64_t j = static_cast<int64_t>(xcd_chunked_block()) * kBlock + threadIdx.x;
+  const bool live = j < n;
+  // a wavefront wholly past the cloud (tail of a 256-thread workgroup) has no tile: its mask words do not exist
+  if (!__ballot(live)) return;
+  const float px = live ? x[j] : 0.0f, py = live ? y[j] : 0.0f, pz = live ? z[j] : 0.0f;
+  const int64_t tile = __builtin_amdgcn_readfirstlane(static_cast<int32_t>(j >> 6));
+  // every camera coordinate of this wavefront is finite (divide_xy_by_z)
+  const bool finite_sure = cam.frames_bounded != 0 && __all(fabsf(px) <= 0x1p40f && fabsf(py) <= 0x1p40f && fabsf(pz) <= 0x1p40f);
+  Top5Deferred t;
+  t.init();
+  const int32_t wbase = f0 >> 5, my_w = wbase + lane;  // the host launches this kernel for ((f1 - 1) >> 5) - wbase < 64 only
+  uint32_t my_todo = 0u;
+  if (my_w <= (f1 - 1) >> 5) my_todo = range_bits(my_w, f0, f1) & tile_mask[tile * words + my_w];
+  for (unsigned long long walk = __builtin_amdgcn_ballot_w64(my_todo != 0u); walk; walk &= walk - 1ull) {
+    const int32_t wl = __builtin_ctzll(walk);
+    const int32_t w = wbase + wl;
+    uint32_t todo = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int32_t>(my_todo), wl));
+    while (todo) {
+      const int32_t f = (w << 5) + __builtin_ctz(todo);
+      todo &= todo - 1u;
+      const DevFrame &fr = frames[f];
+      // the refined masks only keep pairs with a candidate lane: the fp32 rejection test cannot skip the wavefront
+      const auto p = project_point_batched<false, kK3>(cam, fr.w2c, px, py, pz, true, finite_sure);
+      const bool cand = live && p.image_ok && p.map_ok;
+      if (cand) {
+        const uint32_t dbits = cam.enable_zbuf ? depth[static_cast<uint64_t>(static_cast<uint32_t>(f)) * static_cast<uint32_t>(cells) + static_cast<uint32_t>(p.cell)] : 0u;
+        // A4 keep rule (view_culling.cpp:135-171)
+        bool keep = true;
+        if (cam.enable_zbuf) keep = keep_by_depth(p.xc, p.yc, p.zc, static_cast<double>(__uint_as_float(dbits)) + cam.slack);
+        float sx = p.xc, sy = p.yc, sz = p.zc;
+        if (cam.match_mode == PCP_MATCH_ROUNDTRIP && keep) keep = roundtrip_sample(cam, fr, px, py, pz, sx, sy, sz);
+        // (f - f0 is wavefront-uniform: a scalar product and one vector add; below 2^32 by the host's condition)
+        if (keep)
+          t.insert(final_score<true>(sx, sy, sz, fr.px, fr.py, fr.pz),
+                   static_cast<uint32_t>(f - f0) * static_cast<uint32_t>(image_px) + static_cast<uint32_t>(p.pixel));
+      }
+    }
+  }
+  if (!live) return;
+  const int64_t o = perm[j];
+  // The list is final.  The occupied slots are a prefix of it; a lane with an empty list fetches nothing and stores 0.
+  // texel = B | G<<8 | R<<16 | mask<<24; its low 24 bits are 0x00RRGGBB (PointCloudProcessor.cpp:760-762)
+  const uint32_t *__restrict__ first = images + static_cast<uint64_t>(static_cast<uint32_t>(f0)) * static_cast<uint32_t>(image_px);
+  // (five scalars, not an array: with an array the first fetch was waited for before the second was issued)
+  uint32_t c0 = 0u, c1 = 0u, c2 = 0u, c3 = 0u, c4 = 0u;
+  if (t.s0 >= 0.0f) c0 = first[t.i0];
+  if (t.s1 >= 0.0f) c1 = first[t.i1];
+  if (t.s2 >= 0.0f) c2 = first[t.i2];
+  if (t.s3 >= 0.0f) c3 = first[t.i3];
+  if (t.s4 >= 0.0f) c4 = first[t.i4];
+  // (finalise() reads the three colour bytes of a texel and never its mask byte: the mask to 24 bits is in the extraction;
+  // written out here it was sunk into the branches above, each with a wait of its own)
+  rgba[o] = t.s0 >= 0.0f ? t.finalise(c0, c1, c2, c3, c4) : 0u;  // scattered straight into input order, see k_colour_pass
 }
 
 // finalise from stored state (multi-batch runs)
@@ -2262,10 +2340,16 @@ static int colour_pass_impl(pcp_context *ctx, int32_t frame_begin, int32_t frame
     // wider ranges (more than 2048 keyframes) keep k_colour_pass<true, 2, true, false>
     if (common && ctx->dcam.match_mode == PCP_MATCH_ROUNDTRIP && flags == 4 && !label && ctx->tile_mask.p &&
         ((frame_end - 1) >> 5) - (frame_begin >> 5) < 64) {
-      hipLaunchKernelGGL(ctx->k3_dropped ? k_colour_pass_preload<false> : k_colour_pass_preload<true>, dim3(blocks_for(ctx->n)), dim3(kBlock), 0, ctx->stream, ctx->sxyz.p,
+      // ... with the texel fetches after the walk where a 32-bit texel index spans the range (k_colour_pass_deferred);
+      // PCP_COLOUR_DEFER=0 keeps the fetch inside the visit (read per call: the tests run both forms in one process)
+      const int64_t image_px = static_cast<int64_t>(ctx->dcam.img_w) * ctx->dcam.img_h;
+      const char *de = std::getenv("PCP_COLOUR_DEFER");
+      const bool defer = deferred_index_fits(frame_begin, frame_end, image_px) && !(de && de[0] == '0');
+      auto whole_run = ctx->k3_dropped ? k_colour_pass_preload<false> : k_colour_pass_preload<true>;
+      if (defer) whole_run = ctx->k3_dropped ? k_colour_pass_deferred<false> : k_colour_pass_deferred<true>;
+      hipLaunchKernelGGL(whole_run, dim3(blocks_for(ctx->n)), dim3(kBlock), 0, ctx->stream, ctx->sxyz.p,
                          ctx->sxyz.p + plane, ctx->sxyz.p + 2 * plane, ctx->n, ctx->dcam, ctx->frames.p, frame_begin, frame_end,
-                         ctx->depth.p, cells_of(ctx), ctx->tile_mask.p, ctx->mask_words, ctx->images.p,
-                         static_cast<int64_t>(ctx->dcam.img_w) * ctx->dcam.img_h, ctx->perm.p, result);
+                         ctx->depth.p, cells_of(ctx), ctx->tile_mask.p, ctx->mask_words, ctx->images.p, image_px, ctx->perm.p, result);
     } else {
       hipLaunchKernelGGL(kernel, dim3(blocks_for(ctx->n)), dim3(kBlock), 0, ctx->stream, ctx->sxyz.p, ctx->sxyz.p + plane,
                          ctx->sxyz.p + 2 * plane, ctx->n, ctx->dcam, ctx->frames.p, frame_begin, frame_end, ctx->depth.p,

@@ -539,4 +539,61 @@ struct Top5 {
   }
 };
 
+// The list of k_colour_pass_deferred: an entry is (score, 32-bit texel index) and the texels are fetched once the walk is
+// over, for the entries that are still listed (a texel's value never decides an insertion).  No colour, no keyframe, no count:
+// a slot is occupied when its score is >= 0 (scores are >= 0.2, empty slots hold -1).  Same order rule as Top5::insert to the
+// letter -- strict comparisons, so a new entry goes behind equal scores and keyframes arrive ascending.  A type of its own, not
+// a form of Top5: the registers of the kernels that hold a Top5 are pinned (tests/test_label_fusion_cpu.py).
+struct Top5Deferred {
+  float s0, s1, s2, s3, s4;
+  uint32_t i0, i1, i2, i3, i4;
+  __device__ __forceinline__ void init() {
+    s0 = s1 = s2 = s3 = s4 = -1.0f;
+    i0 = i1 = i2 = i3 = i4 = 0u;
+  }
+  __device__ __forceinline__ void insert(float s, uint32_t i) {
+    if (s > s4) {
+      s4 = s; i4 = i;
+      if (s4 > s3) {
+        float ts = s3; s3 = s4; s4 = ts;
+        uint32_t ti = i3; i3 = i4; i4 = ti;
+        if (s3 > s2) {
+          ts = s2; s2 = s3; s3 = ts;
+          ti = i2; i2 = i3; i3 = ti;
+          if (s2 > s1) {
+            ts = s1; s1 = s2; s2 = ts;
+            ti = i1; i1 = i2; i2 = ti;
+            if (s1 > s0) {
+              ts = s0; s0 = s1; s1 = ts;
+              ti = i0; i0 = i1; i1 = ti;
+            }
+          }
+        }
+      }
+    }
+  }
+  // Top5::finalise() on the fetched texels c0 ... c4 (mask<<24 | 0x00RRGGBB, the mask byte is not read) of the occupied slots: the same fp32 sums in list order, the
+  // same quotients, truncation and `has`.  The caller has checked that slot 0 is occupied.
+  __device__ __forceinline__ uint32_t finalise(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t c4) const {
+    float total = 0.0f, r = 0.0f, g = 0.0f, b = 0.0f;
+    const float ss[5] = {s0, s1, s2, s3, s4};
+    const uint32_t c[5] = {c0, c1, c2, c3, c4};
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      if (ss[k] >= 0.0f) {
+        const float s = ss[k];
+        r += static_cast<float>((c[k] >> 16) & 0xffu) * s;
+        g += static_cast<float>((c[k] >> 8) & 0xffu) * s;
+        b += static_cast<float>(c[k] & 0xffu) * s;
+        total += s;
+      }
+    }
+    const uint32_t ri = static_cast<uint32_t>(r / total) & 0xffu;
+    const uint32_t gi = static_cast<uint32_t>(g / total) & 0xffu;
+    const uint32_t bi = static_cast<uint32_t>(b / total) & 0xffu;
+    const uint32_t has = (ri | gi | bi) ? 1u : 0u;  // removePointsWithNoColor hpp:238-252
+    return ri | (gi << 8) | (bi << 16) | (has << 24);
+  }
+};
+
 }  // namespace pcp

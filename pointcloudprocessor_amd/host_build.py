@@ -37,6 +37,7 @@ TARGETS = {
     "ortho_defects_selftest": ["ortho_defects_selftest.cpp"],  # csrc/pcp_ortho_defects.hpp compiled for the host (CPU only)
     "facets_selftest": ["facets_selftest.cpp"],  # csrc/pcp_facets.hpp compiled for the host (CPU only)
     "tile_bounds_selftest": ["tile_bounds_selftest.cpp"],  # csrc/pcp_tile_box.hpp compiled for the host (CPU only)
+    "colour_defer_selftest": ["colour_defer_selftest.cpp"],  # csrc/pcp_colour_defer.hpp compiled for the host (CPU only)
     "options_probe": ["options_probe.cpp"],  # host/cli_options.hpp: parses command lines from stdin (CPU only: never a GPU job)
 }
 

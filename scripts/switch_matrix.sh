@@ -23,3 +23,4 @@ run smooth PCP_CSS_HALO=1 -- tests/test_smooth_stream_gpu.py -k oracle
 run smooth PCP_VGD_GRID=fit -- tests/test_smooth_stream_gpu.py
 run smooth PCP_SOR_BALL=1.2 -- tests/test_smooth_stream_gpu.py
 run smooth PCP_SOR_BALL=2.4 -- tests/test_smooth_stream_gpu.py tests/test_sor_gpu.py
+run colour PCP_COLOUR_DEFER=0 -- tests/test_mask_preload_gpu.py tests/test_k3_term_gpu.py tests/test_colour_defer_gpu.py
