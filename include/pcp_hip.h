@@ -99,7 +99,11 @@ extern "C" {
                                 entry points added, no layout changed: pcp_default_register_params, pcp_compare_register /
                                 _register_sums / _register_host, pcp_compare_base_transform, pcp_compare_set_base_transform,
                                 pcp_register_solve_host (registration of the earlier survey onto the map; nothing runs unless
-                                called) */
+                                called);
+                                entry points added, no layout changed: pcp_default_coarse_params, pcp_coarse_descriptors / _fetch /
+                                _host, pcp_coarse_match / _fetch / _host, pcp_coarse_score / _host, pcp_coarse_hypothesis_host,
+                                pcp_coarse_refit_host, pcp_compare_base_normals_fetch, pcp_compare_register_coarse / _host (coarse
+                                registration of the earlier survey from any pose; nothing runs unless called) */
 
 #define PCP_OK 0
 #define PCP_ERR_INVALID (-1) /* bad argument */
@@ -1122,6 +1126,89 @@ int pcp_compare_set_base_transform(pcp_context *ctx, const double *T16);
 int pcp_compare_register_host(const pcp_register_params *p, int64_t n, const float *xyz, const float *normals, int64_t n_base,
                               const float *base_xyz, const double *T_in16, int32_t run_loop, int64_t *out_sums60, double *out_T16,
                               double *out_log, int32_t *out_status, float *out_rows);
+
+/* ---- coarse registration (no counterpart in the reference; spin images, Johnson & Hebert 1999; Horn 1987) ------------------- */
+/* Coarse registration of the base of the map comparison onto the uploaded map from an arbitrary pose, good enough for
+ * pcp_compare_register to finish ("Coarse registration", CG1-CG9).  Opt-in: nothing runs unless one of these is
+ * called, PCP_ABI_VERSION is unchanged and a caller detects support by the symbols.  Kernels are timed under PCP_K_MISC.
+ * Whole-map contexts only.  side 0 is the uploaded map, side 1 the base's ORIGINAL rows (whatever its transform is).
+ *
+ * Keypoints (CG1): the rows whose index is a multiple of the side's stride, with three finite coordinates and a valid normal
+ * (as in pcp_compare_register).  A keypoint's slot is row / stride; a side has ceil(rows / stride) slots, at most 2^18 (else
+ * PCP_ERR_RANGE: raise the stride).  Map normals: `normals` (3 floats per point) or, NULL, the live estimate of
+ * pcp_estimate_normals.  Base normals: `base_normals` (3 floats per row handed to pcp_compare_set_base) or, NULL, estimated
+ * on the device at normal_radius over the original rows by the normals stage's own code; the map's live estimate is not
+ * touched, and pcp_compare_base_normals_fetch returns the estimate (3 floats per row; PCP_ERR_STATE without one).
+ * Descriptor (CG2): with N = rint(n * 2^11), N2 = N.N, and for every finite point of the SAME side within support_radius
+ * (fl32 d2 <= t as in pcp_estimate_normals, the keypoint included) q = rint(d * 2^20), h = q.N, W = q.q * N2 - h*h: radial bin
+ * = the largest k <= 7 with e_k^2 * N2 <= W, height bin likewise with h*h, e_k = floor(k * E / 8), E = rint(support_radius *
+ * 2^20).  n_i = the number of neighbours; the descriptor is valid iff n_i >= min_neighbours and (n_i - those of height bin 0)
+ * * 1000 >= min_offplane_permille * n_i; D[radial * 8 + height] = floor(count * 65535 / n_i).
+ * pcp_coarse_descriptors: one side; out_counts3 = slots, keypoints, valid descriptors.  _fetch: per slot 64 uint16, n_i, the
+ * state (0 no keypoint, 1 keypoint without a valid descriptor, 2 valid) and the keypoint's coordinates (each nullable).
+ * The map's descriptors live until the next upload or pcp_estimate_normals, the base's until the next pcp_compare_set_base.
+ * Matching (CG3), pcp_coarse_match: needs both sides' descriptors.  Ordinals count the valid descriptors of a side in
+ * ascending row.  Key = (L1 << 32 | ordinal), L1 the exact sum of |D_a - D_b|; per valid keypoint the least and the second
+ * least key over the other side.  (b, m) corresponds iff m is b's best, L1_best * 256 <= ratio_q8 * L1_second (no second: it
+ * passes) and, with mutual, b is m's best; more than 2^18: PCP_ERR_RANGE.  _fetch: out_pairs (2 per correspondence: base
+ * ordinal, map ordinal), out_base_keys / out_map_keys (2 uint64 per valid keypoint; ~0 = none), each nullable.
+ * Scoring (CG5), pcp_coarse_score: n_frames frames of 15 doubles (R row-major, pivot c, t: x' = R (x - c) + c + t in
+ * csrc/pcp_register.hpp's fixed fp64 sequence) over the live correspondences: b' = fl32(x'), d = fl32(m - b'), an inlier iff
+ * every |d_a| <= 1 and q.q <= floor((inlier_distance * 2^20)^2).  out_counts: one per frame; out_flags (nullable): one byte
+ * per frame and correspondence.
+ * pcp_compare_register_coarse: the whole stage.  Hypothesis h < hypotheses draws three correspondences (splitmix64's
+ * finaliser over seed + 0x9E3779B97F4A7C15 * (3 h + slot + 1), the high 32 bits times C, shifted right by 32) and is refused
+ * when an ordinal repeats (1), a map side is shorter than min_side (2), a side differs between the clouds by more than
+ * side_tolerance (3) or either triangle's smallest angle is below min_angle_deg (4: |s12 x s13|^2 < sin^2(min_angle_deg) times
+ * the squared product of its two longest sides); else its frame
+ * takes the base triangle's orthonormal frame and centroid onto the map's.  The winner has the most inliers (ties: lowest h);
+ * fewer than min_inliers: status 2 and the base's transform stays.  Else Horn's quaternion solution over the winner's inliers
+ * (exact integer sums of 2^-16 m quanta about the two boxes' midpoints, 4 x 4 cyclic Jacobi, 12 sweeps) is scored once and
+ * kept iff it has at least as many inliers, and the kept frame is set exactly as pcp_compare_set_base_transform would
+ * (a compare result is dropped).  out_report16: keypoints map, base; valid descriptors map, base; correspondences; hypotheses
+ * scored, refused; inliers of the winner, of the best hypothesis rotated more than 10 degrees from it, of the refit, kept;
+ * status (0 found, 2 too few inliers); the winner's h and its three ordinals (-1 without).  out_T16: the base's transform
+ * after the call.  out_inliers (nullable, 2^18 bytes suffice): one byte per correspondence under the kept frame.
+ * Bounds (else PCP_ERR_INVALID; NaN fails every test): 0.02 <= support_radius <= 0.25, 0.005 <= normal_radius <= 1, 0.005 <=
+ * inlier_distance <= 0.5, 0 < min_side, 0 <= side_tolerance, 0 < min_angle_deg <= 60, strides >= 1, min_neighbours >= 1, 0 <=
+ * min_offplane_permille <= 1000, 0 <= ratio_q8 <= 256, mutual 0 or 1, 1 <= hypotheses <= 65536, min_inliers >= 3.  Without a
+ * cloud, a base, map normals, or the stage before: PCP_ERR_STATE.  Like every call that builds the search grid the
+ * descriptor calls invalidate an open pcp_mls_stream / pcp_cloud_smooth_stream and a pcp_sor_partial.
+ * The _host forms: host only, no context, no GPU, the same by brute force with the arithmetic the kernels use; n, n_base <=
+ * 65536, arrays interleaved, base_normals required.  They also assert CG2's ranges per pair in 128-bit arithmetic.
+ * pcp_coarse_hypothesis_host: hypothesis h over C correspondences (cb, cm: 3 floats each) about pivot3: the refusal code,
+ * the three ordinals, the frame.  pcp_coarse_refit_host: CG6's refit over the flagged correspondences.  The message is at
+ * pcp_last_error(NULL). */
+typedef struct pcp_coarse_params {
+  float support_radius, normal_radius, inlier_distance, min_side, side_tolerance, min_angle_deg;
+  int32_t map_stride, base_stride, min_neighbours, min_offplane_permille, ratio_q8, mutual, hypotheses, min_inliers;
+  uint64_t seed;
+} pcp_coarse_params;
+void pcp_default_coarse_params(pcp_coarse_params *p); /* 0.2, 0.1, 0.05, 0.3, 0.05, 15; 4, 4, 20, 100, 230, 1, 4096, 10; 1 */
+int pcp_coarse_descriptors(pcp_context *ctx, const pcp_coarse_params *p, int32_t side, const float *normals, int64_t *out_counts3);
+int pcp_coarse_descriptors_fetch(pcp_context *ctx, int32_t side, uint16_t *out_desc64, uint32_t *out_total, uint8_t *out_state,
+                                 float *out_xyz);
+int pcp_compare_base_normals_fetch(pcp_context *ctx, float *out_normals);
+int pcp_coarse_match(pcp_context *ctx, const pcp_coarse_params *p, int64_t *out_count);
+int pcp_coarse_match_fetch(pcp_context *ctx, int32_t *out_pairs, uint64_t *out_base_keys, uint64_t *out_map_keys);
+int pcp_coarse_score(pcp_context *ctx, const pcp_coarse_params *p, int64_t n_frames, const double *frames15, int64_t *out_counts,
+                     uint8_t *out_flags);
+int pcp_compare_register_coarse(pcp_context *ctx, const pcp_coarse_params *p, const float *normals, const float *base_normals,
+                                int64_t *out_report16, double *out_T16, uint8_t *out_inliers);
+int pcp_coarse_descriptors_host(const pcp_coarse_params *p, int32_t side, int64_t n, const float *xyz, const float *normals,
+                                uint16_t *out_desc64, uint32_t *out_total, uint8_t *out_state, int64_t *out_counts3);
+int pcp_coarse_match_host(const pcp_coarse_params *p, int64_t k_base, const uint16_t *base_desc64, int64_t k_map,
+                          const uint16_t *map_desc64, int32_t *out_pairs, int64_t *out_count, uint64_t *out_base_keys,
+                          uint64_t *out_map_keys);
+int pcp_coarse_hypothesis_host(const pcp_coarse_params *p, int64_t c, const float *cb, const float *cm, const double *pivot3, int32_t h,
+                               int32_t *out_code, int32_t *out_triple3, double *out_frame15);
+int pcp_coarse_score_host(const pcp_coarse_params *p, int64_t n_frames, const double *frames15, int64_t c, const float *cb,
+                          const float *cm, int64_t *out_counts, uint8_t *out_flags);
+int pcp_coarse_refit_host(int64_t c, const float *cb, const float *cm, const uint8_t *flags, const double *pivot_base3,
+                          const double *pivot_map3, double *out_frame15);
+int pcp_compare_register_coarse_host(const pcp_coarse_params *p, int64_t n, const float *xyz, const float *normals, int64_t n_base,
+                                     const float *base_xyz, const float *base_normals, int64_t *out_report16, double *out_T16,
+                                     uint8_t *out_inliers);
 
 /* ---- mask distance maps (scripts/genNormAndDistanceMask.py: class Crack, preprocess :150-198, cv2.threshold :167, */
 /* ---- scipy.ndimage.distance_transform_edt :9,168) ------------------------------------------------------------------ */

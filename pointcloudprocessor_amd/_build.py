@@ -17,8 +17,8 @@ LIB_PATH = os.path.join(LIB_DIR, "libpcp_hip.so")
 INCLUDE = os.path.join(_ROOT, "include")
 
 SOURCES = ["pcp_context.hip", "pcp_colour.hip", "pcp_mls.hip", "pcp_grid.hip", "pcp_nid.hip", "pcp_hpr.hip", "pcp_colour_smooth.hip", "pcp_match.hip", "pcp_jpeg.hip",
-           "pcp_stream_colour.hip", "pcp_ascii.hip", "pcp_ascii_parse.hip", "pcp_exposure.hip", "pcp_voxel_reduce.hip", "pcp_normals.hip", "pcp_compare.hip", "pcp_register.hip", "pcp_mask_edt.hip", "pcp_ortho.hip", "pcp_ortho_texture.hip", "pcp_ortho_defects.hip", "pcp_facets.hip", "pcp_crack_width.hip", "pcp_crack_fuse.hip", "pcp_crack_length.hip", "pcp_crack_skeleton.hip", "pcp_crack_direction.hip", "pcp_crack_branch.hip", "pcp_image_balance.hip"]
-HEADERS = ["pcp_internal.hpp", "pcp_device.hpp", "pcp_scan.hpp", "pcp_hsv.hpp", "pcp_exact.hpp", "pcp_ascii.hpp", "pcp_ascii_parse.hpp", "pcp_visit_forms.hpp", "pcp_voxel_reduce.hpp", "pcp_eigen33.hpp", "pcp_eigen33_selftest.hpp", "pcp_eigen33_host.hpp", "pcp_facets.hpp", "pcp_normals.hpp", "pcp_compare.hpp", "pcp_register.hpp", "pcp_mask_edt.hpp", "pcp_ortho.hpp", "pcp_ortho_cyl.hpp", "pcp_ortho_texture.hpp", "pcp_ortho_defects.hpp", "pcp_tile_classify.hpp", "pcp_tile_box.hpp", "pcp_crack_width.hpp", "pcp_crack_fuse.hpp", "pcp_crack_length.hpp", "pcp_crack_skeleton.hpp", "pcp_crack_direction.hpp", "pcp_crack_branch.hpp", "pcp_crack_map.hpp", "pcp_image_balance.hpp", "pcp_cell_search.hpp", "pcp_colour_defer.hpp"]
+           "pcp_stream_colour.hip", "pcp_ascii.hip", "pcp_ascii_parse.hip", "pcp_exposure.hip", "pcp_voxel_reduce.hip", "pcp_normals.hip", "pcp_compare.hip", "pcp_register.hip", "pcp_coarse.hip", "pcp_mask_edt.hip", "pcp_ortho.hip", "pcp_ortho_texture.hip", "pcp_ortho_defects.hip", "pcp_facets.hip", "pcp_crack_width.hip", "pcp_crack_fuse.hip", "pcp_crack_length.hip", "pcp_crack_skeleton.hip", "pcp_crack_direction.hip", "pcp_crack_branch.hip", "pcp_image_balance.hip"]
+HEADERS = ["pcp_internal.hpp", "pcp_device.hpp", "pcp_scan.hpp", "pcp_hsv.hpp", "pcp_exact.hpp", "pcp_ascii.hpp", "pcp_ascii_parse.hpp", "pcp_visit_forms.hpp", "pcp_voxel_reduce.hpp", "pcp_eigen33.hpp", "pcp_eigen33_selftest.hpp", "pcp_eigen33_host.hpp", "pcp_facets.hpp", "pcp_normals.hpp", "pcp_compare.hpp", "pcp_register.hpp", "pcp_coarse.hpp", "pcp_mask_edt.hpp", "pcp_ortho.hpp", "pcp_ortho_cyl.hpp", "pcp_ortho_texture.hpp", "pcp_ortho_defects.hpp", "pcp_tile_classify.hpp", "pcp_tile_box.hpp", "pcp_crack_width.hpp", "pcp_crack_fuse.hpp", "pcp_crack_length.hpp", "pcp_crack_skeleton.hpp", "pcp_crack_direction.hpp", "pcp_crack_branch.hpp", "pcp_crack_map.hpp", "pcp_image_balance.hpp", "pcp_cell_search.hpp", "pcp_colour_defer.hpp"]
 
 HIPCC_FLAGS = [
     "--offload-arch=gfx950",

@@ -701,6 +701,157 @@ def compare_register_host(xyz, normals, base_xyz, T_in=None, loop: bool = True, 
     return out
 
 
+class CoarseParams(C.Structure):
+    """pcp_coarse_params (DESIGN.md, "Coarse registration", CG1-CG9)."""
+    _fields_ = [("support_radius", C.c_float), ("normal_radius", C.c_float), ("inlier_distance", C.c_float), ("min_side", C.c_float),
+                ("side_tolerance", C.c_float), ("min_angle_deg", C.c_float), ("map_stride", C.c_int32), ("base_stride", C.c_int32),
+                ("min_neighbours", C.c_int32), ("min_offplane_permille", C.c_int32), ("ratio_q8", C.c_int32), ("mutual", C.c_int32),
+                ("hypotheses", C.c_int32), ("min_inliers", C.c_int32), ("seed", C.c_uint64)]
+
+
+CG_REPORT = ("keypoints_map", "keypoints_base", "valid_map", "valid_base", "correspondences", "scored", "refused", "winner", "runner_up",
+             "refit", "kept", "status", "winner_h")  # CG8: the first thirteen words of the report; the triple follows
+CG_FOUND, CG_TOO_FEW_INLIERS = 0, 2  # CG8: the status
+CG_ACCEPTED, CG_REPEAT, CG_SHORT_SIDE, CG_SIDE_MISMATCH, CG_THIN = range(5)  # CG4: the refusal codes
+CG_MAP, CG_BASE = 0, 1  # the sides
+CG_NO_KEY = (1 << 64) - 1
+
+
+def coarse_params(support_radius: float = 0.2, normal_radius: float = 0.1, inlier_distance: float = 0.05, min_side: float = 0.3,
+                  side_tolerance: float = 0.05, min_angle_deg: float = 15.0, map_stride: int = 4, base_stride: int = 4,
+                  min_neighbours: int = 20, min_offplane_permille: int = 100, ratio_q8: int = 230, mutual: int = 1, hypotheses: int = 4096,
+                  min_inliers: int = 10, seed: int = 1) -> CoarseParams:
+    return CoarseParams(support_radius, normal_radius, inlier_distance, min_side, side_tolerance, min_angle_deg, map_stride, base_stride,
+                        min_neighbours, min_offplane_permille, ratio_q8, int(bool(mutual)), hypotheses, min_inliers, seed)
+
+
+def _coarse_slots(prm: CoarseParams, side: int, rows: int) -> int:
+    stride = max(1, prm.base_stride if side == CG_BASE else prm.map_stride)
+    return (rows + stride - 1) // stride
+
+
+def _coarse_report(report, T, inliers) -> dict:
+    out = {k: int(report[i]) for i, k in enumerate(CG_REPORT)}
+    out.update(triple=tuple(int(v) for v in report[13:16]), T=T, inliers=inliers[:int(report[4])].copy(), report=report)
+    return out
+
+
+def _host_check(rc):
+    if rc != PCP_OK:
+        raise PcpError(rc, load().pcp_last_error(None).decode())
+
+
+def coarse_descriptors_host(side: int, xyz, normals, **params) -> dict:
+    """CG1 + CG2 of one cloud of n <= 65536 rows on the CPU by brute force with the arithmetic the kernel uses
+    (pcp_coarse_descriptors_host): dict(desc (slots, 64) uint16, total (slots,) uint32, state (slots,) uint8, slots, keypoints,
+    valid).  side picks the stride (CG_MAP / CG_BASE).  params: those of coarse_params."""
+    L = load()
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    if normals.shape[0] != xyz.shape[0]:
+        raise ValueError("coarse_descriptors_host: xyz and normals differ in their number of rows")
+    prm = coarse_params(**params)
+    slots = _coarse_slots(prm, side, min(xyz.shape[0], 65536))
+    desc, total, state = np.zeros((slots, 64), np.uint16), np.zeros(slots, np.uint32), np.zeros(slots, np.uint8)
+    counts = np.zeros(3, np.int64)
+    _host_check(L.pcp_coarse_descriptors_host(C.byref(prm), C.c_int32(side), C.c_int64(xyz.shape[0]), _ptr(xyz), _ptr(normals), _ptr(desc),
+                                              _ptr(total), _ptr(state), _ptr(counts)))
+    return dict(desc=desc, total=total, state=state, slots=int(counts[0]), keypoints=int(counts[1]), valid=int(counts[2]))
+
+
+def coarse_match_host(base_desc, map_desc, **params) -> dict:
+    """CG3 over the valid descriptors of the two sides, (K, 64) uint16 each, on the CPU (pcp_coarse_match_host): dict(pairs (C, 2)
+    int32: base ordinal, map ordinal; base_keys (K_base, 2), map_keys (K_map, 2) uint64: best, second, CG_NO_KEY = none)."""
+    L = load()
+    db = np.ascontiguousarray(base_desc, np.uint16).reshape(-1, 64)
+    dm = np.ascontiguousarray(map_desc, np.uint16).reshape(-1, 64)
+    prm = coarse_params(**params)
+    pairs, count = np.zeros((max(1, min(db.shape[0], 65536)), 2), np.int32), C.c_int64()
+    bk, mk = np.zeros((db.shape[0], 2), np.uint64), np.zeros((dm.shape[0], 2), np.uint64)
+    _host_check(L.pcp_coarse_match_host(C.byref(prm), C.c_int64(db.shape[0]), _ptr(db), C.c_int64(dm.shape[0]), _ptr(dm), _ptr(pairs),
+                                        C.byref(count), _ptr(bk), _ptr(mk)))
+    return dict(pairs=pairs[:count.value].copy(), base_keys=bk, map_keys=mk)
+
+
+def coarse_hypothesis_host(cb, cm, pivot, h: int, **params) -> dict:
+    """CG4 for hypothesis h over the correspondences' coordinates cb, cm (C, 3) float32 about `pivot`
+    (pcp_coarse_hypothesis_host): dict(code, triple, frame (15,) float64: R row-major, pivot, t)."""
+    L = load()
+    cb = np.ascontiguousarray(cb, np.float32).reshape(-1, 3)
+    cm = np.ascontiguousarray(cm, np.float32).reshape(-1, 3)
+    if cb.shape != cm.shape:
+        raise ValueError("coarse_hypothesis_host: cb and cm differ in shape")
+    pivot = np.ascontiguousarray(pivot, np.float64).reshape(3)
+    prm = coarse_params(**params)
+    code, triple, frame = C.c_int32(), np.zeros(3, np.int32), np.zeros(15, np.float64)
+    _host_check(L.pcp_coarse_hypothesis_host(C.byref(prm), C.c_int64(cb.shape[0]), _ptr(cb), _ptr(cm), _ptr(pivot), C.c_int32(h),
+                                             C.byref(code), _ptr(triple), _ptr(frame)))
+    return dict(code=code.value, triple=tuple(int(v) for v in triple), frame=frame)
+
+
+def coarse_score_host(frames, cb, cm, flags: bool = False, **params) -> dict:
+    """CG5 for frames (F, 15) float64 over the correspondences' coordinates on the CPU (pcp_coarse_score_host): dict(counts (F,)
+    int64, and with flags flags (F, C) uint8)."""
+    L = load()
+    frames = np.ascontiguousarray(frames, np.float64).reshape(-1, 15)
+    cb = np.ascontiguousarray(cb, np.float32).reshape(-1, 3)
+    cm = np.ascontiguousarray(cm, np.float32).reshape(-1, 3)
+    if cb.shape != cm.shape:
+        raise ValueError("coarse_score_host: cb and cm differ in shape")
+    prm = coarse_params(**params)
+    counts = np.zeros(frames.shape[0], np.int64)
+    fl = np.zeros((frames.shape[0], cb.shape[0]), np.uint8) if flags else None
+    _host_check(L.pcp_coarse_score_host(C.byref(prm), C.c_int64(frames.shape[0]), _ptr(frames), C.c_int64(cb.shape[0]), _ptr(cb), _ptr(cm),
+                                        _ptr(counts), _ptr(fl)))
+    return dict(counts=counts, flags=fl) if flags else dict(counts=counts)
+
+
+def coarse_refit_host(cb, cm, flags, pivot_base, pivot_map) -> np.ndarray:
+    """CG6's refit over the flagged correspondences (pcp_coarse_refit_host): the frame, (15,) float64."""
+    L = load()
+    cb = np.ascontiguousarray(cb, np.float32).reshape(-1, 3)
+    cm = np.ascontiguousarray(cm, np.float32).reshape(-1, 3)
+    flags = np.ascontiguousarray(flags, np.uint8).reshape(-1)
+    if cb.shape != cm.shape or flags.shape[0] != cb.shape[0]:
+        raise ValueError("coarse_refit_host: cb, cm and flags differ in their number of rows")
+    pb, pm = np.ascontiguousarray(pivot_base, np.float64).reshape(3), np.ascontiguousarray(pivot_map, np.float64).reshape(3)
+    frame = np.zeros(15, np.float64)
+    _host_check(L.pcp_coarse_refit_host(C.c_int64(cb.shape[0]), _ptr(cb), _ptr(cm), _ptr(flags), _ptr(pb), _ptr(pm), _ptr(frame)))
+    return frame
+
+
+def compare_register_coarse_host(xyz, normals, base_xyz, base_normals, **params) -> dict:
+    """The whole coarse registration of n_base <= 65536 base rows onto n <= 65536 map points on the CPU with the arithmetic the
+    kernels use (pcp_compare_register_coarse_host; DESIGN.md "Coarse registration"): dict with the entries CG_REPORT, triple, T
+    (4, 4) base -> map (the identity with status CG_TOO_FEW_INLIERS), inliers (C,) uint8, report (16,) int64."""
+    L = load()
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    base_xyz = np.ascontiguousarray(base_xyz, np.float32).reshape(-1, 3)
+    base_normals = np.ascontiguousarray(base_normals, np.float32).reshape(-1, 3)
+    if normals.shape[0] != xyz.shape[0] or base_normals.shape[0] != base_xyz.shape[0]:
+        raise ValueError("compare_register_coarse_host: a cloud and its normals differ in their number of rows")
+    prm = coarse_params(**params)
+    report, T, inliers = np.zeros(16, np.int64), np.zeros((4, 4), np.float64), np.zeros(1 << 18, np.uint8)
+    _host_check(L.pcp_compare_register_coarse_host(C.byref(prm), C.c_int64(xyz.shape[0]), _ptr(xyz), _ptr(normals),
+                                                   C.c_int64(base_xyz.shape[0]), _ptr(base_xyz), _ptr(base_normals), _ptr(report), _ptr(T),
+                                                   _ptr(inliers)))
+    return _coarse_report(report, T, inliers)
+
+
+def coarse_then_fine_host(xyz, normals, base_xyz, base_normals, coarse=None, fine=None) -> dict:
+    """Context.coarse_then_fine on the CPU: compare_register_coarse_host, then compare_register_host from its T with match_radius =
+    2 inlier_distance (the other parameters at their defaults), then from that T with `fine` (the defaults)."""
+    coarse = dict(coarse or {})
+    first = compare_register_coarse_host(xyz, normals, base_xyz, base_normals, **coarse)
+    if first["status"] != CG_FOUND:
+        return dict(coarse=first, wide=None, fine=None, T=first["T"], status=first["status"])
+    inlier = coarse_params(**coarse).inlier_distance
+    wide = compare_register_host(xyz, normals, base_xyz, T_in=first["T"], match_radius=2.0 * inlier)
+    last = compare_register_host(xyz, normals, base_xyz, T_in=wide["T"], **dict(fine or {}))
+    return dict(coarse=first, wide=wide, fine=last, T=last["T"], status=last["status"])
+
+
 def mask_edt_host(gray, threshold: int = 0) -> dict:
     """The mask distance maps of a (H, W) uint8 mask computed on the CPU with the arithmetic the kernels use
     (pcp_mask_edt_host: no context, no GPU; DESIGN.md "Mask distance maps").  A row stride above the width is passed on
@@ -1823,6 +1974,7 @@ class Context:
             base = base.reshape(-1, 3)
         stride = 4 * base.shape[1]
         self._check(self.lib.pcp_compare_set_base(self.h, _ptr(base), C.c_int64(base.shape[0]), C.c_int64(stride)))
+        self.n_base = base.shape[0]  # (the coarse registration's fetches are sized by it)
 
     def compare(self, radius: float = 0.03, half_length: float = 0.05, reg_error: float = 0.0, min_points: int = 5,
                 orient_mode: int = 0, orient=(0.0, 0.0, 0.0), normals=None) -> dict:
@@ -1892,6 +2044,113 @@ class Context:
         (pcp_compare_set_base_transform)."""
         T = np.ascontiguousarray(T, np.float64).reshape(16)
         self._check(self.lib.pcp_compare_set_base_transform(self.h, _ptr(T)))
+
+    # -- coarse registration (DESIGN.md, "Coarse registration") -----------------------
+    def _coarse_normals(self, who, side, normals):
+        if normals is None:
+            return None
+        normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        rows = self.n if side == CG_MAP else getattr(self, "n_base", 0)
+        if normals.shape[0] != rows:
+            raise ValueError(f"{who}: normals must hold one row per {'point of the uploaded cloud' if side == CG_MAP else 'row of the base'}")
+        return normals
+
+    def _coarse_live(self) -> dict:
+        # what the library holds after the calls made through this Context: the valid descriptors per side (CG_MAP, CG_BASE) and
+        # the correspondences ("pairs").  The fetches copy as much as the library holds, so their buffers are sized from here and
+        # never from a caller's figure; an entry is missing whenever this Context cannot vouch for it.
+        if not hasattr(self, "_cg_live"):
+            self._cg_live = {}
+        return self._cg_live
+
+    def coarse_descriptors(self, side: int, normals=None, fetch: bool = True, **params) -> dict:
+        """The keypoints and spin-image descriptors of one side on the device (pcp_coarse_descriptors and its fetch): dict(slots,
+        keypoints, valid, and with fetch desc (slots, 64) uint16, total (slots,) uint32, state (slots,) uint8, xyz (slots, 3)
+        float32).  side CG_MAP: normals (n, 3) or None for the live estimate; CG_BASE: normals (n_base, 3) or None to estimate them
+        on the device at normal_radius.  params: those of coarse_params."""
+        normals = self._coarse_normals("coarse_descriptors", side, normals)
+        prm = coarse_params(**params)
+        counts = np.zeros(3, np.int64)
+        live = self._coarse_live()
+        live.pop(side, None), live.pop("pairs", None)  # (the library drops both first; a failed call leaves neither)
+        self._check(self.lib.pcp_coarse_descriptors(self.h, C.byref(prm), C.c_int32(side), _ptr(normals), _ptr(counts)))
+        out = dict(slots=int(counts[0]), keypoints=int(counts[1]), valid=int(counts[2]))
+        live[side] = out["valid"]
+        if fetch:
+            s = out["slots"]
+            out.update(desc=np.zeros((s, 64), np.uint16), total=np.zeros(s, np.uint32), state=np.zeros(s, np.uint8), xyz=np.zeros((s, 3), np.float32))
+            self._check(self.lib.pcp_coarse_descriptors_fetch(self.h, C.c_int32(side), _ptr(out["desc"]), _ptr(out["total"]), _ptr(out["state"]),
+                                                              _ptr(out["xyz"])))
+        return out
+
+    def compare_base_normals_fetch(self) -> np.ndarray:
+        """The base's normals as the coarse registration estimated them, (n_base, 3) float32 (pcp_compare_base_normals_fetch)."""
+        out = np.zeros((getattr(self, "n_base", 0), 3), np.float32)
+        self._check(self.lib.pcp_compare_base_normals_fetch(self.h, _ptr(out)))
+        return out
+
+    def coarse_match(self, **params) -> dict:
+        """CG3 over the two sides' live descriptors (pcp_coarse_match and its fetch): dict(pairs (C, 2) int32: base ordinal, map
+        ordinal; base_keys, map_keys (K, 2) uint64: best, second per valid keypoint, CG_NO_KEY = none), K the number of valid
+        descriptors that coarse_descriptors reported for that side."""
+        prm = coarse_params(**params)
+        count = C.c_int64()
+        live = self._coarse_live()
+        live.pop("pairs", None)
+        self._check(self.lib.pcp_coarse_match(self.h, C.byref(prm), C.byref(count)))
+        if CG_BASE not in live or CG_MAP not in live:  # (descriptors this Context did not make: their number is not known here)
+            raise ValueError("coarse_match: the descriptors of both sides must come from coarse_descriptors or compare_register_coarse "
+                             "of this Context, which sizes the fetch by their counts")
+        pairs = np.zeros((count.value, 2), np.int32)
+        bk, mk = np.zeros((live[CG_BASE], 2), np.uint64), np.zeros((live[CG_MAP], 2), np.uint64)
+        self._check(self.lib.pcp_coarse_match_fetch(self.h, _ptr(pairs), _ptr(bk), _ptr(mk)))
+        live["pairs"] = count.value
+        return dict(pairs=pairs, base_keys=bk, map_keys=mk)
+
+    def coarse_score(self, frames, flags: bool = False, **params) -> dict:
+        """CG5 for a caller's frames (F, 15) float64 over the live correspondences (pcp_coarse_score): dict(counts (F,) int64, and
+        with flags flags (F, C) uint8, C the number of correspondences of the last match)."""
+        frames = np.ascontiguousarray(frames, np.float64).reshape(-1, 15)
+        prm = coarse_params(**params)
+        counts = np.zeros(frames.shape[0], np.int64)
+        fl = None
+        if flags:
+            pairs = self._coarse_live().get("pairs")
+            if pairs is None:
+                raise ValueError("coarse_score: flags need a match made by coarse_match or compare_register_coarse of this Context, "
+                                 "which sizes them by its correspondences")
+            fl = np.zeros((frames.shape[0], pairs), np.uint8)
+        self._check(self.lib.pcp_coarse_score(self.h, C.byref(prm), C.c_int64(frames.shape[0]), _ptr(frames), _ptr(counts), _ptr(fl)))
+        return dict(counts=counts, flags=fl) if flags else dict(counts=counts)
+
+    def compare_register_coarse(self, normals=None, base_normals=None, **params) -> dict:
+        """Brings the base near the uploaded cloud from an arbitrary pose (pcp_compare_register_coarse): dict with the entries
+        CG_REPORT, triple, T (4, 4) the base's transform after the call, inliers (C,) uint8, report (16,) int64.  Status
+        CG_TOO_FEW_INLIERS leaves the transform as it was."""
+        normals = self._coarse_normals("compare_register_coarse", CG_MAP, normals)
+        base_normals = self._coarse_normals("compare_register_coarse", CG_BASE, base_normals)
+        prm = coarse_params(**params)
+        report, T, inliers = np.zeros(16, np.int64), np.zeros((4, 4), np.float64), np.zeros(1 << 18, np.uint8)
+        live = self._coarse_live()
+        live.clear()  # (the call describes and matches anew)
+        self._check(self.lib.pcp_compare_register_coarse(self.h, C.byref(prm), _ptr(normals), _ptr(base_normals), _ptr(report), _ptr(T),
+                                                         _ptr(inliers)))
+        out = _coarse_report(report, T, inliers)
+        live.update({CG_MAP: out["valid_map"], CG_BASE: out["valid_base"], "pairs": out["correspondences"]})
+        return out
+
+    def coarse_then_fine(self, normals=None, base_normals=None, coarse=None, fine=None) -> dict:
+        """compare_register_coarse, then compare_register with match_radius = 2 inlier_distance (the other parameters at
+        their defaults), then compare_register with `fine` (register_params; the defaults): dict(coarse, wide, fine, T, status =
+        the last stage's that ran).  A coarse status CG_TOO_FEW_INLIERS ends it there."""
+        coarse = dict(coarse or {})
+        first = self.compare_register_coarse(normals=normals, base_normals=base_normals, **coarse)
+        if first["status"] != CG_FOUND:
+            return dict(coarse=first, wide=None, fine=None, T=first["T"], status=first["status"])
+        inlier = coarse_params(**coarse).inlier_distance
+        wide = self.compare_register(normals=normals, match_radius=2.0 * inlier)
+        last = self.compare_register(normals=normals, **dict(fine or {}))
+        return dict(coarse=first, wide=wide, fine=last, T=last["T"], status=last["status"])
 
     # -- planar facets (DESIGN.md, "Planar facets") -----------------------------------
     def facets(self, link_radius: float = 0.1, angle_deg: float = 10.0, plane_tol: float = 0.01, max_curvature: float = 0.02,

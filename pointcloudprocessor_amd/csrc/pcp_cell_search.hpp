@@ -1,6 +1,7 @@
 // pcp_cell_search.hpp -- the search the radius stages share ("The cell-wave search"): local colour smoothing
 // (pcp_colour_smooth.hip), the normals (pcp_normals.hip) and the map comparison (pcp_compare.hip) all need "every record
-// within r of every query, exact integer sums", and all three get it here.  Internal: included by those three units only.
+// within r of every query, exact integer sums", and all three get it here.  The map registration (pcp_register.hip) and the
+// coarse registration's descriptors (pcp_coarse.hip) are members too.  Internal: included by those five units only.
 //
 // The view's points are binned into the uniform grid of the radius searches (build_radius_grid, pcp_grid.hip) and copied
 // into cell order as 16-B records (x, y, z, a word of the stage's).  A work item is up to kCellQ consecutive places of ONE

@@ -256,6 +256,7 @@ int pcp_compare_set_base(pcp_context *ctx, const void *points, int64_t n_base, i
   cs.base_live = false;
   cs.result_live = false;  // (a result belongs to the base it was made with)
   cs.reg.live = false;     // (RG1: so does a registration; the transform starts again at the identity)
+  cs.coarse.release_base();  // (CG7: and the descriptors and normals of the old base's rows)
   // MC3: non-finite rows are never candidates -- they are left out here; the tag keeps the caller's row
   std::vector<float> planes;
   std::vector<uint32_t> tag;

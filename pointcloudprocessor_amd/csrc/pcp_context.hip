@@ -627,7 +627,7 @@ int pcp_create(int32_t device, pcp_context **out) {
     const hipError_t pl[] = {hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k_up_bbox)), preload_colour(), preload_mls(), preload_grid(),
                              preload_nid(), preload_hpr(), preload_colour_smooth(), preload_match(),
                              preload_jpeg(), preload_stream_colour(), preload_ascii(), preload_ascii_parse(), preload_exposure(),
-                             preload_voxel_reduce(), preload_normals(), preload_mask_edt(), preload_ortho(), preload_ortho_texture(), preload_ortho_defects(), preload_compare(), preload_register(), preload_facets(), preload_crack_width(), preload_crack_fuse(), preload_crack_length(), preload_crack_skeleton(), preload_crack_direction(), preload_crack_branch(), preload_image_balance()};
+                             preload_voxel_reduce(), preload_normals(), preload_mask_edt(), preload_ortho(), preload_ortho_texture(), preload_ortho_defects(), preload_compare(), preload_register(), preload_coarse(), preload_facets(), preload_crack_width(), preload_crack_fuse(), preload_crack_length(), preload_crack_skeleton(), preload_crack_direction(), preload_crack_branch(), preload_image_balance()};
     for (hipError_t x : pl)
       if (x != hipSuccess && e == hipSuccess) e = x;
   }

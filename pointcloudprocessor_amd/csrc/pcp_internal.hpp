@@ -245,8 +245,8 @@ struct Facets {
 };
 
 // ---- the uniform grid of the radius searches (pcp_grid.hip; read by the MLS / SOR kernels, by the cell-wave search of
-// local colour smoothing, normals and map comparison (pcp_cell_search.hpp), and by the per-lane walks of the neighbour table
-// of PCP_MATCH_RADIUS and pcp_close_pairs) ---------------------------------------------------------------------------------
+// local colour smoothing, normals, map comparison, map registration and the coarse registration's descriptors
+// (pcp_cell_search.hpp), and by the per-lane walks of the neighbour table of PCP_MATCH_RADIUS and pcp_close_pairs) ---------
 constexpr double kMaxGridCells = 536870912.0;      // 2^29: dense table of cell starts
 constexpr double kMaxSparseCells = 34359738368.0;  // 2^35: bitmap (4 GiB) + running popcounts (2 GiB)
 struct GridDesc {
@@ -276,11 +276,52 @@ struct RegisterState {
   }
 };
 
+// ---- coarse registration (pcp_coarse.hip; DESIGN.md "Coarse registration", CG7): what the staged calls leave for the next.
+// side[0]: the uploaded map (dropped with a compare result, at an upload, and by pcp_estimate_normals: its axes may have been the
+// estimate that call replaces), side[1]: the base's ORIGINAL rows (dropped by
+// pcp_compare_set_base).  A slot is row / stride; the host lists name the slots with a valid descriptor in ascending order.
+struct CoarseSide {
+  bool live = false;
+  int64_t slots = 0, keypoints = 0;
+  DevBuf<uint16_t> desc;   // 64 per slot
+  DevBuf<uint32_t> total;  // n_i per slot
+  DevBuf<uint8_t> state;   // 0: no keypoint, 1: keypoint without a valid descriptor, 2: valid
+  DevBuf<float> xyz;       // 3 per slot
+  std::vector<int32_t> valid_slot;
+  std::vector<float> valid_xyz;
+  void release() {
+    live = false;
+    slots = keypoints = 0;
+    desc.release(), total.release(), state.release(), xyz.release();
+    valid_slot.clear(), valid_xyz.clear();
+  }
+};
+struct CoarseState {
+  CoarseSide side[2];
+  bool base_normals_live = false;  // CG1: the estimate of the base's normals (4 floats per row handed in)
+  float base_normals_radius = 0.0f;
+  DevBuf<float> base_normals;
+  bool match_live = false;
+  std::vector<int32_t> pairs;      // CG3: (base ordinal, map ordinal)
+  std::vector<uint64_t> keys[2];   // best, second per valid keypoint: [0] of the map's, [1] of the base's
+  void release_map() {
+    side[0].release();
+    match_live = false;
+  }
+  void release_base() {
+    side[1].release();
+    match_live = false;
+    base_normals_live = false;
+    base_normals.release();
+  }
+};
+
 // ---- map comparison (pcp_compare.hip; DESIGN.md "Map comparison", MC8): the base survey and the last result ----------------
 // The base (its finite rows as SoA planes and their tags: the caller's row with the epoch bit) lives from pcp_compare_set_base to
 // pcp_compare_end or pcp_destroy; the result (input order of the map) from pcp_compare to the next upload.
 struct CompareState {
   RegisterState reg;
+  CoarseState coarse;
   bool base_live = false, result_live = false;
   int64_t n_base = 0, m_base = 0;  // rows handed in, finite rows kept
   float mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};  // box of the finite rows
@@ -294,6 +335,7 @@ struct CompareState {
   int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   void release_result() {
     result_live = false;
+    coarse.release_map();  // (CG7: the map's descriptors go with the cloud they were made from)
     n = 0;
     distance.release(), lod.release(), status.release(), sums.release(), direction.release();
   }
@@ -303,6 +345,7 @@ struct CompareState {
     n_base = m_base = 0;
     base_xyz.release(), base_tag.release();
     reg.release();
+    coarse.release_base();
   }
 };
 
@@ -819,6 +862,11 @@ hipError_t preload_facets();
 hipError_t preload_ortho_defects();
 hipError_t preload_compare();
 hipError_t preload_register();
+hipError_t preload_coarse();
+// the normals stage's own search and solve over any view (pcp_normals.hip): out_normal (float4) and out_count under the view's
+// remap, the caller's to clear; the map's live estimate is not touched.  *out_most: the largest neighbour count.
+int normals_of_view(pcp_context *ctx, const CloudView &cv, float radius, const char *who, float *out_normal4, int32_t *out_count,
+                    int64_t *out_most);
 // the device parts of pcp_mask_edt (one keyframe, with nearest) and pcp_frame_geometry under the caller's name: checks and
 // kernels, the results left in md_bits / md_d2 / md_nearest and gm_out / s_counter[0]; no copy, no synchronisation
 int mask_edt_device(pcp_context *ctx, const char *who, int32_t frame, int32_t threshold);

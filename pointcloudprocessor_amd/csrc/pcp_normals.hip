@@ -172,20 +172,38 @@ void normals_release(pcp_context *ctx) {
   ctx->gn_count.release();
 }
 
-// the m > 0 finite points of view cv: the search's records and work items, the moments and the solve
-static int normals_finite(pcp_context *ctx, const CloudView &cv, float radius, float t, GnScratch &s) {
-  CellSearch &cs = s.search;
-  int rc = cell_search_prepare(ctx, cv, radius, "pcp_estimate_normals", PCP_K_MISC, GnStage{cv.remap}, cv.n, s.fin.flag, cs);
+// the m > 0 finite points of view cv: the search's records and work items, the moments (nullable) and the solve into the
+// caller's arrays under the view's remap.  s_counter is cleared first (compact_flags left its total there) and holds the tally.
+static int normals_finite(pcp_context *ctx, const CloudView &cv, float radius, const char *who, DevBuf<uint8_t> &flag, CellSearch &cs,
+                          float *out_normal4, int32_t *out_count, long long *out_moments) {
+  int rc = cell_search_prepare(ctx, cv, radius, who, PCP_K_MISC, GnStage{cv.remap}, cv.n, flag, cs);
   if (rc != PCP_OK) return rc;
-  PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->s_counter.p, 0, 16, ctx->stream));  // (compact_flags left its total there)
+  PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->s_counter.p, 0, 16, ctx->stream));
   {
     LaunchTimer lt(ctx, PCP_K_MISC);
     if (cs.n_items > 0)
       hipLaunchKernelGGL(k_gn_normals, dim3(static_cast<uint32_t>(cs.n_items)), dim3(kCellQ), 0, ctx->stream, cs.rec.p, cs.items.p,
-                         cs.g, ctx->g_start.p, t, reinterpret_cast<float4 *>(ctx->gn_normal.p), ctx->gn_count.p, s.moments.p,
+                         cs.g, ctx->g_start.p, gn::threshold_of(radius), reinterpret_cast<float4 *>(out_normal4), out_count, out_moments,
                          ctx->s_counter.p);
     PCP_HIP_TRY(ctx, hipGetLastError());
   }
+  return PCP_OK;
+}
+
+// CG1 (pcp_coarse.hip): the same search, moments and solve over a view that is not the uploaded map (cv.n > 0, cv.remap set);
+// the results go to the caller's arrays and the map's live estimate stays as it is
+int normals_of_view(pcp_context *ctx, const CloudView &cv, float radius, const char *who, float *out_normal4, int32_t *out_count,
+                    int64_t *out_most) {
+  DevBuf<uint8_t> flag;
+  CellSearch cs;
+  PCP_HIP_TRY(ctx, ctx->s_counter.ensure(4));
+  int rc = normals_finite(ctx, cv, radius, who, flag, cs, out_normal4, out_count, nullptr);
+  if (rc != PCP_OK) return rc;
+  unsigned long long tally[2] = {0, 0};
+  PCP_HIP_TRY(ctx, hipMemcpyAsync(tally, ctx->s_counter.p, 16, hipMemcpyDeviceToHost, ctx->stream));
+  PCP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (also: the search's scratch is released on return)
+  drop_large_grid_bitmap(ctx);
+  if (out_most) *out_most = static_cast<int64_t>(tally[1]);
   return PCP_OK;
 }
 
@@ -203,14 +221,15 @@ static int estimate_normals(pcp_context *ctx, float radius, int64_t *out_valid, 
     PCP_HIP_TRY(ctx, s.moments.ensure(sn * gn::kMomentWords + 4));
     PCP_HIP_TRY(ctx, hipMemsetAsync(s.moments.p, 0, sn * gn::kMomentWords * 8, ctx->stream));
   }
-  const float t = gn::threshold_of(radius);
   CloudView cv;
   // GN1: the grid (which needs finite coordinates) is built over the finite points only
   int rc = finite_view(ctx, /*with_remap=*/true, /*timing_slot=*/-1, s.fin, &cv);
   if (rc != PCP_OK) return rc;
   PCP_HIP_TRY(ctx, ctx->s_counter.ensure(4));
   PCP_HIP_TRY(ctx, hipMemsetAsync(ctx->s_counter.p, 0, 16, ctx->stream));
-  if (cv.n > 0 && (rc = normals_finite(ctx, cv, radius, t, s)) != PCP_OK) return rc;
+  if (cv.n > 0 && (rc = normals_finite(ctx, cv, radius, "pcp_estimate_normals", s.fin.flag, s.search, ctx->gn_normal.p, ctx->gn_count.p,
+                                       s.moments.p)) != PCP_OK)
+    return rc;
   unsigned long long tally[2] = {0, 0};
   PCP_HIP_TRY(ctx, hipMemcpyAsync(tally, ctx->s_counter.p, 16, hipMemcpyDeviceToHost, ctx->stream));
   if (out_moments)
@@ -283,6 +302,7 @@ int pcp_estimate_normals(pcp_context *ctx, float radius, int64_t *out_valid, int
   if (!ctx->xyz.p && ctx->n > 0) return set_error(ctx, PCP_ERR_STATE, "pcp_estimate_normals: no cloud uploaded");
   PCP_HIP_TRY(ctx, hipSetDevice(ctx->device));
   ctx->facets.release();  // FA9: a new estimate ends the facets of the old one
+  ctx->compare.coarse.release_map();  // CG7: and the map's descriptors, whose axes may have been the old one's
   if (ctx->n == 0) {
     ctx->gn_live = true;
     ctx->gn_radius = radius;

@@ -491,6 +491,19 @@ class Device {
     return r;
   }
 
+  // ---- coarse registration: the base that pcp_compare_set_base left, brought near the uploaded map from an arbitrary pose
+  // under the live normals, its own normals estimated on the device (pcp_compare_register_coarse); registerBase finishes it
+  struct CoarseRegistration {
+    int64_t report[16] = {0};  // CG8: keypoints, valid descriptors, correspondences, hypotheses, inliers, status, the winner
+    double T[16] = {0};
+    int32_t status() const { return static_cast<int32_t>(report[11]); }  // 0 found, 2 too few inliers (T as it was)
+  };
+  CoarseRegistration registerBaseCoarse(const pcp_coarse_params &p) {
+    CoarseRegistration r;
+    check(pcp_compare_register_coarse(ctx_, &p, nullptr, nullptr, r.report, r.T, nullptr));
+    return r;
+  }
+
   // (reg: the base is registered onto the map first, *registration filled)
   MapComparison compareMap(const pcp_compare_params &p, const float *base_xyz, int64_t n_base, const pcp_register_params *reg = nullptr,
                            Registration *registration = nullptr) {

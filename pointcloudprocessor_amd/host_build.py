@@ -23,6 +23,7 @@ TARGETS = {
     "normals_selftest": ["normals_selftest.cpp"],  # csrc/pcp_normals.hpp compiled for the host (CPU only)
     "compare_selftest": ["compare_selftest.cpp"],  # csrc/pcp_compare.hpp compiled for the host (CPU only)
     "register_selftest": ["register_selftest.cpp"],  # csrc/pcp_register.hpp compiled for the host (CPU only)
+    "coarse_selftest": ["coarse_selftest.cpp"],  # csrc/pcp_coarse.hpp compiled for the host (CPU only)
     "ortho_selftest": ["ortho_selftest.cpp"],  # csrc/pcp_ortho.hpp compiled for the host (CPU only)
     "ortho_texture_selftest": ["ortho_texture_selftest.cpp"],  # csrc/pcp_ortho_texture.hpp compiled for the host (CPU only)
     "crack_width_selftest": ["crack_width_selftest.cpp"],  # csrc/pcp_crack_width.hpp compiled for the host (CPU only)

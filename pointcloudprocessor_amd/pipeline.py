@@ -454,6 +454,45 @@ class PointCloudColorizer:
         ctx.compare_set_base(base)
         return ctx.compare_register(normals=normals, **params)
 
+    def _coarse_base(self, who, base_xyz, normal_radius, normals):
+        import numpy as np
+
+        if self.world > 1:
+            raise ValueError(f"{who}: an index shard sees only its own points; the keypoints and partners of a base lie with every "
+                             "rank, which is not built: run it on one rank holding the whole map")
+        ctx = self.engine.ctx
+        if isinstance(base_xyz, (tuple, list)) and len(base_xyz) == 3 and np.ndim(base_xyz[0]) == 1:
+            base_xyz = np.stack([np.asarray(a, np.float32) for a in base_xyz], axis=1)
+        base = np.asarray(base_xyz, np.float32).reshape(-1, 3)
+        if normals is None and ctx.normals_radius != normal_radius:  # (None after an upload: the library dropped the estimate)
+            ctx.estimate_normals(normal_radius)
+        ctx.compare_set_base(base)
+        return ctx
+
+    def register_base_coarse(self, base_xyz, normal_radius: float = 0.1, normals=None, base_normals=None, **params) -> dict:
+        """Brings an earlier survey near the uploaded map from an arbitrary pose ("Coarse registration"): base_xyz
+        ((n_base, 3), or (x, y, z)) becomes the base of the comparison; spin-image descriptors at strided keypoints of both clouds
+        are matched, triples of correspondences vote for a rigid motion, the winner is refitted over its inliers and set as the
+        base's transform.  The map's normals are `normals` or its own, estimated at normal_radius as compare_map does; the base's
+        are base_normals or estimated on the device at the same radius.  params: those of capi.coarse_params.  dict of
+        capi.Context.compare_register_coarse; `runner_up` near `winner` tells a symmetric structure.  The result is good enough for
+        register_base's method to finish, not for compare_map: see coarse_then_fine.
+
+        An index shard sees only its own points, so world > 1 raises ValueError."""
+        ctx = self._coarse_base("register_base_coarse", base_xyz, normal_radius, normals)
+        params.setdefault("normal_radius", normal_radius)
+        return ctx.compare_register_coarse(normals=normals, base_normals=base_normals, **params)
+
+    def coarse_then_fine(self, base_xyz, normal_radius: float = 0.1, normals=None, base_normals=None, coarse=None, fine=None) -> dict:
+        """register_base_coarse, then the fine registration twice from where it ended: with match_radius = 2 inlier_distance
+        (the other parameters at their defaults), then with `fine` (capi.register_params; the defaults).  dict of
+        capi.Context.coarse_then_fine: coarse, wide, fine, T, status.  compare_map(None, ...) then compares against the registered
+        base."""
+        ctx = self._coarse_base("coarse_then_fine", base_xyz, normal_radius, normals)
+        coarse = dict(coarse or {})
+        coarse.setdefault("normal_radius", normal_radius)
+        return ctx.coarse_then_fine(normals=normals, base_normals=base_normals, coarse=coarse, fine=fine)
+
     def crack_width(self, frame: int, threshold: int = 0, plane_radius: int = 150,
                     want=("flags", "edges", "w2d2", "width", "points", "plane")) -> dict:
         """The crack width maps of one keyframe at camera resolution, made on the device ("Crack width maps"): per
